@@ -20,8 +20,17 @@ Workloads (`--workload`):
 
 Prints ONE JSON line (rank 0).  `roofline` prices the kernel sequence of one step (two HIP events on the library's
 stream) at the algorithmic bytes of the path against 8 TB/s; `roofline.traffic` is read from the PMC summary committed
-under profiles/ (null when this run's arguments differ from the profiled ones); `cpu_baseline` times the CPU oracle
-(oracle/, a port of the reference) on this host: one thread, and one thread per core over tiles of the trace.
+under profiles/ (null when this run's arguments differ from the profiled ones).
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, print the line.  `--full` adds everything
+else, outside the timed region: the parity checks (G7's SHA-256, every stream against a single-stream call, the sharded and
+files self-checks), the per-kernel and single-stream passes (`roofline.kernel_ms`, `roofline.single_stream`), the side
+workloads `int16_file` and `config2`, `h2d_inclusive`, and `cpu_baseline`, which times the CPU oracle (oracle/, a port of the
+reference) on this host: one thread, and one thread per core over tiles of the trace.  `--no-cpu`, `--no-h2d` and
+`--no-detail` leave parts of that out again.
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller (rank 0) as DIR/<name>.npy in float64, right
+after the clock stops; the inputs depend on the arguments only, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -50,6 +59,33 @@ PARAMS = dict(min_width=100, max_width=1000000, window_width=10000, prior_segmen
 HBM_PEAK = 8.0e12          # B/s, MI355X_MICROARCH.md
 PMC_FILE = os.path.join(ROOT, "profiles", "r06_pmc_traffic.json")     # written by tools/profile_round.sh from the PMC passes
 METRIC = "Msamples/sec segmented (SpeedyStatSplit, 10^8-sample trace); %HBM roofline"
+DUMP_CAP = 64 << 20        # bytes --dump-outputs may write in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array (torch or numpy, None skipped) as <path>/<name>.npy in float64 -- int32 boundaries and
+    int64 offsets are exact in it.  Past DUMP_CAP in all, an array longer than its share keeps a fixed, seeded sample of
+    its rows (sorted) and <name>_rows.npy says which.  Returns the names written."""
+    host = {}
+    for name, a in arrays.items():
+        if a is None:
+            continue
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else a
+        host[name] = np.asarray(a, dtype=np.float64)
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in host.values())
+    share = DUMP_CAP // (2 * max(1, len(host)))          # (half of the cap for the rows, the rest leaves room for their indices)
+    written = []
+    for name, a in sorted(host.items()):
+        if total > DUMP_CAP and a.nbytes > share:
+            m = max(1, share // max(1, a.nbytes // max(1, len(a))))
+            rows = np.sort(np.random.default_rng(12345).choice(len(a), size=m, replace=False))
+            a = a[rows]
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+            written.append(name + "_rows")
+        np.save(os.path.join(path, name + ".npy"), a)
+        written.append(name)
+    return written
 
 
 def cpu_model():
@@ -333,6 +369,11 @@ def main():
                          "(engine.apply_env_defaults); without it they are recorded in host.poreseg_env_seen and ignored")
     ap.add_argument("--selftest-dist", action="store_true",
                     help="run only the N > 1 plumbing of this file on CPU tensors over gloo (no GPU needed) and print one JSON line")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need, after the timed steps: parity checks, per-kernel and "
+                         "single-stream passes, the int16_file / config2 side workloads, h2d_inclusive, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0) as DIR/<name>.npy in float64, at most 64 MB")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started by itself: become the launcher of the N ranks (before torch or the GPU are touched)
@@ -400,6 +441,7 @@ def main():
     check = {}                                           # parity evidence gathered outside the timed region
     final_gather = lambda: None                          # noqa: E731
     trace = None
+    last_out = {}                                        # stream t -> what its latest step returned to the caller (--dump-outputs)
     seed = 2024 + (rank if wl in ("trace", "file") else 0)      # rank 0's trace is golden case G7
 
     # ------------------------------------------------------------------------------------------------ workloads
@@ -425,6 +467,7 @@ def main():
                                                      out=acc[k] if k is not None and acc is not None else outs[t])
                 if k is not None and acc is not None:
                     acc_counts[k] = b.numel()
+                last_out[t] = dict(boundaries=b, boundary_offsets=o, segment_stats=st)
                 return b
         else:
             ends, lv, _ = synth.file_trace_table(n, seed)
@@ -437,6 +480,7 @@ def main():
                 if k is not None and acc is not None:
                     acc[k, :b.numel()].copy_(b)
                     acc_counts[k] = b.numel()
+                last_out[t] = dict(event_starts=st_, event_lengths=ln_, boundaries=b, boundary_offsets=o, segment_stats=stt)
                 return b
         samples_per_step = n * world
         bytes_per_sample = 4 if wl == "trace" else 2
@@ -580,9 +624,23 @@ def main():
     gc.unfreeze()
     result = results[-1]
     seq_ms = sum(seq_acc) / steps
+    if args.dump_outputs and rank == 0:
+        # the last timed step ran on stream (steps - 1) % T; the workloads without a pool return everything from step()
+        if wl in ("trace", "file"):
+            dumped = last_out[(steps - 1) % T]
+        elif wl == "sharded-trace":
+            dumped = {"boundaries": result}
+        else:
+            dumped = {"events_per_file": np.array([len(r[0]) for r in result], dtype=np.int64),
+                      "bounds_per_file": np.array([int(r[2].numel()) for r in result], dtype=np.int64),
+                      "event_starts": np.concatenate([np.asarray(r[0]) for r in result]) if result else None,
+                      "event_lengths": np.concatenate([np.asarray(r[1]) for r in result]) if result else None,
+                      "boundaries": torch.cat([r[2] for r in result]) if result else None,
+                      "boundary_offsets": np.concatenate([np.asarray(r[3]) for r in result]) if result else None}
+        stage("outputs of the last timed step -> %s: %s" % (args.dump_outputs, ", ".join(dump_outputs(args.dump_outputs, dumped))))
     # one batch at a time on one stream (the latency of a single call), outside the timed region
     single = None
-    if T > 1:
+    if T > 1 and args.full:
         torch.cuda.synchronize()
         k1 = min(steps, 30)
         s1 = 0.0
@@ -595,7 +653,7 @@ def main():
     tm = ctx.timings()                                   # work counters of the last step on the first context
     # Per-kernel breakdown: a separate, untimed pass with an event between the phases (each such event keeps the next
     # kernel from starting back to back, ~6 us of idle GPU, so the timed region above runs without them).
-    detail = wl in ("trace", "file", "sharded-trace") and not args.no_detail
+    detail = args.full and wl in ("trace", "file", "sharded-trace") and not args.no_detail
     ctx.set_option("timing", 2)
     for _ in range(min(steps, 20) if detail else 0):
         step()
@@ -612,10 +670,10 @@ def main():
     ms_per_step = dt / steps * 1e3
     value = samples_per_step / (dt / steps) / 1e6
 
-    # ------------------------------------------------------------------------------------------------ parity evidence
+    # ------------------------------------------------------------------------------------------------ parity evidence (--full)
     if wl in ("trace", "file"):
         bounds = result
-        if wl == "trace" and rank == 0:
+        if wl == "trace" and rank == 0 and args.full:
             import hashlib
             # (a) the results the T streams produced in flight == the same traces segmented one call at a time on context 0
             last = {}
@@ -643,13 +701,14 @@ def main():
         if use_dist:
             n_bounds = jg.last_counts()                               # the last batch's boundaries, all ranks
             # (the last batch ran on stream (steps - 1) % T, i.e. on that stream's trace)
-            assert torch.equal(jg.row(rank, steps - 1), results[-1][:n_bounds[rank]]), "boundary gather returned something else for this rank"
+            assert not args.full or torch.equal(jg.row(rank, steps - 1), results[-1][:n_bounds[rank]]), \
+                "boundary gather returned something else for this rank"
         else:
             n_bounds = [int(bounds.numel())]
     elif wl == "sharded-trace":
         got = np.asarray(result.cpu().numpy() if hasattr(result, "cpu") else result, dtype=np.int64)
         n_bounds = [int(got.size)]
-        if rank == 0:
+        if rank == 0 and args.full:
             if world == 1:
                 # the same trace as 8 stand-alone pieces with halo on this GPU, joined at common spine anchors
                 pr = pdist.shard_ranges(n, 8, halo)
@@ -669,7 +728,7 @@ def main():
             assert all(v for v in check.values() if isinstance(v, bool)), check
     else:
         n_bounds = [int(sum(r[2].numel() for r in result))]
-        if rank == 0 and mine:
+        if rank == 0 and mine and args.full:
             # every distinct table the step segmented == the same file segmented on its own (fresh upload, one call, outside
             # the timed region); the first events of the first table also against the CPU restatement of the reference
             from pypore_amd import pipeline as _pl
@@ -739,7 +798,7 @@ def main():
             "scaling": scaling, "vs_baseline": None,
             "dtype": "int32/f64 (exact integer block sums of fp32 or int16 samples; decisions in fp64)", "data": "synthetic",
             "config": {"workload": workload_text, "name": wl, "samples_per_step": samples_per_step, "boundaries": n_bounds,
-                       "segment_stats_in_step": bool(args.stats), "checks": check, "streams": T,
+                       "segment_stats_in_step": bool(args.stats), "checks": check, "streams": T, "full": bool(args.full),
                        # what torch.distributed (RCCL on the GPU box) itself reports, and every rank's own clock
                        "ranks_seen": dist.get_world_size() if use_dist else 1,
                        # every rank's boundary count of its last batch (the gathered counts when N > 1)
@@ -814,7 +873,7 @@ def main():
         # BASELINE config 3 beside the fp32 headline: one 1e8-sample .abf-shaped int16 trace per stream,
         # lambda_event_parser(threshold=90) then per-event SpeedyStatSplit, end to end on the GPU, T batches in flight like
         # the headline; priced at ITS algorithmic bytes, 2 B per sample.  Outside the timed region of `value`.
-        if wl == "trace" and not args.no_detail and world == 1 and n == 100_000_000 and not args.dwell:
+        if args.full and wl == "trace" and not args.no_detail and world == 1 and n == 100_000_000 and not args.dwell:
             from pypore_amd import pipeline
             ftraces = []
             for t_ in range(T):
@@ -859,7 +918,7 @@ def main():
                              "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": round(2 * n / tf / HBM_PEAK, 5)}}
             del ftraces
         # ---- BASELINE config 2: 1 024 events x 50 000 samples in ONE call -----------------------
-        if wl == "trace" and not args.no_detail and world == 1 and n == 100_000_000 and not args.dwell:
+        if args.full and wl == "trace" and not args.no_detail and world == 1 and n == 100_000_000 and not args.dwell:
             n_ev2, ln2 = 1024, 50000
             e2, l2 = [], []
             for e_ in range(n_ev2):
@@ -914,7 +973,7 @@ def main():
                               "events_with_exactly_their_four_steps_min": int(min(np.sum(np.diff(o_) == 4) for o_ in o2s))}}
             del t2_, t2s
         # ---- PCIe-inclusive rate (report H2D-inclusive separately; never `value`) ------------------
-        if wl == "trace" and not args.no_h2d and world == 1:
+        if args.full and wl == "trace" and not args.no_h2d and world == 1:
             P = 8
             pr = pdist.shard_ranges(n, P, 8 * W)
             plen = max(hi_ - lo_ for lo_, hi_ in pr)
@@ -977,7 +1036,7 @@ def main():
                                              "boundaries_equal_resident_run": bool(np.array_equal(hb16, bounds.cpu().numpy()))}
             del hbuf, dbuf
         # ---- CPU baseline: the oracle on this host, one thread and one thread per core ------------------------
-        if not args.no_cpu and wl in ("trace", "file"):
+        if args.full and not args.no_cpu and wl in ("trace", "file"):
             import oracle
             m = min(n, args.cpu_samples)
             x = trace[:m].cpu().numpy().astype(np.float64)

@@ -87,9 +87,70 @@ def test_self_launch_command_line(monkeypatch):
     assert "os.exec" not in src and "execv" not in src.replace("no exec", "")
 
 
+def load_bench():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_full_and_dump_outputs_are_options():
+    out = subprocess.run([sys.executable, BENCH, "--help"], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0
+    assert "--full" in out.stdout and "--dump-outputs" in out.stdout
+
+
+def test_dump_outputs_writes_float64_and_samples_past_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs' writer: int32 / int64 arrays arrive exactly as float64, None is skipped; past the cap an array keeps
+    a seeded sample of its rows, the same one every time, and says which rows"""
+    import numpy as np
+    bench = load_bench()
+    b = np.array([3, 17, 2 ** 31 - 1], dtype=np.int32)
+    o = np.array([0, 3], dtype=np.int64)
+    names = bench.dump_outputs(str(tmp_path / "a"), {"boundaries": b, "boundary_offsets": o, "segment_stats": None})
+    assert sorted(names) == ["boundaries", "boundary_offsets"]
+    got = np.load(str(tmp_path / "a" / "boundaries.npy"))
+    assert got.dtype == np.float64 and np.array_equal(got.astype(np.int64), b)
+    assert np.array_equal(np.load(str(tmp_path / "a" / "boundary_offsets.npy")), o)
+    monkeypatch.setattr(bench, "DUMP_CAP", 4096)
+    big = np.arange(10000, dtype=np.int64) * 7
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"boundaries": big})
+    rows = np.load(str(tmp_path / "b" / "boundaries_rows.npy")).astype(np.int64)
+    kept = np.load(str(tmp_path / "b" / "boundaries.npy"))
+    assert 0 < kept.nbytes + rows.nbytes <= 4096 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(kept, big[rows].astype(np.float64))
+    assert np.array_equal(np.load(str(tmp_path / "c" / "boundaries_rows.npy")).astype(np.int64), rows)
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """A plain run times the steps and prints the line, nothing else; its one step runs on stream 0, i.e. on golden case G7,
+    and what --dump-outputs writes is the reference's boundaries (SHA-256 of tests/golden/manifest.json)."""
+    import hashlib
+    import numpy as np
+    out = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "1", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 1 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["config"]["full"] is False
+    for key in ("cpu_baseline", "h2d_inclusive", "int16_file", "config2"):
+        assert key not in d, key
+    assert d["config"]["checks"] == {} and d["roofline"]["single_stream"] is None
+    b = np.load(str(tmp_path / "boundaries.npy"))
+    assert b.dtype == np.float64 and b.size == d["config"]["boundaries"][0]
+    assert np.array_equal(np.load(str(tmp_path / "boundary_offsets.npy")), [0, b.size])
+    with open(os.path.join(ROOT, "tests", "golden", "manifest.json")) as f:
+        g7 = [c for c in json.load(f)["cases"] if c["name"] == "G7_1e8"][0]
+    assert b.size == g7["n_bounds"] and hashlib.sha256(b.astype(np.int32).tobytes()).hexdigest() == g7["sha256"]
+
+
 @pytest.mark.gpu
 def test_short_run_prints_the_contract_line():
-    out = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "4", "--warmup", "2", "--no-cpu", "--no-h2d"],
+    out = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "4", "--warmup", "2", "--full", "--no-cpu", "--no-h2d"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -109,4 +170,5 @@ def test_short_run_prints_the_contract_line():
     assert r["frac"] == pytest.approx(r["achieved"] / r["peak"], rel=1e-3)
     assert d["value"] == pytest.approx(1e8 / (d["ms_per_step"] * 1e-3) / 1e6, rel=1e-3)
     assert d["config"]["checks"]["g7_sha256_equal"] is True and d["config"]["checks"]["all_streams_equal_single_stream"] is True
+    assert d["config"]["full"] is True and d["roofline"]["single_stream"] is not None
     assert d["host"]["gpu_max_hw_queues"] == os.environ.get("GPU_MAX_HW_QUEUES", "16")

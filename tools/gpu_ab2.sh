@@ -7,7 +7,7 @@ for rep in 1 2; do
     [ "$lib" = "''" ] && lib=""
     export PORESEG_LIB=$PWD/pypore_amd/libporeseg$lib.so
     for e in $2; do
-      for s in 1 4; do echo -n "[$lib $e] streams $s: "; env ${e//,/ } python bench.py --no-cpu --no-h2d --steps 40 --warmup 8 --streams $s 2>/dev/null | python -c "$P"; done
+      for s in 1 4; do echo -n "[$lib $e] streams $s: "; env ${e//,/ } python bench.py --full --no-cpu --no-h2d --steps 40 --warmup 8 --streams $s 2>/dev/null | python -c "$P"; done
     done
   done
 done

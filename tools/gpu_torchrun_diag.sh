@@ -4,7 +4,7 @@
 cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out
 export MASTER_ADDR=127.0.0.1
 P='import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=d["roofline"]["single_stream"]; print(d["ms_per_step"], "seq", d["roofline"]["sequence_ms"], "single", s["ms_per_step"], s["sequence_ms"], d.get("host"))'
-A="--no-cpu --no-h2d --no-detail --steps 100 --warmup 20"
+A="--full --no-cpu --no-h2d --no-detail --steps 100 --warmup 20"
 for rep in 1 2; do
 echo -n "plain: "; python bench.py $A 2>/dev/null | python -c "$P"
 echo -n "plain OMP=1: "; OMP_NUM_THREADS=1 python bench.py $A 2>/dev/null | python -c "$P"
