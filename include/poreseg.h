@@ -138,7 +138,9 @@ int ps_set_tiling(ps_ctx *ctx, int64_t tile_len, int64_t halo);
  * "debug" 1: the library reports on stderr which occupancy it found and which seams gave up (prints only);
  * "slots_pct" 1..100 (default 100) share of the resident wave slots the single-wave scan kernels are launched on;
  * "tree_jobs_per_wave" (default 4) subtree kernel: jobs / this many of its slots work, between half and all of them;
- * "noise_k_ppm" (default 100 000 = 0.1): near-tie accounting of the 64-bit digest, margin factor in millionths.
+ * "noise_k_ppm" (default 100 000 = 0.1): near-tie accounting of the 64-bit digest, margin factor in millionths;
+ * "near_tie_log" n (default 65 536, 0 .. 2^30): records of the near-tie log that ps_get_near_ties reads (16 bytes each, device
+ * memory allocated with the first segment call that logs), 0 = no log.
  * Unknown names return PS_ERR_ARG.
  * THE LIBRARY READS NO ENVIRONMENT VARIABLE (round 6): what a call returns depends on its arguments and on these two
  * setters only.  The experiments' switches that return stale or partial results ("dbg_phase", "dbg_k0_nogrp",
@@ -342,6 +344,28 @@ int ps_get_timings(const ps_ctx *ctx, double *ms, int32_t n_ms, int64_t *counter
  * call before it returns): a caller that checks one of them after each call -- counters[11], the near ties -- reads it
  * there instead of making a second call. */
 const int64_t *ps_counters(const ps_ctx *ctx);
+
+/* Where the near ties of counters[11] lie: the windows of the context's most recent ps_segment_batch(_ex), ps_segment_events,
+ * ps_detect_segment_trace (its detected events) or ps_segment_exact_f64 call that were decided by a margin inside the
+ * reference's own rounding noise, one record per distinct (event, window, split), sorted by (event, window_start).
+ * Coordinates are samples of the event: the window [window_start, window_end), split = the boundary the device placed in it
+ * (an index of the event), or -1 when it placed none.  For such a window the reference may differ, usually by one sample.
+ * The records are a SUPERSET of the decisions behind the returned boundaries: speculative scans (tile spines, look-ahead
+ * helpers, seam bridges) are logged as well, just as counters[11] counts them -- a window of the final recursion starts at
+ * 0 or a returned boundary plus a multiple of window_width / 2 and ends at min(that + window_width, 0 / a boundary / the
+ * event's end), and its split, if any, is a returned boundary (pypore_amd.engine.consistent_sites filters on that).
+ * *n_out >= 0: the number of records (PS_ERR_CAPACITY when it exceeds cap: nothing is written, call again with room);
+ * *n_out = PS_NT_NOT_COUNTED: no margins were kept -- the call ran on the LDS-window kernels (counters[11] = -1: min_width < 8,
+ * option "scan_bs" 0 / "stitch_host" 1, counters[7] = 2, ps_segment_exact_f64), option "near_tie_log" is 0, the call failed,
+ * or the library is a PS_STAMP build; *n_out = PS_NT_INCOMPLETE: more near ties than the log holds (option "near_tie_log",
+ * default 65 536 records = 1 MB of device memory per context; the count goes on, the records stop).  Either way the caller
+ * treats every event of the call as flagged.  Synchronises the context's stream when there are records to fetch. */
+#define PS_NT_NOT_COUNTED    -1
+#define PS_NT_INCOMPLETE     -2
+typedef struct ps_near_tie {
+    int32_t event, window_start, window_end, split;   /* event-relative; split -1: none */
+} ps_near_tie;
+int ps_get_near_ties(const ps_ctx *ctx, ps_near_tie *out, int32_t cap, int64_t *n_out);
 
 /* Synthetic step-signal generator (bit-identical to pypore_amd/synth.py):
  * sample i = level_counts[segment containing i] + noise(seed, i), written as fp32 pA

@@ -49,6 +49,9 @@ class MetaEvent(MetaSegment):
 class Event(Segment):
     """A blockade event: its current, and after parse() its segments."""
     json_fields = EVENT_FIELDS
+    # after a parse on the device: the near-tie sites of its segmentation, [(window_start, window_end, split)] in samples of
+    # the event (engine.consistent_sites); None: not counted, or not segmented on the device.  Not persisted.
+    near_ties = None
 
     def __init__(self, current, segments=(), **kwargs):
         segments = list(segments)
@@ -119,7 +122,12 @@ class Event(Segment):
         else:
             # (our own segmenter takes the counts behind a current that has not been written out; any other parser gets
             #  the float64 array)
-            self.segments = parser.parse(raw_current(self) if isinstance(parser, SpeedyStatSplit) else self.current)
+            if isinstance(parser, SpeedyStatSplit):
+                nt = []
+                self.segments = parser.parse_batch([raw_current(self)], near_ties_out=nt)[0]
+                self.near_ties = nt[0]
+            else:
+                self.segments = parser.parse(self.current)
         rate = float(self.file.second)
         for segment in self.segments:
             segment.event = self
@@ -151,22 +159,25 @@ class Event(Segment):
         mode = parser.off_grid if isinstance(parser, SpeedyStatSplit) else None
         if mode == "exact":
             # the reference's own arithmetic on the float64 current itself (ps_segment_exact_f64): nothing is rounded
+            self.near_ties = None
             return self._adopt_filtered(parser.parse_exact(np.asarray(self.current, dtype=np.float64)))
         rounded, _, centre = self._on_fine_grid()
-        if mode == "exact_on_near_tie":
-            import warnings
-            from . import engine
-            with warnings.catch_warnings(record=True) as seen:
-                warnings.simplefilter("always", engine.NearTieWarning)
-                segs = parser.parse_batch([rounded], [centre])[0]
-            # (near_ties() < 0: the call ran where near ties are not counted -- option scan_bs 0, min_width < 8)
-            if any(issubclass(w.category, engine.NearTieWarning) for w in seen) or engine.context(parser._grid["device"]).near_ties() < 0:
-                segs = parser.parse_exact(np.asarray(self.current, dtype=np.float64))
-            return self._adopt_filtered(segs)
         if isinstance(parser, SpeedyStatSplit):
             # (the level goes along: the device judges near ties against the noise of the reference's cumsums, which run on
             #  the uncentred current -- include/poreseg.h, ps_sample_format)
-            return self._adopt_filtered(parser.parse_batch([rounded], [centre])[0])
+            import warnings
+            from . import engine
+            with warnings.catch_warnings():
+                if mode == "exact_on_near_tie":
+                    warnings.simplefilter("ignore", engine.NearTieWarning)      # (acted upon right here, from the sites)
+                nt, fl = [], []
+                segs = parser.parse_batch([rounded], [centre], near_ties_out=nt, flagged_out=fl)[0]
+            self.near_ties = nt[0]
+            # exact_on_near_tie: the exact route when the call logged a near tie for it (speculative scans included), or when
+            # the sites were not counted (LDS-window kernels: option scan_bs 0, min_width < 8; the log off or overflowed)
+            if mode == "exact_on_near_tie" and fl[0]:
+                segs = parser.parse_exact(np.asarray(self.current, dtype=np.float64))
+            return self._adopt_filtered(segs)
         return self._adopt_filtered(parser.parse(rounded))
 
     # ---- persistence ----------------------------------------------------------------------------------------
@@ -272,7 +283,14 @@ class File(Segment):
         if filter_params is not None and hasattr(parser, "parse_filtered_batch") and all(type(ev) is Event for ev in self.events):
             # filter -> grid -> segments without leaving the device: only the filtered float64 currents come back
             order, cutoff = (tuple(filter_params) + (2000.,))[:2] if len(tuple(filter_params)) else (1, 2000.)
-            done = parser.parse_filtered_batch([raw_current(ev) for ev in self.events], order, cutoff, rate)
+            sites = []
+            if isinstance(parser, SpeedyStatSplit):
+                done = parser.parse_filtered_batch([raw_current(ev) for ev in self.events], order, cutoff, rate, near_ties_out=sites)
+            else:
+                done = parser.parse_filtered_batch([raw_current(ev) for ev in self.events], order, cutoff, rate)
+            for k, ev in enumerate(self.events):
+                if sites:
+                    ev.near_ties = sites[k]
             for ev, (cur, segs) in zip(self.events, done):
                 ev.current = cur
                 ev.filtered, ev.filter_order, ev.filter_cutoff = True, order, cutoff
@@ -289,21 +307,43 @@ class File(Segment):
         results = [None] * len(self.events)
         plain_idx = [i for i, ev in enumerate(self.events) if not ev.__dict__.get("filtered")]
         currents = [raw_current(self.events[i]) if batched else self.events[i].current for i in plain_idx]
-        for i, segs in zip(plain_idx, parser.parse_batch(currents) if batched else [parser.parse(c) for c in currents]):
+        ours = isinstance(parser, SpeedyStatSplit)
+        nt = []
+        for i, segs in zip(plain_idx, parser.parse_batch(currents, near_ties_out=nt) if ours else
+                           parser.parse_batch(currents) if batched else [parser.parse(c) for c in currents]):
             results[i] = segs
+        for i, sites in zip(plain_idx, nt):
+            self.events[i].near_ties = sites
         by_step = {}
-        exact_modes = isinstance(parser, SpeedyStatSplit) and parser.off_grid in ("exact", "exact_on_near_tie")
+        mode = parser.off_grid if ours else None
         for i, ev in enumerate(self.events):
             if ev.__dict__.get("filtered"):
-                if exact_modes:                          # (the event decides for itself: Event._parse_filtered)
+                if mode == "exact":                      # (the reference's arithmetic on every event: Event._parse_filtered)
                     results[i] = ev._parse_filtered(parser)
                     continue
                 rounded, step, centre = ev._on_fine_grid()
                 by_step.setdefault(step, []).append((i, rounded, centre))
         for group in by_step.values():
             currents = [r for _, r, _ in group]
-            if batched and isinstance(parser, SpeedyStatSplit):
-                found = parser.parse_batch(currents, [c for _, _, c in group])       # (levels: this package's extension)
+            if ours:
+                import warnings
+                from . import engine
+                nt, fl = [], []
+                with warnings.catch_warnings():
+                    if mode == "exact_on_near_tie":
+                        warnings.simplefilter("ignore", engine.NearTieWarning)      # (acted upon right here, per event)
+                    found = parser.parse_batch(currents, [c for _, _, c in group], near_ties_out=nt, flagged_out=fl)
+                for (i, _, _), sites in zip(group, nt):
+                    self.events[i].near_ties = sites
+                if mode == "exact_on_near_tie":
+                    # only the events whose call logged a near tie for them (all of them when the sites were not counted) take
+                    # the exact route, in one ps_segment_exact_f64 call for the group
+                    redo = [k for k, f in enumerate(fl) if f]
+                    if redo:
+                        exact = parser._fast().parse_exact_batch(
+                            [np.asarray(self.events[group[k][0]].current, dtype=np.float64) for k in redo])
+                        for k, segs in zip(redo, exact):
+                            found[k] = segs
             elif batched:
                 found = parser.parse_batch(currents)     # a user's parser with the one-argument parse_batch of earlier rounds
             else:

@@ -18,7 +18,9 @@ PS_ALIGN_OK, PS_ALIGN_VALUE_ERROR, PS_ALIGN_INDEX_ERROR, PS_ALIGN_ZERO_DIVISION,
 EXPORTS = ["ps_version", "ps_device_count", "ps_create", "ps_destroy", "ps_last_error", "ps_set_tiling", "ps_set_option",
            "ps_synchronize", "ps_min_gain", "ps_segment_batch", "ps_segment_batch_ex", "ps_segment_events", "ps_segment_exact_f64", "ps_detect_events", "ps_detect_segment_trace", "ps_bounds_capacity",
            "ps_best_single_split", "ps_score_window", "ps_get_timings", "ps_synth_trace", "ps_filter_bessel",
-           "ps_requantise", "ps_filter_requantise_batch", "ps_align_batch", "ps_audit_bounds", "ps_counters"]
+           "ps_requantise", "ps_filter_requantise_batch", "ps_align_batch", "ps_audit_bounds", "ps_counters",
+           "ps_get_near_ties"]
+PS_NT_NOT_COUNTED, PS_NT_INCOMPLETE = -1, -2     # ps_get_near_ties: *n_out when the sites are not counted / the log overflowed
 
 
 class SplitParams(ctypes.Structure):
@@ -30,6 +32,12 @@ class SplitParams(ctypes.Structure):
 
 class SampleFormat(ctypes.Structure):
     _fields_ = [("dtype", ctypes.c_int32), ("offset_counts", ctypes.c_int32), ("quantum", ctypes.c_double)]
+
+
+class NearTie(ctypes.Structure):
+    """ps_near_tie: one near-tie window of the last segment call, in samples of its event (split -1: none)."""
+    _fields_ = [("event", ctypes.c_int32), ("window_start", ctypes.c_int32), ("window_end", ctypes.c_int32),
+                ("split", ctypes.c_int32)]
 
 
 _lib = None
@@ -81,6 +89,7 @@ def lib():
     L.ps_align_batch.argtypes = [vp, P(dbl), P(dbl), P(dbl), i32, dbl, dbl, vp, vp, vp, P(i64), i32, vp, vp, vp]
     L.ps_counters.argtypes = [vp]
     L.ps_counters.restype = P(i64)
+    L.ps_get_near_ties.argtypes = [vp, P(NearTie), i32, P(i64)]
     L.ps_audit_bounds.argtypes = [vp, vp, P(SampleFormat), i64, P(SplitParams), P(i32), i32, P(dbl)]
     _lib = L
     return L

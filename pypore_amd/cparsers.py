@@ -57,14 +57,19 @@ class FastStatSplit(object):
         duration in samples), exactly like the reference."""
         return self.parse_batch([current])[0]
 
-    def parse_batch(self, currents, levels=None):
+    def parse_batch(self, currents, levels=None, near_ties_out=None, flagged_out=None):
         """One device call for many independent events (one reference parse() per event).  Events that reach the
         device in different representations (float32 pA / int16 counts, or int16 on different scales) go in one call
         per representation.  levels: per event, the level in pA that was subtracted from it upstream (a filtered event
-        that Event.parse centred and rounded): passed on as offset_counts, see include/poreseg.h."""
+        that Event.parse centred and rounded): passed on as offset_counts, see include/poreseg.h.
+        near_ties_out / flagged_out (lists, optional): per event its near-tie sites in the final recursion,
+        [(window_start, window_end, split)] in samples, or None when they were not counted (Event.near_ties); and whether
+        the exact route should redo it -- any record of its call's log for it, speculative scans included, or not counted."""
         ctx = engine.context(self.device)
         import torch
         out = [None] * len(currents)
+        near_ties = [None] * len(currents)
+        flagged = [True] * len(currents)
 
         def upload(idx, full_detect):
             parts = [engine.to_device(currents[i], self.quantum, self.offset, self.device, full_detect) for i in idx]
@@ -154,6 +159,13 @@ class FastStatSplit(object):
                 return
             b = bounds.cpu().numpy()
             st = stats.cpu().numpy()
+            if near_ties_out is not None or flagged_out is not None:
+                raw = ctx.near_tie_sites()                  # (of this call: one per representation)
+                sites = engine.consistent_sites(raw, b, boff, lens, self._params.window_width)
+                for e, i in enumerate(idx):
+                    if sites is not None:
+                        near_ties[i] = [(int(w0), int(w1), int(sp)) for _, w0, w1, sp in sites[sites["event"] == e].tolist()]
+                        flagged[i] = bool(np.any(raw["event"] == e))
             for e, i in enumerate(idx):
                 cur, n = currents[i], int(lens[e])
                 rows = st[boff[e] + e: boff[e + 1] + e + 1]
@@ -170,6 +182,10 @@ class FastStatSplit(object):
             groups.setdefault(("counts", g[1]) if g is not None else ("values",), []).append(i)
         for idx in groups.values():
             run(idx)
+        if near_ties_out is not None:
+            near_ties_out[:] = near_ties
+        if flagged_out is not None:
+            flagged_out[:] = flagged
         return out
 
     def parse_exact_batch(self, currents):
@@ -208,7 +224,7 @@ class FastStatSplit(object):
             out.append([Segment(current=src[a:z_], start=a, duration=z_ - a, end=z_) for a, z_ in zip(edges, edges[1:])])
         return out
 
-    def parse_filtered_batch(self, currents, order=1, cutoff=2000., sampling_freq=1.e5):
+    def parse_filtered_batch(self, currents, order=1, cutoff=2000., sampling_freq=1.e5, near_ties_out=None):
         """Event.filter + Event.parse for many events without leaving the device in between (the inner loop of
         Experiment.parse, DataTypes.py:975-984): every current is filtered (ps_filter_bessel), re-quantised on the
         device (ps_requantise) and the events that share a grid step are segmented in one ps_segment_batch.  Returns
@@ -282,6 +298,9 @@ class FastStatSplit(object):
         from .grid import Deferred
         filtered = [Deferred.from_tensor(y, off) for y, off in filtered]
         out = [None] * len(currents)
+        # near_ties_out (a list, optional): per input the near-tie sites of its segmentation, [(window_start, window_end, split)]
+        # in samples of the event, or None (not counted, the log overflowed, or off_grid="exact") -- Event.near_ties
+        near_ties = [None] * len(currents)
 
         def exact_bounds(idx, lens):
             """the reference's own arithmetic on the filtered currents THE USER SEES (the file's offset put back, as
@@ -307,12 +326,29 @@ class FastStatSplit(object):
                     bounds, boff, _ = ctx.segment_batch(samples, ev_off, self._params, step, want_stats=False,
                                                         offset_counts=_dc_counts(max((levels[i] for i in idx), key=abs), step))
                 b = bounds.cpu().numpy()
-                if self.off_grid == "exact_on_near_tie" and ctx.near_ties():
-                    b, boff = exact_bounds(idx, lens)          # (the count is per call: the whole group is redone)
+            per_event = [b[boff[e]:boff[e + 1]] for e in range(len(idx))]
+            if self.off_grid != "exact":
+                # the device's near-tie sites of this call (None: not counted / incomplete); Event.near_ties gets those of the
+                # final recursion
+                raw = ctx.near_tie_sites()
+                sites = engine.consistent_sites(raw, b, boff, lens, self._params.window_width)
+                for e, i in enumerate(idx):
+                    near_ties[i] = None if sites is None else \
+                        [(int(w0), int(w1), int(sp)) for _, w0, w1, sp in sites[sites["event"] == e].tolist()]
+                if self.off_grid == "exact_on_near_tie":
+                    # the events with any record -- speculative scans included, the superset that counters[11] counts -- and all
+                    # of them when the sites are not counted
+                    redo = engine.events_to_redo(raw, len(idx))
+                    if redo:
+                        rb, rboff = exact_bounds([idx[e] for e in redo], lens[redo])
+                        for k, e in enumerate(redo):
+                            per_event[e] = rb[rboff[k]:rboff[k + 1]]
             for e, i in enumerate(idx):
                 cur = filtered[i]
-                edges = np.concatenate(([0], b[boff[e]:boff[e + 1]], [int(lens[e])])).tolist()
+                edges = np.concatenate(([0], per_event[e], [int(lens[e])])).tolist()
                 out[i] = (cur, segments_from_edges(cur, edges))
+        if near_ties_out is not None:
+            near_ties_out[:] = near_ties
         return out
 
     # ---- cparsers.pyx:120-155 -------------------------------------------------------------------

@@ -22,6 +22,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <vector>
 
 #include "poreseg.h"
@@ -157,6 +158,13 @@ struct ps_ctx {
     DevBuf ev_info_tr;        // single-pass file route (ps_detect_segment_trace): (centre, phase, first block) of the events cut out of a trace-aligned digest
     DevBuf blk_cls, cls_mm;   // ... K0's verdict per block against the detector's threshold (2 bits), min / max per 128 blocks
     DevBuf pre_c;             // exact route (ps_segment_exact_f64): c and c2 of the call's samples, 16 B per sample
+    // Near-tie log of the segment calls (DevCfg::nt_log, ps_get_near_ties): nt_cap records (option near_tie_log, 0: off), allocated
+    // with the first call that logs.  nt_seen: records the last segment call counted (-1: not counted), nt_call_cap the capacity
+    // it ran with; nt_ev_start / nt_ev_len: its events, kept only when it logged any (the records are mapped to them on request).
+    DevBuf nt_log;
+    int64_t nt_cap = 65536, nt_hdr_cap = -1;   // (nt_hdr_cap: the capacity the header on the device names; -1: none written)
+    int64_t nt_seen = -1, nt_call_cap = 0;
+    std::vector<int64_t> nt_ev_start, nt_ev_len;
     int stitch_host = 0;      // 1: host stitch with halo tiles (the fallback path) always
     DevBuf ev_len, det_counts, det_tics, det_cand;
     DevBuf bridges, bmeta, tile_i32, sp_off, spine_items, asm_hdr, ev_first_tile;
@@ -269,7 +277,8 @@ int chain_publish(ps_ctx *ctx, int device, hipStream_t st, unsigned long long ti
 // (SMALL_TAIL bytes behind it hold the per-event offsets of small batches, so that one copy brings everything back)
 constexpr size_t SMALL_TAIL = 64 * 1024;
 struct SmallLayout { unsigned long long status, work0, work1, work2, dense, stamp[12], life[9], qctl, qhead, tree_tail; AsmHeader hdr;
-                     unsigned long long lat_ctl[6]; int lat_prog[LAT_D]; };     // (helpers of the look-ahead kernel, seg_device.hpp: LAT_D)
+                     unsigned long long lat_ctl[6]; int lat_prog[LAT_D];        // (helpers of the look-ahead kernel, seg_device.hpp: LAT_D)
+                     unsigned long long nt_cur; };                              // near-tie records of the call (DevCfg::nt_cur)
 
 int make_cfg(ps_ctx *ctx, const void *d_samples, const ps_sample_format *fmt, int mw, int maxw, int W,
              double min_gain, DevCfg *c)
@@ -299,6 +308,7 @@ int make_cfg(ps_ctx *ctx, const void *d_samples, const ps_sample_format *fmt, in
     c->k0_unaligned = ctx->k0_unaligned;
     c->pre_c = nullptr; c->pre_c2 = nullptr;
     c->dbg = ctx->small.as<SmallLayout>()->stamp;
+    c->nt_log = nullptr;
     c->rep_eval = ctx->rep_eval; c->rep_stage = ctx->rep_stage; c->rep_sum = ctx->rep_sum;
     return PS_OK;
 }
@@ -656,6 +666,10 @@ int finish_batch(ps_ctx *ctx, const DevCfg &cfg, size_t n_tj, int64_t n_items, i
     // near-tie decisions (seg_bs.hpp: bs_decide); -1: not counted -- the call ran on the LDS-window kernels, which decide every window
     // by one fp64 scan and keep no margins (a caller that redoes near ties on the exact route redoes such a call)
     ctx->counters[11] = cfg.bsum ? static_cast<int64_t>(hs.stamp[0]) : -1;
+    // ... and their records (ps_get_near_ties): the cursor came back with the status block
+    ctx->nt_seen = cfg.bsum && cfg.nt_log ? static_cast<int64_t>(hs.nt_cur) : -1;
+#else
+    ctx->nt_seen = -1;                                 // (the stamps take counters[11]'s words: not counted)
 #endif
     ctx->counters[12] = static_cast<int64_t>(hs.lat_ctl[4]);                                                   // look-ahead helpers: chunk results published
     ctx->counters[13] = static_cast<int64_t>(hs.lat_ctl[5]);                                                   // ... and taken by an owner instead of scanning
@@ -1290,7 +1304,8 @@ void ps_destroy(ps_ctx *ctx)
                       &ctx->det_counts, &ctx->det_tics, &ctx->det_cand, &ctx->bsum, &ctx->ev_info, &ctx->chunk_mabs,
                       &ctx->ev_boff, &ctx->blk_mm, &ctx->grp, &ctx->filt_fwd, &ctx->filt_agg, &ctx->filt_zin, &ctx->up_dev,
                       &ctx->align_in, &ctx->align_scratch, &ctx->bridge_ext, &ctx->ext_slot, &ctx->ext_list,
-                      &ctx->lat_state, &ctx->lat_seam, &ctx->lat_res, &ctx->pre_c, &ctx->ev_info_tr};
+                      &ctx->lat_state, &ctx->lat_seam, &ctx->lat_res, &ctx->pre_c, &ctx->ev_info_tr, &ctx->blk_cls,
+                      &ctx->cls_mm, &ctx->nt_log};
     for (DevBuf *b : bufs) b->release();
     ctx->h_meta.release(); ctx->h_dense.release(); ctx->h_small.release(); ctx->h_up.release(); ctx->h_hdr.release();
     for (auto &e : ctx->ev) if (e) (void)hipEventDestroy(e);
@@ -1346,6 +1361,7 @@ int ps_set_option(ps_ctx *ctx, const char *name, int64_t value)
     else if (n == "stitch_host") ctx->stitch_host = value != 0;
     else if (n == "prune") ctx->prune = value != 0;
     else if (n == "scan_bs") ctx->scan_bs = value != 0;
+    else if (n == "near_tie_log" && value >= 0 && value <= (int64_t(1) << 30)) ctx->nt_cap = value;
     else if (n == "groups") ctx->groups = value != 0;
     else if (n == "tree_par") ctx->tree_par = value != 0;
     else if (n == "k0_waves" && value >= 0 && value <= 16) ctx->k0_waves = static_cast<int>(value);
@@ -1483,7 +1499,62 @@ int ps_segment_exact_f64(ps_ctx *ctx, const double *d_current, const int64_t *h_
     return segment_events_impl(ctx, d_current, &fmt, h_ev_start, h_ev_len, n_ev, params, d_bounds, cap, h_bounds_off, nullptr, nullptr, true);
 }
 
+// Near-tie log (ps_get_near_ties): every segment call starts with "not counted" and no events of its own ...
+static void nt_reset(ps_ctx *ctx)
+{
+    ctx->nt_seen = -1;
+    ctx->nt_call_cap = ctx->nt_cap;
+    ctx->nt_ev_start.clear();
+    ctx->nt_ev_len.clear();
+}
+
+// ... points the call's configuration at the log (block-sum scan only: the LDS-window kernels keep no margins) ...
+static int nt_arm(ps_ctx *ctx, DevCfg &cfg)
+{
+    if (ctx->nt_call_cap <= 0) return PS_OK;
+    const void *before = ctx->nt_log.p;
+    HIP_TRY(ctx, ctx->nt_log.reserve(offsetof(NtLog, rec) + static_cast<size_t>(ctx->nt_call_cap) * sizeof(NtRec)));
+    if (ctx->nt_log.p != before || ctx->nt_hdr_cap != ctx->nt_call_cap) {       // (a new buffer or a new capacity: once, not per call)
+        NtLog h = {};
+        h.cur = &ctx->small.as<SmallLayout>()->nt_cur;
+        h.cap = ctx->nt_call_cap;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->nt_log.p, &h, offsetof(NtLog, rec), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->nt_hdr_cap = ctx->nt_call_cap;
+    }
+    cfg.nt_log = ctx->nt_log.as<NtLog>();
+    return PS_OK;
+}
+
+// ... and keeps its events when it logged anything (finish_batch set nt_seen from the cursor): the records are mapped on request
+static void nt_keep(ps_ctx *ctx, const int64_t *ev_start, const int64_t *ev_len, int32_t n_ev)
+{
+    if (ctx->nt_seen <= 0 || ctx->nt_seen > ctx->nt_call_cap) return;
+    ctx->nt_ev_start.assign(ev_start, ev_start + n_ev);
+    ctx->nt_ev_len.assign(ev_len, ev_len + n_ev);
+}
+
+static int segment_events_body(ps_ctx *ctx, const void *d_samples, const ps_sample_format *fmt,
+                               const int64_t *ev_start, const int64_t *ev_len, int32_t n_ev, const ps_split_params *params,
+                               int32_t *d_bounds, int64_t cap, int64_t *h_bounds_off, ps_segstat *d_stats,
+                               uint8_t *d_is_spine, bool d_f64);
+
 static int segment_events_impl(ps_ctx *ctx, const void *d_samples, const ps_sample_format *fmt,
+                               const int64_t *ev_start, const int64_t *ev_len, int32_t n_ev, const ps_split_params *params,
+                               int32_t *d_bounds, int64_t cap, int64_t *h_bounds_off, ps_segstat *d_stats,
+                               uint8_t *d_is_spine, bool d_f64)
+{
+    if (!ctx) return PS_ERR_ARG;
+    nt_reset(ctx);
+    const int rc = segment_events_body(ctx, d_samples, fmt, ev_start, ev_len, n_ev, params, d_bounds, cap, h_bounds_off, d_stats,
+                                       d_is_spine, d_f64);
+    if (rc == PS_OK && n_ev == 0) ctx->nt_seen = 0;           // (no event, no window: none -- as ps_detect_segment_trace says)
+    else if (rc == PS_OK) nt_keep(ctx, ev_start, ev_len, n_ev);
+    else ctx->nt_seen = -1;
+    return rc;
+}
+
+static int segment_events_body(ps_ctx *ctx, const void *d_samples, const ps_sample_format *fmt,
                                const int64_t *ev_start, const int64_t *ev_len, int32_t n_ev, const ps_split_params *params,
                                int32_t *d_bounds, int64_t cap, int64_t *h_bounds_off, ps_segstat *d_stats,
                                uint8_t *d_is_spine, bool d_f64)
@@ -1512,6 +1583,7 @@ static int segment_events_impl(ps_ctx *ctx, const void *d_samples, const ps_samp
     rc = make_cfg(ctx, d_samples, fmt, mw, maxw, W, min_gain, &cfg);
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!d_f64) { rc = nt_arm(ctx, cfg); if (rc) return rc; }
     for (double &m : ctx->ms) m = 0;
     for (int64_t &c : ctx->counters) c = 0;
     ctx->stream_idle = true;
@@ -2005,12 +2077,13 @@ int ps_detect_segment_trace(ps_ctx *ctx, const void *d_samples, const ps_sample_
                             int32_t *d_bounds, int64_t cap, int64_t *h_bounds_off, ps_segstat *d_stats)
 {
     if (!ctx) return PS_ERR_ARG;
+    nt_reset(ctx);                                     // (a call that fails from here on reports "not counted")
     if (!n_events_out || !params || !h_bounds_off || n < 0 || n > 0x7fffffff - 16 || ev_cap < 0 || cap < 0 ||
         (ev_cap > 0 && (!h_starts || !h_lengths)) || (cap > 0 && !d_bounds))
         return fail(ctx, PS_ERR_ARG, "bad argument");
     *n_events_out = 0;
     h_bounds_off[0] = 0;
-    if (n == 0) return PS_OK;
+    if (n == 0) { ctx->nt_seen = 0; return PS_OK; }
     if (!d_samples) return fail(ctx, PS_ERR_ARG, "d_samples is NULL");
     const auto t_begin = std::chrono::steady_clock::now();
     double min_gain = 0;
@@ -2031,6 +2104,8 @@ int ps_detect_segment_trace(ps_ctx *ctx, const void *d_samples, const ps_sample_
     const bool use_bs = ctx->scan_bs && mw >= 8 && W <= 63 * 1024 && ctx->mode != MODE_EXACT && !ctx->stitch_host && ctx->single_pass &&
                         !(ctx->wide_skip > 0 && fmt->quantum == ctx->wide_quantum);
     if (!use_bs) return two_calls();
+    rc = nt_arm(ctx, cfg);
+    if (rc) return rc;
     for (double &m : ctx->ms) m = 0;
     for (int64_t &c : ctx->counters) c = 0;
     ctx->d_is_spine = nullptr;
@@ -2098,7 +2173,7 @@ int ps_detect_segment_trace(ps_ctx *ctx, const void *d_samples, const ps_sample_
     rc = events_from_edges(ctx, cfg, n, tics, threshold, min_duration, min_current, h_starts, h_lengths, ev_cap, n_events_out);
     if (rc) return rc;
     const int32_t n_ev = static_cast<int32_t>(*n_events_out);
-    if (n_ev == 0) return PS_OK;
+    if (n_ev == 0) { ctx->nt_seen = 0; return PS_OK; }    // (no event, no window: none)
     for (int e = 0; e < n_ev; ++e)
         if (h_lengths[e] > 0x7fffffff - 2LL * W - 16) return fail(ctx, PS_ERR_ARG, "event %d length %lld out of range", e, static_cast<long long>(h_lengths[e]));
     // ---- every event from the trace's digest ----------------------------------------------------------------------------------
@@ -2108,7 +2183,52 @@ int ps_detect_segment_trace(ps_ctx *ctx, const void *d_samples, const ps_sample_
     if (rc == RC_FALLBACK || rc == RC_WIDE) {          // (a seam the device could not mend: the two calls, with the host stitch behind them)
         return ps_segment_events(ctx, d_samples, fmt, h_starts, h_lengths, n_ev, params, d_bounds, cap, h_bounds_off, d_stats, nullptr);
     }
+    if (rc == PS_OK) nt_keep(ctx, h_starts, h_lengths, n_ev);
+    else ctx->nt_seen = -1;
     return rc;
+}
+
+int ps_get_near_ties(const ps_ctx *ctx, ps_near_tie *out, int32_t cap, int64_t *n_out)
+{
+    if (!ctx || !n_out || cap < 0 || (cap > 0 && !out)) return PS_ERR_ARG;
+    if (ctx->nt_seen < 0) { *n_out = PS_NT_NOT_COUNTED; return PS_OK; }
+    if (ctx->nt_seen > ctx->nt_call_cap) { *n_out = PS_NT_INCOMPLETE; return PS_OK; }
+    if (ctx->nt_seen == 0) { *n_out = 0; return PS_OK; }
+    std::vector<NtRec> rec(static_cast<size_t>(ctx->nt_seen));
+    if (hipSetDevice(ctx->device) != hipSuccess ||
+        hipMemcpyAsync(rec.data(), static_cast<const char *>(ctx->nt_log.p) + offsetof(NtLog, rec), rec.size() * sizeof(NtRec), hipMemcpyDeviceToHost,
+                       ctx->stream) != hipSuccess ||
+        hipStreamSynchronize(ctx->stream) != hipSuccess) { (void)hipGetLastError(); return PS_ERR_HIP; }
+    // each record to every event that holds its window (events may overlap in ps_segment_events): events by start, the
+    // largest end so far, walked back from the last event that starts at or before the window
+    const int64_t *st = ctx->nt_ev_start.data(), *ln = ctx->nt_ev_len.data();
+    const size_t ne = ctx->nt_ev_start.size();
+    std::vector<int32_t> ord(ne);
+    for (size_t e = 0; e < ne; ++e) ord[e] = static_cast<int32_t>(e);
+    std::stable_sort(ord.begin(), ord.end(), [&](int32_t a, int32_t b) { return st[a] < st[b]; });
+    std::vector<int64_t> reach(ne);
+    for (size_t i = 0; i < ne; ++i) reach[i] = std::max(i ? reach[i - 1] : INT64_MIN, st[ord[i]] + ln[ord[i]]);
+    std::vector<ps_near_tie> sites;
+    for (const NtRec &r : rec) {
+        const int64_t g = r.start, ge = r.start + r.len;
+        size_t i = static_cast<size_t>(std::upper_bound(ord.begin(), ord.end(), g, [&](int64_t v, int32_t e) { return v < st[e]; }) - ord.begin());
+        while (i > 0 && reach[i - 1] >= ge) {
+            const int32_t e = ord[--i];
+            if (st[e] <= g && ge <= st[e] + ln[e]) {
+                // (the device keeps the split relative to the window's start; the ABI reports it as an index of the event)
+                const int32_t ws = static_cast<int32_t>(g - st[e]);
+                sites.push_back({e, ws, static_cast<int32_t>(ge - st[e]), r.split < 0 ? -1 : ws + r.split});
+            }
+        }
+    }
+    auto key = [](const ps_near_tie &a) { return std::make_tuple(a.event, a.window_start, a.window_end, a.split); };
+    std::sort(sites.begin(), sites.end(), [&](const ps_near_tie &a, const ps_near_tie &b) { return key(a) < key(b); });
+    sites.erase(std::unique(sites.begin(), sites.end(), [&](const ps_near_tie &a, const ps_near_tie &b) { return key(a) == key(b); }),
+                sites.end());
+    *n_out = static_cast<int64_t>(sites.size());
+    if (sites.size() > static_cast<size_t>(cap)) return PS_ERR_CAPACITY;
+    std::copy(sites.begin(), sites.end(), out);
+    return PS_OK;
 }
 
 int ps_get_timings(const ps_ctx *ctx, double *ms, int32_t n_ms, int64_t *counters, int32_t n_counters)

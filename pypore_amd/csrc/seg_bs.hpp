@@ -1093,13 +1093,21 @@ __device__ __attribute__((noinline)) long long bs_scan_exact(BsCold k, int64_t g
 }
 
 // The contenders (at most 64, one per lane) decided with the reference's fp64 arithmetic; first maximum wins.
+// A near tie is also logged here, out of line (DevCfg::nt_log, nullptr: off; g0: the window's first sample in the call's sample
+// array): lane 0 takes a slot of the log and stores the window and its decision; past the capacity the cursor keeps counting,
+// nothing is stored.  BsDecideCold is what the decision needs of the configuration -- the grid and the noise model, no samples --
+// with the log pointer in place of BsCold's sample pointer.
+struct BsDecideCold { const NtLog *lg; double q, q2, dc_counts; float noise_k; };
+__device__ __forceinline__ BsDecideCold bs_decide_cold(const DevCfg &c) { BsDecideCold k = {c.nt_log, c.q, c.q2, c.dc_counts, c.noise_k}; return k; }
 template <int DT>
-__device__ __attribute__((noinline)) long long bs_decide(BsCold k, int m, const void *cont_v, int ccount, int ps, int n,
+__device__ __attribute__((noinline)) long long bs_decide(BsDecideCold k, int m, const void *cont_v, int ccount, int ps, int n,
                                                          typename BsTypes<bs_wide<DT>()>::s1_t T1, typename BsTypes<bs_wide<DT>()>::s2_t T2,
-                                                         double thresh)
+                                                         double thresh, long long g0)
 {
-    const DevCfg cfg = bs_cold_cfg(k);
+    DevCfg cfg = {};
+    cfg.q = k.q; cfg.q2 = k.q2;
     const DevCfg *c = &cfg;
+    const NtLog *lg = k.lg;
     int near = 0;
     constexpr bool WIDE = bs_wide<DT>();
     typedef typename BsTypes<WIDE>::C BsC_t;
@@ -1180,6 +1188,14 @@ __device__ __attribute__((noinline)) long long bs_decide(BsCold k, int m, const 
         if constexpr (WIDE) {
             const bool mine = lane < ccount && gx == gx && thresh - gx < nk * (noise + noise_tot);
             if (__ballot(mine) != 0ull) near = 1;
+        }
+    }
+    if (near && lg && lane == 0) {
+        const unsigned long long slot = atomicAdd(lg->cur, 1ull);
+        if (slot < static_cast<unsigned long long>(lg->cap)) {
+            NtRec r;
+            r.start = g0; r.len = n; r.split = ei >= 0 ? ei - ps : -1;
+            const_cast<NtLog *>(lg)->rec[slot] = r;
         }
     }
     return (static_cast<long long>(near) << 32) | static_cast<unsigned>(ei);
@@ -1906,7 +1922,7 @@ __device__ int scan_window_bs(const DevCfg &c, const EvRef &er, int64_t base, in
     const bool sums_exact = WIDE || static_cast<double>(n) * static_cast<double>(mabsf) * static_cast<double>(mabsf) < 9007199254740992.0;
     if (result == -2 && !anyflag && ccount <= BS_NC && sums_exact) {
         ps_sync<64>();                              // contender stores visible to the other lanes
-        const long long dr = bs_decide<DT>(bs_cold(c), m, cont, ccount, ps, n, T1, T2, thresh);
+        const long long dr = bs_decide<DT>(bs_decide_cold(c), m, cont, ccount, ps, n, T1, T2, thresh, base + ps);
         result = uni(static_cast<int>(dr));
         wk.exact += 1; wk.near += uni(static_cast<int>(dr >> 32));
     }

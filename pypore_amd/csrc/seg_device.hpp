@@ -80,6 +80,14 @@ enum : int { KIND_NONE = 0, KIND_HIT = 1, KIND_EARLY = 2, KIND_LATE = 3, KIND_ST
 enum : unsigned { ST_OFF_GRID = 1u, ST_OUT_OVERFLOW = 2u, ST_STACK_OVERFLOW = 4u, ST_VERIFY_MISMATCH = 8u };
 enum : int { MODE_FAST = 0, MODE_EXACT = 1, MODE_VERIFY = 2 };
 
+// One near-tie decision of the block-sum scan (seg_bs.hpp: scan_window_bs after bs_decide), 16 bytes: the window's first sample
+// in the call's sample array (event base + window start), its length, and the split it decided, relative to the window's
+// start (-1: none).  The host maps the records to events (ps_get_near_ties).
+struct NtRec { long long start; int len, split; };
+// The log: a header the host writes when it allocates the buffer (the cursor lives in the call's status block, so that it comes
+// back with it), then the records.
+struct NtLog { unsigned long long *cur; long long cap; NtRec rec[1]; };
+
 struct DevCfg {
     const void *samples;
     int dtype, off_counts;
@@ -112,6 +120,7 @@ struct DevCfg {
     const double *pre_c;    // exact route for float64 input on no grid (ps_segment_exact_f64): the reference's own prefix sums, c = cumsum(x) and
     const double *pre_c2;   // c2 = cumsum(x * x) per event, strictly sequential like numpy's (cparsers.pyx:110-111); nullptr on every other route
     unsigned long long *dbg;  // diagnostics scratch (12 words) or nullptr
+    const NtLog *nt_log;      // near-tie log of the segment calls (seg_bs.hpp: bs_decide), nullptr: off
     int rep_eval, rep_stage, rep_sum;   // diagnostics: repeat a phase to measure its marginal cost (normally 1)
 };
 

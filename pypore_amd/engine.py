@@ -149,6 +149,26 @@ class Context(object):
             self._cnt = self.L.ps_counters(self.handle)      # the context's counters in place: no call per look
         return int(self._cnt[11])
 
+    def near_tie_sites(self):
+        """Where the near ties of the most recent segment call lie (ps_get_near_ties): a numpy structured array of
+        NEAR_TIE_DTYPE -- (event, window_start, window_end, split) in samples of the event, split -1: none -- sorted by
+        (event, window_start), speculative scans included (consistent_sites removes those).  None when the sites are not
+        counted (LDS-window kernels, option near_tie_log 0) or incomplete (the log overflowed): treat every event as flagged."""
+        with self.lock:
+            n = ctypes.c_int64()
+            cap = 64
+            while True:
+                buf = (_lib.NearTie * cap)()
+                rc = self.L.ps_get_near_ties(self.handle, buf, cap, ctypes.byref(n))
+                if rc == _lib.PS_ERR_CAPACITY and n.value > cap:
+                    cap = int(n.value)
+                    continue
+                _lib.check(rc, self.handle)
+                break
+            if n.value < 0:
+                return None
+            return np.frombuffer(buf, dtype=NEAR_TIE_DTYPE, count=int(n.value)).copy()
+
     # ---- the hot path ---------------------------------------------------------------------------
     @_serialised
     def segment_batch(self, samples, ev_off, params, quantum, offset_counts=0, want_stats=True, cap=None,
@@ -459,6 +479,49 @@ class Context(object):
                                          level_counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), seg_end.size),
                    self.handle)
         return out
+
+
+NEAR_TIE_DTYPE = np.dtype([("event", np.int32), ("window_start", np.int32), ("window_end", np.int32), ("split", np.int32)])
+
+
+def consistent_sites(sites, bounds, bounds_off, lengths, window_width):
+    """The near-tie sites of a call (Context.near_tie_sites) that belong to its final recursion.  The log also holds
+    speculative scans (tile spines, look-ahead helpers, bridges); by DESIGN.md 3 every window the final recursion scans
+    starts at s + k * (window_width // 2) for some s in B = {0} u boundaries u {n} other than n, ends at
+    min(e, window_start + window_width) for some range end e in B beyond its start, and splits, if at all, at a returned
+    boundary.  A site is kept when all three hold.  bounds / bounds_off: the call's boundaries (flat, per-event offsets),
+    lengths: the events' lengths.  None stays None."""
+    if sites is None:
+        return None
+    W = int(window_width)
+    half = max(1, W // 2)
+    arr = sites if isinstance(sites, np.ndarray) else np.array([tuple(x) for x in sites], dtype=NEAR_TIE_DTYPE)
+    keep = np.zeros(len(arr), dtype=bool)
+    bounds = np.asarray(bounds, dtype=np.int64)
+    ev = arr["event"].astype(np.int64)
+    for e in np.unique(ev):                                 # (vectorised per event: sites x range starts)
+        rows = np.nonzero(ev == e)[0]
+        ws = arr["window_start"][rows].astype(np.int64)
+        we = arr["window_end"][rows].astype(np.int64)
+        sp = arr["split"][rows].astype(np.int64)
+        n = int(lengths[e])
+        b = bounds[int(bounds_off[e]):int(bounds_off[e + 1])]
+        starts = np.concatenate(([0], b))                   # B without n
+        d = ws[:, None] - starts[None, :]
+        on_grid = np.any((d >= 0) & (d % half == 0), axis=1)
+        ends = np.concatenate((b, [n]))                     # range ends beyond 0
+        end_ok = ((we == ws + W) & (n >= ws + W)) | ((we < ws + W) & (we > ws) & np.isin(we, ends))
+        split_ok = (sp == -1) | np.isin(sp, b)
+        keep[rows] = on_grid & end_ok & split_ok
+    return sites[keep] if isinstance(sites, np.ndarray) else [x for x, kk in zip(sites, keep) if kk]
+
+
+def events_to_redo(sites, n_ev):
+    """Events of a call that the exact route must redo under off_grid="exact_on_near_tie": those with a site, or all of
+    them when the sites are None (not counted, or the log overflowed)."""
+    if sites is None:
+        return list(range(int(n_ev)))
+    return sorted({int(e) for e in np.asarray(sites["event"] if isinstance(sites, np.ndarray) else [s[0] for s in sites])})
 
 
 class NearTieWarning(UserWarning):

@@ -152,10 +152,11 @@ class SpeedyStatSplit(parser):
     def parse(self, current):
         return self._fast().parse(current)
 
-    def parse_batch(self, currents, levels=None):
+    def parse_batch(self, currents, levels=None, near_ties_out=None, flagged_out=None):
         """All events of a file in one device call (extension; same result as [parse(c) for c in currents]).  levels: the
-        level in pA that was subtracted from each event upstream (Event.parse of a filtered event), or None."""
-        return self._fast().parse_batch(currents, levels)
+        level in pA that was subtracted from each event upstream (Event.parse of a filtered event), or None.
+        near_ties_out / flagged_out: see cparsers.FastStatSplit.parse_batch."""
+        return self._fast().parse_batch(currents, levels, near_ties_out=near_ties_out, flagged_out=flagged_out)
 
     def parse_exact(self, current):
         """The exact route for one float64 current (extension; cparsers.FastStatSplit.parse_exact_batch)."""
@@ -165,9 +166,11 @@ class SpeedyStatSplit(parser):
     def off_grid(self):
         return self._grid["off_grid"]
 
-    def parse_filtered_batch(self, currents, order=1, cutoff=2000., sampling_freq=None):
-        """event.filter(order, cutoff); event.parse(self) for many events, on the device from end to end (extension)."""
-        return self._fast().parse_filtered_batch(currents, order, cutoff, self.sampling_freq if sampling_freq is None else sampling_freq)
+    def parse_filtered_batch(self, currents, order=1, cutoff=2000., sampling_freq=None, near_ties_out=None):
+        """event.filter(order, cutoff); event.parse(self) for many events, on the device from end to end (extension).
+        near_ties_out: a list that receives every event's near-tie sites (cparsers.FastStatSplit.parse_filtered_batch)."""
+        return self._fast().parse_filtered_batch(currents, order, cutoff, self.sampling_freq if sampling_freq is None else sampling_freq,
+                                                 near_ties_out=near_ties_out)
 
     def best_single_split(self, current):
         """(gain, index) of the best single split; like the reference wrapper, without cutoff_freq (:530-534)."""
