@@ -321,6 +321,38 @@ int ps_align_batch(ps_ctx *ctx, const double *h_model_means, const double *h_mod
                    const double *d_seq_stds, const double *d_seq_durs, const int64_t *h_seq_off, int32_t n_seq,
                    double *d_scores, uint32_t *d_paths, int32_t *d_status);
 
+/* A baked hidden Markov model (pypore_amd.hmm.Model.bake), host arrays.  States [0, n_emit) emit, states [n_emit, n_states)
+ * are silent and grouped by topological level: level L is [level_ptr[L], level_ptr[L+1]), level_ptr[0] = n_emit,
+ * level_ptr[n_levels] = n_states, and every silent predecessor of a silent state lies in a lower level.  kind[k]: 0 silent,
+ * 1 normal, 2 uniform; param[3k..3k+2]: normal (mean, 1 / (2 std^2), -log(std sqrt(2 pi))), uniform (low, high,
+ * -log(high - low)).  In-edges of k: [in_ptr[k], in_ptr[k+1]) of in_src / in_lp (source ascending, log probability); out-edges:
+ * the same over out_dst / out_lp.  finite: paths end at `end` after the last observation; otherwise at any state. */
+typedef struct ps_hmm_model {
+    int32_t n_states, n_emit, n_levels, start, end, finite;
+    const int32_t *kind, *level_ptr, *in_ptr, *in_src, *out_ptr, *out_dst;
+    const double *param, *in_lp, *out_lp;
+} ps_hmm_model;
+
+/* Decodes a BATCH of observation sequences against one model: sequence q is d_obs[h_off[q] .. h_off[q+1]) (fp64, device).
+ * mode PS_HMM_VITERBI: d_logp[q] = the best path's log probability; the path (state indices, from start at step 0 to the
+ *   last state, silent states included) goes to d_path[h_path_off[q] ..], its length to d_path_len[q] (0: impossible
+ *   sequence, d_logp[q] = -inf).  When a path is longer than its slot h_path_off[q+1] - h_path_off[q], PS_ERR_CAPACITY is
+ *   returned: the paths that fit are written and d_path_len holds every length, so the caller grows the slots and calls
+ *   again.  Ties go to the lowest source state.
+ * mode PS_HMM_FORWARD / PS_HMM_BACKWARD: d_logp[q] = the sequence's log probability (forward: f[n][end] for a finite
+ *   model, else log-sum-exp of f[n]; backward: b[0][start]).
+ * d_mat (optional, any mode): the (n+1) x n_states log matrix of the pass (Viterbi scores, forward or backward values),
+ *   sequence q at row h_off[q] + q.  Limits: 1 <= n_states <= 4096 and an in-degree of at most 65535 (PS_ERR_ARG beyond).
+ *   Viterbi splits the batch into launches whose backpointers ((n+1) x n_states bytes, two when an in-degree exceeds 255)
+ *   fit in option "hmm_bp_budget" bytes (default 512 MiB).  The model's upload is kept by the context and reused while the
+ *   arrays are unchanged.  Synchronises the context's stream before returning. */
+#define PS_HMM_VITERBI   0
+#define PS_HMM_FORWARD   1
+#define PS_HMM_BACKWARD  2
+int ps_hmm_batch(ps_ctx *ctx, const ps_hmm_model *model, int32_t mode, const double *d_obs, const int64_t *h_off,
+                 int32_t n_seq, double *d_logp, double *d_mat, int32_t *d_path, const int64_t *h_path_off,
+                 int32_t *d_path_len);
+
 /* Timing of the most recent ps_segment_batch, measured with HIP events on the context's stream.
  * ms[7] = the call's device work from the first upload to the last result copy (option "timing" >= 1, the
  * default); ms[3] = whole call on the host's wall clock.  With option "timing" = 2 an event is also recorded

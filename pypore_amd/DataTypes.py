@@ -5,8 +5,9 @@ Call contract kept from the reference (PyPore/DataTypes.py; SURVEY.md 8 a11, f-3
   Event(current, start, end, duration, second, file)   .filter(order, cutoff), .parse(parser), .segments   (:239-333)
   to_dict / to_json / from_json / to_meta on both, MetaEvent, Event.from_segments                         (:480-545, :683-796)
   Experiment(filenames).parse(event_detector, segmenter, filter_params), .files / .events / .segments; Sample   (:938-1049)
-and the JSON schema of README.md:346-391 (tests/golden/readme_file.json).  Plotting, HMM merging and MySQL are out of
-scope.
+and the JSON schema of README.md:346-391 (tests/golden/readme_file.json); apply_hmm on Event / MetaEvent / Experiment
+and HMM-guided parsing (:62-68, :276-333, :349-355, :990-995) with pypore_amd.hmm models decoded on the device.
+Plotting and MySQL are out of scope.
 
 Built here around three pieces: `encode()` turns any tree of records into JSON-able dicts (one recursive walk
 instead of per-class loops), `_rebuild_event()` is the inverse for one event, and a File read from an .abf keeps
@@ -36,9 +37,19 @@ def _parser_from(d):
     return _parser_base.from_json(dump_json(d)) if d is not None else None
 
 
+def _apply_hmm(event, hmm, algorithm):
+    """getattr(hmm, algorithm)(segment means), as the reference calls it (DataTypes.py:62-68, :349-355)."""
+    return getattr(hmm, algorithm)(np.array([seg.mean for seg in event.segments]))
+
+
 class MetaEvent(MetaSegment):
     """An event reduced to its numbers (and its MetaSegments)."""
     json_fields = EVENT_FIELDS
+
+    def apply_hmm(self, hmm, algorithm='viterbi'):
+        """The HMM's `algorithm` ('viterbi', 'forward', 'backward', 'log_probability') on the segment means: for a
+        pypore_amd.hmm.Model, (logp, path) / a log matrix / a float, computed on the device."""
+        return _apply_hmm(self, hmm, algorithm)
 
     def delete(self):
         for segment in self.__dict__.get('segments', []):
@@ -112,11 +123,54 @@ class Event(Segment):
     # ---- Event.parse (DataTypes.py:276-289, :333) -----------------------------------------------------------
     def parse(self, parser=None, hmm=None):
         """segments = parser.parse(current); every segment learns its event and is rescaled from samples to seconds
-        with the file's sampling rate."""
+        with the file's sampling rate.
+
+        With `hmm` (HMM-guided segmentation, DataTypes.py:292-330): the segment means go through hmm.viterbi, and runs of
+        consecutive segments in the same hidden state are merged into one Segment.  The reference's loop is restated
+        behaviour for behaviour, quirks included:
+          * path entry i is compared with entry i+1; the path starts with the model's start state (and holds every
+            silent state visited), so the comparisons are offset against the segments;
+          * after a group closes, j = i (not i + 1): consecutive merged segments share their boundary segment;
+          * the last group closes at i == n-2 and takes segments[-1] as its right edge;
+          * a new segment starts at int(ledge.start * second) and ends at int(redge.start * second + redge.n), with
+            `start` in SAMPLES (the scaling to seconds ran before the merge); `second` is the event's;
+          * its hidden_state is the name of path entry j+1's state;
+          * an event with fewer than two segments ends with no segments.
+        A pypore_amd.hmm.Model is decoded on the device; any other object with a `viterbi` method is called the same
+        way (duck typing; the reference accepts yahmm models only).  An impossible sequence (viterbi returns
+        (-inf, None)) raises ValueError where the reference would fail on indexing None."""
         if parser is None:
             parser = SpeedyStatSplit(prior_segments_per_second=10)
-        if hmm is not None:
-            raise NotImplementedError("HMM-guided merging needs yahmm (out of scope)")
+        if hmm and not callable(getattr(hmm, "viterbi", None)):
+            raise TypeError("hmm must be a pypore_amd.hmm.Model or have a viterbi method")
+        self._segment(parser)
+        if hmm:
+            self.segments = self._merge_by_hmm(hmm)
+        self.state_parser = parser
+
+    def _merge_by_hmm(self, hmm):
+        _, states = self.apply_hmm(hmm)
+        second = self.second
+        i, j, n, segments = 0, 0, len(self.segments), []
+        if states is None and n >= 2:
+            raise ValueError("the HMM gives the segment means probability zero: there is no Viterbi path to merge by")
+        while i < n - 1:
+            if states[i][1].name != states[i + 1][1].name or i == n - 2:
+                ledge = self.segments[j]
+                redge = self.segments[i] if i < n - 2 else self.segments[-1]
+                s, e = int(ledge.start * second), int(redge.start * second + redge.n)
+                segments.append(Segment(start=s, current=self.current[s:e], event=self, second=self.second,
+                                        hidden_state=states[j + 1][1].name))
+                j = i
+            i += 1
+        return segments
+
+    def apply_hmm(self, hmm, algorithm='viterbi'):
+        """The HMM's `algorithm` ('viterbi', 'forward', 'backward', 'log_probability') on the segment means: for a
+        pypore_amd.hmm.Model, (logp, path) / a log matrix / a float, computed on the device."""
+        return _apply_hmm(self, hmm, algorithm)
+
+    def _segment(self, parser):
         if self.__dict__.get("filtered"):
             self.segments = self._parse_filtered(parser)
         else:
@@ -132,7 +186,6 @@ class Event(Segment):
         for segment in self.segments:
             segment.event = self
             segment.scale(rate)
-        self.state_parser = parser
 
     def _on_fine_grid(self):
         """A filtered current is float64 off every ADC grid, and the device segmenter works on exact integer sums.
@@ -492,7 +545,22 @@ class Experiment(object):
                 take(fut.result())
 
     def apply_hmm(self, hmm, filter=None, indices=None):
-        raise NotImplementedError("HMM decoding needs yahmm (out of scope)")
+        """The Viterbi paths of the events' segment means, concatenated (what DataTypes.py:990-995 intends; as written
+        there it cannot run).  Events: `indices` of self.events (all when None), then those for which `filter(event)`
+        is true.  A pypore_amd.hmm.Model decodes them all in ONE viterbi_batch call; another object with a `viterbi`
+        method is called per event.  Returns the list of (index, state) entries of every path in event order (an
+        impossible event contributes nothing).  hmm=None or an object without `viterbi`: NotImplementedError."""
+        if hmm is None or not callable(getattr(hmm, "viterbi", None)):
+            raise NotImplementedError("apply_hmm needs a model with a viterbi method (pypore_amd.hmm.Model)")
+        events = self.events
+        if indices is not None:
+            events = [events[i] for i in indices]
+        if filter is not None:
+            events = [event for event in events if filter(event)]
+        means = [np.array([seg.mean for seg in event.segments], dtype=np.float64) for event in events]
+        batch = getattr(hmm, "viterbi_batch", None)
+        results = batch(means) if callable(batch) else [hmm.viterbi(m) for m in means]
+        return [entry for _, path in results if path is not None for entry in path]
 
     def delete(self):
         for file in self.files:

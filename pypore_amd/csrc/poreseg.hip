@@ -28,6 +28,7 @@
 #include "poreseg.h"
 #include "seg_device.hpp"
 #include "seg_align.hpp"
+#include "seg_hmm.hpp"
 
 using namespace ps;
 
@@ -165,6 +166,10 @@ struct ps_ctx {
     int64_t nt_cap = 65536, nt_hdr_cap = -1;   // (nt_hdr_cap: the capacity the header on the device names; -1: none written)
     int64_t nt_seen = -1, nt_call_cap = 0;
     std::vector<int64_t> nt_ev_start, nt_ev_len;
+    // HMM decoding (ps_hmm_batch): the model's last upload (host copy compared on every call), offsets, backpointers, results
+    DevBuf hmm_model, hmm_off, hmm_bp, hmm_last, hmm_flags;
+    std::vector<char> hmm_blob;
+    long long hmm_bp_budget = 512ll << 20;   // option hmm_bp_budget: bytes of Viterbi backpointers per launch
     int stitch_host = 0;      // 1: host stitch with halo tiles (the fallback path) always
     DevBuf ev_len, det_counts, det_tics, det_cand;
     DevBuf bridges, bmeta, tile_i32, sp_off, spine_items, asm_hdr, ev_first_tile;
@@ -1305,7 +1310,8 @@ void ps_destroy(ps_ctx *ctx)
                       &ctx->ev_boff, &ctx->blk_mm, &ctx->grp, &ctx->filt_fwd, &ctx->filt_agg, &ctx->filt_zin, &ctx->up_dev,
                       &ctx->align_in, &ctx->align_scratch, &ctx->bridge_ext, &ctx->ext_slot, &ctx->ext_list,
                       &ctx->lat_state, &ctx->lat_seam, &ctx->lat_res, &ctx->pre_c, &ctx->ev_info_tr, &ctx->blk_cls,
-                      &ctx->cls_mm, &ctx->nt_log};
+                      &ctx->cls_mm, &ctx->nt_log, &ctx->hmm_model, &ctx->hmm_off, &ctx->hmm_bp,
+                      &ctx->hmm_last, &ctx->hmm_flags};
     for (DevBuf *b : bufs) b->release();
     ctx->h_meta.release(); ctx->h_dense.release(); ctx->h_small.release(); ctx->h_up.release(); ctx->h_hdr.release();
     for (auto &e : ctx->ev) if (e) (void)hipEventDestroy(e);
@@ -1381,6 +1387,7 @@ int ps_set_option(ps_ctx *ctx, const char *name, int64_t value)
         ctx->lat_help = sh ? 0 : 1;
         ctx->k0_admit = value > 3 ? 3 : 0;
     }
+    else if (n == "hmm_bp_budget" && value >= 1) ctx->hmm_bp_budget = value;
     else if (n == "single_pass") ctx->single_pass = value != 0;
     else if (n == "gather_fused") ctx->gather_fused = value != 0;
     else if (n == "download_by_kernel") ctx->download_by_kernel = value != 0;
@@ -2606,6 +2613,178 @@ int ps_align_batch(ps_ctx *ctx, const double *h_model_means, const double *h_mod
     HIP_TRY(ctx, ctx->align_scratch.reserve(static_cast<size_t>(grid) * per_wg * sizeof(double)));
     hipLaunchKernelGGL(align_kernel, dim3(grid), dim3(ALIGN_NT), lds, ctx->stream, M, d_seq_means, d_seq_stds, d_seq_durs,
                        d_off, n_seq, ctx->align_scratch.as<double>(), static_cast<long long>(per_wg), B, d_scores, d_paths, d_status);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return PS_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// ps_hmm_batch: the model's arrays checked and packed into one blob (doubles first, then ints); the device copy is reused
+// while the blob is unchanged
+int hmm_upload(ps_ctx *ctx, const ps_hmm_model *m, HmmDev *D, int *max_in)
+{
+    const int S = m->n_states, NE = m->n_emit, NL = m->n_levels;
+    if (S < 1 || S > HMM_S_MAX) return fail(ctx, PS_ERR_ARG, "model of %d states: the device HMM kernels take 1..%d", S, HMM_S_MAX);
+    if (NE < 0 || NE > S || NL < 0 || NL > S - NE || (NL == 0) != (NE == S)) return fail(ctx, PS_ERR_ARG, "bad state / level counts");
+    if (m->start < NE || m->start >= S || m->end < NE || m->end >= S) return fail(ctx, PS_ERR_ARG, "start and end must be silent states");
+    if (!m->kind || !m->level_ptr || !m->in_ptr || !m->out_ptr || !m->param) return fail(ctx, PS_ERR_ARG, "null model array");
+    for (int k = 0; k < S; ++k)
+        if ((k < NE) != (m->kind[k] == HMM_NORMAL || m->kind[k] == HMM_UNIFORM) || (k >= NE && m->kind[k] != HMM_SILENT))
+            return fail(ctx, PS_ERR_ARG, "state %d: emitting states first, then silent ones", k);
+    if (m->level_ptr[0] != NE || m->level_ptr[NL] != S) return fail(ctx, PS_ERR_ARG, "levels must cover the silent states");
+    for (int L = 0; L < NL; ++L) if (m->level_ptr[L + 1] <= m->level_ptr[L]) return fail(ctx, PS_ERR_ARG, "empty or descending level %d", L);
+    std::vector<int> level(S, -1);
+    for (int L = 0; L < NL; ++L) for (int k = m->level_ptr[L]; k < m->level_ptr[L + 1]; ++k) level[k] = L;
+    const int32_t *ptrs[2] = {m->in_ptr, m->out_ptr}, *idx[2] = {m->in_src, m->out_dst};
+    int64_t n_edge[2];
+    *max_in = 0;
+    for (int d = 0; d < 2; ++d) {
+        if (ptrs[d][0] != 0) return fail(ctx, PS_ERR_ARG, "edge lists must start at 0");
+        for (int k = 0; k < S; ++k) {
+            if (ptrs[d][k + 1] < ptrs[d][k]) return fail(ctx, PS_ERR_ARG, "descending edge offsets");
+            if (d == 0) *max_in = std::max(*max_in, ptrs[d][k + 1] - ptrs[d][k]);
+        }
+        n_edge[d] = ptrs[d][S];
+        if (n_edge[d] > 0 && (!idx[d] || !(d ? m->out_lp : m->in_lp))) return fail(ctx, PS_ERR_ARG, "null edge array");
+        for (int k = 0; k < S; ++k)
+            for (int e = ptrs[d][k]; e < ptrs[d][k + 1]; ++e) {
+                const int o = idx[d][e];
+                if (o < 0 || o >= S) return fail(ctx, PS_ERR_ARG, "edge to a state out of range");
+                const int src = d ? k : o, dst = d ? o : k;
+                if (dst >= NE && src >= NE && level[src] >= level[dst]) return fail(ctx, PS_ERR_ARG, "silent edge %d -> %d does not go up a level", src, dst);
+            }
+    }
+    if (n_edge[0] != n_edge[1]) return fail(ctx, PS_ERR_ARG, "in- and out-edge lists differ in length");
+    if (*max_in > 65535) return fail(ctx, PS_ERR_ARG, "a state with %d in-edges: the device HMM kernels take at most 65535", *max_in);
+    const size_t nd = 3 * static_cast<size_t>(S) + 2 * n_edge[0];
+    const size_t ni = static_cast<size_t>(S) + (NL + 1) + 2 * (S + 1) + 2 * n_edge[0] + 3;
+    std::vector<char> blob(nd * sizeof(double) + ni * sizeof(int32_t), 0);
+    double *bd = reinterpret_cast<double *>(blob.data());
+    std::memcpy(bd, m->param, 3 * S * sizeof(double));
+    if (n_edge[0]) {
+        std::memcpy(bd + 3 * S, m->in_lp, n_edge[0] * sizeof(double));
+        std::memcpy(bd + 3 * S + n_edge[0], m->out_lp, n_edge[0] * sizeof(double));
+    }
+    int32_t *bi = reinterpret_cast<int32_t *>(bd + nd);
+    int32_t *b_kind = bi, *b_lvl = b_kind + S, *b_inp = b_lvl + NL + 1, *b_outp = b_inp + S + 1, *b_src = b_outp + S + 1,
+            *b_dst = b_src + n_edge[0];
+    b_dst[n_edge[0]] = m->start; b_dst[n_edge[0] + 1] = m->end; b_dst[n_edge[0] + 2] = m->finite;   // (part of the comparison)
+    std::memcpy(b_kind, m->kind, S * sizeof(int32_t));
+    std::memcpy(b_lvl, m->level_ptr, (NL + 1) * sizeof(int32_t));
+    std::memcpy(b_inp, m->in_ptr, (S + 1) * sizeof(int32_t));
+    std::memcpy(b_outp, m->out_ptr, (S + 1) * sizeof(int32_t));
+    if (n_edge[0]) {
+        std::memcpy(b_src, m->in_src, n_edge[0] * sizeof(int32_t));
+        std::memcpy(b_dst, m->out_dst, n_edge[0] * sizeof(int32_t));
+    }
+    if (blob != ctx->hmm_blob || !ctx->hmm_model.p) {
+        HIP_TRY(ctx, ctx->hmm_model.reserve(blob.size()));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->hmm_model.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));       // (blob is a local: the copy completes before it goes)
+        ctx->hmm_blob.swap(blob);
+    }
+    const double *dd = ctx->hmm_model.as<double>();
+    const int32_t *di = reinterpret_cast<const int32_t *>(dd + nd);
+    D->param = dd; D->in_lp = dd + 3 * S; D->out_lp = dd + 3 * S + n_edge[0];
+    D->kind = di; D->level_ptr = di + S; D->in_ptr = D->level_ptr + NL + 1; D->out_ptr = D->in_ptr + S + 1;
+    D->in_src = D->out_ptr + S + 1; D->out_dst = D->in_src + n_edge[0];
+    D->S = S; D->n_emit = NE; D->n_levels = NL; D->start = m->start; D->end = m->end; D->finite = m->finite != 0;
+    return PS_OK;
+}
+
+template <typename BP>
+int hmm_viterbi(ps_ctx *ctx, const HmmDev &D, const double *d_obs, const int64_t *h_off, const long long *d_off, int32_t n_seq,
+                double *d_logp, double *d_mat, int32_t *d_path, const long long *d_path_off, int32_t *d_path_len, size_t lds)
+{
+    const size_t S = static_cast<size_t>(D.S);
+    const long long budget = std::max<long long>(1, ctx->hmm_bp_budget);
+    HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_fwd_kernel<HMM_VITERBI, BP>), static_cast<int>(lds)));
+    HIP_TRY(ctx, ctx->hmm_last.reserve(static_cast<size_t>(n_seq) * sizeof(int)));
+    HIP_TRY(ctx, ctx->hmm_flags.reserve(sizeof(int)));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->hmm_flags.p, 0, sizeof(int), ctx->stream));
+    for (int32_t q0 = 0; q0 < n_seq;) {
+        // as many sequences as keep the backpointers within the budget (at least one)
+        long long bytes = (h_off[q0 + 1] - h_off[q0] + 1) * static_cast<long long>(S * sizeof(BP));
+        int32_t q1 = q0 + 1;
+        while (q1 < n_seq) {
+            const long long more = (h_off[q1 + 1] - h_off[q1] + 1) * static_cast<long long>(S * sizeof(BP));
+            if (bytes + more > budget) break;
+            bytes += more; ++q1;
+        }
+        if (bytes > (8ll << 30)) return fail(ctx, PS_ERR_ARG, "sequence %d needs %lld bytes of backpointers (8 GiB at most)", q0, bytes);
+        HIP_TRY(ctx, ctx->hmm_bp.reserve(static_cast<size_t>(bytes)));
+        const long long bp_row0 = h_off[q0] + q0;
+        const int nq = q1 - q0;
+        BP *bp = ctx->hmm_bp.as<BP>();
+        hipLaunchKernelGGL((hmm_fwd_kernel<HMM_VITERBI, BP>), dim3(nq), dim3(HMM_NT), lds, ctx->stream, D, d_obs, d_off, q0, d_logp,
+                           d_mat, bp, bp_row0, ctx->hmm_last.as<int>());
+        HIP_TRY(ctx, hipGetLastError());
+        hipLaunchKernelGGL(hmm_trace_kernel<BP>, dim3((nq + HMM_NT - 1) / HMM_NT), dim3(HMM_NT), 0, ctx->stream, D, d_off, q0, nq,
+                           static_cast<const BP *>(bp), bp_row0, static_cast<const int *>(ctx->hmm_last.as<int>()),
+                           static_cast<const double *>(d_logp), d_path_off, d_path, d_path_len, ctx->hmm_flags.as<int>());
+        HIP_TRY(ctx, hipGetLastError());
+        q0 = q1;
+    }
+    int flags = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&flags, ctx->hmm_flags.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (flags & 2) return fail(ctx, PS_ERR_INTERNAL, "a Viterbi traceback left the model");
+    if (flags & 1) return fail(ctx, PS_ERR_CAPACITY, "a Viterbi path is longer than its slot (d_path_len holds the lengths)");
+    return PS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ps_hmm_batch(ps_ctx *ctx, const ps_hmm_model *model, int32_t mode, const double *d_obs, const int64_t *h_off,
+                 int32_t n_seq, double *d_logp, double *d_mat, int32_t *d_path, const int64_t *h_path_off,
+                 int32_t *d_path_len)
+{
+    if (!ctx) return PS_ERR_ARG;
+    if (!model || !h_off) return fail(ctx, PS_ERR_ARG, "null pointer");
+    if (mode != PS_HMM_VITERBI && mode != PS_HMM_FORWARD && mode != PS_HMM_BACKWARD) return fail(ctx, PS_ERR_ARG, "unknown mode %d", mode);
+    if (n_seq < 0) return fail(ctx, PS_ERR_ARG, "negative sequence count");
+    if (mode == PS_HMM_VITERBI && (!h_path_off || (n_seq > 0 && (!d_path_len || !d_path))))
+        return fail(ctx, PS_ERR_ARG, "Viterbi needs the path buffer, its offsets and the length array");
+    for (int32_t q = 0; q < n_seq; ++q) {
+        if (h_off[q] < 0 || h_off[q + 1] < h_off[q]) return fail(ctx, PS_ERR_ARG, "sequence offsets must be non-negative and ascending");
+        if (h_off[q + 1] - h_off[q] > INT32_MAX / 2) return fail(ctx, PS_ERR_ARG, "sequence %d too long", q);
+        if (mode == PS_HMM_VITERBI && (h_path_off[q] < 0 || h_path_off[q + 1] < h_path_off[q]))
+            return fail(ctx, PS_ERR_ARG, "path offsets must be non-negative and ascending");
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HmmDev D;
+    int max_in = 0;
+    if (int rc = hmm_upload(ctx, model, &D, &max_in)) return rc;
+    if (n_seq == 0) return PS_OK;
+    if (!d_logp || (h_off[n_seq] > 0 && !d_obs)) return fail(ctx, PS_ERR_ARG, "null device pointer");
+    // offsets (and the path slots) in one upload
+    const size_t nb = (static_cast<size_t>(n_seq) + 1) * sizeof(int64_t);
+    const size_t up = mode == PS_HMM_VITERBI ? 2 * nb : nb;
+    HIP_TRY(ctx, ctx->h_up.reserve(up));
+    HIP_TRY(ctx, ctx->hmm_off.reserve(up));
+    std::memcpy(ctx->h_up.p, h_off, nb);
+    if (mode == PS_HMM_VITERBI) std::memcpy(static_cast<char *>(ctx->h_up.p) + nb, h_path_off, nb);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->hmm_off.p, ctx->h_up.p, up, hipMemcpyHostToDevice, ctx->stream));
+    const long long *d_off = ctx->hmm_off.as<long long>();
+    const size_t lds = 2 * static_cast<size_t>(D.S) * sizeof(double);
+    if (mode == PS_HMM_VITERBI) {
+        const long long *d_path_off = d_off + n_seq + 1;
+        return max_in > 255 ? hmm_viterbi<uint16_t>(ctx, D, d_obs, h_off, d_off, n_seq, d_logp, d_mat, d_path, d_path_off, d_path_len, lds)
+                            : hmm_viterbi<uint8_t>(ctx, D, d_obs, h_off, d_off, n_seq, d_logp, d_mat, d_path, d_path_off, d_path_len, lds);
+    }
+    if (mode == PS_HMM_FORWARD) {
+        HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_fwd_kernel<HMM_FORWARD, uint8_t>), static_cast<int>(lds)));
+        hipLaunchKernelGGL((hmm_fwd_kernel<HMM_FORWARD, uint8_t>), dim3(n_seq), dim3(HMM_NT), lds, ctx->stream, D, d_obs, d_off, 0,
+                           d_logp, d_mat, static_cast<uint8_t *>(nullptr), 0ll, static_cast<int *>(nullptr));
+    } else {
+        HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_bwd_kernel), static_cast<int>(lds)));
+        hipLaunchKernelGGL(hmm_bwd_kernel, dim3(n_seq), dim3(HMM_NT), lds, ctx->stream, D, d_obs, d_off, 0, d_logp, d_mat);
+    }
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return PS_OK;

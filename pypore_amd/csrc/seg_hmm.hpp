@@ -1,0 +1,261 @@
+// seg_hmm.hpp -- hidden Markov model decoding (pypore_amd.hmm): Viterbi, forward and backward for a batch of observation
+// sequences against one baked model, on gfx950.
+//
+// States are ordered as pypore_amd.hmm.Model.bake leaves them: emitting states [0, n_emit), then the silent states
+// [n_emit, S) grouped by topological level (a silent state's silent predecessors all lie in lower levels).  A time step t
+// of the forward-type passes runs in two phases:
+//   1. every emitting state combines its in-edges from row t-1 and adds its emission log density of observation t-1;
+//   2. the silent states, level by level, combine their in-edges from row t (emitting states of step t and silent states
+//      of lower levels).
+// The backward pass runs the mirror image over the out-edges (levels descending, then the emitting states).  Viterbi takes
+// the maximum over the in-edges, scanned in ascending source index and updated only on a strictly greater score, so the
+// lowest source wins a tie; forward and backward take log-sum-exp, accumulated online as  max + log1p(sum of the other
+// terms' exp(v - max)),  which keeps values near log(1) accurate.
+//
+// One workgroup of one wave per sequence: the lanes spread over the states, the previous and current score rows live in
+// LDS (16 * S bytes, S <= 4096), and the steps between phases and levels need only a wave-level fence, no s_barrier.  The
+// model arrays are read from global memory: every workgroup reads the same few KB, which stay in L2 / L1.  Viterbi stores
+// one backpointer per (step, state) -- the ordinal of the winning in-edge, 1 or 2 bytes -- in global memory, and a second
+// kernel walks them back with one lane per sequence.  fp64 throughout, no FMA contraction.
+#pragma once
+
+namespace ps {
+
+constexpr int HMM_NT = 64;                 // one wave per workgroup
+constexpr int HMM_S_MAX = 4096;            // states: two fp64 rows of S in LDS = 64 KiB at most
+constexpr int HMM_VITERBI = 0, HMM_FORWARD = 1, HMM_BACKWARD = 2;   // include/poreseg.h PS_HMM_*
+constexpr int HMM_SILENT = 0, HMM_NORMAL = 1, HMM_UNIFORM = 2;
+
+struct HmmDev {                 // device pointers into one upload of the baked model (include/poreseg.h ps_hmm_model)
+    const double *param;        // 3 per state: normal (mean, 1 / (2 std^2), -log(std sqrt(2 pi))), uniform (low, high, -log(high - low))
+    const double *in_lp, *out_lp;
+    const int *kind, *level_ptr, *in_ptr, *in_src, *out_ptr, *out_dst;
+    int S, n_emit, n_levels, start, end, finite;
+};
+
+__device__ __forceinline__ void hm_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+__device__ __forceinline__ double hmm_emit(const HmmDev &M, int k, double x)
+{
+#pragma clang fp contract(off)
+    const double a = M.param[3 * k], b = M.param[3 * k + 1], c = M.param[3 * k + 2];
+    if (M.kind[k] == HMM_NORMAL) {
+        const double d = x - a;
+        return c - (d * d) * b;
+    }
+    return (x >= a && x <= b) ? c : -__builtin_inf();
+}
+
+// log-sum-exp of a stream of terms: m = the largest so far, r = sum of exp(v - m) over the others
+struct HmmLse {
+    double m = -__builtin_inf(), r = 0.0;
+    __device__ __forceinline__ void add(double v)
+    {
+        if (!(v > -__builtin_inf())) return;
+        if (v > m) { r = (r + 1.0) * exp(m - v); m = v; }
+        else r += exp(v - m);
+    }
+    __device__ __forceinline__ double get() const { return m > -__builtin_inf() ? m + log1p(r) : -__builtin_inf(); }
+};
+
+// Viterbi / forward over one sequence per workgroup.  Rows of sequence q: mat (optional, absolute row off[q] + q) and bp
+// (backpointers, Viterbi only, row off[q] + q - bp_row0 of this launch).  Writes logp[q] and, for Viterbi, last[q]: the
+// state the path ends in (end for a finite model, else the best state of step n, lowest index on a tie).
+template <int MODE, typename BP>
+__global__ __launch_bounds__(HMM_NT) void hmm_fwd_kernel(HmmDev M, const double *obs, const long long *off, int q0,
+                                                         double *logp, double *mat, BP *bp, long long bp_row0, int *last)
+{
+#pragma clang fp contract(off)
+    extern __shared__ double hm_lds[];
+    const int S = M.S, NE = M.n_emit, lane = threadIdx.x;
+    const int q = q0 + blockIdx.x;
+    const long long base = off[q];
+    const int n = static_cast<int>(off[q + 1] - base);
+    const double *x = obs + base;
+    const long long row0 = base + q;
+    double *prev = hm_lds, *cur = hm_lds + S;
+    constexpr double NEG = -__builtin_inf();
+
+    // silent states of step t, level by level, from row `cur`
+    auto silent_phase = [&](int t) {
+        BP *bprow = MODE == HMM_VITERBI ? bp + (row0 - bp_row0 + t) * S : nullptr;
+        for (int L = 0; L < M.n_levels; ++L) {
+            const int hi = M.level_ptr[L + 1];
+            for (int k = M.level_ptr[L] + lane; k < hi; k += HMM_NT) {
+                const int e0 = M.in_ptr[k], e1 = M.in_ptr[k + 1];
+                const bool init = t == 0 && k == M.start;
+                if (MODE == HMM_VITERBI) {
+                    double best = init ? 0.0 : NEG; int arg = 0;
+                    for (int e = e0; e < e1; ++e) {
+                        const double v = cur[M.in_src[e]] + M.in_lp[e];
+                        if (v > best) { best = v; arg = e - e0; }
+                    }
+                    cur[k] = best;
+                    bprow[k] = static_cast<BP>(arg);
+                } else {
+                    HmmLse acc;
+                    if (init) acc.add(0.0);
+                    for (int e = e0; e < e1; ++e) acc.add(cur[M.in_src[e]] + M.in_lp[e]);
+                    cur[k] = acc.get();
+                }
+            }
+            hm_sync();
+        }
+    };
+    auto store_row = [&](int t) {
+        if (mat) {
+            double *dst = mat + (row0 + t) * S;
+            for (int k = lane; k < S; k += HMM_NT) dst[k] = cur[k];
+        }
+    };
+
+    for (int k = lane; k < NE; k += HMM_NT) {
+        cur[k] = NEG;
+        if (MODE == HMM_VITERBI) bp[(row0 - bp_row0) * S + k] = 0;
+    }
+    hm_sync();
+    silent_phase(0);
+    store_row(0);
+    for (int t = 1; t <= n; ++t) {
+        double *tmp = prev; prev = cur; cur = tmp;
+        const double xt = x[t - 1];
+        BP *bprow = MODE == HMM_VITERBI ? bp + (row0 - bp_row0 + t) * S : nullptr;
+        for (int k = lane; k < NE; k += HMM_NT) {
+            const int e0 = M.in_ptr[k], e1 = M.in_ptr[k + 1];
+            double v;
+            if (MODE == HMM_VITERBI) {
+                double best = NEG; int arg = 0;
+                for (int e = e0; e < e1; ++e) {
+                    const double c = prev[M.in_src[e]] + M.in_lp[e];
+                    if (c > best) { best = c; arg = e - e0; }
+                }
+                bprow[k] = static_cast<BP>(arg);
+                v = best;
+            } else {
+                HmmLse acc;
+                for (int e = e0; e < e1; ++e) acc.add(prev[M.in_src[e]] + M.in_lp[e]);
+                v = acc.get();
+            }
+            cur[k] = v > NEG ? v + hmm_emit(M, k, xt) : NEG;
+        }
+        hm_sync();
+        silent_phase(t);
+        store_row(t);
+    }
+
+    // the result of the sequence
+    if (M.finite) {
+        if (lane == 0) {
+            logp[q] = cur[M.end];
+            if (MODE == HMM_VITERBI) last[q] = M.end;
+        }
+        return;
+    }
+    double m = NEG; int am = 0x7fffffff;
+    for (int k = lane; k < S; k += HMM_NT) if (cur[k] > m) { m = cur[k]; am = k; }
+    for (int d = 32; d; d >>= 1) {
+        const double om = __shfl_xor(m, d); const int oa = __shfl_xor(am, d);
+        if (om > m || (om == m && oa < am)) { m = om; am = oa; }
+    }
+    if (MODE == HMM_VITERBI) {
+        if (lane == 0) { logp[q] = m; last[q] = am; }
+        return;
+    }
+    double r = 0.0;
+    if (m > NEG)
+        for (int k = lane; k < S; k += HMM_NT) if (k != am) r += exp(cur[k] - m);
+    for (int d = 32; d; d >>= 1) r += __shfl_xor(r, d);
+    if (lane == 0) logp[q] = m > NEG ? m + log1p(r) : NEG;
+}
+
+// Backward over one sequence per workgroup: b[n][k] starts from log 1 at end (finite model) or at every state (infinite),
+// b[t][k] = logsumexp over out-edges k -> l of  lp + (l emitting ? e_l(x_t) + b[t+1][l] : b[t][l]).  logp[q] = b[0][start].
+__global__ __launch_bounds__(HMM_NT) void hmm_bwd_kernel(HmmDev M, const double *obs, const long long *off, int q0,
+                                                         double *logp, double *mat)
+{
+#pragma clang fp contract(off)
+    extern __shared__ double hm_lds[];
+    const int S = M.S, NE = M.n_emit, lane = threadIdx.x;
+    const int q = q0 + blockIdx.x;
+    const long long base = off[q];
+    const int n = static_cast<int>(off[q + 1] - base);
+    const double *x = obs + base;
+    const long long row0 = base + q;
+    double *nxt = hm_lds, *cur = hm_lds + S;       // nxt: row t+1 with the emission of observation t added (emitting states)
+    constexpr double NEG = -__builtin_inf();
+
+    auto one = [&](int k, int t) {
+        HmmLse acc;
+        if (t == n && (!M.finite || k == M.end)) acc.add(0.0);
+        const int e0 = M.out_ptr[k], e1 = M.out_ptr[k + 1];
+        for (int e = e0; e < e1; ++e) {
+            const int l = M.out_dst[e];
+            if (l < NE) { if (t < n) acc.add(nxt[l] + M.out_lp[e]); }
+            else acc.add(cur[l] + M.out_lp[e]);
+        }
+        cur[k] = acc.get();
+    };
+
+    for (int t = n; t >= 0; --t) {
+        if (t < n) {
+            double *tmp = nxt; nxt = cur; cur = tmp;
+            const double xt = x[t];
+            for (int l = lane; l < NE; l += HMM_NT) nxt[l] = nxt[l] > NEG ? nxt[l] + hmm_emit(M, l, xt) : NEG;
+            hm_sync();
+        }
+        for (int L = M.n_levels - 1; L >= 0; --L) {
+            const int hi = M.level_ptr[L + 1];
+            for (int k = M.level_ptr[L] + lane; k < hi; k += HMM_NT) one(k, t);
+            hm_sync();
+        }
+        for (int k = lane; k < NE; k += HMM_NT) one(k, t);
+        hm_sync();
+        if (mat) {
+            double *dst = mat + (row0 + t) * S;
+            for (int k = lane; k < S; k += HMM_NT) dst[k] = cur[k];
+        }
+    }
+    if (lane == 0) logp[q] = cur[M.start];
+}
+
+// Viterbi traceback, one lane per sequence: from (n, last[q]) back to (0, start).  An emitting state steps back one
+// observation, a silent one stays.  The path goes to path[path_off[q] ..] in forward order when it fits; path_len[q] is its
+// length either way (0: the sequence is impossible).  *flags: bit 0 a path did not fit, bit 1 a walk left the model (a bug).
+template <typename BP>
+__global__ __launch_bounds__(HMM_NT) void hmm_trace_kernel(HmmDev M, const long long *off, int q0, int nq, const BP *bp,
+                                                           long long bp_row0, const int *last, const double *logp,
+                                                           const long long *path_off, int *path, int *path_len, int *flags)
+{
+    const int i = blockIdx.x * HMM_NT + threadIdx.x;
+    if (i >= nq) return;
+    const int q = q0 + i, S = M.S;
+    const long long base = off[q];
+    const int n = static_cast<int>(off[q + 1] - base);
+    const BP *b = bp + (base + q - bp_row0) * S;
+    if (!(logp[q] > -__builtin_inf())) { path_len[q] = 0; return; }
+    const long long bound = static_cast<long long>(n + 1) * S + 1;
+    long long len = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        int t = n, k = last[q];
+        long long w = path_off[q] + len - 1;
+        for (long long c = 0;; ++c) {
+            if (c >= bound || k < 0 || k >= S || (k < M.n_emit && t == 0)) { atomicOr(flags, 2); path_len[q] = 0; return; }
+            if (pass) path[w - c] = k;
+            if (t == 0 && k == M.start) { if (!pass) len = c + 1; break; }
+            const int e0 = M.in_ptr[k], e = e0 + static_cast<int>(b[static_cast<long long>(t) * S + k]);
+            if (e >= M.in_ptr[k + 1]) { atomicOr(flags, 2); path_len[q] = 0; return; }
+            if (k < M.n_emit) --t;
+            k = M.in_src[e];
+        }
+        if (!pass) {
+            path_len[q] = static_cast<int>(len);
+            if (len > path_off[q + 1] - path_off[q]) { atomicOr(flags, 1); return; }
+        }
+    }
+}
+
+}  // namespace ps

@@ -458,6 +458,47 @@ class Context(object):
         return scores[:n_seq], paths[:int(off[-1])], status[:n_seq]
 
     @_serialised
+    def hmm_batch(self, model, mode, obs, off, want_mat=False, path_slots=None):
+        """ps_hmm_batch: one HMM pass over a batch of sequences.  model: a _lib.HmmModel (its arrays kept alive by the caller);
+        obs: float64 CUDA tensor, sequence q = obs[off[q]:off[q+1]].  Returns (logp float64 [n_seq], matrix float64
+        [off[-1] + n_seq, n_states] or None, and for Viterbi: (path int32 tensor, path offsets, path lengths int32 tensor)
+        -- else None).  A Viterbi path longer than its slot (path_slots[q] entries, default 2 (n + 1) + the silent states + 1)
+        makes the call run again with slots of the exact lengths (PS_ERR_CAPACITY)."""
+        assert obs.is_cuda and obs.is_contiguous() and obs.dtype == torch.float64
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        n_seq = off.size - 1
+        dev = obs.device
+        S = model.n_states
+        logp = torch.empty(max(n_seq, 1), dtype=torch.float64, device=dev)
+        mat = torch.empty((int(off[-1]) + n_seq, S), dtype=torch.float64, device=dev) if want_mat else None
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        torch.cuda.current_stream(dev).synchronize()
+
+        def call(path, path_off, path_len):
+            return self.L.ps_hmm_batch(self.handle, ctypes.byref(model), int(mode), ctypes.c_void_p(obs.data_ptr()),
+                                       off.ctypes.data_as(i64p), n_seq, ctypes.c_void_p(logp.data_ptr()),
+                                       ctypes.c_void_p(mat.data_ptr() if mat is not None else 0),
+                                       ctypes.c_void_p(path.data_ptr() if path is not None else 0),
+                                       path_off.ctypes.data_as(i64p) if path_off is not None else None,
+                                       ctypes.c_void_p(path_len.data_ptr() if path_len is not None else 0))
+
+        if mode != _lib.PS_HMM_VITERBI:
+            _lib.check(call(None, None, None), self.handle)
+            return logp[:n_seq], mat, None
+        if path_slots is None:
+            path_slots = 2 * (np.diff(off) + 1) + (S - model.n_emit) + 1
+        path_len = torch.empty(max(n_seq, 1), dtype=torch.int32, device=dev)
+        for attempt in range(2):
+            path_off = np.concatenate(([0], np.cumsum(path_slots))).astype(np.int64)
+            path = torch.empty(max(int(path_off[-1]), 1), dtype=torch.int32, device=dev)
+            rc = call(path, path_off, path_len)
+            if rc != _lib.PS_ERR_CAPACITY or attempt:
+                break
+            path_slots = path_len[:n_seq].cpu().numpy().astype(np.int64)      # the exact lengths
+        _lib.check(rc, self.handle)
+        return logp[:n_seq], mat, (path, path_off, path_len[:n_seq])
+
+    @_serialised
     def synth_trace(self, n, seed, seg_end, level_counts, dtype=torch.float32, start=0):
         """Synthetic step trace generated directly in HBM (csrc synth_kernel == pypore_amd.synth).  start > 0: the
         samples [start, start + n) of the trace the table describes (a rank's piece of one long trace): the noise hash
