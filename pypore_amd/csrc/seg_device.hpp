@@ -2682,8 +2682,10 @@ __global__ __launch_bounds__(256) void ev_info_trace_kernel(const int64_t *ev_st
 }
 
 // ---- K2: per-segment statistics, core.py:209-223 ------------------------------------------------
-// One workgroup per segment.  Sums of counts and counts^2 are exact (fp64 holds the integers),
-// mean = q*S1/n, std = q*sqrt(S2/n - (S1/n)^2) (population), min/max exact.
+// One workgroup per segment.  The sums run over y = k - k0, k0 the event's first count (segstat_bs_kernel centres on m
+// the same way): S1 = sum y is an exact integer in fp64 (|y| < 2^24), S2 = sum y^2 only while it stays below 2^53 -- past
+// that it rounds like any fp64 sum.  mean = (k0 + S1/n) q, std = q sqrt(S2/n - (S1/n)^2) (population), min/max exact.
+// Formed about k0, the variance of a quiet segment at a high level does not cancel (about count 0 it lost eps k^2 / var).
 constexpr int STAT_NT = 256;
 template <int DT>
 __global__ __launch_bounds__(STAT_NT) void segstat_kernel(DevCfg c, const int64_t *ev_start, const int64_t *ev_len, int32_t n_ev,
@@ -2709,13 +2711,14 @@ __global__ __launch_bounds__(STAT_NT) void segstat_kernel(DevCfg c, const int64_
     const int b = s == cnt ? n_e : bounds[boff + s];
     const int64_t g0 = ev_start[e];
     unsigned bad = 0;
-    double s1 = 0, s2 = 0;
+    const int k0 = n_e > 0 ? load_count<DT>(c, g0, bad) : 0;      // (an empty event has no first sample)
+    double s1 = 0, s2 = 0;                                          // sums of y = k - k0 and y^2
     int mn = 0x7fffffff, mx = static_cast<int>(0x80000000);
     for (int i = a + threadIdx.x; i < b; i += STAT_NT) {
-        int k = load_count<DT>(c, g0 + i, bad);
-        double d = static_cast<double>(k);
+        const int y = load_count<DT>(c, g0 + i, bad) - k0;
+        const double d = static_cast<double>(y);
         s1 += d; s2 += d * d;
-        mn = k < mn ? k : mn; mx = k > mx ? k : mx;
+        mn = y < mn ? y : mn; mx = y > mx ? y : mx;
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
@@ -2736,11 +2739,12 @@ __global__ __launch_bounds__(STAT_NT) void segstat_kernel(DevCfg c, const int64_
         ps_segstat r;
         const int n = b - a;
         if (n > 0) {
-            double m = t1 / n;
-            double var = t2 / n - m * m;
+            const double dn = static_cast<double>(n);
+            const double my = t1 / dn;
+            double var = t2 / dn - my * my;
             if (var < 0) var = 0;
-            r.mean = m * c.q; r.std = sqrt(var) * c.q;
-            r.min = tm * c.q; r.max = tx * c.q;
+            r.mean = (static_cast<double>(k0) + my) * c.q; r.std = sqrt(var) * c.q;
+            r.min = static_cast<double>(k0 + tm) * c.q; r.max = static_cast<double>(k0 + tx) * c.q;
         } else {
             r.mean = r.std = r.min = r.max = __builtin_nan("");
         }

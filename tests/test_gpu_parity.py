@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import oracle
+import segstat_exact
 from golden_util import case_ids, cases, input_counts, input_pa, npz, offgrid_cases, offgrid_npz
 from pypore_amd import synth
 
@@ -589,16 +590,12 @@ def test_randomised_event_batches_fp32_int16_odd_offsets(seed, ctx):
             b = b.cpu().numpy()
             for e, ref in enumerate(refs):
                 np.testing.assert_array_equal(b[boff[e]:boff[e + 1]], ref)
-            if st is not None:                           # per-segment statistics (K2 from the K0 digest) against numpy
+            if st is not None:                           # per-segment statistics against the exact integer statistics
                 st = st.cpu().numpy()
                 for e, (k, ref) in enumerate(zip(evs, refs)):
-                    edges = [0] + list(ref) + [len(k)]
-                    for i, (a0, b0) in enumerate(zip(edges, edges[1:])):
-                        seg = k[a0:b0].astype(np.float64) * synth.QUANTUM
-                        got = st[boff[e] + e + i]
-                        assert got[2] == seg.min() and got[3] == seg.max()
-                        np.testing.assert_allclose(got[0], seg.mean(), rtol=1e-5, atol=1e-12)
-                        np.testing.assert_allclose(got[1], seg.std(), rtol=1e-5, atol=1e-9)
+                    r = segstat_exact.ranges_of([0] + list(ref) + [len(k)])
+                    segstat_exact.assert_rows(st[boff[e] + e:boff[e + 1] + e + 1], segstat_exact.Exact(k, r, synth.QUANTUM),
+                                              (int(k[0]), int(k[0])), "seed %d, event %d" % (seed, e))
     finally:
         ctx.set_option("mode", int(os.environ.get("PORESEG_MODE", "0")))      # (what the context started with: tools/gpu_validate.sh)
 
@@ -904,6 +901,8 @@ def test_events_at_odd_sample_offsets_take_k0s_fast_route_correctly(ctx, dtype, 
     lens = np.array([290_001, 340_000, 333_333, 480_000], dtype=np.int64)
     refs = [oracle.parse(x[a:a + l], **kw) for a, l in zip(starts, lens)]
     ref_stats = [oracle.segment_stats(x[a:a + l], r) for (a, l), r in zip(zip(starts, lens), refs)]
+    host = t.cpu().numpy()
+    exact_counts = [segstat_exact.counts_of(host[a:a + l], synth.QUANTUM) for a, l in zip(starts, lens)]
     ctx.set_option("wide_bs", 1)
     try:
         for unaligned in (1, 0):
@@ -916,6 +915,9 @@ def test_events_at_odd_sample_offsets_take_k0s_fast_route_correctly(ctx, dtype, 
                 got = st[off[e] + e:off[e + 1] + e + 1]
                 np.testing.assert_allclose(got[:, 0], ref_stats[e][:, 0], rtol=1e-5)
                 np.testing.assert_allclose(got[:, 1], ref_stats[e][:, 1], rtol=1e-5, atol=1e-9)
+                k = exact_counts[e]
+                segstat_exact.assert_rows(got, segstat_exact.Exact(k, segstat_exact.ranges_of([0] + list(r) + [len(k)]), synth.QUANTUM),
+                                          (int(k[0]), int(k[0])), "event %d, unaligned loads %d" % (e, unaligned))
     finally:
         ctx.set_option("k0_unaligned", 1)
         ctx.set_option("k0_waves", int(os.environ.get("PORESEG_K0_WAVES", "0")))
