@@ -209,29 +209,7 @@ class Event(Segment):
         return segments
 
     def _parse_filtered(self, parser):
-        mode = parser.off_grid if isinstance(parser, SpeedyStatSplit) else None
-        if mode == "exact":
-            # the reference's own arithmetic on the float64 current itself (ps_segment_exact_f64): nothing is rounded
-            self.near_ties = None
-            return self._adopt_filtered(parser.parse_exact(np.asarray(self.current, dtype=np.float64)))
-        rounded, _, centre = self._on_fine_grid()
-        if isinstance(parser, SpeedyStatSplit):
-            # (the level goes along: the device judges near ties against the noise of the reference's cumsums, which run on
-            #  the uncentred current -- include/poreseg.h, ps_sample_format)
-            import warnings
-            from . import engine
-            with warnings.catch_warnings():
-                if mode == "exact_on_near_tie":
-                    warnings.simplefilter("ignore", engine.NearTieWarning)      # (acted upon right here, from the sites)
-                nt, fl = [], []
-                segs = parser.parse_batch([rounded], [centre], near_ties_out=nt, flagged_out=fl)[0]
-            self.near_ties = nt[0]
-            # exact_on_near_tie: the exact route when the call logged a near tie for it (speculative scans included), or when
-            # the sites were not counted (LDS-window kernels: option scan_bs 0, min_width < 8; the log off or overflowed)
-            if mode == "exact_on_near_tie" and fl[0]:
-                segs = parser.parse_exact(np.asarray(self.current, dtype=np.float64))
-            return self._adopt_filtered(segs)
-        return self._adopt_filtered(parser.parse(rounded))
+        return _segment_filtered([self], parser)[0]
 
     # ---- persistence ----------------------------------------------------------------------------------------
     def to_dict(self):
@@ -277,6 +255,45 @@ class Event(Segment):
         mean = sum(seg.mean * seg.duration for seg in segments) / dur
         std = float(np.sqrt(sum(seg.std ** 2 * seg.duration for seg in segments) / dur))
         return MetaEvent(start=0, duration=dur, mean=mean, std=std, n=len(segments), segments=segments, filtered=False)
+
+
+def _segment_filtered(events, parser):
+    """Segments of already-filtered events (float64 currents on no ADC grid) with `parser`, in event order.  Every current
+    is centred and rounded onto a fine grid (Event._on_fine_grid), and the events that share a grid step are segmented
+    together.  A SpeedyStatSplit also gets the unrounded currents, for its off_grid policy (cparsers.FastStatSplit.
+    _fast_or_exact), and sets each event's near_ties; when that policy makes no fast call nothing is rounded and all
+    events go to its exact route in one call.  Any other parser gets the rounded currents.  The segments hold views of the unrounded
+    currents and take their statistics from those (Event._adopt_filtered)."""
+    if not events:
+        return []
+    ours = isinstance(parser, SpeedyStatSplit)
+    values = [np.asarray(ev.current, dtype=np.float64) for ev in events] if ours else None
+    if ours and not parser._fast()._fast_call:
+        for ev in events:
+            ev.near_ties = None
+        return [ev._adopt_filtered(segs) for ev, segs in zip(events, parser._fast().parse_exact_batch(values))]
+    by_step = {}
+    for k, ev in enumerate(events):
+        rounded, step, centre = ev._on_fine_grid()
+        by_step.setdefault(step, []).append((k, rounded, centre))
+    found = [None] * len(events)
+    for group in by_step.values():
+        ks = [k for k, _, _ in group]
+        currents = [r for _, r, _ in group]
+        if ours:
+            # (the level goes along: the device judges near ties against the noise of the reference's cumsums, which run on
+            #  the uncentred current -- include/poreseg.h, ps_sample_format)
+            nt = []
+            segs = parser.parse_batch(currents, [c for _, _, c in group], near_ties_out=nt, exact_from=[values[k] for k in ks])
+            for k, sites in zip(ks, nt):
+                events[k].near_ties = sites
+        elif hasattr(parser, "parse_batch"):
+            segs = parser.parse_batch(currents)          # a user's parser with the one-argument parse_batch of earlier rounds
+        else:
+            segs = [parser.parse(c) for c in currents]
+        for k, sg in zip(ks, segs):
+            found[k] = events[k]._adopt_filtered(sg)
+    return found
 
 
 class File(Segment):
@@ -367,42 +384,9 @@ class File(Segment):
             results[i] = segs
         for i, sites in zip(plain_idx, nt):
             self.events[i].near_ties = sites
-        by_step = {}
-        mode = parser.off_grid if ours else None
-        for i, ev in enumerate(self.events):
-            if ev.__dict__.get("filtered"):
-                if mode == "exact":                      # (the reference's arithmetic on every event: Event._parse_filtered)
-                    results[i] = ev._parse_filtered(parser)
-                    continue
-                rounded, step, centre = ev._on_fine_grid()
-                by_step.setdefault(step, []).append((i, rounded, centre))
-        for group in by_step.values():
-            currents = [r for _, r, _ in group]
-            if ours:
-                import warnings
-                from . import engine
-                nt, fl = [], []
-                with warnings.catch_warnings():
-                    if mode == "exact_on_near_tie":
-                        warnings.simplefilter("ignore", engine.NearTieWarning)      # (acted upon right here, per event)
-                    found = parser.parse_batch(currents, [c for _, _, c in group], near_ties_out=nt, flagged_out=fl)
-                for (i, _, _), sites in zip(group, nt):
-                    self.events[i].near_ties = sites
-                if mode == "exact_on_near_tie":
-                    # only the events whose call logged a near tie for them (all of them when the sites were not counted) take
-                    # the exact route, in one ps_segment_exact_f64 call for the group
-                    redo = [k for k, f in enumerate(fl) if f]
-                    if redo:
-                        exact = parser._fast().parse_exact_batch(
-                            [np.asarray(self.events[group[k][0]].current, dtype=np.float64) for k in redo])
-                        for k, segs in zip(redo, exact):
-                            found[k] = segs
-            elif batched:
-                found = parser.parse_batch(currents)     # a user's parser with the one-argument parse_batch of earlier rounds
-            else:
-                found = [parser.parse(c) for c in currents]
-            for (i, _, _), segs in zip(group, found):
-                results[i] = self.events[i]._adopt_filtered(segs)
+        filtered_idx = [i for i, ev in enumerate(self.events) if ev.__dict__.get("filtered")]
+        for i, segs in zip(filtered_idx, _segment_filtered([self.events[i] for i in filtered_idx], parser)):
+            results[i] = segs
         for ev, segs in zip(self.events, results):
             ev.segments = segs
             for segment in segs:

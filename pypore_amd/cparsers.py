@@ -57,19 +57,23 @@ class FastStatSplit(object):
         duration in samples), exactly like the reference."""
         return self.parse_batch([current])[0]
 
-    def parse_batch(self, currents, levels=None, near_ties_out=None, flagged_out=None):
+    def parse_batch(self, currents, levels=None, near_ties_out=None, exact_from=None):
         """One device call for many independent events (one reference parse() per event).  Events that reach the
         device in different representations (float32 pA / int16 counts, or int16 on different scales) go in one call
-        per representation.  levels: per event, the level in pA that was subtracted from it upstream (a filtered event
+        per representation; float input on no ADC grid goes one event at a time, under the off_grid policy
+        (_fast_or_exact).  levels: per event, the level in pA that was subtracted from it upstream (a filtered event
         that Event.parse centred and rounded): passed on as offset_counts, see include/poreseg.h.
-        near_ties_out / flagged_out (lists, optional): per event its near-tie sites in the final recursion,
-        [(window_start, window_end, split)] in samples, or None when they were not counted (Event.near_ties); and whether
-        the exact route should redo it -- any record of its call's log for it, speculative scans included, or not counted."""
+        exact_from (list, optional): per event the float64 current the reference would see, when the caller rounded an
+        off-grid current onto a grid itself (Event.parse of a filtered event): the off_grid policy then applies to these
+        events too.  Without it, input on a grid is segmented as it is (no redo, NearTieWarning on).
+        near_ties_out (list, optional): per event its near-tie sites, [(window_start, window_end, split)] in samples, or
+        None when they were not counted (Event.near_ties)."""
         ctx = engine.context(self.device)
         import torch
         out = [None] * len(currents)
         near_ties = [None] * len(currents)
-        flagged = [True] * len(currents)
+        want_sites = near_ties_out is not None
+        off_grid_ok = self.off_grid != "raise" and self.quantum is None      # (else float input on no grid raises ValueError)
 
         def upload(idx, full_detect):
             parts = [engine.to_device(currents[i], self.quantum, self.offset, self.device, full_detect) for i in idx]
@@ -78,12 +82,10 @@ class FastStatSplit(object):
                 q = min(p.quantum for p in parts)
             return parts, q
 
-        def requantised(i):
-            """off_grid="requantise": float input that lies on no ADC grid (the reference takes any float64 buffer,
-            cparsers.pyx:53,103-111 -- filtered or resampled on the host, np.random.normal test data) is centred and
-            rounded on the device to the finest power-of-two grid that keeps its counts below 2**22 (ps_requantise, what
-            Event.parse does for a filtered event) and segmented on the 64-bit digest.  The segments hold views of the
-            ORIGINAL values and take their statistics from those."""
+        def off_grid_route(i):
+            """Float input on no ADC grid (the reference takes any float64 buffer, cparsers.pyx:53): the fast route
+            re-quantises it on the device (ps_requantise, 2**22 counts at most) for the 64-bit digest.  The segments hold
+            views of the ORIGINAL values and take their statistics from those."""
             cur = np.ascontiguousarray(currents[i], dtype=np.float64)
             if cur.ndim != 1:
                 raise ValueError("Buffer has wrong number of dimensions (expected 1, got %d)" % cur.ndim)
@@ -91,39 +93,26 @@ class FastStatSplit(object):
             if n == 0:
                 out[i] = [Segment(current=currents[i][0:0], start=0, duration=0, end=0)]
                 return
-            dev = torch.device("cuda", torch.cuda.current_device() if self.device is None else int(self.device))
-            z, centre, step = ctx.requantise(torch.from_numpy(cur).to(dev))
-            # (the level that was subtracted, as offset_counts: the device judges near ties against the noise of the reference's
-            #  cumsums, which run on the uncentred values -- include/poreseg.h)
-            bounds, boff, _ = ctx.segment_batch(z, np.array([0, n], dtype=np.int64), self._params, step, want_stats=False,
-                                                offset_counts=_dc_counts(centre, step))
-            edges = np.concatenate(([0], bounds.cpu().numpy(), [n])).tolist()
+
+            def fast(warn):
+                dev = torch.device("cuda", torch.cuda.current_device() if self.device is None else int(self.device))
+                z, centre, step = ctx.requantise(torch.from_numpy(cur).to(dev))
+                # (the level that was subtracted, as offset_counts: the device judges near ties against the noise of the
+                #  reference's cumsums, which run on the uncentred values -- include/poreseg.h)
+                return ctx.segment_batch(z, np.array([0, n], dtype=np.int64), self._params, step, want_stats=False,
+                                         offset_counts=_dc_counts(centre, step), near_tie_warning=warn)
+
+            exact = cur if exact_from is None else exact_from[i]
+            (b,), (near_ties[i],), _ = self._fast_or_exact(fast, [n], lambda ks: [exact], want_sites)
+            edges = np.concatenate(([0], b, [n])).tolist()
             src = currents[i]
             out[i] = [Segment(current=src[a:z_], start=a, duration=z_ - a, end=z_) for a, z_ in zip(edges, edges[1:])]
-
-        def exact(i):
-            """off_grid="exact": the reference's own prefix sums and expressions on the device (ps_segment_exact_f64)."""
-            segs = self.parse_exact_batch([currents[i]])[0]
-            out[i] = segs
-
-        def off_grid_route(i):
-            if self.off_grid == "exact":
-                exact(i)
-            elif self.off_grid == "exact_on_near_tie":
-                import warnings
-                with warnings.catch_warnings():
-                    warnings.simplefilter("ignore", engine.NearTieWarning)      # (acted upon right here)
-                    requantised(i)
-                if ctx.near_ties():
-                    exact(i)
-            else:
-                requantised(i)
 
         def run(idx, full_detect=False):
             try:
                 parts, q = upload(idx, full_detect)
             except ValueError:
-                if self.off_grid == "raise" or self.quantum is not None:
+                if not off_grid_ok:
                     raise
                 if len(idx) > 1:                    # find the event(s) without a grid
                     for i in idx:
@@ -140,15 +129,18 @@ class FastStatSplit(object):
                 q = parts[0].quantum
             lens = np.array([p.tensor.numel() for p in parts], dtype=np.int64)
             ev_off = np.concatenate(([0], np.cumsum(lens)))
+            exact = None if exact_from is None else (lambda ks: [exact_from[idx[k]] for k in ks])
             try:
                 samples = parts[0].tensor if len(parts) == 1 else torch.cat([p.tensor for p in parts])
                 dc = 0
                 if levels is not None and samples.dtype == torch.float32:
                     dc = _dc_counts(max((levels[i] or 0.0 for i in idx), key=abs), q)
-                bounds, boff, stats = ctx.segment_batch(samples, ev_off, self._params, q, offset_counts=dc)
+                bounds, sites, rows = self._fast_or_exact(
+                    lambda warn: ctx.segment_batch(samples, ev_off, self._params, q, offset_counts=dc, near_tie_warning=warn),
+                    lens, exact, want_sites)
             except ValueError:
                 if self.quantum is not None or full_detect:
-                    if self.off_grid != "raise" and self.quantum is None and len(idx) == 1:
+                    if off_grid_ok and len(idx) == 1:
                         off_grid_route(idx[0])
                         return
                     raise
@@ -157,22 +149,12 @@ class FastStatSplit(object):
                 # then resolve to different representations are split again
                 run(idx, True)
                 return
-            b = bounds.cpu().numpy()
-            st = stats.cpu().numpy()
-            if near_ties_out is not None or flagged_out is not None:
-                raw = ctx.near_tie_sites()                  # (of this call: one per representation)
-                sites = engine.consistent_sites(raw, b, boff, lens, self._params.window_width)
-                for e, i in enumerate(idx):
-                    if sites is not None:
-                        near_ties[i] = [(int(w0), int(w1), int(sp)) for _, w0, w1, sp in sites[sites["event"] == e].tolist()]
-                        flagged[i] = bool(np.any(raw["event"] == e))
             for e, i in enumerate(idx):
-                cur, n = currents[i], int(lens[e])
-                rows = st[boff[e] + e: boff[e + 1] + e + 1]
-                if parts[e].offset:                 # device statistics are those of count * quantum
-                    rows = rows + np.array([parts[e].offset, 0.0, parts[e].offset, parts[e].offset])
-                edges = np.concatenate(([0], b[boff[e]:boff[e + 1]], [n])).tolist()
-                out[i] = segments_from_edges(cur, edges, rows)
+                near_ties[i], r = sites[e], rows[e]
+                if r is not None and parts[e].offset:          # device statistics are those of count * quantum
+                    r = r + np.array([parts[e].offset, 0.0, parts[e].offset, parts[e].offset])
+                edges = np.concatenate(([0], bounds[e], [int(lens[e])])).tolist()
+                out[i] = segments_from_edges(currents[i], edges, r)
 
         # group the events by the representation they will have on the device
         from .grid import grid_of
@@ -184,50 +166,85 @@ class FastStatSplit(object):
             run(idx)
         if near_ties_out is not None:
             near_ties_out[:] = near_ties
-        if flagged_out is not None:
-            flagged_out[:] = flagged
         return out
+
+    @property
+    def _fast_call(self):
+        """Whether the off_grid policy makes a fast call at all (else a caller need not round its input for one)."""
+        return self.off_grid != "exact"
+
+    def _fast_or_exact(self, fast, lens, exact, want_sites=True):
+        """The off_grid policy, for every route that segments input on no ADC grid.  fast(near_tie_warning) makes ONE
+        segment call on the events' fast-route input (what Context.segment_batch returns); lens: the events' lengths;
+        exact(ks): the float64 currents the reference would see for the events ks -- None for input on a grid of its own
+        (no policy).  "exact": no fast call, one exact call for all events.  Otherwise the fast call, with its warning
+        except under "exact_on_near_tie": there the events with a record in the call's near-tie log (all of them when it
+        did not count) get one exact call that replaces their boundaries.  Returns per event its boundaries, its near-tie
+        sites (None: not counted, or not wanted) and its statistics rows (None: none computed, or the exact route's)."""
+        n_ev = len(lens)
+        if exact is not None and not self._fast_call:
+            return self._exact_bounds(exact(list(range(n_ev)))), [None] * n_ev, [None] * n_ev
+        redo_here = exact is not None and self.off_grid == "exact_on_near_tie"
+        bounds, boff, stats = fast(not redo_here)
+        b = bounds.cpu().numpy()
+        st = None if stats is None else stats.cpu().numpy()
+        per_event = [b[boff[e]:boff[e + 1]] for e in range(n_ev)]
+        rows = [None if st is None else st[boff[e] + e:boff[e + 1] + e + 1] for e in range(n_ev)]
+        near = [None] * n_ev
+        if want_sites or redo_here:
+            raw = engine.context(self.device).near_tie_sites()      # (of this call)
+            sites = engine.consistent_sites(raw, b, boff, lens, self._params.window_width) if want_sites else None
+            if sites is not None:
+                near = [[(int(w0), int(w1), int(sp)) for _, w0, w1, sp in sites[sites["event"] == e].tolist()]
+                        for e in range(n_ev)]
+            if redo_here:
+                redo = engine.events_to_redo(raw, n_ev)
+                if redo:
+                    for e, eb in zip(redo, self._exact_bounds(exact(redo))):
+                        per_event[e], rows[e] = eb, None
+        return per_event, near, rows
+
+    def _exact_bounds(self, currents):
+        """The exact route (ps_segment_exact_f64, include/poreseg.h) for float64 currents -- numpy arrays, or float64
+        tensors on the device -- in ONE call: per current its boundaries (int32 numpy)."""
+        import torch
+        ctx = engine.context(self.device)
+        ts = []
+        for cur in currents:
+            if isinstance(cur, torch.Tensor):
+                ts.append(cur.contiguous())
+                continue
+            a = np.ascontiguousarray(np.asarray(cur), dtype=np.float64)
+            if a.ndim != 1:
+                raise ValueError("Buffer has wrong number of dimensions (expected 1, got %d)" % a.ndim)
+            ts.append(torch.from_numpy(a).to(torch.device("cuda", ctx.device)))
+        lens = np.array([t.numel() for t in ts], dtype=np.int64)
+        if not lens.sum():                          # (nothing to segment: no call)
+            return [np.zeros(0, dtype=np.int32) for _ in ts]
+        allt = ts[0] if len(ts) == 1 else torch.cat(ts)
+        bounds, boff = ctx.segment_exact_f64(allt, np.concatenate(([0], np.cumsum(lens)))[:-1], lens, self._params)
+        b = bounds.cpu().numpy()
+        return [b[boff[e]:boff[e + 1]] for e in range(len(ts))]
 
     def parse_exact_batch(self, currents):
         """The exact route (ps_segment_exact_f64, include/poreseg.h) for a list of float64 currents (numpy arrays, or float64
         CUDA tensors): the reference's boundaries on the same values by construction.  Returns one list of Segments per
         current (views of the caller's arrays; of a tensor: stretches of its host copy), start / end in samples."""
         import torch
-        ctx = engine.context(self.device)
-        dev = torch.device("cuda", ctx.device)
-        tensors, hosts = [], []
-        for cur in currents:
-            if isinstance(cur, torch.Tensor):
-                t = cur.to(dev, torch.float64).contiguous()
-                hosts.append(None)
-            else:
-                a = np.ascontiguousarray(np.asarray(cur), dtype=np.float64)
-                if a.ndim != 1:
-                    raise ValueError("Buffer has wrong number of dimensions (expected 1, got %d)" % a.ndim)
-                t = torch.from_numpy(a).to(dev)
-                hosts.append(cur)
-            tensors.append(t)
-        lens = np.array([t.numel() for t in tensors], dtype=np.int64)
-        starts = np.concatenate(([0], np.cumsum(lens)))[:-1]
+        dev = torch.device("cuda", engine.context(self.device).device)
+        ins = [cur.to(dev, torch.float64) if isinstance(cur, torch.Tensor) else cur for cur in currents]
         out = []
-        if len(tensors) == 0:
-            return out
-        allt = tensors[0] if len(tensors) == 1 else torch.cat(tensors)
-        if allt.numel() == 0:
-            return [[Segment(current=(h if h is not None else np.zeros(0))[0:0], start=0, duration=0, end=0)] for h in hosts]
-        bounds, boff = ctx.segment_exact_f64(allt, starts, lens, self._params)
-        b = bounds.cpu().numpy()
-        for e, (t, h) in enumerate(zip(tensors, hosts)):
-            n = int(lens[e])
-            src = h if h is not None else t.cpu().numpy()
-            edges = np.concatenate(([0], b[boff[e]:boff[e + 1]], [n])).tolist()
+        for cur, b in zip(ins, self._exact_bounds(ins)):
+            src = cur.cpu().numpy() if isinstance(cur, torch.Tensor) else cur
+            edges = np.concatenate(([0], b, [len(src)])).tolist()
             out.append([Segment(current=src[a:z_], start=a, duration=z_ - a, end=z_) for a, z_ in zip(edges, edges[1:])])
         return out
 
     def parse_filtered_batch(self, currents, order=1, cutoff=2000., sampling_freq=1.e5, near_ties_out=None):
         """Event.filter + Event.parse for many events without leaving the device in between (the inner loop of
         Experiment.parse, DataTypes.py:975-984): every current is filtered (ps_filter_bessel), re-quantised on the
-        device (ps_requantise) and the events that share a grid step are segmented in one ps_segment_batch.  Returns
+        device (ps_requantise) and the events that share a grid step are segmented together, one call of the off_grid
+        policy per step (_fast_or_exact: one ps_segment_batch, and the exact route where the policy says).  Returns
         [(filtered float64 current, [Segment...])] in input order, start / end in samples.  The filtered current --
         Event.current afterwards -- stays on the device until it is read (grid.Deferred: the copy of 8 B per sample
         was 0.08 s of an 0.21 s Experiment.parse); the segments hold stretches of it."""
@@ -301,52 +318,26 @@ class FastStatSplit(object):
         # near_ties_out (a list, optional): per input the near-tie sites of its segmentation, [(window_start, window_end, split)]
         # in samples of the event, or None (not counted, the log overflowed, or off_grid="exact") -- Event.near_ties
         near_ties = [None] * len(currents)
-
-        def exact_bounds(idx, lens):
-            """the reference's own arithmetic on the filtered currents THE USER SEES (the file's offset put back, as
-            Event.current has it): one ps_segment_exact_f64 for the group"""
-            ys = [filtered[i].tensor + filtered[i].offset if filtered[i].offset else filtered[i].tensor for i in idx]
-            allt = ys[0].contiguous() if len(ys) == 1 else torch.cat(ys)
-            starts = np.concatenate(([0], np.cumsum(lens)))[:-1]
-            bounds, boff = ctx.segment_exact_f64(allt, starts, lens, self._params)
-            return bounds.cpu().numpy(), boff
-
         for step, idx in by_step.items():
             lens = np.array([onto_grid[i].numel() for i in idx], dtype=np.int64)
-            ev_off = np.concatenate(([0], np.cumsum(lens)))
-            if self.off_grid == "exact":
-                b, boff = exact_bounds(idx, lens)
-            else:
-                import warnings
+
+            def fast(warn):
                 samples = onto_grid[idx[0]] if len(idx) == 1 else torch.cat([onto_grid[i] for i in idx])
-                with warnings.catch_warnings():
-                    if self.off_grid == "exact_on_near_tie":
-                        warnings.simplefilter("ignore", engine.NearTieWarning)
-                    # (one level for the call: the largest of its events' -- the larger the level, the larger the reference's noise)
-                    bounds, boff, _ = ctx.segment_batch(samples, ev_off, self._params, step, want_stats=False,
-                                                        offset_counts=_dc_counts(max((levels[i] for i in idx), key=abs), step))
-                b = bounds.cpu().numpy()
-            per_event = [b[boff[e]:boff[e + 1]] for e in range(len(idx))]
-            if self.off_grid != "exact":
-                # the device's near-tie sites of this call (None: not counted / incomplete); Event.near_ties gets those of the
-                # final recursion
-                raw = ctx.near_tie_sites()
-                sites = engine.consistent_sites(raw, b, boff, lens, self._params.window_width)
-                for e, i in enumerate(idx):
-                    near_ties[i] = None if sites is None else \
-                        [(int(w0), int(w1), int(sp)) for _, w0, w1, sp in sites[sites["event"] == e].tolist()]
-                if self.off_grid == "exact_on_near_tie":
-                    # the events with any record -- speculative scans included, the superset that counters[11] counts -- and all
-                    # of them when the sites are not counted
-                    redo = engine.events_to_redo(raw, len(idx))
-                    if redo:
-                        rb, rboff = exact_bounds([idx[e] for e in redo], lens[redo])
-                        for k, e in enumerate(redo):
-                            per_event[e] = rb[rboff[k]:rboff[k + 1]]
+                # (one level for the call: the largest of its events' -- the larger the level, the larger the reference's noise)
+                return ctx.segment_batch(samples, np.concatenate(([0], np.cumsum(lens))), self._params, step, want_stats=False,
+                                         offset_counts=_dc_counts(max((levels[i] for i in idx), key=abs), step),
+                                         near_tie_warning=warn)
+
+            def exact(ks):
+                # the filtered currents THE USER SEES: the file's offset put back, as Event.current has it
+                return [filtered[idx[k]].tensor + filtered[idx[k]].offset if filtered[idx[k]].offset else filtered[idx[k]].tensor
+                        for k in ks]
+
+            bounds, sites, _ = self._fast_or_exact(fast, lens, exact)
             for e, i in enumerate(idx):
-                cur = filtered[i]
-                edges = np.concatenate(([0], per_event[e], [int(lens[e])])).tolist()
-                out[i] = (cur, segments_from_edges(cur, edges))
+                near_ties[i] = sites[e]
+                edges = np.concatenate(([0], bounds[e], [int(lens[e])])).tolist()
+                out[i] = (filtered[i], segments_from_edges(filtered[i], edges))
         if near_ties_out is not None:
             near_ties_out[:] = near_ties
         return out

@@ -172,12 +172,13 @@ class Context(object):
     # ---- the hot path ---------------------------------------------------------------------------
     @_serialised
     def segment_batch(self, samples, ev_off, params, quantum, offset_counts=0, want_stats=True, cap=None,
-                      want_spine=False, lead=0, out=None):
+                      want_spine=False, lead=0, out=None, near_tie_warning=True):
         """ps_segment_batch on device-resident `samples` (torch float32 or int16 CUDA tensor).
         Returns (bounds int32 CUDA tensor [total], bounds_off int64 numpy [n_ev+1],
         stats float64 CUDA tensor [total+n_ev, 4] or None).  lead > 0: the boundaries are a view that starts `lead`
         elements into their buffer (dist.BoundaryGather puts its header there and sends the buffer as it is).
-        out: int32 CUDA tensor to receive the boundaries (its size is the capacity; ValueError if they do not fit)."""
+        out: int32 CUDA tensor to receive the boundaries (its size is the capacity; ValueError if they do not fit).
+        near_tie_warning=False: no NearTieWarning from this call (its caller acts on the near ties itself)."""
         assert samples.is_cuda and samples.is_contiguous() and samples.dim() == 1
         if samples.dtype == torch.float32:
             dtype = _lib.PS_DTYPE_F32
@@ -209,7 +210,7 @@ class Context(object):
                                         ctypes.c_void_p(stats.data_ptr()) if want_stats else None,
                                         ctypes.c_void_p(spine.data_ptr()) if want_spine else None)
         _lib.check(rc, self.handle)
-        if NEAR_TIE_WARNING:
+        if NEAR_TIE_WARNING and near_tie_warning:
             nt = self.near_ties()
             if nt > 0:
                 import warnings

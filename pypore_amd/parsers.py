@@ -152,11 +152,11 @@ class SpeedyStatSplit(parser):
     def parse(self, current):
         return self._fast().parse(current)
 
-    def parse_batch(self, currents, levels=None, near_ties_out=None, flagged_out=None):
+    def parse_batch(self, currents, levels=None, near_ties_out=None, exact_from=None):
         """All events of a file in one device call (extension; same result as [parse(c) for c in currents]).  levels: the
         level in pA that was subtracted from each event upstream (Event.parse of a filtered event), or None.
-        near_ties_out / flagged_out: see cparsers.FastStatSplit.parse_batch."""
-        return self._fast().parse_batch(currents, levels, near_ties_out=near_ties_out, flagged_out=flagged_out)
+        near_ties_out / exact_from: see cparsers.FastStatSplit.parse_batch."""
+        return self._fast().parse_batch(currents, levels, near_ties_out=near_ties_out, exact_from=exact_from)
 
     def parse_exact(self, current):
         """The exact route for one float64 current (extension; cparsers.FastStatSplit.parse_exact_batch)."""

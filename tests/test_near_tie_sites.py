@@ -78,9 +78,9 @@ def test_redo_selection():
     assert engine.events_to_redo(None, 3) == [0, 1, 2]
 
 
-def test_redo_selection_in_parse_filtered_batch_with_a_stub_context(monkeypatch):
+def test_redo_selection_and_warning_flag_in_parse_filtered_batch_with_a_stub_context(monkeypatch):
     """parse_filtered_batch sends only the flagged events to the exact route; None sends the whole group; the
-    NEAR_TIE_WARNING switch plays no part."""
+    NEAR_TIE_WARNING switch plays no part; the fast call it acts on is made with segment_batch(near_tie_warning=False)."""
     import torch
     from pypore_amd import cparsers
     from pypore_amd.grid import Deferred
@@ -89,7 +89,7 @@ def test_redo_selection_in_parse_filtered_batch_with_a_stub_context(monkeypatch)
 
     class Ctx:
         def __init__(self, sites):
-            self.sites, self.exact = sites, []
+            self.sites, self.exact, self.warn = sites, [], []
 
         def filter_bessel(self, t, q, cutoff, sampling_freq, order):
             return t.double() * q
@@ -97,7 +97,8 @@ def test_redo_selection_in_parse_filtered_batch_with_a_stub_context(monkeypatch)
         def requantise(self, y):
             return y.float(), 0.0, 1.0
 
-        def segment_batch(self, samples, ev_off, params, step, want_stats=False, offset_counts=0):
+        def segment_batch(self, samples, ev_off, params, step, want_stats=False, offset_counts=0, near_tie_warning=True):
+            self.warn.append(near_tie_warning)
             n_ev = len(ev_off) - 1
             return torch.tensor([300] * n_ev, dtype=torch.int32), np.arange(n_ev + 1, dtype=np.int64), None
 
@@ -134,11 +135,215 @@ def test_redo_selection_in_parse_filtered_batch_with_a_stub_context(monkeypatch)
             nt = []
             out = fs.parse_filtered_batch(currents, near_ties_out=nt)
             assert c.exact == n_exact
+            assert c.warn == [False]                   # (the result is acted upon: no NearTieWarning from the fast call)
             assert [edges[1] for _, edges in out] == firsts
             if sites is None:
                 assert nt == [None] * 3
             else:
                 assert nt == [[(0, 700, 300)] if e in sites["event"].tolist() else [] for e in range(3)]
+
+
+class _StubCtx:
+    """A context that records the calls the policy makes: segment_batch returns one boundary at 300, the exact route one at
+    100 per event."""
+    device = 0
+
+    def __init__(self, sites):
+        self.sites, self.calls = sites, []
+
+    def requantise(self, y):
+        self.calls.append(("requantise", int(y.numel())))
+        return y.float(), 0.0, 1.0
+
+    def segment_batch(self, samples, ev_off, params, q, want_stats=True, offset_counts=0, near_tie_warning=True):
+        import torch
+        n_ev = len(ev_off) - 1
+        self.calls.append(("batch", n_ev, near_tie_warning))
+        stats = torch.zeros((2 * n_ev, 4), dtype=torch.float64) if want_stats else None
+        return torch.tensor([300] * n_ev, dtype=torch.int32), np.arange(n_ev + 1, dtype=np.int64), stats
+
+    def near_tie_sites(self):
+        self.calls.append(("sites",))
+        return self.sites
+
+    def segment_exact_f64(self, allt, starts, lens, params):
+        import torch
+        self.calls.append(("exact", [int(n) for n in lens]))
+        return torch.tensor([100] * len(lens), dtype=torch.int32), np.arange(len(lens) + 1, dtype=np.int64)
+
+
+def _use(monkeypatch, c):
+    from pypore_amd import cparsers
+    monkeypatch.setattr(cparsers.engine, "context", lambda device=None: c)
+
+
+def test_parse_batch_with_exact_from_under_every_mode(monkeypatch):
+    """parse_batch(rounded, levels, exact_from=...): the off_grid policy applies to events the caller rounded itself --
+    which calls it makes, with which warning flag, on which events, and the sites it reports."""
+    import torch
+    import warnings
+    from pypore_amd import cparsers
+    lens = [900, 700, 800]
+    rounded = [np.full(n, 100.0 + 0.125 * k) for k, n in enumerate(lens)]
+    exact_from = [torch.from_numpy(r + 1e-7) for r in rounded]
+
+    class Samples:
+        offset = 0.0
+
+    def to_device(cur, quantum, offset, device, full_detect=False):
+        s = Samples()
+        s.tensor, s.quantum = torch.from_numpy(np.asarray(cur, dtype=np.float32)), 0.125
+        return s
+
+    monkeypatch.setattr(cparsers.engine, "to_device", to_device)
+    one = _sites([(1, 0, 700, 300)])
+    fast_sites = [[], [(0, 700, 300)], []]
+    expect = {   # mode -> (calls, first boundary per event, near_ties)
+        "raise": ([("batch", 3, True), ("sites",)], [300, 300, 300], fast_sites),
+        "requantise": ([("batch", 3, True), ("sites",)], [300, 300, 300], fast_sites),
+        "exact": ([("exact", lens)], [100, 100, 100], [None] * 3),
+        "exact_on_near_tie": ([("batch", 3, False), ("sites",), ("exact", [700])], [300, 100, 300], fast_sites),
+    }
+    for mode, (calls, firsts, near) in expect.items():
+        c = _StubCtx(one)
+        _use(monkeypatch, c)
+        nt = []
+        before, saved = warnings.filters, list(warnings.filters)
+        out = cparsers.FastStatSplit(min_width=50, window_width=1000, off_grid=mode).parse_batch(
+            rounded, [100.0] * 3, near_ties_out=nt, exact_from=exact_from)
+        assert warnings.filters is before and warnings.filters == saved
+        assert c.calls == calls, mode
+        assert [segs[1].start for segs in out] == firsts, mode
+        assert nt == near, mode
+        assert all(segs[0].current.base is r or segs[0].current is r or np.shares_memory(segs[0].current, r)
+                   for segs, r in zip(out, rounded))
+    # sites not counted: the whole call goes to the exact route
+    c = _StubCtx(None)
+    _use(monkeypatch, c)
+    nt = []
+    out = cparsers.FastStatSplit(min_width=50, window_width=1000, off_grid="exact_on_near_tie").parse_batch(
+        rounded, [100.0] * 3, near_ties_out=nt, exact_from=exact_from)
+    assert c.calls == [("batch", 3, False), ("sites",), ("exact", lens)]
+    assert [segs[1].start for segs in out] == [100] * 3 and nt == [None] * 3
+    # without exact_from, input on a grid is segmented as it is, whatever the mode: warning on, no redo, no sites unasked
+    c = _StubCtx(None)
+    _use(monkeypatch, c)
+    out = cparsers.FastStatSplit(min_width=50, window_width=1000, off_grid="exact_on_near_tie").parse_batch(rounded)
+    assert c.calls == [("batch", 3, True)] and [segs[1].start for segs in out] == [300] * 3
+
+
+def test_off_grid_parse_batch_route_under_exact_on_near_tie(monkeypatch):
+    """Float input on no grid: the device requantises it, one fast call without the warning, the sites, and the exact
+    route only when a site was logged or the sites were not counted.  The sites are reported (Event.near_ties); the
+    segments are views of the caller's array."""
+    import torch
+    import warnings
+    from pypore_amd import cparsers
+
+    def off_grid(*a, **kw):
+        raise ValueError("no grid")
+
+    monkeypatch.setattr(cparsers.engine, "to_device", off_grid)
+    cpu = torch.device("cpu")
+    monkeypatch.setattr(torch, "device", lambda *a, **kw: cpu)      # (no GPU here: the stub takes host tensors)
+    x = 100.0 + np.random.default_rng(3).normal(size=900)
+    fs = cparsers.FastStatSplit(min_width=50, window_width=1000, device=0, off_grid="exact_on_near_tie")
+    for sites, exact, first, near in ((None, [("exact", [900])], 100, None),
+                                      (_sites([]), [], 300, []),
+                                      (_sites([(0, 0, 900, 300)]), [("exact", [900])], 100, [(0, 900, 300)])):
+        c = _StubCtx(sites)
+        _use(monkeypatch, c)
+        nt = []
+        before, saved = warnings.filters, list(warnings.filters)
+        segs = fs.parse_batch([x], near_ties_out=nt)[0]
+        assert warnings.filters is before and warnings.filters == saved
+        assert c.calls == [("requantise", 900), ("batch", 1, False), ("sites",)] + exact
+        assert segs[1].start == first and nt == [near]
+        assert np.shares_memory(segs[0].current, x)
+    # "requantise": the warning stays on, and nobody asked for the sites
+    c = _StubCtx(_sites([(0, 0, 900, 300)]))
+    _use(monkeypatch, c)
+    cparsers.FastStatSplit(min_width=50, window_width=1000, device=0, off_grid="requantise").parse(x)
+    assert c.calls == [("requantise", 900), ("batch", 1, True)]
+
+
+def _filtered_events(amplitudes):
+    from pypore_amd.DataTypes import Event, File
+    rng = np.random.default_rng(5)
+    xs = [60.0 + a * np.sin(np.linspace(0, 9, 1500 + 100 * k)) + rng.normal(0, 0.01, 1500 + 100 * k)
+          for k, a in enumerate(amplitudes)]
+    f = File(current=np.concatenate(xs), timestep=0.01)
+    f.events = []
+    for x in xs:
+        ev = Event(current=x, start=0., end=len(x) / f.second, duration=len(x) / f.second, second=f.second, file=f)
+        ev.filtered = True
+        f.events.append(ev)
+    return f
+
+
+@pytest.mark.parametrize("mode", ["raise", "requantise", "exact", "exact_on_near_tie"])
+def test_event_and_file_segment_filtered_events_through_the_same_calls(monkeypatch, mode):
+    """Event._parse_filtered and File._parse_events share one helper: for the same filtered events they make the same
+    parse_batch calls (rounded currents, their levels, the unrounded currents for the exact route) -- one per grid step
+    -- and, when the policy makes no fast call, one exact call with the unrounded currents.  No warning filter is touched."""
+    import warnings
+    from pypore_amd import cparsers
+    from pypore_amd.core import Segment
+    from pypore_amd.parsers import SpeedyStatSplit
+    log = []
+
+    class Spy(SpeedyStatSplit):
+        def parse_batch(self, currents, levels=None, near_ties_out=None, exact_from=None):
+            if len(currents):
+                log.append(("parse_batch", [len(c) for c in currents], [float(v) for v in levels],
+                            [np.asarray(x).tolist() for x in exact_from]))
+            if near_ties_out is not None:
+                near_ties_out[:] = [[(0, len(c), 40)] for c in currents]
+            return [[Segment(current=c[:40], start=0, duration=40, end=40),
+                     Segment(current=c[40:], start=40, duration=len(c) - 40, end=len(c))] for c in currents]
+
+    def exact(self, currents):
+        log.append(("exact", [np.asarray(x).tolist() for x in currents]))
+        return [[Segment(current=c, start=0, duration=len(c), end=len(c))] for c in currents]
+
+    monkeypatch.setattr(cparsers.FastStatSplit, "parse_exact_batch", exact)
+    f = _filtered_events([2.0, 2.0, 30.0])                          # two grid steps
+    steps = {ev._on_fine_grid()[1] for ev in f.events}
+    assert len(steps) == 2
+    parser = Spy(min_width=20, window_width=200, off_grid=mode)
+    before, saved = warnings.filters, list(warnings.filters)
+    one_by_one = []
+    for ev in f.events:
+        log.clear()
+        segs = ev._parse_filtered(parser)
+        one_by_one.append(list(log))
+        assert all(np.shares_memory(s.current, ev.current) for s in segs)
+    log.clear()
+    f._parse_events(parser, None)
+    whole = list(log)
+    assert warnings.filters is before and warnings.filters == saved
+    values = [np.asarray(ev.current, dtype=np.float64).tolist() for ev in f.events]
+    if mode == "exact":
+        assert one_by_one == [[("exact", [v])] for v in values]
+        assert whole == [("exact", values)]                           # one call for the file
+        assert all(ev.near_ties is None for ev in f.events)
+        return
+    for ev, calls in zip(f.events, one_by_one):
+        rounded, _, centre = ev._on_fine_grid()
+        assert calls == [("parse_batch", [len(rounded)], [centre], [np.asarray(ev.current).tolist()])]
+    assert len(whole) == 2                                           # one per grid step, same events, same arguments
+    assert sorted(k for _, lens, _, _ in whole for k in lens) == sorted(len(v) for v in values)
+    merged = {}
+    for _, lens, levels, ex in whole:
+        for n, level, e in zip(lens, levels, ex):
+            merged[tuple(e)] = (n, level)
+    for calls in one_by_one:
+        _, (n,), (level,), (e,) = calls[0]
+        assert merged[tuple(e)] == (n, level)
+    for ev in f.events:
+        assert ev.near_ties == [(0, len(ev.current), 40)]
+        assert [s.start * f.second for s in ev.segments] == [0, 40]
+        assert all(np.shares_memory(s.current, ev.current) for s in ev.segments)
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------
