@@ -353,6 +353,17 @@ int ps_hmm_batch(ps_ctx *ctx, const ps_hmm_model *model, int32_t mode, const dou
                  int32_t n_seq, double *d_logp, double *d_mat, int32_t *d_path, const int64_t *h_path_off,
                  int32_t *d_path_len);
 
+/* E-step of Baum-Welch over a BATCH (sequence q = d_obs[h_off[q] .. h_off[q+1]), fp64, device), summed over the sequences:
+ * d_logp[q] = the sequence's log probability (as PS_HMM_FORWARD); d_counts[e] = the expected count of edge e, e in
+ * out-edge CSR order (n_edges = out_ptr[n_states]; pypore_amd.hmm.Model.edges order); d_stats[3k .. 3k+2] = (W, A, B) of
+ * emitting state k: the sums of the posterior g, g (x - c_k) and g (x - c_k)^2 over the observations, c_k = param[3k].
+ * A sequence with logp = -inf contributes nothing and is counted in *h_skipped.  Forward matrices are kept in HBM for
+ * launches of at most option "hmm_fb_budget" bytes (default 4 GiB; at least one sequence per launch); the accumulators
+ * are per-workgroup rows summed in a fixed order, so the same call with the same options gives the same bits.  Limits as
+ * ps_hmm_batch.  Synchronises the context's stream before returning. */
+int ps_hmm_expect(ps_ctx *ctx, const ps_hmm_model *model, const double *d_obs, const int64_t *h_off, int32_t n_seq,
+                  double *d_logp, double *d_counts, double *d_stats, int32_t *h_skipped);
+
 /* Timing of the most recent ps_segment_batch, measured with HIP events on the context's stream.
  * ms[7] = the call's device work from the first upload to the last result copy (option "timing" >= 1, the
  * default); ms[3] = whole call on the host's wall clock.  With option "timing" = 2 an event is also recorded

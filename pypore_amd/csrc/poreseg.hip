@@ -170,6 +170,10 @@ struct ps_ctx {
     DevBuf hmm_model, hmm_off, hmm_bp, hmm_last, hmm_flags;
     std::vector<char> hmm_blob;
     long long hmm_bp_budget = 512ll << 20;   // option hmm_bp_budget: bytes of Viterbi backpointers per launch
+    // Baum-Welch E-step (ps_hmm_expect): forward matrices of one launch, per-workgroup accumulator rows, the skipped count
+    DevBuf hmm_fmat, hmm_acc, hmm_skip;
+    long long hmm_fb_budget = 4ll << 30;     // option hmm_fb_budget: bytes of forward matrices per launch
+    bool hmm_expect_lds = true;              // option hmm_expect_lds 0: the accumulator rows stay in global memory
     int stitch_host = 0;      // 1: host stitch with halo tiles (the fallback path) always
     DevBuf ev_len, det_counts, det_tics, det_cand;
     DevBuf bridges, bmeta, tile_i32, sp_off, spine_items, asm_hdr, ev_first_tile;
@@ -1311,7 +1315,7 @@ void ps_destroy(ps_ctx *ctx)
                       &ctx->align_in, &ctx->align_scratch, &ctx->bridge_ext, &ctx->ext_slot, &ctx->ext_list,
                       &ctx->lat_state, &ctx->lat_seam, &ctx->lat_res, &ctx->pre_c, &ctx->ev_info_tr, &ctx->blk_cls,
                       &ctx->cls_mm, &ctx->nt_log, &ctx->hmm_model, &ctx->hmm_off, &ctx->hmm_bp,
-                      &ctx->hmm_last, &ctx->hmm_flags};
+                      &ctx->hmm_last, &ctx->hmm_flags, &ctx->hmm_fmat, &ctx->hmm_acc, &ctx->hmm_skip};
     for (DevBuf *b : bufs) b->release();
     ctx->h_meta.release(); ctx->h_dense.release(); ctx->h_small.release(); ctx->h_up.release(); ctx->h_hdr.release();
     for (auto &e : ctx->ev) if (e) (void)hipEventDestroy(e);
@@ -1388,6 +1392,8 @@ int ps_set_option(ps_ctx *ctx, const char *name, int64_t value)
         ctx->k0_admit = value > 3 ? 3 : 0;
     }
     else if (n == "hmm_bp_budget" && value >= 1) ctx->hmm_bp_budget = value;
+    else if (n == "hmm_fb_budget" && value >= 1) ctx->hmm_fb_budget = value;
+    else if (n == "hmm_expect_lds") ctx->hmm_expect_lds = value != 0;
     else if (n == "single_pass") ctx->single_pass = value != 0;
     else if (n == "gather_fused") ctx->gather_fused = value != 0;
     else if (n == "download_by_kernel") ctx->download_by_kernel = value != 0;
@@ -2720,7 +2726,7 @@ int hmm_viterbi(ps_ctx *ctx, const HmmDev &D, const double *d_obs, const int64_t
         const int nq = q1 - q0;
         BP *bp = ctx->hmm_bp.as<BP>();
         hipLaunchKernelGGL((hmm_fwd_kernel<HMM_VITERBI, BP>), dim3(nq), dim3(HMM_NT), lds, ctx->stream, D, d_obs, d_off, q0, d_logp,
-                           d_mat, bp, bp_row0, ctx->hmm_last.as<int>());
+                           d_mat, 0ll, bp, bp_row0, ctx->hmm_last.as<int>());
         HIP_TRY(ctx, hipGetLastError());
         hipLaunchKernelGGL(hmm_trace_kernel<BP>, dim3((nq + HMM_NT - 1) / HMM_NT), dim3(HMM_NT), 0, ctx->stream, D, d_off, q0, nq,
                            static_cast<const BP *>(bp), bp_row0, static_cast<const int *>(ctx->hmm_last.as<int>()),
@@ -2780,7 +2786,7 @@ int ps_hmm_batch(ps_ctx *ctx, const ps_hmm_model *model, int32_t mode, const dou
     if (mode == PS_HMM_FORWARD) {
         HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_fwd_kernel<HMM_FORWARD, uint8_t>), static_cast<int>(lds)));
         hipLaunchKernelGGL((hmm_fwd_kernel<HMM_FORWARD, uint8_t>), dim3(n_seq), dim3(HMM_NT), lds, ctx->stream, D, d_obs, d_off, 0,
-                           d_logp, d_mat, static_cast<uint8_t *>(nullptr), 0ll, static_cast<int *>(nullptr));
+                           d_logp, d_mat, 0ll, static_cast<uint8_t *>(nullptr), 0ll, static_cast<int *>(nullptr));
     } else {
         HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_bwd_kernel), static_cast<int>(lds)));
         hipLaunchKernelGGL(hmm_bwd_kernel, dim3(n_seq), dim3(HMM_NT), lds, ctx->stream, D, d_obs, d_off, 0, d_logp, d_mat);
@@ -2788,6 +2794,108 @@ int ps_hmm_batch(ps_ctx *ctx, const ps_hmm_model *model, int32_t mode, const dou
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return PS_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// ps_hmm_expect: LDS bytes at most for the accumulator row beside the two score rows (else the row stays in global memory),
+// and the bytes of all workgroups' rows at most (the grid shrinks to fit)
+constexpr size_t HMM_EXPECT_LDS = 64u << 10;
+constexpr size_t HMM_EXPECT_ROWS = 256u << 20;
+
+template <bool ACC_LDS>
+int hmm_expect_run(ps_ctx *ctx, const HmmDev &D, const double *d_obs, const int64_t *h_off, const long long *d_off,
+                   int32_t n_seq, int n_acc, int E, double *d_logp, double *d_counts, double *d_stats, int32_t *h_skipped)
+{
+    const size_t S = static_cast<size_t>(D.S);
+    const size_t lds = (2 * S + (ACC_LDS ? static_cast<size_t>(n_acc) : 0)) * sizeof(double);
+    const size_t lds_fwd = 2 * S * sizeof(double);
+    const void *fk = reinterpret_cast<const void *>(hmm_expect_kernel<ACC_LDS>);
+    HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_fwd_kernel<HMM_FORWARD, uint8_t>), static_cast<int>(lds_fwd)));
+    HIP_TRY(ctx, set_dyn_lds(ctx, fk, static_cast<int>(lds)));
+    // a grid of resident workgroups (it depends on the device and the model only, never on timing), within the row budget
+    const size_t row_bytes = static_cast<size_t>(n_acc) * sizeof(double);
+    unsigned G = std::min<unsigned>(static_cast<unsigned>(n_seq), resident_slots(ctx, hmm_expect_kernel<ACC_LDS>, HMM_NT, lds));
+    G = static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>(G, HMM_EXPECT_ROWS / row_bytes)));
+    HIP_TRY(ctx, ctx->hmm_acc.reserve(G * row_bytes));
+    HIP_TRY(ctx, ctx->hmm_skip.reserve(sizeof(double)));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->hmm_acc.p, 0, G * row_bytes, ctx->stream));
+    const long long budget = std::max<long long>(1, ctx->hmm_fb_budget);
+    for (int32_t q0 = 0; q0 < n_seq;) {
+        // as many sequences as keep their forward matrices within the budget (at least one)
+        long long bytes = (h_off[q0 + 1] - h_off[q0] + 1) * static_cast<long long>(S * sizeof(double));
+        int32_t q1 = q0 + 1;
+        while (q1 < n_seq) {
+            const long long more = (h_off[q1 + 1] - h_off[q1] + 1) * static_cast<long long>(S * sizeof(double));
+            if (bytes + more > budget) break;
+            bytes += more; ++q1;
+        }
+        if (bytes > (16ll << 30)) return fail(ctx, PS_ERR_ARG, "sequence %d needs %lld bytes of forward matrix (16 GiB at most)", q0, bytes);
+        HIP_TRY(ctx, ctx->hmm_fmat.reserve(static_cast<size_t>(bytes)));
+        const long long row0 = h_off[q0] + q0;
+        double *fmat = ctx->hmm_fmat.as<double>();
+        hipLaunchKernelGGL((hmm_fwd_kernel<HMM_FORWARD, uint8_t>), dim3(q1 - q0), dim3(HMM_NT), lds_fwd, ctx->stream, D, d_obs, d_off,
+                           q0, d_logp, fmat, row0, static_cast<uint8_t *>(nullptr), 0ll, static_cast<int *>(nullptr));
+        HIP_TRY(ctx, hipGetLastError());
+        hipLaunchKernelGGL(hmm_expect_kernel<ACC_LDS>, dim3(G), dim3(HMM_NT), lds, ctx->stream, D, d_obs, d_off, q0, q1,
+                           static_cast<const double *>(d_logp), static_cast<const double *>(fmat), row0, ctx->hmm_acc.as<double>(), n_acc);
+        HIP_TRY(ctx, hipGetLastError());
+        q0 = q1;
+    }
+    hipLaunchKernelGGL(hmm_expect_reduce_kernel, dim3((n_acc + 255) / 256), dim3(256), 0, ctx->stream,
+                       static_cast<const double *>(ctx->hmm_acc.as<double>()), static_cast<int>(G), n_acc, E, d_counts, d_stats,
+                       ctx->hmm_skip.as<double>());
+    HIP_TRY(ctx, hipGetLastError());
+    double skipped = 0.0;
+    HIP_TRY(ctx, hipMemcpyAsync(&skipped, ctx->hmm_skip.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    *h_skipped = static_cast<int32_t>(skipped);
+    return PS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ps_hmm_expect(ps_ctx *ctx, const ps_hmm_model *model, const double *d_obs, const int64_t *h_off, int32_t n_seq,
+                  double *d_logp, double *d_counts, double *d_stats, int32_t *h_skipped)
+{
+    if (!ctx) return PS_ERR_ARG;
+    if (!model || !h_off || !h_skipped) return fail(ctx, PS_ERR_ARG, "null pointer");
+    if (n_seq < 0) return fail(ctx, PS_ERR_ARG, "negative sequence count");
+    for (int32_t q = 0; q < n_seq; ++q) {
+        if (h_off[q] < 0 || h_off[q + 1] < h_off[q]) return fail(ctx, PS_ERR_ARG, "sequence offsets must be non-negative and ascending");
+        if (h_off[q + 1] - h_off[q] > INT32_MAX / 2) return fail(ctx, PS_ERR_ARG, "sequence %d too long", q);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HmmDev D;
+    int max_in = 0;
+    if (int rc = hmm_upload(ctx, model, &D, &max_in)) return rc;
+    const int E = model->out_ptr[D.S], NE = D.n_emit;
+    const long long n_acc_ll = static_cast<long long>(E) + 3ll * NE + 1;
+    if (n_acc_ll > (1ll << 26)) return fail(ctx, PS_ERR_ARG, "model of %d edges: the E-step takes at most 2^26 accumulators", E);
+    const int n_acc = static_cast<int>(n_acc_ll);
+    if ((E > 0 && !d_counts) || (NE > 0 && !d_stats)) return fail(ctx, PS_ERR_ARG, "null device pointer");
+    *h_skipped = 0;
+    if (n_seq == 0) {
+        if (E > 0) HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, static_cast<size_t>(E) * sizeof(double), ctx->stream));
+        if (NE > 0) HIP_TRY(ctx, hipMemsetAsync(d_stats, 0, 3 * static_cast<size_t>(NE) * sizeof(double), ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return PS_OK;
+    }
+    if (!d_logp || (h_off[n_seq] > 0 && !d_obs)) return fail(ctx, PS_ERR_ARG, "null device pointer");
+    const size_t nb = (static_cast<size_t>(n_seq) + 1) * sizeof(int64_t);
+    HIP_TRY(ctx, ctx->h_up.reserve(nb));
+    HIP_TRY(ctx, ctx->hmm_off.reserve(nb));
+    std::memcpy(ctx->h_up.p, h_off, nb);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->hmm_off.p, ctx->h_up.p, nb, hipMemcpyHostToDevice, ctx->stream));
+    const long long *d_off = ctx->hmm_off.as<long long>();
+    const bool in_lds = (2 * static_cast<size_t>(D.S) + static_cast<size_t>(n_acc)) * sizeof(double) <= HMM_EXPECT_LDS
+                        && ctx->hmm_expect_lds;
+    return in_lds ? hmm_expect_run<true>(ctx, D, d_obs, h_off, d_off, n_seq, n_acc, E, d_logp, d_counts, d_stats, h_skipped)
+                  : hmm_expect_run<false>(ctx, D, d_obs, h_off, d_off, n_seq, n_acc, E, d_logp, d_counts, d_stats, h_skipped);
 }
 
 }  // extern "C"

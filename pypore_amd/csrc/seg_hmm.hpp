@@ -62,12 +62,13 @@ struct HmmLse {
     __device__ __forceinline__ double get() const { return m > -__builtin_inf() ? m + log1p(r) : -__builtin_inf(); }
 };
 
-// Viterbi / forward over one sequence per workgroup.  Rows of sequence q: mat (optional, absolute row off[q] + q) and bp
+// Viterbi / forward over one sequence per workgroup.  Rows of sequence q: mat (optional, row off[q] + q - mat_row0) and bp
 // (backpointers, Viterbi only, row off[q] + q - bp_row0 of this launch).  Writes logp[q] and, for Viterbi, last[q]: the
 // state the path ends in (end for a finite model, else the best state of step n, lowest index on a tie).
 template <int MODE, typename BP>
 __global__ __launch_bounds__(HMM_NT) void hmm_fwd_kernel(HmmDev M, const double *obs, const long long *off, int q0,
-                                                         double *logp, double *mat, BP *bp, long long bp_row0, int *last)
+                                                         double *logp, double *mat, long long mat_row0, BP *bp,
+                                                         long long bp_row0, int *last)
 {
 #pragma clang fp contract(off)
     extern __shared__ double hm_lds[];
@@ -108,7 +109,7 @@ __global__ __launch_bounds__(HMM_NT) void hmm_fwd_kernel(HmmDev M, const double 
     };
     auto store_row = [&](int t) {
         if (mat) {
-            double *dst = mat + (row0 + t) * S;
+            double *dst = mat + (row0 - mat_row0 + t) * S;
             for (int k = lane; k < S; k += HMM_NT) dst[k] = cur[k];
         }
     };
@@ -220,6 +221,116 @@ __global__ __launch_bounds__(HMM_NT) void hmm_bwd_kernel(HmmDev M, const double 
         }
     }
     if (lane == 0) logp[q] = cur[M.start];
+}
+
+// E-step of Baum-Welch (ps_hmm_expect): the backward recursion of hmm_bwd_kernel with the expectations folded in.  The
+// forward matrix of the launch's sequences is in HBM (fmat, sequence q at row off[q] + q - f_row0, from hmm_fwd_kernel);
+// the backward rows stay in LDS and are never written out.  With w = f[t][k] - logp[q], every out-edge term the recursion
+// forms for state k at step t -- nxt[l] + lp (l emitting, b[t+1][l] + e_l(x_t) + lp) or cur[l] + lp (l silent) -- adds
+// exp(w + term) to the count of that edge, and an emitting state k adds its posterior exp(f[t][k] + b[t][k] - logp[q])
+// to (W, A, B) with the observation x[t-1] shifted by c_k = param[3k].
+//
+// Accumulators: one row of n_acc = E + 3 NE + 1 doubles per workgroup (edge counts in out-edge order, (W, A, B) per
+// emitting state, the number of sequences skipped for logp = -inf).  Workgroup g takes the sequences q = g (mod gridDim.x)
+// of [q0, q1), in ascending order, so its row sums the same sequences in the same order however the batch is cut into
+// launches.  An edge belongs to the lane that owns its source state (and a state's statistics to the lane that owns the
+// state) in every step, so a row needs no atomics.  ACC_LDS: the row is loaded into LDS next to the two score rows and
+// stored back at the end; otherwise it is updated in place in global memory.
+template <bool ACC_LDS>
+__global__ __launch_bounds__(HMM_NT) void hmm_expect_kernel(HmmDev M, const double *obs, const long long *off, int q0, int q1,
+                                                            const double *logp, const double *fmat, long long f_row0,
+                                                            double *acc_rows, int n_acc)
+{
+#pragma clang fp contract(off)
+    extern __shared__ double hm_lds[];
+    const int S = M.S, NE = M.n_emit, lane = threadIdx.x, G = gridDim.x;
+    const int E = M.out_ptr[S];
+    double *acc_g = acc_rows + static_cast<long long>(blockIdx.x) * n_acc;
+    double *acc = ACC_LDS ? hm_lds + 2 * S : acc_g;
+    double *cnt = acc, *st = acc + E;
+    constexpr double NEG = -__builtin_inf();
+    if (ACC_LDS) {
+        for (int i = lane; i < n_acc; i += HMM_NT) acc[i] = acc_g[i];
+        hm_sync();
+    }
+    int qs = q0 + static_cast<int>((static_cast<long long>(blockIdx.x) - q0 % G + G) % G);
+    for (int q = qs; q < q1; q += G) {
+        const double lq = logp[q];
+        if (!(lq > NEG)) {
+            if (lane == 0) acc[n_acc - 1] += 1.0;
+            continue;
+        }
+        const long long base = off[q];
+        const int n = static_cast<int>(off[q + 1] - base);
+        const double *x = obs + base;
+        const double *f = fmat + (base + q - f_row0) * S;
+        double *nxt = hm_lds, *cur = hm_lds + S;
+
+        auto one = [&](int k, int t, double fk) {
+            const double w = fk - lq;
+            HmmLse lse;
+            if (t == n && (!M.finite || k == M.end)) lse.add(0.0);
+            const int e0 = M.out_ptr[k], e1 = M.out_ptr[k + 1];
+            for (int e = e0; e < e1; ++e) {
+                const int l = M.out_dst[e];
+                double v;
+                if (l < NE) {
+                    if (t >= n) continue;
+                    v = nxt[l] + M.out_lp[e];
+                } else v = cur[l] + M.out_lp[e];
+                lse.add(v);
+                if (w > NEG && v > NEG) cnt[e] += exp(w + v);
+            }
+            cur[k] = lse.get();
+        };
+
+        for (int t = n; t >= 0; --t) {
+            const double *frow = f + static_cast<long long>(t) * S;
+            if (t < n) {
+                double *tmp = nxt; nxt = cur; cur = tmp;
+                const double xt = x[t];
+                for (int l = lane; l < NE; l += HMM_NT) nxt[l] = nxt[l] > NEG ? nxt[l] + hmm_emit(M, l, xt) : NEG;
+                hm_sync();
+            }
+            for (int L = M.n_levels - 1; L >= 0; --L) {
+                const int hi = M.level_ptr[L + 1];
+                for (int k = M.level_ptr[L] + lane; k < hi; k += HMM_NT) one(k, t, frow[k]);
+                hm_sync();
+            }
+            for (int k = lane; k < NE; k += HMM_NT) {
+                const double fk = frow[k];
+                one(k, t, fk);
+                if (t > 0 && fk > NEG && cur[k] > NEG) {
+                    const double g = exp(fk + cur[k] - lq);
+                    const double d = x[t - 1] - M.param[3 * k];
+                    const double gd = g * d;
+                    st[3 * k] += g;
+                    st[3 * k + 1] += gd;
+                    st[3 * k + 2] += gd * d;
+                }
+            }
+            hm_sync();
+        }
+    }
+    if (ACC_LDS) {
+        hm_sync();
+        for (int i = lane; i < n_acc; i += HMM_NT) acc_g[i] = acc[i];
+    }
+}
+
+// The per-workgroup rows of hmm_expect_kernel summed in workgroup order (one thread per entry: a fixed order, so the same
+// rows give the same bits): counts[E], stats[3 NE], *skipped.
+__global__ __launch_bounds__(256) void hmm_expect_reduce_kernel(const double *acc_rows, int G, int n_acc, int E,
+                                                                double *counts, double *stats, double *skipped)
+{
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_acc) return;
+    double s = 0.0;
+    for (int g = 0; g < G; ++g) s += acc_rows[static_cast<long long>(g) * n_acc + i];
+    if (i < E) counts[i] = s;
+    else if (i < n_acc - 1) stats[i - E] = s;
+    else *skipped = s;
 }
 
 // Viterbi traceback, one lane per sequence: from (n, last[q]) back to (0, start).  An emitting state steps back one

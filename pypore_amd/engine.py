@@ -500,6 +500,27 @@ class Context(object):
         return logp[:n_seq], mat, (path, path_off, path_len[:n_seq])
 
     @_serialised
+    def hmm_expect(self, model, obs, off):
+        """ps_hmm_expect: the Baum-Welch E-step over a batch.  model: a _lib.HmmModel (its arrays kept alive by the caller);
+        obs: float64 CUDA tensor, sequence q = obs[off[q]:off[q+1]].  Returns (logp float64 [n_seq], edge counts float64
+        [n_edges] in out-edge order, (W, A, B) float64 [n_emit, 3], the number of sequences skipped for logp = -inf)."""
+        assert obs.is_cuda and obs.is_contiguous() and obs.dtype == torch.float64
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        n_seq = off.size - 1
+        dev = obs.device
+        n_edges = int(ctypes.cast(model.out_ptr, ctypes.POINTER(ctypes.c_int32))[model.n_states])
+        logp = torch.empty(max(n_seq, 1), dtype=torch.float64, device=dev)
+        counts = torch.empty(max(n_edges, 1), dtype=torch.float64, device=dev)
+        stats = torch.empty((max(model.n_emit, 1), 3), dtype=torch.float64, device=dev)
+        skipped = ctypes.c_int32(0)
+        torch.cuda.current_stream(dev).synchronize()
+        _lib.check(self.L.ps_hmm_expect(self.handle, ctypes.byref(model), ctypes.c_void_p(obs.data_ptr()),
+                                        off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n_seq,
+                                        ctypes.c_void_p(logp.data_ptr()), ctypes.c_void_p(counts.data_ptr()),
+                                        ctypes.c_void_p(stats.data_ptr()), ctypes.byref(skipped)), self.handle)
+        return logp[:n_seq], counts[:n_edges], stats[:model.n_emit], int(skipped.value)
+
+    @_serialised
     def synth_trace(self, n, seed, seg_end, level_counts, dtype=torch.float32, start=0):
         """Synthetic step trace generated directly in HBM (csrc synth_kernel == pypore_amd.synth).  start > 0: the
         samples [start, start + n) of the trace the table describes (a rank's piece of one long trace): the noise hash

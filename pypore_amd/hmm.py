@@ -1,6 +1,7 @@
 """Hidden Markov models with the surface the reference's HMM code uses (yahmm: Model, State, NormalDistribution,
 UniformDistribution; add_state(s), add_transition, add_model, bake; viterbi, forward, backward, log_probability), decoded on
-the MI355X (ps_hmm_batch, csrc/seg_hmm.hpp).
+the MI355X (ps_hmm_batch, csrc/seg_hmm.hpp), and trained there (Model.train: Baum-Welch with its E-step in ps_hmm_expect,
+or Viterbi training).
 
     model = Model("happy model")
     a = State(NormalDistribution(3, 4), 'a')
@@ -27,7 +28,31 @@ Deviations from yahmm, by design:
     and so drop those silent states from its paths; here every silent state visited appears in the path.
   * `end` is kept in model.states even when it cannot be reached (the model is then infinite).
   * Edges of probability 0 are dropped; negative probabilities raise ValueError.
-There is no CPU fallback: inference runs on the GPU library or raises.
+
+Training (Model.train; the device and tests/hmm_train_oracle.py compute the same thing).  For one sequence x of length n
+with forward matrix f, backward matrix b and log probability logp (above):
+  * the expected count of edge k -> l (log probability lp) is  sum_{t=0}^{n-1} exp(f[t][k] + lp + e_l(x_t) + b[t+1][l] - logp)
+    for an emitting l and  sum_{t=0}^{n} exp(f[t][k] + lp + b[t][l] - logp)  for a silent l (finite and infinite models
+    alike: b holds the end condition);
+  * emitting state k's posterior for observation t is g_k(t) = exp(f[t+1][k] + b[t+1][k] - logp), and its statistics are
+    W_k = sum g, A_k = sum g (x - c_k), B_k = sum g (x - c_k)^2 with the shift c_k = its current mean (param[3k]);
+  * a sequence with logp = -inf is skipped (counted, contributes nothing); an empty one contributes its silent edges at
+    t = 0; a batch's statistics are the sums over its sequences (Model.expected_counts_batch).
+The M-step (host): count(k -> l) = expected count + the edge's pseudocount (use_pseudocount) + transition_pseudocount; the
+new probability is count / (sum over k's out-edges), k keeps its old probabilities when that sum is 0, and then
+p = edge_inertia p_old + (1 - edge_inertia) p_new.  A normal state with W > 0 gets mean = c + A/W, var = B/W - (A/W)^2,
+std = max(sqrt(max(var, 0)), min_std), each mixed with its old value by distribution_inertia; W = 0 leaves it.  A
+distribution shared by several states is updated once, from their pooled statistics.  Frozen distributions
+(Distribution.freeze()) are never updated.  The structure stays: `states`, their order and `edges` do not change, an edge
+whose probability becomes 0 keeps its place (log -inf on the device), and the trained probabilities are written back to
+the transitions, so a later bake() starts from them (and drops the zero edges, as always).  algorithm='viterbi' counts
+each consecutive pair of states on every Viterbi path as one transition and gives each observation weight 1 in the
+emitting state that consumed it (the shift and the M-step as above); its log probabilities are the Viterbi scores.
+
+Deviations from yahmm, by design:
+  * uniform distributions are not trained (their support decides which sequences are possible);
+  * Viterbi training runs the same stop loop as Baum-Welch, measured by the sum of the Viterbi scores.
+There is no CPU fallback: inference and the Baum-Welch E-step run on the GPU library or raise.
 """
 import collections
 import math
@@ -46,6 +71,14 @@ class Distribution(object):
 
     def __init__(self, parameters):
         self.parameters = list(parameters)
+        self.frozen = False
+
+    def freeze(self):
+        """Model.train leaves a frozen distribution as it is."""
+        self.frozen = True
+
+    def thaw(self):
+        self.frozen = False
 
     def log_probability(self, x):
         raise NotImplementedError
@@ -118,6 +151,7 @@ class Model(object):
         self._added = []                                   # every state, in the order it joined
         self._known = set()
         self._edges = collections.OrderedDict()            # (from, to) -> probability as given
+        self._pseudo = {}                                  # (from, to) -> pseudocount (train(use_pseudocount=True))
         self.states = None                                 # after bake()
         self._flat = None
         self._c = None                                     # the ctypes view of _flat, made on first use
@@ -140,14 +174,19 @@ class Model(object):
         for s in states:
             self.add_state(s)
 
-    def add_transition(self, a, b, probability):
-        """An edge a -> b (states not yet in the model join it).  A second call for the same pair replaces the first."""
+    def add_transition(self, a, b, probability, pseudocount=None):
+        """An edge a -> b (states not yet in the model join it).  A second call for the same pair replaces the first.
+        pseudocount: what train(use_pseudocount=True) adds to the edge's expected count (default: `probability`)."""
         p = float(probability)
         if p < 0 or math.isnan(p):
             raise ValueError("transition probability must be >= 0, got %r" % probability)
+        c = p if pseudocount is None else float(pseudocount)
+        if c < 0 or math.isnan(c):
+            raise ValueError("pseudocount must be >= 0, got %r" % pseudocount)
         self.add_state(a)
         self.add_state(b)
         self._edges[(a, b)] = p
+        self._pseudo[(a, b)] = c
         self._flat = None
 
     def add_model(self, other):
@@ -156,6 +195,7 @@ class Model(object):
             self.add_state(s)
         for (a, b), p in other._edges.items():
             self._edges[(a, b)] = p
+            self._pseudo[(a, b)] = other._pseudo.get((a, b), p)
         self._flat = None
 
     # ---- bake ---------------------------------------------------------------------------------------------------
@@ -231,6 +271,7 @@ class Model(object):
             in_src=np.ascontiguousarray(src[by_dst]), in_lp=np.ascontiguousarray(lp[by_dst]),
             out_ptr=np.concatenate(([0], np.cumsum(np.bincount(src, minlength=S)))).astype(np.int32),
             out_dst=np.ascontiguousarray(dst[by_src]), out_lp=np.ascontiguousarray(lp[by_src]))
+        self._in_order = by_dst                         # edges (= out-edge order) -> in-edge order
         self._c = None
 
     @property
@@ -253,7 +294,7 @@ class Model(object):
         return self._c
 
     # ---- inference on the device ---------------------------------------------------------------------------------
-    def _run(self, sequences, mode, want_mat, device=None):
+    def _upload(self, sequences, device):
         import torch
         from . import engine
         f = self.flat
@@ -267,6 +308,10 @@ class Model(object):
         off = np.concatenate(([0], np.cumsum([s.size for s in seqs]))).astype(np.int64)
         obs = np.concatenate(seqs) if off[-1] else np.zeros(1, np.float64)
         obs = torch.from_numpy(obs).to(torch.device("cuda", ctx.device))
+        return ctx, off, obs
+
+    def _run(self, sequences, mode, want_mat, device=None):
+        ctx, off, obs = self._upload(sequences, device)
         return off, ctx.hmm_batch(self._c_model(), mode, obs, off, want_mat)
 
     def _matrices(self, sequences, mode, device):
@@ -315,3 +360,179 @@ class Model(object):
 
     def log_probability(self, sequence):
         return float(self.log_probability_batch([sequence])[0])
+
+    # ---- training ------------------------------------------------------------------------------------------------
+    def expected_counts_batch(self, sequences, device=None):
+        """The Baum-Welch E-step on the device (ps_hmm_expect), summed over the sequences: Expectations(counts: float64
+        per edge, aligned with `edges`; stats: float64 [n_emit, 3], (W, A, B) per emitting state (module docstring);
+        logp: float64 per sequence; skipped: the number of sequences with logp = -inf)."""
+        ctx, off, obs = self._upload(sequences, device)
+        logp, counts, stats, skipped = ctx.hmm_expect(self._c_model(), obs, off)
+        return Expectations(counts.cpu().numpy(), stats.cpu().numpy().reshape(-1, 3), logp.cpu().numpy(), skipped)
+
+    def _viterbi_counts(self, sequences, device=None):
+        """Viterbi training's statistics (host counting on viterbi_batch's paths), as an Expectations."""
+        f = self.flat
+        S, NE = f["n_states"], f["n_emit"]
+        src = np.array([e[0] for e in self.edges], np.int64)
+        dst = np.array([e[1] for e in self.edges], np.int64)
+        keys = src * S + dst                             # ascending: edges are sorted by (from, to)
+        counts = np.zeros(len(self.edges))
+        stats = np.zeros((NE, 3))
+        shift = f["param"][0:3 * NE:3]
+        seqs = [np.asarray(x, dtype=np.float64) for x in sequences]
+        res = self.viterbi_batch(seqs, device) if seqs else []
+        logp = np.array([lp for lp, _ in res], np.float64)
+        skipped = 0
+        for (lp, path), x in zip(res, seqs):
+            if path is None:
+                skipped += 1
+                continue
+            idx = np.array([i for i, _ in path], np.int64)
+            pk = idx[:-1] * S + idx[1:]
+            np.add.at(counts, np.searchsorted(keys, pk), 1.0)
+            em = idx[idx < NE]
+            d = x - shift[em]
+            np.add.at(stats[:, 0], em, 1.0)
+            np.add.at(stats[:, 1], em, d)
+            np.add.at(stats[:, 2], em, d * d)
+        return Expectations(counts, stats, logp, skipped)
+
+    def _estep(self, sequences, algorithm, want_stats, device):
+        """(logp per sequence, Expectations or None): the statistics only when want_stats (else a forward pass alone)."""
+        if algorithm == "viterbi":
+            est = self._viterbi_counts(sequences, device)
+            return est.logp, est
+        if want_stats:
+            est = self.expected_counts_batch(sequences, device)
+            return est.logp, est
+        return (self.log_probability_batch(sequences, device) if len(sequences) else np.zeros(0)), None
+
+    def _m_step(self, counts, stats, transition_pseudocount=0, use_pseudocount=False, edge_inertia=0.0,
+                distribution_inertia=0.0, min_std=0.01):
+        """New edge probabilities and normal parameters from the E-step's statistics (module docstring); the flat arrays
+        are derived again, so the next device call uploads the trained model."""
+        f = self.flat
+        S, NE = f["n_states"], f["n_emit"]
+        counts = np.asarray(counts, np.float64).reshape(-1)
+        stats = np.asarray(stats, np.float64).reshape(-1, 3)
+        if counts.size != len(self.edges) or stats.shape[0] != NE:
+            raise ValueError("statistics for %d edges and %d emitting states, the model has %d and %d"
+                             % (counts.size, stats.shape[0], len(self.edges), NE))
+        src = np.array([e[0] for e in self.edges], np.int64)
+        old = np.array([e[2] for e in self.edges], np.float64)
+        c = counts + float(transition_pseudocount)
+        if use_pseudocount:
+            c = c + np.array([self._pseudo.get((self.states[i], self.states[j]), self._edges.get((self.states[i], self.states[j]), 0.0))
+                              for i, j, _ in self.edges], np.float64)
+        total = np.bincount(src, weights=c, minlength=S) if src.size else np.zeros(S)
+        tot = total[src]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            new = np.where(tot > 0, c / np.where(tot > 0, tot, 1.0), old)
+        new = edge_inertia * old + (1.0 - edge_inertia) * new
+        self.edges = [(i, j, float(p)) for (i, j, _), p in zip(self.edges, new)]
+        for i, j, p in self.edges:
+            self._edges[(self.states[i], self.states[j])] = p
+        # normal states, pooled per distribution object
+        pooled = collections.OrderedDict()
+        for k in range(NE):
+            d = self.states[k].distribution
+            if d.kind != KIND_NORMAL or d.frozen:
+                continue
+            acc = pooled.setdefault(id(d), [d, f["param"][3 * k], 0.0, 0.0, 0.0])
+            acc[2:] = [acc[2] + stats[k, 0], acc[3] + stats[k, 1], acc[4] + stats[k, 2]]
+        for d, shift, W, A, B in pooled.values():
+            if not W > 0:
+                continue
+            m = A / W
+            mean = shift + m
+            std = max(math.sqrt(max(B / W - m * m, 0.0)), min_std)
+            om, os_ = d.parameters
+            d.parameters = [distribution_inertia * om + (1.0 - distribution_inertia) * mean,
+                            distribution_inertia * os_ + (1.0 - distribution_inertia) * std]
+        self._recompile()
+
+    def _recompile(self):
+        """The flat arrays again from `edges` and the distributions (same structure: states, levels and CSR lists)."""
+        f = dict(self.flat)
+        with np.errstate(divide="ignore"):
+            lp = np.log(np.array([e[2] for e in self.edges], np.float64).reshape(-1))
+        f["out_lp"] = np.ascontiguousarray(lp)
+        f["in_lp"] = np.ascontiguousarray(lp[self._in_order])
+        param = np.zeros(3 * f["n_states"], np.float64)
+        for k in range(f["n_emit"]):
+            param[3 * k:3 * k + 3] = self.states[k].distribution.compiled()
+        f["param"] = param
+        self._flat = f
+        self._c = None
+
+    def train(self, sequences, stop_threshold=1e-9, min_iterations=0, max_iterations=None, algorithm='baum-welch',
+              verbose=True, transition_pseudocount=0, use_pseudocount=False, edge_inertia=0.0, distribution_inertia=0.0,
+              min_std=0.01, device=None):
+        """Trains the baked model on `sequences` (each a 1-D array of observations) and returns the total improvement of
+        the summed log probability.  Each iteration is an E-step ('baum-welch': ps_hmm_expect on the device; 'viterbi':
+        counts on viterbi_batch's paths) and the M-step of the module docstring.  The loop (sequences impossible under
+        the starting model are left out of every sum):
+
+            initial = sum logp;  improvement = inf;  it = 0;  total = 0
+            while improvement > stop_threshold or it < min_iterations:
+                if max_iterations is not None and it >= max_iterations: break
+                E-step (from the previous pass), M-step;  trained = sum logp under the new model
+                improvement = trained - initial;  total += improvement;  initial = trained;  it += 1
+
+        printing "Training improvement: ..." per iteration and "Total Training Improvement: ..." at the end when verbose.
+        The pass that measures `trained` is the next iteration's E-step, so N iterations make N + 1 passes; the last is a
+        forward pass alone when max_iterations ends the loop."""
+        algorithm = str(algorithm).lower()
+        if algorithm not in ("baum-welch", "viterbi"):
+            raise ValueError("algorithm must be 'baum-welch' or 'viterbi', got %r" % algorithm)
+        if max_iterations is not None and (int(max_iterations) != max_iterations or max_iterations < 0):
+            raise ValueError("max_iterations must be None or an integer >= 0, got %r" % (max_iterations,))
+        if int(min_iterations) != min_iterations or min_iterations < 0:
+            raise ValueError("min_iterations must be an integer >= 0, got %r" % (min_iterations,))
+        for name, v in (("edge_inertia", edge_inertia), ("distribution_inertia", distribution_inertia)):
+            if not 0.0 <= float(v) <= 1.0:
+                raise ValueError("%s must lie in [0, 1], got %r" % (name, v))
+        if not float(transition_pseudocount) >= 0:
+            raise ValueError("transition_pseudocount must be >= 0, got %r" % (transition_pseudocount,))
+        if not float(min_std) > 0:
+            raise ValueError("min_std must be > 0, got %r" % (min_std,))
+        if isinstance(sequences, np.ndarray) and sequences.ndim == 1:
+            raise ValueError("train takes a list of sequences, not one sequence")
+        self.flat                                              # raises before bake()
+        seqs = [np.ascontiguousarray(x, dtype=np.float64) for x in sequences]
+        for x in seqs:
+            if x.ndim != 1:
+                raise ValueError("an observation sequence must be 1-D, got shape %r" % (x.shape,))
+        mstep = dict(transition_pseudocount=float(transition_pseudocount), use_pseudocount=bool(use_pseudocount),
+                     edge_inertia=float(edge_inertia), distribution_inertia=float(distribution_inertia),
+                     min_std=float(min_std))
+
+        def wants_stats(done):
+            return max_iterations is None or done < max_iterations
+
+        logp, est = self._estep(seqs, algorithm, wants_stats(0), device)
+        logp = np.asarray(logp, np.float64)
+        possible = logp > NEG_INF
+        if not possible.all():
+            seqs = [x for x, ok in zip(seqs, possible) if ok]
+        initial = float(np.sum(logp[possible]))
+        improvement, it, total = float("inf"), 0, 0.0
+        while improvement > stop_threshold or it < min_iterations:
+            if max_iterations is not None and it >= max_iterations:
+                break
+            self._m_step(est.counts, est.stats, **mstep)
+            logp, est = self._estep(seqs, algorithm, wants_stats(it + 1), device)
+            trained = float(np.sum(logp))
+            improvement = trained - initial
+            total += improvement
+            initial = trained
+            it += 1
+            if verbose:
+                print("Training improvement: {}".format(improvement))
+        if verbose:
+            print("Total Training Improvement: {}".format(total))
+        return total
+
+
+Expectations = collections.namedtuple("Expectations", "counts stats logp skipped")
