@@ -135,8 +135,10 @@ int ps_set_tiling(ps_ctx *ctx, int64_t tile_len, int64_t halo);
  * "gather_fused" 1 (default): the gather places its items from per-256-job count sums (no scan kernel in front of it), 0: rounds
  * 2-5's item scan + gather; "download_by_kernel" 1 (default): the status block returns by a kernel writing pinned memory;
  * "k0_unaligned" 0: K0's fast route only from 16-byte-aligned addresses (1: whatever the probe at ps_create said);
- * "debug" 1: the library reports on stderr which occupancy it found and which seams gave up (prints only);
- * "slots_pct" 1..100 (default 100) share of the resident wave slots the single-wave scan kernels are launched on;
+ * "debug" 1: the library reports on stderr which occupancy it found, the resident slots every launch sized by them gets, and
+ * which seams gave up (prints only);
+ * "slots_pct" 1..100 (default 100) share of the resident wave slots the kernels of up to 256 threads that are sized by them
+ * (the scan kernels, the aligner, the HMM E-step) are launched on, from the next launch on;
  * "tree_jobs_per_wave" (default 4) subtree kernel: jobs / this many of its slots work, between half and all of them;
  * "noise_k_ppm" (default 100 000 = 0.1): near-tie accounting of the 64-bit digest, margin factor in millionths;
  * "near_tie_log" n (default 65 536, 0 .. 2^30): records of the near-tie log that ps_get_near_ties reads (16 bytes each, device

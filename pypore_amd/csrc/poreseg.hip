@@ -144,8 +144,8 @@ struct ps_ctx {
     // 0.90): with many jobs per slot four waves per SIMD deliver 1.4 x the throughput of two.
     int slots_pct = 100;
     int tree_jobs_per_wave = 4;   // subtree kernel: jobs / this many slots work, between half and all of them (0: all)
-    // host-side caches: occupancy per kernel, dynamic-LDS attribute last set, the tile tables of the last call
-    struct OccKey { const void *fn; int nt; size_t lds; unsigned slots; };
+    // host-side caches: workgroups per CU per kernel, dynamic-LDS attribute last set, the tile tables of the last call
+    struct OccKey { const void *fn; int nt; size_t lds; int per_cu; };
     std::vector<OccKey> occ_cache;
     std::vector<std::pair<const void *, int>> attr_cache;
     struct TileCache {
@@ -334,23 +334,28 @@ inline size_t lds_bytes_for(int lds_cap, int nt)
 constexpr int LDS_BYTES_MAX = 160 * 1024 - static_cast<int>(sizeof(Shared)) - 512 - 64;
 
 // Resident workgroups of a kernel on this device (occupancy x CUs): the scan kernels are launched with one
-// workgroup per slot and stride over their jobs.
+// workgroup per slot and stride over their jobs.  The cache holds the device's workgroups per CU; slots_pct applies on
+// every lookup, so a change of the option takes effect at the next launch.
 template <typename K> unsigned resident_slots(ps_ctx *ctx, K kernel, int nt, size_t lds)
 {
     const void *fn = reinterpret_cast<const void *>(kernel);
+    int per_cu = -1;
     for (const auto &k : ctx->occ_cache)
-        if (k.fn == fn && k.nt == nt && k.lds == lds) return k.slots;
-    int per_cu = 0;
-    if (ctx->n_cu <= 0) {
-        hipDeviceProp_t prop;
-        ctx->n_cu = hipGetDeviceProperties(&prop, ctx->device) == hipSuccess ? prop.multiProcessorCount : 256;
+        if (k.fn == fn && k.nt == nt && k.lds == lds) { per_cu = k.per_cu; break; }
+    if (per_cu < 0) {
+        if (ctx->n_cu <= 0) {
+            hipDeviceProp_t prop;
+            ctx->n_cu = hipGetDeviceProperties(&prop, ctx->device) == hipSuccess ? prop.multiProcessorCount : 256;
+        }
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, nt, lds) != hipSuccess || per_cu <= 0)
+            per_cu = 1;
+        if (ctx->debug) fprintf(stderr, "[poreseg] occupancy: %d workgroups of %d threads per CU (dynamic LDS %zu), %d CUs\n", per_cu, nt, lds, ctx->n_cu);
+        ctx->occ_cache.push_back({fn, nt, lds, per_cu});
     }
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, nt, lds) != hipSuccess || per_cu <= 0)
-        per_cu = 1;
     unsigned slots = static_cast<unsigned>(per_cu) * static_cast<unsigned>(ctx->n_cu);
-    if (ctx->debug) fprintf(stderr, "[poreseg] occupancy: %d workgroups of %d threads per CU (dynamic LDS %zu), %d CUs\n", per_cu, nt, lds, ctx->n_cu);
-    if (nt <= 256) slots = std::max(1u, static_cast<unsigned>(static_cast<unsigned long long>(slots) * static_cast<unsigned>(ctx->slots_pct) / 100u));
-    ctx->occ_cache.push_back({fn, nt, lds, slots});
+    const int pct = nt <= 256 ? ctx->slots_pct : 100;
+    slots = std::max(1u, static_cast<unsigned>(static_cast<unsigned long long>(slots) * static_cast<unsigned>(pct) / 100u));
+    if (ctx->debug) fprintf(stderr, "[poreseg] resident slots: %u (%d threads, dynamic LDS %zu, slots_pct %d)\n", slots, nt, lds, pct);
     return slots;
 }
 

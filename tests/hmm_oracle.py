@@ -331,6 +331,24 @@ def random_model(rng, max_states=300, max_chain=60, finite=True):
     return m
 
 
+def line_model(S):
+    """S states: S - 2 emitting ones on a left-to-right line with self-loops and skips, start entering every 64th."""
+    rng = np.random.default_rng(S)
+    m = Model("line")
+    st = [State(NormalDistribution(float(rng.normal(0, 3)), float(rng.uniform(0.5, 2))), "s%04d" % i) for i in range(S - 2)]
+    for i, s in enumerate(st):
+        if i % 64 == 0:
+            m.add_transition(m.start, s, 1.0)
+        m.add_transition(s, s, 0.3)
+        if i + 1 < len(st):
+            m.add_transition(s, st[i + 1], 0.5)
+        if i + 2 < len(st):
+            m.add_transition(s, st[i + 2], 0.1)
+        m.add_transition(s, m.end, 0.1)
+    m.bake()
+    return m
+
+
 def profile_model(n=54, seed=0, name="profile"):
     """A global profile HMM like the reference tutorial's: per position a match (normal), an insert (uniform over the
     current range) and a silent delete; 3n + 1 + 2 states (n = 54: 165)."""

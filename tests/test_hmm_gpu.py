@@ -1,6 +1,7 @@
 """pypore_amd.hmm on the MI355X (ps_hmm_batch, csrc/seg_hmm.hpp) against the numpy oracle (tests/hmm_oracle.py):
 Viterbi, forward, backward and log_probability on brute-forceable models, random models with long silent chains and a
-54-position profile HMM; edge cases; a ragged batch against single calls; the DataTypes callers end to end.
+54-position profile HMM; edge cases; a ragged batch against single calls; the DataTypes callers end to end; launch
+shapes: in-degrees on both sides of the 8-bit backpointer width, paths longer than their slots, a model at the state cap.
 
 Tolerances: log probabilities and matrix entries to 1e-12 relative (to max(|oracle|, 1), so that entries near log 1 are
 not judged by their rounding noise); -inf exactly where the oracle has -inf.  Viterbi paths are identical wherever the
@@ -13,6 +14,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import hmm_oracle as O  # noqa: E402
+import launch_geometry as LG  # noqa: E402
 
 from pypore_amd.hmm import Model, NormalDistribution, State  # noqa: E402
 
@@ -209,3 +211,145 @@ def test_parse_with_hmm_and_experiment_apply_hmm_end_to_end():
         _, path, _ = O.viterbi(c, np.array([s.mean for s in ev.segments]))
         want += path
     assert [i for i, _ in out] == want
+
+
+# ---- launch shapes of ps_hmm_batch ----------------------------------------------------------------------------------
+
+
+def _hub_model(n_in):
+    """A hub state h with n_in in-edges: from the emitting states e0000 .. (self-loop of h last, since the emitting
+    states sort by name); `end` has n_in in-edges too.  start -> every e, e -> h or end, h -> h, any e or end.  The e
+    levels lie 3 apart at std 0.5, h's far below, so an observation names its state and the Viterbi path its in-edges."""
+    m = Model("hub")
+    h = State(NormalDistribution(-50.0, 1.0), "h")
+    es = [State(NormalDistribution(3.0 * i, 0.5), "e%04d" % i) for i in range(n_in - 1)]
+    for e in es:
+        m.add_transition(m.start, e, 1.0)
+        m.add_transition(e, h, 0.8)
+        m.add_transition(e, m.end, 0.2)
+        m.add_transition(h, e, 0.4 / len(es))
+    m.add_transition(h, h, 0.4)
+    m.add_transition(h, m.end, 0.2)
+    m.bake()
+    return m, h, es
+
+
+def _hub_seqs(rng, es, winners):
+    """Sequences that pass through h from the given e states (ordinals into h's in-edges), plus random ones."""
+    seqs = []
+    for w in winners:
+        v = int(rng.integers(len(es)))
+        seqs.append(np.array([3.0 * w, -50.0, -49.5, 3.0 * v, -50.5, 3.0 * (len(es) - 1 - w)]) + rng.normal(0, 0.05, 6))
+    for _ in range(6):                                  # e, then h one or more times, ...
+        x = []
+        for _ in range(int(rng.integers(0, 4))):
+            x += [3.0 * int(rng.integers(len(es)))] + [-50.0] * int(rng.integers(1, 3))
+        seqs.append(np.array(x) + rng.normal(0, 0.3, len(x)))
+    return seqs
+
+
+@pytest.mark.parametrize("n_in", [255, 256, 257, 600])
+def test_in_degree_across_the_backpointer_width(n_in):
+    """In-degree 255 takes the 8-bit Viterbi backpointers, 256 and more the 16-bit ones.  From 257 up the winning in-edge
+    into h has ordinal >= 256 (the emission makes it unambiguous), so a backpointer cut to 8 bits gives a wrong path."""
+    model, h, es = _hub_model(n_in)
+    ix = {id(s): i for i, s in enumerate(model.states)}
+    ins = {}
+    for i, j, _ in model.edges:
+        ins.setdefault(j, []).append(i)
+    assert len(ins[ix[id(h)]]) == n_in and len(ins[ix[id(model.end)]]) == n_in
+    assert max(len(v) for v in ins.values()) == n_in
+    rng = np.random.default_rng(n_in)
+    winners = [0, min(254, n_in - 2), n_in - 2] + ([256, 300 % (n_in - 1), n_in - 3] if n_in > 257 else [])
+    seqs = _hub_seqs(rng, es, winners)
+    check_all(model, seqs)
+    c = O.Compiled(model)
+    used = []                                           # in-edge ordinals on the oracle's paths
+    for q, s in enumerate(seqs):
+        lp, path, margin = O.viterbi(c, s)
+        if path is None:
+            continue
+        used += [sorted(ins[k]).index(i) for i, k in zip(path[:-1], path[1:])]
+        if q < len(winners):
+            into_h = path[path.index(ix[id(h)]) - 1]
+            assert into_h == ix[id(es[winners[q]])] and margin > 1e-3
+            assert sorted(ins[ix[id(h)]]).index(into_h) == winners[q]
+    if n_in > 256:                                      # (h's self-loop is its last in-edge, ordinal n_in - 1)
+        assert max(used) >= 256
+
+
+def test_in_degree_600_under_a_small_backpointer_budget():
+    """The 16-bit route with launches cut by hmm_bp_budget, one sequence alone exceeding the budget (the at-least-one
+    branch)."""
+    from pypore_amd import engine
+    model, h, es = _hub_model(600)
+    rng = np.random.default_rng(5)
+    seqs = _hub_seqs(rng, es, [256, 598, 400, 3])
+    alt = np.stack([3.0 * rng.integers(599, size=20), np.full(20, -50.0)], axis=1).ravel()     # e, h, e, h, ...
+    seqs.insert(3, alt + rng.normal(0, 0.1, 40))
+    S = len(model.states)
+    budget = 9 * S * 2                                  # rows of 16-bit backpointers: 9 (n + 1 <= 9 for the short ones)
+    assert (len(seqs[3]) + 1) * S * 2 > budget
+    whole = model.viterbi_batch(seqs)
+    with LG.options(engine.context(), hmm_bp_budget=budget):
+        split = model.viterbi_batch(seqs)
+    c = O.Compiled(model)
+    for s, a, b in zip(seqs, whole, split):                  # (an empty sequence is impossible here: path None)
+        assert a[0] == b[0] and [i for i, _ in a[1] or []] == [i for i, _ in b[1] or []]
+        check_viterbi(c, s, b)
+
+
+def _chain_model(n_chain):
+    """An emitting state a whose only way back to itself is a chain of n_chain silent states: every observation after the
+    first adds n_chain + 1 entries to the Viterbi path."""
+    m = Model("loop")
+    a = State(NormalDistribution(0.0, 1.0), "a")
+    b = State(NormalDistribution(2.0, 1.0), "b")
+    chain = [State(None, "c%02d" % i) for i in range(n_chain)]
+    m.add_transition(m.start, a, 0.7)
+    m.add_transition(m.start, b, 0.3)
+    m.add_transition(a, chain[0], 0.8)
+    m.add_transition(a, m.end, 0.2)
+    for x, y in zip(chain[:-1], chain[1:]):
+        m.add_transition(x, y, 1.0)
+    m.add_transition(chain[-1], a, 1.0)
+    m.add_transition(b, b, 0.5)
+    m.add_transition(b, chain[0], 0.3)
+    m.add_transition(b, m.end, 0.2)
+    m.bake()
+    return m
+
+
+def test_viterbi_path_longer_than_its_slot():
+    """Paths of ~50 observations through a 20-state silent loop are about eight times longer than the default slot
+    2 (n + 1) + silent states + 1: the call reruns with slots of the exact lengths (PS_ERR_CAPACITY, hmm_trace_kernel's flag bit 0).
+    Short sequences in the same batch fit their slots.  The same with the backpointers split across launches."""
+    from pypore_amd import engine
+    model = _chain_model(20)
+    S, NE = len(model.states), sum(1 for s in model.states if not s.is_silent())
+    rng = np.random.default_rng(8)
+    seqs = [rng.normal(0, 0.5, n) for n in (50, 1, 2, 48, 0, 1, 55, 2)] + [np.array([2.0, 2.1, 1.9, 0.0])]
+    slot = [2 * (len(s) + 1) + (S - NE) + 1 for s in seqs]
+    c = O.Compiled(model)
+    for opts in ({}, {"hmm_bp_budget": 60 * S}):
+        with LG.options(engine.context(), **opts):
+            got = model.viterbi_batch(seqs)
+        lens = [len(p) if p is not None else 0 for _, p in got]
+        assert any(n > 5 * sl for n, sl in zip(lens, slot)) and any(0 < n <= sl for n, sl in zip(lens, slot))
+        for s, v in zip(seqs, got):
+            check_viterbi(c, s, v)
+
+
+def test_model_at_the_state_cap():
+    """Exactly HMM_S_MAX = 4096 states (64 KiB of LDS score rows): Viterbi, forward, backward and log_probability; one
+    state more is refused, naming the cap."""
+    model = O.line_model(4096)
+    assert len(model.states) == 4096
+    rng = np.random.default_rng(3)
+    check_all(model, [rng.normal(0, 3, n) for n in (0, 1, 3, 6)])
+    over = O.line_model(4097)
+    assert len(over.states) == 4097
+    with pytest.raises(ValueError, match="4096"):
+        over.viterbi([0.0])
+    with pytest.raises(ValueError, match="4096"):
+        over.log_probability_batch([[0.0]])

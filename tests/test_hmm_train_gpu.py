@@ -1,8 +1,8 @@
 """Model.train on the MI355X: the Baum-Welch E-step (ps_hmm_expect, csrc/seg_hmm.hpp hmm_expect_kernel) against the
 numpy oracle (tests/hmm_train_oracle.py) on brute-forceable models, random models with long silent chains, the
 54-position profile, infinite models, impossible and empty sequences and a ragged batch; launch splitting, determinism and
-the global-memory accumulator route; train() against the oracle's loop for both algorithms; decoding after training; the
-reference tutorial's flow.
+the global-memory accumulator route; many sequences per workgroup and a model at the state cap; train() against the
+oracle's loop for both algorithms; decoding after training; the reference tutorial's flow.
 
 Tolerances: counts and (W, A, B) to 1e-9 relative to max(|oracle|, 1); log probabilities to 1e-12; trained parameters and
 improvements to 1e-8."""
@@ -15,6 +15,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import hmm_oracle as O  # noqa: E402
 import hmm_train_oracle as T  # noqa: E402
+import launch_geometry as LG  # noqa: E402
 
 from pypore_amd.hmm import Model, NormalDistribution, State, UniformDistribution  # noqa: E402
 
@@ -240,3 +241,81 @@ def test_tutorial_flow_end_to_end(capsys):
     for e in events[:5]:
         want += O.viterbi(c, np.array([s.mean for s in Ev(e[:60]).segments]))[1]
     assert [i for i, _ in out] == want
+
+
+# ---- launch shapes of ps_hmm_expect -----------------------------------------------------------------------------------
+
+def _launch_cuts(lengths, S, budget):
+    """The first sequence of every launch after the first (hmm_expect_run: forward matrices within the budget, at least
+    one sequence per launch)."""
+    cuts, q0, n = [], 0, len(lengths)
+    while q0 < n:
+        b, q1 = (lengths[q0] + 1) * S * 8, q0 + 1
+        while q1 < n and b + (lengths[q1] + 1) * S * 8 <= budget:
+            b += (lengths[q1] + 1) * S * 8
+            q1 += 1
+        if q1 < n:
+            cuts.append(q1)
+        q0 = q1
+    return cuts
+
+
+_MANY = {}
+
+
+def _many_sequences():
+    """480 short sequences through a 12-position profile and the oracle's E-step of them (computed once)."""
+    if not _MANY:
+        model, means = O.profile_model(12, seed=31)
+        seqs = O.profile_events(means, 480, lo=4, hi=24, seed=32)
+        _MANY["case"] = model, seqs, T.estep(model, seqs)
+    return _MANY["case"]
+
+
+@pytest.mark.parametrize("acc_lds", [1, 0])
+def test_estep_many_sequences_per_workgroup(acc_lds, capfd, record_property):
+    """slots_pct 1 shrinks the E-step grid G to a handful of workgroups, so each one carries its score rows and its
+    accumulator row from sequence to sequence (both accumulator routes), and an hmm_fb_budget cuts the batch into launches
+    whose first sequences are not multiples of G (the `qs` start of hmm_expect_kernel).  Counts, (W, A, B) and logp match
+    the oracle, lie within 1e-12 of the default grid's, and two runs at the same options agree bit for bit."""
+    from pypore_amd import engine
+    model, seqs, (counts, stats, logp, skipped) = _many_sequences()
+    S, E, NE = len(model.states), len(model.edges), T.n_emit(model)
+    lds = (2 * S + (E + 3 * NE + 1 if acc_lds else 0)) * 8
+    ctx = engine.context()
+    with LG.options(ctx, hmm_expect_lds=acc_lds):
+        ref = model.expected_counts_batch(seqs)
+    capfd.readouterr()
+    with LG.options(ctx, hmm_expect_lds=acc_lds, slots_pct=1, debug=1):
+        small = model.expected_counts_batch(seqs)
+    (slots, pct), = LG.printed_slots(capfd.readouterr().err, lds)
+    G = min(len(seqs), slots)
+    assert pct == 1 and 2 <= G and len(seqs) >= 4 * G, G
+    lengths = [len(s) for s in seqs]
+    total = sum((n + 1) * S * 8 for n in lengths)
+    budget = next(b for b in (total // d for d in range(5, 40))
+                  if len(_launch_cuts(lengths, S, b)) >= 3 and any(q % G for q in _launch_cuts(lengths, S, b)))
+    record_property("geometry", {"G": G, "cuts": _launch_cuts(lengths, S, budget)})
+    with LG.options(ctx, hmm_expect_lds=acc_lds, slots_pct=1, hmm_fb_budget=budget):
+        cut = model.expected_counts_batch(seqs)
+        again = model.expected_counts_batch(seqs)
+    for got in (small, cut):
+        close(got.logp, logp, 1e-12)
+        assert got.skipped == skipped == 0
+        close(got.counts, counts, 1e-9)
+        close(got.stats, stats, 1e-9)
+        close(got.counts, ref.counts, 1e-12)
+        close(got.stats, ref.stats, 1e-12)
+        assert np.array_equal(got.logp, ref.logp)
+    for x, y in zip(cut[:3], again[:3]):
+        assert np.array_equal(x, y)
+
+
+def test_estep_at_the_state_cap():
+    """4096 states: two score rows fill 64 KiB, so the accumulators take the global-memory route."""
+    model = O.line_model(4096)
+    assert len(model.states) == 4096
+    assert (2 * 4096 + len(model.edges) + 3 * T.n_emit(model) + 1) * 8 > 64 << 10
+    rng = np.random.default_rng(6)
+    got = check_estep(model, [rng.normal(0, 3, n) for n in (0, 1, 2, 5, 3)])
+    assert got.skipped == 1                                # the empty sequence: start reaches end only through a state
