@@ -881,6 +881,14 @@ def to_device(current, quantum=None, offset=None, device=None, full_detect=False
       raises ValueError: nothing is ever rounded silently;
     * torch tensors (float32 / float64 / int16, host or device) are taken as they are (float64 must be exact in float32).
     """
+    return to_device_with_counts(current, quantum, offset, device, full_detect)[0]
+
+
+def to_device_with_counts(current, quantum=None, offset=None, device=None, full_detect=False):
+    """to_device, and how the caller's pA values x relate to the counts k the kernels read: None when x = fl(fl(k * quantum)
+    + offset) by construction (a file's counts, int16, a tensor, float samples on a power-of-two grid without an offset);
+    otherwise the counts (int64 numpy, on the host) that float samples went up as -- the caller's values are then their own
+    rounding of the grid, and only they can say which count a threshold falls on (detector_thresholds)."""
     from .grid import affine_grid, grid_of
     dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
     g = grid_of(current) if quantum is None else None
@@ -888,11 +896,11 @@ def to_device(current, quantum=None, offset=None, device=None, full_detect=False
         from .grid import Deferred
         if isinstance(current, Deferred) and current.counts is not None:
             # (a file's counts go up once: events cut from the file are stretches of the same device tensor)
-            return Samples(current.device_counts(dev, _int_counts_tensor), g[1], g[2])
-        return Samples(_int_counts_tensor(g[0], dev), g[1], g[2])
+            return Samples(current.device_counts(dev, _int_counts_tensor), g[1], g[2]), None
+        return Samples(_int_counts_tensor(g[0], dev), g[1], g[2]), None
     if isinstance(current, torch.Tensor) or np.asarray(current).dtype == np.int16:
         t, q = to_device_samples(current, quantum, device, full_detect)
-        return Samples(t, q, 0.0 if offset is None else float(offset))
+        return Samples(t, q, 0.0 if offset is None else float(offset)), None
     a = np.asarray(current)
     if a.ndim != 1:
         raise ValueError("Buffer has wrong number of dimensions (expected 1, got %d)" % a.ndim)
@@ -902,19 +910,76 @@ def to_device(current, quantum=None, offset=None, device=None, full_detect=False
     pow2 = quantum is not None and quantum > 0 and np.log2(quantum) == np.rint(np.log2(quantum))
     if quantum is None or pow2:
         try:
-            t, q = to_device_samples(a - off if off else a, quantum, device, full_detect)
-            return Samples(t, q, off)
+            shifted = a - off if off else a
+            t, q = to_device_samples(shifted, quantum, device, full_detect)
+            return Samples(t, q, off), (np.rint(shifted / q).astype(np.int64) if off else None)
         except ValueError:
             if quantum is not None:
                 raise
     if quantum is None:                             # no power-of-two grid: any scale and offset (a real .abf header)
         q, o, k = affine_grid(a)
-        return Samples(_int_counts_tensor(k, dev), q, o)
+        return Samples(_int_counts_tensor(k, dev), q, o), k
     k = (a.astype(np.float64) - off) / float(quantum)
     kr = np.rint(k)
     if a.size and np.max(np.abs(k - kr)) > 1e-6:
         raise ValueError("samples are not integer multiples of quantum=%r above offset=%r" % (quantum, off))
-    return Samples(_int_counts_tensor(kr.astype(np.int64), dev), float(quantum), off)
+    kr = kr.astype(np.int64)
+    return Samples(_int_counts_tensor(kr, dev), float(quantum), off), kr
+
+
+def _first_count(pred, guess):
+    """The smallest integer k (within +-2^31) with pred(k), for a predicate that is monotone in k, found by a walk from guess."""
+    lim = 2147483000
+    k = max(-lim, min(lim, guess))
+    while k > -lim and pred(k - 1):
+        k -= 1
+    while k < lim and not pred(k):
+        k += 1
+    return k
+
+
+def _count_threshold(q, t, offset, strict):
+    """(first - 0.5) * q, first the smallest count k with fl(fl(k q) + offset) >= t (strict: > t); t - offset where there
+    is nothing to round (offset 0: fl(k q) itself is the caller's value) or no count to find (t or q not finite, q <= 0)."""
+    if offset == 0.0 or not (np.isfinite(t) and np.isfinite(q) and q > 0.0):
+        return t - offset
+    g = max(-2.0 ** 31, min(2.0 ** 31, (t - offset) / q))      # (a huge t: the walk starts, and stays, at the clamp)
+    if strict:
+        first = _first_count(lambda k: float(k) * q + offset > t, int(np.floor(g)) + 1)
+    else:
+        first = _first_count(lambda k: float(k) * q + offset >= t, int(np.ceil(g)))
+    return (first - 0.5) * q
+
+
+def detector_thresholds(quantum, threshold, min_current, offset=0.0, values=None, counts=None):
+    """The detector's thresholds as the library must receive them.  The kernels test double(k) * quantum < threshold and
+    > min_current on the counts k; the caller's rule is x < threshold and x > min_current on the pA values x it holds.
+    Both are monotone in k, so each rule is k < kthr (k > kmin) for one integer, and the library is handed
+    (kthr - 0.5) * quantum and (kmin + 0.5) * quantum: half a count from every count, the test is exact for |k| < 2^31.
+
+    values / counts None: x = fl(fl(k * quantum) + offset), as GridArray.from_counts and abf.read_abf compute it (a file, a
+    device tensor, int16 counts); with offset 0 the kernel's own product is x and the thresholds go through unchanged, and
+    a threshold that is not finite (min_current=-inf: the rule off) moves by the offset as it is.  Otherwise the caller's
+    samples and the counts they went up as (to_device_with_counts): the thresholds are read off the data, and None is
+    returned when the data are not monotone in k across a threshold (no count-space threshold reproduces x < threshold)."""
+    threshold, min_current, q = float(threshold), float(min_current), float(quantum)
+    if values is None:
+        offset = float(offset)
+        return _count_threshold(q, threshold, offset, False), _count_threshold(q, min_current, offset, True)
+    x = np.asarray(values)
+    k = np.asarray(counts, dtype=np.int64)
+    out = []
+    for hit in (x >= threshold, x > min_current):          # k_thr: first count at or above the threshold; k_min + 1: first above min_current
+        if hit.all():
+            first = int(k.min()) if k.size else 0
+        elif not hit.any():
+            first = int(k.max()) + 1
+        else:
+            first = int(k[hit].min())
+            if int(k[~hit].max()) >= first:                # the same count on both sides of the rule
+                return None
+        out.append((first - 0.5) * q)
+    return tuple(out)
 
 
 def to_device_samples(current, quantum=None, device=None, full_detect=False):

@@ -88,7 +88,9 @@ class lambda_event_parser(parser):
         pieces).  Custom rules are Python callables on Segment objects and run on the host over numpy pieces."""
         if self._builtin:
             return self._parse_device(current, quantum, device, offset)
-        x = np.asarray(current)
+        return self._parse_host(np.asarray(current))
+
+    def _parse_host(self, x):
         below = x < self.threshold
         cuts = np.flatnonzero(below[1:] != below[:-1]) + 1
         edges = np.concatenate(([0], cuts, [x.shape[0]]))
@@ -97,11 +99,19 @@ class lambda_event_parser(parser):
 
     def _parse_device(self, current, quantum, device, offset):
         from . import engine
-        s = engine.to_device(current, quantum, offset, device)
-        # the kernel compares count * quantum with its arguments: take the offset to the other side
+        s, counts = engine.to_device_with_counts(current, quantum, offset, device)
+        # the kernel compares count * quantum with its arguments: the rules on the caller's pA values become thresholds in
+        # count space (engine.detector_thresholds) -- from the formula the values came from (a file's counts, int16, a device
+        # tensor, float samples on a power-of-two grid), or, for float samples that went up as the counts of another grid or
+        # with an offset, from the samples and those counts
+        if counts is None:
+            thr = engine.detector_thresholds(s.quantum, self.threshold, self.MIN_CURRENT, offset=s.offset)
+        else:
+            thr = engine.detector_thresholds(s.quantum, self.threshold, self.MIN_CURRENT, values=current, counts=counts)
+            if thr is None:                          # not monotone in the counts at a threshold: the rules on the host
+                return self._parse_host(np.asarray(current))
         starts, lens = engine.context(device).detect_events(
-            s.tensor, s.quantum, threshold=float(self.threshold) - s.offset, min_duration=self.MIN_DURATION,
-            min_current=self.MIN_CURRENT - s.offset)
+            s.tensor, s.quantum, threshold=thr[0], min_duration=self.MIN_DURATION, min_current=thr[1])
         if hasattr(current, "is_cuda"):             # device tensor in: the events' values come back as pA
             host = s.tensor.cpu().numpy().astype(np.float64)
             if not s.tensor.dtype.is_floating_point:

@@ -17,12 +17,14 @@ def segment_file_trace(samples, quantum, params=None, threshold=90.0, min_durati
     ctx = ctx or engine.context(device)
     if params is None:
         params = _lib.split_params(prior_segments_per_second=10.)
+    # the caller's rule x < threshold on x = fl(fl(k * quantum) + offset), as the kernels' test on the counts k
+    thr, mc = engine.detector_thresholds(quantum, threshold, min_current, offset=offset)
     if single_pass:
         # one library call, one pass over the samples: K0 over the whole trace serves the detector and every event (round 6)
-        st, ln, bounds, boff, stats = ctx.detect_segment_trace(samples, quantum, params, threshold - offset, min_duration,
-                                                               min_current - offset, offset_counts, want_stats)
+        st, ln, bounds, boff, stats = ctx.detect_segment_trace(samples, quantum, params, thr, min_duration, mc,
+                                                               offset_counts, want_stats)
     else:
-        st, ln = ctx.detect_events(samples, quantum, threshold - offset, min_duration, min_current - offset, offset_counts)
+        st, ln = ctx.detect_events(samples, quantum, thr, min_duration, mc, offset_counts)
         bounds, boff, stats = ctx.segment_events(samples, st, ln, params, quantum, offset_counts, want_stats)
     if stats is not None and offset:
         stats[:, 0] += offset; stats[:, 2] += offset; stats[:, 3] += offset
