@@ -7,7 +7,7 @@ from pypore_amd import engine
 
 # the library's own defaults (csrc/poreseg.hip ps_ctx) of the options these tests change
 LIBRARY_DEFAULTS = {"debug": 0, "slots_pct": 100, "hmm_bp_budget": 512 << 20, "hmm_fb_budget": 4 << 30,
-                    "hmm_expect_lds": 1}
+                    "hmm_expect_lds": 1, "filter_fused": 1}
 
 _SLOTS = re.compile(r"\[poreseg\] resident slots: (\d+) \((\d+) threads, dynamic LDS (\d+), slots_pct (\d+)\)")
 
