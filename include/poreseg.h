@@ -138,7 +138,8 @@ int ps_set_tiling(ps_ctx *ctx, int64_t tile_len, int64_t halo);
  * "debug" 1: the library reports on stderr which occupancy it found, the resident slots every launch sized by them gets, and
  * which seams gave up (prints only);
  * "slots_pct" 1..100 (default 100) share of the resident wave slots the kernels of up to 256 threads that are sized by them
- * (the scan kernels, the aligner, the HMM E-step) are launched on, from the next launch on;
+ * (the scan kernels, the aligner, the pairwise aligner, the HMM E-step) are launched on, from the next launch on;
+ * "pairwise_budget" bytes of score / pointer scratch per launch of ps_pairwise_batch (default 2 GiB);
  * "tree_jobs_per_wave" (default 4) subtree kernel: jobs / this many of its slots work, between half and all of them;
  * "noise_k_ppm" (default 100 000 = 0.1): near-tie accounting of the 64-bit digest, margin factor in millionths;
  * "near_tie_log" n (default 65 536, 0 .. 2^30): records of the near-tie log that ps_get_near_ties reads (16 bytes each, device
@@ -322,6 +323,45 @@ int ps_align_batch(ps_ctx *ctx, const double *h_model_means, const double *h_mod
                    int32_t m, double skip_penalty, double backslip_penalty, const double *d_seq_means,
                    const double *d_seq_stds, const double *d_seq_durs, const int64_t *h_seq_off, int32_t n_seq,
                    double *d_scores, uint32_t *d_paths, int32_t *d_status);
+
+/* Replaces PairwiseAligner(x, y) (alignment.py:97-313): Needleman-Wunsch, Smith-Waterman and the repeated local traceback
+ * over two sequences of segment means.  Sequences are two sets, A (the x side, rows) and B (the y side, columns): set A is
+ * d_a[h_a_off[k] .. h_a_off[k+1]) for k < n_a (fp64, device), B likewise; a NaN element is the gap marker '-' and scores 0
+ * against everything (_score, :112-115), every other cell scores 3 - |x - y|^2 with the square taken by product.  A y of at
+ * most 8190 elements (PS_ERR_ARG beyond); x is bounded by the scratch only.  All arithmetic is fp64 without contraction, and
+ * the candidates of a cell are compared in the reference's order (first one wins), so results do not depend on the launch.
+ *
+ * ps_pairwise_scores: every pair of A x B on the score-only route (no matrix leaves the chip).  d_scores[k * n_b + l] =
+ *   score[m][n] for PS_PW_GLOBAL, the maximum of the matrix for PS_PW_LOCAL; d_pos (optional, local only): two ints per
+ *   pair, the row-major-first cell (i, j) holding that maximum, (0, 0) when no cell is above 0.
+ *
+ * ps_pairwise_batch: pair q = (A[h_pair_a[q]], B[h_pair_b[q]]), with traceback.  d_status[q]: PS_PW_OK, or
+ *   PS_PW_INDEX_ERROR where the reference raises IndexError -- the local traceback marks the mirrored cell [j, i] of every
+ *   cell it walks, which lies outside an m x n matrix when j > m or i > n (:229), and it reads xalign[-1] of an alignment
+ *   that is empty or was trimmed to nothing (:246).  d_scores[q]: score[m][n] (global) or the maximum of the matrix.
+ *   Alignments are index columns in WALK order (the alignment's last column first): d_cols_i / d_cols_j hold the 0-based
+ *   element of x / y or -1 for a gap, pair q's columns in slot [h_col_off[q], h_col_off[q+1]); d_col_need[q] = the columns
+ *   its alignments take.  Per alignment a of pair q, in slot h_aln_off[q] + a: d_aln_score, d_aln_start (first column
+ *   within the pair's slot) and d_aln_len; d_aln_count[q] = alignments completed -- 1 for global, 0 or 1 for local, for
+ *   PS_PW_LOCAL_REPEATED every alignment of at least min_length columns (counted before the trim) in the order the
+ *   reference yields them, also those completed before a PS_PW_INDEX_ERROR.  When a slot of either kind is too small,
+ *   PS_ERR_CAPACITY is returned: d_col_need and d_aln_count hold what every pair takes, the caller grows the slots and
+ *   calls again.  The score matrix (fp64) and a pointer byte per cell live in a scratch per resident workgroup; the batch is
+ *   split into launches whose scratch stays within option "pairwise_budget" bytes (default 2 GiB; a pair that needs more
+ *   runs alone, up to 32 GiB).  Both calls synchronise the context's stream before returning. */
+#define PS_PW_GLOBAL          0
+#define PS_PW_LOCAL           1
+#define PS_PW_LOCAL_REPEATED  2
+#define PS_PW_OK              0
+#define PS_PW_INDEX_ERROR     1
+int ps_pairwise_scores(ps_ctx *ctx, const double *d_a, const int64_t *h_a_off, int32_t n_a, const double *d_b,
+                       const int64_t *h_b_off, int32_t n_b, int32_t mode, double penalty, double *d_scores, int32_t *d_pos);
+int ps_pairwise_batch(ps_ctx *ctx, const double *d_a, const int64_t *h_a_off, int32_t n_a, const double *d_b,
+                      const int64_t *h_b_off, int32_t n_b, const int32_t *h_pair_a, const int32_t *h_pair_b, int32_t n_pairs,
+                      int32_t mode, double penalty, int32_t min_length, double *d_scores, int32_t *d_status,
+                      const int64_t *h_col_off, int32_t *d_cols_i, int32_t *d_cols_j, int32_t *d_col_need,
+                      const int64_t *h_aln_off, double *d_aln_score, int32_t *d_aln_start, int32_t *d_aln_len,
+                      int32_t *d_aln_count);
 
 /* A baked hidden Markov model (pypore_amd.hmm.Model.bake), host arrays.  States [0, n_emit) emit, states [n_emit, n_states)
  * are silent and grouped by topological level: level L is [level_ptr[L], level_ptr[L+1]), level_ptr[0] = n_emit,

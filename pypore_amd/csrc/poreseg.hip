@@ -28,6 +28,7 @@
 #include "poreseg.h"
 #include "seg_device.hpp"
 #include "seg_align.hpp"
+#include "seg_pairwise.hpp"
 #include "seg_hmm.hpp"
 
 using namespace ps;
@@ -156,6 +157,8 @@ struct ps_ctx {
     } tile_cache;
     DevBuf bsum, ev_info, chunk_mabs, ev_boff, blk_mm, grp, filt_fwd, filt_agg, filt_zin, up_dev;
     DevBuf align_in, align_scratch;
+    DevBuf pw_in, pw_scratch; // pairwise aligner (ps_pairwise_scores / ps_pairwise_batch): offsets and pair tables, per-workgroup matrices
+    long long pw_budget = 2ll << 30;         // option pairwise_budget: bytes of pairwise scratch per launch
     DevBuf ev_info_tr;        // single-pass file route (ps_detect_segment_trace): (centre, phase, first block) of the events cut out of a trace-aligned digest
     DevBuf blk_cls, cls_mm;   // ... K0's verdict per block against the detector's threshold (2 bits), min / max per 128 blocks
     DevBuf pre_c;             // exact route (ps_segment_exact_f64): c and c2 of the call's samples, 16 B per sample
@@ -1317,7 +1320,7 @@ void ps_destroy(ps_ctx *ctx)
                       &ctx->tile_i32, &ctx->sp_off, &ctx->spine_items, &ctx->asm_hdr, &ctx->ev_first_tile, &ctx->ev_len,
                       &ctx->det_counts, &ctx->det_tics, &ctx->det_cand, &ctx->bsum, &ctx->ev_info, &ctx->chunk_mabs,
                       &ctx->ev_boff, &ctx->blk_mm, &ctx->grp, &ctx->filt_fwd, &ctx->filt_agg, &ctx->filt_zin, &ctx->up_dev,
-                      &ctx->align_in, &ctx->align_scratch, &ctx->bridge_ext, &ctx->ext_slot, &ctx->ext_list,
+                      &ctx->align_in, &ctx->align_scratch, &ctx->pw_in, &ctx->pw_scratch, &ctx->bridge_ext, &ctx->ext_slot, &ctx->ext_list,
                       &ctx->lat_state, &ctx->lat_seam, &ctx->lat_res, &ctx->pre_c, &ctx->ev_info_tr, &ctx->blk_cls,
                       &ctx->cls_mm, &ctx->nt_log, &ctx->hmm_model, &ctx->hmm_off, &ctx->hmm_bp,
                       &ctx->hmm_last, &ctx->hmm_flags, &ctx->hmm_fmat, &ctx->hmm_acc, &ctx->hmm_skip};
@@ -1398,6 +1401,7 @@ int ps_set_option(ps_ctx *ctx, const char *name, int64_t value)
     }
     else if (n == "hmm_bp_budget" && value >= 1) ctx->hmm_bp_budget = value;
     else if (n == "hmm_fb_budget" && value >= 1) ctx->hmm_fb_budget = value;
+    else if (n == "pairwise_budget" && value >= 1) ctx->pw_budget = value;
     else if (n == "hmm_expect_lds") ctx->hmm_expect_lds = value != 0;
     else if (n == "single_pass") ctx->single_pass = value != 0;
     else if (n == "gather_fused") ctx->gather_fused = value != 0;
@@ -2626,6 +2630,168 @@ int ps_align_batch(ps_ctx *ctx, const double *h_model_means, const double *h_mod
                        d_off, n_seq, ctx->align_scratch.as<double>(), static_cast<long long>(per_wg), B, d_scores, d_paths, d_status);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return PS_OK;
+}
+
+namespace {
+
+// offsets of a set of sequences: non-negative, ascending; *longest = the longest sequence
+int pw_check_off(ps_ctx *ctx, const int64_t *off, int32_t n, const char *what, int64_t *longest)
+{
+    *longest = 0;
+    for (int32_t q = 0; q < n; ++q) {
+        const int64_t len = off[q + 1] - off[q];
+        if (len < 0 || off[q] < 0) return fail(ctx, PS_ERR_ARG, "%s offsets must be non-negative and ascending", what);
+        if (len > INT32_MAX / 2) return fail(ctx, PS_ERR_ARG, "%s sequence %d too long", what, q);
+        *longest = std::max(*longest, len);
+    }
+    return PS_OK;
+}
+
+}  // namespace
+
+int ps_pairwise_scores(ps_ctx *ctx, const double *d_a, const int64_t *h_a_off, int32_t n_a, const double *d_b,
+                       const int64_t *h_b_off, int32_t n_b, int32_t mode, double penalty, double *d_scores, int32_t *d_pos)
+{
+    if (!ctx) return PS_ERR_ARG;
+    if (!h_a_off || !h_b_off) return fail(ctx, PS_ERR_ARG, "null pointer");
+    if (mode != PS_PW_GLOBAL && mode != PS_PW_LOCAL) return fail(ctx, PS_ERR_ARG, "ps_pairwise_scores: mode %d is neither global nor local", mode);
+    if (n_a < 0 || n_b < 0) return fail(ctx, PS_ERR_ARG, "negative sequence count");
+    if (!std::isfinite(penalty)) return fail(ctx, PS_ERR_ARG, "the penalty must be finite");
+    if (n_a == 0 || n_b == 0) return PS_OK;
+    if (!d_scores) return fail(ctx, PS_ERR_ARG, "null output pointer");
+    int64_t m_max = 0, n_max = 0;
+    if (int rc = pw_check_off(ctx, h_a_off, n_a, "A", &m_max)) return rc;
+    if (int rc = pw_check_off(ctx, h_b_off, n_b, "B", &n_max)) return rc;
+    if (n_max > PW_N_MAX) return fail(ctx, PS_ERR_ARG, "a B sequence of %lld elements: the device pairwise aligner takes up to %d", (long long)n_max, PW_N_MAX);
+    if ((h_a_off[n_a] > 0 && !d_a) || (h_b_off[n_b] > 0 && !d_b)) return fail(ctx, PS_ERR_ARG, "null sequence pointer");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t na_b = (static_cast<size_t>(n_a) + 1) * sizeof(int64_t), nb_b = (static_cast<size_t>(n_b) + 1) * sizeof(int64_t);
+    HIP_TRY(ctx, ctx->h_up.reserve(na_b + nb_b));
+    HIP_TRY(ctx, ctx->pw_in.reserve(na_b + nb_b));
+    std::memcpy(ctx->h_up.p, h_a_off, na_b);
+    std::memcpy(static_cast<char *>(ctx->h_up.p) + na_b, h_b_off, nb_b);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->pw_in.p, ctx->h_up.p, na_b + nb_b, hipMemcpyHostToDevice, ctx->stream));
+    const long long *da_off = ctx->pw_in.as<long long>(), *db_off = da_off + n_a + 1;
+    const int n_cap = static_cast<int>(std::max<int64_t>(n_max, 1));
+    const size_t lds = pw_lds_bytes(n_cap);
+    const long long jobs = static_cast<long long>(n_a) * n_b;
+    auto launch = [&](auto kernel) -> int {
+        HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(kernel), static_cast<int>(lds)));
+        const unsigned grid = static_cast<unsigned>(std::min<long long>(jobs, resident_slots(ctx, kernel, PW_NT, lds)));
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(PW_NT), lds, ctx->stream, d_a, da_off, n_a, d_b, db_off, n_b, penalty, n_cap,
+                           d_scores, d_pos);
+        return PS_OK;
+    };
+    if (int rc = mode == PS_PW_LOCAL ? launch(pw_score_kernel<true>) : launch(pw_score_kernel<false>)) return rc;
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return PS_OK;
+}
+
+int ps_pairwise_batch(ps_ctx *ctx, const double *d_a, const int64_t *h_a_off, int32_t n_a, const double *d_b,
+                      const int64_t *h_b_off, int32_t n_b, const int32_t *h_pair_a, const int32_t *h_pair_b, int32_t n_pairs,
+                      int32_t mode, double penalty, int32_t min_length, double *d_scores, int32_t *d_status,
+                      const int64_t *h_col_off, int32_t *d_cols_i, int32_t *d_cols_j, int32_t *d_col_need,
+                      const int64_t *h_aln_off, double *d_aln_score, int32_t *d_aln_start, int32_t *d_aln_len,
+                      int32_t *d_aln_count)
+{
+    if (!ctx) return PS_ERR_ARG;
+    if (!h_a_off || !h_b_off || !h_col_off || !h_aln_off) return fail(ctx, PS_ERR_ARG, "null pointer");
+    if (mode != PS_PW_GLOBAL && mode != PS_PW_LOCAL && mode != PS_PW_LOCAL_REPEATED) return fail(ctx, PS_ERR_ARG, "unknown mode %d", mode);
+    if (n_a < 0 || n_b < 0 || n_pairs < 0) return fail(ctx, PS_ERR_ARG, "negative count");
+    if (!std::isfinite(penalty)) return fail(ctx, PS_ERR_ARG, "the penalty must be finite");
+    if (n_pairs == 0) return PS_OK;
+    if (!h_pair_a || !h_pair_b) return fail(ctx, PS_ERR_ARG, "null pair table");
+    if (!d_scores || !d_status || !d_cols_i || !d_cols_j || !d_col_need || !d_aln_score || !d_aln_start || !d_aln_len || !d_aln_count)
+        return fail(ctx, PS_ERR_ARG, "null output pointer");
+    int64_t m_max = 0, n_max = 0;
+    if (int rc = pw_check_off(ctx, h_a_off, n_a, "A", &m_max)) return rc;
+    if (int rc = pw_check_off(ctx, h_b_off, n_b, "B", &n_max)) return rc;
+    if ((h_a_off[n_a] > 0 && !d_a) || (h_b_off[n_b] > 0 && !d_b)) return fail(ctx, PS_ERR_ARG, "null sequence pointer");
+    for (int32_t q = 0; q < n_pairs; ++q) {
+        if (h_pair_a[q] < 0 || h_pair_a[q] >= n_a || h_pair_b[q] < 0 || h_pair_b[q] >= n_b) return fail(ctx, PS_ERR_ARG, "pair %d names a sequence that is not there", q);
+        if (h_col_off[q] < 0 || h_col_off[q + 1] < h_col_off[q] || h_aln_off[q] < 0 || h_aln_off[q + 1] < h_aln_off[q])
+            return fail(ctx, PS_ERR_ARG, "slot offsets must be non-negative and ascending");
+        const int64_t m = h_a_off[h_pair_a[q] + 1] - h_a_off[h_pair_a[q]], n = h_b_off[h_pair_b[q] + 1] - h_b_off[h_pair_b[q]];
+        if (n > PW_N_MAX) return fail(ctx, PS_ERR_ARG, "pair %d: y of %lld elements, the device pairwise aligner takes up to %d", q, (long long)n, PW_N_MAX);
+        if (m * n > INT32_MAX) return fail(ctx, PS_ERR_ARG, "pair %d: %lld x %lld cells, 2^31 - 1 at most", q, (long long)m, (long long)n);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // one upload: the four 8-byte tables, the two pair tables, the capacity flag
+    const size_t na = static_cast<size_t>(n_a) + 1, nb = static_cast<size_t>(n_b) + 1, np = static_cast<size_t>(n_pairs);
+    const size_t b8 = (na + nb + 2 * (np + 1)) * sizeof(int64_t), bytes = b8 + (2 * np + 2) * sizeof(int32_t);
+    HIP_TRY(ctx, ctx->h_up.reserve(bytes));
+    HIP_TRY(ctx, ctx->pw_in.reserve(bytes));
+    {
+        int64_t *h = ctx->h_up.as<int64_t>();
+        std::memcpy(h, h_a_off, na * 8); std::memcpy(h + na, h_b_off, nb * 8);
+        std::memcpy(h + na + nb, h_col_off, (np + 1) * 8); std::memcpy(h + na + nb + np + 1, h_aln_off, (np + 1) * 8);
+        int32_t *hi = reinterpret_cast<int32_t *>(h + na + nb + 2 * (np + 1));
+        std::memcpy(hi, h_pair_a, np * 4); std::memcpy(hi + np, h_pair_b, np * 4);
+        hi[2 * np] = 0; hi[2 * np + 1] = 0;
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->pw_in.p, ctx->h_up.p, bytes, hipMemcpyHostToDevice, ctx->stream));
+    PwBatch P;
+    P.a = d_a; P.b = d_b;
+    P.a_off = ctx->pw_in.as<long long>(); P.b_off = P.a_off + na; P.col_off = P.b_off + nb; P.aln_off = P.col_off + np + 1;
+    int *di = reinterpret_cast<int *>(const_cast<long long *>(P.aln_off + np + 1));
+    P.pair_a = di; P.pair_b = di + np; P.flag = di + 2 * np;
+    P.mode = mode; P.min_length = min_length; P.penalty = penalty;
+    P.scores = d_scores; P.status = d_status; P.cols_i = d_cols_i; P.cols_j = d_cols_j; P.col_need = d_col_need;
+    P.aln_score = d_aln_score; P.aln_start = d_aln_start; P.aln_len = d_aln_len; P.aln_count = d_aln_count;
+    // Launches: consecutive pairs while the scratch of their launch -- one matrix of the launch's largest pair per workgroup,
+    // a workgroup per pair up to the resident slots -- stays within the budget; a launch whose first pair alone leaves room
+    // for few matrices runs on that many workgroups
+    const unsigned long long budget = static_cast<unsigned long long>(std::max<long long>(1, ctx->pw_budget));
+    auto dims = [&](int32_t q, unsigned long long *cells, unsigned long long *rows, int *n) {
+        const int64_t m = h_a_off[h_pair_a[q] + 1] - h_a_off[h_pair_a[q]];
+        *n = static_cast<int>(h_b_off[h_pair_b[q] + 1] - h_b_off[h_pair_b[q]]);
+        *cells = static_cast<unsigned long long>(m) * static_cast<unsigned long long>(*n); *rows = static_cast<unsigned long long>(m);
+    };
+    for (int32_t q0 = 0; q0 < n_pairs;) {
+        unsigned long long cells = 1, rows = 1; int n_cap = 1;
+        int32_t q1 = q0;
+        unsigned slots = 0;
+        while (q1 < n_pairs) {
+            unsigned long long c, r; int n;
+            dims(q1, &c, &r, &n);
+            const unsigned long long c2 = std::max(cells, c), r2 = std::max(rows, r);
+            const int n2 = std::max(n_cap, n);
+            if (q1 > q0 && (c > cells || r > rows)) {
+                // a pair that enlarges the launch's matrix joins it only while the launch stays within the budget (the slots
+                // of the launch so far bound the grid; a longer y only lowers them)
+                const unsigned long long g = std::min<unsigned long long>(static_cast<unsigned long long>(q1 - q0) + 1, slots);
+                if (g * pw_scratch_bytes(c2, r2) > budget) break;
+            }
+            cells = c2; rows = r2; n_cap = n2; ++q1;
+            if (q1 == q0 + 1) {
+                const size_t lds1 = pw_lds_bytes(n_cap);
+                slots = mode == PS_PW_GLOBAL ? resident_slots(ctx, pw_batch_kernel<false>, PW_NT, lds1) : resident_slots(ctx, pw_batch_kernel<true>, PW_NT, lds1);
+            }
+        }
+        const unsigned long long per_wg = pw_scratch_bytes(cells, rows);
+        if (per_wg > (32ull << 30)) return fail(ctx, PS_ERR_ARG, "pair %d needs more than 32 GiB of scratch", q0);
+        const size_t lds = pw_lds_bytes(n_cap);
+        const int nq = q1 - q0;
+        auto launch = [&](auto kernel) -> int {
+            HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(kernel), static_cast<int>(lds)));
+            unsigned grid = std::min<unsigned>(static_cast<unsigned>(nq), resident_slots(ctx, kernel, PW_NT, lds));
+            grid = static_cast<unsigned>(std::max<unsigned long long>(1, std::min<unsigned long long>(grid, budget / per_wg)));
+            HIP_TRY(ctx, ctx->pw_scratch.reserve(static_cast<size_t>(grid) * per_wg));
+            if (ctx->debug) fprintf(stderr, "[poreseg] pairwise launch: pairs %d..%d, grid %u, %llu bytes of scratch per workgroup, dynamic LDS %zu\n", q0, q1, grid, per_wg, lds);
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(PW_NT), lds, ctx->stream, P, q0, nq, n_cap, ctx->pw_scratch.as<unsigned char>(),
+                               per_wg, cells, rows);
+            return PS_OK;
+        };
+        if (int rc = mode == PS_PW_GLOBAL ? launch(pw_batch_kernel<false>) : launch(pw_batch_kernel<true>)) return rc;
+        HIP_TRY(ctx, hipGetLastError());
+        q0 = q1;
+    }
+    int flag = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&flag, P.flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (flag) return fail(ctx, PS_ERR_CAPACITY, "an alignment slot is too small (d_col_need and d_aln_count hold what the pairs take)");
     return PS_OK;
 }
 

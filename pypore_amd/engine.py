@@ -459,6 +459,79 @@ class Context(object):
         return scores[:n_seq], paths[:int(off[-1])], status[:n_seq]
 
     @_serialised
+    def pairwise_scores(self, a, a_off, b, b_off, mode, penalty, want_pos=False):
+        """ps_pairwise_scores: every pair of the sequence sets A x B on the score-only route.  a, b: float64 CUDA tensors
+        (NaN: the gap marker), set k of A = a[a_off[k]:a_off[k+1]].  Returns (scores float64 [n_a, n_b], positions int32
+        [n_a, n_b, 2] of the local maximum or None)."""
+        a_off = np.ascontiguousarray(a_off, dtype=np.int64)
+        b_off = np.ascontiguousarray(b_off, dtype=np.int64)
+        n_a, n_b = a_off.size - 1, b_off.size - 1
+        for t in (a, b):
+            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float64
+        dev = a.device
+        scores = torch.zeros((n_a, n_b), dtype=torch.float64, device=dev)
+        pos = torch.zeros((n_a, n_b, 2), dtype=torch.int32, device=dev) if want_pos else None
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        torch.cuda.current_stream(dev).synchronize()
+        _lib.check(self.L.ps_pairwise_scores(self.handle, ctypes.c_void_p(a.data_ptr()), a_off.ctypes.data_as(i64p), n_a,
+                                             ctypes.c_void_p(b.data_ptr()), b_off.ctypes.data_as(i64p), n_b, int(mode),
+                                             float(penalty), ctypes.c_void_p(scores.data_ptr() if scores.numel() else 0),
+                                             ctypes.c_void_p(pos.data_ptr() if pos is not None and pos.numel() else 0)),
+                   self.handle)
+        return scores, pos
+
+    @_serialised
+    def pairwise_batch(self, a, a_off, b, b_off, pair_a, pair_b, mode, penalty, min_length=2, col_slots=None,
+                       aln_slots=None):
+        """ps_pairwise_batch: pair q = (A[pair_a[q]], B[pair_b[q]]) with traceback.  Returns numpy arrays: (scores [n],
+        status [n], cols_i, cols_j (index columns in walk order, -1 a gap), col_off [n + 1], aln_score, aln_start, aln_len,
+        aln_off [n + 1], aln_count [n]).  Slots that turn out too small (PS_ERR_CAPACITY) make the call run again with
+        the sizes the first run reported."""
+        a_off = np.ascontiguousarray(a_off, dtype=np.int64)
+        b_off = np.ascontiguousarray(b_off, dtype=np.int64)
+        pair_a = np.ascontiguousarray(pair_a, dtype=np.int32)
+        pair_b = np.ascontiguousarray(pair_b, dtype=np.int32)
+        n = pair_a.size
+        assert pair_b.size == n
+        for t in (a, b):
+            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float64
+        dev = a.device
+        if n and (pair_a.min() < 0 or pair_a.max() >= a_off.size - 1 or pair_b.min() < 0 or pair_b.max() >= b_off.size - 1):
+            raise ValueError("a pair names a sequence that is not there")
+        m_len = np.diff(a_off)[pair_a] if n else np.zeros(0, np.int64)
+        n_len = np.diff(b_off)[pair_b] if n else np.zeros(0, np.int64)
+        if col_slots is None:       # global and local alignments have at most m + n columns; repeated ones are re-run if they need more
+            col_slots = (m_len + n_len) * (1 if mode != _lib.PS_PW_LOCAL_REPEATED else 2)
+        if aln_slots is None:
+            aln_slots = np.ones(n, np.int64) if mode != _lib.PS_PW_LOCAL_REPEATED else np.minimum(m_len, n_len) + 1
+        scores = torch.zeros(max(n, 1), dtype=torch.float64, device=dev)
+        status, col_need, aln_count = (torch.zeros(max(n, 1), dtype=torch.int32, device=dev) for _ in range(3))
+        i64p, i32p = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)
+        torch.cuda.current_stream(dev).synchronize()
+        for attempt in range(2):
+            col_off = np.concatenate(([0], np.cumsum(col_slots))).astype(np.int64)
+            aln_off = np.concatenate(([0], np.cumsum(aln_slots))).astype(np.int64)
+            cols = torch.zeros((2, max(int(col_off[-1]), 1)), dtype=torch.int32, device=dev)
+            aln_score = torch.zeros(max(int(aln_off[-1]), 1), dtype=torch.float64, device=dev)
+            aln_il = torch.zeros((2, max(int(aln_off[-1]), 1)), dtype=torch.int32, device=dev)
+            rc = self.L.ps_pairwise_batch(
+                self.handle, ctypes.c_void_p(a.data_ptr()), a_off.ctypes.data_as(i64p), a_off.size - 1,
+                ctypes.c_void_p(b.data_ptr()), b_off.ctypes.data_as(i64p), b_off.size - 1, pair_a.ctypes.data_as(i32p),
+                pair_b.ctypes.data_as(i32p), n, int(mode), float(penalty), int(min_length), ctypes.c_void_p(scores.data_ptr()),
+                ctypes.c_void_p(status.data_ptr()), col_off.ctypes.data_as(i64p), ctypes.c_void_p(cols[0].data_ptr()),
+                ctypes.c_void_p(cols[1].data_ptr()), ctypes.c_void_p(col_need.data_ptr()), aln_off.ctypes.data_as(i64p),
+                ctypes.c_void_p(aln_score.data_ptr()), ctypes.c_void_p(aln_il[0].data_ptr()),
+                ctypes.c_void_p(aln_il[1].data_ptr()), ctypes.c_void_p(aln_count.data_ptr()))
+            if rc != _lib.PS_ERR_CAPACITY or attempt:
+                break
+            col_slots = col_need[:n].cpu().numpy().astype(np.int64)       # the exact sizes
+            aln_slots = aln_count[:n].cpu().numpy().astype(np.int64)
+        _lib.check(rc, self.handle)
+        cols, aln_il = cols.cpu().numpy(), aln_il.cpu().numpy()
+        return (scores[:n].cpu().numpy(), status[:n].cpu().numpy(), cols[0], cols[1], col_off, aln_score.cpu().numpy(),
+                aln_il[0], aln_il[1], aln_off, aln_count[:n].cpu().numpy())
+
+    @_serialised
     def hmm_batch(self, model, mode, obs, off, want_mat=False, path_slots=None):
         """ps_hmm_batch: one HMM pass over a batch of sequences.  model: a _lib.HmmModel (its arrays kept alive by the caller);
         obs: float64 CUDA tensor, sequence q = obs[off[q]:off[q+1]].  Returns (logp float64 [n_seq], matrix float64
