@@ -368,11 +368,22 @@ int ps_pairwise_batch(ps_ctx *ctx, const double *d_a, const int64_t *h_a_off, in
  * level_ptr[n_levels] = n_states, and every silent predecessor of a silent state lies in a lower level.  kind[k]: 0 silent,
  * 1 normal, 2 uniform; param[3k..3k+2]: normal (mean, 1 / (2 std^2), -log(std sqrt(2 pi))), uniform (low, high,
  * -log(high - low)).  In-edges of k: [in_ptr[k], in_ptr[k+1]) of in_src / in_lp (source ascending, log probability); out-edges:
- * the same over out_dst / out_lp.  finite: paths end at `end` after the last observation; otherwise at any state. */
+ * the same over out_dst / out_lp.  finite: paths end at `end` after the last observation; otherwise at any state.
+ *
+ * kind[k] = 3, a Gaussian kernel density: log density  -log(h sqrt(2 pi)) + log sum_i w_i exp(-(x - p_i)^2 / (2 h^2))  over
+ * the state's points p_i with weights w_i (summing to 1) and bandwidth h.  The points of emitting state k are
+ * [kde_ptr[k], kde_ptr[k+1]) of kde_pt (finite values) and kde_lw (log w_i, <= 0; -inf: the point is skipped): kde_ptr has
+ * n_emit + 1 ascending entries from 0, a kind-3 state has at least one point and any other state none, and there are at
+ * most 2^24 points in all (PS_ERR_ARG otherwise).  param[3k..3k+2] = (weighted mean of the points -- the shift c_k of
+ * ps_hmm_expect's statistics --, 1 / (2 h^2), -log(h sqrt(2 pi))).  The sum is a log-sum-exp over the points in ascending
+ * index: the largest term plus log1p of the others' exp.  The three kde_* fields were appended to the struct; they are read
+ * only when some kind[k] is 3, so a caller built against the shorter struct, which never sets kind 3, stays correct. */
 typedef struct ps_hmm_model {
     int32_t n_states, n_emit, n_levels, start, end, finite;
     const int32_t *kind, *level_ptr, *in_ptr, *in_src, *out_ptr, *out_dst;
     const double *param, *in_lp, *out_lp;
+    const int32_t *kde_ptr;
+    const double *kde_pt, *kde_lw;
 } ps_hmm_model;
 
 /* Decodes a BATCH of observation sequences against one model: sequence q is d_obs[h_off[q] .. h_off[q+1]) (fp64, device).

@@ -4,12 +4,19 @@ cSegmentAligner.  align() returns (score, order) or (None, None) when the aligne
 bookkeeping that reads `self.model`, which the reference never sets; it is not part of the accelerated path.
 
 `PairwiseAligner` (PyPore/alignment.py:97-313) aligns two sequences of segment means on the GPU (ps_pairwise_batch /
-ps_pairwise_scores, csrc/seg_pairwise.hpp); `pairwise_align_batch` and `pairwise_scores` do it for many pairs at once."""
+ps_pairwise_scores, csrc/seg_pairwise.hpp); `pairwise_align_batch` and `pairwise_scores` do it for many pairs at once.
+
+`PSSM`, `ProfileAligner` and `MultipleSequenceAligner` (PyPore/alignment.py:329-796) align sequences of segment means to
+a profile -- a multiple sequence alignment whose columns become Gaussian kernel densities -- with profile HMMs decoded by
+pypore_amd.hmm on the GPU; `profile_align_batch` aligns many sequences to one profile in a single Viterbi launch."""
+import copy
+import itertools as it
 import math
 
 import numpy as np
 
 from .calignment import cSegmentAligner
+from .hmm import GaussianKernelDensity, Model, State, UniformDistribution
 
 
 class SegmentAligner(object):
@@ -178,3 +185,317 @@ class PairwiseAligner(object):
             if isinstance(r, Exception):
                 raise r
             yield r
+
+
+# ---- profile alignment (PyPore/alignment.py:329-796) ---------------------------------------------------------------------
+def _is_gap(x):
+    return isinstance(x, str) and x == '-'
+
+
+class PSSM(object):
+    """A position specific scoring matrix over a multiple sequence alignment of segment means (rows of equal length, '-'
+    for a gap): pssm[i] = the non-gap values of column i, consensus[i] = their mean.  A flat sequence is taken as a
+    one-row alignment.  Columns that hold only gaps are deleted IN PLACE from the rows given (as in the reference)."""
+
+    def __init__(self, msa):
+        if not isinstance(msa, (list, PSSM)):
+            msa = list(msa)
+        if hasattr(msa, '__iter__') and (isinstance(msa[0], str) or not hasattr(msa[0], '__iter__')):
+            msa = [msa]
+        for profile in list(msa):
+            if isinstance(profile, PSSM):
+                msa = [seq for seq in it.chain(msa, profile.msa)]
+        self.msa = msa
+        self.consensus = []
+        self.pssm = []
+        offset = 0
+        for i, column in enumerate(list(zip(*msa))):
+            column = [x for x in column if not _is_gap(x)]
+            if len(column) == 0:
+                for seq in self.msa:
+                    del seq[i - offset]
+                offset += 1
+                continue
+            self.pssm.append([mean for mean in column])
+            self.consensus.append(np.mean([mean for mean in column]))
+
+    def __getitem__(self, slice):
+        return self.pssm[slice]
+
+    def __repr__(self):
+        return '\n'.join("{}".format(mean) for mean in self.consensus)
+
+    def __len__(self):
+        return len(self.pssm)
+
+
+def follow_global(master, slave, names):
+    """The reference's path-following loop of global_alignment (alignment.py:630-641) on the state names of a Viterbi
+    path, start and end included: a delete state puts a gap into the slave, an insert state one into the master, in
+    `pssm` and in every row of `msa`, in place (`consensus` is left alone, as in the reference)."""
+    for i, sname in enumerate(names[1:-1]):
+        if sname.startswith('D'):
+            slave.pssm.insert(i, '-')
+            for seq in slave.msa:
+                seq.insert(i, '-')
+        elif sname.startswith('I'):
+            master.pssm.insert(i, '-')
+            for seq in master.msa:
+                seq.insert(i, '-')
+    return master, slave
+
+
+def follow_local(master, slave, names):
+    """The loop of local_alignment (alignment.py:658-690): at the first match state M<k> the first k columns of the
+    master are dropped (msa, pssm and consensus), gaps go in as in follow_global with the master's position shifted by
+    k, and at PE one element per remaining state is cut from the end of every slave row."""
+    first_match = True
+    offset = 0
+    for i, sname in enumerate(names[1:-1]):
+        if sname.startswith("M") and first_match:
+            first_match = False
+            offset = int(sname[1:])
+            for j in range(offset):
+                for seq in master.msa:
+                    del seq[0]
+                del master.pssm[0]
+                del master.consensus[0]
+        if sname.startswith('D'):
+            slave.pssm.insert(i, '-')
+            for seq in slave.msa:
+                seq.insert(i, '-')
+        elif sname.startswith('I'):
+            master.pssm.insert(i - offset, '-')
+            for seq in master.msa:
+                seq.insert(i - offset, '-')
+        if sname == 'PE':
+            for _ in range(len(names) - i - 3):
+                for seq in slave.msa:
+                    del seq[-1]
+            break
+    return master, slave
+
+
+class ProfileAligner(object):
+    """Aligns a slave profile (its consensus) to a master profile with a profile HMM: match states are the kernel
+    densities of the master's columns, insert states share one uniform distribution over [low, high], delete states are
+    silent.  master and slave: a PSSM, a multiple sequence alignment (list of rows) or one flat sequence.  The state
+    names and transition probabilities are the reference's (alignment.py:427-616); bake() normalises them."""
+
+    def __init__(self, master, slave, bandwidth=1):
+        self.bandwidth = bandwidth
+        self.master = master if isinstance(master, PSSM) else PSSM(master)
+        self.slave = slave if isinstance(slave, PSSM) else PSSM(slave)
+
+    def _match(self, column, name):
+        return State(GaussianKernelDensity(column, self.bandwidth), name=name)
+
+    def _build_global(self, pssm, low, high):
+        model = Model(name="Global Profile Aligner")
+        insert_dist = UniformDistribution(low, high)
+        last_match = model.start
+        last_insert = State(insert_dist, name="I0")
+        last_delete = None
+        model.add_transition(model.start, last_insert, 0.15)
+        model.add_transition(last_insert, last_insert, 0.20)
+        for i, column in enumerate(pssm):
+            match = self._match(column, "M" + str(i + 1))
+            insert = State(insert_dist, name="I" + str(i + 1))
+            delete = State(None, name="D" + str(i + 1))
+            model.add_transition(last_match, match, 0.60)
+            model.add_transition(last_match, delete, 0.25)
+            model.add_transition(last_insert, match, 0.65)
+            model.add_transition(last_insert, delete, 0.20)
+            model.add_transition(delete, insert, 0.15)
+            model.add_transition(insert, insert, 0.15)
+            model.add_transition(match, insert, 0.15)
+            if last_delete is not None:
+                model.add_transition(last_delete, match, 0.65)
+                model.add_transition(last_delete, delete, 0.20)
+            last_match, last_insert, last_delete = match, insert, delete
+        if last_delete is None:
+            raise ValueError("a profile needs at least one column")
+        model.add_transition(last_delete, model.end, 0.85)
+        model.add_transition(last_insert, model.end, 0.85)
+        model.add_transition(last_match, model.end, 0.85)
+        model.bake()
+        return model
+
+    def _profile_repeat(self, model, pssm, insert_dist, start_delete, end_delete):
+        """The columns shared by the local and the repeat model (alignment.py:494-536 and :571-613)."""
+        m = len(pssm)
+        if m < 3:
+            raise ValueError("the local and repeat profile models need at least 3 columns, got %d" % m)
+        last_match = self._match(pssm[0], "M0")
+        last_insert = State(insert_dist, name="I0")
+        last_delete = None
+        model.add_transition(last_match, last_insert, 0.15)
+        model.add_transition(last_match, end_delete, 0.05)
+        model.add_transition(last_insert, last_insert, 0.20)
+        model.add_transition(start_delete, last_match, 1. / m)
+        for i, column in enumerate(pssm[1:-1]):
+            match = self._match(column, "M" + str(i + 1))
+            insert = State(insert_dist, name="I" + str(i + 1))
+            delete = State(None, name="D" + str(i + 1))
+            model.add_transition(start_delete, match, 1. / m)
+            model.add_transition(last_match, match, 0.65)
+            model.add_transition(last_match, delete, 0.15)
+            model.add_transition(last_insert, delete, 0.20)
+            model.add_transition(last_insert, match, 0.65)
+            model.add_transition(insert, insert, 0.15)
+            model.add_transition(delete, insert, 0.15)
+            model.add_transition(match, insert, 0.15)
+            model.add_transition(match, end_delete, 0.05)
+            if last_delete is not None:
+                model.add_transition(last_delete, match, 0.65)
+                model.add_transition(last_delete, delete, 0.20)
+            last_match, last_insert, last_delete = match, insert, delete
+        match = self._match(pssm[-1], "M" + str(i + 2))
+        model.add_transition(start_delete, match, 1. / m)
+        model.add_transition(last_match, match, 0.80)
+        model.add_transition(last_insert, match, 0.85)
+        model.add_transition(last_delete, match, 0.85)
+        model.add_transition(match, end_delete, 1.00)
+
+    def _build_local(self, pssm, low, high):
+        model = Model(name="Local Profile Aligner")
+        insert_dist = UniformDistribution(low, high)
+        start_insert = State(insert_dist, name="Q0")
+        start_delete = State(None, name="P0")
+        model.add_transition(model.start, start_insert, 0.5)
+        model.add_transition(model.start, start_delete, 0.5)
+        model.add_transition(start_insert, start_insert, 0.75)
+        model.add_transition(start_insert, start_delete, 0.25)
+        end_insert = State(insert_dist, name="QE")
+        end_delete = State(None, name="PE")
+        self._profile_repeat(model, pssm, insert_dist, start_delete, end_delete)
+        model.add_transition(end_delete, end_insert, 0.5)
+        model.add_transition(end_delete, model.end, 0.5)
+        model.add_transition(end_insert, end_insert, 0.75)
+        model.add_transition(end_insert, model.end, 0.25)
+        model.bake()
+        return model
+
+    def _build_repeat(self, pssm, low, high):
+        model = Model(name="Local Profile Aligner")
+        insert_dist = UniformDistribution(low, high)
+        intermediate_insert = State(insert_dist, name="Q")
+        start_delete = State(None, name="P0")
+        end_delete = State(None, name="PE")
+        model.add_transition(model.start, start_delete, 0.5)
+        model.add_transition(model.start, intermediate_insert, 0.5)
+        model.add_transition(intermediate_insert, intermediate_insert, 0.50)
+        model.add_transition(intermediate_insert, start_delete, 0.25)
+        model.add_transition(intermediate_insert, model.end, 0.25)
+        model.add_transition(end_delete, intermediate_insert, 0.5)
+        model.add_transition(end_delete, model.end, 0.5)
+        self._profile_repeat(model, pssm, insert_dist, start_delete, end_delete)
+        model.bake()
+        return model
+
+    def _align(self, build, follow, low, high, device=None):
+        profile = build(self.master, low, high)
+        prob, states = profile.viterbi_batch([self.slave.consensus], device)[0]
+        if states is None:
+            return prob, None, None
+        master, slave = follow(self.master, self.slave, [s.name for _, s in states])
+        return prob, master, slave
+
+    def global_alignment(self, low=0, high=60):
+        """(log probability of the best path, master, slave) with the gaps of the alignment put into both profiles in
+        place; (-inf, None, None) when the slave is impossible under the model (the reference would fail there)."""
+        return self._align(self._build_global, follow_global, low, high)
+
+    def local_alignment(self, low=0, high=60):
+        """As global_alignment for the best local alignment: the master loses the columns before the first match, the
+        slave's rows the tail after the profile."""
+        return self._align(self._build_local, follow_local, low, high)
+
+    def repeat_alignment(self, low=0, high=60):
+        """The reference's repeat_alignment is marked incomplete and only prints the path's state names; this returns
+        them: (log probability, [state names between start and end]), (-inf, None) for an impossible slave."""
+        profile = self._build_repeat(self.master, low, high)
+        prob, states = profile.viterbi(self.slave.consensus)
+        return prob, (None if states is None else [s.name for _, s in states[1:-1]])
+
+
+def profile_align_batch(master, slaves, mode='global', low=0, high=60, bandwidth=1, device=None):
+    """Aligns every sequence (or alignment, or PSSM) of `slaves` to one master profile: one model, one viterbi_batch
+    call.  Returns [(prob, master, slave)] -- per slave a deep copy of the master and the slave's PSSM with the
+    alignment's gaps, what ProfileAligner(copy of master, slave, bandwidth).global_alignment(low, high) (mode 'local':
+    local_alignment) returns, (-inf, None, None) for an impossible slave."""
+    if mode not in ('global', 'local'):
+        raise ValueError("mode must be 'global' or 'local', got %r" % (mode,))
+    base = master if isinstance(master, PSSM) else PSSM(master)
+    aligner = ProfileAligner(base, [0.0], bandwidth)
+    model = (aligner._build_global if mode == 'global' else aligner._build_local)(base, low, high)
+    follow = follow_global if mode == 'global' else follow_local
+    pssms = [s if isinstance(s, PSSM) else PSSM(s) for s in slaves]
+    results = model.viterbi_batch([p.consensus for p in pssms], device) if pssms else []
+    out = []
+    for (prob, states), slave in zip(results, pssms):
+        if states is None:
+            out.append((prob, None, None))
+            continue
+        m, s = follow(copy.deepcopy(base), slave, [st.name for _, st in states])
+        out.append((prob, m, s))
+    return out
+
+
+class MultipleSequenceAligner(object):
+    """Multiple sequence alignment by profile HMMs (alignment.py:712-796): an initial alignment built by adding one
+    sequence at a time, then rounds that peel each row off and align it back to the profile of the others, scored by the
+    columns' differential entropy.  Every step depends on the one before, so this is a chain of single-sequence Viterbi
+    launches: bound by launch and transfer latency, not by the kernels."""
+
+    def __init__(self, sequences, bandwidth=1):
+        self.sequences = sequences
+        self.bandwidth = bandwidth
+
+    def _score(self, msa):
+        """sum over columns of  entropy(non-gap values) / (non-gap count)^2,  entropy = 0.5 log(2 pi e std^2) for more
+        than one value of non-zero spread, else 0 (lower is better)."""
+        def entropy(col):
+            return 0.5 * math.log(2 * np.pi * np.e * np.std(col) ** 2) if len(col) > 1 and np.std(col) > 0 else 0
+        return sum(1. / (len(col) - sum(1 for x in col if _is_gap(x))) ** 2 * entropy([x for x in col if not _is_gap(x)])
+                   for col in zip(*msa))
+
+    @staticmethod
+    def _global(master, slave, bandwidth):
+        p, x, y = ProfileAligner(master=master, slave=slave, bandwidth=bandwidth).global_alignment()
+        if x is None:
+            raise ValueError("a sequence cannot be aligned to the profile: a value outside the insert range [0, 60]?")
+        return p, x, y
+
+    def iterative_alignment(self, epsilon=1e-4, max_iterations=10, bandwidth=1):
+        """(score of the last trial alignment, best alignment found), as the reference returns them."""
+        score, msa = self.iterative_initialization(bandwidth=bandwidth)
+        if score == 0:
+            return 0, msa
+        n = len(msa)
+        last_score = float('inf')
+        best_msa, best_score = msa, score
+        iteration = 0
+        while abs(best_score - last_score) >= epsilon and iteration < max_iterations:
+            iteration += 1
+            last_score = best_score
+            for i in range(n):
+                slave = [x for x in best_msa[i] if not _is_gap(x)]
+                master = best_msa[:i] + best_msa[i + 1:]
+                p, x, y = self._global(master, slave, bandwidth)
+                msa = [seq for seq in it.chain(x.msa, y.msa)]
+                score = self._score(msa)
+                if score < best_score:
+                    best_msa, best_score = msa, score
+        m = max(map(len, best_msa))
+        for seq in best_msa:
+            seq.extend(['-'] * (m - len(seq)))
+        return score, best_msa
+
+    def iterative_initialization(self, bandwidth=1):
+        """(score, alignment) from adding the sequences one at a time to a growing profile."""
+        pssm = PSSM(self.sequences[0])
+        for seq in self.sequences[1:]:
+            p, master, slave = self._global(pssm, seq, bandwidth)
+            pssm = PSSM([seq for seq in it.chain(master.msa, slave.msa)])
+        return self._score(pssm.msa), pssm.msa

@@ -2800,17 +2800,41 @@ int ps_pairwise_batch(ps_ctx *ctx, const double *d_a, const int64_t *h_a_off, in
 namespace {
 
 // ps_hmm_batch: the model's arrays checked and packed into one blob (doubles first, then ints); the device copy is reused
-// while the blob is unchanged
-int hmm_upload(ps_ctx *ctx, const ps_hmm_model *m, HmmDev *D, int *max_in)
+// while the blob is unchanged.  *has_kde: some state is a kernel density (kind 3); only then are the model's kde_* fields read,
+// checked and appended to the blob (points and log weights after the doubles, the CSR offsets after the ints).
+constexpr int64_t HMM_KDE_POINTS_MAX = 1 << 24;
+int hmm_upload(ps_ctx *ctx, const ps_hmm_model *m, HmmDevK *D, int *max_in, bool *has_kde)
 {
     const int S = m->n_states, NE = m->n_emit, NL = m->n_levels;
     if (S < 1 || S > HMM_S_MAX) return fail(ctx, PS_ERR_ARG, "model of %d states: the device HMM kernels take 1..%d", S, HMM_S_MAX);
     if (NE < 0 || NE > S || NL < 0 || NL > S - NE || (NL == 0) != (NE == S)) return fail(ctx, PS_ERR_ARG, "bad state / level counts");
     if (m->start < NE || m->start >= S || m->end < NE || m->end >= S) return fail(ctx, PS_ERR_ARG, "start and end must be silent states");
     if (!m->kind || !m->level_ptr || !m->in_ptr || !m->out_ptr || !m->param) return fail(ctx, PS_ERR_ARG, "null model array");
-    for (int k = 0; k < S; ++k)
-        if ((k < NE) != (m->kind[k] == HMM_NORMAL || m->kind[k] == HMM_UNIFORM) || (k >= NE && m->kind[k] != HMM_SILENT))
+    bool kde = false;
+    for (int k = 0; k < S; ++k) {
+        const int kd = m->kind[k];
+        if ((k < NE) != (kd == HMM_NORMAL || kd == HMM_UNIFORM || kd == HMM_KDE) || (k >= NE && kd != HMM_SILENT))
             return fail(ctx, PS_ERR_ARG, "state %d: emitting states first, then silent ones", k);
+        kde = kde || kd == HMM_KDE;
+    }
+    int64_t NP = 0;
+    if (kde) {
+        if (!m->kde_ptr || !m->kde_pt || !m->kde_lw) return fail(ctx, PS_ERR_ARG, "a kernel-density state needs kde_ptr, kde_pt and kde_lw");
+        if (m->kde_ptr[0] != 0) return fail(ctx, PS_ERR_ARG, "kde_ptr must start at 0");
+        for (int k = 0; k < NE; ++k) {
+            if (m->kde_ptr[k + 1] < m->kde_ptr[k]) return fail(ctx, PS_ERR_ARG, "descending kde_ptr at state %d", k);
+            if ((m->kde_ptr[k + 1] > m->kde_ptr[k]) != (m->kind[k] == HMM_KDE))
+                return fail(ctx, PS_ERR_ARG, "state %d: a kernel-density state has at least one point, any other state none", k);
+        }
+        NP = m->kde_ptr[NE];
+        if (NP > HMM_KDE_POINTS_MAX)
+            return fail(ctx, PS_ERR_ARG, "%lld kernel-density points: the device HMM kernels take at most %lld",
+                        static_cast<long long>(NP), static_cast<long long>(HMM_KDE_POINTS_MAX));
+        for (int64_t i = 0; i < NP; ++i)
+            if (!std::isfinite(m->kde_pt[i]) || !(m->kde_lw[i] <= 0.0))
+                return fail(ctx, PS_ERR_ARG, "kernel-density point %lld: points must be finite and log weights <= 0", static_cast<long long>(i));
+    }
+    *has_kde = kde;
     if (m->level_ptr[0] != NE || m->level_ptr[NL] != S) return fail(ctx, PS_ERR_ARG, "levels must cover the silent states");
     for (int L = 0; L < NL; ++L) if (m->level_ptr[L + 1] <= m->level_ptr[L]) return fail(ctx, PS_ERR_ARG, "empty or descending level %d", L);
     std::vector<int> level(S, -1);
@@ -2836,8 +2860,9 @@ int hmm_upload(ps_ctx *ctx, const ps_hmm_model *m, HmmDev *D, int *max_in)
     }
     if (n_edge[0] != n_edge[1]) return fail(ctx, PS_ERR_ARG, "in- and out-edge lists differ in length");
     if (*max_in > 65535) return fail(ctx, PS_ERR_ARG, "a state with %d in-edges: the device HMM kernels take at most 65535", *max_in);
-    const size_t nd = 3 * static_cast<size_t>(S) + 2 * n_edge[0];
-    const size_t ni = static_cast<size_t>(S) + (NL + 1) + 2 * (S + 1) + 2 * n_edge[0] + 3;
+    const size_t nd0 = 3 * static_cast<size_t>(S) + 2 * n_edge[0], nd = nd0 + 2 * static_cast<size_t>(NP);
+    const size_t ni0 = static_cast<size_t>(S) + (NL + 1) + 2 * (S + 1) + 2 * n_edge[0] + 3;
+    const size_t ni = ni0 + (kde ? static_cast<size_t>(NE) + 1 : 0);
     std::vector<char> blob(nd * sizeof(double) + ni * sizeof(int32_t), 0);
     double *bd = reinterpret_cast<double *>(blob.data());
     std::memcpy(bd, m->param, 3 * S * sizeof(double));
@@ -2857,6 +2882,11 @@ int hmm_upload(ps_ctx *ctx, const ps_hmm_model *m, HmmDev *D, int *max_in)
         std::memcpy(b_src, m->in_src, n_edge[0] * sizeof(int32_t));
         std::memcpy(b_dst, m->out_dst, n_edge[0] * sizeof(int32_t));
     }
+    if (kde) {
+        std::memcpy(bd + nd0, m->kde_pt, NP * sizeof(double));
+        std::memcpy(bd + nd0 + NP, m->kde_lw, NP * sizeof(double));
+        std::memcpy(bi + ni0, m->kde_ptr, (static_cast<size_t>(NE) + 1) * sizeof(int32_t));
+    }
     if (blob != ctx->hmm_blob || !ctx->hmm_model.p) {
         HIP_TRY(ctx, ctx->hmm_model.reserve(blob.size()));
         HIP_TRY(ctx, hipMemcpyAsync(ctx->hmm_model.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
@@ -2869,16 +2899,17 @@ int hmm_upload(ps_ctx *ctx, const ps_hmm_model *m, HmmDev *D, int *max_in)
     D->kind = di; D->level_ptr = di + S; D->in_ptr = D->level_ptr + NL + 1; D->out_ptr = D->in_ptr + S + 1;
     D->in_src = D->out_ptr + S + 1; D->out_dst = D->in_src + n_edge[0];
     D->S = S; D->n_emit = NE; D->n_levels = NL; D->start = m->start; D->end = m->end; D->finite = m->finite != 0;
+    D->kde_pt = kde ? dd + nd0 : nullptr; D->kde_lw = kde ? dd + nd0 + NP : nullptr; D->kde_ptr = kde ? di + ni0 : nullptr;
     return PS_OK;
 }
 
-template <typename BP>
-int hmm_viterbi(ps_ctx *ctx, const HmmDev &D, const double *d_obs, const int64_t *h_off, const long long *d_off, int32_t n_seq,
+template <typename BP, typename MD>
+int hmm_viterbi(ps_ctx *ctx, const MD &D, const double *d_obs, const int64_t *h_off, const long long *d_off, int32_t n_seq,
                 double *d_logp, double *d_mat, int32_t *d_path, const long long *d_path_off, int32_t *d_path_len, size_t lds)
 {
     const size_t S = static_cast<size_t>(D.S);
     const long long budget = std::max<long long>(1, ctx->hmm_bp_budget);
-    HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_fwd_kernel<HMM_VITERBI, BP>), static_cast<int>(lds)));
+    HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_fwd_kernel<HMM_VITERBI, BP, MD>), static_cast<int>(lds)));
     HIP_TRY(ctx, ctx->hmm_last.reserve(static_cast<size_t>(n_seq) * sizeof(int)));
     HIP_TRY(ctx, ctx->hmm_flags.reserve(sizeof(int)));
     HIP_TRY(ctx, hipMemsetAsync(ctx->hmm_flags.p, 0, sizeof(int), ctx->stream));
@@ -2896,10 +2927,10 @@ int hmm_viterbi(ps_ctx *ctx, const HmmDev &D, const double *d_obs, const int64_t
         const long long bp_row0 = h_off[q0] + q0;
         const int nq = q1 - q0;
         BP *bp = ctx->hmm_bp.as<BP>();
-        hipLaunchKernelGGL((hmm_fwd_kernel<HMM_VITERBI, BP>), dim3(nq), dim3(HMM_NT), lds, ctx->stream, D, d_obs, d_off, q0, d_logp,
+        hipLaunchKernelGGL((hmm_fwd_kernel<HMM_VITERBI, BP, MD>), dim3(nq), dim3(HMM_NT), lds, ctx->stream, D, d_obs, d_off, q0, d_logp,
                            d_mat, 0ll, bp, bp_row0, ctx->hmm_last.as<int>());
         HIP_TRY(ctx, hipGetLastError());
-        hipLaunchKernelGGL(hmm_trace_kernel<BP>, dim3((nq + HMM_NT - 1) / HMM_NT), dim3(HMM_NT), 0, ctx->stream, D, d_off, q0, nq,
+        hipLaunchKernelGGL(hmm_trace_kernel<BP>, dim3((nq + HMM_NT - 1) / HMM_NT), dim3(HMM_NT), 0, ctx->stream, static_cast<HmmDev>(D), d_off, q0, nq,
                            static_cast<const BP *>(bp), bp_row0, static_cast<const int *>(ctx->hmm_last.as<int>()),
                            static_cast<const double *>(d_logp), d_path_off, d_path, d_path_len, ctx->hmm_flags.as<int>());
         HIP_TRY(ctx, hipGetLastError());
@@ -2934,9 +2965,11 @@ int ps_hmm_batch(ps_ctx *ctx, const ps_hmm_model *model, int32_t mode, const dou
             return fail(ctx, PS_ERR_ARG, "path offsets must be non-negative and ascending");
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HmmDev D;
+    HmmDevK DK;
     int max_in = 0;
-    if (int rc = hmm_upload(ctx, model, &D, &max_in)) return rc;
+    bool kde = false;
+    if (int rc = hmm_upload(ctx, model, &DK, &max_in, &kde)) return rc;
+    const HmmDev &D = DK;
     if (n_seq == 0) return PS_OK;
     if (!d_logp || (h_off[n_seq] > 0 && !d_obs)) return fail(ctx, PS_ERR_ARG, "null device pointer");
     // offsets (and the path slots) in one upload
@@ -2951,17 +2984,27 @@ int ps_hmm_batch(ps_ctx *ctx, const ps_hmm_model *model, int32_t mode, const dou
     const size_t lds = 2 * static_cast<size_t>(D.S) * sizeof(double);
     if (mode == PS_HMM_VITERBI) {
         const long long *d_path_off = d_off + n_seq + 1;
+        if (kde)
+            return max_in > 255 ? hmm_viterbi<uint16_t>(ctx, DK, d_obs, h_off, d_off, n_seq, d_logp, d_mat, d_path, d_path_off, d_path_len, lds)
+                                : hmm_viterbi<uint8_t>(ctx, DK, d_obs, h_off, d_off, n_seq, d_logp, d_mat, d_path, d_path_off, d_path_len, lds);
         return max_in > 255 ? hmm_viterbi<uint16_t>(ctx, D, d_obs, h_off, d_off, n_seq, d_logp, d_mat, d_path, d_path_off, d_path_len, lds)
                             : hmm_viterbi<uint8_t>(ctx, D, d_obs, h_off, d_off, n_seq, d_logp, d_mat, d_path, d_path_off, d_path_len, lds);
     }
-    if (mode == PS_HMM_FORWARD) {
-        HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_fwd_kernel<HMM_FORWARD, uint8_t>), static_cast<int>(lds)));
-        hipLaunchKernelGGL((hmm_fwd_kernel<HMM_FORWARD, uint8_t>), dim3(n_seq), dim3(HMM_NT), lds, ctx->stream, D, d_obs, d_off, 0,
+    // (a model with kernel-density states takes the HmmDevK instantiations, any other the HmmDev ones)
+    auto fwd = [&](const auto &M) -> int {
+        using MD = std::decay_t<decltype(M)>;
+        HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_fwd_kernel<HMM_FORWARD, uint8_t, MD>), static_cast<int>(lds)));
+        hipLaunchKernelGGL((hmm_fwd_kernel<HMM_FORWARD, uint8_t, MD>), dim3(n_seq), dim3(HMM_NT), lds, ctx->stream, M, d_obs, d_off, 0,
                            d_logp, d_mat, 0ll, static_cast<uint8_t *>(nullptr), 0ll, static_cast<int *>(nullptr));
-    } else {
-        HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_bwd_kernel), static_cast<int>(lds)));
-        hipLaunchKernelGGL(hmm_bwd_kernel, dim3(n_seq), dim3(HMM_NT), lds, ctx->stream, D, d_obs, d_off, 0, d_logp, d_mat);
-    }
+        return PS_OK;
+    };
+    auto bwd = [&](const auto &M) -> int {
+        using MD = std::decay_t<decltype(M)>;
+        HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_bwd_kernel<MD>), static_cast<int>(lds)));
+        hipLaunchKernelGGL(hmm_bwd_kernel<MD>, dim3(n_seq), dim3(HMM_NT), lds, ctx->stream, M, d_obs, d_off, 0, d_logp, d_mat);
+        return PS_OK;
+    };
+    if (int rc = mode == PS_HMM_FORWARD ? (kde ? fwd(DK) : fwd(D)) : (kde ? bwd(DK) : bwd(D))) return rc;
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return PS_OK;
@@ -2976,19 +3019,19 @@ namespace {
 constexpr size_t HMM_EXPECT_LDS = 64u << 10;
 constexpr size_t HMM_EXPECT_ROWS = 256u << 20;
 
-template <bool ACC_LDS>
-int hmm_expect_run(ps_ctx *ctx, const HmmDev &D, const double *d_obs, const int64_t *h_off, const long long *d_off,
+template <bool ACC_LDS, typename MD>
+int hmm_expect_run(ps_ctx *ctx, const MD &D, const double *d_obs, const int64_t *h_off, const long long *d_off,
                    int32_t n_seq, int n_acc, int E, double *d_logp, double *d_counts, double *d_stats, int32_t *h_skipped)
 {
     const size_t S = static_cast<size_t>(D.S);
     const size_t lds = (2 * S + (ACC_LDS ? static_cast<size_t>(n_acc) : 0)) * sizeof(double);
     const size_t lds_fwd = 2 * S * sizeof(double);
-    const void *fk = reinterpret_cast<const void *>(hmm_expect_kernel<ACC_LDS>);
-    HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_fwd_kernel<HMM_FORWARD, uint8_t>), static_cast<int>(lds_fwd)));
+    const void *fk = reinterpret_cast<const void *>(hmm_expect_kernel<ACC_LDS, MD>);
+    HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_fwd_kernel<HMM_FORWARD, uint8_t, MD>), static_cast<int>(lds_fwd)));
     HIP_TRY(ctx, set_dyn_lds(ctx, fk, static_cast<int>(lds)));
     // a grid of resident workgroups (it depends on the device and the model only, never on timing), within the row budget
     const size_t row_bytes = static_cast<size_t>(n_acc) * sizeof(double);
-    unsigned G = std::min<unsigned>(static_cast<unsigned>(n_seq), resident_slots(ctx, hmm_expect_kernel<ACC_LDS>, HMM_NT, lds));
+    unsigned G = std::min<unsigned>(static_cast<unsigned>(n_seq), resident_slots(ctx, (hmm_expect_kernel<ACC_LDS, MD>), HMM_NT, lds));
     G = static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>(G, HMM_EXPECT_ROWS / row_bytes)));
     HIP_TRY(ctx, ctx->hmm_acc.reserve(G * row_bytes));
     HIP_TRY(ctx, ctx->hmm_skip.reserve(sizeof(double)));
@@ -3007,10 +3050,10 @@ int hmm_expect_run(ps_ctx *ctx, const HmmDev &D, const double *d_obs, const int6
         HIP_TRY(ctx, ctx->hmm_fmat.reserve(static_cast<size_t>(bytes)));
         const long long row0 = h_off[q0] + q0;
         double *fmat = ctx->hmm_fmat.as<double>();
-        hipLaunchKernelGGL((hmm_fwd_kernel<HMM_FORWARD, uint8_t>), dim3(q1 - q0), dim3(HMM_NT), lds_fwd, ctx->stream, D, d_obs, d_off,
+        hipLaunchKernelGGL((hmm_fwd_kernel<HMM_FORWARD, uint8_t, MD>), dim3(q1 - q0), dim3(HMM_NT), lds_fwd, ctx->stream, D, d_obs, d_off,
                            q0, d_logp, fmat, row0, static_cast<uint8_t *>(nullptr), 0ll, static_cast<int *>(nullptr));
         HIP_TRY(ctx, hipGetLastError());
-        hipLaunchKernelGGL(hmm_expect_kernel<ACC_LDS>, dim3(G), dim3(HMM_NT), lds, ctx->stream, D, d_obs, d_off, q0, q1,
+        hipLaunchKernelGGL((hmm_expect_kernel<ACC_LDS, MD>), dim3(G), dim3(HMM_NT), lds, ctx->stream, D, d_obs, d_off, q0, q1,
                            static_cast<const double *>(d_logp), static_cast<const double *>(fmat), row0, ctx->hmm_acc.as<double>(), n_acc);
         HIP_TRY(ctx, hipGetLastError());
         q0 = q1;
@@ -3041,9 +3084,11 @@ int ps_hmm_expect(ps_ctx *ctx, const ps_hmm_model *model, const double *d_obs, c
         if (h_off[q + 1] - h_off[q] > INT32_MAX / 2) return fail(ctx, PS_ERR_ARG, "sequence %d too long", q);
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HmmDev D;
+    HmmDevK DK;
     int max_in = 0;
-    if (int rc = hmm_upload(ctx, model, &D, &max_in)) return rc;
+    bool kde = false;
+    if (int rc = hmm_upload(ctx, model, &DK, &max_in, &kde)) return rc;
+    const HmmDev &D = DK;
     const int E = model->out_ptr[D.S], NE = D.n_emit;
     const long long n_acc_ll = static_cast<long long>(E) + 3ll * NE + 1;
     if (n_acc_ll > (1ll << 26)) return fail(ctx, PS_ERR_ARG, "model of %d edges: the E-step takes at most 2^26 accumulators", E);
@@ -3065,6 +3110,9 @@ int ps_hmm_expect(ps_ctx *ctx, const ps_hmm_model *model, const double *d_obs, c
     const long long *d_off = ctx->hmm_off.as<long long>();
     const bool in_lds = (2 * static_cast<size_t>(D.S) + static_cast<size_t>(n_acc)) * sizeof(double) <= HMM_EXPECT_LDS
                         && ctx->hmm_expect_lds;
+    if (kde)
+        return in_lds ? hmm_expect_run<true>(ctx, DK, d_obs, h_off, d_off, n_seq, n_acc, E, d_logp, d_counts, d_stats, h_skipped)
+                      : hmm_expect_run<false>(ctx, DK, d_obs, h_off, d_off, n_seq, n_acc, E, d_logp, d_counts, d_stats, h_skipped);
     return in_lds ? hmm_expect_run<true>(ctx, D, d_obs, h_off, d_off, n_seq, n_acc, E, d_logp, d_counts, d_stats, h_skipped)
                   : hmm_expect_run<false>(ctx, D, d_obs, h_off, d_off, n_seq, n_acc, E, d_logp, d_counts, d_stats, h_skipped);
 }

@@ -24,13 +24,22 @@ namespace ps {
 constexpr int HMM_NT = 64;                 // one wave per workgroup
 constexpr int HMM_S_MAX = 4096;            // states: two fp64 rows of S in LDS = 64 KiB at most
 constexpr int HMM_VITERBI = 0, HMM_FORWARD = 1, HMM_BACKWARD = 2;   // include/poreseg.h PS_HMM_*
-constexpr int HMM_SILENT = 0, HMM_NORMAL = 1, HMM_UNIFORM = 2;
+constexpr int HMM_SILENT = 0, HMM_NORMAL = 1, HMM_UNIFORM = 2, HMM_KDE = 3;   // include/poreseg.h ps_hmm_model.kind
 
 struct HmmDev {                 // device pointers into one upload of the baked model (include/poreseg.h ps_hmm_model)
     const double *param;        // 3 per state: normal (mean, 1 / (2 std^2), -log(std sqrt(2 pi))), uniform (low, high, -log(high - low))
     const double *in_lp, *out_lp;
     const int *kind, *level_ptr, *in_ptr, *in_src, *out_ptr, *out_dst;
     int S, n_emit, n_levels, start, end, finite;
+};
+
+// A model with kernel-density states (kind 3): state k's points are [kde_ptr[k], kde_ptr[k+1]) of kde_pt (the points) and
+// kde_lw (their log weights, the weights summing to 1), and its param is (weighted mean of the points, 1 / (2 h^2),
+// -log(h sqrt(2 pi))) for the bandwidth h.  The kernels are instantiated once per model type: a model without such states
+// runs the HmmDev instantiations, whose code knows nothing of these tables.
+struct HmmDevK : HmmDev {
+    const int *kde_ptr;
+    const double *kde_pt, *kde_lw;
 };
 
 __device__ __forceinline__ void hm_sync()
@@ -62,11 +71,28 @@ struct HmmLse {
     __device__ __forceinline__ double get() const { return m > -__builtin_inf() ? m + log1p(r) : -__builtin_inf(); }
 };
 
+// Kernel-density emission  c + log sum_i w_i exp(-(x - p_i)^2 / (2 h^2)):  the lane that owns the state streams its
+// points through HmmLse in ascending index (the largest term plus log1p of the others, so an observation far from every
+// point gives a finite value).  The other kinds take the HmmDev code.
+__device__ __forceinline__ double hmm_emit(const HmmDevK &M, int k, double x)
+{
+#pragma clang fp contract(off)
+    if (M.kind[k] != HMM_KDE) return hmm_emit(static_cast<const HmmDev &>(M), k, x);
+    const double b = M.param[3 * k + 1], c = M.param[3 * k + 2];
+    HmmLse acc;
+    const int i1 = M.kde_ptr[k + 1];
+    for (int i = M.kde_ptr[k]; i < i1; ++i) {
+        const double d = x - M.kde_pt[i];
+        acc.add(M.kde_lw[i] - (d * d) * b);
+    }
+    return c + acc.get();
+}
+
 // Viterbi / forward over one sequence per workgroup.  Rows of sequence q: mat (optional, row off[q] + q - mat_row0) and bp
 // (backpointers, Viterbi only, row off[q] + q - bp_row0 of this launch).  Writes logp[q] and, for Viterbi, last[q]: the
 // state the path ends in (end for a finite model, else the best state of step n, lowest index on a tie).
-template <int MODE, typename BP>
-__global__ __launch_bounds__(HMM_NT) void hmm_fwd_kernel(HmmDev M, const double *obs, const long long *off, int q0,
+template <int MODE, typename BP, typename MD = HmmDev>
+__global__ __launch_bounds__(HMM_NT) void hmm_fwd_kernel(MD M, const double *obs, const long long *off, int q0,
                                                          double *logp, double *mat, long long mat_row0, BP *bp,
                                                          long long bp_row0, int *last)
 {
@@ -175,7 +201,8 @@ __global__ __launch_bounds__(HMM_NT) void hmm_fwd_kernel(HmmDev M, const double 
 
 // Backward over one sequence per workgroup: b[n][k] starts from log 1 at end (finite model) or at every state (infinite),
 // b[t][k] = logsumexp over out-edges k -> l of  lp + (l emitting ? e_l(x_t) + b[t+1][l] : b[t][l]).  logp[q] = b[0][start].
-__global__ __launch_bounds__(HMM_NT) void hmm_bwd_kernel(HmmDev M, const double *obs, const long long *off, int q0,
+template <typename MD = HmmDev>
+__global__ __launch_bounds__(HMM_NT) void hmm_bwd_kernel(MD M, const double *obs, const long long *off, int q0,
                                                          double *logp, double *mat)
 {
 #pragma clang fp contract(off)
@@ -236,8 +263,8 @@ __global__ __launch_bounds__(HMM_NT) void hmm_bwd_kernel(HmmDev M, const double 
 // launches.  An edge belongs to the lane that owns its source state (and a state's statistics to the lane that owns the
 // state) in every step, so a row needs no atomics.  ACC_LDS: the row is loaded into LDS next to the two score rows and
 // stored back at the end; otherwise it is updated in place in global memory.
-template <bool ACC_LDS>
-__global__ __launch_bounds__(HMM_NT) void hmm_expect_kernel(HmmDev M, const double *obs, const long long *off, int q0, int q1,
+template <bool ACC_LDS, typename MD = HmmDev>
+__global__ __launch_bounds__(HMM_NT) void hmm_expect_kernel(MD M, const double *obs, const long long *off, int q0, int q1,
                                                             const double *logp, const double *fmat, long long f_row0,
                                                             double *acc_rows, int n_acc)
 {

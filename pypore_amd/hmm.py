@@ -1,5 +1,5 @@
 """Hidden Markov models with the surface the reference's HMM code uses (yahmm: Model, State, NormalDistribution,
-UniformDistribution; add_state(s), add_transition, add_model, bake; viterbi, forward, backward, log_probability), decoded on
+UniformDistribution, GaussianKernelDensity; add_state(s), add_transition, add_model, bake; viterbi, forward, backward, log_probability), decoded on
 the MI355X (ps_hmm_batch, csrc/seg_hmm.hpp), and trained there (Model.train: Baum-Welch with its E-step in ps_hmm_expect,
 or Viterbi training).
 
@@ -23,7 +23,19 @@ row n and runs the same recursion backwards; b[0][start] = log_probability.  Vit
 in-edges in ascending source index and takes only a strictly greater score, so the lowest source index wins a tie, and an
 infinite model's path ends in the best state of row n (lowest index on a tie).  An impossible sequence gives (-inf, None).
 
+Emission log densities: NormalDistribution(mean, std) is -log(std sqrt(2 pi)) - (x - mean)^2 / (2 std^2);
+UniformDistribution(low, high) is -log(high - low) on [low, high] and -inf outside; GaussianKernelDensity(points, bandwidth
+h, weights w, normalised to sum to 1) is
+    e(x) = -log(h sqrt(2 pi)) + log sum_i w_i exp(-(x - p_i)^2 / (2 h^2)),
+the sum taken as a log-sum-exp over the points of non-zero weight in ascending index -- the largest term plus log1p of the
+others' exp, the form the recursions use -- so an observation far from every point has a finite, accurate log density
+instead of log(0).  With one point it is NormalDistribution(p, h).  On the device the lane that owns the state walks its
+points (csrc/seg_hmm.hpp hmm_emit); the flat form holds them as CSR tables kde_ptr / kde_pt / kde_lw.
+
 Deviations from yahmm, by design:
+  * GaussianKernelDensity is normalised: it carries the 1/h factor above.  yahmm is not available to compare against; as
+    far as is known its kernel density leaves 1/h out, which is the same density at bandwidth 1, the default and what
+    every caller in the reference's alignment.py uses.  Nothing else about its arithmetic is assumed.
   * bake(merge=...) is accepted and ignored: no states are merged.  yahmm may merge chains of probability-1 silent edges
     and so drop those silent states from its paths; here every silent state visited appears in the path.
   * `end` is kept in model.states even when it cannot be reached (the model is then infinite).
@@ -51,6 +63,9 @@ emitting state that consumed it (the shift and the M-step as above); its log pro
 
 Deviations from yahmm, by design:
   * uniform distributions are not trained (their support decides which sequences are possible);
+  * kernel-density distributions are not trained either: their points, bandwidth and weights stay as they are (bit for
+    bit), while a model's edges and normal states train around them.  Their (W, A, B) are still reported, with the shift
+    c_k = the weighted mean of the points;
   * Viterbi training runs the same stop loop as Baum-Welch, measured by the sum of the Viterbi scores.
 There is no CPU fallback: inference and the Baum-Welch E-step run on the GPU library or raise.
 """
@@ -61,7 +76,7 @@ import numpy as np
 
 NEG_INF = float("-inf")
 _LOG_SQRT_2PI = 0.5 * math.log(2.0 * math.pi)
-KIND_SILENT, KIND_NORMAL, KIND_UNIFORM = 0, 1, 2      # include/poreseg.h ps_hmm_model.kind
+KIND_SILENT, KIND_NORMAL, KIND_UNIFORM, KIND_KDE = 0, 1, 2, 3     # include/poreseg.h ps_hmm_model.kind
 MAX_STATES = 4096                                     # csrc/seg_hmm.hpp HMM_S_MAX
 
 
@@ -123,6 +138,62 @@ class UniformDistribution(Distribution):
     def compiled(self):
         low, high = self.parameters
         return low, high, -math.log(high - low)
+
+
+class GaussianKernelDensity(Distribution):
+    """log density -log(h sqrt(2 pi)) + log sum_i w_i exp(-(x - p_i)^2 / (2 h^2)) (module docstring): `points` p,
+    `bandwidth` h > 0, `weights` w >= 0 (default: equal), normalised to sum to 1.  parameters = [points, bandwidth,
+    weights]."""
+    kind = KIND_KDE
+
+    def __init__(self, points, bandwidth=1, weights=None):
+        points = [float(p) for p in np.asarray(points, dtype=np.float64).reshape(-1)]
+        if not points:
+            raise ValueError("GaussianKernelDensity needs at least one point")
+        if not all(math.isfinite(p) for p in points):
+            raise ValueError("GaussianKernelDensity needs finite points")
+        bandwidth = float(bandwidth)
+        if not bandwidth > 0 or not math.isfinite(bandwidth):
+            raise ValueError("GaussianKernelDensity needs a finite bandwidth > 0, got %r" % bandwidth)
+        if weights is None:
+            weights = [1.0] * len(points)
+        weights = [float(w) for w in np.asarray(weights, dtype=np.float64).reshape(-1)]
+        if len(weights) != len(points):
+            raise ValueError("GaussianKernelDensity got %d weights for %d points" % (len(weights), len(points)))
+        if not all(math.isfinite(w) and w >= 0 for w in weights):
+            raise ValueError("GaussianKernelDensity needs finite weights >= 0")
+        total = math.fsum(weights)
+        if not total > 0:
+            raise ValueError("GaussianKernelDensity needs some weight > 0")
+        Distribution.__init__(self, [points, bandwidth, [w / total for w in weights]])
+
+    def tables(self):
+        """(points, log weights) of the points with weight > 0, in order: what the flat form holds."""
+        points, _, weights = self.parameters
+        keep = [(p, math.log(w)) for p, w in zip(points, weights) if w > 0]
+        return [p for p, _ in keep], [lw for _, lw in keep]
+
+    def log_probability(self, x):
+        _, h, _ = self.parameters
+        b = 1.0 / (2.0 * h * h)
+        m, r = NEG_INF, 0.0                     # the device's HmmLse: m the largest term so far, r the others' sum
+        for p, lw in zip(*self.tables()):
+            d = x - p
+            v = lw - (d * d) * b
+            if not v > NEG_INF:
+                continue
+            if v > m:
+                r = (r + 1.0) * math.exp(m - v)
+                m = v
+            else:
+                r += math.exp(v - m)
+        if not m > NEG_INF:
+            return NEG_INF
+        return -(math.log(h) + _LOG_SQRT_2PI) + (m + math.log1p(r))
+
+    def compiled(self):
+        points, h, weights = self.parameters
+        return (math.fsum(p * w for p, w in zip(points, weights)), 1.0 / (2.0 * h * h), -(math.log(h) + _LOG_SQRT_2PI))
 
 
 class State(object):
@@ -251,10 +322,9 @@ class Model(object):
                                                                  "finite" if self.finite else "infinite"))
         # the flat form (include/poreseg.h ps_hmm_model)
         kind = np.zeros(S, np.int32)
-        param = np.zeros(3 * S, np.float64)
         for k, s in enumerate(emitting):
             kind[k] = s.distribution.kind
-            param[3 * k:3 * k + 3] = s.distribution.compiled()
+        param, kde = self._emission_tables(emitting, S)
         lv = np.array([level[id(s)] for s in silent], np.int64)
         n_levels = int(lv.max()) + 1 if lv.size else 0
         level_ptr = (NE + np.searchsorted(lv, np.arange(n_levels + 1))).astype(np.int32)
@@ -270,9 +340,25 @@ class Model(object):
             in_ptr=np.concatenate(([0], np.cumsum(np.bincount(dst, minlength=S)))).astype(np.int32),
             in_src=np.ascontiguousarray(src[by_dst]), in_lp=np.ascontiguousarray(lp[by_dst]),
             out_ptr=np.concatenate(([0], np.cumsum(np.bincount(src, minlength=S)))).astype(np.int32),
-            out_dst=np.ascontiguousarray(dst[by_src]), out_lp=np.ascontiguousarray(lp[by_src]))
+            out_dst=np.ascontiguousarray(dst[by_src]), out_lp=np.ascontiguousarray(lp[by_src]), **kde)
         self._in_order = by_dst                         # edges (= out-edge order) -> in-edge order
         self._c = None
+
+    @staticmethod
+    def _emission_tables(emitting, S):
+        """param[3 S] and the kernel-density CSR tables (kde_ptr[n_emit + 1] into kde_pt / kde_lw: the points and log
+        weights of the kind-3 states, zero-weight points left out)."""
+        param = np.zeros(3 * S, np.float64)
+        ptr, pts, lws = [0], [], []
+        for k, s in enumerate(emitting):
+            param[3 * k:3 * k + 3] = s.distribution.compiled()
+            if s.distribution.kind == KIND_KDE:
+                p, lw = s.distribution.tables()
+                pts.extend(p)
+                lws.extend(lw)
+            ptr.append(len(pts))
+        return param, dict(kde_ptr=np.array(ptr, np.int32), kde_pt=np.array(pts, np.float64).reshape(-1),
+                           kde_lw=np.array(lws, np.float64).reshape(-1))
 
     @property
     def flat(self):
@@ -290,6 +376,9 @@ class Model(object):
                 setattr(m, k, f[k])
             for k in ("kind", "level_ptr", "in_ptr", "in_src", "out_ptr", "out_dst", "param", "in_lp", "out_lp"):
                 setattr(m, k, f[k].ctypes.data if f[k].size else None)
+            if f["kde_pt"].size:                                # (read by the library only when some kind is 3)
+                for k in ("kde_ptr", "kde_pt", "kde_lw"):
+                    setattr(m, k, f[k].ctypes.data)
             self._c = m
         return self._c
 
@@ -433,7 +522,7 @@ class Model(object):
         self.edges = [(i, j, float(p)) for (i, j, _), p in zip(self.edges, new)]
         for i, j, p in self.edges:
             self._edges[(self.states[i], self.states[j])] = p
-        # normal states, pooled per distribution object
+        # normal states, pooled per distribution object (uniform and kernel-density distributions stay as they are)
         pooled = collections.OrderedDict()
         for k in range(NE):
             d = self.states[k].distribution
@@ -459,10 +548,8 @@ class Model(object):
             lp = np.log(np.array([e[2] for e in self.edges], np.float64).reshape(-1))
         f["out_lp"] = np.ascontiguousarray(lp)
         f["in_lp"] = np.ascontiguousarray(lp[self._in_order])
-        param = np.zeros(3 * f["n_states"], np.float64)
-        for k in range(f["n_emit"]):
-            param[3 * k:3 * k + 3] = self.states[k].distribution.compiled()
-        f["param"] = param
+        f["param"], kde = self._emission_tables(self.states[:f["n_emit"]], f["n_states"])
+        f.update(kde)
         self._flat = f
         self._c = None
 
