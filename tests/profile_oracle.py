@@ -40,6 +40,39 @@ def kde_logpdf_longdouble(points, bandwidth, weights, x):
     return -np.log(h * np.sqrt(2 * L(np.pi))) + m + np.log(np.exp(v - m).sum())
 
 
+PROBE_POINTS = (1, 2, 63, 64, 65, 200, 5000)
+PROBE_BANDWIDTHS = (1e-3, 0.05, 1.0, 30.0, 1e3)
+PROBE_ORDERS = ("random", "ascending", "descending", "equal")
+PROBE_WEIGHTS = ("equal", "wide")
+
+
+def kde_probe_grid(seed=1):
+    """The emission probe's configurations, [(name, GaussianKernelDensity, observations)]: points per state x bandwidth x
+    point order (random in [-50, 50], the same ascending -- HmmLse rescales on every term right of them --, descending,
+    all equal to 7.25 -- log1p runs up to log N) x weights (equal, or 10 ** uniform(-300, 0) with one weight 0 when
+    N > 2).  Seven observations each: the first point, the middle point + 0.3 h, -50 - 3 h, 50 + 40 h, 50 + 1e3 h, -1e4, 0.
+    Every emission is finite in float64 (the largest exponent, at h = 1e-3 and x = -1e4, is about 5e13)."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for N in PROBE_POINTS:
+        for h in PROBE_BANDWIDTHS:
+            for order in PROBE_ORDERS:
+                pts = rng.uniform(-50, 50, N)
+                if order == "ascending":
+                    pts = np.sort(pts)
+                elif order == "descending":
+                    pts = np.sort(pts)[::-1]
+                elif order == "equal":
+                    pts = np.full(N, 7.25)
+                for wk in PROBE_WEIGHTS:
+                    w = np.ones(N) if wk == "equal" else 10.0 ** rng.uniform(-300, 0, N)
+                    if wk == "wide" and N > 2:
+                        w[rng.integers(N)] = 0.0
+                    xs = [pts[0], pts[N // 2] + 0.3 * h, -50 - 3 * h, 50 + 40 * h, 50 + 1e3 * h, -1e4, 0.0]
+                    out.append(("k%04d_%g_%s_%s" % (N, h, order, wk), GaussianKernelDensity(pts, h, w), [float(x) for x in xs]))
+    return out
+
+
 def emission(state, x):
     d = state.distribution
     if type(d).__name__ == "GaussianKernelDensity":
@@ -48,8 +81,15 @@ def emission(state, x):
 
 
 class Compiled(O.Compiled):
+    """A view of the model as it is when made: the emissions of an observation are computed once per value and kept."""
+
     def emissions(self, x):
-        return np.array([emission(self.states[k], x) for k in range(self.NE)])
+        memo = self.__dict__.setdefault("_emissions", {})
+        key = float(x)
+        if key not in memo:
+            with np.errstate(over="ignore"):                  # (a distance whose square overflows: the emission is -inf)
+                memo[key] = np.array([emission(self.states[k], x) for k in range(self.NE)])
+        return memo[key].copy()
 
 
 def path_score(c, seq, path):
@@ -120,10 +160,12 @@ def shifts(model):
     return np.array(out, np.float64)
 
 
-def estep_one(model, seq):
-    """(counts aligned with model.edges, stats [NE, 3], logp) of one sequence; zeros when logp = -inf."""
+def estep_one(model, seq, c=None, sh=None):
+    """(counts aligned with model.edges, stats [NE, 3], logp) of one sequence; zeros when logp = -inf.  c, sh: a Compiled of
+    TO.View(model, model.edges) and shifts(model) to use again (made here otherwise)."""
     edges = model.edges
-    c = Compiled(TO.View(model, edges))
+    c = c if c is not None else Compiled(TO.View(model, edges))
+    sh = sh if sh is not None else shifts(model)
     seq = np.asarray(seq, np.float64)
     n, NE = seq.size, c.NE
     counts, stats = np.zeros(len(edges)), np.zeros((NE, 3))
@@ -133,24 +175,33 @@ def estep_one(model, seq):
         return counts, stats, logp
     B = O.backward(c, seq)
     em = np.array([c.emissions(x) for x in seq]).reshape(n, NE)
-    for e, (k, l, p) in enumerate(edges):
-        if not p > 0:
-            continue
-        v = F[:n, k] + math.log(p) + em[:, l] + B[1:, l] - logp if l < NE else F[:, k] + math.log(p) + B[:, l] - logp
-        counts[e] = np.exp(v[v > NEG]).sum() if v.size else 0.0
+    # every edge k -> l at once: f[t][k] + log p + e_l(x_t) + b[t+1][l] - logp over t < n (l emitting), or
+    # f[t][k] + log p + b[t][l] - logp over t <= n (l silent); a term of -inf (p = 0 included) adds exp(-inf) = 0
+    src = np.array([e[0] for e in edges], np.int64).reshape(-1)
+    dst = np.array([e[1] for e in edges], np.int64).reshape(-1)
+    with np.errstate(divide="ignore"):
+        lp = np.log(np.array([e[2] for e in edges], np.float64).reshape(-1))
+    to_emit = dst < NE
+    ke, le = src[to_emit], dst[to_emit]
+    if n and ke.size:
+        counts[to_emit] = np.exp(F[:n][:, ke] + lp[to_emit] + em[:, le] + B[1:][:, le] - logp).sum(axis=0)
+    ks, ls = src[~to_emit], dst[~to_emit]
+    if ks.size:
+        counts[~to_emit] = np.exp(F[:, ks] + lp[~to_emit] + B[:, ls] - logp).sum(axis=0)
     if n:
         with np.errstate(invalid="ignore"):
             g = np.exp(F[1:, :NE] + B[1:, :NE] - logp)
         g = np.where(np.isfinite(F[1:, :NE]) & np.isfinite(B[1:, :NE]), g, 0.0)
-        d = seq[:, None] - shifts(model)[None, :]
+        d = seq[:, None] - sh[None, :]
         stats[:, 0], stats[:, 1], stats[:, 2] = g.sum(axis=0), (g * d).sum(axis=0), (g * d * d).sum(axis=0)
     return counts, stats, logp
 
 
 def estep(model, seqs):
     counts, stats, logp = np.zeros(len(model.edges)), np.zeros((TO.n_emit(model), 3)), []
+    c, sh = Compiled(TO.View(model, model.edges)), shifts(model)
     for s in seqs:
-        cc, st, lp = estep_one(model, s)
+        cc, st, lp = estep_one(model, s, c, sh)
         logp.append(lp)
         if lp > NEG:
             counts += cc

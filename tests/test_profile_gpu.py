@@ -1,7 +1,13 @@
 """Kernel-density HMM states and the profile aligners on the MI355X (csrc/seg_hmm.hpp HmmDevK instantiations,
 pypore_amd.alignment) against tests/profile_oracle.py, with the bar and helpers' pattern of tests/test_hmm_gpu.py:
 log probabilities and matrix entries to 1e-12 relative to max(1, |oracle|), -inf exactly where the oracle has it, Viterbi
-paths identical where the oracle's winning margin exceeds 1e-9 relative and judged by their own score elsewhere."""
+paths identical where the oracle's winning margin exceeds 1e-9 relative and judged by their own score elsewhere.
+
+What this file draws is moderate: 1 to 200 points per state, bandwidths 0.2 to 5, observations within a few bandwidths and one
+far sequence, models of at most 200 states and in-degrees far below 256, and its oracle shares the device's formula.  The
+emission against long double over extreme point counts, orders, weights and bandwidths, the 16-bit backpointers, the state
+cap, the E-step's global-memory route by the model's own size and the upload cache on the kde_* tables are in
+tests/test_profile_kernels_gpu.py, which uses check_all, check_viterbi and assert_close from here."""
 import copy
 import ctypes
 import os
@@ -48,8 +54,8 @@ def check_viterbi(c, seq, got):
         assert score is not None and abs(score - lp) <= 1e-9 * max(1.0, abs(lp))
 
 
-def check_all(model, seqs, matrices=True):
-    c = P.Compiled(model)
+def check_all(model, seqs, matrices=True, c=None):
+    c = P.Compiled(model) if c is None else c
     for s, v in zip(seqs, model.viterbi_batch(seqs)):
         check_viterbi(c, s, v)
     assert_close(model.log_probability_batch(seqs), [O.log_probability(c, s) for s in seqs])

@@ -1,6 +1,8 @@
 """Host-side tests of the kernel-density emission and the profile aligners (no GPU): GaussianKernelDensity against scipy,
 the baked flat form, PSSM, the three model builders against probabilities written out here, the path-following loops on
-hand-made paths, the MSA score on columns worked by hand, and tests/profile_oracle.py against its own brute force."""
+hand-made paths, the MSA score on columns worked by hand, and tests/profile_oracle.py against its own brute force; the
+float64 restatements of the density against np.longdouble on the emission probe's grid (profile_oracle.kde_probe_grid), which
+tests/test_profile_kernels_gpu.py puts to the device."""
 import copy
 import math
 import os
@@ -78,6 +80,47 @@ def test_value_errors_freeze_and_repr():
     d.thaw()
     assert not d.frozen
     assert repr(d) == "GaussianKernelDensity([1.0, 2.0], 2.0, [0.5, 0.5])"
+
+
+# ---- the density against long double on the probe grid ----------------------------------------------------------------------
+def test_long_double_has_a_64_bit_mantissa():
+    assert np.finfo(np.longdouble).nmant >= 63
+
+
+# What the float64 restatements may lose against long double, relative to max(1, |value|).  A term lw - d^2 b carries four
+# roundings (d, d^2, the product, the difference), each at most eps / 2 of a magnitude the value itself bounds; exp turns
+# the error of v - m into a relative one of at most |v - m| eps, which exp(v - m) scales down again (t e^-t <= 1 / e); the N
+# positive terms are summed in sequence, whose error grows as sqrt(N) eps in the mean (7.8e-15 at N = 5000; N eps = 5.6e-13
+# in the worst case, still inside the 1e-12 bar of the device tests); log1p divides it by 1 + r.  So 1e-14 covers every point
+# count of the grid and leaves the device two orders of magnitude of the bar.  (Measured: 9.1e-16 at worst, at N = 200 and 5000.)
+HOST_MARGIN = 1e-14
+
+
+def test_host_restatements_against_long_double_on_the_probe_grid():
+    grid = P.kde_probe_grid()
+    assert len(grid) == 7 * 5 * 4 * 2 and len({name for name, _, _ in grid}) == len(grid)
+    worst = {}
+    for name, d, xs in grid:
+        pts, h, w = d.parameters
+        assert len(xs) == 7
+        for x in xs:
+            ref = P.kde_logpdf_longdouble(pts, h, w, x)
+            assert np.isfinite(ref)
+            for got in (d.log_probability(x), P.kde_logpdf(pts, h, w, x)):
+                err = float(abs(np.longdouble(got) - ref) / max(1.0, abs(float(ref))))
+                worst[len(pts)] = max(worst.get(len(pts), 0.0), err)
+    print("host restatements vs long double, worst per point count:", worst)
+    assert sorted(worst) == list(P.PROBE_POINTS) and max(worst.values()) <= HOST_MARGIN, worst
+
+
+def test_overflowing_distance_is_minus_infinity_on_the_host():
+    """(x - p)^2 overflows float64 at x = 1e200: the class and the float64 oracle give exactly -inf (float64 semantics are
+    the contract).  The long-double value is finite there, about -5e399: it is no yardstick for this case."""
+    d = GaussianKernelDensity([0.0, 1.0, 7.25], 1.0, [1.0, 2.0, 3.0])
+    assert d.log_probability(1e200) == -np.inf
+    with np.errstate(over="ignore"):
+        assert P.kde_logpdf(*d.parameters, 1e200) == -np.inf
+    assert np.isfinite(P.kde_logpdf_longdouble(*d.parameters, 1e200))
 
 
 # ---- the flat form -----------------------------------------------------------------------------------------------------
