@@ -417,6 +417,27 @@ int ps_hmm_batch(ps_ctx *ctx, const ps_hmm_model *model, int32_t mode, const dou
 int ps_hmm_expect(ps_ctx *ctx, const ps_hmm_model *model, const double *d_obs, const int64_t *h_off, int32_t n_seq,
                   double *d_logp, double *d_counts, double *d_stats, int32_t *h_skipped);
 
+/* Posterior decoding over a BATCH (sequence q = d_obs[h_off[q] .. h_off[q+1]), fp64, device; n = its length), nothing summed
+ * over the sequences.  d_logp[q] = the sequence's log probability (as PS_HMM_FORWARD; required).  Every other output is
+ * optional, a null pointer skips it:
+ *   d_post       n_emit doubles per observation, row h_off[q] + t for observation t of sequence q (n rows of n_emit, not
+ *                n + 1 rows of n_states): the log posterior  (f[t+1][k] + b[t+1][k]) - d_logp[q]  of emitting state k, -inf
+ *                where either matrix entry is -inf.
+ *   d_map_state  one int32 per observation, at h_off[q] + t: the emitting state with the largest entry of that row, the
+ *                lowest state index on a tie (the rule Viterbi uses for sources).
+ *   d_map_logp   [q] = the sum over t of those largest entries, added in ascending t: the same call gives the same bits, and
+ *                they are the bits of that sum over d_post.
+ *   d_counts_seq n_edges doubles per sequence at q * n_edges: that sequence's expected count of every out-edge, in the
+ *                order and by the arithmetic of ps_hmm_expect's d_counts (which is their sum over q, in another order).
+ *                The kernel zeroes the row.
+ * A sequence with d_logp[q] = -inf: its d_post rows are -inf, its d_map_state entries -1, d_map_logp[q] = -inf, its counts
+ * row 0.  An empty sequence has no rows, d_map_logp[q] = 0.0, and its counts row holds the silent edges at t = 0.  Forward
+ * matrices are kept in HBM for launches of at most option "hmm_fb_budget" bytes, as for ps_hmm_expect; every output
+ * belongs to one sequence, so the results do not depend on how the batch is cut.  Limits, status codes and the reuse of
+ * the model's upload as ps_hmm_expect.  Synchronises the context's stream before returning. */
+int ps_hmm_posterior(ps_ctx *ctx, const ps_hmm_model *model, const double *d_obs, const int64_t *h_off, int32_t n_seq,
+                     double *d_logp, double *d_post, int32_t *d_map_state, double *d_map_logp, double *d_counts_seq);
+
 /* Timing of the most recent ps_segment_batch, measured with HIP events on the context's stream.
  * ms[7] = the call's device work from the first upload to the last result copy (option "timing" >= 1, the
  * default); ms[3] = whole call on the host's wall clock.  With option "timing" = 2 an event is also recorded

@@ -47,8 +47,9 @@ class MetaEvent(MetaSegment):
     json_fields = EVENT_FIELDS
 
     def apply_hmm(self, hmm, algorithm='viterbi'):
-        """The HMM's `algorithm` ('viterbi', 'forward', 'backward', 'log_probability') on the segment means: for a
-        pypore_amd.hmm.Model, (logp, path) / a log matrix / a float, computed on the device."""
+        """The HMM's `algorithm` ('viterbi', 'forward', 'backward', 'log_probability', 'forward_backward',
+        'maximum_a_posteriori') on the segment means: for a pypore_amd.hmm.Model, (logp, path) / a log matrix / a float /
+        (transitions, emissions) / (logp, path of one emitting state per segment), computed on the device."""
         return _apply_hmm(self, hmm, algorithm)
 
     def delete(self):
@@ -166,8 +167,9 @@ class Event(Segment):
         return segments
 
     def apply_hmm(self, hmm, algorithm='viterbi'):
-        """The HMM's `algorithm` ('viterbi', 'forward', 'backward', 'log_probability') on the segment means: for a
-        pypore_amd.hmm.Model, (logp, path) / a log matrix / a float, computed on the device."""
+        """The HMM's `algorithm` ('viterbi', 'forward', 'backward', 'log_probability', 'forward_backward',
+        'maximum_a_posteriori') on the segment means: for a pypore_amd.hmm.Model, (logp, path) / a log matrix / a float /
+        (transitions, emissions) / (logp, path of one emitting state per segment), computed on the device."""
         return _apply_hmm(self, hmm, algorithm)
 
     def _segment(self, parser):

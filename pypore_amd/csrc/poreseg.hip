@@ -175,6 +175,7 @@ struct ps_ctx {
     long long hmm_bp_budget = 512ll << 20;   // option hmm_bp_budget: bytes of Viterbi backpointers per launch
     // Baum-Welch E-step (ps_hmm_expect): forward matrices of one launch, per-workgroup accumulator rows, the skipped count
     DevBuf hmm_fmat, hmm_acc, hmm_skip;
+    DevBuf hmm_pmax;                         // ps_hmm_posterior: the per-observation maxima that d_map_logp sums
     long long hmm_fb_budget = 4ll << 30;     // option hmm_fb_budget: bytes of forward matrices per launch
     bool hmm_expect_lds = true;              // option hmm_expect_lds 0: the accumulator rows stay in global memory
     int stitch_host = 0;      // 1: host stitch with halo tiles (the fallback path) always
@@ -1323,7 +1324,7 @@ void ps_destroy(ps_ctx *ctx)
                       &ctx->align_in, &ctx->align_scratch, &ctx->pw_in, &ctx->pw_scratch, &ctx->bridge_ext, &ctx->ext_slot, &ctx->ext_list,
                       &ctx->lat_state, &ctx->lat_seam, &ctx->lat_res, &ctx->pre_c, &ctx->ev_info_tr, &ctx->blk_cls,
                       &ctx->cls_mm, &ctx->nt_log, &ctx->hmm_model, &ctx->hmm_off, &ctx->hmm_bp,
-                      &ctx->hmm_last, &ctx->hmm_flags, &ctx->hmm_fmat, &ctx->hmm_acc, &ctx->hmm_skip};
+                      &ctx->hmm_last, &ctx->hmm_flags, &ctx->hmm_fmat, &ctx->hmm_acc, &ctx->hmm_skip, &ctx->hmm_pmax};
     for (DevBuf *b : bufs) b->release();
     ctx->h_meta.release(); ctx->h_dense.release(); ctx->h_small.release(); ctx->h_up.release(); ctx->h_hdr.release();
     for (auto &e : ctx->ev) if (e) (void)hipEventDestroy(e);
@@ -3115,6 +3116,94 @@ int ps_hmm_expect(ps_ctx *ctx, const ps_hmm_model *model, const double *d_obs, c
                       : hmm_expect_run<false>(ctx, DK, d_obs, h_off, d_off, n_seq, n_acc, E, d_logp, d_counts, d_stats, h_skipped);
     return in_lds ? hmm_expect_run<true>(ctx, D, d_obs, h_off, d_off, n_seq, n_acc, E, d_logp, d_counts, d_stats, h_skipped)
                   : hmm_expect_run<false>(ctx, D, d_obs, h_off, d_off, n_seq, n_acc, E, d_logp, d_counts, d_stats, h_skipped);
+}
+
+}  // extern "C"
+
+namespace {
+
+// ps_hmm_posterior: forward matrices per launch as in hmm_expect_run, one workgroup per sequence.  CNT: 0 no counts, 1 the
+// sequence's counts row updated in global memory, 2 in LDS behind the two score rows.
+template <int CNT, typename MD>
+int hmm_posterior_run(ps_ctx *ctx, const MD &D, const double *d_obs, const int64_t *h_off, const long long *d_off,
+                      int32_t n_seq, int E, double *d_logp, double *d_post, int32_t *d_map_state, double *d_map_logp,
+                      double *d_counts_seq)
+{
+    const size_t S = static_cast<size_t>(D.S);
+    const size_t lds = (2 * S + (CNT == 2 ? static_cast<size_t>(E) : 0)) * sizeof(double);
+    const size_t lds_fwd = 2 * S * sizeof(double);
+    HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_fwd_kernel<HMM_FORWARD, uint8_t, MD>), static_cast<int>(lds_fwd)));
+    HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_posterior_kernel<CNT, MD>), static_cast<int>(lds)));
+    if (d_map_logp) HIP_TRY(ctx, ctx->hmm_pmax.reserve(std::max<size_t>(1, static_cast<size_t>(h_off[n_seq])) * sizeof(double)));
+    const long long budget = std::max<long long>(1, ctx->hmm_fb_budget);
+    for (int32_t q0 = 0; q0 < n_seq;) {
+        // as many sequences as keep their forward matrices within the budget (at least one)
+        long long bytes = (h_off[q0 + 1] - h_off[q0] + 1) * static_cast<long long>(S * sizeof(double));
+        int32_t q1 = q0 + 1;
+        while (q1 < n_seq) {
+            const long long more = (h_off[q1 + 1] - h_off[q1] + 1) * static_cast<long long>(S * sizeof(double));
+            if (bytes + more > budget) break;
+            bytes += more; ++q1;
+        }
+        if (bytes > (16ll << 30)) return fail(ctx, PS_ERR_ARG, "sequence %d needs %lld bytes of forward matrix (16 GiB at most)", q0, bytes);
+        HIP_TRY(ctx, ctx->hmm_fmat.reserve(static_cast<size_t>(bytes)));
+        const long long row0 = h_off[q0] + q0;
+        double *fmat = ctx->hmm_fmat.as<double>();
+        if (ctx->debug) fprintf(stderr, "[poreseg] posterior launch: sequences %d..%d, %lld bytes of forward matrix, dynamic LDS %zu\n", q0, q1, bytes, lds);
+        hipLaunchKernelGGL((hmm_fwd_kernel<HMM_FORWARD, uint8_t, MD>), dim3(q1 - q0), dim3(HMM_NT), lds_fwd, ctx->stream, D, d_obs, d_off,
+                           q0, d_logp, fmat, row0, static_cast<uint8_t *>(nullptr), 0ll, static_cast<int *>(nullptr));
+        HIP_TRY(ctx, hipGetLastError());
+        hipLaunchKernelGGL((hmm_posterior_kernel<CNT, MD>), dim3(q1 - q0), dim3(HMM_NT), lds, ctx->stream, D, d_obs, d_off, q0,
+                           static_cast<const double *>(d_logp), static_cast<const double *>(fmat), row0, d_post, d_map_state,
+                           d_map_logp, ctx->hmm_pmax.as<double>(), d_counts_seq);
+        HIP_TRY(ctx, hipGetLastError());
+        q0 = q1;
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return PS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ps_hmm_posterior(ps_ctx *ctx, const ps_hmm_model *model, const double *d_obs, const int64_t *h_off, int32_t n_seq,
+                     double *d_logp, double *d_post, int32_t *d_map_state, double *d_map_logp, double *d_counts_seq)
+{
+    if (!ctx) return PS_ERR_ARG;
+    if (!model || !h_off) return fail(ctx, PS_ERR_ARG, "null pointer");
+    if (n_seq < 0) return fail(ctx, PS_ERR_ARG, "negative sequence count");
+    for (int32_t q = 0; q < n_seq; ++q) {
+        if (h_off[q] < 0 || h_off[q + 1] < h_off[q]) return fail(ctx, PS_ERR_ARG, "sequence offsets must be non-negative and ascending");
+        if (h_off[q + 1] - h_off[q] > INT32_MAX / 2) return fail(ctx, PS_ERR_ARG, "sequence %d too long", q);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HmmDevK DK;
+    int max_in = 0;
+    bool kde = false;
+    if (int rc = hmm_upload(ctx, model, &DK, &max_in, &kde)) return rc;
+    const HmmDev &D = DK;
+    const int E = model->out_ptr[D.S];
+    if (static_cast<long long>(E) + 3ll * D.n_emit + 1 > (1ll << 26)) return fail(ctx, PS_ERR_ARG, "model of %d edges: at most 2^26 accumulators", E);
+    if (n_seq == 0) return PS_OK;
+    if (!d_logp || (h_off[n_seq] > 0 && !d_obs)) return fail(ctx, PS_ERR_ARG, "null device pointer");
+    const size_t nb = (static_cast<size_t>(n_seq) + 1) * sizeof(int64_t);
+    HIP_TRY(ctx, ctx->h_up.reserve(nb));
+    HIP_TRY(ctx, ctx->hmm_off.reserve(nb));
+    std::memcpy(ctx->h_up.p, h_off, nb);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->hmm_off.p, ctx->h_up.p, nb, hipMemcpyHostToDevice, ctx->stream));
+    const long long *d_off = ctx->hmm_off.as<long long>();
+    // the counts row of a sequence: none asked for (or no edges), in LDS when it fits beside the score rows, else in place
+    const int cnt = !d_counts_seq || E == 0 ? 0
+                    : (2 * static_cast<size_t>(D.S) + static_cast<size_t>(E)) * sizeof(double) <= HMM_EXPECT_LDS && ctx->hmm_expect_lds ? 2 : 1;
+    auto run = [&](const auto &M) -> int {
+        switch (cnt) {
+        case 0: return hmm_posterior_run<0>(ctx, M, d_obs, h_off, d_off, n_seq, E, d_logp, d_post, d_map_state, d_map_logp, nullptr);
+        case 1: return hmm_posterior_run<1>(ctx, M, d_obs, h_off, d_off, n_seq, E, d_logp, d_post, d_map_state, d_map_logp, d_counts_seq);
+        default: return hmm_posterior_run<2>(ctx, M, d_obs, h_off, d_off, n_seq, E, d_logp, d_post, d_map_state, d_map_logp, d_counts_seq);
+        }
+    };
+    return kde ? run(DK) : run(D);
 }
 
 }  // extern "C"

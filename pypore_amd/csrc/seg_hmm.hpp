@@ -360,6 +360,131 @@ __global__ __launch_bounds__(256) void hmm_expect_reduce_kernel(const double *ac
     else *skipped = s;
 }
 
+// Posterior decoding (ps_hmm_posterior): the two passes of the E-step with every per-step value kept per observation
+// instead of summed over the batch.  One workgroup of one wave per sequence q of [q0, q0 + gridDim.x); the forward matrix
+// of the launch is in HBM (fmat, as for hmm_expect_kernel), the two backward rows stay in LDS.  For observation t (0 <= t
+// < n) and emitting state k the log posterior is  (f[t+1][k] + b[t+1][k]) - logp[q],  -inf where either term is -inf.
+// Every output is optional (null: skipped) and belongs to one sequence, so nothing is accumulated across workgroups:
+//   post       row off[q] + t, NE doubles: the log posteriors of observation t (stores coalesced over k);
+//   map_state  at off[q] + t: the emitting state of the largest entry of that row.  A lane keeps the maximum of its states
+//              k = lane, lane + 64, ... (ascending, replaced only by a strictly greater value), the lanes' maxima are
+//              combined by an xor butterfly that prefers the lower state on equal values: the lowest index wins a tie;
+//   map_logp   [q]: the sum of those maxima in ascending t.  The butterfly leaves the maximum in every lane; lane t % 64
+//              parks it in pmax[off[q] + t] (a scratch of one double per observation), and after the last step each lane
+//              reads back the entries it wrote, 64 at a time, and the wave adds them in order of t;
+//   counts_seq row q of E doubles: the sequence's expected count of every out-edge, formed as hmm_expect_kernel::one forms
+//              cnt[e], zeroed here by the lane that owns the edge's source state (CNT 1: the row is updated in place in
+//              global memory, CNT 2: in LDS behind the score rows and stored at the end; CNT 0: no counts).
+// logp[q] = -inf: the rows of post are -inf, map_state -1, map_logp -inf, the counts row 0.  n = 0: no rows, map_logp 0.0,
+// and the counts row holds the silent edges of step 0.
+template <int CNT, typename MD = HmmDev>
+__global__ __launch_bounds__(HMM_NT) void hmm_posterior_kernel(MD M, const double *obs, const long long *off, int q0,
+                                                               const double *logp, const double *fmat, long long f_row0,
+                                                               double *post, int *map_state, double *map_logp,
+                                                               double *pmax, double *counts_seq)
+{
+#pragma clang fp contract(off)
+    extern __shared__ double hm_lds[];
+    const int S = M.S, NE = M.n_emit, lane = threadIdx.x;
+    const int E = M.out_ptr[S];
+    const int q = q0 + blockIdx.x;
+    const long long base = off[q];
+    const int n = static_cast<int>(off[q + 1] - base);
+    const double lq = logp[q];
+    constexpr double NEG = -__builtin_inf();
+    double *crow = CNT ? counts_seq + static_cast<long long>(q) * E : nullptr;
+    double *cnt = CNT == 2 ? hm_lds + 2 * S : crow;
+
+    if (!(lq > NEG)) {
+        if (post)
+            for (long long i = lane, m = static_cast<long long>(n) * NE; i < m; i += HMM_NT) post[base * NE + i] = NEG;
+        if (map_state)
+            for (int t = lane; t < n; t += HMM_NT) map_state[base + t] = -1;
+        if (map_logp && lane == 0) map_logp[q] = NEG;
+        if (CNT)
+            for (int e = lane; e < E; e += HMM_NT) crow[e] = 0.0;
+        return;
+    }
+    if (CNT)        // (by the lane that adds to the edge in every step: no ordering between lanes is needed)
+        for (int k = lane; k < S; k += HMM_NT)
+            for (int e = M.out_ptr[k], e1 = M.out_ptr[k + 1]; e < e1; ++e) cnt[e] = 0.0;
+
+    const double *x = obs + base;
+    const double *f = fmat + (base + q - f_row0) * S;
+    double *nxt = hm_lds, *cur = hm_lds + S;
+    const bool want_map = map_state || map_logp;
+
+    auto one = [&](int k, int t, double fk) -> double {
+        const double w = fk - lq;
+        HmmLse lse;
+        if (t == n && (!M.finite || k == M.end)) lse.add(0.0);
+        const int e0 = M.out_ptr[k], e1 = M.out_ptr[k + 1];
+        for (int e = e0; e < e1; ++e) {
+            const int l = M.out_dst[e];
+            double v;
+            if (l < NE) {
+                if (t >= n) continue;
+                v = nxt[l] + M.out_lp[e];
+            } else v = cur[l] + M.out_lp[e];
+            lse.add(v);
+            if (CNT && w > NEG && v > NEG) cnt[e] += exp(w + v);
+        }
+        const double b = lse.get();
+        cur[k] = b;
+        return b;
+    };
+
+    for (int t = n; t >= 0; --t) {
+        const double *frow = f + static_cast<long long>(t) * S;
+        if (t < n) {
+            double *tmp = nxt; nxt = cur; cur = tmp;
+            const double xt = x[t];
+            for (int l = lane; l < NE; l += HMM_NT) nxt[l] = nxt[l] > NEG ? nxt[l] + hmm_emit(M, l, xt) : NEG;
+            hm_sync();
+        }
+        for (int L = M.n_levels - 1; L >= 0; --L) {
+            const int hi = M.level_ptr[L + 1];
+            for (int k = M.level_ptr[L] + lane; k < hi; k += HMM_NT) one(k, t, frow[k]);
+            hm_sync();
+        }
+        double *prow = post && t > 0 ? post + (base + t - 1) * NE : nullptr;
+        double m = NEG; int am = 0x7fffffff;
+        for (int k = lane; k < NE; k += HMM_NT) {
+            const double fk = frow[k];
+            const double bk = one(k, t, fk);
+            if (t > 0) {
+                const double v = (fk > NEG && bk > NEG) ? (fk + bk) - lq : NEG;
+                if (prow) prow[k] = v;
+                if (v > m) { m = v; am = k; }
+            }
+        }
+        hm_sync();
+        if (t > 0 && want_map) {
+            for (int d = 32; d; d >>= 1) {
+                const double om = __shfl_xor(m, d); const int oa = __shfl_xor(am, d);
+                if (om > m || (om == m && oa < am)) { m = om; am = oa; }
+            }
+            if (lane == ((t - 1) & (HMM_NT - 1))) {
+                if (map_state) map_state[base + t - 1] = m > NEG ? am : -1;
+                if (map_logp) pmax[base + t - 1] = m;
+            }
+        }
+    }
+    if (CNT == 2) {
+        hm_sync();
+        for (int e = lane; e < E; e += HMM_NT) crow[e] = cnt[e];
+    }
+    if (map_logp) {
+        double s = 0.0;
+        for (int c = 0; c < n; c += HMM_NT) {
+            const double v = c + lane < n ? pmax[base + c + lane] : 0.0;      // (written by this lane)
+            const int m = n - c < HMM_NT ? n - c : HMM_NT;
+            for (int j = 0; j < m; ++j) s += __shfl(v, j);
+        }
+        if (lane == 0) map_logp[q] = s;
+    }
+}
+
 // Viterbi traceback, one lane per sequence: from (n, last[q]) back to (0, start).  An emitting state steps back one
 // observation, a silent one stays.  The path goes to path[path_off[q] ..] in forward order when it fits; path_len[q] is its
 // length either way (0: the sequence is impossible).  *flags: bit 0 a path did not fit, bit 1 a walk left the model (a bug).

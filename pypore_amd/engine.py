@@ -594,6 +594,31 @@ class Context(object):
         return logp[:n_seq], counts[:n_edges], stats[:model.n_emit], int(skipped.value)
 
     @_serialised
+    def hmm_posterior(self, model, obs, off, want_post=False, want_map=True, want_counts=False):
+        """ps_hmm_posterior: posterior decoding over a batch, nothing summed over the sequences.  model: a _lib.HmmModel
+        (its arrays kept alive by the caller); obs: float64 CUDA tensor, sequence q = obs[off[q]:off[q+1]].  Returns (logp
+        float64 [n_seq]; log posteriors float64 [off[-1], n_emit] when want_post; MAP states int32 [off[-1]] and MAP log
+        probabilities float64 [n_seq] when want_map; per-sequence edge counts float64 [n_seq, n_edges] in out-edge order
+        when want_counts), None for what was not asked for: only the outputs asked for are allocated."""
+        assert obs.is_cuda and obs.is_contiguous() and obs.dtype == torch.float64
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        n_seq, total = off.size - 1, int(off[-1])
+        dev = obs.device
+        n_edges = int(ctypes.cast(model.out_ptr, ctypes.POINTER(ctypes.c_int32))[model.n_states])
+        logp = torch.empty(max(n_seq, 1), dtype=torch.float64, device=dev)
+        post = torch.empty((total, model.n_emit), dtype=torch.float64, device=dev) if want_post else None
+        map_state = torch.empty(total, dtype=torch.int32, device=dev) if want_map else None
+        map_logp = torch.empty(max(n_seq, 1), dtype=torch.float64, device=dev) if want_map else None
+        counts = torch.empty((n_seq, n_edges), dtype=torch.float64, device=dev) if want_counts else None
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)   # noqa: E731
+        torch.cuda.current_stream(dev).synchronize()
+        _lib.check(self.L.ps_hmm_posterior(self.handle, ctypes.byref(model), ctypes.c_void_p(obs.data_ptr()),
+                                           off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n_seq,
+                                           ctypes.c_void_p(logp.data_ptr()), ptr(post), ptr(map_state), ptr(map_logp),
+                                           ptr(counts)), self.handle)
+        return logp[:n_seq], post, map_state, map_logp[:n_seq] if want_map else None, counts
+
+    @_serialised
     def synth_trace(self, n, seed, seg_end, level_counts, dtype=torch.float32, start=0):
         """Synthetic step trace generated directly in HBM (csrc synth_kernel == pypore_amd.synth).  start > 0: the
         samples [start, start + n) of the trace the table describes (a rank's piece of one long trace): the noise hash

@@ -1,6 +1,6 @@
 """Hidden Markov models with the surface the reference's HMM code uses (yahmm: Model, State, NormalDistribution,
-UniformDistribution, GaussianKernelDensity; add_state(s), add_transition, add_model, bake; viterbi, forward, backward, log_probability), decoded on
-the MI355X (ps_hmm_batch, csrc/seg_hmm.hpp), and trained there (Model.train: Baum-Welch with its E-step in ps_hmm_expect,
+UniformDistribution, GaussianKernelDensity; add_state(s), add_transition, add_model, bake; viterbi, forward, backward, log_probability,
+forward_backward, maximum_a_posteriori), decoded on the MI355X (ps_hmm_batch, ps_hmm_posterior, csrc/seg_hmm.hpp), and trained there (Model.train: Baum-Welch with its E-step in ps_hmm_expect,
 or Viterbi training).
 
     model = Model("happy model")
@@ -40,6 +40,29 @@ Deviations from yahmm, by design:
     and so drop those silent states from its paths; here every silent state visited appears in the path.
   * `end` is kept in model.states even when it cannot be reached (the model is then infinite).
   * Edges of probability 0 are dropped; negative probabilities raise ValueError.
+
+Posterior decoding (forward_backward, maximum_a_posteriori and their _batch twins; the device -- ps_hmm_posterior,
+csrc/seg_hmm.hpp hmm_posterior_kernel -- and tests/posterior_oracle.py compute the same thing).  For one sequence x of
+length n with f, b and logp as above:
+  * the log posterior of emitting state k for observation t (0 <= t < n) is  (f[t+1][k] + b[t+1][k]) - logp,  -inf where
+    either matrix entry is -inf: `emissions`, n rows of n_emit (the emitting states come first in `states`);
+  * the MAP state of observation t is the emitting state with the largest entry of row t, the lowest index on a tie (the
+    rule Viterbi uses for sources); the MAP log probability is the sum of those largest entries in ascending t, so it is
+    bit for bit the sum one takes over `emissions`.  The MAP path need not be a path of the model: it maximises every
+    observation's state on its own;
+  * `transitions`[k][l] is the sequence's expected count of edge k -> l by the formula under Training below, per
+    sequence instead of summed over the batch, 0 where the model has no such edge;
+  * an impossible sequence (logp = -inf) has emissions -inf, transitions 0 and MAP result (-inf, None); an empty one has
+    no rows, MAP result (0.0, []), and its transitions hold the silent edges at t = 0.
+Nothing is summed across sequences, so a batch gives the bits of the single calls however the library cuts it.
+
+Deviations from yahmm, by design:
+  * yahmm is not available to compare against.  What is assumed of its forward_backward is the shape of its result, a
+    pair (transitions, emissions): expected transition counts NOT in log space, as a dense states x states array in
+    the order of `states`, and emission weights IN log space, one row per observation.  Here emissions has a column per
+    emitting state (the first n_emit of `states`), none for silent states.
+  * maximum_a_posteriori returns (logp, path) in viterbi's element format, (index, state) per observation, and (-inf,
+    None) for an impossible sequence; silent states never appear in it.
 
 Training (Model.train; the device and tests/hmm_train_oracle.py compute the same thing).  For one sequence x of length n
 with forward matrix f, backward matrix b and log probability logp (above):
@@ -449,6 +472,48 @@ class Model(object):
 
     def log_probability(self, sequence):
         return float(self.log_probability_batch([sequence])[0])
+
+    # ---- posterior decoding ---------------------------------------------------------------------------------------
+    def maximum_a_posteriori_batch(self, sequences, device=None):
+        """[(logp, path) per sequence] by posterior decoding on the device (ps_hmm_posterior, module docstring): path =
+        [(index into `states`, state)] with one entry per observation -- the emitting state of the largest posterior, the
+        lowest index on a tie; emitting states only -- and logp = the sum of those log posteriors.  An impossible
+        sequence gives (-inf, None), an empty one (0.0, []).  Only the MAP states and their sums leave the device."""
+        ctx, off, obs = self._upload(sequences, device)
+        seq_logp, _, state, logp, _ = ctx.hmm_posterior(self._c_model(), obs, off, want_post=False, want_map=True)
+        seq_logp, state, logp = seq_logp.cpu().numpy(), state.cpu().numpy(), logp.cpu().numpy()
+        out = []
+        for q in range(off.size - 1):
+            if not seq_logp[q] > NEG_INF:
+                out.append((NEG_INF, None))
+                continue
+            out.append((float(logp[q]), [(int(i), self.states[i]) for i in state[off[q]:off[q + 1]]]))
+        return out
+
+    def forward_backward_batch(self, sequences, device=None):
+        """[(transitions, emissions) per sequence] (ps_hmm_posterior, module docstring): transitions = float64
+        [len(states), len(states)], the expected count of every edge (from, to) in the sequence (not in log space; 0
+        where there is no edge), scattered from the device's per-sequence row through `edges`; emissions = float64
+        [n, n_emit], the log posterior of every emitting state per observation.  An impossible sequence has transitions
+        0 and emissions -inf."""
+        ctx, off, obs = self._upload(sequences, device)
+        _, post, _, _, counts = ctx.hmm_posterior(self._c_model(), obs, off, want_post=True, want_map=False, want_counts=True)
+        post, counts = post.cpu().numpy(), counts.cpu().numpy()
+        S = len(self.states)
+        src = np.array([e[0] for e in self.edges], np.int64).reshape(-1)
+        dst = np.array([e[1] for e in self.edges], np.int64).reshape(-1)
+        out = []
+        for q in range(off.size - 1):
+            transitions = np.zeros((S, S), np.float64)
+            transitions[src, dst] = counts[q]
+            out.append((transitions, post[off[q]:off[q + 1]]))
+        return out
+
+    def maximum_a_posteriori(self, sequence):
+        return self.maximum_a_posteriori_batch([sequence])[0]
+
+    def forward_backward(self, sequence):
+        return self.forward_backward_batch([sequence])[0]
 
     # ---- training ------------------------------------------------------------------------------------------------
     def expected_counts_batch(self, sequences, device=None):
