@@ -52,3 +52,43 @@ def passes(launches):
             out.append([])
         out[-1].append(l)
     return out
+
+
+SENTINEL = -7
+
+
+def batch_once(ctx, pairs, mode, penalty, min_length, col_slots, aln_slots):
+    """One ps_pairwise_batch call, as engine.Context.pairwise_batch makes it, with the caller's slots and with every
+    output buffer filled with SENTINEL beforehand; nothing is run again.  pairs: (x, y) of float64 arrays (NaN: the marker).
+    Returns (return code, dict of the raw buffers as numpy arrays, col_off, aln_off)."""
+    import ctypes
+
+    import numpy as np
+    import torch
+    dev = torch.device("cuda", ctx.device)
+
+    def pack(seqs):
+        off = np.concatenate(([0], np.cumsum([len(s) for s in seqs]))).astype(np.int64)
+        flat = np.concatenate([np.asarray(s, dtype=np.float64) for s in seqs]) if off[-1] else np.zeros(1)
+        return torch.from_numpy(np.ascontiguousarray(flat, dtype=np.float64)).to(dev), off
+    a, a_off = pack([p[0] for p in pairs])
+    b, b_off = pack([p[1] for p in pairs])
+    n = len(pairs)
+    idx = np.arange(n, dtype=np.int32)
+    col_off = np.concatenate(([0], np.cumsum(col_slots))).astype(np.int64)
+    aln_off = np.concatenate(([0], np.cumsum(aln_slots))).astype(np.int64)
+    n_col, n_aln = int(col_off[-1]) + 16, int(aln_off[-1]) + 16          # a margin behind the last slot, watched too
+    i32 = lambda k: torch.full((k,), SENTINEL, dtype=torch.int32, device=dev)
+    f64 = lambda k: torch.full((k,), float(SENTINEL), dtype=torch.float64, device=dev)
+    buf = {"scores": f64(n), "status": i32(n), "cols_i": i32(n_col), "cols_j": i32(n_col), "col_need": i32(n),
+           "aln_score": f64(n_aln), "aln_start": i32(n_aln), "aln_len": i32(n_aln), "aln_count": i32(n)}
+    i64p, i32p = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)
+    ptr = lambda name: ctypes.c_void_p(buf[name].data_ptr())
+    torch.cuda.synchronize(dev)
+    with ctx.lock:
+        rc = ctx.L.ps_pairwise_batch(
+            ctx.handle, ctypes.c_void_p(a.data_ptr()), a_off.ctypes.data_as(i64p), n, ctypes.c_void_p(b.data_ptr()),
+            b_off.ctypes.data_as(i64p), n, idx.ctypes.data_as(i32p), idx.ctypes.data_as(i32p), n, int(mode), float(penalty),
+            int(min_length), ptr("scores"), ptr("status"), col_off.ctypes.data_as(i64p), ptr("cols_i"), ptr("cols_j"),
+            ptr("col_need"), aln_off.ctypes.data_as(i64p), ptr("aln_score"), ptr("aln_start"), ptr("aln_len"), ptr("aln_count"))
+    return rc, {k: v.cpu().numpy() for k, v in buf.items()}, col_off, aln_off
