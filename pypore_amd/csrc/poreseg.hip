@@ -18,6 +18,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <condition_variable>
 #include <mutex>
 #include <string>
@@ -2568,6 +2569,52 @@ int ps_filter_requantise_batch(ps_ctx *ctx, const void *d_samples, const ps_samp
     return PS_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// Offsets of a set of sequences (`what` names it in the error): non-negative, ascending, no sequence longer than
+// INT32_MAX / 2; *longest = the longest sequence
+int check_offsets(ps_ctx *ctx, const int64_t *off, int32_t n, const char *what, int64_t *longest)
+{
+    *longest = 0;
+    for (int32_t q = 0; q < n; ++q) {
+        const int64_t len = off[q + 1] - off[q];
+        if (len < 0 || off[q] < 0) return fail(ctx, PS_ERR_ARG, "%s offsets must be non-negative and ascending", what);
+        if (len > INT32_MAX / 2) return fail(ctx, PS_ERR_ARG, "%s %d too long", what, q);
+        *longest = std::max(*longest, len);
+    }
+    return PS_OK;
+}
+
+// Host arrays staged back to back through h_up and copied to the start of `dev` in one transfer (the layout is the caller's:
+// 8-byte tables before 4-byte ones).  The first `head` bytes are not copied from anywhere: fill(h_up) writes them in place.
+struct HostTable { const void *p; size_t bytes; };
+template <typename Fill>
+int upload_tables(ps_ctx *ctx, DevBuf &dev, size_t head, Fill &&fill, std::initializer_list<HostTable> tables)
+{
+    size_t bytes = head;
+    for (const HostTable &t : tables) bytes += t.bytes;
+    HIP_TRY(ctx, ctx->h_up.reserve(bytes));
+    HIP_TRY(ctx, dev.reserve(bytes));
+    fill(ctx->h_up.p);
+    char *h = static_cast<char *>(ctx->h_up.p) + head;
+    for (const HostTable &t : tables) {
+        if (t.bytes) std::memcpy(h, t.p, t.bytes);
+        h += t.bytes;
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(dev.p, ctx->h_up.p, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return PS_OK;
+}
+int upload_tables(ps_ctx *ctx, DevBuf &dev, std::initializer_list<HostTable> tables)
+{
+    return upload_tables(ctx, dev, 0, [](void *) {}, tables);
+}
+
+}  // namespace
+
+extern "C" {
+
 int ps_align_batch(ps_ctx *ctx, const double *h_model_means, const double *h_model_stds, const double *h_model_durs,
                    int32_t m, double skip_penalty, double backslip_penalty, const double *d_seq_means,
                    const double *d_seq_stds, const double *d_seq_durs, const int64_t *h_seq_off, int32_t n_seq,
@@ -2580,21 +2627,12 @@ int ps_align_batch(ps_ctx *ctx, const double *h_model_means, const double *h_mod
     if (n_seq == 0) return PS_OK;
     if (!d_scores || !d_paths || !d_status) return fail(ctx, PS_ERR_ARG, "null output pointer");
     int64_t s_max = 0;
-    for (int32_t q = 0; q < n_seq; ++q) {
-        const int64_t len = h_seq_off[q + 1] - h_seq_off[q];
-        if (len < 0 || h_seq_off[q] < 0) return fail(ctx, PS_ERR_ARG, "sequence offsets must be non-negative and ascending");
-        if (len > INT32_MAX / 2) return fail(ctx, PS_ERR_ARG, "sequence %d too long", q);
-        s_max = std::max(s_max, len);
-    }
+    if (int rc = check_offsets(ctx, h_seq_off, n_seq, "sequence", &s_max)) return rc;
     if (h_seq_off[n_seq] > 0 && (!d_seq_means || !d_seq_stds || !d_seq_durs)) return fail(ctx, PS_ERR_ARG, "null sequence pointer");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // one upload: model rows (mean, std, dur*skip, dur*backslip, first-row penalty, dur), then the offsets
-    const size_t model_bytes = static_cast<size_t>(6) * m * sizeof(double);
-    const size_t off_bytes = (static_cast<size_t>(n_seq) + 1) * sizeof(int64_t);
-    HIP_TRY(ctx, ctx->h_up.reserve(model_bytes + off_bytes));
-    HIP_TRY(ctx, ctx->align_in.reserve(model_bytes + off_bytes));
-    {
-        double *h = ctx->h_up.as<double>();
+    auto model_rows = [&](void *staging) {
+        double *h = static_cast<double *>(staging);
         double run = 0.0;                                   // np.cumsum(model_dur): sequential (calignment.pyx:30)
         for (int j = 0; j < m; ++j) {
             run = j ? run + h_model_durs[j] : h_model_durs[j];
@@ -2605,9 +2643,9 @@ int ps_align_batch(ps_ctx *ctx, const double *h_model_means, const double *h_mod
             h[4 * m + j] = skip_penalty * (run - h_model_durs[j]);      // :52
             h[5 * m + j] = h_model_durs[j];
         }
-        std::memcpy(h + 6 * m, h_seq_off, off_bytes);
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->align_in.p, ctx->h_up.p, model_bytes + off_bytes, hipMemcpyHostToDevice, ctx->stream));
+    };
+    if (int rc = upload_tables(ctx, ctx->align_in, static_cast<size_t>(6) * m * sizeof(double), model_rows,
+                               {{h_seq_off, (static_cast<size_t>(n_seq) + 1) * sizeof(int64_t)}})) return rc;
     AlignModel M;
     const double *dm = ctx->align_in.as<double>();
     M.mean = dm; M.std = dm + m; M.dsp = dm + 2 * m; M.dbp = dm + 3 * m; M.pen0 = dm + 4 * m; M.dur = dm + 5 * m;
@@ -2634,23 +2672,6 @@ int ps_align_batch(ps_ctx *ctx, const double *h_model_means, const double *h_mod
     return PS_OK;
 }
 
-namespace {
-
-// offsets of a set of sequences: non-negative, ascending; *longest = the longest sequence
-int pw_check_off(ps_ctx *ctx, const int64_t *off, int32_t n, const char *what, int64_t *longest)
-{
-    *longest = 0;
-    for (int32_t q = 0; q < n; ++q) {
-        const int64_t len = off[q + 1] - off[q];
-        if (len < 0 || off[q] < 0) return fail(ctx, PS_ERR_ARG, "%s offsets must be non-negative and ascending", what);
-        if (len > INT32_MAX / 2) return fail(ctx, PS_ERR_ARG, "%s sequence %d too long", what, q);
-        *longest = std::max(*longest, len);
-    }
-    return PS_OK;
-}
-
-}  // namespace
-
 int ps_pairwise_scores(ps_ctx *ctx, const double *d_a, const int64_t *h_a_off, int32_t n_a, const double *d_b,
                        const int64_t *h_b_off, int32_t n_b, int32_t mode, double penalty, double *d_scores, int32_t *d_pos)
 {
@@ -2662,17 +2683,13 @@ int ps_pairwise_scores(ps_ctx *ctx, const double *d_a, const int64_t *h_a_off, i
     if (n_a == 0 || n_b == 0) return PS_OK;
     if (!d_scores) return fail(ctx, PS_ERR_ARG, "null output pointer");
     int64_t m_max = 0, n_max = 0;
-    if (int rc = pw_check_off(ctx, h_a_off, n_a, "A", &m_max)) return rc;
-    if (int rc = pw_check_off(ctx, h_b_off, n_b, "B", &n_max)) return rc;
+    if (int rc = check_offsets(ctx, h_a_off, n_a, "A sequence", &m_max)) return rc;
+    if (int rc = check_offsets(ctx, h_b_off, n_b, "B sequence", &n_max)) return rc;
     if (n_max > PW_N_MAX) return fail(ctx, PS_ERR_ARG, "a B sequence of %lld elements: the device pairwise aligner takes up to %d", (long long)n_max, PW_N_MAX);
     if ((h_a_off[n_a] > 0 && !d_a) || (h_b_off[n_b] > 0 && !d_b)) return fail(ctx, PS_ERR_ARG, "null sequence pointer");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t na_b = (static_cast<size_t>(n_a) + 1) * sizeof(int64_t), nb_b = (static_cast<size_t>(n_b) + 1) * sizeof(int64_t);
-    HIP_TRY(ctx, ctx->h_up.reserve(na_b + nb_b));
-    HIP_TRY(ctx, ctx->pw_in.reserve(na_b + nb_b));
-    std::memcpy(ctx->h_up.p, h_a_off, na_b);
-    std::memcpy(static_cast<char *>(ctx->h_up.p) + na_b, h_b_off, nb_b);
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->pw_in.p, ctx->h_up.p, na_b + nb_b, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = upload_tables(ctx, ctx->pw_in, {{h_a_off, (static_cast<size_t>(n_a) + 1) * sizeof(int64_t)},
+                                                  {h_b_off, (static_cast<size_t>(n_b) + 1) * sizeof(int64_t)}})) return rc;
     const long long *da_off = ctx->pw_in.as<long long>(), *db_off = da_off + n_a + 1;
     const int n_cap = static_cast<int>(std::max<int64_t>(n_max, 1));
     const size_t lds = pw_lds_bytes(n_cap);
@@ -2707,8 +2724,8 @@ int ps_pairwise_batch(ps_ctx *ctx, const double *d_a, const int64_t *h_a_off, in
     if (!d_scores || !d_status || !d_cols_i || !d_cols_j || !d_col_need || !d_aln_score || !d_aln_start || !d_aln_len || !d_aln_count)
         return fail(ctx, PS_ERR_ARG, "null output pointer");
     int64_t m_max = 0, n_max = 0;
-    if (int rc = pw_check_off(ctx, h_a_off, n_a, "A", &m_max)) return rc;
-    if (int rc = pw_check_off(ctx, h_b_off, n_b, "B", &n_max)) return rc;
+    if (int rc = check_offsets(ctx, h_a_off, n_a, "A sequence", &m_max)) return rc;
+    if (int rc = check_offsets(ctx, h_b_off, n_b, "B sequence", &n_max)) return rc;
     if ((h_a_off[n_a] > 0 && !d_a) || (h_b_off[n_b] > 0 && !d_b)) return fail(ctx, PS_ERR_ARG, "null sequence pointer");
     for (int32_t q = 0; q < n_pairs; ++q) {
         if (h_pair_a[q] < 0 || h_pair_a[q] >= n_a || h_pair_b[q] < 0 || h_pair_b[q] >= n_b) return fail(ctx, PS_ERR_ARG, "pair %d names a sequence that is not there", q);
@@ -2721,18 +2738,9 @@ int ps_pairwise_batch(ps_ctx *ctx, const double *d_a, const int64_t *h_a_off, in
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // one upload: the four 8-byte tables, the two pair tables, the capacity flag
     const size_t na = static_cast<size_t>(n_a) + 1, nb = static_cast<size_t>(n_b) + 1, np = static_cast<size_t>(n_pairs);
-    const size_t b8 = (na + nb + 2 * (np + 1)) * sizeof(int64_t), bytes = b8 + (2 * np + 2) * sizeof(int32_t);
-    HIP_TRY(ctx, ctx->h_up.reserve(bytes));
-    HIP_TRY(ctx, ctx->pw_in.reserve(bytes));
-    {
-        int64_t *h = ctx->h_up.as<int64_t>();
-        std::memcpy(h, h_a_off, na * 8); std::memcpy(h + na, h_b_off, nb * 8);
-        std::memcpy(h + na + nb, h_col_off, (np + 1) * 8); std::memcpy(h + na + nb + np + 1, h_aln_off, (np + 1) * 8);
-        int32_t *hi = reinterpret_cast<int32_t *>(h + na + nb + 2 * (np + 1));
-        std::memcpy(hi, h_pair_a, np * 4); std::memcpy(hi + np, h_pair_b, np * 4);
-        hi[2 * np] = 0; hi[2 * np + 1] = 0;
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->pw_in.p, ctx->h_up.p, bytes, hipMemcpyHostToDevice, ctx->stream));
+    const int32_t no_flags[2] = {0, 0};
+    if (int rc = upload_tables(ctx, ctx->pw_in, {{h_a_off, na * 8}, {h_b_off, nb * 8}, {h_col_off, (np + 1) * 8}, {h_aln_off, (np + 1) * 8},
+                                                  {h_pair_a, np * 4}, {h_pair_b, np * 4}, {no_flags, sizeof(no_flags)}})) return rc;
     PwBatch P;
     P.a = d_a; P.b = d_b;
     P.a_off = ctx->pw_in.as<long long>(); P.b_off = P.a_off + na; P.col_off = P.b_off + nb; P.aln_off = P.col_off + np + 1;
@@ -2904,25 +2912,88 @@ int hmm_upload(ps_ctx *ctx, const ps_hmm_model *m, HmmDevK *D, int *max_in, bool
     return PS_OK;
 }
 
+// The launch plan the sequence-model entry points share.
+
+// q1 of the launch that starts at sequence q0: as many sequences as keep (len + 1) * row_bytes within the budget, at least
+// one; *bytes = what they take
+int32_t next_chunk(const int64_t *h_off, int32_t q0, int32_t n_seq, size_t row_bytes, long long budget, long long *bytes)
+{
+    *bytes = (h_off[q0 + 1] - h_off[q0] + 1) * static_cast<long long>(row_bytes);
+    int32_t q1 = q0 + 1;
+    while (q1 < n_seq) {
+        const long long more = (h_off[q1 + 1] - h_off[q1] + 1) * static_cast<long long>(row_bytes);
+        if (*bytes + more > budget) break;
+        *bytes += more; ++q1;
+    }
+    return q1;
+}
+
+// a model with kernel-density states takes the HmmDevK instantiations, any other the HmmDev ones
+template <typename F> int with_model(bool kde, const HmmDevK &DK, F &&f)
+{
+    return kde ? f(DK) : f(static_cast<const HmmDev &>(DK));
+}
+
+// The forward pass of sequences [q0, q1): logp, and the matrix (optional) with sequence q at row off[q] + q - row0 of fmat
+template <typename MD>
+int launch_forward(ps_ctx *ctx, const MD &D, const double *d_obs, const long long *d_off, int32_t q0, int32_t q1, double *d_logp,
+                   double *fmat, long long row0)
+{
+    const size_t lds = 2 * static_cast<size_t>(D.S) * sizeof(double);
+    HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_fwd_kernel<HMM_FORWARD, uint8_t, MD>), static_cast<int>(lds)));
+    hipLaunchKernelGGL((hmm_fwd_kernel<HMM_FORWARD, uint8_t, MD>), dim3(q1 - q0), dim3(HMM_NT), lds, ctx->stream, D, d_obs, d_off,
+                       q0, d_logp, fmat, row0, static_cast<uint8_t *>(nullptr), 0ll, static_cast<int *>(nullptr));
+    HIP_TRY(ctx, hipGetLastError());
+    return PS_OK;
+}
+
+// What ps_hmm_batch, ps_hmm_expect and ps_hmm_posterior begin with: the arguments checked (host_ok: the entry point's own
+// host pointers are there), the model uploaded -- a bad one is refused whatever the batch --, own(C): the entry point's
+// checks that need the model (and what it does for an empty batch), and last, for a batch that is not empty, the offsets,
+// followed by the path slots' where there are some, on the device.  An empty batch leaves d_off null.
+struct HmmCall {
+    HmmDevK DK;
+    bool kde = false;
+    int max_in = 0, E = 0;                  // most in-edges of a state, out-edges of the model
+    const long long *d_off = nullptr;
+};
+template <typename Own>
+int hmm_begin(ps_ctx *ctx, const ps_hmm_model *model, bool host_ok, const double *d_obs, const int64_t *h_off,
+              const int64_t *h_path_off, int32_t n_seq, const double *d_logp, HmmCall *C, Own &&own)
+{
+    if (!ctx) return PS_ERR_ARG;
+    if (!model || !h_off || !host_ok) return fail(ctx, PS_ERR_ARG, "null pointer");
+    if (n_seq < 0) return fail(ctx, PS_ERR_ARG, "negative sequence count");
+    int64_t longest = 0;
+    if (int rc = check_offsets(ctx, h_off, n_seq, "sequence", &longest)) return rc;
+    for (int32_t q = 0; h_path_off && q < n_seq; ++q)
+        if (h_path_off[q] < 0 || h_path_off[q + 1] < h_path_off[q]) return fail(ctx, PS_ERR_ARG, "path offsets must be non-negative and ascending");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int rc = hmm_upload(ctx, model, &C->DK, &C->max_in, &C->kde)) return rc;
+    C->E = model->out_ptr[C->DK.S];
+    if (int rc = own(*C)) return rc;
+    if (n_seq == 0) return PS_OK;
+    if (!d_logp || (h_off[n_seq] > 0 && !d_obs)) return fail(ctx, PS_ERR_ARG, "null device pointer");
+    const size_t nb = (static_cast<size_t>(n_seq) + 1) * sizeof(int64_t);
+    if (int rc = upload_tables(ctx, ctx->hmm_off, {{h_off, nb}, {h_path_off, h_path_off ? nb : 0}})) return rc;
+    C->d_off = ctx->hmm_off.as<long long>();
+    return PS_OK;
+}
+
 template <typename BP, typename MD>
 int hmm_viterbi(ps_ctx *ctx, const MD &D, const double *d_obs, const int64_t *h_off, const long long *d_off, int32_t n_seq,
-                double *d_logp, double *d_mat, int32_t *d_path, const long long *d_path_off, int32_t *d_path_len, size_t lds)
+                double *d_logp, double *d_mat, int32_t *d_path, int32_t *d_path_len)
 {
-    const size_t S = static_cast<size_t>(D.S);
+    const size_t S = static_cast<size_t>(D.S), lds = 2 * S * sizeof(double);
+    const long long *d_path_off = d_off + n_seq + 1;
     const long long budget = std::max<long long>(1, ctx->hmm_bp_budget);
     HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_fwd_kernel<HMM_VITERBI, BP, MD>), static_cast<int>(lds)));
     HIP_TRY(ctx, ctx->hmm_last.reserve(static_cast<size_t>(n_seq) * sizeof(int)));
     HIP_TRY(ctx, ctx->hmm_flags.reserve(sizeof(int)));
     HIP_TRY(ctx, hipMemsetAsync(ctx->hmm_flags.p, 0, sizeof(int), ctx->stream));
-    for (int32_t q0 = 0; q0 < n_seq;) {
-        // as many sequences as keep the backpointers within the budget (at least one)
-        long long bytes = (h_off[q0 + 1] - h_off[q0] + 1) * static_cast<long long>(S * sizeof(BP));
-        int32_t q1 = q0 + 1;
-        while (q1 < n_seq) {
-            const long long more = (h_off[q1 + 1] - h_off[q1] + 1) * static_cast<long long>(S * sizeof(BP));
-            if (bytes + more > budget) break;
-            bytes += more; ++q1;
-        }
+    for (int32_t q0 = 0, q1; q0 < n_seq; q0 = q1) {
+        long long bytes;
+        q1 = next_chunk(h_off, q0, n_seq, S * sizeof(BP), budget, &bytes);
         if (bytes > (8ll << 30)) return fail(ctx, PS_ERR_ARG, "sequence %d needs %lld bytes of backpointers (8 GiB at most)", q0, bytes);
         HIP_TRY(ctx, ctx->hmm_bp.reserve(static_cast<size_t>(bytes)));
         const long long bp_row0 = h_off[q0] + q0;
@@ -2935,7 +3006,6 @@ int hmm_viterbi(ps_ctx *ctx, const MD &D, const double *d_obs, const int64_t *h_
                            static_cast<const BP *>(bp), bp_row0, static_cast<const int *>(ctx->hmm_last.as<int>()),
                            static_cast<const double *>(d_logp), d_path_off, d_path, d_path_len, ctx->hmm_flags.as<int>());
         HIP_TRY(ctx, hipGetLastError());
-        q0 = q1;
     }
     int flags = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&flags, ctx->hmm_flags.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
@@ -2944,76 +3014,6 @@ int hmm_viterbi(ps_ctx *ctx, const MD &D, const double *d_obs, const int64_t *h_
     if (flags & 1) return fail(ctx, PS_ERR_CAPACITY, "a Viterbi path is longer than its slot (d_path_len holds the lengths)");
     return PS_OK;
 }
-
-}  // namespace
-
-extern "C" {
-
-int ps_hmm_batch(ps_ctx *ctx, const ps_hmm_model *model, int32_t mode, const double *d_obs, const int64_t *h_off,
-                 int32_t n_seq, double *d_logp, double *d_mat, int32_t *d_path, const int64_t *h_path_off,
-                 int32_t *d_path_len)
-{
-    if (!ctx) return PS_ERR_ARG;
-    if (!model || !h_off) return fail(ctx, PS_ERR_ARG, "null pointer");
-    if (mode != PS_HMM_VITERBI && mode != PS_HMM_FORWARD && mode != PS_HMM_BACKWARD) return fail(ctx, PS_ERR_ARG, "unknown mode %d", mode);
-    if (n_seq < 0) return fail(ctx, PS_ERR_ARG, "negative sequence count");
-    if (mode == PS_HMM_VITERBI && (!h_path_off || (n_seq > 0 && (!d_path_len || !d_path))))
-        return fail(ctx, PS_ERR_ARG, "Viterbi needs the path buffer, its offsets and the length array");
-    for (int32_t q = 0; q < n_seq; ++q) {
-        if (h_off[q] < 0 || h_off[q + 1] < h_off[q]) return fail(ctx, PS_ERR_ARG, "sequence offsets must be non-negative and ascending");
-        if (h_off[q + 1] - h_off[q] > INT32_MAX / 2) return fail(ctx, PS_ERR_ARG, "sequence %d too long", q);
-        if (mode == PS_HMM_VITERBI && (h_path_off[q] < 0 || h_path_off[q + 1] < h_path_off[q]))
-            return fail(ctx, PS_ERR_ARG, "path offsets must be non-negative and ascending");
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HmmDevK DK;
-    int max_in = 0;
-    bool kde = false;
-    if (int rc = hmm_upload(ctx, model, &DK, &max_in, &kde)) return rc;
-    const HmmDev &D = DK;
-    if (n_seq == 0) return PS_OK;
-    if (!d_logp || (h_off[n_seq] > 0 && !d_obs)) return fail(ctx, PS_ERR_ARG, "null device pointer");
-    // offsets (and the path slots) in one upload
-    const size_t nb = (static_cast<size_t>(n_seq) + 1) * sizeof(int64_t);
-    const size_t up = mode == PS_HMM_VITERBI ? 2 * nb : nb;
-    HIP_TRY(ctx, ctx->h_up.reserve(up));
-    HIP_TRY(ctx, ctx->hmm_off.reserve(up));
-    std::memcpy(ctx->h_up.p, h_off, nb);
-    if (mode == PS_HMM_VITERBI) std::memcpy(static_cast<char *>(ctx->h_up.p) + nb, h_path_off, nb);
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->hmm_off.p, ctx->h_up.p, up, hipMemcpyHostToDevice, ctx->stream));
-    const long long *d_off = ctx->hmm_off.as<long long>();
-    const size_t lds = 2 * static_cast<size_t>(D.S) * sizeof(double);
-    if (mode == PS_HMM_VITERBI) {
-        const long long *d_path_off = d_off + n_seq + 1;
-        if (kde)
-            return max_in > 255 ? hmm_viterbi<uint16_t>(ctx, DK, d_obs, h_off, d_off, n_seq, d_logp, d_mat, d_path, d_path_off, d_path_len, lds)
-                                : hmm_viterbi<uint8_t>(ctx, DK, d_obs, h_off, d_off, n_seq, d_logp, d_mat, d_path, d_path_off, d_path_len, lds);
-        return max_in > 255 ? hmm_viterbi<uint16_t>(ctx, D, d_obs, h_off, d_off, n_seq, d_logp, d_mat, d_path, d_path_off, d_path_len, lds)
-                            : hmm_viterbi<uint8_t>(ctx, D, d_obs, h_off, d_off, n_seq, d_logp, d_mat, d_path, d_path_off, d_path_len, lds);
-    }
-    // (a model with kernel-density states takes the HmmDevK instantiations, any other the HmmDev ones)
-    auto fwd = [&](const auto &M) -> int {
-        using MD = std::decay_t<decltype(M)>;
-        HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_fwd_kernel<HMM_FORWARD, uint8_t, MD>), static_cast<int>(lds)));
-        hipLaunchKernelGGL((hmm_fwd_kernel<HMM_FORWARD, uint8_t, MD>), dim3(n_seq), dim3(HMM_NT), lds, ctx->stream, M, d_obs, d_off, 0,
-                           d_logp, d_mat, 0ll, static_cast<uint8_t *>(nullptr), 0ll, static_cast<int *>(nullptr));
-        return PS_OK;
-    };
-    auto bwd = [&](const auto &M) -> int {
-        using MD = std::decay_t<decltype(M)>;
-        HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_bwd_kernel<MD>), static_cast<int>(lds)));
-        hipLaunchKernelGGL(hmm_bwd_kernel<MD>, dim3(n_seq), dim3(HMM_NT), lds, ctx->stream, M, d_obs, d_off, 0, d_logp, d_mat);
-        return PS_OK;
-    };
-    if (int rc = mode == PS_HMM_FORWARD ? (kde ? fwd(DK) : fwd(D)) : (kde ? bwd(DK) : bwd(D))) return rc;
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return PS_OK;
-}
-
-}  // extern "C"
-
-namespace {
 
 // ps_hmm_expect: LDS bytes at most for the accumulator row beside the two score rows (else the row stays in global memory),
 // and the bytes of all workgroups' rows at most (the grid shrinks to fit)
@@ -3024,12 +3024,8 @@ template <bool ACC_LDS, typename MD>
 int hmm_expect_run(ps_ctx *ctx, const MD &D, const double *d_obs, const int64_t *h_off, const long long *d_off,
                    int32_t n_seq, int n_acc, int E, double *d_logp, double *d_counts, double *d_stats, int32_t *h_skipped)
 {
-    const size_t S = static_cast<size_t>(D.S);
-    const size_t lds = (2 * S + (ACC_LDS ? static_cast<size_t>(n_acc) : 0)) * sizeof(double);
-    const size_t lds_fwd = 2 * S * sizeof(double);
-    const void *fk = reinterpret_cast<const void *>(hmm_expect_kernel<ACC_LDS, MD>);
-    HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_fwd_kernel<HMM_FORWARD, uint8_t, MD>), static_cast<int>(lds_fwd)));
-    HIP_TRY(ctx, set_dyn_lds(ctx, fk, static_cast<int>(lds)));
+    const size_t lds = (2 * static_cast<size_t>(D.S) + (ACC_LDS ? static_cast<size_t>(n_acc) : 0)) * sizeof(double);
+    HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_expect_kernel<ACC_LDS, MD>), static_cast<int>(lds)));
     // a grid of resident workgroups (it depends on the device and the model only, never on timing), within the row budget
     const size_t row_bytes = static_cast<size_t>(n_acc) * sizeof(double);
     unsigned G = std::min<unsigned>(static_cast<unsigned>(n_seq), resident_slots(ctx, (hmm_expect_kernel<ACC_LDS, MD>), HMM_NT, lds));
@@ -3038,26 +3034,17 @@ int hmm_expect_run(ps_ctx *ctx, const MD &D, const double *d_obs, const int64_t 
     HIP_TRY(ctx, ctx->hmm_skip.reserve(sizeof(double)));
     HIP_TRY(ctx, hipMemsetAsync(ctx->hmm_acc.p, 0, G * row_bytes, ctx->stream));
     const long long budget = std::max<long long>(1, ctx->hmm_fb_budget);
-    for (int32_t q0 = 0; q0 < n_seq;) {
-        // as many sequences as keep their forward matrices within the budget (at least one)
-        long long bytes = (h_off[q0 + 1] - h_off[q0] + 1) * static_cast<long long>(S * sizeof(double));
-        int32_t q1 = q0 + 1;
-        while (q1 < n_seq) {
-            const long long more = (h_off[q1 + 1] - h_off[q1] + 1) * static_cast<long long>(S * sizeof(double));
-            if (bytes + more > budget) break;
-            bytes += more; ++q1;
-        }
+    for (int32_t q0 = 0, q1; q0 < n_seq; q0 = q1) {
+        long long bytes;
+        q1 = next_chunk(h_off, q0, n_seq, static_cast<size_t>(D.S) * sizeof(double), budget, &bytes);
         if (bytes > (16ll << 30)) return fail(ctx, PS_ERR_ARG, "sequence %d needs %lld bytes of forward matrix (16 GiB at most)", q0, bytes);
         HIP_TRY(ctx, ctx->hmm_fmat.reserve(static_cast<size_t>(bytes)));
         const long long row0 = h_off[q0] + q0;
-        double *fmat = ctx->hmm_fmat.as<double>();
-        hipLaunchKernelGGL((hmm_fwd_kernel<HMM_FORWARD, uint8_t, MD>), dim3(q1 - q0), dim3(HMM_NT), lds_fwd, ctx->stream, D, d_obs, d_off,
-                           q0, d_logp, fmat, row0, static_cast<uint8_t *>(nullptr), 0ll, static_cast<int *>(nullptr));
-        HIP_TRY(ctx, hipGetLastError());
+        if (int rc = launch_forward(ctx, D, d_obs, d_off, q0, q1, d_logp, ctx->hmm_fmat.as<double>(), row0)) return rc;
         hipLaunchKernelGGL((hmm_expect_kernel<ACC_LDS, MD>), dim3(G), dim3(HMM_NT), lds, ctx->stream, D, d_obs, d_off, q0, q1,
-                           static_cast<const double *>(d_logp), static_cast<const double *>(fmat), row0, ctx->hmm_acc.as<double>(), n_acc);
+                           static_cast<const double *>(d_logp), static_cast<const double *>(ctx->hmm_fmat.as<double>()), row0,
+                           ctx->hmm_acc.as<double>(), n_acc);
         HIP_TRY(ctx, hipGetLastError());
-        q0 = q1;
     }
     hipLaunchKernelGGL(hmm_expect_reduce_kernel, dim3((n_acc + 255) / 256), dim3(256), 0, ctx->stream,
                        static_cast<const double *>(ctx->hmm_acc.as<double>()), static_cast<int>(G), n_acc, E, d_counts, d_stats,
@@ -3070,58 +3057,6 @@ int hmm_expect_run(ps_ctx *ctx, const MD &D, const double *d_obs, const int64_t 
     return PS_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int ps_hmm_expect(ps_ctx *ctx, const ps_hmm_model *model, const double *d_obs, const int64_t *h_off, int32_t n_seq,
-                  double *d_logp, double *d_counts, double *d_stats, int32_t *h_skipped)
-{
-    if (!ctx) return PS_ERR_ARG;
-    if (!model || !h_off || !h_skipped) return fail(ctx, PS_ERR_ARG, "null pointer");
-    if (n_seq < 0) return fail(ctx, PS_ERR_ARG, "negative sequence count");
-    for (int32_t q = 0; q < n_seq; ++q) {
-        if (h_off[q] < 0 || h_off[q + 1] < h_off[q]) return fail(ctx, PS_ERR_ARG, "sequence offsets must be non-negative and ascending");
-        if (h_off[q + 1] - h_off[q] > INT32_MAX / 2) return fail(ctx, PS_ERR_ARG, "sequence %d too long", q);
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HmmDevK DK;
-    int max_in = 0;
-    bool kde = false;
-    if (int rc = hmm_upload(ctx, model, &DK, &max_in, &kde)) return rc;
-    const HmmDev &D = DK;
-    const int E = model->out_ptr[D.S], NE = D.n_emit;
-    const long long n_acc_ll = static_cast<long long>(E) + 3ll * NE + 1;
-    if (n_acc_ll > (1ll << 26)) return fail(ctx, PS_ERR_ARG, "model of %d edges: the E-step takes at most 2^26 accumulators", E);
-    const int n_acc = static_cast<int>(n_acc_ll);
-    if ((E > 0 && !d_counts) || (NE > 0 && !d_stats)) return fail(ctx, PS_ERR_ARG, "null device pointer");
-    *h_skipped = 0;
-    if (n_seq == 0) {
-        if (E > 0) HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, static_cast<size_t>(E) * sizeof(double), ctx->stream));
-        if (NE > 0) HIP_TRY(ctx, hipMemsetAsync(d_stats, 0, 3 * static_cast<size_t>(NE) * sizeof(double), ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        return PS_OK;
-    }
-    if (!d_logp || (h_off[n_seq] > 0 && !d_obs)) return fail(ctx, PS_ERR_ARG, "null device pointer");
-    const size_t nb = (static_cast<size_t>(n_seq) + 1) * sizeof(int64_t);
-    HIP_TRY(ctx, ctx->h_up.reserve(nb));
-    HIP_TRY(ctx, ctx->hmm_off.reserve(nb));
-    std::memcpy(ctx->h_up.p, h_off, nb);
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->hmm_off.p, ctx->h_up.p, nb, hipMemcpyHostToDevice, ctx->stream));
-    const long long *d_off = ctx->hmm_off.as<long long>();
-    const bool in_lds = (2 * static_cast<size_t>(D.S) + static_cast<size_t>(n_acc)) * sizeof(double) <= HMM_EXPECT_LDS
-                        && ctx->hmm_expect_lds;
-    if (kde)
-        return in_lds ? hmm_expect_run<true>(ctx, DK, d_obs, h_off, d_off, n_seq, n_acc, E, d_logp, d_counts, d_stats, h_skipped)
-                      : hmm_expect_run<false>(ctx, DK, d_obs, h_off, d_off, n_seq, n_acc, E, d_logp, d_counts, d_stats, h_skipped);
-    return in_lds ? hmm_expect_run<true>(ctx, D, d_obs, h_off, d_off, n_seq, n_acc, E, d_logp, d_counts, d_stats, h_skipped)
-                  : hmm_expect_run<false>(ctx, D, d_obs, h_off, d_off, n_seq, n_acc, E, d_logp, d_counts, d_stats, h_skipped);
-}
-
-}  // extern "C"
-
-namespace {
-
 // ps_hmm_posterior: forward matrices per launch as in hmm_expect_run, one workgroup per sequence.  CNT: 0 no counts, 1 the
 // sequence's counts row updated in global memory, 2 in LDS behind the two score rows.
 template <int CNT, typename MD>
@@ -3129,35 +3064,22 @@ int hmm_posterior_run(ps_ctx *ctx, const MD &D, const double *d_obs, const int64
                       int32_t n_seq, int E, double *d_logp, double *d_post, int32_t *d_map_state, double *d_map_logp,
                       double *d_counts_seq)
 {
-    const size_t S = static_cast<size_t>(D.S);
-    const size_t lds = (2 * S + (CNT == 2 ? static_cast<size_t>(E) : 0)) * sizeof(double);
-    const size_t lds_fwd = 2 * S * sizeof(double);
-    HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_fwd_kernel<HMM_FORWARD, uint8_t, MD>), static_cast<int>(lds_fwd)));
+    const size_t lds = (2 * static_cast<size_t>(D.S) + (CNT == 2 ? static_cast<size_t>(E) : 0)) * sizeof(double);
     HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_posterior_kernel<CNT, MD>), static_cast<int>(lds)));
     if (d_map_logp) HIP_TRY(ctx, ctx->hmm_pmax.reserve(std::max<size_t>(1, static_cast<size_t>(h_off[n_seq])) * sizeof(double)));
     const long long budget = std::max<long long>(1, ctx->hmm_fb_budget);
-    for (int32_t q0 = 0; q0 < n_seq;) {
-        // as many sequences as keep their forward matrices within the budget (at least one)
-        long long bytes = (h_off[q0 + 1] - h_off[q0] + 1) * static_cast<long long>(S * sizeof(double));
-        int32_t q1 = q0 + 1;
-        while (q1 < n_seq) {
-            const long long more = (h_off[q1 + 1] - h_off[q1] + 1) * static_cast<long long>(S * sizeof(double));
-            if (bytes + more > budget) break;
-            bytes += more; ++q1;
-        }
+    for (int32_t q0 = 0, q1; q0 < n_seq; q0 = q1) {
+        long long bytes;
+        q1 = next_chunk(h_off, q0, n_seq, static_cast<size_t>(D.S) * sizeof(double), budget, &bytes);
         if (bytes > (16ll << 30)) return fail(ctx, PS_ERR_ARG, "sequence %d needs %lld bytes of forward matrix (16 GiB at most)", q0, bytes);
         HIP_TRY(ctx, ctx->hmm_fmat.reserve(static_cast<size_t>(bytes)));
         const long long row0 = h_off[q0] + q0;
-        double *fmat = ctx->hmm_fmat.as<double>();
         if (ctx->debug) fprintf(stderr, "[poreseg] posterior launch: sequences %d..%d, %lld bytes of forward matrix, dynamic LDS %zu\n", q0, q1, bytes, lds);
-        hipLaunchKernelGGL((hmm_fwd_kernel<HMM_FORWARD, uint8_t, MD>), dim3(q1 - q0), dim3(HMM_NT), lds_fwd, ctx->stream, D, d_obs, d_off,
-                           q0, d_logp, fmat, row0, static_cast<uint8_t *>(nullptr), 0ll, static_cast<int *>(nullptr));
-        HIP_TRY(ctx, hipGetLastError());
+        if (int rc = launch_forward(ctx, D, d_obs, d_off, q0, q1, d_logp, ctx->hmm_fmat.as<double>(), row0)) return rc;
         hipLaunchKernelGGL((hmm_posterior_kernel<CNT, MD>), dim3(q1 - q0), dim3(HMM_NT), lds, ctx->stream, D, d_obs, d_off, q0,
-                           static_cast<const double *>(d_logp), static_cast<const double *>(fmat), row0, d_post, d_map_state,
-                           d_map_logp, ctx->hmm_pmax.as<double>(), d_counts_seq);
+                           static_cast<const double *>(d_logp), static_cast<const double *>(ctx->hmm_fmat.as<double>()), row0, d_post,
+                           d_map_state, d_map_logp, ctx->hmm_pmax.as<double>(), CNT ? d_counts_seq : nullptr);
         HIP_TRY(ctx, hipGetLastError());
-        q0 = q1;
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return PS_OK;
@@ -3167,43 +3089,92 @@ int hmm_posterior_run(ps_ctx *ctx, const MD &D, const double *d_obs, const int64
 
 extern "C" {
 
+int ps_hmm_batch(ps_ctx *ctx, const ps_hmm_model *model, int32_t mode, const double *d_obs, const int64_t *h_off,
+                 int32_t n_seq, double *d_logp, double *d_mat, int32_t *d_path, const int64_t *h_path_off,
+                 int32_t *d_path_len)
+{
+    // (the mode is judged between hmm_begin's first checks, so they stand here too, in their order)
+    if (!ctx) return PS_ERR_ARG;
+    if (!model || !h_off) return fail(ctx, PS_ERR_ARG, "null pointer");
+    if (mode != PS_HMM_VITERBI && mode != PS_HMM_FORWARD && mode != PS_HMM_BACKWARD) return fail(ctx, PS_ERR_ARG, "unknown mode %d", mode);
+    if (n_seq < 0) return fail(ctx, PS_ERR_ARG, "negative sequence count");
+    const bool vit = mode == PS_HMM_VITERBI;
+    if (vit && (!h_path_off || (n_seq > 0 && (!d_path_len || !d_path))))
+        return fail(ctx, PS_ERR_ARG, "Viterbi needs the path buffer, its offsets and the length array");
+    HmmCall C;
+    if (int rc = hmm_begin(ctx, model, true, d_obs, h_off, vit ? h_path_off : nullptr, n_seq, d_logp, &C,
+                           [](const HmmCall &) { return PS_OK; })) return rc;
+    if (!C.d_off) return PS_OK;
+    if (vit)
+        return with_model(C.kde, C.DK, [&](const auto &M) {
+            return C.max_in > 255 ? hmm_viterbi<uint16_t>(ctx, M, d_obs, h_off, C.d_off, n_seq, d_logp, d_mat, d_path, d_path_len)
+                                  : hmm_viterbi<uint8_t>(ctx, M, d_obs, h_off, C.d_off, n_seq, d_logp, d_mat, d_path, d_path_len);
+        });
+    const int rc = with_model(C.kde, C.DK, [&](const auto &M) -> int {
+        using MD = std::decay_t<decltype(M)>;
+        if (mode == PS_HMM_FORWARD) return launch_forward(ctx, M, d_obs, C.d_off, 0, n_seq, d_logp, d_mat, 0ll);
+        const size_t lds = 2 * static_cast<size_t>(M.S) * sizeof(double);
+        HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_bwd_kernel<MD>), static_cast<int>(lds)));
+        hipLaunchKernelGGL(hmm_bwd_kernel<MD>, dim3(n_seq), dim3(HMM_NT), lds, ctx->stream, M, d_obs, C.d_off, 0, d_logp, d_mat);
+        HIP_TRY(ctx, hipGetLastError());
+        return PS_OK;
+    });
+    if (rc) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return PS_OK;
+}
+
+int ps_hmm_expect(ps_ctx *ctx, const ps_hmm_model *model, const double *d_obs, const int64_t *h_off, int32_t n_seq,
+                  double *d_logp, double *d_counts, double *d_stats, int32_t *h_skipped)
+{
+    HmmCall C;
+    int n_acc = 0;
+    auto own = [&](const HmmCall &c) -> int {
+        const int E = c.E, NE = c.DK.n_emit;
+        const long long n_acc_ll = static_cast<long long>(E) + 3ll * NE + 1;
+        if (n_acc_ll > (1ll << 26)) return fail(ctx, PS_ERR_ARG, "model of %d edges: the E-step takes at most 2^26 accumulators", E);
+        n_acc = static_cast<int>(n_acc_ll);
+        if ((E > 0 && !d_counts) || (NE > 0 && !d_stats)) return fail(ctx, PS_ERR_ARG, "null device pointer");
+        *h_skipped = 0;
+        if (n_seq == 0) {
+            if (E > 0) HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, static_cast<size_t>(E) * sizeof(double), ctx->stream));
+            if (NE > 0) HIP_TRY(ctx, hipMemsetAsync(d_stats, 0, 3 * static_cast<size_t>(NE) * sizeof(double), ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        return PS_OK;
+    };
+    if (int rc = hmm_begin(ctx, model, h_skipped != nullptr, d_obs, h_off, nullptr, n_seq, d_logp, &C, own)) return rc;
+    if (!C.d_off) return PS_OK;
+    const int E = C.E;
+    const bool in_lds = (2 * static_cast<size_t>(C.DK.S) + static_cast<size_t>(n_acc)) * sizeof(double) <= HMM_EXPECT_LDS
+                        && ctx->hmm_expect_lds;
+    return with_model(C.kde, C.DK, [&](const auto &M) {
+        return in_lds ? hmm_expect_run<true>(ctx, M, d_obs, h_off, C.d_off, n_seq, n_acc, E, d_logp, d_counts, d_stats, h_skipped)
+                      : hmm_expect_run<false>(ctx, M, d_obs, h_off, C.d_off, n_seq, n_acc, E, d_logp, d_counts, d_stats, h_skipped);
+    });
+}
+
 int ps_hmm_posterior(ps_ctx *ctx, const ps_hmm_model *model, const double *d_obs, const int64_t *h_off, int32_t n_seq,
                      double *d_logp, double *d_post, int32_t *d_map_state, double *d_map_logp, double *d_counts_seq)
 {
-    if (!ctx) return PS_ERR_ARG;
-    if (!model || !h_off) return fail(ctx, PS_ERR_ARG, "null pointer");
-    if (n_seq < 0) return fail(ctx, PS_ERR_ARG, "negative sequence count");
-    for (int32_t q = 0; q < n_seq; ++q) {
-        if (h_off[q] < 0 || h_off[q + 1] < h_off[q]) return fail(ctx, PS_ERR_ARG, "sequence offsets must be non-negative and ascending");
-        if (h_off[q + 1] - h_off[q] > INT32_MAX / 2) return fail(ctx, PS_ERR_ARG, "sequence %d too long", q);
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HmmDevK DK;
-    int max_in = 0;
-    bool kde = false;
-    if (int rc = hmm_upload(ctx, model, &DK, &max_in, &kde)) return rc;
-    const HmmDev &D = DK;
-    const int E = model->out_ptr[D.S];
-    if (static_cast<long long>(E) + 3ll * D.n_emit + 1 > (1ll << 26)) return fail(ctx, PS_ERR_ARG, "model of %d edges: at most 2^26 accumulators", E);
-    if (n_seq == 0) return PS_OK;
-    if (!d_logp || (h_off[n_seq] > 0 && !d_obs)) return fail(ctx, PS_ERR_ARG, "null device pointer");
-    const size_t nb = (static_cast<size_t>(n_seq) + 1) * sizeof(int64_t);
-    HIP_TRY(ctx, ctx->h_up.reserve(nb));
-    HIP_TRY(ctx, ctx->hmm_off.reserve(nb));
-    std::memcpy(ctx->h_up.p, h_off, nb);
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->hmm_off.p, ctx->h_up.p, nb, hipMemcpyHostToDevice, ctx->stream));
-    const long long *d_off = ctx->hmm_off.as<long long>();
+    HmmCall C;
+    auto own = [&](const HmmCall &c) -> int {
+        if (static_cast<long long>(c.E) + 3ll * c.DK.n_emit + 1 > (1ll << 26)) return fail(ctx, PS_ERR_ARG, "model of %d edges: at most 2^26 accumulators", c.E);
+        return PS_OK;
+    };
+    if (int rc = hmm_begin(ctx, model, true, d_obs, h_off, nullptr, n_seq, d_logp, &C, own)) return rc;
+    if (!C.d_off) return PS_OK;
+    const int E = C.E;
     // the counts row of a sequence: none asked for (or no edges), in LDS when it fits beside the score rows, else in place
     const int cnt = !d_counts_seq || E == 0 ? 0
-                    : (2 * static_cast<size_t>(D.S) + static_cast<size_t>(E)) * sizeof(double) <= HMM_EXPECT_LDS && ctx->hmm_expect_lds ? 2 : 1;
-    auto run = [&](const auto &M) -> int {
+                    : (2 * static_cast<size_t>(C.DK.S) + static_cast<size_t>(E)) * sizeof(double) <= HMM_EXPECT_LDS && ctx->hmm_expect_lds ? 2 : 1;
+    return with_model(C.kde, C.DK, [&](const auto &M) {
         switch (cnt) {
-        case 0: return hmm_posterior_run<0>(ctx, M, d_obs, h_off, d_off, n_seq, E, d_logp, d_post, d_map_state, d_map_logp, nullptr);
-        case 1: return hmm_posterior_run<1>(ctx, M, d_obs, h_off, d_off, n_seq, E, d_logp, d_post, d_map_state, d_map_logp, d_counts_seq);
-        default: return hmm_posterior_run<2>(ctx, M, d_obs, h_off, d_off, n_seq, E, d_logp, d_post, d_map_state, d_map_logp, d_counts_seq);
+        case 0: return hmm_posterior_run<0>(ctx, M, d_obs, h_off, C.d_off, n_seq, E, d_logp, d_post, d_map_state, d_map_logp, d_counts_seq);
+        case 1: return hmm_posterior_run<1>(ctx, M, d_obs, h_off, C.d_off, n_seq, E, d_logp, d_post, d_map_state, d_map_logp, d_counts_seq);
+        default: return hmm_posterior_run<2>(ctx, M, d_obs, h_off, C.d_off, n_seq, E, d_logp, d_post, d_map_state, d_map_logp, d_counts_seq);
         }
-    };
-    return kde ? run(DK) : run(D);
+    });
 }
 
 }  // extern "C"

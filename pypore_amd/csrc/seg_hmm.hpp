@@ -7,7 +7,8 @@
 //   1. every emitting state combines its in-edges from row t-1 and adds its emission log density of observation t-1;
 //   2. the silent states, level by level, combine their in-edges from row t (emitting states of step t and silent states
 //      of lower levels).
-// The backward pass runs the mirror image over the out-edges (levels descending, then the emitting states).  Viterbi takes
+// The backward pass runs the mirror image over the out-edges (levels descending, then the emitting states); it is written
+// once (hmm_bwd_sweep, hmm_bwd_state) for the three kernels that run it: backward, E-step and posterior.  Viterbi takes
 // the maximum over the in-edges, scanned in ascending source index and updated only on a strictly greater score, so the
 // lowest source wins a tie; forward and backward take log-sum-exp, accumulated online as  max + log1p(sum of the other
 // terms' exp(v - max)),  which keeps values near log(1) accurate.
@@ -199,35 +200,46 @@ __global__ __launch_bounds__(HMM_NT) void hmm_fwd_kernel(MD M, const double *obs
     if (lane == 0) logp[q] = m > NEG ? m + log1p(r) : NEG;
 }
 
-// Backward over one sequence per workgroup: b[n][k] starts from log 1 at end (finite model) or at every state (infinite),
-// b[t][k] = logsumexp over out-edges k -> l of  lp + (l emitting ? e_l(x_t) + b[t+1][l] : b[t][l]).  logp[q] = b[0][start].
-template <typename MD = HmmDev>
-__global__ __launch_bounds__(HMM_NT) void hmm_bwd_kernel(MD M, const double *obs, const long long *off, int q0,
-                                                         double *logp, double *mat)
+// The backward recursion, written once for hmm_bwd_kernel, hmm_expect_kernel and hmm_posterior_kernel:  b[n][k] starts from
+// log 1 at end (finite model) or at every state (infinite),  b[t][k] = logsumexp over out-edges k -> l of  lp + (l emitting ?
+// e_l(x_t) + b[t+1][l] : b[t][l]).  The kernels differ only in their hooks (generic lambdas, inlined):
+//   fwd(k, t)            what the kernel folds in for state k at step t (f[t][k]; hmm_bwd_kernel: nothing), handed to
+//   term(e, v, fk)       every term v the sum of state k forms for out-edge e, in edge order, right after it is added;
+//   emitted(k, t, fk, b) an emitting state whose b[t][k] = b is finished (same lane, right after its last term);
+//   row(t, cur)          row t finished and fenced.
+
+// b[t][k] from rows nxt (row t+1 with the emission of observation t added: emitting successors) and cur (row t: silent ones)
+template <typename MD, typename Term>
+__device__ __forceinline__ double hmm_bwd_state(const MD &M, const double *nxt, double *cur, int k, int t, int n, double fk,
+                                                Term &&term)
 {
 #pragma clang fp contract(off)
-    extern __shared__ double hm_lds[];
-    const int S = M.S, NE = M.n_emit, lane = threadIdx.x;
-    const int q = q0 + blockIdx.x;
-    const long long base = off[q];
-    const int n = static_cast<int>(off[q + 1] - base);
-    const double *x = obs + base;
-    const long long row0 = base + q;
-    double *nxt = hm_lds, *cur = hm_lds + S;       // nxt: row t+1 with the emission of observation t added (emitting states)
+    const int NE = M.n_emit;
+    HmmLse acc;
+    if (t == n && (!M.finite || k == M.end)) acc.add(0.0);
+    const int e0 = M.out_ptr[k], e1 = M.out_ptr[k + 1];
+    for (int e = e0; e < e1; ++e) {
+        const int l = M.out_dst[e];
+        if (l < NE && t >= n) continue;
+        const double v = (l < NE ? nxt[l] : cur[l]) + M.out_lp[e];
+        acc.add(v);
+        term(e, v, fk);
+    }
+    const double b = acc.get();
+    cur[k] = b;
+    return b;
+}
+
+// Steps t = n .. 0 of one sequence x[0, n) with the two score rows in rows[0, 2 S): the silent levels from the top down, then
+// the emitting states.  Returns row 0.
+template <typename MD, typename Fwd, typename Term, typename Emitted, typename Row>
+__device__ __forceinline__ const double *hmm_bwd_sweep(const MD &M, const double *x, int n, double *rows, Fwd &&fwd, Term &&term,
+                                                       Emitted &&emitted, Row &&row)
+{
+#pragma clang fp contract(off)
+    const int NE = M.n_emit, lane = threadIdx.x;
+    double *nxt = rows, *cur = rows + M.S;
     constexpr double NEG = -__builtin_inf();
-
-    auto one = [&](int k, int t) {
-        HmmLse acc;
-        if (t == n && (!M.finite || k == M.end)) acc.add(0.0);
-        const int e0 = M.out_ptr[k], e1 = M.out_ptr[k + 1];
-        for (int e = e0; e < e1; ++e) {
-            const int l = M.out_dst[e];
-            if (l < NE) { if (t < n) acc.add(nxt[l] + M.out_lp[e]); }
-            else acc.add(cur[l] + M.out_lp[e]);
-        }
-        cur[k] = acc.get();
-    };
-
     for (int t = n; t >= 0; --t) {
         if (t < n) {
             double *tmp = nxt; nxt = cur; cur = tmp;
@@ -237,25 +249,49 @@ __global__ __launch_bounds__(HMM_NT) void hmm_bwd_kernel(MD M, const double *obs
         }
         for (int L = M.n_levels - 1; L >= 0; --L) {
             const int hi = M.level_ptr[L + 1];
-            for (int k = M.level_ptr[L] + lane; k < hi; k += HMM_NT) one(k, t);
+            for (int k = M.level_ptr[L] + lane; k < hi; k += HMM_NT) hmm_bwd_state(M, nxt, cur, k, t, n, fwd(k, t), term);
             hm_sync();
         }
-        for (int k = lane; k < NE; k += HMM_NT) one(k, t);
-        hm_sync();
-        if (mat) {
-            double *dst = mat + (row0 + t) * S;
-            for (int k = lane; k < S; k += HMM_NT) dst[k] = cur[k];
+        for (int k = lane; k < NE; k += HMM_NT) {
+            const double fk = fwd(k, t);
+            emitted(k, t, fk, hmm_bwd_state(M, nxt, cur, k, t, n, fk, term));
         }
+        hm_sync();
+        row(t, cur);
     }
-    if (lane == 0) logp[q] = cur[M.start];
+    return cur;
 }
 
-// E-step of Baum-Welch (ps_hmm_expect): the backward recursion of hmm_bwd_kernel with the expectations folded in.  The
-// forward matrix of the launch's sequences is in HBM (fmat, sequence q at row off[q] + q - f_row0, from hmm_fwd_kernel);
-// the backward rows stay in LDS and are never written out.  With w = f[t][k] - logp[q], every out-edge term the recursion
-// forms for state k at step t -- nxt[l] + lp (l emitting, b[t+1][l] + e_l(x_t) + lp) or cur[l] + lp (l silent) -- adds
-// exp(w + term) to the count of that edge, and an emitting state k adds its posterior exp(f[t][k] + b[t][k] - logp[q])
-// to (W, A, B) with the observation x[t-1] shifted by c_k = param[3k].
+// Backward over one sequence per workgroup.  Row t of sequence q goes to mat (optional) at row off[q] + q + t;
+// logp[q] = b[0][start].
+template <typename MD = HmmDev>
+__global__ __launch_bounds__(HMM_NT) void hmm_bwd_kernel(MD M, const double *obs, const long long *off, int q0,
+                                                         double *logp, double *mat)
+{
+#pragma clang fp contract(off)
+    extern __shared__ double hm_lds[];
+    const int S = M.S, lane = threadIdx.x;
+    const int q = q0 + blockIdx.x;
+    const long long base = off[q];
+    const int n = static_cast<int>(off[q + 1] - base);
+    const long long row0 = base + q;
+    const double *b0 = hmm_bwd_sweep(
+        M, obs + base, n, hm_lds, [](int, int) { return 0.0; }, [](int, double, double) {}, [](int, int, double, double) {},
+        [&](int t, const double *cur) {
+            if (mat) {
+                double *dst = mat + (row0 + t) * S;
+                for (int k = lane; k < S; k += HMM_NT) dst[k] = cur[k];
+            }
+        });
+    if (lane == 0) logp[q] = b0[M.start];
+}
+
+// E-step of Baum-Welch (ps_hmm_expect): the backward recursion with the expectations folded in.  The forward matrix of the
+// launch's sequences is in HBM (fmat, sequence q at row off[q] + q - f_row0, from hmm_fwd_kernel); the backward rows stay in
+// LDS and are never written out.  With w = f[t][k] - logp[q], every out-edge term the recursion forms for state k at step t
+// -- nxt[l] + lp (l emitting, b[t+1][l] + e_l(x_t) + lp) or cur[l] + lp (l silent) -- adds exp(w + term) to the count of
+// that edge, and an emitting state k adds its posterior exp(f[t][k] + b[t][k] - logp[q]) to (W, A, B) with the observation
+// x[t-1] shifted by c_k = param[3k].
 //
 // Accumulators: one row of n_acc = E + 3 NE + 1 doubles per workgroup (edge counts in out-edge order, (W, A, B) per
 // emitting state, the number of sequences skipped for logp = -inf).  Workgroup g takes the sequences q = g (mod gridDim.x)
@@ -270,7 +306,7 @@ __global__ __launch_bounds__(HMM_NT) void hmm_expect_kernel(MD M, const double *
 {
 #pragma clang fp contract(off)
     extern __shared__ double hm_lds[];
-    const int S = M.S, NE = M.n_emit, lane = threadIdx.x, G = gridDim.x;
+    const int S = M.S, lane = threadIdx.x, G = gridDim.x;
     const int E = M.out_ptr[S];
     double *acc_g = acc_rows + static_cast<long long>(blockIdx.x) * n_acc;
     double *acc = ACC_LDS ? hm_lds + 2 * S : acc_g;
@@ -291,53 +327,23 @@ __global__ __launch_bounds__(HMM_NT) void hmm_expect_kernel(MD M, const double *
         const int n = static_cast<int>(off[q + 1] - base);
         const double *x = obs + base;
         const double *f = fmat + (base + q - f_row0) * S;
-        double *nxt = hm_lds, *cur = hm_lds + S;
-
-        auto one = [&](int k, int t, double fk) {
-            const double w = fk - lq;
-            HmmLse lse;
-            if (t == n && (!M.finite || k == M.end)) lse.add(0.0);
-            const int e0 = M.out_ptr[k], e1 = M.out_ptr[k + 1];
-            for (int e = e0; e < e1; ++e) {
-                const int l = M.out_dst[e];
-                double v;
-                if (l < NE) {
-                    if (t >= n) continue;
-                    v = nxt[l] + M.out_lp[e];
-                } else v = cur[l] + M.out_lp[e];
-                lse.add(v);
+        hmm_bwd_sweep(
+            M, x, n, hm_lds, [&](int k, int t) { return f[static_cast<long long>(t) * S + k]; },
+            [&](int e, double v, double fk) {
+                const double w = fk - lq;
                 if (w > NEG && v > NEG) cnt[e] += exp(w + v);
-            }
-            cur[k] = lse.get();
-        };
-
-        for (int t = n; t >= 0; --t) {
-            const double *frow = f + static_cast<long long>(t) * S;
-            if (t < n) {
-                double *tmp = nxt; nxt = cur; cur = tmp;
-                const double xt = x[t];
-                for (int l = lane; l < NE; l += HMM_NT) nxt[l] = nxt[l] > NEG ? nxt[l] + hmm_emit(M, l, xt) : NEG;
-                hm_sync();
-            }
-            for (int L = M.n_levels - 1; L >= 0; --L) {
-                const int hi = M.level_ptr[L + 1];
-                for (int k = M.level_ptr[L] + lane; k < hi; k += HMM_NT) one(k, t, frow[k]);
-                hm_sync();
-            }
-            for (int k = lane; k < NE; k += HMM_NT) {
-                const double fk = frow[k];
-                one(k, t, fk);
-                if (t > 0 && fk > NEG && cur[k] > NEG) {
-                    const double g = exp(fk + cur[k] - lq);
+            },
+            [&](int k, int t, double fk, double bk) {
+                if (t > 0 && fk > NEG && bk > NEG) {
+                    const double g = exp(fk + bk - lq);
                     const double d = x[t - 1] - M.param[3 * k];
                     const double gd = g * d;
                     st[3 * k] += g;
                     st[3 * k + 1] += gd;
                     st[3 * k + 2] += gd * d;
                 }
-            }
-            hm_sync();
-        }
+            },
+            [](int, const double *) {});
     }
     if (ACC_LDS) {
         hm_sync();
@@ -372,7 +378,7 @@ __global__ __launch_bounds__(256) void hmm_expect_reduce_kernel(const double *ac
 //   map_logp   [q]: the sum of those maxima in ascending t.  The butterfly leaves the maximum in every lane; lane t % 64
 //              parks it in pmax[off[q] + t] (a scratch of one double per observation), and after the last step each lane
 //              reads back the entries it wrote, 64 at a time, and the wave adds them in order of t;
-//   counts_seq row q of E doubles: the sequence's expected count of every out-edge, formed as hmm_expect_kernel::one forms
+//   counts_seq row q of E doubles: the sequence's expected count of every out-edge, formed as hmm_expect_kernel forms
 //              cnt[e], zeroed here by the lane that owns the edge's source state (CNT 1: the row is updated in place in
 //              global memory, CNT 2: in LDS behind the score rows and stored at the end; CNT 0: no counts).
 // logp[q] = -inf: the rows of post are -inf, map_state -1, map_logp -inf, the counts row 0.  n = 0: no rows, map_logp 0.0,
@@ -409,67 +415,35 @@ __global__ __launch_bounds__(HMM_NT) void hmm_posterior_kernel(MD M, const doubl
         for (int k = lane; k < S; k += HMM_NT)
             for (int e = M.out_ptr[k], e1 = M.out_ptr[k + 1]; e < e1; ++e) cnt[e] = 0.0;
 
-    const double *x = obs + base;
     const double *f = fmat + (base + q - f_row0) * S;
-    double *nxt = hm_lds, *cur = hm_lds + S;
     const bool want_map = map_state || map_logp;
-
-    auto one = [&](int k, int t, double fk) -> double {
-        const double w = fk - lq;
-        HmmLse lse;
-        if (t == n && (!M.finite || k == M.end)) lse.add(0.0);
-        const int e0 = M.out_ptr[k], e1 = M.out_ptr[k + 1];
-        for (int e = e0; e < e1; ++e) {
-            const int l = M.out_dst[e];
-            double v;
-            if (l < NE) {
-                if (t >= n) continue;
-                v = nxt[l] + M.out_lp[e];
-            } else v = cur[l] + M.out_lp[e];
-            lse.add(v);
+    double m = NEG; int am = 0x7fffffff;      // the lane's largest log posterior of the step and its state
+    hmm_bwd_sweep(
+        M, obs + base, n, hm_lds, [&](int k, int t) { return f[static_cast<long long>(t) * S + k]; },
+        [&](int e, double v, double fk) {
+            const double w = fk - lq;
             if (CNT && w > NEG && v > NEG) cnt[e] += exp(w + v);
-        }
-        const double b = lse.get();
-        cur[k] = b;
-        return b;
-    };
-
-    for (int t = n; t >= 0; --t) {
-        const double *frow = f + static_cast<long long>(t) * S;
-        if (t < n) {
-            double *tmp = nxt; nxt = cur; cur = tmp;
-            const double xt = x[t];
-            for (int l = lane; l < NE; l += HMM_NT) nxt[l] = nxt[l] > NEG ? nxt[l] + hmm_emit(M, l, xt) : NEG;
-            hm_sync();
-        }
-        for (int L = M.n_levels - 1; L >= 0; --L) {
-            const int hi = M.level_ptr[L + 1];
-            for (int k = M.level_ptr[L] + lane; k < hi; k += HMM_NT) one(k, t, frow[k]);
-            hm_sync();
-        }
-        double *prow = post && t > 0 ? post + (base + t - 1) * NE : nullptr;
-        double m = NEG; int am = 0x7fffffff;
-        for (int k = lane; k < NE; k += HMM_NT) {
-            const double fk = frow[k];
-            const double bk = one(k, t, fk);
+        },
+        [&](int k, int t, double fk, double bk) {
             if (t > 0) {
                 const double v = (fk > NEG && bk > NEG) ? (fk + bk) - lq : NEG;
-                if (prow) prow[k] = v;
+                if (post) post[(base + t - 1) * NE + k] = v;
                 if (v > m) { m = v; am = k; }
             }
-        }
-        hm_sync();
-        if (t > 0 && want_map) {
-            for (int d = 32; d; d >>= 1) {
-                const double om = __shfl_xor(m, d); const int oa = __shfl_xor(am, d);
-                if (om > m || (om == m && oa < am)) { m = om; am = oa; }
+        },
+        [&](int t, const double *) {
+            if (t > 0 && want_map) {
+                for (int d = 32; d; d >>= 1) {
+                    const double om = __shfl_xor(m, d); const int oa = __shfl_xor(am, d);
+                    if (om > m || (om == m && oa < am)) { m = om; am = oa; }
+                }
+                if (lane == ((t - 1) & (HMM_NT - 1))) {
+                    if (map_state) map_state[base + t - 1] = m > NEG ? am : -1;
+                    if (map_logp) pmax[base + t - 1] = m;
+                }
             }
-            if (lane == ((t - 1) & (HMM_NT - 1))) {
-                if (map_state) map_state[base + t - 1] = m > NEG ? am : -1;
-                if (map_logp) pmax[base + t - 1] = m;
-            }
-        }
-    }
+            m = NEG; am = 0x7fffffff;
+        });
     if (CNT == 2) {
         hm_sync();
         for (int e = lane; e < E; e += HMM_NT) crow[e] = cnt[e];

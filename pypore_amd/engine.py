@@ -73,6 +73,24 @@ def apply_env_defaults(environ=None):
     return opts, tiling, pool
 
 
+def _ptr(t):
+    """The device address of a CUDA tensor as the C ABI takes it (None or an empty tensor: null)."""
+    return ctypes.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
+
+
+def _offsets(off):
+    """Sequence offsets for the C ABI: (contiguous int64 array, its const int64_t * -- valid while the array lives)."""
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    return off, off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+
+
+def _f64_device(*tensors):
+    """The device of contiguous float64 CUDA tensors (asserted)."""
+    for t in tensors:
+        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float64
+    return tensors[0].device
+
+
 def _serialised(method):
     """The method runs under its Context's lock."""
     import functools
@@ -439,23 +457,19 @@ class Context(object):
         unsigned j [total], status int32 [n_seq])."""
         mm, ms, md = (np.ascontiguousarray(a, dtype=np.float64) for a in (model_means, model_stds, model_durs))
         assert mm.size == ms.size == md.size
-        off = np.ascontiguousarray(seq_off, dtype=np.int64)
+        off, off_p = _offsets(seq_off)
         n_seq = off.size - 1
-        for t in (seq_means, seq_stds, seq_durs):
-            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and t.numel() >= int(off[-1])
-        dev = seq_means.device
+        assert min(t.numel() for t in (seq_means, seq_stds, seq_durs)) >= int(off[-1])
+        dev = _f64_device(seq_means, seq_stds, seq_durs)
         scores = torch.zeros(max(n_seq, 1), dtype=torch.float64, device=dev)
         paths = torch.zeros(max(int(off[-1]), 1), dtype=torch.int32, device=dev)
         status = torch.zeros(max(n_seq, 1), dtype=torch.int32, device=dev)
         torch.cuda.current_stream(dev).synchronize()
         dp = ctypes.POINTER(ctypes.c_double)
         _lib.check(self.L.ps_align_batch(self.handle, mm.ctypes.data_as(dp), ms.ctypes.data_as(dp), md.ctypes.data_as(dp),
-                                         mm.size, float(skip_penalty), float(backslip_penalty),
-                                         ctypes.c_void_p(seq_means.data_ptr()), ctypes.c_void_p(seq_stds.data_ptr()),
-                                         ctypes.c_void_p(seq_durs.data_ptr()),
-                                         off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n_seq,
-                                         ctypes.c_void_p(scores.data_ptr()), ctypes.c_void_p(paths.data_ptr()),
-                                         ctypes.c_void_p(status.data_ptr())), self.handle)
+                                         mm.size, float(skip_penalty), float(backslip_penalty), _ptr(seq_means),
+                                         _ptr(seq_stds), _ptr(seq_durs), off_p, n_seq, _ptr(scores), _ptr(paths),
+                                         _ptr(status)), self.handle)
         return scores[:n_seq], paths[:int(off[-1])], status[:n_seq]
 
     @_serialised
@@ -463,21 +477,14 @@ class Context(object):
         """ps_pairwise_scores: every pair of the sequence sets A x B on the score-only route.  a, b: float64 CUDA tensors
         (NaN: the gap marker), set k of A = a[a_off[k]:a_off[k+1]].  Returns (scores float64 [n_a, n_b], positions int32
         [n_a, n_b, 2] of the local maximum or None)."""
-        a_off = np.ascontiguousarray(a_off, dtype=np.int64)
-        b_off = np.ascontiguousarray(b_off, dtype=np.int64)
+        (a_off, a_off_p), (b_off, b_off_p) = _offsets(a_off), _offsets(b_off)
         n_a, n_b = a_off.size - 1, b_off.size - 1
-        for t in (a, b):
-            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float64
-        dev = a.device
+        dev = _f64_device(a, b)
         scores = torch.zeros((n_a, n_b), dtype=torch.float64, device=dev)
         pos = torch.zeros((n_a, n_b, 2), dtype=torch.int32, device=dev) if want_pos else None
-        i64p = ctypes.POINTER(ctypes.c_int64)
         torch.cuda.current_stream(dev).synchronize()
-        _lib.check(self.L.ps_pairwise_scores(self.handle, ctypes.c_void_p(a.data_ptr()), a_off.ctypes.data_as(i64p), n_a,
-                                             ctypes.c_void_p(b.data_ptr()), b_off.ctypes.data_as(i64p), n_b, int(mode),
-                                             float(penalty), ctypes.c_void_p(scores.data_ptr() if scores.numel() else 0),
-                                             ctypes.c_void_p(pos.data_ptr() if pos is not None and pos.numel() else 0)),
-                   self.handle)
+        _lib.check(self.L.ps_pairwise_scores(self.handle, _ptr(a), a_off_p, n_a, _ptr(b), b_off_p, n_b, int(mode),
+                                             float(penalty), _ptr(scores), _ptr(pos)), self.handle)
         return scores, pos
 
     @_serialised
@@ -487,15 +494,12 @@ class Context(object):
         status [n], cols_i, cols_j (index columns in walk order, -1 a gap), col_off [n + 1], aln_score, aln_start, aln_len,
         aln_off [n + 1], aln_count [n]).  Slots that turn out too small (PS_ERR_CAPACITY) make the call run again with
         the sizes the first run reported."""
-        a_off = np.ascontiguousarray(a_off, dtype=np.int64)
-        b_off = np.ascontiguousarray(b_off, dtype=np.int64)
+        (a_off, a_off_p), (b_off, b_off_p) = _offsets(a_off), _offsets(b_off)
         pair_a = np.ascontiguousarray(pair_a, dtype=np.int32)
         pair_b = np.ascontiguousarray(pair_b, dtype=np.int32)
         n = pair_a.size
         assert pair_b.size == n
-        for t in (a, b):
-            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float64
-        dev = a.device
+        dev = _f64_device(a, b)
         if n and (pair_a.min() < 0 or pair_a.max() >= a_off.size - 1 or pair_b.min() < 0 or pair_b.max() >= b_off.size - 1):
             raise ValueError("a pair names a sequence that is not there")
         m_len = np.diff(a_off)[pair_a] if n else np.zeros(0, np.int64)
@@ -506,22 +510,19 @@ class Context(object):
             aln_slots = np.ones(n, np.int64) if mode != _lib.PS_PW_LOCAL_REPEATED else np.minimum(m_len, n_len) + 1
         scores = torch.zeros(max(n, 1), dtype=torch.float64, device=dev)
         status, col_need, aln_count = (torch.zeros(max(n, 1), dtype=torch.int32, device=dev) for _ in range(3))
-        i64p, i32p = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32)
+        i32p = ctypes.POINTER(ctypes.c_int32)
         torch.cuda.current_stream(dev).synchronize()
         for attempt in range(2):
-            col_off = np.concatenate(([0], np.cumsum(col_slots))).astype(np.int64)
-            aln_off = np.concatenate(([0], np.cumsum(aln_slots))).astype(np.int64)
+            col_off, col_off_p = _offsets(np.concatenate(([0], np.cumsum(col_slots))))
+            aln_off, aln_off_p = _offsets(np.concatenate(([0], np.cumsum(aln_slots))))
             cols = torch.zeros((2, max(int(col_off[-1]), 1)), dtype=torch.int32, device=dev)
             aln_score = torch.zeros(max(int(aln_off[-1]), 1), dtype=torch.float64, device=dev)
             aln_il = torch.zeros((2, max(int(aln_off[-1]), 1)), dtype=torch.int32, device=dev)
             rc = self.L.ps_pairwise_batch(
-                self.handle, ctypes.c_void_p(a.data_ptr()), a_off.ctypes.data_as(i64p), a_off.size - 1,
-                ctypes.c_void_p(b.data_ptr()), b_off.ctypes.data_as(i64p), b_off.size - 1, pair_a.ctypes.data_as(i32p),
-                pair_b.ctypes.data_as(i32p), n, int(mode), float(penalty), int(min_length), ctypes.c_void_p(scores.data_ptr()),
-                ctypes.c_void_p(status.data_ptr()), col_off.ctypes.data_as(i64p), ctypes.c_void_p(cols[0].data_ptr()),
-                ctypes.c_void_p(cols[1].data_ptr()), ctypes.c_void_p(col_need.data_ptr()), aln_off.ctypes.data_as(i64p),
-                ctypes.c_void_p(aln_score.data_ptr()), ctypes.c_void_p(aln_il[0].data_ptr()),
-                ctypes.c_void_p(aln_il[1].data_ptr()), ctypes.c_void_p(aln_count.data_ptr()))
+                self.handle, _ptr(a), a_off_p, a_off.size - 1, _ptr(b), b_off_p, b_off.size - 1, pair_a.ctypes.data_as(i32p),
+                pair_b.ctypes.data_as(i32p), n, int(mode), float(penalty), int(min_length), _ptr(scores), _ptr(status),
+                col_off_p, _ptr(cols[0]), _ptr(cols[1]), _ptr(col_need), aln_off_p, _ptr(aln_score), _ptr(aln_il[0]),
+                _ptr(aln_il[1]), _ptr(aln_count))
             if rc != _lib.PS_ERR_CAPACITY or attempt:
                 break
             col_slots = col_need[:n].cpu().numpy().astype(np.int64)       # the exact sizes
@@ -538,23 +539,17 @@ class Context(object):
         [off[-1] + n_seq, n_states] or None, and for Viterbi: (path int32 tensor, path offsets, path lengths int32 tensor)
         -- else None).  A Viterbi path longer than its slot (path_slots[q] entries, default 2 (n + 1) + the silent states + 1)
         makes the call run again with slots of the exact lengths (PS_ERR_CAPACITY)."""
-        assert obs.is_cuda and obs.is_contiguous() and obs.dtype == torch.float64
-        off = np.ascontiguousarray(off, dtype=np.int64)
+        off, off_p = _offsets(off)
         n_seq = off.size - 1
-        dev = obs.device
+        dev = _f64_device(obs)
         S = model.n_states
         logp = torch.empty(max(n_seq, 1), dtype=torch.float64, device=dev)
         mat = torch.empty((int(off[-1]) + n_seq, S), dtype=torch.float64, device=dev) if want_mat else None
-        i64p = ctypes.POINTER(ctypes.c_int64)
         torch.cuda.current_stream(dev).synchronize()
 
-        def call(path, path_off, path_len):
-            return self.L.ps_hmm_batch(self.handle, ctypes.byref(model), int(mode), ctypes.c_void_p(obs.data_ptr()),
-                                       off.ctypes.data_as(i64p), n_seq, ctypes.c_void_p(logp.data_ptr()),
-                                       ctypes.c_void_p(mat.data_ptr() if mat is not None else 0),
-                                       ctypes.c_void_p(path.data_ptr() if path is not None else 0),
-                                       path_off.ctypes.data_as(i64p) if path_off is not None else None,
-                                       ctypes.c_void_p(path_len.data_ptr() if path_len is not None else 0))
+        def call(path, path_off_p, path_len):
+            return self.L.ps_hmm_batch(self.handle, ctypes.byref(model), int(mode), _ptr(obs), off_p, n_seq, _ptr(logp),
+                                       _ptr(mat), _ptr(path), path_off_p, _ptr(path_len))
 
         if mode != _lib.PS_HMM_VITERBI:
             _lib.check(call(None, None, None), self.handle)
@@ -563,9 +558,9 @@ class Context(object):
             path_slots = 2 * (np.diff(off) + 1) + (S - model.n_emit) + 1
         path_len = torch.empty(max(n_seq, 1), dtype=torch.int32, device=dev)
         for attempt in range(2):
-            path_off = np.concatenate(([0], np.cumsum(path_slots))).astype(np.int64)
+            path_off, path_off_p = _offsets(np.concatenate(([0], np.cumsum(path_slots))))
             path = torch.empty(max(int(path_off[-1]), 1), dtype=torch.int32, device=dev)
-            rc = call(path, path_off, path_len)
+            rc = call(path, path_off_p, path_len)
             if rc != _lib.PS_ERR_CAPACITY or attempt:
                 break
             path_slots = path_len[:n_seq].cpu().numpy().astype(np.int64)      # the exact lengths
@@ -577,20 +572,17 @@ class Context(object):
         """ps_hmm_expect: the Baum-Welch E-step over a batch.  model: a _lib.HmmModel (its arrays kept alive by the caller);
         obs: float64 CUDA tensor, sequence q = obs[off[q]:off[q+1]].  Returns (logp float64 [n_seq], edge counts float64
         [n_edges] in out-edge order, (W, A, B) float64 [n_emit, 3], the number of sequences skipped for logp = -inf)."""
-        assert obs.is_cuda and obs.is_contiguous() and obs.dtype == torch.float64
-        off = np.ascontiguousarray(off, dtype=np.int64)
+        off, off_p = _offsets(off)
         n_seq = off.size - 1
-        dev = obs.device
+        dev = _f64_device(obs)
         n_edges = int(ctypes.cast(model.out_ptr, ctypes.POINTER(ctypes.c_int32))[model.n_states])
         logp = torch.empty(max(n_seq, 1), dtype=torch.float64, device=dev)
         counts = torch.empty(max(n_edges, 1), dtype=torch.float64, device=dev)
         stats = torch.empty((max(model.n_emit, 1), 3), dtype=torch.float64, device=dev)
         skipped = ctypes.c_int32(0)
         torch.cuda.current_stream(dev).synchronize()
-        _lib.check(self.L.ps_hmm_expect(self.handle, ctypes.byref(model), ctypes.c_void_p(obs.data_ptr()),
-                                        off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n_seq,
-                                        ctypes.c_void_p(logp.data_ptr()), ctypes.c_void_p(counts.data_ptr()),
-                                        ctypes.c_void_p(stats.data_ptr()), ctypes.byref(skipped)), self.handle)
+        _lib.check(self.L.ps_hmm_expect(self.handle, ctypes.byref(model), _ptr(obs), off_p, n_seq, _ptr(logp), _ptr(counts),
+                                        _ptr(stats), ctypes.byref(skipped)), self.handle)
         return logp[:n_seq], counts[:n_edges], stats[:model.n_emit], int(skipped.value)
 
     @_serialised
@@ -600,22 +592,18 @@ class Context(object):
         float64 [n_seq]; log posteriors float64 [off[-1], n_emit] when want_post; MAP states int32 [off[-1]] and MAP log
         probabilities float64 [n_seq] when want_map; per-sequence edge counts float64 [n_seq, n_edges] in out-edge order
         when want_counts), None for what was not asked for: only the outputs asked for are allocated."""
-        assert obs.is_cuda and obs.is_contiguous() and obs.dtype == torch.float64
-        off = np.ascontiguousarray(off, dtype=np.int64)
+        off, off_p = _offsets(off)
         n_seq, total = off.size - 1, int(off[-1])
-        dev = obs.device
+        dev = _f64_device(obs)
         n_edges = int(ctypes.cast(model.out_ptr, ctypes.POINTER(ctypes.c_int32))[model.n_states])
         logp = torch.empty(max(n_seq, 1), dtype=torch.float64, device=dev)
         post = torch.empty((total, model.n_emit), dtype=torch.float64, device=dev) if want_post else None
         map_state = torch.empty(total, dtype=torch.int32, device=dev) if want_map else None
         map_logp = torch.empty(max(n_seq, 1), dtype=torch.float64, device=dev) if want_map else None
         counts = torch.empty((n_seq, n_edges), dtype=torch.float64, device=dev) if want_counts else None
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)   # noqa: E731
         torch.cuda.current_stream(dev).synchronize()
-        _lib.check(self.L.ps_hmm_posterior(self.handle, ctypes.byref(model), ctypes.c_void_p(obs.data_ptr()),
-                                           off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), n_seq,
-                                           ctypes.c_void_p(logp.data_ptr()), ptr(post), ptr(map_state), ptr(map_logp),
-                                           ptr(counts)), self.handle)
+        _lib.check(self.L.ps_hmm_posterior(self.handle, ctypes.byref(model), _ptr(obs), off_p, n_seq, _ptr(logp), _ptr(post),
+                                           _ptr(map_state), _ptr(map_logp), _ptr(counts)), self.handle)
         return logp[:n_seq], post, map_state, map_logp[:n_seq] if want_map else None, counts
 
     @_serialised

@@ -217,6 +217,43 @@ def test_one_sequence_per_launch_gives_the_same_bits(batch_300, capfd):
     assert raw.same_bits(cut)
 
 
+def planned_launches(off, row_bytes, budget):
+    """The launches of a batch by the rule the library states: from q0, as many sequences as keep (n + 1) * row_bytes
+    within the budget, at least one.  Returns [(q0, q1, bytes)]."""
+    out, q0, n_seq = [], 0, len(off) - 1
+    while q0 < n_seq:
+        q1, total = q0 + 1, (int(off[q0 + 1] - off[q0]) + 1) * row_bytes
+        while q1 < n_seq and total + (int(off[q1 + 1] - off[q1]) + 1) * row_bytes <= budget:
+            total += (int(off[q1 + 1] - off[q1]) + 1) * row_bytes
+            q1 += 1
+        out.append((q0, q1, total))
+        q0 = q1
+    return out
+
+
+@pytest.mark.parametrize("case", ["exactly_three", "one_byte_less", "first_alone_over_budget"])
+def test_launches_at_the_edges_of_the_budget(batch_300, capfd, case):
+    """A budget that holds exactly the first three forward matrices puts three sequences in the first launch, one byte
+    less two, and a sequence larger than the budget goes alone; every launch is the stated rule's, and the bits are those
+    of the uncut call."""
+    import re
+    from pypore_amd import engine
+    model, seqs, raw = batch_300
+    seqs, row = seqs[:12], 8 * len(model.states)
+    off = np.concatenate(([0], np.cumsum([len(s) for s in seqs])))
+    sizes = [(len(s) + 1) * row for s in seqs]
+    budget, first = {"exactly_three": (sum(sizes[:3]), 3), "one_byte_less": (sum(sizes[:3]) - 1, 2),
+                     "first_alone_over_budget": (sizes[0] - 1, 1)}[case]
+    whole = Raw(model, seqs)
+    capfd.readouterr()
+    with LG.options(engine.context(), hmm_fb_budget=budget, debug=1):
+        cut = Raw(model, seqs)
+    got = [tuple(int(g) for g in m.groups()) for m in
+           re.finditer(r"posterior launch: sequences (\d+)\.\.(\d+), (\d+) bytes of forward matrix", capfd.readouterr().err)]
+    assert got == planned_launches(off, row, budget) and got[0] == (0, first, sum(sizes[:first]))
+    assert whole.same_bits(cut)
+
+
 def test_counts_row_in_global_memory_gives_the_same_bits(batch_300):
     """Option hmm_expect_lds 0 keeps the sequence's counts row in global memory (the route a model takes by itself when
     the row does not fit LDS beside the score rows): the same additions in the same order."""
