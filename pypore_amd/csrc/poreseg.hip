@@ -8,6 +8,10 @@
 //   phase 3  tree_kernel       one job per true spine step: rec(a_k, a_{k+1}) in order
 //   gather   item_scan + gather kernels -> contiguous, sorted boundary list per event
 //   K2       segstat_kernel (optional)
+// Which kernel runs with which grid is decided once each: by_dtype / by_nt (run-time sample type and workgroup width -> the
+// kernels' template arguments), reserve_digest + launch_k0 (phase 0, for every route that runs K0), scan_shape (launch shape of
+// the scan kernels), launch_scans_bs / launch_spine_nt (phases 1, 1b), launch_subtrees (phase 3), make_spine_job and
+// reserve_items (tile tables and item buffers), begin_segment_call (prologue of the segment entry points).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -24,6 +28,7 @@
 #include <string>
 #include <thread>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "poreseg.h"
@@ -338,6 +343,33 @@ inline size_t lds_bytes_for(int lds_cap, int nt)
 // LDS budget: 160 KB per CU minus the static Shared block and a little slack
 constexpr int LDS_BYTES_MAX = 160 * 1024 - static_cast<int>(sizeof(Shared)) - 512 - 64;
 
+// Compute units of the context's device (queried once)
+int cu_count(ps_ctx *ctx)
+{
+    if (ctx->n_cu <= 0) {
+        hipDeviceProp_t prop;
+        ctx->n_cu = hipGetDeviceProperties(&prop, ctx->device) == hipSuccess ? prop.multiProcessorCount : 256;
+    }
+    return ctx->n_cu;
+}
+
+// The sample type of a call, known at run time, as the compile-time DT of its kernels: f(std::integral_constant<int, DT>).
+// FLAGS are the bits the call site decides at compile time (DT_WIDE): a site that serves both digests names each of them in a
+// call of its own, so only the kernels that site launches are instantiated.
+template <int FLAGS = 0, typename F> auto by_dtype(int dtype, F &&f)
+{
+    if (dtype == PS_DTYPE_F32) return f(std::integral_constant<int, PS_DTYPE_F32 | FLAGS>());
+    return f(std::integral_constant<int, PS_DTYPE_I16 | FLAGS>());
+}
+
+// A workgroup width of the LDS-window kernels (options spine_nt / tree_nt) as the compile-time NT: the widths the call site
+// lists are the ones its kernel is built for, the last of them serves every other value.
+template <int NT0, int... NTS, typename F> int by_nt(int nt, F &&f)
+{
+    if constexpr (sizeof...(NTS) == 0) return f(std::integral_constant<int, NT0>());
+    else return nt == NT0 ? f(std::integral_constant<int, NT0>()) : by_nt<NTS...>(nt, f);
+}
+
 // Resident workgroups of a kernel on this device (occupancy x CUs): the scan kernels are launched with one
 // workgroup per slot and stride over their jobs.  The cache holds the device's workgroups per CU; slots_pct applies on
 // every lookup, so a change of the option takes effect at the next launch.
@@ -348,10 +380,7 @@ template <typename K> unsigned resident_slots(ps_ctx *ctx, K kernel, int nt, siz
     for (const auto &k : ctx->occ_cache)
         if (k.fn == fn && k.nt == nt && k.lds == lds) { per_cu = k.per_cu; break; }
     if (per_cu < 0) {
-        if (ctx->n_cu <= 0) {
-            hipDeviceProp_t prop;
-            ctx->n_cu = hipGetDeviceProperties(&prop, ctx->device) == hipSuccess ? prop.multiProcessorCount : 256;
-        }
+        cu_count(ctx);
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, nt, lds) != hipSuccess || per_cu <= 0)
             per_cu = 1;
         if (ctx->debug) fprintf(stderr, "[poreseg] occupancy: %d workgroups of %d threads per CU (dynamic LDS %zu), %d CUs\n", per_cu, nt, lds, ctx->n_cu);
@@ -379,12 +408,29 @@ hipError_t set_dyn_lds(ps_ctx *ctx, const void *fn, int lds)
     return e;
 }
 
+// Launch shape of a scan kernel: its dynamic LDS (with the attribute that allows it), the workgroups the device keeps resident
+// and the grid -- one workgroup per slot, striding over its jobs, and no more workgroups than `want`.
+struct ScanShape { size_t lds = 0; unsigned slots = 0, grid = 0; };
+template <typename K> int scan_shape(ps_ctx *ctx, K kernel, int nt, size_t lds, unsigned want, ScanShape *s)
+{
+    HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(kernel), static_cast<int>(lds)));
+    s->lds = lds;
+    s->slots = resident_slots(ctx, kernel, nt, lds);
+    s->grid = std::max(1u, std::min(want, s->slots));
+    return PS_OK;
+}
+// ... of spine_kernel, bridge_kernel and tree_kernel: NT threads; the LDS-window widths hold the window's image, a single wave
+// (block-sum scan) holds nothing (scan_lds_pad: diagnostics)
+template <int NT, typename K> int scan_shape(ps_ctx *ctx, K kernel, const DevCfg &cfg, unsigned want, ScanShape *s)
+{
+    return scan_shape(ctx, kernel, NT, NT == 64 ? static_cast<size_t>(ctx->scan_lds_pad) : lds_bytes_for(cfg.lds_cap, NT), want, s);
+}
+
 template <int NT, int DT> int launch_spine(ps_ctx *ctx, const DevCfg &cfg, unsigned nj, SmallLayout *sm, bool list_mode = false)
 {
-    const size_t lds = NT == 64 ? static_cast<size_t>(ctx->scan_lds_pad) : lds_bytes_for(cfg.lds_cap, NT);
-    HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(spine_kernel<NT, DT>), static_cast<int>(lds)));
-    const unsigned grid = std::min(nj, resident_slots(ctx, spine_kernel<NT, DT>, NT, lds));
-    hipLaunchKernelGGL((spine_kernel<NT, DT>), dim3(grid), dim3(NT), lds, ctx->stream, cfg,
+    ScanShape s;
+    if (int rc = scan_shape<NT>(ctx, spine_kernel<NT, DT>, cfg, nj, &s)) return rc;
+    hipLaunchKernelGGL((spine_kernel<NT, DT>), dim3(s.grid), dim3(NT), s.lds, ctx->stream, cfg,
                        ctx->spine_jobs.as<SpineJob>(), ctx->spine_scratch.as<int2>(),
                        list_mode ? nullptr : ctx->spine_dense.as<int2>(), ctx->spine_meta.as<int4>(), &sm->dense, reinterpret_cast<unsigned *>(&sm->status), &sm->work0,
                        static_cast<int>(nj));
@@ -395,10 +441,9 @@ template <int NT, int DT> int launch_spine(ps_ctx *ctx, const DevCfg &cfg, unsig
 template <int NT, int DT> int launch_tree(ps_ctx *ctx, const DevCfg &cfg, unsigned nj, SmallLayout *sm, size_t n_jobs,
                                           const AsmHeader *d_hdr, int par_max_jobs = 0)
 {
-    const size_t lds = NT == 64 ? static_cast<size_t>(ctx->scan_lds_pad) : lds_bytes_for(cfg.lds_cap, NT);
-    HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(tree_kernel<NT, DT>), static_cast<int>(lds)));
-    const unsigned grid = std::min(nj, resident_slots(ctx, tree_kernel<NT, DT>, NT, lds));
-    hipLaunchKernelGGL((tree_kernel<NT, DT>), dim3(grid), dim3(NT), lds, ctx->stream, cfg,
+    ScanShape s;
+    if (int rc = scan_shape<NT>(ctx, tree_kernel<NT, DT>, cfg, nj, &s)) return rc;
+    hipLaunchKernelGGL((tree_kernel<NT, DT>), dim3(s.grid), dim3(NT), s.lds, ctx->stream, cfg,
                        ctx->tree_jobs.as<TreeJob>(), ctx->tree_scratch.as<int32_t>(), ctx->tree_spill.as<int2>(),
                        ctx->tree_counts.as<int32_t>(), reinterpret_cast<unsigned *>(&sm->status), &sm->work0,
                        static_cast<long long>(n_jobs), d_hdr,
@@ -409,15 +454,21 @@ template <int NT, int DT> int launch_tree(ps_ctx *ctx, const DevCfg &cfg, unsign
     return PS_OK;
 }
 
+// LDS-window scan: the spine kernel at the option's width (spine_nt)
+int launch_spine_nt(ps_ctx *ctx, const DevCfg &cfg, unsigned nj, SmallLayout *sm, bool list_mode)
+{
+    return by_nt<256, 512, 1024>(ctx->spine_nt, [&](auto nt) {
+        return by_dtype(cfg.dtype, [&](auto dt) { return launch_spine<decltype(nt)::value, dt()>(ctx, cfg, nj, sm, list_mode); });
+    });
+}
+
 // block-sum scan, TREE_W waves per workgroup sharing the workgroup's job list (tree_mw_kernel)
 template <int DT> int launch_tree_mw(ps_ctx *ctx, const DevCfg &cfg, unsigned nj, SmallLayout *sm, size_t n_jobs,
                                      const AsmHeader *d_hdr)
 {
-    const unsigned want = (nj + TREE_W - 1) / TREE_W;
-    const size_t lds = sizeof(SharedT<64>) * TREE_W;
-    HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(tree_mw_kernel<DT>), static_cast<int>(lds)));
-    const unsigned grid = std::max(1u, std::min(want, resident_slots(ctx, tree_mw_kernel<DT>, 64 * TREE_W, lds)));
-    hipLaunchKernelGGL((tree_mw_kernel<DT>), dim3(grid), dim3(64 * TREE_W), lds, ctx->stream, cfg,
+    ScanShape s;
+    if (int rc = scan_shape(ctx, tree_mw_kernel<DT>, 64 * TREE_W, sizeof(SharedT<64>) * TREE_W, (nj + TREE_W - 1) / TREE_W, &s)) return rc;
+    hipLaunchKernelGGL((tree_mw_kernel<DT>), dim3(s.grid), dim3(64 * TREE_W), s.lds, ctx->stream, cfg,
                        ctx->tree_jobs.as<TreeJob>(), ctx->tree_scratch.as<int32_t>(), ctx->tree_spill.as<int2>(),
                        ctx->tree_counts.as<int32_t>(), reinterpret_cast<unsigned *>(&sm->status), &sm->work0,
                        static_cast<long long>(n_jobs), d_hdr, &sm->tree_tail, ctx->tree_tail_pct);
@@ -429,19 +480,36 @@ template <int DT> int launch_tree_mw(ps_ctx *ctx, const DevCfg &cfg, unsigned nj
 template <int DT> int launch_tree_par(ps_ctx *ctx, const DevCfg &cfg, unsigned nj, SmallLayout *sm, size_t n_jobs,
                                       const AsmHeader *d_hdr)
 {
-    const size_t lds = sizeof(SharedT<64>) * PAR_W + sizeof(ParQ);
-    HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(tree_par_kernel<DT>), static_cast<int>(lds)));
-    const unsigned slots = resident_slots(ctx, tree_par_kernel<DT>, 64 * PAR_W, lds);
-    const unsigned grid = std::max(1u, std::min(nj, slots));
+    ScanShape s;
+    if (int rc = scan_shape(ctx, tree_par_kernel<DT>, 64 * PAR_W, sizeof(SharedT<64>) * PAR_W + sizeof(ParQ), nj, &s)) return rc;
     // calls with at most one job per workgroup slot are this kernel's; the others go to tree_kernel (decided on the device,
     // where the job count is known: both are launched, one of them returns at once)
-    const int par_max = static_cast<int>(slots);
-    hipLaunchKernelGGL((tree_par_kernel<DT>), dim3(grid), dim3(64 * PAR_W), lds, ctx->stream, cfg,
+    const int par_max = static_cast<int>(s.slots);
+    hipLaunchKernelGGL((tree_par_kernel<DT>), dim3(s.grid), dim3(64 * PAR_W), s.lds, ctx->stream, cfg,
                        ctx->tree_jobs.as<TreeJob>(), ctx->tree_scratch.as<int32_t>(), ctx->tree_spill.as<int2>(),
                        ctx->tree_counts.as<int32_t>(), reinterpret_cast<unsigned *>(&sm->status), &sm->work0,
                        static_cast<long long>(n_jobs), d_hdr, par_max);
     HIP_TRY(ctx, hipGetLastError());
     return launch_tree<64, DT>(ctx, cfg, nj, sm, n_jobs, d_hdr, par_max);
+}
+
+// Phase 3: which kernel takes the call's subtree jobs.  On the 64-bit digest (filtered events: deep recursions) tree_par, then
+// tree_mw, then one wave per job; on the 32-bit digest tree_mw, then one wave per job; without a digest the LDS-window kernel
+// at the option's width (tree_nt).
+int launch_subtrees(ps_ctx *ctx, const DevCfg &cfg, unsigned nj, SmallLayout *sm, size_t n_jobs, const AsmHeader *d_hdr)
+{
+    if (cfg.bsum != nullptr && cfg.bs_wide) {
+        if (ctx->tree_par) return by_dtype<DT_WIDE>(cfg.dtype, [&](auto dt) { return launch_tree_par<dt()>(ctx, cfg, nj, sm, n_jobs, d_hdr); });
+        if (ctx->tree_mw) return by_dtype<DT_WIDE>(cfg.dtype, [&](auto dt) { return launch_tree_mw<dt()>(ctx, cfg, nj, sm, n_jobs, d_hdr); });
+        return by_dtype<DT_WIDE>(cfg.dtype, [&](auto dt) { return launch_tree<64, dt()>(ctx, cfg, nj, sm, n_jobs, d_hdr); });
+    }
+    if (cfg.bsum != nullptr) {
+        if (ctx->tree_mw) return by_dtype(cfg.dtype, [&](auto dt) { return launch_tree_mw<dt()>(ctx, cfg, nj, sm, n_jobs, d_hdr); });
+        return by_dtype(cfg.dtype, [&](auto dt) { return launch_tree<64, dt()>(ctx, cfg, nj, sm, n_jobs, d_hdr); });
+    }
+    return by_nt<512, 256>(ctx->tree_nt, [&](auto nt) {
+        return by_dtype(cfg.dtype, [&](auto dt) { return launch_tree<decltype(nt)::value, dt()>(ctx, cfg, nj, sm, n_jobs, d_hdr); });
+    });
 }
 
 struct Anchor { int32_t pos, kind; };
@@ -484,16 +552,7 @@ int run_spines(ps_ctx *ctx, const DevCfg &cfg, const std::vector<SpineJob> &jobs
     HIP_TRY(ctx, hipMemcpyAsync(ctx->spine_jobs.p, ctx->h_up.p, nj * sizeof(SpineJob), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(&sm->dense, 0, sizeof(unsigned long long), ctx->stream));
     if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
-    {
-        const unsigned g = static_cast<unsigned>(nj);
-        const bool f32 = cfg.dtype == PS_DTYPE_F32;
-        int lrc = ctx->spine_nt == 256
-                      ? (f32 ? launch_spine<256, PS_DTYPE_F32>(ctx, cfg, g, sm) : launch_spine<256, PS_DTYPE_I16>(ctx, cfg, g, sm))
-                  : ctx->spine_nt == 512
-                      ? (f32 ? launch_spine<512, PS_DTYPE_F32>(ctx, cfg, g, sm) : launch_spine<512, PS_DTYPE_I16>(ctx, cfg, g, sm))
-                      : (f32 ? launch_spine<1024, PS_DTYPE_F32>(ctx, cfg, g, sm) : launch_spine<1024, PS_DTYPE_I16>(ctx, cfg, g, sm));
-        if (lrc) return lrc;
-    }
+    if (int lrc = launch_spine_nt(ctx, cfg, static_cast<unsigned>(nj), sm, false)) return lrc;
     if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
     HIP_TRY(ctx, ctx->h_meta.reserve(nj * sizeof(int4)));
     HIP_TRY(ctx, ctx->h_small.reserve(sizeof(SmallLayout)));
@@ -529,6 +588,28 @@ int run_spines(ps_ctx *ctx, const DevCfg &cfg, const std::vector<SpineJob> &jobs
 // anchors of one chain are >= min_width apart and at most one lies at or beyond `stop`
 inline int64_t spine_cap(int64_t start, int64_t stop, int mw) { return (stop - start) / mw + 4; }
 
+// The spine job of tile [start, stop) of event `ev` (`len` samples at `base` of the sample array), its anchor list at out_off.
+// TilePlace: where the tile stands among the tiles of its event (device stitch); the halo tiles of the host stitch and its
+// seam repairs stand alone.
+struct TilePlace { int64_t first_tile = 0, ntiles = 1, tile_len = 0x7fffffff, vbase = 0; };
+SpineJob make_spine_job(int64_t base, int32_t ev, int64_t len, int64_t start, int64_t stop, int mw, int64_t out_off,
+                        const TilePlace &place = TilePlace())
+{
+    SpineJob j;
+    j.base = base;
+    j.start = static_cast<int32_t>(start);
+    j.end = static_cast<int32_t>(len);
+    j.stop = static_cast<int32_t>(stop);
+    j.out_cap = static_cast<int32_t>(std::min<int64_t>(spine_cap(start, stop, mw), 0x7fffffff));
+    j.out_off = out_off;
+    j.first_tile = static_cast<int32_t>(place.first_tile);
+    j.ntiles = static_cast<int32_t>(place.ntiles);
+    j.tile_len = static_cast<int32_t>(place.tile_len);
+    j.ev = ev;
+    j.vbase = place.vbase;
+    return j;
+}
+
 // position of `pos` in a tile list (exact match), -1 if the tile starts there, -2 if absent
 int find_in(const TileList &t, int32_t pos)
 {
@@ -558,21 +639,7 @@ int finish_batch(ps_ctx *ctx, const DevCfg &cfg, size_t n_tj, int64_t n_items, i
     if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
     if (n_tj) {
         const unsigned g = static_cast<unsigned>(std::min<size_t>(n_tj, 0x7fffffff));
-        const bool f32 = cfg.dtype == PS_DTYPE_F32;
-        int lrc = cfg.bsum != nullptr && cfg.bs_wide && ctx->tree_par
-                      ? (f32 ? launch_tree_par<PS_DTYPE_F32 | DT_WIDE>(ctx, cfg, g, sm, n_tj, d_hdr) : launch_tree_par<PS_DTYPE_I16 | DT_WIDE>(ctx, cfg, g, sm, n_tj, d_hdr))
-                  : cfg.bsum != nullptr && cfg.bs_wide && ctx->tree_mw
-                      ? (f32 ? launch_tree_mw<PS_DTYPE_F32 | DT_WIDE>(ctx, cfg, g, sm, n_tj, d_hdr) : launch_tree_mw<PS_DTYPE_I16 | DT_WIDE>(ctx, cfg, g, sm, n_tj, d_hdr))
-                  : cfg.bsum != nullptr && cfg.bs_wide
-                      ? (f32 ? launch_tree<64, PS_DTYPE_F32 | DT_WIDE>(ctx, cfg, g, sm, n_tj, d_hdr) : launch_tree<64, PS_DTYPE_I16 | DT_WIDE>(ctx, cfg, g, sm, n_tj, d_hdr))
-                  : cfg.bsum != nullptr && ctx->tree_mw
-                      ? (f32 ? launch_tree_mw<PS_DTYPE_F32>(ctx, cfg, g, sm, n_tj, d_hdr) : launch_tree_mw<PS_DTYPE_I16>(ctx, cfg, g, sm, n_tj, d_hdr))
-                  : cfg.bsum != nullptr
-                      ? (f32 ? launch_tree<64, PS_DTYPE_F32>(ctx, cfg, g, sm, n_tj, d_hdr) : launch_tree<64, PS_DTYPE_I16>(ctx, cfg, g, sm, n_tj, d_hdr))
-                  : ctx->tree_nt == 512
-                      ? (f32 ? launch_tree<512, PS_DTYPE_F32>(ctx, cfg, g, sm, n_tj, d_hdr) : launch_tree<512, PS_DTYPE_I16>(ctx, cfg, g, sm, n_tj, d_hdr))
-                      : (f32 ? launch_tree<256, PS_DTYPE_F32>(ctx, cfg, g, sm, n_tj, d_hdr) : launch_tree<256, PS_DTYPE_I16>(ctx, cfg, g, sm, n_tj, d_hdr));
-        if (lrc) return lrc;
+        if (int lrc = launch_subtrees(ctx, cfg, g, sm, n_tj, d_hdr)) return lrc;
     }
     if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
     const bool fused = d_hdr != nullptr && ctx->gather_fused;      // (device stitch: job index == item index)
@@ -603,14 +670,11 @@ int finish_batch(ps_ctx *ctx, const DevCfg &cfg, size_t n_tj, int64_t n_items, i
         // K2 from the K0 digest: launched before the sync, the segment count is read on the device
         const int64_t scap = cap + n_ev;
         const unsigned sg = static_cast<unsigned>(std::min<int64_t>(std::max<int64_t>(scap, 1), 8192));
-        if (cfg.dtype == PS_DTYPE_F32)
-            hipLaunchKernelGGL(segstat_bs_kernel<PS_DTYPE_F32>, dim3(sg), dim3(64), 0, ctx->stream, cfg, ctx->ev_off.as<int64_t>(),
+        by_dtype(cfg.dtype, [&](auto dt) {
+            hipLaunchKernelGGL(segstat_bs_kernel<dt()>, dim3(sg), dim3(64), 0, ctx->stream, cfg, ctx->ev_off.as<int64_t>(),
                                ctx->ev_len.as<int64_t>(), n_ev, d_bounds, ctx->bounds_off.as<int64_t>(), d_stats, scap,
                                reinterpret_cast<unsigned *>(&sm->status), d_hdr);
-        else
-            hipLaunchKernelGGL(segstat_bs_kernel<PS_DTYPE_I16>, dim3(sg), dim3(64), 0, ctx->stream, cfg, ctx->ev_off.as<int64_t>(),
-                               ctx->ev_len.as<int64_t>(), n_ev, d_bounds, ctx->bounds_off.as<int64_t>(), d_stats, scap,
-                               reinterpret_cast<unsigned *>(&sm->status), d_hdr);
+        });
         HIP_TRY(ctx, hipGetLastError());
         if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
     }
@@ -715,14 +779,11 @@ int finish_batch(ps_ctx *ctx, const DevCfg &cfg, size_t n_tj, int64_t n_items, i
     if (d_stats && !stats_from_digest) {
         const int64_t nseg = total + n_ev;
         if (nseg > 0) {
-            if (cfg.dtype == PS_DTYPE_F32)
-                hipLaunchKernelGGL(segstat_kernel<PS_DTYPE_F32>, dim3(static_cast<unsigned>(nseg)), dim3(STAT_NT), 0,
+            by_dtype(cfg.dtype, [&](auto dt) {
+                hipLaunchKernelGGL(segstat_kernel<dt()>, dim3(static_cast<unsigned>(nseg)), dim3(STAT_NT), 0,
                                    ctx->stream, cfg, ctx->ev_off.as<int64_t>(), ctx->ev_len.as<int64_t>(), n_ev, d_bounds,
                                    ctx->bounds_off.as<int64_t>(), d_stats, reinterpret_cast<unsigned *>(&sm->status));
-            else
-                hipLaunchKernelGGL(segstat_kernel<PS_DTYPE_I16>, dim3(static_cast<unsigned>(nseg)), dim3(STAT_NT), 0,
-                                   ctx->stream, cfg, ctx->ev_off.as<int64_t>(), ctx->ev_len.as<int64_t>(), n_ev, d_bounds,
-                                   ctx->bounds_off.as<int64_t>(), d_stats, reinterpret_cast<unsigned *>(&sm->status));
+            });
             HIP_TRY(ctx, hipGetLastError());
         }
     }
@@ -768,16 +829,143 @@ template <int DT> int launch_bridge_la(ps_ctx *ctx, const DevCfg &cfg, unsigned 
 
 template <int NT, int DT> int launch_bridge(ps_ctx *ctx, const DevCfg &cfg, unsigned nj, SmallLayout *sm)
 {
-    const size_t lds = NT == 64 ? static_cast<size_t>(ctx->scan_lds_pad) : lds_bytes_for(cfg.lds_cap, NT);
-    HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(bridge_kernel<NT, DT>), static_cast<int>(lds)));
-    const unsigned grid = std::min(nj, resident_slots(ctx, bridge_kernel<NT, DT>, NT, lds));
-    hipLaunchKernelGGL((bridge_kernel<NT, DT>), dim3(grid), dim3(NT), lds, ctx->stream, cfg,
+    ScanShape s;
+    if (int rc = scan_shape<NT>(ctx, bridge_kernel<NT, DT>, cfg, nj, &s)) return rc;
+    hipLaunchKernelGGL((bridge_kernel<NT, DT>), dim3(s.grid), dim3(NT), s.lds, ctx->stream, cfg,
                        ctx->spine_jobs.as<SpineJob>(), ctx->spine_scratch.as<int2>(), ctx->spine_meta.as<int4>(),
                        ctx->bridges.as<int2>(), ctx->bmeta.as<int4>(), reinterpret_cast<unsigned *>(&sm->status),
                        &sm->work0, static_cast<int>(nj), ctx->bridge_single, ctx->bridge_budget,
                        NT == 64 ? lat_help_of(ctx, cfg, sm) : LAT_NONE);
     HIP_TRY(ctx, hipGetLastError());
     return PS_OK;
+}
+
+// Every segment call (and every redo of one on another route) starts its timings and work counters from zero
+void reset_call_stats(ps_ctx *ctx)
+{
+    for (double &m : ctx->ms) m = 0;
+    for (int64_t &c : ctx->counters) c = 0;
+}
+
+// The buffers sized by the items of a call -- true spine anchors, one subtree job each at most -- for up to items_cap of them
+// (the first sizing of the device stitch, and again when a second-chance round makes room for the anchors it may add)
+int reserve_items(ps_ctx *ctx, int64_t items_cap, int64_t total_len, int mw)
+{
+    const size_t n = static_cast<size_t>(std::max<int64_t>(1, items_cap));
+    const size_t tscratch_bound = static_cast<size_t>(total_len / mw + items_cap + 1);     // tree output regions: (base+pred)/mw + item
+    HIP_TRY(ctx, ctx->spine_items.reserve(n * sizeof(int4)));
+    HIP_TRY(ctx, ctx->tree_jobs.reserve(n * sizeof(TreeJob)));
+    HIP_TRY(ctx, ctx->tree_counts.reserve((n + (static_cast<size_t>(items_cap) >> GS_LOG) + 2) * sizeof(int32_t)));   // (+ the sums per 256 jobs: gather_scan_kernel)
+    HIP_TRY(ctx, ctx->items.reserve(n * sizeof(Item)));
+    HIP_TRY(ctx, ctx->item_pos.reserve((static_cast<size_t>(items_cap) + 1) * sizeof(int64_t)));
+    HIP_TRY(ctx, ctx->tree_scratch.reserve(tscratch_bound * sizeof(int32_t)));
+    HIP_TRY(ctx, ctx->tree_spill.reserve(tscratch_bound * sizeof(int2)));
+    return PS_OK;
+}
+
+// K0's digest of nb_pad blocks (k0_padded_blocks: a wave of K0 takes 256 blocks, the arrays are padded to whole waves, +1: the
+// end boundary) of n_ev events: block sums, the events' centres, totals + max|k| per chunk.  The caller says what it wants beside
+// them: the 64-bit digest, the group records of the coarse pass, per-block min / max for the statistics kernel, the detector's
+// verdict per block (ps_detect_segment_trace).
+struct DigestWant { bool wide = false, grp = false, blk_mm = false, cls = false; };
+int reserve_digest(ps_ctx *ctx, int64_t nb_pad, int32_t n_ev, const DigestWant &want)
+{
+    const size_t nb = static_cast<size_t>(nb_pad);
+    // (at least 16 KB: a wave block of K0's general route fetches -- and ignores -- the head of this buffer, seg_bs.hpp)
+    HIP_TRY(ctx, ctx->bsum.reserve(std::max<size_t>(16384, nb * (want.wide ? sizeof(int4) : sizeof(uint2)))));
+    HIP_TRY(ctx, ctx->ev_info.reserve(static_cast<size_t>(std::max(1, n_ev)) * sizeof(int4)));
+    HIP_TRY(ctx, ctx->chunk_mabs.reserve(static_cast<size_t>(nb_pad / BS_CHUNK + 1) * (want.wide ? 2 : 1) * sizeof(int4)));
+    // group records of the coarse pass (16 B per 32 blocks; +1: the end boundary's)
+    if (want.grp) HIP_TRY(ctx, ctx->grp.reserve(static_cast<size_t>(nb_pad / BS_GRP + 1) * sizeof(uint4)));
+    // per-block min/max for the statistics kernel (4 B per block; int16 pairs)
+    if (want.blk_mm) HIP_TRY(ctx, ctx->blk_mm.reserve(nb * sizeof(int)));
+    // K0's verdict per block against the detector's threshold (2 bits), min / max per 128 blocks
+    if (want.cls) {
+        HIP_TRY(ctx, ctx->blk_cls.reserve(static_cast<size_t>(nb_pad / 4 + 64)));
+        HIP_TRY(ctx, ctx->cls_mm.reserve(static_cast<size_t>(nb_pad / BS_CHUNK + 2) * sizeof(int2)));
+    }
+    return PS_OK;
+}
+
+// One call's K0: the event tables on the device, and what differs between the routes that launch it.
+struct K0Call {
+    const int64_t *ev_start, *ev_len, *ev_boff;
+    int32_t n_ev;
+    int64_t n_samples, nb_pad;
+    bool persistent = true;   // false: one wave per wave block whatever k0_waves says (ps_audit_bounds)
+    bool admit = false;       // the call takes a ticket of the device's K0 chain (k0_admit) in front of K0; k0_done() records it
+    bool batch = false;       // diagnostic library: the batch route, where k0_sets applies ...
+    bool repeat = false;      // ... and a call that repeats the previous one's layout, where dbg_phase / dbg_k0_nogrp apply
+};
+// (NS_F32 / NS_I16: register sets of a wave for either sample type, seg_bs.hpp: blocksum_kernel<DT, NS>)
+template <int FLAGS, int NS_F32, int NS_I16>
+void enqueue_k0(ps_ctx *ctx, const DevCfg &cfg, hipStream_t st, const K0Call &k, unsigned grid, uint4 *grp)
+{
+    SmallLayout *sm = ctx->small.as<SmallLayout>();
+    by_dtype<FLAGS>(cfg.dtype, [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        constexpr int NS = sdt(DT) == PS_DTYPE_F32 ? NS_F32 : NS_I16;
+        hipLaunchKernelGGL((blocksum_kernel<DT, NS>), dim3(grid), dim3(64 * K0_WAVES), 0, st, cfg, k.ev_start, k.ev_len, k.ev_boff, k.n_ev,
+                           k.n_samples, ctx->bsum.p, ctx->ev_info.as<int4>(), ctx->chunk_mabs.as<int4>(),
+                           reinterpret_cast<unsigned *>(&sm->status), grp);
+    });
+}
+// K0 on stream st: chunk-prefixed block sums (one streaming pass), per-event centre m, totals + max|k| per 256 blocks, on the
+// digest reserve_digest() sized (FLAGS: DT_WIDE for the 64-bit one).  cfg as K0 sees it: grp / blk_mm / blk_cls set, bsum not yet.
+template <int FLAGS> int launch_k0(ps_ctx *ctx, const DevCfg &cfg, hipStream_t st, const K0Call &k)
+{
+    const bool f32 = cfg.dtype == PS_DTYPE_F32;
+    int ns = 2;                                        // register sets of a persistent wave (ps_ctx::k0_sets)
+    bool skip_k0 = false;
+    uint4 *k0_grp = const_cast<uint4 *>(static_cast<const uint4 *>(cfg.grp));
+#ifdef PS_DIAG
+    if (k.batch && !(FLAGS & DT_WIDE) && ctx->k0_sets > 2 && ctx->k0_waves > 0) ns = ctx->k0_sets;
+    skip_k0 = ctx->dbg_phase == 1 && k.repeat;         // diagnostics: the previous call's digest
+    if (ctx->dbg_k0_nogrp && k.repeat) k0_grp = nullptr;
+#endif
+    // K0 is persistent (round 5): k0_waves workgroups per CU (K0_WAVES waves each, i.e. that many waves per SIMD), every
+    // wave striding over the wave blocks of the call with its next block's samples in flight.  One or two waves per SIMD
+    // saturate HBM; the rest of the SIMD stays free for the scan waves of the other calls in flight.  k0_waves = 0: one wave
+    // per wave block as in rounds 3 and 4 (the launch then fills every slot the registers allow).
+    const unsigned n_cu = k.persistent ? static_cast<unsigned>(cu_count(ctx)) : 0u;
+    const unsigned k0_full = static_cast<unsigned>((k.nb_pad / K0_WB + K0_WAVES - 1) / K0_WAVES);
+    // (a wave block of int16 samples is half the bytes: twice the waves keep the same bytes in flight)
+    const unsigned k0_per_cu = static_cast<unsigned>(ctx->k0_waves) * ((f32 || ns > 2) ? 1u : 2u);   // (ns > 2: diagnostic library only)
+    const unsigned k0_grid = k.persistent && ctx->k0_waves > 0 ? std::min(k0_full, k0_per_cu * n_cu * (4u / K0_WAVES)) : k0_full;
+    if (k.admit && ctx->k0_admit > 0) {
+        const int grc = chain_enter(ctx, ctx->device, ctx->k0_admit, st, &ctx->chain_ticket);
+        if (grc) return grc;
+        ctx->chain_held = true;
+    }
+    bool queued = skip_k0;
+#ifdef PS_DIAG
+    // (measured and rejected, round 6 -- docs/ROUND_6.md: fatter K0 waves hold fewer registers per byte in flight, but a lone K0
+    //  wave per SIMD cannot issue fast enough beside four scan waves; the instances exist in the diagnostic library only)
+    if constexpr (!(FLAGS & DT_WIDE)) {
+        if (!queued && ns == 3) { enqueue_k0<FLAGS, 3, 6>(ctx, cfg, st, k, k0_grid, k0_grp); queued = true; }
+        if (!queued && ns == 4) { enqueue_k0<FLAGS, 4, 8>(ctx, cfg, st, k, k0_grid, k0_grp); queued = true; }
+    }
+#endif
+    if (!queued) enqueue_k0<FLAGS, 2, 2>(ctx, cfg, st, k, k0_grid, k0_grp);
+    HIP_TRY(ctx, hipGetLastError());
+    return PS_OK;
+}
+// K0 is behind this point of st: the call M tickets later waits for it on the device
+int k0_done(ps_ctx *ctx, hipStream_t st)
+{
+    if (!ctx->chain_held) return PS_OK;
+    ctx->chain_held = false;
+    return chain_publish(ctx, ctx->device, st, ctx->chain_ticket);
+}
+
+// Phases 1 and 1b of the block-sum pipeline: single-wave spines, then single-wave bridges; the seams that run into a stretch
+// without splits are finished by the look-ahead kernel
+template <int FLAGS> int launch_scans_bs(ps_ctx *ctx, const DevCfg &cfg, unsigned nj, SmallLayout *sm)
+{
+    if (int rc = by_dtype<FLAGS>(cfg.dtype, [&](auto dt) { return launch_spine<64, dt()>(ctx, cfg, nj, sm, true); })) return rc;
+    if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
+    if (int rc = by_dtype<FLAGS>(cfg.dtype, [&](auto dt) { return launch_bridge<64, dt()>(ctx, cfg, nj, sm); })) return rc;
+    return by_dtype<FLAGS>(cfg.dtype, [&](auto dt) { return launch_bridge_la<dt()>(ctx, cfg, nj, sm); });
 }
 
 // Device-stitch pipeline: tile spines without halo, seam bridges, assemble kernel (true spine,
@@ -834,20 +1022,9 @@ int device_stitch_batch_(ps_ctx *ctx, const DevCfg &cfg_in, int bs_mode, const i
             const int64_t nt = (len + Le - 1) / Le;
             if (static_cast<int64_t>(jobs.size()) + nt > 0x7ffffff0) return RC_FALLBACK;
             for (int64_t t = 0; t < nt; ++t) {
-                SpineJob j;
-                j.base = ev_start[e];
-                j.start = static_cast<int32_t>(t * Le);
-                j.end = static_cast<int32_t>(len);
-                j.stop = static_cast<int32_t>(t == nt - 1 ? len : (t + 1) * Le);
-                j.out_cap = static_cast<int32_t>(std::min<int64_t>((j.stop - j.start) / mw + 4, 0x7fffffff));
-                j.out_off = list_entries;
-                j.first_tile = static_cast<int32_t>(ev_first_tile[e]);
-                j.ntiles = static_cast<int32_t>(nt);
-                j.tile_len = static_cast<int32_t>(Le);
-                j.ev = e;
-                j.vbase = vbase;
-                list_entries += j.out_cap;
-                jobs.push_back(j);
+                jobs.push_back(make_spine_job(ev_start[e], e, len, t * Le, t == nt - 1 ? len : (t + 1) * Le, mw, list_entries,
+                                              {ev_first_tile[e], nt, Le, vbase}));
+                list_entries += jobs.back().out_cap;
             }
         }
         ev_first_tile[n_ev] = static_cast<int64_t>(jobs.size());
@@ -874,7 +1051,6 @@ int device_stitch_batch_(ps_ctx *ctx, const DevCfg &cfg_in, int bs_mode, const i
     const int64_t list_entries = tc.list_entries, total_len = tc.total_len, sample_end = tc.sample_end;
     ctx->counters[2] = static_cast<int64_t>(nj);
     const int64_t max_items = list_entries + static_cast<int64_t>(nj) * BR_MAX;
-    const int64_t tscratch_bound = total_len / mw + max_items + 1;     // tree output regions: (base+pred)/mw + item
 
     HIP_TRY(ctx, ctx->spine_scratch.reserve(std::max<int64_t>(1, list_entries) * sizeof(int2)));
     HIP_TRY(ctx, ctx->spine_meta.reserve(std::max<size_t>(4, nj) * sizeof(int4)));
@@ -897,13 +1073,7 @@ int device_stitch_batch_(ps_ctx *ctx, const DevCfg &cfg_in, int bs_mode, const i
     HIP_TRY(ctx, ctx->bmeta.reserve(std::max<size_t>(1, nj) * sizeof(int4)));
     HIP_TRY(ctx, ctx->tile_i32.reserve(std::max<size_t>(1, nj) * 4 * sizeof(int)));
     HIP_TRY(ctx, ctx->sp_off.reserve((nj + 1) * sizeof(long long)));
-    HIP_TRY(ctx, ctx->spine_items.reserve(std::max<int64_t>(1, max_items) * sizeof(int4)));
-    HIP_TRY(ctx, ctx->tree_jobs.reserve(std::max<int64_t>(1, max_items) * sizeof(TreeJob)));
-    HIP_TRY(ctx, ctx->tree_counts.reserve((std::max<int64_t>(1, max_items) + (max_items >> GS_LOG) + 2) * sizeof(int32_t)));   // (+ the sums per 256 jobs: gather_scan_kernel)
-    HIP_TRY(ctx, ctx->items.reserve(std::max<int64_t>(1, max_items) * sizeof(Item)));
-    HIP_TRY(ctx, ctx->item_pos.reserve((static_cast<size_t>(max_items) + 1) * sizeof(int64_t)));
-    HIP_TRY(ctx, ctx->tree_scratch.reserve(static_cast<size_t>(tscratch_bound) * sizeof(int32_t)));
-    HIP_TRY(ctx, ctx->tree_spill.reserve(static_cast<size_t>(tscratch_bound) * sizeof(int2)));
+    if (int irc = reserve_items(ctx, max_items, total_len, mw)) return irc;
     HIP_TRY(ctx, ctx->first_item.reserve(evb));
     if (evb <= SMALL_TAIL) ctx->bounds_off.alias(ctx->small.as<char>() + sizeof(SmallLayout));   // comes back with the status block
     else HIP_TRY(ctx, ctx->bounds_off.reserve(evb));
@@ -947,7 +1117,6 @@ int device_stitch_batch_(ps_ctx *ctx, const DevCfg &cfg_in, int bs_mode, const i
     ctx->ev_boff.alias(dup + jb + 3 * evb);
 
     SmallLayout *sm = ctx->small.as<SmallLayout>();
-    const bool f32 = cfg.dtype == PS_DTYPE_F32;
     if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[7], fs));
     if (use_bs && nj && digest_ready) {
         HIP_TRY(ctx, ctx->ev_info_tr.reserve(static_cast<size_t>(std::max(1, n_ev)) * sizeof(int4)));
@@ -960,74 +1129,25 @@ int device_stitch_batch_(ps_ctx *ctx, const DevCfg &cfg_in, int bs_mode, const i
         cfg.grp = ctx->groups ? ctx->grp.p : nullptr;
         cfg.blk_mm = d_stats ? ctx->blk_mm.as<int>() : nullptr;
     } else if (use_bs && nj) {
-        // K0: chunk-prefixed block sums (one streaming pass), per-event centre m, totals + max|k| per 256 blocks
-        const int64_t nb_total = tc.nb_total;
-        // (a wave of K0 takes 256 blocks; the digest arrays are padded to whole waves, +1: the end boundary)
-        const int64_t nb_pad = k0_padded_blocks(nb_total);
-        // (at least 16 KB: a wave block of K0's general route fetches -- and ignores -- the head of this buffer, seg_bs.hpp)
-        HIP_TRY(ctx, ctx->bsum.reserve(std::max<size_t>(16384, static_cast<size_t>(nb_pad) * (wide ? sizeof(int4) : sizeof(uint2)))));
-        HIP_TRY(ctx, ctx->ev_info.reserve(static_cast<size_t>(std::max(1, n_ev)) * sizeof(int4)));
-        HIP_TRY(ctx, ctx->chunk_mabs.reserve(static_cast<size_t>(nb_pad / BS_CHUNK + 1) * (wide ? 2 : 1) * sizeof(int4)));
-        if (!wide && ctx->groups) {                    // group records of the coarse pass (16 B per 32 blocks; +1: the end boundary's)
-            HIP_TRY(ctx, ctx->grp.reserve(static_cast<size_t>(nb_pad / BS_GRP + 1) * sizeof(uint4)));
-            cfg.grp = ctx->grp.p;
-        }
-        if (d_stats && !wide) {                        // per-block min/max for the statistics kernel (4 B per block; int16 pairs)
-            HIP_TRY(ctx, ctx->blk_mm.reserve(static_cast<size_t>(nb_pad) * sizeof(int)));
-            cfg.blk_mm = ctx->blk_mm.as<int>();
-        }
-        // K0 is persistent (round 5): k0_waves workgroups per CU (K0_WAVES waves each, i.e. that many waves per SIMD), every
-        // wave striding over the wave blocks of the call with its next block's samples in flight.  One or two waves per SIMD
-        // saturate HBM; the rest of the SIMD stays free for the scan waves of the other calls in flight.  k0_waves = 0: one wave
-        // per wave block as in rounds 3 and 4 (the launch then fills every slot the registers allow).
-        if (ctx->n_cu <= 0) {
-            hipDeviceProp_t prop;
-            ctx->n_cu = hipGetDeviceProperties(&prop, ctx->device) == hipSuccess ? prop.multiProcessorCount : 256;
-        }
-        const unsigned k0_full = static_cast<unsigned>((nb_pad / K0_WB + K0_WAVES - 1) / K0_WAVES);
-        // (a wave block of int16 samples is half the bytes: twice the waves keep the same bytes in flight)
-        const unsigned k0_per_cu = static_cast<unsigned>(ctx->k0_waves) * ((f32 || (ctx->k0_sets > 2 && !wide)) ? 1u : 2u);   // (k0_sets > 2: diagnostic library only)
-        const unsigned k0_grid = ctx->k0_waves > 0 ? std::min(k0_full, k0_per_cu * static_cast<unsigned>(ctx->n_cu) * (4u / K0_WAVES)) : k0_full;
-        const size_t k0_lds = 0;
-#define PS_K0N(DTV, NSV) hipLaunchKernelGGL((blocksum_kernel<DTV, NSV>), dim3(k0_grid), dim3(64 * K0_WAVES), k0_lds, fs, cfg,       \
-                                    ctx->ev_off.as<int64_t>(), ctx->ev_len.as<int64_t>(), ctx->ev_boff.as<int64_t>(), n_ev, sample_end, \
-                                    ctx->bsum.p, ctx->ev_info.as<int4>(), ctx->chunk_mabs.as<int4>(),                                   \
-                                    reinterpret_cast<unsigned *>(&sm->status), k0_grp)
-        if (ctx->k0_admit > 0 && !front) {
-            const int grc = chain_enter(ctx, ctx->device, ctx->k0_admit, fs, &ctx->chain_ticket);
-            if (grc) return grc;
-            ctx->chain_held = true;
-        }
-#ifdef PS_DIAG
-        const bool skip_k0 = ctx->dbg_phase == 1 && reuse;     // diagnostics: the previous call's digest
-        uint4 *const k0_grp = (ctx->dbg_k0_nogrp && reuse) ? nullptr : const_cast<uint4 *>(static_cast<const uint4 *>(cfg.grp));
-#else
-        const bool skip_k0 = false;
-        uint4 *const k0_grp = const_cast<uint4 *>(static_cast<const uint4 *>(cfg.grp));
-#endif
-#define PS_K0(DTV) PS_K0N(DTV, 2)
-        if (skip_k0) { }
-        else if (wide) { if (f32) PS_K0(PS_DTYPE_F32 | DT_WIDE); else PS_K0(PS_DTYPE_I16 | DT_WIDE); }
-#ifdef PS_DIAG
-        // (measured and rejected, round 6 -- docs/ROUND_6.md: fatter K0 waves hold fewer registers per byte in flight, but a lone K0
-        //  wave per SIMD cannot issue fast enough beside four scan waves; the instances exist in the diagnostic library only)
-        else if (ctx->k0_sets == 3 && ctx->k0_waves > 0) { if (f32) PS_K0N(PS_DTYPE_F32, 3); else PS_K0N(PS_DTYPE_I16, 6); }
-        else if (ctx->k0_sets == 4 && ctx->k0_waves > 0) { if (f32) PS_K0N(PS_DTYPE_F32, 4); else PS_K0N(PS_DTYPE_I16, 8); }
-#endif
-        else           { if (f32) PS_K0(PS_DTYPE_F32); else PS_K0(PS_DTYPE_I16); }
-#undef PS_K0
-#undef PS_K0N
-        HIP_TRY(ctx, hipGetLastError());
+        const int64_t nb_pad = k0_padded_blocks(tc.nb_total);
+        DigestWant want;
+        want.wide = wide;
+        want.grp = !wide && ctx->groups;
+        want.blk_mm = d_stats && !wide;
+        if (int drc = reserve_digest(ctx, nb_pad, n_ev, want)) return drc;
+        if (want.grp) cfg.grp = ctx->grp.p;
+        if (want.blk_mm) cfg.blk_mm = ctx->blk_mm.as<int>();
+        K0Call k0 = {ctx->ev_off.as<int64_t>(), ctx->ev_len.as<int64_t>(), ctx->ev_boff.as<int64_t>(), n_ev, sample_end, nb_pad};
+        k0.admit = !front;                             // (the front stream serialises the K0s of its contexts by itself)
+        k0.batch = true;
+        k0.repeat = reuse;
+        if (int krc = wide ? launch_k0<DT_WIDE>(ctx, cfg, fs, k0) : launch_k0<0>(ctx, cfg, fs, k0)) return krc;
         cfg.bsum = ctx->bsum.p;
         cfg.ev_info = ctx->ev_info.as<int4>();
         cfg.chunk_tot = ctx->chunk_mabs.as<int4>();
     }
     if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[0], fs));
-    if (ctx->chain_held) {                             // K0 is behind this event: the call M tickets later waits for it on the device
-        ctx->chain_held = false;
-        const int crc = chain_publish(ctx, ctx->device, fs, ctx->chain_ticket);
-        if (crc) return crc;
-    }
+    if (int crc = k0_done(ctx, fs)) return crc;         // (K0 is behind this event)
 #ifdef PS_DIAG
     if (ctx->dbg_phase == 2) {                           // diagnostics: K0 only
         if (front) front_lock.unlock();
@@ -1041,38 +1161,20 @@ int device_stitch_batch_(ps_ctx *ctx, const DevCfg &cfg_in, int bs_mode, const i
         front_lock.unlock();
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_front[1], 0));
     }
-    if (nj && wide) {
-        // (the 64-bit digest: same kernels, compiled for it)
+    if (nj) {
         const unsigned g = static_cast<unsigned>(nj);
-        int lrc = f32 ? launch_spine<64, PS_DTYPE_F32 | DT_WIDE>(ctx, cfg, g, sm, true) : launch_spine<64, PS_DTYPE_I16 | DT_WIDE>(ctx, cfg, g, sm, true);
-        if (lrc) return lrc;
-        if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
-        lrc = f32 ? launch_bridge<64, PS_DTYPE_F32 | DT_WIDE>(ctx, cfg, g, sm) : launch_bridge<64, PS_DTYPE_I16 | DT_WIDE>(ctx, cfg, g, sm);
-        if (lrc) return lrc;
-        lrc = f32 ? launch_bridge_la<PS_DTYPE_F32 | DT_WIDE>(ctx, cfg, g, sm) : launch_bridge_la<PS_DTYPE_I16 | DT_WIDE>(ctx, cfg, g, sm);
-        if (lrc) return lrc;
-    } else if (nj && use_bs) {
-        const unsigned g = static_cast<unsigned>(nj);
-        int lrc = f32 ? launch_spine<64, PS_DTYPE_F32>(ctx, cfg, g, sm, true) : launch_spine<64, PS_DTYPE_I16>(ctx, cfg, g, sm, true);
-        if (lrc) return lrc;
-        if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
-        // single-wave bridges first; the seams that run into a stretch without splits are finished by the look-ahead kernel
-        lrc = f32 ? launch_bridge<64, PS_DTYPE_F32>(ctx, cfg, g, sm) : launch_bridge<64, PS_DTYPE_I16>(ctx, cfg, g, sm);
-        if (lrc) return lrc;
-        lrc = f32 ? launch_bridge_la<PS_DTYPE_F32>(ctx, cfg, g, sm) : launch_bridge_la<PS_DTYPE_I16>(ctx, cfg, g, sm);
-        if (lrc) return lrc;
-    } else if (nj) {
-        const unsigned g = static_cast<unsigned>(nj);
-        int lrc = ctx->spine_nt == 256
-                      ? (f32 ? launch_spine<256, PS_DTYPE_F32>(ctx, cfg, g, sm, true) : launch_spine<256, PS_DTYPE_I16>(ctx, cfg, g, sm, true))
-                  : ctx->spine_nt == 512
-                      ? (f32 ? launch_spine<512, PS_DTYPE_F32>(ctx, cfg, g, sm, true) : launch_spine<512, PS_DTYPE_I16>(ctx, cfg, g, sm, true))
-                      : (f32 ? launch_spine<1024, PS_DTYPE_F32>(ctx, cfg, g, sm, true) : launch_spine<1024, PS_DTYPE_I16>(ctx, cfg, g, sm, true));
-        if (lrc) return lrc;
-        if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
-        lrc = ctx->spine_nt == 256
-                  ? (f32 ? launch_bridge<256, PS_DTYPE_F32>(ctx, cfg, g, sm) : launch_bridge<256, PS_DTYPE_I16>(ctx, cfg, g, sm))
-                  : (f32 ? launch_bridge<512, PS_DTYPE_F32>(ctx, cfg, g, sm) : launch_bridge<512, PS_DTYPE_I16>(ctx, cfg, g, sm));
+        int lrc;
+        if (wide) lrc = launch_scans_bs<DT_WIDE>(ctx, cfg, g, sm);      // (the 64-bit digest: same kernels, compiled for it)
+        else if (use_bs) lrc = launch_scans_bs<0>(ctx, cfg, g, sm);
+        else {
+            // LDS-window scan at the option's width (spine_nt); the widest spine is bridged by the 512-thread kernel
+            lrc = launch_spine_nt(ctx, cfg, g, sm, true);
+            if (lrc) return lrc;
+            if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
+            lrc = by_nt<256, 512>(ctx->spine_nt, [&](auto nt) {
+                return by_dtype(cfg.dtype, [&](auto dt) { return launch_bridge<decltype(nt)::value, dt()>(ctx, cfg, g, sm); });
+            });
+        }
         if (lrc) return lrc;
     }
     if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
@@ -1146,30 +1248,23 @@ int device_stitch_batch_(ps_ctx *ctx, const DevCfg &cfg_in, int bs_mode, const i
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                       // (list is a local)
         HIP_TRY(ctx, hipMemsetAsync(&sm->hdr, 0, sizeof(AsmHeader), ctx->stream));
         {
-            const bool f32 = cfg.dtype == PS_DTYPE_F32;
             const unsigned g = static_cast<unsigned>(n_ext);
-#define PS_EXT(DTV) hipLaunchKernelGGL((bridge_la_kernel<DTV, true>), dim3(g), dim3(64 * BR_LA), 0, ctx->stream, cfg,                      \
-                                       ctx->spine_jobs.as<SpineJob>(), ctx->spine_scratch.as<int2>(), ctx->spine_meta.as<int4>(),          \
-                                       ctx->bridges.as<int2>(), ctx->bmeta.as<int4>(), reinterpret_cast<unsigned *>(&sm->status),           \
-                                       &sm->work0, static_cast<int>(n_ext), ctx->ext_list.as<int>(), ctx->bridge_ext.as<int2>(),           \
-                                       ctx->ext_slot.as<int>(), slots_used, BR_MAX, ext_stride)
-            if (wide) { if (f32) PS_EXT(PS_DTYPE_F32 | DT_WIDE); else PS_EXT(PS_DTYPE_I16 | DT_WIDE); }
-            else      { if (f32) PS_EXT(PS_DTYPE_F32); else PS_EXT(PS_DTYPE_I16); }
-#undef PS_EXT
+            auto extend = [&](auto dt) {
+                hipLaunchKernelGGL((bridge_la_kernel<dt(), true>), dim3(g), dim3(64 * BR_LA), 0, ctx->stream, cfg,
+                                   ctx->spine_jobs.as<SpineJob>(), ctx->spine_scratch.as<int2>(), ctx->spine_meta.as<int4>(),
+                                   ctx->bridges.as<int2>(), ctx->bmeta.as<int4>(), reinterpret_cast<unsigned *>(&sm->status),
+                                   &sm->work0, static_cast<int>(n_ext), ctx->ext_list.as<int>(), ctx->bridge_ext.as<int2>(),
+                                   ctx->ext_slot.as<int>(), slots_used, BR_MAX, ext_stride);
+            };
+            if (wide) by_dtype<DT_WIDE>(cfg.dtype, extend);
+            else by_dtype(cfg.dtype, extend);
             HIP_TRY(ctx, hipGetLastError());
         }
         ctx->counters[4] += static_cast<int64_t>(n_ext);
         slots_used += static_cast<int>(n_ext);
         // room for the anchors the continued seams may add
         items_cap += static_cast<int64_t>(n_ext) * ext_stride;
-        const int64_t ts2 = total_len / mw + items_cap + 1;
-        HIP_TRY(ctx, ctx->spine_items.reserve(static_cast<size_t>(items_cap) * sizeof(int4)));
-        HIP_TRY(ctx, ctx->tree_jobs.reserve(static_cast<size_t>(items_cap) * sizeof(TreeJob)));
-        HIP_TRY(ctx, ctx->tree_counts.reserve((static_cast<size_t>(items_cap) + (static_cast<size_t>(items_cap) >> GS_LOG) + 2) * sizeof(int32_t)));
-        HIP_TRY(ctx, ctx->items.reserve(static_cast<size_t>(items_cap) * sizeof(Item)));
-        HIP_TRY(ctx, ctx->item_pos.reserve((static_cast<size_t>(items_cap) + 1) * sizeof(int64_t)));
-        HIP_TRY(ctx, ctx->tree_scratch.reserve(static_cast<size_t>(ts2) * sizeof(int32_t)));
-        HIP_TRY(ctx, ctx->tree_spill.reserve(static_cast<size_t>(ts2) * sizeof(int2)));
+        if (int irc = reserve_items(ctx, items_cap, total_len, mw)) return irc;
     }
     ctx->counters[3] = hd.n_items;
     float ms = 0;
@@ -1352,10 +1447,7 @@ int ps_set_tiling(ps_ctx *ctx, int64_t tile_len, int64_t halo)
 // hardware queue of its own: 0.67 ms per step) -- K0 on CUs of its own is not reachable through stream masks.
 static int diag_mask_stream(ps_ctx *ctx, hipStream_t *st, int first, int count, int stride, bool invert)
 {
-    if (ctx->n_cu <= 0) {
-        hipDeviceProp_t prop;
-        ctx->n_cu = hipGetDeviceProperties(&prop, ctx->device) == hipSuccess ? prop.multiProcessorCount : 256;
-    }
+    cu_count(ctx);
     HIP_TRY(ctx, hipStreamSynchronize(*st));
     HIP_TRY(ctx, hipStreamDestroy(*st));
     *st = nullptr;
@@ -1523,6 +1615,39 @@ int ps_segment_exact_f64(ps_ctx *ctx, const double *d_current, const int64_t *h_
     return segment_events_impl(ctx, d_current, &fmt, h_ev_start, h_ev_len, n_ev, params, d_bounds, cap, h_bounds_off, nullptr, nullptr, true);
 }
 
+// What the two segment entry points (ps_segment_events and its kin, ps_detect_segment_trace) do first, each behind the
+// pointer checks of its own arguments: the reference's assertions and its min_gain, the widths, the events' ranges (the trace
+// route has no events yet: n_ev 0), the call's configuration, the device.
+struct SegCall {
+    std::chrono::steady_clock::time_point t_begin;
+    int mw = 0, maxw = 0, W = 0;
+    DevCfg cfg;
+};
+static int begin_segment_call(ps_ctx *ctx, const void *d_samples, const ps_sample_format *fmt, const ps_split_params *params,
+                              const int64_t *ev_start, const int64_t *ev_len, int32_t n_ev, SegCall *c)
+{
+    c->t_begin = std::chrono::steady_clock::now();
+    ctx->chain_held = false;                           // (a ticket of the K0 chain that an earlier call did not record is forgotten)
+    double min_gain = 0;
+    int rc = ps_min_gain(params, &min_gain);
+    if (rc) return fail(ctx, rc, "reference assertion failed (cparsers.pyx:69-76)");
+    const int mw = params->min_width, maxw = params->max_width, W = params->window_width;
+    if (mw < 1 || W < 2) return fail(ctx, PS_ERR_ARG, "min_width must be >= 1 and window_width >= 2");
+    int64_t total_len = 0;
+    for (int e = 0; e < n_ev; ++e) {
+        const int64_t len = ev_len[e];
+        if (len < 0 || ev_start[e] < 0 || len > 0x7fffffff - 2LL * W - 8)
+            return fail(ctx, PS_ERR_ARG, "event %d length %lld out of range", e, static_cast<long long>(len));
+        total_len += len;
+    }
+    if (total_len > 0 && !d_samples) return fail(ctx, PS_ERR_ARG, "d_samples is NULL");
+    c->mw = mw; c->maxw = maxw; c->W = W;
+    rc = make_cfg(ctx, d_samples, fmt, mw, maxw, W, min_gain, &c->cfg);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return PS_OK;
+}
+
 // Near-tie log (ps_get_near_ties): every segment call starts with "not counted" and no events of its own ...
 static void nt_reset(ps_ctx *ctx)
 {
@@ -1561,55 +1686,20 @@ static void nt_keep(ps_ctx *ctx, const int64_t *ev_start, const int64_t *ev_len,
 static int segment_events_body(ps_ctx *ctx, const void *d_samples, const ps_sample_format *fmt,
                                const int64_t *ev_start, const int64_t *ev_len, int32_t n_ev, const ps_split_params *params,
                                int32_t *d_bounds, int64_t cap, int64_t *h_bounds_off, ps_segstat *d_stats,
-                               uint8_t *d_is_spine, bool d_f64);
-
-static int segment_events_impl(ps_ctx *ctx, const void *d_samples, const ps_sample_format *fmt,
-                               const int64_t *ev_start, const int64_t *ev_len, int32_t n_ev, const ps_split_params *params,
-                               int32_t *d_bounds, int64_t cap, int64_t *h_bounds_off, ps_segstat *d_stats,
-                               uint8_t *d_is_spine, bool d_f64)
-{
-    if (!ctx) return PS_ERR_ARG;
-    nt_reset(ctx);
-    const int rc = segment_events_body(ctx, d_samples, fmt, ev_start, ev_len, n_ev, params, d_bounds, cap, h_bounds_off, d_stats,
-                                       d_is_spine, d_f64);
-    if (rc == PS_OK && n_ev == 0) ctx->nt_seen = 0;           // (no event, no window: none -- as ps_detect_segment_trace says)
-    else if (rc == PS_OK) nt_keep(ctx, ev_start, ev_len, n_ev);
-    else ctx->nt_seen = -1;
-    return rc;
-}
-
-static int segment_events_body(ps_ctx *ctx, const void *d_samples, const ps_sample_format *fmt,
-                               const int64_t *ev_start, const int64_t *ev_len, int32_t n_ev, const ps_split_params *params,
-                               int32_t *d_bounds, int64_t cap, int64_t *h_bounds_off, ps_segstat *d_stats,
                                uint8_t *d_is_spine, bool d_f64)
 {
     if (!ctx) return PS_ERR_ARG;
     ctx->d_is_spine = d_is_spine;
-    const auto t_begin = std::chrono::steady_clock::now();
     if (!ev_start || !ev_len || !params || !h_bounds_off || n_ev < 0 || cap < 0 || (cap > 0 && !d_bounds))
         return fail(ctx, PS_ERR_ARG, "null/negative argument");
-    double min_gain = 0;
-    int rc = ps_min_gain(params, &min_gain);
-    if (rc) return fail(ctx, rc, "reference assertion failed (cparsers.pyx:69-76)");
-    const int mw = params->min_width, maxw = params->max_width, W = params->window_width;
-    if (mw < 1 || W < 2) return fail(ctx, PS_ERR_ARG, "min_width must be >= 1 and window_width >= 2");
-    for (int e = 0; e < n_ev; ++e) {
-        const int64_t len = ev_len[e];
-        if (len < 0 || ev_start[e] < 0 || len > 0x7fffffff - 2LL * W - 8)
-            return fail(ctx, PS_ERR_ARG, "event %d length %lld out of range", e, static_cast<long long>(len));
-    }
-    {
-        int64_t tl = 0;
-        for (int e = 0; e < n_ev; ++e) tl += ev_len[e];
-        if (tl > 0 && !d_samples) return fail(ctx, PS_ERR_ARG, "d_samples is NULL");
-    }
-    DevCfg cfg;
-    rc = make_cfg(ctx, d_samples, fmt, mw, maxw, W, min_gain, &cfg);
+    SegCall call;
+    int rc = begin_segment_call(ctx, d_samples, fmt, params, ev_start, ev_len, n_ev, &call);
     if (rc) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const auto t_begin = call.t_begin;
+    const int mw = call.mw, W = call.W;
+    DevCfg &cfg = call.cfg;
     if (!d_f64) { rc = nt_arm(ctx, cfg); if (rc) return rc; }
-    for (double &m : ctx->ms) m = 0;
-    for (int64_t &c : ctx->counters) c = 0;
+    reset_call_stats(ctx);
     ctx->stream_idle = true;
     if (ctx->k0_shared && hipStreamQuery(ctx->stream) != hipSuccess) { ctx->stream_idle = false; (void)hipGetLastError(); }
     if (ctx->timing >= 1) HIP_TRY(ctx, hipEventRecord(ctx->ev[8], ctx->stream));
@@ -1650,8 +1740,7 @@ static int segment_events_body(ps_ctx *ctx, const void *d_samples, const ps_samp
             ctx->wide_quantum = fmt->quantum;
             ctx->wide_mode = bs_mode;
             ctx->wide_skip = 16;
-            for (double &m : ctx->ms) m = 0;
-            for (int64_t &c : ctx->counters) c = 0;
+            reset_call_stats(ctx);
             HIP_TRY(ctx, hipMemsetAsync(ctx->small.p, 0, sizeof(SmallLayout), ctx->stream));
             ctx->stream_idle = false;                  // (the front stream, if used, waits for this memset)
             rc = device_stitch_batch(ctx, cfg, bs_mode, ev_start, ev_len, n_ev, mw, W, d_bounds, cap, h_bounds_off, d_stats, t_begin);
@@ -1659,8 +1748,7 @@ static int segment_events_body(ps_ctx *ctx, const void *d_samples, const ps_samp
         if (redo) ctx->counters[7] = redo;
         if (rc != RC_FALLBACK) return rc;
         // a seam could not be bridged on the device: redo with the host stitch (halo tiles + repairs)
-        for (double &m : ctx->ms) m = 0;
-        for (int64_t &c : ctx->counters) c = 0;
+        reset_call_stats(ctx);
         ctx->counters[4] = 1000000;
         HIP_TRY(ctx, hipMemsetAsync(ctx->small.p, 0, sizeof(SmallLayout), ctx->stream));
     }
@@ -1686,18 +1774,9 @@ static int segment_events_body(ps_ctx *ctx, const void *d_samples, const ps_samp
         if (len == 0) continue;
         const int64_t nt = len <= L + H ? 1 : (len + L - 1) / L;
         for (int64_t t = 0; t < nt; ++t) {
-            SpineJob j;
-            j.base = ev_start[e];
-            j.start = static_cast<int32_t>(t * L);
-            j.end = static_cast<int32_t>(len);
             const int64_t stop = (t == nt - 1) ? len : std::min(len, (t + 1) * L + H);
-            j.stop = static_cast<int32_t>(stop);
-            const int64_t capj = spine_cap(j.start, stop, mw);
-            j.out_cap = static_cast<int32_t>(std::min<int64_t>(capj, 0x7fffffff));
-            j.out_off = scratch;
-            j.first_tile = 0; j.ntiles = 1; j.tile_len = 0x7fffffff; j.ev = e; j.vbase = 0;
-            scratch += j.out_cap;
-            jobs.push_back(j);
+            jobs.push_back(make_spine_job(ev_start[e], e, len, t * L, stop, mw, scratch));
+            scratch += jobs.back().out_cap;
         }
     }
     ev_first_tile[n_ev] = static_cast<int64_t>(jobs.size());
@@ -1728,16 +1807,8 @@ static int segment_events_body(ps_ctx *ctx, const void *d_samples, const ps_samp
                 // the chain stopped (passed its stop position) without meeting a later tile:
                 // continue it from its last (true) anchor -- "seam repair"
                 const int32_t z = Lc.a.empty() ? Lc.start : Lc.a.back().pos;
-                std::vector<SpineJob> rj(1);
-                rj[0].base = ev_start[e];
-                rj[0].start = z;
-                rj[0].end = static_cast<int32_t>(len);
                 const int64_t stop = std::min<int64_t>(len, static_cast<int64_t>(z) + L + H);
-                rj[0].stop = static_cast<int32_t>(stop);
-                const int64_t capj = spine_cap(z, stop, mw);
-                rj[0].out_cap = static_cast<int32_t>(std::min<int64_t>(capj, 0x7fffffff));
-                rj[0].out_off = 0;
-                rj[0].first_tile = 0; rj[0].ntiles = 1; rj[0].tile_len = 0x7fffffff; rj[0].ev = e; rj[0].vbase = 0;
+                const std::vector<SpineJob> rj(1, make_spine_job(ev_start[e], e, len, z, stop, mw, 0));
                 std::vector<TileList> ext;
                 rc = run_spines(ctx, cfg, rj, rj[0].out_cap, ext);
                 if (rc) return rc;
@@ -1829,6 +1900,21 @@ static int segment_events_body(ps_ctx *ctx, const void *d_samples, const ps_samp
     return finish_batch(ctx, cfg, n_tj, n_items, n_ev, d_bounds, cap, h_bounds_off, d_stats, t_begin);
 }
 
+static int segment_events_impl(ps_ctx *ctx, const void *d_samples, const ps_sample_format *fmt,
+                               const int64_t *ev_start, const int64_t *ev_len, int32_t n_ev, const ps_split_params *params,
+                               int32_t *d_bounds, int64_t cap, int64_t *h_bounds_off, ps_segstat *d_stats,
+                               uint8_t *d_is_spine, bool d_f64)
+{
+    if (!ctx) return PS_ERR_ARG;
+    nt_reset(ctx);
+    const int rc = segment_events_body(ctx, d_samples, fmt, ev_start, ev_len, n_ev, params, d_bounds, cap, h_bounds_off, d_stats,
+                                       d_is_spine, d_f64);
+    if (rc == PS_OK && n_ev == 0) ctx->nt_seen = 0;           // (no event, no window: none -- as ps_detect_segment_trace says)
+    else if (rc == PS_OK) nt_keep(ctx, ev_start, ev_len, n_ev);
+    else ctx->nt_seen = -1;
+    return rc;
+}
+
 static int single_scan(ps_ctx *ctx, const void *d_samples, const ps_sample_format *fmt, int64_t n, int mode,
                        int mw, double min_gain, double *d_scores, double *gain_out, int32_t *idx_out)
 {
@@ -1847,17 +1933,14 @@ static int single_scan(ps_ctx *ctx, const void *d_samples, const ps_sample_forma
     cfg.lds_cap = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(n, ctx->lds_max_samples)));
     {
         const size_t lds = lds_bytes_for(cfg.lds_cap, 1024);
-        if (cfg.dtype == PS_DTYPE_F32) {
-            HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(single_scan_kernel<1024, PS_DTYPE_F32>), static_cast<int>(lds)));
-            hipLaunchKernelGGL((single_scan_kernel<1024, PS_DTYPE_F32>), dim3(1), dim3(1024), lds, ctx->stream, cfg,
+        rc = by_dtype(cfg.dtype, [&](auto dt) {
+            HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(single_scan_kernel<1024, dt()>), static_cast<int>(lds)));
+            hipLaunchKernelGGL((single_scan_kernel<1024, dt()>), dim3(1), dim3(1024), lds, ctx->stream, cfg,
                                static_cast<int>(n), mode, d_scores, d_gain, d_idx,
                                reinterpret_cast<unsigned *>(&sm->status), &sm->work0);
-        } else {
-            HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(single_scan_kernel<1024, PS_DTYPE_I16>), static_cast<int>(lds)));
-            hipLaunchKernelGGL((single_scan_kernel<1024, PS_DTYPE_I16>), dim3(1), dim3(1024), lds, ctx->stream, cfg,
-                               static_cast<int>(n), mode, d_scores, d_gain, d_idx,
-                               reinterpret_cast<unsigned *>(&sm->status), &sm->work0);
-        }
+            return PS_OK;
+        });
+        if (rc) return rc;
     }
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, ctx->h_small.reserve(sizeof(SmallLayout)));
@@ -1913,10 +1996,10 @@ int ps_audit_bounds(ps_ctx *ctx, const void *d_samples, const ps_sample_format *
     const int64_t nb_total = (n + 7) / 8, nb_pad = k0_padded_blocks(nb_total);
     const int64_t tab[4] = {0, n, 0, nb_total};                            // ev_start | ev_len | ev_boff[0..1]
     const size_t win_bytes = static_cast<size_t>(n_win) * 2 * sizeof(int32_t);
-    HIP_TRY(ctx, ctx->bsum.reserve(std::max<size_t>(16384, static_cast<size_t>(nb_pad) * sizeof(uint2))));
-    HIP_TRY(ctx, ctx->ev_info.reserve(sizeof(int4)));
-    HIP_TRY(ctx, ctx->chunk_mabs.reserve(static_cast<size_t>(nb_pad / BS_CHUNK + 1) * sizeof(int4)));
-    HIP_TRY(ctx, ctx->grp.reserve(static_cast<size_t>(nb_pad / BS_GRP + 1) * sizeof(uint4)));
+    DigestWant want;
+    want.grp = true;
+    rc = reserve_digest(ctx, nb_pad, 1, want);
+    if (rc) return rc;
     HIP_TRY(ctx, ctx->up_dev.reserve(sizeof(tab) + 128 + win_bytes));
     HIP_TRY(ctx, ctx->h_small.reserve(sizeof(SmallLayout)));
     char *d = ctx->up_dev.as<char>();
@@ -1929,23 +2012,20 @@ int ps_audit_bounds(ps_ctx *ctx, const void *d_samples, const ps_sample_format *
     SmallLayout *sm = ctx->small.as<SmallLayout>();
     const int64_t *dt = reinterpret_cast<const int64_t *>(d);
     cfg.grp = ctx->grp.p;
-    const unsigned k0_grid = static_cast<unsigned>((nb_pad / K0_WB + K0_WAVES - 1) / K0_WAVES);
-    const bool f32 = cfg.dtype == PS_DTYPE_F32;
-#define PS_K0A(DTV) hipLaunchKernelGGL((blocksum_kernel<DTV>), dim3(k0_grid), dim3(64 * K0_WAVES), 0, ctx->stream, cfg, dt, dt + 1, dt + 2, 1, n, \
-                                     ctx->bsum.p, ctx->ev_info.as<int4>(), ctx->chunk_mabs.as<int4>(), reinterpret_cast<unsigned *>(&sm->status), \
-                                     static_cast<uint4 *>(ctx->grp.p))
-    if (f32) PS_K0A(PS_DTYPE_F32); else PS_K0A(PS_DTYPE_I16);
-#undef PS_K0A
-    HIP_TRY(ctx, hipGetLastError());
+    // (always one wave per wave block, the narrow digest with its group records, no admission: the audit is no call of a pool)
+    K0Call k0 = {dt, dt + 1, dt + 2, 1, n, nb_pad};
+    k0.persistent = false;
+    rc = launch_k0<0>(ctx, cfg, ctx->stream, k0);
+    if (rc) return rc;
     cfg.bsum = ctx->bsum.p;
     cfg.ev_info = ctx->ev_info.as<int4>();
     cfg.chunk_tot = ctx->chunk_mabs.as<int4>();
     cfg.dbg = reinterpret_cast<unsigned long long *>(d + 32);
     const unsigned g = static_cast<unsigned>(std::min<int32_t>(n_win, 4096));
-    if (f32) hipLaunchKernelGGL((audit_kernel<PS_DTYPE_F32>), dim3(g), dim3(64), 0, ctx->stream, cfg, reinterpret_cast<const int2 *>(d + 128), n_win,
-                                reinterpret_cast<unsigned *>(&sm->status));
-    else     hipLaunchKernelGGL((audit_kernel<PS_DTYPE_I16>), dim3(g), dim3(64), 0, ctx->stream, cfg, reinterpret_cast<const int2 *>(d + 128), n_win,
-                                reinterpret_cast<unsigned *>(&sm->status));
+    by_dtype(cfg.dtype, [&](auto dt_) {
+        hipLaunchKernelGGL((audit_kernel<dt_()>), dim3(g), dim3(64), 0, ctx->stream, cfg, reinterpret_cast<const int2 *>(d + 128), n_win,
+                           reinterpret_cast<unsigned *>(&sm->status));
+    });
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(ctx->h_small.p, ctx->small.p, sizeof(SmallLayout), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(acc, d + 32, sizeof(acc), hipMemcpyDeviceToHost, ctx->stream));
@@ -1975,7 +2055,6 @@ namespace {
 int events_from_edges(ps_ctx *ctx, const DevCfg &cfg, int64_t n, std::vector<int> &tics, double threshold, int64_t min_duration,
                       double min_current, int64_t *h_starts, int64_t *h_lengths, int64_t cap, int64_t *n_events_out)
 {
-    const bool f32 = cfg.dtype == PS_DTYPE_F32;
     std::sort(tics.begin(), tics.end());
     std::vector<int2> cand;
     int a = 0;
@@ -1991,8 +2070,9 @@ int events_from_edges(ps_ctx *ctx, const DevCfg &cfg, int64_t n, std::vector<int
     std::memcpy(ctx->h_up.p, cand.data(), nc * sizeof(int2));
     int2 *d_cand = ctx->det_cand.as<int2>(), *d_mm = d_cand + nc;
     HIP_TRY(ctx, hipMemcpyAsync(d_cand, ctx->h_up.p, nc * sizeof(int2), hipMemcpyHostToDevice, ctx->stream));
-    if (f32) hipLaunchKernelGGL((piece_minmax_kernel<PS_DTYPE_F32>), dim3(static_cast<unsigned>(nc)), dim3(256), 0, ctx->stream, cfg, d_cand, static_cast<int>(nc), ctx->det_counts.as<int2>(), d_mm);
-    else     hipLaunchKernelGGL((piece_minmax_kernel<PS_DTYPE_I16>), dim3(static_cast<unsigned>(nc)), dim3(256), 0, ctx->stream, cfg, d_cand, static_cast<int>(nc), ctx->det_counts.as<int2>(), d_mm);
+    by_dtype(cfg.dtype, [&](auto dt) {
+        hipLaunchKernelGGL((piece_minmax_kernel<dt()>), dim3(static_cast<unsigned>(nc)), dim3(256), 0, ctx->stream, cfg, d_cand, static_cast<int>(nc), ctx->det_counts.as<int2>(), d_mm);
+    });
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, ctx->h_dense.reserve(nc * sizeof(int2)));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->h_dense.p, d_mm, nc * sizeof(int2), hipMemcpyDeviceToHost, ctx->stream));
@@ -2017,7 +2097,6 @@ int detect_edges(ps_ctx *ctx, const DevCfg &cfg, int64_t n, double threshold, bo
                  unsigned *status_out)
 {
     const int nb = static_cast<int>((n + DET_CHUNK - 1) / DET_CHUNK);
-    const bool f32 = cfg.dtype == PS_DTYPE_F32;
     SmallLayout *sm = ctx->small.as<SmallLayout>();
     unsigned *d_ntics = reinterpret_cast<unsigned *>(&sm->dense);
     HIP_TRY(ctx, ctx->det_counts.reserve(static_cast<size_t>(nb) * sizeof(int2)));
@@ -2030,18 +2109,15 @@ int detect_edges(ps_ctx *ctx, const DevCfg &cfg, int64_t n, double threshold, bo
         if (!by_blocks) HIP_TRY(ctx, hipMemsetAsync(ctx->small.p, 0, sizeof(SmallLayout), ctx->stream));
         else if (attempt > 0) HIP_TRY(ctx, hipMemsetAsync(&sm->dense, 0, sizeof(unsigned long long), ctx->stream));
         const unsigned cls_grid = static_cast<unsigned>((((n + 7) / 8 + 63) / 64 + CLS_NT - 1) / CLS_NT);
-#define PS_EDGE(DTV)                                                                                                                        \
-        do {                                                                                                                                \
-            if (by_blocks) hipLaunchKernelGGL((edge_cls_kernel<DTV>), dim3(cls_grid), dim3(CLS_NT), 0, ctx->stream, cfg, n, threshold,      \
-                                              ctx->blk_cls.as<unsigned char>(), ctx->cls_mm.as<int2>(), ctx->ev_info.as<int4>(),            \
-                                              ctx->det_tics.as<int>(), d_ntics, static_cast<unsigned>(tics_cap),                            \
-                                              ctx->det_counts.as<int2>(), reinterpret_cast<unsigned *>(&sm->status));                       \
-            else hipLaunchKernelGGL((edge_scan_kernel<DTV>), dim3(nb), dim3(DET_NT), 0, ctx->stream, cfg, n, threshold,                     \
-                                    ctx->det_tics.as<int>(), d_ntics, static_cast<unsigned>(tics_cap), ctx->det_counts.as<int2>(),          \
-                                    reinterpret_cast<unsigned *>(&sm->status));                                                             \
-        } while (0)
-        if (f32) PS_EDGE(PS_DTYPE_F32); else PS_EDGE(PS_DTYPE_I16);
-#undef PS_EDGE
+        by_dtype(cfg.dtype, [&](auto dt) {
+            if (by_blocks) hipLaunchKernelGGL((edge_cls_kernel<dt()>), dim3(cls_grid), dim3(CLS_NT), 0, ctx->stream, cfg, n, threshold,
+                                              ctx->blk_cls.as<unsigned char>(), ctx->cls_mm.as<int2>(), ctx->ev_info.as<int4>(),
+                                              ctx->det_tics.as<int>(), d_ntics, static_cast<unsigned>(tics_cap),
+                                              ctx->det_counts.as<int2>(), reinterpret_cast<unsigned *>(&sm->status));
+            else hipLaunchKernelGGL((edge_scan_kernel<dt()>), dim3(nb), dim3(DET_NT), 0, ctx->stream, cfg, n, threshold,
+                                    ctx->det_tics.as<int>(), d_ntics, static_cast<unsigned>(tics_cap), ctx->det_counts.as<int2>(),
+                                    reinterpret_cast<unsigned *>(&sm->status));
+        });
         HIP_TRY(ctx, hipGetLastError());
         // speculative copy of the first edges together with the count: one sync in the common case
         const size_t spec = std::min<size_t>(tics_cap, 4096);
@@ -2109,16 +2185,12 @@ int ps_detect_segment_trace(ps_ctx *ctx, const void *d_samples, const ps_sample_
     h_bounds_off[0] = 0;
     if (n == 0) { ctx->nt_seen = 0; return PS_OK; }
     if (!d_samples) return fail(ctx, PS_ERR_ARG, "d_samples is NULL");
-    const auto t_begin = std::chrono::steady_clock::now();
-    double min_gain = 0;
-    int rc = ps_min_gain(params, &min_gain);
-    if (rc) return fail(ctx, rc, "reference assertion failed (cparsers.pyx:69-76)");
-    const int mw = params->min_width, maxw = params->max_width, W = params->window_width;
-    if (mw < 1 || W < 2) return fail(ctx, PS_ERR_ARG, "min_width must be >= 1 and window_width >= 2");
-    DevCfg cfg;
-    rc = make_cfg(ctx, d_samples, fmt, mw, maxw, W, min_gain, &cfg);
+    SegCall call;
+    int rc = begin_segment_call(ctx, d_samples, fmt, params, nullptr, nullptr, 0, &call);
     if (rc) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const auto t_begin = call.t_begin;
+    const int mw = call.mw, W = call.W;
+    DevCfg &cfg = call.cfg;
     auto two_calls = [&]() -> int {
         int r2 = ps_detect_events(ctx, d_samples, fmt, n, threshold, min_duration, min_current, h_starts, h_lengths, ev_cap, n_events_out);
         if (r2) return r2;
@@ -2130,21 +2202,17 @@ int ps_detect_segment_trace(ps_ctx *ctx, const void *d_samples, const ps_sample_
     if (!use_bs) return two_calls();
     rc = nt_arm(ctx, cfg);
     if (rc) return rc;
-    for (double &m : ctx->ms) m = 0;
-    for (int64_t &c : ctx->counters) c = 0;
+    reset_call_stats(ctx);
     ctx->d_is_spine = nullptr;
     if (ctx->timing >= 1) HIP_TRY(ctx, hipEventRecord(ctx->ev[8], ctx->stream));
     // ---- K0 over the whole trace: one event [0, n), blocks aligned to the trace, per-block extremes on -------------------------
-    const bool f32 = cfg.dtype == PS_DTYPE_F32;
-    SmallLayout *sm = ctx->small.as<SmallLayout>();
     const int64_t nb_total = (n + 7) / 8, nb_pad = k0_padded_blocks(nb_total);
-    HIP_TRY(ctx, ctx->bsum.reserve(std::max<size_t>(16384, static_cast<size_t>(nb_pad) * sizeof(uint2))));
-    HIP_TRY(ctx, ctx->ev_info.reserve(sizeof(int4)));
-    HIP_TRY(ctx, ctx->chunk_mabs.reserve(static_cast<size_t>(nb_pad / BS_CHUNK + 1) * sizeof(int4)));
-    if (d_stats) HIP_TRY(ctx, ctx->blk_mm.reserve(static_cast<size_t>(nb_pad) * sizeof(int)));
-    if (ctx->groups) HIP_TRY(ctx, ctx->grp.reserve(static_cast<size_t>(nb_pad / BS_GRP + 1) * sizeof(uint4)));
-    HIP_TRY(ctx, ctx->blk_cls.reserve(static_cast<size_t>(nb_pad / 4 + 64)));
-    HIP_TRY(ctx, ctx->cls_mm.reserve(static_cast<size_t>(nb_pad / BS_CHUNK + 2) * sizeof(int2)));
+    DigestWant want;
+    want.grp = ctx->groups != 0;
+    want.blk_mm = d_stats != nullptr;
+    want.cls = true;
+    rc = reserve_digest(ctx, nb_pad, 1, want);
+    if (rc) return rc;
     HIP_TRY(ctx, ctx->det_cand.reserve(4 * sizeof(int64_t)));
     // below(k) <=> double(k) * q < threshold (below_thr): monotone in k, so there is ONE integer kthr with below(k) <=> k < kthr
     int kthr;
@@ -2167,26 +2235,15 @@ int ps_detect_segment_trace(ps_ctx *ctx, const void *d_samples, const ps_sample_
     cfg.blk_cls = ctx->blk_cls.as<unsigned char>();
     cfg.cls_mm = ctx->cls_mm.as<int2>();
     cfg.cls_kthr = kthr;
-    if (ctx->n_cu <= 0) {
-        hipDeviceProp_t prop;
-        ctx->n_cu = hipGetDeviceProperties(&prop, ctx->device) == hipSuccess ? prop.multiProcessorCount : 256;
-    }
     {
-        const unsigned k0_full = static_cast<unsigned>((nb_pad / K0_WB + K0_WAVES - 1) / K0_WAVES);
-        const unsigned k0_per_cu = static_cast<unsigned>(ctx->k0_waves) * (f32 ? 1u : 2u);
-        const unsigned k0_grid = ctx->k0_waves > 0 ? std::min(k0_full, k0_per_cu * static_cast<unsigned>(ctx->n_cu) * (4u / K0_WAVES)) : k0_full;
+        // (the narrow digest, on the context's own stream, with the per-block verdicts cfg names)
         const int64_t *d_ev = ctx->det_cand.as<int64_t>();
-        if (ctx->k0_admit > 0) {
-            const int grc = chain_enter(ctx, ctx->device, ctx->k0_admit, ctx->stream, &ctx->chain_ticket);
-            if (grc) return grc;
-        }
-#define PS_K0T(DTV) hipLaunchKernelGGL((blocksum_kernel<DTV, 2>), dim3(k0_grid), dim3(64 * K0_WAVES), 0, ctx->stream, cfg, d_ev, d_ev + 1, d_ev + 2, 1, n, \
-                                     ctx->bsum.p, ctx->ev_info.as<int4>(), ctx->chunk_mabs.as<int4>(), reinterpret_cast<unsigned *>(&sm->status),          \
-                                     const_cast<uint4 *>(static_cast<const uint4 *>(cfg.grp)))
-        if (f32) PS_K0T(PS_DTYPE_F32); else PS_K0T(PS_DTYPE_I16);
-#undef PS_K0T
-        HIP_TRY(ctx, hipGetLastError());
-        if (ctx->k0_admit > 0) { const int crc = chain_publish(ctx, ctx->device, ctx->stream, ctx->chain_ticket); if (crc) return crc; }
+        K0Call k0 = {d_ev, d_ev + 1, d_ev + 2, 1, n, nb_pad};
+        k0.admit = true;
+        rc = launch_k0<0>(ctx, cfg, ctx->stream, k0);
+        if (rc) return rc;
+        rc = k0_done(ctx, ctx->stream);
+        if (rc) return rc;
     }
     // ---- the detector on K0's verdicts per block ----------------------------------------------------------------------------
     std::vector<int> tics;

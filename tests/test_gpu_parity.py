@@ -491,6 +491,34 @@ def test_both_scan_implementations_on_goldens(scan_bs, ctx):
         ctx.set_option("scan_bs", 1)
 
 
+@pytest.mark.parametrize("stitch_host", [0, 1])
+@pytest.mark.parametrize("dtype", ["float32", "int16"])
+@pytest.mark.parametrize("name", ["G4_small_windows", "G9_rd_short_dwell"])
+@pytest.mark.parametrize("spine_nt,tree_nt", [(256, 256), (512, 512), (1024, 256)])
+def test_lds_window_scan_at_every_workgroup_width(spine_nt, tree_nt, name, dtype, stitch_host, ctx):
+    """The LDS-window kernels (scan_bs 0) at every width the options spine_nt / tree_nt accept -- the widest spine is bridged
+    by the 512-thread kernel -- on short tiles, so that several tiles, seams and bridges exist, with the device stitch and the
+    host stitch, from fp32 and from int16 samples: the goldens' boundaries."""
+    from pypore_amd.parsers import SpeedyStatSplit
+    (case,) = [c for c in cases("parse") if c["name"] == name]
+    counts = input_counts(case)
+    x = counts.astype(np.int16) if dtype == "int16" else synth.counts_to_pa(counts, np.float32)
+    ctx.set_option("scan_bs", 0)
+    ctx.set_option("spine_nt", spine_nt)
+    ctx.set_option("tree_nt", tree_nt)
+    ctx.set_tiling(7000, 1)
+    ctx.set_option("stitch_host", stitch_host)
+    try:
+        segs = SpeedyStatSplit(quantum=synth.QUANTUM, **case["params"]).parse(x)
+    finally:                                            # (what the context started with: tools/gpu_validate.sh)
+        ctx.set_option("scan_bs", int(os.environ.get("PORESEG_SCAN_BS", "1")))
+        ctx.set_option("spine_nt", int(os.environ.get("PORESEG_SPINE_NT", "512")))
+        ctx.set_option("tree_nt", int(os.environ.get("PORESEG_TREE_NT", "256")))
+        ctx.set_tiling(0, 0)
+        ctx.set_option("stitch_host", int(os.environ.get("PORESEG_STITCH") == "host"))
+    np.testing.assert_array_equal(_bounds(segs), npz()[name + "/bounds"])
+
+
 def test_event_detector_kernel_matches_reference_parsers_py(ctx):
     """K3: ps_detect_events against the events the reference's own lambda_event_parser found (G6) and
     against the oracle on a longer file-shaped trace; fp32 and int16 inputs."""
@@ -671,7 +699,9 @@ def test_large_dc_offset_on_a_fine_grid(ctx):
         assert ctx.timings()["wide_redo"] == 0
 
 
-@pytest.mark.parametrize("option,value,default", [("groups", 0, 1), ("tree_par", 0, 1), ("k0_waves", 2, 0), ("k0_waves", 1, 0)])
+@pytest.mark.parametrize("option,value,default", [("groups", 0, 1), ("tree_par", 0, 1), ("k0_waves", 2, 0), ("k0_waves", 1, 0),
+                                                  ("tree_mw", 1, 0), ("gather_fused", 0, 1), ("download_by_kernel", 0, 1),
+                                                  ("upload_by_kernel", 0, 1)])
 def test_round4_options_change_no_result(ctx, option, value, default):
     """The switches of round 4 -- the coarse pass over the group records, the deep subtree jobs shared by the waves of a
     workgroup, K0's occupancy cap -- are tuning knobs: same boundaries with each of them off, on the narrow digest (dense
