@@ -1,12 +1,14 @@
 """Test-side oracle for pypore_amd.hmm: a plain numpy log-space dynamic programme with the device's tie rule (in-edges
 in ascending source index, a strictly greater score wins, so the lowest source wins a tie), and a brute-force enumerator
 over every state path for tiny models.  Reads only a baked model's `states`, `edges`, `start`, `end` and `finite`, and
-computes the emission densities from the distributions' parameters itself."""
+computes the emission densities from the distributions' parameters itself.  Beside it `viterbi_exact`, which restates the
+device's Viterbi operation by operation on the uploaded arrays (model.flat) and so gives the device's bits: the yardstick
+of tests/test_viterbi_exact_gpu.py, itself checked against the numpy programme in tests/test_viterbi_exact_host.py."""
 import math
 
 import numpy as np
 
-from pypore_amd.hmm import Model, NormalDistribution, State, UniformDistribution
+from pypore_amd.hmm import GaussianKernelDensity, Model, NormalDistribution, State, UniformDistribution
 
 NEG = -np.inf
 
@@ -160,34 +162,146 @@ def backward(c, seq):
     return B
 
 
-def viterbi(c, seq):
-    """(logp, path as state indices or None, margin): margin = the smallest relative gap between the winner and the
-    runner-up over the decisions on the winning path (inf when there was no alternative)."""
+def viterbi_ties(c, seq, flip_near=False):
+    """(logp, path as state indices or None, gap, ties, tied): the decisions on the winning path, told apart by kind.
+    A decision is the choice among one state's in-edge candidates (or, for an infinite model, among the entries of the
+    last row).  gap = the smallest NON-ZERO relative gap between a decision's winner and its best candidate that scores
+    strictly less (inf when there is none); ties = the number of decisions where a second candidate equals the winner
+    exactly; tied = those decisions as a sorted list of (t, state), the last row's as (n + 1, -1).
+    flip_near: at every in-edge decision whose best lesser candidate lies within 1e-9 relative of the winner -- a near tie,
+    which another arithmetic may decide the other way -- the traceback follows that candidate instead: the other path."""
     seq = np.asarray(seq, dtype=np.float64)
     F, bp = _forward_like(c, seq, True)
     n = seq.size
     logp, k = final(c, F[n], True)
     if not logp > NEG:
-        return NEG, None, np.inf
-    margin = np.inf
+        return NEG, None, np.inf, 0, []
+    gap, tied = np.inf, []
 
-    def note(best, cands):
-        nonlocal margin
-        rest = sorted(cands, reverse=True)
-        if len(rest) > 1 and rest[1] > NEG:
-            margin = min(margin, (rest[0] - rest[1]) / max(1.0, abs(best)))
+    def note(cands, where):
+        """the ordinal of the best lesser candidate when it is a near tie, else None"""
+        nonlocal gap
+        best = max(cands)
+        if sum(1 for v in cands if v == best) > 1:
+            tied.append(where)
+        below = [v for v in cands if NEG < v < best]
+        if below:
+            g = (best - max(below)) / max(1.0, abs(best))
+            gap = min(gap, g)
+            if g <= 1e-9:
+                return cands.index(max(below))
+        return None
 
     if not c.finite:
-        note(logp, list(F[n]))
+        note([float(v) for v in F[n]], (n + 1, -1))
     path, t = [k], n
     while not (t == 0 and k == c.start):
         src_t = t - 1 if k < c.NE else t
-        cands = [F[src_t][i] + w for i, w in c.ins[k]]
-        note(max(cands), cands)
-        j = c.ins[k][bp[t, k]][0]
+        near = note([float(F[src_t][i] + w) for i, w in c.ins[k]], (t, k))
+        j = c.ins[k][near if (flip_near and near is not None) else bp[t, k]][0]
         t, k = src_t, j
         path.append(k)
-    return logp, path[::-1], margin
+    return logp, path[::-1], gap, len(tied), sorted(tied)
+
+
+def viterbi(c, seq):
+    """(logp, path as state indices or None, margin): margin = the smallest relative gap between the winner and the
+    runner-up over the decisions on the winning path (inf when there was no alternative; 0.0 at an exact tie)."""
+    logp, path, gap, ties, _ = viterbi_ties(c, seq)
+    return logp, path, (0.0 if ties else gap)
+
+
+def viterbi_exact(model, seq):
+    """The device's Viterbi (csrc/seg_hmm.hpp hmm_fwd_kernel<HMM_VITERBI>, hmm_trace_kernel) restated operation by
+    operation in plain Python floats, which are IEEE fp64 and never fuse a multiply-add, on the uploaded numbers themselves
+    (model.flat: param, kind, in_ptr / in_src / in_lp, level_ptr, start, end, finite, and the kde_* tables).  Every
+    operation is an fp64 addition, subtraction, multiplication or comparison in the device's order, so the results are the
+    device's bit for bit:
+      * an emitting state at step t >= 1 scans its in-edges over row t-1 in ordinal order from -inf, replacing on a
+        strictly greater score, then takes  best + emission  where best > -inf, else -inf;
+      * the silent states of row t go level by level over row t; `start` at t = 0 begins from 0.0;
+      * emissions: normal  c - (d*d)*b;  uniform  c  inside [low, high], else -inf;  a kernel density of exactly one point
+        c + (lw - (d*d)*b)  (HmmLse of one term returns  m + log1p(0) = m).  A kernel density of any other number of
+        points raises ValueError: it goes through exp and log1p, which are not reproducible bit for bit;
+      * the result is row[n][end] (finite) or the largest entry of row n, the lowest index on a tie (infinite).
+    Returns (logp, path as state indices or None, the (n+1) x S score matrix, ties, other):  ties = the number of decisions
+    on the winning path (final row included) where a second candidate equalled the winner;  other = the path under the
+    opposite rule -- the LAST candidate wins a tie, the HIGHEST state wins in the final row -- which has the same scores."""
+    f = model.flat
+    S, NE, start, end = f["n_states"], f["n_emit"], f["start"], f["end"]
+    param, kind = f["param"].tolist(), f["kind"].tolist()
+    in_ptr, in_src, in_lp = f["in_ptr"].tolist(), f["in_src"].tolist(), f["in_lp"].tolist()
+    level_ptr = f["level_ptr"].tolist()
+    kde_ptr, kde_pt, kde_lw = f["kde_ptr"].tolist(), f["kde_pt"].tolist(), f["kde_lw"].tolist()
+    for k in range(NE):
+        if kind[k] == 3 and kde_ptr[k + 1] - kde_ptr[k] != 1:
+            raise ValueError("state %d is a kernel density of %d points: only one point is exact" % (k, kde_ptr[k + 1] - kde_ptr[k]))
+    xs = [float(v) for v in np.asarray(seq, dtype=np.float64).reshape(-1)]
+    n = len(xs)
+    ninf = float("-inf")
+
+    def emit(k, x):
+        a, b, c = param[3 * k], param[3 * k + 1], param[3 * k + 2]
+        if kind[k] == 1:
+            d = x - a
+            return c - (d * d) * b
+        if kind[k] == 2:
+            return c if (x >= a and x <= b) else ninf
+        d = x - kde_pt[kde_ptr[k]]
+        return c + (kde_lw[kde_ptr[k]] - (d * d) * b)
+
+    def scan(row, k, best):
+        """(best, ordinal of the first candidate that reached it, of the last, how many reached it)"""
+        first = last = 0
+        cnt = 1 if best > ninf else 0
+        e0 = in_ptr[k]
+        for o in range(in_ptr[k + 1] - e0):
+            v = row[in_src[e0 + o]] + in_lp[e0 + o]
+            if v > best:
+                best, first, last, cnt = v, o, o, 1
+            elif v == best and v > ninf:
+                last, cnt = o, cnt + 1
+        return best, first, last, cnt
+
+    F, first, last, count = [], [], [], []
+    for t in range(n + 1):
+        row, bf, bl, bc = [ninf] * S, [0] * S, [0] * S, [0] * S
+        if t > 0:
+            prev, x = F[t - 1], xs[t - 1]
+            for k in range(NE):
+                best, bf[k], bl[k], bc[k] = scan(prev, k, ninf)
+                row[k] = best + emit(k, x) if best > ninf else ninf
+        for L in range(len(level_ptr) - 1):
+            for k in range(level_ptr[L], level_ptr[L + 1]):
+                row[k], bf[k], bl[k], bc[k] = scan(row, k, 0.0 if (t == 0 and k == start) else ninf)
+        F.append(row)
+        first.append(bf)
+        last.append(bl)
+        count.append(bc)
+
+    mat = np.array(F, np.float64).reshape(n + 1, S)
+    if f["finite"]:
+        logp, k_lo, k_hi, final_ties = F[n][end], end, end, 0
+    else:
+        logp = max(F[n])
+        at = [k for k in range(S) if F[n][k] == logp]
+        k_lo, k_hi, final_ties = at[0], at[-1], int(len(at) > 1)
+    if not logp > ninf:
+        return ninf, None, mat, 0, None
+
+    def trace(bp, k):
+        t, path, ties = n, [k], 0
+        while not (t == 0 and k == start):
+            ties += count[t][k] > 1
+            e = in_ptr[k] + bp[t][k]
+            if k < NE:
+                t -= 1
+            k = in_src[e]
+            path.append(k)
+        return path[::-1], ties
+
+    path, ties = trace(first, k_lo)
+    return logp, path, mat, ties + final_ties, trace(last, k_hi)[0]
 
 
 def path_score(c, seq, path):
@@ -349,14 +463,16 @@ def line_model(S):
     return m
 
 
-def profile_model(n=54, seed=0, name="profile"):
+def profile_model(n=54, seed=0, name="profile", kde=False):
     """A global profile HMM like the reference tutorial's: per position a match (normal), an insert (uniform over the
-    current range) and a silent delete; 3n + 1 + 2 states (n = 54: 165)."""
+    current range) and a silent delete; 3n + 1 + 2 states (n = 54: 165).  kde: every match state is the one-point kernel
+    density GaussianKernelDensity([mean], std) instead, the same density through the kernel-density code."""
     rng = np.random.default_rng(seed)
     means = rng.uniform(20, 60, n)
     m = Model(name)
     insert = lambda i: State(UniformDistribution(0, 90), "I:%d" % i)           # noqa: E731
-    M = [State(NormalDistribution(float(means[i]), float(rng.uniform(0.8, 2.0))), "M:%d" % (i + 1)) for i in range(n)]
+    match = (lambda mean, std: GaussianKernelDensity([mean], std)) if kde else NormalDistribution
+    M = [State(match(float(means[i]), float(rng.uniform(0.8, 2.0))), "M:%d" % (i + 1)) for i in range(n)]
     I = [insert(i) for i in range(n + 1)]                                      # noqa: E741
     D = [State(None, "D:%d" % (i + 1)) for i in range(n)]
     m.add_transition(m.start, M[0], 0.90)
@@ -381,6 +497,49 @@ def profile_model(n=54, seed=0, name="profile"):
             m.add_transition(D[i], D[i + 1], 0.40)
     m.bake()
     return m, means
+
+
+def hub_model(n_in, shared=None):
+    """A hub state h with n_in in-edges: from the emitting states e0000 .. (self-loop of h last, since the emitting
+    states sort by name); `end` has n_in in-edges too.  start -> every e, e -> h or end, h -> h, any e or end.  The e
+    levels lie 3 apart at std 0.5, h's far below, so an observation names its state and the Viterbi path its in-edges.
+    shared = (lo, hi): e<hi> takes e<lo>'s distribution object, so the two hold the same bits wherever both are entered
+    and h's in-edges of ordinals lo and hi tie.  Returns (model, h, [e states])."""
+    m = Model("hub")
+    h = State(NormalDistribution(-50.0, 1.0), "h")
+    es = [State(NormalDistribution(3.0 * i, 0.5), "e%04d" % i) for i in range(n_in - 1)]
+    if shared is not None:
+        es[shared[1]].distribution = es[shared[0]].distribution
+    for e in es:
+        m.add_transition(m.start, e, 1.0)
+        m.add_transition(e, h, 0.8)
+        m.add_transition(e, m.end, 0.2)
+        m.add_transition(h, e, 0.4 / len(es))
+    m.add_transition(h, h, 0.4)
+    m.add_transition(h, m.end, 0.2)
+    m.bake()
+    return m, h, es
+
+
+def chain_model(n_chain):
+    """An emitting state a whose only way back to itself is a chain of n_chain silent states: every observation after the
+    first adds n_chain + 1 entries to the Viterbi path."""
+    m = Model("loop")
+    a = State(NormalDistribution(0.0, 1.0), "a")
+    b = State(NormalDistribution(2.0, 1.0), "b")
+    chain = [State(None, "c%02d" % i) for i in range(n_chain)]
+    m.add_transition(m.start, a, 0.7)
+    m.add_transition(m.start, b, 0.3)
+    m.add_transition(a, chain[0], 0.8)
+    m.add_transition(a, m.end, 0.2)
+    for x, y in zip(chain[:-1], chain[1:]):
+        m.add_transition(x, y, 1.0)
+    m.add_transition(chain[-1], a, 1.0)
+    m.add_transition(b, b, 0.5)
+    m.add_transition(b, chain[0], 0.3)
+    m.add_transition(b, m.end, 0.2)
+    m.bake()
+    return m
 
 
 def profile_events(means, count, lo=50, hi=400, seed=1):

@@ -386,18 +386,59 @@ def follow_local(master, slave, names):
             break
 
 
-def align(master, slave, mode="global", low=0, high=60, bandwidth=1):
-    """(prob, master Pssm, slave Pssm, Viterbi margin) by the oracle's Viterbi; (-inf, None, None, inf) when impossible.
-    master / slave: Pssm objects or what Pssm takes."""
+class CompiledLongDouble(Compiled):
+    """The same view with every kernel-density emission taken from kde_logpdf_longdouble and rounded to double: other bits
+    than the float64 formula's wherever its exp / log1p rounded, so a tie that survives the change owes nothing to them."""
+
+    def emissions(self, x):
+        memo = self.__dict__.setdefault("_emissions", {})
+        key = float(x)
+        if key not in memo:
+            out = []
+            with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+                for k in range(self.NE):
+                    d = self.states[k].distribution
+                    if type(d).__name__ == "GaussianKernelDensity":
+                        v = float(kde_logpdf_longdouble(d.parameters[0], d.parameters[1], d.parameters[2], x))
+                        out.append(v if v == v else NEG)
+                    else:
+                        out.append(O.emission(self.states[k], x))
+            memo[key] = np.array(out)
+        return memo[key].copy()
+
+
+def viterbi_structural(model, seq, flip_near=False):
+    """(logp, path, gap, ties, structural) of O.viterbi_ties on Compiled(model).  structural: every exact tie on the winning
+    path has identical operands on both sides -- judged by running the same Viterbi again with the kernel-density
+    emissions from long double (CompiledLongDouble): the winning path and the set of tied decisions are unchanged.  A
+    device whose exp / log1p differ from numpy's by ulps then ties at the same decisions.  True when there is no tie.
+    flip_near: the path that takes the other side of every near tie (O.viterbi_ties); structural is then not judged (None)."""
+    logp, path, gap, ties, tied = O.viterbi_ties(Compiled(model), seq, flip_near)
+    if flip_near:
+        return logp, path, gap, ties, None
+    if not ties:
+        return logp, path, gap, ties, True
+    _, path2, _, _, tied2 = O.viterbi_ties(CompiledLongDouble(model), seq)
+    return logp, path, gap, ties, path2 == path and tied2 == tied
+
+
+def align_ties(master, slave, mode="global", low=0, high=60, bandwidth=1, flip_near=False):
+    """(prob, master Pssm, slave Pssm, gap, ties, structural) by the oracle's Viterbi (viterbi_structural);
+    (-inf, None, None, inf, 0, True) when impossible.  master / slave: Pssm objects or what Pssm takes."""
     master = master if isinstance(master, Pssm) else Pssm(master)
     slave = slave if isinstance(slave, Pssm) else Pssm(slave)
     model = (build_global if mode == "global" else build_local)(master, low, high, bandwidth)
-    c = Compiled(model)
-    prob, path, margin = O.viterbi(c, slave.consensus)
+    prob, path, gap, ties, structural = viterbi_structural(model, slave.consensus, flip_near)
     if path is None:
-        return NEG, None, None, np.inf
-    (follow_global if mode == "global" else follow_local)(master, slave, [c.states[k].name for k in path])
-    return prob, master, slave, margin
+        return NEG, None, None, np.inf, 0, True
+    (follow_global if mode == "global" else follow_local)(master, slave, [model.states[k].name for k in path])
+    return prob, master, slave, gap, ties, structural
+
+
+def align(master, slave, mode="global", low=0, high=60, bandwidth=1):
+    """(prob, master Pssm, slave Pssm, Viterbi margin): align_ties with the margin 0.0 at an exact tie."""
+    prob, master, slave, gap, ties, _ = align_ties(master, slave, mode, low, high, bandwidth)
+    return prob, master, slave, (0.0 if ties else gap)
 
 
 def msa_score(msa):
@@ -410,21 +451,25 @@ def msa_score(msa):
     return total
 
 
-def msa_initialization(sequences, bandwidth=1):
-    """alignment.py:790-796: (score, msa, smallest Viterbi margin met)."""
-    pssm, worst = Pssm(sequences[0]), np.inf
+def msa_iterative_ties(sequences, epsilon=1e-4, max_iterations=10, bandwidth=1, flip_near=False):
+    """alignment.py:790-796 and :743-782: (score of the last trial, best msa, smallest non-zero Viterbi gap met, exact ties
+    met, whether all of them were structural).  flip_near: every alignment takes the other side of its near ties
+    (O.viterbi_ties), the outcome of an arithmetic that decides them the other way; structural is then None."""
+    worst, ties, structural = np.inf, 0, (None if flip_near else True)
+
+    def one(master, slave):
+        nonlocal worst, ties, structural
+        _, x, y, gap, t, s = align_ties(master, slave, bandwidth=bandwidth, flip_near=flip_near)
+        worst, ties, structural = min(worst, gap), ties + t, (None if flip_near else structural and s)
+        return x, y
+
+    pssm = Pssm(sequences[0])
     for seq in sequences[1:]:
-        _, master, slave, margin = align(pssm, seq, bandwidth=bandwidth)
-        worst = min(worst, margin)
+        master, slave = one(pssm, seq)
         pssm = Pssm(master.msa + slave.msa)
-    return msa_score(pssm.msa), pssm.msa, worst
-
-
-def msa_iterative(sequences, epsilon=1e-4, max_iterations=10, bandwidth=1):
-    """alignment.py:743-782: (score of the last trial, best msa, smallest Viterbi margin met)."""
-    score, msa, worst = msa_initialization(sequences, bandwidth)
+    score, msa = msa_score(pssm.msa), pssm.msa
     if score == 0:
-        return 0, msa, worst
+        return 0, msa, worst, ties, structural
     n = len(msa)
     last_score, best_msa, best_score, iteration = float('inf'), msa, score, 0
     while abs(best_score - last_score) >= epsilon and iteration < max_iterations:
@@ -433,8 +478,7 @@ def msa_iterative(sequences, epsilon=1e-4, max_iterations=10, bandwidth=1):
         for i in range(n):
             slave = [x for x in best_msa[i] if not is_gap(x)]
             master = best_msa[:i] + best_msa[i + 1:]
-            _, x, y, margin = align(master, slave, bandwidth=bandwidth)
-            worst = min(worst, margin)
+            x, y = one(master, slave)
             msa = x.msa + y.msa
             score = msa_score(msa)
             if score < best_score:
@@ -442,7 +486,13 @@ def msa_iterative(sequences, epsilon=1e-4, max_iterations=10, bandwidth=1):
     m = max(len(s) for s in best_msa)
     for seq in best_msa:
         seq.extend(['-'] * (m - len(seq)))
-    return score, best_msa, worst
+    return score, best_msa, worst, ties, structural
+
+
+def msa_iterative(sequences, epsilon=1e-4, max_iterations=10, bandwidth=1):
+    """(score of the last trial, best msa, smallest Viterbi margin met: 0.0 at an exact tie)."""
+    score, msa, worst, ties, _ = msa_iterative_ties(sequences, epsilon, max_iterations, bandwidth)
+    return score, msa, (0.0 if ties else worst)
 
 
 def derived_sequences(rng, columns, rows, noise=0.8, p_del=0.08, p_ins=0.08, lo=5.0, hi=55.0):

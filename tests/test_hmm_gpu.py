@@ -216,22 +216,7 @@ def test_parse_with_hmm_and_experiment_apply_hmm_end_to_end():
 # ---- launch shapes of ps_hmm_batch ----------------------------------------------------------------------------------
 
 
-def _hub_model(n_in):
-    """A hub state h with n_in in-edges: from the emitting states e0000 .. (self-loop of h last, since the emitting
-    states sort by name); `end` has n_in in-edges too.  start -> every e, e -> h or end, h -> h, any e or end.  The e
-    levels lie 3 apart at std 0.5, h's far below, so an observation names its state and the Viterbi path its in-edges."""
-    m = Model("hub")
-    h = State(NormalDistribution(-50.0, 1.0), "h")
-    es = [State(NormalDistribution(3.0 * i, 0.5), "e%04d" % i) for i in range(n_in - 1)]
-    for e in es:
-        m.add_transition(m.start, e, 1.0)
-        m.add_transition(e, h, 0.8)
-        m.add_transition(e, m.end, 0.2)
-        m.add_transition(h, e, 0.4 / len(es))
-    m.add_transition(h, h, 0.4)
-    m.add_transition(h, m.end, 0.2)
-    m.bake()
-    return m, h, es
+_hub_model = O.hub_model                  # (model, h, [e states]); shared with tests/viterbi_ties.py
 
 
 def _hub_seqs(rng, es, winners):
@@ -299,25 +284,7 @@ def test_in_degree_600_under_a_small_backpointer_budget():
         check_viterbi(c, s, b)
 
 
-def _chain_model(n_chain):
-    """An emitting state a whose only way back to itself is a chain of n_chain silent states: every observation after the
-    first adds n_chain + 1 entries to the Viterbi path."""
-    m = Model("loop")
-    a = State(NormalDistribution(0.0, 1.0), "a")
-    b = State(NormalDistribution(2.0, 1.0), "b")
-    chain = [State(None, "c%02d" % i) for i in range(n_chain)]
-    m.add_transition(m.start, a, 0.7)
-    m.add_transition(m.start, b, 0.3)
-    m.add_transition(a, chain[0], 0.8)
-    m.add_transition(a, m.end, 0.2)
-    for x, y in zip(chain[:-1], chain[1:]):
-        m.add_transition(x, y, 1.0)
-    m.add_transition(chain[-1], a, 1.0)
-    m.add_transition(b, b, 0.5)
-    m.add_transition(b, chain[0], 0.3)
-    m.add_transition(b, m.end, 0.2)
-    m.bake()
-    return m
+_chain_model = O.chain_model
 
 
 def test_viterbi_path_longer_than_its_slot():

@@ -281,9 +281,13 @@ def test_bad_kernel_density_tables_are_refused():
 
 
 # ---- the aligners end to end -----------------------------------------------------------------------------------------------------
-# seeds chosen on the CPU with tests/profile_oracle.py alone (P.alignment_case; margins of the oracle's Viterbi): none of
-# their global or local alignments has a winning margin <= 1e-9, so every case below compares whole alignments
-ALIGN_SEEDS = [0, 1, 2, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 16, 17, 18, 19, 20, 21]      # (3 and 15 have exact ties)
+# P.alignment_case(0..21), every seed: P.align_ties gives per alignment the smallest NON-ZERO gap on the winning path, the
+# number of exact ties there and whether those are structural (identical operands on both sides: the device, whose exp and
+# log1p round differently, ties too, and the shared rule -- lowest source -- picks the same path).  An alignment whose
+# non-zero gaps all exceed 1e-9 and whose ties are structural compares whole alignments; any other is only counted.  On the
+# CPU (tests/test_viterbi_exact_host.py): seed 3 meets 1 and seed 15 meets 2 alignments with an exact tie, all structural,
+# no non-zero gap of the 176 alignments is below 2.1e-4, so the oracle leaves out 0 of 176 (0 of the 220 cases below).
+ALIGN_SEEDS = list(range(22))
 MAX_TIE_SHARE = 0.05
 
 
@@ -296,16 +300,16 @@ def test_profile_aligner_and_batch_end_to_end():
     for seed in ALIGN_SEEDS:
         msa, slaves = P.alignment_case(seed)
         for mode in ("global", "local"):
-            want = [P.align(copy.deepcopy(msa), list(s), mode) for s in slaves]
+            want = [P.align_ties(copy.deepcopy(msa), list(s), mode) for s in slaves]
             pa = A.ProfileAligner(copy.deepcopy(msa), list(slaves[0]))
             single = pa.global_alignment() if mode == "global" else pa.local_alignment()
             master = copy.deepcopy(msa)
             batch = A.profile_align_batch(master, [list(s) for s in slaves], mode)
             assert master == P.Pssm(copy.deepcopy(msa)).msa                        # all-gap columns deleted, nothing else
-            for got, (prob, wm, ws, margin) in zip([single] + batch, [want[0]] + want):
+            for got, (prob, wm, ws, gap, exact, structural) in zip([single] + batch, [want[0]] + want):
                 cases += 1
                 assert_close([got[0]], [prob])
-                if margin > 1e-9:
+                if gap > 1e-9 and structural:
                     assert same_profile(got[1], wm) and same_profile(got[2], ws)
                 else:
                     ties += 1
@@ -327,19 +331,29 @@ def test_impossible_slave_and_repeat_alignment():
     assert margin <= 1e-9 or names == [c.states[k].name for k in path[1:-1]]
 
 
-MSA_SEEDS = [1, 2, 4, 5]                                                       # (0 and 3 meet exact ties)
+# Seeds 1, 2, 4, 5 meet no exact tie and no non-zero gap below 1e-2.  Seed 3 meets 1 exact tie, structural.  Seeds 0 and 3
+# each meet one decision whose two candidates are the same sum added in two orders and differ by one ulp (relative gaps
+# 1.4e-16 and 2.8e-16; M11 entered from I10 or D10).  That is rounding, not structure -- seed 0 never met an exact tie --
+# so a device whose emissions differ by ulps may take either side.  The oracle therefore solves these seeds twice, the
+# second time taking the other side of every near tie (flip_near), and the device must return one of the two outcomes,
+# alignment and score.  (Seed 0: both sides give the same alignment, the near-tie trial is not the one kept; seed 3: two.)
+MSA_SEEDS = [0, 1, 2, 3, 4, 5]
+MSA_NEAR_TIE_SEEDS = (0, 3)
 
 
 @pytest.mark.parametrize("seed", MSA_SEEDS)
 def test_multiple_sequence_aligner_end_to_end(seed):
     rng = np.random.default_rng(700 + seed)
     _, seqs = P.derived_sequences(rng, int(rng.integers(6, 16)), int(rng.integers(3, 7)))
-    want_score, want_msa, margin = P.msa_iterative(copy.deepcopy(seqs), max_iterations=3)
-    assert margin > 1e-9                                                       # (seeds chosen so on the CPU)
+    want_score, want_msa, gap, exact, structural = P.msa_iterative_ties(copy.deepcopy(seqs), max_iterations=3)
+    assert structural and (gap > 1e-9) == (seed not in MSA_NEAR_TIE_SEEDS)     # (found so on the CPU)
+    outcomes = [(want_score, want_msa)]
+    if not gap > 1e-9:
+        outcomes.append(P.msa_iterative_ties(copy.deepcopy(seqs), max_iterations=3, flip_near=True)[:2])
     score, msa = A.MultipleSequenceAligner(copy.deepcopy(seqs)).iterative_alignment(max_iterations=3)
     assert len({len(r) for r in msa}) == 1
     assert sorted([x for x in r if x != '-'] for r in msa) == sorted(seqs)
-    assert msa == want_msa and abs(score - want_score) <= TOL * max(1.0, abs(want_score))
+    assert any(msa == m and abs(score - sc) <= TOL * max(1.0, abs(sc)) for sc, m in outcomes)
 
 
 def test_profile_above_the_state_cap():
