@@ -1,7 +1,9 @@
 """Hidden Markov models with the surface the reference's HMM code uses (yahmm: Model, State, NormalDistribution,
-UniformDistribution, GaussianKernelDensity; add_state(s), add_transition, add_model, bake; viterbi, forward, backward, log_probability,
-forward_backward, maximum_a_posteriori), decoded on the MI355X (ps_hmm_batch, ps_hmm_posterior, csrc/seg_hmm.hpp), and trained there (Model.train: Baum-Welch with its E-step in ps_hmm_expect,
-or Viterbi training).
+UniformDistribution, GaussianKernelDensity; add_state(s), add_transition, add_model, bake; viterbi, forward, backward,
+log_probability, forward_backward, maximum_a_posteriori) and the reference's profile HMM builders (HMMBoard, the three
+board modules, ModularProfileModel, Phi29ProfileHMM, Hel308ProfileHMM: the end of this module), decoded on the MI355X
+(ps_hmm_batch, ps_hmm_posterior, csrc/seg_hmm.hpp), and trained there (Model.train: Baum-Welch with its E-step in
+ps_hmm_expect, or Viterbi training).
 
     model = Model("happy model")
     a = State(NormalDistribution(3, 4), 'a')
@@ -36,8 +38,17 @@ Deviations from yahmm, by design:
   * GaussianKernelDensity is normalised: it carries the 1/h factor above.  yahmm is not available to compare against; as
     far as is known its kernel density leaves 1/h out, which is the same density at bandwidth 1, the default and what
     every caller in the reference's alignment.py uses.  Nothing else about its arithmetic is assumed.
-  * bake(merge=...) is accepted and ignored: no states are merged.  yahmm may merge chains of probability-1 silent edges
-    and so drop those silent states from its paths; here every silent state visited appears in the path.
+  * bake(merge=...) merges nothing by default (None, 'none'); as far as is known yahmm's default is 'all'.  The default
+    differs so that a model baked without the argument keeps every silent state it was given, and its paths.  The rule,
+    in this package's own terms (yahmm is not available to compare against): with merge='all', repeat until no state
+    qualifies -- the first state a, in the order the states joined, that is silent, is neither start nor end, and has
+    exactly one out-edge of positive probability, a -> b with b != a, leaves the model with that edge, and every in-edge
+    x -> a becomes x -> b with its probability and pseudocount.  merge='partial' is the same with b silent as well.  Where
+    x -> b exists already the two are parallel edges and are summed (probability and pseudocount): forward, backward,
+    log_probability and the expected counts see the same total, so they stay as they were up to rounding, while Viterbi
+    now scores the two ways as one, the sum, and may give a higher score or another path.  Without parallel edges the
+    merged model's Viterbi path is the unmerged one with the removed states left out.  Merging rewrites the model's own
+    construction graph: train() trains the merged structure and a later bake() starts from it.
   * `end` is kept in model.states even when it cannot be reached (the model is then infinite).
   * Edges of probability 0 are dropped; negative probabilities raise ValueError.
 
@@ -51,7 +62,8 @@ length n with f, b and logp as above:
     bit for bit the sum one takes over `emissions`.  The MAP path need not be a path of the model: it maximises every
     observation's state on its own;
   * `transitions`[k][l] is the sequence's expected count of edge k -> l by the formula under Training below, per
-    sequence instead of summed over the batch, 0 where the model has no such edge;
+    sequence instead of summed over the batch, 0 where the model has no such edge; expected_transitions(_batch) returns
+    the same counts as one row per sequence in the order of `edges`, without the dense array;
   * an impossible sequence (logp = -inf) has emissions -inf, transitions 0 and MAP result (-inf, None); an empty one has
     no rows, MAP result (0.0, []), and its transitions hold the silent edges at t = 0.
 Nothing is summed across sequences, so a batch gives the bits of the single calls however the library cuts it.
@@ -297,7 +309,13 @@ class Model(object):
         """Normalises each state's out-edges to sum to 1, drops the states `start` cannot reach (never `end`), rejects a
         cycle of silent states (ValueError), orders `states` -- emitting states by name (stable), then silent states in
         topological order (by level, then in the order they joined) -- and compiles the flat form the device reads.
-        `merge` is accepted and ignored (module docstring)."""
+        merge: None / 'none' (the default: nothing is merged), 'partial' or 'all' (any letter case): silent states with one
+        way out are folded into their successor first (_merge_silent, module docstring); anything else raises ValueError."""
+        mode = "none" if merge is None else str(merge).lower()
+        if mode not in ("none", "partial", "all"):
+            raise ValueError("merge must be None, 'none', 'partial' or 'all', got %r" % (merge,))
+        if mode != "none":
+            self._merge_silent(mode == "partial")
         out = collections.OrderedDict((id(s), []) for s in self._added)
         for (a, b), p in self._edges.items():
             if p > 0:
@@ -366,6 +384,46 @@ class Model(object):
             out_dst=np.ascontiguousarray(dst[by_src]), out_lp=np.ascontiguousarray(lp[by_src]), **kde)
         self._in_order = by_dst                         # edges (= out-edge order) -> in-edge order
         self._c = None
+
+    def _merge_silent(self, silent_only):
+        """bake(merge='partial' | 'all'): rewrites the construction graph (_added, _edges, _pseudo).  Repeated until no
+        state qualifies: the first state a, in joining order, that is silent, neither start nor end, and has exactly one
+        out-edge of positive probability, a -> b with b != a (silent_only: b silent as well), leaves the model; every
+        in-edge x -> a becomes x -> b, its probability and pseudocount added to an x -> b already there."""
+        pos = {s: i for i, s in enumerate(self._added)}
+        succ = {s: collections.OrderedDict() for s in self._added}      # out-edges, those of probability 0 too
+        pred = {s: collections.OrderedDict() for s in self._added}
+        for a, b in self._edges:
+            succ[a][b] = pred[b][a] = None
+        gone = set()
+        i = 0
+        while i < len(self._added):
+            a = self._added[i]
+            i += 1
+            if a in gone or not a.is_silent() or a is self.start or a is self.end:
+                continue
+            live = [b for b in succ[a] if self._edges[(a, b)] > 0]
+            if len(live) != 1 or live[0] is a or (silent_only and not live[0].is_silent()):
+                continue
+            b = live[0]
+            for x in pred[a]:
+                p, c = self._edges.pop((x, a)), self._pseudo.pop((x, a), None)
+                del succ[x][a]
+                if x is a:
+                    continue
+                c = p if c is None else c
+                if (x, b) in self._edges:
+                    c += self._pseudo.get((x, b), self._edges[(x, b)])
+                    p += self._edges[(x, b)]
+                self._edges[(x, b)], self._pseudo[(x, b)] = p, c
+                succ[x][b] = pred[b][x] = None
+                i = min(i, pos[x])                       # x may qualify now: the scan goes back to it
+            for y in succ[a]:
+                del self._edges[(a, y)], pred[y][a]
+                self._pseudo.pop((a, y), None)
+            gone.add(a)
+        self._added = [s for s in self._added if s not in gone]
+        self._known = {id(s) for s in self._added}
 
     @staticmethod
     def _emission_tables(emitting, S):
@@ -509,8 +567,20 @@ class Model(object):
             out.append((transitions, post[off[q]:off[q + 1]]))
         return out
 
+    def expected_transitions_batch(self, sequences, device=None):
+        """float64 [n_seq, len(edges)]: every sequence's expected count of every edge, in the order of `edges` -- the
+        numbers forward_backward_batch scatters into its dense arrays, from one ps_hmm_posterior call that asks for the
+        counts alone (no posterior matrix on the device, no states x states array here).  An impossible sequence has a row
+        of zeros."""
+        ctx, off, obs = self._upload(sequences, device)
+        _, _, _, _, counts = ctx.hmm_posterior(self._c_model(), obs, off, want_post=False, want_map=False, want_counts=True)
+        return counts.cpu().numpy()
+
     def maximum_a_posteriori(self, sequence):
         return self.maximum_a_posteriori_batch([sequence])[0]
+
+    def expected_transitions(self, sequence):
+        return self.expected_transitions_batch([sequence])[0]
 
     def forward_backward(self, sequence):
         return self.forward_backward_batch([sequence])[0]
@@ -688,3 +758,256 @@ class Model(object):
 
 
 Expectations = collections.namedtuple("Expectations", "counts stats logp skipped")
+
+
+# ---- the reference's profile HMM builders (PyPore/hmm.py) -------------------------------------------------------------
+# A board is an unbaked Model with n lanes: silent ports s1..sn on its left and e1..en on its right.  A lane of direction
+# '>' runs from the previous board's e port into this board's s port, a lane '<' from this board's s port back into the
+# previous board's e port.  Each module below is a table of (from, to, probability) read by _wire; the keys name the
+# board's ports and the module's own states.
+class HMMBoard(Model):
+    """A Model "Board {name}" with silent ports s1..sn and e1..en (attributes; named b{name}s{i} and b{name}e{i}),
+    `n`, and `directions`, '>' for every lane until the module says otherwise."""
+
+    def __init__(self, n, name=None):
+        Model.__init__(self, name="Board {}".format(name))
+        self.directions = ['>'] * n
+        self.n = n
+        for i in range(1, n + 1):
+            for side in "se":
+                port = State(None, name="b{}{}{}".format(name, side, i))
+                setattr(self, "{}{}".format(side, i), port)
+                self.add_state(port)
+
+
+def _wire(board, states, table):
+    """add_transition for every row of a module's table; a key is a port of the board or a key of `states`."""
+    def find(key):
+        return states[key] if key in states else getattr(board, key)
+    for a, b, p in table:
+        board.add_transition(find(a), find(b), p)
+    return board
+
+
+_GLOBAL_TABLE = (
+    ("s1", "D", 1.00), ("s2", "M", 1.00),
+    ("M", "e2", 0.90), ("M", "e1", 0.05), ("M", "I", 0.05),
+    ("D", "I", 0.15), ("D", "e1", 0.15), ("D", "e2", 0.70),
+    ("I", "I", 0.70), ("I", "e1", 0.15), ("I", "e2", 0.15))
+
+_NANOPORE_TABLE = (
+    ("s1", "D", 1.0), ("s2", "M", 1.0), ("e3", "B", 1.0),
+    ("B", "M", 0.85), ("B", "s3", 0.15),
+    ("D", "e1", 0.1), ("D", "e2", 0.8), ("D", "I", 0.1),
+    ("M", "s3", 0.033), ("M", "M", 0.4), ("M", "e2", 0.5), ("M", "I", 0.033), ("M", "e1", 0.34),
+    ("I", "I", 0.50), ("I", "M", 0.20), ("I", "e1", 0.05), ("I", "e2", 0.25))
+
+_PHI29_MATCH_TABLE = (
+    ("start", "M", 0.95), ("start", "MO", 0.05),
+    ("M", "M", 0.10), ("M", "end", 0.90),
+    ("MO", "MO", 0.80), ("MO", "end", 0.20))
+
+_PHI29_TABLE = (
+    ("s1", "D", 1.00), ("s2", "M.start", 1.00), ("e3", "ME", 1.00), ("s4", "MS", 1.00),
+    ("e5", "M.start", 0.90), ("e5", "ME", 0.05), ("e5", "s5", 0.05),
+    ("D", "e1", 0.1), ("D", "I", 0.1), ("D", "e2", 0.8),
+    ("I", "M.start", 0.10), ("I", "I", 0.50), ("I", "e1", 0.05), ("I", "e2", 0.35),
+    ("M.end", "I", 0.01), ("M.end", "e1", 0.01), ("M.end", "e2", 0.97), ("M.end", "s5", 0.01),
+    ("MS", "s3", 0.80), ("MS", "MS", 0.20),
+    ("ME", "e2", 0.10), ("ME", "ME", 0.10), ("ME", "e4", 0.80))
+
+
+def GlobalAlignmentModule(distribution, name, insert):
+    """The repeating unit of a global alignment profile: two lanes (1 delete, 2 match), states D:, I: and M:."""
+    board = HMMBoard(2, name)
+    states = collections.OrderedDict((("D", State(None, name="D:{}".format(name))),
+                                      ("I", State(insert, name="I:{}".format(name))),
+                                      ("M", State(distribution, name="M:{}".format(name)))))
+    return _wire(board, states, _GLOBAL_TABLE)
+
+
+def NanoporeGlobalAlignmentModule(distribution, name, insert):
+    """The global alignment unit with a match self-loop, a way from the insert back to the match, and a third lane that
+    runs backwards through the silent backslip state B:."""
+    board = HMMBoard(3, name)
+    board.directions = ['>', '>', '<']
+    states = collections.OrderedDict((("I", State(insert, name="I:{}".format(name))),
+                                      ("M", State(distribution, name="M:{}".format(name))),
+                                      ("D", State(None, name="D:{}".format(name))),
+                                      ("B", State(None, name="B:{}".format(name)))))
+    return _wire(board, states, _NANOPORE_TABLE)
+
+
+def Phi29GlobalAlignmentModule(distribution, name, insert=UniformDistribution(0, 90)):
+    """One position of a Phi29 profile on five lanes: 1 delete and 2 match forwards, 3 and 5 backwards (backslips), 4
+    forwards again after a backslip.  The match is a sub-model of M: and MO: (an oversegmented match: a long self-loop);
+    MS: and ME: are the match entered on the way back and left on the way forward again; D: and I: as usual."""
+    match = Model(name=str(name))
+    inner = {"start": match.start, "end": match.end, "M": State(distribution, name="M:{}".format(name)),
+             "MO": State(distribution, name="MO:{}".format(name))}
+    match.add_states([inner["M"], inner["MO"]])
+    _wire(match, inner, _PHI29_MATCH_TABLE)
+
+    board = HMMBoard(n=5, name=str(name))
+    board.directions = ['>', '>', '<', '>', '<']
+    states = collections.OrderedDict((("D", State(None, name="D:{}".format(name))),
+                                      ("I", State(insert, name="I:{}".format(name))),
+                                      ("MS", State(distribution, name="MS:{}".format(name))),
+                                      ("ME", State(distribution, name="ME:{}".format(name)))))
+    board.add_model(match)
+    board.add_states(list(states.values()))
+    states["M.start"], states["M.end"] = match.start, match.end
+    return _wire(board, states, _PHI29_TABLE)
+
+
+def _join(model, left, right, forward, backward):
+    """Lane by lane: '>' is left.e_j -> right.s_j with probability `forward`, '<' is right.s_j -> left.e_j with `backward`."""
+    for j, d in zip(range(1, right.n + 1), right.directions):
+        e, s = getattr(left, "e%d" % j), getattr(right, "s%d" % j)
+        if d == '>':
+            model.add_transition(e, s, forward)
+        elif d == '<':
+            model.add_transition(s, e, backward)
+
+
+def ModularProfileModel(board_func, distributions, name, insert, merge=None):
+    """A profile HMM of one board per entry of `distributions`, chained port to port and baked with bake(merge=merge).  An
+    entry is a Distribution (board named by its 0-based position i) or a dict key -> Distribution, a fork: one board per
+    key, named "{key}:{i+1}", side by side.  Into a fork of n branches the '>' lanes split 1/n each and the '<' lanes
+    carry 1; out of it the '>' lanes carry 1 and the '<' lanes split 1/n; a fork after a fork joins equal keys.  Head:
+    I:0 (`insert`, self-loop 0.70) -> s1 0.1, s2 0.2 of the first board; start -> I:0 0.02, s1 0.08, s2 0.90.  Tail: e1 and
+    e2 of the last board -> end.  Every insert state shares the one `insert` object.  ValueError for an empty profile,
+    a fork in the first or last position, and consecutive forks with different key lists."""
+    distributions = list(distributions)
+    if not distributions:
+        raise ValueError("ModularProfileModel needs at least one distribution")
+    if isinstance(distributions[0], dict) or isinstance(distributions[-1], dict):
+        raise ValueError("a fork cannot be the first or the last position of a profile")
+    model = Model(name)
+    last = None                                            # the boards of the previous position
+    for i, entry in enumerate(distributions):
+        if isinstance(entry, Distribution):
+            boards = [board_func(entry, name=i, insert=insert)]
+        elif isinstance(entry, dict):
+            if not entry:
+                raise ValueError("position %d is a fork without branches" % i)
+            if isinstance(distributions[i - 1], dict) and list(distributions[i - 1]) != list(entry):
+                raise ValueError("consecutive forks need the same keys: %r at position %d, %r at %d"
+                                 % (list(distributions[i - 1]), i - 1, list(entry), i))
+            boards = [board_func(d, "{}:{}".format(key, i + 1), insert=insert) for key, d in entry.items()]
+        else:
+            raise TypeError("position %d holds neither a Distribution nor a dict: %r" % (i, entry))
+        for b, board in enumerate(boards):
+            model.add_model(board)
+            if last is None:
+                continue
+            if len(last) == len(boards):                   # board to board, or branch to the branch of the same key
+                _join(model, last[b], board, 1.00, 1.00)
+            elif len(last) == 1:                           # into a fork
+                _join(model, last[0], board, 1.00 / len(boards), 1.00)
+            else:                                          # out of a fork
+                for branch in last:
+                    _join(model, branch, board, 1.00, 1.00 / len(last))
+        last = boards
+        if i == 0:
+            first = boards[0]
+    head = State(insert, name="I:0")
+    model.add_state(head)
+    for a, b, p in ((head, head, 0.70), (head, first.s1, 0.1), (head, first.s2, 0.2),
+                    (model.start, head, 0.02), (model.start, first.s1, 0.08), (model.start, first.s2, 0.90),
+                    (last[0].e1, model.end, 1.00), (last[0].e2, model.end, 1.00)):
+        model.add_transition(a, b, p)
+    model.bake(merge=merge)
+    return model
+
+
+def _linear_profile(distributions, name, low, high, sb_length, lb_length, match_p, sb_p, delete_p):
+    """What Phi29ProfileHMM and Hel308ProfileHMM share, unbaked.  Per position i (named i + 1): a match sub-model M of two
+    states of the same name (plain, and oversegmented with a long self-loop), an insert I (uniform on [low, high], one
+    object for all), a silent delete D; from position sb_length on a silent short backslip S that goes back one match --
+    directly, or through a pair of repeat states (named as the two matches) that flicker between the two levels -- or on to
+    the S before it; from position lb_length on (lb_length not None) a silent long backslip L that goes lb_length matches
+    back or on to the L before it.  match_p(i): previous match -> this match; sb_p = (S -> previous match with and
+    without an S before it, S -> the repeat states); delete_p = (previous D -> this match, previous D -> this D)."""
+    distributions = list(distributions)
+    if not distributions:
+        raise ValueError("a profile needs at least one distribution")
+    if sb_length < 1 or (lb_length is not None and lb_length < 1):
+        raise ValueError("backslip lengths must be at least 1, got sb_length=%r%s"
+                         % (sb_length, "" if lb_length is None else ", lb_length=%r" % lb_length))
+    model = Model("{}-{}".format(name, len(distributions)))
+    insert_distribution = UniformDistribution(low, high)
+    add = model.add_transition
+    matches = []
+    last_out, last_insert = model.start, State(insert_distribution, name="I0")    # last_out: the previous match's way out
+    last_delete = last_sb = last_lb = None
+    add(model.start, last_insert, 0.02)
+    add(last_insert, last_insert, 0.70)
+    for i, distribution in enumerate(distributions):
+        label = "M" + str(i + 1)
+        match = Model(name=label)
+        plain, overseg = State(distribution, name=label), State(distribution, name=label)
+        for a, b, p in ((match.start, plain, 0.75), (match.start, overseg, 0.25), (plain, plain, 0.10),
+                        (plain, match.end, 0.90), (overseg, overseg, 0.80), (overseg, match.end, 0.20)):
+            match.add_transition(a, b, p)
+        insert = State(insert_distribution, name="I" + str(i + 1))
+        delete = State(None, name="D" + str(i + 1))
+        short = State(None, name="S" + str(i + 1)) if i >= sb_length else None
+        long_ = State(None, name="L" + str(i + 1)) if lb_length is not None and i >= lb_length else None
+        model.add_model(match)
+        add(last_out, match.start, match_p(i))
+        add(last_out, delete, 0.08 if i == 0 else 0.03)
+        add(match.end, insert, 0.02)
+        add(insert, insert, 0.75)
+        add(insert, match.start, 0.10)
+        add(last_insert, delete, 0.05)
+        add(last_insert, match.start, 0.10)
+        add(delete, insert, 0.10)
+        if short is not None:
+            previous = matches[-1]
+            add(match.end, short, 0.03)
+            add(short, previous.start, sb_p[0] if last_sb is not None else sb_p[1])
+            repeat = State(distribution, name=label)
+            repeat_previous = State(distributions[i - 1], name=previous.name)
+            add(short, repeat_previous, sb_p[2])
+            add(repeat_previous, repeat, 0.70)
+            add(repeat_previous, match.start, 0.10)
+            add(repeat_previous, repeat_previous, 0.20)
+            add(repeat, repeat, 0.20)
+            add(repeat, repeat_previous, 0.80)
+            if last_sb is not None:
+                add(short, last_sb, 0.15)
+        if long_ is not None:
+            add(match.end, long_, 0.02)
+            add(long_, matches[-lb_length].start, 0.75 if last_lb is not None else 1.00)
+            if last_lb is not None:
+                add(long_, last_lb, 0.25)
+        if last_delete is not None:
+            add(last_delete, match.start, delete_p[0])
+            add(last_delete, delete, delete_p[1])
+        last_out, last_insert, last_delete, last_sb, last_lb = match.end, insert, delete, short, long_
+        matches.append(match)
+    add(last_delete, model.end, 0.95)
+    add(last_insert, model.end, 0.70)
+    add(last_out, model.end, 0.50)
+    return model
+
+
+def Phi29ProfileHMM(distributions, name="Phi29 Profile HMM", low=0, high=90, sb_length=1, verbose=True, merge='all'):
+    """The reference's linear Phi29 profile: short backslips and their repeat states, oversegmentation through the
+    two-state match (_linear_profile).  Baked with bake(verbose=verbose, merge=merge)."""
+    model = _linear_profile(distributions, name, low, high, sb_length, None,
+                            lambda i: 0.90 if i == 0 else 0.80 if i <= sb_length else 0.77,
+                            (0.75, 0.90, 0.10), (0.80, 0.10))
+    model.bake(verbose=verbose, merge=merge)
+    return model
+
+
+def Hel308ProfileHMM(distributions, name="Hel308 Profile HMM", low=0, high=90, sb_length=1, lb_length=9):
+    """The reference's linear Hel308 profile: Phi29ProfileHMM's states with its own numbers, and long backslips of
+    lb_length positions (_linear_profile).  Baked with the default bake()."""
+    model = _linear_profile(distributions, name, low, high, sb_length, lb_length,
+                            lambda i: 0.90 if i == 0 else 0.80 if i <= sb_length else 0.77 if i <= lb_length else 0.75,
+                            (0.80, 0.95, 0.05), (0.70, 0.20))
+    model.bake()
+    return model
