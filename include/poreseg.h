@@ -141,6 +141,9 @@ int ps_set_tiling(ps_ctx *ctx, int64_t tile_len, int64_t halo);
  * (the scan kernels, the aligner, the pairwise aligner, the HMM E-step) are launched on, from the next launch on;
  * "pairwise_budget" bytes of score / pointer scratch per launch of ps_pairwise_batch (default 2 GiB);
  * "tree_jobs_per_wave" (default 4) subtree kernel: jobs / this many of its slots work, between half and all of them;
+ * "tree_screen" 1 (default): on the 32-bit digest a lean kernel walks the subtree jobs first, proves the windows that hold no
+ * split empty and leaves the subtree kernel the jobs it cannot decide (counters[14], [15] of ps_get_timings), 0: the subtree
+ * kernel takes every job, launch for launch as before; same results either way;
  * "noise_k_ppm" (default 100 000 = 0.1): near-tie accounting of the 64-bit digest, margin factor in millionths;
  * "near_tie_log" n (default 65 536, 0 .. 2^30): records of the near-tie log that ps_get_near_ties reads (16 bytes each, device
  * memory allocated with the first segment call that logs), 0 = no log.
@@ -455,9 +458,11 @@ int ps_hmm_posterior(ps_ctx *ctx, const ps_hmm_model *model, const double *d_obs
  * the reference (first maximum wins, cparsers.pyx:175-177) and counted too; -1 = not counted: the call ran on the
  * LDS-window kernels (min_width < 8, option "scan_bs" 0 / "stitch_host" 1, counters[7] = 2, ps_segment_exact_f64); [12] chunk results (16 windows each) that the
  * look-ahead kernel's helpers published (option "lat_help"), [13] published chunks that a seam's owner took instead of
- * scanning them. */
+ * scanning them, [14] subtree jobs the screen kernel (option "tree_screen") handed on to the subtree kernel, [15] windows the
+ * screen kernel decided (they are part of [0] and [10], so [10] - [15] are the windows the subtree kernel scanned); both
+ * cover every round of the call, like [0] and [10], and both are -1 when the call did not launch the screen kernel. */
 int ps_get_timings(const ps_ctx *ctx, double *ms, int32_t n_ms, int64_t *counters, int32_t n_counters);
-/* The fourteen work counters of ps_get_timings in place (valid for the life of the context; host memory, updated by every
+/* The sixteen work counters of ps_get_timings in place (valid for the life of the context; host memory, updated by every
  * call before it returns): a caller that checks one of them after each call -- counters[11], the near ties -- reads it
  * there instead of making a second call. */
 const int64_t *ps_counters(const ps_ctx *ctx);

@@ -151,6 +151,8 @@ struct ps_ctx {
     // 0.90): with many jobs per slot four waves per SIMD deliver 1.4 x the throughput of two.
     int slots_pct = 100;
     int tree_jobs_per_wave = 4;   // subtree kernel: jobs / this many slots work, between half and all of them (0: all)
+    int tree_screen = 1;          // 1: on the narrow digest tree_screen_kernel runs in front of the subtree kernel and leaves it the jobs it cannot
+                                  // prove empty (seg_device.hpp), 0: the subtree kernel takes every job, launch for launch as before
     // host-side caches: workgroups per CU per kernel, dynamic-LDS attribute last set, the tile tables of the last call
     struct OccKey { const void *fn; int nt; size_t lds; int per_cu; };
     std::vector<OccKey> occ_cache;
@@ -195,14 +197,16 @@ struct ps_ctx {
     int bridge_budget = BR_MAX;                     // option bridge_budget (1 .. BR_MAX): anchors before a seam gives up -- tests lower it to reach the second chance on small inputs
     int bridge_ext_on = 1;                          // option bridge_ext / PORESEG_BRIDGE_EXT: 0 = straight to the host stitch, as before round 5
     HostBuf h_hdr;
-    DevBuf spine_jobs, spine_scratch, spine_dense, spine_meta, tree_jobs, tree_scratch, tree_spill,
+    DevBuf spine_jobs, spine_scratch, spine_dense, spine_meta, tree_jobs, tree_scratch, tree_spill, tree_defer, screen_acc,
         tree_counts, items, item_pos, first_item, ev_off, bounds_off, small;
     HostBuf h_meta, h_dense, h_small, h_up;
     hipEvent_t ev[10] = {};   // [0..7] phase marks (timing level 2), [8] start and [9] end of the call's device work (level 1)
     int timing = 1;           // 0: no events, 1: start/end of the sequence, 2: an event between the phases as well (each costs
                               // ~6 us of idle GPU: the next kernel does not start back to back)
     double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int64_t counters[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // [12] chunk results the look-ahead helpers published, [13] of which an owner took
+    int64_t counters[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, -1, -1};   // [12] chunk results the look-ahead helpers published, [13] of which an owner took,
+                              // [14] subtree jobs tree_screen_kernel deferred, [15] windows it decided (-1: it was not launched)
+    bool screen_ran = false;  // the current call launched tree_screen_kernel
 };
 
 namespace {
@@ -297,7 +301,9 @@ int chain_publish(ps_ctx *ctx, int device, hipStream_t st, unsigned long long ti
 constexpr size_t SMALL_TAIL = 64 * 1024;
 struct SmallLayout { unsigned long long status, work0, work1, work2, dense, stamp[12], life[9], qctl, qhead, tree_tail; AsmHeader hdr;
                      unsigned long long lat_ctl[6]; int lat_prog[LAT_D];        // (helpers of the look-ahead kernel, seg_device.hpp: LAT_D)
-                     unsigned long long nt_cur; };                              // near-tie records of the call (DevCfg::nt_cur)
+                     unsigned long long nt_cur;                                 // near-tie records of the call (DevCfg::nt_cur)
+                     unsigned long long tree_defer[3]; };                       // tree_screen_kernel: [0] jobs on its deferred list (of the current round),
+                                                                                // [1] windows it decided, [2] jobs it deferred (both over all rounds of the call)
 
 int make_cfg(ps_ctx *ctx, const void *d_samples, const ps_sample_format *fmt, int mw, int maxw, int W,
              double min_gain, DevCfg *c)
@@ -439,7 +445,7 @@ template <int NT, int DT> int launch_spine(ps_ctx *ctx, const DevCfg &cfg, unsig
 }
 
 template <int NT, int DT> int launch_tree(ps_ctx *ctx, const DevCfg &cfg, unsigned nj, SmallLayout *sm, size_t n_jobs,
-                                          const AsmHeader *d_hdr, int par_max_jobs = 0)
+                                          const AsmHeader *d_hdr, int par_max_jobs = 0, bool screened = false)
 {
     ScanShape s;
     if (int rc = scan_shape<NT>(ctx, tree_kernel<NT, DT>, cfg, nj, &s)) return rc;
@@ -449,9 +455,30 @@ template <int NT, int DT> int launch_tree(ps_ctx *ctx, const DevCfg &cfg, unsign
                        static_cast<long long>(n_jobs), d_hdr,
                        // (not on the 64-bit digest: those are filtered events, whose jobs hold many windows each -- 32 of them:
                        //  subtree kernel 1.30 ms on all slots, 1.71 ms with the rule)
-                       NT == 64 && !(DT & DT_WIDE) ? ctx->tree_jobs_per_wave : 0, par_max_jobs);
+                       NT == 64 && !(DT & DT_WIDE) ? ctx->tree_jobs_per_wave : 0, par_max_jobs,
+                       screened ? ctx->tree_defer.as<int2>() : nullptr, screened ? sm->tree_defer : nullptr,
+                       screened ? ctx->screen_acc.as<unsigned long long>() : nullptr);
     HIP_TRY(ctx, hipGetLastError());
     return PS_OK;
+}
+
+// Narrow digest: the screen in front of the subtree kernel (seg_device.hpp: tree_screen_kernel) -- single-wave workgroups without
+// LDS, one per resident slot, striding over the jobs; the subtree kernel behind it walks the deferred list.
+template <int DT> int launch_tree_screened(ps_ctx *ctx, const DevCfg &cfg, unsigned nj, SmallLayout *sm, size_t n_jobs,
+                                           const AsmHeader *d_hdr)
+{
+    ScanShape s;
+    if (int rc = scan_shape(ctx, tree_screen_kernel<DT>, 64, 0, nj, &s)) return rc;
+    hipLaunchKernelGGL((tree_screen_kernel<DT>), dim3(s.grid), dim3(64), 0, ctx->stream, cfg, ctx->tree_jobs.as<TreeJob>(),
+                       ctx->tree_defer.as<int2>(), sm->tree_defer, ctx->screen_acc.as<unsigned long long>(),
+                       static_cast<long long>(n_jobs), d_hdr);
+    HIP_TRY(ctx, hipGetLastError());
+    ctx->screen_ran = true;
+    const int rc = launch_tree<64, DT>(ctx, cfg, nj, sm, n_jobs, d_hdr, 0, true);
+    // (screen_acc is zero between calls because the subtree kernel clears what it collects: if that kernel was not launched,
+    //  what the screen's waves left there must not reach the next call's counters)
+    if (rc != PS_OK) (void)hipMemsetAsync(ctx->screen_acc.p, 0, ctx->screen_acc.cap, ctx->stream);
+    return rc;
 }
 
 // LDS-window scan: the spine kernel at the option's width (spine_nt)
@@ -505,6 +532,17 @@ int launch_subtrees(ps_ctx *ctx, const DevCfg &cfg, unsigned nj, SmallLayout *sm
     }
     if (cfg.bsum != nullptr) {
         if (ctx->tree_mw) return by_dtype(cfg.dtype, [&](auto dt) { return launch_tree_mw<dt()>(ctx, cfg, nj, sm, n_jobs, d_hdr); });
+#ifndef PS_STAMP
+        // the screen proves windows empty from the group records, in the product's mode only: without them (option groups 0,
+        // prune 0) it could decide nothing, and verify mode checks every window of the full scan
+        // (reserve_items sizes the screen's buffers with the job buffers; a caller whose jobs did not come through it gets the
+        //  subtree kernel alone, which computes the same)
+        const bool reserved = ctx->tree_defer.cap >= n_jobs * sizeof(int2) &&
+                              ctx->screen_acc.cap >= static_cast<size_t>(SCREEN_ACC) * SCREEN_ACC_STRIDE * sizeof(unsigned long long);
+        if (ctx->tree_screen && reserved && cfg.mode == MODE_FAST && cfg.grp != nullptr && cfg.prune) {
+            return by_dtype(cfg.dtype, [&](auto dt) { return launch_tree_screened<dt()>(ctx, cfg, nj, sm, n_jobs, d_hdr); });
+        }
+#endif
         return by_dtype(cfg.dtype, [&](auto dt) { return launch_tree<64, dt()>(ctx, cfg, nj, sm, n_jobs, d_hdr); });
     }
     return by_nt<512, 256>(ctx->tree_nt, [&](auto nt) {
@@ -754,6 +792,8 @@ int finish_batch(ps_ctx *ctx, const DevCfg &cfg, size_t n_tj, int64_t n_items, i
 #else
     ctx->nt_seen = -1;                                 // (the stamps take counters[11]'s words: not counted)
 #endif
+    ctx->counters[14] = ctx->screen_ran ? static_cast<int64_t>(hs.tree_defer[2]) : -1;                         // subtree jobs the screen deferred
+    ctx->counters[15] = ctx->screen_ran ? static_cast<int64_t>(hs.tree_defer[1]) : -1;                         // windows the screen decided
     ctx->counters[12] = static_cast<int64_t>(hs.lat_ctl[4]);                                                   // look-ahead helpers: chunk results published
     ctx->counters[13] = static_cast<int64_t>(hs.lat_ctl[5]);                                                   // ... and taken by an owner instead of scanning
 #ifdef PS_STAMP
@@ -845,6 +885,8 @@ void reset_call_stats(ps_ctx *ctx)
 {
     for (double &m : ctx->ms) m = 0;
     for (int64_t &c : ctx->counters) c = 0;
+    ctx->counters[14] = ctx->counters[15] = -1;
+    ctx->screen_ran = false;
 }
 
 // The buffers sized by the items of a call -- true spine anchors, one subtree job each at most -- for up to items_cap of them
@@ -860,6 +902,13 @@ int reserve_items(ps_ctx *ctx, int64_t items_cap, int64_t total_len, int mw)
     HIP_TRY(ctx, ctx->item_pos.reserve((static_cast<size_t>(items_cap) + 1) * sizeof(int64_t)));
     HIP_TRY(ctx, ctx->tree_scratch.reserve(tscratch_bound * sizeof(int32_t)));
     HIP_TRY(ctx, ctx->tree_spill.reserve(tscratch_bound * sizeof(int2)));
+    if (ctx->tree_screen) {
+        HIP_TRY(ctx, ctx->tree_defer.reserve(n * sizeof(int2)));                       // the screen's deferred list: at most every job
+        // ... and where its waves leave their window counts.  Invariant: all zero between calls -- zeroed here when allocated,
+        // and the subtree kernel launched behind the screen clears every line it collects (launch_tree_screened clears them
+        // itself if that launch fails)
+        HIP_TRY(ctx, ctx->screen_acc.reserve_zeroed(static_cast<size_t>(SCREEN_ACC) * SCREEN_ACC_STRIDE * sizeof(unsigned long long), ctx->stream));
+    }
     return PS_OK;
 }
 
@@ -1247,6 +1296,8 @@ int device_stitch_batch_(ps_ctx *ctx, const DevCfg &cfg_in, int bs_mode, const i
         HIP_TRY(ctx, hipMemcpyAsync(ctx->ext_list.p, list.data(), n_ext * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                       // (list is a local)
         HIP_TRY(ctx, hipMemsetAsync(&sm->hdr, 0, sizeof(AsmHeader), ctx->stream));
+        // (the next round's screen starts a new list; what the rounds so far decided and deferred stays, as in work[])
+        if (ctx->tree_screen) HIP_TRY(ctx, hipMemsetAsync(&sm->tree_defer[0], 0, sizeof sm->tree_defer[0], ctx->stream));
         {
             const unsigned g = static_cast<unsigned>(n_ext);
             auto extend = [&](auto dt) {
@@ -1412,7 +1463,7 @@ void ps_destroy(ps_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     DevBuf *bufs[] = {&ctx->spine_jobs, &ctx->spine_scratch, &ctx->spine_dense, &ctx->spine_meta, &ctx->tree_jobs,
-                      &ctx->tree_scratch, &ctx->tree_spill, &ctx->tree_counts, &ctx->items, &ctx->item_pos,
+                      &ctx->tree_scratch, &ctx->tree_spill, &ctx->tree_defer, &ctx->screen_acc, &ctx->tree_counts, &ctx->items, &ctx->item_pos,
                       &ctx->first_item, &ctx->ev_off, &ctx->bounds_off, &ctx->small, &ctx->bridges, &ctx->bmeta,
                       &ctx->tile_i32, &ctx->sp_off, &ctx->spine_items, &ctx->asm_hdr, &ctx->ev_first_tile, &ctx->ev_len,
                       &ctx->det_counts, &ctx->det_tics, &ctx->det_cand, &ctx->bsum, &ctx->ev_info, &ctx->chunk_mabs,
@@ -1505,6 +1556,7 @@ int ps_set_option(ps_ctx *ctx, const char *name, int64_t value)
     else if (n == "k0_unaligned") ctx->k0_unaligned = value != 0 ? k0_unaligned_probe(ctx->device, ctx->stream) : 0;
     else if (n == "slots_pct" && value >= 1 && value <= 100) ctx->slots_pct = static_cast<int>(value);
     else if (n == "tree_jobs_per_wave" && value >= 0 && value <= 1024) ctx->tree_jobs_per_wave = static_cast<int>(value);
+    else if (n == "tree_screen") ctx->tree_screen = value != 0;
     else if (n == "noise_k_ppm" && value >= 0) ctx->noise_k = static_cast<float>(static_cast<double>(value) * 1.0e-6);
 #ifdef PS_DIAG
     else if (n == "dbg_phase" && value >= 0 && value <= 2) ctx->dbg_phase = static_cast<int>(value);
@@ -2316,11 +2368,11 @@ int ps_get_timings(const ps_ctx *ctx, double *ms, int32_t n_ms, int64_t *counter
 {
     if (!ctx) return PS_ERR_ARG;
     for (int i = 0; i < n_ms && ms; ++i) ms[i] = i < 8 ? ctx->ms[i] : 0.0;
-    for (int i = 0; i < n_counters && counters; ++i) counters[i] = i < 14 ? ctx->counters[i] : 0;
+    for (int i = 0; i < n_counters && counters; ++i) counters[i] = i < 16 ? ctx->counters[i] : 0;
     return PS_OK;
 }
 
-// The context's fourteen work counters where ps_get_timings copies them from: a host that looks at one of them after every
+// The context's sixteen work counters where ps_get_timings copies them from: a host that looks at one of them after every
 // call (the near-tie count, counters[11]) reads it in place instead of making a second call.
 const int64_t *ps_counters(const ps_ctx *ctx) { return ctx ? ctx->counters : nullptr; }
 

@@ -1955,6 +1955,213 @@ __device__ __forceinline__ int scan_window_ph(const DevCfg &c, const EvRef &er, 
     return r >= 0 ? r - ph : r;
 }
 
+// ---- the window screen: "proven empty" or "undecided", and nothing else ----------------------------------
+// What a window costs that ends "no split" -- 95 % of the subtree jobs -- without the machinery of the windows that do not:
+// scan_window_bs's setup, its coarse pass over the group records, its sweep of the live rows, one comparison.  No LDS, no
+// block queue, no top-2, no contender list, no second phase, no sample fetch; the screen decides nothing but "empty".
+// Narrow digest only.  Returns true ("the reference finds no split in [ps, pe)") under exactly the inequalities under which
+// scan_window_bs returns -1 without looking at a sample (docs/BOUNDS.md; nothing new is bounded here):
+//   - every boundary candidate in range has a screened gain below the band,   ge < thr_log2 - dthr,  and none is `unsure`;
+//   - every group of a row that is not swept is bounded below  T = (thr_log2 - dthr) - 2 dlt  (bs_group_slack) -- T is what
+//     Tprune is in scan_window_bs when no gain reaches the band, and Tprune only rises from there;
+//   - every block with interior candidates is bounded below T: by the corner bound of the sweep, or else by bs_block_bound2
+//     from both of its boundaries (what the drain's filter does with a queued block, here on the spot: the left boundary
+//     is the lane below's; lane 0 repeats the previous row's last boundary, so no row needs its predecessor).
+// Everything else is false ("undecided": costs time only -- the full scan takes the window): wherever scan_window_bs would
+// leave its screened path (tiny / huge windows, candidates in the ragged ends, a window without variance) or has no coarse
+// pass (no group records, prune off, more than 64 rows, no whole group inside), a gain that reaches the band, a variance
+// below the floor, a block neither bound puts below T.  The caller shifts an event with a phase (EvRef::ph) as
+// scan_window_ph does.
+template <int DT>
+__device__ __forceinline__ bool screen_window_bs(const DevCfg &c, const EvRef &er, int64_t base, int ps, int pe, int cand_lo, int cand_hi, double thresh)
+{
+    static_assert(!bs_wide<DT>(), "the window screen reads the narrow digest");
+    const int lane = threadIdx.x & 63;
+    const int n = pe - ps;
+    const int g0 = (ps + 7) & ~7, g1 = pe & ~7;
+    const int nblk = (g1 - g0) >> 3;
+    const long long gb0 = er.boff + (g0 >> 3);
+    const int gbl = static_cast<int>(gb0 & (BS_CHUNK - 1));
+    const int nch = ((gbl + nblk) >> BS_CHUNK_LOG) + 1;
+    if (nblk < 4 || nch > BS_MAXCH || c.mode != MODE_FAST || cand_lo < g0 || cand_hi > g1) return false;
+    const int rows = (nblk + BS_STRIDE - 1) / BS_STRIDE;
+    const long long G0 = (gb0 + BS_GRP - 1) >> BS_GRP_LOG;
+    if (c.grp == nullptr || !c.prune || rows > 64) return false;
+    const int ngc = min(static_cast<int>(((gb0 + nblk) >> BS_GRP_LOG) - G0), 63);
+    if (ngc < 1) return false;
+    const int m = er.m;
+    const uint2 *bsw = static_cast<const uint2 *>(c.bsum) + gb0;
+    const long long c0 = gb0 >> BS_CHUNK_LOG;
+    auto row_load = [&](int r) { return bsw[min(max(r, 0) * BS_STRIDE + lane, nblk)]; };
+    // setup loads, issued together (as in scan_window_bs: clamped indices, no lane conditions)
+    const int nh = g0 - ps, nt = pe - g1;
+    const int ht_idx = lane < 32 ? ps + min(lane, max(nh - 1, 0)) : min(g1 + min(lane - 32, max(nt - 1, 0)), pe - 1);
+    const typename Raw<DT>::type ht_raw = static_cast<const typename Raw<DT>::type *>(c.samples)[base + ht_idx];
+    int4 ct = c.chunk_tot[c0 + min(lane, nch - 1)];
+    const uint2 e0 = bsw[0], eN = bsw[nblk];
+    const uint4 gent = (static_cast<const uint4 *>(c.grp) + G0)[min(lane, ngc)];
+    uint2 ring[2] = {row_load(0), row_load(rows - 1)};                     // the rows of the window's two ends: practically always live
+    if (lane >= nch) ct = make_int4(0, 0, 0, 0);
+    const bool ht_in = lane < nh || (lane >= 32 && lane - 32 < nt);
+    const int yht = ht_in ? bs_count_of<DT>(c, ht_raw) - m : 0;
+    const int h1 = oct_sum(yht), h2 = oct_sum(yht * yht);
+    const int H1 = lane_get(h1, 7), TL1 = lane_get(h1, 39);
+    const double H2 = static_cast<double>(lane_get(h2, 7)), TL2 = static_cast<double>(lane_get(h2, 39));
+    // chunk offsets: exclusive scan of the chunk totals over the lanes
+    const bool many = nch > 16;
+    int yabs = ct.y;
+    const int cs1 = ct.x;
+    const double cs2 = bs_d(i64_of(ct.z, ct.w));
+    int i1 = cs1;
+    double i2 = cs2;
+#define PS_ROW_STEPS(X) X(0x111, 0xf) X(0x112, 0xf) X(0x114, 0xf) X(0x118, 0xf)
+#define PS_BC_STEPS(X) X(0x142, 0xa) X(0x143, 0xc)
+#define PS_STEP(CTRL, RM) { yabs = max(yabs, dpp_mov<CTRL, RM>(0, yabs)); i1 += dpp_mov<CTRL, RM>(0, i1); i2 += dpp_movd<CTRL, RM>(i2); }
+    PS_ROW_STEPS(PS_STEP)
+    if (many) { PS_BC_STEPS(PS_STEP) }
+#undef PS_STEP
+#undef PS_ROW_STEPS
+#undef PS_BC_STEPS
+    yabs = lane_get(yabs, many ? 63 : 15);
+    const int off1 = (i1 - cs1) + (H1 - bs8_s1(e0));
+    const double off2 = ((i2 - cs2) + (H2 - static_cast<double>(bs8_s2(e0)))) - BS_BIAS;
+    const int T1 = bs8_s1(eN) + lane_get(off1, nch - 1) + TL1;
+    const double T2 = (bs8_s2_biased(eN) + lane_get(off2, nch - 1)) + TL2;
+    const double T1d = uni(bs_d(T1)), T2d = uni(T2);
+    const double dn = static_cast<double>(n);
+    const double Dtot = dn * T2d - T1d * T1d;
+    if (!(Dtot > 0.0)) return false;
+    const float nf = static_cast<float>(n);
+    const float rn = __builtin_amdgcn_rcpf(nf);
+    const float c0f = uni(__builtin_amdgcn_logf(static_cast<float>(Dtot) * rn * rn));
+    const float SSt = uni(static_cast<float>(Dtot) * rn);
+    const f2 cc = {c0f, c0f};
+    const float dlt = screen_delta_log2(n);
+    const float thr_log2 = static_cast<float>(thresh * 1.4426950408889634);
+    const float dthr = dlt + 3.0e-6f * nf + 1.0e-6f * fabsf(thr_log2);
+    const float LOG2E = 1.4426950408889634f;
+    const float ymaxf = static_cast<float>(yabs);
+    const float mabsf = fabsf(static_cast<float>(m)) + ymaxf;
+    const float vfloor = uni(fmaxf(mabsf * mabsf * 1.0e-9f, ymaxf * ymaxf * 1.5e-8f));
+    const unsigned crange = static_cast<unsigned>(cand_hi - cand_lo);
+    const float band = thr_log2 - dthr;                                    // a gain that reaches it: not empty for the screen
+    const float T = band - 2.0f * dlt;
+    // ---- coarse pass (scan_window_bs, GROUPS): lane L evaluates group boundary L and bounds the group (L-1, L) ----
+    unsigned long long live;
+    {
+        const int tC = static_cast<int>((G0 << BS_GRP_LOG) - gb0) + BS_GRP * lane;
+        const bool cin = lane <= ngc;
+        const int nlc = cin ? nh + 8 * tC : 1;
+        const int cb = min((gbl + (cin ? tC : 0)) >> BS_CHUNK_LOG, nch - 1) << 2;
+        const uint2 gentry = make_uint2(gent.x, gent.y);
+        const int a1 = bs_a1(gentry, bs_from_lane(off1, cb));
+        const double a2 = bs_a2(gentry, bs_from_lane(off2, cb));
+        const bool bval = cin && nlc >= 1 && nlc <= n - 1;
+        const int nlv = bval ? nlc : 1;
+        const double a1d = bs_d(a1), nld = static_cast<double>(nlv);
+        const BsEval e = bs_eval(a1d, a2, T1d - a1d, T2d - a2, nlv, n - nlv, cc, vfloor);
+        const bool inr = bval && static_cast<unsigned>(ps + nlc - cand_lo) <= crange;
+        const bool eok = bval && e.okL && e.okR;
+        if (__ballot(inr && eok && e.g >= band) != 0ull) return false;
+        const bool hasL = lane >= 1, hasR = lane < ngc;
+        const float D1r = __uint_as_float(gent.z), D2r = __uint_as_float(gent.w);
+        const float D1l = from_lane_below(D1r), D2l = from_lane_below(D2r);
+        const float D1 = fmaxf(hasL ? D1l : 0.0f, hasR ? D1r : 0.0f), D2 = fmaxf(hasL ? D2l : 0.0f, hasR ? D2r : 0.0f);
+        const int sgl = a1 - from_lane_below(a1), sgr = from_lane_above(a1) - a1;
+        const double ig = 1.0 / static_cast<double>(BS_GRP_SAMPLES);
+        const float wLl = static_cast<float>(fma(nld, static_cast<double>(sgl) * ig, -a1d)) * e.r.x;
+        const float wLr = static_cast<float>(fma(nld, static_cast<double>(sgr) * ig, -a1d)) * e.r.x;
+        const float dmu = static_cast<float>(fma(dn, a1d, -(nld * T1d))) * e.r.x * e.r.y;
+        const float A = bs_group_slack(e, D1, D2, hasL ? wLl : wLr, hasR ? wLr : wLl, dmu);
+        const float nlf = static_cast<float>(nlv), nrf = nf - nlf;
+        const bool okF = e.u.x * nlf >= vfloor * (nlf + static_cast<float>(BS_GRP_SAMPLES)) &&
+                         e.u.y * nrf >= vfloor * (nrf + static_cast<float>(BS_GRP_SAMPLES));
+        const float GA = (eok && okF) ? e.g + A : INFINITY;
+        const float ghb = fmaxf(GA, from_lane_below(GA));
+        // rows to sweep (lane r works it out for row r): all whose blocks do not all lie in groups below T
+        const unsigned long long dead = __ballot(lane >= 1 && lane <= ngc && ghb < T);
+        const int tl = BS_STRIDE * lane, th = min(tl + BS_STRIDE, nblk) - 1;
+        const int lo = static_cast<int>(((gb0 + tl) >> BS_GRP_LOG) - G0) + 1, hi = static_cast<int>(((gb0 + th) >> BS_GRP_LOG) - G0) + 1;
+        const unsigned long long span = ((2ull << (hi - lo)) - 1ull) << max(lo, 0);
+        live = __ballot(lane < rows && !(lo >= 1 && hi <= ngc && (dead & span) == span));
+    }
+    // ---- the live rows: the arithmetic of scan_window_bs's row_eval, judged on the spot ----
+    const int nl0 = nh + 8 * lane;
+    auto row_empty = [&](int r, const uint2 &cur) -> bool {                // (uniform)
+        const int tb = gbl + BS_STRIDE * r;
+        const int cb = min((tb + lane) >> BS_CHUNK_LOG, nch - 1) << 2;
+        const int o1 = bs_from_lane(off1, cb);
+        const double o2 = bs_from_lane(off2, cb);
+        const int nl = nl0 + 8 * BS_STRIDE * r, J = ps + nl;
+        const float nlf = static_cast<float>(nl);
+        const double nld = static_cast<double>(nl);
+        const int a1 = bs_a1(cur, o1);
+        const double a2 = bs_a2(cur, o2);
+        const double a1d = bs_d(a1), b1d = T1d - a1d, b2d = T2d - a2;
+        const double DL = fma(nld, a2, -(a1d * a1d));
+        const double DR = fma(dn - nld, b2d, -(b1d * b1d));
+        const float nrf = nf - nlf;
+        const f2 D = {static_cast<float>(DL), static_cast<float>(DR)};
+        const f2 nv = {nlf, nrf};
+        const f2 rr = {__builtin_amdgcn_rcpf(nlf), __builtin_amdgcn_rcpf(nrf)};
+        const f2 u = D * rr * rr;
+        const f2 lgu = {__builtin_amdgcn_logf(u.x), __builtin_amdgcn_logf(u.y)};
+        const f2 lg = lgu - cc;
+        const f2 tt = nv * lg;
+        const float g = -(tt.x + tt.y);
+        const bool valid = static_cast<unsigned>(nl - 1) < static_cast<unsigned>(n - 1);
+        const bool okL = valid && u.x >= vfloor, okR = valid && u.y >= vfloor;
+        const bool inr = static_cast<unsigned>(J - cand_lo) <= crange && (lane != 0 || r == 0);
+        // a boundary gain in the band or above, or a boundary the screen cannot judge (variance floor)
+        if (__ballot(inr && !(okL && okR && g < band)) != 0ull) return false;
+        // the block (J - 8, J): the corner bound
+        const float aL = from_lane_below(lg.x), rlb = from_lane_below(rr.x);
+        const bool pokL = from_lane_below(static_cast<int>(okL)) != 0;
+        const bool blk = lane >= 1 && static_cast<unsigned>(J - 1 - cand_lo) <= crange + 6u;
+        const float h0 = -fmaf(nlf - 8.0f, aL, (nrf + 8.0f) * (lg.y - 8.0f * LOG2E * rr.y));
+        const float h1 = -fmaf(nlf - 1.0f, aL - 7.0f * LOG2E * rlb, (nrf + 1.0f) * (lg.y - LOG2E * rr.y));
+        const bool prunable = static_cast<bool>(static_cast<int>(pokL) & static_cast<int>(okR) & static_cast<int>(nl >= 9));
+        const bool keep = static_cast<bool>(static_cast<int>(blk) & static_cast<int>(!(prunable && fmaxf(h0, h1) < T)));
+        if (__ballot(keep) == 0ull) return true;
+        // ... and for the blocks it leaves, the bound from both boundaries (the branch is the wave's: every lane is here)
+        BsEval eq, ep;
+        eq.g = g; eq.lg = lg; eq.r = rr; eq.u = u; eq.okL = okL; eq.okR = okR;
+        ep.g = from_lane_below(g);
+        ep.lg.x = aL; ep.lg.y = from_lane_below(lg.y);
+        ep.r.x = rlb; ep.r.y = from_lane_below(rr.y);
+        ep.u.x = from_lane_below(u.x); ep.u.y = from_lane_below(u.y);
+        ep.okL = pokL; ep.okR = from_lane_below(static_cast<int>(okR)) != 0;
+        const int nlp = nl - 8;
+        const float b2 = bs_block_bound2(ep, eq, max(nlp, 1), n, SSt, rn);
+        return __ballot(keep && !(nlp >= 1 && b2 < T)) == 0ull;
+    };
+    auto take_row = [&]() {
+        if (live == 0ull) return -1;
+        const int r = __builtin_ctzll(live);
+        live &= live - 1ull;
+        return r;
+    };
+    int rr[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int pr = i == 0 ? 0 : rows - 1;
+        if ((live >> pr) & 1ull) { rr[i] = pr; live &= ~(1ull << pr); }
+        else { rr[i] = take_row(); ring[i] = row_load(rr[i]); }
+    }
+    for (bool any = true; any;) {
+        any = false;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            if (rr[i] >= 0) {
+                if (!row_empty(rr[i], ring[i])) return false;
+                any = true;
+            }
+            if (any) { rr[i] = take_row(); ring[i] = row_load(rr[i]); }
+        }
+    }
+    return true;
+}
+
 // ---- K2 from the K0 digest: per-segment statistics without a second pass over the samples ------------------
 // Segment.mean/std/min/max (core.py:209-223).  One wave per segment (workgroups stride over the segments):
 // S1, S2 of the full blocks inside the segment from the chunk prefix and the chunk totals, min/max from the per-block

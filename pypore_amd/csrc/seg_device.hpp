@@ -1867,15 +1867,33 @@ __device__ __forceinline__ int tree_job(const DevCfg &c, int *ys, const TreeJob 
     return cnt;
 }
 
+constexpr int SCREEN_ACC = 64;           // cache lines the waves of tree_screen_kernel spread their window counts over ...
+constexpr int SCREEN_ACC_STRIDE = 32;    // ... 256 bytes apart (in 8-byte words)
 template <int NT, int DT>
 __global__ __launch_bounds__(NT, (NT == 64 ? PS_BS_MINW : 4)) PS_SCAN_REGS void tree_kernel(DevCfg c, const TreeJob *__restrict__ jobs, int32_t *scratch,
                                                   int2 *spill, int32_t *counts, unsigned *status,
                                                   unsigned long long *work, long long n_jobs_host, const AsmHeader *hdr,
-                                                  int jobs_per_wave, int par_max_jobs = 0)
+                                                  int jobs_per_wave, int par_max_jobs = 0, const int2 *__restrict__ deferred = nullptr,
+                                                  unsigned long long *defer_ctl = nullptr, unsigned long long *screen_acc = nullptr)
 {
     extern __shared__ int ys[];
     __shared__ SharedT<NT> sh;
-    const long long n_jobs = dev_count(hdr, n_jobs_host);
+    // (behind the screen: its window counts, which its waves left spread over SCREEN_ACC cache lines, go to the call's counters
+    //  here -- under kernel index 2, like this kernel's own -- and the lines are clear again for the next call)
+    if (deferred && blockIdx.x == 0 && threadIdx.x < SCREEN_ACC) {
+        if (threadIdx.x == 0) defer_ctl[2] += defer_ctl[0];            // (jobs deferred, over the rounds of a call: [0] is cleared per round)
+        const unsigned long long v = screen_acc[threadIdx.x * SCREEN_ACC_STRIDE];
+        if (v) {
+            screen_acc[threadIdx.x * SCREEN_ACC_STRIDE] = 0;
+            atomicAdd(&work[0], v >> 40);
+            atomicAdd(&work[1], v & ((1ull << 40) - 1ull));
+            atomicAdd(&work[17 + 3 * 2], v >> 40);
+            atomicAdd(&defer_ctl[1], v >> 40);
+        }
+    }
+    // deferred != nullptr: tree_screen_kernel ran in front of this kernel and left the jobs it could not prove empty -- entry k
+    // is (job index, first window the screen did not decide); the job's windows before that one hold no split
+    const long long n_jobs = deferred ? static_cast<long long>(defer_ctl[0]) : dev_count(hdr, n_jobs_host);
     if (n_jobs <= par_max_jobs) return;                // (few, deep jobs: tree_par_kernel, launched next to this one, takes the call)
     // How many of the launched slots work (jobs_per_wave > 0; the job count is only known on the device).  With few
     // jobs per slot the kernel's duration is a handful of windows in a row, and a window's latency doubles from two to
@@ -1893,14 +1911,74 @@ __global__ __launch_bounds__(NT, (NT == 64 ? PS_BS_MINW : 4)) PS_SCAN_REGS void 
     Work wk = PS_WORK_INIT;
     // One workgroup per resident slot, striding over the jobs (a workgroup per job costs more in launches than the
     // one or two scans of a typical job: 0.28 ms against 0.17 ms for the 9 231 jobs of the bench trace).
-    for (long long ji = blockIdx.x; ji < n_jobs; ji += G) {
-        const TreeJob job = jobs[ji];
+    for (long long k = blockIdx.x; k < n_jobs; k += G) {
+        long long ji = k;
+        int j0d = -1;
+        if (deferred) {
+            const int2 d = deferred[k];
+            ji = __builtin_amdgcn_readfirstlane(d.x);
+            j0d = __builtin_amdgcn_readfirstlane(d.y);
+        }
+        TreeJob job = jobs[ji];
         // (all fields in one round trip: otherwise the compiler fetches out_cap, tests it, and only then the rest)
         asm volatile("" : : "s"(job.base), "s"(job.start), "s"(job.end), "s"(job.j0), "s"(job.out_off), "s"(job.m), "s"(job.boff));
         if (job.out_cap == 0) continue;                // spine anchor without a left subtree (device stitch)
+        if (j0d >= 0) job.j0 = j0d;
         tree_job<NT, DT>(c, ys, job, ji, scratch, spill, counts, sh, bad, wk, hdr ? counts + n_jobs_host : nullptr);
     }
     flush(bad, wk, status, work, 2);
+}
+
+// ---- phase 3, in front of tree_kernel<64, DT> on the narrow digest: the subtree jobs that hold nothing ----------------
+// 95 % of the subtree jobs find no split, in about 1.9 windows each.  tree_kernel carries all of scan_window_bs for them --
+// block queue, sample drain, contender list, bs_decide, the exact scan, the traversal stack, the output buffer: the registers
+// and the LDS that keep its waves from running beside another call's K0.  This kernel can do one thing: walk a job's windows
+// as find_split enumerates them and prove each of them empty (screen_window_bs: no LDS, no queue, no second phase).  A job
+// all of whose windows are empty is done -- its counts[] entry stays 0, as it does for a job in which tree_kernel finds
+// nothing.  At the first window it cannot prove empty the job goes to the deferred list with that window's index, and
+// tree_kernel takes it from there.  A job longer than max_width (the forced splits of find_split) is deferred untouched.
+// Counters: a window is counted by the kernel that decides it -- the empty ones here, under kernel index 2 like tree_kernel's.
+// A wave leaves its counts with ONE atomic, windows << 40 | candidates, on one of SCREEN_ACC cache lines, and tree_kernel adds
+// the lines to the call's counters: the kernel is a few windows long and all of its waves end together -- four atomics each
+// on the status block's one cache line, one after the other at ~5 ns, were 0.14 ms behind 0.03 ms of work (7 168 waves).
+// defer_ctl[0]: deferred jobs (the list's length; cleared with the call's status block, and again in front of every second-chance
+// round), [1]: windows decided here, [2]: jobs deferred -- both summed over the rounds of a call by tree_kernel, like work[].
+#ifndef PS_SCREEN_VGPRS
+#define PS_SCREEN_VGPRS 44         // (as PS_SCAN_VGPRS: x 2 of the unified file -- a cap of 88, five waves per SIMD, three beside two K0 waves;
+                                   //  the kernel comes out at 64 registers, no scratch, no LDS: two waves fit beside three K0 waves)
+#endif
+template <int DT>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(PS_SCREEN_VGPRS))) void tree_screen_kernel(DevCfg c, const TreeJob *__restrict__ jobs, int2 *__restrict__ deferred,
+                                                  unsigned long long *defer_ctl, unsigned long long *screen_acc,
+                                                  long long n_jobs_host, const AsmHeader *hdr)
+{
+    const long long n_jobs = dev_count(hdr, n_jobs_host);
+    Work wk = PS_WORK_INIT;
+    for (long long ji = blockIdx.x; ji < n_jobs; ji += gridDim.x) {
+        const TreeJob job = jobs[ji];
+        asm volatile("" : : "s"(job.base), "s"(job.start), "s"(job.end), "s"(job.j0), "s"(job.m), "s"(job.boff));
+        if (job.out_cap == 0) continue;
+        const EvRef er = {job.m, job.boff, job.pad_};
+        const long long start = job.start, end = job.end;
+        int j = job.j0;
+        bool empty = end - start <= c.maxw;            // (longer: find_split's forced splits -- the whole job is tree_kernel's)
+        if (empty) {
+            const long long lim = end - 2LL * c.mw;
+            for (long long ps = start + static_cast<long long>(j) * c.half; ps < lim; ps += c.half, ++j) {
+                const long long pe = min(ps + c.W, end);
+                if (pe - ps <= 2LL * c.mw) continue;   // (cparsers.pyx:164: nothing to scan)
+                const int ph = er.ph;                  // (a trace-aligned digest: shifted coordinates, see scan_window_ph)
+                empty = screen_window_bs<DT>(c, er, job.base - ph, static_cast<int>(ps) + ph, static_cast<int>(pe) + ph,
+                                             static_cast<int>(ps) + c.mw + ph, static_cast<int>(pe) - c.mw + ph, c.min_gain);
+                if (!empty) break;
+                wk.windows += 1; wk.cands += pe - ps - 2LL * c.mw + 1;
+            }
+        }
+        if (!empty && threadIdx.x == 0) deferred[atomicAdd(&defer_ctl[0], 1ull)] = make_int2(static_cast<int>(ji), j);
+    }
+    if (threadIdx.x == 0 && wk.windows)
+        atomicAdd(&screen_acc[(blockIdx.x & (SCREEN_ACC - 1)) * SCREEN_ACC_STRIDE],
+                  (static_cast<unsigned long long>(wk.windows) << 40) + static_cast<unsigned long long>(wk.cands));
 }
 
 // Block-sum scan, TREE_W waves per workgroup: every wave runs single-wave jobs on its own, and the waves of a

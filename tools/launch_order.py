@@ -8,7 +8,12 @@ kernel trace, once per library, so that the two ordered lists of launches can be
 
 --compare reads the *kernel_trace.csv under each directory and compares, launch by launch in dispatch order, kernel name,
 grid, workgroup size and LDS size (whatever of these columns the trace has; it says which are missing).  Exit status 1
-when the lists differ.  A refactor of the host code that leaves the device code alone must leave these lists equal."""
+when the lists differ.  A refactor of the host code that leaves the device code alone must leave these lists equal.
+
+`--tree-screen 0` (before any other argument) sets option tree_screen 0 on the context: the list of a library that has the
+subtree screen is then, launch for launch, the list of one that does not (tree_screen 1, the default, adds one
+tree_screen_kernel in front of every tree_kernel<64> of the narrow digest).  `--compare A B --names-only` compares the kernel
+names without their parameter lists (tree_kernel gained arguments with the screen)."""
 import csv
 import glob
 import os
@@ -17,6 +22,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+NAMES_ONLY = False        # --compare A B --names-only: kernel names without their parameter lists (a kernel that gained an argument)
 COLUMNS = ["Kernel_Name", "Grid_Size_X", "Grid_Size_Y", "Grid_Size_Z", "Workgroup_Size_X", "Workgroup_Size_Y", "Workgroup_Size_Z",
            "LDS_Block_Size"]
 
@@ -32,7 +38,7 @@ def launches(directory):
     have = [c for c in COLUMNS if rows and c in rows[0]]
     order = "Dispatch_Id" if rows and "Dispatch_Id" in rows[0] else "Start_Timestamp"
     rows.sort(key=lambda r: int(r[order]))
-    return have, order, [tuple(r[c] for c in have) for r in rows]
+    return have, order, [tuple(r[c].split("(")[0] if c == "Kernel_Name" and NAMES_ONLY else r[c] for c in have) for r in rows]
 
 
 def compare(dir_a, dir_b):
@@ -57,11 +63,13 @@ def compare(dir_a, dir_b):
     return 0
 
 
-def routes():
+def routes(tree_screen=None):
     import numpy as np
     import torch
     from pypore_amd import _lib, engine, synth
     ctx = engine.Context(0)
+    if tree_screen is not None:
+        ctx.set_option("tree_screen", tree_screen)
     q = synth.QUANTUM
     p = _lib.split_params(prior_segments_per_second=10.)
     dense = _lib.split_params(min_width=100, max_width=1000000, window_width=10000, prior_segments_per_second=10., sampling_freq=1e5)
@@ -126,6 +134,7 @@ def routes():
 
 
 if __name__ == "__main__":
-    if len(sys.argv) == 4 and sys.argv[1] == "--compare":
+    if len(sys.argv) in (4, 5) and sys.argv[1] == "--compare":
+        NAMES_ONLY = len(sys.argv) == 5 and sys.argv[4] == "--names-only"
         sys.exit(compare(sys.argv[2], sys.argv[3]))
-    routes()
+    routes(int(sys.argv[2]) if len(sys.argv) == 3 and sys.argv[1] == "--tree-screen" else None)
