@@ -1222,6 +1222,309 @@ __device__ __forceinline__ void bs_audit_note(unsigned long long *a, int icnt, i
 #else
 #define PS_MARK(n) do { } while (0)
 #endif
+
+// ---- the front of a window scan, written once ------------------------------------------------------------
+// What scan_window_bs and screen_window_bs both do before and while they judge a row.  The screen proves a window empty
+// under exactly the inequalities under which the scan returns -1 without looking at a sample (docs/BOUNDS.md): each of
+// those inequalities stands in one of the helpers below and nowhere else.  Arguments and results travel by value (see K0Gen;
+// a struct passed by reference cost the wide kernels four registers); `lane` is threadIdx.x & 63.
+// Geometry of the window [ps, pe) of an event: its whole blocks [g0, g1), the chunks and rows they span.
+struct BsGeom {
+    int n, g0, g1, nblk, gbl, nch, rows, nh, nt;
+    long long gb0, G0;
+    // tiny or huge window, or candidates in the ragged head / tail (min_width < 8): not a window for the screened path
+    __device__ __forceinline__ bool off_path(int cand_lo, int cand_hi) const { return nblk < 4 || nch > BS_MAXCH || cand_lo < g0 || cand_hi > g1; }
+    // groups entirely inside the window (<= 0: none)
+    __device__ __forceinline__ int whole_groups() const { return min(static_cast<int>(((gb0 + nblk) >> BS_GRP_LOG) - G0), 63); }
+};
+__device__ __forceinline__ BsGeom bs_geom(const EvRef &er, int ps, int pe)
+{
+    BsGeom g;
+    g.n = pe - ps; g.g0 = (ps + 7) & ~7; g.g1 = pe & ~7;
+    g.nblk = (g.g1 - g.g0) >> 3;
+    g.gb0 = er.boff + (g.g0 >> 3);
+    g.gbl = static_cast<int>(g.gb0 & (BS_CHUNK - 1));                 // chunk of boundary t: (gbl + t) >> 7
+    g.nch = ((g.gbl + g.nblk) >> BS_CHUNK_LOG) + 1;                   // chunks touched
+    g.rows = (g.nblk + BS_STRIDE - 1) / BS_STRIDE;                    // nblk + 1 boundaries, 63 new ones per row
+    g.nh = g.g0 - ps; g.nt = pe - g.g1;                               // ragged head [ps, g0) and tail [g1, pe): <= 7 raw samples each
+    g.G0 = (g.gb0 + BS_GRP - 1) >> BS_GRP_LOG;                        // first group boundary at or behind g0
+    return g;
+}
+
+// Setup, first half: the loads every window needs before its first boundary.  The caller issues its own (ring, sampled
+// boundary, group record) right behind this call and only then calls bs_setup_sums: all of the setup's loads are out
+// before anything consumes one.
+// (The head / tail sample is loaded by every lane from a clamped index and converted after all of the setup's loads are
+//  out: under a lane condition the compiler finishes the conversion inside the branch and waits for the sample right there
+//  -- two exposed round trips to HBM in front of the other loads, which is what rounds 1 and 2 did.  The chunk totals
+//  likewise: every lane loads a clamped entry, lanes beyond the window's chunks are masked afterwards.)
+template <int DT> struct BsSetupLoads { typename Raw<DT>::type ht; int4 ct, cm; typename BsTypes<bs_wide<DT>()>::E e0, eN; };
+template <int DT>
+__device__ __forceinline__ BsSetupLoads<DT> bs_setup_loads(const DevCfg &c, BsGeom g, int64_t base, int ps, int pe,
+                                                           const typename BsTypes<bs_wide<DT>()>::E *bsw, int lane)
+{
+    BsSetupLoads<DT> l;
+    const int ht_idx = lane < 32 ? ps + min(lane, max(g.nh - 1, 0)) : min(g.g1 + min(lane - 32, max(g.nt - 1, 0)), pe - 1);
+    l.ht = static_cast<const typename Raw<DT>::type *>(c.samples)[base + ht_idx];
+    const long long cidx = (g.gb0 >> BS_CHUNK_LOG) + min(lane, g.nch - 1);
+    l.cm = make_int4(0, 0, 0, 0);
+    if constexpr (bs_wide<DT>()) { l.ct = c.chunk_tot[2 * cidx]; l.cm = c.chunk_tot[2 * cidx + 1]; }
+    else l.ct = c.chunk_tot[cidx];
+    l.e0 = bsw[0]; l.eN = bsw[g.nblk];
+    return l;
+}
+// Setup, second half: the head / tail sums (lanes 0..7 head, 32..39 tail), the chunk offsets by an exclusive scan of the
+// chunk totals over the lanes (rows of 16 suffice for windows up to 15 000 samples), the window totals about m and the
+// largest |k - m|.  Lane c keeps off1 / off2 of chunk c: the sums of [ps, first boundary of chunk c) minus that chunk's
+// prefix base, so that a(t) = E[t] + off[chunk(t)] (bs_a1, bs_a2).
+template <bool WIDE> struct BsSetup { typename BsTypes<WIDE>::s1_t off1, T1; typename BsTypes<WIDE>::o2_t off2; typename BsTypes<WIDE>::s2_t T2; int yabs; };
+template <int DT>
+__device__ __forceinline__ BsSetup<bs_wide<DT>()> bs_setup_sums(const DevCfg &c, BsGeom g, int m, BsSetupLoads<DT> l, int lane)
+{
+    constexpr bool WIDE = bs_wide<DT>();
+    typedef typename BsTypes<WIDE>::s1_t s1_t;
+    typedef typename BsTypes<WIDE>::s2_t s2_t;
+    const int nch = g.nch;
+    int4 ct = l.ct;
+    if (lane >= nch) ct = make_int4(0, 0, 0, 0);
+    const int yab = lane < nch ? (WIDE ? l.cm.x : ct.y) : 0;
+    const bool ht_in = lane < g.nh || (lane >= 32 && lane - 32 < g.nt);
+    const int yht = ht_in ? bs_count_of<DT>(c, l.ht) - m : 0;
+    s1_t H1, TL1;
+    s2_t H2, TL2;
+    if constexpr (WIDE) {
+        const long long h1 = oct_sum(static_cast<long long>(yht)), h2 = oct_sum(static_cast<long long>(yht) * static_cast<long long>(yht));
+        H1 = lane_get(h1, 7); H2 = lane_get(h2, 7); TL1 = lane_get(h1, 39); TL2 = lane_get(h2, 39);
+    } else {
+        const int h1 = oct_sum(yht), h2 = oct_sum(yht * yht);      // 7 * 2^28 < 2^31
+        H1 = lane_get(h1, 7); H2 = static_cast<double>(lane_get(h2, 7)); TL1 = lane_get(h1, 39); TL2 = static_cast<double>(lane_get(h2, 39));
+    }
+    const bool many = nch > 16;                        // (uniform)
+    BsSetup<WIDE> s;
+    int yabs = yab;
+#define PS_ROW_STEPS(X) X(0x111, 0xf) X(0x112, 0xf) X(0x114, 0xf) X(0x118, 0xf)
+#define PS_BC_STEPS(X) X(0x142, 0xa) X(0x143, 0xc)
+#define PS_MSTEP(CTRL, RM) { yabs = max(yabs, dpp_mov<CTRL, RM>(0, yabs)); }
+    PS_ROW_STEPS(PS_MSTEP)
+    if (many) { PS_BC_STEPS(PS_MSTEP) }
+#undef PS_MSTEP
+    s.yabs = lane_get(yabs, many ? 63 : 15);
+    if constexpr (WIDE) {
+        const long long cs1 = i64_of(ct.x, ct.y), cs2 = i64_of(ct.z, ct.w);
+        long long i1 = cs1, i2 = cs2;
+#define PS_STEP(CTRL, RM) { const int l1_ = dpp_mov<CTRL, RM>(0, static_cast<int>(i1)), h1_ = dpp_mov<CTRL, RM>(0, static_cast<int>(i1 >> 32)); \
+                            const int l2_ = dpp_mov<CTRL, RM>(0, static_cast<int>(i2)), h2_ = dpp_mov<CTRL, RM>(0, static_cast<int>(i2 >> 32)); \
+                            i1 += i64_of(l1_, h1_); i2 += i64_of(l2_, h2_); }
+        PS_ROW_STEPS(PS_STEP)
+        if (many) { PS_BC_STEPS(PS_STEP) }
+#undef PS_STEP
+        s.off1 = (i1 - cs1) + (H1 - i64_of(l.e0.x, l.e0.y));
+        s.off2 = (i2 - cs2) + (H2 - i64_of(l.e0.z, l.e0.w));
+        s.T1 = i64_of(l.eN.x, l.eN.y) + lane_get(s.off1, nch - 1) + TL1;
+        s.T2 = i64_of(l.eN.z, l.eN.w) + lane_get(s.off2, nch - 1) + TL2;
+    } else {
+        const int cs1 = ct.x;
+        const double cs2 = bs_d(i64_of(ct.z, ct.w));                   // < 2^38: exact
+        int i1 = cs1;
+        double i2 = cs2;
+#define PS_STEP(CTRL, RM) { i1 += dpp_mov<CTRL, RM>(0, i1); i2 += dpp_movd<CTRL, RM>(i2); }
+        PS_ROW_STEPS(PS_STEP)
+        if (many) { PS_BC_STEPS(PS_STEP) }
+#undef PS_STEP
+        s.off1 = (i1 - cs1) + (H1 - bs8_s1(l.e0));
+        const double o2 = (i2 - cs2) + (H2 - static_cast<double>(bs8_s2(l.e0)));   // exact integers below 2^45
+        s.off2 = o2 - BS_BIAS;
+        s.T1 = bs8_s1(l.eN) + lane_get(s.off1, nch - 1) + TL1;
+        s.T2 = (bs8_s2_biased(l.eN) + lane_get(s.off2, nch - 1)) + TL2;
+    }
+#undef PS_ROW_STEPS
+#undef PS_BC_STEPS
+    return s;
+}
+
+// Screening levels of a window of n samples with the totals (T1, T2) about m: what every gain of the window is measured
+// in and against.  The caller leaves the screened path when !(Dtot > 0) (a window without variance).
+struct BsLevels {
+    double T1d, T2d, dn, Dtot;
+    float nf, rn, SSt; f2 cc;                          // n, 1 / n, sum of squared deviations of the whole window, log2 of its variance (twice)
+    float dlt, thr_log2, dthr, mabsf, vfloor;          // screen error, threshold, half width of its band (log2 units); largest |k|, variance floor
+};
+template <bool WIDE>
+__device__ __forceinline__ BsLevels bs_levels(BsSetup<WIDE> s, int n, int m, double thresh)
+{
+    BsLevels v;
+    v.T1d = uni(bs_d(s.T1)); v.T2d = uni(bs_d(s.T2));                 // window totals about m
+    v.dn = static_cast<double>(n); v.nf = static_cast<float>(n);
+    v.Dtot = v.dn * v.T2d - v.T1d * v.T1d;
+    v.rn = __builtin_amdgcn_rcpf(v.nf);
+    const float c0f = uni(__builtin_amdgcn_logf(static_cast<float>(v.Dtot) * v.rn * v.rn));
+    v.SSt = uni(static_cast<float>(v.Dtot) * v.rn);
+    v.cc = f2{c0f, c0f};
+    v.dlt = screen_delta_log2(n);
+    v.thr_log2 = static_cast<float>(thresh * 1.4426950408889634);
+    v.dthr = v.dlt + 3.0e-6f * v.nf + 1.0e-6f * fabsf(v.thr_log2);
+    // variance floor: the reference's own fp64 rounding (max|k|^2 * 2^-52 * n; max|k| <= |m| + max|k-m|) and the fp64 D
+    // above (kappa_m <= 2^26; wide digest: S2 is rounded to fp64 once, kappa_m <= 2^22 keeps D to 2^-30)
+    const float ymaxf = static_cast<float>(s.yabs);
+    v.mabsf = fabsf(static_cast<float>(m)) + ymaxf;
+    v.vfloor = uni(fmaxf(v.mabsf * v.mabsf * 1.0e-9f, ymaxf * ymaxf * (WIDE ? 2.4e-7f : 1.5e-8f)));
+    return v;
+}
+
+// Coarse pass (narrow digest), one call per lane; `gent` is the record of group G0 + min(lane, ngc), ngc >= 1 whole groups.
+// Lane L evaluates group boundary L -- block boundary tC = 32 (G0 + L) - gb0 of the window; its exact sums: the record's
+// entry plus the chunk offset -- like any boundary of the sweep (e; inr: a candidate in range, eok: valid and both variances
+// above the floor).  Then every group (L-1, L) is bounded: gain(k) <= ghb = max(G(L-1) + A(L-1), G(L) + A(L)) for all of its
+// 255 interior candidates, where A = bs_group_slack is what the group's prefix path can gain over its chord (one A per
+// boundary, from the larger amplitudes and the worse mean of its two neighbours); lanes 1 .. ngc.  a1i, a2, nlc: the
+// boundary's sums and the samples left of it, for the AUDIT walk.
+struct BsGroup { BsEval e; bool inr, eok; float ghb; int a1i, nlc; double a2; };
+__device__ __forceinline__ BsGroup bs_group_bound(BsGeom g, BsSetup<false> s, BsLevels v, uint4 gent, int ngc,
+                                                  int ps, int cand_lo, unsigned crange, int lane)
+{
+    BsGroup o;
+    const int n = g.n;
+    const int tC = static_cast<int>((g.G0 << BS_GRP_LOG) - g.gb0) + BS_GRP * lane;
+    const bool cin = lane <= ngc;
+    const int nlc = cin ? g.nh + 8 * tC : 1;                          // samples left of the boundary (clamped lanes: any valid value)
+    const int cb = min((g.gbl + (cin ? tC : 0)) >> BS_CHUNK_LOG, g.nch - 1) << 2;
+    const uint2 gentry = make_uint2(gent.x, gent.y);
+    const int a1 = bs_a1(gentry, bs_from_lane(s.off1, cb));
+    const double a2 = bs_a2(gentry, bs_from_lane(s.off2, cb));
+    const bool bval = cin && nlc >= 1 && nlc <= n - 1;
+    const int nlv = bval ? nlc : 1;
+    const double a1d = bs_d(a1), nld = static_cast<double>(nlv);
+    const BsEval e = bs_eval(a1d, a2, v.T1d - a1d, v.T2d - a2, nlv, n - nlv, v.cc, v.vfloor);
+    o.e = e;
+    o.inr = bval && static_cast<unsigned>(ps + nlc - cand_lo) <= crange;
+    o.eok = bval && e.okL && e.okR;
+    // the two neighbours of this boundary: group (L-1, L) -- amplitudes in the record of the lane below -- and (L, L+1)
+    const bool hasL = lane >= 1, hasR = lane < ngc;
+    const float D1r = __uint_as_float(gent.z), D2r = __uint_as_float(gent.w);
+    const float D1l = from_lane_below(D1r), D2l = from_lane_below(D2r);
+    const float D1 = fmaxf(hasL ? D1l : 0.0f, hasR ? D1r : 0.0f), D2 = fmaxf(hasL ? D2l : 0.0f, hasR ? D2r : 0.0f);
+    // mean of a neighbour minus the mean of the left part, well conditioned: (k S1g / 256 - a1) / k with an exact numerator
+    const int sgl = a1 - from_lane_below(a1), sgr = from_lane_above(a1) - a1;                  // S1 of the two groups
+    const double ig = 1.0 / static_cast<double>(BS_GRP_SAMPLES);
+    const float wLl = static_cast<float>(fma(nld, static_cast<double>(sgl) * ig, -a1d)) * e.r.x;
+    const float wLr = static_cast<float>(fma(nld, static_cast<double>(sgr) * ig, -a1d)) * e.r.x;
+    const float dmu = static_cast<float>(fma(v.dn, a1d, -(nld * v.T1d))) * e.r.x * e.r.y;   // mean left - mean right
+    const float A = bs_group_slack(e, D1, D2, hasL ? wLl : wLr, hasR ? wLr : wLl, dmu);
+    // (interior candidates have a variance of at least u P / Q on the left, u (n-Q) / (n-P) on the right: none below the floor)
+    const float nlf = static_cast<float>(nlv), nrf = v.nf - nlf;
+    const bool okF = e.u.x * nlf >= v.vfloor * (nlf + static_cast<float>(BS_GRP_SAMPLES)) &&
+                     e.u.y * nrf >= v.vfloor * (nrf + static_cast<float>(BS_GRP_SAMPLES));
+    const float GA = (o.eok && okF) ? e.g + A : INFINITY;             // (A itself is +inf when the expansion does not apply)
+    o.ghb = fmaxf(GA, from_lane_below(GA));
+    o.a1i = a1; o.nlc = nlc; o.a2 = a2;
+    return o;
+}
+
+// Rows to sweep after the coarse pass: bit r of the result (lane r works it out for row r).  Row r holds the blocks
+// 63 r + 1 .. min(63 r + 63, nblk) (block t lies left of boundary t); the group of a block is the group of its left boundary;
+// a group (L-1, L) is dead when its bound ghb lies below `level`, and a row is skipped -- not even loaded -- when all of its
+// blocks lie in dead groups.  Blocks outside the whole groups (the window's two ends) are always swept.
+__device__ __forceinline__ unsigned long long bs_live_rows(BsGeom g, int ngc, float ghb, float level, int lane)
+{
+    const unsigned long long dead = __ballot(lane >= 1 && lane <= ngc && ghb < level);
+    const int tl = BS_STRIDE * lane, th = min(tl + BS_STRIDE, g.nblk) - 1;
+    const int lo = static_cast<int>(((g.gb0 + tl) >> BS_GRP_LOG) - g.G0) + 1, hi = static_cast<int>(((g.gb0 + th) >> BS_GRP_LOG) - g.G0) + 1;
+    const unsigned long long span = ((2ull << (hi - lo)) - 1ull) << max(lo, 0);
+    return __ballot(lane < g.rows && !(lo >= 1 && hi <= ngc && (dead & span) == span));
+}
+
+// Next row of a live-row mask (-1: none left) and the mask without it (uniform).
+struct BsRow { int r; unsigned long long live; };
+__device__ __forceinline__ BsRow bs_take_row(unsigned long long live)
+{
+    return live == 0ull ? BsRow{-1, 0ull} : BsRow{__builtin_ctzll(live), live & (live - 1ull)};
+}
+
+// Chunk offsets of this lane's boundary in row r: lane L takes boundary t = 63 r + L; the row's boundaries lie in at most two chunks.
+template <bool WIDE> struct BsRowOff { typename BsTypes<WIDE>::s1_t o1; typename BsTypes<WIDE>::o2_t o2; };
+template <bool WIDE>
+__device__ __forceinline__ BsRowOff<WIDE> bs_row_offsets(BsGeom g, BsSetup<WIDE> s, int r, int lane)
+{
+    const int tb = g.gbl + BS_STRIDE * r;                              // (uniform) chunk-relative index of the row's first boundary
+    BsRowOff<WIDE> o;
+#if PS_ROW_OFFSETS_BPERMUTE
+    // every lane fetches the offsets of ITS chunk from the lane that holds them (ds_bpermute: three or four LDS-pipe
+    // instructions and the index) -- two v_readlane per value plus moves and selects were 22 instructions a row
+    const int cb = min((tb + lane) >> BS_CHUNK_LOG, g.nch - 1) << 2;
+    o.o1 = bs_from_lane(s.off1, cb);
+    o.o2 = bs_from_lane(s.off2, cb);
+#else
+    const int cA = min(tb >> BS_CHUNK_LOG, g.nch - 1), cB = min(cA + 1, g.nch - 1);
+    const int lsw = ((tb >> BS_CHUNK_LOG) + 1) * BS_CHUNK - tb;        // first lane in the second chunk (>= 64: none)
+    const bool second = lane >= lsw;
+    const auto o1A = lane_get(s.off1, cA), o1B = lane_get(s.off1, cB);   // (both read unconditionally: a select, not a branch)
+    const auto o2A = lane_get(s.off2, cA), o2B = lane_get(s.off2, cB);
+    o.o1 = second ? o1B : o1A;
+    o.o2 = second ? o2B : o2A;
+#endif
+    return o;
+}
+
+// Boundary J = ps + nl of row r (digest entry `cur`, chunk offsets `off`) and the block (J - 8, J) to its left.
+//   a1, a2, nl: exact sums of [ps, J) about m and their count;
+//   e: the screened gain of the boundary (bs_eval's arithmetic with the running nl and the right side from the totals); okL / okR
+//      are false past the window's end;
+//   inr: the boundary is a candidate in range (lane 0 of rows > 0 repeats a boundary already counted);
+//   aL, rlb, pokL: lg.x, r.x and okL of the lane below -- boundary t - 1, the block's left end;
+//   blk: the block has interior candidates in range; prunable: its corner bound is sound;
+//   h0, h1: the corner bound's two corners -- left side bounded from boundary t - 1, right side from this one; the bound is
+//      their maximum.
+template <bool WIDE> struct BsBoundary {
+    typename BsTypes<WIDE>::s1_t a1; typename BsTypes<WIDE>::s2_t a2; int nl;
+    BsEval e; bool inr; float aL, rlb; bool pokL, blk, prunable; float h0, h1;
+};
+template <bool WIDE>
+__device__ __forceinline__ BsBoundary<WIDE> bs_boundary(BsGeom g, BsSetup<WIDE> s, BsLevels v, typename BsTypes<WIDE>::E cur,
+                                                        BsRowOff<WIDE> off, int r, int ps, int cand_lo, unsigned crange, int lane)
+{
+    const float LOG2E = 1.4426950408889634f;
+    BsBoundary<WIDE> b;
+    const int nl0 = g.nh + 8 * lane;                                   // samples left of this lane's boundary in row 0
+    const int nl = nl0 + 8 * BS_STRIDE * r, J = ps + nl;
+    const float nlf = static_cast<float>(nl);
+    const double nld = static_cast<double>(nl);
+    b.a1 = bs_a1(cur, off.o1);
+    b.a2 = bs_a2(cur, off.o2);
+    b.nl = nl;
+    const double a1d = bs_d(b.a1), b1d = v.T1d - a1d;                  // (exact: |S1| < 2^53)
+    double a2d, b2d;
+    if constexpr (WIDE) { a2d = d_of_i64(b.a2); b2d = d_of_i64(s.T2 - b.a2); }
+    else { a2d = b.a2; b2d = v.T2d - b.a2; }
+    const double DL = fma(nld, a2d, -(a1d * a1d));
+    const double DR = fma(v.dn - nld, b2d, -(b1d * b1d));
+    const float nrf = v.nf - nlf;
+    const f2 D = {static_cast<float>(DL), static_cast<float>(DR)};
+    const f2 nv = {nlf, nrf};
+    const f2 rr = {__builtin_amdgcn_rcpf(nlf), __builtin_amdgcn_rcpf(nrf)};
+    const f2 u = D * rr * rr;
+    const f2 lgu = {__builtin_amdgcn_logf(u.x), __builtin_amdgcn_logf(u.y)};
+    const f2 lg = lgu - v.cc;
+    const f2 tt = nv * lg;
+    const bool valid = static_cast<unsigned>(nl - 1) < static_cast<unsigned>(g.n - 1);    // 1 <= nl <= n-1 (false past the end)
+    const bool okL = valid && u.x >= v.vfloor, okR = valid && u.y >= v.vfloor;
+    b.e.g = -(tt.x + tt.y); b.e.lg = lg; b.e.r = rr; b.e.u = u; b.e.okL = okL; b.e.okR = okR;
+    b.inr = static_cast<unsigned>(J - cand_lo) <= crange && (lane != 0 || r == 0);
+    b.aL = from_lane_below(lg.x); b.rlb = from_lane_below(rr.x);
+    b.pokL = from_lane_below(static_cast<int>(okL)) != 0;
+    b.blk = lane >= 1 && static_cast<unsigned>(J - 1 - cand_lo) <= crange + 6u;             // has interior candidates
+    const float nl0f = nlf - 8.0f, nlef = nlf - 1.0f;
+    const float nr0f = nrf + 8.0f, nref = nrf + 1.0f;
+    const float bR = lg.y, rre = rr.y;
+    const float cR0 = bR - 8.0f * LOG2E * rre;
+    const float cR1 = bR - LOG2E * rre;
+    const float cL1 = b.aL - 7.0f * LOG2E * b.rlb;
+    b.h0 = -fmaf(nl0f, b.aL, nr0f * cR0);
+    b.h1 = -fmaf(nlef, cL1, nref * cR1);
+    // (bitwise, not short-circuit: with && the compiler puts the bound under an exec-mask branch)
+    b.prunable = static_cast<bool>(static_cast<int>(b.pokL) & static_cast<int>(okR) & static_cast<int>(nl >= 9));
+    return b;
+}
+
 // One wave scans the window [ps, pe) of an event (samples at c.samples[base + .], event constants `er`).
 //
 // Setup (one memory round trip): the ragged head / tail samples, the totals of the <= 64 chunks the window touches (one
@@ -1252,14 +1555,10 @@ __device__ int scan_window_bs(const DevCfg &c, const EvRef &er, int64_t base, in
     typedef typename BsTypes<WIDE>::C BsC_t;
     typedef typename BsTypes<WIDE>::E ent_t;           // digest entry: 8 / 16 bytes
     const int lane = threadIdx.x & 63;                 // (one wave; possibly one of several in its workgroup)
-    const int n = pe - ps;
-    const int g0 = (ps + 7) & ~7, g1 = pe & ~7;
-    const int nblk = (g1 - g0) >> 3;
-    const long long gb0 = er.boff + (g0 >> 3);
-    const int gbl = static_cast<int>(gb0 & (BS_CHUNK - 1));            // chunk of boundary t: (gbl + t) >> 7
-    const int nch = ((gbl + nblk) >> BS_CHUNK_LOG) + 1;                // chunks touched
-    if (nblk < 4 || nch > BS_MAXCH || c.mode == MODE_EXACT || cand_lo < g0 || cand_hi > g1) {
-        // tiny or huge window, or candidates in the ragged head/tail (min_width < 8): exact scan straight from HBM
+    const BsGeom geo = bs_geom(er, ps, pe);
+    const int n = geo.n, g0 = geo.g0, nblk = geo.nblk, gbl = geo.gbl, rows = geo.rows;
+    if (geo.off_path(cand_lo, cand_hi) || c.mode == MODE_EXACT) {
+        // not a window for the screened path: exact scan straight from HBM
         wk.exact += 1;                                 // (counters are wave-uniform: scalar registers; lane 0 reports them)
         const long long ex = bs_scan_exact<DT>(bs_cold(c), base + ps, ps, n, cand_lo, cand_hi, thresh, &sh);
         bad |= static_cast<unsigned>(ex >> 32);
@@ -1268,23 +1567,10 @@ __device__ int scan_window_bs(const DevCfg &c, const EvRef &er, int64_t base, in
     PS_STAMP_AT(wk, 7);                                // (diagnostic build) time between scans: recursion control, stack
     PS_MARK(scan_begin);
     const int m = er.m;
-    const ent_t *bsw = static_cast<const ent_t *>(c.bsum) + gb0;      // bsw[t]: chunk prefix at boundary t = 0..nblk
-    const long long c0 = gb0 >> BS_CHUNK_LOG;
-    const int rows = (nblk + BS_STRIDE - 1) / BS_STRIDE;               // nblk + 1 boundaries, 63 new ones per row
+    const ent_t *bsw = static_cast<const ent_t *>(c.bsum) + geo.gb0;  // bsw[t]: chunk prefix at boundary t = 0..nblk
     auto row_load = [&](int r) { return bsw[min(max(r, 0) * BS_STRIDE + lane, nblk)]; };
-    // everything the window needs before its first boundary, issued together
-    const int nh = g0 - ps, nt = pe - g1;              // ragged head [ps, g0) and tail [g1, pe): <= 7 raw samples each
-    // (loaded by every lane from a clamped index and converted after all of the setup's loads are out: under a lane
-    //  condition the compiler finishes the conversion inside the branch and waits for the sample right there -- two
-    //  exposed round trips to HBM in front of the other loads, which is what rounds 1 and 2 did)
-    const int ht_idx = lane < 32 ? ps + min(lane, max(nh - 1, 0)) : min(g1 + min(lane - 32, max(nt - 1, 0)), pe - 1);
-    const typename Raw<DT>::type ht_raw = static_cast<const typename Raw<DT>::type *>(c.samples)[base + ht_idx];
-    // (chunk totals likewise: every lane loads a clamped entry, lanes beyond the window's chunks are masked afterwards)
-    const long long cidx = c0 + min(lane, nch - 1);
-    int4 ct, cm = make_int4(0, 0, 0, 0);
-    if constexpr (WIDE) { ct = c.chunk_tot[2 * cidx]; cm = c.chunk_tot[2 * cidx + 1]; }
-    else ct = c.chunk_tot[cidx];
-    const ent_t e0 = bsw[0], eN = bsw[nblk];
+    // everything the window needs before its first boundary, issued together: the shared setup loads, then this scan's own
+    const BsSetupLoads<DT> sl = bs_setup_loads<DT>(c, geo, base, ps, pe, bsw, lane);
     // One sampled boundary per lane, spread over the window -- in the instances that skip rows (spine, bridges).  Subtree
     // windows rarely hold a split (95 % of the jobs find nothing): they start at the threshold level without the sampling
     // pass (no gather of 64 scattered entries, ~100 instructions less) and RAISE the level from the gains seen so far
@@ -1296,17 +1582,16 @@ __device__ int scan_window_bs(const DevCfg &c, const EvRef &er, int64_t base, in
     constexpr bool GROUPS = !WIDE;
     constexpr bool SAMPLE = WIDE && (ROWSKIP || WIDE || PS_TREE_SAMPLE);      // (wide digest: filtered events, whose subtree windows mostly DO hold splits)
     const int tS = SAMPLE ? min(nblk, lane * rows) : 0;
-    ent_t smp = e0;
+    ent_t smp = sl.e0;
     if constexpr (SAMPLE) smp = bsw[tS];
-    // group records: lane L takes the group boundary c = L, block boundary tC = 32 (G0 + L) - gb0 of the window -- the
-    // record of group G0 + L holds the exact sums at that boundary and the amplitudes of the group to its RIGHT
-    const long long G0 = (gb0 + BS_GRP - 1) >> BS_GRP_LOG;
+    // group records: lane L takes the group boundary c = L (bs_group_bound) -- the record of group G0 + L holds the exact
+    // sums at that boundary and the amplitudes of the group to its RIGHT
     const bool coarse = GROUPS && c.grp != nullptr && c.prune && rows <= 64;                   // (uniform)
-    const int ngc = coarse ? min(static_cast<int>(((gb0 + nblk) >> BS_GRP_LOG) - G0), 63) : 0;  // groups entirely inside the window (<= 0: none)
+    const int ngc = coarse ? geo.whole_groups() : 0;
     uint4 gent = make_uint4(0u, 0u, 0u, 0u);
     if constexpr (GROUPS) {
-        // (unconditional load from a clamped index, like the rest of the setup: see above)
-        const uint4 *gp = coarse ? static_cast<const uint4 *>(c.grp) + G0 : reinterpret_cast<const uint4 *>(bsw);
+        // (unconditional load from a clamped index, like the rest of the setup: see bs_setup_loads)
+        const uint4 *gp = coarse ? static_cast<const uint4 *>(c.grp) + geo.G0 : reinterpret_cast<const uint4 *>(bsw);
         gent = gp[coarse ? min(lane, max(ngc, 0)) : 0];
     }
     ent_t ring[BS_D];                                  // rows in flight
@@ -1317,91 +1602,22 @@ __device__ int scan_window_bs(const DevCfg &c, const EvRef &er, int64_t base, in
     auto pre_row = [&](int i) { return !edge_rows ? i : i == 0 ? 0 : i == 1 ? rows - 1 : i == 2 ? 1 : rows - 2; };
 #pragma unroll
     for (int i = 0; i < BS_D; ++i) ring[i] = row_load(pre_row(i));
-    if (lane >= nch) ct = make_int4(0, 0, 0, 0);
-    const int yab = lane < nch ? (WIDE ? cm.x : ct.y) : 0;
-    // head / tail sums (lanes 0..7 head, 32..39 tail)
-    const bool ht_in = lane < nh || (lane >= 32 && lane - 32 < nt);
-    const int yht = ht_in ? bs_count_of<DT>(c, ht_raw) - m : 0;
-    s1_t H1, TL1;
-    s2_t H2, TL2;
-    if constexpr (WIDE) {
-        const long long h1 = oct_sum(static_cast<long long>(yht)), h2 = oct_sum(static_cast<long long>(yht) * static_cast<long long>(yht));
-        H1 = lane_get(h1, 7); H2 = lane_get(h2, 7); TL1 = lane_get(h1, 39); TL2 = lane_get(h2, 39);
-    } else {
-        const int h1 = oct_sum(yht), h2 = oct_sum(yht * yht);      // 7 * 2^28 < 2^31
-        H1 = lane_get(h1, 7); H2 = static_cast<double>(lane_get(h2, 7)); TL1 = lane_get(h1, 39); TL2 = static_cast<double>(lane_get(h2, 39));
-    }
-    // chunk offsets: exclusive scan of the chunk totals over the lanes (rows of 16 suffice for windows up to 15 000 samples)
-    const bool many = nch > 16;                        // (uniform)
-    s1_t off1;                                         // lane c: sums of [ps, first boundary of chunk c) minus that chunk's prefix base
-    o2_t off2;
-    s1_t T1;
-    s2_t T2;
-    int yabs = yab;
-    {
-#define PS_ROW_STEPS(X) X(0x111, 0xf) X(0x112, 0xf) X(0x114, 0xf) X(0x118, 0xf)
-#define PS_BC_STEPS(X) X(0x142, 0xa) X(0x143, 0xc)
-#define PS_MSTEP(CTRL, RM) { yabs = max(yabs, dpp_mov<CTRL, RM>(0, yabs)); }
-        PS_ROW_STEPS(PS_MSTEP)
-        if (many) { PS_BC_STEPS(PS_MSTEP) }
-#undef PS_MSTEP
-        yabs = lane_get(yabs, many ? 63 : 15);
-        if constexpr (WIDE) {
-            const long long cs1 = i64_of(ct.x, ct.y), cs2 = i64_of(ct.z, ct.w);
-            long long i1 = cs1, i2 = cs2;
-#define PS_STEP(CTRL, RM) { const int l1_ = dpp_mov<CTRL, RM>(0, static_cast<int>(i1)), h1_ = dpp_mov<CTRL, RM>(0, static_cast<int>(i1 >> 32)); \
-                            const int l2_ = dpp_mov<CTRL, RM>(0, static_cast<int>(i2)), h2_ = dpp_mov<CTRL, RM>(0, static_cast<int>(i2 >> 32)); \
-                            i1 += i64_of(l1_, h1_); i2 += i64_of(l2_, h2_); }
-            PS_ROW_STEPS(PS_STEP)
-            if (many) { PS_BC_STEPS(PS_STEP) }
-#undef PS_STEP
-            off1 = (i1 - cs1) + (H1 - i64_of(e0.x, e0.y));
-            off2 = (i2 - cs2) + (H2 - i64_of(e0.z, e0.w));
-            T1 = i64_of(eN.x, eN.y) + lane_get(off1, nch - 1) + TL1;
-            T2 = i64_of(eN.z, eN.w) + lane_get(off2, nch - 1) + TL2;
-        } else {
-            const int cs1 = ct.x;
-            const double cs2 = bs_d(i64_of(ct.z, ct.w));                   // < 2^38: exact
-            int i1 = cs1;
-            double i2 = cs2;
-#define PS_STEP(CTRL, RM) { i1 += dpp_mov<CTRL, RM>(0, i1); i2 += dpp_movd<CTRL, RM>(i2); }
-            PS_ROW_STEPS(PS_STEP)
-            if (many) { PS_BC_STEPS(PS_STEP) }
-#undef PS_STEP
-            off1 = (i1 - cs1) + (H1 - bs8_s1(e0));
-            const double o2 = (i2 - cs2) + (H2 - static_cast<double>(bs8_s2(e0)));   // exact integers below 2^45
-            off2 = o2 - BS_BIAS;
-            T1 = bs8_s1(eN) + lane_get(off1, nch - 1) + TL1;
-            T2 = (bs8_s2_biased(eN) + lane_get(off2, nch - 1)) + TL2;
-        }
-#undef PS_ROW_STEPS
-#undef PS_BC_STEPS
-    }
+    const BsSetup<WIDE> su = bs_setup_sums<DT>(c, geo, m, sl, lane);
+    const s1_t off1 = su.off1, T1 = su.T1;             // (the names the rest of the scan uses)
+    const o2_t off2 = su.off2; const s2_t T2 = su.T2;
     PS_STAMP_AT(wk, 5);                                // setup loads + head / tail / chunk scans
     PS_MARK(setup_done);
-    const double T1d = uni(bs_d(T1)), T2d = uni(bs_d(T2));                // window totals about m
-    const double dn = static_cast<double>(n);
-    const double Dtot = dn * T2d - T1d * T1d;
-    if (!(Dtot > 0.0)) {
+    const BsLevels lv = bs_levels<WIDE>(su, n, m, thresh);
+    if (!(lv.Dtot > 0.0)) {
         wk.exact += 1;                                 // (counters are wave-uniform: scalar registers; lane 0 reports them)
         const long long ex = bs_scan_exact<DT>(bs_cold(c), base + ps, ps, n, cand_lo, cand_hi, thresh, &sh);
         bad |= static_cast<unsigned>(ex >> 32);
         return uni(static_cast<int>(ex));
     }
-    const float nf = static_cast<float>(n);
-    const float rn = __builtin_amdgcn_rcpf(nf);
-    const float c0f = uni(__builtin_amdgcn_logf(static_cast<float>(Dtot) * rn * rn));
-    const float SSt = uni(static_cast<float>(Dtot) * rn);                  // sum of squared deviations of the whole window
-    const f2 cc = {c0f, c0f};
-    const float dlt = screen_delta_log2(n);
-    const float thr_log2 = static_cast<float>(thresh * 1.4426950408889634);
-    const float dthr = dlt + 3.0e-6f * nf + 1.0e-6f * fabsf(thr_log2);
+    const double T1d = lv.T1d, T2d = lv.T2d;
+    const float rn = lv.rn, SSt = lv.SSt, dlt = lv.dlt, thr_log2 = lv.thr_log2, dthr = lv.dthr, vfloor = lv.vfloor, mabsf = lv.mabsf;
+    const f2 cc = lv.cc;
     const float LOG2E = 1.4426950408889634f;
-    // variance floor: the reference's own fp64 rounding (max|k|^2 * 2^-52 * n; max|k| <= |m| + max|k-m|) and the fp64 D
-    // above (kappa_m <= 2^26; wide digest: S2 is rounded to fp64 once, kappa_m <= 2^22 keeps D to 2^-30)
-    const float ymaxf = static_cast<float>(yabs);
-    const float mabsf = fabsf(static_cast<float>(m)) + ymaxf;
-    const float vfloor = uni(fmaxf(mabsf * mabsf * 1.0e-9f, ymaxf * ymaxf * (WIDE ? 2.4e-7f : 1.5e-8f)));
     const unsigned crange = static_cast<unsigned>(cand_hi - cand_lo);
     BsQ_t *queue = reinterpret_cast<BsQ_t *>(sh.q);
     int2 *qblk = reinterpret_cast<int2 *>(queue + BS_QN);             // the queued block's own sums (S1, S2 of its 8 samples; narrow digest)
@@ -1452,59 +1668,24 @@ __device__ int scan_window_bs(const DevCfg &c, const EvRef &er, int64_t base, in
         }
     }
     // ---- coarse pass (narrow digest) ---------------------------------------------------------------------------------
-    // Lane L evaluates group boundary L (its exact sums: the record's entry plus the chunk offset) like any boundary of
-    // the sweep; the largest of those gains sets the pruning level, as the sampled boundaries used to.  Then every group
-    // (L-1, L) is bounded: gain(k) <= max(G(L-1) + A(L-1), G(L) + A(L)) for all of its 255 interior candidates, where
-    // A = bs_group_slack is what the group's prefix path can gain over its chord (one A per boundary, from the larger
-    // amplitudes and the worse mean of its two neighbours).  Rows of the sweep whose blocks all lie in groups below the
-    // pruning level are not swept -- nor loaded.  Blocks outside the groups (the window's two ends) are always swept.
+    // bs_group_bound evaluates the group boundaries and bounds the groups between them; the largest of the boundary gains sets the
+    // pruning level, as the sampled boundaries used to.  Rows whose blocks all lie in groups below it are not swept (bs_live_rows).
     float ghb = INFINITY;                              // bound of group (lane - 1, lane), lanes 1 .. ngc
     if constexpr (GROUPS) {
         if (ngc >= 1) {
-            const int tC = static_cast<int>((G0 << BS_GRP_LOG) - gb0) + BS_GRP * lane;
-            const bool cin = lane <= ngc;
-            const int nlc = cin ? nh + 8 * tC : 1;                          // samples left of the boundary (clamped lanes: any valid value)
-            const int cb = min((gbl + (cin ? tC : 0)) >> BS_CHUNK_LOG, nch - 1) << 2;
-            const uint2 gentry = make_uint2(gent.x, gent.y);
-            const s1_t a1 = bs_a1(gentry, static_cast<s1_t>(bs_from_lane(off1, cb)));
-            const s2_t a2 = bs_a2(gentry, static_cast<o2_t>(bs_from_lane(off2, cb)));
-            const bool bval = cin && nlc >= 1 && nlc <= n - 1;
-            const int nlv = bval ? nlc : 1;
-            const double a1d = bs_d(a1), nld = static_cast<double>(nlv);
-            const BsEval e = bs_eval(a1d, bs_d(a2), T1d - a1d, T2d - bs_d(a2), nlv, n - nlv, cc, vfloor);
-            const bool inr = bval && static_cast<unsigned>(ps + nlc - cand_lo) <= crange;
-            const bool eok = bval && e.okL && e.okR;
-            float bm = (inr && eok) ? e.g : -INFINITY;
-            bm = wave_max_f32(bm);
+            const BsGroup cg = bs_group_bound(geo, su, lv, gent, ngc, ps, cand_lo, crange, lane);
+            const float bm = wave_max_f32((cg.inr && cg.eok) ? cg.e.g : -INFINITY);
             Tprune = fmaxf(thr_log2 - dthr, bm - 2.0f * dlt) - 2.0f * dlt;
-            // the two neighbours of this boundary: group (L-1, L) -- amplitudes in the record of the lane below -- and (L, L+1)
-            const bool hasL = lane >= 1, hasR = lane < ngc;
-            const float D1r = __uint_as_float(gent.z), D2r = __uint_as_float(gent.w);
-            const float D1l = from_lane_below(D1r), D2l = from_lane_below(D2r);
-            const float D1 = fmaxf(hasL ? D1l : 0.0f, hasR ? D1r : 0.0f), D2 = fmaxf(hasL ? D2l : 0.0f, hasR ? D2r : 0.0f);
-            // mean of a neighbour minus the mean of the left part, well conditioned: (k S1g / 256 - a1) / k with an exact numerator
-            const int a1i = static_cast<int>(a1);
-            const int sgl = a1i - from_lane_below(a1i), sgr = from_lane_above(a1i) - a1i;          // S1 of the two groups
-            const double ig = 1.0 / static_cast<double>(BS_GRP_SAMPLES);
-            const float wLl = static_cast<float>(fma(nld, static_cast<double>(sgl) * ig, -a1d)) * e.r.x;
-            const float wLr = static_cast<float>(fma(nld, static_cast<double>(sgr) * ig, -a1d)) * e.r.x;
-            const float dmu = static_cast<float>(fma(dn, a1d, -(nld * T1d))) * e.r.x * e.r.y;   // mean left - mean right
-            const float A = bs_group_slack(e, D1, D2, hasL ? wLl : wLr, hasR ? wLr : wLl, dmu);
-            // (interior candidates have a variance of at least u P / Q on the left, u (n-Q) / (n-P) on the right: none below the floor)
-            const float nlf = static_cast<float>(nlv), nrf = nf - nlf;
-            const bool okF = e.u.x * nlf >= vfloor * (nlf + static_cast<float>(BS_GRP_SAMPLES)) &&
-                             e.u.y * nrf >= vfloor * (nrf + static_cast<float>(BS_GRP_SAMPLES));
-            const float GA = (eok && okF) ? e.g + A : INFINITY;             // (A itself is +inf when the expansion does not apply)
-            ghb = fmaxf(GA, from_lane_below(GA));
+            ghb = cg.ghb;
             hitlike = true;
             if constexpr (AUDIT) {
                 // lane L walks the 255 candidates inside its group (L-1, L) from the sums at the boundary below
-                const int a1b = from_lane_below(a1i);
-                const double a2b = __hiloint2double(from_lane_below(__double2hiint(bs_d(a2))), from_lane_below(__double2loint(bs_d(a2))));
+                const int a1b = from_lane_below(cg.a1i);
+                const double a2b = __hiloint2double(from_lane_below(__double2hiint(cg.a2)), from_lane_below(__double2loint(cg.a2)));
                 if (lane >= 1 && lane <= ngc) {
                     int x1 = a1b;
                     double x2 = a2b;
-                    const int nl0g = nlc - BS_GRP_SAMPLES;
+                    const int nl0g = cg.nlc - BS_GRP_SAMPLES;
                     float gmx = -INFINITY;
                     for (int j = 1; j < BS_GRP_SAMPLES; ++j) {
                         const int y = bs_count<DT>(c, base + ps + nl0g + j - 1) - m;
@@ -1541,7 +1722,6 @@ __device__ int scan_window_bs(const DevCfg &c, const EvRef &er, int64_t base, in
             ccount += __popcll(cm_);                                                                          \
         }                                                                                                     \
     }
-    const int nl0 = nh + 8 * lane;                     // samples left of this lane's boundary in row 0
     ps_sync<64>();                                     // previous user of sh.q (this wave) is done
     for (int phase = 0; phase < 2; ++phase) {
         Top2 top = {-INFINITY, -INFINITY, -1};
@@ -1553,13 +1733,7 @@ __device__ int scan_window_bs(const DevCfg &c, const EvRef &er, int64_t base, in
         unsigned long long live = ~0ull;
         if constexpr (GROUPS) {
             if (hitlike) {
-                // row r holds the blocks 63 r + 1 .. min(63 r + 63, nblk) (block t lies left of boundary t); the group of a block
-                // is the group of its left boundary; bit L of `dead`: group (L-1, L) is below the pruning level
-                const unsigned long long dead = __ballot(lane >= 1 && lane <= ngc && ghb < Tprune);
-                const int tl = BS_STRIDE * lane, th = min(tl + BS_STRIDE, nblk) - 1;
-                const int lo = static_cast<int>(((gb0 + tl) >> BS_GRP_LOG) - G0) + 1, hi = static_cast<int>(((gb0 + th) >> BS_GRP_LOG) - G0) + 1;
-                const unsigned long long span = ((2ull << (hi - lo)) - 1ull) << max(lo, 0);
-                live = __ballot(lane < rows && !(lo >= 1 && hi <= ngc && (dead & span) == span));
+                live = bs_live_rows(geo, ngc, ghb, Tprune, lane);
                 if constexpr (AUDIT) live = __ballot(lane < rows);
             }
         } else if (hitlike) {
@@ -1576,24 +1750,20 @@ __device__ int scan_window_bs(const DevCfg &c, const EvRef &er, int64_t base, in
         // run on a pair of CUs at once, and the instruction cache of the pair holds 64 KB).
         int rbase = 0;                                 // (uniform) first row of the mask
         if (!hitlike) live = rows >= 64 ? ~0ull : (1ull << rows) - 1ull;
+#else
+        constexpr int rbase = 0;
+#endif
         auto take_row = [&]() {                        // next live row, -1: none left (uniform)
-            if (live == 0ull) {
-                if (hitlike || rbase + 64 >= rows) return -1;
+#if PS_ONE_ROW_LOOP
+            if (live == 0ull && !hitlike && rbase + 64 < rows) {
                 rbase += 64;
                 live = rows - rbase >= 64 ? ~0ull : (1ull << (rows - rbase)) - 1ull;
             }
-            const int r = __builtin_ctzll(live);
-            live &= live - 1ull;
-            return rbase + r;
-        };
-#else
-        auto take_row = [&]() {                        // next live row, -1: none left (uniform)
-            if (live == 0ull) return -1;
-            const int r = __builtin_ctzll(live);
-            live &= live - 1ull;
-            return r;
-        };
 #endif
+            const BsRow t = bs_take_row(live);
+            live = t.live;
+            return t.r < 0 ? t.r : rbase + t.r;
+        };
         auto drain = [&]() {
             // drain: interior candidates of the queued blocks
             PS_MARK(drain_begin);
@@ -1706,72 +1876,16 @@ __device__ int scan_window_bs(const DevCfg &c, const EvRef &er, int64_t base, in
                 Tprune = fmaxf(Tprune, fmaxf(thr_log2 - dthr, bx - 2.0f * dlt) - 2.0f * dlt);
             }
         };
-        // row r: lane L takes boundary t = 63 r + L (J = g0 + 8 t); the row's boundaries lie in at most two chunks
+        // row r: lane L takes boundary t = 63 r + L (bs_boundary); ge: the boundary itself as a candidate, hb: the corner bound of its block
         struct RowOut { s1_t a1; s2_t a2; int nl; float ge, hb; bool blk, prunable, unsure; };
-        auto row_eval = [&](int r, const ent_t &cur_in) -> RowOut {
+        auto row_eval = [&](int r, const ent_t &cur) -> RowOut {
             PS_MARK(row_eval_begin);
-            ent_t cur = cur_in;
 #ifdef PS_STAMP
             wk.ph[8] += 1;                                                 // (diagnostic build) rows swept
 #endif
-            const bool first_row = r == 0;
-            const int tb = gbl + BS_STRIDE * r;                            // (uniform) chunk-relative index of the row's first boundary
-#if PS_ROW_OFFSETS_BPERMUTE
-            // every lane fetches the offsets of ITS chunk from the lane that holds them (ds_bpermute: three or four LDS-pipe
-            // instructions and the index) -- two v_readlane per value plus moves and selects were 22 instructions a row
-            const int cb = min((tb + lane) >> BS_CHUNK_LOG, nch - 1) << 2;
-            const s1_t o1 = bs_from_lane(off1, cb);
-            const o2_t o2 = bs_from_lane(off2, cb);
-#else
-            const int cA = min(tb >> BS_CHUNK_LOG, nch - 1), cB = min(cA + 1, nch - 1);
-            const int lsw = ((tb >> BS_CHUNK_LOG) + 1) * BS_CHUNK - tb;    // first lane in the second chunk (>= 64: none)
-            const bool second = lane >= lsw;
-            const s1_t o1A = lane_get(off1, cA), o1B = lane_get(off1, cB);   // (both read unconditionally: a select, not a branch)
-            const o2_t o2A = lane_get(off2, cA), o2B = lane_get(off2, cB);
-            const s1_t o1 = second ? o1B : o1A;
-            const o2_t o2 = second ? o2B : o2A;
-#endif
-            const int nl = nl0 + 8 * BS_STRIDE * r, J = ps + nl;
-            const float nlf = static_cast<float>(nl);
-            const double nld = static_cast<double>(nl);
-            const s1_t a1 = bs_a1(cur, o1);
-            const s2_t a2 = bs_a2(cur, o2);
-            // screened gain of the boundary (bs_eval, with the running nl and the right side from the totals)
-            const double a1d = bs_d(a1), b1d = T1d - a1d;                  // (exact: |S1| < 2^53)
-            double a2d, b2d;
-            if constexpr (WIDE) { a2d = d_of_i64(a2); b2d = d_of_i64(T2 - a2); }
-            else { a2d = a2; b2d = T2d - a2; }
-            const double DL = fma(nld, a2d, -(a1d * a1d));
-            const double DR = fma(dn - nld, b2d, -(b1d * b1d));
-            const float nrf = nf - nlf;
-            const f2 D = {static_cast<float>(DL), static_cast<float>(DR)};
-            const f2 nv = {nlf, nrf};
-            const f2 rr = {__builtin_amdgcn_rcpf(nlf), __builtin_amdgcn_rcpf(nrf)};
-            const f2 u = D * rr * rr;
-            const f2 lgu = {__builtin_amdgcn_logf(u.x), __builtin_amdgcn_logf(u.y)};
-            const f2 lg = lgu - cc;
-            const f2 tt = nv * lg;
-            const float g = -(tt.x + tt.y);
-            const bool valid = static_cast<unsigned>(nl - 1) < static_cast<unsigned>(n - 1);    // 1 <= nl <= n-1 (false past the end)
-            const bool okL = valid && u.x >= vfloor, okR = valid && u.y >= vfloor;
-            // the boundary itself as a candidate (lane 0 of rows > 0 repeats a boundary already counted)
-            const bool inr = static_cast<unsigned>(J - cand_lo) <= crange && (lane != 0 || first_row);
-            const float ge = (inr && okL && okR) ? g : -INFINITY;
-            // the block (J - 8, J): left side bounded from boundary t-1 (the lane below), right side from this one
-            const float aL = from_lane_below(lg.x), rlb = from_lane_below(rr.x);
-            const bool pokL = from_lane_below(static_cast<int>(okL)) != 0;
-            const bool blk = lane >= 1 && static_cast<unsigned>(J - 1 - cand_lo) <= crange + 6u;   // has interior candidates
-            const float nl0f = nlf - 8.0f, nlef = nlf - 1.0f;
-            const float nr0f = nrf + 8.0f, nref = nrf + 1.0f;
-            const float bR = lg.y, rre = rr.y;
-            const float cR0 = bR - 8.0f * LOG2E * rre;
-            const float cR1 = bR - LOG2E * rre;
-            const float cL1 = aL - 7.0f * LOG2E * rlb;
-            const float h0 = -fmaf(nl0f, aL, nr0f * cR0);
-            const float h1 = -fmaf(nlef, cL1, nref * cR1);
-            // (bitwise, not short-circuit: with && the compiler puts the bound under an exec-mask branch)
-            const bool prunable = static_cast<bool>(static_cast<int>(pokL) & static_cast<int>(okR) & static_cast<int>(nl >= 9));
-            return RowOut{a1, a2, nl, ge, fmaxf(h0, h1), blk, prunable, inr && !(okL && okR)};
+            const BsBoundary<WIDE> b = bs_boundary<WIDE>(geo, su, lv, cur, bs_row_offsets<WIDE>(geo, su, r, lane), r, ps, cand_lo, crange, lane);
+            const bool ok = b.e.okL && b.e.okR;
+            return RowOut{b.a1, b.a2, b.nl, (b.inr && ok) ? b.e.g : -INFINITY, fmaxf(b.h0, b.h1), b.blk, b.prunable, b.inr && !ok};
         };
         // (the part with side effects, in row order: per-lane top-2, the block queue, the contender list)
         auto row_commit = [&](const RowOut &o) {
@@ -1957,14 +2071,17 @@ __device__ __forceinline__ int scan_window_ph(const DevCfg &c, const EvRef &er, 
 
 // ---- the window screen: "proven empty" or "undecided", and nothing else ----------------------------------
 // What a window costs that ends "no split" -- 95 % of the subtree jobs -- without the machinery of the windows that do not:
-// scan_window_bs's setup, its coarse pass over the group records, its sweep of the live rows, one comparison.  No LDS, no
-// block queue, no top-2, no contender list, no second phase, no sample fetch; the screen decides nothing but "empty".
+// geometry (bs_geom), setup (bs_setup_loads, bs_setup_sums), levels (bs_levels), the coarse pass over the group records
+// (bs_group_bound), the live rows (bs_live_rows), and per row bs_boundary and one comparison each.  No LDS, no block queue,
+// no top-2, no contender list, no second phase, no sample fetch; the screen decides nothing but "empty".
 // Narrow digest only.  Returns true ("the reference finds no split in [ps, pe)") under exactly the inequalities under which
-// scan_window_bs returns -1 without looking at a sample (docs/BOUNDS.md; nothing new is bounded here):
-//   - every boundary candidate in range has a screened gain below the band,   ge < thr_log2 - dthr,  and none is `unsure`;
-//   - every group of a row that is not swept is bounded below  T = (thr_log2 - dthr) - 2 dlt  (bs_group_slack) -- T is what
-//     Tprune is in scan_window_bs when no gain reaches the band, and Tprune only rises from there;
-//   - every block with interior candidates is bounded below T: by the corner bound of the sweep, or else by bs_block_bound2
+// scan_window_bs returns -1 without looking at a sample (docs/BOUNDS.md).  Both call the same helpers, so the screen states no
+// inequality of its own; what it adds are comparisons of their results:
+//   - every boundary candidate in range (bs_group_bound, bs_boundary: inr) has a screened gain below the band,
+//     e.g < thr_log2 - dthr,  and none is `unsure` (a variance below bs_levels' floor);
+//   - every group of a row that is not swept is bounded below  T = (thr_log2 - dthr) - 2 dlt  (bs_group_bound's ghb) -- T is
+//     what Tprune is in scan_window_bs when no gain reaches the band, and Tprune only rises from there;
+//   - every block with interior candidates is bounded below T: by bs_boundary's corner bound, or else by bs_block_bound2
 //     from both of its boundaries (what the drain's filter does with a queued block, here on the spot: the left boundary
 //     is the lane below's; lane 0 repeats the previous row's last boundary, so no row needs its predecessor).
 // Everything else is false ("undecided": costs time only -- the full scan takes the window): wherever scan_window_bs would
@@ -1977,170 +2094,50 @@ __device__ __forceinline__ bool screen_window_bs(const DevCfg &c, const EvRef &e
 {
     static_assert(!bs_wide<DT>(), "the window screen reads the narrow digest");
     const int lane = threadIdx.x & 63;
-    const int n = pe - ps;
-    const int g0 = (ps + 7) & ~7, g1 = pe & ~7;
-    const int nblk = (g1 - g0) >> 3;
-    const long long gb0 = er.boff + (g0 >> 3);
-    const int gbl = static_cast<int>(gb0 & (BS_CHUNK - 1));
-    const int nch = ((gbl + nblk) >> BS_CHUNK_LOG) + 1;
-    if (nblk < 4 || nch > BS_MAXCH || c.mode != MODE_FAST || cand_lo < g0 || cand_hi > g1) return false;
-    const int rows = (nblk + BS_STRIDE - 1) / BS_STRIDE;
-    const long long G0 = (gb0 + BS_GRP - 1) >> BS_GRP_LOG;
-    if (c.grp == nullptr || !c.prune || rows > 64) return false;
-    const int ngc = min(static_cast<int>(((gb0 + nblk) >> BS_GRP_LOG) - G0), 63);
+    const BsGeom geo = bs_geom(er, ps, pe);
+    if (geo.off_path(cand_lo, cand_hi) || c.mode != MODE_FAST) return false;
+    if (c.grp == nullptr || !c.prune || geo.rows > 64) return false;
+    const int ngc = geo.whole_groups();
     if (ngc < 1) return false;
-    const int m = er.m;
-    const uint2 *bsw = static_cast<const uint2 *>(c.bsum) + gb0;
-    const long long c0 = gb0 >> BS_CHUNK_LOG;
+    const int n = geo.n, nblk = geo.nblk, rows = geo.rows;
+    const uint2 *bsw = static_cast<const uint2 *>(c.bsum) + geo.gb0;
     auto row_load = [&](int r) { return bsw[min(max(r, 0) * BS_STRIDE + lane, nblk)]; };
-    // setup loads, issued together (as in scan_window_bs: clamped indices, no lane conditions)
-    const int nh = g0 - ps, nt = pe - g1;
-    const int ht_idx = lane < 32 ? ps + min(lane, max(nh - 1, 0)) : min(g1 + min(lane - 32, max(nt - 1, 0)), pe - 1);
-    const typename Raw<DT>::type ht_raw = static_cast<const typename Raw<DT>::type *>(c.samples)[base + ht_idx];
-    int4 ct = c.chunk_tot[c0 + min(lane, nch - 1)];
-    const uint2 e0 = bsw[0], eN = bsw[nblk];
-    const uint4 gent = (static_cast<const uint4 *>(c.grp) + G0)[min(lane, ngc)];
-    uint2 ring[2] = {row_load(0), row_load(rows - 1)};                     // the rows of the window's two ends: practically always live
-    if (lane >= nch) ct = make_int4(0, 0, 0, 0);
-    const bool ht_in = lane < nh || (lane >= 32 && lane - 32 < nt);
-    const int yht = ht_in ? bs_count_of<DT>(c, ht_raw) - m : 0;
-    const int h1 = oct_sum(yht), h2 = oct_sum(yht * yht);
-    const int H1 = lane_get(h1, 7), TL1 = lane_get(h1, 39);
-    const double H2 = static_cast<double>(lane_get(h2, 7)), TL2 = static_cast<double>(lane_get(h2, 39));
-    // chunk offsets: exclusive scan of the chunk totals over the lanes
-    const bool many = nch > 16;
-    int yabs = ct.y;
-    const int cs1 = ct.x;
-    const double cs2 = bs_d(i64_of(ct.z, ct.w));
-    int i1 = cs1;
-    double i2 = cs2;
-#define PS_ROW_STEPS(X) X(0x111, 0xf) X(0x112, 0xf) X(0x114, 0xf) X(0x118, 0xf)
-#define PS_BC_STEPS(X) X(0x142, 0xa) X(0x143, 0xc)
-#define PS_STEP(CTRL, RM) { yabs = max(yabs, dpp_mov<CTRL, RM>(0, yabs)); i1 += dpp_mov<CTRL, RM>(0, i1); i2 += dpp_movd<CTRL, RM>(i2); }
-    PS_ROW_STEPS(PS_STEP)
-    if (many) { PS_BC_STEPS(PS_STEP) }
-#undef PS_STEP
-#undef PS_ROW_STEPS
-#undef PS_BC_STEPS
-    yabs = lane_get(yabs, many ? 63 : 15);
-    const int off1 = (i1 - cs1) + (H1 - bs8_s1(e0));
-    const double off2 = ((i2 - cs2) + (H2 - static_cast<double>(bs8_s2(e0)))) - BS_BIAS;
-    const int T1 = bs8_s1(eN) + lane_get(off1, nch - 1) + TL1;
-    const double T2 = (bs8_s2_biased(eN) + lane_get(off2, nch - 1)) + TL2;
-    const double T1d = uni(bs_d(T1)), T2d = uni(T2);
-    const double dn = static_cast<double>(n);
-    const double Dtot = dn * T2d - T1d * T1d;
-    if (!(Dtot > 0.0)) return false;
-    const float nf = static_cast<float>(n);
-    const float rn = __builtin_amdgcn_rcpf(nf);
-    const float c0f = uni(__builtin_amdgcn_logf(static_cast<float>(Dtot) * rn * rn));
-    const float SSt = uni(static_cast<float>(Dtot) * rn);
-    const f2 cc = {c0f, c0f};
-    const float dlt = screen_delta_log2(n);
-    const float thr_log2 = static_cast<float>(thresh * 1.4426950408889634);
-    const float dthr = dlt + 3.0e-6f * nf + 1.0e-6f * fabsf(thr_log2);
-    const float LOG2E = 1.4426950408889634f;
-    const float ymaxf = static_cast<float>(yabs);
-    const float mabsf = fabsf(static_cast<float>(m)) + ymaxf;
-    const float vfloor = uni(fmaxf(mabsf * mabsf * 1.0e-9f, ymaxf * ymaxf * 1.5e-8f));
+    // setup loads, issued together: the shared ones, the group record, and the rows of the window's two ends (practically always live)
+    const BsSetupLoads<DT> sl = bs_setup_loads<DT>(c, geo, base, ps, pe, bsw, lane);
+    const uint4 gent = (static_cast<const uint4 *>(c.grp) + geo.G0)[min(lane, ngc)];
+    uint2 ring[2] = {row_load(0), row_load(rows - 1)};
+    const BsSetup<false> su = bs_setup_sums<DT>(c, geo, er.m, sl, lane);
+    const BsLevels lv = bs_levels<false>(su, n, er.m, thresh);
+    if (!(lv.Dtot > 0.0)) return false;
     const unsigned crange = static_cast<unsigned>(cand_hi - cand_lo);
-    const float band = thr_log2 - dthr;                                    // a gain that reaches it: not empty for the screen
-    const float T = band - 2.0f * dlt;
-    // ---- coarse pass (scan_window_bs, GROUPS): lane L evaluates group boundary L and bounds the group (L-1, L) ----
-    unsigned long long live;
-    {
-        const int tC = static_cast<int>((G0 << BS_GRP_LOG) - gb0) + BS_GRP * lane;
-        const bool cin = lane <= ngc;
-        const int nlc = cin ? nh + 8 * tC : 1;
-        const int cb = min((gbl + (cin ? tC : 0)) >> BS_CHUNK_LOG, nch - 1) << 2;
-        const uint2 gentry = make_uint2(gent.x, gent.y);
-        const int a1 = bs_a1(gentry, bs_from_lane(off1, cb));
-        const double a2 = bs_a2(gentry, bs_from_lane(off2, cb));
-        const bool bval = cin && nlc >= 1 && nlc <= n - 1;
-        const int nlv = bval ? nlc : 1;
-        const double a1d = bs_d(a1), nld = static_cast<double>(nlv);
-        const BsEval e = bs_eval(a1d, a2, T1d - a1d, T2d - a2, nlv, n - nlv, cc, vfloor);
-        const bool inr = bval && static_cast<unsigned>(ps + nlc - cand_lo) <= crange;
-        const bool eok = bval && e.okL && e.okR;
-        if (__ballot(inr && eok && e.g >= band) != 0ull) return false;
-        const bool hasL = lane >= 1, hasR = lane < ngc;
-        const float D1r = __uint_as_float(gent.z), D2r = __uint_as_float(gent.w);
-        const float D1l = from_lane_below(D1r), D2l = from_lane_below(D2r);
-        const float D1 = fmaxf(hasL ? D1l : 0.0f, hasR ? D1r : 0.0f), D2 = fmaxf(hasL ? D2l : 0.0f, hasR ? D2r : 0.0f);
-        const int sgl = a1 - from_lane_below(a1), sgr = from_lane_above(a1) - a1;
-        const double ig = 1.0 / static_cast<double>(BS_GRP_SAMPLES);
-        const float wLl = static_cast<float>(fma(nld, static_cast<double>(sgl) * ig, -a1d)) * e.r.x;
-        const float wLr = static_cast<float>(fma(nld, static_cast<double>(sgr) * ig, -a1d)) * e.r.x;
-        const float dmu = static_cast<float>(fma(dn, a1d, -(nld * T1d))) * e.r.x * e.r.y;
-        const float A = bs_group_slack(e, D1, D2, hasL ? wLl : wLr, hasR ? wLr : wLl, dmu);
-        const float nlf = static_cast<float>(nlv), nrf = nf - nlf;
-        const bool okF = e.u.x * nlf >= vfloor * (nlf + static_cast<float>(BS_GRP_SAMPLES)) &&
-                         e.u.y * nrf >= vfloor * (nrf + static_cast<float>(BS_GRP_SAMPLES));
-        const float GA = (eok && okF) ? e.g + A : INFINITY;
-        const float ghb = fmaxf(GA, from_lane_below(GA));
-        // rows to sweep (lane r works it out for row r): all whose blocks do not all lie in groups below T
-        const unsigned long long dead = __ballot(lane >= 1 && lane <= ngc && ghb < T);
-        const int tl = BS_STRIDE * lane, th = min(tl + BS_STRIDE, nblk) - 1;
-        const int lo = static_cast<int>(((gb0 + tl) >> BS_GRP_LOG) - G0) + 1, hi = static_cast<int>(((gb0 + th) >> BS_GRP_LOG) - G0) + 1;
-        const unsigned long long span = ((2ull << (hi - lo)) - 1ull) << max(lo, 0);
-        live = __ballot(lane < rows && !(lo >= 1 && hi <= ngc && (dead & span) == span));
-    }
-    // ---- the live rows: the arithmetic of scan_window_bs's row_eval, judged on the spot ----
-    const int nl0 = nh + 8 * lane;
+    const float band = lv.thr_log2 - lv.dthr;                              // a gain that reaches it: not empty for the screen
+    const float T = band - 2.0f * lv.dlt;
+    // coarse pass: no group boundary's gain in the band; the rows whose blocks do not all lie in groups below T are live
+    const BsGroup cg = bs_group_bound(geo, su, lv, gent, ngc, ps, cand_lo, crange, lane);
+    if (__ballot(cg.inr && cg.eok && cg.e.g >= band) != 0ull) return false;
+    unsigned long long live = bs_live_rows(geo, ngc, cg.ghb, T, lane);
+    // a live row, judged on the spot
     auto row_empty = [&](int r, const uint2 &cur) -> bool {                // (uniform)
-        const int tb = gbl + BS_STRIDE * r;
-        const int cb = min((tb + lane) >> BS_CHUNK_LOG, nch - 1) << 2;
-        const int o1 = bs_from_lane(off1, cb);
-        const double o2 = bs_from_lane(off2, cb);
-        const int nl = nl0 + 8 * BS_STRIDE * r, J = ps + nl;
-        const float nlf = static_cast<float>(nl);
-        const double nld = static_cast<double>(nl);
-        const int a1 = bs_a1(cur, o1);
-        const double a2 = bs_a2(cur, o2);
-        const double a1d = bs_d(a1), b1d = T1d - a1d, b2d = T2d - a2;
-        const double DL = fma(nld, a2, -(a1d * a1d));
-        const double DR = fma(dn - nld, b2d, -(b1d * b1d));
-        const float nrf = nf - nlf;
-        const f2 D = {static_cast<float>(DL), static_cast<float>(DR)};
-        const f2 nv = {nlf, nrf};
-        const f2 rr = {__builtin_amdgcn_rcpf(nlf), __builtin_amdgcn_rcpf(nrf)};
-        const f2 u = D * rr * rr;
-        const f2 lgu = {__builtin_amdgcn_logf(u.x), __builtin_amdgcn_logf(u.y)};
-        const f2 lg = lgu - cc;
-        const f2 tt = nv * lg;
-        const float g = -(tt.x + tt.y);
-        const bool valid = static_cast<unsigned>(nl - 1) < static_cast<unsigned>(n - 1);
-        const bool okL = valid && u.x >= vfloor, okR = valid && u.y >= vfloor;
-        const bool inr = static_cast<unsigned>(J - cand_lo) <= crange && (lane != 0 || r == 0);
+        const BsBoundary<false> b = bs_boundary<false>(geo, su, lv, cur, bs_row_offsets<false>(geo, su, r, lane), r, ps, cand_lo, crange, lane);
         // a boundary gain in the band or above, or a boundary the screen cannot judge (variance floor)
-        if (__ballot(inr && !(okL && okR && g < band)) != 0ull) return false;
+        if (__ballot(b.inr && !(b.e.okL && b.e.okR && b.e.g < band)) != 0ull) return false;
         // the block (J - 8, J): the corner bound
-        const float aL = from_lane_below(lg.x), rlb = from_lane_below(rr.x);
-        const bool pokL = from_lane_below(static_cast<int>(okL)) != 0;
-        const bool blk = lane >= 1 && static_cast<unsigned>(J - 1 - cand_lo) <= crange + 6u;
-        const float h0 = -fmaf(nlf - 8.0f, aL, (nrf + 8.0f) * (lg.y - 8.0f * LOG2E * rr.y));
-        const float h1 = -fmaf(nlf - 1.0f, aL - 7.0f * LOG2E * rlb, (nrf + 1.0f) * (lg.y - LOG2E * rr.y));
-        const bool prunable = static_cast<bool>(static_cast<int>(pokL) & static_cast<int>(okR) & static_cast<int>(nl >= 9));
-        const bool keep = static_cast<bool>(static_cast<int>(blk) & static_cast<int>(!(prunable && fmaxf(h0, h1) < T)));
+        const bool keep = static_cast<bool>(static_cast<int>(b.blk) & static_cast<int>(!(b.prunable && fmaxf(b.h0, b.h1) < T)));
         if (__ballot(keep) == 0ull) return true;
         // ... and for the blocks it leaves, the bound from both boundaries (the branch is the wave's: every lane is here)
-        BsEval eq, ep;
-        eq.g = g; eq.lg = lg; eq.r = rr; eq.u = u; eq.okL = okL; eq.okR = okR;
-        ep.g = from_lane_below(g);
-        ep.lg.x = aL; ep.lg.y = from_lane_below(lg.y);
-        ep.r.x = rlb; ep.r.y = from_lane_below(rr.y);
-        ep.u.x = from_lane_below(u.x); ep.u.y = from_lane_below(u.y);
-        ep.okL = pokL; ep.okR = from_lane_below(static_cast<int>(okR)) != 0;
-        const int nlp = nl - 8;
-        const float b2 = bs_block_bound2(ep, eq, max(nlp, 1), n, SSt, rn);
+        const BsEval eq = b.e;
+        BsEval ep;
+        ep.g = from_lane_below(eq.g);
+        ep.lg.x = b.aL; ep.lg.y = from_lane_below(eq.lg.y);
+        ep.r.x = b.rlb; ep.r.y = from_lane_below(eq.r.y);
+        ep.u.x = from_lane_below(eq.u.x); ep.u.y = from_lane_below(eq.u.y);
+        ep.okL = b.pokL; ep.okR = from_lane_below(static_cast<int>(eq.okR)) != 0;
+        const int nlp = b.nl - 8;
+        const float b2 = bs_block_bound2(ep, eq, max(nlp, 1), n, lv.SSt, lv.rn);
         return __ballot(keep && !(nlp >= 1 && b2 < T)) == 0ull;
     };
-    auto take_row = [&]() {
-        if (live == 0ull) return -1;
-        const int r = __builtin_ctzll(live);
-        live &= live - 1ull;
-        return r;
-    };
+    // (every window here has a coarse pass: PS_ONE_ROW_LOOP's refill of the mask, for windows that sweep all rows, never applies)
+    auto take_row = [&]() { const BsRow t = bs_take_row(live); live = t.live; return t.r; };
     int rr[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
