@@ -380,13 +380,32 @@ int ps_pairwise_batch(ps_ctx *ctx, const double *d_a, const int64_t *h_a_off, in
  * most 2^24 points in all (PS_ERR_ARG otherwise).  param[3k..3k+2] = (weighted mean of the points -- the shift c_k of
  * ps_hmm_expect's statistics --, 1 / (2 h^2), -log(h sqrt(2 pi))).  The sum is a log-sum-exp over the points in ascending
  * index: the largest term plus log1p of the others' exp.  The three kde_* fields were appended to the struct; they are read
- * only when some kind[k] is 3, so a caller built against the shorter struct, which never sets kind 3, stays correct. */
+ * only when some kind[k] is 3, so a caller built against the shorter struct, which never sets kind 3, stays correct.
+ *
+ * kind[k] = 4, a vector state: an observation is n_dim doubles (1 <= n_dim <= 16) and the state's log density is the
+ * weighted sum  w_0 l_0(x_0) + w_1 l_1(x_1) + ...  of n_dim independent components, added in ascending d from the first
+ * product.  Component d of emitting state k is entry i = k n_dim + d of comp_kind, comp_w (finite, > 0) and
+ * comp_param[3i..3i+2]:
+ *   comp_kind 1 normal       (mean, 1 / (2 std^2), -log(std sqrt(2 pi))):           c - (x - a)^2 b
+ *   comp_kind 2 uniform      (low, high, -log(high - low)):                         c on [a, b], else -inf
+ *   comp_kind 5 log-normal   (mu, 1 / (2 sigma^2), -log(sigma sqrt(2 pi))):         (c - (log x - a)^2 b) - log x for x > 0,
+ *                                                                                    else -inf
+ *   comp_kind 6 exponential  (0, rate, log rate):                                   c - x b for x >= 0, else -inf
+ * Slot 0 of a triple is the shift c of the component's statistics in ps_hmm_expect.  In a vector model EVERY emitting state
+ * is kind 4 (a plain normal state is one component of weight 1) and `param` is not read (it may be NULL); kind 4 beside kinds 1..3, n_dim
+ * out of range, an unknown component kind, a bad weight or a null table is PS_ERR_ARG.  d_obs then holds n_dim doubles
+ * per observation -- observation t of sequence q at (h_off[q] + t) n_dim; h_off still counts observations -- and
+ * ps_hmm_expect's d_stats 1 + 2 n_dim doubles per emitting state.  n_dim and the three comp_* fields were appended to the
+ * struct; they are read only when some kind[k] is 4, so a caller built against a shorter struct stays correct. */
 typedef struct ps_hmm_model {
     int32_t n_states, n_emit, n_levels, start, end, finite;
     const int32_t *kind, *level_ptr, *in_ptr, *in_src, *out_ptr, *out_dst;
     const double *param, *in_lp, *out_lp;
     const int32_t *kde_ptr;
     const double *kde_pt, *kde_lw;
+    int32_t n_dim;
+    const int32_t *comp_kind;
+    const double *comp_param, *comp_w;
 } ps_hmm_model;
 
 /* Decodes a BATCH of observation sequences against one model: sequence q is d_obs[h_off[q] .. h_off[q+1]) (fp64, device).
@@ -413,6 +432,10 @@ int ps_hmm_batch(ps_ctx *ctx, const ps_hmm_model *model, int32_t mode, const dou
  * d_logp[q] = the sequence's log probability (as PS_HMM_FORWARD); d_counts[e] = the expected count of edge e, e in
  * out-edge CSR order (n_edges = out_ptr[n_states]; pypore_amd.hmm.Model.edges order); d_stats[3k .. 3k+2] = (W, A, B) of
  * emitting state k: the sums of the posterior g, g (x - c_k) and g (x - c_k)^2 over the observations, c_k = param[3k].
+ * For a vector model (kind 4) d_stats holds 1 + 2 n_dim doubles per emitting state instead: W, then (A_d, B_d) for d = 0 ..
+ * n_dim - 1, with A_d = sum g (y_d - c_d), B_d = sum g (y_d - c_d)^2, y_d = log x_d for a log-normal component and x_d
+ * otherwise, c_d = the component's comp_param slot 0; at n_dim = 1 that is the (W, A, B) layout.  The accumulators
+ * (n_edges + (1 + 2 n_dim) n_emit + 1, at most 2^26) live in LDS when 16 n_states + 8 of them fit in 64 KiB.
  * A sequence with logp = -inf contributes nothing and is counted in *h_skipped.  Forward matrices are kept in HBM for
  * launches of at most option "hmm_fb_budget" bytes (default 4 GiB; at least one sequence per launch); the accumulators
  * are per-workgroup rows summed in a fixed order, so the same call with the same options gives the same bits.  Limits as

@@ -37,20 +37,44 @@ def _parser_from(d):
     return _parser_base.from_json(dump_json(d)) if d is not None else None
 
 
-def _apply_hmm(event, hmm, algorithm):
-    """getattr(hmm, algorithm)(segment means), as the reference calls it (DataTypes.py:62-68, :349-355)."""
-    return getattr(hmm, algorithm)(np.array([seg.mean for seg in event.segments]))
+def _observations(event, hmm, features):
+    """What an HMM is handed for one event.  features None: the segment means as a 1-D array (the reference's call); a
+    tuple of segment attribute names, e.g. ('mean', 'std', 'duration'): the (n, len(features)) array of those attributes
+    as they stand now.  A pypore_amd.hmm.Model of n_dim > 1 needs `features`, as many as its n_dim (ValueError); any
+    other object is not asked about its dimension."""
+    from .hmm import Model
+    n_dim = hmm.n_dim if isinstance(hmm, Model) else None
+    if features is None:
+        if n_dim is not None and n_dim > 1:
+            raise ValueError("the model takes %d values per observation: pass features=, a tuple of %d segment attribute "
+                             "names such as ('mean', 'std', 'duration')" % (n_dim, n_dim))
+        return np.array([seg.mean for seg in event.segments], dtype=np.float64)
+    if isinstance(features, str):
+        raise ValueError("features must be a tuple of segment attribute names, got the string %r" % features)
+    features = tuple(features)
+    if n_dim is not None and len(features) != n_dim:
+        raise ValueError("%d features for a model of n_dim = %d" % (len(features), n_dim))
+    return np.array([[getattr(seg, name) for name in features] for seg in event.segments],
+                    dtype=np.float64).reshape(-1, len(features))
+
+
+def _apply_hmm(event, hmm, algorithm, features=None):
+    """getattr(hmm, algorithm)(segment means), as the reference calls it (DataTypes.py:62-68, :349-355); with `features`
+    the (n, D) array of those segment attributes instead (_observations)."""
+    return getattr(hmm, algorithm)(_observations(event, hmm, features))
 
 
 class MetaEvent(MetaSegment):
     """An event reduced to its numbers (and its MetaSegments)."""
     json_fields = EVENT_FIELDS
 
-    def apply_hmm(self, hmm, algorithm='viterbi'):
+    def apply_hmm(self, hmm, algorithm='viterbi', features=None):
         """The HMM's `algorithm` ('viterbi', 'forward', 'backward', 'log_probability', 'forward_backward',
         'maximum_a_posteriori') on the segment means: for a pypore_amd.hmm.Model, (logp, path) / a log matrix / a float /
-        (transitions, emissions) / (logp, path of one emitting state per segment), computed on the device."""
-        return _apply_hmm(self, hmm, algorithm)
+        (transitions, emissions) / (logp, path of one emitting state per segment), computed on the device.  features: a
+        tuple of segment attribute names, e.g. ('mean', 'std', 'duration') -- the model is handed the (n, D) array of
+        those instead of the means (a vector model, pypore_amd.hmm, of n_dim = D)."""
+        return _apply_hmm(self, hmm, algorithm, features)
 
     def delete(self):
         for segment in self.__dict__.get('segments', []):
@@ -122,7 +146,7 @@ class Event(Segment):
         self.filtered, self.filter_order, self.filter_cutoff = True, order, cutoff
 
     # ---- Event.parse (DataTypes.py:276-289, :333) -----------------------------------------------------------
-    def parse(self, parser=None, hmm=None):
+    def parse(self, parser=None, hmm=None, features=None):
         """segments = parser.parse(current); every segment learns its event and is rescaled from samples to seconds
         with the file's sampling rate.
 
@@ -139,18 +163,19 @@ class Event(Segment):
           * an event with fewer than two segments ends with no segments.
         A pypore_amd.hmm.Model is decoded on the device; any other object with a `viterbi` method is called the same
         way (duck typing; the reference accepts yahmm models only).  An impossible sequence (viterbi returns
-        (-inf, None)) raises ValueError where the reference would fail on indexing None."""
+        (-inf, None)) raises ValueError where the reference would fail on indexing None.  features: as for apply_hmm --
+        the segment attributes hmm.viterbi is handed instead of the means; the merge is the same."""
         if parser is None:
             parser = SpeedyStatSplit(prior_segments_per_second=10)
         if hmm and not callable(getattr(hmm, "viterbi", None)):
             raise TypeError("hmm must be a pypore_amd.hmm.Model or have a viterbi method")
         self._segment(parser)
         if hmm:
-            self.segments = self._merge_by_hmm(hmm)
+            self.segments = self._merge_by_hmm(hmm, features)
         self.state_parser = parser
 
-    def _merge_by_hmm(self, hmm):
-        _, states = self.apply_hmm(hmm)
+    def _merge_by_hmm(self, hmm, features=None):
+        _, states = self.apply_hmm(hmm, features=features)
         second = self.second
         i, j, n, segments = 0, 0, len(self.segments), []
         if states is None and n >= 2:
@@ -166,11 +191,13 @@ class Event(Segment):
             i += 1
         return segments
 
-    def apply_hmm(self, hmm, algorithm='viterbi'):
+    def apply_hmm(self, hmm, algorithm='viterbi', features=None):
         """The HMM's `algorithm` ('viterbi', 'forward', 'backward', 'log_probability', 'forward_backward',
         'maximum_a_posteriori') on the segment means: for a pypore_amd.hmm.Model, (logp, path) / a log matrix / a float /
-        (transitions, emissions) / (logp, path of one emitting state per segment), computed on the device."""
-        return _apply_hmm(self, hmm, algorithm)
+        (transitions, emissions) / (logp, path of one emitting state per segment), computed on the device.  features: a
+        tuple of segment attribute names, e.g. ('mean', 'std', 'duration') -- the model is handed the (n, D) array of
+        those instead of the means (a vector model, pypore_amd.hmm, of n_dim = D)."""
+        return _apply_hmm(self, hmm, algorithm, features)
 
     def _segment(self, parser):
         if self.__dict__.get("filtered"):
@@ -530,12 +557,13 @@ class Experiment(object):
             for fut in [pool.submit(one, entry) for entry in entries]:
                 take(fut.result())
 
-    def apply_hmm(self, hmm, filter=None, indices=None):
+    def apply_hmm(self, hmm, filter=None, indices=None, features=None):
         """The Viterbi paths of the events' segment means, concatenated (what DataTypes.py:990-995 intends; as written
         there it cannot run).  Events: `indices` of self.events (all when None), then those for which `filter(event)`
         is true.  A pypore_amd.hmm.Model decodes them all in ONE viterbi_batch call; another object with a `viterbi`
         method is called per event.  Returns the list of (index, state) entries of every path in event order (an
-        impossible event contributes nothing).  hmm=None or an object without `viterbi`: NotImplementedError."""
+        impossible event contributes nothing).  hmm=None or an object without `viterbi`: NotImplementedError.  features:
+        as for Event.apply_hmm -- a tuple of segment attribute names instead of the means, for a vector model."""
         if hmm is None or not callable(getattr(hmm, "viterbi", None)):
             raise NotImplementedError("apply_hmm needs a model with a viterbi method (pypore_amd.hmm.Model)")
         events = self.events
@@ -543,7 +571,7 @@ class Experiment(object):
             events = [events[i] for i in indices]
         if filter is not None:
             events = [event for event in events if filter(event)]
-        means = [np.array([seg.mean for seg in event.segments], dtype=np.float64) for event in events]
+        means = [_observations(event, hmm, features) for event in events]
         batch = getattr(hmm, "viterbi_batch", None)
         results = batch(means) if callable(batch) else [hmm.viterbi(m) for m in means]
         return [entry for _, path in results if path is not None for entry in path]

@@ -48,7 +48,8 @@ class HmmModel(ctypes.Structure):
     _fields_ = [("n_states", ctypes.c_int32), ("n_emit", ctypes.c_int32), ("n_levels", ctypes.c_int32),
                 ("start", ctypes.c_int32), ("end", ctypes.c_int32), ("finite", ctypes.c_int32)] + \
                [(f, ctypes.c_void_p) for f in ("kind", "level_ptr", "in_ptr", "in_src", "out_ptr", "out_dst",
-                                                "param", "in_lp", "out_lp", "kde_ptr", "kde_pt", "kde_lw")]
+                                                "param", "in_lp", "out_lp", "kde_ptr", "kde_pt", "kde_lw")] + \
+               [("n_dim", ctypes.c_int32)] + [(f, ctypes.c_void_p) for f in ("comp_kind", "comp_param", "comp_w")]
 
 
 _lib = None

@@ -2919,22 +2919,43 @@ namespace {
 
 // ps_hmm_batch: the model's arrays checked and packed into one blob (doubles first, then ints); the device copy is reused
 // while the blob is unchanged.  *has_kde: some state is a kernel density (kind 3); only then are the model's kde_* fields read,
-// checked and appended to the blob (points and log weights after the doubles, the CSR offsets after the ints).
+// checked and appended to the blob (points and log weights after the doubles, the CSR offsets after the ints).  *V, *has_vec:
+// the same for a vector model (every emitting state kind 4): only then are n_dim and the comp_* fields read, checked and
+// appended (parameters and weights after the doubles; the component kinds and n_dim after the ints), so a changed weight
+// or parameter is a changed blob.
 constexpr int64_t HMM_KDE_POINTS_MAX = 1 << 24;
-int hmm_upload(ps_ctx *ctx, const ps_hmm_model *m, HmmDevK *D, int *max_in, bool *has_kde)
+int hmm_upload(ps_ctx *ctx, const ps_hmm_model *m, HmmDevK *D, HmmDevV *V, int *max_in, bool *has_kde, bool *has_vec)
 {
     const int S = m->n_states, NE = m->n_emit, NL = m->n_levels;
     if (S < 1 || S > HMM_S_MAX) return fail(ctx, PS_ERR_ARG, "model of %d states: the device HMM kernels take 1..%d", S, HMM_S_MAX);
     if (NE < 0 || NE > S || NL < 0 || NL > S - NE || (NL == 0) != (NE == S)) return fail(ctx, PS_ERR_ARG, "bad state / level counts");
     if (m->start < NE || m->start >= S || m->end < NE || m->end >= S) return fail(ctx, PS_ERR_ARG, "start and end must be silent states");
-    if (!m->kind || !m->level_ptr || !m->in_ptr || !m->out_ptr || !m->param) return fail(ctx, PS_ERR_ARG, "null model array");
-    bool kde = false;
+    if (!m->kind || !m->level_ptr || !m->in_ptr || !m->out_ptr) return fail(ctx, PS_ERR_ARG, "null model array");
+    bool kde = false, vec = false, plain = false;
     for (int k = 0; k < S; ++k) {
         const int kd = m->kind[k];
-        if ((k < NE) != (kd == HMM_NORMAL || kd == HMM_UNIFORM || kd == HMM_KDE) || (k >= NE && kd != HMM_SILENT))
+        if ((k < NE) != (kd == HMM_NORMAL || kd == HMM_UNIFORM || kd == HMM_KDE || kd == HMM_VECTOR) || (k >= NE && kd != HMM_SILENT))
             return fail(ctx, PS_ERR_ARG, "state %d: emitting states first, then silent ones", k);
         kde = kde || kd == HMM_KDE;
+        vec = vec || kd == HMM_VECTOR;
+        plain = plain || (k < NE && kd != HMM_VECTOR);
     }
+    if (!vec && !m->param) return fail(ctx, PS_ERR_ARG, "null model array");      // (a vector model's param is not read)
+    size_t NC = 0;                                       // components of a vector model: n_emit * n_dim
+    if (vec) {
+        if (plain) return fail(ctx, PS_ERR_ARG, "a vector model's emitting states are all kind 4: kinds 1..3 cannot be mixed with it");
+        if (m->n_dim < 1 || m->n_dim > HMM_D_MAX) return fail(ctx, PS_ERR_ARG, "n_dim %d: a vector model takes 1..%d components", m->n_dim, HMM_D_MAX);
+        if (!m->comp_kind || !m->comp_param || !m->comp_w) return fail(ctx, PS_ERR_ARG, "a vector model needs comp_kind, comp_param and comp_w");
+        NC = static_cast<size_t>(NE) * m->n_dim;
+        for (size_t i = 0; i < NC; ++i) {
+            const int ck = m->comp_kind[i];
+            if (ck != HMM_NORMAL && ck != HMM_UNIFORM && ck != HMM_LOGNORMAL && ck != HMM_EXPONENTIAL)
+                return fail(ctx, PS_ERR_ARG, "component %lld: unknown component kind %d", static_cast<long long>(i), ck);
+            if (!std::isfinite(m->comp_w[i]) || !(m->comp_w[i] > 0.0))
+                return fail(ctx, PS_ERR_ARG, "component %lld: a weight must be finite and > 0", static_cast<long long>(i));
+        }
+    }
+    *has_vec = vec;
     int64_t NP = 0;
     if (kde) {
         if (!m->kde_ptr || !m->kde_pt || !m->kde_lw) return fail(ctx, PS_ERR_ARG, "a kernel-density state needs kde_ptr, kde_pt and kde_lw");
@@ -2978,12 +2999,12 @@ int hmm_upload(ps_ctx *ctx, const ps_hmm_model *m, HmmDevK *D, int *max_in, bool
     }
     if (n_edge[0] != n_edge[1]) return fail(ctx, PS_ERR_ARG, "in- and out-edge lists differ in length");
     if (*max_in > 65535) return fail(ctx, PS_ERR_ARG, "a state with %d in-edges: the device HMM kernels take at most 65535", *max_in);
-    const size_t nd0 = 3 * static_cast<size_t>(S) + 2 * n_edge[0], nd = nd0 + 2 * static_cast<size_t>(NP);
+    const size_t nd0 = 3 * static_cast<size_t>(S) + 2 * n_edge[0], nd = nd0 + 2 * static_cast<size_t>(NP) + 4 * NC;
     const size_t ni0 = static_cast<size_t>(S) + (NL + 1) + 2 * (S + 1) + 2 * n_edge[0] + 3;
-    const size_t ni = ni0 + (kde ? static_cast<size_t>(NE) + 1 : 0);
+    const size_t ni = ni0 + (kde ? static_cast<size_t>(NE) + 1 : 0) + (vec ? NC + 1 : 0);      // (kde and vec exclude each other)
     std::vector<char> blob(nd * sizeof(double) + ni * sizeof(int32_t), 0);
     double *bd = reinterpret_cast<double *>(blob.data());
-    std::memcpy(bd, m->param, 3 * S * sizeof(double));
+    if (!vec) std::memcpy(bd, m->param, 3 * S * sizeof(double));      // (a vector model's slots stay 0)
     if (n_edge[0]) {
         std::memcpy(bd + 3 * S, m->in_lp, n_edge[0] * sizeof(double));
         std::memcpy(bd + 3 * S + n_edge[0], m->out_lp, n_edge[0] * sizeof(double));
@@ -3005,6 +3026,12 @@ int hmm_upload(ps_ctx *ctx, const ps_hmm_model *m, HmmDevK *D, int *max_in, bool
         std::memcpy(bd + nd0 + NP, m->kde_lw, NP * sizeof(double));
         std::memcpy(bi + ni0, m->kde_ptr, (static_cast<size_t>(NE) + 1) * sizeof(int32_t));
     }
+    if (vec) {
+        std::memcpy(bd + nd0, m->comp_param, 3 * NC * sizeof(double));
+        std::memcpy(bd + nd0 + 3 * NC, m->comp_w, NC * sizeof(double));
+        std::memcpy(bi + ni0, m->comp_kind, NC * sizeof(int32_t));
+        bi[ni0 + NC] = m->n_dim;
+    }
     if (blob != ctx->hmm_blob || !ctx->hmm_model.p) {
         HIP_TRY(ctx, ctx->hmm_model.reserve(blob.size()));
         HIP_TRY(ctx, hipMemcpyAsync(ctx->hmm_model.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
@@ -3018,6 +3045,9 @@ int hmm_upload(ps_ctx *ctx, const ps_hmm_model *m, HmmDevK *D, int *max_in, bool
     D->in_src = D->out_ptr + S + 1; D->out_dst = D->in_src + n_edge[0];
     D->S = S; D->n_emit = NE; D->n_levels = NL; D->start = m->start; D->end = m->end; D->finite = m->finite != 0;
     D->kde_pt = kde ? dd + nd0 : nullptr; D->kde_lw = kde ? dd + nd0 + NP : nullptr; D->kde_ptr = kde ? di + ni0 : nullptr;
+    static_cast<HmmDev &>(*V) = *D;
+    V->comp_param = vec ? dd + nd0 : nullptr; V->comp_w = vec ? dd + nd0 + 3 * NC : nullptr; V->comp_kind = vec ? di + ni0 : nullptr;
+    V->D = vec ? m->n_dim : 1;
     return PS_OK;
 }
 
@@ -3037,11 +3067,6 @@ int32_t next_chunk(const int64_t *h_off, int32_t q0, int32_t n_seq, size_t row_b
     return q1;
 }
 
-// a model with kernel-density states takes the HmmDevK instantiations, any other the HmmDev ones
-template <typename F> int with_model(bool kde, const HmmDevK &DK, F &&f)
-{
-    return kde ? f(DK) : f(static_cast<const HmmDev &>(DK));
-}
 
 // The forward pass of sequences [q0, q1): logp, and the matrix (optional) with sequence q at row off[q] + q - row0 of fmat
 template <typename MD>
@@ -3062,10 +3087,18 @@ int launch_forward(ps_ctx *ctx, const MD &D, const double *d_obs, const long lon
 // followed by the path slots' where there are some, on the device.  An empty batch leaves d_off null.
 struct HmmCall {
     HmmDevK DK;
-    bool kde = false;
+    HmmDevV DV;
+    bool kde = false, vec = false;
     int max_in = 0, E = 0;                  // most in-edges of a state, out-edges of the model
     const long long *d_off = nullptr;
+    int dim() const { return vec ? DV.D : 1; }                                        // doubles per observation
+    long long n_acc() const { return E + (1ll + 2 * dim()) * DK.n_emit + 1; }          // hmm_expect_kernel's accumulators
 };
+// a vector model takes the HmmDevV instantiations, one with kernel-density states the HmmDevK ones, any other the HmmDev ones
+template <typename F> int with_model(const HmmCall &C, F &&f)
+{
+    return C.vec ? f(C.DV) : C.kde ? f(C.DK) : f(static_cast<const HmmDev &>(C.DK));
+}
 template <typename Own>
 int hmm_begin(ps_ctx *ctx, const ps_hmm_model *model, bool host_ok, const double *d_obs, const int64_t *h_off,
               const int64_t *h_path_off, int32_t n_seq, const double *d_logp, HmmCall *C, Own &&own)
@@ -3078,7 +3111,7 @@ int hmm_begin(ps_ctx *ctx, const ps_hmm_model *model, bool host_ok, const double
     for (int32_t q = 0; h_path_off && q < n_seq; ++q)
         if (h_path_off[q] < 0 || h_path_off[q + 1] < h_path_off[q]) return fail(ctx, PS_ERR_ARG, "path offsets must be non-negative and ascending");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (int rc = hmm_upload(ctx, model, &C->DK, &C->max_in, &C->kde)) return rc;
+    if (int rc = hmm_upload(ctx, model, &C->DK, &C->DV, &C->max_in, &C->kde, &C->vec)) return rc;
     C->E = model->out_ptr[C->DK.S];
     if (int rc = own(*C)) return rc;
     if (n_seq == 0) return PS_OK;
@@ -3215,11 +3248,11 @@ int ps_hmm_batch(ps_ctx *ctx, const ps_hmm_model *model, int32_t mode, const dou
                            [](const HmmCall &) { return PS_OK; })) return rc;
     if (!C.d_off) return PS_OK;
     if (vit)
-        return with_model(C.kde, C.DK, [&](const auto &M) {
+        return with_model(C, [&](const auto &M) {
             return C.max_in > 255 ? hmm_viterbi<uint16_t>(ctx, M, d_obs, h_off, C.d_off, n_seq, d_logp, d_mat, d_path, d_path_len)
                                   : hmm_viterbi<uint8_t>(ctx, M, d_obs, h_off, C.d_off, n_seq, d_logp, d_mat, d_path, d_path_len);
         });
-    const int rc = with_model(C.kde, C.DK, [&](const auto &M) -> int {
+    const int rc = with_model(C, [&](const auto &M) -> int {
         using MD = std::decay_t<decltype(M)>;
         if (mode == PS_HMM_FORWARD) return launch_forward(ctx, M, d_obs, C.d_off, 0, n_seq, d_logp, d_mat, 0ll);
         const size_t lds = 2 * static_cast<size_t>(M.S) * sizeof(double);
@@ -3240,14 +3273,14 @@ int ps_hmm_expect(ps_ctx *ctx, const ps_hmm_model *model, const double *d_obs, c
     int n_acc = 0;
     auto own = [&](const HmmCall &c) -> int {
         const int E = c.E, NE = c.DK.n_emit;
-        const long long n_acc_ll = static_cast<long long>(E) + 3ll * NE + 1;
+        const long long n_acc_ll = c.n_acc();
         if (n_acc_ll > (1ll << 26)) return fail(ctx, PS_ERR_ARG, "model of %d edges: the E-step takes at most 2^26 accumulators", E);
         n_acc = static_cast<int>(n_acc_ll);
         if ((E > 0 && !d_counts) || (NE > 0 && !d_stats)) return fail(ctx, PS_ERR_ARG, "null device pointer");
         *h_skipped = 0;
         if (n_seq == 0) {
             if (E > 0) HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, static_cast<size_t>(E) * sizeof(double), ctx->stream));
-            if (NE > 0) HIP_TRY(ctx, hipMemsetAsync(d_stats, 0, 3 * static_cast<size_t>(NE) * sizeof(double), ctx->stream));
+            if (NE > 0) HIP_TRY(ctx, hipMemsetAsync(d_stats, 0, (1 + 2 * static_cast<size_t>(c.dim())) * NE * sizeof(double), ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         }
         return PS_OK;
@@ -3257,7 +3290,7 @@ int ps_hmm_expect(ps_ctx *ctx, const ps_hmm_model *model, const double *d_obs, c
     const int E = C.E;
     const bool in_lds = (2 * static_cast<size_t>(C.DK.S) + static_cast<size_t>(n_acc)) * sizeof(double) <= HMM_EXPECT_LDS
                         && ctx->hmm_expect_lds;
-    return with_model(C.kde, C.DK, [&](const auto &M) {
+    return with_model(C, [&](const auto &M) {
         return in_lds ? hmm_expect_run<true>(ctx, M, d_obs, h_off, C.d_off, n_seq, n_acc, E, d_logp, d_counts, d_stats, h_skipped)
                       : hmm_expect_run<false>(ctx, M, d_obs, h_off, C.d_off, n_seq, n_acc, E, d_logp, d_counts, d_stats, h_skipped);
     });
@@ -3268,7 +3301,7 @@ int ps_hmm_posterior(ps_ctx *ctx, const ps_hmm_model *model, const double *d_obs
 {
     HmmCall C;
     auto own = [&](const HmmCall &c) -> int {
-        if (static_cast<long long>(c.E) + 3ll * c.DK.n_emit + 1 > (1ll << 26)) return fail(ctx, PS_ERR_ARG, "model of %d edges: at most 2^26 accumulators", c.E);
+        if (c.n_acc() > (1ll << 26)) return fail(ctx, PS_ERR_ARG, "model of %d edges: at most 2^26 accumulators", c.E);
         return PS_OK;
     };
     if (int rc = hmm_begin(ctx, model, true, d_obs, h_off, nullptr, n_seq, d_logp, &C, own)) return rc;
@@ -3277,7 +3310,7 @@ int ps_hmm_posterior(ps_ctx *ctx, const ps_hmm_model *model, const double *d_obs
     // the counts row of a sequence: none asked for (or no edges), in LDS when it fits beside the score rows, else in place
     const int cnt = !d_counts_seq || E == 0 ? 0
                     : (2 * static_cast<size_t>(C.DK.S) + static_cast<size_t>(E)) * sizeof(double) <= HMM_EXPECT_LDS && ctx->hmm_expect_lds ? 2 : 1;
-    return with_model(C.kde, C.DK, [&](const auto &M) {
+    return with_model(C, [&](const auto &M) {
         switch (cnt) {
         case 0: return hmm_posterior_run<0>(ctx, M, d_obs, h_off, C.d_off, n_seq, E, d_logp, d_post, d_map_state, d_map_logp, d_counts_seq);
         case 1: return hmm_posterior_run<1>(ctx, M, d_obs, h_off, C.d_off, n_seq, E, d_logp, d_post, d_map_state, d_map_logp, d_counts_seq);

@@ -26,6 +26,9 @@ constexpr int HMM_NT = 64;                 // one wave per workgroup
 constexpr int HMM_S_MAX = 4096;            // states: two fp64 rows of S in LDS = 64 KiB at most
 constexpr int HMM_VITERBI = 0, HMM_FORWARD = 1, HMM_BACKWARD = 2;   // include/poreseg.h PS_HMM_*
 constexpr int HMM_SILENT = 0, HMM_NORMAL = 1, HMM_UNIFORM = 2, HMM_KDE = 3;   // include/poreseg.h ps_hmm_model.kind
+constexpr int HMM_VECTOR = 4;              // ... kind: a state of D components (a vector model)
+constexpr int HMM_LOGNORMAL = 5, HMM_EXPONENTIAL = 6;   // ps_hmm_model.comp_kind, beside HMM_NORMAL and HMM_UNIFORM
+constexpr int HMM_D_MAX = 16;              // components of a vector model's observation
 
 struct HmmDev {                 // device pointers into one upload of the baked model (include/poreseg.h ps_hmm_model)
     const double *param;        // 3 per state: normal (mean, 1 / (2 std^2), -log(std sqrt(2 pi))), uniform (low, high, -log(high - low))
@@ -42,6 +45,26 @@ struct HmmDevK : HmmDev {
     const int *kde_ptr;
     const double *kde_pt, *kde_lw;
 };
+
+// A vector model (every emitting state is kind 4): an observation is a row of D doubles, and state k scores it with the D
+// independent components [k D, (k + 1) D) of comp_kind / comp_param (3 per component: normal and uniform as param,
+// log-normal (mu, 1 / (2 sigma^2), -log(sigma sqrt(2 pi))), exponential (0, rate, log rate)) / comp_w (weights > 0).  Its
+// `param` is not read.  A third set of instantiations: the HmmDev and HmmDevK code knows nothing of these tables.
+struct HmmDevV : HmmDev {
+    const int *comp_kind;
+    const double *comp_param, *comp_w;
+    int D;
+};
+
+// The observation as the kernels hand it to hmm_emit: doubles per observation, and observation t of the sequence that
+// starts at x -- the double itself, or for a vector model the row of D doubles (one address for the whole wave).
+template <typename MD> __device__ __forceinline__ int hmm_dim(const MD &) { return 1; }
+__device__ __forceinline__ int hmm_dim(const HmmDevV &M) { return M.D; }
+template <typename MD> __device__ __forceinline__ double hmm_obs(const MD &, const double *x, int t) { return x[t]; }
+__device__ __forceinline__ const double *hmm_obs(const HmmDevV &M, const double *x, int t)
+{
+    return x + static_cast<long long>(t) * M.D;
+}
 
 __device__ __forceinline__ void hm_sync()
 {
@@ -89,6 +112,51 @@ __device__ __forceinline__ double hmm_emit(const HmmDevK &M, int k, double x)
     return c + acc.get();
 }
 
+// Vector emission  w_0 l_0(x_0) + w_1 l_1(x_1) + ...:  the lane that owns the state walks its D components in ascending d,
+// the sum starting from the first product, so one component of weight 1 gives that component's own bits.  A weight is
+// finite and > 0: an impossible component makes the sum -inf, never NaN.
+__device__ __forceinline__ double hmm_emit(const HmmDevV &M, int k, const double *x)
+{
+#pragma clang fp contract(off)
+    double s = 0.0;
+    for (int d = 0, i = k * M.D; d < M.D; ++d, ++i) {
+        const double a = M.comp_param[3 * i], b = M.comp_param[3 * i + 1], c = M.comp_param[3 * i + 2];
+        const double xd = x[d];
+        const int kd = M.comp_kind[i];
+        double l;
+        if (kd == HMM_NORMAL) {
+            const double u = xd - a;
+            l = c - (u * u) * b;
+        } else if (kd == HMM_UNIFORM) {
+            l = (xd >= a && xd <= b) ? c : -__builtin_inf();
+        } else if (kd == HMM_LOGNORMAL) {
+            if (xd > 0.0) {
+                const double y = log(xd), u = y - a;
+                l = (c - (u * u) * b) - y;
+            } else l = -__builtin_inf();
+        } else {
+            l = xd >= 0.0 ? c - xd * b : -__builtin_inf();
+        }
+        const double wl = M.comp_w[i] * l;
+        s = d ? s + wl : wl;
+    }
+    return s;
+}
+
+// What the E-step's statistics sum for component d of emitting state k: y - c, with y the observation (its logarithm for
+// a log-normal component) and c the component's shift (slot 0 of its parameters).  Called only where the state's posterior
+// is positive, so a log-normal component sees x > 0.
+template <typename MD> __device__ __forceinline__ double hmm_stat(const MD &M, int k, int, double x)
+{
+    return x - M.param[3 * k];
+}
+__device__ __forceinline__ double hmm_stat(const HmmDevV &M, int k, int d, const double *x)
+{
+    const int i = k * M.D + d;
+    const double y = M.comp_kind[i] == HMM_LOGNORMAL ? log(x[d]) : x[d];
+    return y - M.comp_param[3 * i];
+}
+
 // Viterbi / forward over one sequence per workgroup.  Rows of sequence q: mat (optional, row off[q] + q - mat_row0) and bp
 // (backpointers, Viterbi only, row off[q] + q - bp_row0 of this launch).  Writes logp[q] and, for Viterbi, last[q]: the
 // state the path ends in (end for a finite model, else the best state of step n, lowest index on a tie).
@@ -103,7 +171,7 @@ __global__ __launch_bounds__(HMM_NT) void hmm_fwd_kernel(MD M, const double *obs
     const int q = q0 + blockIdx.x;
     const long long base = off[q];
     const int n = static_cast<int>(off[q + 1] - base);
-    const double *x = obs + base;
+    const double *x = obs + base * hmm_dim(M);
     const long long row0 = base + q;
     double *prev = hm_lds, *cur = hm_lds + S;
     constexpr double NEG = -__builtin_inf();
@@ -150,7 +218,7 @@ __global__ __launch_bounds__(HMM_NT) void hmm_fwd_kernel(MD M, const double *obs
     store_row(0);
     for (int t = 1; t <= n; ++t) {
         double *tmp = prev; prev = cur; cur = tmp;
-        const double xt = x[t - 1];
+        const auto xt = hmm_obs(M, x, t - 1);
         BP *bprow = MODE == HMM_VITERBI ? bp + (row0 - bp_row0 + t) * S : nullptr;
         for (int k = lane; k < NE; k += HMM_NT) {
             const int e0 = M.in_ptr[k], e1 = M.in_ptr[k + 1];
@@ -243,7 +311,7 @@ __device__ __forceinline__ const double *hmm_bwd_sweep(const MD &M, const double
     for (int t = n; t >= 0; --t) {
         if (t < n) {
             double *tmp = nxt; nxt = cur; cur = tmp;
-            const double xt = x[t];
+            const auto xt = hmm_obs(M, x, t);
             for (int l = lane; l < NE; l += HMM_NT) nxt[l] = nxt[l] > NEG ? nxt[l] + hmm_emit(M, l, xt) : NEG;
             hm_sync();
         }
@@ -276,7 +344,8 @@ __global__ __launch_bounds__(HMM_NT) void hmm_bwd_kernel(MD M, const double *obs
     const int n = static_cast<int>(off[q + 1] - base);
     const long long row0 = base + q;
     const double *b0 = hmm_bwd_sweep(
-        M, obs + base, n, hm_lds, [](int, int) { return 0.0; }, [](int, double, double) {}, [](int, int, double, double) {},
+        M, obs + base * hmm_dim(M), n, hm_lds, [](int, int) { return 0.0; }, [](int, double, double) {},
+        [](int, int, double, double) {},
         [&](int t, const double *cur) {
             if (mat) {
                 double *dst = mat + (row0 + t) * S;
@@ -291,10 +360,11 @@ __global__ __launch_bounds__(HMM_NT) void hmm_bwd_kernel(MD M, const double *obs
 // LDS and are never written out.  With w = f[t][k] - logp[q], every out-edge term the recursion forms for state k at step t
 // -- nxt[l] + lp (l emitting, b[t+1][l] + e_l(x_t) + lp) or cur[l] + lp (l silent) -- adds exp(w + term) to the count of
 // that edge, and an emitting state k adds its posterior exp(f[t][k] + b[t][k] - logp[q]) to (W, A, B) with the observation
-// x[t-1] shifted by c_k = param[3k].
+// x[t-1] shifted by c_k = param[3k]; a vector model's state adds it to W once and to (A_d, B_d) per component (hmm_stat).
 //
-// Accumulators: one row of n_acc = E + 3 NE + 1 doubles per workgroup (edge counts in out-edge order, (W, A, B) per
-// emitting state, the number of sequences skipped for logp = -inf).  Workgroup g takes the sequences q = g (mod gridDim.x)
+// Accumulators: one row of n_acc = E + (1 + 2 D) NE + 1 doubles per workgroup (edge counts in out-edge order, W and
+// (A_d, B_d) for d < D per emitting state -- D = 1, so (W, A, B), unless the model is a vector model --, the number of
+// sequences skipped for logp = -inf).  Workgroup g takes the sequences q = g (mod gridDim.x)
 // of [q0, q1), in ascending order, so its row sums the same sequences in the same order however the batch is cut into
 // launches.  An edge belongs to the lane that owns its source state (and a state's statistics to the lane that owns the
 // state) in every step, so a row needs no atomics.  ACC_LDS: the row is loaded into LDS next to the two score rows and
@@ -325,7 +395,7 @@ __global__ __launch_bounds__(HMM_NT) void hmm_expect_kernel(MD M, const double *
         }
         const long long base = off[q];
         const int n = static_cast<int>(off[q + 1] - base);
-        const double *x = obs + base;
+        const double *x = obs + base * hmm_dim(M);
         const double *f = fmat + (base + q - f_row0) * S;
         hmm_bwd_sweep(
             M, x, n, hm_lds, [&](int k, int t) { return f[static_cast<long long>(t) * S + k]; },
@@ -336,11 +406,16 @@ __global__ __launch_bounds__(HMM_NT) void hmm_expect_kernel(MD M, const double *
             [&](int k, int t, double fk, double bk) {
                 if (t > 0 && fk > NEG && bk > NEG) {
                     const double g = exp(fk + bk - lq);
-                    const double d = x[t - 1] - M.param[3 * k];
-                    const double gd = g * d;
-                    st[3 * k] += g;
-                    st[3 * k + 1] += gd;
-                    st[3 * k + 2] += gd * d;
+                    const int D = hmm_dim(M);
+                    double *s = st + (1 + 2 * D) * k;
+                    const auto xt = hmm_obs(M, x, t - 1);
+                    s[0] += g;
+                    for (int c = 0; c < D; ++c) {
+                        const double d = hmm_stat(M, k, c, xt);
+                        const double gd = g * d;
+                        s[1 + 2 * c] += gd;
+                        s[2 + 2 * c] += gd * d;
+                    }
                 }
             },
             [](int, const double *) {});
@@ -352,7 +427,7 @@ __global__ __launch_bounds__(HMM_NT) void hmm_expect_kernel(MD M, const double *
 }
 
 // The per-workgroup rows of hmm_expect_kernel summed in workgroup order (one thread per entry: a fixed order, so the same
-// rows give the same bits): counts[E], stats[3 NE], *skipped.
+// rows give the same bits): counts[E], stats[(1 + 2 D) NE], *skipped.
 __global__ __launch_bounds__(256) void hmm_expect_reduce_kernel(const double *acc_rows, int G, int n_acc, int E,
                                                                 double *counts, double *stats, double *skipped)
 {
@@ -419,7 +494,7 @@ __global__ __launch_bounds__(HMM_NT) void hmm_posterior_kernel(MD M, const doubl
     const bool want_map = map_state || map_logp;
     double m = NEG; int am = 0x7fffffff;      // the lane's largest log posterior of the step and its state
     hmm_bwd_sweep(
-        M, obs + base, n, hm_lds, [&](int k, int t) { return f[static_cast<long long>(t) * S + k]; },
+        M, obs + base * hmm_dim(M), n, hm_lds, [&](int k, int t) { return f[static_cast<long long>(t) * S + k]; },
         [&](int e, double v, double fk) {
             const double w = fk - lq;
             if (CNT && w > NEG && v > NEG) cnt[e] += exp(w + v);

@@ -569,17 +569,20 @@ class Context(object):
         return logp[:n_seq], mat, (path, path_off, path_len[:n_seq])
 
     @_serialised
-    def hmm_expect(self, model, obs, off):
+    def hmm_expect(self, model, obs, off, stat_width=3):
         """ps_hmm_expect: the Baum-Welch E-step over a batch.  model: a _lib.HmmModel (its arrays kept alive by the caller);
         obs: float64 CUDA tensor, sequence q = obs[off[q]:off[q+1]].  Returns (logp float64 [n_seq], edge counts float64
-        [n_edges] in out-edge order, (W, A, B) float64 [n_emit, 3], the number of sequences skipped for logp = -inf)."""
+        [n_edges] in out-edge order, statistics float64 [n_emit, stat_width], the number of sequences skipped for
+        logp = -inf).  stat_width: the doubles per emitting state the library writes -- 3, (W, A, B), or 1 + 2 n_dim for a
+        vector model (kind 4), whose obs holds n_dim doubles per observation; the caller, who built the model, says which
+        (pypore_amd.hmm.Model._stat_width)."""
         off, off_p = _offsets(off)
         n_seq = off.size - 1
         dev = _f64_device(obs)
         n_edges = int(ctypes.cast(model.out_ptr, ctypes.POINTER(ctypes.c_int32))[model.n_states])
         logp = torch.empty(max(n_seq, 1), dtype=torch.float64, device=dev)
         counts = torch.empty(max(n_edges, 1), dtype=torch.float64, device=dev)
-        stats = torch.empty((max(model.n_emit, 1), 3), dtype=torch.float64, device=dev)
+        stats = torch.empty((max(model.n_emit, 1), int(stat_width)), dtype=torch.float64, device=dev)
         skipped = ctypes.c_int32(0)
         torch.cuda.current_stream(dev).synchronize()
         _lib.check(self.L.ps_hmm_expect(self.handle, ctypes.byref(model), _ptr(obs), off_p, n_seq, _ptr(logp), _ptr(counts),

@@ -1,5 +1,6 @@
 """Hidden Markov models with the surface the reference's HMM code uses (yahmm: Model, State, NormalDistribution,
-UniformDistribution, GaussianKernelDensity; add_state(s), add_transition, add_model, bake; viterbi, forward, backward,
+UniformDistribution, GaussianKernelDensity, MultivariateDistribution, LogNormalDistribution, ExponentialDistribution;
+add_state(s), add_transition, add_model, bake; viterbi, forward, backward,
 log_probability, forward_backward, maximum_a_posteriori) and the reference's profile HMM builders (HMMBoard, the three
 board modules, ModularProfileModel, Phi29ProfileHMM, Hel308ProfileHMM: the end of this module), decoded on the MI355X
 (ps_hmm_batch, ps_hmm_posterior, csrc/seg_hmm.hpp), and trained there (Model.train: Baum-Welch with its E-step in
@@ -34,7 +35,32 @@ others' exp, the form the recursions use -- so an observation far from every poi
 instead of log(0).  With one point it is NormalDistribution(p, h).  On the device the lane that owns the state walks its
 points (csrc/seg_hmm.hpp hmm_emit); the flat form holds them as CSR tables kde_ptr / kde_pt / kde_lw.
 
+Vector models (observations of more than one number: the reference's tutorial decodes
+`[(s.mean, s.std, s.duration) for s in event.segments]`).  MultivariateDistribution(distributions, weights) is D >= 1
+independent univariate components -- Normal, Uniform, LogNormal or ExponentialDistribution -- with weights w_d, finite and
+> 0 (default 1); its log density of a length-D observation is  w_0 l_0(x_0) + w_1 l_1(x_1) + ...,  added in ascending d
+from the first product (not from 0.0), so one component of weight 1 gives that component's own bits, and an impossible
+component gives -inf, never NaN.  LogNormalDistribution(mu, sigma), with y = log x:
+(-log(sigma sqrt(2 pi)) - (y - mu)^2 / (2 sigma^2)) - y  for x > 0, -inf otherwise; ExponentialDistribution(rate):
+log(rate) - rate x  for x >= 0, -inf otherwise (a dwell time is not normal: a duration component takes one of the two).
+Every emitting state of a model has the same dimension D = Model.n_dim (ValueError at bake() otherwise).  A model whose
+emitting states are all normal, uniform or kernel density is compiled, uploaded and run as ever: the same flat arrays,
+kernels and bits; n_dim = 1 and the flat entries comp_kind / comp_param / comp_w are empty.  Any model with a Multivariate,
+LogNormal or ExponentialDistribution state is a vector model: every emitting state is compiled as D components (kind 4; a
+plain normal or uniform state of a D = 1 model becomes one component of weight 1), the device reads the component tables
+(csrc/seg_hmm.hpp HmmDevV: the lane that owns the state walks its components) and `param` is left 0.  A vector model takes
+sequences of shape (n, D) -- anything np.asarray makes of that shape, a list of tuples as in the tutorial; [] is the empty
+sequence; at D = 1 also 1-D -- in every method below, their _batch twins, expected_counts_batch and train; any other shape
+is a ValueError that names D.  The device's log is not numpy's bit for bit, so results with log-normal components agree
+with tests/multivariate_oracle.py to 1e-12, not to the bit; every other component does.
+
 Deviations from yahmm, by design:
+  * yahmm is not available to compare against.  What is assumed of its MultivariateDistribution is the constructor
+    (distributions, weights), `parameters = [distributions, weights]`, and that a weight multiplies its component's log
+    probability; of its LogNormalDistribution(mu, sigma) and ExponentialDistribution(rate) the argument order and the
+    textbook densities above.  Nothing about its arithmetic or its training of these classes is assumed.
+  * a GaussianKernelDensity cannot be a component, nor stand in a vector model (ValueError; the point loop inside the
+    component loop is not built), and a MultivariateDistribution cannot be nested (ValueError).
   * GaussianKernelDensity is normalised: it carries the 1/h factor above.  yahmm is not available to compare against; as
     far as is known its kernel density leaves 1/h out, which is the same density at bandwidth 1, the default and what
     every caller in the reference's alignment.py uses.  Nothing else about its arithmetic is assumed.
@@ -90,7 +116,14 @@ new probability is count / (sum over k's out-edges), k keeps its old probabiliti
 p = edge_inertia p_old + (1 - edge_inertia) p_new.  A normal state with W > 0 gets mean = c + A/W, var = B/W - (A/W)^2,
 std = max(sqrt(max(var, 0)), min_std), each mixed with its old value by distribution_inertia; W = 0 leaves it.  A
 distribution shared by several states is updated once, from their pooled statistics.  Frozen distributions
-(Distribution.freeze()) are never updated.  The structure stays: `states`, their order and `edges` do not change, an edge
+(Distribution.freeze()) are never updated.  In a vector model state k's statistics are W_k and, per component d,
+A_kd = sum g (y_d - c_kd), B_kd = sum g (y_d - c_kd)^2 with y_d = log x_d for a log-normal component and x_d otherwise,
+and c_kd the component's shift (normal: mean; log-normal: mu; exponential: 0; uniform: low) -- `stats` is [n_emit, 1 + 2 D],
+the (W, A, B) layout at D = 1.  The M-step updates COMPONENT distributions, pooled per distribution object over the
+states and the component slots that hold it: a normal as above from (W, A_d, B_d); a log-normal by the same formulas on
+log x, giving mu and sigma, with min_std the floor of sigma; an exponential  rate = W / A  (left as it is when A <= 0);
+uniform components are untouched, and a frozen MultivariateDistribution freezes all its components.
+The structure stays: `states`, their order and `edges` do not change, an edge
 whose probability becomes 0 keeps its place (log -inf on the device), and the trained probabilities are written back to
 the transitions, so a later bake() starts from them (and drops the zero edges, as always).  algorithm='viterbi' counts
 each consecutive pair of states on every Viterbi path as one transition and gives each observation weight 1 in the
@@ -112,7 +145,11 @@ import numpy as np
 NEG_INF = float("-inf")
 _LOG_SQRT_2PI = 0.5 * math.log(2.0 * math.pi)
 KIND_SILENT, KIND_NORMAL, KIND_UNIFORM, KIND_KDE = 0, 1, 2, 3     # include/poreseg.h ps_hmm_model.kind
+KIND_VECTOR = 4                                       # ... kind: a state of n_dim components (a vector model)
+KIND_LOGNORMAL, KIND_EXPONENTIAL = 5, 6               # ps_hmm_model.comp_kind, beside KIND_NORMAL and KIND_UNIFORM
+COMPONENT_KINDS = (KIND_NORMAL, KIND_UNIFORM, KIND_LOGNORMAL, KIND_EXPONENTIAL)
 MAX_STATES = 4096                                     # csrc/seg_hmm.hpp HMM_S_MAX
+MAX_DIM = 16                                          # csrc/seg_hmm.hpp HMM_D_MAX
 
 
 class Distribution(object):
@@ -231,6 +268,99 @@ class GaussianKernelDensity(Distribution):
         return (math.fsum(p * w for p, w in zip(points, weights)), 1.0 / (2.0 * h * h), -(math.log(h) + _LOG_SQRT_2PI))
 
 
+class LogNormalDistribution(Distribution):
+    """log density, with y = log x:  (-log(sigma sqrt(2 pi)) - (y - mu)^2 / (2 sigma^2)) - y  for x > 0, -inf otherwise.
+    A state with it makes its model a vector model (module docstring)."""
+    kind = KIND_LOGNORMAL
+
+    def __init__(self, mu, sigma):
+        mu, sigma = float(mu), float(sigma)
+        if not math.isfinite(mu):
+            raise ValueError("LogNormalDistribution needs a finite mu, got %r" % mu)
+        if not sigma > 0 or not math.isfinite(sigma):
+            raise ValueError("LogNormalDistribution needs a finite sigma > 0, got %r" % sigma)
+        Distribution.__init__(self, [mu, sigma])
+
+    def log_probability(self, x):
+        if not x > 0:
+            return NEG_INF
+        mu, sigma = self.parameters
+        y = math.log(x)
+        return (-math.log(sigma) - _LOG_SQRT_2PI - (y - mu) ** 2 / (2 * sigma * sigma)) - y
+
+    def compiled(self):
+        mu, sigma = self.parameters
+        return mu, 1.0 / (2.0 * sigma * sigma), -(math.log(sigma) + _LOG_SQRT_2PI)
+
+
+class ExponentialDistribution(Distribution):
+    """log density log(rate) - rate x for x >= 0, -inf otherwise.  A state with it makes its model a vector model."""
+    kind = KIND_EXPONENTIAL
+
+    def __init__(self, rate):
+        rate = float(rate)
+        if not rate > 0 or not math.isfinite(rate):
+            raise ValueError("ExponentialDistribution needs a finite rate > 0, got %r" % rate)
+        Distribution.__init__(self, [rate])
+
+    def log_probability(self, x):
+        rate, = self.parameters
+        return math.log(rate) - rate * x if x >= 0 else NEG_INF
+
+    def compiled(self):
+        rate, = self.parameters
+        return 0.0, rate, math.log(rate)
+
+
+class MultivariateDistribution(Distribution):
+    """D >= 1 independent univariate components (NormalDistribution, UniformDistribution, LogNormalDistribution or
+    ExponentialDistribution), each with a weight w_d, finite and > 0 (default 1): the log density of a length-D observation
+    is  w_0 l_0(x_0) + w_1 l_1(x_1) + ...,  added in ascending d from the first product, so one component of weight 1 gives
+    that component's own bits.  parameters = [distributions, weights].  A GaussianKernelDensity or another
+    MultivariateDistribution as a component raises ValueError.  freeze() freezes every component with it."""
+    kind = KIND_VECTOR
+
+    def __init__(self, distributions, weights=None):
+        distributions = list(distributions)
+        if not distributions:
+            raise ValueError("MultivariateDistribution needs at least one component")
+        for d in distributions:
+            if isinstance(d, MultivariateDistribution):
+                raise ValueError("a MultivariateDistribution cannot be a component of another")
+            if isinstance(d, GaussianKernelDensity):
+                raise ValueError("a GaussianKernelDensity cannot be a component of a MultivariateDistribution")
+            if not isinstance(d, Distribution) or d.kind not in COMPONENT_KINDS:
+                raise ValueError("a component must be a Normal, Uniform, LogNormal or ExponentialDistribution, got %r"
+                                 % (d,))
+        if weights is None:
+            weights = [1.0] * len(distributions)
+        weights = [float(w) for w in np.asarray(weights, dtype=np.float64).reshape(-1)]
+        if len(weights) != len(distributions):
+            raise ValueError("MultivariateDistribution got %d weights for %d components"
+                             % (len(weights), len(distributions)))
+        if not all(math.isfinite(w) and w > 0 for w in weights):
+            raise ValueError("MultivariateDistribution needs finite weights > 0")
+        Distribution.__init__(self, [distributions, weights])
+
+    def log_probability(self, x):
+        distributions, weights = self.parameters
+        x = np.asarray(x, dtype=np.float64).reshape(-1)
+        if x.size != len(distributions):
+            raise ValueError("an observation of %d values for %d components" % (x.size, len(distributions)))
+        total = None
+        for d, w, v in zip(distributions, weights, x.tolist()):
+            term = w * d.log_probability(v)
+            total = term if total is None else total + term
+        return total
+
+
+def _components(distribution):
+    """[(component distribution, weight, frozen)] of an emitting state's distribution: its own components, or itself."""
+    if distribution.kind == KIND_VECTOR:
+        return [(d, w, d.frozen or distribution.frozen) for d, w in zip(*distribution.parameters)]
+    return [(distribution, 1.0, distribution.frozen)]
+
+
 class State(object):
     """A state of a Model: emitting with a Distribution, silent with None."""
 
@@ -259,6 +389,7 @@ class Model(object):
         self._edges = collections.OrderedDict()            # (from, to) -> probability as given
         self._pseudo = {}                                  # (from, to) -> pseudocount (train(use_pseudocount=True))
         self.states = None                                 # after bake()
+        self.n_dim = None                                  # after bake(): values per observation
         self._flat = None
         self._c = None                                     # the ctypes view of _flat, made on first use
         self.add_state(self.start)
@@ -362,10 +493,11 @@ class Model(object):
             print("%s: %d states (%d silent), %d edges, %s" % (self.name, S, S - NE, len(self.edges),
                                                                  "finite" if self.finite else "infinite"))
         # the flat form (include/poreseg.h ps_hmm_model)
+        self.n_dim, vector = self._dimension(emitting)
         kind = np.zeros(S, np.int32)
         for k, s in enumerate(emitting):
-            kind[k] = s.distribution.kind
-        param, kde = self._emission_tables(emitting, S)
+            kind[k] = KIND_VECTOR if vector else s.distribution.kind
+        param, kde = self._emission_tables(emitting, S, self.n_dim if vector else 0)
         lv = np.array([level[id(s)] for s in silent], np.int64)
         n_levels = int(lv.max()) + 1 if lv.size else 0
         level_ptr = (NE + np.searchsorted(lv, np.arange(n_levels + 1))).astype(np.int32)
@@ -377,7 +509,7 @@ class Model(object):
         by_src = np.lexsort((dst, src))                 # out-edges: per source, target ascending
         self._flat = dict(
             n_states=S, n_emit=NE, n_levels=n_levels, start=index[id(self.start)], end=index[id(self.end)],
-            finite=int(self.finite), kind=kind, level_ptr=level_ptr, param=param,
+            finite=int(self.finite), n_dim=self.n_dim, kind=kind, level_ptr=level_ptr, param=param,
             in_ptr=np.concatenate(([0], np.cumsum(np.bincount(dst, minlength=S)))).astype(np.int32),
             in_src=np.ascontiguousarray(src[by_dst]), in_lp=np.ascontiguousarray(lp[by_dst]),
             out_ptr=np.concatenate(([0], np.cumsum(np.bincount(src, minlength=S)))).astype(np.int32),
@@ -425,21 +557,52 @@ class Model(object):
         self._added = [s for s in self._added if s not in gone]
         self._known = {id(s) for s in self._added}
 
+    def _dimension(self, emitting):
+        """(n_dim, vector): the one dimension of the emitting states' distributions (ValueError when they differ; 1 without
+        emitting states), and whether the model is a vector model -- some state is a MultivariateDistribution, log-normal or
+        exponential -- which cannot hold a kernel-density state (ValueError)."""
+        dims = sorted({len(_components(s.distribution)) for s in emitting}) or [1]
+        if len(dims) > 1:
+            raise ValueError("model %r: every emitting state must have the same dimension, got %s"
+                             % (self.name, ", ".join(str(d) for d in dims)))
+        vector = any(s.distribution.kind in (KIND_VECTOR, KIND_LOGNORMAL, KIND_EXPONENTIAL) for s in emitting)
+        if vector and dims[0] > MAX_DIM:
+            raise ValueError("model %r has %d components per state: the device HMM kernels take at most %d"
+                             % (self.name, dims[0], MAX_DIM))
+        if vector and any(s.distribution.kind == KIND_KDE for s in emitting):
+            raise ValueError("model %r: a kernel-density state cannot stand in a vector model (one with a Multivariate, "
+                             "LogNormal or ExponentialDistribution state)" % self.name)
+        return dims[0], vector
+
     @staticmethod
-    def _emission_tables(emitting, S):
-        """param[3 S] and the kernel-density CSR tables (kde_ptr[n_emit + 1] into kde_pt / kde_lw: the points and log
-        weights of the kind-3 states, zero-weight points left out)."""
+    def _emission_tables(emitting, S, vector_dim=0):
+        """param[3 S], the kernel-density CSR tables (kde_ptr[n_emit + 1] into kde_pt / kde_lw: the points and log
+        weights of the kind-3 states, zero-weight points left out) and the component tables comp_kind / comp_param /
+        comp_w (n_emit * vector_dim components; empty unless the model is a vector model, whose param stays 0)."""
         param = np.zeros(3 * S, np.float64)
         ptr, pts, lws = [0], [], []
+        ckind, cparam, cw = [], [], []
         for k, s in enumerate(emitting):
-            param[3 * k:3 * k + 3] = s.distribution.compiled()
-            if s.distribution.kind == KIND_KDE:
-                p, lw = s.distribution.tables()
-                pts.extend(p)
-                lws.extend(lw)
+            if vector_dim:
+                for d, w, _ in _components(s.distribution):
+                    ckind.append(d.kind)
+                    cparam.extend(d.compiled())
+                    cw.append(w)
+            else:
+                param[3 * k:3 * k + 3] = s.distribution.compiled()
+                if s.distribution.kind == KIND_KDE:
+                    p, lw = s.distribution.tables()
+                    pts.extend(p)
+                    lws.extend(lw)
             ptr.append(len(pts))
         return param, dict(kde_ptr=np.array(ptr, np.int32), kde_pt=np.array(pts, np.float64).reshape(-1),
-                           kde_lw=np.array(lws, np.float64).reshape(-1))
+                           kde_lw=np.array(lws, np.float64).reshape(-1), comp_kind=np.array(ckind, np.int32).reshape(-1),
+                           comp_param=np.array(cparam, np.float64).reshape(-1), comp_w=np.array(cw, np.float64).reshape(-1))
+
+    @property
+    def _vector(self):
+        """The baked model is a vector model: its emitting states are kind 4 and read the component tables."""
+        return bool(self.flat["comp_kind"].size)
 
     @property
     def flat(self):
@@ -460,23 +623,42 @@ class Model(object):
             if f["kde_pt"].size:                                # (read by the library only when some kind is 3)
                 for k in ("kde_ptr", "kde_pt", "kde_lw"):
                     setattr(m, k, f[k].ctypes.data)
+            m.n_dim = f["n_dim"]
+            if f["comp_kind"].size:                             # (read by the library only when some kind is 4)
+                for k in ("comp_kind", "comp_param", "comp_w"):
+                    setattr(m, k, f[k].ctypes.data)
             self._c = m
         return self._c
 
     # ---- inference on the device ---------------------------------------------------------------------------------
+    def _sequences(self, sequences):
+        """The sequences as contiguous float64 arrays: 1-D for n_dim = 1, (n, n_dim) for a vector model of n_dim > 1 (a
+        list of tuples; [] is the empty sequence).  A vector model of n_dim = 1 takes (n, 1) as well."""
+        D = self.flat["n_dim"]
+        seqs = [np.ascontiguousarray(s, dtype=np.float64) for s in sequences]
+        for i, s in enumerate(seqs):
+            if D == 1:
+                if s.ndim == 2 and s.shape[1] == 1 and self._vector:
+                    seqs[i] = s.reshape(-1)
+                elif s.ndim != 1:
+                    raise ValueError("an observation sequence must be 1-D, got shape %r" % (s.shape,))
+            elif s.ndim == 1 and s.size == 0:
+                seqs[i] = s.reshape(0, D)
+            elif s.ndim != 2 or s.shape[1] != D:
+                raise ValueError("an observation sequence of a model with n_dim = %d must have shape (n, %d), got %r"
+                                 % (D, D, s.shape))
+        return seqs
+
     def _upload(self, sequences, device):
         import torch
         from . import engine
         f = self.flat
-        seqs = [np.ascontiguousarray(s, dtype=np.float64) for s in sequences]
-        for s in seqs:
-            if s.ndim != 1:
-                raise ValueError("an observation sequence must be 1-D, got shape %r" % (s.shape,))
+        seqs = self._sequences(sequences)
         if f["n_states"] > MAX_STATES:
             raise ValueError("model %r has %d states: the device HMM kernels take at most %d" % (self.name, f["n_states"], MAX_STATES))
         ctx = engine.context(device)
-        off = np.concatenate(([0], np.cumsum([s.size for s in seqs]))).astype(np.int64)
-        obs = np.concatenate(seqs) if off[-1] else np.zeros(1, np.float64)
+        off = np.concatenate(([0], np.cumsum([s.shape[0] for s in seqs]))).astype(np.int64)
+        obs = np.concatenate([s.reshape(-1) for s in seqs]) if off[-1] else np.zeros(1, np.float64)
         obs = torch.from_numpy(obs).to(torch.device("cuda", ctx.device))
         return ctx, off, obs
 
@@ -588,11 +770,18 @@ class Model(object):
     # ---- training ------------------------------------------------------------------------------------------------
     def expected_counts_batch(self, sequences, device=None):
         """The Baum-Welch E-step on the device (ps_hmm_expect), summed over the sequences: Expectations(counts: float64
-        per edge, aligned with `edges`; stats: float64 [n_emit, 3], (W, A, B) per emitting state (module docstring);
+        per edge, aligned with `edges`; stats: float64 [n_emit, 3], (W, A, B) per emitting state -- for a vector model
+        [n_emit, 1 + 2 n_dim]: W, then (A_d, B_d) per component (module docstring);
         logp: float64 per sequence; skipped: the number of sequences with logp = -inf)."""
         ctx, off, obs = self._upload(sequences, device)
-        logp, counts, stats, skipped = ctx.hmm_expect(self._c_model(), obs, off)
-        return Expectations(counts.cpu().numpy(), stats.cpu().numpy().reshape(-1, 3), logp.cpu().numpy(), skipped)
+        width = self._stat_width
+        logp, counts, stats, skipped = ctx.hmm_expect(self._c_model(), obs, off, width)
+        return Expectations(counts.cpu().numpy(), stats.cpu().numpy().reshape(-1, width), logp.cpu().numpy(), skipped)
+
+    @property
+    def _stat_width(self):
+        """Statistics per emitting state: (W, A, B), or W and (A_d, B_d) per component of a vector model."""
+        return 1 + 2 * self.flat["n_dim"] if self._vector else 3
 
     def _viterbi_counts(self, sequences, device=None):
         """Viterbi training's statistics (host counting on viterbi_batch's paths), as an Expectations."""
@@ -602,9 +791,15 @@ class Model(object):
         dst = np.array([e[1] for e in self.edges], np.int64)
         keys = src * S + dst                             # ascending: edges are sorted by (from, to)
         counts = np.zeros(len(self.edges))
-        stats = np.zeros((NE, 3))
-        shift = f["param"][0:3 * NE:3]
-        seqs = [np.asarray(x, dtype=np.float64) for x in sequences]
+        stats = np.zeros((NE, self._stat_width))
+        vector, D = self._vector, f["n_dim"]
+        if vector:                                       # per component: its shift, and whether it counts log x
+            shift = f["comp_param"][0::3].reshape(NE, D)
+            logs = f["comp_kind"].reshape(NE, D) == KIND_LOGNORMAL
+            seqs = [x.reshape(-1, D) for x in self._sequences(sequences)]
+        else:
+            shift = f["param"][0:3 * NE:3]
+            seqs = [np.asarray(x, dtype=np.float64) for x in sequences]
         res = self.viterbi_batch(seqs, device) if seqs else []
         logp = np.array([lp for lp, _ in res], np.float64)
         skipped = 0
@@ -616,8 +811,16 @@ class Model(object):
             pk = idx[:-1] * S + idx[1:]
             np.add.at(counts, np.searchsorted(keys, pk), 1.0)
             em = idx[idx < NE]
-            d = x - shift[em]
             np.add.at(stats[:, 0], em, 1.0)
+            if vector:
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    y = np.where(logs[em], np.log(x), x)
+                d = y - shift[em]
+                for c in range(D):
+                    np.add.at(stats[:, 1 + 2 * c], em, d[:, c])
+                    np.add.at(stats[:, 2 + 2 * c], em, d[:, c] * d[:, c])
+                continue
+            d = x - shift[em]
             np.add.at(stats[:, 1], em, d)
             np.add.at(stats[:, 2], em, d * d)
         return Expectations(counts, stats, logp, skipped)
@@ -634,15 +837,17 @@ class Model(object):
 
     def _m_step(self, counts, stats, transition_pseudocount=0, use_pseudocount=False, edge_inertia=0.0,
                 distribution_inertia=0.0, min_std=0.01):
-        """New edge probabilities and normal parameters from the E-step's statistics (module docstring); the flat arrays
-        are derived again, so the next device call uploads the trained model."""
+        """New edge probabilities and distribution parameters from the E-step's statistics (module docstring); the flat
+        arrays are derived again, so the next device call uploads the trained model."""
         f = self.flat
         S, NE = f["n_states"], f["n_emit"]
         counts = np.asarray(counts, np.float64).reshape(-1)
-        stats = np.asarray(stats, np.float64).reshape(-1, 3)
-        if counts.size != len(self.edges) or stats.shape[0] != NE:
-            raise ValueError("statistics for %d edges and %d emitting states, the model has %d and %d"
-                             % (counts.size, stats.shape[0], len(self.edges), NE))
+        width = self._stat_width
+        stats = np.asarray(stats, np.float64)
+        if counts.size != len(self.edges) or stats.size != NE * width:
+            raise ValueError("statistics for %d edges and %d values of the emitting states, the model has %d edges and "
+                             "%d emitting states of %d values each" % (counts.size, stats.size, len(self.edges), NE, width))
+        stats = stats.reshape(NE, width)
         src = np.array([e[0] for e in self.edges], np.int64)
         old = np.array([e[2] for e in self.edges], np.float64)
         c = counts + float(transition_pseudocount)
@@ -657,18 +862,25 @@ class Model(object):
         self.edges = [(i, j, float(p)) for (i, j, _), p in zip(self.edges, new)]
         for i, j, p in self.edges:
             self._edges[(self.states[i], self.states[j])] = p
-        # normal states, pooled per distribution object (uniform and kernel-density distributions stay as they are)
+        # normal, log-normal and exponential distributions, pooled per distribution object over the states and component
+        # slots that hold it (uniform and kernel-density distributions stay as they are)
+        vector, D = self._vector, f["n_dim"]
         pooled = collections.OrderedDict()
         for k in range(NE):
-            d = self.states[k].distribution
-            if d.kind != KIND_NORMAL or d.frozen:
-                continue
-            acc = pooled.setdefault(id(d), [d, f["param"][3 * k], 0.0, 0.0, 0.0])
-            acc[2:] = [acc[2] + stats[k, 0], acc[3] + stats[k, 1], acc[4] + stats[k, 2]]
+            for c, (d, _, frozen) in enumerate(_components(self.states[k].distribution)):
+                if d.kind not in (KIND_NORMAL, KIND_LOGNORMAL, KIND_EXPONENTIAL) or frozen:
+                    continue
+                shift = f["comp_param"][3 * (k * D + c)] if vector else f["param"][3 * k]
+                acc = pooled.setdefault(id(d), [d, shift, 0.0, 0.0, 0.0])
+                acc[2:] = [acc[2] + stats[k, 0], acc[3] + stats[k, 1 + 2 * c], acc[4] + stats[k, 2 + 2 * c]]
         for d, shift, W, A, B in pooled.values():
             if not W > 0:
                 continue
-            m = A / W
+            if d.kind == KIND_EXPONENTIAL:               # (shift 0: A = sum g x)
+                if A > 0:
+                    d.parameters = [distribution_inertia * d.parameters[0] + (1.0 - distribution_inertia) * (W / A)]
+                continue
+            m = A / W                                    # (of log x for a log-normal: mu and sigma)
             mean = shift + m
             std = max(math.sqrt(max(B / W - m * m, 0.0)), min_std)
             om, os_ = d.parameters
@@ -683,16 +895,17 @@ class Model(object):
             lp = np.log(np.array([e[2] for e in self.edges], np.float64).reshape(-1))
         f["out_lp"] = np.ascontiguousarray(lp)
         f["in_lp"] = np.ascontiguousarray(lp[self._in_order])
-        f["param"], kde = self._emission_tables(self.states[:f["n_emit"]], f["n_states"])
-        f.update(kde)
+        f["param"], tables = self._emission_tables(self.states[:f["n_emit"]], f["n_states"],
+                                                   f["n_dim"] if self._vector else 0)
+        f.update(tables)
         self._flat = f
         self._c = None
 
     def train(self, sequences, stop_threshold=1e-9, min_iterations=0, max_iterations=None, algorithm='baum-welch',
               verbose=True, transition_pseudocount=0, use_pseudocount=False, edge_inertia=0.0, distribution_inertia=0.0,
               min_std=0.01, device=None):
-        """Trains the baked model on `sequences` (each a 1-D array of observations) and returns the total improvement of
-        the summed log probability.  Each iteration is an E-step ('baum-welch': ps_hmm_expect on the device; 'viterbi':
+        """Trains the baked model on `sequences` (each a 1-D array of observations; (n, n_dim) for a vector model) and
+        returns the total improvement of the summed log probability.  Each iteration is an E-step ('baum-welch': ps_hmm_expect on the device; 'viterbi':
         counts on viterbi_batch's paths) and the M-step of the module docstring.  The loop (sequences impossible under
         the starting model are left out of every sum):
 
@@ -722,10 +935,7 @@ class Model(object):
         if isinstance(sequences, np.ndarray) and sequences.ndim == 1:
             raise ValueError("train takes a list of sequences, not one sequence")
         self.flat                                              # raises before bake()
-        seqs = [np.ascontiguousarray(x, dtype=np.float64) for x in sequences]
-        for x in seqs:
-            if x.ndim != 1:
-                raise ValueError("an observation sequence must be 1-D, got shape %r" % (x.shape,))
+        seqs = self._sequences(sequences)
         mstep = dict(transition_pseudocount=float(transition_pseudocount), use_pseudocount=bool(use_pseudocount),
                      edge_inertia=float(edge_inertia), distribution_inertia=float(distribution_inertia),
                      min_std=float(min_std))
