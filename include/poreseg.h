@@ -464,6 +464,49 @@ int ps_hmm_expect(ps_ctx *ctx, const ps_hmm_model *model, const double *d_obs, c
 int ps_hmm_posterior(ps_ctx *ctx, const ps_hmm_model *model, const double *d_obs, const int64_t *h_off, int32_t n_seq,
                      double *d_logp, double *d_post, int32_t *d_map_state, double *d_map_logp, double *d_counts_seq);
 
+/* What sampling reads beside the model (pypore_amd.hmm.Model._sample_tables), host arrays built in fp64 from the
+ * distributions themselves, so that no decision of a walk depends on a device logarithm or exponential:
+ *   out_cdf    n_cdf = out_ptr[n_states] doubles, aligned with out_dst: per state the running sum of its out-edges'
+ *              probabilities, added one by one (>= 0 and ascending), the state's last entry stored as exactly 1.0;
+ *   emit_param n_param = 2 n_emit doubles (2 n_emit n_dim for a vector model, component k n_dim + d): normal (mean, std),
+ *              uniform (low, high - low), log-normal (mu, sigma), exponential (0, rate), kernel density (0, bandwidth);
+ *   kde_cdf    n_kde = kde_ptr[n_emit] doubles, aligned with kde_pt: per kernel-density state the running sum of its
+ *              points' weights, the state's last entry exactly 1.0 (NULL and 0 without kind-3 states).
+ * The weights comp_w of a vector model are not read: a weight scales a log density and defines nothing to draw from. */
+typedef struct ps_hmm_sample_tables {
+    const double *out_cdf, *emit_param, *kde_cdf;
+    int64_t n_cdf, n_param, n_kde;
+} ps_hmm_sample_tables;
+
+/* Samples n_seq sequences from the model: walks from `start` along the out-edges, an observation drawn on entering an
+ * emitting state.  length = 0: a walk runs until it enters `end` (a model that is not finite: PS_ERR_ARG); length > 0: it
+ * stops at `end` or right after its length-th emission, whichever comes first.  A walk that has made max_length (>= 1)
+ * emissions without such an end stops there.
+ *
+ * The random stream: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85) with key
+ * (seed & 0xffffffff, seed >> 32).  Sequence Q = first + q (first >= 0) owns the blocks j = 0, 1, 2, ... at counter
+ * (j & 0xffffffff, j >> 32, Q & 0xffffffff, Q >> 32); a block r0..r3 gives  u0 = ((r0 >> 5) 2^26 + (r1 >> 6)) 2^-53  and u1
+ * likewise from r2, r3.  Blocks are taken in walk order.  A transition out of state k takes one: the first out-edge e of
+ * k with u0 < out_cdf[e].  An emission takes one per component in ascending d, with  z = sqrt(-2 log(1 - u0)) cos(2 pi u1):
+ * normal  mean + std z;  uniform  low + u0 (high - low);  log-normal  exp(mu + sigma z);  exponential  -log(1 - u0) / rate;
+ * a kernel-density state takes two: the first point i with u0 < kde_cdf[i], then  p_i + h z  from the next block.  No
+ * multiply-add is fused.  So a call with the same arguments gives the same bits, a batch cut in two with `first` moved on
+ * gives the bits of the whole, and a walk's path and length depend on (seed, Q, out_cdf) alone.
+ *
+ * Sequence q writes its observations, n_dim doubles each, to d_obs at slot [h_off[q], h_off[q+1]) (counted in
+ * observations) and, when d_path and h_path_off are given, its path -- the states visited from `start` on, silent ones
+ * included -- to d_path[h_path_off[q] .. h_path_off[q+1]).  d_len[q] and d_path_len[q] (optional without a path buffer)
+ * always receive the full lengths; d_flags[q] = 0 (the walk entered `end` or made its `length` emissions), 1 (stopped at
+ * max_length) or 2 (it stood in a state without out-edges).  A walk whose slot is full goes on counting without writing,
+ * and the call returns PS_ERR_CAPACITY with every length reported and the sequences that fit written: the walks are
+ * deterministic, so the caller sizes the slots exactly and calls again.  Limits as ps_hmm_batch; besides,
+ * (max_length + 1) (n_levels + 1) + 2, the longest path there can be, must fit in int32 (PS_ERR_ARG).  The tables are
+ * uploaded per call; the model's upload is the one ps_hmm_batch keeps.  Synchronises the context's stream before
+ * returning. */
+int ps_hmm_sample(ps_ctx *ctx, const ps_hmm_model *model, const ps_hmm_sample_tables *tables, uint64_t seed, int64_t first,
+                  int32_t n_seq, int32_t length, int32_t max_length, double *d_obs, const int64_t *h_off, int32_t *d_len,
+                  int32_t *d_flags, int32_t *d_path, const int64_t *h_path_off, int32_t *d_path_len);
+
 /* Timing of the most recent ps_segment_batch, measured with HIP events on the context's stream.
  * ms[7] = the call's device work from the first upload to the last result copy (option "timing" >= 1, the
  * default); ms[3] = whole call on the host's wall clock.  With option "timing" = 2 an event is also recorded

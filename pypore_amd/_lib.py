@@ -19,7 +19,7 @@ EXPORTS = ["ps_version", "ps_device_count", "ps_create", "ps_destroy", "ps_last_
            "ps_synchronize", "ps_min_gain", "ps_segment_batch", "ps_segment_batch_ex", "ps_segment_events", "ps_segment_exact_f64", "ps_detect_events", "ps_detect_segment_trace", "ps_bounds_capacity",
            "ps_best_single_split", "ps_score_window", "ps_get_timings", "ps_synth_trace", "ps_filter_bessel",
            "ps_requantise", "ps_filter_requantise_batch", "ps_align_batch", "ps_audit_bounds", "ps_counters",
-           "ps_get_near_ties", "ps_hmm_batch", "ps_hmm_expect", "ps_hmm_posterior", "ps_pairwise_scores", "ps_pairwise_batch"]
+           "ps_get_near_ties", "ps_hmm_batch", "ps_hmm_expect", "ps_hmm_posterior", "ps_hmm_sample", "ps_pairwise_scores", "ps_pairwise_batch"]
 PS_HMM_VITERBI, PS_HMM_FORWARD, PS_HMM_BACKWARD = 0, 1, 2
 PS_PW_GLOBAL, PS_PW_LOCAL, PS_PW_LOCAL_REPEATED = 0, 1, 2
 PS_PW_OK, PS_PW_INDEX_ERROR = 0, 1
@@ -50,6 +50,12 @@ class HmmModel(ctypes.Structure):
                [(f, ctypes.c_void_p) for f in ("kind", "level_ptr", "in_ptr", "in_src", "out_ptr", "out_dst",
                                                 "param", "in_lp", "out_lp", "kde_ptr", "kde_pt", "kde_lw")] + \
                [("n_dim", ctypes.c_int32)] + [(f, ctypes.c_void_p) for f in ("comp_kind", "comp_param", "comp_w")]
+
+
+class HmmSampleTables(ctypes.Structure):
+    """ps_hmm_sample_tables: what ps_hmm_sample reads beside the model (pypore_amd.hmm.Model._sample_tables)."""
+    _fields_ = [(f, ctypes.c_void_p) for f in ("out_cdf", "emit_param", "kde_cdf")] + \
+               [(f, ctypes.c_int64) for f in ("n_cdf", "n_param", "n_kde")]
 
 
 _lib = None
@@ -105,6 +111,8 @@ def lib():
     L.ps_hmm_batch.argtypes = [vp, P(HmmModel), i32, vp, P(i64), i32, vp, vp, vp, P(i64), vp]
     L.ps_hmm_expect.argtypes = [vp, P(HmmModel), vp, P(i64), i32, vp, vp, vp, P(i32)]
     L.ps_hmm_posterior.argtypes = [vp, P(HmmModel), vp, P(i64), i32, vp, vp, vp, vp, vp]
+    L.ps_hmm_sample.argtypes = [vp, P(HmmModel), P(HmmSampleTables), ctypes.c_uint64, i64, i32, i32, i32, vp, P(i64), vp, vp, vp,
+                                P(i64), vp]
     L.ps_pairwise_scores.argtypes = [vp, vp, P(i64), i32, vp, P(i64), i32, i32, dbl, vp, vp]
     L.ps_pairwise_batch.argtypes = [vp, vp, P(i64), i32, vp, P(i64), i32, P(i32), P(i32), i32, i32, dbl, i32, vp, vp,
                                     P(i64), vp, vp, vp, P(i64), vp, vp, vp, vp]

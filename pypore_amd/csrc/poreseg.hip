@@ -184,6 +184,7 @@ struct ps_ctx {
     // Baum-Welch E-step (ps_hmm_expect): forward matrices of one launch, per-workgroup accumulator rows, the skipped count
     DevBuf hmm_fmat, hmm_acc, hmm_skip;
     DevBuf hmm_pmax;                         // ps_hmm_posterior: the per-observation maxima that d_map_logp sums
+    DevBuf hmm_samp;                         // ps_hmm_sample: the sampling tables, then the observation and path offsets
     long long hmm_fb_budget = 4ll << 30;     // option hmm_fb_budget: bytes of forward matrices per launch
     bool hmm_expect_lds = true;              // option hmm_expect_lds 0: the accumulator rows stay in global memory
     int stitch_host = 0;      // 1: host stitch with halo tiles (the fallback path) always
@@ -1471,7 +1472,8 @@ void ps_destroy(ps_ctx *ctx)
                       &ctx->align_in, &ctx->align_scratch, &ctx->pw_in, &ctx->pw_scratch, &ctx->bridge_ext, &ctx->ext_slot, &ctx->ext_list,
                       &ctx->lat_state, &ctx->lat_seam, &ctx->lat_res, &ctx->pre_c, &ctx->ev_info_tr, &ctx->blk_cls,
                       &ctx->cls_mm, &ctx->nt_log, &ctx->hmm_model, &ctx->hmm_off, &ctx->hmm_bp,
-                      &ctx->hmm_last, &ctx->hmm_flags, &ctx->hmm_fmat, &ctx->hmm_acc, &ctx->hmm_skip, &ctx->hmm_pmax};
+                      &ctx->hmm_last, &ctx->hmm_flags, &ctx->hmm_fmat, &ctx->hmm_acc, &ctx->hmm_skip, &ctx->hmm_pmax,
+                      &ctx->hmm_samp};
     for (DevBuf *b : bufs) b->release();
     ctx->h_meta.release(); ctx->h_dense.release(); ctx->h_small.release(); ctx->h_up.release(); ctx->h_hdr.release();
     for (auto &e : ctx->ev) if (e) (void)hipEventDestroy(e);
@@ -3317,6 +3319,95 @@ int ps_hmm_posterior(ps_ctx *ctx, const ps_hmm_model *model, const double *d_obs
         default: return hmm_posterior_run<2>(ctx, M, d_obs, h_off, C.d_off, n_seq, E, d_logp, d_post, d_map_state, d_map_logp, d_counts_seq);
         }
     });
+}
+
+int ps_hmm_sample(ps_ctx *ctx, const ps_hmm_model *model, const ps_hmm_sample_tables *tables, uint64_t seed, int64_t first,
+                  int32_t n_seq, int32_t length, int32_t max_length, double *d_obs, const int64_t *h_off, int32_t *d_len,
+                  int32_t *d_flags, int32_t *d_path, const int64_t *h_path_off, int32_t *d_path_len)
+{
+    if (!ctx) return PS_ERR_ARG;
+    if (!model || !tables || !h_off) return fail(ctx, PS_ERR_ARG, "null pointer");
+    if (n_seq < 0) return fail(ctx, PS_ERR_ARG, "negative sequence count");
+    if (first < 0 || first > INT64_MAX - n_seq) return fail(ctx, PS_ERR_ARG, "first must be >= 0 and first + n_seq fit in int64");
+    if (length < 0) return fail(ctx, PS_ERR_ARG, "negative length");
+    if (max_length < 1) return fail(ctx, PS_ERR_ARG, "max_length must be >= 1");
+    const bool want_path = d_path && h_path_off;
+    if ((d_path != nullptr) != (h_path_off != nullptr)) return fail(ctx, PS_ERR_ARG, "a path buffer and its offsets go together");
+    if (want_path && n_seq > 0 && !d_path_len) return fail(ctx, PS_ERR_ARG, "paths need the length array");
+    int64_t longest = 0;
+    if (int rc = check_offsets(ctx, h_off, n_seq, "observation slot", &longest)) return rc;
+    for (int32_t q = 0; want_path && q < n_seq; ++q)
+        if (h_path_off[q] < 0 || h_path_off[q + 1] < h_path_off[q]) return fail(ctx, PS_ERR_ARG, "path offsets must be non-negative and ascending");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HmmCall C;
+    if (int rc = hmm_upload(ctx, model, &C.DK, &C.DV, &C.max_in, &C.kde, &C.vec)) return rc;
+    const int S = C.DK.S, NE = C.DK.n_emit;
+    C.E = model->out_ptr[S];
+    if (!model->finite && length == 0) return fail(ctx, PS_ERR_ARG, "a model without an edge into end never ends a walk: a length must be given");
+    if ((static_cast<long long>(max_length) + 1) * (C.DK.n_levels + 1) + 2 > INT32_MAX)
+        return fail(ctx, PS_ERR_ARG, "max_length %d with %d silent levels: a path could exceed int32", max_length, C.DK.n_levels);
+    // the tables against the model: sizes, every state's cdf ascending within [0, 1] and closed by exactly 1.0
+    const int64_t n_param = 2 * static_cast<int64_t>(NE) * C.dim(), n_kde = C.kde ? model->kde_ptr[NE] : 0;
+    if (tables->n_cdf != C.E || tables->n_param != n_param || tables->n_kde != n_kde)
+        return fail(ctx, PS_ERR_ARG, "sampling tables of %lld / %lld / %lld entries, the model takes %d / %lld / %lld",
+                    static_cast<long long>(tables->n_cdf), static_cast<long long>(tables->n_param), static_cast<long long>(tables->n_kde),
+                    C.E, static_cast<long long>(n_param), static_cast<long long>(n_kde));
+    if ((C.E > 0 && !tables->out_cdf) || (n_param > 0 && !tables->emit_param) || (n_kde > 0 && !tables->kde_cdf))
+        return fail(ctx, PS_ERR_ARG, "null sampling table");
+    auto cdf_ok = [](const double *cdf, int lo, int hi) {
+        double prev = 0.0;
+        for (int i = lo; i < hi; ++i) {
+            const double v = cdf[i];
+            if (i == hi - 1) return v == 1.0;
+            if (!(v >= prev) || !std::isfinite(v)) return false;      // (a rounded running sum may pass 1.0 by an ulp)
+            prev = v;
+        }
+        return true;
+    };
+    for (int k = 0; k < S; ++k)
+        if (!cdf_ok(tables->out_cdf, model->out_ptr[k], model->out_ptr[k + 1]))
+            return fail(ctx, PS_ERR_ARG, "out_cdf of state %d: ascending from >= 0 with the last entry 1.0", k);
+    for (int k = 0; C.kde && k < NE; ++k)
+        if (!cdf_ok(tables->kde_cdf, model->kde_ptr[k], model->kde_ptr[k + 1]))
+            return fail(ctx, PS_ERR_ARG, "kde_cdf of state %d: ascending from >= 0 with the last entry 1.0", k);
+    for (int64_t i = 0; i < n_param; ++i)
+        if (!std::isfinite(tables->emit_param[i])) return fail(ctx, PS_ERR_ARG, "emit_param %lld is not finite", static_cast<long long>(i));
+    if (n_seq == 0) return PS_OK;
+    if (!d_len || !d_flags || (h_off[n_seq] > 0 && !d_obs)) return fail(ctx, PS_ERR_ARG, "null device pointer");
+    const size_t nb = (static_cast<size_t>(n_seq) + 1) * sizeof(int64_t);
+    if (int rc = upload_tables(ctx, ctx->hmm_samp, {{tables->out_cdf, static_cast<size_t>(C.E) * sizeof(double)},
+                                                    {tables->emit_param, static_cast<size_t>(n_param) * sizeof(double)},
+                                                    {tables->kde_cdf, static_cast<size_t>(n_kde) * sizeof(double)},
+                                                    {h_off, nb}, {h_path_off, want_path ? nb : 0}})) return rc;
+    HmmSampleDev T;
+    T.out_cdf = ctx->hmm_samp.as<double>();
+    T.emit_param = T.out_cdf + C.E;
+    T.kde_cdf = T.emit_param + n_param;
+    const long long *d_off = reinterpret_cast<const long long *>(T.kde_cdf + n_kde);
+    const long long *d_path_off = want_path ? d_off + n_seq + 1 : nullptr;
+    const int rc = with_model(C, [&](const auto &M) -> int {
+        using MD = std::decay_t<decltype(M)>;
+        hipLaunchKernelGGL(hmm_sample_kernel<MD>, dim3((n_seq + HMM_NT - 1) / HMM_NT), dim3(HMM_NT), 0, ctx->stream, M, T,
+                           static_cast<unsigned long long>(seed), static_cast<long long>(first), n_seq, length, max_length, d_obs,
+                           d_off, d_len, d_flags, want_path ? d_path : nullptr, d_path_off, d_path_len);
+        HIP_TRY(ctx, hipGetLastError());
+        return PS_OK;
+    });
+    if (rc) return rc;
+    // the lengths against the slots, on the host: the kernel keeps no shared flag
+    std::vector<int32_t> lens(static_cast<size_t>(n_seq)), plens(want_path ? static_cast<size_t>(n_seq) : 0);
+    HIP_TRY(ctx, hipMemcpyAsync(lens.data(), d_len, lens.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (want_path) HIP_TRY(ctx, hipMemcpyAsync(plens.data(), d_path_len, plens.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    int64_t short_obs = 0, short_path = 0;
+    for (int32_t q = 0; q < n_seq; ++q) {
+        short_obs += lens[q] > h_off[q + 1] - h_off[q];
+        if (want_path) short_path += plens[q] > h_path_off[q + 1] - h_path_off[q];
+    }
+    if (short_obs || short_path)
+        return fail(ctx, PS_ERR_CAPACITY, "%lld observation slots and %lld path slots are too small (d_len and d_path_len hold the lengths)",
+                    static_cast<long long>(short_obs), static_cast<long long>(short_path));
+    return PS_OK;
 }
 
 }  // extern "C"

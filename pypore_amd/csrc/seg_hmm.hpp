@@ -570,4 +570,145 @@ __global__ __launch_bounds__(HMM_NT) void hmm_trace_kernel(HmmDev M, const long 
     }
 }
 
+// ---- sampling (ps_hmm_sample) ----------------------------------------------------------------------------------------
+// A walk from `start` along the out-edges, an observation drawn on entering an emitting state.  The decoding kernels above
+// spread one sequence's states over a wave; a walk touches one state per step, so here it is one lane per sequence: lane l
+// of workgroup g owns sequence q = g * HMM_NT + l, keeps (k, j, emitted, path_len) in registers, reads the model and the
+// sampling tables through global memory and writes its own slots.  No LDS, no atomics, no barrier.
+//
+// The random stream is counter-based, Philox4x32-10 with key (seed low, seed high): sequence Q = first + q owns the blocks
+// j = 0, 1, 2, ... at counter (j low, j high, Q low, Q high); a block of four words gives two doubles in [0, 1) and the
+// walk consumes blocks strictly in walk order (one per transition, one per component of an emission, two for a
+// kernel-density state), so a walk's path and length depend on (seed, Q, out_cdf) alone, never on the values drawn.
+
+struct HmmSampleDev {           // device copies of ps_hmm_sample_tables (include/poreseg.h)
+    const double *out_cdf;      // per out-edge: the running sum of the state's edge probabilities, its last entry 1.0
+    const double *emit_param;   // 2 per emitting state (per component k D + d of a vector model)
+    const double *kde_cdf;      // per kernel-density point: the running sum of the state's weights, its last entry 1.0
+};
+
+struct HmmPhilox {
+    unsigned r[4];
+    __device__ __forceinline__ HmmPhilox(unsigned long long seed, unsigned long long Q, unsigned long long j)
+    {
+        unsigned c0 = static_cast<unsigned>(j), c1 = static_cast<unsigned>(j >> 32);
+        unsigned c2 = static_cast<unsigned>(Q), c3 = static_cast<unsigned>(Q >> 32);
+        unsigned k0 = static_cast<unsigned>(seed), k1 = static_cast<unsigned>(seed >> 32);
+#pragma unroll
+        for (int i = 0; i < 10; ++i) {
+            const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
+            const unsigned n0 = static_cast<unsigned>(p1 >> 32) ^ c1 ^ k0, n2 = static_cast<unsigned>(p0 >> 32) ^ c3 ^ k1;
+            c1 = static_cast<unsigned>(p1); c3 = static_cast<unsigned>(p0); c0 = n0; c2 = n2;
+            k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+        }
+        r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
+    }
+    // 53 bits of two words: a multiple of 2^-53 in [0, 1), so 1 - u is exact and > 0
+    __device__ __forceinline__ static double unit(unsigned a, unsigned b)
+    {
+        return static_cast<double>((static_cast<unsigned long long>(a >> 5) << 26) | (b >> 6)) * 0x1p-53;
+    }
+    __device__ __forceinline__ double u0() const { return unit(r[0], r[1]); }
+    __device__ __forceinline__ double u1() const { return unit(r[2], r[3]); }
+    // a standard normal from the block's two doubles (Box-Muller, the cosine branch)
+    __device__ __forceinline__ double normal() const
+    {
+#pragma clang fp contract(off)
+        return sqrt(-2.0 * log(1.0 - u0())) * cos(6.283185307179586 * u1());
+    }
+};
+
+// The first i of [lo, hi) with u < cdf[i], by bisection.  cdf ascends over [lo, hi - 1) and cdf[hi - 1] = 1.0 > u, so
+// "u < cdf[i]" is false up to some i and true from there on: bisection finds the index a linear scan would.  hi > lo.
+__device__ __forceinline__ int hmm_cdf_pick(const double *cdf, int lo, int hi, double u)
+{
+    --hi;                                   // (the last entry is never read: it is 1.0)
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (u < cdf[mid]) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+// One draw of kind kd with the table's two parameters (a, b): normal (mean, std), uniform (low, high - low), log-normal
+// (mu, sigma), exponential (0, rate).
+__device__ __forceinline__ double hmm_draw(int kd, double a, double b, const HmmPhilox &R)
+{
+#pragma clang fp contract(off)
+    if (kd == HMM_UNIFORM) return a + R.u0() * b;
+    if (kd == HMM_EXPONENTIAL) return -log(1.0 - R.u0()) / b;
+    const double v = a + b * R.normal();
+    return kd == HMM_LOGNORMAL ? exp(v) : v;
+}
+
+// The emission of state k: its values go to x (null: drawn and dropped, the slot is full); j counts the blocks taken.
+__device__ __forceinline__ void hmm_sample_emit(const HmmDev &M, const HmmSampleDev &T, int k, unsigned long long seed,
+                                                unsigned long long Q, unsigned long long &j, double *x)
+{
+    const double v = hmm_draw(M.kind[k], T.emit_param[2 * k], T.emit_param[2 * k + 1], HmmPhilox(seed, Q, j++));
+    if (x) *x = v;
+}
+__device__ __forceinline__ void hmm_sample_emit(const HmmDevK &M, const HmmSampleDev &T, int k, unsigned long long seed,
+                                                unsigned long long Q, unsigned long long &j, double *x)
+{
+#pragma clang fp contract(off)
+    if (M.kind[k] != HMM_KDE) return hmm_sample_emit(static_cast<const HmmDev &>(M), T, k, seed, Q, j, x);
+    const int i = hmm_cdf_pick(T.kde_cdf, M.kde_ptr[k], M.kde_ptr[k + 1], HmmPhilox(seed, Q, j++).u0());
+    const double v = M.kde_pt[i] + T.emit_param[2 * k + 1] * HmmPhilox(seed, Q, j++).normal();
+    if (x) *x = v;
+}
+__device__ __forceinline__ void hmm_sample_emit(const HmmDevV &M, const HmmSampleDev &T, int k, unsigned long long seed,
+                                                unsigned long long Q, unsigned long long &j, double *x)
+{
+    for (int d = 0, i = k * M.D; d < M.D; ++d, ++i) {
+        const double v = hmm_draw(M.comp_kind[i], T.emit_param[2 * i], T.emit_param[2 * i + 1], HmmPhilox(seed, Q, j++));
+        if (x) x[d] = v;
+    }
+}
+
+// Sequence q of [0, nq): observations (hmm_dim(M) doubles each) into obs[off[q] .. off[q+1]), the path -- every state
+// visited from start on, silent ones included; path null: none -- into path[path_off[q] .. path_off[q+1]).  What does not
+// fit its slot is counted and not written: len[q] and path_len[q] (null: not kept) are the full lengths whatever the slots
+// hold.  flags[q]: 0 the walk entered end or made its `length` emissions (length 0: no such stop), 1 it stopped at
+// max_length emissions, 2 it stood in a state without out-edges.
+//
+// Termination: bake rejects cycles of silent states and the library checks that every silent edge goes up a level, so
+// between two emissions a walk takes at most n_levels silent steps and one emitting step: at most
+// (max_length + 1) * (n_levels + 1) + 1 transitions in all.  The loop is bounded by that as well.
+template <typename MD = HmmDev>
+__global__ __launch_bounds__(HMM_NT) void hmm_sample_kernel(MD M, HmmSampleDev T, unsigned long long seed, long long first,
+                                                            int nq, int length, int max_length, double *obs,
+                                                            const long long *off, int *len, int *flags, int *path,
+                                                            const long long *path_off, int *path_len)
+{
+    const int q = blockIdx.x * HMM_NT + threadIdx.x;
+    if (q >= nq) return;
+    const unsigned long long Q = static_cast<unsigned long long>(first) + static_cast<unsigned long long>(q);
+    const int D = hmm_dim(M), NE = M.n_emit;
+    const long long cap = off[q + 1] - off[q], pcap = path ? path_off[q + 1] - path_off[q] : 0;
+    double *x = obs + off[q] * D;
+    int *p = path ? path + path_off[q] : nullptr;
+    const long long bound = (static_cast<long long>(max_length) + 1) * (M.n_levels + 1) + 1;
+    unsigned long long j = 0;
+    int k = M.start, emitted = 0, flag = 1;
+    long long plen = 1;
+    if (pcap > 0) p[0] = k;
+    for (long long step = 0; step < bound; ++step) {
+        if (k == M.end || (length > 0 && emitted >= length)) { flag = 0; break; }
+        if (emitted >= max_length) break;
+        const int e0 = M.out_ptr[k], e1 = M.out_ptr[k + 1];
+        if (e0 == e1) { flag = 2; break; }
+        k = M.out_dst[hmm_cdf_pick(T.out_cdf, e0, e1, HmmPhilox(seed, Q, j++).u0())];
+        if (plen < pcap) p[plen] = k;
+        ++plen;
+        if (k < NE) {
+            hmm_sample_emit(M, T, k, seed, Q, j, emitted < cap ? x + static_cast<long long>(emitted) * D : nullptr);
+            ++emitted;
+        }
+    }
+    len[q] = emitted;
+    flags[q] = flag;
+    if (path_len) path_len[q] = static_cast<int>(plen);
+}
+
 }  // namespace ps

@@ -611,6 +611,49 @@ class Context(object):
         return logp[:n_seq], post, map_state, map_logp[:n_seq] if want_map else None, counts
 
     @_serialised
+    def hmm_sample(self, model, tables, seed, first, n_seq, length=0, max_length=1000000, want_path=False, obs_slots=None,
+                   path_slots=None, retry=True):
+        """ps_hmm_sample: n_seq walks of the model, sequence q on the random stream of (seed, first + q).  model: a
+        _lib.HmmModel, tables: a _lib.HmmSampleTables (their arrays kept alive by the caller).  Returns (rc, obs float64
+        tensor [slots, n_dim], off, lengths int32 [n_seq], flags int32 [n_seq], and (path int32 tensor, path offsets, path
+        lengths int32 [n_seq]) or None): sequence q is obs[off[q]:off[q] + lengths[q]].  obs_slots / path_slots: entries per
+        sequence (default: `length`, or 2 n_emit observations when it is 0; 2 (slot + 1) + the silent states + 1 path
+        entries).  A walk longer than its slot is counted, not written (PS_ERR_CAPACITY); with retry the call then runs
+        again with slots of the exact lengths -- the walks are the same -- and rc is PS_OK; without, rc is returned as it
+        is (PS_OK or PS_ERR_CAPACITY) with whatever fitted.  Any other status raises."""
+        n_seq = int(n_seq)
+        dev = torch.device("cuda", self.device)
+        D = model.n_dim if model.n_dim > 1 else 1
+        if obs_slots is None:
+            obs_slots = np.full(max(n_seq, 0), int(length) if length > 0 else 2 * model.n_emit, np.int64)
+        obs_slots = np.asarray(obs_slots, np.int64).reshape(-1)
+        if want_path and path_slots is None:
+            path_slots = 2 * (obs_slots + 1) + (model.n_states - model.n_emit) + 1
+        lens = torch.empty(max(n_seq, 1), dtype=torch.int32, device=dev)
+        flags = torch.empty(max(n_seq, 1), dtype=torch.int32, device=dev)
+        path_len = torch.empty(max(n_seq, 1), dtype=torch.int32, device=dev) if want_path else None
+        torch.cuda.current_stream(dev).synchronize()
+        for attempt in range(2):
+            off, off_p = _offsets(np.concatenate(([0], np.cumsum(obs_slots))))
+            obs = torch.empty((max(int(off[-1]), 1), D), dtype=torch.float64, device=dev)
+            path = path_off = path_off_p = None
+            if want_path:
+                path_off, path_off_p = _offsets(np.concatenate(([0], np.cumsum(np.asarray(path_slots, np.int64).reshape(-1)))))
+                path = torch.empty(max(int(path_off[-1]), 1), dtype=torch.int32, device=dev)
+            rc = self.L.ps_hmm_sample(self.handle, ctypes.byref(model), ctypes.byref(tables),
+                                      ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(first), n_seq, int(length),
+                                      int(max_length), ctypes.c_void_p(obs.data_ptr()), off_p, _ptr(lens), _ptr(flags),
+                                      ctypes.c_void_p(path.data_ptr()) if want_path else None, path_off_p, _ptr(path_len))
+            if rc != _lib.PS_ERR_CAPACITY or attempt or not retry:
+                break
+            obs_slots = lens[:n_seq].cpu().numpy().astype(np.int64)           # the exact lengths
+            if want_path:
+                path_slots = path_len[:n_seq].cpu().numpy().astype(np.int64)
+        if rc != _lib.PS_ERR_CAPACITY or retry:
+            _lib.check(rc, self.handle)
+        return rc, obs, off, lens[:n_seq], flags[:n_seq], ((path, path_off, path_len[:n_seq]) if want_path else None)
+
+    @_serialised
     def synth_trace(self, n, seed, seg_end, level_counts, dtype=torch.float32, start=0):
         """Synthetic step trace generated directly in HBM (csrc synth_kernel == pypore_amd.synth).  start > 0: the
         samples [start, start + n) of the trace the table describes (a rank's piece of one long trace): the noise hash

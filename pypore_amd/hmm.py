@@ -135,7 +135,34 @@ Deviations from yahmm, by design:
     bit), while a model's edges and normal states train around them.  Their (W, A, B) are still reported, with the shift
     c_k = the weighted mean of the points;
   * Viterbi training runs the same stop loop as Baum-Welch, measured by the sum of the Viterbi scores.
-There is no CPU fallback: inference and the Baum-Welch E-step run on the GPU library or raise.
+
+Sampling (Model.sample, Model.sample_batch; the device -- ps_hmm_sample, csrc/seg_hmm.hpp hmm_sample_kernel -- and
+tests/sample_oracle.py compute the same thing; Distribution.sample is one numpy draw on the host).  A walk starts in `start`
+and, before every step, stops when it stands in `end` or has made `length` > 0 emissions (flag 0), has made max_length
+emissions (flag 1) or stands in a state without out-edges (flag 2); otherwise it takes one transition and, when the new
+state emits, draws one observation.  The random stream is counter-based, Philox4x32-10 with key (seed & 0xffffffff,
+seed >> 32): sequence Q = first + q owns the blocks j = 0, 1, 2, ... at counter (j & 0xffffffff, j >> 32, Q & 0xffffffff,
+Q >> 32), a block r0..r3 gives u0 = ((r0 >> 5) 2^26 + (r1 >> 6)) 2^-53 and u1 likewise from r2, r3, and blocks are taken in walk
+order: one per transition -- the first out-edge e of the state with u0 < out_cdf[e] --, one per component of an emission in
+ascending d, with z = sqrt(-2 log(1 - u0)) cos(2 pi u1): normal mean + std z, uniform low + u0 (high - low), log-normal
+exp(mu + sigma z), exponential -log(1 - u0) / rate; a kernel-density state takes two: the first point i with u0 < kde_cdf[i],
+then p_i + h z from the next block.  The tables are built on the host in float64 (Model._sample_tables, not part of `flat`):
+out_cdf, per state the running sum of np.exp(out_lp) in out-edge order, added one by one, the last entry stored as exactly
+1.0; kde_cdf the same over exp(kde_lw); emit_param, two doubles per emitting state or component: normal (mean, std), uniform
+(low, high - low), log-normal (mu, sigma), exponential (0, rate), kernel density (0, bandwidth).  So a walk's path and
+length depend on (seed, Q, out_cdf) alone, an integer seed reproduces a call bit for bit, and a batch cut in two with `first`
+moved on gives the bits of the whole.  Values that pass through the device's log, cos and exp agree with the oracle to
+1e-12, uniform draws to the bit.
+
+Deviations from yahmm, by design:
+  * yahmm is not available to compare against.  What is assumed of its Model.sample is the signature (length=0, path=False),
+    that it returns a list, or (list, path) with path=True, and that an infinite model without a length is an error.
+  * length > 0 on a finite model: the walk stops at `end` or after `length` emissions, whichever comes first, so the result
+    is the prefix of a true sample.  As far as is known yahmm renormalises the walk away from `end` until the length is
+    reached, which is not a sample of the model; that walk is not built.
+  * a MultivariateDistribution's weights take no part in sampling, on the device or in Distribution.sample: a weight scales
+    a log density and defines no distribution to draw from (yahmm ignores them as well).
+There is no CPU fallback: inference, sampling and the Baum-Welch E-step run on the GPU library or raise.
 """
 import collections
 import math
@@ -150,6 +177,10 @@ KIND_LOGNORMAL, KIND_EXPONENTIAL = 5, 6               # ps_hmm_model.comp_kind, 
 COMPONENT_KINDS = (KIND_NORMAL, KIND_UNIFORM, KIND_LOGNORMAL, KIND_EXPONENTIAL)
 MAX_STATES = 4096                                     # csrc/seg_hmm.hpp HMM_S_MAX
 MAX_DIM = 16                                          # csrc/seg_hmm.hpp HMM_D_MAX
+
+
+def _rng(rng):
+    return np.random.default_rng() if rng is None else rng
 
 
 class Distribution(object):
@@ -170,6 +201,10 @@ class Distribution(object):
     def log_probability(self, x):
         raise NotImplementedError
 
+    def sample(self, rng=None):
+        """One draw on the host (numpy; rng: a np.random.Generator, default a fresh np.random.default_rng())."""
+        raise NotImplementedError
+
     def __repr__(self):
         return "%s(%s)" % (type(self).__name__, ", ".join(repr(p) for p in self.parameters))
 
@@ -187,6 +222,10 @@ class NormalDistribution(Distribution):
     def log_probability(self, x):
         mean, std = self.parameters
         return -math.log(std) - _LOG_SQRT_2PI - (x - mean) ** 2 / (2 * std * std)
+
+    def sample(self, rng=None):
+        mean, std = self.parameters
+        return float(_rng(rng).normal(mean, std))
 
     def compiled(self):
         mean, std = self.parameters
@@ -206,6 +245,10 @@ class UniformDistribution(Distribution):
     def log_probability(self, x):
         low, high = self.parameters
         return -math.log(high - low) if low <= x <= high else NEG_INF
+
+    def sample(self, rng=None):
+        low, high = self.parameters
+        return low + float(_rng(rng).random()) * (high - low)
 
     def compiled(self):
         low, high = self.parameters
@@ -263,6 +306,12 @@ class GaussianKernelDensity(Distribution):
             return NEG_INF
         return -(math.log(h) + _LOG_SQRT_2PI) + (m + math.log1p(r))
 
+    def sample(self, rng=None):
+        """A point chosen by its weight, then a normal of the bandwidth around it."""
+        points, h, weights = self.parameters
+        rng = _rng(rng)
+        return float(rng.normal(points[int(rng.choice(len(points), p=np.asarray(weights) / math.fsum(weights)))], h))
+
     def compiled(self):
         points, h, weights = self.parameters
         return (math.fsum(p * w for p, w in zip(points, weights)), 1.0 / (2.0 * h * h), -(math.log(h) + _LOG_SQRT_2PI))
@@ -288,6 +337,10 @@ class LogNormalDistribution(Distribution):
         y = math.log(x)
         return (-math.log(sigma) - _LOG_SQRT_2PI - (y - mu) ** 2 / (2 * sigma * sigma)) - y
 
+    def sample(self, rng=None):
+        mu, sigma = self.parameters
+        return float(_rng(rng).lognormal(mu, sigma))
+
     def compiled(self):
         mu, sigma = self.parameters
         return mu, 1.0 / (2.0 * sigma * sigma), -(math.log(sigma) + _LOG_SQRT_2PI)
@@ -306,6 +359,10 @@ class ExponentialDistribution(Distribution):
     def log_probability(self, x):
         rate, = self.parameters
         return math.log(rate) - rate * x if x >= 0 else NEG_INF
+
+    def sample(self, rng=None):
+        rate, = self.parameters
+        return float(_rng(rng).exponential(1.0 / rate))
 
     def compiled(self):
         rate, = self.parameters
@@ -353,12 +410,30 @@ class MultivariateDistribution(Distribution):
             total = term if total is None else total + term
         return total
 
+    def sample(self, rng=None):
+        """One draw per component, independently, as a list; the weights are ignored, as in yahmm (a weight scales a log
+        density and defines no distribution to draw from)."""
+        rng = _rng(rng)
+        return [d.sample(rng) for d in self.parameters[0]]
+
 
 def _components(distribution):
     """[(component distribution, weight, frozen)] of an emitting state's distribution: its own components, or itself."""
     if distribution.kind == KIND_VECTOR:
         return [(d, w, d.frozen or distribution.frozen) for d, w in zip(*distribution.parameters)]
     return [(distribution, 1.0, distribution.frozen)]
+
+
+def _sample_param(d):
+    """The two doubles ps_hmm_sample draws component d from (include/poreseg.h ps_hmm_sample_tables.emit_param)."""
+    a = d.parameters
+    if d.kind == KIND_UNIFORM:
+        return a[0], a[1] - a[0]
+    if d.kind == KIND_EXPONENTIAL:
+        return 0.0, a[0]
+    if d.kind == KIND_KDE:
+        return 0.0, a[1]
+    return a[0], a[1]                                     # normal (mean, std), log-normal (mu, sigma)
 
 
 class State(object):
@@ -392,6 +467,7 @@ class Model(object):
         self.n_dim = None                                  # after bake(): values per observation
         self._flat = None
         self._c = None                                     # the ctypes view of _flat, made on first use
+        self._s = None                                     # the sampling tables (_sample_tables), made on first use
         self.add_state(self.start)
         self.add_state(self.end)
 
@@ -515,7 +591,7 @@ class Model(object):
             out_ptr=np.concatenate(([0], np.cumsum(np.bincount(src, minlength=S)))).astype(np.int32),
             out_dst=np.ascontiguousarray(dst[by_src]), out_lp=np.ascontiguousarray(lp[by_src]), **kde)
         self._in_order = by_dst                         # edges (= out-edge order) -> in-edge order
-        self._c = None
+        self._c = self._s = None
 
     def _merge_silent(self, silent_only):
         """bake(merge='partial' | 'all'): rewrites the construction graph (_added, _edges, _pseudo).  Repeated until no
@@ -713,6 +789,85 @@ class Model(object):
     def log_probability(self, sequence):
         return float(self.log_probability_batch([sequence])[0])
 
+    # ---- sampling ---------------------------------------------------------------------------------------------------
+    def _sample_tables(self):
+        """What ps_hmm_sample reads beside the model (module docstring, Sampling), built in float64 from the distributions
+        and `flat` and cached beside the ctypes view: dict(out_cdf, emit_param, kde_cdf, c: the _lib.HmmSampleTables)."""
+        from . import _lib
+        f = self.flat
+        if self._s is None:
+            def cdf(lw, ptr):
+                p, out = np.exp(lw), np.zeros(lw.size, np.float64)
+                for k in range(ptr.size - 1):
+                    run = 0.0
+                    for e in range(int(ptr[k]), int(ptr[k + 1])):
+                        run = run + float(p[e])                # (added one by one, in edge order)
+                        out[e] = run
+                    if ptr[k + 1] > ptr[k]:
+                        out[ptr[k + 1] - 1] = 1.0
+                return out
+            emit = []
+            for s in self.states[:f["n_emit"]]:
+                for d, _, _ in (_components(s.distribution) if self._vector else [(s.distribution, 1.0, False)]):
+                    emit.extend(_sample_param(d))
+            t = dict(out_cdf=cdf(f["out_lp"], f["out_ptr"]), emit_param=np.array(emit, np.float64).reshape(-1),
+                     kde_cdf=cdf(f["kde_lw"], f["kde_ptr"]))
+            c = _lib.HmmSampleTables()
+            for k, count in (("out_cdf", "n_cdf"), ("emit_param", "n_param"), ("kde_cdf", "n_kde")):
+                setattr(c, k, t[k].ctypes.data if t[k].size else None)
+                setattr(c, count, t[k].size)
+            t["c"] = c
+            self._s = t
+        return self._s
+
+    def sample_batch(self, n, length=0, path=False, seed=0, first=0, max_length=1000000, device=None):
+        """n sequences sampled from the model on the device (ps_hmm_sample, module docstring): a list of float64 arrays,
+        (len,) for n_dim = 1 and (len, n_dim) for a vector model of n_dim > 1; with path=True also the list of their paths in
+        viterbi's format, [(index into `states`, state)] from `start` to the last state visited, silent states included.
+        length = 0: every walk runs until it enters `end` (ValueError for an infinite model); length > 0: until `end` or
+        `length` emissions, whichever comes first.  seed: an integer (taken modulo 2^64) makes the call reproducible bit
+        for bit; None draws one from os.urandom.  first: the index of the batch's first sequence in the random stream:
+        sample_batch(a + b, seed=s) == sample_batch(a, seed=s) + sample_batch(b, seed=s, first=a).  A walk that has made
+        max_length emissions without ending, or stands in a state without out-edges, stops there: one RuntimeWarning per
+        call says how many."""
+        import warnings
+        from . import engine
+        f = self.flat
+        n, length, first, max_length = int(n), int(length), int(first), int(max_length)
+        if n < 0 or length < 0 or first < 0:
+            raise ValueError("n, length and first must be >= 0, got %d, %d, %d" % (n, length, first))
+        if max_length < 1:
+            raise ValueError("max_length must be >= 1, got %d" % max_length)
+        if not f["finite"] and length == 0:
+            raise ValueError("model %r is infinite (no edge into end): must specify a length" % self.name)
+        if f["n_states"] > MAX_STATES:
+            raise ValueError("model %r has %d states: the device HMM kernels take at most %d" % (self.name, f["n_states"], MAX_STATES))
+        if seed is None:
+            import os
+            seed = int.from_bytes(os.urandom(8), "little")
+        tables = self._sample_tables()
+        ctx = engine.context(device)
+        _, obs, off, lens, flags, paths = ctx.hmm_sample(self._c_model(), tables["c"], int(seed), first, n, length, max_length,
+                                                         want_path=bool(path))
+        obs, lens, flags = obs.cpu().numpy(), lens.cpu().numpy(), flags.cpu().numpy()
+        if f["n_dim"] == 1:
+            obs = obs.reshape(-1)
+        seqs = [obs[off[q]:off[q] + lens[q]].copy() for q in range(n)]
+        cut, dead = int(np.count_nonzero(flags == 1)), int(np.count_nonzero(flags == 2))
+        if cut or dead:
+            warnings.warn("model %r: %d of %d sampled sequences are truncated (%d stopped at max_length = %d, %d in a state "
+                          "without out-edges)" % (self.name, cut + dead, n, cut, max_length, dead), RuntimeWarning, stacklevel=2)
+        if not path:
+            return seqs
+        p, p_off, p_len = paths[0].cpu().numpy(), paths[1], paths[2].cpu().numpy()
+        return seqs, [[(int(i), self.states[i]) for i in p[p_off[q]:p_off[q] + p_len[q]]] for q in range(n)]
+
+    def sample(self, length=0, path=False, seed=None):
+        """One sequence sampled from the model, as a plain list (of lists for a vector model of n_dim > 1), or (list, path)
+        with path=True: sample_batch(1, ...)[0]."""
+        out = self.sample_batch(1, length=length, path=path, seed=seed)
+        return (out[0][0].tolist(), out[1][0]) if path else out[0].tolist()
+
     # ---- posterior decoding ---------------------------------------------------------------------------------------
     def maximum_a_posteriori_batch(self, sequences, device=None):
         """[(logp, path) per sequence] by posterior decoding on the device (ps_hmm_posterior, module docstring): path =
@@ -899,7 +1054,7 @@ class Model(object):
                                                    f["n_dim"] if self._vector else 0)
         f.update(tables)
         self._flat = f
-        self._c = None
+        self._c = self._s = None
 
     def train(self, sequences, stop_threshold=1e-9, min_iterations=0, max_iterations=None, algorithm='baum-welch',
               verbose=True, transition_pseudocount=0, use_pseudocount=False, edge_inertia=0.0, distribution_inertia=0.0,
