@@ -396,7 +396,21 @@ int ps_pairwise_batch(ps_ctx *ctx, const double *d_a, const int64_t *h_a_off, in
  * out of range, an unknown component kind, a bad weight or a null table is PS_ERR_ARG.  d_obs then holds n_dim doubles
  * per observation -- observation t of sequence q at (h_off[q] + t) n_dim; h_off still counts observations -- and
  * ps_hmm_expect's d_stats 1 + 2 n_dim doubles per emitting state.  n_dim and the three comp_* fields were appended to the
- * struct; they are read only when some kind[k] is 4, so a caller built against a shorter struct stays correct. */
+ * struct; they are read only when some kind[k] is 4, so a caller built against a shorter struct stays correct.
+ *
+ * kind[k] = 7, a mixture state: log density  log sum_i w_i p_i(x)  over the state's components, a weighted choice between
+ * univariate distributions (weights summing to 1).  The components of emitting state k are [mix_ptr[k], mix_ptr[k+1]) of
+ * mix_kind (1, 2, 5 or 6, as comp_kind), mix_param (the component's triple, as comp_param; slot 0 is the shift of its
+ * statistics in ps_hmm_expect) and mix_lw (log w_i, <= 0; -inf: the component keeps its slot and is skipped): mix_ptr has
+ * n_emit + 1 ascending entries from 0, a kind-7 state has at least one component and any other state none, and there are
+ * at most 2^24 components in all.  param[3k..3k+2] = (0, 0, 0).  The sum is a log-sum-exp in ascending index over the
+ * terms  log w_i + l_i(x)  that are > -inf -- the largest term plus log1p of the others' exp --, -inf when there is none,
+ * never NaN; one component of weight 1 gives that component's own bits.  Observations are single doubles: a mixture state
+ * stands beside kinds 1, 2, 3 and 7 only, and kind 7 beside kind 4 is refused as kinds 1..3 are.  A null table among the
+ * four, a mix_ptr that does not start at 0 or descends, a kind-7 state without a component or another state with one, too
+ * many components, an unknown component kind, or a log weight that is NaN or > 0 is PS_ERR_ARG.  mix_cdf and mix_draw
+ * are read by ps_hmm_sample alone (see there) and may be NULL in every other call.  The six mix_* fields were appended to
+ * the struct; they are read only when some kind[k] is 7, so a caller built against a shorter struct stays correct. */
 typedef struct ps_hmm_model {
     int32_t n_states, n_emit, n_levels, start, end, finite;
     const int32_t *kind, *level_ptr, *in_ptr, *in_src, *out_ptr, *out_dst;
@@ -406,6 +420,8 @@ typedef struct ps_hmm_model {
     int32_t n_dim;
     const int32_t *comp_kind;
     const double *comp_param, *comp_w;
+    const int32_t *mix_ptr, *mix_kind;
+    const double *mix_param, *mix_lw, *mix_cdf, *mix_draw;
 } ps_hmm_model;
 
 /* Decodes a BATCH of observation sequences against one model: sequence q is d_obs[h_off[q] .. h_off[q+1]) (fp64, device).
@@ -434,8 +450,14 @@ int ps_hmm_batch(ps_ctx *ctx, const ps_hmm_model *model, int32_t mode, const dou
  * emitting state k: the sums of the posterior g, g (x - c_k) and g (x - c_k)^2 over the observations, c_k = param[3k].
  * For a vector model (kind 4) d_stats holds 1 + 2 n_dim doubles per emitting state instead: W, then (A_d, B_d) for d = 0 ..
  * n_dim - 1, with A_d = sum g (y_d - c_d), B_d = sum g (y_d - c_d)^2, y_d = log x_d for a log-normal component and x_d
- * otherwise, c_d = the component's comp_param slot 0; at n_dim = 1 that is the (W, A, B) layout.  The accumulators
- * (n_edges + (1 + 2 n_dim) n_emit + 1, at most 2^26) live in LDS when 16 n_states + 8 of them fit in 64 KiB.
+ * otherwise, c_d = the component's comp_param slot 0; at n_dim = 1 that is the (W, A, B) layout.
+ * For a model with mixture states (kind 7) and n_mix = mix_ptr[n_emit] components d_stats holds 3 (n_emit + n_mix) doubles:
+ * the states' (W, A, B) as ever -- a kind-7 state's shift is param[3k] = 0, so its row holds the raw moments --, then one
+ * (W_i, A_i, B_i) per mixture component in table order.  Where state k's posterior g at observation x is positive, each
+ * component i of k whose term  v_i = mix_lw[i] + l_i(x)  is > -inf has the responsibility  r = exp(v_i - e_k(x))  and adds
+ * w = g r  to W_i,  w d  to A_i and  (w d) d  to B_i,  d = y - mix_param[3i],  y = log x for a log-normal component and x
+ * otherwise.  The accumulators
+ * (n_acc = n_edges + (1 + 2 n_dim) n_emit + 3 n_mix + 1, at most 2^26) live in LDS when 16 n_states + 8 n_acc fit in 64 KiB.
  * A sequence with logp = -inf contributes nothing and is counted in *h_skipped.  Forward matrices are kept in HBM for
  * launches of at most option "hmm_fb_budget" bytes (default 4 GiB; at least one sequence per launch); the accumulators
  * are per-workgroup rows summed in a fixed order, so the same call with the same options gives the same bits.  Limits as
@@ -472,7 +494,13 @@ int ps_hmm_posterior(ps_ctx *ctx, const ps_hmm_model *model, const double *d_obs
  *              uniform (low, high - low), log-normal (mu, sigma), exponential (0, rate), kernel density (0, bandwidth);
  *   kde_cdf    n_kde = kde_ptr[n_emit] doubles, aligned with kde_pt: per kernel-density state the running sum of its
  *              points' weights, the state's last entry exactly 1.0 (NULL and 0 without kind-3 states).
- * The weights comp_w of a vector model are not read: a weight scales a log density and defines nothing to draw from. */
+ * The weights comp_w of a vector model are not read: a weight scales a log density and defines nothing to draw from.
+ * A model with mixture states (kind 7) brings two more tables in ps_hmm_model itself (this struct keeps its size; without
+ * them ps_hmm_sample returns PS_ERR_ARG); emit_param still holds 2 doubles per emitting state, (0, 0) for a mixture state:
+ *   mix_cdf    mix_ptr[n_emit] doubles, aligned with mix_lw: per mixture state the running sum of its components' weights,
+ *              added one by one; the entry of the state's last component of positive weight and every entry after it is
+ *              exactly 1.0, so a component of weight 0 is never picked;
+ *   mix_draw   2 doubles per mixture component, by emit_param's rule for the component's kind. */
 typedef struct ps_hmm_sample_tables {
     const double *out_cdf, *emit_param, *kde_cdf;
     int64_t n_cdf, n_param, n_kde;
@@ -489,7 +517,9 @@ typedef struct ps_hmm_sample_tables {
  * likewise from r2, r3.  Blocks are taken in walk order.  A transition out of state k takes one: the first out-edge e of
  * k with u0 < out_cdf[e].  An emission takes one per component in ascending d, with  z = sqrt(-2 log(1 - u0)) cos(2 pi u1):
  * normal  mean + std z;  uniform  low + u0 (high - low);  log-normal  exp(mu + sigma z);  exponential  -log(1 - u0) / rate;
- * a kernel-density state takes two: the first point i with u0 < kde_cdf[i], then  p_i + h z  from the next block.  No
+ * a kernel-density state takes two: the first point i with u0 < kde_cdf[i], then  p_i + h z  from the next block; a mixture
+ * state takes two as well: the first component i of the state with u0 < mix_cdf[i], then that component's draw by
+ * (mix_kind[i], mix_draw[2i], mix_draw[2i+1]) from the next block.  No
  * multiply-add is fused.  So a call with the same arguments gives the same bits, a batch cut in two with `first` moved on
  * gives the bits of the whole, and a walk's path and length depend on (seed, Q, out_cdf) alone.
  *

@@ -49,7 +49,8 @@ class HmmModel(ctypes.Structure):
                 ("start", ctypes.c_int32), ("end", ctypes.c_int32), ("finite", ctypes.c_int32)] + \
                [(f, ctypes.c_void_p) for f in ("kind", "level_ptr", "in_ptr", "in_src", "out_ptr", "out_dst",
                                                 "param", "in_lp", "out_lp", "kde_ptr", "kde_pt", "kde_lw")] + \
-               [("n_dim", ctypes.c_int32)] + [(f, ctypes.c_void_p) for f in ("comp_kind", "comp_param", "comp_w")]
+               [("n_dim", ctypes.c_int32)] + [(f, ctypes.c_void_p) for f in ("comp_kind", "comp_param", "comp_w")] + \
+               [(f, ctypes.c_void_p) for f in ("mix_ptr", "mix_kind", "mix_param", "mix_lw", "mix_cdf", "mix_draw")]
 
 
 class HmmSampleTables(ctypes.Structure):

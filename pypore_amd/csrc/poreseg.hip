@@ -2924,22 +2924,28 @@ namespace {
 // checked and appended to the blob (points and log weights after the doubles, the CSR offsets after the ints).  *V, *has_vec:
 // the same for a vector model (every emitting state kind 4): only then are n_dim and the comp_* fields read, checked and
 // appended (parameters and weights after the doubles; the component kinds and n_dim after the ints), so a changed weight
-// or parameter is a changed blob.
+// or parameter is a changed blob.  *X, *has_mix: the same for a model with mixture states (kind 7): only then are mix_ptr,
+// mix_kind, mix_param and mix_lw read, checked and appended (parameters and log weights last among the doubles; the CSR
+// offsets and the component kinds last among the ints), so a changed weight, parameter, kind or split is a changed blob.
+// mix_cdf and mix_draw are ps_hmm_sample's and are not read here.
 constexpr int64_t HMM_KDE_POINTS_MAX = 1 << 24;
-int hmm_upload(ps_ctx *ctx, const ps_hmm_model *m, HmmDevK *D, HmmDevV *V, int *max_in, bool *has_kde, bool *has_vec)
+constexpr int64_t HMM_MIX_COMPONENTS_MAX = 1 << 24;
+int hmm_upload(ps_ctx *ctx, const ps_hmm_model *m, HmmDevK *D, HmmDevV *V, HmmDevM *X, int *max_in, bool *has_kde, bool *has_vec,
+               bool *has_mix)
 {
     const int S = m->n_states, NE = m->n_emit, NL = m->n_levels;
     if (S < 1 || S > HMM_S_MAX) return fail(ctx, PS_ERR_ARG, "model of %d states: the device HMM kernels take 1..%d", S, HMM_S_MAX);
     if (NE < 0 || NE > S || NL < 0 || NL > S - NE || (NL == 0) != (NE == S)) return fail(ctx, PS_ERR_ARG, "bad state / level counts");
     if (m->start < NE || m->start >= S || m->end < NE || m->end >= S) return fail(ctx, PS_ERR_ARG, "start and end must be silent states");
     if (!m->kind || !m->level_ptr || !m->in_ptr || !m->out_ptr) return fail(ctx, PS_ERR_ARG, "null model array");
-    bool kde = false, vec = false, plain = false;
+    bool kde = false, vec = false, plain = false, mix = false;
     for (int k = 0; k < S; ++k) {
         const int kd = m->kind[k];
-        if ((k < NE) != (kd == HMM_NORMAL || kd == HMM_UNIFORM || kd == HMM_KDE || kd == HMM_VECTOR) || (k >= NE && kd != HMM_SILENT))
+        if ((k < NE) != (kd == HMM_NORMAL || kd == HMM_UNIFORM || kd == HMM_KDE || kd == HMM_VECTOR || kd == HMM_MIXTURE) || (k >= NE && kd != HMM_SILENT))
             return fail(ctx, PS_ERR_ARG, "state %d: emitting states first, then silent ones", k);
         kde = kde || kd == HMM_KDE;
         vec = vec || kd == HMM_VECTOR;
+        mix = mix || kd == HMM_MIXTURE;
         plain = plain || (k < NE && kd != HMM_VECTOR);
     }
     if (!vec && !m->param) return fail(ctx, PS_ERR_ARG, "null model array");      // (a vector model's param is not read)
@@ -2976,6 +2982,29 @@ int hmm_upload(ps_ctx *ctx, const ps_hmm_model *m, HmmDevK *D, HmmDevV *V, int *
                 return fail(ctx, PS_ERR_ARG, "kernel-density point %lld: points must be finite and log weights <= 0", static_cast<long long>(i));
     }
     *has_kde = kde;
+    int64_t NM = 0;                                      // mixture components in all
+    if (mix) {                                           // (never beside kind 4: refused above)
+        if (!m->mix_ptr || !m->mix_kind || !m->mix_param || !m->mix_lw)
+            return fail(ctx, PS_ERR_ARG, "a mixture state needs mix_ptr, mix_kind, mix_param and mix_lw");
+        if (m->mix_ptr[0] != 0) return fail(ctx, PS_ERR_ARG, "mix_ptr must start at 0");
+        for (int k = 0; k < NE; ++k) {
+            if (m->mix_ptr[k + 1] < m->mix_ptr[k]) return fail(ctx, PS_ERR_ARG, "descending mix_ptr at state %d", k);
+            if ((m->mix_ptr[k + 1] > m->mix_ptr[k]) != (m->kind[k] == HMM_MIXTURE))
+                return fail(ctx, PS_ERR_ARG, "state %d: a mixture state has at least one component, any other state none", k);
+        }
+        NM = m->mix_ptr[NE];
+        if (NM > HMM_MIX_COMPONENTS_MAX)
+            return fail(ctx, PS_ERR_ARG, "%lld mixture components: the device HMM kernels take at most %lld",
+                        static_cast<long long>(NM), static_cast<long long>(HMM_MIX_COMPONENTS_MAX));
+        for (int64_t i = 0; i < NM; ++i) {
+            const int ck = m->mix_kind[i];
+            if (ck != HMM_NORMAL && ck != HMM_UNIFORM && ck != HMM_LOGNORMAL && ck != HMM_EXPONENTIAL)
+                return fail(ctx, PS_ERR_ARG, "mixture component %lld: unknown component kind %d", static_cast<long long>(i), ck);
+            if (!(m->mix_lw[i] <= 0.0))
+                return fail(ctx, PS_ERR_ARG, "mixture component %lld: a log weight must be <= 0", static_cast<long long>(i));
+        }
+    }
+    *has_mix = mix;
     if (m->level_ptr[0] != NE || m->level_ptr[NL] != S) return fail(ctx, PS_ERR_ARG, "levels must cover the silent states");
     for (int L = 0; L < NL; ++L) if (m->level_ptr[L + 1] <= m->level_ptr[L]) return fail(ctx, PS_ERR_ARG, "empty or descending level %d", L);
     std::vector<int> level(S, -1);
@@ -3001,9 +3030,11 @@ int hmm_upload(ps_ctx *ctx, const ps_hmm_model *m, HmmDevK *D, HmmDevV *V, int *
     }
     if (n_edge[0] != n_edge[1]) return fail(ctx, PS_ERR_ARG, "in- and out-edge lists differ in length");
     if (*max_in > 65535) return fail(ctx, PS_ERR_ARG, "a state with %d in-edges: the device HMM kernels take at most 65535", *max_in);
-    const size_t nd0 = 3 * static_cast<size_t>(S) + 2 * n_edge[0], nd = nd0 + 2 * static_cast<size_t>(NP) + 4 * NC;
+    const size_t nd0 = 3 * static_cast<size_t>(S) + 2 * n_edge[0], nd1 = nd0 + 2 * static_cast<size_t>(NP) + 4 * NC,
+                 nd = nd1 + 4 * static_cast<size_t>(NM);
     const size_t ni0 = static_cast<size_t>(S) + (NL + 1) + 2 * (S + 1) + 2 * n_edge[0] + 3;
-    const size_t ni = ni0 + (kde ? static_cast<size_t>(NE) + 1 : 0) + (vec ? NC + 1 : 0);      // (kde and vec exclude each other)
+    const size_t ni1 = ni0 + (kde ? static_cast<size_t>(NE) + 1 : 0) + (vec ? NC + 1 : 0);     // (kde and vec exclude each other)
+    const size_t ni = ni1 + (mix ? static_cast<size_t>(NE) + 1 + static_cast<size_t>(NM) : 0);
     std::vector<char> blob(nd * sizeof(double) + ni * sizeof(int32_t), 0);
     double *bd = reinterpret_cast<double *>(blob.data());
     if (!vec) std::memcpy(bd, m->param, 3 * S * sizeof(double));      // (a vector model's slots stay 0)
@@ -3034,6 +3065,12 @@ int hmm_upload(ps_ctx *ctx, const ps_hmm_model *m, HmmDevK *D, HmmDevV *V, int *
         std::memcpy(bi + ni0, m->comp_kind, NC * sizeof(int32_t));
         bi[ni0 + NC] = m->n_dim;
     }
+    if (mix) {
+        std::memcpy(bd + nd1, m->mix_param, 3 * static_cast<size_t>(NM) * sizeof(double));
+        std::memcpy(bd + nd1 + 3 * NM, m->mix_lw, static_cast<size_t>(NM) * sizeof(double));
+        std::memcpy(bi + ni1, m->mix_ptr, (static_cast<size_t>(NE) + 1) * sizeof(int32_t));
+        std::memcpy(bi + ni1 + NE + 1, m->mix_kind, static_cast<size_t>(NM) * sizeof(int32_t));
+    }
     if (blob != ctx->hmm_blob || !ctx->hmm_model.p) {
         HIP_TRY(ctx, ctx->hmm_model.reserve(blob.size()));
         HIP_TRY(ctx, hipMemcpyAsync(ctx->hmm_model.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
@@ -3050,6 +3087,10 @@ int hmm_upload(ps_ctx *ctx, const ps_hmm_model *m, HmmDevK *D, HmmDevV *V, int *
     static_cast<HmmDev &>(*V) = *D;
     V->comp_param = vec ? dd + nd0 : nullptr; V->comp_w = vec ? dd + nd0 + 3 * NC : nullptr; V->comp_kind = vec ? di + ni0 : nullptr;
     V->D = vec ? m->n_dim : 1;
+    static_cast<HmmDevK &>(*X) = *D;
+    X->mix_param = mix ? dd + nd1 : nullptr; X->mix_lw = mix ? dd + nd1 + 3 * NM : nullptr;
+    X->mix_ptr = mix ? di + ni1 : nullptr; X->mix_kind = mix ? di + ni1 + NE + 1 : nullptr;
+    X->mix_cdf = X->mix_draw = nullptr;                  // (ps_hmm_sample's: it sets them after its own upload)
     return PS_OK;
 }
 
@@ -3090,16 +3131,27 @@ int launch_forward(ps_ctx *ctx, const MD &D, const double *d_obs, const long lon
 struct HmmCall {
     HmmDevK DK;
     HmmDevV DV;
-    bool kde = false, vec = false;
+    HmmDevM DM;
+    bool kde = false, vec = false, mix = false;
+    int n_mix = 0;                          // mixture components of the model (mix_ptr[n_emit])
     int max_in = 0, E = 0;                  // most in-edges of a state, out-edges of the model
     const long long *d_off = nullptr;
     int dim() const { return vec ? DV.D : 1; }                                        // doubles per observation
-    long long n_acc() const { return E + (1ll + 2 * dim()) * DK.n_emit + 1; }          // hmm_expect_kernel's accumulators
+    long long n_stats() const { return (1ll + 2 * dim()) * DK.n_emit + 3ll * n_mix; }  // doubles of ps_hmm_expect's d_stats
+    long long n_acc() const { return E + n_stats() + 1; }                              // hmm_expect_kernel's accumulators
 };
-// a vector model takes the HmmDevV instantiations, one with kernel-density states the HmmDevK ones, any other the HmmDev ones
+// a vector model takes the HmmDevV instantiations, one with mixture states the HmmDevM ones, one with kernel-density states
+// (and no mixture) the HmmDevK ones, any other the HmmDev ones
 template <typename F> int with_model(const HmmCall &C, F &&f)
 {
-    return C.vec ? f(C.DV) : C.kde ? f(C.DK) : f(static_cast<const HmmDev &>(C.DK));
+    return C.vec ? f(C.DV) : C.mix ? f(C.DM) : C.kde ? f(C.DK) : f(static_cast<const HmmDev &>(C.DK));
+}
+int hmm_upload(ps_ctx *ctx, const ps_hmm_model *model, HmmCall *C)
+{
+    if (int rc = hmm_upload(ctx, model, &C->DK, &C->DV, &C->DM, &C->max_in, &C->kde, &C->vec, &C->mix)) return rc;
+    C->E = model->out_ptr[C->DK.S];
+    C->n_mix = C->mix ? model->mix_ptr[C->DK.n_emit] : 0;
+    return PS_OK;
 }
 template <typename Own>
 int hmm_begin(ps_ctx *ctx, const ps_hmm_model *model, bool host_ok, const double *d_obs, const int64_t *h_off,
@@ -3113,8 +3165,7 @@ int hmm_begin(ps_ctx *ctx, const ps_hmm_model *model, bool host_ok, const double
     for (int32_t q = 0; h_path_off && q < n_seq; ++q)
         if (h_path_off[q] < 0 || h_path_off[q + 1] < h_path_off[q]) return fail(ctx, PS_ERR_ARG, "path offsets must be non-negative and ascending");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (int rc = hmm_upload(ctx, model, &C->DK, &C->DV, &C->max_in, &C->kde, &C->vec)) return rc;
-    C->E = model->out_ptr[C->DK.S];
+    if (int rc = hmm_upload(ctx, model, C)) return rc;
     if (int rc = own(*C)) return rc;
     if (n_seq == 0) return PS_OK;
     if (!d_logp || (h_off[n_seq] > 0 && !d_obs)) return fail(ctx, PS_ERR_ARG, "null device pointer");
@@ -3282,7 +3333,7 @@ int ps_hmm_expect(ps_ctx *ctx, const ps_hmm_model *model, const double *d_obs, c
         *h_skipped = 0;
         if (n_seq == 0) {
             if (E > 0) HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, static_cast<size_t>(E) * sizeof(double), ctx->stream));
-            if (NE > 0) HIP_TRY(ctx, hipMemsetAsync(d_stats, 0, (1 + 2 * static_cast<size_t>(c.dim())) * NE * sizeof(double), ctx->stream));
+            if (NE > 0) HIP_TRY(ctx, hipMemsetAsync(d_stats, 0, static_cast<size_t>(c.n_stats()) * sizeof(double), ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         }
         return PS_OK;
@@ -3340,14 +3391,14 @@ int ps_hmm_sample(ps_ctx *ctx, const ps_hmm_model *model, const ps_hmm_sample_ta
         if (h_path_off[q] < 0 || h_path_off[q + 1] < h_path_off[q]) return fail(ctx, PS_ERR_ARG, "path offsets must be non-negative and ascending");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HmmCall C;
-    if (int rc = hmm_upload(ctx, model, &C.DK, &C.DV, &C.max_in, &C.kde, &C.vec)) return rc;
+    if (int rc = hmm_upload(ctx, model, &C)) return rc;
     const int S = C.DK.S, NE = C.DK.n_emit;
-    C.E = model->out_ptr[S];
     if (!model->finite && length == 0) return fail(ctx, PS_ERR_ARG, "a model without an edge into end never ends a walk: a length must be given");
     if ((static_cast<long long>(max_length) + 1) * (C.DK.n_levels + 1) + 2 > INT32_MAX)
         return fail(ctx, PS_ERR_ARG, "max_length %d with %d silent levels: a path could exceed int32", max_length, C.DK.n_levels);
     // the tables against the model: sizes, every state's cdf ascending within [0, 1] and closed by exactly 1.0
-    const int64_t n_param = 2 * static_cast<int64_t>(NE) * C.dim(), n_kde = C.kde ? model->kde_ptr[NE] : 0;
+    const int64_t n_param = 2 * static_cast<int64_t>(NE) * C.dim(), n_kde = C.kde ? model->kde_ptr[NE] : 0, n_mix = C.n_mix;
+    if (C.mix && (!model->mix_cdf || !model->mix_draw)) return fail(ctx, PS_ERR_ARG, "sampling a mixture state needs mix_cdf and mix_draw");
     if (tables->n_cdf != C.E || tables->n_param != n_param || tables->n_kde != n_kde)
         return fail(ctx, PS_ERR_ARG, "sampling tables of %lld / %lld / %lld entries, the model takes %d / %lld / %lld",
                     static_cast<long long>(tables->n_cdf), static_cast<long long>(tables->n_param), static_cast<long long>(tables->n_kde),
@@ -3370,6 +3421,11 @@ int ps_hmm_sample(ps_ctx *ctx, const ps_hmm_model *model, const ps_hmm_sample_ta
     for (int k = 0; C.kde && k < NE; ++k)
         if (!cdf_ok(tables->kde_cdf, model->kde_ptr[k], model->kde_ptr[k + 1]))
             return fail(ctx, PS_ERR_ARG, "kde_cdf of state %d: ascending from >= 0 with the last entry 1.0", k);
+    for (int k = 0; C.mix && k < NE; ++k)
+        if (!cdf_ok(model->mix_cdf, model->mix_ptr[k], model->mix_ptr[k + 1]))
+            return fail(ctx, PS_ERR_ARG, "mix_cdf of state %d: ascending from >= 0 with the last entry 1.0", k);
+    for (int64_t i = 0; i < 2 * n_mix; ++i)
+        if (!std::isfinite(model->mix_draw[i])) return fail(ctx, PS_ERR_ARG, "mix_draw %lld is not finite", static_cast<long long>(i));
     for (int64_t i = 0; i < n_param; ++i)
         if (!std::isfinite(tables->emit_param[i])) return fail(ctx, PS_ERR_ARG, "emit_param %lld is not finite", static_cast<long long>(i));
     if (n_seq == 0) return PS_OK;
@@ -3378,12 +3434,16 @@ int ps_hmm_sample(ps_ctx *ctx, const ps_hmm_model *model, const ps_hmm_sample_ta
     if (int rc = upload_tables(ctx, ctx->hmm_samp, {{tables->out_cdf, static_cast<size_t>(C.E) * sizeof(double)},
                                                     {tables->emit_param, static_cast<size_t>(n_param) * sizeof(double)},
                                                     {tables->kde_cdf, static_cast<size_t>(n_kde) * sizeof(double)},
+                                                    {C.mix ? model->mix_cdf : nullptr, static_cast<size_t>(n_mix) * sizeof(double)},
+                                                    {C.mix ? model->mix_draw : nullptr, 2 * static_cast<size_t>(n_mix) * sizeof(double)},
                                                     {h_off, nb}, {h_path_off, want_path ? nb : 0}})) return rc;
     HmmSampleDev T;
     T.out_cdf = ctx->hmm_samp.as<double>();
     T.emit_param = T.out_cdf + C.E;
     T.kde_cdf = T.emit_param + n_param;
-    const long long *d_off = reinterpret_cast<const long long *>(T.kde_cdf + n_kde);
+    C.DM.mix_cdf = T.kde_cdf + n_kde;
+    C.DM.mix_draw = C.DM.mix_cdf + n_mix;
+    const long long *d_off = reinterpret_cast<const long long *>(C.DM.mix_draw + 2 * n_mix);
     const long long *d_path_off = want_path ? d_off + n_seq + 1 : nullptr;
     const int rc = with_model(C, [&](const auto &M) -> int {
         using MD = std::decay_t<decltype(M)>;

@@ -29,6 +29,7 @@ constexpr int HMM_SILENT = 0, HMM_NORMAL = 1, HMM_UNIFORM = 2, HMM_KDE = 3;   //
 constexpr int HMM_VECTOR = 4;              // ... kind: a state of D components (a vector model)
 constexpr int HMM_LOGNORMAL = 5, HMM_EXPONENTIAL = 6;   // ps_hmm_model.comp_kind, beside HMM_NORMAL and HMM_UNIFORM
 constexpr int HMM_D_MAX = 16;              // components of a vector model's observation
+constexpr int HMM_MIXTURE = 7;             // ... kind: a weighted choice between component distributions (HmmDevM)
 
 struct HmmDev {                 // device pointers into one upload of the baked model (include/poreseg.h ps_hmm_model)
     const double *param;        // 3 per state: normal (mean, 1 / (2 std^2), -log(std sqrt(2 pi))), uniform (low, high, -log(high - low))
@@ -54,6 +55,19 @@ struct HmmDevV : HmmDev {
     const int *comp_kind;
     const double *comp_param, *comp_w;
     int D;
+};
+
+// A model with mixture states (kind 7), beside normal, uniform and kernel-density ones: state k's components are
+// [mix_ptr[k], mix_ptr[k+1]) of mix_kind (1, 2, 5, 6 as comp_kind), mix_param (3 per component, as comp_param) and mix_lw
+// (their log weights, the weights summing to 1; -inf: the component is skipped), and its param is (0, 0, 0).  A fourth set
+// of instantiations: the HmmDev, HmmDevK and HmmDevV code knows nothing of these tables.  The two sampling tables of
+// ps_hmm_model ride here as well (HmmSampleDev stays the struct the other instantiations were compiled with): they are set
+// by ps_hmm_sample alone, which uploads them per call, and are null in every other call.
+struct HmmDevM : HmmDevK {
+    const int *mix_ptr, *mix_kind;
+    const double *mix_param, *mix_lw;
+    const double *mix_cdf;      // per component: the running sum of the state's weights; 1.0 from the last positive weight on
+    const double *mix_draw;     // 2 per component, as HmmSampleDev.emit_param
 };
 
 // The observation as the kernels hand it to hmm_emit: doubles per observation, and observation t of the sequence that
@@ -143,6 +157,47 @@ __device__ __forceinline__ double hmm_emit(const HmmDevV &M, int k, const double
     return s;
 }
 
+// The log density of one mixture component of kind kd with its triple (a, b, c) at x: the formulas of the vector emission's
+// component switch above (include/poreseg.h comp_kind).  The vector emission keeps its own body: routed through this
+// function the HmmDevV kernels compile to other code than they did, and their E-step measured slower.
+__device__ __forceinline__ double hmm_comp_logp(int kd, double a, double b, double c, double x)
+{
+#pragma clang fp contract(off)
+    if (kd == HMM_NORMAL) {
+        const double u = x - a;
+        return c - (u * u) * b;
+    }
+    if (kd == HMM_UNIFORM) return (x >= a && x <= b) ? c : -__builtin_inf();
+    if (kd == HMM_LOGNORMAL) {
+        if (x > 0.0) {
+            const double y = log(x), u = y - a;
+            return (c - (u * u) * b) - y;
+        }
+        return -__builtin_inf();
+    }
+    return x >= 0.0 ? c - x * b : -__builtin_inf();
+}
+
+// Term i of a mixture state's density at x:  log w_i + l_i(x),  -inf for a component of weight 0 or one that excludes x.
+__device__ __forceinline__ double hmm_mix_term(const HmmDevM &M, int i, double x)
+{
+#pragma clang fp contract(off)
+    return M.mix_lw[i] + hmm_comp_logp(M.mix_kind[i], M.mix_param[3 * i], M.mix_param[3 * i + 1], M.mix_param[3 * i + 2], x);
+}
+
+// Mixture emission  log sum_i w_i p_i(x):  the lane that owns the state streams its components' terms through HmmLse in
+// ascending index, as the kernel-density loop does its points: -inf when no term is finite, never NaN, and one component
+// of weight 1 gives that component's own bits (0.0 + l = l, l + log1p(0) = l).  The other kinds take the HmmDevK code.
+__device__ __forceinline__ double hmm_emit(const HmmDevM &M, int k, double x)
+{
+#pragma clang fp contract(off)
+    if (M.kind[k] != HMM_MIXTURE) return hmm_emit(static_cast<const HmmDevK &>(M), k, x);
+    HmmLse acc;
+    const int i1 = M.mix_ptr[k + 1];
+    for (int i = M.mix_ptr[k]; i < i1; ++i) acc.add(hmm_mix_term(M, i, x));
+    return acc.get();
+}
+
 // What the E-step's statistics sum for component d of emitting state k: y - c, with y the observation (its logarithm for
 // a log-normal component) and c the component's shift (slot 0 of its parameters).  Called only where the state's posterior
 // is positive, so a log-normal component sees x > 0.
@@ -155,6 +210,32 @@ __device__ __forceinline__ double hmm_stat(const HmmDevV &M, int k, int d, const
     const int i = k * M.D + d;
     const double y = M.comp_kind[i] == HMM_LOGNORMAL ? log(x[d]) : x[d];
     return y - M.comp_param[3 * i];
+}
+
+// The E-step's rows of a mixture state's components (rows: one (W_i, A_i, B_i) per component in table order, behind the
+// states' rows): state k's posterior g > 0 at observation x is shared out by the responsibilities  r_i = exp(v_i - e)  of
+// the terms v_i > -inf, e = the state's emission (finite here), and component i sums  w = g r_i,  w d  and  (w d) d  with
+// d = y - mix_param[3 i],  y = log x  for a log-normal component (its term is finite only for x > 0).  The rows belong to
+// the lane that owns the state.  Models without mixture states have no such rows.
+template <typename MD, typename X> __device__ __forceinline__ void hmm_mix_stat(const MD &, int, X, double, double *) {}
+__device__ __forceinline__ void hmm_mix_stat(const HmmDevM &M, int k, double x, double g, double *rows)
+{
+#pragma clang fp contract(off)
+    if (M.kind[k] != HMM_MIXTURE) return;
+    const double e = hmm_emit(M, k, x);
+    const int i1 = M.mix_ptr[k + 1];
+    for (int i = M.mix_ptr[k]; i < i1; ++i) {
+        const double v = hmm_mix_term(M, i, x);
+        if (!(v > -__builtin_inf())) continue;
+        const double w = g * exp(v - e);
+        const double y = M.mix_kind[i] == HMM_LOGNORMAL ? log(x) : x;
+        const double d = y - M.mix_param[3 * i];
+        const double wd = w * d;
+        double *s = rows + 3 * i;
+        s[0] += w;
+        s[1] += wd;
+        s[2] += wd * d;
+    }
 }
 
 // Viterbi / forward over one sequence per workgroup.  Rows of sequence q: mat (optional, row off[q] + q - mat_row0) and bp
@@ -362,9 +443,9 @@ __global__ __launch_bounds__(HMM_NT) void hmm_bwd_kernel(MD M, const double *obs
 // that edge, and an emitting state k adds its posterior exp(f[t][k] + b[t][k] - logp[q]) to (W, A, B) with the observation
 // x[t-1] shifted by c_k = param[3k]; a vector model's state adds it to W once and to (A_d, B_d) per component (hmm_stat).
 //
-// Accumulators: one row of n_acc = E + (1 + 2 D) NE + 1 doubles per workgroup (edge counts in out-edge order, W and
-// (A_d, B_d) for d < D per emitting state -- D = 1, so (W, A, B), unless the model is a vector model --, the number of
-// sequences skipped for logp = -inf).  Workgroup g takes the sequences q = g (mod gridDim.x)
+// Accumulators: one row of n_acc = E + (1 + 2 D) NE + 3 n_mix + 1 doubles per workgroup (edge counts in out-edge order, W
+// and (A_d, B_d) for d < D per emitting state -- D = 1, so (W, A, B), unless the model is a vector model --, one (W, A, B)
+// per mixture component of a model with mixture states (hmm_mix_stat), the number of sequences skipped for logp = -inf).  Workgroup g takes the sequences q = g (mod gridDim.x)
 // of [q0, q1), in ascending order, so its row sums the same sequences in the same order however the batch is cut into
 // launches.  An edge belongs to the lane that owns its source state (and a state's statistics to the lane that owns the
 // state) in every step, so a row needs no atomics.  ACC_LDS: the row is loaded into LDS next to the two score rows and
@@ -416,6 +497,7 @@ __global__ __launch_bounds__(HMM_NT) void hmm_expect_kernel(MD M, const double *
                         s[1 + 2 * c] += gd;
                         s[2 + 2 * c] += gd * d;
                     }
+                    hmm_mix_stat(M, k, xt, g, st + (1 + 2 * D) * M.n_emit);
                 }
             },
             [](int, const double *) {});
@@ -579,7 +661,7 @@ __global__ __launch_bounds__(HMM_NT) void hmm_trace_kernel(HmmDev M, const long 
 // The random stream is counter-based, Philox4x32-10 with key (seed low, seed high): sequence Q = first + q owns the blocks
 // j = 0, 1, 2, ... at counter (j low, j high, Q low, Q high); a block of four words gives two doubles in [0, 1) and the
 // walk consumes blocks strictly in walk order (one per transition, one per component of an emission, two for a
-// kernel-density state), so a walk's path and length depend on (seed, Q, out_cdf) alone, never on the values drawn.
+// kernel-density or a mixture state), so a walk's path and length depend on (seed, Q, out_cdf) alone, never on the values drawn.
 
 struct HmmSampleDev {           // device copies of ps_hmm_sample_tables (include/poreseg.h)
     const double *out_cdf;      // per out-edge: the running sum of the state's edge probabilities, its last entry 1.0
@@ -655,6 +737,15 @@ __device__ __forceinline__ void hmm_sample_emit(const HmmDevK &M, const HmmSampl
     if (M.kind[k] != HMM_KDE) return hmm_sample_emit(static_cast<const HmmDev &>(M), T, k, seed, Q, j, x);
     const int i = hmm_cdf_pick(T.kde_cdf, M.kde_ptr[k], M.kde_ptr[k + 1], HmmPhilox(seed, Q, j++).u0());
     const double v = M.kde_pt[i] + T.emit_param[2 * k + 1] * HmmPhilox(seed, Q, j++).normal();
+    if (x) *x = v;
+}
+// a mixture state takes two blocks: the first component i with u0 < mix_cdf[i] (never one of weight 0), then its draw
+__device__ __forceinline__ void hmm_sample_emit(const HmmDevM &M, const HmmSampleDev &T, int k, unsigned long long seed,
+                                                unsigned long long Q, unsigned long long &j, double *x)
+{
+    if (M.kind[k] != HMM_MIXTURE) return hmm_sample_emit(static_cast<const HmmDevK &>(M), T, k, seed, Q, j, x);
+    const int i = hmm_cdf_pick(M.mix_cdf, M.mix_ptr[k], M.mix_ptr[k + 1], HmmPhilox(seed, Q, j++).u0());
+    const double v = hmm_draw(M.mix_kind[i], M.mix_draw[2 * i], M.mix_draw[2 * i + 1], HmmPhilox(seed, Q, j++));
     if (x) *x = v;
 }
 __device__ __forceinline__ void hmm_sample_emit(const HmmDevV &M, const HmmSampleDev &T, int k, unsigned long long seed,

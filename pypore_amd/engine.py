@@ -569,25 +569,27 @@ class Context(object):
         return logp[:n_seq], mat, (path, path_off, path_len[:n_seq])
 
     @_serialised
-    def hmm_expect(self, model, obs, off, stat_width=3):
+    def hmm_expect(self, model, obs, off, stat_width=3, mix_rows=0):
         """ps_hmm_expect: the Baum-Welch E-step over a batch.  model: a _lib.HmmModel (its arrays kept alive by the caller);
         obs: float64 CUDA tensor, sequence q = obs[off[q]:off[q+1]].  Returns (logp float64 [n_seq], edge counts float64
         [n_edges] in out-edge order, statistics float64 [n_emit, stat_width], the number of sequences skipped for
         logp = -inf).  stat_width: the doubles per emitting state the library writes -- 3, (W, A, B), or 1 + 2 n_dim for a
         vector model (kind 4), whose obs holds n_dim doubles per observation; the caller, who built the model, says which
-        (pypore_amd.hmm.Model._stat_width)."""
+        (pypore_amd.hmm.Model._stat_width).  mix_rows: the mixture components of a model with kind-7 states (mix_ptr[n_emit]):
+        the statistics are then [n_emit + mix_rows, 3], the states' rows followed by one row per component."""
         off, off_p = _offsets(off)
         n_seq = off.size - 1
         dev = _f64_device(obs)
         n_edges = int(ctypes.cast(model.out_ptr, ctypes.POINTER(ctypes.c_int32))[model.n_states])
         logp = torch.empty(max(n_seq, 1), dtype=torch.float64, device=dev)
         counts = torch.empty(max(n_edges, 1), dtype=torch.float64, device=dev)
-        stats = torch.empty((max(model.n_emit, 1), int(stat_width)), dtype=torch.float64, device=dev)
+        rows = model.n_emit + int(mix_rows)
+        stats = torch.empty((max(rows, 1), int(stat_width)), dtype=torch.float64, device=dev)
         skipped = ctypes.c_int32(0)
         torch.cuda.current_stream(dev).synchronize()
         _lib.check(self.L.ps_hmm_expect(self.handle, ctypes.byref(model), _ptr(obs), off_p, n_seq, _ptr(logp), _ptr(counts),
                                         _ptr(stats), ctypes.byref(skipped)), self.handle)
-        return logp[:n_seq], counts[:n_edges], stats[:model.n_emit], int(skipped.value)
+        return logp[:n_seq], counts[:n_edges], stats[:rows], int(skipped.value)
 
     @_serialised
     def hmm_posterior(self, model, obs, off, want_post=False, want_map=True, want_counts=False):

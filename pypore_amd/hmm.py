@@ -1,5 +1,6 @@
 """Hidden Markov models with the surface the reference's HMM code uses (yahmm: Model, State, NormalDistribution,
-UniformDistribution, GaussianKernelDensity, MultivariateDistribution, LogNormalDistribution, ExponentialDistribution;
+UniformDistribution, GaussianKernelDensity, MultivariateDistribution, LogNormalDistribution, ExponentialDistribution,
+MixtureDistribution;
 add_state(s), add_transition, add_model, bake; viterbi, forward, backward,
 log_probability, forward_backward, maximum_a_posteriori) and the reference's profile HMM builders (HMMBoard, the three
 board modules, ModularProfileModel, Phi29ProfileHMM, Hel308ProfileHMM: the end of this module), decoded on the MI355X
@@ -35,6 +36,25 @@ others' exp, the form the recursions use -- so an observation far from every poi
 instead of log(0).  With one point it is NormalDistribution(p, h).  On the device the lane that owns the state walks its
 points (csrc/seg_hmm.hpp hmm_emit); the flat form holds them as CSR tables kde_ptr / kde_pt / kde_lw.
 
+Mixture states.  MixtureDistribution(distributions, weights) is one state whose level is a weighted choice between J >= 1
+univariate components -- Normal, Uniform, LogNormal or ExponentialDistribution -- with weights w_j, finite and >= 0 with a
+sum > 0 (default: equal), normalised to sum to 1 as a kernel density's are.  Its log density is
+    e(x) = log sum_j w_j p_j(x),
+taken as a log-sum-exp in ascending j over the terms  log w_j + l_j(x)  that are > -inf -- the largest term so far plus
+log1p of the others' exp, the form the recursions use (csrc/seg_hmm.hpp HmmLse) --, with l_j the component's own log
+density above and below: -inf when no term is finite, never NaN, and one component of weight 1 gives that component's own
+bits (log 1 = 0.0, 0.0 + l = l, l + log1p(0) = l).  A component of weight 0 keeps its slot -- component index equals table
+index, always -- with log weight -inf, and is skipped.  responsibilities(x) are  exp((log w_j + l_j(x)) - e(x)),  0 for a
+skipped term and all 0 where e(x) = -inf.  Mixture states stand in scalar models only: n_dim = 1, beside normal, uniform,
+kernel-density and other mixture states; a mixture state in a vector model is a ValueError at bake() that names the state.
+A log-normal or exponential COMPONENT of a mixture does not make the model a vector model: the mixture evaluates it
+itself.  In `flat` a mixture state has kind 7 and param (0, 0, 0); `flat` gains no key.  The components live beside it in
+Model._mix, built by bake() and again after every M-step: mix_ptr (int32, n_emit + 1: a CSR index, a kind-7 state has >= 1
+entries and every other state none), mix_kind, mix_param (the component's compiled triple), mix_lw (log weights) and the
+two sampling tables mix_cdf and mix_draw (Sampling, below); all empty for a model without mixture states, whose flat form,
+upload, kernels and bits are what they were.  On the device the lane that owns the state walks its components
+(csrc/seg_hmm.hpp HmmDevM, a fourth set of kernel instantiations, taken only when some state is kind 7).
+
 Vector models (observations of more than one number: the reference's tutorial decodes
 `[(s.mean, s.std, s.duration) for s in event.segments]`).  MultivariateDistribution(distributions, weights) is D >= 1
 independent univariate components -- Normal, Uniform, LogNormal or ExponentialDistribution -- with weights w_d, finite and
@@ -61,6 +81,10 @@ Deviations from yahmm, by design:
     textbook densities above.  Nothing about its arithmetic or its training of these classes is assumed.
   * a GaussianKernelDensity cannot be a component, nor stand in a vector model (ValueError; the point loop inside the
     component loop is not built), and a MultivariateDistribution cannot be nested (ValueError).
+  * what is assumed of yahmm's MixtureDistribution is the constructor (distributions, weights) and `parameters =
+    [distributions, weights]`.  The mixture arithmetic -- the order of the log-sum-exp, the responsibilities, the M-step
+    below -- is this package's own; nothing about yahmm's is assumed.  A kernel density, a multivariate or another mixture
+    cannot be a component, and a mixture cannot be a component of a MultivariateDistribution (ValueError).
   * GaussianKernelDensity is normalised: it carries the 1/h factor above.  yahmm is not available to compare against; as
     far as is known its kernel density leaves 1/h out, which is the same density at bandwidth 1, the default and what
     every caller in the reference's alignment.py uses.  Nothing else about its arithmetic is assumed.
@@ -123,6 +147,16 @@ the (W, A, B) layout at D = 1.  The M-step updates COMPONENT distributions, pool
 states and the component slots that hold it: a normal as above from (W, A_d, B_d); a log-normal by the same formulas on
 log x, giving mu and sigma, with min_std the floor of sigma; an exponential  rate = W / A  (left as it is when A <= 0);
 uniform components are untouched, and a frozen MultivariateDistribution freezes all its components.
+In a model with mixture states `stats` is [n_emit + n_mix, 3]: the states' rows -- a mixture state's shift is 0, its row the
+raw moments --, then one row per mixture component in the order of Model._mix.  Where mixture state k has posterior g for
+observation x, component i with a term  v_i = log w_i + l_i(x) > -inf  has the responsibility  r = exp(v_i - e_k(x))  and
+adds  W_i += g r,  A_i += g r d,  B_i += (g r d) d  with  d = y - c_i,  y = log x for a log-normal component and x
+otherwise, c_i the component's shift as above.  In the M-step the components of a mixture join the pooling per distribution
+object -- over plain states and mixture slots alike -- and take the formulas above from their own rows; a mixture's weights
+are pooled per mixture object over the states that hold it:  w_j = W_j / sum_j W_j  when that sum is > 0, otherwise kept,
+then mixed with the old weight by distribution_inertia.  A weight that becomes 0 keeps its slot (log weight -inf).  A
+frozen mixture changes neither its weights nor, in its slots, its components.  Viterbi training gives each observation
+weight 1 in its state and shares it out over the state's components by responsibilities(x), computed on the host.
 The structure stays: `states`, their order and `edges` do not change, an edge
 whose probability becomes 0 keeps its place (log -inf on the device), and the trained probabilities are written back to
 the transitions, so a later bake() starts from them (and drops the zero edges, as always).  algorithm='viterbi' counts
@@ -146,7 +180,11 @@ Q >> 32), a block r0..r3 gives u0 = ((r0 >> 5) 2^26 + (r1 >> 6)) 2^-53 and u1 li
 order: one per transition -- the first out-edge e of the state with u0 < out_cdf[e] --, one per component of an emission in
 ascending d, with z = sqrt(-2 log(1 - u0)) cos(2 pi u1): normal mean + std z, uniform low + u0 (high - low), log-normal
 exp(mu + sigma z), exponential -log(1 - u0) / rate; a kernel-density state takes two: the first point i with u0 < kde_cdf[i],
-then p_i + h z from the next block.  The tables are built on the host in float64 (Model._sample_tables, not part of `flat`):
+then p_i + h z from the next block; a mixture state takes two as well: the first component i of the state with
+u0 < mix_cdf[i], then that component's draw by its kind from the next block.  mix_cdf (Model._mix, aligned with mix_lw) is
+per mixture state the running sum of the weights, added one by one, with the entry of the state's last component of positive
+weight and every entry after it stored as exactly 1.0, so a component of weight 0 is never picked; mix_draw holds two
+doubles per component by emit_param's rule, and emit_param (0, 0) for a mixture state.  The tables are built on the host in float64 (Model._sample_tables, not part of `flat`):
 out_cdf, per state the running sum of np.exp(out_lp) in out-edge order, added one by one, the last entry stored as exactly
 1.0; kde_cdf the same over exp(kde_lw); emit_param, two doubles per emitting state or component: normal (mean, std), uniform
 (low, high - low), log-normal (mu, sigma), exponential (0, rate), kernel density (0, bandwidth).  So a walk's path and
@@ -175,6 +213,7 @@ KIND_SILENT, KIND_NORMAL, KIND_UNIFORM, KIND_KDE = 0, 1, 2, 3     # include/pore
 KIND_VECTOR = 4                                       # ... kind: a state of n_dim components (a vector model)
 KIND_LOGNORMAL, KIND_EXPONENTIAL = 5, 6               # ps_hmm_model.comp_kind, beside KIND_NORMAL and KIND_UNIFORM
 COMPONENT_KINDS = (KIND_NORMAL, KIND_UNIFORM, KIND_LOGNORMAL, KIND_EXPONENTIAL)
+KIND_MIXTURE = 7                                      # ... kind: a weighted choice between components (scalar models)
 MAX_STATES = 4096                                     # csrc/seg_hmm.hpp HMM_S_MAX
 MAX_DIM = 16                                          # csrc/seg_hmm.hpp HMM_D_MAX
 
@@ -386,6 +425,9 @@ class MultivariateDistribution(Distribution):
                 raise ValueError("a MultivariateDistribution cannot be a component of another")
             if isinstance(d, GaussianKernelDensity):
                 raise ValueError("a GaussianKernelDensity cannot be a component of a MultivariateDistribution")
+            if isinstance(d, MixtureDistribution):
+                raise ValueError("a MixtureDistribution cannot be a component of a MultivariateDistribution: mixture "
+                                 "states stand in scalar models only")
             if not isinstance(d, Distribution) or d.kind not in COMPONENT_KINDS:
                 raise ValueError("a component must be a Normal, Uniform, LogNormal or ExponentialDistribution, got %r"
                                  % (d,))
@@ -417,6 +459,87 @@ class MultivariateDistribution(Distribution):
         return [d.sample(rng) for d in self.parameters[0]]
 
 
+class MixtureDistribution(Distribution):
+    """One state whose level is a weighted choice between J >= 1 univariate components (NormalDistribution,
+    UniformDistribution, LogNormalDistribution or ExponentialDistribution) with `weights` w_j, finite and >= 0 with a sum
+    > 0 (default: equal), normalised to sum to 1: log density  log sum_j w_j p_j(x)  (module docstring).  parameters =
+    [distributions, weights].  A component of weight 0 keeps its slot -- component index equals table index -- and is
+    skipped.  A GaussianKernelDensity, MultivariateDistribution or MixtureDistribution as a component raises ValueError.
+    Scalar models only.  freeze() freezes the weights and, in this slot, every component; Model.train fits both."""
+    kind = KIND_MIXTURE
+
+    def __init__(self, distributions, weights=None):
+        distributions = list(distributions)
+        if not distributions:
+            raise ValueError("MixtureDistribution needs at least one component")
+        for d in distributions:
+            if isinstance(d, MixtureDistribution):
+                raise ValueError("a MixtureDistribution cannot be a component of another")
+            if isinstance(d, (GaussianKernelDensity, MultivariateDistribution)):
+                raise ValueError("a %s cannot be a component of a MixtureDistribution" % type(d).__name__)
+            if not isinstance(d, Distribution) or d.kind not in COMPONENT_KINDS:
+                raise ValueError("a component must be a Normal, Uniform, LogNormal or ExponentialDistribution, got %r"
+                                 % (d,))
+        if weights is None:
+            weights = [1.0] * len(distributions)
+        weights = [float(w) for w in np.asarray(weights, dtype=np.float64).reshape(-1)]
+        if len(weights) != len(distributions):
+            raise ValueError("MixtureDistribution got %d weights for %d components" % (len(weights), len(distributions)))
+        if not all(math.isfinite(w) and w >= 0 for w in weights):
+            raise ValueError("MixtureDistribution needs finite weights >= 0")
+        total = math.fsum(weights)
+        if not total > 0:
+            raise ValueError("MixtureDistribution needs some weight > 0")
+        Distribution.__init__(self, [distributions, [w / total for w in weights]])
+
+    def log_weights(self):
+        """log w_j per component, -inf for a weight of 0: the table mix_lw."""
+        return [math.log(w) if w > 0 else NEG_INF for w in self.parameters[1]]
+
+    def _terms(self, x):
+        """log w_j + l_j(x) per component; -inf for a component of weight 0, whatever its density."""
+        return [lw + d.log_probability(x) if lw > NEG_INF else NEG_INF
+                for d, lw in zip(self.parameters[0], self.log_weights())]
+
+    def log_probability(self, x):
+        m, r = NEG_INF, 0.0                     # the device's HmmLse: m the largest term so far, r the others' sum
+        for v in self._terms(x):
+            if not v > NEG_INF:
+                continue
+            if v > m:
+                r = (r + 1.0) * math.exp(m - v)
+                m = v
+            else:
+                r += math.exp(v - m)
+        if not m > NEG_INF:
+            return NEG_INF
+        return m + math.log1p(r)
+
+    def responsibilities(self, x):
+        """exp((log w_j + l_j(x)) - log_probability(x)) per component, 0 for a skipped term; all 0 where the density is
+        -inf.  What Viterbi training shares an observation out by."""
+        e = self.log_probability(x)
+        if not e > NEG_INF:
+            return [0.0] * len(self.parameters[0])
+        return [math.exp(v - e) if v > NEG_INF else 0.0 for v in self._terms(x)]
+
+    def sample(self, rng=None):
+        """A component chosen by its weight, then that component's draw."""
+        distributions, weights = self.parameters
+        rng = _rng(rng)
+        return distributions[int(rng.choice(len(distributions), p=np.asarray(weights) / math.fsum(weights)))].sample(rng)
+
+    def compiled(self):
+        return 0.0, 0.0, 0.0                    # (the state's triple is not read: the components' live in Model._mix)
+
+
+def _mixture_slots(distribution):
+    """[(component distribution, weight, frozen)] of a mixture state's distribution, [] for any other."""
+    if distribution.kind != KIND_MIXTURE:
+        return []
+    return [(d, w, d.frozen or distribution.frozen) for d, w in zip(*distribution.parameters)]
+
+
 def _components(distribution):
     """[(component distribution, weight, frozen)] of an emitting state's distribution: its own components, or itself."""
     if distribution.kind == KIND_VECTOR:
@@ -433,6 +556,8 @@ def _sample_param(d):
         return 0.0, a[0]
     if d.kind == KIND_KDE:
         return 0.0, a[1]
+    if d.kind == KIND_MIXTURE:
+        return 0.0, 0.0                                   # (its components' pairs are Model._mix["mix_draw"])
     return a[0], a[1]                                     # normal (mean, std), log-normal (mu, sigma)
 
 
@@ -466,7 +591,8 @@ class Model(object):
         self.states = None                                 # after bake()
         self.n_dim = None                                  # after bake(): values per observation
         self._flat = None
-        self._c = None                                     # the ctypes view of _flat, made on first use
+        self._mix = None                                   # after bake(): the mixture states' tables (_mixture_tables)
+        self._c = None                                     # the ctypes view of _flat and _mix, made on first use
         self._s = None                                     # the sampling tables (_sample_tables), made on first use
         self.add_state(self.start)
         self.add_state(self.end)
@@ -590,6 +716,7 @@ class Model(object):
             in_src=np.ascontiguousarray(src[by_dst]), in_lp=np.ascontiguousarray(lp[by_dst]),
             out_ptr=np.concatenate(([0], np.cumsum(np.bincount(src, minlength=S)))).astype(np.int32),
             out_dst=np.ascontiguousarray(dst[by_src]), out_lp=np.ascontiguousarray(lp[by_src]), **kde)
+        self._mix = self._mixture_tables(emitting)
         self._in_order = by_dst                         # edges (= out-edge order) -> in-edge order
         self._c = self._s = None
 
@@ -645,6 +772,10 @@ class Model(object):
         if vector and dims[0] > MAX_DIM:
             raise ValueError("model %r has %d components per state: the device HMM kernels take at most %d"
                              % (self.name, dims[0], MAX_DIM))
+        for s in emitting:
+            if vector and s.distribution.kind == KIND_MIXTURE:
+                raise ValueError("model %r: mixture state %r cannot stand in a vector model (one with a Multivariate, "
+                                 "LogNormal or ExponentialDistribution state)" % (self.name, s.name))
         if vector and any(s.distribution.kind == KIND_KDE for s in emitting):
             raise ValueError("model %r: a kernel-density state cannot stand in a vector model (one with a Multivariate, "
                              "LogNormal or ExponentialDistribution state)" % self.name)
@@ -675,6 +806,38 @@ class Model(object):
                            kde_lw=np.array(lws, np.float64).reshape(-1), comp_kind=np.array(ckind, np.int32).reshape(-1),
                            comp_param=np.array(cparam, np.float64).reshape(-1), comp_w=np.array(cw, np.float64).reshape(-1))
 
+    @staticmethod
+    def _mixture_tables(emitting):
+        """The tables of the mixture states (kind 7), kept beside `flat` (include/poreseg.h ps_hmm_model mix_*): mix_ptr
+        [n_emit + 1], a CSR index into the others (a kind-7 state has >= 1 entries, every other state none); per component
+        mix_kind, mix_param (its compiled() triple), mix_lw (log weight, -inf for weight 0) and the two sampling tables:
+        mix_cdf, per state the running sum of the weights, added one by one, with the entry of the state's last component
+        of positive weight and every entry after it stored as exactly 1.0, and mix_draw, the _sample_param pair.  All
+        empty (mix_ptr all 0) without mixture states."""
+        ptr, kinds, params, lws, cdf, draw = [0], [], [], [], [], []
+        for s in emitting:
+            slots = _mixture_slots(s.distribution)
+            if slots:
+                lws.extend(s.distribution.log_weights())
+                last = max(j for j, (_, w, _) in enumerate(slots) if w > 0)
+                run = 0.0
+                for j, (d, w, _) in enumerate(slots):
+                    kinds.append(d.kind)
+                    params.extend(d.compiled())
+                    draw.extend(_sample_param(d))
+                    run = run + w
+                    cdf.append(1.0 if j >= last else run)
+            ptr.append(len(kinds))
+        return dict(mix_ptr=np.array(ptr, np.int32), mix_kind=np.array(kinds, np.int32).reshape(-1),
+                    mix_param=np.array(params, np.float64).reshape(-1), mix_lw=np.array(lws, np.float64).reshape(-1),
+                    mix_cdf=np.array(cdf, np.float64).reshape(-1), mix_draw=np.array(draw, np.float64).reshape(-1))
+
+    @property
+    def _n_mix(self):
+        """Mixture components of the baked model: the rows `stats` holds behind the states'."""
+        self.flat
+        return int(self._mix["mix_kind"].size)
+
     @property
     def _vector(self):
         """The baked model is a vector model: its emitting states are kind 4 and read the component tables."""
@@ -703,6 +866,9 @@ class Model(object):
             if f["comp_kind"].size:                             # (read by the library only when some kind is 4)
                 for k in ("comp_kind", "comp_param", "comp_w"):
                     setattr(m, k, f[k].ctypes.data)
+            if self._mix["mix_kind"].size:                      # (read by the library only when some kind is 7)
+                for k, a in self._mix.items():
+                    setattr(m, k, a.ctypes.data)
             self._c = m
         return self._c
 
@@ -926,11 +1092,12 @@ class Model(object):
     def expected_counts_batch(self, sequences, device=None):
         """The Baum-Welch E-step on the device (ps_hmm_expect), summed over the sequences: Expectations(counts: float64
         per edge, aligned with `edges`; stats: float64 [n_emit, 3], (W, A, B) per emitting state -- for a vector model
-        [n_emit, 1 + 2 n_dim]: W, then (A_d, B_d) per component (module docstring);
+        [n_emit, 1 + 2 n_dim]: W, then (A_d, B_d) per component; for a model with mixture states [n_emit + n_mix, 3]: the
+        states' rows, then one (W, A, B) per mixture component in the order of _mix (module docstring);
         logp: float64 per sequence; skipped: the number of sequences with logp = -inf)."""
         ctx, off, obs = self._upload(sequences, device)
         width = self._stat_width
-        logp, counts, stats, skipped = ctx.hmm_expect(self._c_model(), obs, off, width)
+        logp, counts, stats, skipped = ctx.hmm_expect(self._c_model(), obs, off, width, mix_rows=self._n_mix)
         return Expectations(counts.cpu().numpy(), stats.cpu().numpy().reshape(-1, width), logp.cpu().numpy(), skipped)
 
     @property
@@ -946,8 +1113,9 @@ class Model(object):
         dst = np.array([e[1] for e in self.edges], np.int64)
         keys = src * S + dst                             # ascending: edges are sorted by (from, to)
         counts = np.zeros(len(self.edges))
-        stats = np.zeros((NE, self._stat_width))
+        stats = np.zeros((NE + self._n_mix, self._stat_width))
         vector, D = self._vector, f["n_dim"]
+        mixed = [k for k in range(NE) if f["kind"][k] == KIND_MIXTURE]
         if vector:                                       # per component: its shift, and whether it counts log x
             shift = f["comp_param"][0::3].reshape(NE, D)
             logs = f["comp_kind"].reshape(NE, D) == KIND_LOGNORMAL
@@ -978,6 +1146,15 @@ class Model(object):
             d = x - shift[em]
             np.add.at(stats[:, 1], em, d)
             np.add.at(stats[:, 2], em, d * d)
+            for k in mixed:                              # the component rows: each observation shared out on the host
+                i0, dist = int(self._mix["mix_ptr"][k]), self.states[k].distribution
+                for xv in x[em == k].tolist():
+                    for j, r in enumerate(dist.responsibilities(xv)):
+                        if r > 0:
+                            i = i0 + j
+                            y = math.log(xv) if self._mix["mix_kind"][i] == KIND_LOGNORMAL else xv
+                            dv = y - float(self._mix["mix_param"][3 * i])
+                            stats[NE + i] += (r, r * dv, (r * dv) * dv)
         return Expectations(counts, stats, logp, skipped)
 
     def _estep(self, sequences, algorithm, want_stats, device):
@@ -999,10 +1176,12 @@ class Model(object):
         counts = np.asarray(counts, np.float64).reshape(-1)
         width = self._stat_width
         stats = np.asarray(stats, np.float64)
-        if counts.size != len(self.edges) or stats.size != NE * width:
+        n_mix = self._n_mix
+        if counts.size != len(self.edges) or stats.size != (NE + n_mix) * width:
             raise ValueError("statistics for %d edges and %d values of the emitting states, the model has %d edges and "
-                             "%d emitting states of %d values each" % (counts.size, stats.size, len(self.edges), NE, width))
-        stats = stats.reshape(NE, width)
+                             "%d emitting states and mixture components of %d values each"
+                             % (counts.size, stats.size, len(self.edges), NE + n_mix, width))
+        stats = stats.reshape(NE + n_mix, width)
         src = np.array([e[0] for e in self.edges], np.int64)
         old = np.array([e[2] for e in self.edges], np.float64)
         c = counts + float(transition_pseudocount)
@@ -1021,13 +1200,34 @@ class Model(object):
         # slots that hold it (uniform and kernel-density distributions stay as they are)
         vector, D = self._vector, f["n_dim"]
         pooled = collections.OrderedDict()
+        weights = collections.OrderedDict()              # per mixture object: [mixture, W_j pooled over its states]
         for k in range(NE):
-            for c, (d, _, frozen) in enumerate(_components(self.states[k].distribution)):
+            dist = self.states[k].distribution
+            if dist.kind == KIND_MIXTURE:                # its slots' rows stand behind the states', in table order
+                i0 = int(self._mix["mix_ptr"][k])
+                rows = stats[NE + i0:NE + i0 + len(dist.parameters[0])]
+                if not dist.frozen:
+                    acc = weights.setdefault(id(dist), [dist, np.zeros(len(rows))])
+                    acc[1] = acc[1] + rows[:, 0]
+                for j, (d, _, frozen) in enumerate(_mixture_slots(dist)):
+                    if d.kind not in (KIND_NORMAL, KIND_LOGNORMAL, KIND_EXPONENTIAL) or frozen:
+                        continue
+                    acc = pooled.setdefault(id(d), [d, self._mix["mix_param"][3 * (i0 + j)], 0.0, 0.0, 0.0])
+                    acc[2:] = [acc[2] + rows[j, 0], acc[3] + rows[j, 1], acc[4] + rows[j, 2]]
+                continue
+            for c, (d, _, frozen) in enumerate(_components(dist)):
                 if d.kind not in (KIND_NORMAL, KIND_LOGNORMAL, KIND_EXPONENTIAL) or frozen:
                     continue
                 shift = f["comp_param"][3 * (k * D + c)] if vector else f["param"][3 * k]
                 acc = pooled.setdefault(id(d), [d, shift, 0.0, 0.0, 0.0])
                 acc[2:] = [acc[2] + stats[k, 0], acc[3] + stats[k, 1 + 2 * c], acc[4] + stats[k, 2 + 2 * c]]
+        for dist, W in weights.values():                 # w_j = W_j / sum W, mixed with the old weight; a weight of 0 stays
+            total = 0.0                                  # in its slot (log weight -inf)
+            for w in W.tolist():
+                total = total + w
+            if total > 0:
+                dist.parameters[1] = [min(distribution_inertia * old + (1.0 - distribution_inertia) * (w / total), 1.0)
+                                      for old, w in zip(dist.parameters[1], W.tolist())]
         for d, shift, W, A, B in pooled.values():
             if not W > 0:
                 continue
@@ -1054,6 +1254,7 @@ class Model(object):
                                                    f["n_dim"] if self._vector else 0)
         f.update(tables)
         self._flat = f
+        self._mix = self._mixture_tables(self.states[:f["n_emit"]])
         self._c = self._s = None
 
     def train(self, sequences, stop_threshold=1e-9, min_iterations=0, max_iterations=None, algorithm='baum-welch',
