@@ -489,11 +489,18 @@ int ps_hmm_posterior(ps_ctx *ctx, const ps_hmm_model *model, const double *d_obs
 /* What sampling reads beside the model (pypore_amd.hmm.Model._sample_tables), host arrays built in fp64 from the
  * distributions themselves, so that no decision of a walk depends on a device logarithm or exponential:
  *   out_cdf    n_cdf = out_ptr[n_states] doubles, aligned with out_dst: per state the running sum of its out-edges'
- *              probabilities, added one by one (>= 0 and ascending), the state's last entry stored as exactly 1.0;
+ *              probabilities, added one by one (>= 0 and ascending); the entry of the state's last out-edge of positive
+ *              probability and every entry after it is exactly 1.0, so an edge of probability 0 is never taken;
  *   emit_param n_param = 2 n_emit doubles (2 n_emit n_dim for a vector model, component k n_dim + d): normal (mean, std),
  *              uniform (low, high - low), log-normal (mu, sigma), exponential (0, rate), kernel density (0, bandwidth);
  *   kde_cdf    n_kde = kde_ptr[n_emit] doubles, aligned with kde_pt: per kernel-density state the running sum of its
- *              points' weights, the state's last entry exactly 1.0 (NULL and 0 without kind-3 states).
+ *              points' weights, exactly 1.0 from the state's last point of positive weight on (NULL and 0 without kind-3
+ *              states).
+ * Every row of the three cdf tables is checked against the model (PS_ERR_ARG, the message names the table and the state): its
+ * entries are finite and >= 0, none below its predecessor -- but a running sum that rounding carried past 1.0 may be followed
+ * by the entries stored as 1.0 --, the last is exactly 1.0, and an entry above its predecessor (the first: above 0) is one
+ * whose log probability in the model (out_lp, kde_lw, mix_lw) is > -inf: a row that gives an interval of u to an entry the
+ * model calls impossible is refused.  An entry equal to its predecessor is never picked.
  * The weights comp_w of a vector model are not read: a weight scales a log density and defines nothing to draw from.
  * A model with mixture states (kind 7) brings two more tables in ps_hmm_model itself (this struct keeps its size; without
  * them ps_hmm_sample returns PS_ERR_ARG); emit_param still holds 2 doubles per emitting state, (0, 0) for a mixture state:

@@ -3405,25 +3405,31 @@ int ps_hmm_sample(ps_ctx *ctx, const ps_hmm_model *model, const ps_hmm_sample_ta
                     C.E, static_cast<long long>(n_param), static_cast<long long>(n_kde));
     if ((C.E > 0 && !tables->out_cdf) || (n_param > 0 && !tables->emit_param) || (n_kde > 0 && !tables->kde_cdf))
         return fail(ctx, PS_ERR_ARG, "null sampling table");
-    auto cdf_ok = [](const double *cdf, int lo, int hi) {
+    // One row [lo, hi) of a cdf table beside the model's log probabilities lp of its entries.  A rounded running sum may pass
+    // 1.0 by an ulp, and the entries stored as 1.0 behind it then step back onto 1.0: both are above every u the kernel
+    // draws, so the bisection still finds the linear scan's entry.  An entry above its predecessor (the first: above 0)
+    // owns an interval of u; where the model says -inf the row gives mass to an impossible entry.
+    auto cdf_row = [&](const char *what, const double *cdf, const double *lp, const int32_t *ptr, int k) -> int {
+        const int lo = ptr[k], hi = ptr[k + 1];
         double prev = 0.0;
         for (int i = lo; i < hi; ++i) {
             const double v = cdf[i];
-            if (i == hi - 1) return v == 1.0;
-            if (!(v >= prev) || !std::isfinite(v)) return false;      // (a rounded running sum may pass 1.0 by an ulp)
+            const bool closes = i == hi - 1;
+            if (closes ? v != 1.0 : !std::isfinite(v) || !(v >= prev || (v == 1.0 && prev > 1.0)))
+                return fail(ctx, PS_ERR_ARG, "%s of state %d: ascending from >= 0 with the last entry 1.0", what, k);
+            if (v > prev && lp[i] == -INFINITY)
+                return fail(ctx, PS_ERR_ARG, "%s of state %d: entry %d rises above its predecessor, its log probability is -inf",
+                            what, k, i - lo);
             prev = v;
         }
-        return true;
+        return PS_OK;
     };
     for (int k = 0; k < S; ++k)
-        if (!cdf_ok(tables->out_cdf, model->out_ptr[k], model->out_ptr[k + 1]))
-            return fail(ctx, PS_ERR_ARG, "out_cdf of state %d: ascending from >= 0 with the last entry 1.0", k);
+        if (int rc = cdf_row("out_cdf", tables->out_cdf, model->out_lp, model->out_ptr, k)) return rc;
     for (int k = 0; C.kde && k < NE; ++k)
-        if (!cdf_ok(tables->kde_cdf, model->kde_ptr[k], model->kde_ptr[k + 1]))
-            return fail(ctx, PS_ERR_ARG, "kde_cdf of state %d: ascending from >= 0 with the last entry 1.0", k);
+        if (int rc = cdf_row("kde_cdf", tables->kde_cdf, model->kde_lw, model->kde_ptr, k)) return rc;
     for (int k = 0; C.mix && k < NE; ++k)
-        if (!cdf_ok(model->mix_cdf, model->mix_ptr[k], model->mix_ptr[k + 1]))
-            return fail(ctx, PS_ERR_ARG, "mix_cdf of state %d: ascending from >= 0 with the last entry 1.0", k);
+        if (int rc = cdf_row("mix_cdf", model->mix_cdf, model->mix_lw, model->mix_ptr, k)) return rc;
     for (int64_t i = 0; i < 2 * n_mix; ++i)
         if (!std::isfinite(model->mix_draw[i])) return fail(ctx, PS_ERR_ARG, "mix_draw %lld is not finite", static_cast<long long>(i));
     for (int64_t i = 0; i < n_param; ++i)

@@ -185,9 +185,10 @@ u0 < mix_cdf[i], then that component's draw by its kind from the next block.  mi
 per mixture state the running sum of the weights, added one by one, with the entry of the state's last component of positive
 weight and every entry after it stored as exactly 1.0, so a component of weight 0 is never picked; mix_draw holds two
 doubles per component by emit_param's rule, and emit_param (0, 0) for a mixture state.  The tables are built on the host in float64 (Model._sample_tables, not part of `flat`):
-out_cdf, per state the running sum of np.exp(out_lp) in out-edge order, added one by one, the last entry stored as exactly
-1.0; kde_cdf the same over exp(kde_lw); emit_param, two doubles per emitting state or component: normal (mean, std), uniform
-(low, high - low), log-normal (mu, sigma), exponential (0, rate), kernel density (0, bandwidth).  So a walk's path and
+out_cdf, per state the running sum of np.exp(out_lp) in out-edge order, added one by one, with the entry of the state's last
+out-edge of positive probability and every entry after it stored as exactly 1.0 (mix_cdf's rule: an edge that training left
+at probability 0 is never taken, wherever it stands); kde_cdf the same over exp(kde_lw); emit_param, two doubles per
+emitting state or component: normal (mean, std), uniform (low, high - low), log-normal (mu, sigma), exponential (0, rate), kernel density (0, bandwidth).  So a walk's path and
 length depend on (seed, Q, out_cdf) alone, an integer seed reproduces a call bit for bit, and a batch cut in two with `first`
 moved on gives the bits of the whole.  Values that pass through the device's log, cos and exp agree with the oracle to
 1e-12, uniform draws to the bit.
@@ -965,12 +966,14 @@ class Model(object):
             def cdf(lw, ptr):
                 p, out = np.exp(lw), np.zeros(lw.size, np.float64)
                 for k in range(ptr.size - 1):
-                    run = 0.0
+                    run, last = 0.0, int(ptr[k + 1]) - 1           # last: the row's last entry of positive probability
                     for e in range(int(ptr[k]), int(ptr[k + 1])):
                         run = run + float(p[e])                # (added one by one, in edge order)
                         out[e] = run
+                    while last > ptr[k] and not p[last] > 0:
+                        last -= 1
                     if ptr[k + 1] > ptr[k]:
-                        out[ptr[k + 1] - 1] = 1.0
+                        out[last:ptr[k + 1]] = 1.0             # (an entry of probability 0 behind it is never picked)
                 return out
             emit = []
             for s in self.states[:f["n_emit"]]:

@@ -41,15 +41,18 @@ def block(seed, Q, j):
 
 
 def running(p, ptr):
-    """Per CSR row the running sum of p, added one by one, the row's last entry exactly 1.0."""
+    """Per CSR row the running sum of p, added one by one, exactly 1.0 from the row's last entry of positive probability on
+    (a row without one: its last entry)."""
     out = [0.0] * len(p)
     for k in range(len(ptr) - 1):
+        lo, hi = int(ptr[k]), int(ptr[k + 1])
         run = 0.0
-        for e in range(int(ptr[k]), int(ptr[k + 1])):
+        for e in range(lo, hi):
             run = run + float(p[e])
             out[e] = run
-        if ptr[k + 1] > ptr[k]:
-            out[int(ptr[k + 1]) - 1] = 1.0
+        positive = [e for e in range(lo, hi) if p[e] > 0]
+        for e in range(positive[-1] if positive else max(hi - 1, lo), hi):
+            out[e] = 1.0
     return out
 
 
