@@ -144,6 +144,17 @@ int ps_set_tiling(ps_ctx *ctx, int64_t tile_len, int64_t halo);
  * "tree_screen" 1 (default): on the 32-bit digest a lean kernel walks the subtree jobs first, proves the windows that hold no
  * split empty and leaves the subtree kernel the jobs it cannot decide (counters[14], [15] of ps_get_timings), 0: the subtree
  * kernel takes every job, launch for launch as before; same results either way;
+ * "short_chain" 1 (default): a call on that route -- the 32-bit digest in the default mode with "tree_screen" 1 -- leaves out
+ * the launches it can do without.  (a) A context that shares its device ("shared_device" n > 1) issues no look-ahead launch:
+ * its seam bridges walk 16 windows without a hit ("bridge_patience", 1 .. 4096: tests) in their own wave instead of 3.  If
+ * seams still run out of patience -- any number of them -- the look-ahead kernel runs behind the stitch and finishes them where
+ * they stopped, and the stitch and what follows it run again: one more round trip for that call, no host stitch.  The next 16
+ * calls of the context then launch the look-ahead kernel in the chain, patience 3, exactly as with the option off (data with
+ * stretches of more than 8 window widths without a split: 237 of 1 536 seams at dwells of 8 .. 16 widths), before the option is
+ * tried again.  A lone context keeps patience 3 and the look-ahead kernel with its helpers.  (b) The download kernel of a call without statistics leaves the status block zero
+ * behind its copy, and the next call launches no upload kernel when it repeats the event layout and nothing else has used
+ * the context in between.  0: the launches of the library before the option, launch for launch; 2 / 3: (a) / (b) alone, for
+ * measurements.  Same results either way; counters[16] .. [18] of ps_get_timings say what a call did without;
  * "noise_k_ppm" (default 100 000 = 0.1): near-tie accounting of the 64-bit digest, margin factor in millionths;
  * "near_tie_log" n (default 65 536, 0 .. 2^30): records of the near-tie log that ps_get_near_ties reads (16 bytes each, device
  * memory allocated with the first segment call that logs), 0 = no log.
@@ -563,9 +574,11 @@ int ps_hmm_sample(ps_ctx *ctx, const ps_hmm_model *model, const ps_hmm_sample_ta
  * look-ahead kernel's helpers published (option "lat_help"), [13] published chunks that a seam's owner took instead of
  * scanning them, [14] subtree jobs the screen kernel (option "tree_screen") handed on to the subtree kernel, [15] windows the
  * screen kernel decided (they are part of [0] and [10], so [10] - [15] are the windows the subtree kernel scanned); both
- * cover every round of the call, like [0] and [10], and both are -1 when the call did not launch the screen kernel. */
+ * cover every round of the call, like [0] and [10], and both are -1 when the call did not launch the screen kernel; [16] [17]
+ * look-ahead / upload launches the call did without (option "short_chain": 0 or 1 each), [18] seams its bridges left deferred
+ * that the look-ahead kernel finished behind the stitch (they are part of [4]).  Twenty counters in all. */
 int ps_get_timings(const ps_ctx *ctx, double *ms, int32_t n_ms, int64_t *counters, int32_t n_counters);
-/* The sixteen work counters of ps_get_timings in place (valid for the life of the context; host memory, updated by every
+/* The twenty work counters of ps_get_timings in place (valid for the life of the context; host memory, updated by every
  * call before it returns): a caller that checks one of them after each call -- counters[11], the near ties -- reads it
  * there instead of making a second call. */
 const int64_t *ps_counters(const ps_ctx *ctx);

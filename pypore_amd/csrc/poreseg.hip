@@ -88,6 +88,8 @@ struct HostBuf {          // pinned staging memory
 
 }  // namespace
 
+enum : int { SC_NO_LA = 1, SC_NO_UPLOAD = 2, SC_ALL = 3 };
+constexpr int LA_KEEP = 16;        // calls that keep the look-ahead launch after one that needed it (ps_ctx::la_keep)
 struct ps_ctx {
     int device = 0;
     int n_cu = 0;             // compute units (queried once)
@@ -197,6 +199,19 @@ struct ps_ctx {
     int lat_help = 1;                               // option lat_help / PORESEG_LAT_HELP: 0 = every seam walks alone, as before round 5
     int bridge_budget = BR_MAX;                     // option bridge_budget (1 .. BR_MAX): anchors before a seam gives up -- tests lower it to reach the second chance on small inputs
     int bridge_ext_on = 1;                          // option bridge_ext / PORESEG_BRIDGE_EXT: 0 = straight to the host stitch, as before round 5
+    // option short_chain (include/poreseg.h): launches a call can do without.  Bits: SC_NO_LA a pooled call (shared_n > 1) issues no
+    // look-ahead launch -- its bridges walk pool_patience windows, a seam still deferred takes the second chance; SC_NO_UPLOAD the
+    // download kernel leaves the status block zero, so that a call that repeats the layout launches no upload (small_clean)
+    int short_chain = SC_ALL;
+    int shared_n = 0;                               // option shared_device as last set (<= 1: a lone context)
+    int pool_patience = BR_PATIENCE_POOL;           // option bridge_patience (1 .. 4096): tests lower it to reach the hand-over on small inputs
+    // la_keep: a pooled call whose bridges left seams deferred had the look-ahead kernel run behind its stitch, a round trip late;
+    // the next LA_KEEP calls of the context launch it in the chain again, patience 3, as without the option (the data at hand has
+    // long stretches without splits), then the option is tried anew.  la_now: the current call is one of those.
+    int la_keep = 0;
+    bool la_now = false;
+    bool small_clean = false;                       // the last thing that touched the status block was a call's download kernel, which left it zero
+    bool small_clean_in = false;                    // ... as the current call found it (make_cfg)
     HostBuf h_hdr;
     DevBuf spine_jobs, spine_scratch, spine_dense, spine_meta, tree_jobs, tree_scratch, tree_spill, tree_defer, screen_acc,
         tree_counts, items, item_pos, first_item, ev_off, bounds_off, small;
@@ -205,8 +220,10 @@ struct ps_ctx {
     int timing = 1;           // 0: no events, 1: start/end of the sequence, 2: an event between the phases as well (each costs
                               // ~6 us of idle GPU: the next kernel does not start back to back)
     double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int64_t counters[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, -1, -1};   // [12] chunk results the look-ahead helpers published, [13] of which an owner took,
-                              // [14] subtree jobs tree_screen_kernel deferred, [15] windows it decided (-1: it was not launched)
+    int64_t counters[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, -1, -1, 0, 0, 0, 0};   // [12] chunk results the look-ahead helpers published, [13] of which an owner took,
+                              // [14] subtree jobs tree_screen_kernel deferred, [15] windows it decided (-1: it was not launched),
+                              // [16] [17] look-ahead / upload launches the call did without (option short_chain), [18] seams its
+                              // bridges left deferred that the second chance resumed
     bool screen_ran = false;  // the current call launched tree_screen_kernel
 };
 
@@ -309,6 +326,9 @@ struct SmallLayout { unsigned long long status, work0, work1, work2, dense, stam
 int make_cfg(ps_ctx *ctx, const void *d_samples, const ps_sample_format *fmt, int mw, int maxw, int W,
              double min_gain, DevCfg *c)
 {
+    // (every entry that queues work on the status block comes through here: whatever it is, the block is no longer known clean)
+    ctx->small_clean_in = ctx->small_clean;
+    ctx->small_clean = false;
     if (!fmt) return fail(ctx, PS_ERR_ARG, "sample format is NULL");
     if (fmt->dtype != PS_DTYPE_F32 && fmt->dtype != PS_DTYPE_I16)
         return fail(ctx, PS_ERR_ARG, "unknown dtype %d", fmt->dtype);
@@ -682,6 +702,8 @@ int finish_batch(ps_ctx *ctx, const DevCfg &cfg, size_t n_tj, int64_t n_items, i
     }
     if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
     const bool fused = d_hdr != nullptr && ctx->gather_fused;      // (device stitch: job index == item index)
+    const bool one_copy = ctx->bounds_off.p == ctx->small.as<char>() + sizeof(SmallLayout);
+    int dl_clear = 0;                                  // (option short_chain: the download kernel leaves the status block zero behind its copy)
     if (fused) {
         const int64_t blocks = (n_items >> GS_LOG) + 1;
         const unsigned gg = static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>(blocks, 1024)));
@@ -717,7 +739,6 @@ int finish_batch(ps_ctx *ctx, const DevCfg &cfg, size_t n_tj, int64_t n_items, i
         HIP_TRY(ctx, hipGetLastError());
         if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
     }
-    const bool one_copy = ctx->bounds_off.p == ctx->small.as<char>() + sizeof(SmallLayout);
     if (one_copy) {
         HIP_TRY(ctx, ctx->h_small.reserve(sizeof(SmallLayout) + evb));
         void *h_dev = nullptr;                         // the pinned block as the device sees it (else: plain copy)
@@ -725,8 +746,10 @@ int finish_batch(ps_ctx *ctx, const DevCfg &cfg, size_t n_tj, int64_t n_items, i
         if (h_dev) {
             static_assert(sizeof(SmallLayout) % 8 == 0, "the status block is copied in 8-byte words");
             const long long nw = static_cast<long long>((sizeof(SmallLayout) + evb) / 8);
+            // (a call without statistics on the screened route, see short_route: the calls the option was measured on)
+            if (fused && d_stats == nullptr && ctx->screen_ran && (ctx->short_chain & SC_NO_UPLOAD)) dl_clear = static_cast<int>(sizeof(SmallLayout) / 8);
             hipLaunchKernelGGL(download_kernel, dim3(static_cast<unsigned>(std::min<long long>((nw + 255) / 256, 64))), dim3(256), 0, ctx->stream,
-                               ctx->small.as<unsigned long long>(), static_cast<unsigned long long *>(h_dev), nw);
+                               ctx->small.as<unsigned long long>(), static_cast<unsigned long long *>(h_dev), nw, dl_clear, &sm->hdr.fail);
             HIP_TRY(ctx, hipGetLastError());
         } else {
             HIP_TRY(ctx, hipMemcpyAsync(ctx->h_small.p, ctx->small.p, sizeof(SmallLayout) + evb, hipMemcpyDeviceToHost, ctx->stream));
@@ -761,14 +784,14 @@ int finish_batch(ps_ctx *ctx, const DevCfg &cfg, size_t n_tj, int64_t n_items, i
                     int shown = 0;
                     size_t n_open = 0, n_gave_up = 0, n_defer = 0;
                     for (size_t g = 0; g < nt; ++g) {
-                        if (bm[g].w == 4) ++n_defer;
+                        if (bm[g].w == BR_DEFER || bm[g].w == BR_DEFER_REACHED) ++n_defer;
                         else if (bm[g].w == 3 && mt[g].x == 0 && bm[g].x == 0) ++n_open;
                         else if (bm[g].w == 3) ++n_gave_up;
                     }
                     fprintf(stderr, "[poreseg] stitch failed: %zu tiles; bridges that gave up after anchors of their own %zu, open tiles not bridged %zu, deferred and not finished %zu\n",
                             nt, n_gave_up, n_open, n_defer);
                     for (size_t g = 0; g < nt && shown < 6; ++g)
-                        if ((bm[g].w == 3 && !(mt[g].x == 0 && bm[g].x == 0)) || bm[g].w == 4) {
+                        if ((bm[g].w == 3 && !(mt[g].x == 0 && bm[g].x == 0)) || bm[g].w == BR_DEFER || bm[g].w == BR_DEFER_REACHED) {
                             fprintf(stderr, "[poreseg] stitch failed: tile %zu (event %d, tile %zu of %d, [%d, %d) of %d) bridge status %d after %d anchors (next window %d); its own list: %d anchors, ended %d, open at %d\n",
                                     g, jb[g].ev, g - static_cast<size_t>(jb[g].first_tile), jb[g].ntiles, jb[g].start, jb[g].stop, jb[g].end,
                                     bm[g].w, bm[g].x, bm[g].y, mt[g].x, mt[g].y, mt[g].z);
@@ -836,6 +859,7 @@ int finish_batch(ps_ctx *ctx, const DevCfg &cfg, size_t n_tj, int64_t n_items, i
     if (ctx->timing >= 2 && hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]) == hipSuccess) ctx->ms[1] = ms;
     if (ctx->timing >= 2 && hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]) == hipSuccess) ctx->ms[2] = ms;
     ctx->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    ctx->small_clean = dl_clear > 0;                   // (the copy of a call that came through left the status block zero)
     return PS_OK;
 }
 
@@ -868,6 +892,18 @@ template <int DT> int launch_bridge_la(ps_ctx *ctx, const DevCfg &cfg, unsigned 
     return PS_OK;
 }
 
+// Option short_chain applies on the route of the screened subtrees only -- the 32-bit digest in the product's mode with
+// tree_screen 1 (launch_subtrees) -- and leaves every other route its launches, one for one.
+bool short_route(const ps_ctx *ctx, const DevCfg &cfg)
+{
+    return cfg.bsum != nullptr && !cfg.bs_wide && !ctx->tree_mw && ctx->tree_screen && cfg.mode == MODE_FAST && cfg.grp != nullptr && cfg.prune;
+}
+// (a pooled call on that route issues no look-ahead launch: its bridges keep walking in their own wave)
+bool no_look_ahead(const ps_ctx *ctx, const DevCfg &cfg)
+{
+    return (ctx->short_chain & SC_NO_LA) != 0 && ctx->shared_n > 1 && ctx->bridge_ext_on && !ctx->la_now && short_route(ctx, cfg);
+}
+
 template <int NT, int DT> int launch_bridge(ps_ctx *ctx, const DevCfg &cfg, unsigned nj, SmallLayout *sm)
 {
     ScanShape s;
@@ -876,7 +912,8 @@ template <int NT, int DT> int launch_bridge(ps_ctx *ctx, const DevCfg &cfg, unsi
                        ctx->spine_jobs.as<SpineJob>(), ctx->spine_scratch.as<int2>(), ctx->spine_meta.as<int4>(),
                        ctx->bridges.as<int2>(), ctx->bmeta.as<int4>(), reinterpret_cast<unsigned *>(&sm->status),
                        &sm->work0, static_cast<int>(nj), ctx->bridge_single, ctx->bridge_budget,
-                       NT == 64 ? lat_help_of(ctx, cfg, sm) : LAT_NONE);
+                       NT == 64 ? lat_help_of(ctx, cfg, sm) : LAT_NONE,
+                       no_look_ahead(ctx, cfg) ? ctx->pool_patience : static_cast<int>(BR_PATIENCE));
     HIP_TRY(ctx, hipGetLastError());
     return PS_OK;
 }
@@ -1015,6 +1052,7 @@ template <int FLAGS> int launch_scans_bs(ps_ctx *ctx, const DevCfg &cfg, unsigne
     if (int rc = by_dtype<FLAGS>(cfg.dtype, [&](auto dt) { return launch_spine<64, dt()>(ctx, cfg, nj, sm, true); })) return rc;
     if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
     if (int rc = by_dtype<FLAGS>(cfg.dtype, [&](auto dt) { return launch_bridge<64, dt()>(ctx, cfg, nj, sm); })) return rc;
+    if (no_look_ahead(ctx, cfg)) { ctx->counters[16] += 1; return PS_OK; }
     return by_dtype<FLAGS>(cfg.dtype, [&](auto dt) { return launch_bridge_la<dt()>(ctx, cfg, nj, sm); });
 }
 
@@ -1030,6 +1068,8 @@ int device_stitch_batch_(ps_ctx *ctx, const DevCfg &cfg_in, int bs_mode, const i
                         std::chrono::steady_clock::time_point t_begin, bool digest_ready = false)
 {
     DevCfg cfg = cfg_in;
+    ctx->la_now = ctx->la_keep > 0;
+    if (ctx->la_now) --ctx->la_keep;
     const bool use_bs = bs_mode != 0;                  // 1: block-sum scan on the 32-bit digest, 2: on the 64-bit (wide) digest
     const bool wide = bs_mode == 2;
     cfg.bs_wide = wide ? 1 : 0;
@@ -1145,7 +1185,13 @@ int device_stitch_batch_(ps_ctx *ctx, const DevCfg &cfg_in, int bs_mode, const i
         const char *up = ctx->h_up.as<char>();
         void *up_devptr = nullptr;                     // the pinned blob as the device sees it (else: plain copy)
         if (ctx->upload_by_kernel && hipHostGetDevicePointer(&up_devptr, const_cast<char *>(up), 0) != hipSuccess) { up_devptr = nullptr; (void)hipGetLastError(); }
-        if (up_devptr) {
+        // (option short_chain: the tables are still on the device and the previous call's download kernel left the status block zero)
+        // (... on the route the option applies to, short_route, as far as it is known before K0: every other route launches what it launched)
+        const bool short_rt = use_bs && !wide && !digest_ready && ctx->groups && !ctx->tree_mw && ctx->tree_screen && cfg.mode == MODE_FAST && cfg.prune;
+        const bool skip_upload = reuse && ctx->small_clean_in && !front && short_rt && ctx->upload_by_kernel && (ctx->short_chain & SC_NO_UPLOAD);
+        ctx->small_clean_in = false;                   // (a redo of this call on another digest starts from a block it cleared itself)
+        if (skip_upload) ctx->counters[17] += 1;
+        else if (up_devptr) {
             // (tables still on the device from the previous call: the kernel only clears the status block)
             const long long n16 = reuse ? 0 : static_cast<long long>((up_bytes + 15) / 16);
             const unsigned ug = static_cast<unsigned>(std::max<long long>(1, std::min<long long>((n16 + 255) / 256, 1024)));
@@ -1239,6 +1285,8 @@ int device_stitch_batch_(ps_ctx *ctx, const DevCfg &cfg_in, int bs_mode, const i
     int rc = PS_OK;
     int64_t items_cap = max_items;                      // (grows with the seams a second-chance round extends)
     int slots_used = 0, ext_stride = EXT_MAX;
+    const bool no_la = nj && no_look_ahead(ctx, cfg);
+    bool la_done = false, stride_set = false;          // (the look-ahead kernel ran behind the stitch; the stride of the side buffer is fixed)
     for (int round = 0;; ++round) {
         hipLaunchKernelGGL(assemble_tiles_kernel, dim3(1), dim3(1024), use_lds ? tile_lds : 0, ctx->stream,
                            static_cast<int>(nj), ctx->spine_meta.as<int4>(), ctx->bmeta.as<int4>(),
@@ -1263,7 +1311,7 @@ int device_stitch_batch_(ps_ctx *ctx, const DevCfg &cfg_in, int bs_mode, const i
         rc = finish_batch(ctx, cfg, static_cast<size_t>(items_cap), items_cap, n_ev, d_bounds, cap, h_bounds_off, d_stats, t_begin,
                           d_hdr, &hd, use_bs);
         // ---- second chance for seams that gave up (the block-sum pipeline only: it has the look-ahead kernel) -------------
-        if (rc != RC_FALLBACK || !use_bs || !nj || round == EXT_ROUNDS || !ctx->bridge_ext_on) break;
+        if (rc != RC_FALLBACK || !use_bs || !nj || round == EXT_ROUNDS + (la_done ? 1 : 0) || !ctx->bridge_ext_on) break;
         HIP_TRY(ctx, ctx->h_meta.reserve(2 * nj * sizeof(int4)));
         int4 *h_bm = ctx->h_meta.as<int4>(), *h_mt = h_bm + nj;
         HIP_TRY(ctx, hipMemcpyAsync(h_bm, ctx->bmeta.p, nj * sizeof(int4), hipMemcpyDeviceToHost, ctx->stream));
@@ -1271,12 +1319,32 @@ int device_stitch_batch_(ps_ctx *ctx, const DevCfg &cfg_in, int bs_mode, const i
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         // on the true path: whatever failed there (a seam out of anchors, an open tile entered at its start); elsewhere: the
         // seams that ran out of anchors (few; they may lie on the path once the first ones are mended)
+        // A call that issued no look-ahead launch (option short_chain) and whose bridges left seams deferred: the look-ahead
+        // kernel it did without runs now, once, over every deferred seam, however many, from the window each stopped at --
+        // exactly what it would have done behind the bridge kernel, one round trip later.  Seams that gave up are the business
+        // of the rounds after it.
+        if (no_la && !la_done) {
+            int64_t n_def = 0;
+            for (size_t g = 0; g < nj; ++g) n_def += h_bm[g].w == BR_DEFER || h_bm[g].w == BR_DEFER_REACHED;
+            if (n_def) {
+                if (ctx->debug) fprintf(stderr, "[poreseg] look-ahead kernel behind the stitch: %lld deferred seams\n", static_cast<long long>(n_def));
+                HIP_TRY(ctx, hipMemsetAsync(&sm->hdr, 0, sizeof(AsmHeader), ctx->stream));
+                if (ctx->tree_screen) HIP_TRY(ctx, hipMemsetAsync(&sm->tree_defer[0], 0, sizeof sm->tree_defer[0], ctx->stream));
+                if (int lrc = by_dtype(cfg.dtype, [&](auto dt) { return launch_bridge_la<dt()>(ctx, cfg, static_cast<unsigned>(nj), sm); })) return lrc;
+                la_done = true;
+                ctx->la_keep = LA_KEEP;
+                ctx->counters[4] += n_def;
+                ctx->counters[18] += n_def;
+                continue;
+            }
+        }
         std::vector<int> list;
         bool hopeless = false;
-        if (round == 0) {                              // few seams: long extensions; many (a batch of events): shorter ones
+        if (!stride_set) {                             // few seams: long extensions; many (a batch of events): shorter ones
             size_t n_fail = 0;
             for (size_t g = 0; g < nj; ++g) n_fail += h_bm[g].w == BR_FAIL_REACHED || (h_bm[g].w == BR_FAIL && h_bm[g].x == ctx->bridge_budget);
             ext_stride = n_fail <= static_cast<size_t>(EXT_SLOTS) ? EXT_MAX : EXT_MAX_MANY;
+            stride_set = true;
         }
         const int slot_cap = EXT_SLOTS * (EXT_MAX / ext_stride);
         for (size_t g = 0; g < nj; ++g) {
@@ -1319,6 +1387,7 @@ int device_stitch_batch_(ps_ctx *ctx, const DevCfg &cfg_in, int bs_mode, const i
         if (int irc = reserve_items(ctx, items_cap, total_len, mw)) return irc;
     }
     ctx->counters[3] = hd.n_items;
+    if (slots_used > 0 || la_done) ctx->small_clean = false;   // (a second round: the next call uploads as ever)
     float ms = 0;
     if (ctx->timing >= 2 && nj && hipEventElapsedTime(&ms, ctx->ev[7], ctx->ev[0]) == hipSuccess) ctx->ms[6] = ms;       // blocksum_kernel (K0)
     if (ctx->timing >= 2 && nj && hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[6]) == hipSuccess) ctx->ms[0] = ms;       // spine_kernel
@@ -1542,6 +1611,8 @@ int ps_set_option(ps_ctx *ctx, const char *name, int64_t value)
     // persistent K0 at one wave per SIMD, no helpers, and for n > 3 at most three K0s in flight on the device
     else if (n == "shared_device" && value >= 0 && value <= 4096) {
         const bool sh = value > 1;
+        ctx->shared_n = static_cast<int>(value);
+        ctx->la_keep = 0;
         ctx->k0_waves = sh ? 1 : 0;
         ctx->lat_help = sh ? 0 : 1;
         ctx->k0_admit = value > 3 ? 3 : 0;
@@ -1559,6 +1630,16 @@ int ps_set_option(ps_ctx *ctx, const char *name, int64_t value)
     else if (n == "slots_pct" && value >= 1 && value <= 100) ctx->slots_pct = static_cast<int>(value);
     else if (n == "tree_jobs_per_wave" && value >= 0 && value <= 1024) ctx->tree_jobs_per_wave = static_cast<int>(value);
     else if (n == "tree_screen") ctx->tree_screen = value != 0;
+    // short_chain: 1 (default) the launches a call can do without are left out, 0 the launches of the library before the option,
+    // launch for launch; 2 / 3 one part at a time, for measurements: no look-ahead launch in a pooled call / no upload launch on a
+    // repeated layout (include/poreseg.h)
+    else if (n == "short_chain" && value >= 0 && value <= 3) {
+        static const int bits[4] = {0, SC_ALL, SC_NO_LA, SC_NO_UPLOAD};
+        if (ctx->short_chain != bits[value]) ctx->small_clean = false;
+        ctx->short_chain = bits[value];
+    }
+    // bridge_patience: windows without a hit that a bridge of a pooled call walks before it defers its seam (short_chain)
+    else if (n == "bridge_patience" && value >= 1 && value <= 4096) { ctx->pool_patience = static_cast<int>(value); ctx->la_keep = 0; }
     else if (n == "noise_k_ppm" && value >= 0) ctx->noise_k = static_cast<float>(static_cast<double>(value) * 1.0e-6);
 #ifdef PS_DIAG
     else if (n == "dbg_phase" && value >= 0 && value <= 2) ctx->dbg_phase = static_cast<int>(value);
@@ -2370,11 +2451,11 @@ int ps_get_timings(const ps_ctx *ctx, double *ms, int32_t n_ms, int64_t *counter
 {
     if (!ctx) return PS_ERR_ARG;
     for (int i = 0; i < n_ms && ms; ++i) ms[i] = i < 8 ? ctx->ms[i] : 0.0;
-    for (int i = 0; i < n_counters && counters; ++i) counters[i] = i < 16 ? ctx->counters[i] : 0;
+    for (int i = 0; i < n_counters && counters; ++i) counters[i] = i < 20 ? ctx->counters[i] : 0;
     return PS_OK;
 }
 
-// The context's sixteen work counters where ps_get_timings copies them from: a host that looks at one of them after every
+// The context's twenty work counters where ps_get_timings copies them from: a host that looks at one of them after every
 // call (the near-tie count, counters[11]) reads it in place instead of making a second call.
 const int64_t *ps_counters(const ps_ctx *ctx) { return ctx ? ctx->counters : nullptr; }
 
@@ -2630,6 +2711,7 @@ int ps_filter_requantise_batch(ps_ctx *ctx, const void *d_samples, const ps_samp
     // (longest first: the scratch of the filter paths grows at most once, before anything that uses it is in flight)
     std::sort(by_len.begin(), by_len.end(), [&](int a, int b) { return ev_len[a] > ev_len[b]; });
     HIP_TRY(ctx, ctx->h_small.reserve(sizeof(SmallLayout)));
+    ctx->small_clean = false;
     HIP_TRY(ctx, hipMemsetAsync(ctx->small.p, 0, sizeof(SmallLayout), ctx->stream));
     // 1. every event's filter, queued back to back (one status word for all of them)
     ctx->defer_sync = true;

@@ -1405,7 +1405,8 @@ __global__ __launch_bounds__(NT, (NT == 64 ? PS_BS_MINW : 4)) PS_SCAN_REGS void 
 // status); status 0 nothing to do, 1 joined (continue with list[join_tile][join_idx+1..]),
 // 2 the chain reached the end of the event, 3 gave up (host fallback).
 enum : int { BR_NONE = 0, BR_JOINED = 1, BR_ENDED = 2, BR_FAIL = 3, BR_DEFER = 4,
-              BR_FAIL_REACHED = 5 };                     // (set by the stitch: a failed seam that lies on the true path)
+              BR_FAIL_REACHED = 5,                       // (set by the stitch: a failed seam that lies on the true path)
+              BR_DEFER_REACHED = 6 };                    // (... a deferred seam nobody finished that does: short_chain, no look-ahead launch)
 __device__ __forceinline__ int2 bridge_at(const int2 *bridges, const int2 *ext, const int *ext_slot, int ext_stride, int g, int i)
 {
     return i < BR_MAX ? bridges[static_cast<long long>(g) * BR_MAX + i]
@@ -1413,13 +1414,16 @@ __device__ __forceinline__ int2 bridge_at(const int2 *bridges, const int2 *ext, 
 }
 constexpr int BR_PATIENCE = 3;     // windows without a hit a single-wave bridge scans in one find_split before it defers
                                    // the seam to the look-ahead kernel (bmeta = (count, next window, -, BR_DEFER))
+constexpr int BR_PATIENCE_POOL = LAT_W;   // ... of a pooled call without the look-ahead launch (option short_chain): the seam keeps
+                                   // walking in its own wave; if one still defers the host launches the look-ahead kernel behind the stitch
 
 template <int NT, int DT>
 __global__ __launch_bounds__(NT, (NT == 64 ? PS_BRIDGE_MINW : 4)) PS_BRIDGE_REGS void bridge_kernel(DevCfg c, const SpineJob *jobs, const int2 *lists,
                                                        const int4 *meta, int2 *bridges, int4 *bmeta,
                                                        unsigned *status, unsigned long long *work, int n_jobs, int max_single,
                                                        int budget = BR_MAX,       // anchors before the seam gives up (option bridge_budget: tests)
-                                                       LatHelp lat = LAT_NONE)
+                                                       LatHelp lat = LAT_NONE,
+                                                       int patience = BR_PATIENCE) // windows without a hit before the seam is deferred
 {
     extern __shared__ int ys[];
     __shared__ SharedT<NT> sh;
@@ -1477,7 +1481,7 @@ __global__ __launch_bounds__(NT, (NT == 64 ? PS_BRIDGE_MINW : 4)) PS_BRIDGE_REGS
             // (the samples a bridge reads were validated by the downstream tiles' own spine scans; the first call skips
             // the windows the tile's own chain already scanned without a hit before it gave up)
             const int s = find_split<NT, DT, false>(c, ys, job.base, a, job.end, step == 0 ? m.z : 0, kind, sh, bad, wk, job.end, er,
-                                                    0x7fffffffffffffffLL, (NT == 64 && c.bsum != nullptr) ? BR_PATIENCE : 0x7fffffff);
+                                                    0x7fffffffffffffffLL, (NT == 64 && c.bsum != nullptr) ? patience : 0x7fffffff);
             if (kind == KIND_NONE) { st = BR_ENDED; break; }
             if (kind == KIND_STOP) { st = BR_DEFER; jt = s; break; }     // a long stretch: the look-ahead kernel takes over at window s
             if (threadIdx.x == 0) sh.obuf[cnt] = make_int2(s, kind);
@@ -1541,7 +1545,9 @@ __global__ __launch_bounds__(64 * BR_LA, PS_BRIDGE_MINW) PS_BRIDGE_REGS void bri
     for (int gi = blockIdx.x; gi < n_jobs; gi += gridDim.x) {
         const int g = EXT ? ext_list[gi] : gi;
         const int4 bm = bmeta[g];
-        if (!EXT && bm.w != BR_DEFER) continue;        // only the seams the single-wave bridge kernel deferred
+        // only the seams the single-wave bridge kernel deferred (REACHED: the kernel runs behind the stitch, in a pooled call
+        // that launched its bridges with more patience and no look-ahead kernel, and the stitch has marked those on the true path)
+        if (!EXT && bm.w != BR_DEFER && bm.w != BR_DEFER_REACHED) continue;
         const SpineJob job = jobs[g];
         const int4 m = meta[g];
         int cnt = bm.x;                                // anchors the seam already has; the chain resumes behind the last one
@@ -2359,9 +2365,18 @@ __global__ __launch_bounds__(256) void gather_scan_kernel(const Item *items, con
 
 // The call's status block and per-event offsets go back to the host by a KERNEL that writes the pinned buffer (like the
 // upload: no hand-over to a copy engine between the last kernel and the host's wake-up).
-__global__ __launch_bounds__(256) void download_kernel(const unsigned long long *src, unsigned long long *dst_host, long long n_words)
+// clear_words > 0 (option short_chain): the first clear_words words -- the status block -- are left zero behind the copy, each by
+// the thread that copied it, as the upload kernel of the next call would leave them: a call that repeats the layout then
+// launches no upload (ps_ctx::small_clean).  Not after a stitch that failed (*fail, a word of the block itself, which only
+// ever goes from zero to zero here): the rounds of a second chance add to the block's counters.
+__global__ __launch_bounds__(256) void download_kernel(unsigned long long *src, unsigned long long *dst_host, long long n_words,
+                                                       int clear_words = 0, const int *fail = nullptr)
 {
-    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n_words; i += gridDim.x * 256LL) dst_host[i] = src[i];
+    const long long nz = (clear_words > 0 && !(fail && *fail)) ? clear_words : 0;
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n_words; i += gridDim.x * 256LL) {
+        dst_host[i] = src[i];
+        if (i < nz) src[i] = 0ull;
+    }
 }
 
 // ---- device-side stitch: true spine, tree jobs and items from the tile lists and bridges ----------
@@ -2441,9 +2456,10 @@ __global__ __launch_bounds__(1024) void assemble_tiles_kernel(
         if (!reach[g]) continue;
         const int4 b = bmeta[g];
         if (b.w == BR_JOINED) entry[b.y] = b.z + 1;
-        if (b.w == BR_FAIL || b.w == BR_DEFER || b.w == BR_FAIL_REACHED) {
+        if (b.w == BR_FAIL || b.w == BR_DEFER || b.w == BR_FAIL_REACHED || b.w == BR_DEFER_REACHED) {
             fail_s = 1;
             if (b.w == BR_FAIL) bmeta[g].w = BR_FAIL_REACHED;      // (for the host: this one lies on the true path)
+            if (b.w == BR_DEFER) bmeta[g].w = BR_DEFER_REACHED;
         }
     }
     __syncthreads();

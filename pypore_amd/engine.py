@@ -35,6 +35,7 @@ _ENV_OPTIONS = {
     "PORESEG_UPLOAD": "upload_by_kernel", "PORESEG_TIMING": "timing", "PORESEG_TREE_MW": "tree_mw",
     "PORESEG_TREE_JPW": "tree_jobs_per_wave", "PORESEG_TREE_SCREEN": "tree_screen", "PORESEG_SLOTS_PCT": "slots_pct", "PORESEG_BRIDGE_EXT": "bridge_ext",
     "PORESEG_LAT_HELP": "lat_help", "PORESEG_BRIDGE_BUDGET": "bridge_budget", "PORESEG_DEBUG": "debug",
+    "PORESEG_SHORT_CHAIN": "short_chain", "PORESEG_BRIDGE_PATIENCE": "bridge_patience",
     "PORESEG_GATHER_FUSED": "gather_fused", "PORESEG_SINGLE_PASS": "single_pass", "PORESEG_DOWNLOAD": "download_by_kernel", "PORESEG_K0_UNALIGNED": "k0_unaligned",
     # libporeseg_diag.so only (PORESEG_LIB=.../libporeseg_diag.so): stale or partial results, never the product
     "PORESEG_DBG_PHASE": "dbg_phase", "PORESEG_DBG_K0_NOGRP": "dbg_k0_nogrp", "PORESEG_SCAN_LDS_PAD": "scan_lds_pad", "PORESEG_REP_STAGE": "rep_stage",
@@ -150,14 +151,16 @@ class Context(object):
 
     def timings(self):
         ms = (ctypes.c_double * 8)()
-        cnt = (ctypes.c_int64 * 16)()
-        _lib.check(self.L.ps_get_timings(self.handle, ms, 8, cnt, 16))
+        cnt = (ctypes.c_int64 * 20)()
+        _lib.check(self.L.ps_get_timings(self.handle, ms, 8, cnt, 20))
         return dict(spine_ms=ms[0], tree_ms=ms[1], gather_ms=ms[2], total_ms=ms[3], stitch_ms=ms[4], bridge_ms=ms[5], blocksum_ms=ms[6], seq_ms=ms[7],
                     windows=cnt[0], candidates=cnt[1], tiles=cnt[2], tree_jobs=cnt[3], repairs=cnt[4],
                     exact_rescans=cnt[5], full_exact_scans=cnt[6], wide_redo=cnt[7],
                     windows_spine=cnt[8], windows_bridge=cnt[9], windows_tree=cnt[10], near_ties=cnt[11],
                     helper_chunks_published=cnt[12], helper_chunks_taken=cnt[13],
-                    tree_deferred=cnt[14], windows_screen=cnt[15])
+                    tree_deferred=cnt[14], windows_screen=cnt[15],
+                    # option "short_chain": launches the call did without, seams its bridges left to the second chance
+                    lookahead_skipped=cnt[16], upload_skipped=cnt[17], seams_resumed=cnt[18])
 
     def near_ties(self):
         """Windows of the most recent segment call that were decided among fp64 contenders with a margin inside the

@@ -13,7 +13,12 @@ when the lists differ.  A refactor of the host code that leaves the device code 
 `--tree-screen 0` (before any other argument) sets option tree_screen 0 on the context: the list of a library that has the
 subtree screen is then, launch for launch, the list of one that does not (tree_screen 1, the default, adds one
 tree_screen_kernel in front of every tree_kernel<64> of the narrow digest).  `--compare A B --names-only` compares the kernel
-names without their parameter lists (tree_kernel gained arguments with the screen)."""
+names without their parameter lists (tree_kernel gained arguments with the screen).
+
+`--short-chain 0|1` sets option short_chain on the context (1 is the library's default): with 0 the list is, launch for launch,
+the one of a library without the option.  The routes below run on a lone context, where the option only leaves out the upload
+kernel of a call that repeats the layout of the call before it; `--pooled` runs them as a context that shares its device
+(shared_device 16), where it also leaves out the look-ahead kernel.  Both flags go before any other argument, in any order."""
 import csv
 import glob
 import os
@@ -63,13 +68,17 @@ def compare(dir_a, dir_b):
     return 0
 
 
-def routes(tree_screen=None):
+def routes(tree_screen=None, short_chain=None, pooled=False):
     import numpy as np
     import torch
     from pypore_amd import _lib, engine, synth
     ctx = engine.Context(0)
     if tree_screen is not None:
         ctx.set_option("tree_screen", tree_screen)
+    if short_chain is not None:
+        ctx.set_option("short_chain", short_chain)
+    if pooled:
+        ctx.set_option("shared_device", 16)
     q = synth.QUANTUM
     p = _lib.split_params(prior_segments_per_second=10.)
     dense = _lib.split_params(min_width=100, max_width=1000000, window_width=10000, prior_segments_per_second=10., sampling_freq=1e5)
@@ -137,4 +146,12 @@ if __name__ == "__main__":
     if len(sys.argv) in (4, 5) and sys.argv[1] == "--compare":
         NAMES_ONLY = len(sys.argv) == 5 and sys.argv[4] == "--names-only"
         sys.exit(compare(sys.argv[2], sys.argv[3]))
-    routes(int(sys.argv[2]) if len(sys.argv) == 3 and sys.argv[1] == "--tree-screen" else None)
+    opts, a = {}, sys.argv[1:]
+    while a:
+        if a[0] == "--pooled":
+            opts["pooled"], a = True, a[1:]
+        elif a[0] in ("--tree-screen", "--short-chain") and len(a) >= 2:
+            opts[a[0][2:].replace("-", "_")], a = int(a[1]), a[2:]
+        else:
+            raise SystemExit("usage: launch_order.py [--tree-screen 0|1] [--short-chain 0|1] [--pooled] | --compare A B [--names-only]")
+    routes(**opts)
