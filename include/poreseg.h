@@ -306,6 +306,32 @@ int ps_filter_bessel(ps_ctx *ctx, const void *d_samples, const ps_sample_format 
  * and d_in no longer read when the call returns). */
 int ps_requantise(ps_ctx *ctx, const double *d_in, int64_t n, float *d_out, double *centre_out, double *step_out);
 
+/* A float64 current that is already on the device finds its way back to the int16 ADC counts it came from (the reference
+ * takes any double[:], PyPore/parsers.py:524-528, cparsers.pyx:53,103; an .abf reader returns counts * scale + offset with a
+ * scale that is almost never a power of two).  The three calls below are the full-array passes of that recovery; the caller
+ * proposes the grid (pypore_amd.grid.affine_grid_device: the spacing from a small subset on the host, up to four refinements)
+ * and takes every decision from the numbers that come back.  d_in[n]: fp64, device, 8-byte aligned, n >= 1.  Per sample the
+ * kernels compute k = (x - origin) / quantum and kr = rint(k) with the IEEE operations numpy performs (no contraction, no
+ * reciprocal, round half to even); every reduced quantity is a minimum, a maximum or an integer count, so the report does
+ * not depend on the launch shape.  Each call runs on the context's stream and synchronises it before returning. */
+typedef struct ps_grid_report {
+    double  max_frac;         /* max |k - kr| over the samples for which it is defined (0 if there is none)         */
+    double  min_frac_above;   /* the smallest |k - kr| that is > tol; INFINITY when there is none                    */
+    double  min_count;        /* min kr                                                                              */
+    double  max_count;        /* max kr                                                                              */
+    int64_t n_nonfinite;      /* samples that are NaN or infinite                                                    */
+    int64_t n_undefined;      /* samples whose |k - kr| is NaN (numpy's maximum would be NaN: the check has failed)  */
+} ps_grid_report;
+int ps_grid_check_f64(ps_ctx *ctx, const double *d_in, int64_t n, double origin, double quantum, double tol,
+                      ps_grid_report *out);
+/* d_out[i] = int16(kr - centre) (device, 2-byte aligned).  Only after a check that passed and whose re-centred range
+ * [min_count - centre, max_count - centre] lies inside int16: the conversion of anything else is not defined. */
+int ps_grid_counts_f64(ps_ctx *ctx, const double *d_in, int64_t n, double origin, double quantum, int64_t centre,
+                       int16_t *d_out);
+/* d_out[i] = float(d_in[i]) (device, 4-byte aligned; round to nearest even, numpy's astype) and *n_inexact_out = the number
+ * of samples with double(float(x)) != x -- a NaN counts.  0: the float32 copy is the current, exactly. */
+int ps_narrow_f64(ps_ctx *ctx, const double *d_in, int64_t n, float *d_out, int64_t *n_inexact_out);
+
 /* Event.filter + the representation step for MANY events of one trace in one call (the inner loop of Experiment.parse,
  * DataTypes.py:975-984; File.parse_events here): event e is samples[ev_start[e] .. + ev_len[e]) of d_samples; its filtered
  * current (ps_filter_bessel) goes to d_filtered + sum of the lengths before it, its re-quantised copy (ps_requantise) to the

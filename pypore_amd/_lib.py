@@ -18,7 +18,7 @@ PS_ALIGN_OK, PS_ALIGN_VALUE_ERROR, PS_ALIGN_INDEX_ERROR, PS_ALIGN_ZERO_DIVISION,
 EXPORTS = ["ps_version", "ps_device_count", "ps_create", "ps_destroy", "ps_last_error", "ps_set_tiling", "ps_set_option",
            "ps_synchronize", "ps_min_gain", "ps_segment_batch", "ps_segment_batch_ex", "ps_segment_events", "ps_segment_exact_f64", "ps_detect_events", "ps_detect_segment_trace", "ps_bounds_capacity",
            "ps_best_single_split", "ps_score_window", "ps_get_timings", "ps_synth_trace", "ps_filter_bessel",
-           "ps_requantise", "ps_filter_requantise_batch", "ps_align_batch", "ps_audit_bounds", "ps_counters",
+           "ps_requantise", "ps_grid_check_f64", "ps_grid_counts_f64", "ps_narrow_f64", "ps_filter_requantise_batch", "ps_align_batch", "ps_audit_bounds", "ps_counters",
            "ps_get_near_ties", "ps_hmm_batch", "ps_hmm_expect", "ps_hmm_posterior", "ps_hmm_sample", "ps_pairwise_scores", "ps_pairwise_batch"]
 PS_HMM_VITERBI, PS_HMM_FORWARD, PS_HMM_BACKWARD = 0, 1, 2
 PS_PW_GLOBAL, PS_PW_LOCAL, PS_PW_LOCAL_REPEATED = 0, 1, 2
@@ -57,6 +57,12 @@ class HmmSampleTables(ctypes.Structure):
     """ps_hmm_sample_tables: what ps_hmm_sample reads beside the model (pypore_amd.hmm.Model._sample_tables)."""
     _fields_ = [(f, ctypes.c_void_p) for f in ("out_cdf", "emit_param", "kde_cdf")] + \
                [(f, ctypes.c_int64) for f in ("n_cdf", "n_param", "n_kde")]
+
+
+class GridReport(ctypes.Structure):
+    """ps_grid_report: what ps_grid_check_f64 found on a float64 current for one candidate grid."""
+    _fields_ = [("max_frac", ctypes.c_double), ("min_frac_above", ctypes.c_double), ("min_count", ctypes.c_double),
+                ("max_count", ctypes.c_double), ("n_nonfinite", ctypes.c_int64), ("n_undefined", ctypes.c_int64)]
 
 
 _lib = None
@@ -103,6 +109,9 @@ def lib():
     L.ps_synth_trace.argtypes = [vp, vp, i32, i64, ctypes.c_uint64, P(i64), P(i32), i64]
     L.ps_filter_bessel.argtypes = [vp, vp, P(SampleFormat), i64, i32, dbl, dbl, vp]
     L.ps_requantise.argtypes = [vp, vp, i64, vp, P(dbl), P(dbl)]
+    L.ps_grid_check_f64.argtypes = [vp, vp, i64, dbl, dbl, dbl, P(GridReport)]
+    L.ps_grid_counts_f64.argtypes = [vp, vp, i64, dbl, dbl, i64, vp]
+    L.ps_narrow_f64.argtypes = [vp, vp, i64, vp, P(i64)]
     L.ps_filter_requantise_batch.argtypes = [vp, vp, P(SampleFormat), P(i64), P(i64), ctypes.c_int32, ctypes.c_int32, dbl, dbl,
                                              vp, vp, P(dbl), P(dbl)]
     L.ps_align_batch.argtypes = [vp, P(dbl), P(dbl), P(dbl), i32, dbl, dbl, vp, vp, vp, P(i64), i32, vp, vp, vp]

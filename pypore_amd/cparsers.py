@@ -86,17 +86,24 @@ class FastStatSplit(object):
             """Float input on no ADC grid (the reference takes any float64 buffer, cparsers.pyx:53): the fast route
             re-quantises it on the device (ps_requantise, 2**22 counts at most) for the 64-bit digest.  The segments hold
             views of the ORIGINAL values and take their statistics from those."""
-            cur = np.ascontiguousarray(currents[i], dtype=np.float64)
+            def dev():
+                return torch.device("cuda", torch.cuda.current_device() if self.device is None else int(self.device))
+
+            src = currents[i]
+            f64_on_device = isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.float64
+            if f64_on_device:                       # (both routes read the tensor where it is)
+                cur = src.detach().to(dev()).contiguous()
+            else:
+                cur = np.ascontiguousarray(currents[i], dtype=np.float64)
             if cur.ndim != 1:
                 raise ValueError("Buffer has wrong number of dimensions (expected 1, got %d)" % cur.ndim)
-            n = cur.size
+            n = cur.shape[0]
             if n == 0:
                 out[i] = [Segment(current=currents[i][0:0], start=0, duration=0, end=0)]
                 return
 
             def fast(warn):
-                dev = torch.device("cuda", torch.cuda.current_device() if self.device is None else int(self.device))
-                z, centre, step = ctx.requantise(torch.from_numpy(cur).to(dev))
+                z, centre, step = ctx.requantise(cur if f64_on_device else torch.from_numpy(cur).to(dev()))
                 # (the level that was subtracted, as offset_counts: the device judges near ties against the noise of the
                 #  reference's cumsums, which run on the uncentred values -- include/poreseg.h)
                 return ctx.segment_batch(z, np.array([0, n], dtype=np.int64), self._params, step, want_stats=False,

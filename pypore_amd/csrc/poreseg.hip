@@ -36,6 +36,7 @@
 #include "seg_align.hpp"
 #include "seg_pairwise.hpp"
 #include "seg_hmm.hpp"
+#include "seg_ingest.hpp"
 
 using namespace ps;
 
@@ -2688,6 +2689,76 @@ int ps_requantise(ps_ctx *ctx, const double *d_in, int64_t n, float *d_out, doub
     // (the context's stream does not block on torch's: the caller may read d_out, or free d_in, as soon as this returns)
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     *centre_out = centre; *step_out = step;
+    return PS_OK;
+}
+
+// ---- float64 currents on the device back to their ADC grid (seg_ingest.hpp; grid.affine_grid_device, engine.to_device_with_counts) ----
+static int ingest_args(ps_ctx *ctx, const double *d_in, int64_t n)
+{
+    if (!d_in || n < 1) return fail(ctx, PS_ERR_ARG, "null pointer or empty input");
+    if (reinterpret_cast<uintptr_t>(d_in) & 7u) return fail(ctx, PS_ERR_ARG, "float64 samples must be 8-byte aligned");
+    return PS_OK;
+}
+
+int ps_grid_check_f64(ps_ctx *ctx, const double *d_in, int64_t n, double origin, double quantum, double tol, ps_grid_report *out)
+{
+    if (!ctx) return PS_ERR_ARG;
+    if (!out) return fail(ctx, PS_ERR_ARG, "null pointer or empty input");
+    if (int rc = ingest_args(ctx, d_in, n)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const unsigned grid = ingest_grid(n);
+    HIP_TRY(ctx, ctx->filt_agg.reserve(static_cast<size_t>(grid) * sizeof(GridPartial)));
+    HIP_TRY(ctx, ctx->h_meta.reserve(static_cast<size_t>(grid) * sizeof(GridPartial)));
+    hipLaunchKernelGGL(grid_check_kernel, dim3(grid), dim3(ING_NT), 0, ctx->stream, ingest_span(d_in, n), static_cast<long long>(n), d_in,
+                       origin, quantum, tol, ctx->filt_agg.as<GridPartial>());
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_meta.p, ctx->filt_agg.p, static_cast<size_t>(grid) * sizeof(GridPartial), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const GridPartial *part = ctx->h_meta.as<GridPartial>();
+    ps_grid_report r = {0.0, INFINITY, INFINITY, -INFINITY, 0, 0};
+    for (unsigned g = 0; g < grid; ++g) {                                // (minima, maxima and counts: any order gives the same)
+        r.max_frac = std::fmax(r.max_frac, part[g].max_frac); r.min_frac_above = std::fmin(r.min_frac_above, part[g].min_frac_above);
+        r.min_count = std::fmin(r.min_count, part[g].min_count); r.max_count = std::fmax(r.max_count, part[g].max_count);
+        r.n_nonfinite += static_cast<int64_t>(part[g].n_nonfinite); r.n_undefined += static_cast<int64_t>(part[g].n_undefined);
+    }
+    *out = r;
+    return PS_OK;
+}
+
+int ps_grid_counts_f64(ps_ctx *ctx, const double *d_in, int64_t n, double origin, double quantum, int64_t centre, int16_t *d_out)
+{
+    if (!ctx) return PS_ERR_ARG;
+    if (!d_out) return fail(ctx, PS_ERR_ARG, "null pointer or empty input");
+    if (int rc = ingest_args(ctx, d_in, n)) return rc;
+    if (reinterpret_cast<uintptr_t>(d_out) & 1u) return fail(ctx, PS_ERR_ARG, "int16 counts must be 2-byte aligned");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(grid_counts_kernel, dim3(ingest_grid(n)), dim3(ING_NT), 0, ctx->stream, ingest_span(d_in, n), static_cast<long long>(n), d_in,
+                       origin, quantum, static_cast<long long>(centre), reinterpret_cast<short *>(d_out));
+    HIP_TRY(ctx, hipGetLastError());
+    // (the context's stream does not block on torch's: the caller may read d_out, or free d_in, as soon as this returns)
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return PS_OK;
+}
+
+int ps_narrow_f64(ps_ctx *ctx, const double *d_in, int64_t n, float *d_out, int64_t *n_inexact_out)
+{
+    if (!ctx) return PS_ERR_ARG;
+    if (!d_out || !n_inexact_out) return fail(ctx, PS_ERR_ARG, "null pointer or empty input");
+    if (int rc = ingest_args(ctx, d_in, n)) return rc;
+    if (reinterpret_cast<uintptr_t>(d_out) & 3u) return fail(ctx, PS_ERR_ARG, "float32 samples must be 4-byte aligned");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const unsigned grid = ingest_grid(n);
+    HIP_TRY(ctx, ctx->filt_agg.reserve(static_cast<size_t>(grid) * sizeof(unsigned long long)));
+    HIP_TRY(ctx, ctx->h_meta.reserve(static_cast<size_t>(grid) * sizeof(unsigned long long)));
+    hipLaunchKernelGGL(narrow_f64_kernel, dim3(grid), dim3(ING_NT), 0, ctx->stream, ingest_span(d_in, n), static_cast<long long>(n), d_in, d_out,
+                       ctx->filt_agg.as<unsigned long long>());
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_meta.p, ctx->filt_agg.p, static_cast<size_t>(grid) * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const unsigned long long *part = ctx->h_meta.as<unsigned long long>();
+    unsigned long long bad = 0;
+    for (unsigned g = 0; g < grid; ++g) bad += part[g];
+    *n_inexact_out = static_cast<int64_t>(bad);
     return PS_OK;
 }
 

@@ -453,6 +453,39 @@ class Context(object):
         return out[:current.numel()], centre.value, step.value
 
     @_serialised
+    def grid_check(self, current, origin, quantum, tol=1e-6):
+        """ps_grid_check_f64: a candidate grid origin + k * quantum tried on every sample of a float64 CUDA tensor.  Returns
+        _lib.GridReport (max |k - rint k|, the smallest one above tol, min and max rint k, non-finite samples)."""
+        assert current.is_cuda and current.is_contiguous() and current.dim() == 1 and current.dtype == torch.float64
+        r = _lib.GridReport()
+        torch.cuda.current_stream(current.device).synchronize()
+        _lib.check(self.L.ps_grid_check_f64(self.handle, ctypes.c_void_p(current.data_ptr()), current.numel(), float(origin),
+                                            float(quantum), float(tol), ctypes.byref(r)), self.handle)
+        return r
+
+    @_serialised
+    def grid_counts(self, current, origin, quantum, centre):
+        """ps_grid_counts_f64: int16 CUDA tensor of rint((x - origin) / quantum) - centre, for a grid that grid_check
+        confirmed and whose re-centred range the caller found inside int16."""
+        assert current.is_cuda and current.is_contiguous() and current.dim() == 1 and current.dtype == torch.float64
+        out = torch.empty(current.numel(), dtype=torch.int16, device=current.device)
+        torch.cuda.current_stream(current.device).synchronize()
+        _lib.check(self.L.ps_grid_counts_f64(self.handle, ctypes.c_void_p(current.data_ptr()), current.numel(), float(origin),
+                                             float(quantum), int(centre), ctypes.c_void_p(out.data_ptr())), self.handle)
+        return out
+
+    @_serialised
+    def narrow_f64(self, current):
+        """ps_narrow_f64: (float32 CUDA tensor of a float64 one, the number of samples the conversion changed)."""
+        assert current.is_cuda and current.is_contiguous() and current.dim() == 1 and current.dtype == torch.float64
+        out = torch.empty(current.numel(), dtype=torch.float32, device=current.device)
+        bad = ctypes.c_int64()
+        torch.cuda.current_stream(current.device).synchronize()
+        _lib.check(self.L.ps_narrow_f64(self.handle, ctypes.c_void_p(current.data_ptr()), current.numel(),
+                                        ctypes.c_void_p(out.data_ptr()), ctypes.byref(bad)), self.handle)
+        return out, bad.value
+
+    @_serialised
     def align_batch(self, model_means, model_stds, model_durs, skip_penalty, backslip_penalty,
                     seq_means, seq_stds, seq_durs, seq_off):
         """ps_align_batch: cSegmentAligner.align (calignment.pyx:20-100) for a batch of sequences.  Model arrays: host
@@ -920,6 +953,11 @@ def _note_live(device, cx):
 
 
 # ---- host-side input normalisation -------------------------------------------------------------
+class GridRefusal(ValueError):
+    """The values are not what a road takes -- on no power-of-two grid (detect_quantum), or not exact in float32 -- so the
+    caller may try the next road.  Every other ValueError of the upload is an error and goes through to the caller."""
+
+
 def detect_quantum(x, max_bits=24, full=True):
     """Largest power of two q = 2**-k (0 <= k <= max_bits) such that every sample of the numpy
     array `x` is an integer multiple of q; ValueError if there is none (off-grid data).
@@ -947,16 +985,20 @@ def detect_quantum(x, max_bits=24, full=True):
     sub = x[::max(1, x.size // 65536)]
     k = smallest_k(sub)
     if k is None:
-        raise ValueError("samples are not on a power-of-two ADC grid; pass quantum= (pA per count)")
+        raise GridRefusal("samples are not on a power-of-two ADC grid; pass quantum= (pA per count)")
     if not full or sub.size == x.size or integral(x, k):
         return 2.0 ** -k
     k = smallest_k(x)                                      # the subset was too coarse a witness: full search
     if k is None:
-        raise ValueError("samples are not on a power-of-two ADC grid; pass quantum= (pA per count)")
+        raise GridRefusal("samples are not on a power-of-two ADC grid; pass quantum= (pA per count)")
     return 2.0 ** -k
 
 
 Samples = collections.namedtuple("Samples", "tensor quantum offset")      # pA = count * quantum + offset
+
+
+COUNTS_BEYOND_INT16 = "ADC counts beyond int16 on a grid that is not a power of two: not supported"
+NOT_FLOAT32 = "samples are not exactly representable in float32; pass int16 counts or a coarser grid"
 
 
 def _int_counts_tensor(counts, dev):
@@ -964,7 +1006,7 @@ def _int_counts_tensor(counts, dev):
     counts = np.asarray(counts)
     if counts.dtype != np.int16:
         if counts.size and (counts.min() < -32768 or counts.max() > 32767):
-            raise ValueError("ADC counts beyond int16 on a grid that is not a power of two: not supported")
+            raise ValueError(COUNTS_BEYOND_INT16)
         counts = counts.astype(np.int16)
     if counts.size >= _STAGE_MIN:
         return _staged_upload(counts, dev)
@@ -975,6 +1017,11 @@ def _int_counts_tensor(counts, dev):
 
 _STAGE_MIN = 1 << 22                                    # samples: below this one pageable copy is as fast
 _STAGE_CHUNK = 1 << 24                                  # int16 samples per staging buffer (32 MB)
+_STAGE_F64_MIN = _STAGE_MIN                             # numpy float64 of at least this many samples goes up raw and finds its grid
+                                                        # on the device (_float64_on_device); None: always the host passes
+_STAGE_CHUNK_F64 = 1 << 22                              # float64 samples per staging buffer (32 MB)
+INGEST_PASS = 2048                                      # samples per workgroup pass of the ingest kernels (csrc/seg_ingest.hpp ING_T)
+INGEST_GRID_MAX = 2048                                  # ... and their workgroups at most (ING_GRID_MAX): longer buffers stride
 _stage = {}
 _stage_lock = threading.Lock()                          # the staging buffers of a device are shared: one upload at a time
 
@@ -982,21 +1029,25 @@ _stage_lock = threading.Lock()                          # the staging buffers of
 def _staged_upload(counts, dev):
     """A long int16 array (the data section of an .abf, usually a memmap of the page cache) -> CUDA tensor through two
     pinned staging buffers: the host's copy of chunk k+1 out of the page cache runs while chunk k crosses PCIe.  One
-    `np.ascontiguousarray` of the whole file plus a pageable copy of it is 2-3 x slower (tools/bench_experiment.py)."""
-    key = dev.index
+    `np.ascontiguousarray` of the whole file plus a pageable copy of it is 2-3 x slower (tools/bench_experiment.py).
+    A float64 array (a caller's pA values on their way to the device's grid recovery) goes the same way through
+    buffers of its own."""
+    f64 = counts.dtype == np.float64
+    dtype, chunk = (torch.float64, _STAGE_CHUNK_F64) if f64 else (torch.int16, _STAGE_CHUNK)
+    key = (dev.index, dtype)
     with _stage_lock:                                    # (two host threads uploading to one device would overwrite each other's chunks)
-        if key not in _stage:
-            _stage[key] = ([torch.empty(_STAGE_CHUNK, dtype=torch.int16, pin_memory=True) for _ in range(2)],
+        if key not in _stage or _stage[key][0][0].numel() != chunk:
+            _stage[key] = ([torch.empty(chunk, dtype=dtype, pin_memory=True) for _ in range(2)],
                            [torch.cuda.Event() for _ in range(2)], torch.cuda.Stream(device=dev))
         bufs, events, stream = _stage[key]
-        out = torch.empty(counts.size, dtype=torch.int16, device=dev)
+        out = torch.empty(counts.size, dtype=dtype, device=dev)
         # `out` comes from the caching allocator on the CURRENT stream: work still queued there on a recycled block must
         # be finished before the side stream writes into it
         stream.wait_stream(torch.cuda.current_stream(dev))
         used = [False, False]
         with torch.cuda.stream(stream):
-            for k, a in enumerate(range(0, counts.size, _STAGE_CHUNK)):
-                b = min(counts.size, a + _STAGE_CHUNK)
+            for k, a in enumerate(range(0, counts.size, chunk)):
+                b = min(counts.size, a + chunk)
                 i = k & 1
                 if used[i]:
                     events[i].synchronize()              # the copy that last read this buffer is done
@@ -1008,6 +1059,30 @@ def _staged_upload(counts, dev):
     return out
 
 
+def _recovered(x, dev, want_counts):
+    """A float64 CUDA tensor on no power-of-two grid -> (Samples(int16 counts, quantum, offset), the counts on the host as
+    int64 when asked for: 2 B/sample come down) by grid.affine_grid_device; ValueError as grid.affine_grid raises it."""
+    from .grid import affine_grid_device
+    q, o, k = affine_grid_device(x, dev)
+    return Samples(k, q, o), (k.cpu().numpy().astype(np.int64) if want_counts else None)
+
+
+def _float64_on_device(a, dev, want_counts):
+    """to_device_with_counts for a long numpy float64 array without quantum= / offset=: the raw values go up once through
+    pinned staging and the full-array passes run there.  The decisions are the host road's, in its order: the power-of-two
+    grid of the subset (detect_quantum) and an exact float32 copy (ps_narrow_f64 for astype / astype / array_equal) give
+    the float32 tensor; a refusal of either leads to the affine grid (grid.affine_grid_device for grid.affine_grid)."""
+    x = _staged_upload(a, dev)
+    try:
+        q = detect_quantum(a, full=False)
+        t, bad = context(dev.index).narrow_f64(x)
+        if bad:
+            raise GridRefusal(NOT_FLOAT32)
+        return Samples(t, q, 0.0), None
+    except GridRefusal:
+        return _recovered(x, dev, want_counts)
+
+
 def to_device(current, quantum=None, offset=None, device=None, full_detect=False):
     """Anything a caller of the parser API may hand over -> Samples(CUDA tensor, quantum, offset).
 
@@ -1016,17 +1091,24 @@ def to_device(current, quantum=None, offset=None, device=None, full_detect=False
     * numpy float64 / float32 pA: with `quantum` a power of two (or none given and a power-of-two grid found) the
       values go up as float32, exactly; otherwise the counts are recovered -- rint((x - offset) / quantum) when the
       grid is given, grid.affine_grid(x) when it is not -- and go up as int16.  Data that lies on no grid at all
-      raises ValueError: nothing is ever rounded silently;
-    * torch tensors (float32 / float64 / int16, host or device) are taken as they are (float64 must be exact in float32).
+      raises ValueError: nothing is ever rounded silently.  A float64 array of _STAGE_F64_MIN samples or more without
+      quantum= / offset= goes up raw and takes these decisions on the device (_float64_on_device): same tensors;
+    * torch tensors (float32 / float64 / int16, host or device) are taken as they are; a float64 CUDA tensor that is not
+      exact in float32 finds its grid on the device (grid.affine_grid_device) and becomes int16 counts there.
     """
-    return to_device_with_counts(current, quantum, offset, device, full_detect)[0]
+    return _to_device(current, quantum, offset, device, full_detect, False)[0]
 
 
 def to_device_with_counts(current, quantum=None, offset=None, device=None, full_detect=False):
     """to_device, and how the caller's pA values x relate to the counts k the kernels read: None when x = fl(fl(k * quantum)
     + offset) by construction (a file's counts, int16, a tensor, float samples on a power-of-two grid without an offset);
     otherwise the counts (int64 numpy, on the host) that float samples went up as -- the caller's values are then their own
-    rounding of the grid, and only they can say which count a threshold falls on (detector_thresholds)."""
+    rounding of the grid, and only they can say which count a threshold falls on (detector_thresholds).  Counts that were
+    recovered on the device come down as int16 for this (to_device leaves them there)."""
+    return _to_device(current, quantum, offset, device, full_detect, True)
+
+
+def _to_device(current, quantum, offset, device, full_detect, want_counts):
     from .grid import affine_grid, grid_of
     dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
     g = grid_of(current) if quantum is None else None
@@ -1036,6 +1118,14 @@ def to_device_with_counts(current, quantum=None, offset=None, device=None, full_
             # (a file's counts go up once: events cut from the file are stretches of the same device tensor)
             return Samples(current.device_counts(dev, _int_counts_tensor), g[1], g[2]), None
         return Samples(_int_counts_tensor(g[0], dev), g[1], g[2]), None
+    if (isinstance(current, torch.Tensor) and current.is_cuda and current.dtype == torch.float64 and current.dim() == 1
+            and quantum is None and offset is None):
+        try:                                        # exact in float32 on a power-of-two grid: as it always went up
+            t, q = to_device_samples(current, quantum, device, full_detect)
+            return Samples(t, q, 0.0), None
+        except GridRefusal:                         # not float32, or float32 on no power-of-two grid (numpy input goes on to the
+                                                    # affine grid after either): any scale and offset, the counts found on the device
+            return _recovered(current.detach().to(dev), dev, want_counts)
     if isinstance(current, torch.Tensor) or np.asarray(current).dtype == np.int16:
         t, q = to_device_samples(current, quantum, device, full_detect)
         return Samples(t, q, 0.0 if offset is None else float(offset)), None
@@ -1044,6 +1134,9 @@ def to_device_with_counts(current, quantum=None, offset=None, device=None, full_
         raise ValueError("Buffer has wrong number of dimensions (expected 1, got %d)" % a.ndim)
     if a.dtype not in (np.float64, np.float32):
         raise ValueError("Buffer dtype mismatch, expected 'double' but got %s" % a.dtype)
+    if (a.dtype == np.float64 and quantum is None and offset is None and not full_detect
+            and _STAGE_F64_MIN is not None and a.size >= _STAGE_F64_MIN):
+        return _float64_on_device(a, dev, want_counts)
     off = 0.0 if offset is None else float(offset)
     pow2 = quantum is not None and quantum > 0 and np.log2(quantum) == np.rint(np.log2(quantum))
     if quantum is None or pow2:
@@ -1130,7 +1223,7 @@ def to_device_samples(current, quantum=None, device=None, full_detect=False):
         if t.dtype == torch.float64:
             t32 = t.to(torch.float32)
             if not torch.equal(t32.to(torch.float64), t):
-                raise ValueError("samples are not exactly representable in float32; pass int16 counts or a coarser grid")
+                raise GridRefusal(NOT_FLOAT32)
             t = t32
         if t.dtype not in (torch.float32, torch.int16):
             raise ValueError("Buffer dtype mismatch, expected float64/float32 pA or int16 counts")
@@ -1148,5 +1241,5 @@ def to_device_samples(current, quantum=None, device=None, full_detect=False):
         quantum = detect_quantum(a, full=full_detect)
     a32 = a.astype(np.float32)
     if a.dtype == np.float64 and not np.array_equal(a32.astype(np.float64), a):
-        raise ValueError("samples are not exactly representable in float32; pass int16 counts or a coarser grid")
+        raise GridRefusal(NOT_FLOAT32)
     return torch.from_numpy(np.ascontiguousarray(a32)).to(dev), quantum

@@ -63,6 +63,32 @@ def grid_of(current):
     return None
 
 
+NO_GRID = "samples are not on an ADC grid (counts * quantum + offset); pass quantum= and offset="
+REFINEMENTS = 4                                          # candidates affine_grid tries before it gives up
+
+
+def subset_step(n, sample=65536):
+    """The stride of the subset that proposes the spacing: at most about 2 * sample values of an array of n."""
+    return max(1, n // sample)
+
+
+def subset_candidate(sub):
+    """(distinct values ascending, candidate spacing) of a subset of the samples: the smallest gap between distinct
+    values (noisy traces visit neighbouring counts); spacing None with fewer than two distinct values."""
+    u = np.unique(sub)
+    if u.size < 2:
+        return u, None
+    return u, float(np.diff(u).min())
+
+
+def recentre(kmin, kmax, origin, q):
+    """(mid-range count c, offset of the grid re-centred on it).  The counts are anchored at the subset minimum
+    (0 .. max - min), and a trace that touches both int16 rails would leave the int16 range although it is exactly
+    int16 -- shift by the mid-range count."""
+    c = (int(kmin) + int(kmax) + 1) // 2
+    return c, float(origin) + c * q
+
+
 def affine_grid(x, sample=65536, tol=1e-6):
     """(quantum, offset, counts int64) with x == counts * quantum + offset to within float64 rounding, for an array
     that came from integer ADC counts through any scale and offset; ValueError if there is no such grid.  The spacing
@@ -71,29 +97,65 @@ def affine_grid(x, sample=65536, tol=1e-6):
     x = np.asarray(x, dtype=np.float64)
     if x.size == 0:
         return 1.0, 0.0, np.zeros(0, dtype=np.int64)
-    u = np.unique(x[::max(1, x.size // sample)])
-    if u.size < 2:
-        u = np.unique(x)
-    if u.size < 2:
+    u, q = subset_candidate(x[::subset_step(x.size, sample)])
+    if q is None:
+        u, q = subset_candidate(x)
+    if q is None:
         return 1.0, float(u[0]), np.zeros(x.size, dtype=np.int64)
-    gaps = np.diff(u)
-    q = float(gaps.min())
     # the smallest gap may be a multiple of the true spacing only if no two neighbouring counts occur: the check on the
     # whole array below then fails for the samples in between and a finer candidate is tried
-    for _ in range(4):
+    for _ in range(REFINEMENTS):
         k = (x - u[0]) / q
         kr = np.rint(k)
         if np.max(np.abs(k - kr)) <= tol:
             if np.max(np.abs(kr)) >= 2 ** 31:
                 break
-            # re-centre: the counts are anchored at the subset minimum (0 .. max - min), and a trace that touches both
-            # int16 rails would leave the int16 range although it is exactly int16 -- shift by the mid-range count
             ki = kr.astype(np.int64)
-            c = (int(ki.min()) + int(ki.max()) + 1) // 2
-            return q, float(u[0]) + c * q, ki - c
+            c, o = recentre(ki.min(), ki.max(), u[0], q)
+            return q, o, ki - c
         frac = np.abs(k - kr)
         q = float(np.min(frac[frac > tol])) * q              # a remainder that is itself on the grid, or garbage
-    raise ValueError("samples are not on an ADC grid (counts * quantum + offset); pass quantum= and offset=")
+    raise ValueError(NO_GRID)
+
+
+def affine_grid_device(tensor, device=None, sample=65536, tol=1e-6):
+    """affine_grid for a float64 CUDA tensor, with the passes over the whole array on the device: (quantum, offset, int16
+    CUDA tensor of the counts).  The candidate spacing comes from the same strided subset (downloaded: at most about
+    2 * sample values) through the same helper, the refinements run here and drive ps_grid_check_f64, the re-centring is
+    affine_grid's -- so quantum and offset are affine_grid's to the bit, the counts are its counts, and ValueError is
+    raised where it raises: no grid (non-finite samples included), or counts that leave int16 after re-centring (the
+    message of engine._int_counts_tensor)."""
+    import torch
+    from . import engine
+    dev = tensor.device if device is None else (device if isinstance(device, torch.device) else torch.device("cuda", int(device)))
+    if tensor.dtype != torch.float64 or tensor.dim() != 1:
+        raise ValueError("affine_grid_device takes a one-dimensional float64 tensor")
+    x = tensor.detach().to(dev).contiguous()
+    n = x.numel()
+    if n == 0:
+        return 1.0, 0.0, torch.zeros(0, dtype=torch.int16, device=dev)
+    u, q = subset_candidate(x[::subset_step(n, sample)].cpu().numpy())
+    if q is None:                                        # (rare: the subset is one value -- all distinct values, from the device)
+        u, q = subset_candidate(torch.unique(x).cpu().numpy())
+    if q is None:
+        return 1.0, float(u[0]), torch.zeros(n, dtype=torch.int16, device=dev)
+    ctx = engine.context(dev.index)
+    origin = float(u[0])
+    for _ in range(REFINEMENTS):
+        r = ctx.grid_check(x, origin, q, tol)
+        if r.n_nonfinite:                                # (affine_grid ends in ValueError on NaN / inf: its own message)
+            break
+        if not r.n_undefined and r.max_frac <= tol:
+            if max(abs(r.min_count), abs(r.max_count)) >= 2 ** 31:
+                break
+            c, o = recentre(r.min_count, r.max_count, u[0], q)
+            if int(r.min_count) - c < -32768 or int(r.max_count) - c > 32767:
+                raise ValueError(engine.COUNTS_BEYOND_INT16)
+            return q, o, ctx.grid_counts(x, origin, q, c)
+        if not r.min_frac_above < np.inf:                # (numpy: the minimum of nothing)
+            break
+        q = float(r.min_frac_above) * q
+    raise ValueError(NO_GRID)
 
 
 class Deferred(object):

@@ -104,15 +104,21 @@ class lambda_event_parser(parser):
         # count space (engine.detector_thresholds) -- from the formula the values came from (a file's counts, int16, a device
         # tensor, float samples on a power-of-two grid), or, for float samples that went up as the counts of another grid or
         # with an offset, from the samples and those counts
+        on_device = hasattr(current, "is_cuda")
+        values = current
+        if on_device and counts is not None:        # a float64 tensor that went up as recovered counts: its own values, once
+            values = current.detach().cpu().numpy()
         if counts is None:
             thr = engine.detector_thresholds(s.quantum, self.threshold, self.MIN_CURRENT, offset=s.offset)
         else:
-            thr = engine.detector_thresholds(s.quantum, self.threshold, self.MIN_CURRENT, values=current, counts=counts)
+            thr = engine.detector_thresholds(s.quantum, self.threshold, self.MIN_CURRENT, values=values, counts=counts)
             if thr is None:                          # not monotone in the counts at a threshold: the rules on the host
-                return self._parse_host(np.asarray(current))
+                return self._parse_host(np.asarray(values))
         starts, lens = engine.context(device).detect_events(
             s.tensor, s.quantum, threshold=thr[0], min_duration=self.MIN_DURATION, min_current=thr[1])
-        if hasattr(current, "is_cuda"):             # device tensor in: the events' values come back as pA
+        if on_device and counts is not None:        # (the events hold the caller's values, not count * quantum + offset again)
+            host = values
+        elif on_device:                             # device tensor in: the events' values come back as pA
             host = s.tensor.cpu().numpy().astype(np.float64)
             if not s.tensor.dtype.is_floating_point:
                 host = host * s.quantum
