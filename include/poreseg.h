@@ -227,6 +227,43 @@ int ps_segment_exact_f64(ps_ctx *ctx, const double *d_current, const int64_t *h_
                          int32_t n_ev, const ps_split_params *params, int32_t *d_bounds, int64_t cap,
                          int64_t *h_bounds_off);
 
+/* StatSplit (parsers.py:220-503), the reference's older pure-Python segmenter, on the device: gains on the variance
+ * (use_log 0) or its logarithm, each side of a split modelled as a level ("stepwise") or as a straight line plus noise
+ * ("slanted"); windows of window_width samples advancing by window_width / 2, scanned when they hold at least 2 * min_width
+ * samples (a window of exactly 2 * min_width has one candidate; cparsers.pyx:164 refuses it), threshold = min_gain_per_sample
+ * * window_width (formed by the caller, as Python forms it), forced splits every max_width samples. */
+#define PS_STATSPLIT_STEPWISE 0
+#define PS_STATSPLIT_SLANTED  1
+typedef struct ps_statsplit_params {
+    int32_t min_width;                   /* >= 1                                     */
+    int32_t max_width;                   /* >= min_width   (PS_ERR_ASSERT_WIDTH)     */
+    int32_t window_width;                /* >= 2 min_width (PS_ERR_ASSERT_WINDOW)    */
+    double  threshold;                   /* a gain must exceed it (strict)           */
+    int32_t use_log;                     /* 0 / 1                                    */
+    int32_t splitter;                    /* PS_STATSPLIT_*                           */
+} ps_statsplit_params;
+
+/* Segments events of a float64 current as StatSplit.parse does.  The prefix sums c = cumsum(x), c2 = cumsum(x * x) and, for
+ * the slanted splitter, ct = cumsum(x * t) (t = 0, 1, ... from the event's first sample) are numpy's sequential chains, one
+ * wave per event; one workgroup per event then walks _segment_cumulative with the reference's expressions, operation for
+ * operation in fp64 without contraction: the reference's boundaries by construction, up to the logarithm's last bit when
+ * use_log is set.
+ *   d_current   float64 pA, device; event e = [h_ev_start[e], h_ev_start[e] + h_ev_len[e]), at most 2^30 samples each
+ *   h_lo, h_hi  (each may be NULL: 0 / the event's length) the range [h_lo[e], h_hi[e]) of event e that is segmented, in
+ *               samples from its start, 0 <= lo, hi <= length; the prefix sums always run from the event's first sample
+ *   d_bounds / cap / h_bounds_off   as ps_segment_exact_f64: positions from the event's start, ascending per event;
+ *               PS_ERR_CAPACITY with the required size in h_bounds_off[n_ev] when cap is too small
+ * PS_ERR_INTERNAL: the interval stack or a boundary slot was too small (both are sized from the model, seg_statsplit.hpp).
+ * Cost: the chains run at ~10-20 ns per sample and event, events side by side; one event is one workgroup, so a lone long
+ * trace uses one compute unit. */
+int ps_statsplit_f64(ps_ctx *ctx, const double *d_current, const int64_t *h_ev_start, const int64_t *h_ev_len, int32_t n_ev,
+                     const int64_t *h_lo, const int64_t *h_hi, const ps_statsplit_params *params, int32_t *d_bounds,
+                     int64_t cap, int64_t *h_bounds_off);
+
+/* Diagnostics: the prefix sums ps_statsplit_f64 forms of ONE event, d_current[0 .. n): d_c, d_c2 and (when not NULL) d_ct,
+ * n doubles each, device -- bit for bit np.cumsum(x), np.cumsum(x * x), np.cumsum(x * arange(n)). */
+int ps_statsplit_prefix_f64(ps_ctx *ctx, const double *d_current, int64_t n, double *d_c, double *d_c2, double *d_ct);
+
 /* Upper bound on the number of breakpoints ps_segment_batch can emit for these events
  * (sum over events of len/min_width): a safe `cap`. */
 int64_t ps_bounds_capacity(const int64_t *h_ev_off, int32_t n_ev, int32_t min_width);

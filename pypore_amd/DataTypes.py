@@ -16,7 +16,7 @@ the int16 counts next to the float64 current (pypore_amd.grid), so that parsing 
 import numpy as np
 
 from .core import MetaSegment, Segment, SEGMENT_FIELDS, dump_json, fields_of, gc_paused, ignored, load_json, plain, raw_current
-from .parsers import SpeedyStatSplit, lambda_event_parser, parser as _parser_base
+from .parsers import SpeedyStatSplit, StatSplit, lambda_event_parser, parser as _parser_base  # noqa: F401 (StatSplit: re-export)
 
 EVENT_FIELDS = SEGMENT_FIELDS + ('filtered', 'filter_order', 'filter_cutoff', 'n', 'state_parser', 'segments')
 FILE_FIELDS = ('filename', 'n', 'event_parser', 'mean', 'std', 'duration', 'start', 'end', 'events')

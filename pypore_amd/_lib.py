@@ -19,7 +19,9 @@ EXPORTS = ["ps_version", "ps_device_count", "ps_create", "ps_destroy", "ps_last_
            "ps_synchronize", "ps_min_gain", "ps_segment_batch", "ps_segment_batch_ex", "ps_segment_events", "ps_segment_exact_f64", "ps_detect_events", "ps_detect_segment_trace", "ps_bounds_capacity",
            "ps_best_single_split", "ps_score_window", "ps_get_timings", "ps_synth_trace", "ps_filter_bessel",
            "ps_requantise", "ps_grid_check_f64", "ps_grid_counts_f64", "ps_narrow_f64", "ps_filter_requantise_batch", "ps_align_batch", "ps_audit_bounds", "ps_counters",
-           "ps_get_near_ties", "ps_hmm_batch", "ps_hmm_expect", "ps_hmm_posterior", "ps_hmm_sample", "ps_pairwise_scores", "ps_pairwise_batch"]
+           "ps_get_near_ties", "ps_hmm_batch", "ps_hmm_expect", "ps_hmm_posterior", "ps_hmm_sample", "ps_pairwise_scores", "ps_pairwise_batch",
+           "ps_statsplit_f64", "ps_statsplit_prefix_f64"]
+PS_STATSPLIT_STEPWISE, PS_STATSPLIT_SLANTED = 0, 1
 PS_HMM_VITERBI, PS_HMM_FORWARD, PS_HMM_BACKWARD = 0, 1, 2
 PS_PW_GLOBAL, PS_PW_LOCAL, PS_PW_LOCAL_REPEATED = 0, 1, 2
 PS_PW_OK, PS_PW_INDEX_ERROR = 0, 1
@@ -31,6 +33,12 @@ class SplitParams(ctypes.Structure):
                 ("min_gain_per_sample", ctypes.c_double), ("false_positive_rate", ctypes.c_double),
                 ("prior_segments_per_second", ctypes.c_double), ("sampling_freq", ctypes.c_double),
                 ("cutoff_freq", ctypes.c_double)]
+
+
+class StatSplitParams(ctypes.Structure):
+    """ps_statsplit_params: StatSplit's widths, its threshold min_gain_per_sample * window_width, use_log and the splitter."""
+    _fields_ = [("min_width", ctypes.c_int32), ("max_width", ctypes.c_int32), ("window_width", ctypes.c_int32),
+                ("threshold", ctypes.c_double), ("use_log", ctypes.c_int32), ("splitter", ctypes.c_int32)]
 
 
 class SampleFormat(ctypes.Structure):
@@ -127,6 +135,8 @@ def lib():
     L.ps_pairwise_batch.argtypes = [vp, vp, P(i64), i32, vp, P(i64), i32, P(i32), P(i32), i32, i32, dbl, i32, vp, vp,
                                     P(i64), vp, vp, vp, P(i64), vp, vp, vp, vp]
     L.ps_audit_bounds.argtypes = [vp, vp, P(SampleFormat), i64, P(SplitParams), P(i32), i32, P(dbl)]
+    L.ps_statsplit_f64.argtypes = [vp, vp, P(i64), P(i64), i32, P(i64), P(i64), P(StatSplitParams), vp, i64, P(i64)]
+    L.ps_statsplit_prefix_f64.argtypes = [vp, vp, i64, vp, vp, vp]
     _lib = L
     return L
 

@@ -37,6 +37,7 @@
 #include "seg_pairwise.hpp"
 #include "seg_hmm.hpp"
 #include "seg_ingest.hpp"
+#include "seg_statsplit.hpp"
 
 using namespace ps;
 
@@ -173,6 +174,9 @@ struct ps_ctx {
     DevBuf ev_info_tr;        // single-pass file route (ps_detect_segment_trace): (centre, phase, first block) of the events cut out of a trace-aligned digest
     DevBuf blk_cls, cls_mm;   // ... K0's verdict per block against the detector's threshold (2 bits), min / max per 128 blocks
     DevBuf pre_c;             // exact route (ps_segment_exact_f64): c and c2 of the call's samples, 16 B per sample
+    // StatSplit (ps_statsplit_f64): per-event tables, prefix sums (c, c2, ct), boundary slots, interval stacks, counts +
+    // status word, output offsets
+    DevBuf ss_tab, ss_pre, ss_tmp, ss_stack, ss_cnt, ss_off;
     // Near-tie log of the segment calls (DevCfg::nt_log, ps_get_near_ties): nt_cap records (option near_tie_log, 0: off), allocated
     // with the first call that logs.  nt_seen: records the last segment call counted (-1: not counted), nt_call_cap the capacity
     // it ran with; nt_ev_start / nt_ev_len: its events, kept only when it logged any (the records are mapped to them on request).
@@ -1543,7 +1547,7 @@ void ps_destroy(ps_ctx *ctx)
                       &ctx->lat_state, &ctx->lat_seam, &ctx->lat_res, &ctx->pre_c, &ctx->ev_info_tr, &ctx->blk_cls,
                       &ctx->cls_mm, &ctx->nt_log, &ctx->hmm_model, &ctx->hmm_off, &ctx->hmm_bp,
                       &ctx->hmm_last, &ctx->hmm_flags, &ctx->hmm_fmat, &ctx->hmm_acc, &ctx->hmm_skip, &ctx->hmm_pmax,
-                      &ctx->hmm_samp};
+                      &ctx->hmm_samp, &ctx->ss_tab, &ctx->ss_pre, &ctx->ss_tmp, &ctx->ss_stack, &ctx->ss_cnt, &ctx->ss_off};
     for (DevBuf *b : bufs) b->release();
     ctx->h_meta.release(); ctx->h_dense.release(); ctx->h_small.release(); ctx->h_up.release(); ctx->h_hdr.release();
     for (auto &e : ctx->ev) if (e) (void)hipEventDestroy(e);
@@ -1749,6 +1753,124 @@ int ps_segment_exact_f64(ps_ctx *ctx, const double *d_current, const int64_t *h_
     if (!ctx) return PS_ERR_ARG;
     const ps_sample_format fmt = {PS_DTYPE_F32, 0, 1.0};        // (unused by the scans of this route: they read c and c2 only)
     return segment_events_impl(ctx, d_current, &fmt, h_ev_start, h_ev_len, n_ev, params, d_bounds, cap, h_bounds_off, nullptr, nullptr, true);
+}
+
+// ---- StatSplit (seg_statsplit.hpp) -----------------------------------------------------------------------------------
+// The call's per-event tables go up in one copy (SsEvents: start, len, pre, lo, hi, slot), the prefix sums lie event after
+// event (pre[e]); returns the launch-ready view of them.
+static int statsplit_upload(ps_ctx *ctx, const std::vector<int64_t> &tab, int32_t n_ev, SsEvents *ev)
+{
+    HIP_TRY(ctx, ctx->ss_tab.reserve(tab.size() * sizeof(int64_t)));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->ss_tab.p, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    const int64_t *t = ctx->ss_tab.as<int64_t>();
+    const size_t n = static_cast<size_t>(n_ev);
+    ev->start = t; ev->len = t + n; ev->pre = t + 2 * n; ev->lo = t + 3 * n; ev->hi = t + 4 * n; ev->slot = t + 5 * n;
+    ev->n_ev = n_ev;
+    return PS_OK;
+}
+
+int ps_statsplit_f64(ps_ctx *ctx, const double *d_current, const int64_t *h_ev_start, const int64_t *h_ev_len, int32_t n_ev,
+                     const int64_t *h_lo, const int64_t *h_hi, const ps_statsplit_params *params, int32_t *d_bounds,
+                     int64_t cap, int64_t *h_bounds_off)
+{
+    if (!ctx) return PS_ERR_ARG;
+    if (!h_ev_start || !h_ev_len || !params || !h_bounds_off || n_ev < 0 || cap < 0 || (cap > 0 && !d_bounds))
+        return fail(ctx, PS_ERR_ARG, "null/negative argument");
+    const int64_t mw = params->min_width, maxw = params->max_width, W = params->window_width;
+    if (mw < 1) return fail(ctx, PS_ERR_ARG, "min_width must be >= 1");
+    if (!(maxw >= mw)) return fail(ctx, PS_ERR_ASSERT_WIDTH, "reference assertion failed (parsers.py:243)");
+    if (!(W >= 2 * mw)) return fail(ctx, PS_ERR_ASSERT_WINDOW, "reference assertion failed (parsers.py:244)");
+    if ((params->use_log != 0 && params->use_log != 1) ||
+        (params->splitter != PS_STATSPLIT_STEPWISE && params->splitter != PS_STATSPLIT_SLANTED))
+        return fail(ctx, PS_ERR_ARG, "use_log must be 0 or 1 and splitter PS_STATSPLIT_STEPWISE or PS_STATSPLIT_SLANTED");
+    const bool slanted = params->splitter == PS_STATSPLIT_SLANTED;
+    const size_t n = static_cast<size_t>(n_ev);
+    std::vector<int64_t> tab(6 * n + 1, 0);
+    int64_t *t_start = tab.data(), *t_len = t_start + n, *t_pre = t_len + n, *t_lo = t_pre + n, *t_hi = t_lo + n, *t_slot = t_hi + n;
+    int64_t total_len = 0, slots = 0, longest = 0;
+    for (int e = 0; e < n_ev; ++e) {
+        const int64_t len = h_ev_len[e];
+        if (len < 0 || h_ev_start[e] < 0 || len > (1ll << 30))         // (2^30: the slanted splitter's N fits in int64)
+            return fail(ctx, PS_ERR_ARG, "event %d length %lld out of range (2^30 samples at most)", e, static_cast<long long>(len));
+        const int64_t lo = h_lo ? h_lo[e] : 0, hi = h_hi ? h_hi[e] : len;
+        if (lo < 0 || lo > len || hi < 0 || hi > len)
+            return fail(ctx, PS_ERR_ARG, "event %d: range [%lld, %lld) outside its %lld samples", e, static_cast<long long>(lo),
+                        static_cast<long long>(hi), static_cast<long long>(len));
+        const int64_t span = std::max<int64_t>(0, hi - lo);
+        t_start[e] = h_ev_start[e]; t_len[e] = len; t_pre[e] = total_len; t_lo[e] = lo; t_hi[e] = hi; t_slot[e] = slots;
+        total_len += len;
+        slots += 2 * (span / mw) + 2;                                 // (seg_statsplit.hpp: boundary slots)
+        longest = std::max(longest, span);
+    }
+    t_slot[n] = slots;
+    for (int e = 0; e <= n_ev; ++e) h_bounds_off[e] = 0;
+    if (n_ev == 0) return PS_OK;
+    if (total_len > 0 && !d_current) return fail(ctx, PS_ERR_ARG, "d_current is NULL");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const unsigned n_wg = static_cast<unsigned>(std::min<int64_t>(n_ev, 4ll * cu_count(ctx)));   // (more events: grid stride)
+    const int64_t stack_cap = longest / mw + 2;                       // (seg_statsplit.hpp: stack size)
+    SsEvents ev;
+    int rc = statsplit_upload(ctx, tab, n_ev, &ev);
+    if (rc) return rc;
+    const size_t pre_n = static_cast<size_t>(std::max<int64_t>(1, total_len));
+    HIP_TRY(ctx, ctx->ss_pre.reserve((slanted ? 3 : 2) * pre_n * sizeof(double)));
+    HIP_TRY(ctx, ctx->ss_tmp.reserve(static_cast<size_t>(slots) * sizeof(int32_t)));
+    HIP_TRY(ctx, ctx->ss_stack.reserve(static_cast<size_t>(n_wg) * static_cast<size_t>(stack_cap) * sizeof(SsFrame)));
+    HIP_TRY(ctx, ctx->ss_cnt.reserve((n + 2) * sizeof(int32_t)));     // counts, then the status word
+    SsCfg cfg;
+    cfg.C = ctx->ss_pre.as<double>(); cfg.C2 = cfg.C + pre_n; cfg.Ct = slanted ? cfg.C2 + pre_n : nullptr;
+    cfg.mw = static_cast<int>(mw); cfg.maxw = static_cast<int>(maxw); cfg.W = static_cast<int>(W);
+    cfg.thresh = params->threshold;
+    cfg.stack = ctx->ss_stack.as<SsFrame>(); cfg.stack_cap = stack_cap;
+    cfg.tmp = ctx->ss_tmp.as<int32_t>();
+    cfg.count = ctx->ss_cnt.as<int32_t>();
+    cfg.status = reinterpret_cast<unsigned *>(cfg.count + n);
+    HIP_TRY(ctx, hipMemsetAsync(cfg.status, 0, sizeof(unsigned), ctx->stream));
+    hipLaunchKernelGGL(statsplit_prefix_kernel, dim3(static_cast<unsigned>(std::min<int64_t>(n_ev, 65535))), dim3(64), 0, ctx->stream,
+                       d_current, ev, const_cast<double *>(cfg.C), const_cast<double *>(cfg.C2), const_cast<double *>(cfg.Ct));
+    HIP_TRY(ctx, hipGetLastError());
+    const int mode = (params->use_log ? 1 : 0) | (slanted ? 2 : 0);
+    switch (mode) {
+    case 0: hipLaunchKernelGGL(statsplit_kernel<0>, dim3(n_wg), dim3(SS_NT), 0, ctx->stream, ev, cfg); break;
+    case 1: hipLaunchKernelGGL(statsplit_kernel<1>, dim3(n_wg), dim3(SS_NT), 0, ctx->stream, ev, cfg); break;
+    case 2: hipLaunchKernelGGL(statsplit_kernel<2>, dim3(n_wg), dim3(SS_NT), 0, ctx->stream, ev, cfg); break;
+    default: hipLaunchKernelGGL(statsplit_kernel<3>, dim3(n_wg), dim3(SS_NT), 0, ctx->stream, ev, cfg); break;
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    std::vector<int32_t> cnt(n + 1);
+    HIP_TRY(ctx, hipMemcpyAsync(cnt.data(), cfg.count, (n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const unsigned st = static_cast<unsigned>(cnt[n]);
+    if (st & SS_ST_STACK) return fail(ctx, PS_ERR_INTERNAL, "StatSplit: device interval stack overflow");
+    if (st & SS_ST_OUT) return fail(ctx, PS_ERR_INTERNAL, "StatSplit: device boundary slot overflow");
+    for (int e = 0; e < n_ev; ++e) h_bounds_off[e + 1] = h_bounds_off[e] + cnt[e];
+    const int64_t total = h_bounds_off[n_ev];
+    if (total > cap)
+        return fail(ctx, PS_ERR_CAPACITY, "bounds capacity %lld < required %lld", static_cast<long long>(cap), static_cast<long long>(total));
+    if (total == 0) return PS_OK;
+    HIP_TRY(ctx, ctx->ss_off.reserve((n + 1) * sizeof(int64_t)));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->ss_off.p, h_bounds_off, (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(statsplit_gather_kernel, dim3(static_cast<unsigned>(std::min<int64_t>(n_ev, 4096))), dim3(256), 0, ctx->stream,
+                       cfg.tmp, ev.slot, ctx->ss_off.as<int64_t>(), n_ev, d_bounds);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return PS_OK;
+}
+
+int ps_statsplit_prefix_f64(ps_ctx *ctx, const double *d_current, int64_t n, double *d_c, double *d_c2, double *d_ct)
+{
+    if (!ctx) return PS_ERR_ARG;
+    if (n < 0 || n > (1ll << 30) || (n > 0 && (!d_current || !d_c || !d_c2))) return fail(ctx, PS_ERR_ARG, "null pointer or bad length");
+    if (n == 0) return PS_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const std::vector<int64_t> tab = {0, n, 0, 0, n, 0, 0};           // one event: start, len, pre, lo, hi, slot[2]
+    SsEvents ev;
+    const int rc = statsplit_upload(ctx, tab, 1, &ev);
+    if (rc) return rc;
+    hipLaunchKernelGGL(statsplit_prefix_kernel, dim3(1), dim3(64), 0, ctx->stream, d_current, ev, d_c, d_c2, d_ct);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return PS_OK;
 }
 
 // What the two segment entry points (ps_segment_events and its kin, ps_detect_segment_trace) do first, each behind the

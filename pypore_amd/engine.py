@@ -356,6 +356,45 @@ class Context(object):
         return bounds[:int(boff[-1])], boff
 
     @_serialised
+    def statsplit_f64(self, current, ev_start, ev_len, params, lo=None, hi=None, cap=None):
+        """ps_statsplit_f64: events [start, start + len) of a float64 CUDA tensor segmented as the reference's StatSplit does
+        (include/poreseg.h); params: _lib.StatSplitParams.  lo / hi: per event the range [lo, hi) that is segmented, in
+        samples from its start (None: all of it).  cap: boundaries the output may hold (None: what the model allows); when
+        it is too small, CapacityError names the size required.  Returns (bounds int32 CUDA tensor, bounds_off)."""
+        assert current.is_cuda and current.is_contiguous() and current.dim() == 1 and current.dtype == torch.float64
+        ev_start = np.ascontiguousarray(ev_start, dtype=np.int64)
+        ev_len = np.ascontiguousarray(ev_len, dtype=np.int64)
+        n_ev = ev_start.size
+        P64 = ctypes.POINTER(ctypes.c_int64)
+        lo = None if lo is None else np.ascontiguousarray(lo, dtype=np.int64)
+        hi = None if hi is None else np.ascontiguousarray(hi, dtype=np.int64)
+        if cap is None:
+            span = np.maximum((ev_len if hi is None else hi) - (0 if lo is None else lo), 0)
+            cap = int(np.sum(2 * (span // max(int(params.min_width), 1)) + 2)) if n_ev else 0
+        bounds = torch.empty(max(cap, 1), dtype=torch.int32, device=current.device)
+        boff = np.zeros(n_ev + 1, dtype=np.int64)
+        torch.cuda.current_stream(current.device).synchronize()
+        rc = self.L.ps_statsplit_f64(self.handle, _ptr(current), ev_start.ctypes.data_as(P64), ev_len.ctypes.data_as(P64), n_ev,
+                                     None if lo is None else lo.ctypes.data_as(P64), None if hi is None else hi.ctypes.data_as(P64),
+                                     ctypes.byref(params), ctypes.c_void_p(bounds.data_ptr()), cap, boff.ctypes.data_as(P64))
+        if rc == _lib.PS_ERR_CAPACITY:
+            raise CapacityError(int(boff[-1]), cap)
+        _lib.check(rc, self.handle)
+        return bounds[:int(boff[-1])], boff
+
+    @_serialised
+    def statsplit_prefix_f64(self, current, want_ct=True):
+        """ps_statsplit_prefix_f64 (diagnostics): the prefix sums StatSplit forms of one float64 CUDA tensor -- (c, c2, ct) as
+        CUDA tensors, ct None unless asked for."""
+        assert current.is_cuda and current.is_contiguous() and current.dim() == 1 and current.dtype == torch.float64
+        c, c2 = torch.empty_like(current), torch.empty_like(current)
+        ct = torch.empty_like(current) if want_ct else None
+        torch.cuda.current_stream(current.device).synchronize()
+        _lib.check(self.L.ps_statsplit_prefix_f64(self.handle, _ptr(current), current.numel(), _ptr(c), _ptr(c2), _ptr(ct)),
+                   self.handle)
+        return c, c2, ct
+
+    @_serialised
     def best_single_split(self, samples, quantum, offset_counts=0):
         fmt = _lib.SampleFormat(_lib.PS_DTYPE_F32 if samples.dtype == torch.float32 else _lib.PS_DTYPE_I16,
                                 int(offset_counts), float(quantum))
@@ -761,6 +800,14 @@ def events_to_redo(sites, n_ev):
 class NearTieWarning(UserWarning):
     """A segment call decided at least one window by a margin inside the reference's own rounding noise: the logarithm's last
     bit on grid data, the noise of its uncentred cumsums on re-quantised float64 data (Context.near_ties)."""
+
+
+class CapacityError(RuntimeError):
+    """The caller's output capacity was too small (PS_ERR_CAPACITY): `required` is the size that fits."""
+
+    def __init__(self, required, cap):
+        RuntimeError.__init__(self, "poreseg: output capacity %d < required %d" % (cap, required))
+        self.required, self.cap = int(required), int(cap)
 
 
 NEAR_TIE_WARNING = True      # set False to skip the counter read after every call (one ps_get_timings, ~1 us)

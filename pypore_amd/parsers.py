@@ -191,3 +191,107 @@ class SpeedyStatSplit(parser):
     def best_single_split(self, current):
         """(gain, index) of the best single split; like the reference wrapper, without cutoff_freq (:530-534)."""
         return self._fast(cutoff=False).best_single_split(current)
+
+
+class StatSplit(parser):
+    """The reference's older segmenter (parsers.py:220-503; "DEPRECATED: USE SPEEDYSTATSPLIT" there, but the only one that
+    splits on the variance itself and the only one with a slanted model), on the GPU (ps_statsplit_f64, include/poreseg.h).
+
+    It is not SpeedyStatSplit under another name: a window is scanned when it holds at least 2 * min_width samples (so one
+    of exactly 2 * min_width has a single candidate; cparsers.pyx:164 refuses it), the threshold is min_gain_per_sample *
+    window_width (not doubled), `use_log=False` compares variances instead of their logarithms, and `splitter="slanted"`
+    models each side of a split as a straight line plus noise -- ramps and drifting levels.  The prefix sums are numpy's
+    sequential cumsums and every expression is the reference's, operation for operation in float64: the reference's
+    boundaries by construction, up to the last bit of the logarithm when use_log is set.
+
+    Attributes carry the reference's names (they are the JSON schema).  Deliberate deviations from the reference:
+    * splitter="slanted" with use_log=True works (the reference calls an undefined `log`: NameError);
+    * a parser stays what it was built as: the reference's parse() overwrites `splitter` with a bound method, so that a
+      second parse() of a slanted parser silently runs stepwise;
+    * splitter="slanted" with an `end` short of len(current) raises ValueError, as the reference's broadcast of
+      current * linspace(0, end, num=end) does;
+    * a callable splitter raises NotImplementedError (the reference would call it; nothing on the device can);
+    * no RecursionError on long traces: the recursion runs on an explicit stack on the device.
+    Input: numpy arrays or float64 CUDA tensors (what SpeedyStatSplit.parse_exact_batch takes), converted to float64."""
+
+    def __init__(self, min_width=1000, max_width=1000000, min_gain_per_sample=0.03, window_width=10000, use_log=True,
+                 splitter="stepwise"):
+        self.min_width = max(min_width, 1)
+        self.max_width = max_width or 100 * min_width
+        self.min_gain_per_sample = min_gain_per_sample
+        self.window_width = window_width or 10 * min_width
+        assert self.max_width >= self.min_width
+        assert self.window_width >= 2 * self.min_width
+        self.use_log = use_log
+        self.splitter = splitter
+
+    def _params(self):
+        from . import _lib
+        if callable(self.splitter):
+            raise NotImplementedError("StatSplit: a callable splitter cannot run on the device; use 'stepwise' or 'slanted'")
+        slanted = self.splitter == "slanted"
+        return _lib.StatSplitParams(int(self.min_width), int(self.max_width), int(self.window_width),
+                                    float(self.min_gain_per_sample * self.window_width), 1 if self.use_log else 0,
+                                    _lib.PS_STATSPLIT_SLANTED if slanted else _lib.PS_STATSPLIT_STEPWISE)
+
+    @staticmethod
+    def _normalise(n, start, end):
+        """start / end as subscripts of a current of n samples (parsers.py:263-268)."""
+        if start < 0:
+            start += n + 1
+        if end < 0:
+            end += n + 1
+        return min(start, n), min(end, n)
+
+    def _bounds(self, currents, ranges):
+        """Boundaries (int32 numpy, positions in the current) per current, all in one device call; ranges: (start, end)
+        per current, normalised.  Returns them with the host arrays the Segments are cut from."""
+        import torch
+        from . import engine
+        params = self._params()
+        ctx = engine.context(None)
+        dev = torch.device("cuda", ctx.device)
+        ts, srcs = [], []
+        for cur in currents:
+            if isinstance(cur, torch.Tensor):
+                t = cur.to(dev, torch.float64).contiguous()
+                src = cur.detach().cpu().numpy()
+            else:
+                src = cur if isinstance(cur, np.ndarray) else np.asarray(cur)
+                a = np.ascontiguousarray(src, dtype=np.float64)
+                if a.ndim != 1:
+                    raise ValueError("Buffer has wrong number of dimensions (expected 1, got %d)" % a.ndim)
+                t = torch.from_numpy(a).to(dev)
+            ts.append(t)
+            srcs.append(src)
+        lens = np.array([t.numel() for t in ts], dtype=np.int64)
+        lo = np.array([r[0] for r in ranges], dtype=np.int64)
+        hi = np.array([r[1] for r in ranges], dtype=np.int64)
+        if self.splitter == "slanted" and np.any(hi != lens):
+            raise ValueError("operands could not be broadcast together: splitter='slanted' needs end == len(current)")
+        if lo.size and (lo.min() < 0 or hi.min() < 0):
+            raise ValueError("start / end before the first sample")
+        if not lens.sum():
+            return [np.zeros(0, dtype=np.int32) for _ in ts], srcs
+        allt = ts[0] if len(ts) == 1 else torch.cat(ts)
+        bounds, boff = ctx.statsplit_f64(allt, np.concatenate(([0], np.cumsum(lens)))[:-1], lens, params, lo=lo, hi=hi)
+        b = bounds.cpu().numpy()
+        return [b[boff[e]:boff[e + 1]] for e in range(len(ts))], srcs
+
+    @staticmethod
+    def _segments(src, b, start, end):
+        edges = [start] + b.tolist() + [end]
+        return [Segment(current=src[a:z_], start=a, duration=z_ - a) for a, z_ in zip(edges, edges[1:])]
+
+    def parse(self, current, start=0, end=-1):
+        """Segments current[start:end] (negative start / end count from len + 1, as in the reference).  Returns Segments
+        with absolute `start` and `duration` in samples; their `current` is a view of the input."""
+        start, end = self._normalise(len(current), start, end)
+        (b,), (src,) = self._bounds([current], [(start, end)])
+        return self._segments(src, b, start, end)
+
+    def parse_batch(self, currents):
+        """Many currents in one device call (extension): [parse(c) for c in currents]."""
+        ranges = [(0, len(c)) for c in currents]
+        bs, srcs = self._bounds(currents, ranges)
+        return [self._segments(src, b, a, z_) for src, b, (a, z_) in zip(srcs, bs, ranges)]
