@@ -87,7 +87,11 @@ int ps_device_count(void);
 /* Creates a context on GPU `device`; stream = an existing hipStream_t to launch on, or NULL
  * to let the context create its own. */
 int ps_create(int device, void *stream, ps_ctx **out);
+/* Waits for the context's stream, then frees every buffer, event and stream the context made (never a caller's stream). */
 void ps_destroy(ps_ctx *ctx);
+/* Diagnostic: bytes of device memory plus pinned host memory that the contexts of this process hold right now (the library's
+ * own bookkeeping, not the device's free memory).  Back at its earlier value once the contexts made since are destroyed. */
+int64_t ps_live_bytes(void);
 const char *ps_last_error(const ps_ctx *ctx);
 /* Tiling of long traces: a trace longer than tile_len + halo samples is cut into tiles whose
  * spines are computed speculatively and stitched.  0 keeps the default. */

@@ -20,7 +20,7 @@ EXPORTS = ["ps_version", "ps_device_count", "ps_create", "ps_destroy", "ps_last_
            "ps_best_single_split", "ps_score_window", "ps_get_timings", "ps_synth_trace", "ps_filter_bessel",
            "ps_requantise", "ps_grid_check_f64", "ps_grid_counts_f64", "ps_narrow_f64", "ps_filter_requantise_batch", "ps_align_batch", "ps_audit_bounds", "ps_counters",
            "ps_get_near_ties", "ps_hmm_batch", "ps_hmm_expect", "ps_hmm_posterior", "ps_hmm_sample", "ps_pairwise_scores", "ps_pairwise_batch",
-           "ps_statsplit_f64", "ps_statsplit_prefix_f64"]
+           "ps_statsplit_f64", "ps_statsplit_prefix_f64", "ps_live_bytes"]
 PS_STATSPLIT_STEPWISE, PS_STATSPLIT_SLANTED = 0, 1
 PS_HMM_VITERBI, PS_HMM_FORWARD, PS_HMM_BACKWARD = 0, 1, 2
 PS_PW_GLOBAL, PS_PW_LOCAL, PS_PW_LOCAL_REPEATED = 0, 1, 2
@@ -96,6 +96,8 @@ def lib():
     L.ps_create.argtypes = [ctypes.c_int, vp, P(vp)]
     L.ps_destroy.argtypes = [vp]
     L.ps_destroy.restype = None
+    L.ps_live_bytes.argtypes = []
+    L.ps_live_bytes.restype = i64
     L.ps_last_error.argtypes = [vp]
     L.ps_last_error.restype = ctypes.c_char_p
     L.ps_set_tiling.argtypes = [vp, i64, i64]

@@ -12,9 +12,14 @@
 // kernels' template arguments), reserve_digest + launch_k0 (phase 0, for every route that runs K0), scan_shape (launch shape of
 // the scan kernels), launch_scans_bs / launch_spine_nt (phases 1, 1b), launch_subtrees (phase 3), make_spine_job and
 // reserve_items (tile tables and item buffers), begin_segment_call (prologue of the segment entry points).
+// The context (ps_ctx) owns its GPU resources: DevBuf, HostBuf, Event and Stream free themselves, so ps_destroy is `delete ctx`
+// and a half-built context of ps_create releases what it had.  The segmentation chain's members are flat; every other feature
+// keeps its buffers, budgets and caches in one sub-struct of ps_ctx (filt, align, pw, ss, nt, hmm).  A new feature adds its
+// sub-struct there and needs no entry anywhere else.  ps_live_bytes counts what the owning buffers of the process hold.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <complex>
 #include <cmath>
@@ -43,18 +48,25 @@ using namespace ps;
 
 namespace {
 
-struct DevBuf {
+// Device + pinned host bytes the owning DevBufs and HostBufs of the process hold (ps_live_bytes): touched only where memory is
+// really allocated or freed, never by a reserve() that finds room.
+std::atomic<int64_t> g_live_bytes{0};
+
+struct NoCopy { NoCopy() = default; NoCopy(const NoCopy &) = delete; NoCopy &operator=(const NoCopy &) = delete; };
+
+struct DevBuf : NoCopy {  // device memory that frees itself: an owner (reserve) or a view into another buffer (alias)
     void *p = nullptr;
     size_t cap = 0;
     bool owned = true;        // false: p points into another buffer (alias), nothing to free
+    ~DevBuf() { release(); }
     hipError_t reserve(size_t bytes)
     {
         if (!owned) { p = nullptr; cap = 0; owned = true; }
         if (bytes <= cap) return hipSuccess;
-        if (p) { hipError_t e = hipFree(p); if (e != hipSuccess) return e; p = nullptr; cap = 0; }
+        if (p) { hipError_t e = hipFree(p); if (e != hipSuccess) return e; g_live_bytes -= cap; p = nullptr; cap = 0; }
         size_t want = std::max(bytes, cap + cap / 2);
         hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) cap = want;
+        if (e == hipSuccess) { cap = want; g_live_bytes += cap; }
         return e;
     }
     // as reserve(), but a fresh allocation is cleared (buffers whose stale contents are compared with an epoch)
@@ -67,25 +79,39 @@ struct DevBuf {
         return e;
     }
     // Points this buffer into `blob` (one upload for several small arrays); a later reserve() allocates afresh.
-    void alias(void *ptr) { if (p && owned) (void)hipFree(p); p = ptr; cap = 0; owned = false; }
-    void release() { if (p && owned) (void)hipFree(p); p = nullptr; cap = 0; owned = true; }
+    void alias(void *ptr) { release(); p = ptr; owned = false; }
+    void release() { if (p && owned) { (void)hipFree(p); g_live_bytes -= cap; } p = nullptr; cap = 0; owned = true; }
     template <class T> T *as() { return static_cast<T *>(p); }
 };
 
-struct HostBuf {          // pinned staging memory
+struct HostBuf : NoCopy { // pinned staging memory that frees itself
     void *p = nullptr;
     size_t cap = 0;
+    ~HostBuf() { release(); }
     hipError_t reserve(size_t bytes)
     {
         if (bytes <= cap) return hipSuccess;
-        if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
+        release();
         size_t want = std::max(bytes, cap + cap / 2);
         hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-        if (e == hipSuccess) cap = want;
+        if (e == hipSuccess) { cap = want; g_live_bytes += cap; }
         return e;
     }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
+    void release() { if (p) { (void)hipHostFree(p); g_live_bytes -= cap; } p = nullptr; cap = 0; }
     template <class T> T *as() { return static_cast<T *>(p); }
+};
+
+struct Event : NoCopy {   // an event of the context, destroyed with it
+    hipEvent_t e = nullptr;
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    operator hipEvent_t() const { return e; }
+};
+
+struct Stream : NoCopy {  // the context's stream: destroyed with it when the context made it (own), never when the caller handed it in
+    hipStream_t s = nullptr;
+    bool own = false;
+    ~Stream() { if (own && s) (void)hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
 };
 
 }  // namespace
@@ -95,8 +121,12 @@ constexpr int LA_KEEP = 16;        // calls that keep the look-ahead launch afte
 struct ps_ctx {
     int device = 0;
     int n_cu = 0;             // compute units (queried once)
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+    // The stream and the events stand in front of every buffer: members go in reverse order, so the buffers are freed after
+    // the destructor's synchronise and before the stream and the events are destroyed.
+    Stream stream;
+    Event ev[10];             // [0..7] phase marks (timing level 2), [8] start and [9] end of the call's device work (level 1)
+    Event ev_front[2];        // hand-over events (no timing): [0] context stream -> front stream, [1] front stream -> context stream
+    ~ps_ctx() { (void)hipSetDevice(device); if (stream.s) (void)hipStreamSynchronize(stream.s); }
     std::string err;
     int64_t tile_len = 0, halo = 0;
     int mode = MODE_FAST, spine_nt = 512, tree_nt = 256;
@@ -109,7 +139,6 @@ struct ps_ctx {
     int wide_mode = 0;        // ... 2 = block-sum scan on the 64-bit digest, 0 = LDS-window scan
     int tree_mw = 0;          // 1: block-sum tree kernel with TREE_W waves per workgroup sharing their job list (round 3: single-wave workgroups are faster at four waves per SIMD and need no spills)
     int upload_by_kernel = 1; // 1: the call's host tables are fetched by a kernel (no SDMA hand-over), 0: hipMemcpyAsync
-    int filter_fused = 1;     // 1: fast filters run both directions in one kernel over tiles with halos, 0: always the exact three-pass scan
     int k0_waves = 0;         // > 0: K0 runs as a persistent kernel, this many waves per SIMD (twice that for int16 samples) striding over the call with
                               // their next wave block's samples in flight (round 5) -- what a context that shares the chip wants (engine.StreamPool
                               // sets 1: 0.193 -> 0.170 ms per step with sixteen calls in flight); 0: one wave per wave block, as many as the registers
@@ -139,7 +168,6 @@ struct ps_ctx {
                               // ask for it are serialised there, back to back, and the context's own stream takes over behind an event.  K0 is the
                               // one kernel of a call that is bound by HBM; several of them at once only share the same bytes per second while the
                               // scan kernels behind each of them wait -- in a row, call i's scans run under call i+1's K0.  engine.StreamPool sets it.
-    hipEvent_t ev_front[2] = {};   // hand-over events (no timing): [0] context stream -> front stream, [1] front stream -> context stream
     bool stream_idle = true;  // the context's stream had nothing queued when the current call began (no hand-over to the front stream needed)
     int tree_par = 1;         // 1: subtree jobs on the 64-bit digest (filtered events: deep recursions) are shared by the waves of a workgroup (tree_par_kernel), 0: one wave per job
     int groups = 1;           // 1: K0 writes group records and the window scans start with the coarse pass over them (narrow digest), 0: every row is swept
@@ -167,33 +195,46 @@ struct ps_ctx {
         std::vector<int64_t> ev_start, ev_len;
         size_t nj = 0, jb = 0, up_bytes = 0; int64_t list_entries = 0, total_len = 0, sample_end = 0, nb_total = 0;
     } tile_cache;
-    DevBuf bsum, ev_info, chunk_mabs, ev_boff, blk_mm, grp, filt_fwd, filt_agg, filt_zin, up_dev;
-    DevBuf align_in, align_scratch;
-    DevBuf pw_in, pw_scratch; // pairwise aligner (ps_pairwise_scores / ps_pairwise_batch): offsets and pair tables, per-workgroup matrices
-    long long pw_budget = 2ll << 30;         // option pairwise_budget: bytes of pairwise scratch per launch
+    DevBuf bsum, ev_info, chunk_mabs, ev_boff, blk_mm, grp, up_dev;
+    // The segmentation chain's own buffers and options are flat members.  The state of every self-contained feature stands
+    // together in a sub-struct (filt, align, pw, ss, nt, hmm): its buffers, its budgets, its host-side caches.  A new feature
+    // adds its group here and nowhere else: the buffers free themselves with the context.
+    struct {                // Bessel filter (ps_filter_bessel, ps_filter_requantise_batch)
+        DevBuf fwd, agg, zin;
+        int fused = 1;        // option filter_fused 1: fast filters run both directions in one kernel over tiles with halos, 0: always the exact three-pass scan
+    } filt;
+    struct { DevBuf in, scratch; } align;    // profile aligner (ps_align_batch)
+    struct {                  // pairwise aligner (ps_pairwise_scores / ps_pairwise_batch): offsets and pair tables, per-workgroup matrices
+        DevBuf in, scratch;
+        long long budget = 2ll << 30;        // option pairwise_budget: bytes of pairwise scratch per launch
+    } pw;
     DevBuf ev_info_tr;        // single-pass file route (ps_detect_segment_trace): (centre, phase, first block) of the events cut out of a trace-aligned digest
     DevBuf blk_cls, cls_mm;   // ... K0's verdict per block against the detector's threshold (2 bits), min / max per 128 blocks
     DevBuf pre_c;             // exact route (ps_segment_exact_f64): c and c2 of the call's samples, 16 B per sample
     // StatSplit (ps_statsplit_f64): per-event tables, prefix sums (c, c2, ct), boundary slots, interval stacks, counts +
     // status word, output offsets
-    DevBuf ss_tab, ss_pre, ss_tmp, ss_stack, ss_cnt, ss_off;
-    // Near-tie log of the segment calls (DevCfg::nt_log, ps_get_near_ties): nt_cap records (option near_tie_log, 0: off), allocated
-    // with the first call that logs.  nt_seen: records the last segment call counted (-1: not counted), nt_call_cap the capacity
-    // it ran with; nt_ev_start / nt_ev_len: its events, kept only when it logged any (the records are mapped to them on request).
-    DevBuf nt_log;
-    int64_t nt_cap = 65536, nt_hdr_cap = -1;   // (nt_hdr_cap: the capacity the header on the device names; -1: none written)
-    int64_t nt_seen = -1, nt_call_cap = 0;
-    std::vector<int64_t> nt_ev_start, nt_ev_len;
-    // HMM decoding (ps_hmm_batch): the model's last upload (host copy compared on every call), offsets, backpointers, results
-    DevBuf hmm_model, hmm_off, hmm_bp, hmm_last, hmm_flags;
-    std::vector<char> hmm_blob;
-    long long hmm_bp_budget = 512ll << 20;   // option hmm_bp_budget: bytes of Viterbi backpointers per launch
-    // Baum-Welch E-step (ps_hmm_expect): forward matrices of one launch, per-workgroup accumulator rows, the skipped count
-    DevBuf hmm_fmat, hmm_acc, hmm_skip;
-    DevBuf hmm_pmax;                         // ps_hmm_posterior: the per-observation maxima that d_map_logp sums
-    DevBuf hmm_samp;                         // ps_hmm_sample: the sampling tables, then the observation and path offsets
-    long long hmm_fb_budget = 4ll << 30;     // option hmm_fb_budget: bytes of forward matrices per launch
-    bool hmm_expect_lds = true;              // option hmm_expect_lds 0: the accumulator rows stay in global memory
+    struct { DevBuf tab, pre, tmp, stack, cnt, off; } ss;
+    // Near-tie log of the segment calls (DevCfg::nt_log, ps_get_near_ties): nt.cap records (option near_tie_log, 0: off), allocated
+    // with the first call that logs.  nt.seen: records the last segment call counted (-1: not counted), nt.call_cap the capacity
+    // it ran with; nt.ev_start / nt.ev_len: its events, kept only when it logged any (the records are mapped to them on request).
+    struct {
+        DevBuf log;
+        int64_t cap = 65536, hdr_cap = -1;     // (hdr_cap: the capacity the header on the device names; -1: none written)
+        int64_t seen = -1, call_cap = 0;
+        std::vector<int64_t> ev_start, ev_len;
+    } nt;
+    struct {
+        // HMM decoding (ps_hmm_batch): the model's last upload (host copy compared on every call), offsets, backpointers, results
+        DevBuf model, off, bp, last, flags;
+        std::vector<char> blob;
+        long long bp_budget = 512ll << 20;   // option hmm_bp_budget: bytes of Viterbi backpointers per launch
+        // Baum-Welch E-step (ps_hmm_expect): forward matrices of one launch, per-workgroup accumulator rows, the skipped count
+        DevBuf fmat, acc, skip;
+        DevBuf pmax;                         // ps_hmm_posterior: the per-observation maxima that d_map_logp sums
+        DevBuf samp;                         // ps_hmm_sample: the sampling tables, then the observation and path offsets
+        long long fb_budget = 4ll << 30;     // option hmm_fb_budget: bytes of forward matrices per launch
+        bool expect_lds = true;              // option hmm_expect_lds 0: the accumulator rows stay in global memory
+    } hmm;
     int stitch_host = 0;      // 1: host stitch with halo tiles (the fallback path) always
     DevBuf ev_len, det_counts, det_tics, det_cand;
     DevBuf bridges, bmeta, tile_i32, sp_off, spine_items, asm_hdr, ev_first_tile;
@@ -221,7 +262,6 @@ struct ps_ctx {
     DevBuf spine_jobs, spine_scratch, spine_dense, spine_meta, tree_jobs, tree_scratch, tree_spill, tree_defer, screen_acc,
         tree_counts, items, item_pos, first_item, ev_off, bounds_off, small;
     HostBuf h_meta, h_dense, h_small, h_up;
-    hipEvent_t ev[10] = {};   // [0..7] phase marks (timing level 2), [8] start and [9] end of the call's device work (level 1)
     int timing = 1;           // 0: no events, 1: start/end of the sequence, 2: an event between the phases as well (each costs
                               // ~6 us of idle GPU: the next kernel does not start back to back)
     double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -817,9 +857,9 @@ int finish_batch(ps_ctx *ctx, const DevCfg &cfg, size_t n_tj, int64_t n_items, i
     // by one fp64 scan and keep no margins (a caller that redoes near ties on the exact route redoes such a call)
     ctx->counters[11] = cfg.bsum ? static_cast<int64_t>(hs.stamp[0]) : -1;
     // ... and their records (ps_get_near_ties): the cursor came back with the status block
-    ctx->nt_seen = cfg.bsum && cfg.nt_log ? static_cast<int64_t>(hs.nt_cur) : -1;
+    ctx->nt.seen = cfg.bsum && cfg.nt_log ? static_cast<int64_t>(hs.nt_cur) : -1;
 #else
-    ctx->nt_seen = -1;                                 // (the stamps take counters[11]'s words: not counted)
+    ctx->nt.seen = -1;                                 // (the stamps take counters[11]'s words: not counted)
 #endif
     ctx->counters[14] = ctx->screen_ran ? static_cast<int64_t>(hs.tree_defer[2]) : -1;                         // subtree jobs the screen deferred
     ctx->counters[15] = ctx->screen_ran ? static_cast<int64_t>(hs.tree_defer[1]) : -1;                         // windows the screen decided
@@ -1425,9 +1465,10 @@ int k0_unaligned_probe(int device, hipStream_t st)
     ok = 0;
     unsigned char h[128];
     for (int i = 0; i < 128; ++i) h[i] = static_cast<unsigned char>(37 * i + 11);
-    unsigned char *d = nullptr;
-    unsigned *bad = nullptr;
-    if (hipMalloc(&d, 256) != hipSuccess || hipMalloc(&bad, sizeof(unsigned)) != hipSuccess) { if (d) (void)hipFree(d); (void)hipGetLastError(); return ok; }
+    DevBuf d_buf, bad_buf;
+    if (d_buf.reserve(256) != hipSuccess || bad_buf.reserve(sizeof(unsigned)) != hipSuccess) { (void)hipGetLastError(); return ok; }
+    unsigned char *d = d_buf.as<unsigned char>();
+    unsigned *bad = bad_buf.as<unsigned>();
     unsigned hb = 1;
     if (hipMemcpyAsync(d, h, 128, hipMemcpyHostToDevice, st) == hipSuccess && hipMemsetAsync(bad, 0, sizeof(unsigned), st) == hipSuccess) {
         hipLaunchKernelGGL(k0_unaligned_probe_kernel<2>, dim3(1), dim3(64), 0, st, d, 16, bad);     // int16: offsets 0, 2, .. 30 bytes
@@ -1436,7 +1477,7 @@ int k0_unaligned_probe(int device, hipStream_t st)
             hipStreamSynchronize(st) == hipSuccess)
             ok = hb == 0 ? 1 : 0;
     }
-    (void)hipFree(d); (void)hipFree(bad); (void)hipGetLastError();
+    d_buf.release(); bad_buf.release(); (void)hipGetLastError();
     return ok;
 }
 }  // namespace
@@ -1467,7 +1508,7 @@ void diag_env(ps_ctx *ctx)
     if (const char *e = std::getenv("PORESEG_WIDE_BS")) ctx->wide_bs = std::atoi(e) != 0;
     if (const char *e = std::getenv("PORESEG_BRIDGE_SINGLE")) ctx->bridge_single = std::max(1, std::atoi(e));
     if (const char *e = std::getenv("PORESEG_TREE_TAIL")) ctx->tree_tail_pct = std::max(0, std::min(100, std::atoi(e)));
-    if (const char *e = std::getenv("PORESEG_FILTER_FUSED")) ctx->filter_fused = std::atoi(e) != 0;
+    if (const char *e = std::getenv("PORESEG_FILTER_FUSED")) ctx->filt.fused = std::atoi(e) != 0;
     if (const char *e = std::getenv("PORESEG_UPLOAD")) ctx->upload_by_kernel = std::atoi(e) != 0;
     if (const char *e = std::getenv("PORESEG_TIMING")) ctx->timing = std::max(0, std::min(2, std::atoi(e)));
     if (const char *e = std::getenv("PORESEG_TREE_MW")) ctx->tree_mw = std::atoi(e) != 0;
@@ -1513,15 +1554,15 @@ int ps_create(int device, void *stream, ps_ctx **out)
     ps_ctx *ctx = new ps_ctx();
     ctx->device = device;
     if (stream) {
-        ctx->stream = static_cast<hipStream_t>(stream);
+        ctx->stream.s = static_cast<hipStream_t>(stream);
     } else {
-        if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) { delete ctx; return PS_ERR_HIP; }
-        ctx->own_stream = true;
+        if (hipStreamCreateWithFlags(&ctx->stream.s, hipStreamNonBlocking) != hipSuccess) { delete ctx; return PS_ERR_HIP; }
+        ctx->stream.own = true;
     }
     for (auto &e : ctx->ev)
-        if (hipEventCreate(&e) != hipSuccess) { delete ctx; return PS_ERR_HIP; }
+        if (hipEventCreate(&e.e) != hipSuccess) { delete ctx; return PS_ERR_HIP; }
     for (auto &e : ctx->ev_front)
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { delete ctx; return PS_ERR_HIP; }
+        if (hipEventCreateWithFlags(&e.e, hipEventDisableTiming) != hipSuccess) { delete ctx; return PS_ERR_HIP; }
     if (ctx->small.reserve(sizeof(SmallLayout) + SMALL_TAIL) != hipSuccess) { delete ctx; return PS_ERR_HIP; }
     ctx->lds_max_samples = (LDS_BYTES_MAX - 1024 * 8 - 256) / (static_cast<int>(sizeof(lds_t)) + 1);   // samples + block sums
     ctx->k0_unaligned = k0_unaligned_probe(device, ctx->stream);
@@ -1535,26 +1576,10 @@ int ps_create(int device, void *stream, ps_ctx **out)
 void ps_destroy(ps_ctx *ctx)
 {
     if (!ctx) return;
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
-    DevBuf *bufs[] = {&ctx->spine_jobs, &ctx->spine_scratch, &ctx->spine_dense, &ctx->spine_meta, &ctx->tree_jobs,
-                      &ctx->tree_scratch, &ctx->tree_spill, &ctx->tree_defer, &ctx->screen_acc, &ctx->tree_counts, &ctx->items, &ctx->item_pos,
-                      &ctx->first_item, &ctx->ev_off, &ctx->bounds_off, &ctx->small, &ctx->bridges, &ctx->bmeta,
-                      &ctx->tile_i32, &ctx->sp_off, &ctx->spine_items, &ctx->asm_hdr, &ctx->ev_first_tile, &ctx->ev_len,
-                      &ctx->det_counts, &ctx->det_tics, &ctx->det_cand, &ctx->bsum, &ctx->ev_info, &ctx->chunk_mabs,
-                      &ctx->ev_boff, &ctx->blk_mm, &ctx->grp, &ctx->filt_fwd, &ctx->filt_agg, &ctx->filt_zin, &ctx->up_dev,
-                      &ctx->align_in, &ctx->align_scratch, &ctx->pw_in, &ctx->pw_scratch, &ctx->bridge_ext, &ctx->ext_slot, &ctx->ext_list,
-                      &ctx->lat_state, &ctx->lat_seam, &ctx->lat_res, &ctx->pre_c, &ctx->ev_info_tr, &ctx->blk_cls,
-                      &ctx->cls_mm, &ctx->nt_log, &ctx->hmm_model, &ctx->hmm_off, &ctx->hmm_bp,
-                      &ctx->hmm_last, &ctx->hmm_flags, &ctx->hmm_fmat, &ctx->hmm_acc, &ctx->hmm_skip, &ctx->hmm_pmax,
-                      &ctx->hmm_samp, &ctx->ss_tab, &ctx->ss_pre, &ctx->ss_tmp, &ctx->ss_stack, &ctx->ss_cnt, &ctx->ss_off};
-    for (DevBuf *b : bufs) b->release();
-    ctx->h_meta.release(); ctx->h_dense.release(); ctx->h_small.release(); ctx->h_up.release(); ctx->h_hdr.release();
-    for (auto &e : ctx->ev) if (e) (void)hipEventDestroy(e);
-    for (auto &e : ctx->ev_front) if (e) (void)hipEventDestroy(e);
-    if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
+
+int64_t ps_live_bytes(void) { return g_live_bytes.load(); }
 
 const char *ps_last_error(const ps_ctx *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
@@ -1600,7 +1625,7 @@ int ps_set_option(ps_ctx *ctx, const char *name, int64_t value)
     else if (n == "stitch_host") ctx->stitch_host = value != 0;
     else if (n == "prune") ctx->prune = value != 0;
     else if (n == "scan_bs") ctx->scan_bs = value != 0;
-    else if (n == "near_tie_log" && value >= 0 && value <= (int64_t(1) << 30)) ctx->nt_cap = value;
+    else if (n == "near_tie_log" && value >= 0 && value <= (int64_t(1) << 30)) ctx->nt.cap = value;
     else if (n == "groups") ctx->groups = value != 0;
     else if (n == "tree_par") ctx->tree_par = value != 0;
     else if (n == "k0_waves" && value >= 0 && value <= 16) ctx->k0_waves = static_cast<int>(value);
@@ -1622,10 +1647,10 @@ int ps_set_option(ps_ctx *ctx, const char *name, int64_t value)
         ctx->lat_help = sh ? 0 : 1;
         ctx->k0_admit = value > 3 ? 3 : 0;
     }
-    else if (n == "hmm_bp_budget" && value >= 1) ctx->hmm_bp_budget = value;
-    else if (n == "hmm_fb_budget" && value >= 1) ctx->hmm_fb_budget = value;
-    else if (n == "pairwise_budget" && value >= 1) ctx->pw_budget = value;
-    else if (n == "hmm_expect_lds") ctx->hmm_expect_lds = value != 0;
+    else if (n == "hmm_bp_budget" && value >= 1) ctx->hmm.bp_budget = value;
+    else if (n == "hmm_fb_budget" && value >= 1) ctx->hmm.fb_budget = value;
+    else if (n == "pairwise_budget" && value >= 1) ctx->pw.budget = value;
+    else if (n == "hmm_expect_lds") ctx->hmm.expect_lds = value != 0;
     else if (n == "single_pass") ctx->single_pass = value != 0;
     else if (n == "gather_fused") ctx->gather_fused = value != 0;
     else if (n == "download_by_kernel") ctx->download_by_kernel = value != 0;
@@ -1650,8 +1675,8 @@ int ps_set_option(ps_ctx *ctx, const char *name, int64_t value)
     else if (n == "dbg_phase" && value >= 0 && value <= 2) ctx->dbg_phase = static_cast<int>(value);
     else if (n == "dbg_k0_nogrp") ctx->dbg_k0_nogrp = value != 0;
     // cu_mask: value = first | count << 12 | stride << 24 | invert << 32: the context's OWN stream on those CUs only (count 0: all)
-    else if (n == "cu_mask" && ctx->own_stream)
-        return diag_mask_stream(ctx, &ctx->stream, static_cast<int>(value & 0xfff), static_cast<int>((value >> 12) & 0xfff),
+    else if (n == "cu_mask" && ctx->stream.own)
+        return diag_mask_stream(ctx, &ctx->stream.s, static_cast<int>(value & 0xfff), static_cast<int>((value >> 12) & 0xfff),
                                 static_cast<int>((value >> 24) & 0xff), ((value >> 32) & 1) != 0);
     else if (n == "k0_sets" && value >= 2 && value <= 4) ctx->k0_sets = static_cast<int>(value);
     else if (n == "scan_lds_pad" && value >= 0 && value <= 65536) ctx->scan_lds_pad = static_cast<int>(value);
@@ -1663,7 +1688,7 @@ int ps_set_option(ps_ctx *ctx, const char *name, int64_t value)
     else if (n == "wide_bs") { ctx->wide_bs = value != 0; ctx->wide_skip = 0; }
     else if (n == "bridge_single" && value >= 1) ctx->bridge_single = static_cast<int>(value);
     else if (n == "tree_tail_pct" && value >= 0 && value <= 100) ctx->tree_tail_pct = static_cast<int>(value);
-    else if (n == "filter_fused") ctx->filter_fused = value != 0;
+    else if (n == "filter_fused") ctx->filt.fused = value != 0;
     else if (n == "upload_by_kernel") ctx->upload_by_kernel = value != 0;
     else if (n == "timing") ctx->timing = static_cast<int>(std::max<int64_t>(0, std::min<int64_t>(2, value)));
     else if (n == "tree_mw") ctx->tree_mw = value != 0;
@@ -1760,9 +1785,9 @@ int ps_segment_exact_f64(ps_ctx *ctx, const double *d_current, const int64_t *h_
 // event (pre[e]); returns the launch-ready view of them.
 static int statsplit_upload(ps_ctx *ctx, const std::vector<int64_t> &tab, int32_t n_ev, SsEvents *ev)
 {
-    HIP_TRY(ctx, ctx->ss_tab.reserve(tab.size() * sizeof(int64_t)));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->ss_tab.p, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    const int64_t *t = ctx->ss_tab.as<int64_t>();
+    HIP_TRY(ctx, ctx->ss.tab.reserve(tab.size() * sizeof(int64_t)));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->ss.tab.p, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    const int64_t *t = ctx->ss.tab.as<int64_t>();
     const size_t n = static_cast<size_t>(n_ev);
     ev->start = t; ev->len = t + n; ev->pre = t + 2 * n; ev->lo = t + 3 * n; ev->hi = t + 4 * n; ev->slot = t + 5 * n;
     ev->n_ev = n_ev;
@@ -1813,17 +1838,17 @@ int ps_statsplit_f64(ps_ctx *ctx, const double *d_current, const int64_t *h_ev_s
     int rc = statsplit_upload(ctx, tab, n_ev, &ev);
     if (rc) return rc;
     const size_t pre_n = static_cast<size_t>(std::max<int64_t>(1, total_len));
-    HIP_TRY(ctx, ctx->ss_pre.reserve((slanted ? 3 : 2) * pre_n * sizeof(double)));
-    HIP_TRY(ctx, ctx->ss_tmp.reserve(static_cast<size_t>(slots) * sizeof(int32_t)));
-    HIP_TRY(ctx, ctx->ss_stack.reserve(static_cast<size_t>(n_wg) * static_cast<size_t>(stack_cap) * sizeof(SsFrame)));
-    HIP_TRY(ctx, ctx->ss_cnt.reserve((n + 2) * sizeof(int32_t)));     // counts, then the status word
+    HIP_TRY(ctx, ctx->ss.pre.reserve((slanted ? 3 : 2) * pre_n * sizeof(double)));
+    HIP_TRY(ctx, ctx->ss.tmp.reserve(static_cast<size_t>(slots) * sizeof(int32_t)));
+    HIP_TRY(ctx, ctx->ss.stack.reserve(static_cast<size_t>(n_wg) * static_cast<size_t>(stack_cap) * sizeof(SsFrame)));
+    HIP_TRY(ctx, ctx->ss.cnt.reserve((n + 2) * sizeof(int32_t)));     // counts, then the status word
     SsCfg cfg;
-    cfg.C = ctx->ss_pre.as<double>(); cfg.C2 = cfg.C + pre_n; cfg.Ct = slanted ? cfg.C2 + pre_n : nullptr;
+    cfg.C = ctx->ss.pre.as<double>(); cfg.C2 = cfg.C + pre_n; cfg.Ct = slanted ? cfg.C2 + pre_n : nullptr;
     cfg.mw = static_cast<int>(mw); cfg.maxw = static_cast<int>(maxw); cfg.W = static_cast<int>(W);
     cfg.thresh = params->threshold;
-    cfg.stack = ctx->ss_stack.as<SsFrame>(); cfg.stack_cap = stack_cap;
-    cfg.tmp = ctx->ss_tmp.as<int32_t>();
-    cfg.count = ctx->ss_cnt.as<int32_t>();
+    cfg.stack = ctx->ss.stack.as<SsFrame>(); cfg.stack_cap = stack_cap;
+    cfg.tmp = ctx->ss.tmp.as<int32_t>();
+    cfg.count = ctx->ss.cnt.as<int32_t>();
     cfg.status = reinterpret_cast<unsigned *>(cfg.count + n);
     HIP_TRY(ctx, hipMemsetAsync(cfg.status, 0, sizeof(unsigned), ctx->stream));
     hipLaunchKernelGGL(statsplit_prefix_kernel, dim3(static_cast<unsigned>(std::min<int64_t>(n_ev, 65535))), dim3(64), 0, ctx->stream,
@@ -1848,10 +1873,10 @@ int ps_statsplit_f64(ps_ctx *ctx, const double *d_current, const int64_t *h_ev_s
     if (total > cap)
         return fail(ctx, PS_ERR_CAPACITY, "bounds capacity %lld < required %lld", static_cast<long long>(cap), static_cast<long long>(total));
     if (total == 0) return PS_OK;
-    HIP_TRY(ctx, ctx->ss_off.reserve((n + 1) * sizeof(int64_t)));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->ss_off.p, h_bounds_off, (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, ctx->ss.off.reserve((n + 1) * sizeof(int64_t)));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->ss.off.p, h_bounds_off, (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(statsplit_gather_kernel, dim3(static_cast<unsigned>(std::min<int64_t>(n_ev, 4096))), dim3(256), 0, ctx->stream,
-                       cfg.tmp, ev.slot, ctx->ss_off.as<int64_t>(), n_ev, d_bounds);
+                       cfg.tmp, ev.slot, ctx->ss.off.as<int64_t>(), n_ev, d_bounds);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return PS_OK;
@@ -1909,36 +1934,36 @@ static int begin_segment_call(ps_ctx *ctx, const void *d_samples, const ps_sampl
 // Near-tie log (ps_get_near_ties): every segment call starts with "not counted" and no events of its own ...
 static void nt_reset(ps_ctx *ctx)
 {
-    ctx->nt_seen = -1;
-    ctx->nt_call_cap = ctx->nt_cap;
-    ctx->nt_ev_start.clear();
-    ctx->nt_ev_len.clear();
+    ctx->nt.seen = -1;
+    ctx->nt.call_cap = ctx->nt.cap;
+    ctx->nt.ev_start.clear();
+    ctx->nt.ev_len.clear();
 }
 
 // ... points the call's configuration at the log (block-sum scan only: the LDS-window kernels keep no margins) ...
 static int nt_arm(ps_ctx *ctx, DevCfg &cfg)
 {
-    if (ctx->nt_call_cap <= 0) return PS_OK;
-    const void *before = ctx->nt_log.p;
-    HIP_TRY(ctx, ctx->nt_log.reserve(offsetof(NtLog, rec) + static_cast<size_t>(ctx->nt_call_cap) * sizeof(NtRec)));
-    if (ctx->nt_log.p != before || ctx->nt_hdr_cap != ctx->nt_call_cap) {       // (a new buffer or a new capacity: once, not per call)
+    if (ctx->nt.call_cap <= 0) return PS_OK;
+    const void *before = ctx->nt.log.p;
+    HIP_TRY(ctx, ctx->nt.log.reserve(offsetof(NtLog, rec) + static_cast<size_t>(ctx->nt.call_cap) * sizeof(NtRec)));
+    if (ctx->nt.log.p != before || ctx->nt.hdr_cap != ctx->nt.call_cap) {       // (a new buffer or a new capacity: once, not per call)
         NtLog h = {};
         h.cur = &ctx->small.as<SmallLayout>()->nt_cur;
-        h.cap = ctx->nt_call_cap;
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->nt_log.p, &h, offsetof(NtLog, rec), hipMemcpyHostToDevice, ctx->stream));
+        h.cap = ctx->nt.call_cap;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->nt.log.p, &h, offsetof(NtLog, rec), hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->nt_hdr_cap = ctx->nt_call_cap;
+        ctx->nt.hdr_cap = ctx->nt.call_cap;
     }
-    cfg.nt_log = ctx->nt_log.as<NtLog>();
+    cfg.nt_log = ctx->nt.log.as<NtLog>();
     return PS_OK;
 }
 
-// ... and keeps its events when it logged anything (finish_batch set nt_seen from the cursor): the records are mapped on request
+// ... and keeps its events when it logged anything (finish_batch set nt.seen from the cursor): the records are mapped on request
 static void nt_keep(ps_ctx *ctx, const int64_t *ev_start, const int64_t *ev_len, int32_t n_ev)
 {
-    if (ctx->nt_seen <= 0 || ctx->nt_seen > ctx->nt_call_cap) return;
-    ctx->nt_ev_start.assign(ev_start, ev_start + n_ev);
-    ctx->nt_ev_len.assign(ev_len, ev_len + n_ev);
+    if (ctx->nt.seen <= 0 || ctx->nt.seen > ctx->nt.call_cap) return;
+    ctx->nt.ev_start.assign(ev_start, ev_start + n_ev);
+    ctx->nt.ev_len.assign(ev_len, ev_len + n_ev);
 }
 
 static int segment_events_body(ps_ctx *ctx, const void *d_samples, const ps_sample_format *fmt,
@@ -2167,9 +2192,9 @@ static int segment_events_impl(ps_ctx *ctx, const void *d_samples, const ps_samp
     nt_reset(ctx);
     const int rc = segment_events_body(ctx, d_samples, fmt, ev_start, ev_len, n_ev, params, d_bounds, cap, h_bounds_off, d_stats,
                                        d_is_spine, d_f64);
-    if (rc == PS_OK && n_ev == 0) ctx->nt_seen = 0;           // (no event, no window: none -- as ps_detect_segment_trace says)
+    if (rc == PS_OK && n_ev == 0) ctx->nt.seen = 0;           // (no event, no window: none -- as ps_detect_segment_trace says)
     else if (rc == PS_OK) nt_keep(ctx, ev_start, ev_len, n_ev);
-    else ctx->nt_seen = -1;
+    else ctx->nt.seen = -1;
     return rc;
 }
 
@@ -2441,7 +2466,7 @@ int ps_detect_segment_trace(ps_ctx *ctx, const void *d_samples, const ps_sample_
         return fail(ctx, PS_ERR_ARG, "bad argument");
     *n_events_out = 0;
     h_bounds_off[0] = 0;
-    if (n == 0) { ctx->nt_seen = 0; return PS_OK; }
+    if (n == 0) { ctx->nt.seen = 0; return PS_OK; }
     if (!d_samples) return fail(ctx, PS_ERR_ARG, "d_samples is NULL");
     SegCall call;
     int rc = begin_segment_call(ctx, d_samples, fmt, params, nullptr, nullptr, 0, &call);
@@ -2512,7 +2537,7 @@ int ps_detect_segment_trace(ps_ctx *ctx, const void *d_samples, const ps_sample_
     rc = events_from_edges(ctx, cfg, n, tics, threshold, min_duration, min_current, h_starts, h_lengths, ev_cap, n_events_out);
     if (rc) return rc;
     const int32_t n_ev = static_cast<int32_t>(*n_events_out);
-    if (n_ev == 0) { ctx->nt_seen = 0; return PS_OK; }    // (no event, no window: none)
+    if (n_ev == 0) { ctx->nt.seen = 0; return PS_OK; }    // (no event, no window: none)
     for (int e = 0; e < n_ev; ++e)
         if (h_lengths[e] > 0x7fffffff - 2LL * W - 16) return fail(ctx, PS_ERR_ARG, "event %d length %lld out of range", e, static_cast<long long>(h_lengths[e]));
     // ---- every event from the trace's digest ----------------------------------------------------------------------------------
@@ -2523,25 +2548,25 @@ int ps_detect_segment_trace(ps_ctx *ctx, const void *d_samples, const ps_sample_
         return ps_segment_events(ctx, d_samples, fmt, h_starts, h_lengths, n_ev, params, d_bounds, cap, h_bounds_off, d_stats, nullptr);
     }
     if (rc == PS_OK) nt_keep(ctx, h_starts, h_lengths, n_ev);
-    else ctx->nt_seen = -1;
+    else ctx->nt.seen = -1;
     return rc;
 }
 
 int ps_get_near_ties(const ps_ctx *ctx, ps_near_tie *out, int32_t cap, int64_t *n_out)
 {
     if (!ctx || !n_out || cap < 0 || (cap > 0 && !out)) return PS_ERR_ARG;
-    if (ctx->nt_seen < 0) { *n_out = PS_NT_NOT_COUNTED; return PS_OK; }
-    if (ctx->nt_seen > ctx->nt_call_cap) { *n_out = PS_NT_INCOMPLETE; return PS_OK; }
-    if (ctx->nt_seen == 0) { *n_out = 0; return PS_OK; }
-    std::vector<NtRec> rec(static_cast<size_t>(ctx->nt_seen));
+    if (ctx->nt.seen < 0) { *n_out = PS_NT_NOT_COUNTED; return PS_OK; }
+    if (ctx->nt.seen > ctx->nt.call_cap) { *n_out = PS_NT_INCOMPLETE; return PS_OK; }
+    if (ctx->nt.seen == 0) { *n_out = 0; return PS_OK; }
+    std::vector<NtRec> rec(static_cast<size_t>(ctx->nt.seen));
     if (hipSetDevice(ctx->device) != hipSuccess ||
-        hipMemcpyAsync(rec.data(), static_cast<const char *>(ctx->nt_log.p) + offsetof(NtLog, rec), rec.size() * sizeof(NtRec), hipMemcpyDeviceToHost,
+        hipMemcpyAsync(rec.data(), static_cast<const char *>(ctx->nt.log.p) + offsetof(NtLog, rec), rec.size() * sizeof(NtRec), hipMemcpyDeviceToHost,
                        ctx->stream) != hipSuccess ||
         hipStreamSynchronize(ctx->stream) != hipSuccess) { (void)hipGetLastError(); return PS_ERR_HIP; }
     // each record to every event that holds its window (events may overlap in ps_segment_events): events by start, the
     // largest end so far, walked back from the last event that starts at or before the window
-    const int64_t *st = ctx->nt_ev_start.data(), *ln = ctx->nt_ev_len.data();
-    const size_t ne = ctx->nt_ev_start.size();
+    const int64_t *st = ctx->nt.ev_start.data(), *ln = ctx->nt.ev_len.data();
+    const size_t ne = ctx->nt.ev_start.size();
     std::vector<int32_t> ord(ne);
     for (size_t e = 0; e < ne; ++e) ord[e] = static_cast<int32_t>(e);
     std::stable_sort(ord.begin(), ord.end(), [&](int32_t a, int32_t b) { return st[a] < st[b]; });
@@ -2685,14 +2710,14 @@ int filter_order_n(ps_ctx *ctx, const DevCfg &cfg, int64_t n, int order, double 
     if (!H) return fail(ctx, PS_ERR_ARG, "a Bessel filter of order %d this slow (cutoff / Nyquist = %g) does not run on the device", order, wn);
     const int S = std::max(1024, 4 * H);
     const int64_t m = n + 2LL * f.pad, nseg = (m + S - 1) / S;
-    HIP_TRY(ctx, ctx->filt_fwd.reserve(static_cast<size_t>(nseg) * static_cast<size_t>(S + H) * sizeof(double)));
+    HIP_TRY(ctx, ctx->filt.fwd.reserve(static_cast<size_t>(nseg) * static_cast<size_t>(S + H) * sizeof(double)));
     HIP_TRY(ctx, ctx->h_small.reserve(sizeof(SmallLayout)));
     if (!ctx->defer_sync) HIP_TRY(ctx, hipMemsetAsync(ctx->small.p, 0, sizeof(SmallLayout), ctx->stream));
     unsigned *st = reinterpret_cast<unsigned *>(&ctx->small.as<SmallLayout>()->status);
     const dim3 grid(static_cast<unsigned>((nseg + 63) / 64));
-    if (cfg.dtype == PS_DTYPE_F32)      hipLaunchKernelGGL((filt_halo_kernel<PS_DTYPE_F32>), grid, dim3(64), 0, ctx->stream, cfg, f, n, S, H, ctx->filt_fwd.as<double>(), d_out, st);
-    else if (cfg.dtype == PS_DTYPE_F64) hipLaunchKernelGGL((filt_halo_kernel<PS_DTYPE_F64>), grid, dim3(64), 0, ctx->stream, cfg, f, n, S, H, ctx->filt_fwd.as<double>(), d_out, st);
-    else                                hipLaunchKernelGGL((filt_halo_kernel<PS_DTYPE_I16>), grid, dim3(64), 0, ctx->stream, cfg, f, n, S, H, ctx->filt_fwd.as<double>(), d_out, st);
+    if (cfg.dtype == PS_DTYPE_F32)      hipLaunchKernelGGL((filt_halo_kernel<PS_DTYPE_F32>), grid, dim3(64), 0, ctx->stream, cfg, f, n, S, H, ctx->filt.fwd.as<double>(), d_out, st);
+    else if (cfg.dtype == PS_DTYPE_F64) hipLaunchKernelGGL((filt_halo_kernel<PS_DTYPE_F64>), grid, dim3(64), 0, ctx->stream, cfg, f, n, S, H, ctx->filt.fwd.as<double>(), d_out, st);
+    else                                hipLaunchKernelGGL((filt_halo_kernel<PS_DTYPE_I16>), grid, dim3(64), 0, ctx->stream, cfg, f, n, S, H, ctx->filt.fwd.as<double>(), d_out, st);
     HIP_TRY(ctx, hipGetLastError());
     if (ctx->defer_sync) return PS_OK;                   // (a batch: one status check for all of its events)
     HIP_TRY(ctx, hipMemcpyAsync(ctx->h_small.p, ctx->small.p, sizeof(SmallLayout), hipMemcpyDeviceToHost, ctx->stream));
@@ -2736,7 +2761,7 @@ int ps_filter_bessel(ps_ctx *ctx, const void *d_samples, const ps_sample_format 
     g.n = n; g.total = n + 2 * FILT_PAD;
     // Fast filters (the state forgets within a halo of <= 1024 samples): both directions in one kernel over tiles
     // with halos.  alpha^H <= 2^-60.
-    if (ctx->filter_fused && f.alpha > 0.0 && f.alpha < 1.0) {
+    if (ctx->filt.fused && f.alpha > 0.0 && f.alpha < 1.0) {
         const double h_req = std::ceil(60.0 * std::log(2.0) / -std::log(f.alpha));
         const int H = h_req <= 1024.0 ? std::max(64, (static_cast<int>(h_req) + 63) / 64 * 64) : 0;   // a multiple of 64, at most 1024
         if (H) {
@@ -2759,16 +2784,16 @@ int ps_filter_bessel(ps_ctx *ctx, const void *d_samples, const ps_sample_format 
     const int64_t n_chunks = (g.total + FILT_CHUNK - 1) / FILT_CHUNK;
     g.padded = n_chunks * FILT_CHUNK;                  // the intermediate is stored behind a lead-in (seg_filter.hpp)
     g.lead = g.padded - g.total;
-    HIP_TRY(ctx, ctx->filt_fwd.reserve(static_cast<size_t>(g.padded) * sizeof(double)));
-    HIP_TRY(ctx, ctx->filt_agg.reserve(static_cast<size_t>(n_chunks) * 2 * sizeof(double2)));
-    HIP_TRY(ctx, ctx->filt_zin.reserve(static_cast<size_t>(n_chunks) * sizeof(double)));
+    HIP_TRY(ctx, ctx->filt.fwd.reserve(static_cast<size_t>(g.padded) * sizeof(double)));
+    HIP_TRY(ctx, ctx->filt.agg.reserve(static_cast<size_t>(n_chunks) * 2 * sizeof(double2)));
+    HIP_TRY(ctx, ctx->filt.zin.reserve(static_cast<size_t>(n_chunks) * sizeof(double)));
     HIP_TRY(ctx, ctx->h_small.reserve(sizeof(SmallLayout)));
     if (!ctx->defer_sync) HIP_TRY(ctx, hipMemsetAsync(ctx->small.p, 0, sizeof(SmallLayout), ctx->stream));
     SmallLayout *sm = ctx->small.as<SmallLayout>();
     unsigned *st = reinterpret_cast<unsigned *>(&sm->status);
-    double *fwd = ctx->filt_fwd.as<double>();
-    double2 *agg = ctx->filt_agg.as<double2>(), *agg_b = agg + n_chunks;
-    double *zin = ctx->filt_zin.as<double>();
+    double *fwd = ctx->filt.fwd.as<double>();
+    double2 *agg = ctx->filt.agg.as<double2>(), *agg_b = agg + n_chunks;
+    double *zin = ctx->filt.zin.as<double>();
     const dim3 grid(static_cast<unsigned>(n_chunks));
 #define PS_FILT(DT)                                                                                                          \
     hipLaunchKernelGGL((filt_local_kernel<DT>), grid, dim3(FILT_NT), 0, ctx->stream, cfg, f, g, agg, st);                     \
@@ -2791,11 +2816,11 @@ int ps_requantise(ps_ctx *ctx, const double *d_in, int64_t n, float *d_out, doub
     if (!d_in || !d_out || !centre_out || !step_out || n < 1) return fail(ctx, PS_ERR_ARG, "null pointer or empty input");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const unsigned grid = static_cast<unsigned>(std::min<int64_t>(1024, (n + 8 * RQ_NT - 1) / (8 * RQ_NT)));
-    HIP_TRY(ctx, ctx->filt_agg.reserve(static_cast<size_t>(grid) * 3 * sizeof(double)));
+    HIP_TRY(ctx, ctx->filt.agg.reserve(static_cast<size_t>(grid) * 3 * sizeof(double)));
     HIP_TRY(ctx, ctx->h_meta.reserve(static_cast<size_t>(grid) * 3 * sizeof(double)));
-    hipLaunchKernelGGL(requant_stats_kernel, dim3(grid), dim3(RQ_NT), 0, ctx->stream, d_in, static_cast<long long>(n), ctx->filt_agg.as<double>());
+    hipLaunchKernelGGL(requant_stats_kernel, dim3(grid), dim3(RQ_NT), 0, ctx->stream, d_in, static_cast<long long>(n), ctx->filt.agg.as<double>());
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_meta.p, ctx->filt_agg.p, static_cast<size_t>(grid) * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_meta.p, ctx->filt.agg.p, static_cast<size_t>(grid) * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const double *part = ctx->h_meta.as<double>();
     double sum = 0.0, mn = INFINITY, mx = -INFINITY;
@@ -2829,12 +2854,12 @@ int ps_grid_check_f64(ps_ctx *ctx, const double *d_in, int64_t n, double origin,
     if (int rc = ingest_args(ctx, d_in, n)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const unsigned grid = ingest_grid(n);
-    HIP_TRY(ctx, ctx->filt_agg.reserve(static_cast<size_t>(grid) * sizeof(GridPartial)));
+    HIP_TRY(ctx, ctx->filt.agg.reserve(static_cast<size_t>(grid) * sizeof(GridPartial)));
     HIP_TRY(ctx, ctx->h_meta.reserve(static_cast<size_t>(grid) * sizeof(GridPartial)));
     hipLaunchKernelGGL(grid_check_kernel, dim3(grid), dim3(ING_NT), 0, ctx->stream, ingest_span(d_in, n), static_cast<long long>(n), d_in,
-                       origin, quantum, tol, ctx->filt_agg.as<GridPartial>());
+                       origin, quantum, tol, ctx->filt.agg.as<GridPartial>());
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_meta.p, ctx->filt_agg.p, static_cast<size_t>(grid) * sizeof(GridPartial), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_meta.p, ctx->filt.agg.p, static_cast<size_t>(grid) * sizeof(GridPartial), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const GridPartial *part = ctx->h_meta.as<GridPartial>();
     ps_grid_report r = {0.0, INFINITY, INFINITY, -INFINITY, 0, 0};
@@ -2870,12 +2895,12 @@ int ps_narrow_f64(ps_ctx *ctx, const double *d_in, int64_t n, float *d_out, int6
     if (reinterpret_cast<uintptr_t>(d_out) & 3u) return fail(ctx, PS_ERR_ARG, "float32 samples must be 4-byte aligned");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const unsigned grid = ingest_grid(n);
-    HIP_TRY(ctx, ctx->filt_agg.reserve(static_cast<size_t>(grid) * sizeof(unsigned long long)));
+    HIP_TRY(ctx, ctx->filt.agg.reserve(static_cast<size_t>(grid) * sizeof(unsigned long long)));
     HIP_TRY(ctx, ctx->h_meta.reserve(static_cast<size_t>(grid) * sizeof(unsigned long long)));
     hipLaunchKernelGGL(narrow_f64_kernel, dim3(grid), dim3(ING_NT), 0, ctx->stream, ingest_span(d_in, n), static_cast<long long>(n), d_in, d_out,
-                       ctx->filt_agg.as<unsigned long long>());
+                       ctx->filt.agg.as<unsigned long long>());
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_meta.p, ctx->filt_agg.p, static_cast<size_t>(grid) * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_meta.p, ctx->filt.agg.p, static_cast<size_t>(grid) * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const unsigned long long *part = ctx->h_meta.as<unsigned long long>();
     unsigned long long bad = 0;
@@ -2924,13 +2949,13 @@ int ps_filter_requantise_batch(ps_ctx *ctx, const void *d_samples, const ps_samp
         poff[e + 1] = poff[e] + grid[e];
     }
     const size_t pbytes = poff[n_ev] * 3 * sizeof(double);
-    HIP_TRY(ctx, ctx->filt_agg.reserve(pbytes));         // (the filters above are done with it only in stream order: reserve() may
+    HIP_TRY(ctx, ctx->filt.agg.reserve(pbytes));         // (the filters above are done with it only in stream order: reserve() may
     HIP_TRY(ctx, ctx->h_meta.reserve(pbytes));           //  free and allocate, which waits for the device -- correct, and rare)
     for (int e = 0; e < n_ev; ++e)
         hipLaunchKernelGGL(requant_stats_kernel, dim3(grid[e]), dim3(RQ_NT), 0, ctx->stream, d_filtered + off[e], static_cast<long long>(ev_len[e]),
-                           ctx->filt_agg.as<double>() + 3 * poff[e]);
+                           ctx->filt.agg.as<double>() + 3 * poff[e]);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_meta.p, ctx->filt_agg.p, pbytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_meta.p, ctx->filt.agg.p, pbytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->h_small.p, ctx->small.p, sizeof(SmallLayout), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     rc = check_status(ctx, static_cast<unsigned>(ctx->h_small.as<SmallLayout>()->status));
@@ -3030,10 +3055,10 @@ int ps_align_batch(ps_ctx *ctx, const double *h_model_means, const double *h_mod
             h[5 * m + j] = h_model_durs[j];
         }
     };
-    if (int rc = upload_tables(ctx, ctx->align_in, static_cast<size_t>(6) * m * sizeof(double), model_rows,
+    if (int rc = upload_tables(ctx, ctx->align.in, static_cast<size_t>(6) * m * sizeof(double), model_rows,
                                {{h_seq_off, (static_cast<size_t>(n_seq) + 1) * sizeof(int64_t)}})) return rc;
     AlignModel M;
-    const double *dm = ctx->align_in.as<double>();
+    const double *dm = ctx->align.in.as<double>();
     M.mean = dm; M.std = dm + m; M.dsp = dm + 2 * m; M.dbp = dm + 3 * m; M.pen0 = dm + 4 * m; M.dur = dm + 5 * m;
     M.m = m; M.skip_pen = skip_penalty; M.back_pen = backslip_penalty;
     const long long *d_off = reinterpret_cast<const long long *>(dm + 6 * m);
@@ -3050,9 +3075,9 @@ int ps_align_batch(ps_ctx *ctx, const double *h_model_means, const double *h_mod
     if (per_wg * sizeof(double) > (32ull << 30)) return fail(ctx, PS_ERR_ARG, "a %lld x %d alignment needs more than 32 GiB of scratch", (long long)s_max, m);
     unsigned grid = std::min<unsigned>(static_cast<unsigned>(n_seq), resident_slots(ctx, align_kernel, ALIGN_NT, lds));
     grid = static_cast<unsigned>(std::max<unsigned long long>(1, std::min<unsigned long long>(grid, budget / (per_wg * sizeof(double)))));
-    HIP_TRY(ctx, ctx->align_scratch.reserve(static_cast<size_t>(grid) * per_wg * sizeof(double)));
+    HIP_TRY(ctx, ctx->align.scratch.reserve(static_cast<size_t>(grid) * per_wg * sizeof(double)));
     hipLaunchKernelGGL(align_kernel, dim3(grid), dim3(ALIGN_NT), lds, ctx->stream, M, d_seq_means, d_seq_stds, d_seq_durs,
-                       d_off, n_seq, ctx->align_scratch.as<double>(), static_cast<long long>(per_wg), B, d_scores, d_paths, d_status);
+                       d_off, n_seq, ctx->align.scratch.as<double>(), static_cast<long long>(per_wg), B, d_scores, d_paths, d_status);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return PS_OK;
@@ -3074,9 +3099,9 @@ int ps_pairwise_scores(ps_ctx *ctx, const double *d_a, const int64_t *h_a_off, i
     if (n_max > PW_N_MAX) return fail(ctx, PS_ERR_ARG, "a B sequence of %lld elements: the device pairwise aligner takes up to %d", (long long)n_max, PW_N_MAX);
     if ((h_a_off[n_a] > 0 && !d_a) || (h_b_off[n_b] > 0 && !d_b)) return fail(ctx, PS_ERR_ARG, "null sequence pointer");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (int rc = upload_tables(ctx, ctx->pw_in, {{h_a_off, (static_cast<size_t>(n_a) + 1) * sizeof(int64_t)},
+    if (int rc = upload_tables(ctx, ctx->pw.in, {{h_a_off, (static_cast<size_t>(n_a) + 1) * sizeof(int64_t)},
                                                   {h_b_off, (static_cast<size_t>(n_b) + 1) * sizeof(int64_t)}})) return rc;
-    const long long *da_off = ctx->pw_in.as<long long>(), *db_off = da_off + n_a + 1;
+    const long long *da_off = ctx->pw.in.as<long long>(), *db_off = da_off + n_a + 1;
     const int n_cap = static_cast<int>(std::max<int64_t>(n_max, 1));
     const size_t lds = pw_lds_bytes(n_cap);
     const long long jobs = static_cast<long long>(n_a) * n_b;
@@ -3125,11 +3150,11 @@ int ps_pairwise_batch(ps_ctx *ctx, const double *d_a, const int64_t *h_a_off, in
     // one upload: the four 8-byte tables, the two pair tables, the capacity flag
     const size_t na = static_cast<size_t>(n_a) + 1, nb = static_cast<size_t>(n_b) + 1, np = static_cast<size_t>(n_pairs);
     const int32_t no_flags[2] = {0, 0};
-    if (int rc = upload_tables(ctx, ctx->pw_in, {{h_a_off, na * 8}, {h_b_off, nb * 8}, {h_col_off, (np + 1) * 8}, {h_aln_off, (np + 1) * 8},
+    if (int rc = upload_tables(ctx, ctx->pw.in, {{h_a_off, na * 8}, {h_b_off, nb * 8}, {h_col_off, (np + 1) * 8}, {h_aln_off, (np + 1) * 8},
                                                   {h_pair_a, np * 4}, {h_pair_b, np * 4}, {no_flags, sizeof(no_flags)}})) return rc;
     PwBatch P;
     P.a = d_a; P.b = d_b;
-    P.a_off = ctx->pw_in.as<long long>(); P.b_off = P.a_off + na; P.col_off = P.b_off + nb; P.aln_off = P.col_off + np + 1;
+    P.a_off = ctx->pw.in.as<long long>(); P.b_off = P.a_off + na; P.col_off = P.b_off + nb; P.aln_off = P.col_off + np + 1;
     int *di = reinterpret_cast<int *>(const_cast<long long *>(P.aln_off + np + 1));
     P.pair_a = di; P.pair_b = di + np; P.flag = di + 2 * np;
     P.mode = mode; P.min_length = min_length; P.penalty = penalty;
@@ -3138,7 +3163,7 @@ int ps_pairwise_batch(ps_ctx *ctx, const double *d_a, const int64_t *h_a_off, in
     // Launches: consecutive pairs while the scratch of their launch -- one matrix of the launch's largest pair per workgroup,
     // a workgroup per pair up to the resident slots -- stays within the budget; a launch whose first pair alone leaves room
     // for few matrices runs on that many workgroups
-    const unsigned long long budget = static_cast<unsigned long long>(std::max<long long>(1, ctx->pw_budget));
+    const unsigned long long budget = static_cast<unsigned long long>(std::max<long long>(1, ctx->pw.budget));
     auto dims = [&](int32_t q, unsigned long long *cells, unsigned long long *rows, int *n) {
         const int64_t m = h_a_off[h_pair_a[q] + 1] - h_a_off[h_pair_a[q]];
         *n = static_cast<int>(h_b_off[h_pair_b[q] + 1] - h_b_off[h_pair_b[q]]);
@@ -3173,9 +3198,9 @@ int ps_pairwise_batch(ps_ctx *ctx, const double *d_a, const int64_t *h_a_off, in
             HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(kernel), static_cast<int>(lds)));
             unsigned grid = std::min<unsigned>(static_cast<unsigned>(nq), resident_slots(ctx, kernel, PW_NT, lds));
             grid = static_cast<unsigned>(std::max<unsigned long long>(1, std::min<unsigned long long>(grid, budget / per_wg)));
-            HIP_TRY(ctx, ctx->pw_scratch.reserve(static_cast<size_t>(grid) * per_wg));
+            HIP_TRY(ctx, ctx->pw.scratch.reserve(static_cast<size_t>(grid) * per_wg));
             if (ctx->debug) fprintf(stderr, "[poreseg] pairwise launch: pairs %d..%d, grid %u, %llu bytes of scratch per workgroup, dynamic LDS %zu\n", q0, q1, grid, per_wg, lds);
-            hipLaunchKernelGGL(kernel, dim3(grid), dim3(PW_NT), lds, ctx->stream, P, q0, nq, n_cap, ctx->pw_scratch.as<unsigned char>(),
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(PW_NT), lds, ctx->stream, P, q0, nq, n_cap, ctx->pw.scratch.as<unsigned char>(),
                                per_wg, cells, rows);
             return PS_OK;
         };
@@ -3346,13 +3371,13 @@ int hmm_upload(ps_ctx *ctx, const ps_hmm_model *m, HmmDevK *D, HmmDevV *V, HmmDe
         std::memcpy(bi + ni1, m->mix_ptr, (static_cast<size_t>(NE) + 1) * sizeof(int32_t));
         std::memcpy(bi + ni1 + NE + 1, m->mix_kind, static_cast<size_t>(NM) * sizeof(int32_t));
     }
-    if (blob != ctx->hmm_blob || !ctx->hmm_model.p) {
-        HIP_TRY(ctx, ctx->hmm_model.reserve(blob.size()));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->hmm_model.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
+    if (blob != ctx->hmm.blob || !ctx->hmm.model.p) {
+        HIP_TRY(ctx, ctx->hmm.model.reserve(blob.size()));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->hmm.model.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));       // (blob is a local: the copy completes before it goes)
-        ctx->hmm_blob.swap(blob);
+        ctx->hmm.blob.swap(blob);
     }
-    const double *dd = ctx->hmm_model.as<double>();
+    const double *dd = ctx->hmm.model.as<double>();
     const int32_t *di = reinterpret_cast<const int32_t *>(dd + nd);
     D->param = dd; D->in_lp = dd + 3 * S; D->out_lp = dd + 3 * S + n_edge[0];
     D->kind = di; D->level_ptr = di + S; D->in_ptr = D->level_ptr + NL + 1; D->out_ptr = D->in_ptr + S + 1;
@@ -3445,8 +3470,8 @@ int hmm_begin(ps_ctx *ctx, const ps_hmm_model *model, bool host_ok, const double
     if (n_seq == 0) return PS_OK;
     if (!d_logp || (h_off[n_seq] > 0 && !d_obs)) return fail(ctx, PS_ERR_ARG, "null device pointer");
     const size_t nb = (static_cast<size_t>(n_seq) + 1) * sizeof(int64_t);
-    if (int rc = upload_tables(ctx, ctx->hmm_off, {{h_off, nb}, {h_path_off, h_path_off ? nb : 0}})) return rc;
-    C->d_off = ctx->hmm_off.as<long long>();
+    if (int rc = upload_tables(ctx, ctx->hmm.off, {{h_off, nb}, {h_path_off, h_path_off ? nb : 0}})) return rc;
+    C->d_off = ctx->hmm.off.as<long long>();
     return PS_OK;
 }
 
@@ -3456,29 +3481,29 @@ int hmm_viterbi(ps_ctx *ctx, const MD &D, const double *d_obs, const int64_t *h_
 {
     const size_t S = static_cast<size_t>(D.S), lds = 2 * S * sizeof(double);
     const long long *d_path_off = d_off + n_seq + 1;
-    const long long budget = std::max<long long>(1, ctx->hmm_bp_budget);
+    const long long budget = std::max<long long>(1, ctx->hmm.bp_budget);
     HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_fwd_kernel<HMM_VITERBI, BP, MD>), static_cast<int>(lds)));
-    HIP_TRY(ctx, ctx->hmm_last.reserve(static_cast<size_t>(n_seq) * sizeof(int)));
-    HIP_TRY(ctx, ctx->hmm_flags.reserve(sizeof(int)));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->hmm_flags.p, 0, sizeof(int), ctx->stream));
+    HIP_TRY(ctx, ctx->hmm.last.reserve(static_cast<size_t>(n_seq) * sizeof(int)));
+    HIP_TRY(ctx, ctx->hmm.flags.reserve(sizeof(int)));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->hmm.flags.p, 0, sizeof(int), ctx->stream));
     for (int32_t q0 = 0, q1; q0 < n_seq; q0 = q1) {
         long long bytes;
         q1 = next_chunk(h_off, q0, n_seq, S * sizeof(BP), budget, &bytes);
         if (bytes > (8ll << 30)) return fail(ctx, PS_ERR_ARG, "sequence %d needs %lld bytes of backpointers (8 GiB at most)", q0, bytes);
-        HIP_TRY(ctx, ctx->hmm_bp.reserve(static_cast<size_t>(bytes)));
+        HIP_TRY(ctx, ctx->hmm.bp.reserve(static_cast<size_t>(bytes)));
         const long long bp_row0 = h_off[q0] + q0;
         const int nq = q1 - q0;
-        BP *bp = ctx->hmm_bp.as<BP>();
+        BP *bp = ctx->hmm.bp.as<BP>();
         hipLaunchKernelGGL((hmm_fwd_kernel<HMM_VITERBI, BP, MD>), dim3(nq), dim3(HMM_NT), lds, ctx->stream, D, d_obs, d_off, q0, d_logp,
-                           d_mat, 0ll, bp, bp_row0, ctx->hmm_last.as<int>());
+                           d_mat, 0ll, bp, bp_row0, ctx->hmm.last.as<int>());
         HIP_TRY(ctx, hipGetLastError());
         hipLaunchKernelGGL(hmm_trace_kernel<BP>, dim3((nq + HMM_NT - 1) / HMM_NT), dim3(HMM_NT), 0, ctx->stream, static_cast<HmmDev>(D), d_off, q0, nq,
-                           static_cast<const BP *>(bp), bp_row0, static_cast<const int *>(ctx->hmm_last.as<int>()),
-                           static_cast<const double *>(d_logp), d_path_off, d_path, d_path_len, ctx->hmm_flags.as<int>());
+                           static_cast<const BP *>(bp), bp_row0, static_cast<const int *>(ctx->hmm.last.as<int>()),
+                           static_cast<const double *>(d_logp), d_path_off, d_path, d_path_len, ctx->hmm.flags.as<int>());
         HIP_TRY(ctx, hipGetLastError());
     }
     int flags = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&flags, ctx->hmm_flags.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&flags, ctx->hmm.flags.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (flags & 2) return fail(ctx, PS_ERR_INTERNAL, "a Viterbi traceback left the model");
     if (flags & 1) return fail(ctx, PS_ERR_CAPACITY, "a Viterbi path is longer than its slot (d_path_len holds the lengths)");
@@ -3500,28 +3525,28 @@ int hmm_expect_run(ps_ctx *ctx, const MD &D, const double *d_obs, const int64_t 
     const size_t row_bytes = static_cast<size_t>(n_acc) * sizeof(double);
     unsigned G = std::min<unsigned>(static_cast<unsigned>(n_seq), resident_slots(ctx, (hmm_expect_kernel<ACC_LDS, MD>), HMM_NT, lds));
     G = static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>(G, HMM_EXPECT_ROWS / row_bytes)));
-    HIP_TRY(ctx, ctx->hmm_acc.reserve(G * row_bytes));
-    HIP_TRY(ctx, ctx->hmm_skip.reserve(sizeof(double)));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->hmm_acc.p, 0, G * row_bytes, ctx->stream));
-    const long long budget = std::max<long long>(1, ctx->hmm_fb_budget);
+    HIP_TRY(ctx, ctx->hmm.acc.reserve(G * row_bytes));
+    HIP_TRY(ctx, ctx->hmm.skip.reserve(sizeof(double)));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->hmm.acc.p, 0, G * row_bytes, ctx->stream));
+    const long long budget = std::max<long long>(1, ctx->hmm.fb_budget);
     for (int32_t q0 = 0, q1; q0 < n_seq; q0 = q1) {
         long long bytes;
         q1 = next_chunk(h_off, q0, n_seq, static_cast<size_t>(D.S) * sizeof(double), budget, &bytes);
         if (bytes > (16ll << 30)) return fail(ctx, PS_ERR_ARG, "sequence %d needs %lld bytes of forward matrix (16 GiB at most)", q0, bytes);
-        HIP_TRY(ctx, ctx->hmm_fmat.reserve(static_cast<size_t>(bytes)));
+        HIP_TRY(ctx, ctx->hmm.fmat.reserve(static_cast<size_t>(bytes)));
         const long long row0 = h_off[q0] + q0;
-        if (int rc = launch_forward(ctx, D, d_obs, d_off, q0, q1, d_logp, ctx->hmm_fmat.as<double>(), row0)) return rc;
+        if (int rc = launch_forward(ctx, D, d_obs, d_off, q0, q1, d_logp, ctx->hmm.fmat.as<double>(), row0)) return rc;
         hipLaunchKernelGGL((hmm_expect_kernel<ACC_LDS, MD>), dim3(G), dim3(HMM_NT), lds, ctx->stream, D, d_obs, d_off, q0, q1,
-                           static_cast<const double *>(d_logp), static_cast<const double *>(ctx->hmm_fmat.as<double>()), row0,
-                           ctx->hmm_acc.as<double>(), n_acc);
+                           static_cast<const double *>(d_logp), static_cast<const double *>(ctx->hmm.fmat.as<double>()), row0,
+                           ctx->hmm.acc.as<double>(), n_acc);
         HIP_TRY(ctx, hipGetLastError());
     }
     hipLaunchKernelGGL(hmm_expect_reduce_kernel, dim3((n_acc + 255) / 256), dim3(256), 0, ctx->stream,
-                       static_cast<const double *>(ctx->hmm_acc.as<double>()), static_cast<int>(G), n_acc, E, d_counts, d_stats,
-                       ctx->hmm_skip.as<double>());
+                       static_cast<const double *>(ctx->hmm.acc.as<double>()), static_cast<int>(G), n_acc, E, d_counts, d_stats,
+                       ctx->hmm.skip.as<double>());
     HIP_TRY(ctx, hipGetLastError());
     double skipped = 0.0;
-    HIP_TRY(ctx, hipMemcpyAsync(&skipped, ctx->hmm_skip.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&skipped, ctx->hmm.skip.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     *h_skipped = static_cast<int32_t>(skipped);
     return PS_OK;
@@ -3536,19 +3561,19 @@ int hmm_posterior_run(ps_ctx *ctx, const MD &D, const double *d_obs, const int64
 {
     const size_t lds = (2 * static_cast<size_t>(D.S) + (CNT == 2 ? static_cast<size_t>(E) : 0)) * sizeof(double);
     HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_posterior_kernel<CNT, MD>), static_cast<int>(lds)));
-    if (d_map_logp) HIP_TRY(ctx, ctx->hmm_pmax.reserve(std::max<size_t>(1, static_cast<size_t>(h_off[n_seq])) * sizeof(double)));
-    const long long budget = std::max<long long>(1, ctx->hmm_fb_budget);
+    if (d_map_logp) HIP_TRY(ctx, ctx->hmm.pmax.reserve(std::max<size_t>(1, static_cast<size_t>(h_off[n_seq])) * sizeof(double)));
+    const long long budget = std::max<long long>(1, ctx->hmm.fb_budget);
     for (int32_t q0 = 0, q1; q0 < n_seq; q0 = q1) {
         long long bytes;
         q1 = next_chunk(h_off, q0, n_seq, static_cast<size_t>(D.S) * sizeof(double), budget, &bytes);
         if (bytes > (16ll << 30)) return fail(ctx, PS_ERR_ARG, "sequence %d needs %lld bytes of forward matrix (16 GiB at most)", q0, bytes);
-        HIP_TRY(ctx, ctx->hmm_fmat.reserve(static_cast<size_t>(bytes)));
+        HIP_TRY(ctx, ctx->hmm.fmat.reserve(static_cast<size_t>(bytes)));
         const long long row0 = h_off[q0] + q0;
         if (ctx->debug) fprintf(stderr, "[poreseg] posterior launch: sequences %d..%d, %lld bytes of forward matrix, dynamic LDS %zu\n", q0, q1, bytes, lds);
-        if (int rc = launch_forward(ctx, D, d_obs, d_off, q0, q1, d_logp, ctx->hmm_fmat.as<double>(), row0)) return rc;
+        if (int rc = launch_forward(ctx, D, d_obs, d_off, q0, q1, d_logp, ctx->hmm.fmat.as<double>(), row0)) return rc;
         hipLaunchKernelGGL((hmm_posterior_kernel<CNT, MD>), dim3(q1 - q0), dim3(HMM_NT), lds, ctx->stream, D, d_obs, d_off, q0,
-                           static_cast<const double *>(d_logp), static_cast<const double *>(ctx->hmm_fmat.as<double>()), row0, d_post,
-                           d_map_state, d_map_logp, ctx->hmm_pmax.as<double>(), CNT ? d_counts_seq : nullptr);
+                           static_cast<const double *>(d_logp), static_cast<const double *>(ctx->hmm.fmat.as<double>()), row0, d_post,
+                           d_map_state, d_map_logp, ctx->hmm.pmax.as<double>(), CNT ? d_counts_seq : nullptr);
         HIP_TRY(ctx, hipGetLastError());
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -3617,7 +3642,7 @@ int ps_hmm_expect(ps_ctx *ctx, const ps_hmm_model *model, const double *d_obs, c
     if (!C.d_off) return PS_OK;
     const int E = C.E;
     const bool in_lds = (2 * static_cast<size_t>(C.DK.S) + static_cast<size_t>(n_acc)) * sizeof(double) <= HMM_EXPECT_LDS
-                        && ctx->hmm_expect_lds;
+                        && ctx->hmm.expect_lds;
     return with_model(C, [&](const auto &M) {
         return in_lds ? hmm_expect_run<true>(ctx, M, d_obs, h_off, C.d_off, n_seq, n_acc, E, d_logp, d_counts, d_stats, h_skipped)
                       : hmm_expect_run<false>(ctx, M, d_obs, h_off, C.d_off, n_seq, n_acc, E, d_logp, d_counts, d_stats, h_skipped);
@@ -3637,7 +3662,7 @@ int ps_hmm_posterior(ps_ctx *ctx, const ps_hmm_model *model, const double *d_obs
     const int E = C.E;
     // the counts row of a sequence: none asked for (or no edges), in LDS when it fits beside the score rows, else in place
     const int cnt = !d_counts_seq || E == 0 ? 0
-                    : (2 * static_cast<size_t>(C.DK.S) + static_cast<size_t>(E)) * sizeof(double) <= HMM_EXPECT_LDS && ctx->hmm_expect_lds ? 2 : 1;
+                    : (2 * static_cast<size_t>(C.DK.S) + static_cast<size_t>(E)) * sizeof(double) <= HMM_EXPECT_LDS && ctx->hmm.expect_lds ? 2 : 1;
     return with_model(C, [&](const auto &M) {
         switch (cnt) {
         case 0: return hmm_posterior_run<0>(ctx, M, d_obs, h_off, C.d_off, n_seq, E, d_logp, d_post, d_map_state, d_map_logp, d_counts_seq);
@@ -3712,14 +3737,14 @@ int ps_hmm_sample(ps_ctx *ctx, const ps_hmm_model *model, const ps_hmm_sample_ta
     if (n_seq == 0) return PS_OK;
     if (!d_len || !d_flags || (h_off[n_seq] > 0 && !d_obs)) return fail(ctx, PS_ERR_ARG, "null device pointer");
     const size_t nb = (static_cast<size_t>(n_seq) + 1) * sizeof(int64_t);
-    if (int rc = upload_tables(ctx, ctx->hmm_samp, {{tables->out_cdf, static_cast<size_t>(C.E) * sizeof(double)},
+    if (int rc = upload_tables(ctx, ctx->hmm.samp, {{tables->out_cdf, static_cast<size_t>(C.E) * sizeof(double)},
                                                     {tables->emit_param, static_cast<size_t>(n_param) * sizeof(double)},
                                                     {tables->kde_cdf, static_cast<size_t>(n_kde) * sizeof(double)},
                                                     {C.mix ? model->mix_cdf : nullptr, static_cast<size_t>(n_mix) * sizeof(double)},
                                                     {C.mix ? model->mix_draw : nullptr, 2 * static_cast<size_t>(n_mix) * sizeof(double)},
                                                     {h_off, nb}, {h_path_off, want_path ? nb : 0}})) return rc;
     HmmSampleDev T;
-    T.out_cdf = ctx->hmm_samp.as<double>();
+    T.out_cdf = ctx->hmm.samp.as<double>();
     T.emit_param = T.out_cdf + C.E;
     T.kde_cdf = T.emit_param + n_param;
     C.DM.mix_cdf = T.kde_cdf + n_kde;

@@ -92,6 +92,11 @@ def _f64_device(*tensors):
     return tensors[0].device
 
 
+def live_bytes():
+    """ps_live_bytes: device + pinned host bytes that the library's contexts of this process hold right now (a diagnostic)."""
+    return int(_lib.lib().ps_live_bytes())
+
+
 def _serialised(method):
     """The method runs under its Context's lock."""
     import functools
