@@ -142,8 +142,9 @@ int ps_set_tiling(ps_ctx *ctx, int64_t tile_len, int64_t halo);
  * "debug" 1: the library reports on stderr which occupancy it found, the resident slots every launch sized by them gets, and
  * which seams gave up (prints only);
  * "slots_pct" 1..100 (default 100) share of the resident wave slots the kernels of up to 256 threads that are sized by them
- * (the scan kernels, the aligner, the pairwise aligner, the HMM E-step) are launched on, from the next launch on;
+ * (the scan kernels, the aligner, the pairwise aligner, the repeat splitter, the HMM E-step) are launched on, from the next launch on;
  * "pairwise_budget" bytes of score / pointer scratch per launch of ps_pairwise_batch (default 2 GiB);
+ * "trf_budget" bytes of mask / pointer scratch per launch of ps_trf_split_batch (default 2 GiB);
  * "tree_jobs_per_wave" (default 4) subtree kernel: jobs / this many of its slots work, between half and all of them;
  * "tree_screen" 1 (default): on the 32-bit digest a lean kernel walks the subtree jobs first, proves the windows that hold no
  * split empty and leaves the subtree kernel the jobs it cannot decide (counters[14], [15] of ps_get_timings), 0: the subtree
@@ -443,6 +444,29 @@ int ps_pairwise_batch(ps_ctx *ctx, const double *d_a, const int64_t *h_a_off, in
                       const int64_t *h_col_off, int32_t *d_cols_i, int32_t *d_cols_j, int32_t *d_col_need,
                       const int64_t *h_aln_off, double *d_aln_score, int32_t *d_aln_start, int32_t *d_aln_len,
                       int32_t *d_aln_count);
+
+/* Replaces NaiveSplitter, the inner generator of NaiveTRF(seq, penalty, min_score) (alignment.py:806-870): the off-diagonal
+ * local self-alignments of a sequence of segments with itself, which are the re-reads of an event in which the enzyme slipped
+ * back.  Sequence q is the segments [h_off[q], h_off[q+1]) of d_mean / d_std (fp64, device; finite means, finite stds > 0:
+ * the caller checks them), at most 2048 of them (PS_ERR_ARG beyond); an empty sequence is legal and yields nothing.  Cell
+ * (i, j) of the (n + 1)^2 matrix is the maximum of 0, diagonal + 2 - |mean_i - mean_j|^2 / (std_i std_j), left + penalty and
+ * up + penalty, first candidate winning a tie, a candidate whose SOURCE cell is masked left out; the mask starts as the
+ * identity.  A repeat: the row-major-first maximum of the matrix, if above min_score, is walked back along the pointers to
+ * the first cell whose pointer is 0; every walked cell and that end cell are masked, (score, length, i, j) -- the maximum,
+ * the cells walked, the end cell -- is appended to the sequence's slot [h_slot_off[q], h_slot_off[q+1]) of d_score / d_len /
+ * d_i / d_j, and the matrix is filled again.  A sequence ends when no cell is above min_score (d_status[q] =
+ * PS_TRF_DONE) or after max_repeats yields (0: no cap; PS_TRF_MAX_REPEATS).  d_count[q] = its yields, also where the slot
+ * was too small: the yields beyond the slot are counted, not stored, and the call returns PS_ERR_CAPACITY -- the caller
+ * grows the slots and calls again.  PS_ERR_ARG for penalty >= 0 (the diagonal and the lower triangle, which the device does
+ * not compute, would become observable) and for min_score < 0 (the reference never ends there).  All arithmetic is fp64
+ * without contraction, division included, so the yields equal the reference's bit for bit.  A mask bit and a pointer of 2
+ * bits per cell live in a scratch per resident workgroup; the batch is split into launches whose scratch stays within option
+ * "trf_budget" bytes (default 2 GiB), sized by "slots_pct".  The call synchronises the context's stream before returning. */
+#define PS_TRF_DONE         0
+#define PS_TRF_MAX_REPEATS  1
+int ps_trf_split_batch(ps_ctx *ctx, const double *d_mean, const double *d_std, const int64_t *h_off, int32_t n_seq,
+                       double penalty, double min_score, int64_t max_repeats, double *d_score, int32_t *d_len, int32_t *d_i,
+                       int32_t *d_j, const int64_t *h_slot_off, int32_t *d_count, int32_t *d_status);
 
 /* A baked hidden Markov model (pypore_amd.hmm.Model.bake), host arrays.  States [0, n_emit) emit, states [n_emit, n_states)
  * are silent and grouped by topological level: level L is [level_ptr[L], level_ptr[L+1]), level_ptr[0] = n_emit,

@@ -20,11 +20,13 @@ EXPORTS = ["ps_version", "ps_device_count", "ps_create", "ps_destroy", "ps_last_
            "ps_best_single_split", "ps_score_window", "ps_get_timings", "ps_synth_trace", "ps_filter_bessel",
            "ps_requantise", "ps_grid_check_f64", "ps_grid_counts_f64", "ps_narrow_f64", "ps_filter_requantise_batch", "ps_align_batch", "ps_audit_bounds", "ps_counters",
            "ps_get_near_ties", "ps_hmm_batch", "ps_hmm_expect", "ps_hmm_posterior", "ps_hmm_sample", "ps_pairwise_scores", "ps_pairwise_batch",
-           "ps_statsplit_f64", "ps_statsplit_prefix_f64", "ps_live_bytes"]
+           "ps_statsplit_f64", "ps_statsplit_prefix_f64", "ps_live_bytes", "ps_trf_split_batch"]
 PS_STATSPLIT_STEPWISE, PS_STATSPLIT_SLANTED = 0, 1
 PS_HMM_VITERBI, PS_HMM_FORWARD, PS_HMM_BACKWARD = 0, 1, 2
 PS_PW_GLOBAL, PS_PW_LOCAL, PS_PW_LOCAL_REPEATED = 0, 1, 2
 PS_PW_OK, PS_PW_INDEX_ERROR = 0, 1
+PS_TRF_DONE, PS_TRF_MAX_REPEATS = 0, 1
+TRF_N_MAX = 2048          # segments per sequence of ps_trf_split_batch
 PS_NT_NOT_COUNTED, PS_NT_INCOMPLETE = -1, -2     # ps_get_near_ties: *n_out when the sites are not counted / the log overflowed
 
 
@@ -136,6 +138,7 @@ def lib():
     L.ps_pairwise_scores.argtypes = [vp, vp, P(i64), i32, vp, P(i64), i32, i32, dbl, vp, vp]
     L.ps_pairwise_batch.argtypes = [vp, vp, P(i64), i32, vp, P(i64), i32, P(i32), P(i32), i32, i32, dbl, i32, vp, vp,
                                     P(i64), vp, vp, vp, P(i64), vp, vp, vp, vp]
+    L.ps_trf_split_batch.argtypes = [vp, vp, vp, P(i64), i32, dbl, dbl, i64, vp, vp, vp, vp, P(i64), vp, vp]
     L.ps_audit_bounds.argtypes = [vp, vp, P(SampleFormat), i64, P(SplitParams), P(i32), i32, P(dbl)]
     L.ps_statsplit_f64.argtypes = [vp, vp, P(i64), P(i64), i32, P(i64), P(i64), P(StatSplitParams), vp, i64, P(i64)]
     L.ps_statsplit_prefix_f64.argtypes = [vp, vp, i64, vp, vp, vp]

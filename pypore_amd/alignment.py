@@ -8,13 +8,18 @@ ps_pairwise_scores, csrc/seg_pairwise.hpp); `pairwise_align_batch` and `pairwise
 
 `PSSM`, `ProfileAligner` and `MultipleSequenceAligner` (PyPore/alignment.py:329-796) align sequences of segment means to
 a profile -- a multiple sequence alignment whose columns become Gaussian kernel densities -- with profile HMMs decoded by
-pypore_amd.hmm on the GPU; `profile_align_batch` aligns many sequences to one profile in a single Viterbi launch."""
+pypore_amd.hmm on the GPU; `profile_align_batch` aligns many sequences to one profile in a single Viterbi launch.
+
+`NaiveTRF` (PyPore/alignment.py:799-893) finds the re-reads of an event in which the enzyme slipped back and lays them out
+as a naive multiple alignment; its splitter runs on the GPU (ps_trf_split_batch, csrc/seg_trf.hpp), `naive_trf_batch` and
+`naive_splits_batch` do it for many sequences in one call."""
 import copy
 import itertools as it
 import math
 
 import numpy as np
 
+from . import _lib
 from .calignment import cSegmentAligner
 from .hmm import GaussianKernelDensity, Model, State, UniformDistribution
 
@@ -499,3 +504,99 @@ class MultipleSequenceAligner(object):
             p, master, slave = self._global(pssm, seq, bandwidth)
             pssm = PSSM([seq for seq in it.chain(master.msa, slave.msa)])
         return self._score(pssm.msa), pssm.msa
+
+
+# ---- tandem repeats (PyPore/alignment.py:799-893) --------------------------------------------------------------------------
+def _trf_args(penalty, min_score, max_repeats):
+    penalty, min_score = float(penalty), float(min_score)
+    if not (math.isfinite(penalty) and penalty < 0):
+        raise ValueError("NaiveTRF: the penalty must be finite and < 0 (with penalty >= 0 the reference's diagonal and lower "
+                         "triangle, which the device does not compute, take part in the result)")
+    if not (math.isfinite(min_score) and min_score >= 0):
+        raise ValueError("NaiveTRF: min_score must be finite and >= 0 (the reference never ends for min_score < 0: it yields "
+                         "the border cell (0, 0) for ever)")
+    max_repeats = 0 if max_repeats is None else int(max_repeats)
+    if max_repeats < 0:
+        raise ValueError("max_repeats must be None or >= 0 (0: no cap)")
+    return penalty, min_score, max_repeats
+
+
+def _trf_values(seq, q):
+    """(means, stds) of a sequence as float64 arrays, checked: a list of objects with .mean and .std, or a pair of arrays."""
+    if isinstance(seq, tuple) and len(seq) == 2 and all(isinstance(v, (np.ndarray, list, tuple)) for v in seq):
+        means, stds = (np.array(v, dtype=np.float64).reshape(-1) for v in seq)
+        if means.size != stds.size:
+            raise ValueError("sequence %d: %d means and %d stds" % (q, means.size, stds.size))
+    else:
+        means = np.array([s.mean for s in seq], dtype=np.float64).reshape(-1)
+        stds = np.array([s.std for s in seq], dtype=np.float64).reshape(-1)
+    if not np.all(np.isfinite(means)):
+        raise ValueError("sequence %d: a mean is not finite" % q)
+    if not np.all(np.isfinite(stds) & (stds > 0)):
+        raise ValueError("sequence %d: a std is not finite and > 0 (the reference's score divides by std * std: inf or nan, "
+                         "whose maximum depends on the order)" % q)
+    if means.size > _lib.TRF_N_MAX:
+        raise ValueError("sequence %d: %d segments, the device repeat splitter takes up to %d" % (q, means.size, _lib.TRF_N_MAX))
+    return means, stds
+
+
+def naive_splits_batch_raw(seqs, penalty=-1, min_score=2, max_repeats=None, device=None, slots=None, retry=True):
+    """The arrays of engine.Context.trf_split_batch for `seqs`: (rc, score, length, i, j, slot_off, count, status).  Every
+    argument is checked before the library is touched (ValueError)."""
+    penalty, min_score, max_repeats = _trf_args(penalty, min_score, max_repeats)
+    vals = [_trf_values(s, q) for q, s in enumerate(seqs)]
+    off = np.concatenate(([0], np.cumsum([m.size for m, _ in vals]))).astype(np.int64)
+    means = np.concatenate([m for m, _ in vals]) if vals and off[-1] else np.zeros(1, np.float64)
+    stds = np.concatenate([s for _, s in vals]) if vals and off[-1] else np.ones(1, np.float64)
+    import torch
+    from . import engine
+    ctx = engine.context(device)
+    dev = torch.device("cuda", ctx.device)
+    return ctx.trf_split_batch(torch.from_numpy(means).to(dev), torch.from_numpy(stds).to(dev), off, penalty, min_score,
+                               max_repeats, slots, retry)
+
+
+def naive_splits_batch(seqs, penalty=-1, min_score=2, max_repeats=None, device=None):
+    """Per sequence the list of (score, length, start, end) that the reference's NaiveSplitter yields, in yield order, from
+    one library call for the whole batch.  A sequence is a list of objects with .mean and .std, or a (means, stds) pair of
+    arrays.  max_repeats: at most that many yields per sequence (None: all)."""
+    seqs = list(seqs)
+    _, score, length, i, j, slot_off, count, _ = naive_splits_batch_raw(seqs, penalty, min_score, max_repeats, device)
+    return [[(float(score[k]), int(length[k]), int(i[k]), int(j[k])) for k in range(int(slot_off[q]), int(slot_off[q]) + int(count[q]))]
+            for q in range(len(seqs))]
+
+
+def _trf_stitch(seq, splits):
+    """The stitching loop of alignment.py:873-893: the re-reads laid out under each other, padded with '-'."""
+    last_end, last_start, offset, sequences = 0, 0, 0, []
+    for score, length, start, end in sorted(splits, key=lambda x: x[3]):
+        sequences.append(['-'] * offset + seq[last_end:end])
+        offset = (len(sequences[-1]) - (end - start) if last_start != start else offset)
+        last_end, last_start = end, start
+    sequences.append(['-'] * offset + seq[last_end:])
+    n = max(map(len, sequences))
+    return [s + ['-'] * (n - len(s)) for s in sequences]
+
+
+def naive_trf_batch(seqs, penalty=-1, min_score=2, max_repeats=None, device=None):
+    """NaiveTRF for many sequences (lists of objects with .mean and .std) from one library call: per sequence the
+    reference's list of rows, made of the caller's own objects and '-'."""
+    seqs = [list(s) for s in seqs]
+    return [_trf_stitch(s, sp) for s, sp in zip(seqs, naive_splits_batch(seqs, penalty, min_score, max_repeats, device))]
+
+
+def NaiveTRF(seq, penalty=-1, min_score=2):
+    """NaiveTRF of PyPore/alignment.py:799-893 on the GPU.  `seq`: the segments of an event in which the enzyme slipped back
+    and re-read part of the strand (objects with .mean and .std, e.g. event.segments).  Step 1, on the device
+    (ps_trf_split_batch, csrc/seg_trf.hpp): the local self-alignment matrix of the sequence is filled, its best off-diagonal
+    path pulled out and masked, and the matrix filled again until nothing scores above min_score.  Step 2, on the host: the
+    paths, sorted stably by their end, are stitched into a naive multiple alignment -- a list of rows of equal length made
+    of the caller's own objects and '-'.
+
+    Deliberate deviations from the reference, all ValueError before any library call: min_score < 0 (the reference never
+    returns: it yields the border cell for ever); penalty >= 0 (the reference's diagonal and lower triangle, which the
+    device does not compute, would take part); a mean that is not finite; a std that is not finite and > 0 (inf / nan
+    scores whose maximum depends on the order of a tuple).  Sequences of up to 2048 segments.  The square of the
+    reference's score, `** 2`, is taken as the product -- the correctly rounded value; the reference's is its host's
+    libm pow, one ulp off for about 0.07 % of the operands.  There is no CPU fallback."""
+    return naive_trf_batch([seq], penalty, min_score)[0]

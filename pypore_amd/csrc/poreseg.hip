@@ -40,6 +40,7 @@
 #include "seg_device.hpp"
 #include "seg_align.hpp"
 #include "seg_pairwise.hpp"
+#include "seg_trf.hpp"
 #include "seg_hmm.hpp"
 #include "seg_ingest.hpp"
 #include "seg_statsplit.hpp"
@@ -197,7 +198,7 @@ struct ps_ctx {
     } tile_cache;
     DevBuf bsum, ev_info, chunk_mabs, ev_boff, blk_mm, grp, up_dev;
     // The segmentation chain's own buffers and options are flat members.  The state of every self-contained feature stands
-    // together in a sub-struct (filt, align, pw, ss, nt, hmm): its buffers, its budgets, its host-side caches.  A new feature
+    // together in a sub-struct (filt, align, pw, trf, ss, nt, hmm): its buffers, its budgets, its host-side caches.  A new feature
     // adds its group here and nowhere else: the buffers free themselves with the context.
     struct {                // Bessel filter (ps_filter_bessel, ps_filter_requantise_batch)
         DevBuf fwd, agg, zin;
@@ -208,6 +209,10 @@ struct ps_ctx {
         DevBuf in, scratch;
         long long budget = 2ll << 30;        // option pairwise_budget: bytes of pairwise scratch per launch
     } pw;
+    struct {                  // NaiveTRF's splitter (ps_trf_split_batch): offsets and the capacity flag, per-workgroup mask and pointer bits
+        DevBuf in, scratch;
+        long long budget = 2ll << 30;        // option trf_budget: bytes of splitter scratch per launch
+    } trf;
     DevBuf ev_info_tr;        // single-pass file route (ps_detect_segment_trace): (centre, phase, first block) of the events cut out of a trace-aligned digest
     DevBuf blk_cls, cls_mm;   // ... K0's verdict per block against the detector's threshold (2 bits), min / max per 128 blocks
     DevBuf pre_c;             // exact route (ps_segment_exact_f64): c and c2 of the call's samples, 16 B per sample
@@ -1650,6 +1655,7 @@ int ps_set_option(ps_ctx *ctx, const char *name, int64_t value)
     else if (n == "hmm_bp_budget" && value >= 1) ctx->hmm.bp_budget = value;
     else if (n == "hmm_fb_budget" && value >= 1) ctx->hmm.fb_budget = value;
     else if (n == "pairwise_budget" && value >= 1) ctx->pw.budget = value;
+    else if (n == "trf_budget" && value >= 1) ctx->trf.budget = value;
     else if (n == "hmm_expect_lds") ctx->hmm.expect_lds = value != 0;
     else if (n == "single_pass") ctx->single_pass = value != 0;
     else if (n == "gather_fused") ctx->gather_fused = value != 0;
@@ -3212,6 +3218,72 @@ int ps_pairwise_batch(ps_ctx *ctx, const double *d_a, const int64_t *h_a_off, in
     HIP_TRY(ctx, hipMemcpyAsync(&flag, P.flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (flag) return fail(ctx, PS_ERR_CAPACITY, "an alignment slot is too small (d_col_need and d_aln_count hold what the pairs take)");
+    return PS_OK;
+}
+
+int ps_trf_split_batch(ps_ctx *ctx, const double *d_mean, const double *d_std, const int64_t *h_off, int32_t n_seq,
+                       double penalty, double min_score, int64_t max_repeats, double *d_score, int32_t *d_len, int32_t *d_i,
+                       int32_t *d_j, const int64_t *h_slot_off, int32_t *d_count, int32_t *d_status)
+{
+    if (!ctx) return PS_ERR_ARG;
+    if (!h_off || !h_slot_off) return fail(ctx, PS_ERR_ARG, "null pointer");
+    if (n_seq < 0 || max_repeats < 0) return fail(ctx, PS_ERR_ARG, "negative count");
+    // the reference never ends for min_score < 0 (the border cell (0, 0) is yielded for ever); with penalty >= 0 the
+    // diagonal and the lower triangle are no longer unobservable
+    if (!(penalty < 0.0) || !std::isfinite(penalty)) return fail(ctx, PS_ERR_ARG, "ps_trf_split_batch: the penalty must be finite and < 0");
+    if (!(min_score >= 0.0) || !std::isfinite(min_score)) return fail(ctx, PS_ERR_ARG, "ps_trf_split_batch: min_score must be finite and >= 0");
+    if (n_seq == 0) return PS_OK;
+    if (!d_score || !d_len || !d_i || !d_j || !d_count || !d_status) return fail(ctx, PS_ERR_ARG, "null output pointer");
+    int64_t n_max = 0;
+    if (int rc = check_offsets(ctx, h_off, n_seq, "sequence", &n_max)) return rc;
+    if (n_max > TRF_N_MAX) return fail(ctx, PS_ERR_ARG, "a sequence of %lld segments: the device repeat splitter takes up to %d", (long long)n_max, TRF_N_MAX);
+    if (h_off[n_seq] > 0 && (!d_mean || !d_std)) return fail(ctx, PS_ERR_ARG, "null sequence pointer");
+    for (int32_t q = 0; q < n_seq; ++q)
+        if (h_slot_off[q] < 0 || h_slot_off[q + 1] < h_slot_off[q]) return fail(ctx, PS_ERR_ARG, "slot offsets must be non-negative and ascending");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // one upload: the two 8-byte tables, the capacity flag
+    const size_t ns = static_cast<size_t>(n_seq) + 1;
+    const int32_t no_flags[2] = {0, 0};
+    if (int rc = upload_tables(ctx, ctx->trf.in, {{h_off, ns * 8}, {h_slot_off, ns * 8}, {no_flags, sizeof(no_flags)}})) return rc;
+    TrfBatch P;
+    P.mean = d_mean; P.std = d_std;
+    P.off = ctx->trf.in.as<long long>(); P.slot_off = P.off + ns;
+    P.flag = reinterpret_cast<int *>(const_cast<long long *>(P.slot_off + ns));
+    P.penalty = penalty; P.min_score = min_score; P.max_repeats = max_repeats;
+    P.score = d_score; P.len = d_len; P.i = d_i; P.j = d_j; P.count = d_count; P.status = d_status;
+    // Launches: consecutive sequences while the scratch of their launch -- the mask and pointer bits of the launch's longest
+    // sequence per workgroup, a workgroup per sequence up to the resident slots -- stays within the budget; a launch whose
+    // first sequence alone leaves room for few workgroups runs on that many
+    const unsigned long long budget = static_cast<unsigned long long>(std::max<long long>(1, ctx->trf.budget));
+    static_assert(trf_lds_bytes(TRF_N_MAX) <= 64u << 10, "beyond 64 KiB the launch needs hipFuncAttributeMaxDynamicSharedMemorySize (set_dyn_lds)");
+    for (int32_t q0 = 0; q0 < n_seq;) {
+        int n_cap = 1;
+        int32_t q1 = q0;
+        unsigned slots = 0;
+        while (q1 < n_seq) {
+            const int n = static_cast<int>(h_off[q1 + 1] - h_off[q1]);
+            if (q1 > q0 && n > n_cap) {
+                const unsigned long long g = std::min<unsigned long long>(static_cast<unsigned long long>(q1 - q0) + 1, slots);
+                if (g * trf_scratch_bytes(n) > budget) break;
+            }
+            n_cap = std::max(n_cap, n); ++q1;
+            if (q1 == q0 + 1) slots = resident_slots(ctx, trf_kernel, TRF_NT, trf_lds_bytes(n_cap));
+        }
+        const unsigned long long per_wg = trf_scratch_bytes(n_cap);
+        const size_t lds = trf_lds_bytes(n_cap);
+        const int nq = q1 - q0;
+        unsigned grid = std::min<unsigned>(static_cast<unsigned>(nq), resident_slots(ctx, trf_kernel, TRF_NT, lds));
+        grid = static_cast<unsigned>(std::max<unsigned long long>(1, std::min<unsigned long long>(grid, budget / per_wg)));
+        HIP_TRY(ctx, ctx->trf.scratch.reserve(static_cast<size_t>(grid) * per_wg));
+        if (ctx->debug) fprintf(stderr, "[poreseg] trf launch: sequences %d..%d, grid %u, %llu bytes of scratch per workgroup, dynamic LDS %zu\n", q0, q1, grid, per_wg, lds);
+        hipLaunchKernelGGL(trf_kernel, dim3(grid), dim3(TRF_NT), lds, ctx->stream, P, q0, nq, n_cap, ctx->trf.scratch.as<unsigned char>(), per_wg);
+        HIP_TRY(ctx, hipGetLastError());
+        q0 = q1;
+    }
+    int flag = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&flag, P.flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (flag) return fail(ctx, PS_ERR_CAPACITY, "a repeat slot is too small (d_count holds the yields every sequence has)");
     return PS_OK;
 }
 

@@ -614,6 +614,39 @@ class Context(object):
                 aln_il[0], aln_il[1], aln_off, aln_count[:n].cpu().numpy())
 
     @_serialised
+    def trf_split_batch(self, mean, std, off, penalty, min_score, max_repeats=0, slots=None, retry=True):
+        """ps_trf_split_batch: the repeats of every sequence q = (mean, std)[off[q]:off[q+1]] (float64 CUDA tensors), the
+        reference's NaiveSplitter.  Returns (rc, score float64, length, i, j int32 -- numpy, sequence q's yields at
+        slot_off[q] .. slot_off[q] + count[q] in yield order --, slot_off [n + 1], count int32 [n], status int32 [n]).
+        slots: entries per sequence (default: its segments, what random levels yield about twice over).  Yields beyond a
+        slot are counted, not stored (PS_ERR_CAPACITY); with retry the call then runs again with slots of the exact counts
+        and rc is PS_OK; without, rc is returned as it is (PS_OK or PS_ERR_CAPACITY) with whatever fitted and the true
+        counts.  Any other status raises."""
+        off, off_p = _offsets(off)
+        n = off.size - 1
+        dev = _f64_device(mean, std)
+        if slots is None:
+            slots = np.diff(off)
+        slots = np.asarray(slots, np.int64).reshape(-1)
+        assert slots.size == n
+        count, status = (torch.zeros(max(n, 1), dtype=torch.int32, device=dev) for _ in range(2))
+        torch.cuda.current_stream(dev).synchronize()
+        for attempt in range(2):
+            slot_off, slot_off_p = _offsets(np.concatenate(([0], np.cumsum(slots))))
+            score = torch.zeros(max(int(slot_off[-1]), 1), dtype=torch.float64, device=dev)
+            lij = torch.zeros((3, max(int(slot_off[-1]), 1)), dtype=torch.int32, device=dev)
+            rc = self.L.ps_trf_split_batch(self.handle, _ptr(mean), _ptr(std), off_p, n, float(penalty), float(min_score),
+                                           int(max_repeats), _ptr(score), _ptr(lij[0]), _ptr(lij[1]), _ptr(lij[2]), slot_off_p,
+                                           _ptr(count), _ptr(status))
+            if rc != _lib.PS_ERR_CAPACITY or attempt or not retry:
+                break
+            slots = count[:n].cpu().numpy().astype(np.int64)                  # the exact counts
+        if rc != _lib.PS_ERR_CAPACITY or retry:
+            _lib.check(rc, self.handle)
+        lij = lij.cpu().numpy()
+        return rc, score.cpu().numpy(), lij[0], lij[1], lij[2], slot_off, count[:n].cpu().numpy(), status[:n].cpu().numpy()
+
+    @_serialised
     def hmm_batch(self, model, mode, obs, off, want_mat=False, path_slots=None):
         """ps_hmm_batch: one HMM pass over a batch of sequences.  model: a _lib.HmmModel (its arrays kept alive by the caller);
         obs: float64 CUDA tensor, sequence q = obs[off[q]:off[q+1]].  Returns (logp float64 [n_seq], matrix float64
