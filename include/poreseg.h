@@ -121,7 +121,8 @@ int ps_set_tiling(ps_ctx *ctx, int64_t tile_len, int64_t halo);
  * several contexts busy (engine.StreamPool) sets it for the duration of its runs (measured slower: nothing sets it);
  * "k0_admit" M > 0: at most M calls of this device have their K0 in flight at a time -- enforced on the device (round 6): a
  * call queues a wait for the K0 of the call M tickets before it in front of its own K0 (hipStreamWaitEvent); the host thread
- * never waits --, 0 (default) no limit; engine.StreamPool sets 3 ("shared_device");
+ * never waits for the device, only -- for the length of a kernel launch -- for the thread that holds that ticket and has
+ * not queued its K0 yet (ps_gate_stats) --, 0 (default) no limit; "shared_device" sets what ps_pool_plan says;
  * "bridge_ext" 1 (default): seams whose bridge ran out of anchors (256 without meeting a downstream tile's chain:
  * densely stepped data) and open tiles entered exactly at their start are continued on the device -- up to four rounds,
  * 16 384 more anchors per seam -- before the call falls back to the host stitch, 0 straight to the host stitch;
@@ -133,8 +134,15 @@ int ps_set_tiling(ps_ctx *ctx, int64_t tile_len, int64_t halo);
  * "bridge_budget" 1..256 (default 256): anchors a bridge may add before it gives up (tests lower it to reach the second
  * chance on small inputs);
  * "shared_device" n: ONE call for a host that keeps n contexts busy on one device (a pool of host threads, one context
- * each): n > 1 sets k0_waves 1, lat_help 0 and, for n > 3, k0_admit 3 -- the measured settings of a shared chip
- * (INTEGRATION.md has the table) --, n <= 1 restores the defaults of a lone context (k0_waves 0, lat_help 1, k0_admit 0);
+ * each).  HIP maps the streams of a process onto its hardware queues, and streams that share a queue run their kernels one
+ * after the other: of n contexts on Q queues, n_eff = min(n, Q) calls execute at a time, and a call is configured for
+ * that many -- it sets k0_waves, k0_admit and lat_help to exactly what ps_pool_plan(n, Q) returns (the table is there and in
+ * INTEGRATION.md); "k0_waves" / "k0_admit" / "lat_help" set afterwards still win.  Everything that asks whether the call is
+ * one of a pool ("short_chain") goes by n itself, whatever Q is.  n <= 1 restores the defaults of a lone context (k0_waves 0,
+ * lat_help 1, k0_admit 0);
+ * "hw_queues" Q (1 .. 32; 0, the default: the process's own): the hardware queues the next "shared_device" plans for.  The
+ * process's own number is GPU_MAX_HW_QUEUES as the HIP runtime reads it -- read once, unset or not a number: HIP's default
+ * of 4; the library never sets the variable.  For tests and tools;
  * "single_pass" 1 (default): ps_detect_segment_trace streams a file trace once (see there), 0: it makes the two calls;
  * "gather_fused" 1 (default): the gather places its items from per-256-job count sums (no scan kernel in front of it), 0: rounds
  * 2-5's item scan + gather; "download_by_kernel" 1 (default): the status block returns by a kernel writing pinned memory;
@@ -164,11 +172,47 @@ int ps_set_tiling(ps_ctx *ctx, int64_t tile_len, int64_t halo);
  * "near_tie_log" n (default 65 536, 0 .. 2^30): records of the near-tie log that ps_get_near_ties reads (16 bytes each, device
  * memory allocated with the first segment call that logs), 0 = no log.
  * Unknown names return PS_ERR_ARG.
- * THE LIBRARY READS NO ENVIRONMENT VARIABLE (round 6): what a call returns depends on its arguments and on these two
- * setters only.  The experiments' switches that return stale or partial results ("dbg_phase", "dbg_k0_nogrp",
+ * THE LIBRARY READS NO ENVIRONMENT VARIABLE OF ITS OWN (round 6): what a call returns depends on its arguments and on these
+ * two setters only.  (GPU_MAX_HW_QUEUES, the runtime's variable, is read for "shared_device": it changes how a call is
+ * scheduled, never what it returns.)  The experiments' switches that return stale or partial results ("dbg_phase", "dbg_k0_nogrp",
  * "scan_lds_pad", "rep_*") and the PORESEG_* variables exist in libporeseg_diag.so only (make -C pypore_amd/csrc diag;
  * ps_version() of that build says DIAGNOSTIC BUILD). */
 int ps_set_option(ps_ctx *ctx, const char *name, int64_t value);
+/* The current value of one of the options that "shared_device" plans -- "k0_waves", "k0_admit", "lat_help" -- or of
+ * "shared_device" / "hw_queues" as last set; PS_ERR_ARG for any other name. */
+int ps_get_option(const ps_ctx *ctx, const char *name, int64_t *value);
+
+/* What option "shared_device" n sets on a process with hw_queues hardware queues: a pure function of min(n, hw_queues) -- no
+ * context, no GPU.  n_eff = min(n_contexts, hw_queues) calls execute at a time (hw_queues <= 0: HIP's default of 4; more than
+ * 32 counts as 32).
+ *     n_eff      k0_waves  k0_admit  lat_help
+ *     0, 1       0         0         1          a lone call: one-shot K0 on every slot it can get, no gate, helpers on
+ *     2          0         0         0          measured: sixteen contexts on 2 queues
+ *     3 .. 5     4         0         0          measured: sixteen contexts on 4 queues (HIP's default; 8 % under the row below)
+ *     6 .. 11    1         0         0          measured: sixteen contexts on 8 queues
+ *     12 .. 15   1         3         0          not measured: as the nearest measured point, the row below
+ *     >= 16      1         3         0          measured with sixteen calls in flight (round 5, and again on 16 queues)
+ * (tools/pool_plan_sweep.py, profiles/pool_queues_ab.json; DESIGN.md section 6 has the numbers and the rule that chose the rows.)
+ * Down the table a call never gets a larger share of the chip: the K0 waves per SIMD (0 = every slot) and the K0s admitted
+ * at a time (0 = all) do not grow, the helpers do not come back.  PS_ERR_ARG for a null pointer or a negative count. */
+typedef struct ps_pool_plan_t {
+    int32_t n_eff;                       /* calls that execute at a time: min(n_contexts, hw_queues) */
+    int32_t k0_waves;                    /* option "k0_waves" */
+    int32_t k0_admit;                    /* option "k0_admit" */
+    int32_t lat_help;                    /* option "lat_help" */
+} ps_pool_plan_t;
+int ps_pool_plan(int32_t n_contexts, int32_t hw_queues, ps_pool_plan_t *out);
+/* The hardware queues of this process as "shared_device" sees them: GPU_MAX_HW_QUEUES read once (unset or not a number: 4;
+ * clamped to 1 .. 32).  No GPU needed. */
+int ps_hw_queues(void);
+/* The K0 gate of `device` ("k0_admit"), for tests: out[0] tickets taken so far, [1] calls that have gone through the gate with
+ * their ticket and have not yet queued the event behind their K0 (or given the ticket up), right now, [2] the most there
+ * have been of them at a time, [3] times a host thread waited for such a call before it queued its own wait, [4] times it
+ * gave that up (200 ms) and went on without a wait.  [2] never exceeds the largest "k0_admit" in use while [4] is zero:
+ * that is what keeps M K0s in flight and no more.  reset != 0 sets [2] back to [1] and [3], [4] to zero behind the read.
+ * Host bookkeeping only: no GPU call.  device 0 .. 15. */
+int ps_gate_stats(int device, int64_t *out, int32_t n_out, int reset);
+
 /* Blocks until all work submitted on the context's stream has finished. */
 int ps_synchronize(ps_ctx *ctx);
 

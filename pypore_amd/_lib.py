@@ -20,7 +20,8 @@ EXPORTS = ["ps_version", "ps_device_count", "ps_create", "ps_destroy", "ps_last_
            "ps_best_single_split", "ps_score_window", "ps_get_timings", "ps_synth_trace", "ps_filter_bessel",
            "ps_requantise", "ps_grid_check_f64", "ps_grid_counts_f64", "ps_narrow_f64", "ps_filter_requantise_batch", "ps_align_batch", "ps_audit_bounds", "ps_counters",
            "ps_get_near_ties", "ps_hmm_batch", "ps_hmm_expect", "ps_hmm_posterior", "ps_hmm_sample", "ps_pairwise_scores", "ps_pairwise_batch",
-           "ps_statsplit_f64", "ps_statsplit_prefix_f64", "ps_live_bytes", "ps_trf_split_batch"]
+           "ps_statsplit_f64", "ps_statsplit_prefix_f64", "ps_live_bytes", "ps_trf_split_batch",
+           "ps_pool_plan", "ps_hw_queues", "ps_gate_stats", "ps_get_option"]
 PS_STATSPLIT_STEPWISE, PS_STATSPLIT_SLANTED = 0, 1
 PS_HMM_VITERBI, PS_HMM_FORWARD, PS_HMM_BACKWARD = 0, 1, 2
 PS_PW_GLOBAL, PS_PW_LOCAL, PS_PW_LOCAL_REPEATED = 0, 1, 2
@@ -67,6 +68,11 @@ class HmmSampleTables(ctypes.Structure):
     """ps_hmm_sample_tables: what ps_hmm_sample reads beside the model (pypore_amd.hmm.Model._sample_tables)."""
     _fields_ = [(f, ctypes.c_void_p) for f in ("out_cdf", "emit_param", "kde_cdf")] + \
                [(f, ctypes.c_int64) for f in ("n_cdf", "n_param", "n_kde")]
+
+
+class PoolPlan(ctypes.Structure):
+    """ps_pool_plan_t: what option "shared_device" n sets on a process with a given number of hardware queues."""
+    _fields_ = [("n_eff", ctypes.c_int32), ("k0_waves", ctypes.c_int32), ("k0_admit", ctypes.c_int32), ("lat_help", ctypes.c_int32)]
 
 
 class GridReport(ctypes.Structure):
@@ -187,3 +193,27 @@ def min_gain(**kw):
     p = split_params(**kw)
     check(lib().ps_min_gain(ctypes.byref(p), ctypes.byref(out)))
     return out.value
+
+
+def pool_plan(n_contexts, hw_queues=0):
+    """ps_pool_plan (no GPU): the options "shared_device" n_contexts sets with hw_queues hardware queues (0: HIP's default of 4),
+    as a dict with n_eff = min(n_contexts, hw_queues)."""
+    L = lib()
+    L.ps_pool_plan.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(PoolPlan)]
+    p = PoolPlan()
+    check(L.ps_pool_plan(int(n_contexts), int(hw_queues), ctypes.byref(p)))
+    return {f: int(getattr(p, f)) for f, _ in PoolPlan._fields_}
+
+
+def hw_queues():
+    """ps_hw_queues (no GPU): the hardware queues of this process as the library read them from GPU_MAX_HW_QUEUES."""
+    return int(lib().ps_hw_queues())
+
+
+def gate_stats(device=0, reset=False):
+    """ps_gate_stats (host bookkeeping of the K0 gate): tickets, open now, most open at a time, host waits, waits given up."""
+    L = lib()
+    L.ps_gate_stats.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32, ctypes.c_int]
+    out = (ctypes.c_int64 * 5)()
+    check(L.ps_gate_stats(int(device), out, 5, 1 if reset else 0))
+    return dict(zip(("tickets", "open", "open_max", "host_waits", "gave_up"), (int(v) for v in out)))

@@ -44,6 +44,7 @@
 #include "seg_hmm.hpp"
 #include "seg_ingest.hpp"
 #include "seg_statsplit.hpp"
+#include "pool_plan.hpp"
 
 using namespace ps;
 
@@ -255,6 +256,7 @@ struct ps_ctx {
     // download kernel leaves the status block zero, so that a call that repeats the layout launches no upload (small_clean)
     int short_chain = SC_ALL;
     int shared_n = 0;                               // option shared_device as last set (<= 1: a lone context)
+    int hw_queues = 0;                              // option hw_queues: the hardware queues shared_device plans for (0: the process's, process_hw_queues)
     int pool_patience = BR_PATIENCE_POOL;           // option bridge_patience (1 .. 4096): tests lower it to reach the hand-over on small inputs
     // la_keep: a pooled call whose bridges left seams deferred had the look-ahead kernel run behind its stitch, a round trip late;
     // the next LA_KEEP calls of the context launch it in the chain again, patience 3, as without the option (the data at hand has
@@ -326,42 +328,86 @@ FrontStream *front_for(ps_ctx *ctx)
 // together (sixteen contexts: 0.188 -> 0.175 ms per step with M = 3, round 5).  Round 6: ON THE DEVICE.  The calls of a device
 // take tickets; call t queues, in front of its K0, a wait for the event recorded behind the K0 of call t - M (hipStreamWaitEvent:
 // a barrier packet in its own queue).  Round 5's gate had host threads poll hipEventQuery every 25 us under one mutex and could
-// spin forever on a faulted device; here the host thread never waits, so there is nothing to time out or to leak: a
-// call that fails between its ticket and its record leaves a ticket nobody finds recorded, and whoever looks for it does not
-// wait.  Same step time as the polling gate (0.1709 against 0.1690 ms, 5 interleaved pairs: profiles/r06_experiments).
+// spin forever on a faulted device; here no host thread ever waits for the device.  Same step time as the polling
+// gate (0.1709 against 0.1690 ms, 5 interleaved pairs: profiles/r06_experiments).
+// A ticket is closed by the record behind its K0 (chain_publish) or when its call gives it up (chain_drop: a call that failed
+// between the two).  Call t used to go on without a wait when ticket t - M was taken but not closed -- its thread had not queued
+// its K0 yet --, so that more than M K0s could be in flight; with M small against the calls in flight that race decided how many
+// ran.  Now the host thread of t waits until that ticket is closed: the other thread is inside a kernel launch, microseconds,
+// and waits for nothing in there (the wait is bounded all the same).  Tickets are handed out in order, so every ticket below
+// `next` has been taken: the ticket counter is the slots' "taken" generation, gen / dropped are their "closed" ones.  A ticket is
+// OPEN from the moment its call leaves chain_enter until it is closed.  Call t leaves only behind the record of t - M, so the
+// open tickets of a residue class mod M are one at most, M in all: open_max (ps_gate_stats) says so.
 struct K0Chain {
     static constexpr int RING = 64;
     std::mutex mu;
+    std::condition_variable cv;                         // a ticket was closed
     hipEvent_t ev[RING] = {};
     unsigned long long gen[RING];                       // ticket whose K0 the event was last recorded behind (+1; 0: never)
+    unsigned long long dropped[RING];                   // ticket last given up on the slot without a record (+1; 0: never)
+    unsigned long long left[RING];                      // ticket whose call last left chain_enter on the slot (+1; 0: never)
     unsigned long long next = 0;
     bool made = false;
+    long long open = 0, open_max = 0, host_waits = 0, gave_up = 0;     // ps_gate_stats
+    bool closed(unsigned long long w) const { return gen[w % RING] == w + 1 || dropped[w % RING] == w + 1; }
+    void close(unsigned long long t, bool recorded)
+    {
+        (recorded ? gen : dropped)[t % RING] = t + 1;
+        if (left[t % RING] == t + 1) --open;
+        cv.notify_all();
+    }
 };
 K0Chain g_chain[16];
 int chain_enter(ps_ctx *ctx, int device, int max_in_flight, hipStream_t st, unsigned long long *ticket)
 {
     K0Chain &c = g_chain[device & 15];
-    std::lock_guard<std::mutex> lk(c.mu);
+    std::unique_lock<std::mutex> lk(c.mu);
     if (!c.made) {
-        for (int i = 0; i < K0Chain::RING; ++i) { HIP_TRY(ctx, hipEventCreateWithFlags(&c.ev[i], hipEventDisableTiming)); c.gen[i] = 0; }
+        for (int i = 0; i < K0Chain::RING; ++i) {
+            HIP_TRY(ctx, hipEventCreateWithFlags(&c.ev[i], hipEventDisableTiming));
+            c.gen[i] = c.dropped[i] = c.left[i] = 0;
+        }
         c.made = true;
     }
     const unsigned long long t = c.next++;
     *ticket = t;
-    const int m = std::min(max_in_flight, K0Chain::RING / 2);
+    const int m = std::max(1, std::min(max_in_flight, K0Chain::RING / 2));
     if (t >= static_cast<unsigned long long>(m)) {
         const unsigned long long w = t - static_cast<unsigned long long>(m);
-        if (c.gen[w % K0Chain::RING] == w + 1) HIP_TRY(ctx, hipStreamWaitEvent(st, c.ev[w % K0Chain::RING], 0));
+        if (!c.closed(w)) {
+            ++c.host_waits;
+            // (bounded: a thread that died between its ticket and its record must not stop the device's other calls for good)
+            if (!c.cv.wait_for(lk, std::chrono::milliseconds(200), [&] { return c.closed(w); })) ++c.gave_up;
+        }
+        if (c.gen[w % K0Chain::RING] == w + 1) {
+            const hipError_t e = hipStreamWaitEvent(st, c.ev[w % K0Chain::RING], 0);
+            if (e != hipSuccess) {
+                c.close(t, false);
+                return fail(ctx, PS_ERR_HIP, "hipStreamWaitEvent (K0 gate) failed: %s", hipGetErrorString(e));
+            }
+        }
     }
+    c.left[t % K0Chain::RING] = t + 1;
+    c.open_max = std::max(c.open_max, ++c.open);
     return PS_OK;
 }
 int chain_publish(ps_ctx *ctx, int device, hipStream_t st, unsigned long long ticket)     // K0 has been queued on st
 {
     K0Chain &c = g_chain[device & 15];
     std::lock_guard<std::mutex> lk(c.mu);
-    HIP_TRY(ctx, hipEventRecord(c.ev[ticket % K0Chain::RING], st));
-    c.gen[ticket % K0Chain::RING] = ticket + 1;
+    const hipError_t e = hipEventRecord(c.ev[ticket % K0Chain::RING], st);
+    c.close(ticket, e == hipSuccess);
+    if (e != hipSuccess) return fail(ctx, PS_ERR_HIP, "hipEventRecord (K0 gate) failed: %s", hipGetErrorString(e));
     return PS_OK;
+}
+// the call gives its ticket up (it failed between chain_enter and its record): whoever waits for it goes on without a wait
+void chain_drop(ps_ctx *ctx)
+{
+    if (!ctx->chain_held) return;
+    ctx->chain_held = false;
+    K0Chain &c = g_chain[ctx->device & 15];
+    std::lock_guard<std::mutex> lk(c.mu);
+    c.close(ctx->chain_ticket, false);
 }
 // status word + work counters live in ctx->small: [0] status (u32, padded to 8), [1..3] work, [4] dense count
 // (hdr: the stitch header lives behind the counters so that one copy brings both back)
@@ -1084,7 +1130,11 @@ template <int FLAGS> int launch_k0(ps_ctx *ctx, const DevCfg &cfg, hipStream_t s
     }
 #endif
     if (!queued) enqueue_k0<FLAGS, 2, 2>(ctx, cfg, st, k, k0_grid, k0_grp);
-    HIP_TRY(ctx, hipGetLastError());
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) {
+        chain_drop(ctx);                               // (nobody waits for a K0 that was never queued)
+        return fail(ctx, PS_ERR_HIP, "K0 launch failed: %s", hipGetErrorString(le));
+    }
     return PS_OK;
 }
 // K0 is behind this point of st: the call M tickets later waits for it on the device
@@ -1451,7 +1501,7 @@ int device_stitch_batch(ps_ctx *ctx, const DevCfg &cfg_in, int bs_mode, const in
                         std::chrono::steady_clock::time_point t_begin, bool digest_ready = false)
 {
     const int rc = device_stitch_batch_(ctx, cfg_in, bs_mode, ev_start, ev_len, n_ev, mw, W, d_bounds, cap, h_bounds_off, d_stats, t_begin, digest_ready);
-    ctx->chain_held = false;
+    chain_drop(ctx);                                    // (a call that failed between its ticket and its record gives the ticket up)
     return rc;
 }
 }  // namespace
@@ -1531,6 +1581,16 @@ void diag_env(ps_ctx *ctx)
 }  // namespace
 #endif
 
+namespace {
+// The hardware queues of the process: the HIP runtime reads GPU_MAX_HW_QUEUES when it starts and maps every stream onto that
+// many queues; the library reads it once as well (and never sets it) -- the one variable of the environment it looks at.
+int process_hw_queues()
+{
+    static const int q = hw_queues_parse(std::getenv("GPU_MAX_HW_QUEUES"));
+    return q;
+}
+}  // namespace
+
 extern "C" {
 
 const char *ps_version(void)
@@ -1581,6 +1641,7 @@ int ps_create(int device, void *stream, ps_ctx **out)
 void ps_destroy(ps_ctx *ctx)
 {
     if (!ctx) return;
+    chain_drop(ctx);
     delete ctx;
 }
 
@@ -1642,16 +1703,20 @@ int ps_set_option(ps_ctx *ctx, const char *name, int64_t value)
     // that must SEE the helpers work; only for a call that has the chip to itself (a helper then waits for nobody)
     else if (n == "lat_help" && value >= 0 && value <= 2) ctx->lat_help = static_cast<int>(value);
     // shared_device: the number of contexts that share this device (a pool of host threads, include/poreseg.h) -- one call that sets
-    // what engine.StreamPool set by hand until round 5: n <= 1 a lone context (one-shot K0, helpers on, no admission), n > 1
-    // persistent K0 at one wave per SIMD, no helpers, and for n > 3 at most three K0s in flight on the device
+    // what engine.StreamPool set by hand until round 5.  Of n contexts min(n, hardware queues) calls execute at a time: the call
+    // is planned for that many (ps_pool_plan, pool_plan.hpp), but it is a pooled call (shared_n: no_look_ahead) whenever n > 1
     else if (n == "shared_device" && value >= 0 && value <= 4096) {
-        const bool sh = value > 1;
+        ps_pool_plan_t plan;
+        if (pool_plan(static_cast<int>(value), ctx->hw_queues > 0 ? ctx->hw_queues : process_hw_queues(), &plan) != PS_OK)
+            return fail(ctx, PS_ERR_ARG, "shared_device: no plan for %lld contexts", static_cast<long long>(value));
         ctx->shared_n = static_cast<int>(value);
         ctx->la_keep = 0;
-        ctx->k0_waves = sh ? 1 : 0;
-        ctx->lat_help = sh ? 0 : 1;
-        ctx->k0_admit = value > 3 ? 3 : 0;
+        ctx->k0_waves = plan.k0_waves;
+        ctx->lat_help = plan.lat_help;
+        ctx->k0_admit = plan.k0_admit;
     }
+    // hw_queues: the hardware queues the next shared_device plans for (0: the process's own, GPU_MAX_HW_QUEUES) -- tests, tools
+    else if (n == "hw_queues" && value >= 0 && value <= HW_QUEUES_MAX) ctx->hw_queues = static_cast<int>(value);
     else if (n == "hmm_bp_budget" && value >= 1) ctx->hmm.bp_budget = value;
     else if (n == "hmm_fb_budget" && value >= 1) ctx->hmm.fb_budget = value;
     else if (n == "pairwise_budget" && value >= 1) ctx->pw.budget = value;
@@ -1701,6 +1766,34 @@ int ps_set_option(ps_ctx *ctx, const char *name, int64_t value)
     else if (n == "spine_nt" && (value == 256 || value == 512 || value == 1024)) ctx->spine_nt = static_cast<int>(value);
     else if (n == "tree_nt" && (value == 256 || value == 512)) ctx->tree_nt = static_cast<int>(value);
     else return fail(ctx, PS_ERR_ARG, "unknown option or value: %s", name);
+    return PS_OK;
+}
+
+int ps_get_option(const ps_ctx *ctx, const char *name, int64_t *value)
+{
+    if (!ctx || !name || !value) return PS_ERR_ARG;
+    const std::string n(name);
+    if (n == "k0_waves") *value = ctx->k0_waves;
+    else if (n == "k0_admit") *value = ctx->k0_admit;
+    else if (n == "lat_help") *value = ctx->lat_help;
+    else if (n == "shared_device") *value = ctx->shared_n;
+    else if (n == "hw_queues") *value = ctx->hw_queues;
+    else return PS_ERR_ARG;
+    return PS_OK;
+}
+
+int ps_pool_plan(int32_t n_contexts, int32_t hw_queues, ps_pool_plan_t *out) { return pool_plan(n_contexts, hw_queues, out); }
+
+int ps_hw_queues(void) { return process_hw_queues(); }
+
+int ps_gate_stats(int device, int64_t *out, int32_t n_out, int reset)
+{
+    if (device < 0 || device >= 16 || (!out && n_out > 0) || n_out < 0) return PS_ERR_ARG;
+    K0Chain &c = g_chain[device];
+    std::lock_guard<std::mutex> lk(c.mu);
+    const int64_t v[5] = {static_cast<int64_t>(c.next), c.open, c.open_max, c.host_waits, c.gave_up};
+    for (int i = 0; i < n_out; ++i) out[i] = i < 5 ? v[i] : 0;
+    if (reset) { c.open_max = c.open; c.host_waits = 0; c.gave_up = 0; }
     return PS_OK;
 }
 
@@ -1916,7 +2009,7 @@ static int begin_segment_call(ps_ctx *ctx, const void *d_samples, const ps_sampl
                               const int64_t *ev_start, const int64_t *ev_len, int32_t n_ev, SegCall *c)
 {
     c->t_begin = std::chrono::steady_clock::now();
-    ctx->chain_held = false;                           // (a ticket of the K0 chain that an earlier call did not record is forgotten)
+    chain_drop(ctx);                                   // (a ticket of the K0 chain that an earlier call did not record is given up)
     double min_gain = 0;
     int rc = ps_min_gain(params, &min_gain);
     if (rc) return fail(ctx, rc, "reference assertion failed (cparsers.pyx:69-76)");

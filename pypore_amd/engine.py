@@ -146,6 +146,14 @@ class Context(object):
         with self.lock:
             _lib.check(self.L.ps_set_option(self.handle, name.encode(), int(value)), self.handle)
 
+    def get_option(self, name):
+        """ps_get_option: "k0_waves", "k0_admit", "lat_help" as they stand, "shared_device" / "hw_queues" as last set."""
+        out = ctypes.c_int64()
+        self.L.ps_get_option.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64)]
+        with self.lock:
+            _lib.check(self.L.ps_get_option(self.handle, name.encode(), ctypes.byref(out)), self.handle)
+        return int(out.value)
+
     def seq_ms(self):
         """Device time of the most recent segment call (HIP events, first upload .. last result copy), in ms: the
         light accessor for timed loops (timings() builds a dict of everything)."""
@@ -866,9 +874,11 @@ class StreamPool(object):
     then waits for it on its way out of the C call -- 0.33 instead of 0.35-0.43 ms per 1e8-sample batch over runs of
     400-2000 batches (tools/pool_stalls.py).
 
-    HIP maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4): set it to at least the number of
-    contexts before the runtime starts (bench.py: 16).  Round 4, 1e8-sample trace: 4 / 8 / 16 contexts in flight deliver a
-    batch every 0.216 / 0.202 / 0.189 ms."""
+    HIP maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4), and streams that share a queue run their
+    kernels one after the other: of T contexts min(T, queues) calls execute at a time.  The library plans each pooled call
+    for that many ("shared_device", ps_pool_plan: DESIGN.md section 6 has the table), so the pool needs nothing set; a host
+    that wants sixteen calls in flight exports GPU_MAX_HW_QUEUES=16 before the runtime starts.  Round 4, 1e8-sample trace,
+    as many queues as contexts: 4 / 8 / 16 contexts in flight deliver a batch every 0.216 / 0.202 / 0.189 ms."""
 
     def __init__(self, device=None, streams=2, overrides=None):
         """overrides: ps_set_option name -> value applied to the pool's contexts while it runs, on top of "shared_device"
@@ -919,7 +929,8 @@ class StreamPool(object):
             self._inbox[t].put(None)
         self._threads = []
 
-    # What a context that shares the chip wants (ps_set_option "shared_device" n, include/poreseg.h; measured in round 5):
+    # What a context that shares the chip wants is decided in the library (ps_set_option "shared_device" n -> ps_pool_plan for
+    # min(n, hardware queues) calls executing at a time, include/poreseg.h).  With sixteen calls in flight (measured in round 5):
     #   * K0 as a persistent kernel at one wave per SIMD: beside the scan waves of other calls a K0 that takes every wave slot
     #     it can get is in the way (sixteen in flight: 0.193 -> 0.170 ms per step); a lone call is faster with the one-shot K0;
     #   * no look-ahead helpers: with sixteen calls in flight the other calls are the better use of an idle workgroup (a trace
