@@ -747,6 +747,41 @@ int ps_get_near_ties(const ps_ctx *ctx, ps_near_tie *out, int32_t cap, int64_t *
 int ps_synth_trace(ps_ctx *ctx, void *d_out, int32_t dtype, int64_t n, uint64_t seed,
                    const int64_t *h_seg_end, const int32_t *h_level_counts, int64_t nseg);
 
+/* The reference's state parsers (parsers.py:572-679) on the device: what they RETURN, quirks included.
+ * Both take float64 currents in the batch layout of ps_statsplit_f64 (event e = [h_ev_start[e], h_ev_start[e] + h_ev_len[e]),
+ * at most 2^30 samples each) and write spans: (start, end) int32 pairs, positions from the event's start, event after event.
+ *   d_spans     2 * cap int32 values, device
+ *   h_span_off  n_ev + 1 entries: event e's spans are h_span_off[e] .. h_span_off[e + 1]; when cap is too small the call
+ *               returns PS_ERR_CAPACITY with the required size in h_span_off[n_ev] and writes no span
+ * PS_ERR_ARG (message in ps_last_error): a negative start or length, an event longer than 2^30 samples.
+ *
+ * ps_snakebase_f64 -- snakebase_parser.parse: with m = n - 1 and low the ascending positions j in [0, m) where
+ * |current[j + 1] - current[j]| < 1e-3 (a NaN difference is not), the spans are (low[0], low[1]), (low[2], low[3]), ... and,
+ * when low has an odd number of entries, (low[-1], m).  The parser's threshold takes no part in what the reference returns,
+ * so it is no argument.  n of 0 or 1: no span.  No span is empty. */
+int ps_snakebase_f64(ps_ctx *ctx, const double *d_current, const int64_t *h_ev_start, const int64_t *h_ev_len, int32_t n_ev,
+                     int32_t *d_spans, int64_t cap, int64_t *h_span_off);
+
+/* ps_filter_derivative_f64 -- FilterDerivativeSegmenter.parse: y = filtfilt(bessel(1, cutoff_freq / (sampling_freq / 2)),
+ * current) (the kernels of ps_filter_bessel, one event after the other on the context's stream), deriv[j] = |y[j + 1] - y[j]|,
+ * blocks[j] = deriv[j] > low_threshold, tics = the j + 1 with blocks[j + 1] != blocks[j], pairs (tics[0], tics[1]), (tics[2],
+ * tics[3]), ... (an unpaired last tic is dropped; when blocks[0] is set the pairs are the gaps between the blocks, as in the
+ * reference).  A pair (s, t) is kept when np.argmax(deriv[s:t]) > high_threshold -- the INDEX of the first maximum, as the
+ * reference has it: with h = floor(high_threshold), max(deriv[s + h + 1 : t]) > max(deriv[s : s + h + 1]), strictly; an empty
+ * right part is not kept, a negative high_threshold keeps every pair.  With the kept pairs (s_1, t_1) .. (s_k, t_k) the spans
+ * are [0, s_1), [t_1, s_2), ..., [t_k, n); none kept: [0, n).  An empty event (prefiltered only) has no span.
+ * prefiltered 1: d_current is y itself and no filter runs (cutoff_freq, sampling_freq unused) -- the decisions are then the
+ * reference's bit for bit; with the filter they are the reference's wherever a decision's margin exceeds the filter's
+ * distance from scipy (1e-11 of max|y|, docs/CALLERS.md).  Non-finite input is undefined, as it is in scipy.
+ * PS_ERR_ARG also for: an event of n <= 6 samples when prefiltered is 0 (scipy's padlen), a cutoff outside (0, Nyquist), a
+ * NaN threshold, prefiltered other than 0 / 1. */
+typedef struct ps_filter_derivative_params {
+    double low_threshold, high_threshold, cutoff_freq, sampling_freq;
+    int32_t prefiltered;
+} ps_filter_derivative_params;
+int ps_filter_derivative_f64(ps_ctx *ctx, const double *d_current, const int64_t *h_ev_start, const int64_t *h_ev_len, int32_t n_ev,
+                             const ps_filter_derivative_params *params, int32_t *d_spans, int64_t cap, int64_t *h_span_off);
+
 #ifdef __cplusplus
 }
 #endif

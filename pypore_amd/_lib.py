@@ -20,7 +20,7 @@ EXPORTS = ["ps_version", "ps_device_count", "ps_create", "ps_destroy", "ps_last_
            "ps_best_single_split", "ps_score_window", "ps_get_timings", "ps_synth_trace", "ps_filter_bessel",
            "ps_requantise", "ps_grid_check_f64", "ps_grid_counts_f64", "ps_narrow_f64", "ps_filter_requantise_batch", "ps_align_batch", "ps_audit_bounds", "ps_counters",
            "ps_get_near_ties", "ps_hmm_batch", "ps_hmm_expect", "ps_hmm_posterior", "ps_hmm_sample", "ps_pairwise_scores", "ps_pairwise_batch",
-           "ps_statsplit_f64", "ps_statsplit_prefix_f64", "ps_live_bytes", "ps_trf_split_batch",
+           "ps_statsplit_f64", "ps_statsplit_prefix_f64", "ps_snakebase_f64", "ps_filter_derivative_f64", "ps_live_bytes", "ps_trf_split_batch",
            "ps_pool_plan", "ps_hw_queues", "ps_gate_stats", "ps_get_option"]
 PS_STATSPLIT_STEPWISE, PS_STATSPLIT_SLANTED = 0, 1
 PS_HMM_VITERBI, PS_HMM_FORWARD, PS_HMM_BACKWARD = 0, 1, 2
@@ -42,6 +42,13 @@ class StatSplitParams(ctypes.Structure):
     """ps_statsplit_params: StatSplit's widths, its threshold min_gain_per_sample * window_width, use_log and the splitter."""
     _fields_ = [("min_width", ctypes.c_int32), ("max_width", ctypes.c_int32), ("window_width", ctypes.c_int32),
                 ("threshold", ctypes.c_double), ("use_log", ctypes.c_int32), ("splitter", ctypes.c_int32)]
+
+
+class FilterDerivativeParams(ctypes.Structure):
+    """ps_filter_derivative_params: FilterDerivativeSegmenter's four attributes; prefiltered 1: the input is the filtered
+    current itself."""
+    _fields_ = [("low_threshold", ctypes.c_double), ("high_threshold", ctypes.c_double), ("cutoff_freq", ctypes.c_double),
+                ("sampling_freq", ctypes.c_double), ("prefiltered", ctypes.c_int32)]
 
 
 class SampleFormat(ctypes.Structure):
@@ -148,6 +155,8 @@ def lib():
     L.ps_audit_bounds.argtypes = [vp, vp, P(SampleFormat), i64, P(SplitParams), P(i32), i32, P(dbl)]
     L.ps_statsplit_f64.argtypes = [vp, vp, P(i64), P(i64), i32, P(i64), P(i64), P(StatSplitParams), vp, i64, P(i64)]
     L.ps_statsplit_prefix_f64.argtypes = [vp, vp, i64, vp, vp, vp]
+    L.ps_snakebase_f64.argtypes = [vp, vp, P(i64), P(i64), i32, vp, i64, P(i64)]
+    L.ps_filter_derivative_f64.argtypes = [vp, vp, P(i64), P(i64), i32, P(FilterDerivativeParams), vp, i64, P(i64)]
     _lib = L
     return L
 

@@ -44,6 +44,7 @@
 #include "seg_hmm.hpp"
 #include "seg_ingest.hpp"
 #include "seg_statsplit.hpp"
+#include "seg_state.hpp"
 #include "pool_plan.hpp"
 
 using namespace ps;
@@ -199,7 +200,7 @@ struct ps_ctx {
     } tile_cache;
     DevBuf bsum, ev_info, chunk_mabs, ev_boff, blk_mm, grp, up_dev;
     // The segmentation chain's own buffers and options are flat members.  The state of every self-contained feature stands
-    // together in a sub-struct (filt, align, pw, trf, ss, nt, hmm): its buffers, its budgets, its host-side caches.  A new feature
+    // together in a sub-struct (filt, align, pw, trf, ss, sp, nt, hmm): its buffers, its budgets, its host-side caches.  A new feature
     // adds its group here and nowhere else: the buffers free themselves with the context.
     struct {                // Bessel filter (ps_filter_bessel, ps_filter_requantise_batch)
         DevBuf fwd, agg, zin;
@@ -220,6 +221,10 @@ struct ps_ctx {
     // StatSplit (ps_statsplit_f64): per-event tables, prefix sums (c, c2, ct), boundary slots, interval stacks, counts +
     // status word, output offsets
     struct { DevBuf tab, pre, tmp, stack, cnt, off; } ss;
+    // State parsers (ps_snakebase_f64, ps_filter_derivative_f64): the compaction's tables (tab, tab2), predicate mask, tile counts
+    // and their scan, hits before each event of the first / second compaction (off1, off2), hit list (hits: low / tics), pair
+    // offsets, keep flags, kept pairs, the filtered current, event lengths, span offsets
+    struct { DevBuf tab, tab2, mask, cnt, excl, off1, off2, hits, pair_off, keep, kept, y, len, span_off; } sp;
     // Near-tie log of the segment calls (DevCfg::nt_log, ps_get_near_ties): nt.cap records (option near_tie_log, 0: off), allocated
     // with the first call that logs.  nt.seen: records the last segment call counted (-1: not counted), nt.call_cap the capacity
     // it ran with; nt.ev_start / nt.ev_len: its events, kept only when it logged any (the records are mapped to them on request).
@@ -3938,6 +3943,231 @@ int ps_hmm_sample(ps_ctx *ctx, const ps_hmm_model *model, const ps_hmm_sample_ta
     if (short_obs || short_path)
         return fail(ctx, PS_ERR_CAPACITY, "%lld observation slots and %lld path slots are too small (d_len and d_path_len hold the lengths)",
                     static_cast<long long>(short_obs), static_cast<long long>(short_path));
+    return PS_OK;
+}
+
+}  // extern "C"
+
+// ---- the state parsers: snakebase and filter-derivative (seg_state.hpp) -------------------------------------------------------
+namespace {
+
+// One compaction's tables on the device: start, npos, tile_off (n_ev + 1) in one copy; *n_tiles = its tiles.  `tab` must
+// outlive the call's next synchronisation (pageable source).
+int sp_upload(ps_ctx *ctx, DevBuf &buf, std::vector<int64_t> &tab, const int64_t *start, const int64_t *npos, int32_t n_ev,
+              SpEvents *ev, int64_t *n_tiles)
+{
+    const size_t n = static_cast<size_t>(n_ev);
+    tab.assign(3 * n + 1, 0);
+    int64_t tiles = 0;
+    for (size_t e = 0; e < n; ++e) {
+        tab[e] = start[e]; tab[n + e] = npos[e]; tab[2 * n + e] = tiles;
+        tiles += (npos[e] + SP_TILE - 1) / SP_TILE;
+    }
+    tab[3 * n] = tiles;
+    if (tiles > INT32_MAX) return fail(ctx, PS_ERR_ARG, "too many samples for one call");
+    HIP_TRY(ctx, buf.reserve(tab.size() * sizeof(int64_t)));
+    HIP_TRY(ctx, hipMemcpyAsync(buf.p, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    const int64_t *t = buf.as<int64_t>();
+    ev->start = t; ev->npos = t + n; ev->tile_off = t + 2 * n; ev->n_ev = n_ev;
+    *n_tiles = tiles;
+    return PS_OK;
+}
+
+// Pass 1, the scan and the hits before each event (d_off, n_ev + 1 entries) of one compaction, queued; h_off receives d_off
+// with the caller's next synchronisation.
+template <class Pred>
+int sp_count(ps_ctx *ctx, Pred pred, const SpEvents &ev, int64_t n_tiles, DevBuf &off, std::vector<int64_t> &h_off)
+{
+    const size_t n1 = static_cast<size_t>(ev.n_ev) + 1;
+    h_off.assign(n1, 0);
+    HIP_TRY(ctx, off.reserve(n1 * sizeof(int64_t)));
+    if (n_tiles == 0) {
+        HIP_TRY(ctx, hipMemsetAsync(off.p, 0, n1 * sizeof(int64_t), ctx->stream));
+        return PS_OK;
+    }
+    const size_t nt = static_cast<size_t>(n_tiles);
+    HIP_TRY(ctx, ctx->sp.mask.reserve(nt * SP_WORDS * sizeof(unsigned long long)));
+    HIP_TRY(ctx, ctx->sp.cnt.reserve(nt * sizeof(uint32_t)));
+    HIP_TRY(ctx, ctx->sp.excl.reserve((nt + 1) * sizeof(int64_t)));
+    hipLaunchKernelGGL(sp_count_kernel<Pred>, dim3(static_cast<unsigned>(n_tiles)), dim3(SP_NT), 0, ctx->stream, pred, ev,
+                       ctx->sp.mask.as<unsigned long long>(), ctx->sp.cnt.as<uint32_t>());
+    hipLaunchKernelGGL(sp_scan_kernel, dim3(1), dim3(SP_SCAN_NT), 0, ctx->stream, ctx->sp.cnt.as<uint32_t>(), n_tiles, ctx->sp.excl.as<int64_t>());
+    hipLaunchKernelGGL(sp_event_off_kernel, dim3(static_cast<unsigned>((n1 + 255) / 256)), dim3(256), 0, ctx->stream, ev,
+                       ctx->sp.excl.as<int64_t>(), off.as<int64_t>());
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(h_off.data(), off.p, n1 * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    return PS_OK;
+}
+
+// Pass 2 of the compaction sp_count queued last: its `total` hits into out (positions + add)
+int sp_scatter(ps_ctx *ctx, const SpEvents &ev, int64_t n_tiles, int64_t total, int32_t add, DevBuf &out)
+{
+    HIP_TRY(ctx, out.reserve(static_cast<size_t>(std::max<int64_t>(total, 1)) * sizeof(int32_t)));
+    if (total == 0) return PS_OK;
+    hipLaunchKernelGGL(sp_scatter_kernel, dim3(static_cast<unsigned>(n_tiles)), dim3(SP_NT), 0, ctx->stream, ev,
+                       ctx->sp.mask.as<unsigned long long>(), ctx->sp.excl.as<int64_t>(), add, out.as<int32_t>());
+    HIP_TRY(ctx, hipGetLastError());
+    return PS_OK;
+}
+
+int sp_args(ps_ctx *ctx, const double *d_current, const int64_t *h_ev_start, const int64_t *h_ev_len, int32_t n_ev, int32_t *d_spans,
+            int64_t cap, int64_t *h_span_off, int64_t min_len)
+{
+    if (!h_ev_start || !h_ev_len || !h_span_off || n_ev < 0 || cap < 0 || (cap > 0 && !d_spans))
+        return fail(ctx, PS_ERR_ARG, "null/negative argument");
+    int64_t total = 0;
+    for (int e = 0; e < n_ev; ++e) {
+        const int64_t len = h_ev_len[e];
+        if (len < 0 || h_ev_start[e] < 0) return fail(ctx, PS_ERR_ARG, "event %d: negative start or length", e);
+        if (len > (1ll << 30))
+            return fail(ctx, PS_ERR_ARG, "event %d length %lld out of range (2^30 samples at most)", e, static_cast<long long>(len));
+        if (len < min_len)
+            return fail(ctx, PS_ERR_ARG, "event %d: the length of the input must be greater than padlen, which is %d", e, FILT_PAD);
+        total += len;
+    }
+    for (int e = 0; e <= n_ev; ++e) h_span_off[e] = 0;
+    if (total > 0 && !d_current) return fail(ctx, PS_ERR_ARG, "d_current is NULL");
+    return PS_OK;
+}
+
+// The spans per event are known: h_span_off from the counts, the capacity check, the offsets on the device.
+int sp_span_offsets(ps_ctx *ctx, const std::vector<int64_t> &n_spans, int64_t cap, int64_t *h_span_off)
+{
+    const size_t n = n_spans.size();
+    for (size_t e = 0; e < n; ++e) h_span_off[e + 1] = h_span_off[e] + n_spans[e];
+    const int64_t total = h_span_off[n];
+    if (total > cap)
+        return fail(ctx, PS_ERR_CAPACITY, "span capacity %lld < required %lld", static_cast<long long>(cap), static_cast<long long>(total));
+    if (total == 0) return PS_OK;
+    HIP_TRY(ctx, ctx->sp.span_off.reserve((n + 1) * sizeof(int64_t)));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->sp.span_off.p, h_span_off, (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    return PS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ps_snakebase_f64(ps_ctx *ctx, const double *d_current, const int64_t *h_ev_start, const int64_t *h_ev_len, int32_t n_ev,
+                     int32_t *d_spans, int64_t cap, int64_t *h_span_off)
+{
+    if (!ctx) return PS_ERR_ARG;
+    if (int rc = sp_args(ctx, d_current, h_ev_start, h_ev_len, n_ev, d_spans, cap, h_span_off, 0)) return rc;
+    if (n_ev == 0) return PS_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t n = static_cast<size_t>(n_ev);
+    std::vector<int64_t> npos(n), tab, hit_off;
+    for (size_t e = 0; e < n; ++e) npos[e] = std::max<int64_t>(0, h_ev_len[e] - 1);      // m = n - 1 differences
+    SpEvents ev;
+    int64_t n_tiles = 0;
+    if (int rc = sp_upload(ctx, ctx->sp.tab, tab, h_ev_start, npos.data(), n_ev, &ev, &n_tiles)) return rc;
+    if (int rc = sp_count(ctx, SnakePred{d_current}, ev, n_tiles, ctx->sp.off1, hit_off)) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<int64_t> n_spans(n);
+    for (size_t e = 0; e < n; ++e) n_spans[e] = (hit_off[e + 1] - hit_off[e] + 1) / 2;
+    if (int rc = sp_span_offsets(ctx, n_spans, cap, h_span_off)) return rc;
+    const int64_t total = h_span_off[n_ev];
+    if (total == 0) return PS_OK;
+    if (int rc = sp_scatter(ctx, ev, n_tiles, hit_off[n], 0, ctx->sp.hits)) return rc;
+    hipLaunchKernelGGL(sp_snake_spans_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, ctx->stream, ev,
+                       ctx->sp.hits.as<int32_t>(), ctx->sp.off1.as<int64_t>(), ctx->sp.span_off.as<int64_t>(), total, d_spans);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return PS_OK;
+}
+
+int ps_filter_derivative_f64(ps_ctx *ctx, const double *d_current, const int64_t *h_ev_start, const int64_t *h_ev_len, int32_t n_ev,
+                             const ps_filter_derivative_params *params, int32_t *d_spans, int64_t cap, int64_t *h_span_off)
+{
+    if (!ctx) return PS_ERR_ARG;
+    if (!params) return fail(ctx, PS_ERR_ARG, "null/negative argument");
+    const bool filter = params->prefiltered == 0;
+    if (params->prefiltered != 0 && params->prefiltered != 1) return fail(ctx, PS_ERR_ARG, "prefiltered must be 0 or 1");
+    if (std::isnan(params->low_threshold) || std::isnan(params->high_threshold)) return fail(ctx, PS_ERR_ARG, "a threshold is NaN");
+    if (filter) {
+        const double wn = params->cutoff_freq / (params->sampling_freq / 2.0);
+        if (!(wn > 0.0) || !(wn < 1.0)) return fail(ctx, PS_ERR_ARG, "cutoff must lie strictly between 0 and the Nyquist frequency");
+    }
+    if (int rc = sp_args(ctx, d_current, h_ev_start, h_ev_len, n_ev, d_spans, cap, h_span_off, filter ? FILT_PAD + 1 : 0)) return rc;
+    if (n_ev == 0) return PS_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t n = static_cast<size_t>(n_ev);
+    // np.argmax(...) > high_threshold: the index is at least h1 = floor(high_threshold) + 1; every index when it is negative
+    const double ht = params->high_threshold;
+    const int32_t h1 = ht < 0.0 ? 0 : (ht >= 2147483646.0 ? INT32_MAX : static_cast<int32_t>(std::floor(ht)) + 1);
+    // 1. y: the caller's (prefiltered) or the order-1 Bessel filtfilt of every event, packed, the launches queued back to
+    //    back on the context's stream (float64 input has the per-event entry only)
+    const double *d_y = d_current;
+    std::vector<int64_t> start(h_ev_start, h_ev_start + n);
+    if (filter) {
+        std::vector<int> by_len(n);
+        int64_t total_len = 0;
+        for (size_t e = 0; e < n; ++e) { start[e] = total_len; total_len += h_ev_len[e]; by_len[e] = static_cast<int>(e); }
+        std::sort(by_len.begin(), by_len.end(), [&](int a, int b) { return h_ev_len[a] > h_ev_len[b]; });   // (scratch grows once)
+        HIP_TRY(ctx, ctx->sp.y.reserve(static_cast<size_t>(total_len) * sizeof(double)));
+        HIP_TRY(ctx, ctx->h_small.reserve(sizeof(SmallLayout)));
+        ctx->small_clean = false;
+        HIP_TRY(ctx, hipMemsetAsync(ctx->small.p, 0, sizeof(SmallLayout), ctx->stream));
+        const ps_sample_format f64 = {PS_DTYPE_F64, 0, 1.0};
+        ctx->defer_sync = true;
+        int rc = PS_OK;
+        for (size_t k = 0; k < n && rc == PS_OK; ++k) {
+            const int e = by_len[k];
+            rc = ps_filter_bessel(ctx, d_current + h_ev_start[e], &f64, h_ev_len[e], 1, params->cutoff_freq, params->sampling_freq,
+                                  ctx->sp.y.as<double>() + start[e]);
+        }
+        ctx->defer_sync = false;
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        d_y = ctx->sp.y.as<double>();
+    }
+    // 2. the tics: j + 1 where blocks[j + 1] != blocks[j], j in [0, n - 2)
+    std::vector<int64_t> npos(n), tab, tab2, tic_off, kept_off(n + 1, 0);
+    for (size_t e = 0; e < n; ++e) npos[e] = std::max<int64_t>(0, h_ev_len[e] - 2);
+    SpEvents ev;
+    int64_t n_tiles = 0;
+    if (int rc = sp_upload(ctx, ctx->sp.tab, tab, start.data(), npos.data(), n_ev, &ev, &n_tiles)) return rc;
+    if (int rc = sp_count(ctx, FdPred{d_y, params->low_threshold}, ev, n_tiles, ctx->sp.off1, tic_off)) return rc;
+    if (filter) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_small.p, ctx->small.p, sizeof(SmallLayout), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (filter) if (int rc = check_status(ctx, static_cast<unsigned>(ctx->h_small.as<SmallLayout>()->status))) return rc;
+    if (int rc = sp_scatter(ctx, ev, n_tiles, tic_off[n], 1, ctx->sp.hits)) return rc;
+    // 3. the pairs (tics[2 i], tics[2 i + 1]), an unpaired last tic dropped: judged, the kept ones compacted
+    std::vector<int64_t> pair_off(n + 1, 0), n_pairs(n);
+    for (size_t e = 0; e < n; ++e) { n_pairs[e] = (tic_off[e + 1] - tic_off[e]) / 2; pair_off[e + 1] = pair_off[e] + n_pairs[e]; }
+    const int64_t pairs = pair_off[n];
+    HIP_TRY(ctx, ctx->sp.pair_off.reserve((n + 1) * sizeof(int64_t)));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->sp.pair_off.p, pair_off.data(), (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    SpPairs pr;
+    pr.start = ev.start; pr.tic_off = ctx->sp.off1.as<int64_t>(); pr.pair_off = ctx->sp.pair_off.as<int64_t>(); pr.n_ev = n_ev;
+    SpEvents ev2 = {};
+    int64_t n_tiles2 = 0;
+    if (pairs > 0) {
+        HIP_TRY(ctx, ctx->sp.keep.reserve(static_cast<size_t>(pairs)));
+        const unsigned jgrid = static_cast<unsigned>(std::min<int64_t>((pairs + 3) / 4, 1 << 20));
+        hipLaunchKernelGGL(sp_judge_kernel, dim3(jgrid), dim3(256), 0, ctx->stream, d_y, pr, ctx->sp.hits.as<int32_t>(), pairs, h1,
+                           ctx->sp.keep.as<uint8_t>());
+        HIP_TRY(ctx, hipGetLastError());
+        if (int rc = sp_upload(ctx, ctx->sp.tab2, tab2, pair_off.data(), n_pairs.data(), n_ev, &ev2, &n_tiles2)) return rc;
+        if (int rc = sp_count(ctx, KeepPred{ctx->sp.keep.as<uint8_t>()}, ev2, n_tiles2, ctx->sp.off2, kept_off)) return rc;
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    } else {
+        HIP_TRY(ctx, ctx->sp.off2.reserve((n + 1) * sizeof(int64_t)));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->sp.off2.p, 0, (n + 1) * sizeof(int64_t), ctx->stream));
+    }
+    // 4. the spans [0, s_1), [t_1, s_2), ..., [t_k, n): one more than the kept pairs (an empty event has none)
+    std::vector<int64_t> n_spans(n);
+    for (size_t e = 0; e < n; ++e) n_spans[e] = h_ev_len[e] > 0 ? kept_off[e + 1] - kept_off[e] + 1 : 0;
+    if (int rc = sp_span_offsets(ctx, n_spans, cap, h_span_off)) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    const int64_t total = h_span_off[n_ev];
+    if (total == 0) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); return PS_OK; }
+    if (int rc = sp_scatter(ctx, ev2, n_tiles2, kept_off[n], 0, ctx->sp.kept)) return rc;
+    HIP_TRY(ctx, ctx->sp.len.reserve(n * sizeof(int64_t)));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->sp.len.p, h_ev_len, n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(sp_fd_spans_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, ctx->stream, pr,
+                       ctx->sp.len.as<int64_t>(), ctx->sp.hits.as<int32_t>(), ctx->sp.kept.as<int32_t>(), ctx->sp.off2.as<int64_t>(),
+                       ctx->sp.span_off.as<int64_t>(), total, d_spans);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return PS_OK;
 }
 

@@ -395,6 +395,49 @@ class Context(object):
         _lib.check(rc, self.handle)
         return bounds[:int(boff[-1])], boff
 
+    def _spans_f64(self, call, current, ev_start, ev_len, cap, guess):
+        """The state parsers' common call: spans (n, 2) int32 CUDA tensor and span_off.  cap None: a first call sized by
+        guess(ev_len), repeated once with the size the library reports when that is too small."""
+        assert current.is_cuda and current.is_contiguous() and current.dim() == 1 and current.dtype == torch.float64
+        ev_start = np.ascontiguousarray(ev_start, dtype=np.int64)
+        ev_len = np.ascontiguousarray(ev_len, dtype=np.int64)
+        n_ev = ev_start.size
+        P64 = ctypes.POINTER(ctypes.c_int64)
+        soff = np.zeros(n_ev + 1, dtype=np.int64)
+        torch.cuda.current_stream(current.device).synchronize()
+        grow = cap is None
+        if grow:
+            cap = int(guess(ev_len))
+        while True:
+            spans = torch.empty((max(cap, 1), 2), dtype=torch.int32, device=current.device)
+            rc = call(ev_start.ctypes.data_as(P64), ev_len.ctypes.data_as(P64), n_ev, ctypes.c_void_p(spans.data_ptr()), cap,
+                      soff.ctypes.data_as(P64))
+            if rc != _lib.PS_ERR_CAPACITY:
+                break
+            if not grow:
+                raise CapacityError(int(soff[-1]), cap)
+            cap, grow = int(soff[-1]), False
+        _lib.check(rc, self.handle)
+        return spans[:int(soff[-1])], soff
+
+    @_serialised
+    def snakebase_f64(self, current, ev_start, ev_len, cap=None):
+        """ps_snakebase_f64: the spans snakebase_parser.parse returns for events [start, start + len) of a float64 CUDA
+        tensor (include/poreseg.h).  cap: spans the output may hold -- CapacityError names the size required when it is
+        too small; None: the most an event can have, a span per two samples (the normal case on ADC-grid data is not far
+        from it).  Returns (spans (n, 2) int32 CUDA tensor of (start, end), span_off)."""
+        return self._spans_f64(lambda st, ln, n, out, c, off: self.L.ps_snakebase_f64(self.handle, _ptr(current), st, ln, n, out, c, off),
+                               current, ev_start, ev_len, cap, lambda ln: (ln // 2).sum())
+
+    @_serialised
+    def filter_derivative_f64(self, current, ev_start, ev_len, params, cap=None):
+        """ps_filter_derivative_f64: the spans FilterDerivativeSegmenter.parse returns; params: _lib.FilterDerivativeParams
+        (prefiltered 1: `current` is the filtered current).  cap and the result as for snakebase_f64; None: a span per 64
+        samples, and one more call with the size the library reports when that is too small."""
+        return self._spans_f64(lambda st, ln, n, out, c, off: self.L.ps_filter_derivative_f64(self.handle, _ptr(current), st, ln, n,
+                                                                                              ctypes.byref(params), out, c, off),
+                               current, ev_start, ev_len, cap, lambda ln: ln.sum() // 64 + ln.size + 1)
+
     @_serialised
     def statsplit_prefix_f64(self, current, want_ct=True):
         """ps_statsplit_prefix_f64 (diagnostics): the prefix sums StatSplit forms of one float64 CUDA tensor -- (c, c2, ct) as

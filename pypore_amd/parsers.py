@@ -3,7 +3,8 @@
 Surface kept from the reference (PyPore/parsers.py; SURVEY.md 8 a7, a11, b): `SpeedyStatSplit` with its eight
 constructor keywords stored as attributes of the same names (:505-534) -- they are also its JSON schema --,
 `lambda_event_parser(threshold, rules)` (:124-155), `MemoryParse(starts, ends)` (:110-122) and the base `parser`
-with `to_dict` / `to_json` / `from_json` / `parse` (:34-107).  The Qt GUI hooks are UI and out of scope.
+with `to_dict` / `to_json` / `from_json` / `parse` (:34-107); beside them `StatSplit` (:220-503) and the two state
+parsers, `snakebase_parser` (:572-607) and `FilterDerivativeSegmenter` (:609-679).  The Qt GUI hooks are UI and out of scope.
 
 How it is built here: every subclass of `parser` registers itself by name (that is what `from_json` resolves),
 a parser's JSON is its public scalar attributes, and the two parsers that compute -- SpeedyStatSplit and the
@@ -15,6 +16,9 @@ import numpy as np
 
 from .core import Segment, dump_json, load_json, plain
 from .cparsers import FastStatSplit
+
+__all__ = ["parser", "MemoryParse", "lambda_event_parser", "SpeedyStatSplit", "StatSplit", "snakebase_parser",
+           "FilterDerivativeSegmenter", "FastStatSplit", "Segment"]
 
 _REGISTRY = {}
 
@@ -193,6 +197,26 @@ class SpeedyStatSplit(parser):
         return self._fast(cutoff=False).best_single_split(current)
 
 
+def _stage_f64(currents, dev):
+    """Currents (numpy arrays, anything numpy.asarray takes -- a grid-backed current gives its float64 values --, or CUDA
+    tensors) as float64 tensors on `dev`, with the host arrays the Segments are cut from."""
+    import torch
+    ts, srcs = [], []
+    for cur in currents:
+        if isinstance(cur, torch.Tensor):
+            t = cur.to(dev, torch.float64).contiguous()
+            src = cur.detach().cpu().numpy()
+        else:
+            src = cur if isinstance(cur, np.ndarray) else np.asarray(cur)
+            a = np.ascontiguousarray(src, dtype=np.float64)
+            if a.ndim != 1:
+                raise ValueError("Buffer has wrong number of dimensions (expected 1, got %d)" % a.ndim)
+            t = torch.from_numpy(a).to(dev)
+        ts.append(t)
+        srcs.append(src)
+    return ts, srcs
+
+
 class StatSplit(parser):
     """The reference's older segmenter (parsers.py:220-503; "DEPRECATED: USE SPEEDYSTATSPLIT" there, but the only one that
     splits on the variance itself and the only one with a slanted model), on the GPU (ps_statsplit_f64, include/poreseg.h).
@@ -251,19 +275,7 @@ class StatSplit(parser):
         params = self._params()
         ctx = engine.context(None)
         dev = torch.device("cuda", ctx.device)
-        ts, srcs = [], []
-        for cur in currents:
-            if isinstance(cur, torch.Tensor):
-                t = cur.to(dev, torch.float64).contiguous()
-                src = cur.detach().cpu().numpy()
-            else:
-                src = cur if isinstance(cur, np.ndarray) else np.asarray(cur)
-                a = np.ascontiguousarray(src, dtype=np.float64)
-                if a.ndim != 1:
-                    raise ValueError("Buffer has wrong number of dimensions (expected 1, got %d)" % a.ndim)
-                t = torch.from_numpy(a).to(dev)
-            ts.append(t)
-            srcs.append(src)
+        ts, srcs = _stage_f64(currents, dev)
         lens = np.array([t.numel() for t in ts], dtype=np.int64)
         lo = np.array([r[0] for r in ranges], dtype=np.int64)
         hi = np.array([r[1] for r in ranges], dtype=np.int64)
@@ -295,3 +307,86 @@ class StatSplit(parser):
         ranges = [(0, len(c)) for c in currents]
         bs, srcs = self._bounds(currents, ranges)
         return [self._segments(src, b, a, z_) for src, b, (a, z_) in zip(srcs, bs, ranges)]
+
+
+class _SpanParser(parser):
+    """What the two state parsers share: the currents of a call go to the device as one float64 array, the device returns
+    (start, end) spans per current, and the Segments are cut on the host with the keywords the reference passes."""
+
+    def _call(self, ctx, allt, starts, lens):
+        raise NotImplementedError
+
+    def _check(self, lens):
+        pass
+
+    def _spans(self, currents):
+        lens = np.array([len(c) for c in currents], dtype=np.int64)
+        self._check(lens)                                  # (before anything touches the device)
+        import torch
+        from . import engine
+        ctx = engine.context(None)
+        ts, srcs = _stage_f64(currents, torch.device("cuda", ctx.device))
+        if not lens.sum():
+            return [np.zeros((0, 2), dtype=np.int32) for _ in ts], srcs
+        allt = ts[0] if len(ts) == 1 else torch.cat(ts)
+        spans, soff = self._call(ctx, allt, np.concatenate(([0], np.cumsum(lens)))[:-1], lens)
+        sp = spans.cpu().numpy()
+        return [sp[soff[e]:soff[e + 1]] for e in range(len(ts))], srcs
+
+    @staticmethod
+    def _segments(src, spans):
+        return [Segment(current=src[a:z_], start=a) for a, z_ in spans.tolist()]
+
+    def parse(self, current):
+        (sp,), (src,) = self._spans([current])
+        return self._segments(src, sp)
+
+    def parse_batch(self, currents):
+        """Many currents in one device call (extension): [parse(c) for c in currents]."""
+        sps, srcs = self._spans(currents)
+        return [self._segments(src, sp) for src, sp in zip(srcs, sps)]
+
+
+class snakebase_parser(_SpanParser):
+    """The reference's snakebase_parser (parsers.py:572-607) on the GPU (ps_snakebase_f64, include/poreseg.h): what its
+    parse() RETURNS.  With low = the positions j where |current[j + 1] - current[j]| < 1e-3, the segments are
+    current[low[0]:low[1]], current[low[2]:low[3]], ... and, when low has an odd number of entries, current[low[-1]:n - 1];
+    `start` is the left end, in samples.  The reference also forms a piecewise cumulative sum and the points where it
+    passes `threshold` and then uses neither: the threshold has no influence on the result.  The attribute is kept (it is
+    the parser's JSON); the cumulative sum is not computed."""
+
+    def __init__(self, threshold=1.5):
+        self.threshold = threshold
+
+    def _call(self, ctx, allt, starts, lens):
+        return ctx.snakebase_f64(allt, starts, lens)
+
+
+class FilterDerivativeSegmenter(_SpanParser):
+    """The reference's FilterDerivativeSegmenter (parsers.py:609-679) on the GPU (ps_filter_derivative_f64): a first-order
+    Bessel low-pass at cutoff_freq run forward and backward, the absolute derivative of the result, blocks where it exceeds
+    low_threshold, and the states between the blocks that are kept.  What parse() RETURNS, quirks included:
+    * the edges of the blocks are paired in order, so when the derivative starts above low_threshold the pairs are the gaps
+      between the blocks; an unpaired last edge is dropped;
+    * a pair is kept when np.argmax(deriv[start:end]) > high_threshold: the INDEX of the maximum within the pair, not its
+      value, is compared with the threshold.
+    A current of 6 samples or fewer raises ValueError, as scipy's filtfilt does.  The device filter agrees with scipy to
+    1e-11 of max|y|: a decision closer than that to its threshold may fall the other way.  Non-finite samples: undefined."""
+
+    def __init__(self, low_threshold=1, high_threshold=2, cutoff_freq=1000., sampling_freq=1.e5):
+        self.low_threshold = low_threshold
+        self.high_threshold = high_threshold
+        self.cutoff_freq = cutoff_freq
+        self.sampling_freq = sampling_freq
+
+    def _check(self, lens):
+        if lens.size and lens.min() <= 6:
+            raise ValueError("The length of the input vector x must be greater than padlen, which is 6.")
+
+    def _params(self, prefiltered=False):
+        from . import _lib
+        return _lib.FilterDerivativeParams(float(self.low_threshold), float(self.high_threshold), float(self.cutoff_freq),
+                                           float(self.sampling_freq), 1 if prefiltered else 0)
+
+    def _call(self, ctx, allt, starts, lens):
+        return ctx.filter_derivative_f64(allt, starts, lens, self._params())
