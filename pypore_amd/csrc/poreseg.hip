@@ -10,8 +10,10 @@
 //   K2       segstat_kernel (optional)
 // Which kernel runs with which grid is decided once each: by_dtype / by_nt (run-time sample type and workgroup width -> the
 // kernels' template arguments), reserve_digest + launch_k0 (phase 0, for every route that runs K0), scan_shape (launch shape of
-// the scan kernels), launch_scans_bs / launch_spine_nt (phases 1, 1b), launch_subtrees (phase 3), make_spine_job and
-// reserve_items (tile tables and item buffers), begin_segment_call (prologue of the segment entry points).
+// the scan kernels), launch_scans_bs / launch_spine_nt (phases 1, 1b), launch_subtrees (phase 3), reserve_items (item buffers),
+// begin_segment_call (prologue of the segment entry points).  What a segment call plans on the host -- its scan route, the tile
+// tables of either stitch route, the host stitch, the seams of the second chance -- is plain C++ in seg_plan.hpp, checked on the
+// CPU (tests/native/seg_plan_check.cpp); device_stitch_batch and host_stitch_batch act on it: buffers, uploads, launches.
 // The context (ps_ctx) owns its GPU resources: DevBuf, HostBuf, Event and Stream free themselves, so ps_destroy is `delete ctx`
 // and a half-built context of ps_create releases what it had.  The segmentation chain's members are flat; every other feature
 // keeps its buffers, budgets and caches in one sub-struct of ps_ctx (filt, align, pw, ss, nt, hmm).  A new feature adds its
@@ -46,6 +48,7 @@
 #include "seg_statsplit.hpp"
 #include "seg_state.hpp"
 #include "pool_plan.hpp"
+#include "seg_plan.hpp"
 
 using namespace ps;
 
@@ -137,9 +140,7 @@ struct ps_ctx {
     int rep_eval = 1, rep_stage = 1, rep_sum = 1;
     uint8_t *d_is_spine = nullptr;   // optional output of the current call
     int prune = 1;
-    double wide_quantum = 0;  // quantum of the last call K0 refused (counts too wide) ...
-    int wide_skip = 0;        // ... and the number of calls with that quantum that still start where that call ended:
-    int wide_mode = 0;        // ... 2 = block-sum scan on the 64-bit digest, 0 = LDS-window scan
+    WideRedo wide;            // the last call K0 refused (counts too wide) and where the calls after it start (seg_plan.hpp)
     int tree_mw = 0;          // 1: block-sum tree kernel with TREE_W waves per workgroup sharing their job list (round 3: single-wave workgroups are faster at four waves per SIMD and need no spills)
     int upload_by_kernel = 1; // 1: the call's host tables are fetched by a kernel (no SDMA hand-over), 0: hipMemcpyAsync
     int k0_waves = 0;         // > 0: K0 runs as a persistent kernel, this many waves per SIMD (twice that for int16 samples) striding over the call with
@@ -192,11 +193,10 @@ struct ps_ctx {
     struct OccKey { const void *fn; int nt; size_t lds; int per_cu; };
     std::vector<OccKey> occ_cache;
     std::vector<std::pair<const void *, int>> attr_cache;
-    struct TileCache {
+    struct TileCache {        // the device route's tile plan (seg_plan.hpp), what it was planned for, and whether its tables are on the device
         bool valid = false;
-        int32_t n_ev = 0; int mw = 0, W = 0; int64_t L = 0; bool use_bs = false;
-        std::vector<int64_t> ev_start, ev_len;
-        size_t nj = 0, jb = 0, up_bytes = 0; int64_t list_entries = 0, total_len = 0, sample_end = 0, nb_total = 0;
+        DeviceTileKey key;
+        DeviceTilePlan plan;
     } tile_cache;
     DevBuf bsum, ev_info, chunk_mabs, ev_boff, blk_mm, grp, up_dev;
     // The segmentation chain's own buffers and options are flat members.  The state of every self-contained feature stands
@@ -672,14 +672,6 @@ int launch_subtrees(ps_ctx *ctx, const DevCfg &cfg, unsigned nj, SmallLayout *sm
     });
 }
 
-struct Anchor { int32_t pos, kind; };
-
-struct TileList {
-    int32_t start = 0;
-    std::vector<Anchor> a;
-    bool ended = false;
-};
-
 int check_status(ps_ctx *ctx, unsigned st)
 {
     if (st & ST_OFF_GRID)
@@ -745,164 +737,26 @@ int run_spines(ps_ctx *ctx, const DevCfg &cfg, const std::vector<SpineJob> &jobs
     return PS_OK;
 }
 
-// anchors of one chain are >= min_width apart and at most one lies at or beyond `stop`
-inline int64_t spine_cap(int64_t start, int64_t stop, int mw) { return (stop - start) / mw + 4; }
-
-// The spine job of tile [start, stop) of event `ev` (`len` samples at `base` of the sample array), its anchor list at out_off.
-// TilePlace: where the tile stands among the tiles of its event (device stitch); the halo tiles of the host stitch and its
-// seam repairs stand alone.
-struct TilePlace { int64_t first_tile = 0, ntiles = 1, tile_len = 0x7fffffff, vbase = 0; };
-SpineJob make_spine_job(int64_t base, int32_t ev, int64_t len, int64_t start, int64_t stop, int mw, int64_t out_off,
-                        const TilePlace &place = TilePlace())
-{
-    SpineJob j;
-    j.base = base;
-    j.start = static_cast<int32_t>(start);
-    j.end = static_cast<int32_t>(len);
-    j.stop = static_cast<int32_t>(stop);
-    j.out_cap = static_cast<int32_t>(std::min<int64_t>(spine_cap(start, stop, mw), 0x7fffffff));
-    j.out_off = out_off;
-    j.first_tile = static_cast<int32_t>(place.first_tile);
-    j.ntiles = static_cast<int32_t>(place.ntiles);
-    j.tile_len = static_cast<int32_t>(place.tile_len);
-    j.ev = ev;
-    j.vbase = place.vbase;
-    return j;
-}
-
-// position of `pos` in a tile list (exact match), -1 if the tile starts there, -2 if absent
-int find_in(const TileList &t, int32_t pos)
-{
-    if (pos == t.start) return -1;
-    auto it = std::lower_bound(t.a.begin(), t.a.end(), pos, [](const Anchor &x, int32_t v) { return x.pos < v; });
-    if (it != t.a.end() && it->pos == pos) return static_cast<int>(it - t.a.begin());
-    return -2;
-}
-
 }  // namespace
 
 namespace {
 constexpr int RC_FALLBACK = 1;      // internal: the device stitch gave up, use the host-stitch pipeline
 constexpr int RC_WIDE = 2;          // internal: counts too wide for the block sums, use the LDS-window scan
-// Phase 3 onwards.  Expects tree_jobs / items / first_item / ev_off populated on the device.
-// d_hdr == nullptr: n_tj / n_items are the exact counts (host stitch).  Otherwise they are upper bounds used
-// to size the launches and the kernels read the counts from *d_hdr on the device; the header and the status
-// word are then checked after the single synchronisation at the end (*hdr_out receives the header).
-int finish_batch(ps_ctx *ctx, const DevCfg &cfg, size_t n_tj, int64_t n_items, int32_t n_ev,
-                        int32_t *d_bounds, int64_t cap, int64_t *h_bounds_off, ps_segstat *d_stats,
-                        std::chrono::steady_clock::time_point t_begin, const AsmHeader *d_hdr = nullptr,
-                        AsmHeader *hdr_out = nullptr, bool wide_check = false)
+// What a batch call works on and where its results go, the same on every route it may be redone on
+struct SegBatch {
+    const int64_t *ev_start, *ev_len;
+    int32_t n_ev;
+    int mw, W;
+    int32_t *d_bounds;
+    int64_t cap;
+    int64_t *h_bounds_off;
+    ps_segstat *d_stats;
+    std::chrono::steady_clock::time_point t_begin;
+};
+// The work counters of a call that came through, from the status block it brought back (ps_get_timings; with PS_STAMP: the
+// phase stamps on stderr)
+void read_call_counters(ps_ctx *ctx, const DevCfg &cfg, const SmallLayout &hs)
 {
-    int rc;
-    const size_t evb = (static_cast<size_t>(n_ev) + 1) * sizeof(int64_t);
-    SmallLayout *sm = ctx->small.as<SmallLayout>();
-    if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
-    if (n_tj) {
-        const unsigned g = static_cast<unsigned>(std::min<size_t>(n_tj, 0x7fffffff));
-        if (int lrc = launch_subtrees(ctx, cfg, g, sm, n_tj, d_hdr)) return lrc;
-    }
-    if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
-    const bool fused = d_hdr != nullptr && ctx->gather_fused;      // (device stitch: job index == item index)
-    const bool one_copy = ctx->bounds_off.p == ctx->small.as<char>() + sizeof(SmallLayout);
-    int dl_clear = 0;                                  // (option short_chain: the download kernel leaves the status block zero behind its copy)
-    if (fused) {
-        const int64_t blocks = (n_items >> GS_LOG) + 1;
-        const unsigned gg = static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>(blocks, 1024)));
-        hipLaunchKernelGGL(gather_scan_kernel, dim3(gg), dim3(1 << GS_LOG), 0, ctx->stream, ctx->items.as<Item>(),
-                           ctx->tree_jobs.as<TreeJob>(), ctx->tree_counts.as<int32_t>(), ctx->tree_scratch.as<int32_t>(),
-                           static_cast<long long>(n_items), d_bounds, cap, ctx->d_is_spine, d_hdr, ctx->first_item.as<int64_t>(),
-                           n_ev, ctx->bounds_off.as<int64_t>());
-        HIP_TRY(ctx, hipGetLastError());
-    } else {
-    hipLaunchKernelGGL(item_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, ctx->items.as<Item>(),
-                       ctx->tree_counts.as<int32_t>(), n_items, ctx->item_pos.as<int64_t>(), d_hdr,
-                       ctx->first_item.as<int64_t>(), n_ev, ctx->bounds_off.as<int64_t>());
-    HIP_TRY(ctx, hipGetLastError());
-    }
-    if (n_items && !fused) {
-        const unsigned gg = static_cast<unsigned>(d_hdr ? std::min<int64_t>(n_items, 16384) : n_items);
-        hipLaunchKernelGGL(gather_kernel, dim3(gg), dim3(64), 0, ctx->stream,
-                           ctx->items.as<Item>(), ctx->tree_jobs.as<TreeJob>(), ctx->tree_counts.as<int32_t>(),
-                           ctx->tree_scratch.as<int32_t>(), ctx->item_pos.as<int64_t>(), n_items, d_bounds, cap, ctx->d_is_spine,
-                           d_hdr);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    const bool stats_from_digest = d_stats != nullptr && cfg.bsum != nullptr && cfg.blk_mm != nullptr;
-    if (stats_from_digest) {
-        // K2 from the K0 digest: launched before the sync, the segment count is read on the device
-        const int64_t scap = cap + n_ev;
-        const unsigned sg = static_cast<unsigned>(std::min<int64_t>(std::max<int64_t>(scap, 1), 8192));
-        by_dtype(cfg.dtype, [&](auto dt) {
-            hipLaunchKernelGGL(segstat_bs_kernel<dt()>, dim3(sg), dim3(64), 0, ctx->stream, cfg, ctx->ev_off.as<int64_t>(),
-                               ctx->ev_len.as<int64_t>(), n_ev, d_bounds, ctx->bounds_off.as<int64_t>(), d_stats, scap,
-                               reinterpret_cast<unsigned *>(&sm->status), d_hdr);
-        });
-        HIP_TRY(ctx, hipGetLastError());
-        if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
-    }
-    if (one_copy) {
-        HIP_TRY(ctx, ctx->h_small.reserve(sizeof(SmallLayout) + evb));
-        void *h_dev = nullptr;                         // the pinned block as the device sees it (else: plain copy)
-        if (ctx->download_by_kernel && hipHostGetDevicePointer(&h_dev, ctx->h_small.p, 0) != hipSuccess) { h_dev = nullptr; (void)hipGetLastError(); }
-        if (h_dev) {
-            static_assert(sizeof(SmallLayout) % 8 == 0, "the status block is copied in 8-byte words");
-            const long long nw = static_cast<long long>((sizeof(SmallLayout) + evb) / 8);
-            // (a call without statistics on the screened route, see short_route: the calls the option was measured on)
-            if (fused && d_stats == nullptr && ctx->screen_ran && (ctx->short_chain & SC_NO_UPLOAD)) dl_clear = static_cast<int>(sizeof(SmallLayout) / 8);
-            hipLaunchKernelGGL(download_kernel, dim3(static_cast<unsigned>(std::min<long long>((nw + 255) / 256, 64))), dim3(256), 0, ctx->stream,
-                               ctx->small.as<unsigned long long>(), static_cast<unsigned long long *>(h_dev), nw, dl_clear, &sm->hdr.fail);
-            HIP_TRY(ctx, hipGetLastError());
-        } else {
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->h_small.p, ctx->small.p, sizeof(SmallLayout) + evb, hipMemcpyDeviceToHost, ctx->stream));
-        }
-    } else {
-        HIP_TRY(ctx, ctx->h_meta.reserve(evb));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_meta.p, ctx->bounds_off.p, evb, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_small.p, ctx->small.p, sizeof(SmallLayout), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (ctx->timing >= 1) HIP_TRY(ctx, hipEventRecord(ctx->ev[9], ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    {
-        float seq = 0;                                 // the call's device work, upload to result copies, by HIP events
-        if (ctx->timing >= 1 && hipEventElapsedTime(&seq, ctx->ev[8], ctx->ev[9]) == hipSuccess) ctx->ms[7] = seq;
-    }
-    std::memcpy(h_bounds_off, one_copy ? ctx->h_small.as<char>() + sizeof(SmallLayout) : ctx->h_meta.as<char>(), evb);
-    const SmallLayout hs = *ctx->h_small.as<SmallLayout>();
-    if (wide_check && (static_cast<unsigned>(hs.status) & ST_WIDE_RANGE)) return RC_WIDE;    // counts too wide for the block sums
-    rc = check_status(ctx, static_cast<unsigned>(hs.status));
-    if (rc) return rc;
-    if (d_hdr) {
-        const AsmHeader hd = hs.hdr;
-        if (hdr_out) *hdr_out = hd;
-        if (hd.fail) {
-            if (ctx->debug) {                          // which seams gave up (option debug)
-                const size_t nt = static_cast<size_t>(ctx->counters[2]);
-                std::vector<int4> bm(nt), mt(nt);
-                std::vector<SpineJob> jb(nt);
-                if (nt && hipMemcpy(bm.data(), ctx->bmeta.p, nt * sizeof(int4), hipMemcpyDeviceToHost) == hipSuccess &&
-                    hipMemcpy(mt.data(), ctx->spine_meta.p, nt * sizeof(int4), hipMemcpyDeviceToHost) == hipSuccess &&
-                    hipMemcpy(jb.data(), ctx->spine_jobs.p, nt * sizeof(SpineJob), hipMemcpyDeviceToHost) == hipSuccess) {
-                    int shown = 0;
-                    size_t n_open = 0, n_gave_up = 0, n_defer = 0;
-                    for (size_t g = 0; g < nt; ++g) {
-                        if (bm[g].w == BR_DEFER || bm[g].w == BR_DEFER_REACHED) ++n_defer;
-                        else if (bm[g].w == 3 && mt[g].x == 0 && bm[g].x == 0) ++n_open;
-                        else if (bm[g].w == 3) ++n_gave_up;
-                    }
-                    fprintf(stderr, "[poreseg] stitch failed: %zu tiles; bridges that gave up after anchors of their own %zu, open tiles not bridged %zu, deferred and not finished %zu\n",
-                            nt, n_gave_up, n_open, n_defer);
-                    for (size_t g = 0; g < nt && shown < 6; ++g)
-                        if ((bm[g].w == 3 && !(mt[g].x == 0 && bm[g].x == 0)) || bm[g].w == BR_DEFER || bm[g].w == BR_DEFER_REACHED) {
-                            fprintf(stderr, "[poreseg] stitch failed: tile %zu (event %d, tile %zu of %d, [%d, %d) of %d) bridge status %d after %d anchors (next window %d); its own list: %d anchors, ended %d, open at %d\n",
-                                    g, jb[g].ev, g - static_cast<size_t>(jb[g].first_tile), jb[g].ntiles, jb[g].start, jb[g].stop, jb[g].end,
-                                    bm[g].w, bm[g].x, bm[g].y, mt[g].x, mt[g].y, mt[g].z);
-                            ++shown;
-                        }
-                }
-            }
-            return RC_FALLBACK;
-        }
-    }
     ctx->counters[0] = static_cast<int64_t>(hs.work0);
     ctx->counters[1] = static_cast<int64_t>(hs.work1);
     ctx->counters[5] = static_cast<int64_t>(hs.work2 & 0xffffffffULL) + static_cast<int64_t>(hs.work2 >> 32);   // exact decisions
@@ -937,6 +791,156 @@ int finish_batch(ps_ctx *ctx, const DevCfg &cfg, size_t n_tj, int64_t n_items, i
                     k == 0 ? "spine" : k == 1 ? "bridge" : "tree", hs.life[3 * k], hs.life[3 * k + 1], hs.life[3 * k + 2]);
     }
 #endif
+}
+
+// Option debug: says on stderr which seams of a failed device stitch gave up (their records are fetched for this alone)
+void report_failed_seams(ps_ctx *ctx)
+{
+    const size_t nt = static_cast<size_t>(ctx->counters[2]);
+    std::vector<int4> bm(nt), mt(nt);
+    std::vector<SpineJob> jb(nt);
+    if (!nt || hipMemcpy(bm.data(), ctx->bmeta.p, nt * sizeof(int4), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(mt.data(), ctx->spine_meta.p, nt * sizeof(int4), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(jb.data(), ctx->spine_jobs.p, nt * sizeof(SpineJob), hipMemcpyDeviceToHost) != hipSuccess)
+        return;
+    int shown = 0;
+    size_t n_open = 0, n_gave_up = 0, n_defer = 0;
+    for (size_t g = 0; g < nt; ++g) {
+        if (bm[g].w == BR_DEFER || bm[g].w == BR_DEFER_REACHED) ++n_defer;
+        else if (bm[g].w == BR_FAIL && mt[g].x == 0 && bm[g].x == 0) ++n_open;
+        else if (bm[g].w == BR_FAIL) ++n_gave_up;
+    }
+    fprintf(stderr, "[poreseg] stitch failed: %zu tiles; bridges that gave up after anchors of their own %zu, open tiles not bridged %zu, deferred and not finished %zu\n",
+            nt, n_gave_up, n_open, n_defer);
+    for (size_t g = 0; g < nt && shown < 6; ++g)
+        if ((bm[g].w == BR_FAIL && !(mt[g].x == 0 && bm[g].x == 0)) || bm[g].w == BR_DEFER || bm[g].w == BR_DEFER_REACHED) {
+            fprintf(stderr, "[poreseg] stitch failed: tile %zu (event %d, tile %zu of %d, [%d, %d) of %d) bridge status %d after %d anchors (next window %d); its own list: %d anchors, ended %d, open at %d\n",
+                    g, jb[g].ev, g - static_cast<size_t>(jb[g].first_tile), jb[g].ntiles, jb[g].start, jb[g].stop, jb[g].end,
+                    bm[g].w, bm[g].x, bm[g].y, mt[g].x, mt[g].y, mt[g].z);
+            ++shown;
+        }
+}
+
+// The gather: every true anchor behind the boundaries of its left subtree, per-event offsets -- one kernel that places its items
+// from per-256-job count sums (device stitch, gather_fused), else the item scan and the gather of rounds 2-5
+int queue_gather(ps_ctx *ctx, const SegBatch &B, int64_t n_items, const AsmHeader *d_hdr, bool fused)
+{
+    const int32_t n_ev = B.n_ev;
+    int32_t *const d_bounds = B.d_bounds;
+    const int64_t cap = B.cap;
+    if (fused) {
+        const int64_t blocks = (n_items >> GS_LOG) + 1;
+        const unsigned gg = static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>(blocks, 1024)));
+        hipLaunchKernelGGL(gather_scan_kernel, dim3(gg), dim3(1 << GS_LOG), 0, ctx->stream, ctx->items.as<Item>(),
+                           ctx->tree_jobs.as<TreeJob>(), ctx->tree_counts.as<int32_t>(), ctx->tree_scratch.as<int32_t>(),
+                           static_cast<long long>(n_items), d_bounds, cap, ctx->d_is_spine, d_hdr, ctx->first_item.as<int64_t>(),
+                           n_ev, ctx->bounds_off.as<int64_t>());
+        HIP_TRY(ctx, hipGetLastError());
+    } else {
+    hipLaunchKernelGGL(item_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, ctx->items.as<Item>(),
+                       ctx->tree_counts.as<int32_t>(), n_items, ctx->item_pos.as<int64_t>(), d_hdr,
+                       ctx->first_item.as<int64_t>(), n_ev, ctx->bounds_off.as<int64_t>());
+    HIP_TRY(ctx, hipGetLastError());
+    }
+    if (n_items && !fused) {
+        const unsigned gg = static_cast<unsigned>(d_hdr ? std::min<int64_t>(n_items, 16384) : n_items);
+        hipLaunchKernelGGL(gather_kernel, dim3(gg), dim3(64), 0, ctx->stream,
+                           ctx->items.as<Item>(), ctx->tree_jobs.as<TreeJob>(), ctx->tree_counts.as<int32_t>(),
+                           ctx->tree_scratch.as<int32_t>(), ctx->item_pos.as<int64_t>(), n_items, d_bounds, cap, ctx->d_is_spine,
+                           d_hdr);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return PS_OK;
+}
+
+// Status block and per-event offsets go back to the host: in one piece where the offsets ride behind the block (one_copy) -- by
+// download_kernel into pinned memory, which may leave the block zero behind it (may_clear, option short_chain; *dl_clear: the
+// words it clears), or by a plain copy -- else by two copies
+int queue_download(ps_ctx *ctx, size_t evb, bool one_copy, bool may_clear, int *dl_clear)
+{
+    SmallLayout *sm = ctx->small.as<SmallLayout>();
+    if (one_copy) {
+        HIP_TRY(ctx, ctx->h_small.reserve(sizeof(SmallLayout) + evb));
+        void *h_dev = nullptr;                         // the pinned block as the device sees it (else: plain copy)
+        if (ctx->download_by_kernel && hipHostGetDevicePointer(&h_dev, ctx->h_small.p, 0) != hipSuccess) { h_dev = nullptr; (void)hipGetLastError(); }
+        if (h_dev) {
+            static_assert(sizeof(SmallLayout) % 8 == 0, "the status block is copied in 8-byte words");
+            const long long nw = static_cast<long long>((sizeof(SmallLayout) + evb) / 8);
+            // (a call without statistics on the screened route, see short_route: the calls the option was measured on)
+            if (may_clear && ctx->screen_ran && (ctx->short_chain & SC_NO_UPLOAD)) *dl_clear = static_cast<int>(sizeof(SmallLayout) / 8);
+            hipLaunchKernelGGL(download_kernel, dim3(static_cast<unsigned>(std::min<long long>((nw + 255) / 256, 64))), dim3(256), 0, ctx->stream,
+                               ctx->small.as<unsigned long long>(), static_cast<unsigned long long *>(h_dev), nw, *dl_clear, &sm->hdr.fail);
+            HIP_TRY(ctx, hipGetLastError());
+        } else {
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->h_small.p, ctx->small.p, sizeof(SmallLayout) + evb, hipMemcpyDeviceToHost, ctx->stream));
+        }
+    } else {
+        HIP_TRY(ctx, ctx->h_meta.reserve(evb));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_meta.p, ctx->bounds_off.p, evb, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_small.p, ctx->small.p, sizeof(SmallLayout), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    return PS_OK;
+}
+
+// Phase 3 onwards.  Expects tree_jobs / items / first_item / ev_off populated on the device.
+// d_hdr == nullptr: n_tj / n_items are the exact counts (host stitch).  Otherwise they are upper bounds used
+// to size the launches and the kernels read the counts from *d_hdr on the device; the header and the status
+// word are then checked after the single synchronisation at the end (*hdr_out receives the header).
+int finish_batch(ps_ctx *ctx, const DevCfg &cfg, const SegBatch &B, size_t n_tj, int64_t n_items, const AsmHeader *d_hdr = nullptr,
+                 AsmHeader *hdr_out = nullptr, bool wide_check = false)
+{
+    const int32_t n_ev = B.n_ev;
+    int32_t *const d_bounds = B.d_bounds;
+    const int64_t cap = B.cap;
+    int64_t *const h_bounds_off = B.h_bounds_off;
+    ps_segstat *const d_stats = B.d_stats;
+    int rc;
+    const size_t evb = (static_cast<size_t>(n_ev) + 1) * sizeof(int64_t);
+    SmallLayout *sm = ctx->small.as<SmallLayout>();
+    if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+    if (n_tj) {
+        const unsigned g = static_cast<unsigned>(std::min<size_t>(n_tj, 0x7fffffff));
+        if (int lrc = launch_subtrees(ctx, cfg, g, sm, n_tj, d_hdr)) return lrc;
+    }
+    if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+    const bool fused = d_hdr != nullptr && ctx->gather_fused;      // (device stitch: job index == item index)
+    const bool one_copy = ctx->bounds_off.p == ctx->small.as<char>() + sizeof(SmallLayout);
+    int dl_clear = 0;                                  // (option short_chain: the download kernel leaves the status block zero behind its copy)
+    if (int grc = queue_gather(ctx, B, n_items, d_hdr, fused)) return grc;
+    const bool stats_from_digest = d_stats != nullptr && cfg.bsum != nullptr && cfg.blk_mm != nullptr;
+    if (stats_from_digest) {
+        // K2 from the K0 digest: launched before the sync, the segment count is read on the device
+        const int64_t scap = cap + n_ev;
+        const unsigned sg = static_cast<unsigned>(std::min<int64_t>(std::max<int64_t>(scap, 1), 8192));
+        by_dtype(cfg.dtype, [&](auto dt) {
+            hipLaunchKernelGGL(segstat_bs_kernel<dt()>, dim3(sg), dim3(64), 0, ctx->stream, cfg, ctx->ev_off.as<int64_t>(),
+                               ctx->ev_len.as<int64_t>(), n_ev, d_bounds, ctx->bounds_off.as<int64_t>(), d_stats, scap,
+                               reinterpret_cast<unsigned *>(&sm->status), d_hdr);
+        });
+        HIP_TRY(ctx, hipGetLastError());
+        if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
+    }
+    if (int drc = queue_download(ctx, evb, one_copy, fused && d_stats == nullptr, &dl_clear)) return drc;
+    if (ctx->timing >= 1) HIP_TRY(ctx, hipEventRecord(ctx->ev[9], ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    {
+        float seq = 0;                                 // the call's device work, upload to result copies, by HIP events
+        if (ctx->timing >= 1 && hipEventElapsedTime(&seq, ctx->ev[8], ctx->ev[9]) == hipSuccess) ctx->ms[7] = seq;
+    }
+    std::memcpy(h_bounds_off, one_copy ? ctx->h_small.as<char>() + sizeof(SmallLayout) : ctx->h_meta.as<char>(), evb);
+    const SmallLayout hs = *ctx->h_small.as<SmallLayout>();
+    if (wide_check && (static_cast<unsigned>(hs.status) & ST_WIDE_RANGE)) return RC_WIDE;    // counts too wide for the block sums
+    rc = check_status(ctx, static_cast<unsigned>(hs.status));
+    if (rc) return rc;
+    if (d_hdr) {
+        const AsmHeader hd = hs.hdr;
+        if (hdr_out) *hdr_out = hd;
+        if (hd.fail) {
+            if (ctx->debug) report_failed_seams(ctx);
+            return RC_FALLBACK;
+        }
+    }
+    read_call_counters(ctx, cfg, hs);
     const int64_t total = h_bounds_off[n_ev];
     if (total > cap)
         return fail(ctx, PS_ERR_CAPACITY, "bounds capacity %lld < required %lld", static_cast<long long>(cap),
@@ -959,11 +963,10 @@ int finish_batch(ps_ctx *ctx, const DevCfg &cfg, size_t n_tj, int64_t n_items, i
     float ms = 0;
     if (ctx->timing >= 2 && hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]) == hipSuccess) ctx->ms[1] = ms;
     if (ctx->timing >= 2 && hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]) == hipSuccess) ctx->ms[2] = ms;
-    ctx->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    ctx->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - B.t_begin).count();
     ctx->small_clean = dl_clear > 0;                   // (the copy of a call that came through left the status block zero)
     return PS_OK;
 }
-
 
 
 // The helpers' shared state for this call (none when switched off, or not the block-sum pipeline)
@@ -1168,89 +1171,50 @@ template <int FLAGS> int launch_scans_bs(ps_ctx *ctx, const DevCfg &cfg, unsigne
 // digest_ready (round 6, ps_detect_segment_trace): the digest of the WHOLE trace is already in the context's buffers (K0 ran over
 // it as one event, trace-aligned blocks): no K0 here; the events get (centre of the trace, phase, first block) from
 // ev_info_trace_kernel and the scans run in shifted coordinates (seg_bs.hpp: scan_window_ph).
-int device_stitch_batch_(ps_ctx *ctx, const DevCfg &cfg_in, int bs_mode, const int64_t *ev_start, const int64_t *ev_len, int32_t n_ev, int mw, int W,
-                        int32_t *d_bounds, int64_t cap, int64_t *h_bounds_off, ps_segstat *d_stats,
-                        std::chrono::steady_clock::time_point t_begin, bool digest_ready = false)
+// device_stitch_batch_ runs the steps below in their order; DeviceCall is what they hand on to each other.
+struct DeviceCall {
+    DevCfg cfg;               // the call's configuration; queue_upload_k0 enters the digest
+    bool use_bs = false;      // block-sum scan on the 32-bit digest, or ...
+    bool wide = false;        // ... on the 64-bit (wide) digest; neither: the LDS-window kernels
+    bool digest_ready = false;
+    bool reuse = false;       // the call repeats the previous one's layout: its plan, and its tables on the device, serve again
+    size_t nj = 0;            // tiles
+    int64_t max_items = 0;    // true anchors the first stitch round has room for
+};
+
+// Step 1.  The tile tables depend only on the event layout and the parameters: a call that repeats the previous one's
+// (the bench loop; a file segmented with several parameter sets) reuses the tables that are still on the device.  Any other
+// call plans (seg_plan.hpp) and stages its upload.
+int plan_or_reuse(ps_ctx *ctx, const SegBatch &B, DeviceCall &C)
 {
-    DevCfg cfg = cfg_in;
-    ctx->la_now = ctx->la_keep > 0;
-    if (ctx->la_now) --ctx->la_keep;
-    const bool use_bs = bs_mode != 0;                  // 1: block-sum scan on the 32-bit digest, 2: on the 64-bit (wide) digest
-    const bool wide = bs_mode == 2;
-    cfg.bs_wide = wide ? 1 : 0;
-    int64_t L = ctx->tile_len;
-    // The tile tables depend only on the event layout and the parameters: a call that repeats the previous one's
-    // (the bench loop; a file segmented with several parameter sets) reuses the tables that are still on the device.
     ps_ctx::TileCache &tc = ctx->tile_cache;
-    const size_t evb = (static_cast<size_t>(n_ev) + 1) * sizeof(int64_t);
-    bool reuse = tc.valid && tc.n_ev == n_ev && tc.mw == mw && tc.W == W && tc.L == L && tc.use_bs == use_bs &&
-                 std::equal(ev_start, ev_start + n_ev, tc.ev_start.begin()) && std::equal(ev_len, ev_len + n_ev, tc.ev_len.begin());
-    if (!reuse) {
+    const int64_t L = ctx->tile_len;
+    C.reuse = tc.valid && tc.key.matches(B.ev_start, B.ev_len, B.n_ev, B.mw, B.W, L, C.use_bs);
+    if (!C.reuse) {
         tc.valid = false;
-        int64_t total_len = 0, sample_end = 0;
-        for (int e = 0; e < n_ev; ++e) { total_len += ev_len[e]; sample_end = std::max(sample_end, ev_start[e] + ev_len[e]); }
-        int64_t Lt = L;
-        // block-sum scan: one tile per wave slot of the scan kernels (4 096 at four waves per SIMD) when the tiles stay
-        // long (>= 8 W: a 1e9-sample trace, 3.05 -> 2.70 ms), else 1 536 tiles of at least 4 W (shorter tiles only add
-        // speculative windows and seams: measured on the 1e8-sample trace; round 4, with the lighter windows
-        // of the coarse pass: 2 048 -> 1 536 tiles, 0.2298 -> 0.2247 ms per step in five interleaved rounds, one call unchanged)
-        if (Lt <= 0) Lt = use_bs ? ((total_len + 4095) / 4096 >= 8LL * W ? (total_len + 4095) / 4096
-                                                                         : std::max<int64_t>(4LL * W, (total_len + 1535) / 1536))
-                                 : std::max<int64_t>(8LL * W, (total_len + 1023) / 1024);
-        Lt = (Lt + 7) & ~7LL;
-        Lt = std::min<int64_t>(Lt, 0x7fffffff);
-        std::vector<SpineJob> jobs;
-        std::vector<int64_t> ev_first_tile(static_cast<size_t>(n_ev) + 1, 0);
-        int64_t list_entries = 0, vb_run = 0;
-        for (int e = 0; e < n_ev; ++e) {
-            ev_first_tile[e] = static_cast<int64_t>(jobs.size());
-            const int64_t len = ev_len[e];
-            if (len == 0) continue;
-            const int64_t vbase = vb_run;
-            vb_run += len;
-            // tiles of one event share one length: the event is cut evenly.  An event of up to 1.5 tile lengths stays ONE tile
-            // (round 6: a 50k event with L = 40k used to be 2 x 25k -- two chains of three windows, a seam, a bridge and a stitch
-            // entry for nothing: every event start is a true anchor.  BASELINE config 2, 1 024 x 50 000: 0.338-0.355 -> 0.309 ms
-            // for a lone call, 2 048 -> 1 024 tiles, 15 459 -> 14 435 windows; profiles/r06_experiments/r6_config2_tile.txt)
-            const int64_t nt0 = use_bs ? std::max<int64_t>(1, (len + Lt / 2) / Lt) : (len + Lt - 1) / Lt;
-            const int64_t Le = std::min<int64_t>(((len + nt0 - 1) / nt0 + 7) & ~7LL, 0x7fffffff);
-            const int64_t nt = (len + Le - 1) / Le;
-            if (static_cast<int64_t>(jobs.size()) + nt > 0x7ffffff0) return RC_FALLBACK;
-            for (int64_t t = 0; t < nt; ++t) {
-                jobs.push_back(make_spine_job(ev_start[e], e, len, t * Le, t == nt - 1 ? len : (t + 1) * Le, mw, list_entries,
-                                              {ev_first_tile[e], nt, Le, vbase}));
-                list_entries += jobs.back().out_cap;
-            }
-        }
-        ev_first_tile[n_ev] = static_cast<int64_t>(jobs.size());
-        const size_t nj = jobs.size();
-        // one upload: [jobs | ev_first_tile | ev_start | ev_len | ev_boff] -> one device blob the five arrays point into
-        const size_t jb = (nj * sizeof(SpineJob) + 15) & ~static_cast<size_t>(15);
-        std::vector<int64_t> boff(static_cast<size_t>(n_ev) + 1, 0);           // first block of every event (K0)
-        for (int e = 0; e < n_ev; ++e) boff[e + 1] = boff[e] + (ev_len[e] + 7) / 8;
-        const size_t up_bytes = jb + 4 * evb;
+        tc.plan = plan_device_tiles(B.ev_start, B.ev_len, B.n_ev, B.mw, B.W, L, C.use_bs);
+        if (tc.plan.too_many) return RC_FALLBACK;
+        const size_t up_bytes = tc.plan.up_bytes(B.n_ev);
         HIP_TRY(ctx, ctx->h_up.reserve(up_bytes + 64));
         HIP_TRY(ctx, ctx->up_dev.reserve(up_bytes + 64));
-        char *up = ctx->h_up.as<char>();
-        if (nj) std::memcpy(up, jobs.data(), nj * sizeof(SpineJob));
-        std::memcpy(up + jb, ev_first_tile.data(), evb);
-        std::memcpy(up + jb + evb, ev_start, evb - sizeof(int64_t));
-        std::memcpy(up + jb + 2 * evb, ev_len, evb - sizeof(int64_t));
-        std::memcpy(up + jb + 3 * evb, boff.data(), evb);
-        tc.n_ev = n_ev; tc.mw = mw; tc.W = W; tc.L = L; tc.use_bs = use_bs;
-        tc.ev_start.assign(ev_start, ev_start + n_ev); tc.ev_len.assign(ev_len, ev_len + n_ev);
-        tc.nj = nj; tc.jb = jb; tc.up_bytes = up_bytes; tc.list_entries = list_entries; tc.total_len = total_len;
-        tc.sample_end = sample_end; tc.nb_total = boff[n_ev];
+        tc.plan.stage(ctx->h_up.as<char>(), B.ev_start, B.ev_len, B.n_ev);
+        tc.key.set(B.ev_start, B.ev_len, B.n_ev, B.mw, B.W, L, C.use_bs);
     }
-    const size_t nj = tc.nj, jb = tc.jb, up_bytes = tc.up_bytes;
-    const int64_t list_entries = tc.list_entries, total_len = tc.total_len, sample_end = tc.sample_end;
-    ctx->counters[2] = static_cast<int64_t>(nj);
-    const int64_t max_items = list_entries + static_cast<int64_t>(nj) * BR_MAX;
+    C.nj = tc.plan.jobs.size();
+    C.max_items = tc.plan.list_entries + static_cast<int64_t>(C.nj) * BR_MAX;
+    ctx->counters[2] = static_cast<int64_t>(C.nj);
+    return PS_OK;
+}
 
-    HIP_TRY(ctx, ctx->spine_scratch.reserve(std::max<int64_t>(1, list_entries) * sizeof(int2)));
+// Step 2.  The buffers of the scans and of the stitch, sized by the plan (a call that repeats the layout finds them all)
+int reserve_call_buffers(ps_ctx *ctx, const SegBatch &B, const DeviceCall &C)
+{
+    const DeviceTilePlan &plan = ctx->tile_cache.plan;
+    const size_t nj = C.nj, evb = DeviceTilePlan::table_bytes(B.n_ev);
+    HIP_TRY(ctx, ctx->spine_scratch.reserve(std::max<int64_t>(1, plan.list_entries) * sizeof(int2)));
     HIP_TRY(ctx, ctx->spine_meta.reserve(std::max<size_t>(4, nj) * sizeof(int4)));
     HIP_TRY(ctx, ctx->bridges.reserve(std::max<size_t>(1, nj) * BR_MAX * sizeof(int2)));
-    if (use_bs && ctx->lat_help) {
+    if (C.use_bs && ctx->lat_help) {
         // (published chunk results carry the tag of their listing; a fresh buffer is zero, tags start at 1, and before the 24
         //  bits run out the buffer is cleared)
         const size_t res_bytes = static_cast<size_t>(LAT_D) * LAT_C * sizeof(unsigned long long);
@@ -1268,15 +1232,97 @@ int device_stitch_batch_(ps_ctx *ctx, const DevCfg &cfg_in, int bs_mode, const i
     HIP_TRY(ctx, ctx->bmeta.reserve(std::max<size_t>(1, nj) * sizeof(int4)));
     HIP_TRY(ctx, ctx->tile_i32.reserve(std::max<size_t>(1, nj) * 4 * sizeof(int)));
     HIP_TRY(ctx, ctx->sp_off.reserve((nj + 1) * sizeof(long long)));
-    if (int irc = reserve_items(ctx, max_items, total_len, mw)) return irc;
+    if (int irc = reserve_items(ctx, C.max_items, plan.total_len, B.mw)) return irc;
     HIP_TRY(ctx, ctx->first_item.reserve(evb));
     if (evb <= SMALL_TAIL) ctx->bounds_off.alias(ctx->small.as<char>() + sizeof(SmallLayout));   // comes back with the status block
     else HIP_TRY(ctx, ctx->bounds_off.reserve(evb));
     ctx->asm_hdr.alias(&ctx->small.as<SmallLayout>()->hdr);
     HIP_TRY(ctx, ctx->h_small.reserve(sizeof(SmallLayout)));
-    // Where upload + K0 are queued: the context's own stream, or the device's front stream (k0_shared) -- then under the front
-    // stream's mutex until K0's event is recorded, and the context's stream continues behind that event.
-    FrontStream *front = (ctx->k0_shared && use_bs && tc.nj) ? front_for(ctx) : nullptr;
+    return PS_OK;
+}
+
+// The call's tables go up and the status block is cleared, on stream fs: by upload_kernel from the pinned blob, by plain copies
+// where the device cannot see it, or not at all (option short_chain)
+int queue_upload(ps_ctx *ctx, const SegBatch &B, const DeviceCall &C, hipStream_t fs, bool front)
+{
+    const char *up = ctx->h_up.as<char>();
+    const size_t up_bytes = ctx->tile_cache.plan.up_bytes(B.n_ev);
+    void *up_devptr = nullptr;                     // the pinned blob as the device sees it (else: plain copy)
+    if (ctx->upload_by_kernel && hipHostGetDevicePointer(&up_devptr, const_cast<char *>(up), 0) != hipSuccess) { up_devptr = nullptr; (void)hipGetLastError(); }
+    // (option short_chain: the tables are still on the device and the previous call's download kernel left the status block zero)
+    // (... on the route the option applies to, short_route, as far as it is known before K0: every other route launches what it launched)
+    const bool short_rt = C.use_bs && !C.wide && !C.digest_ready && ctx->groups && !ctx->tree_mw && ctx->tree_screen && C.cfg.mode == MODE_FAST && C.cfg.prune;
+    const bool skip_upload = C.reuse && ctx->small_clean_in && !front && short_rt && ctx->upload_by_kernel && (ctx->short_chain & SC_NO_UPLOAD);
+    ctx->small_clean_in = false;                   // (a redo of this call on another digest starts from a block it cleared itself)
+    if (skip_upload) ctx->counters[17] += 1;
+    else if (up_devptr) {
+        // (tables still on the device from the previous call: the kernel only clears the status block)
+        const long long n16 = C.reuse ? 0 : static_cast<long long>((up_bytes + 15) / 16);
+        const unsigned ug = static_cast<unsigned>(std::max<long long>(1, std::min<long long>((n16 + 255) / 256, 1024)));
+        hipLaunchKernelGGL(upload_kernel, dim3(ug), dim3(256), 0, fs, static_cast<const int4 *>(up_devptr),
+                           ctx->up_dev.as<int4>(), n16, ctx->small.as<unsigned long long>(),
+                           static_cast<int>(sizeof(SmallLayout) / sizeof(unsigned long long)));
+        HIP_TRY(ctx, hipGetLastError());
+    } else {
+        HIP_TRY(ctx, hipMemsetAsync(ctx->small.p, 0, sizeof(SmallLayout), fs));
+        if (!C.reuse) HIP_TRY(ctx, hipMemcpyAsync(ctx->up_dev.p, up, up_bytes, hipMemcpyHostToDevice, fs));
+    }
+    ctx->tile_cache.valid = true;
+    // the five arrays of the blob: [jobs | ev_first_tile | ev_start | ev_len | boff]
+    char *dup = ctx->up_dev.as<char>();
+    const size_t jb = ctx->tile_cache.plan.jobs_bytes(), evb = DeviceTilePlan::table_bytes(B.n_ev);
+    ctx->spine_jobs.alias(dup);
+    ctx->ev_first_tile.alias(dup + jb);
+    ctx->ev_off.alias(dup + jb + evb);
+    ctx->ev_len.alias(dup + jb + 2 * evb);
+    ctx->ev_boff.alias(dup + jb + 3 * evb);
+    return PS_OK;
+}
+
+// K0 over the call's events on stream fs -- or, where the digest of the whole trace is there already (digest_ready), the
+// events' places in it -- and the digest entered into the call's configuration
+int queue_digest(ps_ctx *ctx, const SegBatch &B, DeviceCall &C, hipStream_t fs, bool front)
+{
+    DevCfg &cfg = C.cfg;
+    const int32_t n_ev = B.n_ev;
+    if (C.use_bs && C.nj && C.digest_ready) {
+        HIP_TRY(ctx, ctx->ev_info_tr.reserve(static_cast<size_t>(std::max(1, n_ev)) * sizeof(int4)));
+        hipLaunchKernelGGL(ev_info_trace_kernel, dim3(static_cast<unsigned>(std::min(64, (n_ev + 255) / 256))), dim3(256), 0, fs,
+                           ctx->ev_off.as<int64_t>(), n_ev, ctx->ev_info.as<int4>(), ctx->ev_info_tr.as<int4>());
+        HIP_TRY(ctx, hipGetLastError());
+        cfg.bsum = ctx->bsum.p;
+        cfg.ev_info = ctx->ev_info_tr.as<int4>();
+        cfg.chunk_tot = ctx->chunk_mabs.as<int4>();
+        cfg.grp = ctx->groups ? ctx->grp.p : nullptr;
+        cfg.blk_mm = B.d_stats ? ctx->blk_mm.as<int>() : nullptr;
+    } else if (C.use_bs && C.nj) {
+        const DeviceTilePlan &plan = ctx->tile_cache.plan;
+        const int64_t nb_pad = k0_padded_blocks(plan.boff[n_ev]);
+        DigestWant want;
+        want.wide = C.wide;
+        want.grp = !C.wide && ctx->groups;
+        want.blk_mm = B.d_stats && !C.wide;
+        if (int drc = reserve_digest(ctx, nb_pad, n_ev, want)) return drc;
+        if (want.grp) cfg.grp = ctx->grp.p;
+        if (want.blk_mm) cfg.blk_mm = ctx->blk_mm.as<int>();
+        K0Call k0 = {ctx->ev_off.as<int64_t>(), ctx->ev_len.as<int64_t>(), ctx->ev_boff.as<int64_t>(), n_ev, plan.sample_end, nb_pad};
+        k0.admit = !front;                             // (the front stream serialises the K0s of its contexts by itself)
+        k0.batch = true;
+        k0.repeat = C.reuse;
+        if (int krc = C.wide ? launch_k0<DT_WIDE>(ctx, cfg, fs, k0) : launch_k0<0>(ctx, cfg, fs, k0)) return krc;
+        cfg.bsum = ctx->bsum.p;
+        cfg.ev_info = ctx->ev_info.as<int4>();
+        cfg.chunk_tot = ctx->chunk_mabs.as<int4>();
+    }
+    return PS_OK;
+}
+
+// Step 3.  Upload + K0 are queued on the context's own stream, or on the device's front stream (k0_shared) -- then under the
+// front stream's mutex until K0's event is recorded, and the context's stream continues behind that event.
+// *k0_only (diagnostic library, dbg_phase 2): the call ends here.
+int queue_upload_k0(ps_ctx *ctx, const SegBatch &B, DeviceCall &C, bool *k0_only)
+{
+    FrontStream *front = (ctx->k0_shared && C.use_bs && C.nj) ? front_for(ctx) : nullptr;
     hipStream_t fs = front ? front->s : ctx->stream;
     std::unique_lock<std::mutex> front_lock;
     if (front) {
@@ -1286,74 +1332,18 @@ int device_stitch_batch_(ps_ctx *ctx, const DevCfg &cfg_in, int bs_mode, const i
             HIP_TRY(ctx, hipStreamWaitEvent(fs, ctx->ev_front[0], 0));
         }
     }
-    {
-        const char *up = ctx->h_up.as<char>();
-        void *up_devptr = nullptr;                     // the pinned blob as the device sees it (else: plain copy)
-        if (ctx->upload_by_kernel && hipHostGetDevicePointer(&up_devptr, const_cast<char *>(up), 0) != hipSuccess) { up_devptr = nullptr; (void)hipGetLastError(); }
-        // (option short_chain: the tables are still on the device and the previous call's download kernel left the status block zero)
-        // (... on the route the option applies to, short_route, as far as it is known before K0: every other route launches what it launched)
-        const bool short_rt = use_bs && !wide && !digest_ready && ctx->groups && !ctx->tree_mw && ctx->tree_screen && cfg.mode == MODE_FAST && cfg.prune;
-        const bool skip_upload = reuse && ctx->small_clean_in && !front && short_rt && ctx->upload_by_kernel && (ctx->short_chain & SC_NO_UPLOAD);
-        ctx->small_clean_in = false;                   // (a redo of this call on another digest starts from a block it cleared itself)
-        if (skip_upload) ctx->counters[17] += 1;
-        else if (up_devptr) {
-            // (tables still on the device from the previous call: the kernel only clears the status block)
-            const long long n16 = reuse ? 0 : static_cast<long long>((up_bytes + 15) / 16);
-            const unsigned ug = static_cast<unsigned>(std::max<long long>(1, std::min<long long>((n16 + 255) / 256, 1024)));
-            hipLaunchKernelGGL(upload_kernel, dim3(ug), dim3(256), 0, fs, static_cast<const int4 *>(up_devptr),
-                               ctx->up_dev.as<int4>(), n16, ctx->small.as<unsigned long long>(),
-                               static_cast<int>(sizeof(SmallLayout) / sizeof(unsigned long long)));
-            HIP_TRY(ctx, hipGetLastError());
-        } else {
-            HIP_TRY(ctx, hipMemsetAsync(ctx->small.p, 0, sizeof(SmallLayout), fs));
-            if (!reuse) HIP_TRY(ctx, hipMemcpyAsync(ctx->up_dev.p, up, up_bytes, hipMemcpyHostToDevice, fs));
-        }
-        tc.valid = true;
-    }
-    char *dup = ctx->up_dev.as<char>();
-    ctx->spine_jobs.alias(dup);
-    ctx->ev_first_tile.alias(dup + jb);
-    ctx->ev_off.alias(dup + jb + evb);
-    ctx->ev_len.alias(dup + jb + 2 * evb);
-    ctx->ev_boff.alias(dup + jb + 3 * evb);
-
-    SmallLayout *sm = ctx->small.as<SmallLayout>();
+    if (int urc = queue_upload(ctx, B, C, fs, front != nullptr)) return urc;
     if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[7], fs));
-    if (use_bs && nj && digest_ready) {
-        HIP_TRY(ctx, ctx->ev_info_tr.reserve(static_cast<size_t>(std::max(1, n_ev)) * sizeof(int4)));
-        hipLaunchKernelGGL(ev_info_trace_kernel, dim3(static_cast<unsigned>(std::min(64, (n_ev + 255) / 256))), dim3(256), 0, fs,
-                           ctx->ev_off.as<int64_t>(), n_ev, ctx->ev_info.as<int4>(), ctx->ev_info_tr.as<int4>());
-        HIP_TRY(ctx, hipGetLastError());
-        cfg.bsum = ctx->bsum.p;
-        cfg.ev_info = ctx->ev_info_tr.as<int4>();
-        cfg.chunk_tot = ctx->chunk_mabs.as<int4>();
-        cfg.grp = ctx->groups ? ctx->grp.p : nullptr;
-        cfg.blk_mm = d_stats ? ctx->blk_mm.as<int>() : nullptr;
-    } else if (use_bs && nj) {
-        const int64_t nb_pad = k0_padded_blocks(tc.nb_total);
-        DigestWant want;
-        want.wide = wide;
-        want.grp = !wide && ctx->groups;
-        want.blk_mm = d_stats && !wide;
-        if (int drc = reserve_digest(ctx, nb_pad, n_ev, want)) return drc;
-        if (want.grp) cfg.grp = ctx->grp.p;
-        if (want.blk_mm) cfg.blk_mm = ctx->blk_mm.as<int>();
-        K0Call k0 = {ctx->ev_off.as<int64_t>(), ctx->ev_len.as<int64_t>(), ctx->ev_boff.as<int64_t>(), n_ev, sample_end, nb_pad};
-        k0.admit = !front;                             // (the front stream serialises the K0s of its contexts by itself)
-        k0.batch = true;
-        k0.repeat = reuse;
-        if (int krc = wide ? launch_k0<DT_WIDE>(ctx, cfg, fs, k0) : launch_k0<0>(ctx, cfg, fs, k0)) return krc;
-        cfg.bsum = ctx->bsum.p;
-        cfg.ev_info = ctx->ev_info.as<int4>();
-        cfg.chunk_tot = ctx->chunk_mabs.as<int4>();
-    }
+    if (int drc = queue_digest(ctx, B, C, fs, front != nullptr)) return drc;
     if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[0], fs));
     if (int crc = k0_done(ctx, fs)) return crc;         // (K0 is behind this event)
+    *k0_only = false;
 #ifdef PS_DIAG
     if (ctx->dbg_phase == 2) {                           // diagnostics: K0 only
         if (front) front_lock.unlock();
         HIP_TRY(ctx, hipStreamSynchronize(fs));
-        for (int e = 0; e <= n_ev; ++e) h_bounds_off[e] = 0;
+        for (int e = 0; e <= B.n_ev; ++e) B.h_bounds_off[e] = 0;
+        *k0_only = true;
         return PS_OK;
     }
 #endif
@@ -1362,11 +1352,19 @@ int device_stitch_batch_(ps_ctx *ctx, const DevCfg &cfg_in, int bs_mode, const i
         front_lock.unlock();
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_front[1], 0));
     }
-    if (nj) {
-        const unsigned g = static_cast<unsigned>(nj);
+    return PS_OK;
+}
+
+// Step 4.  Phases 1 and 1b over the tiles, on the context's stream
+int queue_scans(ps_ctx *ctx, const DeviceCall &C)
+{
+    const DevCfg &cfg = C.cfg;
+    SmallLayout *sm = ctx->small.as<SmallLayout>();
+    if (C.nj) {
+        const unsigned g = static_cast<unsigned>(C.nj);
         int lrc;
-        if (wide) lrc = launch_scans_bs<DT_WIDE>(ctx, cfg, g, sm);      // (the 64-bit digest: same kernels, compiled for it)
-        else if (use_bs) lrc = launch_scans_bs<0>(ctx, cfg, g, sm);
+        if (C.wide) lrc = launch_scans_bs<DT_WIDE>(ctx, cfg, g, sm);      // (the 64-bit digest: same kernels, compiled for it)
+        else if (C.use_bs) lrc = launch_scans_bs<0>(ctx, cfg, g, sm);
         else {
             // LDS-window scan at the option's width (spine_nt); the widest spine is bridged by the 512-thread kernel
             lrc = launch_spine_nt(ctx, cfg, g, sm, true);
@@ -1379,117 +1377,124 @@ int device_stitch_batch_(ps_ctx *ctx, const DevCfg &cfg_in, int bs_mode, const i
         if (lrc) return lrc;
     }
     if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    return PS_OK;
+}
+
+// One stitch: the true spine per event from the tile lists and the bridges, then items and subtree jobs for up to items_cap
+// anchors.  No host round trip here: the downstream kernels read the item count from the header on the device (launches sized
+// by the host-side upper bound), header and status are checked after the final sync.
+struct StitchShape { size_t tile_lds = 0; int use_lds = 0; };     // per-tile arrays of the stitch live in LDS when they fit
+int queue_stitch(ps_ctx *ctx, const SegBatch &B, const DeviceCall &C, const StitchShape &shape, int64_t items_cap, int ext_stride)
+{
+    const size_t nj = C.nj, njp = std::max<size_t>(1, nj);
+    SmallLayout *sm = ctx->small.as<SmallLayout>();
     int *ti = ctx->tile_i32.as<int>();
-    const size_t njp = std::max<size_t>(1, nj);
-    // per-tile arrays of the stitch live in LDS when they fit: (nj+1) int64 + 4*nj int32
-    const size_t tile_lds = (nj + 1) * sizeof(long long) + 4 * nj * sizeof(int);
-    const int use_lds = tile_lds <= 150 * 1024;
-    if (use_lds)
-        HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(assemble_tiles_kernel), static_cast<int>(tile_lds)));
+    hipLaunchKernelGGL(assemble_tiles_kernel, dim3(1), dim3(1024), shape.use_lds ? shape.tile_lds : 0, ctx->stream,
+                       static_cast<int>(nj), ctx->spine_meta.as<int4>(), ctx->bmeta.as<int4>(),
+                       ctx->ev_first_tile.as<int64_t>(), B.n_ev, ti, ti + njp, ti + 2 * njp, ti + 3 * njp,
+                       ctx->sp_off.as<long long>(), ctx->first_item.as<int64_t>(), ctx->asm_hdr.as<AsmHeader>(),
+                       static_cast<long long>(items_cap), shape.use_lds, reinterpret_cast<const unsigned *>(&sm->status));
+    HIP_TRY(ctx, hipGetLastError());
+    if (items_cap > 0) {
+        const unsigned ag = static_cast<unsigned>(std::min<int64_t>((items_cap + 255) / 256, 2048));
+        hipLaunchKernelGGL(assemble_items_kernel, dim3(ag), dim3(256), 0,
+                           ctx->stream, ctx->spine_jobs.as<SpineJob>(), static_cast<int>(nj), ctx->spine_meta.as<int4>(),
+                           ctx->spine_scratch.as<int2>(), ctx->bridges.as<int2>(), ti + 3 * njp,
+                           ctx->sp_off.as<long long>(), static_cast<long long>(items_cap), B.mw, B.W, ctx->tree_jobs.as<TreeJob>(),
+                           ctx->items.as<Item>(), ctx->tree_counts.as<int32_t>(), ctx->asm_hdr.as<AsmHeader>(),
+                           C.cfg.bsum != nullptr ? C.cfg.ev_info : nullptr,
+                           ctx->bridge_ext.as<int2>(), ctx->ext_slot.as<int>(), ext_stride);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return PS_OK;
+}
+
+// A call that issued no look-ahead launch (option short_chain) and whose bridges left seams deferred: the look-ahead
+// kernel it did without runs now, once, over every deferred seam, however many, from the window each stopped at --
+// exactly what it would have done behind the bridge kernel, one round trip later.  Seams that gave up are the business
+// of the rounds after it.
+int resume_deferred_seams(ps_ctx *ctx, const DeviceCall &C, int64_t n_def)
+{
+    SmallLayout *sm = ctx->small.as<SmallLayout>();
+    if (ctx->debug) fprintf(stderr, "[poreseg] look-ahead kernel behind the stitch: %lld deferred seams\n", static_cast<long long>(n_def));
+    HIP_TRY(ctx, hipMemsetAsync(&sm->hdr, 0, sizeof(AsmHeader), ctx->stream));
+    if (ctx->tree_screen) HIP_TRY(ctx, hipMemsetAsync(&sm->tree_defer[0], 0, sizeof sm->tree_defer[0], ctx->stream));
+    if (int lrc = by_dtype(C.cfg.dtype, [&](auto dt) { return launch_bridge_la<dt()>(ctx, C.cfg, static_cast<unsigned>(C.nj), sm); })) return lrc;
+    ctx->la_keep = LA_KEEP;
+    ctx->counters[4] += n_def;
+    ctx->counters[18] += n_def;
+    return PS_OK;
+}
+
+// The seams of `list` are continued by the look-ahead kernel, their further anchors in the side buffer from slot slots_used on
+int extend_seams(ps_ctx *ctx, const DeviceCall &C, const std::vector<int> &list, int slots_used, int ext_stride)
+{
+    const size_t nj = C.nj, n_ext = list.size();
+    SmallLayout *sm = ctx->small.as<SmallLayout>();
+    HIP_TRY(ctx, ctx->bridge_ext.reserve(static_cast<size_t>(EXT_SLOTS) * EXT_MAX * sizeof(int2)));
+    HIP_TRY(ctx, ctx->ext_slot.reserve(nj * sizeof(int)));
+    HIP_TRY(ctx, ctx->ext_list.reserve(static_cast<size_t>(EXT_SLOTS) * (EXT_MAX / EXT_MAX_MANY) * sizeof(int)));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->ext_list.p, list.data(), n_ext * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                       // (the list is the caller's local)
+    HIP_TRY(ctx, hipMemsetAsync(&sm->hdr, 0, sizeof(AsmHeader), ctx->stream));
+    // (the next round's screen starts a new list; what the rounds so far decided and deferred stays, as in work[])
+    if (ctx->tree_screen) HIP_TRY(ctx, hipMemsetAsync(&sm->tree_defer[0], 0, sizeof sm->tree_defer[0], ctx->stream));
+    const unsigned g = static_cast<unsigned>(n_ext);
+    auto extend = [&](auto dt) {
+        hipLaunchKernelGGL((bridge_la_kernel<dt(), true>), dim3(g), dim3(64 * BR_LA), 0, ctx->stream, C.cfg,
+                           ctx->spine_jobs.as<SpineJob>(), ctx->spine_scratch.as<int2>(), ctx->spine_meta.as<int4>(),
+                           ctx->bridges.as<int2>(), ctx->bmeta.as<int4>(), reinterpret_cast<unsigned *>(&sm->status),
+                           &sm->work0, static_cast<int>(n_ext), ctx->ext_list.as<int>(), ctx->bridge_ext.as<int2>(),
+                           ctx->ext_slot.as<int>(), slots_used, BR_MAX, ext_stride);
+    };
+    if (C.wide) by_dtype<DT_WIDE>(C.cfg.dtype, extend);
+    else by_dtype(C.cfg.dtype, extend);
+    HIP_TRY(ctx, hipGetLastError());
+    ctx->counters[4] += static_cast<int64_t>(n_ext);
+    return PS_OK;
+}
+
+// Step 5.  Stitch, subtrees and gather, to the call's one synchronisation (finish_batch); a stitch that failed gets its
+// second chance on the device (the block-sum pipeline only: it has the look-ahead kernel) and the round is run again.
+int stitch_rounds(ps_ctx *ctx, const SegBatch &B, const DeviceCall &C)
+{
+    const size_t nj = C.nj;
+    StitchShape shape;
+    shape.tile_lds = (nj + 1) * sizeof(long long) + 4 * nj * sizeof(int);      // (nj+1) int64 + 4*nj int32
+    shape.use_lds = shape.tile_lds <= 150 * 1024;
+    if (shape.use_lds)
+        HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(assemble_tiles_kernel), static_cast<int>(shape.tile_lds)));
     AsmHeader hd = {};
     int rc = PS_OK;
-    int64_t items_cap = max_items;                      // (grows with the seams a second-chance round extends)
+    int64_t items_cap = C.max_items;                    // (grows with the seams a second-chance round extends)
     int slots_used = 0, ext_stride = EXT_MAX;
-    const bool no_la = nj && no_look_ahead(ctx, cfg);
+    const bool no_la = nj && no_look_ahead(ctx, C.cfg);
     bool la_done = false, stride_set = false;          // (the look-ahead kernel ran behind the stitch; the stride of the side buffer is fixed)
     for (int round = 0;; ++round) {
-        hipLaunchKernelGGL(assemble_tiles_kernel, dim3(1), dim3(1024), use_lds ? tile_lds : 0, ctx->stream,
-                           static_cast<int>(nj), ctx->spine_meta.as<int4>(), ctx->bmeta.as<int4>(),
-                           ctx->ev_first_tile.as<int64_t>(), n_ev, ti, ti + njp, ti + 2 * njp, ti + 3 * njp,
-                           ctx->sp_off.as<long long>(), ctx->first_item.as<int64_t>(), ctx->asm_hdr.as<AsmHeader>(),
-                           static_cast<long long>(items_cap), use_lds, reinterpret_cast<const unsigned *>(&sm->status));
-        HIP_TRY(ctx, hipGetLastError());
-        // no host round trip here: the downstream kernels read the item count from the header on the device
-        // (launches sized by the host-side upper bound), header and status are checked after the final sync
-        const AsmHeader *d_hdr = ctx->asm_hdr.as<AsmHeader>();
-        if (items_cap > 0) {
-            const unsigned ag = static_cast<unsigned>(std::min<int64_t>((items_cap + 255) / 256, 2048));
-            hipLaunchKernelGGL(assemble_items_kernel, dim3(ag), dim3(256), 0,
-                               ctx->stream, ctx->spine_jobs.as<SpineJob>(), static_cast<int>(nj), ctx->spine_meta.as<int4>(),
-                               ctx->spine_scratch.as<int2>(), ctx->bridges.as<int2>(), ti + 3 * njp,
-                               ctx->sp_off.as<long long>(), static_cast<long long>(items_cap), mw, W, ctx->tree_jobs.as<TreeJob>(),
-                               ctx->items.as<Item>(), ctx->tree_counts.as<int32_t>(), d_hdr, cfg.bsum != nullptr ? cfg.ev_info : nullptr,
-                               ctx->bridge_ext.as<int2>(), ctx->ext_slot.as<int>(), ext_stride);
-            HIP_TRY(ctx, hipGetLastError());
-        }
+        if (int qrc = queue_stitch(ctx, B, C, shape, items_cap, ext_stride)) return qrc;
         if (ctx->timing >= 2 && round == 0) HIP_TRY(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
-        rc = finish_batch(ctx, cfg, static_cast<size_t>(items_cap), items_cap, n_ev, d_bounds, cap, h_bounds_off, d_stats, t_begin,
-                          d_hdr, &hd, use_bs);
-        // ---- second chance for seams that gave up (the block-sum pipeline only: it has the look-ahead kernel) -------------
-        if (rc != RC_FALLBACK || !use_bs || !nj || round == EXT_ROUNDS + (la_done ? 1 : 0) || !ctx->bridge_ext_on) break;
+        rc = finish_batch(ctx, C.cfg, B, static_cast<size_t>(items_cap), items_cap, ctx->asm_hdr.as<AsmHeader>(), &hd, C.use_bs);
+        if (rc != RC_FALLBACK || !C.use_bs || !nj || round == EXT_ROUNDS + (la_done ? 1 : 0) || !ctx->bridge_ext_on) break;
         HIP_TRY(ctx, ctx->h_meta.reserve(2 * nj * sizeof(int4)));
         int4 *h_bm = ctx->h_meta.as<int4>(), *h_mt = h_bm + nj;
         HIP_TRY(ctx, hipMemcpyAsync(h_bm, ctx->bmeta.p, nj * sizeof(int4), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(h_mt, ctx->spine_meta.p, nj * sizeof(int4), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        // on the true path: whatever failed there (a seam out of anchors, an open tile entered at its start); elsewhere: the
-        // seams that ran out of anchors (few; they may lie on the path once the first ones are mended)
-        // A call that issued no look-ahead launch (option short_chain) and whose bridges left seams deferred: the look-ahead
-        // kernel it did without runs now, once, over every deferred seam, however many, from the window each stopped at --
-        // exactly what it would have done behind the bridge kernel, one round trip later.  Seams that gave up are the business
-        // of the rounds after it.
-        if (no_la && !la_done) {
-            int64_t n_def = 0;
-            for (size_t g = 0; g < nj; ++g) n_def += h_bm[g].w == BR_DEFER || h_bm[g].w == BR_DEFER_REACHED;
-            if (n_def) {
-                if (ctx->debug) fprintf(stderr, "[poreseg] look-ahead kernel behind the stitch: %lld deferred seams\n", static_cast<long long>(n_def));
-                HIP_TRY(ctx, hipMemsetAsync(&sm->hdr, 0, sizeof(AsmHeader), ctx->stream));
-                if (ctx->tree_screen) HIP_TRY(ctx, hipMemsetAsync(&sm->tree_defer[0], 0, sizeof sm->tree_defer[0], ctx->stream));
-                if (int lrc = by_dtype(cfg.dtype, [&](auto dt) { return launch_bridge_la<dt()>(ctx, cfg, static_cast<unsigned>(nj), sm); })) return lrc;
-                la_done = true;
-                ctx->la_keep = LA_KEEP;
-                ctx->counters[4] += n_def;
-                ctx->counters[18] += n_def;
-                continue;
-            }
+        const SecondChance sc = pick_second_chance(h_bm, h_mt, nj, ctx->bridge_budget, slots_used, stride_set, ext_stride, no_la && !la_done);
+        if (sc.n_deferred) {
+            if (int lrc = resume_deferred_seams(ctx, C, sc.n_deferred)) return lrc;
+            la_done = true;
+            continue;
         }
-        std::vector<int> list;
-        bool hopeless = false;
-        if (!stride_set) {                             // few seams: long extensions; many (a batch of events): shorter ones
-            size_t n_fail = 0;
-            for (size_t g = 0; g < nj; ++g) n_fail += h_bm[g].w == BR_FAIL_REACHED || (h_bm[g].w == BR_FAIL && h_bm[g].x == ctx->bridge_budget);
-            ext_stride = n_fail <= static_cast<size_t>(EXT_SLOTS) ? EXT_MAX : EXT_MAX_MANY;
-            stride_set = true;
-        }
-        const int slot_cap = EXT_SLOTS * (EXT_MAX / ext_stride);
-        for (size_t g = 0; g < nj; ++g) {
-            const bool reached = h_bm[g].w == BR_FAIL_REACHED;
-            const bool gave_up = h_bm[g].x == ctx->bridge_budget;                 // (out of anchors in the first pass)
-            if (!reached && !(h_bm[g].w == BR_FAIL && gave_up)) continue;
-            const bool open_tile = h_mt[g].x == 0 && h_bm[g].x == 0;
-            if (!gave_up && !open_tile) { if (reached) hopeless = true; continue; }   // (extended before and still not joined)
-            if (slots_used + static_cast<int>(list.size()) < slot_cap) list.push_back(static_cast<int>(g));
-            else if (reached) hopeless = true;
-        }
-        if (list.empty() || hopeless) break;
-        if (ctx->debug) fprintf(stderr, "[poreseg] second chance, round %d: %zu seams continued on the device\n", round + 1, list.size());
-        const size_t n_ext = list.size();
-        HIP_TRY(ctx, ctx->bridge_ext.reserve(static_cast<size_t>(EXT_SLOTS) * EXT_MAX * sizeof(int2)));
-        HIP_TRY(ctx, ctx->ext_slot.reserve(nj * sizeof(int)));
-        HIP_TRY(ctx, ctx->ext_list.reserve(static_cast<size_t>(EXT_SLOTS) * (EXT_MAX / EXT_MAX_MANY) * sizeof(int)));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->ext_list.p, list.data(), n_ext * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                       // (list is a local)
-        HIP_TRY(ctx, hipMemsetAsync(&sm->hdr, 0, sizeof(AsmHeader), ctx->stream));
-        // (the next round's screen starts a new list; what the rounds so far decided and deferred stays, as in work[])
-        if (ctx->tree_screen) HIP_TRY(ctx, hipMemsetAsync(&sm->tree_defer[0], 0, sizeof sm->tree_defer[0], ctx->stream));
-        {
-            const unsigned g = static_cast<unsigned>(n_ext);
-            auto extend = [&](auto dt) {
-                hipLaunchKernelGGL((bridge_la_kernel<dt(), true>), dim3(g), dim3(64 * BR_LA), 0, ctx->stream, cfg,
-                                   ctx->spine_jobs.as<SpineJob>(), ctx->spine_scratch.as<int2>(), ctx->spine_meta.as<int4>(),
-                                   ctx->bridges.as<int2>(), ctx->bmeta.as<int4>(), reinterpret_cast<unsigned *>(&sm->status),
-                                   &sm->work0, static_cast<int>(n_ext), ctx->ext_list.as<int>(), ctx->bridge_ext.as<int2>(),
-                                   ctx->ext_slot.as<int>(), slots_used, BR_MAX, ext_stride);
-            };
-            if (wide) by_dtype<DT_WIDE>(cfg.dtype, extend);
-            else by_dtype(cfg.dtype, extend);
-            HIP_TRY(ctx, hipGetLastError());
-        }
-        ctx->counters[4] += static_cast<int64_t>(n_ext);
-        slots_used += static_cast<int>(n_ext);
+        ext_stride = sc.ext_stride;
+        stride_set = true;
+        if (sc.list.empty() || sc.hopeless) break;
+        if (ctx->debug) fprintf(stderr, "[poreseg] second chance, round %d: %zu seams continued on the device\n", round + 1, sc.list.size());
+        if (int erc = extend_seams(ctx, C, sc.list, slots_used, ext_stride)) return erc;
+        slots_used += static_cast<int>(sc.list.size());
         // room for the anchors the continued seams may add
-        items_cap += static_cast<int64_t>(n_ext) * ext_stride;
-        if (int irc = reserve_items(ctx, items_cap, total_len, mw)) return irc;
+        items_cap += static_cast<int64_t>(sc.list.size()) * ext_stride;
+        if (int irc = reserve_items(ctx, items_cap, ctx->tile_cache.plan.total_len, B.mw)) return irc;
     }
     ctx->counters[3] = hd.n_items;
     if (slots_used > 0 || la_done) ctx->small_clean = false;   // (a second round: the next call uploads as ever)
@@ -1500,14 +1505,110 @@ int device_stitch_batch_(ps_ctx *ctx, const DevCfg &cfg_in, int bs_mode, const i
     if (ctx->timing >= 2 && hipEventElapsedTime(&ms, ctx->ev[1], ctx->ev[5]) == hipSuccess) ctx->ms[4] = ms;     // device stitch incl. header sync
     return rc;
 }
-// (whatever way the call ends: a ticket of the K0 chain that was not recorded is forgotten)
-int device_stitch_batch(ps_ctx *ctx, const DevCfg &cfg_in, int bs_mode, const int64_t *ev_start, const int64_t *ev_len, int32_t n_ev, int mw, int W,
-                        int32_t *d_bounds, int64_t cap, int64_t *h_bounds_off, ps_segstat *d_stats,
-                        std::chrono::steady_clock::time_point t_begin, bool digest_ready = false)
+
+int device_stitch_batch_(ps_ctx *ctx, const DevCfg &cfg_in, int bs_mode, const SegBatch &B, bool digest_ready)
 {
-    const int rc = device_stitch_batch_(ctx, cfg_in, bs_mode, ev_start, ev_len, n_ev, mw, W, d_bounds, cap, h_bounds_off, d_stats, t_begin, digest_ready);
+    DeviceCall C;
+    C.cfg = cfg_in;
+    ctx->la_now = ctx->la_keep > 0;
+    if (ctx->la_now) --ctx->la_keep;
+    C.use_bs = bs_mode != 0;                           // 1: block-sum scan on the 32-bit digest, 2: on the 64-bit (wide) digest
+    C.wide = bs_mode == 2;
+    C.cfg.bs_wide = C.wide ? 1 : 0;
+    C.digest_ready = digest_ready;
+    if (int rc = plan_or_reuse(ctx, B, C)) return rc;
+    if (int rc = reserve_call_buffers(ctx, B, C)) return rc;
+    bool k0_only = false;
+    if (int rc = queue_upload_k0(ctx, B, C, &k0_only)) return rc;
+    if (k0_only) return PS_OK;
+    if (int rc = queue_scans(ctx, C)) return rc;
+    return stitch_rounds(ctx, B, C);
+}
+// (whatever way the call ends: a ticket of the K0 chain that was not recorded is forgotten)
+int device_stitch_batch(ps_ctx *ctx, const DevCfg &cfg_in, int bs_mode, const SegBatch &B, bool digest_ready = false)
+{
+    const int rc = device_stitch_batch_(ctx, cfg_in, bs_mode, B, digest_ready);
     chain_drop(ctx);                                    // (a call that failed between its ticket and its record gives the ticket up)
     return rc;
+}
+
+// The host stitch's subtree jobs, items and per-event tables go to the device, the buffers of phase 3 and the gather sized by them
+int upload_host_stitch(ps_ctx *ctx, const SegBatch &B, const HostStitch &st)
+{
+    const int32_t n_ev = B.n_ev;
+    const size_t n_tj = st.tjobs.size(), n_items = st.items.size(), tscratch = static_cast<size_t>(st.tscratch);
+    const size_t evb = (static_cast<size_t>(n_ev) + 1) * sizeof(int64_t);
+    const size_t up_bytes = n_tj * sizeof(TreeJob) + n_items * sizeof(Item) + evb * 3;
+    HIP_TRY(ctx, ctx->h_up.reserve(up_bytes + 64));
+    HIP_TRY(ctx, ctx->tree_jobs.reserve(std::max<size_t>(1, n_tj) * sizeof(TreeJob)));
+    // (item_scan_kernel reads counts[item index] speculatively: cover the items as well)
+    HIP_TRY(ctx, ctx->tree_counts.reserve(std::max<size_t>(std::max<size_t>(1, n_tj), n_items) * sizeof(int32_t)));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->tree_counts.p, 0, std::max<size_t>(std::max<size_t>(1, n_tj), n_items) * sizeof(int32_t), ctx->stream));   // (tree_job stores only non-zero counts)
+    HIP_TRY(ctx, ctx->tree_scratch.reserve(std::max<size_t>(1, tscratch) * sizeof(int32_t)));
+    HIP_TRY(ctx, ctx->tree_spill.reserve(std::max<size_t>(1, tscratch) * sizeof(int2)));
+    HIP_TRY(ctx, ctx->items.reserve(std::max<size_t>(1, n_items) * sizeof(Item)));
+    HIP_TRY(ctx, ctx->item_pos.reserve((n_items + 1) * sizeof(int64_t)));
+    HIP_TRY(ctx, ctx->first_item.reserve(evb));
+    HIP_TRY(ctx, ctx->ev_off.reserve(evb));
+    HIP_TRY(ctx, ctx->ev_len.reserve(evb));
+    HIP_TRY(ctx, ctx->bounds_off.reserve(evb));
+    char *up = ctx->h_up.as<char>();
+    size_t o = 0;
+    if (n_tj) {
+        std::memcpy(up + o, st.tjobs.data(), n_tj * sizeof(TreeJob));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->tree_jobs.p, up + o, n_tj * sizeof(TreeJob), hipMemcpyHostToDevice, ctx->stream));
+        o += n_tj * sizeof(TreeJob);
+    }
+    if (n_items) {
+        std::memcpy(up + o, st.items.data(), n_items * sizeof(Item));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->items.p, up + o, n_items * sizeof(Item), hipMemcpyHostToDevice, ctx->stream));
+        o += n_items * sizeof(Item);
+    }
+    o = (o + 7) & ~static_cast<size_t>(7);
+    std::memcpy(up + o, st.first_item.data(), evb);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->first_item.p, up + o, evb, hipMemcpyHostToDevice, ctx->stream));
+    o += evb;
+    std::memcpy(up + o, B.ev_start, evb - sizeof(int64_t));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->ev_off.p, up + o, evb, hipMemcpyHostToDevice, ctx->stream));
+    o += evb;
+    std::memcpy(up + o, B.ev_len, evb - sizeof(int64_t));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->ev_len.p, up + o, evb, hipMemcpyHostToDevice, ctx->stream));
+    return PS_OK;
+}
+
+// Host-stitch pipeline (the fallback of the device stitch, and option stitch_host): halo tiles, one spine workgroup each; their
+// anchor lists come back and the true spine of every event is walked on the host (seg_plan.hpp: stitch_lists), a seam whose
+// list stops short repaired by a spine launch of its own; then phase 3 and the gather as on the device route.
+int host_stitch_batch(ps_ctx *ctx, const DevCfg &cfg, const SegBatch &B)
+{
+    const HostTilePlan plan = plan_host_tiles(B.ev_start, B.ev_len, B.n_ev, B.mw, B.W, ctx->tile_len, ctx->halo);
+    ctx->counters[2] = static_cast<int64_t>(plan.jobs.size());
+    std::vector<TileList> lists;
+    int rc = run_spines(ctx, cfg, plan.jobs, plan.scratch, lists);
+    if (rc) return rc;
+
+    const auto t_stitch0 = std::chrono::steady_clock::now();
+    auto repair = [&](int32_t e, int32_t z, int64_t stop, TileList *ext) {
+        const std::vector<SpineJob> rj(1, make_spine_job(B.ev_start[e], e, B.ev_len[e], z, stop, B.mw, 0));
+        std::vector<TileList> got;
+        rc = run_spines(ctx, cfg, rj, rj[0].out_cap, got);
+        if (rc) return false;
+        ctx->counters[4] += 1;
+        *ext = std::move(got[0]);
+        return true;
+    };
+    HostStitch st;
+    switch (stitch_lists(plan, lists, B.ev_start, B.ev_len, B.n_ev, B.mw, B.W, repair, &st)) {
+    case STITCH_OK: break;
+    case STITCH_REPAIR_FAILED: return rc;
+    case STITCH_NO_PROGRESS: return fail(ctx, PS_ERR_INTERNAL, "seam repair made no progress");
+    }
+    ctx->counters[3] = static_cast<int64_t>(st.tjobs.size());
+    ctx->ms[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_stitch0).count();
+
+    rc = upload_host_stitch(ctx, B, st);
+    if (rc) return rc;
+    return finish_batch(ctx, cfg, B, st.tjobs.size(), static_cast<int64_t>(st.items.size()));
 }
 }  // namespace
 
@@ -1761,7 +1862,7 @@ int ps_set_option(ps_ctx *ctx, const char *name, int64_t value)
     else if (n == "rep_sum" && value >= 1) ctx->rep_sum = static_cast<int>(value);
 #endif
     else if (n == "bridge_budget" && value >= 1 && value <= BR_MAX) ctx->bridge_budget = static_cast<int>(value);
-    else if (n == "wide_bs") { ctx->wide_bs = value != 0; ctx->wide_skip = 0; }
+    else if (n == "wide_bs") { ctx->wide_bs = value != 0; ctx->wide.forget(); }
     else if (n == "bridge_single" && value >= 1) ctx->bridge_single = static_cast<int>(value);
     else if (n == "tree_tail_pct" && value >= 0 && value <= 100) ctx->tree_tail_pct = static_cast<int>(value);
     else if (n == "filter_fused") ctx->filt.fused = value != 0;
@@ -2111,180 +2212,30 @@ static int segment_events_body(ps_ctx *ctx, const void *d_samples, const ps_samp
         }
     }
 
+    const SegBatch B = {ev_start, ev_len, n_ev, mw, W, d_bounds, cap, h_bounds_off, d_stats, t_begin};
     if (!ctx->stitch_host) {
-        // block-sum scan: candidates must avoid the ragged ends of a window (min_width >= 8) and a window must fit
-        // the single-wave sweep (at most 64 digest chunks: W <= 64 512); otherwise the LDS-window kernels take the call
-        bool use_bs = ctx->scan_bs && mw >= 8 && W <= 63 * 1024 && ctx->mode != MODE_EXACT && !d_f64;
-        // Counts too wide for the 32-bit digest (K0 says so: RC_WIDE): the call is redone on the 64-bit digest, and if
-        // that refuses too (|k - m| >= 2^23) on the LDS-window kernels.  The next 16 calls on the same grid start where
-        // this one ended (counters[7]: 1 = 64-bit digest, 2 = LDS-window scan).
-        int bs_mode = use_bs ? 1 : 0, redo = 0;
-        if (use_bs && ctx->wide_skip > 0 && fmt->quantum == ctx->wide_quantum) { bs_mode = ctx->wide_mode; --ctx->wide_skip; redo = bs_mode == 2 ? 1 : 2; }
-        rc = device_stitch_batch(ctx, cfg, bs_mode, ev_start, ev_len, n_ev, mw, W, d_bounds, cap, h_bounds_off, d_stats, t_begin);
+        // The route (seg_plan.hpp): the block-sum scan where the call fits it, else the LDS-window kernels.  Counts too wide for
+        // the 32-bit digest (K0 says so: RC_WIDE): the call is redone on the 64-bit digest, and if that refuses too on the
+        // LDS-window kernels; the calls after it on the same grid start where it ended (counters[7]: 1 = 64-bit digest, 2 =
+        // LDS-window scan).
+        WideRedo &wide = ctx->wide;
+        const bool use_bs = scan_route_bs(ctx->scan_bs != 0, mw, W, ctx->mode == MODE_EXACT, d_f64);
+        rc = device_stitch_batch(ctx, cfg, wide.begin(use_bs, fmt->quantum), B);
         while (rc == RC_WIDE) {
-            bs_mode = (bs_mode == 1 && ctx->wide_bs) ? 2 : 0;
-            redo = bs_mode == 2 ? 1 : 2;
-            ctx->wide_quantum = fmt->quantum;
-            ctx->wide_mode = bs_mode;
-            ctx->wide_skip = 16;
+            const int bs_mode = wide.refused(ctx->wide_bs != 0, fmt->quantum);
             reset_call_stats(ctx);
             HIP_TRY(ctx, hipMemsetAsync(ctx->small.p, 0, sizeof(SmallLayout), ctx->stream));
             ctx->stream_idle = false;                  // (the front stream, if used, waits for this memset)
-            rc = device_stitch_batch(ctx, cfg, bs_mode, ev_start, ev_len, n_ev, mw, W, d_bounds, cap, h_bounds_off, d_stats, t_begin);
+            rc = device_stitch_batch(ctx, cfg, bs_mode, B);
         }
-        if (redo) ctx->counters[7] = redo;
+        if (wide.redo) ctx->counters[7] = wide.redo;
         if (rc != RC_FALLBACK) return rc;
         // a seam could not be bridged on the device: redo with the host stitch (halo tiles + repairs)
         reset_call_stats(ctx);
         ctx->counters[4] = 1000000;
         HIP_TRY(ctx, hipMemsetAsync(ctx->small.p, 0, sizeof(SmallLayout), ctx->stream));
     }
-
-    // ---- tiles ----------------------------------------------------------------------------------
-    // Tiling: one spine workgroup per tile.  Default: as many tiles as the chip keeps resident at once
-    // (2 workgroups of 512 threads per CU on 256 CUs) so the grid runs as a single wave of blocks,
-    // but never shorter than 8 windows (the halo is pure overhead).
-    int64_t total_len = 0;
-    for (int e = 0; e < n_ev; ++e) total_len += ev_len[e];
-    const int64_t H = ctx->halo > 0 ? ctx->halo : 4LL * W;
-    int64_t L = ctx->tile_len;
-    if (L <= 0) {
-        const int64_t resident = 512;
-        L = std::max<int64_t>(8LL * W, (total_len + resident - 1) / resident);
-    }
-    std::vector<SpineJob> jobs;
-    std::vector<int64_t> ev_first_tile(static_cast<size_t>(n_ev) + 1, 0);
-    int64_t scratch = 0;
-    for (int e = 0; e < n_ev; ++e) {
-        ev_first_tile[e] = static_cast<int64_t>(jobs.size());
-        const int64_t len = ev_len[e];
-        if (len == 0) continue;
-        const int64_t nt = len <= L + H ? 1 : (len + L - 1) / L;
-        for (int64_t t = 0; t < nt; ++t) {
-            const int64_t stop = (t == nt - 1) ? len : std::min(len, (t + 1) * L + H);
-            jobs.push_back(make_spine_job(ev_start[e], e, len, t * L, stop, mw, scratch));
-            scratch += jobs.back().out_cap;
-        }
-    }
-    ev_first_tile[n_ev] = static_cast<int64_t>(jobs.size());
-    ctx->counters[2] = static_cast<int64_t>(jobs.size());
-
-    std::vector<TileList> lists;
-    rc = run_spines(ctx, cfg, jobs, scratch, lists);
-    if (rc) return rc;
-
-    // ---- stitch: true spine per event -------------------------------------------------------------
-    const auto t_stitch0 = std::chrono::steady_clock::now();
-    std::vector<TreeJob> tjobs;
-    std::vector<Item> items;
-    std::vector<int64_t> first_item(static_cast<size_t>(n_ev) + 1, 0);
-    int64_t tscratch = 0;
-    for (int e = 0; e < n_ev; ++e) {
-        first_item[e] = static_cast<int64_t>(items.size());
-        const int64_t len = ev_len[e];
-        const int64_t t0 = ev_first_tile[e], t1 = ev_first_tile[e + 1];
-        if (t0 == t1) continue;
-        int64_t cur = t0;
-        size_t idx = 0;
-        int32_t prev = 0;
-        for (;;) {
-            TileList &Lc = lists[cur];
-            if (idx >= Lc.a.size()) {
-                if (Lc.ended) break;
-                // the chain stopped (passed its stop position) without meeting a later tile:
-                // continue it from its last (true) anchor -- "seam repair"
-                const int32_t z = Lc.a.empty() ? Lc.start : Lc.a.back().pos;
-                const int64_t stop = std::min<int64_t>(len, static_cast<int64_t>(z) + L + H);
-                const std::vector<SpineJob> rj(1, make_spine_job(ev_start[e], e, len, z, stop, mw, 0));
-                std::vector<TileList> ext;
-                rc = run_spines(ctx, cfg, rj, rj[0].out_cap, ext);
-                if (rc) return rc;
-                ctx->counters[4] += 1;
-                Lc.a.insert(Lc.a.end(), ext[0].a.begin(), ext[0].a.end());
-                Lc.ended = ext[0].ended;
-                if (ext[0].a.empty() && !ext[0].ended)
-                    return fail(ctx, PS_ERR_INTERNAL, "seam repair made no progress");
-                continue;
-            }
-            const Anchor an = Lc.a[idx];
-            // emit this true anchor
-            Item it;
-            it.anchor = an.pos;
-            it.job = -1;
-            if (an.kind == KIND_HIT || an.kind == KIND_LATE) {
-                TreeJob tj;
-                tj.base = ev_start[e];
-                tj.start = prev;
-                tj.end = an.pos;
-                const int64_t d = static_cast<int64_t>(an.pos) - W - prev;
-                tj.j0 = d < 0 ? 0 : static_cast<int32_t>(d / (W / 2)) + 1;
-                tj.out_cap = (an.pos - prev) / mw + 1;
-                tj.out_off = tscratch;
-                tj.m = 0; tj.pad_ = 0; tj.boff = 0;
-                tscratch += tj.out_cap;
-                it.job = static_cast<int32_t>(tjobs.size());
-                tjobs.push_back(tj);
-            }
-            items.push_back(it);
-            prev = an.pos;
-            ++idx;
-            // does a later tile's speculative spine contain this anchor?  (latest tile wins)
-            if (cur + 1 < t1 && an.pos >= lists[cur + 1].start) {
-                int64_t u = t0 + std::min<int64_t>(an.pos / L, t1 - t0 - 1);
-                for (; u > cur; --u) {
-                    const int f = find_in(lists[u], an.pos);
-                    if (f != -2) { cur = u; idx = static_cast<size_t>(f + 1); break; }
-                }
-            }
-        }
-    }
-    first_item[n_ev] = static_cast<int64_t>(items.size());
-    const int64_t n_items = static_cast<int64_t>(items.size());
-    const size_t n_tj = tjobs.size();
-    ctx->counters[3] = static_cast<int64_t>(n_tj);
-    const auto t_stitch1 = std::chrono::steady_clock::now();
-    ctx->ms[4] = std::chrono::duration<double, std::milli>(t_stitch1 - t_stitch0).count();
-
-    // ---- upload jobs/items, phase 3, gather ------------------------------------------------------
-    const size_t up_bytes = n_tj * sizeof(TreeJob) + static_cast<size_t>(n_items) * sizeof(Item) +
-                            (static_cast<size_t>(n_ev) + 1) * sizeof(int64_t) * 3;
-    HIP_TRY(ctx, ctx->h_up.reserve(up_bytes + 64));
-    HIP_TRY(ctx, ctx->tree_jobs.reserve(std::max<size_t>(1, n_tj) * sizeof(TreeJob)));
-    // (item_scan_kernel reads counts[item index] speculatively: cover the items as well)
-    HIP_TRY(ctx, ctx->tree_counts.reserve(std::max<size_t>(std::max<size_t>(1, n_tj), static_cast<size_t>(n_items)) * sizeof(int32_t)));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->tree_counts.p, 0, std::max<size_t>(std::max<size_t>(1, n_tj), static_cast<size_t>(n_items)) * sizeof(int32_t), ctx->stream));   // (tree_job stores only non-zero counts)
-    HIP_TRY(ctx, ctx->tree_scratch.reserve(std::max<size_t>(1, static_cast<size_t>(tscratch)) * sizeof(int32_t)));
-    HIP_TRY(ctx, ctx->tree_spill.reserve(std::max<size_t>(1, static_cast<size_t>(tscratch)) * sizeof(int2)));
-    HIP_TRY(ctx, ctx->items.reserve(std::max<size_t>(1, static_cast<size_t>(n_items)) * sizeof(Item)));
-    HIP_TRY(ctx, ctx->item_pos.reserve((static_cast<size_t>(n_items) + 1) * sizeof(int64_t)));
-    HIP_TRY(ctx, ctx->first_item.reserve((static_cast<size_t>(n_ev) + 1) * sizeof(int64_t)));
-    HIP_TRY(ctx, ctx->ev_off.reserve((static_cast<size_t>(n_ev) + 1) * sizeof(int64_t)));
-    HIP_TRY(ctx, ctx->ev_len.reserve((static_cast<size_t>(n_ev) + 1) * sizeof(int64_t)));
-    HIP_TRY(ctx, ctx->bounds_off.reserve((static_cast<size_t>(n_ev) + 1) * sizeof(int64_t)));
-    char *up = ctx->h_up.as<char>();
-    size_t o = 0;
-    if (n_tj) {
-        std::memcpy(up + o, tjobs.data(), n_tj * sizeof(TreeJob));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->tree_jobs.p, up + o, n_tj * sizeof(TreeJob), hipMemcpyHostToDevice, ctx->stream));
-        o += n_tj * sizeof(TreeJob);
-    }
-    if (n_items) {
-        std::memcpy(up + o, items.data(), static_cast<size_t>(n_items) * sizeof(Item));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->items.p, up + o, static_cast<size_t>(n_items) * sizeof(Item), hipMemcpyHostToDevice, ctx->stream));
-        o += static_cast<size_t>(n_items) * sizeof(Item);
-    }
-    o = (o + 7) & ~static_cast<size_t>(7);
-    const size_t evb = (static_cast<size_t>(n_ev) + 1) * sizeof(int64_t);
-    std::memcpy(up + o, first_item.data(), evb);
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->first_item.p, up + o, evb, hipMemcpyHostToDevice, ctx->stream));
-    o += evb;
-    std::memcpy(up + o, ev_start, evb - sizeof(int64_t));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->ev_off.p, up + o, evb, hipMemcpyHostToDevice, ctx->stream));
-    o += evb;
-    std::memcpy(up + o, ev_len, evb - sizeof(int64_t));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->ev_len.p, up + o, evb, hipMemcpyHostToDevice, ctx->stream));
-
-    return finish_batch(ctx, cfg, n_tj, n_items, n_ev, d_bounds, cap, h_bounds_off, d_stats, t_begin);
+    return host_stitch_batch(ctx, cfg, B);
 }
 
 static int segment_events_impl(ps_ctx *ctx, const void *d_samples, const ps_sample_format *fmt,
@@ -2584,8 +2535,8 @@ int ps_detect_segment_trace(ps_ctx *ctx, const void *d_samples, const ps_sample_
         return ps_segment_events(ctx, d_samples, fmt, h_starts, h_lengths, static_cast<int32_t>(*n_events_out), params, d_bounds, cap,
                                  h_bounds_off, d_stats, nullptr);
     };
-    const bool use_bs = ctx->scan_bs && mw >= 8 && W <= 63 * 1024 && ctx->mode != MODE_EXACT && !ctx->stitch_host && ctx->single_pass &&
-                        !(ctx->wide_skip > 0 && fmt->quantum == ctx->wide_quantum);
+    const bool use_bs = scan_route_bs(ctx->scan_bs != 0, mw, W, ctx->mode == MODE_EXACT, false) && !ctx->stitch_host && ctx->single_pass &&
+                        !ctx->wide.remembers(fmt->quantum);
     if (!use_bs) return two_calls();
     rc = nt_arm(ctx, cfg);
     if (rc) return rc;
@@ -2647,7 +2598,8 @@ int ps_detect_segment_trace(ps_ctx *ctx, const void *d_samples, const ps_sample_
     // ---- every event from the trace's digest ----------------------------------------------------------------------------------
     cfg.bsum = ctx->bsum.p;
     cfg.blk_cls = nullptr;
-    rc = device_stitch_batch(ctx, cfg, 1, h_starts, h_lengths, n_ev, mw, W, d_bounds, cap, h_bounds_off, d_stats, t_begin, true);
+    const SegBatch B = {h_starts, h_lengths, n_ev, mw, W, d_bounds, cap, h_bounds_off, d_stats, t_begin};
+    rc = device_stitch_batch(ctx, cfg, 1, B, true);
     if (rc == RC_FALLBACK || rc == RC_WIDE) {          // (a seam the device could not mend: the two calls, with the host stitch behind them)
         return ps_segment_events(ctx, d_samples, fmt, h_starts, h_lengths, n_ev, params, d_bounds, cap, h_bounds_off, d_stats, nullptr);
     }

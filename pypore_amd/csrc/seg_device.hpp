@@ -25,20 +25,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "poreseg.h"
+#include "seg_types.hpp"   // SpineJob, TreeJob, Item, AsmHeader, KIND_*, BR_* status, BR_MAX, EXT_*: shared with the host plan (seg_plan.hpp)
 
 namespace ps {
 
 constexpr int LDS_STACK = 128;   // DFS stack entries kept in LDS before spilling to HBM
 constexpr int MAX_WAVES = 16;
 constexpr int OBUF = 256;          // (>= BR_MAX: a bridge buffers its whole chain in LDS)
-constexpr int BR_MAX = 256;       // bridge chain: anchors a seam may add before it must have joined (densely stepped
-                                  // data: two chains pick the best of ~10 steps per window and can take dozens of
-                                  // anchors to meet; a seam that gives up sends the whole call to the host stitch)
 constexpr int LST_MAX = 256;
-// Round 5: seams that the bridges gave up on (BR_MAX anchors without meeting a downstream list: densely stepped data, where two
-// chains can stay out of step for a long stretch) and open tiles that the true chain enters exactly at their start get a second
-// chance on the device before the call falls back to the host stitch: the look-ahead kernel continues them with room for
-// EXT_MAX more anchors each, in a side buffer (anchor i >= BR_MAX of seam g lives at ext[ext_slot[g] * EXT_MAX + i - BR_MAX]).
+// (Round 5, the second chance of seams that the bridges gave up on: EXT_MAX and its kin, seg_types.hpp)
 // Round 5, long stretches without splits.  The windows of a chain between two anchors lie on a lattice a + J * W/2, and whether
 // window J holds a split does not depend on who asks.  In the look-ahead kernel an OWNER (the workgroup that walks a seam) that
 // has scanned LAT_W windows of one find_split without a hit LISTS the stretch: lattice origin, a fresh tag, the chunk (LAT_W
@@ -68,15 +63,10 @@ __device__ __forceinline__ unsigned long long lat_ld(const unsigned long long *p
 __device__ __forceinline__ int lat_ld(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void lat_st(unsigned long long *p, unsigned long long v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void lat_st(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-constexpr int EXT_MAX = 16384;     // further anchors of an extended seam when few seams need them (<= EXT_SLOTS) ...
-constexpr int EXT_SLOTS = 64;
-constexpr int EXT_MAX_MANY = 2048; // ... and when many do (a batch of events with a failed seam each): the side buffer holds
-constexpr int EXT_ROUNDS = 4;      // EXT_SLOTS * EXT_MAX anchors either way; the stride is fixed by the first round of a call
 constexpr int GS_LOG = 8;          // gather_scan_kernel: items per workgroup (256); tree jobs add their counts to blk[job >> GS_LOG]
 constexpr int QMAX = 256;          // blocks of candidates queued for full evaluation per window
 constexpr int PBLK = 8;            // candidates per pruning block      // anchors of the downstream tile cached in LDS for membership tests        // buffered outputs per job (int2 anchors / 2x int boundaries)
 
-enum : int { KIND_NONE = 0, KIND_HIT = 1, KIND_EARLY = 2, KIND_LATE = 3, KIND_STOP = 4 };   // STOP: gave up at stop_lim (spine tiles)
 enum : unsigned { ST_OFF_GRID = 1u, ST_OUT_OVERFLOW = 2u, ST_STACK_OVERFLOW = 4u, ST_VERIFY_MISMATCH = 8u };
 enum : int { MODE_FAST = 0, MODE_EXACT = 1, MODE_VERIFY = 2 };
 
@@ -130,28 +120,6 @@ struct DevCfg {
 // ph = 0 on every other route.  A window [ps, pe) of such an event is the window [ps + ph, pe + ph) of the 8-aligned stretch that
 // starts ph samples earlier: scan_window_ph runs the scan unchanged in those shifted coordinates.
 struct EvRef { int m; long long boff; int ph; };
-
-struct SpineJob {           // speculative spine of one tile: rec(start, end) without left subtrees
-    int64_t base;           // offset of the event in the sample array
-    int32_t start, end;     // chain anchor, event length
-    int32_t stop;           // stop after the first spine anchor >= stop
-    int32_t out_cap;
-    int64_t out_off;        // into the anchor list storage (int2 entries)
-    int32_t first_tile;     // global index of the event's first tile
-    int32_t ntiles;         // tiles of this event
-    int32_t tile_len;       // tile t of the event starts at t * tile_len
-    int32_t ev;             // event index
-    int64_t vbase;          // sum of the lengths of the preceding events (layout of the tree output regions)
-};
-
-struct TreeJob {            // full in-order traversal of rec(start, end), first window index j0
-    int64_t base;
-    int32_t start, end, j0;
-    int32_t out_cap;
-    int64_t out_off;        // into the private boundary scratch (int32) and the spill stack (int2)
-    int32_t m, pad_;        // the event's centre (first count), pad_ = its phase (EvRef::ph), and first block (K0 digest; 0 on the LDS-window path)
-    int64_t boff;
-};
 
 typedef short lds_t;               // window samples in LDS: ADC counts as int16 (windows that do not fit go the exact HBM path)
 
@@ -1049,10 +1017,7 @@ __device__ int scan_screen_pruned(const DevCfg &c, const lds_t *ys, int2 *bsum, 
 }  // namespace ps
 
 #include "seg_filter.hpp"
-// Header written by assemble_tiles_kernel.  Kernels downstream of the device stitch take it as `hdr`: when
-// it is non-null the item / job count is read from it on the device (no host round trip in the middle of
-// the pipeline) and a failed stitch turns them into no-ops; when null the host-provided count is used.
-struct AsmHeader { long long n_items, n_jobs, tscratch; int fail, pad; };
+// (AsmHeader, the header written by assemble_tiles_kernel: seg_types.hpp)
 __device__ __forceinline__ long long dev_count(const AsmHeader *hdr, long long host_n)
 {
     return hdr ? (hdr->fail ? 0 : hdr->n_items) : host_n;
@@ -1404,9 +1369,7 @@ __global__ __launch_bounds__(NT, (NT == 64 ? PS_BS_MINW : 4)) PS_SCAN_REGS void 
 // start): from there on the two chains are identical.  bmeta[g] = (count, join_tile, join_idx,
 // status); status 0 nothing to do, 1 joined (continue with list[join_tile][join_idx+1..]),
 // 2 the chain reached the end of the event, 3 gave up (host fallback).
-enum : int { BR_NONE = 0, BR_JOINED = 1, BR_ENDED = 2, BR_FAIL = 3, BR_DEFER = 4,
-              BR_FAIL_REACHED = 5,                       // (set by the stitch: a failed seam that lies on the true path)
-              BR_DEFER_REACHED = 6 };                    // (... a deferred seam nobody finished that does: short_chain, no look-ahead launch)
+// (the status codes BR_NONE .. BR_DEFER_REACHED: seg_types.hpp)
 __device__ __forceinline__ int2 bridge_at(const int2 *bridges, const int2 *ext, const int *ext_slot, int ext_stride, int g, int i)
 {
     return i < BR_MAX ? bridges[static_cast<long long>(g) * BR_MAX + i]
@@ -2186,8 +2149,7 @@ __global__ __launch_bounds__(NT) void single_scan_kernel(DevCfg c, int n, int mo
     flush(bad, wk, status, work);
 }
 
-// ---- gather: final boundary list = for every true spine anchor: [its left subtree..., anchor] ----
-struct Item { int32_t job; int32_t anchor; };
+// ---- gather: final boundary list = for every true spine anchor: [its left subtree..., anchor] (Item: seg_types.hpp) ----
 
 // single-workgroup exclusive scan of (tree count + 1) per item -> pos[n_items + 1]; then the per-event
 // offsets bounds_off[e] = pos[first_item[e]].
