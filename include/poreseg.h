@@ -418,11 +418,25 @@ int ps_grid_counts_f64(ps_ctx *ctx, const double *d_in, int64_t n, double origin
  * of samples with double(float(x)) != x -- a NaN counts.  0: the float32 copy is the current, exactly. */
 int ps_narrow_f64(ps_ctx *ctx, const double *d_in, int64_t n, float *d_out, int64_t *n_inexact_out);
 
+/* Event.filter for MANY events of one device buffer in one call: event e is samples[ev_start[e] .. + ev_len[e]) of d_samples
+ * (fmt as for ps_filter_bessel, PS_DTYPE_F64 included); events may overlap, touch and come in any order.  Its filtered current
+ * goes to d_out + sum of the lengths before it (device, float64, room for the sum of all lengths), bit for bit what
+ * ps_filter_bessel writes for that event alone.  Order 1 on the fused route (poles up to ~0.96) is ONE launch, one workgroup per
+ * (event, tile); orders 2..8 take one launch per group of events whose scratch rows fit the context option
+ * "filt_batch_scratch" (bytes, default 256 MiB; an event that alone exceeds it is a group of its own); slower order-1 filters
+ * (the three-pass scan) have no batched kernel and are queued per event.  One status word and one host synchronisation for the
+ * batch.  n_ev == 0 returns PS_OK.  Argument errors are ps_filter_bessel's; an event with a negative start or no samples, the
+ * first event of at most padlen samples (both named in ps_last_error) and a batch of more than 2^24 - 1 tiles are refused too --
+ * all before anything is queued. */
+int ps_filter_bessel_batch(ps_ctx *ctx, const void *d_samples, const ps_sample_format *fmt, const int64_t *ev_start,
+                           const int64_t *ev_len, int32_t n_ev, int32_t order, double cutoff, double sampling_freq, double *d_out);
+
 /* Event.filter + the representation step for MANY events of one trace in one call (the inner loop of Experiment.parse,
  * DataTypes.py:975-984; File.parse_events here): event e is samples[ev_start[e] .. + ev_len[e]) of d_samples; its filtered
  * current (ps_filter_bessel) goes to d_filtered + sum of the lengths before it, its re-quantised copy (ps_requantise) to the
  * same position of d_rounded, its centre and grid step to h_centre[e] / h_step[e].  Same results as the two entries called
- * per event; one status check and two host synchronisations for the whole batch instead of three per event. */
+ * per event; one status check and two host synchronisations for the whole batch instead of three per event, and -- on the
+ * filter routes ps_filter_bessel_batch has a kernel for -- three launches for the batch: filter, statistics, rounding. */
 int ps_filter_requantise_batch(ps_ctx *ctx, const void *d_samples, const ps_sample_format *fmt, const int64_t *ev_start,
                                const int64_t *ev_len, int32_t n_ev, int32_t order, double cutoff, double sampling_freq,
                                double *d_filtered, float *d_rounded, double *h_centre, double *h_step);

@@ -233,7 +233,10 @@ class Event(Segment):
     def _adopt_filtered(self, segments):
         """Segments found on the rounded current keep views of the unrounded one and take their statistics from those."""
         for segment in segments:
-            segment.current = self.current[int(segment.start):int(segment.end)]
+            # (a state parser's segments carry the reference's keywords, `current` and `start`, and no `end`: snakebase_parser)
+            start = int(segment.start)
+            end = int(segment.end) if 'end' in segment.__dict__ else start + len(raw_current(segment))
+            segment.current = self.current[start:end]
             segment.__dict__.pop('_gpu_stats', None)
         return segments
 
@@ -284,6 +287,82 @@ class Event(Segment):
         mean = sum(seg.mean * seg.duration for seg in segments) / dur
         std = float(np.sqrt(sum(seg.std ** 2 * seg.duration for seg in segments) / dur))
         return MetaEvent(start=0, duration=dur, mean=mean, std=std, n=len(segments), segments=segments, filtered=False)
+
+
+def filter_events(events, order=1, cutoff=2000.):
+    """`event.filter(order, cutoff)` for every Event of `events`, in as few device calls as their currents allow
+    (engine.Context.filter_bessel_batch: one launch for a batch on the order-1 route): every event ends as Event.filter would
+    leave it -- the same float64 `current`, bit for bit, `filtered`, `filter_order`, `filter_cutoff`.  The events are routed
+    as Event.filter routes one:
+      * a current on an ADC grid goes up as counts.  Events cut from one file are stretches of the file's one device tensor
+        and take one call per file tensor, nothing is copied; counts of any other origin (a GridArray, float samples whose
+        grid is found) are packed into one tensor per grid and sampling rate; the offset is put back afterwards;
+      * everything else -- an event that was filtered before, float64 data on no grid -- is packed into one float64 tensor
+        per sampling rate.
+    One download per group.  A MetaEvent raises Event.filter's TypeError, before anything is filtered."""
+    import torch
+    from . import engine
+    from .grid import grid_of
+    events = list(events)
+    for ev in events:
+        if type(ev) is not Event:
+            raise TypeError("Cannot filter a metaevent. Must have the current.")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    # group key -> [(event, tensor or (first sample, length) of the group's base tensor, offset to put back)]
+    stretched, packed = {}, {}
+    for ev in events:
+        cur = raw_current(ev)
+        rate = float(ev.second)
+        s = None
+        if not ev.__dict__.get("filtered"):
+            stretch = getattr(cur, "device_stretch", None)
+            g = grid_of(cur) if stretch is not None else None
+            where = stretch(dev, engine._int_counts_tensor) if g is not None else None
+            if where is not None:
+                base, a0, n0 = where
+                stretched.setdefault((base.data_ptr(), float(g[1]), rate), [base]).append((ev, a0, n0, float(g[2])))
+                continue
+            try:
+                s = engine.to_device(cur, None)
+            except ValueError:
+                s = None
+        if s is not None:
+            packed.setdefault((s.tensor.dtype, float(s.quantum), rate, s.tensor.device.index), []).append((ev, s.tensor, float(s.offset or 0.0)))
+            continue
+        t = getattr(cur, "tensor", None)
+        off = 0.0
+        if t is None or not t.is_cuda:
+            a = np.ascontiguousarray(np.asarray(ev.current), dtype=np.float64)
+            if a.ndim != 1:
+                raise ValueError("Buffer has wrong number of dimensions (expected 1, got %d)" % a.ndim)
+            t = torch.from_numpy(a)
+        else:
+            # (a parked tensor holds the current WITHOUT the file's offset: Event.filter)
+            off = float(getattr(cur, "offset", 0.0) or 0.0)
+        packed.setdefault((torch.float64, 1.0, rate, t.device.index if t.is_cuda else dev.index), []).append((ev, t, off))
+
+    def finish(members, y, offsets):
+        y = y.cpu().numpy()                              # (one download per group)
+        for k, (ev, off) in enumerate(members):
+            out = y[int(offsets[k]):int(offsets[k + 1])]
+            # (a DC offset passes a unit-gain low-pass unchanged: filter the counts, put the offset back)
+            ev.current = out + off if off else out
+            ev.filtered, ev.filter_order, ev.filter_cutoff = True, order, cutoff
+
+    for (_, quantum, rate), group in stretched.items():
+        base, members = group[0], group[1:]
+        y, offsets = engine.context(base.device.index).filter_bessel_batch(
+            base, [a0 for _, a0, _, _ in members], [n0 for _, _, n0, _ in members], quantum, cutoff=cutoff, sampling_freq=rate, order=order)
+        finish([(ev, o) for ev, _, _, o in members], y, offsets)
+    for (dtype, quantum, rate, index), members in packed.items():
+        where = torch.device("cuda", index)
+        # (a host array goes up on its own: one pinned staging copy of the whole group would cost a second pass over it)
+        ts = [t.to(where).contiguous() for _, t, _ in members]
+        lens = np.array([t.numel() for t in ts], dtype=np.int64)
+        allt = ts[0] if len(ts) == 1 else torch.cat(ts)
+        y, offsets = engine.context(index).filter_bessel_batch(allt, np.concatenate(([0], np.cumsum(lens)))[:-1], lens, quantum, cutoff=cutoff,
+                                                               sampling_freq=rate, order=order)
+        finish([(ev, o) for ev, _, o in members], y, offsets)
 
 
 def _segment_filtered(events, parser):
@@ -364,6 +443,11 @@ class File(Segment):
                        for seg in parser.parse(raw_current(self) if device_route else self.current)]
         self.event_parser = parser
 
+    def filter_events(self, order=1, cutoff=2000.):
+        """`event.filter(order, cutoff)` for every event of the file, batched on the device (DataTypes.filter_events): the
+        filtered currents of a file's events without segmenting them, in one call per file tensor."""
+        filter_events(self.events, order=order, cutoff=cutoff)
+
     def parse_events(self, parser=None, filter_params=None):
         """The inner loop of Experiment.parse (DataTypes.py:975-984) for this file: every event is filtered when
         `filter_params` = (order, cutoff) is given, then all events are segmented in as few device calls as their
@@ -400,8 +484,11 @@ class File(Segment):
                 ev.state_parser = parser
             return
         if filter_params is not None:
-            for ev in self.events:
-                ev.filter(*filter_params)
+            if all(type(ev) is Event for ev in self.events) and len(tuple(filter_params)) <= 2:
+                filter_events(self.events, *filter_params)
+            else:                                        # (a MetaEvent raises where the loop reaches it; a third entry names a grid)
+                for ev in self.events:
+                    ev.filter(*filter_params)
         batched = hasattr(parser, "parse_batch")
         results = [None] * len(self.events)
         plain_idx = [i for i, ev in enumerate(self.events) if not ev.__dict__.get("filtered")]

@@ -49,6 +49,7 @@
 #include "seg_state.hpp"
 #include "pool_plan.hpp"
 #include "seg_plan.hpp"
+#include "filt_plan.hpp"
 
 using namespace ps;
 
@@ -202,9 +203,11 @@ struct ps_ctx {
     // The segmentation chain's own buffers and options are flat members.  The state of every self-contained feature stands
     // together in a sub-struct (filt, align, pw, trf, ss, sp, nt, hmm): its buffers, its budgets, its host-side caches.  A new feature
     // adds its group here and nowhere else: the buffers free themselves with the context.
-    struct {                // Bessel filter (ps_filter_bessel, ps_filter_requantise_batch)
+    struct {                // Bessel filter (ps_filter_bessel, ps_filter_bessel_batch, ps_filter_requantise_batch)
         DevBuf fwd, agg, zin;
+        DevBuf tab, rq_par;   // a batch's event and unit tables (filt_plan.hpp; the re-quantisation's behind them), (centre, 1 / step, step) per event
         int fused = 1;        // option filter_fused 1: fast filters run both directions in one kernel over tiles with halos, 0: always the exact three-pass scan
+        long long batch_scratch = FILT_BATCH_SCRATCH_DEFAULT;   // option filt_batch_scratch: bytes of order-n scratch rows per launch of a batch
     } filt;
     struct { DevBuf in, scratch; } align;    // profile aligner (ps_align_batch)
     struct {                  // pairwise aligner (ps_pairwise_scores / ps_pairwise_batch): offsets and pair tables, per-workgroup matrices
@@ -1866,6 +1869,7 @@ int ps_set_option(ps_ctx *ctx, const char *name, int64_t value)
     else if (n == "bridge_single" && value >= 1) ctx->bridge_single = static_cast<int>(value);
     else if (n == "tree_tail_pct" && value >= 0 && value <= 100) ctx->tree_tail_pct = static_cast<int>(value);
     else if (n == "filter_fused") ctx->filt.fused = value != 0;
+    else if (n == "filt_batch_scratch" && value >= 1) ctx->filt.batch_scratch = value;
     else if (n == "upload_by_kernel") ctx->upload_by_kernel = value != 0;
     else if (n == "timing") ctx->timing = static_cast<int>(std::max<int64_t>(0, std::min<int64_t>(2, value)));
     else if (n == "tree_mw") ctx->tree_mw = value != 0;
@@ -1884,6 +1888,7 @@ int ps_get_option(const ps_ctx *ctx, const char *name, int64_t *value)
     else if (n == "lat_help") *value = ctx->lat_help;
     else if (n == "shared_device") *value = ctx->shared_n;
     else if (n == "hw_queues") *value = ctx->hw_queues;
+    else if (n == "filt_batch_scratch") *value = ctx->filt.batch_scratch;
     else return PS_ERR_ARG;
     return PS_OK;
 }
@@ -2684,12 +2689,64 @@ int ps_synth_trace(ps_ctx *ctx, void *d_out, int32_t dtype, int64_t n, uint64_t 
     return PS_OK;
 }
 
+}  // extern "C"
+
 namespace {
+
+// Host arrays staged back to back through h_up and copied to the start of `dev` in one transfer (the layout is the caller's:
+// 8-byte tables before 4-byte ones).  The first `head` bytes are not copied from anywhere: fill(h_up) writes them in place.
+struct HostTable { const void *p; size_t bytes; };
+template <typename Fill>
+int upload_tables(ps_ctx *ctx, DevBuf &dev, size_t head, Fill &&fill, std::initializer_list<HostTable> tables)
+{
+    size_t bytes = head;
+    for (const HostTable &t : tables) bytes += t.bytes;
+    HIP_TRY(ctx, ctx->h_up.reserve(bytes));
+    HIP_TRY(ctx, dev.reserve(bytes));
+    fill(ctx->h_up.p);
+    char *h = static_cast<char *>(ctx->h_up.p) + head;
+    for (const HostTable &t : tables) {
+        if (t.bytes) std::memcpy(h, t.p, t.bytes);
+        h += t.bytes;
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(dev.p, ctx->h_up.p, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return PS_OK;
+}
+int upload_tables(ps_ctx *ctx, DevBuf &dev, std::initializer_list<HostTable> tables)
+{
+    return upload_tables(ctx, dev, 0, [](void *) {}, tables);
+}
+
+// The sample format of a filter call as the kernels' DevCfg: float32 on a grid / int16 counts as everywhere, or -- the filter
+// entries only -- PS_DTYPE_F64, the current itself.
+int filter_cfg(ps_ctx *ctx, const void *d_samples, const ps_sample_format *fmt, DevCfg *cfg)
+{
+    if (fmt && fmt->dtype == PS_DTYPE_F64) {
+        const ps_sample_format f32 = {PS_DTYPE_F32, 0, 1.0};
+        if (int rc = make_cfg(ctx, d_samples, &f32, 1, 1, 2, 0.0, cfg)) return rc;
+        cfg->dtype = PS_DTYPE_F64; cfg->q = 1.0; cfg->q2 = 1.0; cfg->inv_q = 1.0f;
+        return PS_OK;
+    }
+    return make_cfg(ctx, d_samples, fmt, 1, 1, 2, 0.0, cfg);
+}
+
+// scipy.signal.bessel(1, wn, 'low', analog=False): one real pole, bilinear transform with pre-warping (fs = 2)
+FiltCoef filter_coef1(double wn)
+{
+    FiltCoef f;
+    const double wo = 4.0 * std::tan(3.14159265358979323846 * wn / 2.0);
+    f.b0 = wo / (4.0 + wo); f.b1 = f.b0; f.a1 = (wo - 4.0) / (wo + 4.0);
+    f.alpha = -f.a1; f.beta = f.b1 - f.a1 * f.b0;
+    f.zi = (f.b1 - f.a1 * f.b0) / (1.0 + f.a1);        // lfilter_zi: steady state of the delay for a unit step input
+    return f;
+}
+
 // scipy.signal.bessel(N, wn, 'low', analog=False, output='ba') for N = 2..8: poles of the phase-normalised analog
 // prototype (what scipy.signal.besselap(N, 'phase') returns; conjugates implied), lp2lp with the pre-warped frequency,
 // bilinear transform with fs = 2, polynomial expansion.  Then lfilter_zi (steady state of the delays for a unit step:
-// (I - A) zi = B), the halo from the powers of the state matrix, and one launch of filt_halo_kernel.
-int filter_order_n(ps_ctx *ctx, const DevCfg &cfg, int64_t n, int order, double wn, double *d_out)
+// (I - A) zi = B), the halo H from the powers of the state matrix and the segment length S.
+struct FiltDesignN { FiltN f; int H, S; };
+int filter_design_n(ps_ctx *ctx, int order, double wn, FiltDesignN *design)
 {
     typedef std::complex<double> cd;
     static const double poles[FILT_MAXORD + 1][4][2] = {       // [order][pair][re, im]; im == 0: a single real pole
@@ -2764,7 +2821,17 @@ int filter_order_n(ps_ctx *ctx, const DevCfg &cfg, int64_t n, int order, double 
         mul(P, A64, P);
     }
     if (!H) return fail(ctx, PS_ERR_ARG, "a Bessel filter of order %d this slow (cutoff / Nyquist = %g) does not run on the device", order, wn);
-    const int S = std::max(1024, 4 * H);
+    design->f = f; design->H = H; design->S = std::max(1024, 4 * H);
+    return PS_OK;
+}
+
+// One event, orders 2..8: the design above and one launch of filt_halo_kernel.
+int filter_order_n(ps_ctx *ctx, const DevCfg &cfg, int64_t n, int order, double wn, double *d_out)
+{
+    FiltDesignN design;
+    if (int rc = filter_design_n(ctx, order, wn, &design)) return rc;
+    const FiltN &f = design.f;
+    const int H = design.H, S = design.S;
     const int64_t m = n + 2LL * f.pad, nseg = (m + S - 1) / S;
     HIP_TRY(ctx, ctx->filt.fwd.reserve(static_cast<size_t>(nseg) * static_cast<size_t>(S + H) * sizeof(double)));
     HIP_TRY(ctx, ctx->h_small.reserve(sizeof(SmallLayout)));
@@ -2782,6 +2849,8 @@ int filter_order_n(ps_ctx *ctx, const DevCfg &cfg, int64_t n, int order, double 
 }
 }  // namespace
 
+extern "C" {
+
 int ps_filter_bessel(ps_ctx *ctx, const void *d_samples, const ps_sample_format *fmt, int64_t n, int32_t order,
                      double cutoff, double sampling_freq, double *d_out)
 {
@@ -2795,35 +2864,19 @@ int ps_filter_bessel(ps_ctx *ctx, const void *d_samples, const ps_sample_format 
     if (!(wn > 0.0) || !(wn < 1.0)) return fail(ctx, PS_ERR_ARG, "cutoff must lie strictly between 0 and the Nyquist frequency");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     DevCfg cfg;
-    int rc;
-    if (fmt && fmt->dtype == PS_DTYPE_F64) {
-        // float64 input (this entry only): the values are the current itself
-        const ps_sample_format f32 = {PS_DTYPE_F32, 0, 1.0};
-        rc = make_cfg(ctx, d_samples, &f32, 1, 1, 2, 0.0, &cfg);
-        if (rc) return rc;
-        cfg.dtype = PS_DTYPE_F64; cfg.q = 1.0; cfg.q2 = 1.0; cfg.inv_q = 1.0f;
-    } else {
-        rc = make_cfg(ctx, d_samples, fmt, 1, 1, 2, 0.0, &cfg);
-    }
-    if (rc) return rc;
+    if (int rc = filter_cfg(ctx, d_samples, fmt, &cfg)) return rc;
     if (order > 1) return filter_order_n(ctx, cfg, n, order, wn, d_out);
-    // scipy.signal.bessel(1, wn, 'low', analog=False): one real pole, bilinear transform with pre-warping (fs = 2)
-    FiltCoef f;
-    const double wo = 4.0 * std::tan(3.14159265358979323846 * wn / 2.0);
-    f.b0 = wo / (4.0 + wo); f.b1 = f.b0; f.a1 = (wo - 4.0) / (wo + 4.0);
-    f.alpha = -f.a1; f.beta = f.b1 - f.a1 * f.b0;
-    f.zi = (f.b1 - f.a1 * f.b0) / (1.0 + f.a1);        // lfilter_zi: steady state of the delay for a unit step input
+    const FiltCoef f = filter_coef1(wn);
     FiltGeom g;
     g.n = n; g.total = n + 2 * FILT_PAD;
     // Fast filters (the state forgets within a halo of <= 1024 samples): both directions in one kernel over tiles
-    // with halos.  alpha^H <= 2^-60.
-    if (ctx->filt.fused && f.alpha > 0.0 && f.alpha < 1.0) {
-        const double h_req = std::ceil(60.0 * std::log(2.0) / -std::log(f.alpha));
-        const int H = h_req <= 1024.0 ? std::max(64, (static_cast<int>(h_req) + 63) / 64 * 64) : 0;   // a multiple of 64, at most 1024
+    // with halos.  alpha^H <= 2^-60.  The route is filt_plan.hpp's: the batch entry takes the same one.
+    {
+        const int H = filt_route1(f.alpha, ctx->filt.fused);
         if (H) {
             g.lead = 0; g.padded = g.total;
-            const int T = FILT_CHUNK - 2 * H;
-            const dim3 fgrid(static_cast<unsigned>((g.total + T - 1) / T));
+            const int T = filt_tile(H);
+            const dim3 fgrid(static_cast<unsigned>(filt_units(n, FILT_PAD, T)));
             HIP_TRY(ctx, ctx->h_small.reserve(sizeof(SmallLayout)));
             if (!ctx->defer_sync) HIP_TRY(ctx, hipMemsetAsync(ctx->small.p, 0, sizeof(SmallLayout), ctx->stream));
             unsigned *fst = reinterpret_cast<unsigned *>(&ctx->small.as<SmallLayout>()->status);
@@ -2965,6 +3018,126 @@ int ps_narrow_f64(ps_ctx *ctx, const double *d_in, int64_t n, float *d_out, int6
     return PS_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// A batch of events of one device buffer, filtered: validated, planned (filt_plan.hpp) and queued on the context's stream, the
+// status block cleared in front of it.  Nothing is queued when the call is refused.  The caller copies the status block back
+// with its next synchronisation and checks it (one status word for the batch).  Event e's result goes to d_out + (sum of the
+// lengths before e).
+//   order 1, fused route: one launch of filt_fused_batch_kernel, one workgroup per (event, tile)
+//   orders 2..8:          one launch of filt_halo_batch_kernel per scratch group of the plan (option filt_batch_scratch)
+//   order 1, scan route:  no batched kernel -- the events are queued one after the other through ps_filter_bessel, longest first
+//                         (its scratch grows at most once, before anything that uses it is in flight)
+// rq (optional): the tables of the re-quantisation that follows go up in the same transfer; *d_rq_ev, *d_rq_unit: where they are.
+int filter_batch_queue(ps_ctx *ctx, const void *d_samples, const ps_sample_format *fmt, const int64_t *ev_start, const int64_t *ev_len,
+                       int32_t n_ev, int32_t order, double cutoff, double sampling_freq, double *d_out, const RequantPlan *rq = nullptr,
+                       const RequantEvent **d_rq_ev = nullptr, const FiltUnit **d_rq_unit = nullptr)
+{
+    if (!d_samples || !d_out || !ev_start || !ev_len) return fail(ctx, PS_ERR_ARG, "null pointer");
+    if (order < 1 || order > FILT_MAXORD)
+        return fail(ctx, PS_ERR_ARG, "Bessel orders 1..%d run on the device (the reference's default is 1)", FILT_MAXORD);
+    const double wn = cutoff / (sampling_freq / 2.0);
+    if (!(wn > 0.0) || !(wn < 1.0)) return fail(ctx, PS_ERR_ARG, "cutoff must lie strictly between 0 and the Nyquist frequency");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    DevCfg cfg;
+    if (int rc = filter_cfg(ctx, d_samples, fmt, &cfg)) return rc;
+    const int pad = filt_padlen(order);
+    FiltCoef f1 = {};
+    FiltDesignN dn = {};
+    int H = 0;
+    int64_t unit = FILT_CHUNK, row_bytes = 0;            // (the scan route is planned for its refusals only)
+    if (order == 1) {
+        f1 = filter_coef1(wn);
+        H = filt_route1(f1.alpha, ctx->filt.fused);
+        if (H) unit = filt_tile(H);
+    } else {
+        if (int rc = filter_design_n(ctx, order, wn, &dn)) return rc;
+        H = dn.H; unit = dn.S;
+        row_bytes = static_cast<int64_t>(dn.S + dn.H) * static_cast<int64_t>(sizeof(double));
+    }
+    const bool per_event = order == 1 && !H;
+    FiltPlan plan;
+    switch (plan_filter_batch(ev_start, ev_len, n_ev, pad, unit, row_bytes, ctx->filt.batch_scratch, &plan)) {
+    case FILT_PLAN_OK: break;
+    case FILT_PLAN_RANGE: return fail(ctx, PS_ERR_ARG, "event %d: empty or negative range", plan.bad_event);
+    case FILT_PLAN_SHORT:
+        return fail(ctx, PS_ERR_ARG, "event %d: the length of the input must be greater than padlen, which is %d", plan.bad_event, pad);
+    default: return fail(ctx, PS_ERR_ARG, "too many samples for one call");
+    }
+    // (a launch holds fewer than 2^32 threads)
+    if (plan.unit.size() > 0xffffffu || (rq && rq->unit.size() > 0xffffffu)) return fail(ctx, PS_ERR_ARG, "too many samples for one call");
+    size_t rows_max = 0;
+    for (const FiltGroup &g : plan.group) rows_max = std::max(rows_max, static_cast<size_t>(g.units));
+    if (row_bytes) HIP_TRY(ctx, ctx->filt.fwd.reserve(rows_max * static_cast<size_t>(row_bytes)));
+    HIP_TRY(ctx, ctx->h_small.reserve(sizeof(SmallLayout)));
+    ctx->small_clean = false;
+    const size_t ne = static_cast<size_t>(n_ev);
+    const size_t b_ev = per_event ? 0 : ne * sizeof(FiltEvent), b_unit = per_event ? 0 : plan.unit.size() * sizeof(FiltUnit);
+    const size_t b_rq_ev = rq ? ne * sizeof(RequantEvent) : 0, b_rq_unit = rq ? rq->unit.size() * sizeof(FiltUnit) : 0;
+    if (b_ev + b_rq_ev)
+        if (int rc = upload_tables(ctx, ctx->filt.tab, {{plan.ev.data(), b_ev}, {rq ? rq->ev.data() : nullptr, b_rq_ev}, {plan.unit.data(), b_unit},
+                                                        {rq ? rq->unit.data() : nullptr, b_rq_unit}})) return rc;
+    const char *tab = ctx->filt.tab.as<char>();
+    const FiltEvent *d_ev = reinterpret_cast<const FiltEvent *>(tab);
+    const FiltUnit *d_unit = reinterpret_cast<const FiltUnit *>(tab + b_ev + b_rq_ev);
+    if (d_rq_ev) *d_rq_ev = reinterpret_cast<const RequantEvent *>(tab + b_ev);
+    if (d_rq_unit) *d_rq_unit = reinterpret_cast<const FiltUnit *>(tab + b_ev + b_rq_ev + b_unit);
+    HIP_TRY(ctx, hipMemsetAsync(ctx->small.p, 0, sizeof(SmallLayout), ctx->stream));
+    unsigned *st = reinterpret_cast<unsigned *>(&ctx->small.as<SmallLayout>()->status);
+    if (per_event) {
+        std::vector<int> by_len(ne);
+        for (int e = 0; e < n_ev; ++e) by_len[e] = e;
+        std::sort(by_len.begin(), by_len.end(), [&](int a, int b) { return ev_len[a] > ev_len[b]; });
+        const size_t es = cfg.dtype == PS_DTYPE_I16 ? 2 : cfg.dtype == PS_DTYPE_F64 ? 8 : 4;
+        ctx->defer_sync = true;
+        int rc = PS_OK;
+        for (size_t k = 0; k < ne && rc == PS_OK; ++k) {
+            const int e = by_len[k];
+            rc = ps_filter_bessel(ctx, static_cast<const char *>(d_samples) + static_cast<size_t>(ev_start[e]) * es, fmt, ev_len[e], order, cutoff,
+                                  sampling_freq, d_out + plan.ev[e].out_off);
+        }
+        ctx->defer_sync = false;
+        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        return PS_OK;
+    }
+    if (order == 1) {
+        const dim3 grid(static_cast<unsigned>(plan.unit.size()));
+#define PS_FILT(DT) hipLaunchKernelGGL((filt_fused_batch_kernel<DT>), grid, dim3(FILT_NT), 0, ctx->stream, cfg, f1, H, d_ev, d_unit, d_out, st);
+        if (cfg.dtype == PS_DTYPE_F32) { PS_FILT(PS_DTYPE_F32) } else if (cfg.dtype == PS_DTYPE_F64) { PS_FILT(PS_DTYPE_F64) } else { PS_FILT(PS_DTYPE_I16) }
+#undef PS_FILT
+    } else {
+        double *scratch = ctx->filt.fwd.as<double>();
+        for (const FiltGroup &g : plan.group) {            // (one scratch for all groups: they run in stream order)
+            const dim3 grid(static_cast<unsigned>((g.units + 63) / 64));
+#define PS_FILT(DT) hipLaunchKernelGGL((filt_halo_batch_kernel<DT>), grid, dim3(64), 0, ctx->stream, cfg, dn.f, dn.S, dn.H, d_ev, d_unit, g.unit0, \
+                                       g.units, scratch, d_out, st);
+            if (cfg.dtype == PS_DTYPE_F32) { PS_FILT(PS_DTYPE_F32) } else if (cfg.dtype == PS_DTYPE_F64) { PS_FILT(PS_DTYPE_F64) } else { PS_FILT(PS_DTYPE_I16) }
+#undef PS_FILT
+        }
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return PS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ps_filter_bessel_batch(ps_ctx *ctx, const void *d_samples, const ps_sample_format *fmt, const int64_t *ev_start, const int64_t *ev_len,
+                           int32_t n_ev, int32_t order, double cutoff, double sampling_freq, double *d_out)
+{
+    if (!ctx) return PS_ERR_ARG;
+    if (n_ev < 0) return fail(ctx, PS_ERR_ARG, "null pointer or negative count");
+    if (n_ev == 0) return PS_OK;
+    if (int rc = filter_batch_queue(ctx, d_samples, fmt, ev_start, ev_len, n_ev, order, cutoff, sampling_freq, d_out)) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_small.p, ctx->small.p, sizeof(SmallLayout), hipMemcpyDeviceToHost, ctx->stream));
+    // (the context's stream does not block on torch's: the caller may read d_out, or free d_samples, as soon as this returns)
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return check_status(ctx, static_cast<unsigned>(ctx->h_small.as<SmallLayout>()->status));
+}
+
 int ps_filter_requantise_batch(ps_ctx *ctx, const void *d_samples, const ps_sample_format *fmt, const int64_t *ev_start,
                                const int64_t *ev_len, int32_t n_ev, int32_t order, double cutoff, double sampling_freq,
                                double *d_filtered, float *d_rounded, double *h_centre, double *h_step)
@@ -2973,64 +3146,48 @@ int ps_filter_requantise_batch(ps_ctx *ctx, const void *d_samples, const ps_samp
     if (n_ev < 0 || (n_ev > 0 && (!d_samples || !fmt || !ev_start || !ev_len || !d_filtered || !d_rounded || !h_centre || !h_step)))
         return fail(ctx, PS_ERR_ARG, "null pointer or negative count");
     if (n_ev == 0) return PS_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t es = fmt->dtype == PS_DTYPE_I16 ? 2 : fmt->dtype == PS_DTYPE_F64 ? 8 : 4;
-    std::vector<int64_t> off(static_cast<size_t>(n_ev) + 1, 0);
-    std::vector<int> by_len(static_cast<size_t>(n_ev));
-    for (int e = 0; e < n_ev; ++e) {
+    for (int e = 0; e < n_ev; ++e)
         if (ev_len[e] < 1 || ev_start[e] < 0) return fail(ctx, PS_ERR_ARG, "event %d: empty or negative range", e);
-        off[e + 1] = off[e] + ev_len[e];
-        by_len[e] = e;
-    }
-    // (longest first: the scratch of the filter paths grows at most once, before anything that uses it is in flight)
-    std::sort(by_len.begin(), by_len.end(), [&](int a, int b) { return ev_len[a] > ev_len[b]; });
-    HIP_TRY(ctx, ctx->h_small.reserve(sizeof(SmallLayout)));
-    ctx->small_clean = false;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->small.p, 0, sizeof(SmallLayout), ctx->stream));
-    // 1. every event's filter, queued back to back (one status word for all of them)
-    ctx->defer_sync = true;
+    // 1. every event's filter (filter_batch_queue: one launch on the fused route), one status word for all of them; the tables
+    //    of steps 2 and 3 go up with the filter's
+    RequantPlan rq;
+    plan_requant_batch(ev_len, n_ev, &rq);
+    const RequantEvent *d_rq_ev = nullptr;
+    const FiltUnit *d_rq_unit = nullptr;
+    if (int rc = filter_batch_queue(ctx, d_samples, fmt, ev_start, ev_len, n_ev, order, cutoff, sampling_freq, d_filtered, &rq, &d_rq_ev, &d_rq_unit))
+        return rc;
     int rc = PS_OK;
-    for (int k = 0; k < n_ev && rc == PS_OK; ++k) {
-        const int e = by_len[k];
-        rc = ps_filter_bessel(ctx, static_cast<const char *>(d_samples) + static_cast<size_t>(ev_start[e]) * es, fmt, ev_len[e], order, cutoff,
-                              sampling_freq, d_filtered + off[e]);
-    }
-    ctx->defer_sync = false;
-    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    // 2. sum / min / max of every filtered current, all events' partial results in one copy
-    std::vector<unsigned> grid(static_cast<size_t>(n_ev));
-    std::vector<size_t> poff(static_cast<size_t>(n_ev) + 1, 0);
-    for (int e = 0; e < n_ev; ++e) {
-        grid[e] = static_cast<unsigned>(std::min<int64_t>(1024, (ev_len[e] + 8 * RQ_NT - 1) / (8 * RQ_NT)));
-        poff[e + 1] = poff[e] + grid[e];
-    }
-    const size_t pbytes = poff[n_ev] * 3 * sizeof(double);
+    // 2. sum / min / max of every filtered current: one launch, all events' partial results in one copy
+    const size_t pbytes = rq.unit.size() * 3 * sizeof(double);
     HIP_TRY(ctx, ctx->filt.agg.reserve(pbytes));         // (the filters above are done with it only in stream order: reserve() may
     HIP_TRY(ctx, ctx->h_meta.reserve(pbytes));           //  free and allocate, which waits for the device -- correct, and rare)
-    for (int e = 0; e < n_ev; ++e)
-        hipLaunchKernelGGL(requant_stats_kernel, dim3(grid[e]), dim3(RQ_NT), 0, ctx->stream, d_filtered + off[e], static_cast<long long>(ev_len[e]),
-                           ctx->filt.agg.as<double>() + 3 * poff[e]);
+    const dim3 rq_grid(static_cast<unsigned>(rq.unit.size()));
+    hipLaunchKernelGGL(requant_stats_batch_kernel, rq_grid, dim3(RQ_NT), 0, ctx->stream, d_filtered, d_rq_ev, d_rq_unit, ctx->filt.agg.as<double>());
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(ctx->h_meta.p, ctx->filt.agg.p, pbytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->h_small.p, ctx->small.p, sizeof(SmallLayout), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     rc = check_status(ctx, static_cast<unsigned>(ctx->h_small.as<SmallLayout>()->status));
     if (rc) return rc;
-    // 3. centre and grid step per event (ps_requantise's rule), then the rounding passes
+    // 3. centre and grid step per event (ps_requantise's rule) as a table, then the rounding pass: one launch
     const double *part = ctx->h_meta.as<double>();
+    std::vector<double> par(3 * static_cast<size_t>(n_ev));
     for (int e = 0; e < n_ev; ++e) {
         double sum = 0.0, mn = INFINITY, mx = -INFINITY;
-        for (size_t g = poff[e]; g < poff[e + 1]; ++g) { sum += part[3 * g]; mn = std::min(mn, part[3 * g + 1]); mx = std::max(mx, part[3 * g + 2]); }
+        const size_t g0 = static_cast<size_t>(rq.ev[e].poff), g1 = g0 + static_cast<size_t>(rq.ev[e].grid);
+        for (size_t g = g0; g < g1; ++g) { sum += part[3 * g]; mn = std::min(mn, part[3 * g + 1]); mx = std::max(mx, part[3 * g + 2]); }
         if (!std::isfinite(sum) || !std::isfinite(mn) || !std::isfinite(mx)) return fail(ctx, PS_ERR_ARG, "the current of event %d holds NaN or infinity", e);
         double centre = sum / static_cast<double>(ev_len[e]);
         const double span = std::max(mx - centre, centre - mn);
         const double step = span > 0.0 ? std::ldexp(1.0, static_cast<int>(std::ceil(std::log2(span * 1.01))) - 22) : 1.0;
         centre = std::nearbyint(centre / step) * step;
         h_centre[e] = centre; h_step[e] = step;
-        const unsigned rg = static_cast<unsigned>(std::min<int64_t>(65535, (ev_len[e] + 4 * RQ_NT - 1) / (4 * RQ_NT)));
-        hipLaunchKernelGGL(requant_round_kernel, dim3(rg), dim3(RQ_NT), 0, ctx->stream, d_filtered + off[e], static_cast<long long>(ev_len[e]), centre,
-                           1.0 / step, step, d_rounded + off[e]);
+        par[3 * static_cast<size_t>(e)] = centre; par[3 * static_cast<size_t>(e) + 1] = 1.0 / step; par[3 * static_cast<size_t>(e) + 2] = step;
     }
+    // (h_up is free again: the tables of step 1 were copied before the synchronisation above)
+    if (int rc2 = upload_tables(ctx, ctx->filt.rq_par, {{par.data(), par.size() * sizeof(double)}})) return rc2;
+    hipLaunchKernelGGL(requant_round_batch_kernel, rq_grid, dim3(RQ_NT), 0, ctx->stream, d_filtered, d_rq_ev, d_rq_unit, ctx->filt.rq_par.as<double>(),
+                       d_rounded);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return PS_OK;
@@ -3052,30 +3209,6 @@ int check_offsets(ps_ctx *ctx, const int64_t *off, int32_t n, const char *what, 
         *longest = std::max(*longest, len);
     }
     return PS_OK;
-}
-
-// Host arrays staged back to back through h_up and copied to the start of `dev` in one transfer (the layout is the caller's:
-// 8-byte tables before 4-byte ones).  The first `head` bytes are not copied from anywhere: fill(h_up) writes them in place.
-struct HostTable { const void *p; size_t bytes; };
-template <typename Fill>
-int upload_tables(ps_ctx *ctx, DevBuf &dev, size_t head, Fill &&fill, std::initializer_list<HostTable> tables)
-{
-    size_t bytes = head;
-    for (const HostTable &t : tables) bytes += t.bytes;
-    HIP_TRY(ctx, ctx->h_up.reserve(bytes));
-    HIP_TRY(ctx, dev.reserve(bytes));
-    fill(ctx->h_up.p);
-    char *h = static_cast<char *>(ctx->h_up.p) + head;
-    for (const HostTable &t : tables) {
-        if (t.bytes) std::memcpy(h, t.p, t.bytes);
-        h += t.bytes;
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(dev.p, ctx->h_up.p, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return PS_OK;
-}
-int upload_tables(ps_ctx *ctx, DevBuf &dev, std::initializer_list<HostTable> tables)
-{
-    return upload_tables(ctx, dev, 0, [](void *) {}, tables);
 }
 
 }  // namespace
@@ -4047,29 +4180,18 @@ int ps_filter_derivative_f64(ps_ctx *ctx, const double *d_current, const int64_t
     // np.argmax(...) > high_threshold: the index is at least h1 = floor(high_threshold) + 1; every index when it is negative
     const double ht = params->high_threshold;
     const int32_t h1 = ht < 0.0 ? 0 : (ht >= 2147483646.0 ? INT32_MAX : static_cast<int32_t>(std::floor(ht)) + 1);
-    // 1. y: the caller's (prefiltered) or the order-1 Bessel filtfilt of every event, packed, the launches queued back to
-    //    back on the context's stream (float64 input has the per-event entry only)
+    // 1. y: the caller's (prefiltered) or the order-1 Bessel filtfilt of every event, packed: the batched float64 filter on the
+    //    context's stream
     const double *d_y = d_current;
     std::vector<int64_t> start(h_ev_start, h_ev_start + n);
     if (filter) {
-        std::vector<int> by_len(n);
         int64_t total_len = 0;
-        for (size_t e = 0; e < n; ++e) { start[e] = total_len; total_len += h_ev_len[e]; by_len[e] = static_cast<int>(e); }
-        std::sort(by_len.begin(), by_len.end(), [&](int a, int b) { return h_ev_len[a] > h_ev_len[b]; });   // (scratch grows once)
+        for (size_t e = 0; e < n; ++e) { start[e] = total_len; total_len += h_ev_len[e]; }
         HIP_TRY(ctx, ctx->sp.y.reserve(static_cast<size_t>(total_len) * sizeof(double)));
-        HIP_TRY(ctx, ctx->h_small.reserve(sizeof(SmallLayout)));
-        ctx->small_clean = false;
-        HIP_TRY(ctx, hipMemsetAsync(ctx->small.p, 0, sizeof(SmallLayout), ctx->stream));
         const ps_sample_format f64 = {PS_DTYPE_F64, 0, 1.0};
-        ctx->defer_sync = true;
-        int rc = PS_OK;
-        for (size_t k = 0; k < n && rc == PS_OK; ++k) {
-            const int e = by_len[k];
-            rc = ps_filter_bessel(ctx, d_current + h_ev_start[e], &f64, h_ev_len[e], 1, params->cutoff_freq, params->sampling_freq,
-                                  ctx->sp.y.as<double>() + start[e]);
-        }
-        ctx->defer_sync = false;
-        if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+        // (filter_batch_queue: one launch for all events on the fused route; it packs the results as `start` does)
+        if (int rc = filter_batch_queue(ctx, d_current, &f64, h_ev_start, h_ev_len, n_ev, 1, params->cutoff_freq, params->sampling_freq,
+                                        ctx->sp.y.as<double>())) return rc;
         d_y = ctx->sp.y.as<double>();
     }
     // 2. the tics: j + 1 where blocks[j + 1] != blocks[j], j in [0, n - 2)

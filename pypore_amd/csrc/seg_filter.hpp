@@ -16,12 +16,9 @@
 // Included by seg_device.hpp (DevCfg, load_count).
 #pragma once
 
-namespace ps {
+#include "filt_plan.hpp"   // FILT_NT, FILT_PER, FILT_CHUNK, FILT_PAD, FILT_MAXORD, RQ_NT, FiltEvent, FiltUnit, RequantEvent: shared with the host plan
 
-constexpr int FILT_NT = 256;
-constexpr int FILT_PER = 16;                        // consecutive samples per thread
-constexpr int FILT_CHUNK = FILT_NT * FILT_PER;
-constexpr int FILT_PAD = 6;                         // scipy: padlen = 3 * max(len(a), len(b)) for a first-order section
+namespace ps {
 
 struct FiltCoef { double b0, b1, a1, alpha, beta, zi; };
 
@@ -267,13 +264,14 @@ __global__ __launch_bounds__(FILT_NT) void filt_apply_kernel(DevCfg c, FiltCoef 
 #ifndef PS_FILT_OCC
 #define PS_FILT_OCC 2          // workgroups per CU the fused kernel is compiled for
 #endif
+// One tile: what a workgroup of either fused kernel does once it knows its event (c.samples at the event's first sample, g, out at
+// the event's first output) and its tile within the event.  Written once: the batched launch gives the per-event launch's bits.
 template <int DT>
-__global__ __launch_bounds__(FILT_NT, PS_FILT_OCC) void filt_fused_kernel(DevCfg c, FiltCoef f, FiltGeom g, int H, double *out, unsigned *status)
+__device__ __forceinline__ void filt_fused_tile(const DevCfg &c, const FiltCoef &f, const FiltGeom &g, int H, int64_t tile, double *out,
+                                                unsigned *status, Affine *wsum /*[FILT_NT/64]*/, double *lds /*[FILT_LDS]*/)
 {
-    __shared__ Affine wsum[FILT_NT / 64];
-    __shared__ double lds[FILT_LDS];
     const int T = FILT_CHUNK - 2 * H;
-    const int64_t w0 = static_cast<int64_t>(blockIdx.x) * T - H;      // window element e <-> sequence index i = w0 + e
+    const int64_t w0 = tile * T - H;                                  // window element e <-> sequence index i = w0 + e
     unsigned bad = 0;
     double x[FILT_PER];
     FiltGeom g0 = g;
@@ -330,6 +328,42 @@ __global__ __launch_bounds__(FILT_NT, PS_FILT_OCC) void filt_fused_kernel(DevCfg
     if (bad) atomicOr(status, bad);
 }
 
+template <int DT>
+__global__ __launch_bounds__(FILT_NT, PS_FILT_OCC) void filt_fused_kernel(DevCfg c, FiltCoef f, FiltGeom g, int H, double *out, unsigned *status)
+{
+    __shared__ Affine wsum[FILT_NT / 64];
+    __shared__ double lds[FILT_LDS];
+    filt_fused_tile<DT>(c, f, g, H, static_cast<int64_t>(blockIdx.x), out, status, wsum, lds);
+}
+
+// Bytes of one sample of the filter kernels' input
+template <int DT> constexpr int filt_elem() { return DT == PS_DTYPE_F64 ? 8 : DT == PS_DTYPE_I16 ? 2 : 4; }
+// The event of a batch as the per-event kernels see one: the samples from its first one (any start: the loads are scalar-indexed and
+// need the element's own alignment only)
+template <int DT>
+__device__ __forceinline__ DevCfg filt_event_cfg(DevCfg c, const FiltEvent &e)
+{
+    c.samples = static_cast<const char *>(c.samples) + e.start * filt_elem<DT>();
+    return c;
+}
+
+// The batch (ps_filter_bessel_batch): workgroup b takes (event, tile) from entry b of the plan's unit table (filt_plan.hpp) -- one
+// uniform load, no search -- and is from there on workgroup `tile` of filt_fused_kernel on that event alone; the output goes to the
+// event's place in the packed buffer.  Slow order-1 filters (the three-pass scan above: H would exceed 1 024, or filter_fused is
+// off) have no batched kernel: the batch entry queues them per event.
+template <int DT>
+__global__ __launch_bounds__(FILT_NT, PS_FILT_OCC) void filt_fused_batch_kernel(DevCfg c, FiltCoef f, int H, const FiltEvent *__restrict__ evs,
+                                                                                const FiltUnit *__restrict__ units, double *out, unsigned *status)
+{
+    __shared__ Affine wsum[FILT_NT / 64];
+    __shared__ double lds[FILT_LDS];
+    const FiltUnit u = units[blockIdx.x];
+    const FiltEvent e = evs[u.ev];
+    FiltGeom g;
+    g.n = e.n; g.total = e.n + 2 * FILT_PAD; g.lead = 0; g.padded = g.total;
+    filt_fused_tile<DT>(filt_event_cfg<DT>(c, e), f, g, H, static_cast<int64_t>(u.idx), out + e.out_off, status, wsum, lds);
+}
+
 // ---- orders 2..4: Event.filter(order=n) (DataTypes.py:258-274 hands `order` to scipy.signal.bessel) -------------------
 // The n-th order section in direct form II transposed carries n delays:  y = b0 x + z0,  z_k <- b_{k+1} x - a_{k+1} y
 // + z_{k+1}.  Orders other than 1 are rare in the reference's workflows (its default and every example use 1), so this
@@ -339,15 +373,15 @@ __global__ __launch_bounds__(FILT_NT, PS_FILT_OCC) void filt_fused_kernel(DevCfg
 // at the start of the sequence) to H samples behind it, the forward values kept in a private scratch row, then
 // backward from the end of that row (exact zi * last value at the end of the sequence).  The arithmetic per sample is
 // scipy's lfilter's, in its order; only the warm-up replaces the history.  Work: (S + 2H) + (S + H) samples per S.
-constexpr int FILT_MAXORD = 8;
 struct FiltN { int order, pad; double b[FILT_MAXORD + 1], a[FILT_MAXORD + 1], zi[FILT_MAXORD]; };
 
+// One segment: what a thread of either order-n kernel does once it knows its event (c.samples at the event's first sample, n, out at
+// the event's first output), its segment t within the event and its scratch row of S + H doubles.
 template <int DT>
-__global__ __launch_bounds__(64) void filt_halo_kernel(DevCfg c, FiltN f, int64_t n, int S, int H, double *scratch, double *out,
-                                                       unsigned *status)
+__device__ __forceinline__ void filt_halo_segment(const DevCfg &c, const FiltN &f, int64_t n, int64_t t, int S, int H, double *row, double *out,
+                                                  unsigned *status)
 {
     const int64_t m = n + 2LL * f.pad;
-    const int64_t t = blockIdx.x * 64LL + threadIdx.x;
     const int64_t lo = t * S;
     if (lo >= m) return;
     const int64_t hi = min(m, lo + S);
@@ -360,7 +394,6 @@ __global__ __launch_bounds__(64) void filt_halo_kernel(DevCfg c, FiltN f, int64_
         const double v = filt_load<DT>(c, idx, bad);
         return (jj < 0 ? 2.0 * x0 - v : (jj >= n ? 2.0 * xl - v : v)) * c.q;
     };
-    double *row = scratch + t * static_cast<int64_t>(S + H);
     double z[FILT_MAXORD];
     auto step = [&](double x) {                        // scipy's lfilter, in its operation order, no FMA contraction
 #pragma clang fp contract(off)
@@ -396,18 +429,43 @@ __global__ __launch_bounds__(64) void filt_halo_kernel(DevCfg c, FiltN f, int64_
     if (bad) atomicOr(status, bad);
 }
 
+template <int DT>
+__global__ __launch_bounds__(64) void filt_halo_kernel(DevCfg c, FiltN f, int64_t n, int S, int H, double *scratch, double *out,
+                                                       unsigned *status)
+{
+    const int64_t t = blockIdx.x * 64LL + threadIdx.x;
+    if (t * S >= n + 2LL * f.pad) return;              // (before the row's address is formed: the scratch holds the segments' rows only)
+    filt_halo_segment<DT>(c, f, n, t, S, H, scratch + t * static_cast<int64_t>(S + H), out, status);
+}
+
+// The batch, one launch per scratch group of the plan (filt_plan.hpp): thread t of the group takes (event, segment) from entry
+// unit0 + t of the unit table and its scratch row at t * (S + H); the arithmetic per sample is filt_halo_segment's `step`.
+template <int DT>
+__global__ __launch_bounds__(64) void filt_halo_batch_kernel(DevCfg c, FiltN f, int S, int H, const FiltEvent *__restrict__ evs,
+                                                             const FiltUnit *__restrict__ units, int64_t unit0, int64_t n_units, double *scratch,
+                                                             double *out, unsigned *status)
+{
+    const int64_t t = blockIdx.x * 64LL + threadIdx.x;
+    if (t >= n_units) return;
+    const FiltUnit u = units[unit0 + t];
+    const FiltEvent e = evs[u.ev];
+    filt_halo_segment<DT>(filt_event_cfg<DT>(c, e), f, e.n, static_cast<int64_t>(u.idx), S, H, scratch + t * static_cast<int64_t>(S + H),
+                          out + e.out_off, status);
+}
+
 // ---- K5b: a filtered current back onto a grid (ps_requantise) -----------------------------------------------------
 // The segmenter works on exact integer sums; a filtered current is float64 off every grid.  DataTypes.Event.parse
 // centres it on its mean and rounds it to the finest power-of-two grid that keeps every count below 2^22 (DESIGN.md
 // 7c).  These two kernels do that for a current that is still on the device: partial sum / min / max per workgroup
 // (combined on the host in a fixed order), then out[i] = (x[i] - centre) rounded to a multiple of `step`, as fp32
 // (22-bit counts times a power of two: exact).  8 B in, 4 B out per sample and pass: bound by HBM.
-constexpr int RQ_NT = 256;
-__global__ __launch_bounds__(RQ_NT) void requant_stats_kernel(const double *x, long long n, double *part)
+// Block g of `grid` over x[0, n): its partial (sum, min, max) to part[3 g].  Written once for the per-event and the batched launch:
+// the same strides, the same order of the additions.
+__device__ __forceinline__ void requant_stats_block(const double *x, long long n, long long g, long long grid, double *part)
 {
     __shared__ double s_sum[RQ_NT / 64], s_min[RQ_NT / 64], s_max[RQ_NT / 64];
     double sum = 0.0, mn = INFINITY, mx = -INFINITY;
-    for (long long i = blockIdx.x * static_cast<long long>(RQ_NT) + threadIdx.x; i < n; i += gridDim.x * static_cast<long long>(RQ_NT)) {
+    for (long long i = g * static_cast<long long>(RQ_NT) + threadIdx.x; i < n; i += grid * static_cast<long long>(RQ_NT)) {
         const double v = x[i];
         sum += v; mn = fmin(mn, v); mx = fmax(mx, v);
     }
@@ -420,15 +478,43 @@ __global__ __launch_bounds__(RQ_NT) void requant_stats_kernel(const double *x, l
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int w = 1; w < RQ_NT / 64; ++w) { sum += s_sum[w]; mn = fmin(mn, s_min[w]); mx = fmax(mx, s_max[w]); }
-        part[3 * blockIdx.x] = sum; part[3 * blockIdx.x + 1] = mn; part[3 * blockIdx.x + 2] = mx;
+        part[3 * g] = sum; part[3 * g + 1] = mn; part[3 * g + 2] = mx;
     }
+}
+__global__ __launch_bounds__(RQ_NT) void requant_stats_kernel(const double *x, long long n, double *part)
+{
+    requant_stats_block(x, n, blockIdx.x, gridDim.x, part);
+}
+__device__ __forceinline__ void requant_round_block(const double *x, long long n, long long g, long long grid, double centre, double inv_step,
+                                                    double step, float *out)
+{
+#pragma clang fp contract(off)
+    for (long long i = g * static_cast<long long>(RQ_NT) + threadIdx.x; i < n; i += grid * static_cast<long long>(RQ_NT))
+        out[i] = static_cast<float>(rint((x[i] - centre) * inv_step) * step);
 }
 __global__ __launch_bounds__(RQ_NT) void requant_round_kernel(const double *x, long long n, double centre, double inv_step, double step,
                                                            float *out)
 {
-#pragma clang fp contract(off)
-    for (long long i = blockIdx.x * static_cast<long long>(RQ_NT) + threadIdx.x; i < n; i += gridDim.x * static_cast<long long>(RQ_NT))
-        out[i] = static_cast<float>(rint((x[i] - centre) * inv_step) * step);
+    requant_round_block(x, n, blockIdx.x, gridDim.x, centre, inv_step, step, out);
+}
+
+// The batch (ps_filter_requantise_batch): one workgroup per (event, block g of the event's own grid) of the plan's table
+// (filt_plan.hpp: plan_requant_batch) over the packed float64 buffer.  The partial sums land where the per-event launches left
+// them, 3 * (poff[e] + g); the rounding reads (centre, 1 / step, step) of its event from the table the host forms from them.
+__global__ __launch_bounds__(RQ_NT) void requant_stats_batch_kernel(const double *x, const RequantEvent *__restrict__ evs,
+                                                                 const FiltUnit *__restrict__ units, double *part)
+{
+    const FiltUnit u = units[blockIdx.x];
+    const RequantEvent e = evs[u.ev];
+    requant_stats_block(x + e.off, e.n, u.idx, e.grid, part + 3 * e.poff);
+}
+__global__ __launch_bounds__(RQ_NT) void requant_round_batch_kernel(const double *x, const RequantEvent *__restrict__ evs,
+                                                                 const FiltUnit *__restrict__ units, const double *__restrict__ par /*[3 n_ev]*/,
+                                                                 float *out)
+{
+    const FiltUnit u = units[blockIdx.x];
+    const RequantEvent e = evs[u.ev];
+    requant_round_block(x + e.off, e.n, u.idx, e.grid, par[3 * u.ev], par[3 * u.ev + 1], par[3 * u.ev + 2], out + e.off);
 }
 
 }  // namespace ps

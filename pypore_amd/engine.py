@@ -535,6 +535,32 @@ class Context(object):
         return filtered[:total], rounded[:total], off, centre[:n_ev], step[:n_ev]
 
     @_serialised
+    def filter_bessel_batch(self, samples, ev_start, ev_len, quantum, cutoff=2000., sampling_freq=1.e5, order=1, offset_counts=0):
+        """ps_filter_bessel_batch: Event.filter for many events of ONE device-resident tensor in one call -- event e is
+        samples[ev_start[e] : ev_start[e] + ev_len[e]]; events may overlap and come in any order.  `samples` as for filter_bessel
+        (float32 on the grid `quantum`, int16 counts, or float64 on no grid).  Returns (float64 CUDA tensor, the filtered
+        events back to back, each bit for bit what filter_bessel returns for it alone; offsets int64 numpy [n_ev + 1]).  One
+        launch on the fused order-1 route, one host synchronisation for the batch."""
+        assert samples.is_cuda and samples.is_contiguous() and samples.dim() == 1
+        fmt = _lib.SampleFormat(_lib.PS_DTYPE_F64, 0, 1.0) if samples.dtype == torch.float64 else self._fmt(samples, quantum, offset_counts)
+        ev_start = np.ascontiguousarray(ev_start, dtype=np.int64)
+        ev_len = np.ascontiguousarray(ev_len, dtype=np.int64)
+        if ev_start.shape != ev_len.shape or ev_start.ndim != 1:
+            raise ValueError("ev_start and ev_len must be one-dimensional and of one length")
+        n_ev = ev_start.size
+        if n_ev and (int(ev_start.min()) < 0 or int(ev_len.min()) < 0 or int((ev_start + ev_len).max()) > samples.numel()):
+            raise ValueError("an event lies outside the samples")
+        off = np.concatenate(([0], np.cumsum(ev_len))).astype(np.int64)
+        total = int(off[-1])
+        out = torch.empty(max(1, total), dtype=torch.float64, device=samples.device)
+        P64 = ctypes.POINTER(ctypes.c_int64)
+        torch.cuda.current_stream(samples.device).synchronize()
+        _lib.check(self.L.ps_filter_bessel_batch(self.handle, ctypes.c_void_p(samples.data_ptr()), ctypes.byref(fmt),
+                                                 ev_start.ctypes.data_as(P64), ev_len.ctypes.data_as(P64), n_ev, int(order),
+                                                 float(cutoff), float(sampling_freq), ctypes.c_void_p(out.data_ptr())), self.handle)
+        return out[:total], off
+
+    @_serialised
     def requantise(self, current):
         """ps_requantise: a filtered current (float64 CUDA tensor, pA) centred and rounded to the finest power-of-two
         grid that keeps its counts below 2**22.  Returns (float32 CUDA tensor on that grid, centre, step): segment it

@@ -6,8 +6,8 @@ of --runs after --warmup warm-ups; the spans stay on the device (no Segment obje
 
 Modes: snakebase; filter-derivative at its defaults (low_threshold 1: on this data no derivative reaches it, the call is
 filter + one pass) and at low_threshold 0.05 (the steps of the data become blocks), each also with prefiltered = 1 on the
-device filter's own output (the decision kernels alone).  The float64 filter has the per-event launch only: a batch is one
-fused filter launch per event, queued back to back on the context's stream.
+device filter's own output (the decision kernels alone).  The filter of a batch is one launch (ps_filter_bessel_batch's
+kernels; tools/bench_filter_batch.py times it on its own and against the per-event entry).
 
 Two yardsticks from the same run:
 * the numpy restatement (tests/state_parser_oracle.py) on one CPU core, timed on --cpu-events events and scaled to all;
