@@ -50,6 +50,7 @@
 #include "pool_plan.hpp"
 #include "seg_plan.hpp"
 #include "filt_plan.hpp"
+#include "batch_plan.hpp"
 
 using namespace ps;
 
@@ -2004,6 +2005,20 @@ static int statsplit_upload(ps_ctx *ctx, const std::vector<int64_t> &tab, int32_
     return PS_OK;
 }
 
+// The counts per event are known: h_off (n + 1 entries) from them, the capacity check (`what` names the capacity in the error),
+// the offsets on the device in buf (none for a total of 0).
+extern "C++" template <class Count>
+static int offsets_to_device(ps_ctx *ctx, DevBuf &buf, const Count *counts, size_t n, int64_t cap, const char *what, int64_t *h_off)
+{
+    int64_t total = 0;
+    if (offsets_from_counts(counts, n, cap, h_off, &total))
+        return fail(ctx, PS_ERR_CAPACITY, "%s capacity %lld < required %lld", what, static_cast<long long>(cap), static_cast<long long>(total));
+    if (total == 0) return PS_OK;
+    HIP_TRY(ctx, buf.reserve((n + 1) * sizeof(int64_t)));
+    HIP_TRY(ctx, hipMemcpyAsync(buf.p, h_off, (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    return PS_OK;
+}
+
 int ps_statsplit_f64(ps_ctx *ctx, const double *d_current, const int64_t *h_ev_start, const int64_t *h_ev_len, int32_t n_ev,
                      const int64_t *h_lo, const int64_t *h_hi, const ps_statsplit_params *params, int32_t *d_bounds,
                      int64_t cap, int64_t *h_bounds_off)
@@ -2020,32 +2035,23 @@ int ps_statsplit_f64(ps_ctx *ctx, const double *d_current, const int64_t *h_ev_s
         return fail(ctx, PS_ERR_ARG, "use_log must be 0 or 1 and splitter PS_STATSPLIT_STEPWISE or PS_STATSPLIT_SLANTED");
     const bool slanted = params->splitter == PS_STATSPLIT_SLANTED;
     const size_t n = static_cast<size_t>(n_ev);
-    std::vector<int64_t> tab(6 * n + 1, 0);
-    int64_t *t_start = tab.data(), *t_len = t_start + n, *t_pre = t_len + n, *t_lo = t_pre + n, *t_hi = t_lo + n, *t_slot = t_hi + n;
-    int64_t total_len = 0, slots = 0, longest = 0;
-    for (int e = 0; e < n_ev; ++e) {
-        const int64_t len = h_ev_len[e];
-        if (len < 0 || h_ev_start[e] < 0 || len > (1ll << 30))         // (2^30: the slanted splitter's N fits in int64)
-            return fail(ctx, PS_ERR_ARG, "event %d length %lld out of range (2^30 samples at most)", e, static_cast<long long>(len));
-        const int64_t lo = h_lo ? h_lo[e] : 0, hi = h_hi ? h_hi[e] : len;
-        if (lo < 0 || lo > len || hi < 0 || hi > len)
-            return fail(ctx, PS_ERR_ARG, "event %d: range [%lld, %lld) outside its %lld samples", e, static_cast<long long>(lo),
-                        static_cast<long long>(hi), static_cast<long long>(len));
-        const int64_t span = std::max<int64_t>(0, hi - lo);
-        t_start[e] = h_ev_start[e]; t_len[e] = len; t_pre[e] = total_len; t_lo[e] = lo; t_hi[e] = hi; t_slot[e] = slots;
-        total_len += len;
-        slots += 2 * (span / mw) + 2;                                 // (seg_statsplit.hpp: boundary slots)
-        longest = std::max(longest, span);
+    StatsplitTables T;                                                // (batch_plan.hpp; 2^30: the slanted splitter's N fits in int64)
+    int32_t bad = -1;
+    if (const BatchPlanError err = plan_statsplit_tables(h_ev_start, h_ev_len, n_ev, h_lo, h_hi, mw, &T, &bad)) {
+        const long long len = h_ev_len[bad];
+        if (err == BATCH_PLAN_RANGE)
+            return fail(ctx, PS_ERR_ARG, "event %d: range [%lld, %lld) outside its %lld samples", bad, static_cast<long long>(h_lo ? h_lo[bad] : 0),
+                        h_hi ? static_cast<long long>(h_hi[bad]) : len, len);
+        return fail(ctx, PS_ERR_ARG, "event %d length %lld out of range (2^30 samples at most)", bad, len);
     }
-    t_slot[n] = slots;
+    const int64_t total_len = T.total_len, slots = T.slots, stack_cap = T.stack_cap;
     for (int e = 0; e <= n_ev; ++e) h_bounds_off[e] = 0;
     if (n_ev == 0) return PS_OK;
     if (total_len > 0 && !d_current) return fail(ctx, PS_ERR_ARG, "d_current is NULL");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const unsigned n_wg = static_cast<unsigned>(std::min<int64_t>(n_ev, 4ll * cu_count(ctx)));   // (more events: grid stride)
-    const int64_t stack_cap = longest / mw + 2;                       // (seg_statsplit.hpp: stack size)
     SsEvents ev;
-    int rc = statsplit_upload(ctx, tab, n_ev, &ev);
+    int rc = statsplit_upload(ctx, T.tab, n_ev, &ev);
     if (rc) return rc;
     const size_t pre_n = static_cast<size_t>(std::max<int64_t>(1, total_len));
     HIP_TRY(ctx, ctx->ss.pre.reserve((slanted ? 3 : 2) * pre_n * sizeof(double)));
@@ -2078,13 +2084,8 @@ int ps_statsplit_f64(ps_ctx *ctx, const double *d_current, const int64_t *h_ev_s
     const unsigned st = static_cast<unsigned>(cnt[n]);
     if (st & SS_ST_STACK) return fail(ctx, PS_ERR_INTERNAL, "StatSplit: device interval stack overflow");
     if (st & SS_ST_OUT) return fail(ctx, PS_ERR_INTERNAL, "StatSplit: device boundary slot overflow");
-    for (int e = 0; e < n_ev; ++e) h_bounds_off[e + 1] = h_bounds_off[e] + cnt[e];
-    const int64_t total = h_bounds_off[n_ev];
-    if (total > cap)
-        return fail(ctx, PS_ERR_CAPACITY, "bounds capacity %lld < required %lld", static_cast<long long>(cap), static_cast<long long>(total));
-    if (total == 0) return PS_OK;
-    HIP_TRY(ctx, ctx->ss.off.reserve((n + 1) * sizeof(int64_t)));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->ss.off.p, h_bounds_off, (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = offsets_to_device(ctx, ctx->ss.off, cnt.data(), n, cap, "bounds", h_bounds_off))) return rc;
+    if (h_bounds_off[n_ev] == 0) return PS_OK;
     hipLaunchKernelGGL(statsplit_gather_kernel, dim3(static_cast<unsigned>(std::min<int64_t>(n_ev, 4096))), dim3(256), 0, ctx->stream,
                        cfg.tmp, ev.slot, ctx->ss.off.as<int64_t>(), n_ev, d_bounds);
     HIP_TRY(ctx, hipGetLastError());
@@ -3197,18 +3198,21 @@ int ps_filter_requantise_batch(ps_ctx *ctx, const void *d_samples, const ps_samp
 
 namespace {
 
-// Offsets of a set of sequences (`what` names it in the error): non-negative, ascending, no sequence longer than
-// INT32_MAX / 2; *longest = the longest sequence
-int check_offsets(ps_ctx *ctx, const int64_t *off, int32_t n, const char *what, int64_t *longest)
+// check_offsets (batch_plan.hpp) of a set of sequences, `what` names it in the error; *longest = the longest sequence
+int sequence_offsets(ps_ctx *ctx, const int64_t *off, int32_t n, const char *what, int64_t *longest)
 {
-    *longest = 0;
-    for (int32_t q = 0; q < n; ++q) {
-        const int64_t len = off[q + 1] - off[q];
-        if (len < 0 || off[q] < 0) return fail(ctx, PS_ERR_ARG, "%s offsets must be non-negative and ascending", what);
-        if (len > INT32_MAX / 2) return fail(ctx, PS_ERR_ARG, "%s %d too long", what, q);
-        *longest = std::max(*longest, len);
+    int32_t bad = -1;
+    switch (check_offsets(off, n, longest, &bad)) {
+    case BATCH_PLAN_OK: return PS_OK;
+    case BATCH_PLAN_LONG: return fail(ctx, PS_ERR_ARG, "%s %d too long", what, bad);
+    default: return fail(ctx, PS_ERR_ARG, "%s offsets must be non-negative and ascending", what);
     }
-    return PS_OK;
+}
+// check_slot_offsets (batch_plan.hpp) of the slots of n items, `what` names them in the error
+int slot_offsets(ps_ctx *ctx, const int64_t *off, int32_t n, const char *what)
+{
+    int32_t bad = -1;
+    return check_slot_offsets(off, n, &bad) ? fail(ctx, PS_ERR_ARG, "%s offsets must be non-negative and ascending", what) : PS_OK;
 }
 
 }  // namespace
@@ -3227,7 +3231,7 @@ int ps_align_batch(ps_ctx *ctx, const double *h_model_means, const double *h_mod
     if (n_seq == 0) return PS_OK;
     if (!d_scores || !d_paths || !d_status) return fail(ctx, PS_ERR_ARG, "null output pointer");
     int64_t s_max = 0;
-    if (int rc = check_offsets(ctx, h_seq_off, n_seq, "sequence", &s_max)) return rc;
+    if (int rc = sequence_offsets(ctx, h_seq_off, n_seq, "sequence", &s_max)) return rc;
     if (h_seq_off[n_seq] > 0 && (!d_seq_means || !d_seq_stds || !d_seq_durs)) return fail(ctx, PS_ERR_ARG, "null sequence pointer");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // one upload: model rows (mean, std, dur*skip, dur*backslip, first-row penalty, dur), then the offsets
@@ -3251,19 +3255,16 @@ int ps_align_batch(ps_ctx *ctx, const double *h_model_means, const double *h_mod
     M.mean = dm; M.std = dm + m; M.dsp = dm + 2 * m; M.dbp = dm + 3 * m; M.pen0 = dm + 4 * m; M.dur = dm + 5 * m;
     M.m = m; M.skip_pen = skip_penalty; M.back_pen = backslip_penalty;
     const long long *d_off = reinterpret_cast<const long long *>(dm + 6 * m);
-    // scratch: score, skip_score and backslip_score of one sequence per resident workgroup
-    // traceback block: as many rows as fit in ~48 KB of LDS next to the 9 working rows; 12 KB when the batch is
-    // large enough to want many resident workgroups per CU instead
-    const size_t blk_budget = n_seq > 512 ? (12u << 10) : (48u << 10);
-    const int B = static_cast<int>(std::max<size_t>(1, std::min<size_t>(ALIGN_B_MAX, blk_budget / (3u * m * sizeof(double)))));
-    const size_t lds = align_lds_doubles(m, B) * sizeof(double);
+    // the traceback block, the LDS and the scratch -- score, skip_score and backslip_score of one sequence per resident
+    // workgroup -- are align_plan's (batch_plan.hpp)
+    AlignPlan A;
+    if (align_plan(m, n_seq, s_max, &A)) return fail(ctx, PS_ERR_ARG, "a %lld x %d alignment needs more than 32 GiB of scratch", (long long)s_max, m);
+    const int B = A.B;
+    const size_t lds = A.lds;
+    const unsigned long long per_wg = A.per_wg;            // doubles
     HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(align_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      static_cast<int>(lds)));
-    const unsigned long long per_wg = 3ull * static_cast<unsigned long long>(std::max<int64_t>(s_max, 1)) * m;   // doubles
-    const unsigned long long budget = 2ull << 30;          // bytes of scratch at most (unless one sequence needs more)
-    if (per_wg * sizeof(double) > (32ull << 30)) return fail(ctx, PS_ERR_ARG, "a %lld x %d alignment needs more than 32 GiB of scratch", (long long)s_max, m);
-    unsigned grid = std::min<unsigned>(static_cast<unsigned>(n_seq), resident_slots(ctx, align_kernel, ALIGN_NT, lds));
-    grid = static_cast<unsigned>(std::max<unsigned long long>(1, std::min<unsigned long long>(grid, budget / (per_wg * sizeof(double)))));
+    const unsigned grid = std::min({static_cast<unsigned>(n_seq), resident_slots(ctx, align_kernel, ALIGN_NT, lds), A.grid_cap});
     HIP_TRY(ctx, ctx->align.scratch.reserve(static_cast<size_t>(grid) * per_wg * sizeof(double)));
     hipLaunchKernelGGL(align_kernel, dim3(grid), dim3(ALIGN_NT), lds, ctx->stream, M, d_seq_means, d_seq_stds, d_seq_durs,
                        d_off, n_seq, ctx->align.scratch.as<double>(), static_cast<long long>(per_wg), B, d_scores, d_paths, d_status);
@@ -3283,8 +3284,8 @@ int ps_pairwise_scores(ps_ctx *ctx, const double *d_a, const int64_t *h_a_off, i
     if (n_a == 0 || n_b == 0) return PS_OK;
     if (!d_scores) return fail(ctx, PS_ERR_ARG, "null output pointer");
     int64_t m_max = 0, n_max = 0;
-    if (int rc = check_offsets(ctx, h_a_off, n_a, "A sequence", &m_max)) return rc;
-    if (int rc = check_offsets(ctx, h_b_off, n_b, "B sequence", &n_max)) return rc;
+    if (int rc = sequence_offsets(ctx, h_a_off, n_a, "A sequence", &m_max)) return rc;
+    if (int rc = sequence_offsets(ctx, h_b_off, n_b, "B sequence", &n_max)) return rc;
     if (n_max > PW_N_MAX) return fail(ctx, PS_ERR_ARG, "a B sequence of %lld elements: the device pairwise aligner takes up to %d", (long long)n_max, PW_N_MAX);
     if ((h_a_off[n_a] > 0 && !d_a) || (h_b_off[n_b] > 0 && !d_b)) return fail(ctx, PS_ERR_ARG, "null sequence pointer");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -3324,13 +3325,12 @@ int ps_pairwise_batch(ps_ctx *ctx, const double *d_a, const int64_t *h_a_off, in
     if (!d_scores || !d_status || !d_cols_i || !d_cols_j || !d_col_need || !d_aln_score || !d_aln_start || !d_aln_len || !d_aln_count)
         return fail(ctx, PS_ERR_ARG, "null output pointer");
     int64_t m_max = 0, n_max = 0;
-    if (int rc = check_offsets(ctx, h_a_off, n_a, "A sequence", &m_max)) return rc;
-    if (int rc = check_offsets(ctx, h_b_off, n_b, "B sequence", &n_max)) return rc;
+    if (int rc = sequence_offsets(ctx, h_a_off, n_a, "A sequence", &m_max)) return rc;
+    if (int rc = sequence_offsets(ctx, h_b_off, n_b, "B sequence", &n_max)) return rc;
     if ((h_a_off[n_a] > 0 && !d_a) || (h_b_off[n_b] > 0 && !d_b)) return fail(ctx, PS_ERR_ARG, "null sequence pointer");
     for (int32_t q = 0; q < n_pairs; ++q) {
         if (h_pair_a[q] < 0 || h_pair_a[q] >= n_a || h_pair_b[q] < 0 || h_pair_b[q] >= n_b) return fail(ctx, PS_ERR_ARG, "pair %d names a sequence that is not there", q);
-        if (h_col_off[q] < 0 || h_col_off[q + 1] < h_col_off[q] || h_aln_off[q] < 0 || h_aln_off[q + 1] < h_aln_off[q])
-            return fail(ctx, PS_ERR_ARG, "slot offsets must be non-negative and ascending");
+        if (!slot_ok(h_col_off, q) || !slot_ok(h_aln_off, q)) return fail(ctx, PS_ERR_ARG, "slot offsets must be non-negative and ascending");
         const int64_t m = h_a_off[h_pair_a[q] + 1] - h_a_off[h_pair_a[q]], n = h_b_off[h_pair_b[q] + 1] - h_b_off[h_pair_b[q]];
         if (n > PW_N_MAX) return fail(ctx, PS_ERR_ARG, "pair %d: y of %lld elements, the device pairwise aligner takes up to %d", q, (long long)n, PW_N_MAX);
         if (m * n > INT32_MAX) return fail(ctx, PS_ERR_ARG, "pair %d: %lld x %lld cells, 2^31 - 1 at most", q, (long long)m, (long long)n);
@@ -3351,52 +3351,27 @@ int ps_pairwise_batch(ps_ctx *ctx, const double *d_a, const int64_t *h_a_off, in
     P.aln_score = d_aln_score; P.aln_start = d_aln_start; P.aln_len = d_aln_len; P.aln_count = d_aln_count;
     // Launches: consecutive pairs while the scratch of their launch -- one matrix of the launch's largest pair per workgroup,
     // a workgroup per pair up to the resident slots -- stays within the budget; a launch whose first pair alone leaves room
-    // for few matrices runs on that many workgroups
+    // for few matrices runs on that many workgroups (next_scratch_launch, batch_plan.hpp)
     const unsigned long long budget = static_cast<unsigned long long>(std::max<long long>(1, ctx->pw.budget));
-    auto dims = [&](int32_t q, unsigned long long *cells, unsigned long long *rows, int *n) {
-        const int64_t m = h_a_off[h_pair_a[q] + 1] - h_a_off[h_pair_a[q]];
-        *n = static_cast<int>(h_b_off[h_pair_b[q] + 1] - h_b_off[h_pair_b[q]]);
-        *cells = static_cast<unsigned long long>(m) * static_cast<unsigned long long>(*n); *rows = static_cast<unsigned long long>(m);
+    auto dims = [&](int32_t q) {
+        const int64_t m = h_a_off[h_pair_a[q] + 1] - h_a_off[h_pair_a[q]], n = h_b_off[h_pair_b[q] + 1] - h_b_off[h_pair_b[q]];
+        return PwDims{static_cast<unsigned long long>(m) * static_cast<unsigned long long>(n), static_cast<unsigned long long>(m), static_cast<int>(n)};
     };
-    for (int32_t q0 = 0; q0 < n_pairs;) {
-        unsigned long long cells = 1, rows = 1; int n_cap = 1;
-        int32_t q1 = q0;
-        unsigned slots = 0;
-        while (q1 < n_pairs) {
-            unsigned long long c, r; int n;
-            dims(q1, &c, &r, &n);
-            const unsigned long long c2 = std::max(cells, c), r2 = std::max(rows, r);
-            const int n2 = std::max(n_cap, n);
-            if (q1 > q0 && (c > cells || r > rows)) {
-                // a pair that enlarges the launch's matrix joins it only while the launch stays within the budget (the slots
-                // of the launch so far bound the grid; a longer y only lowers them)
-                const unsigned long long g = std::min<unsigned long long>(static_cast<unsigned long long>(q1 - q0) + 1, slots);
-                if (g * pw_scratch_bytes(c2, r2) > budget) break;
-            }
-            cells = c2; rows = r2; n_cap = n2; ++q1;
-            if (q1 == q0 + 1) {
-                const size_t lds1 = pw_lds_bytes(n_cap);
-                slots = mode == PS_PW_GLOBAL ? resident_slots(ctx, pw_batch_kernel<false>, PW_NT, lds1) : resident_slots(ctx, pw_batch_kernel<true>, PW_NT, lds1);
-            }
+    auto run = [&](auto kernel) -> int {
+        auto slots = [&](size_t lds) { return resident_slots(ctx, kernel, PW_NT, lds); };
+        ScratchLaunch<PwDims> L;
+        for (int32_t q0 = 0; q0 < n_pairs; q0 = L.q1) {
+            if (next_scratch_launch(q0, n_pairs, budget, dims, slots, &L)) return fail(ctx, PS_ERR_ARG, "pair %d needs more than 32 GiB of scratch", q0);
+            HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(kernel), static_cast<int>(L.lds)));
+            HIP_TRY(ctx, ctx->pw.scratch.reserve(static_cast<size_t>(L.grid) * L.per_wg));
+            if (ctx->debug) fprintf(stderr, "[poreseg] pairwise launch: pairs %d..%d, grid %u, %llu bytes of scratch per workgroup, dynamic LDS %zu\n", L.q0, L.q1, L.grid, L.per_wg, L.lds);
+            hipLaunchKernelGGL(kernel, dim3(L.grid), dim3(PW_NT), L.lds, ctx->stream, P, L.q0, L.q1 - L.q0, L.dims.n_cap, ctx->pw.scratch.as<unsigned char>(),
+                               L.per_wg, L.dims.cells, L.dims.rows);
+            HIP_TRY(ctx, hipGetLastError());
         }
-        const unsigned long long per_wg = pw_scratch_bytes(cells, rows);
-        if (per_wg > (32ull << 30)) return fail(ctx, PS_ERR_ARG, "pair %d needs more than 32 GiB of scratch", q0);
-        const size_t lds = pw_lds_bytes(n_cap);
-        const int nq = q1 - q0;
-        auto launch = [&](auto kernel) -> int {
-            HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(kernel), static_cast<int>(lds)));
-            unsigned grid = std::min<unsigned>(static_cast<unsigned>(nq), resident_slots(ctx, kernel, PW_NT, lds));
-            grid = static_cast<unsigned>(std::max<unsigned long long>(1, std::min<unsigned long long>(grid, budget / per_wg)));
-            HIP_TRY(ctx, ctx->pw.scratch.reserve(static_cast<size_t>(grid) * per_wg));
-            if (ctx->debug) fprintf(stderr, "[poreseg] pairwise launch: pairs %d..%d, grid %u, %llu bytes of scratch per workgroup, dynamic LDS %zu\n", q0, q1, grid, per_wg, lds);
-            hipLaunchKernelGGL(kernel, dim3(grid), dim3(PW_NT), lds, ctx->stream, P, q0, nq, n_cap, ctx->pw.scratch.as<unsigned char>(),
-                               per_wg, cells, rows);
-            return PS_OK;
-        };
-        if (int rc = mode == PS_PW_GLOBAL ? launch(pw_batch_kernel<false>) : launch(pw_batch_kernel<true>)) return rc;
-        HIP_TRY(ctx, hipGetLastError());
-        q0 = q1;
-    }
+        return PS_OK;
+    };
+    if (int rc = mode == PS_PW_GLOBAL ? run(pw_batch_kernel<false>) : run(pw_batch_kernel<true>)) return rc;
     int flag = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&flag, P.flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -3418,11 +3393,10 @@ int ps_trf_split_batch(ps_ctx *ctx, const double *d_mean, const double *d_std, c
     if (n_seq == 0) return PS_OK;
     if (!d_score || !d_len || !d_i || !d_j || !d_count || !d_status) return fail(ctx, PS_ERR_ARG, "null output pointer");
     int64_t n_max = 0;
-    if (int rc = check_offsets(ctx, h_off, n_seq, "sequence", &n_max)) return rc;
+    if (int rc = sequence_offsets(ctx, h_off, n_seq, "sequence", &n_max)) return rc;
     if (n_max > TRF_N_MAX) return fail(ctx, PS_ERR_ARG, "a sequence of %lld segments: the device repeat splitter takes up to %d", (long long)n_max, TRF_N_MAX);
     if (h_off[n_seq] > 0 && (!d_mean || !d_std)) return fail(ctx, PS_ERR_ARG, "null sequence pointer");
-    for (int32_t q = 0; q < n_seq; ++q)
-        if (h_slot_off[q] < 0 || h_slot_off[q + 1] < h_slot_off[q]) return fail(ctx, PS_ERR_ARG, "slot offsets must be non-negative and ascending");
+    if (int rc = slot_offsets(ctx, h_slot_off, n_seq, "slot")) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // one upload: the two 8-byte tables, the capacity flag
     const size_t ns = static_cast<size_t>(n_seq) + 1;
@@ -3436,32 +3410,18 @@ int ps_trf_split_batch(ps_ctx *ctx, const double *d_mean, const double *d_std, c
     P.score = d_score; P.len = d_len; P.i = d_i; P.j = d_j; P.count = d_count; P.status = d_status;
     // Launches: consecutive sequences while the scratch of their launch -- the mask and pointer bits of the launch's longest
     // sequence per workgroup, a workgroup per sequence up to the resident slots -- stays within the budget; a launch whose
-    // first sequence alone leaves room for few workgroups runs on that many
+    // first sequence alone leaves room for few workgroups runs on that many (next_scratch_launch, batch_plan.hpp)
     const unsigned long long budget = static_cast<unsigned long long>(std::max<long long>(1, ctx->trf.budget));
     static_assert(trf_lds_bytes(TRF_N_MAX) <= 64u << 10, "beyond 64 KiB the launch needs hipFuncAttributeMaxDynamicSharedMemorySize (set_dyn_lds)");
-    for (int32_t q0 = 0; q0 < n_seq;) {
-        int n_cap = 1;
-        int32_t q1 = q0;
-        unsigned slots = 0;
-        while (q1 < n_seq) {
-            const int n = static_cast<int>(h_off[q1 + 1] - h_off[q1]);
-            if (q1 > q0 && n > n_cap) {
-                const unsigned long long g = std::min<unsigned long long>(static_cast<unsigned long long>(q1 - q0) + 1, slots);
-                if (g * trf_scratch_bytes(n) > budget) break;
-            }
-            n_cap = std::max(n_cap, n); ++q1;
-            if (q1 == q0 + 1) slots = resident_slots(ctx, trf_kernel, TRF_NT, trf_lds_bytes(n_cap));
-        }
-        const unsigned long long per_wg = trf_scratch_bytes(n_cap);
-        const size_t lds = trf_lds_bytes(n_cap);
-        const int nq = q1 - q0;
-        unsigned grid = std::min<unsigned>(static_cast<unsigned>(nq), resident_slots(ctx, trf_kernel, TRF_NT, lds));
-        grid = static_cast<unsigned>(std::max<unsigned long long>(1, std::min<unsigned long long>(grid, budget / per_wg)));
-        HIP_TRY(ctx, ctx->trf.scratch.reserve(static_cast<size_t>(grid) * per_wg));
-        if (ctx->debug) fprintf(stderr, "[poreseg] trf launch: sequences %d..%d, grid %u, %llu bytes of scratch per workgroup, dynamic LDS %zu\n", q0, q1, grid, per_wg, lds);
-        hipLaunchKernelGGL(trf_kernel, dim3(grid), dim3(TRF_NT), lds, ctx->stream, P, q0, nq, n_cap, ctx->trf.scratch.as<unsigned char>(), per_wg);
+    auto dims = [&](int32_t q) { return TrfDims{static_cast<int>(h_off[q + 1] - h_off[q])}; };
+    auto slots = [&](size_t lds) { return resident_slots(ctx, trf_kernel, TRF_NT, lds); };
+    ScratchLaunch<TrfDims> L;
+    for (int32_t q0 = 0; q0 < n_seq; q0 = L.q1) {
+        next_scratch_launch(q0, n_seq, budget, dims, slots, &L);        // (never refused: 1.6 MB of scratch at TRF_N_MAX)
+        HIP_TRY(ctx, ctx->trf.scratch.reserve(static_cast<size_t>(L.grid) * L.per_wg));
+        if (ctx->debug) fprintf(stderr, "[poreseg] trf launch: sequences %d..%d, grid %u, %llu bytes of scratch per workgroup, dynamic LDS %zu\n", L.q0, L.q1, L.grid, L.per_wg, L.lds);
+        hipLaunchKernelGGL(trf_kernel, dim3(L.grid), dim3(TRF_NT), L.lds, ctx->stream, P, L.q0, L.q1 - L.q0, L.dims.n_cap, ctx->trf.scratch.as<unsigned char>(), L.per_wg);
         HIP_TRY(ctx, hipGetLastError());
-        q0 = q1;
     }
     int flag = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&flag, P.flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
@@ -3649,22 +3609,7 @@ int hmm_upload(ps_ctx *ctx, const ps_hmm_model *m, HmmDevK *D, HmmDevV *V, HmmDe
     return PS_OK;
 }
 
-// The launch plan the sequence-model entry points share.
-
-// q1 of the launch that starts at sequence q0: as many sequences as keep (len + 1) * row_bytes within the budget, at least
-// one; *bytes = what they take
-int32_t next_chunk(const int64_t *h_off, int32_t q0, int32_t n_seq, size_t row_bytes, long long budget, long long *bytes)
-{
-    *bytes = (h_off[q0 + 1] - h_off[q0] + 1) * static_cast<long long>(row_bytes);
-    int32_t q1 = q0 + 1;
-    while (q1 < n_seq) {
-        const long long more = (h_off[q1 + 1] - h_off[q1] + 1) * static_cast<long long>(row_bytes);
-        if (*bytes + more > budget) break;
-        *bytes += more; ++q1;
-    }
-    return q1;
-}
-
+// The launch plan the sequence-model entry points share: next_chunk (batch_plan.hpp) cuts a batch into launches.
 
 // The forward pass of sequences [q0, q1): logp, and the matrix (optional) with sequence q at row off[q] + q - row0 of fmat
 template <typename MD>
@@ -3716,9 +3661,8 @@ int hmm_begin(ps_ctx *ctx, const ps_hmm_model *model, bool host_ok, const double
     if (!model || !h_off || !host_ok) return fail(ctx, PS_ERR_ARG, "null pointer");
     if (n_seq < 0) return fail(ctx, PS_ERR_ARG, "negative sequence count");
     int64_t longest = 0;
-    if (int rc = check_offsets(ctx, h_off, n_seq, "sequence", &longest)) return rc;
-    for (int32_t q = 0; h_path_off && q < n_seq; ++q)
-        if (h_path_off[q] < 0 || h_path_off[q + 1] < h_path_off[q]) return fail(ctx, PS_ERR_ARG, "path offsets must be non-negative and ascending");
+    if (int rc = sequence_offsets(ctx, h_off, n_seq, "sequence", &longest)) return rc;
+    if (h_path_off) if (int rc = slot_offsets(ctx, h_path_off, n_seq, "path")) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (int rc = hmm_upload(ctx, model, C)) return rc;
     if (int rc = own(*C)) return rc;
@@ -3765,11 +3709,6 @@ int hmm_viterbi(ps_ctx *ctx, const MD &D, const double *d_obs, const int64_t *h_
     return PS_OK;
 }
 
-// ps_hmm_expect: LDS bytes at most for the accumulator row beside the two score rows (else the row stays in global memory),
-// and the bytes of all workgroups' rows at most (the grid shrinks to fit)
-constexpr size_t HMM_EXPECT_LDS = 64u << 10;
-constexpr size_t HMM_EXPECT_ROWS = 256u << 20;
-
 template <bool ACC_LDS, typename MD>
 int hmm_expect_run(ps_ctx *ctx, const MD &D, const double *d_obs, const int64_t *h_off, const long long *d_off,
                    int32_t n_seq, int n_acc, int E, double *d_logp, double *d_counts, double *d_stats, int32_t *h_skipped)
@@ -3778,8 +3717,7 @@ int hmm_expect_run(ps_ctx *ctx, const MD &D, const double *d_obs, const int64_t 
     HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_expect_kernel<ACC_LDS, MD>), static_cast<int>(lds)));
     // a grid of resident workgroups (it depends on the device and the model only, never on timing), within the row budget
     const size_t row_bytes = static_cast<size_t>(n_acc) * sizeof(double);
-    unsigned G = std::min<unsigned>(static_cast<unsigned>(n_seq), resident_slots(ctx, (hmm_expect_kernel<ACC_LDS, MD>), HMM_NT, lds));
-    G = static_cast<unsigned>(std::max<size_t>(1, std::min<size_t>(G, HMM_EXPECT_ROWS / row_bytes)));
+    const unsigned G = budget_grid(static_cast<unsigned>(n_seq), resident_slots(ctx, (hmm_expect_kernel<ACC_LDS, MD>), HMM_NT, lds), HMM_EXPECT_ROWS, row_bytes);
     HIP_TRY(ctx, ctx->hmm.acc.reserve(G * row_bytes));
     HIP_TRY(ctx, ctx->hmm.skip.reserve(sizeof(double)));
     HIP_TRY(ctx, hipMemsetAsync(ctx->hmm.acc.p, 0, G * row_bytes, ctx->stream));
@@ -3941,9 +3879,8 @@ int ps_hmm_sample(ps_ctx *ctx, const ps_hmm_model *model, const ps_hmm_sample_ta
     if ((d_path != nullptr) != (h_path_off != nullptr)) return fail(ctx, PS_ERR_ARG, "a path buffer and its offsets go together");
     if (want_path && n_seq > 0 && !d_path_len) return fail(ctx, PS_ERR_ARG, "paths need the length array");
     int64_t longest = 0;
-    if (int rc = check_offsets(ctx, h_off, n_seq, "observation slot", &longest)) return rc;
-    for (int32_t q = 0; want_path && q < n_seq; ++q)
-        if (h_path_off[q] < 0 || h_path_off[q + 1] < h_path_off[q]) return fail(ctx, PS_ERR_ARG, "path offsets must be non-negative and ascending");
+    if (int rc = sequence_offsets(ctx, h_off, n_seq, "observation slot", &longest)) return rc;
+    if (want_path) if (int rc = slot_offsets(ctx, h_path_off, n_seq, "path")) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HmmCall C;
     if (int rc = hmm_upload(ctx, model, &C)) return rc;
@@ -4042,19 +3979,11 @@ int sp_upload(ps_ctx *ctx, DevBuf &buf, std::vector<int64_t> &tab, const int64_t
               SpEvents *ev, int64_t *n_tiles)
 {
     const size_t n = static_cast<size_t>(n_ev);
-    tab.assign(3 * n + 1, 0);
-    int64_t tiles = 0;
-    for (size_t e = 0; e < n; ++e) {
-        tab[e] = start[e]; tab[n + e] = npos[e]; tab[2 * n + e] = tiles;
-        tiles += (npos[e] + SP_TILE - 1) / SP_TILE;
-    }
-    tab[3 * n] = tiles;
-    if (tiles > INT32_MAX) return fail(ctx, PS_ERR_ARG, "too many samples for one call");
+    if (plan_tile_table(start, npos, n_ev, &tab, n_tiles)) return fail(ctx, PS_ERR_ARG, "too many samples for one call");
     HIP_TRY(ctx, buf.reserve(tab.size() * sizeof(int64_t)));
     HIP_TRY(ctx, hipMemcpyAsync(buf.p, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     const int64_t *t = buf.as<int64_t>();
     ev->start = t; ev->npos = t + n; ev->tile_off = t + 2 * n; ev->n_ev = n_ev;
-    *n_tiles = tiles;
     return PS_OK;
 }
 
@@ -4101,31 +4030,16 @@ int sp_args(ps_ctx *ctx, const double *d_current, const int64_t *h_ev_start, con
     if (!h_ev_start || !h_ev_len || !h_span_off || n_ev < 0 || cap < 0 || (cap > 0 && !d_spans))
         return fail(ctx, PS_ERR_ARG, "null/negative argument");
     int64_t total = 0;
-    for (int e = 0; e < n_ev; ++e) {
-        const int64_t len = h_ev_len[e];
-        if (len < 0 || h_ev_start[e] < 0) return fail(ctx, PS_ERR_ARG, "event %d: negative start or length", e);
-        if (len > (1ll << 30))
-            return fail(ctx, PS_ERR_ARG, "event %d length %lld out of range (2^30 samples at most)", e, static_cast<long long>(len));
-        if (len < min_len)
-            return fail(ctx, PS_ERR_ARG, "event %d: the length of the input must be greater than padlen, which is %d", e, FILT_PAD);
-        total += len;
+    int32_t bad = -1;
+    switch (check_events(h_ev_start, h_ev_len, n_ev, nullptr, nullptr, min_len, &total, &bad)) {
+    case BATCH_PLAN_OK: break;
+    case BATCH_PLAN_NEGATIVE: return fail(ctx, PS_ERR_ARG, "event %d: negative start or length", bad);
+    case BATCH_PLAN_LONG:
+        return fail(ctx, PS_ERR_ARG, "event %d length %lld out of range (2^30 samples at most)", bad, static_cast<long long>(h_ev_len[bad]));
+    default: return fail(ctx, PS_ERR_ARG, "event %d: the length of the input must be greater than padlen, which is %d", bad, FILT_PAD);
     }
     for (int e = 0; e <= n_ev; ++e) h_span_off[e] = 0;
     if (total > 0 && !d_current) return fail(ctx, PS_ERR_ARG, "d_current is NULL");
-    return PS_OK;
-}
-
-// The spans per event are known: h_span_off from the counts, the capacity check, the offsets on the device.
-int sp_span_offsets(ps_ctx *ctx, const std::vector<int64_t> &n_spans, int64_t cap, int64_t *h_span_off)
-{
-    const size_t n = n_spans.size();
-    for (size_t e = 0; e < n; ++e) h_span_off[e + 1] = h_span_off[e] + n_spans[e];
-    const int64_t total = h_span_off[n];
-    if (total > cap)
-        return fail(ctx, PS_ERR_CAPACITY, "span capacity %lld < required %lld", static_cast<long long>(cap), static_cast<long long>(total));
-    if (total == 0) return PS_OK;
-    HIP_TRY(ctx, ctx->sp.span_off.reserve((n + 1) * sizeof(int64_t)));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->sp.span_off.p, h_span_off, (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     return PS_OK;
 }
 
@@ -4150,7 +4064,7 @@ int ps_snakebase_f64(ps_ctx *ctx, const double *d_current, const int64_t *h_ev_s
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     std::vector<int64_t> n_spans(n);
     for (size_t e = 0; e < n; ++e) n_spans[e] = (hit_off[e + 1] - hit_off[e] + 1) / 2;
-    if (int rc = sp_span_offsets(ctx, n_spans, cap, h_span_off)) return rc;
+    if (int rc = offsets_to_device(ctx, ctx->sp.span_off, n_spans.data(), n, cap, "span", h_span_off)) return rc;
     const int64_t total = h_span_off[n_ev];
     if (total == 0) return PS_OK;
     if (int rc = sp_scatter(ctx, ev, n_tiles, hit_off[n], 0, ctx->sp.hits)) return rc;
@@ -4231,7 +4145,7 @@ int ps_filter_derivative_f64(ps_ctx *ctx, const double *d_current, const int64_t
     // 4. the spans [0, s_1), [t_1, s_2), ..., [t_k, n): one more than the kept pairs (an empty event has none)
     std::vector<int64_t> n_spans(n);
     for (size_t e = 0; e < n; ++e) n_spans[e] = h_ev_len[e] > 0 ? kept_off[e + 1] - kept_off[e] + 1 : 0;
-    if (int rc = sp_span_offsets(ctx, n_spans, cap, h_span_off)) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    if (int rc = offsets_to_device(ctx, ctx->sp.span_off, n_spans.data(), n, cap, "span", h_span_off)) { (void)hipStreamSynchronize(ctx->stream); return rc; }
     const int64_t total = h_span_off[n_ev];
     if (total == 0) { HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); return PS_OK; }
     if (int rc = sp_scatter(ctx, ev2, n_tiles2, kept_off[n], 0, ctx->sp.kept)) return rc;

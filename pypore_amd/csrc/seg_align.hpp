@@ -17,11 +17,10 @@
 // build has none).
 #pragma once
 
+#include "batch_plan.hpp"                       // ALIGN_NT, ALIGN_M_MAX, ALIGN_B_MAX, align_lds_doubles
+
 namespace ps {
 
-constexpr int ALIGN_NT = 64;
-constexpr int ALIGN_M_MAX = 1024;               // model segments (LDS: 13+ rows of m doubles)
-constexpr int ALIGN_B_MAX = 32;                 // rows per traceback block
 constexpr double ALIGN_NEGINF = -99999999.0;    // calignment.pyx:38
 
 // per-sequence status: what the compiled reference does on the same input (include/poreseg.h)
@@ -51,10 +50,6 @@ __device__ __forceinline__ void al_sync()
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();
 }
-
-// LDS (doubles): 5 model rows, 2 score rows, skip, back | traceback block: (B+1) score rows, B skip rows, B back rows
-// | 3 x 64 sequence values | 2 dummy cells
-__host__ __device__ inline size_t align_lds_doubles(int m, int B) { return static_cast<size_t>(9 + 3 * B + 1) * m + 3 * 64 + 2; }
 
 __global__ __launch_bounds__(ALIGN_NT) void align_kernel(AlignModel M, const double *seq_mean, const double *seq_std,
                                                          const double *seq_dur, const long long *seq_off, int n_seq,

@@ -20,9 +20,10 @@
 // kernel walks them back with one lane per sequence.  fp64 throughout, no FMA contraction.
 #pragma once
 
+#include "batch_plan.hpp"                  // HMM_NT
+
 namespace ps {
 
-constexpr int HMM_NT = 64;                 // one wave per workgroup
 constexpr int HMM_S_MAX = 4096;            // states: two fp64 rows of S in LDS = 64 KiB at most
 constexpr int HMM_VITERBI = 0, HMM_FORWARD = 1, HMM_BACKWARD = 2;   // include/poreseg.h PS_HMM_*
 constexpr int HMM_SILENT = 0, HMM_NORMAL = 1, HMM_UNIFORM = 2, HMM_KDE = 3;   // include/poreseg.h ps_hmm_model.kind

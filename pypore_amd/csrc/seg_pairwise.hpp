@@ -15,21 +15,13 @@
 // over the row maxima and refreshes only the rows a walk touched.  fp64 throughout, no FMA contraction.
 #pragma once
 
+#include "batch_plan.hpp"                       // PW_NT, PW_N_MAX, pw_lds_bytes, pw_scratch_bytes
+
 namespace ps {
 
-constexpr int PW_NT = 64;
-constexpr int PW_N_MAX = 8190;                  // y elements (LDS: y and the border row, 16 bytes per element)
 constexpr double PW_NEGINF = -999999999.0;      // alignment.py NEGINF: the mark of a walked cell
 constexpr int PW_GLOBAL = 0, PW_LOCAL = 1, PW_REPEATED = 2;
 constexpr int PW_OK = 0, PW_INDEX = 1;          // per-pair status (include/poreseg.h)
-
-__host__ __device__ inline size_t pw_lds_bytes(int n_cap) { return (2 * static_cast<size_t>(n_cap) + 2) * sizeof(double); }
-
-// bytes of scratch per workgroup: scores, row maxima (8-byte entries first), first columns, pointer bytes
-__host__ __device__ inline unsigned long long pw_scratch_bytes(unsigned long long cells, unsigned long long rows)
-{
-    return (8ull * cells + 8ull * rows + 4ull * rows + cells + 15ull) & ~15ull;
-}
 
 // _score (alignment.py:112-115): 0 for the gap marker (uploaded as NaN), else 3 - |x - y|^2 with the square by product
 __device__ __forceinline__ double pw_match(double x, double y)

@@ -24,11 +24,10 @@
 #include <cmath>
 #include <cstdint>
 
+#include "batch_plan.hpp"                          // SP_NT, SP_ROUNDS, SP_TILE
+
 namespace ps {
 
-constexpr int SP_NT = 256;                         // threads of a compaction workgroup
-constexpr int SP_ROUNDS = 8;                       // positions per thread
-constexpr int SP_TILE = SP_NT * SP_ROUNDS;         // positions per tile (2 048)
 constexpr int SP_WORDS = SP_TILE / 64;             // mask words per tile
 
 // The compaction's view of a call (device copies, int64 each): event e has npos[e] positions, its data starts at

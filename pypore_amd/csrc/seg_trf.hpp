@@ -21,21 +21,11 @@
 // fp64 throughout, no FMA contraction, IEEE division.
 #pragma once
 
+#include "batch_plan.hpp"                       // TRF_NT, TRF_N_MAX, trf_lds_bytes, trf_row_words, trf_scratch_bytes
+
 namespace ps {
 
-constexpr int TRF_NT = 64;
-constexpr int TRF_N_MAX = 2048;                 // segments per sequence (LDS: 24 bytes per segment; scratch: 1.6 MB at the cap)
 constexpr int TRF_DONE = 0, TRF_MAX_REPEATS = 1;    // per-sequence status (include/poreseg.h)
-
-__host__ __device__ constexpr size_t trf_lds_bytes(int n_cap) { return (3 * static_cast<size_t>(n_cap) + 1) * sizeof(double); }
-// 64-bit words per row of the mask in skewed coordinates (steps of a stripe: at most n + 63); the pointers take twice that
-__host__ __device__ inline unsigned long long trf_row_words(int n_cap) { return (static_cast<unsigned long long>(n_cap) + 127ull) / 64ull; }
-// bytes of scratch per workgroup: mask rows 0 .. n_cap, pointer rows 1 .. n_cap
-__host__ __device__ inline unsigned long long trf_scratch_bytes(int n_cap)
-{
-    const unsigned long long w = trf_row_words(n_cap), n = static_cast<unsigned long long>(n_cap);
-    return 8ull * w * (n + 1ull) + 16ull * w * n;
-}
 
 // _score (alignment.py:812): 2 - |x.mean - y.mean| ** 2 / (x.std * y.std), the square by product
 __device__ __forceinline__ double trf_match(double mi, double si, double mj, double sj)
