@@ -441,6 +441,21 @@ int ps_filter_requantise_batch(ps_ctx *ctx, const void *d_samples, const ps_samp
                                const int64_t *ev_len, int32_t n_ev, int32_t order, double cutoff, double sampling_freq,
                                double *d_filtered, float *d_rounded, double *h_centre, double *h_step);
 
+/* Segment.mean / std / min / max (core.py:209-223, std = population) of caller-given ranges of one device buffer: range r is
+ * samples [h_start[r], h_end[r]) of d_samples (n samples; int16 counts or float32 on the grid -- PS_DTYPE_F64 is PS_ERR_ARG),
+ * its row goes to d_stats[r] (device).  The ranges may overlap, repeat, touch the buffer's two ends and come in any order: the
+ * merged segments of HMM-guided segmentation (DataTypes.py:292-330) are such ranges.  Two launches whatever n_ranges is: every
+ * range is cut into units of at most "range_tile" samples (context option, 64 .. 2^20, default 16 384; float32 units are at most
+ * 2^14 samples), one workgroup per unit leaves exact integer sums of y = count - k0 and y^2 (k0: the count of the range's first
+ * sample), then one lane per range adds them in unit order: mean = (k0 + S1 / n) q, std = sqrt(max(0, S2 / n - (S1 / n)^2)) q,
+ * min and max from the integers, no multiply-add fused.  int16: S1 and S2 are exact in int64, S2 is rounded to double once;
+ * float32: exact while S2 stays below 2^53.  The same ranges give the same bits however range_tile cuts them.
+ * n_ranges == 0 returns PS_OK and launches nothing.  PS_ERR_ARG, with the first offending index in ps_last_error and nothing
+ * launched: start < 0, end > n, end <= start, a range of more than 2^31 - 1 samples; also more than 2^24 - 1 units in one call.
+ * One status word and one host synchronisation per call; the scratch (tables, partial rows) belongs to the context. */
+int ps_range_stats(ps_ctx *ctx, const void *d_samples, const ps_sample_format *fmt, int64_t n, const int64_t *h_start,
+                   const int64_t *h_end, int64_t n_ranges, ps_segstat *d_stats);
+
 /* Replaces cSegmentAligner(model_means, model_stds, model_durs, skip_penalty, backslip_penalty).align(seq_means,
  * seq_stds, seq_durs) (calignment.pyx:20-100; called from SegmentAligner.align, alignment.py:33-46) for a BATCH of
  * sequences against one model: sequence q is entries [h_seq_off[q], h_seq_off[q+1]) of the three device arrays

@@ -365,6 +365,154 @@ def filter_events(events, order=1, cutoff=2000.):
         finish([(ev, o) for ev, _, o in members], y, offsets)
 
 
+def state_name_ids(states):
+    """(ids, names) of a model's states: ids[k] = the index into `names` of states[k].name, so equal names share an id (the
+    reference's merge compares path entries by state NAME: two states that share one do not end a group)."""
+    seen, ids = {}, np.empty(len(states), dtype=np.int64)
+    for k, state in enumerate(states):
+        ids[k] = seen.setdefault(state.name, len(seen))
+    return ids, list(seen)
+
+
+def merge_ranges(seg_start, seg_n, path, name_ids, second):
+    """The reference's HMM-guided merge (DataTypes.py:292-330; Event._merge_by_hmm restates it as a loop) for one event, in
+    numpy and without a loop over the segments.  seg_start: the segments' starts in SECONDS, seg_n: their sample counts, path:
+    the Viterbi path as state indices (start state first, silent states included: at least as many entries as segments),
+    name_ids: state index -> name id (state_name_ids).  Returns (s, e, hidden) int64 arrays, one entry per merged segment:
+    first and end sample in the event, name id of its hidden state.  Quirks kept: entry i is compared with entry i + 1 by name;
+    after a group closes j = i, so consecutive merged segments share their boundary segment and overlap; the last group
+    closes at i == n - 2 and ends with the last segment; the hidden state is entry j + 1's; fewer than two segments give
+    nothing; s = int(start_j * second) and e = int(start_r * second + n_r) are these two float64 expressions, truncated --
+    (a / second) * second falls just below a for about 8 % of the sample indices, and then s = a - 1."""
+    n = len(seg_n)
+    none = np.zeros(0, dtype=np.int64)
+    if n < 2:
+        return none, none, none
+    start = np.asarray(seg_start, dtype=np.float64)
+    count = np.asarray(seg_n).astype(np.float64)
+    nid = np.asarray(name_ids, dtype=np.int64)[np.asarray(path, dtype=np.int64)[:n]]
+    close = nid[:n - 2] != nid[1:n - 1]                      # i = 0 .. n - 3: path entry i against entry i + 1
+    i = np.concatenate((np.flatnonzero(close), [n - 2]))     # ... and i = n - 2 always closes
+    j = np.concatenate(([0], i[:-1]))
+    r = i.copy()
+    r[-1] = n - 1                                            # (i < n - 2: segments[i]; the last group: segments[-1])
+    second = float(second)
+    s = np.trunc(start[j] * second).astype(np.int64)
+    e = np.trunc(start[r] * second + count[r]).astype(np.int64)
+    return s, e, nid[j + 1]
+
+
+def _viterbi_paths(events, hmm, features):
+    """[path or None per event] from ONE hmm.viterbi_batch call when the object has one, else hmm.viterbi per event."""
+    obs = [_observations(ev, hmm, features) for ev in events]
+    batch = getattr(hmm, "viterbi_batch", None)
+    results = batch(obs) if callable(batch) else [hmm.viterbi(o) for o in obs]
+    return [path for _, path in results]
+
+
+def merge_by_hmm(events, hmm, features=None):
+    """`ev.segments = ev._merge_by_hmm(hmm, features)` for every Event of `events` (HMM-guided segmentation, DataTypes.py:
+    292-330, of events that are segmented already), in as few device calls as their currents allow:
+      * one hmm.viterbi_batch call for all events (a pypore_amd.hmm.Model: one launch); an object with `viterbi` only is
+        called per event, duck-typed as Event.parse takes it;
+      * the merge itself in numpy (merge_ranges);
+      * unfiltered events that are stretches of one file tensor (the grouping of filter_events) take their merged segments'
+        mean / std / min / max from ONE engine.Context.range_stats call per file tensor: a merged Segment holds the same
+        deferred stretch of the file's counts that parse_events' segments hold, and the file's float64 current is not written
+        out.  Filtered events and events whose current is a host array keep what Event.parse does: a view of ev.current, lazy
+        numpy statistics.
+    Every merged segment has start (in samples, as the reference leaves it), event, second and hidden_state as _merge_by_hmm
+    sets them.  Raised before any event is changed: TypeError for a MetaEvent and for an hmm without `viterbi`; ValueError,
+    naming the event's index, for an event of two or more segments that the model gives probability zero."""
+    if not hmm or not callable(getattr(hmm, "viterbi", None)):
+        raise TypeError("hmm must be a pypore_amd.hmm.Model or have a viterbi method")
+    events = list(events)
+    for ev in events:
+        if type(ev) is not Event:
+            raise TypeError("Cannot merge the segments of a metaevent. Must have the current.")
+    paths = _viterbi_paths(events, hmm, features)
+    for k, (ev, path) in enumerate(zip(events, paths)):
+        if path is None and len(ev.segments) >= 2:
+            raise ValueError("event %d: the HMM gives the segment means probability zero: there is no Viterbi path to merge by" % k)
+    states = getattr(hmm, "states", None)
+    if states is not None:
+        ids, names = state_name_ids(states)
+    else:
+        ids, names, seen = None, [], {}                  # (a model that shows no state list: the names the paths hold)
+    merged = []
+    for ev, path in zip(events, paths):
+        n = len(ev.segments)
+        if n < 2:
+            merged.append(merge_ranges((), (), (), (), ev.second))
+            continue
+        if ids is not None:
+            idx, table = [entry[0] for entry in path[:n]], ids
+        else:
+            idx = [seen.setdefault(entry[1].name, len(seen)) for entry in path[:n]]
+            table = np.arange(len(seen), dtype=np.int64)
+        merged.append(merge_ranges([seg.start for seg in ev.segments], [seg.n for seg in ev.segments], idx, table, ev.second))
+    if ids is None:
+        names = list(seen)
+    # the events whose counts are parked on the device as stretches of one tensor: one range_stats call per tensor
+    rows = [None] * len(events)
+    stretched = {}
+    if any(len(m[0]) for m in merged):
+        stretched = _device_stretches([(k, ev) for k, ev in enumerate(events) if len(merged[k][0]) and not ev.__dict__.get("filtered")])
+    for (_, quantum, offset), group in stretched.items():
+        base, members = group[0], group[1:]
+        lo = np.concatenate([a0 + np.clip(merged[k][0], 0, n0) for k, a0, n0 in members])
+        hi = np.concatenate([a0 + np.clip(merged[k][1], 0, n0) for k, a0, n0 in members])
+        ok = hi > lo                                         # (an empty slice has no statistics: numpy's nan, as in the loop)
+        from . import engine
+        stats = engine.context(base.device.index).range_stats(base, lo[ok], hi[ok], quantum)
+        if offset:
+            stats[:, [0, 2, 3]] += offset
+        at = np.concatenate(([0], np.cumsum(ok)))
+        pos = 0
+        for k, _, _ in members:
+            m = len(merged[k][0])
+            rows[k] = [stats[at[pos + q]] if ok[pos + q] else None for q in range(m)]
+            pos += m
+    with gc_paused():
+        for k, ev in enumerate(events):
+            s, e, hid = merged[k]
+            # (an event that ends with no segments is not asked for its current: that would write a file's out)
+            cur = None if not len(s) else raw_current(ev) if rows[k] is not None else ev.current
+            out = []
+            for q in range(len(s)):
+                seg = Segment(start=int(s[q]), current=cur[int(s[q]):int(e[q])], event=ev, second=ev.second, hidden_state=names[hid[q]])
+                if rows[k] is not None and rows[k][q] is not None:
+                    seg.__dict__['_gpu_stats'] = rows[k][q]
+                out.append(seg)
+            ev.segments = out
+
+
+def _device_stretches(members):
+    """{(base tensor's address, quantum, offset): [base tensor, (key, first sample, length) ...]} for the (key, event) pairs
+    whose current is a stretch of a file's counts parked on the current device -- the grouping of filter_events; the pairs
+    whose current is anything else are left out."""
+    import torch
+    from . import engine
+    from .grid import grid_of
+    out = {}
+    dev = None
+    for key, ev in members:
+        cur = raw_current(ev)
+        stretch = getattr(cur, "device_stretch", None)
+        if stretch is None or getattr(cur, "counts", None) is None:
+            continue
+        g = grid_of(cur)
+        if g is None:
+            continue
+        if dev is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        where = stretch(dev, engine._int_counts_tensor)
+        if where is not None:
+            base, a0, n0 = where
+            out.setdefault((base.data_ptr(), float(g[1]), float(g[2])), [base]).append((key, a0, n0))
+    return out
+
+
 def _segment_filtered(events, parser):
     """Segments of already-filtered events (float64 currents on no ADC grid) with `parser`, in event order.  Every current
     is centred and rounded onto a fine grid (Event._on_fine_grid), and the events that share a grid step are segmented
@@ -448,16 +596,26 @@ class File(Segment):
         filtered currents of a file's events without segmenting them, in one call per file tensor."""
         filter_events(self.events, order=order, cutoff=cutoff)
 
-    def parse_events(self, parser=None, filter_params=None):
+    def parse_events(self, parser=None, filter_params=None, hmm=None, features=None):
         """The inner loop of Experiment.parse (DataTypes.py:975-984) for this file: every event is filtered when
         `filter_params` = (order, cutoff) is given, then all events are segmented in as few device calls as their
         representations allow -- one for unfiltered events, one per grid step for filtered ones (events of one file span
         similar ranges and mostly share a step).  Same result as `event.filter(...); event.parse(parser)` per event.
         With a SpeedyStatSplit the filtered currents never leave the device between the two steps
         (parse_filtered_batch: filter, re-quantisation and segmentation on the device, one copy of the float64 result
-        back for Event.current)."""
+        back for Event.current).
+
+        hmm (HMM-guided segmentation, as Event.parse(parser, hmm=model)): after the segmentation the segment means of ALL events
+        go through the model in one viterbi_batch call and runs of segments in one hidden state are merged (merge_by_hmm; the
+        statistics of the merged segments of unfiltered events come from one device call, the file's current stays unwritten).
+        features: the segment attributes a vector model is handed instead of the means.  Same result as
+        `event.parse(parser, hmm=hmm, features=features)` per event."""
+        if hmm and not callable(getattr(hmm, "viterbi", None)):
+            raise TypeError("hmm must be a pypore_amd.hmm.Model or have a viterbi method")
         with gc_paused():                                # (one pause for the file: re-enabling after every event costs a
             self._parse_events(parser, filter_params)    #  collection each time, 0.5 ms x the number of events)
+            if hmm:
+                merge_by_hmm(self.events, hmm, features)
 
     def _parse_events(self, parser, filter_params):
         if parser is None:
@@ -589,10 +747,12 @@ class Experiment(object):
 
     _DEFAULT = object()
 
-    def parse(self, event_detector=None, segmenter=_DEFAULT, filter_params=(1, 2000), verbose=True, meta=False, workers=None):
+    def parse(self, event_detector=None, segmenter=_DEFAULT, filter_params=(1, 2000), verbose=True, meta=False, workers=None,
+              hmm=None, features=None):
         """Defaults as in the reference (:956-960): lambda_event_parser(threshold=90), SpeedyStatSplit with
         prior_segments_per_second=10 and cutoff_freq=2000, a first-order 2 kHz Bessel filter.  segmenter=None: events
         are detected (and filtered) only; filter_params=None: no filter; meta=True: the currents are dropped afterwards.
+        hmm, features: HMM-guided segmentation of every file's events (File.parse_events); ignored without a segmenter.
 
         The reference takes one file after the other (:968-984).  Files are independent, so here up to `workers` of them
         are in flight (default: 2 when detector and segmenter are this package's own device classes, else 1): while file
@@ -618,7 +778,7 @@ class Experiment(object):
             file.parse(parser=event_detector)
             say("\tDetected {} Events".format(file.n))
             if segmenter is not None:
-                file.parse_events(segmenter, filter_params)
+                file.parse_events(segmenter, filter_params, hmm=hmm, features=features)
                 for i, event in enumerate(file.events):
                     say("\t\tEvent {} has {} segments".format(i + 1, event.n))
             elif filter_params is not None:

@@ -18,7 +18,7 @@ PS_ALIGN_OK, PS_ALIGN_VALUE_ERROR, PS_ALIGN_INDEX_ERROR, PS_ALIGN_ZERO_DIVISION,
 EXPORTS = ["ps_version", "ps_device_count", "ps_create", "ps_destroy", "ps_last_error", "ps_set_tiling", "ps_set_option",
            "ps_synchronize", "ps_min_gain", "ps_segment_batch", "ps_segment_batch_ex", "ps_segment_events", "ps_segment_exact_f64", "ps_detect_events", "ps_detect_segment_trace", "ps_bounds_capacity",
            "ps_best_single_split", "ps_score_window", "ps_get_timings", "ps_synth_trace", "ps_filter_bessel",
-           "ps_requantise", "ps_grid_check_f64", "ps_grid_counts_f64", "ps_narrow_f64", "ps_filter_requantise_batch", "ps_filter_bessel_batch", "ps_align_batch", "ps_audit_bounds", "ps_counters",
+           "ps_requantise", "ps_grid_check_f64", "ps_grid_counts_f64", "ps_narrow_f64", "ps_filter_requantise_batch", "ps_filter_bessel_batch", "ps_range_stats", "ps_align_batch", "ps_audit_bounds", "ps_counters",
            "ps_get_near_ties", "ps_hmm_batch", "ps_hmm_expect", "ps_hmm_posterior", "ps_hmm_sample", "ps_pairwise_scores", "ps_pairwise_batch",
            "ps_statsplit_f64", "ps_statsplit_prefix_f64", "ps_snakebase_f64", "ps_filter_derivative_f64", "ps_live_bytes", "ps_trf_split_batch",
            "ps_pool_plan", "ps_hw_queues", "ps_gate_stats", "ps_get_option"]
@@ -140,6 +140,7 @@ def lib():
     L.ps_filter_requantise_batch.argtypes = [vp, vp, P(SampleFormat), P(i64), P(i64), ctypes.c_int32, ctypes.c_int32, dbl, dbl,
                                              vp, vp, P(dbl), P(dbl)]
     L.ps_filter_bessel_batch.argtypes = [vp, vp, P(SampleFormat), P(i64), P(i64), ctypes.c_int32, ctypes.c_int32, dbl, dbl, vp]
+    L.ps_range_stats.argtypes = [vp, vp, P(SampleFormat), i64, P(i64), P(i64), i64, vp]
     L.ps_align_batch.argtypes = [vp, P(dbl), P(dbl), P(dbl), i32, dbl, dbl, vp, vp, vp, P(i64), i32, vp, vp, vp]
     L.ps_counters.argtypes = [vp]
     L.ps_counters.restype = P(i64)

@@ -47,6 +47,7 @@
 #include "seg_ingest.hpp"
 #include "seg_statsplit.hpp"
 #include "seg_state.hpp"
+#include "seg_ranges.hpp"
 #include "pool_plan.hpp"
 #include "seg_plan.hpp"
 #include "filt_plan.hpp"
@@ -210,6 +211,10 @@ struct ps_ctx {
         int fused = 1;        // option filter_fused 1: fast filters run both directions in one kernel over tiles with halos, 0: always the exact three-pass scan
         long long batch_scratch = FILT_BATCH_SCRATCH_DEFAULT;   // option filt_batch_scratch: bytes of order-n scratch rows per launch of a batch
     } filt;
+    struct {                  // statistics of caller-given ranges (ps_range_stats): the range and unit tables (range_plan.hpp), a RangePart per unit
+        DevBuf tab, part;
+        long long tile = RANGE_TILE_DEFAULT;     // option range_tile: samples per unit at most
+    } rng;
     struct { DevBuf in, scratch; } align;    // profile aligner (ps_align_batch)
     struct {                  // pairwise aligner (ps_pairwise_scores / ps_pairwise_batch): offsets and pair tables, per-workgroup matrices
         DevBuf in, scratch;
@@ -1871,6 +1876,7 @@ int ps_set_option(ps_ctx *ctx, const char *name, int64_t value)
     else if (n == "tree_tail_pct" && value >= 0 && value <= 100) ctx->tree_tail_pct = static_cast<int>(value);
     else if (n == "filter_fused") ctx->filt.fused = value != 0;
     else if (n == "filt_batch_scratch" && value >= 1) ctx->filt.batch_scratch = value;
+    else if (n == "range_tile" && range_tile_ok(value)) ctx->rng.tile = value;
     else if (n == "upload_by_kernel") ctx->upload_by_kernel = value != 0;
     else if (n == "timing") ctx->timing = static_cast<int>(std::max<int64_t>(0, std::min<int64_t>(2, value)));
     else if (n == "tree_mw") ctx->tree_mw = value != 0;
@@ -1890,6 +1896,7 @@ int ps_get_option(const ps_ctx *ctx, const char *name, int64_t *value)
     else if (n == "shared_device") *value = ctx->shared_n;
     else if (n == "hw_queues") *value = ctx->hw_queues;
     else if (n == "filt_batch_scratch") *value = ctx->filt.batch_scratch;
+    else if (n == "range_tile") *value = ctx->rng.tile;
     else return PS_ERR_ARG;
     return PS_OK;
 }
@@ -3135,6 +3142,53 @@ int ps_filter_bessel_batch(ps_ctx *ctx, const void *d_samples, const ps_sample_f
     if (int rc = filter_batch_queue(ctx, d_samples, fmt, ev_start, ev_len, n_ev, order, cutoff, sampling_freq, d_out)) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(ctx->h_small.p, ctx->small.p, sizeof(SmallLayout), hipMemcpyDeviceToHost, ctx->stream));
     // (the context's stream does not block on torch's: the caller may read d_out, or free d_samples, as soon as this returns)
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return check_status(ctx, static_cast<unsigned>(ctx->h_small.as<SmallLayout>()->status));
+}
+
+int ps_range_stats(ps_ctx *ctx, const void *d_samples, const ps_sample_format *fmt, int64_t n, const int64_t *h_start, const int64_t *h_end,
+                   int64_t n_ranges, ps_segstat *d_stats)
+{
+    if (!ctx) return PS_ERR_ARG;
+    if (n_ranges < 0 || n < 0) return fail(ctx, PS_ERR_ARG, "null pointer or negative count");
+    if (n_ranges == 0) return PS_OK;
+    if (!d_samples || !fmt || !h_start || !h_end || !d_stats) return fail(ctx, PS_ERR_ARG, "null pointer or negative count");
+    if (fmt->dtype == PS_DTYPE_F64)
+        return fail(ctx, PS_ERR_ARG, "range statistics take int16 counts or float32 samples on a grid, not float64");
+    if (fmt->dtype != PS_DTYPE_F32 && fmt->dtype != PS_DTYPE_I16) return fail(ctx, PS_ERR_ARG, "unknown dtype %d", fmt->dtype);
+    // validated and planned (range_plan.hpp) before anything is reserved or queued
+    RangePlan plan;
+    int64_t bad = -1;
+    switch (plan_ranges(h_start, h_end, n_ranges, n, range_unit(fmt->dtype == PS_DTYPE_F32, ctx->rng.tile), &plan, &bad)) {
+    case RANGE_PLAN_OK: break;
+    case RANGE_PLAN_START: return fail(ctx, PS_ERR_ARG, "range %lld: negative start", static_cast<long long>(bad));
+    case RANGE_PLAN_END: return fail(ctx, PS_ERR_ARG, "range %lld: ends behind the %lld samples", static_cast<long long>(bad), static_cast<long long>(n));
+    case RANGE_PLAN_EMPTY: return fail(ctx, PS_ERR_ARG, "range %lld: empty (end <= start)", static_cast<long long>(bad));
+    case RANGE_PLAN_LONG: return fail(ctx, PS_ERR_ARG, "range %lld: longer than 2^31 - 1 samples", static_cast<long long>(bad));
+    default: return fail(ctx, PS_ERR_ARG, "too many ranges or units for one call (option range_tile: %lld)", ctx->rng.tile);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    DevCfg cfg;
+    if (int rc = make_cfg(ctx, d_samples, fmt, 1, 1, 2, 0.0, &cfg)) return rc;
+    const size_t b_row = plan.row.size() * sizeof(RangeRow), n_unit = plan.unit.size();
+    HIP_TRY(ctx, ctx->h_small.reserve(sizeof(SmallLayout)));
+    HIP_TRY(ctx, ctx->rng.part.reserve(n_unit * sizeof(RangePart)));
+    if (int rc = upload_tables(ctx, ctx->rng.tab, {{plan.row.data(), b_row}, {plan.unit.data(), n_unit * sizeof(RangeUnit)}})) return rc;
+    const RangeRow *d_row = ctx->rng.tab.as<RangeRow>();
+    const RangeUnit *d_unit = reinterpret_cast<const RangeUnit *>(ctx->rng.tab.as<char>() + b_row);
+    RangePart *d_part = ctx->rng.part.as<RangePart>();
+    HIP_TRY(ctx, hipMemsetAsync(ctx->small.p, 0, sizeof(SmallLayout), ctx->stream));
+    unsigned *st = reinterpret_cast<unsigned *>(&ctx->small.as<SmallLayout>()->status);
+    const int32_t nr = static_cast<int32_t>(n_ranges);
+    by_dtype(cfg.dtype, [&](auto dt) {
+        hipLaunchKernelGGL((range_part_kernel<dt()>), dim3(static_cast<unsigned>(n_unit)), dim3(RANGE_NT), 0, ctx->stream, cfg, d_row, d_unit, d_part, st);
+        hipLaunchKernelGGL((range_final_kernel<dt()>), dim3(static_cast<unsigned>((n_ranges + RANGE_NT - 1) / RANGE_NT)), dim3(RANGE_NT), 0, ctx->stream,
+                           cfg, d_row, nr, static_cast<const RangePart *>(d_part), d_stats);
+        return 0;
+    });
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_small.p, ctx->small.p, sizeof(SmallLayout), hipMemcpyDeviceToHost, ctx->stream));
+    // (the context's stream does not block on torch's: the caller may read d_stats, or free d_samples, as soon as this returns)
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return check_status(ctx, static_cast<unsigned>(ctx->h_small.as<SmallLayout>()->status));
 }

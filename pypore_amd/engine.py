@@ -147,7 +147,7 @@ class Context(object):
             _lib.check(self.L.ps_set_option(self.handle, name.encode(), int(value)), self.handle)
 
     def get_option(self, name):
-        """ps_get_option: "k0_waves", "k0_admit", "lat_help" as they stand, "shared_device" / "hw_queues" as last set."""
+        """ps_get_option: "k0_waves", "k0_admit", "lat_help" as they stand, "shared_device" / "hw_queues" / "range_tile" as last set."""
         out = ctypes.c_int64()
         self.L.ps_get_option.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64)]
         with self.lock:
@@ -559,6 +559,29 @@ class Context(object):
                                                  ev_start.ctypes.data_as(P64), ev_len.ctypes.data_as(P64), n_ev, int(order),
                                                  float(cutoff), float(sampling_freq), ctypes.c_void_p(out.data_ptr())), self.handle)
         return out[:total], off
+
+    @_serialised
+    def range_stats(self, samples, starts, ends, quantum, offset_counts=0):
+        """ps_range_stats: mean / std / min / max of the sample ranges [starts[r], ends[r]) of ONE device-resident tensor (int16
+        counts, or float32 on the grid `quantum`) as an (n_ranges, 4) float64 numpy array in core.STAT_COLUMNS order.  The
+        ranges may overlap, repeat and come in any order (the merged segments of DataTypes.merge_by_hmm do); two launches
+        whatever their number, one download.  Exact integer sums: the same ranges give the same bits however option
+        "range_tile" cuts them.  An empty or reversed range, one that leaves the samples, or float64 samples: ValueError,
+        nothing is launched."""
+        assert samples.is_cuda and samples.is_contiguous() and samples.dim() == 1
+        fmt = _lib.SampleFormat(_lib.PS_DTYPE_F64, 0, 1.0) if samples.dtype == torch.float64 else self._fmt(samples, quantum, offset_counts)
+        starts = np.ascontiguousarray(starts, dtype=np.int64)
+        ends = np.ascontiguousarray(ends, dtype=np.int64)
+        if starts.shape != ends.shape or starts.ndim != 1:
+            raise ValueError("starts and ends must be one-dimensional and of one length")
+        n_ranges = starts.size
+        out = torch.empty((max(1, n_ranges), 4), dtype=torch.float64, device=samples.device)
+        P64 = ctypes.POINTER(ctypes.c_int64)
+        torch.cuda.current_stream(samples.device).synchronize()
+        _lib.check(self.L.ps_range_stats(self.handle, ctypes.c_void_p(samples.data_ptr()), ctypes.byref(fmt), samples.numel(),
+                                         starts.ctypes.data_as(P64), ends.ctypes.data_as(P64), n_ranges, ctypes.c_void_p(out.data_ptr())),
+                   self.handle)
+        return out[:n_ranges].cpu().numpy()
 
     @_serialised
     def requantise(self, current):
