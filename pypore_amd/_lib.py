@@ -15,13 +15,6 @@ PS_DTYPE_F32, PS_DTYPE_I16 = 0, 1
 PS_DTYPE_F64 = 2          # float64 pA on no grid: ps_filter_bessel input only
 PS_ALIGN_OK, PS_ALIGN_VALUE_ERROR, PS_ALIGN_INDEX_ERROR, PS_ALIGN_ZERO_DIVISION, PS_ALIGN_UNDEFINED = 0, 1, 2, 3, 4
 
-EXPORTS = ["ps_version", "ps_device_count", "ps_create", "ps_destroy", "ps_last_error", "ps_set_tiling", "ps_set_option",
-           "ps_synchronize", "ps_min_gain", "ps_segment_batch", "ps_segment_batch_ex", "ps_segment_events", "ps_segment_exact_f64", "ps_detect_events", "ps_detect_segment_trace", "ps_bounds_capacity",
-           "ps_best_single_split", "ps_score_window", "ps_get_timings", "ps_synth_trace", "ps_filter_bessel",
-           "ps_requantise", "ps_grid_check_f64", "ps_grid_counts_f64", "ps_narrow_f64", "ps_filter_requantise_batch", "ps_filter_bessel_batch", "ps_range_stats", "ps_align_batch", "ps_audit_bounds", "ps_counters",
-           "ps_get_near_ties", "ps_hmm_batch", "ps_hmm_expect", "ps_hmm_posterior", "ps_hmm_sample", "ps_pairwise_scores", "ps_pairwise_batch",
-           "ps_statsplit_f64", "ps_statsplit_prefix_f64", "ps_snakebase_f64", "ps_filter_derivative_f64", "ps_live_bytes", "ps_trf_split_batch",
-           "ps_pool_plan", "ps_hw_queues", "ps_gate_stats", "ps_get_option"]
 PS_STATSPLIT_STEPWISE, PS_STATSPLIT_SLANTED = 0, 1
 PS_HMM_VITERBI, PS_HMM_FORWARD, PS_HMM_BACKWARD = 0, 1, 2
 PS_PW_GLOBAL, PS_PW_LOCAL, PS_PW_LOCAL_REPEATED = 0, 1, 2
@@ -88,11 +81,69 @@ class GridReport(ctypes.Structure):
                 ("max_count", ctypes.c_double), ("n_nonfinite", ctypes.c_int64), ("n_undefined", ctypes.c_int64)]
 
 
+vp, i32, i64, u64, dbl, cint, cstr, P = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_double, ctypes.c_int,
+                                         ctypes.c_char_p, ctypes.POINTER)
+# The C ABI, declared once: every function of include/poreseg.h -> (restype, argtypes).  lib() applies the table when it loads
+# the library; tests/test_host_logic.py compares every row with the header's prototype.
+_ABI = {
+    "ps_version": (cstr, []),
+    "ps_device_count": (cint, []),
+    "ps_create": (cint, [cint, vp, P(vp)]),
+    "ps_destroy": (None, [vp]),
+    "ps_live_bytes": (i64, []),
+    "ps_last_error": (cstr, [vp]),
+    "ps_set_tiling": (cint, [vp, i64, i64]),
+    "ps_set_option": (cint, [vp, cstr, i64]),
+    "ps_get_option": (cint, [vp, cstr, P(i64)]),
+    "ps_pool_plan": (cint, [i32, i32, P(PoolPlan)]),
+    "ps_hw_queues": (cint, []),
+    "ps_gate_stats": (cint, [cint, P(i64), i32, cint]),
+    "ps_synchronize": (cint, [vp]),
+    "ps_min_gain": (cint, [P(SplitParams), P(dbl)]),
+    "ps_segment_batch": (cint, [vp, vp, P(SampleFormat), P(i64), i32, P(SplitParams), vp, i64, P(i64), vp]),
+    "ps_segment_batch_ex": (cint, [vp, vp, P(SampleFormat), P(i64), i32, P(SplitParams), vp, i64, P(i64), vp, vp]),
+    "ps_segment_events": (cint, [vp, vp, P(SampleFormat), P(i64), P(i64), i32, P(SplitParams), vp, i64, P(i64), vp, vp]),
+    "ps_segment_exact_f64": (cint, [vp, vp, P(i64), P(i64), i32, P(SplitParams), vp, i64, P(i64)]),
+    "ps_statsplit_f64": (cint, [vp, vp, P(i64), P(i64), i32, P(i64), P(i64), P(StatSplitParams), vp, i64, P(i64)]),
+    "ps_statsplit_prefix_f64": (cint, [vp, vp, i64, vp, vp, vp]),
+    "ps_bounds_capacity": (i64, [P(i64), i32, i32]),
+    "ps_best_single_split": (cint, [vp, vp, P(SampleFormat), i64, P(dbl), P(i32)]),
+    "ps_score_window": (cint, [vp, vp, P(SampleFormat), i64, i32, dbl, vp, P(i32)]),
+    "ps_audit_bounds": (cint, [vp, vp, P(SampleFormat), i64, P(SplitParams), P(i32), i32, P(dbl)]),
+    "ps_detect_events": (cint, [vp, vp, P(SampleFormat), i64, dbl, i64, dbl, P(i64), P(i64), i64, P(i64)]),
+    "ps_detect_segment_trace": (cint, [vp, vp, P(SampleFormat), i64, dbl, i64, dbl, P(SplitParams), P(i64), P(i64), i64, P(i64),
+                                       vp, i64, P(i64), vp]),
+    "ps_filter_bessel": (cint, [vp, vp, P(SampleFormat), i64, i32, dbl, dbl, vp]),
+    "ps_requantise": (cint, [vp, vp, i64, vp, P(dbl), P(dbl)]),
+    "ps_grid_check_f64": (cint, [vp, vp, i64, dbl, dbl, dbl, P(GridReport)]),
+    "ps_grid_counts_f64": (cint, [vp, vp, i64, dbl, dbl, i64, vp]),
+    "ps_narrow_f64": (cint, [vp, vp, i64, vp, P(i64)]),
+    "ps_filter_bessel_batch": (cint, [vp, vp, P(SampleFormat), P(i64), P(i64), i32, i32, dbl, dbl, vp]),
+    "ps_filter_requantise_batch": (cint, [vp, vp, P(SampleFormat), P(i64), P(i64), i32, i32, dbl, dbl, vp, vp, P(dbl), P(dbl)]),
+    "ps_range_stats": (cint, [vp, vp, P(SampleFormat), i64, P(i64), P(i64), i64, vp]),
+    "ps_align_batch": (cint, [vp, P(dbl), P(dbl), P(dbl), i32, dbl, dbl, vp, vp, vp, P(i64), i32, vp, vp, vp]),
+    "ps_pairwise_scores": (cint, [vp, vp, P(i64), i32, vp, P(i64), i32, i32, dbl, vp, vp]),
+    "ps_pairwise_batch": (cint, [vp, vp, P(i64), i32, vp, P(i64), i32, P(i32), P(i32), i32, i32, dbl, i32, vp, vp,
+                                 P(i64), vp, vp, vp, P(i64), vp, vp, vp, vp]),
+    "ps_trf_split_batch": (cint, [vp, vp, vp, P(i64), i32, dbl, dbl, i64, vp, vp, vp, vp, P(i64), vp, vp]),
+    "ps_hmm_batch": (cint, [vp, P(HmmModel), i32, vp, P(i64), i32, vp, vp, vp, P(i64), vp]),
+    "ps_hmm_expect": (cint, [vp, P(HmmModel), vp, P(i64), i32, vp, vp, vp, P(i32)]),
+    "ps_hmm_posterior": (cint, [vp, P(HmmModel), vp, P(i64), i32, vp, vp, vp, vp, vp]),
+    "ps_hmm_sample": (cint, [vp, P(HmmModel), P(HmmSampleTables), u64, i64, i32, i32, i32, vp, P(i64), vp, vp, vp, P(i64), vp]),
+    "ps_get_timings": (cint, [vp, P(dbl), i32, P(i64), i32]),
+    "ps_counters": (P(i64), [vp]),
+    "ps_get_near_ties": (cint, [vp, P(NearTie), i32, P(i64)]),
+    "ps_synth_trace": (cint, [vp, vp, i32, i64, u64, P(i64), P(i32), i64]),
+    "ps_snakebase_f64": (cint, [vp, vp, P(i64), P(i64), i32, vp, i64, P(i64)]),
+    "ps_filter_derivative_f64": (cint, [vp, vp, P(i64), P(i64), i32, P(FilterDerivativeParams), vp, i64, P(i64)]),
+}
+EXPORTS = list(_ABI)
+
 _lib = None
 
 
 def lib():
-    """Loads libporeseg.so; raises RuntimeError (never falls back) when it is absent."""
+    """Loads libporeseg.so and declares every function of _ABI; raises RuntimeError (never falls back) when it is absent."""
     global _lib
     if _lib is not None:
         return _lib
@@ -104,61 +155,9 @@ def lib():
     # process has exactly one HIP runtime, shared by torch's allocator and our kernels.
     import torch  # noqa: F401
     L = ctypes.CDLL(LIB_PATH)
-    vp, i32, i64, dbl = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
-    P = ctypes.POINTER
-    L.ps_version.restype = ctypes.c_char_p
-    L.ps_device_count.restype = ctypes.c_int
-    L.ps_create.argtypes = [ctypes.c_int, vp, P(vp)]
-    L.ps_destroy.argtypes = [vp]
-    L.ps_destroy.restype = None
-    L.ps_live_bytes.argtypes = []
-    L.ps_live_bytes.restype = i64
-    L.ps_last_error.argtypes = [vp]
-    L.ps_last_error.restype = ctypes.c_char_p
-    L.ps_set_tiling.argtypes = [vp, i64, i64]
-    L.ps_set_option.argtypes = [vp, ctypes.c_char_p, i64]
-    L.ps_synchronize.argtypes = [vp]
-    L.ps_min_gain.argtypes = [P(SplitParams), P(dbl)]
-    L.ps_segment_batch.argtypes = [vp, vp, P(SampleFormat), P(i64), i32, P(SplitParams), vp, i64, P(i64), vp]
-    L.ps_segment_batch_ex.argtypes = [vp, vp, P(SampleFormat), P(i64), i32, P(SplitParams), vp, i64, P(i64), vp, vp]
-    L.ps_segment_events.argtypes = [vp, vp, P(SampleFormat), P(i64), P(i64), i32, P(SplitParams), vp, i64, P(i64), vp, vp]
-    L.ps_segment_exact_f64.argtypes = [vp, vp, P(i64), P(i64), i32, P(SplitParams), vp, i64, P(i64)]
-    L.ps_detect_events.argtypes = [vp, vp, P(SampleFormat), i64, dbl, i64, dbl, P(i64), P(i64), i64, P(i64)]
-    L.ps_detect_segment_trace.argtypes = [vp, vp, P(SampleFormat), i64, dbl, i64, dbl, P(SplitParams), P(i64), P(i64), i64, P(i64),
-                                          vp, i64, P(i64), vp]
-    L.ps_bounds_capacity.argtypes = [P(i64), i32, i32]
-    L.ps_bounds_capacity.restype = i64
-    L.ps_best_single_split.argtypes = [vp, vp, P(SampleFormat), i64, P(dbl), P(i32)]
-    L.ps_score_window.argtypes = [vp, vp, P(SampleFormat), i64, i32, dbl, vp, P(i32)]
-    L.ps_get_timings.argtypes = [vp, P(dbl), i32, P(i64), i32]
-    L.ps_synth_trace.argtypes = [vp, vp, i32, i64, ctypes.c_uint64, P(i64), P(i32), i64]
-    L.ps_filter_bessel.argtypes = [vp, vp, P(SampleFormat), i64, i32, dbl, dbl, vp]
-    L.ps_requantise.argtypes = [vp, vp, i64, vp, P(dbl), P(dbl)]
-    L.ps_grid_check_f64.argtypes = [vp, vp, i64, dbl, dbl, dbl, P(GridReport)]
-    L.ps_grid_counts_f64.argtypes = [vp, vp, i64, dbl, dbl, i64, vp]
-    L.ps_narrow_f64.argtypes = [vp, vp, i64, vp, P(i64)]
-    L.ps_filter_requantise_batch.argtypes = [vp, vp, P(SampleFormat), P(i64), P(i64), ctypes.c_int32, ctypes.c_int32, dbl, dbl,
-                                             vp, vp, P(dbl), P(dbl)]
-    L.ps_filter_bessel_batch.argtypes = [vp, vp, P(SampleFormat), P(i64), P(i64), ctypes.c_int32, ctypes.c_int32, dbl, dbl, vp]
-    L.ps_range_stats.argtypes = [vp, vp, P(SampleFormat), i64, P(i64), P(i64), i64, vp]
-    L.ps_align_batch.argtypes = [vp, P(dbl), P(dbl), P(dbl), i32, dbl, dbl, vp, vp, vp, P(i64), i32, vp, vp, vp]
-    L.ps_counters.argtypes = [vp]
-    L.ps_counters.restype = P(i64)
-    L.ps_get_near_ties.argtypes = [vp, P(NearTie), i32, P(i64)]
-    L.ps_hmm_batch.argtypes = [vp, P(HmmModel), i32, vp, P(i64), i32, vp, vp, vp, P(i64), vp]
-    L.ps_hmm_expect.argtypes = [vp, P(HmmModel), vp, P(i64), i32, vp, vp, vp, P(i32)]
-    L.ps_hmm_posterior.argtypes = [vp, P(HmmModel), vp, P(i64), i32, vp, vp, vp, vp, vp]
-    L.ps_hmm_sample.argtypes = [vp, P(HmmModel), P(HmmSampleTables), ctypes.c_uint64, i64, i32, i32, i32, vp, P(i64), vp, vp, vp,
-                                P(i64), vp]
-    L.ps_pairwise_scores.argtypes = [vp, vp, P(i64), i32, vp, P(i64), i32, i32, dbl, vp, vp]
-    L.ps_pairwise_batch.argtypes = [vp, vp, P(i64), i32, vp, P(i64), i32, P(i32), P(i32), i32, i32, dbl, i32, vp, vp,
-                                    P(i64), vp, vp, vp, P(i64), vp, vp, vp, vp]
-    L.ps_trf_split_batch.argtypes = [vp, vp, vp, P(i64), i32, dbl, dbl, i64, vp, vp, vp, vp, P(i64), vp, vp]
-    L.ps_audit_bounds.argtypes = [vp, vp, P(SampleFormat), i64, P(SplitParams), P(i32), i32, P(dbl)]
-    L.ps_statsplit_f64.argtypes = [vp, vp, P(i64), P(i64), i32, P(i64), P(i64), P(StatSplitParams), vp, i64, P(i64)]
-    L.ps_statsplit_prefix_f64.argtypes = [vp, vp, i64, vp, vp, vp]
-    L.ps_snakebase_f64.argtypes = [vp, vp, P(i64), P(i64), i32, vp, i64, P(i64)]
-    L.ps_filter_derivative_f64.argtypes = [vp, vp, P(i64), P(i64), i32, P(FilterDerivativeParams), vp, i64, P(i64)]
+    for name, (restype, argtypes) in _ABI.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -209,10 +208,8 @@ def min_gain(**kw):
 def pool_plan(n_contexts, hw_queues=0):
     """ps_pool_plan (no GPU): the options "shared_device" n_contexts sets with hw_queues hardware queues (0: HIP's default of 4),
     as a dict with n_eff = min(n_contexts, hw_queues)."""
-    L = lib()
-    L.ps_pool_plan.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(PoolPlan)]
     p = PoolPlan()
-    check(L.ps_pool_plan(int(n_contexts), int(hw_queues), ctypes.byref(p)))
+    check(lib().ps_pool_plan(int(n_contexts), int(hw_queues), ctypes.byref(p)))
     return {f: int(getattr(p, f)) for f, _ in PoolPlan._fields_}
 
 
@@ -223,8 +220,6 @@ def hw_queues():
 
 def gate_stats(device=0, reset=False):
     """ps_gate_stats (host bookkeeping of the K0 gate): tickets, open now, most open at a time, host waits, waits given up."""
-    L = lib()
-    L.ps_gate_stats.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32, ctypes.c_int]
     out = (ctypes.c_int64 * 5)()
-    check(L.ps_gate_stats(int(device), out, 5, 1 if reset else 0))
+    check(lib().ps_gate_stats(int(device), out, 5, 1 if reset else 0))
     return dict(zip(("tickets", "open", "open_max", "host_waits", "gave_up"), (int(v) for v in out)))

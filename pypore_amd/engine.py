@@ -79,17 +79,93 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
 
 
-def _offsets(off):
-    """Sequence offsets for the C ABI: (contiguous int64 array, its const int64_t * -- valid while the array lives)."""
-    off = np.ascontiguousarray(off, dtype=np.int64)
-    return off, off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+def _addr(t):
+    """The address of a CUDA tensor as torch gives it: an empty view of a live tensor keeps its own (the library refuses NULL
+    where it must have samples, so _ptr is for the arguments that may be absent)."""
+    return ctypes.c_void_p(t.data_ptr())
 
 
-def _f64_device(*tensors):
-    """The device of contiguous float64 CUDA tensors (asserted)."""
+_HOST_POINTER = {np.int64: ctypes.POINTER(ctypes.c_int64), np.int32: ctypes.POINTER(ctypes.c_int32),
+                 np.float64: ctypes.POINTER(ctypes.c_double)}
+
+
+def _host(a, dtype=np.int64):
+    """A host array for the C ABI: (contiguous array of int64, int32 or float64, the pointer to it -- valid while the array lives)."""
+    a = np.ascontiguousarray(a, dtype=dtype)
+    return a, a.ctypes.data_as(_HOST_POINTER[dtype])
+
+
+_offsets = _host
+
+
+def _slot_offsets(slots):
+    """Per-sequence slot sizes as the offsets the C ABI takes: ([0, s0, s0 + s1, ...], the pointer to them)."""
+    return _host(np.concatenate(([0], np.cumsum(slots))))
+
+
+def _device_input(*tensors, dtype=None, one_dim=True):
+    """What a device input must be (asserted): a contiguous CUDA tensor, one-dimensional and of `dtype` where the caller
+    says so.  Returns the device."""
     for t in tensors:
-        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float64
+        assert t.is_cuda and t.is_contiguous() and (not one_dim or t.dim() == 1) and (dtype is None or t.dtype == dtype)
     return tensors[0].device
+
+
+def _fmt(samples, quantum, offset_counts, f64=False):
+    """The ps_sample_format of a tensor: float32 on the grid `quantum`, int16 counts, and -- only for a call that takes it,
+    f64=True -- float64 on no grid (quantum and offset are ignored then)."""
+    if samples.dtype == torch.float32:
+        return _lib.SampleFormat(_lib.PS_DTYPE_F32, int(offset_counts), float(quantum))
+    if samples.dtype == torch.int16:
+        return _lib.SampleFormat(_lib.PS_DTYPE_I16, int(offset_counts), float(quantum))
+    if f64 and samples.dtype == torch.float64:
+        return _lib.SampleFormat(_lib.PS_DTYPE_F64, 0, 1.0)
+    raise ValueError("samples must be float32 or int16, got %s" % samples.dtype)
+
+
+def _call_rc(dev, fn, handle, *args):
+    """The one path of a library call: what torch's current stream of `dev` was given is finished (inputs produced there are
+    ready; dev None: the call reads no device memory), then fn(handle, *args).  Returns the status for a caller that
+    interprets it itself."""
+    if dev is not None:
+        torch.cuda.current_stream(dev).synchronize()
+    return fn(handle, *args)
+
+
+def _call(dev, fn, handle, *args):
+    """_call_rc with the status checked: any but PS_OK raises (_lib.check)."""
+    _lib.check(_call_rc(dev, fn, handle, *args), handle)
+
+
+def _retry_capacity(handle, attempt, cap, fixed=False):
+    """A call whose output has ONE capacity.  attempt(cap) makes it with room for cap entries and returns (status, the size
+    the library reported, result).  PS_ERR_CAPACITY with a reported size above cap: CapacityError when the caller fixed cap,
+    else one more attempt with the reported size.  Whatever status stands then is checked; returns the result."""
+    rc, need, out = attempt(cap)
+    if rc == _lib.PS_ERR_CAPACITY and fixed:
+        raise CapacityError(need, cap)
+    if rc == _lib.PS_ERR_CAPACITY and need > cap:
+        rc, need, out = attempt(int(need))
+    _lib.check(rc, handle)
+    return out
+
+
+def _retry_slots(handle, attempt, reported, slots, retry=True):
+    """A call whose output has a slot PER SEQUENCE.  attempt(*slots) makes it with the given slot sizes and returns (status,
+    result); reported() reads the exact sizes the call counted, as a tuple like slots.  PS_ERR_CAPACITY: with retry one more
+    attempt with the reported sizes, and whatever status stands then is checked; without, the status is returned as it is
+    with whatever fitted.  Any other status is checked.  Returns (status, result)."""
+    rc, out = attempt(*slots)
+    if rc == _lib.PS_ERR_CAPACITY and retry:
+        rc, out = attempt(*reported())
+    if rc != _lib.PS_ERR_CAPACITY or retry:
+        _lib.check(rc, handle)
+    return rc, out
+
+
+def _int64_host(counts, n):
+    """The first n of a device tensor of counts as an int64 numpy array (the exact sizes for _retry_slots)."""
+    return counts[:n].cpu().numpy().astype(np.int64)
 
 
 def live_bytes():
@@ -139,19 +215,18 @@ class Context(object):
 
     def set_tiling(self, tile_len=0, halo=0):
         with self.lock:
-            _lib.check(self.L.ps_set_tiling(self.handle, int(tile_len), int(halo)), self.handle)
+            _call(None, self.L.ps_set_tiling, self.handle, int(tile_len), int(halo))
 
     def set_option(self, name, value):
         """ps_set_option, under the context's lock: an option never changes in the middle of another thread's call."""
         with self.lock:
-            _lib.check(self.L.ps_set_option(self.handle, name.encode(), int(value)), self.handle)
+            _call(None, self.L.ps_set_option, self.handle, name.encode(), int(value))
 
     def get_option(self, name):
         """ps_get_option: "k0_waves", "k0_admit", "lat_help" as they stand, "shared_device" / "hw_queues" / "range_tile" as last set."""
         out = ctypes.c_int64()
-        self.L.ps_get_option.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64)]
         with self.lock:
-            _lib.check(self.L.ps_get_option(self.handle, name.encode(), ctypes.byref(out)), self.handle)
+            _call(None, self.L.ps_get_option, self.handle, name.encode(), ctypes.byref(out))
         return int(out.value)
 
     def seq_ms(self):
@@ -165,7 +240,7 @@ class Context(object):
     def timings(self):
         ms = (ctypes.c_double * 8)()
         cnt = (ctypes.c_int64 * 20)()
-        _lib.check(self.L.ps_get_timings(self.handle, ms, 8, cnt, 20))
+        _call(None, self.L.ps_get_timings, self.handle, ms, 8, cnt, 20)
         return dict(spine_ms=ms[0], tree_ms=ms[1], gather_ms=ms[2], total_ms=ms[3], stitch_ms=ms[4], bridge_ms=ms[5], blocksum_ms=ms[6], seq_ms=ms[7],
                     windows=cnt[0], candidates=cnt[1], tiles=cnt[2], tree_jobs=cnt[3], repairs=cnt[4],
                     exact_rescans=cnt[5], full_exact_scans=cnt[6], wide_redo=cnt[7],
@@ -189,20 +264,17 @@ class Context(object):
         NEAR_TIE_DTYPE -- (event, window_start, window_end, split) in samples of the event, split -1: none -- sorted by
         (event, window_start), speculative scans included (consistent_sites removes those).  None when the sites are not
         counted (LDS-window kernels, option near_tie_log 0) or incomplete (the log overflowed): treat every event as flagged."""
+        n = ctypes.c_int64()
+
+        def attempt(cap):
+            buf = (_lib.NearTie * cap)()
+            return _call_rc(None, self.L.ps_get_near_ties, self.handle, buf, cap, ctypes.byref(n)), n.value, buf
+
         with self.lock:
-            n = ctypes.c_int64()
-            cap = 64
-            while True:
-                buf = (_lib.NearTie * cap)()
-                rc = self.L.ps_get_near_ties(self.handle, buf, cap, ctypes.byref(n))
-                if rc == _lib.PS_ERR_CAPACITY and n.value > cap:
-                    cap = int(n.value)
-                    continue
-                _lib.check(rc, self.handle)
-                break
-            if n.value < 0:
-                return None
-            return np.frombuffer(buf, dtype=NEAR_TIE_DTYPE, count=int(n.value)).copy()
+            buf = _retry_capacity(self.handle, attempt, 64)
+        if n.value < 0:
+            return None
+        return np.frombuffer(buf, dtype=NEAR_TIE_DTYPE, count=int(n.value)).copy()
 
     # ---- the hot path ---------------------------------------------------------------------------
     @_serialised
@@ -258,70 +330,51 @@ class Context(object):
             return bounds[:total], boff, (stats[:total + n_ev] if want_stats else None), spine[:total]
         return bounds[:total], boff, (stats[:total + n_ev] if want_stats else None)
 
-    def _fmt(self, samples, quantum, offset_counts):
-        if samples.dtype == torch.float32:
-            return _lib.SampleFormat(_lib.PS_DTYPE_F32, int(offset_counts), float(quantum))
-        if samples.dtype == torch.int16:
-            return _lib.SampleFormat(_lib.PS_DTYPE_I16, int(offset_counts), float(quantum))
-        raise ValueError("samples must be float32 or int16, got %s" % samples.dtype)
+    _fmt = staticmethod(_fmt)        # (tools/ build a format for their own ctx.L calls)
 
     @_serialised
     def detect_events(self, samples, quantum, threshold=90.0, min_duration=100000, min_current=-0.5,
                       offset_counts=0):
         """ps_detect_events on a device-resident trace: (starts, lengths) int64 numpy arrays of the
         events lambda_event_parser(threshold) keeps with its default rules (parsers.py:124-155)."""
-        assert samples.is_cuda and samples.is_contiguous() and samples.dim() == 1
-        fmt = self._fmt(samples, quantum, offset_counts)
+        dev = _device_input(samples)
+        fmt = _fmt(samples, quantum, offset_counts)
         n = samples.numel()
+        cnt = ctypes.c_int64()
+
+        def attempt(cap):
+            (st, st_p), (ln, ln_p) = _host(np.zeros(cap, dtype=np.int64)), _host(np.zeros(cap, dtype=np.int64))
+            rc = _call_rc(dev, self.L.ps_detect_events, self.handle, _addr(samples), ctypes.byref(fmt), n, float(threshold),
+                          int(min_duration), float(min_current), st_p, ln_p, cap, ctypes.byref(cnt))
+            return rc, cnt.value, (st, ln)
+
         # (room for every event the rules can keep is n / min_duration + 2 -- gigabytes of host memory for a long trace and a
         #  small min_duration; a file has a few hundred: start with EVENT_CAP and take the count the library reports if it is more)
-        cap = min(n // max(1, int(min_duration)) + 2, EVENT_CAP)
-        cnt = ctypes.c_int64()
-        torch.cuda.current_stream(samples.device).synchronize()
-        P64 = ctypes.POINTER(ctypes.c_int64)
-        while True:
-            st = np.zeros(cap, dtype=np.int64)
-            ln = np.zeros(cap, dtype=np.int64)
-            rc = self.L.ps_detect_events(self.handle, ctypes.c_void_p(samples.data_ptr()), ctypes.byref(fmt), n,
-                                         float(threshold), int(min_duration), float(min_current),
-                                         st.ctypes.data_as(P64), ln.ctypes.data_as(P64), cap, ctypes.byref(cnt))
-            if rc == _lib.PS_ERR_CAPACITY and cnt.value > cap:
-                cap = int(cnt.value)
-                continue
-            _lib.check(rc, self.handle)
-            return st[:cnt.value].copy(), ln[:cnt.value].copy()
+        st, ln = _retry_capacity(self.handle, attempt, min(n // max(1, int(min_duration)) + 2, EVENT_CAP))
+        return st[:cnt.value].copy(), ln[:cnt.value].copy()
 
     @_serialised
     def detect_segment_trace(self, samples, quantum, params, threshold=90.0, min_duration=100000, min_current=-0.5,
                              offset_counts=0, want_stats=False):
         """ps_detect_segment_trace: detect_events + segment_events of a device-resident file trace in one call and one pass
         over its samples (include/poreseg.h).  Returns (starts, lengths, bounds, bounds_off, stats or None)."""
-        assert samples.is_cuda and samples.is_contiguous() and samples.dim() == 1
-        fmt = self._fmt(samples, quantum, offset_counts)
+        dev = _device_input(samples)
+        fmt = _fmt(samples, quantum, offset_counts)
         n = samples.numel()
-        ev_cap = min(n // max(1, int(min_duration)) + 2, EVENT_CAP)      # (see detect_events)
         cnt = ctypes.c_int64()
-        dev = samples.device
-        P64 = ctypes.POINTER(ctypes.c_int64)
-        torch.cuda.current_stream(dev).synchronize()
-        while True:
-            # (every event holds at most length / min_width boundaries, all of them together n / min_width)
-            cap = n // int(params.min_width) + 1
-            st = np.zeros(ev_cap, dtype=np.int64)
-            ln = np.zeros(ev_cap, dtype=np.int64)
-            boff = np.zeros(ev_cap + 1, dtype=np.int64)
+        cap = n // int(params.min_width) + 1     # (every event holds at most length / min_width boundaries, all of them together n / min_width)
+
+        def attempt(ev_cap):
+            st, ln, boff = np.zeros(ev_cap, dtype=np.int64), np.zeros(ev_cap, dtype=np.int64), np.zeros(ev_cap + 1, dtype=np.int64)
             bounds = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
             stats = torch.empty((max(cap, 1) + ev_cap, 4), dtype=torch.float64, device=dev) if want_stats else None
-            rc = self.L.ps_detect_segment_trace(self.handle, ctypes.c_void_p(samples.data_ptr()), ctypes.byref(fmt), n,
-                                                float(threshold), int(min_duration), float(min_current), ctypes.byref(params),
-                                                st.ctypes.data_as(P64), ln.ctypes.data_as(P64), ev_cap, ctypes.byref(cnt),
-                                                ctypes.c_void_p(bounds.data_ptr()), cap, boff.ctypes.data_as(P64),
-                                                ctypes.c_void_p(stats.data_ptr()) if want_stats else None)
-            if rc == _lib.PS_ERR_CAPACITY and cnt.value > ev_cap:        # more events than EVENT_CAP: once more with room for all
-                ev_cap = int(cnt.value)
-                continue
-            _lib.check(rc, self.handle)
-            break
+            rc = _call_rc(dev, self.L.ps_detect_segment_trace, self.handle, _addr(samples), ctypes.byref(fmt), n, float(threshold),
+                          int(min_duration), float(min_current), ctypes.byref(params), _host(st)[1], _host(ln)[1], ev_cap,
+                          ctypes.byref(cnt), _addr(bounds), cap, _host(boff)[1], _ptr(stats))
+            return rc, cnt.value, (st, ln, boff, bounds, stats)
+
+        # (more events than EVENT_CAP: once more with room for all; see detect_events)
+        st, ln, boff, bounds, stats = _retry_capacity(self.handle, attempt, min(n // max(1, int(min_duration)) + 2, EVENT_CAP))
         n_ev = int(cnt.value)
         total = int(boff[n_ev])
         return st[:n_ev].copy(), ln[:n_ev].copy(), bounds[:total], boff[:n_ev + 1].copy(), (stats[:total + n_ev] if want_stats else None)
@@ -329,24 +382,16 @@ class Context(object):
     @_serialised
     def segment_events(self, samples, ev_start, ev_len, params, quantum, offset_counts=0, want_stats=False):
         """ps_segment_events: events are sub-ranges [start, start+len) of one device-resident trace."""
-        assert samples.is_cuda and samples.is_contiguous() and samples.dim() == 1
-        fmt = self._fmt(samples, quantum, offset_counts)
-        ev_start = np.ascontiguousarray(ev_start, dtype=np.int64)
-        ev_len = np.ascontiguousarray(ev_len, dtype=np.int64)
+        dev = _device_input(samples)
+        fmt = _fmt(samples, quantum, offset_counts)
+        (ev_start, st_p), (ev_len, ln_p) = _host(ev_start), _host(ev_len)
         n_ev = ev_start.size
         cap = int(np.sum(ev_len // int(params.min_width) + 1)) if n_ev else 0
-        dev = samples.device
         bounds = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
         stats = torch.empty((max(cap, 1) + n_ev, 4), dtype=torch.float64, device=dev) if want_stats else None
-        boff = np.zeros(n_ev + 1, dtype=np.int64)
-        P64 = ctypes.POINTER(ctypes.c_int64)
-        torch.cuda.current_stream(dev).synchronize()
-        _lib.check(self.L.ps_segment_events(self.handle, ctypes.c_void_p(samples.data_ptr()), ctypes.byref(fmt),
-                                            ev_start.ctypes.data_as(P64), ev_len.ctypes.data_as(P64), n_ev,
-                                            ctypes.byref(params), ctypes.c_void_p(bounds.data_ptr()), cap,
-                                            boff.ctypes.data_as(P64),
-                                            ctypes.c_void_p(stats.data_ptr()) if want_stats else None, None),
-                   self.handle)
+        boff, boff_p = _host(np.zeros(n_ev + 1, dtype=np.int64))
+        _call(dev, self.L.ps_segment_events, self.handle, _addr(samples), ctypes.byref(fmt), st_p, ln_p, n_ev, ctypes.byref(params),
+              _addr(bounds), cap, boff_p, _ptr(stats), None)
         total = int(boff[-1])
         return bounds[:total], boff, (stats[:total + n_ev] if want_stats else None)
 
@@ -354,18 +399,14 @@ class Context(object):
     def segment_exact_f64(self, current, ev_start, ev_len, params):
         """ps_segment_exact_f64: events [start, start + len) of a float64 CUDA tensor (pA, on no grid) segmented from the
         reference's own sequential prefix sums (include/poreseg.h).  Returns (bounds int32 CUDA tensor, bounds_off)."""
-        assert current.is_cuda and current.is_contiguous() and current.dim() == 1 and current.dtype == torch.float64
-        ev_start = np.ascontiguousarray(ev_start, dtype=np.int64)
-        ev_len = np.ascontiguousarray(ev_len, dtype=np.int64)
+        dev = _device_input(current, dtype=torch.float64)
+        (ev_start, st_p), (ev_len, ln_p) = _host(ev_start), _host(ev_len)
         n_ev = ev_start.size
         cap = int(np.sum(ev_len // int(params.min_width) + 1)) if n_ev else 0
-        bounds = torch.empty(max(cap, 1), dtype=torch.int32, device=current.device)
-        boff = np.zeros(n_ev + 1, dtype=np.int64)
-        P64 = ctypes.POINTER(ctypes.c_int64)
-        torch.cuda.current_stream(current.device).synchronize()
-        _lib.check(self.L.ps_segment_exact_f64(self.handle, ctypes.c_void_p(current.data_ptr()), ev_start.ctypes.data_as(P64),
-                                               ev_len.ctypes.data_as(P64), n_ev, ctypes.byref(params),
-                                               ctypes.c_void_p(bounds.data_ptr()), cap, boff.ctypes.data_as(P64)), self.handle)
+        bounds = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+        boff, boff_p = _host(np.zeros(n_ev + 1, dtype=np.int64))
+        _call(dev, self.L.ps_segment_exact_f64, self.handle, _addr(current), st_p, ln_p, n_ev, ctypes.byref(params), _addr(bounds),
+              cap, boff_p)
         return bounds[:int(boff[-1])], boff
 
     @_serialised
@@ -374,50 +415,39 @@ class Context(object):
         (include/poreseg.h); params: _lib.StatSplitParams.  lo / hi: per event the range [lo, hi) that is segmented, in
         samples from its start (None: all of it).  cap: boundaries the output may hold (None: what the model allows); when
         it is too small, CapacityError names the size required.  Returns (bounds int32 CUDA tensor, bounds_off)."""
-        assert current.is_cuda and current.is_contiguous() and current.dim() == 1 and current.dtype == torch.float64
-        ev_start = np.ascontiguousarray(ev_start, dtype=np.int64)
-        ev_len = np.ascontiguousarray(ev_len, dtype=np.int64)
+        dev = _device_input(current, dtype=torch.float64)
+        (ev_start, st_p), (ev_len, ln_p) = _host(ev_start), _host(ev_len)
         n_ev = ev_start.size
-        P64 = ctypes.POINTER(ctypes.c_int64)
-        lo = None if lo is None else np.ascontiguousarray(lo, dtype=np.int64)
-        hi = None if hi is None else np.ascontiguousarray(hi, dtype=np.int64)
+        lo, lo_p = (None, None) if lo is None else _host(lo)
+        hi, hi_p = (None, None) if hi is None else _host(hi)
         if cap is None:
             span = np.maximum((ev_len if hi is None else hi) - (0 if lo is None else lo), 0)
             cap = int(np.sum(2 * (span // max(int(params.min_width), 1)) + 2)) if n_ev else 0
-        bounds = torch.empty(max(cap, 1), dtype=torch.int32, device=current.device)
-        boff = np.zeros(n_ev + 1, dtype=np.int64)
-        torch.cuda.current_stream(current.device).synchronize()
-        rc = self.L.ps_statsplit_f64(self.handle, _ptr(current), ev_start.ctypes.data_as(P64), ev_len.ctypes.data_as(P64), n_ev,
-                                     None if lo is None else lo.ctypes.data_as(P64), None if hi is None else hi.ctypes.data_as(P64),
-                                     ctypes.byref(params), ctypes.c_void_p(bounds.data_ptr()), cap, boff.ctypes.data_as(P64))
-        if rc == _lib.PS_ERR_CAPACITY:
-            raise CapacityError(int(boff[-1]), cap)
-        _lib.check(rc, self.handle)
-        return bounds[:int(boff[-1])], boff
+        bounds = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+        boff, boff_p = _host(np.zeros(n_ev + 1, dtype=np.int64))
 
-    def _spans_f64(self, call, current, ev_start, ev_len, cap, guess):
-        """The state parsers' common call: spans (n, 2) int32 CUDA tensor and span_off.  cap None: a first call sized by
-        guess(ev_len), repeated once with the size the library reports when that is too small."""
-        assert current.is_cuda and current.is_contiguous() and current.dim() == 1 and current.dtype == torch.float64
-        ev_start = np.ascontiguousarray(ev_start, dtype=np.int64)
-        ev_len = np.ascontiguousarray(ev_len, dtype=np.int64)
+        def attempt(cap):
+            rc = _call_rc(dev, self.L.ps_statsplit_f64, self.handle, _ptr(current), st_p, ln_p, n_ev, lo_p, hi_p, ctypes.byref(params),
+                          _addr(bounds), cap, boff_p)
+            return rc, int(boff[-1]), bounds
+
+        return _retry_capacity(self.handle, attempt, cap, fixed=True)[:int(boff[-1])], boff
+
+    def _spans_f64(self, fn, current, ev_start, ev_len, cap, guess, *params):
+        """The state parsers' common call fn(handle, current, starts, lengths, n_ev, *params, spans, cap, span_off): spans (n, 2)
+        int32 CUDA tensor and span_off.  cap None: a first call sized by guess(ev_len), repeated once with the size the library
+        reports when that is too small."""
+        dev = _device_input(current, dtype=torch.float64)
+        (ev_start, st_p), (ev_len, ln_p) = _host(ev_start), _host(ev_len)
         n_ev = ev_start.size
-        P64 = ctypes.POINTER(ctypes.c_int64)
-        soff = np.zeros(n_ev + 1, dtype=np.int64)
-        torch.cuda.current_stream(current.device).synchronize()
-        grow = cap is None
-        if grow:
-            cap = int(guess(ev_len))
-        while True:
-            spans = torch.empty((max(cap, 1), 2), dtype=torch.int32, device=current.device)
-            rc = call(ev_start.ctypes.data_as(P64), ev_len.ctypes.data_as(P64), n_ev, ctypes.c_void_p(spans.data_ptr()), cap,
-                      soff.ctypes.data_as(P64))
-            if rc != _lib.PS_ERR_CAPACITY:
-                break
-            if not grow:
-                raise CapacityError(int(soff[-1]), cap)
-            cap, grow = int(soff[-1]), False
-        _lib.check(rc, self.handle)
+        soff, soff_p = _host(np.zeros(n_ev + 1, dtype=np.int64))
+
+        def attempt(cap):
+            spans = torch.empty((max(cap, 1), 2), dtype=torch.int32, device=dev)
+            rc = _call_rc(dev, fn, self.handle, _ptr(current), st_p, ln_p, n_ev, *params, _addr(spans), cap, soff_p)
+            return rc, int(soff[-1]), spans
+
+        spans = _retry_capacity(self.handle, attempt, int(guess(ev_len)) if cap is None else cap, fixed=cap is not None)
         return spans[:int(soff[-1])], soff
 
     @_serialised
@@ -426,39 +456,34 @@ class Context(object):
         tensor (include/poreseg.h).  cap: spans the output may hold -- CapacityError names the size required when it is
         too small; None: the most an event can have, a span per two samples (the normal case on ADC-grid data is not far
         from it).  Returns (spans (n, 2) int32 CUDA tensor of (start, end), span_off)."""
-        return self._spans_f64(lambda st, ln, n, out, c, off: self.L.ps_snakebase_f64(self.handle, _ptr(current), st, ln, n, out, c, off),
-                               current, ev_start, ev_len, cap, lambda ln: (ln // 2).sum())
+        return self._spans_f64(self.L.ps_snakebase_f64, current, ev_start, ev_len, cap, lambda ln: (ln // 2).sum())
 
     @_serialised
     def filter_derivative_f64(self, current, ev_start, ev_len, params, cap=None):
         """ps_filter_derivative_f64: the spans FilterDerivativeSegmenter.parse returns; params: _lib.FilterDerivativeParams
         (prefiltered 1: `current` is the filtered current).  cap and the result as for snakebase_f64; None: a span per 64
         samples, and one more call with the size the library reports when that is too small."""
-        return self._spans_f64(lambda st, ln, n, out, c, off: self.L.ps_filter_derivative_f64(self.handle, _ptr(current), st, ln, n,
-                                                                                              ctypes.byref(params), out, c, off),
-                               current, ev_start, ev_len, cap, lambda ln: ln.sum() // 64 + ln.size + 1)
+        return self._spans_f64(self.L.ps_filter_derivative_f64, current, ev_start, ev_len, cap, lambda ln: ln.sum() // 64 + ln.size + 1,
+                               ctypes.byref(params))
 
     @_serialised
     def statsplit_prefix_f64(self, current, want_ct=True):
         """ps_statsplit_prefix_f64 (diagnostics): the prefix sums StatSplit forms of one float64 CUDA tensor -- (c, c2, ct) as
         CUDA tensors, ct None unless asked for."""
-        assert current.is_cuda and current.is_contiguous() and current.dim() == 1 and current.dtype == torch.float64
+        dev = _device_input(current, dtype=torch.float64)
         c, c2 = torch.empty_like(current), torch.empty_like(current)
         ct = torch.empty_like(current) if want_ct else None
-        torch.cuda.current_stream(current.device).synchronize()
-        _lib.check(self.L.ps_statsplit_prefix_f64(self.handle, _ptr(current), current.numel(), _ptr(c), _ptr(c2), _ptr(ct)),
-                   self.handle)
+        _call(dev, self.L.ps_statsplit_prefix_f64, self.handle, _ptr(current), current.numel(), _ptr(c), _ptr(c2), _ptr(ct))
         return c, c2, ct
 
     @_serialised
     def best_single_split(self, samples, quantum, offset_counts=0):
-        fmt = _lib.SampleFormat(_lib.PS_DTYPE_F32 if samples.dtype == torch.float32 else _lib.PS_DTYPE_I16,
-                                int(offset_counts), float(quantum))
+        dev = _device_input(samples)
+        fmt = _fmt(samples, quantum, offset_counts)
         g = ctypes.c_double()
         i = ctypes.c_int32()
-        torch.cuda.current_stream(samples.device).synchronize()
-        _lib.check(self.L.ps_best_single_split(self.handle, ctypes.c_void_p(samples.data_ptr()), ctypes.byref(fmt),
-                                               samples.numel(), ctypes.byref(g), ctypes.byref(i)), self.handle)
+        _call(dev, self.L.ps_best_single_split, self.handle, _addr(samples), ctypes.byref(fmt), samples.numel(), ctypes.byref(g),
+              ctypes.byref(i))
         return g.value, i.value
 
     @_serialised
@@ -466,13 +491,11 @@ class Context(object):
         """ps_audit_bounds (diagnostic): the pruning bounds of the block-sum scan -- corner, two-boundary, group -- against
         the gains they cover, evaluated on the device from the raw samples, for the given windows [(ps, pe), ...] of the
         trace taken as one event.  Returns a dict of counts, violations and smallest margins per kind."""
-        fmt = self._fmt(samples, quantum, offset_counts)
-        w = np.ascontiguousarray(np.asarray(windows, dtype=np.int32).reshape(-1, 2))
+        fmt = _fmt(samples, quantum, offset_counts)
+        w, w_p = _host(np.asarray(windows, dtype=np.int32).reshape(-1, 2), np.int32)
         out = (ctypes.c_double * 12)()
-        torch.cuda.current_stream(samples.device).synchronize()
-        _lib.check(self.L.ps_audit_bounds(self.handle, ctypes.c_void_p(samples.data_ptr()), ctypes.byref(fmt), samples.numel(),
-                                          ctypes.byref(params), w.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(w.shape[0]), out),
-                   self.handle)
+        _call(samples.device, self.L.ps_audit_bounds, self.handle, _addr(samples), ctypes.byref(fmt), samples.numel(),
+              ctypes.byref(params), w_p, int(w.shape[0]), out)
         o = list(out)
         return {"corner": {"blocks": int(o[0]), "violations": int(o[1]), "min_margin": o[6]},
                 "two_boundary": {"blocks": int(o[2]), "violations": int(o[3]), "min_margin": o[7]},
@@ -481,14 +504,12 @@ class Context(object):
 
     @_serialised
     def score_window(self, samples, quantum, min_width, min_gain, offset_counts=0):
-        fmt = _lib.SampleFormat(_lib.PS_DTYPE_F32 if samples.dtype == torch.float32 else _lib.PS_DTYPE_I16,
-                                int(offset_counts), float(quantum))
-        scores = torch.empty(max(1, samples.numel()), dtype=torch.float64, device=samples.device)
+        dev = _device_input(samples)
+        fmt = _fmt(samples, quantum, offset_counts)
+        scores = torch.empty(max(1, samples.numel()), dtype=torch.float64, device=dev)
         i = ctypes.c_int32()
-        torch.cuda.current_stream(samples.device).synchronize()
-        _lib.check(self.L.ps_score_window(self.handle, ctypes.c_void_p(samples.data_ptr()), ctypes.byref(fmt),
-                                          samples.numel(), int(min_width), float(min_gain),
-                                          ctypes.c_void_p(scores.data_ptr()), ctypes.byref(i)), self.handle)
+        _call(dev, self.L.ps_score_window, self.handle, _addr(samples), ctypes.byref(fmt), samples.numel(), int(min_width),
+              float(min_gain), _addr(scores), ctypes.byref(i))
         return i.value, scores[:samples.numel()]
 
     @_serialised
@@ -497,16 +518,11 @@ class Context(object):
         (scipy filtfilt semantics); returns the filtered current in pA as a float64 CUDA tensor.  `samples`: float32 pA on
         the grid `quantum` / int16 counts (what a file holds), or a float64 tensor of pA on no grid at all -- the current
         of an event that was filtered before (quantum is ignored then)."""
-        assert samples.is_cuda and samples.is_contiguous() and samples.dim() == 1
-        if samples.dtype == torch.float64:
-            fmt = _lib.SampleFormat(_lib.PS_DTYPE_F64, 0, 1.0)
-        else:
-            fmt = self._fmt(samples, quantum, offset_counts)
-        out = torch.empty(max(1, samples.numel()), dtype=torch.float64, device=samples.device)
-        torch.cuda.current_stream(samples.device).synchronize()
-        _lib.check(self.L.ps_filter_bessel(self.handle, ctypes.c_void_p(samples.data_ptr()), ctypes.byref(fmt),
-                                           samples.numel(), int(order), float(cutoff), float(sampling_freq),
-                                           ctypes.c_void_p(out.data_ptr())), self.handle)
+        dev = _device_input(samples)
+        fmt = _fmt(samples, quantum, offset_counts, f64=True)
+        out = torch.empty(max(1, samples.numel()), dtype=torch.float64, device=dev)
+        _call(dev, self.L.ps_filter_bessel, self.handle, _addr(samples), ctypes.byref(fmt), samples.numel(), int(order), float(cutoff),
+              float(sampling_freq), _addr(out))
         return out[:samples.numel()]
 
     @_serialised
@@ -514,24 +530,18 @@ class Context(object):
         """ps_filter_requantise_batch: Event.filter + the re-quantisation for many events of ONE device-resident trace in one
         call (two host synchronisations for the batch instead of three per event).  Returns (filtered float64 CUDA tensor,
         rounded float32 CUDA tensor -- both the events back to back --, offsets int64 numpy [n_ev + 1], centres, steps)."""
-        assert samples.is_cuda and samples.is_contiguous() and samples.dim() == 1
-        fmt = _lib.SampleFormat(_lib.PS_DTYPE_F64, 0, 1.0) if samples.dtype == torch.float64 else self._fmt(samples, quantum, offset_counts)
-        ev_start = np.ascontiguousarray(ev_start, dtype=np.int64)
-        ev_len = np.ascontiguousarray(ev_len, dtype=np.int64)
+        dev = _device_input(samples)
+        fmt = _fmt(samples, quantum, offset_counts, f64=True)
+        (ev_start, st_p), (ev_len, ln_p) = _host(ev_start), _host(ev_len)
         n_ev = ev_start.size
-        off = np.concatenate(([0], np.cumsum(ev_len))).astype(np.int64)
+        off = _slot_offsets(ev_len)[0]
         total = int(off[-1])
-        filtered = torch.empty(max(1, total), dtype=torch.float64, device=samples.device)
-        rounded = torch.empty(max(1, total), dtype=torch.float32, device=samples.device)
-        centre = np.zeros(max(1, n_ev), dtype=np.float64)
-        step = np.zeros(max(1, n_ev), dtype=np.float64)
-        P64, PD = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double)
-        torch.cuda.current_stream(samples.device).synchronize()
-        _lib.check(self.L.ps_filter_requantise_batch(self.handle, ctypes.c_void_p(samples.data_ptr()), ctypes.byref(fmt),
-                                                     ev_start.ctypes.data_as(P64), ev_len.ctypes.data_as(P64), n_ev, int(order),
-                                                     float(cutoff), float(sampling_freq), ctypes.c_void_p(filtered.data_ptr()),
-                                                     ctypes.c_void_p(rounded.data_ptr()), centre.ctypes.data_as(PD), step.ctypes.data_as(PD)),
-                   self.handle)
+        filtered = torch.empty(max(1, total), dtype=torch.float64, device=dev)
+        rounded = torch.empty(max(1, total), dtype=torch.float32, device=dev)
+        centre, centre_p = _host(np.zeros(max(1, n_ev), dtype=np.float64), np.float64)
+        step, step_p = _host(np.zeros(max(1, n_ev), dtype=np.float64), np.float64)
+        _call(dev, self.L.ps_filter_requantise_batch, self.handle, _addr(samples), ctypes.byref(fmt), st_p, ln_p, n_ev, int(order),
+              float(cutoff), float(sampling_freq), _addr(filtered), _addr(rounded), centre_p, step_p)
         return filtered[:total], rounded[:total], off, centre[:n_ev], step[:n_ev]
 
     @_serialised
@@ -541,23 +551,19 @@ class Context(object):
         (float32 on the grid `quantum`, int16 counts, or float64 on no grid).  Returns (float64 CUDA tensor, the filtered
         events back to back, each bit for bit what filter_bessel returns for it alone; offsets int64 numpy [n_ev + 1]).  One
         launch on the fused order-1 route, one host synchronisation for the batch."""
-        assert samples.is_cuda and samples.is_contiguous() and samples.dim() == 1
-        fmt = _lib.SampleFormat(_lib.PS_DTYPE_F64, 0, 1.0) if samples.dtype == torch.float64 else self._fmt(samples, quantum, offset_counts)
-        ev_start = np.ascontiguousarray(ev_start, dtype=np.int64)
-        ev_len = np.ascontiguousarray(ev_len, dtype=np.int64)
+        dev = _device_input(samples)
+        fmt = _fmt(samples, quantum, offset_counts, f64=True)
+        (ev_start, st_p), (ev_len, ln_p) = _host(ev_start), _host(ev_len)
         if ev_start.shape != ev_len.shape or ev_start.ndim != 1:
             raise ValueError("ev_start and ev_len must be one-dimensional and of one length")
         n_ev = ev_start.size
         if n_ev and (int(ev_start.min()) < 0 or int(ev_len.min()) < 0 or int((ev_start + ev_len).max()) > samples.numel()):
             raise ValueError("an event lies outside the samples")
-        off = np.concatenate(([0], np.cumsum(ev_len))).astype(np.int64)
+        off = _slot_offsets(ev_len)[0]
         total = int(off[-1])
-        out = torch.empty(max(1, total), dtype=torch.float64, device=samples.device)
-        P64 = ctypes.POINTER(ctypes.c_int64)
-        torch.cuda.current_stream(samples.device).synchronize()
-        _lib.check(self.L.ps_filter_bessel_batch(self.handle, ctypes.c_void_p(samples.data_ptr()), ctypes.byref(fmt),
-                                                 ev_start.ctypes.data_as(P64), ev_len.ctypes.data_as(P64), n_ev, int(order),
-                                                 float(cutoff), float(sampling_freq), ctypes.c_void_p(out.data_ptr())), self.handle)
+        out = torch.empty(max(1, total), dtype=torch.float64, device=dev)
+        _call(dev, self.L.ps_filter_bessel_batch, self.handle, _addr(samples), ctypes.byref(fmt), st_p, ln_p, n_ev, int(order),
+              float(cutoff), float(sampling_freq), _addr(out))
         return out[:total], off
 
     @_serialised
@@ -568,19 +574,15 @@ class Context(object):
         whatever their number, one download.  Exact integer sums: the same ranges give the same bits however option
         "range_tile" cuts them.  An empty or reversed range, one that leaves the samples, or float64 samples: ValueError,
         nothing is launched."""
-        assert samples.is_cuda and samples.is_contiguous() and samples.dim() == 1
-        fmt = _lib.SampleFormat(_lib.PS_DTYPE_F64, 0, 1.0) if samples.dtype == torch.float64 else self._fmt(samples, quantum, offset_counts)
-        starts = np.ascontiguousarray(starts, dtype=np.int64)
-        ends = np.ascontiguousarray(ends, dtype=np.int64)
+        dev = _device_input(samples)
+        fmt = _fmt(samples, quantum, offset_counts, f64=True)        # (float64: passed on for the library to refuse in its own words)
+        (starts, starts_p), (ends, ends_p) = _host(starts), _host(ends)
         if starts.shape != ends.shape or starts.ndim != 1:
             raise ValueError("starts and ends must be one-dimensional and of one length")
         n_ranges = starts.size
-        out = torch.empty((max(1, n_ranges), 4), dtype=torch.float64, device=samples.device)
-        P64 = ctypes.POINTER(ctypes.c_int64)
-        torch.cuda.current_stream(samples.device).synchronize()
-        _lib.check(self.L.ps_range_stats(self.handle, ctypes.c_void_p(samples.data_ptr()), ctypes.byref(fmt), samples.numel(),
-                                         starts.ctypes.data_as(P64), ends.ctypes.data_as(P64), n_ranges, ctypes.c_void_p(out.data_ptr())),
-                   self.handle)
+        out = torch.empty((max(1, n_ranges), 4), dtype=torch.float64, device=dev)
+        _call(dev, self.L.ps_range_stats, self.handle, _addr(samples), ctypes.byref(fmt), samples.numel(), starts_p, ends_p, n_ranges,
+              _addr(out))
         return out[:n_ranges].cpu().numpy()
 
     @_serialised
@@ -588,45 +590,39 @@ class Context(object):
         """ps_requantise: a filtered current (float64 CUDA tensor, pA) centred and rounded to the finest power-of-two
         grid that keeps its counts below 2**22.  Returns (float32 CUDA tensor on that grid, centre, step): segment it
         with quantum = step."""
-        assert current.is_cuda and current.is_contiguous() and current.dim() == 1 and current.dtype == torch.float64
-        out = torch.empty(max(1, current.numel()), dtype=torch.float32, device=current.device)
+        dev = _device_input(current, dtype=torch.float64)
+        out = torch.empty(max(1, current.numel()), dtype=torch.float32, device=dev)
         centre, step = ctypes.c_double(), ctypes.c_double()
-        torch.cuda.current_stream(current.device).synchronize()
-        _lib.check(self.L.ps_requantise(self.handle, ctypes.c_void_p(current.data_ptr()), current.numel(),
-                                        ctypes.c_void_p(out.data_ptr()), ctypes.byref(centre), ctypes.byref(step)), self.handle)
+        _call(dev, self.L.ps_requantise, self.handle, _addr(current), current.numel(), _addr(out), ctypes.byref(centre), ctypes.byref(step))
         return out[:current.numel()], centre.value, step.value
 
     @_serialised
     def grid_check(self, current, origin, quantum, tol=1e-6):
         """ps_grid_check_f64: a candidate grid origin + k * quantum tried on every sample of a float64 CUDA tensor.  Returns
         _lib.GridReport (max |k - rint k|, the smallest one above tol, min and max rint k, non-finite samples)."""
-        assert current.is_cuda and current.is_contiguous() and current.dim() == 1 and current.dtype == torch.float64
+        dev = _device_input(current, dtype=torch.float64)
         r = _lib.GridReport()
-        torch.cuda.current_stream(current.device).synchronize()
-        _lib.check(self.L.ps_grid_check_f64(self.handle, ctypes.c_void_p(current.data_ptr()), current.numel(), float(origin),
-                                            float(quantum), float(tol), ctypes.byref(r)), self.handle)
+        _call(dev, self.L.ps_grid_check_f64, self.handle, _addr(current), current.numel(), float(origin), float(quantum), float(tol),
+              ctypes.byref(r))
         return r
 
     @_serialised
     def grid_counts(self, current, origin, quantum, centre):
         """ps_grid_counts_f64: int16 CUDA tensor of rint((x - origin) / quantum) - centre, for a grid that grid_check
         confirmed and whose re-centred range the caller found inside int16."""
-        assert current.is_cuda and current.is_contiguous() and current.dim() == 1 and current.dtype == torch.float64
-        out = torch.empty(current.numel(), dtype=torch.int16, device=current.device)
-        torch.cuda.current_stream(current.device).synchronize()
-        _lib.check(self.L.ps_grid_counts_f64(self.handle, ctypes.c_void_p(current.data_ptr()), current.numel(), float(origin),
-                                             float(quantum), int(centre), ctypes.c_void_p(out.data_ptr())), self.handle)
+        dev = _device_input(current, dtype=torch.float64)
+        out = torch.empty(current.numel(), dtype=torch.int16, device=dev)
+        _call(dev, self.L.ps_grid_counts_f64, self.handle, _addr(current), current.numel(), float(origin), float(quantum), int(centre),
+              _addr(out))
         return out
 
     @_serialised
     def narrow_f64(self, current):
         """ps_narrow_f64: (float32 CUDA tensor of a float64 one, the number of samples the conversion changed)."""
-        assert current.is_cuda and current.is_contiguous() and current.dim() == 1 and current.dtype == torch.float64
-        out = torch.empty(current.numel(), dtype=torch.float32, device=current.device)
+        dev = _device_input(current, dtype=torch.float64)
+        out = torch.empty(current.numel(), dtype=torch.float32, device=dev)
         bad = ctypes.c_int64()
-        torch.cuda.current_stream(current.device).synchronize()
-        _lib.check(self.L.ps_narrow_f64(self.handle, ctypes.c_void_p(current.data_ptr()), current.numel(),
-                                        ctypes.c_void_p(out.data_ptr()), ctypes.byref(bad)), self.handle)
+        _call(dev, self.L.ps_narrow_f64, self.handle, _addr(current), current.numel(), _addr(out), ctypes.byref(bad))
         return out, bad.value
 
     @_serialised
@@ -636,21 +632,17 @@ class Context(object):
         (numpy); sequence arrays: float64 CUDA tensors, sequence q = [seq_off[q], seq_off[q+1]).  Returns CUDA tensors
         (scores float64 [n_seq] = score[s-1][m-1], paths uint32-as-int64 view avoided: int32 bits of the reference's
         unsigned j [total], status int32 [n_seq])."""
-        mm, ms, md = (np.ascontiguousarray(a, dtype=np.float64) for a in (model_means, model_stds, model_durs))
+        (mm, mm_p), (ms, ms_p), (md, md_p) = (_host(a, np.float64) for a in (model_means, model_stds, model_durs))
         assert mm.size == ms.size == md.size
-        off, off_p = _offsets(seq_off)
+        off, off_p = _host(seq_off)
         n_seq = off.size - 1
         assert min(t.numel() for t in (seq_means, seq_stds, seq_durs)) >= int(off[-1])
-        dev = _f64_device(seq_means, seq_stds, seq_durs)
+        dev = _device_input(seq_means, seq_stds, seq_durs, dtype=torch.float64, one_dim=False)
         scores = torch.zeros(max(n_seq, 1), dtype=torch.float64, device=dev)
         paths = torch.zeros(max(int(off[-1]), 1), dtype=torch.int32, device=dev)
         status = torch.zeros(max(n_seq, 1), dtype=torch.int32, device=dev)
-        torch.cuda.current_stream(dev).synchronize()
-        dp = ctypes.POINTER(ctypes.c_double)
-        _lib.check(self.L.ps_align_batch(self.handle, mm.ctypes.data_as(dp), ms.ctypes.data_as(dp), md.ctypes.data_as(dp),
-                                         mm.size, float(skip_penalty), float(backslip_penalty), _ptr(seq_means),
-                                         _ptr(seq_stds), _ptr(seq_durs), off_p, n_seq, _ptr(scores), _ptr(paths),
-                                         _ptr(status)), self.handle)
+        _call(dev, self.L.ps_align_batch, self.handle, mm_p, ms_p, md_p, mm.size, float(skip_penalty), float(backslip_penalty),
+              _ptr(seq_means), _ptr(seq_stds), _ptr(seq_durs), off_p, n_seq, _ptr(scores), _ptr(paths), _ptr(status))
         return scores[:n_seq], paths[:int(off[-1])], status[:n_seq]
 
     @_serialised
@@ -658,14 +650,13 @@ class Context(object):
         """ps_pairwise_scores: every pair of the sequence sets A x B on the score-only route.  a, b: float64 CUDA tensors
         (NaN: the gap marker), set k of A = a[a_off[k]:a_off[k+1]].  Returns (scores float64 [n_a, n_b], positions int32
         [n_a, n_b, 2] of the local maximum or None)."""
-        (a_off, a_off_p), (b_off, b_off_p) = _offsets(a_off), _offsets(b_off)
+        (a_off, a_off_p), (b_off, b_off_p) = _host(a_off), _host(b_off)
         n_a, n_b = a_off.size - 1, b_off.size - 1
-        dev = _f64_device(a, b)
+        dev = _device_input(a, b, dtype=torch.float64, one_dim=False)
         scores = torch.zeros((n_a, n_b), dtype=torch.float64, device=dev)
         pos = torch.zeros((n_a, n_b, 2), dtype=torch.int32, device=dev) if want_pos else None
-        torch.cuda.current_stream(dev).synchronize()
-        _lib.check(self.L.ps_pairwise_scores(self.handle, _ptr(a), a_off_p, n_a, _ptr(b), b_off_p, n_b, int(mode),
-                                             float(penalty), _ptr(scores), _ptr(pos)), self.handle)
+        _call(dev, self.L.ps_pairwise_scores, self.handle, _ptr(a), a_off_p, n_a, _ptr(b), b_off_p, n_b, int(mode), float(penalty),
+              _ptr(scores), _ptr(pos))
         return scores, pos
 
     @_serialised
@@ -675,12 +666,11 @@ class Context(object):
         status [n], cols_i, cols_j (index columns in walk order, -1 a gap), col_off [n + 1], aln_score, aln_start, aln_len,
         aln_off [n + 1], aln_count [n]).  Slots that turn out too small (PS_ERR_CAPACITY) make the call run again with
         the sizes the first run reported."""
-        (a_off, a_off_p), (b_off, b_off_p) = _offsets(a_off), _offsets(b_off)
-        pair_a = np.ascontiguousarray(pair_a, dtype=np.int32)
-        pair_b = np.ascontiguousarray(pair_b, dtype=np.int32)
+        (a_off, a_off_p), (b_off, b_off_p) = _host(a_off), _host(b_off)
+        (pair_a, pair_a_p), (pair_b, pair_b_p) = _host(pair_a, np.int32), _host(pair_b, np.int32)
         n = pair_a.size
         assert pair_b.size == n
-        dev = _f64_device(a, b)
+        dev = _device_input(a, b, dtype=torch.float64, one_dim=False)
         if n and (pair_a.min() < 0 or pair_a.max() >= a_off.size - 1 or pair_b.min() < 0 or pair_b.max() >= b_off.size - 1):
             raise ValueError("a pair names a sequence that is not there")
         m_len = np.diff(a_off)[pair_a] if n else np.zeros(0, np.int64)
@@ -691,24 +681,20 @@ class Context(object):
             aln_slots = np.ones(n, np.int64) if mode != _lib.PS_PW_LOCAL_REPEATED else np.minimum(m_len, n_len) + 1
         scores = torch.zeros(max(n, 1), dtype=torch.float64, device=dev)
         status, col_need, aln_count = (torch.zeros(max(n, 1), dtype=torch.int32, device=dev) for _ in range(3))
-        i32p = ctypes.POINTER(ctypes.c_int32)
-        torch.cuda.current_stream(dev).synchronize()
-        for attempt in range(2):
-            col_off, col_off_p = _offsets(np.concatenate(([0], np.cumsum(col_slots))))
-            aln_off, aln_off_p = _offsets(np.concatenate(([0], np.cumsum(aln_slots))))
+
+        def attempt(col_slots, aln_slots):
+            (col_off, col_off_p), (aln_off, aln_off_p) = _slot_offsets(col_slots), _slot_offsets(aln_slots)
             cols = torch.zeros((2, max(int(col_off[-1]), 1)), dtype=torch.int32, device=dev)
             aln_score = torch.zeros(max(int(aln_off[-1]), 1), dtype=torch.float64, device=dev)
             aln_il = torch.zeros((2, max(int(aln_off[-1]), 1)), dtype=torch.int32, device=dev)
-            rc = self.L.ps_pairwise_batch(
-                self.handle, _ptr(a), a_off_p, a_off.size - 1, _ptr(b), b_off_p, b_off.size - 1, pair_a.ctypes.data_as(i32p),
-                pair_b.ctypes.data_as(i32p), n, int(mode), float(penalty), int(min_length), _ptr(scores), _ptr(status),
-                col_off_p, _ptr(cols[0]), _ptr(cols[1]), _ptr(col_need), aln_off_p, _ptr(aln_score), _ptr(aln_il[0]),
-                _ptr(aln_il[1]), _ptr(aln_count))
-            if rc != _lib.PS_ERR_CAPACITY or attempt:
-                break
-            col_slots = col_need[:n].cpu().numpy().astype(np.int64)       # the exact sizes
-            aln_slots = aln_count[:n].cpu().numpy().astype(np.int64)
-        _lib.check(rc, self.handle)
+            rc = _call_rc(dev, self.L.ps_pairwise_batch, self.handle, _ptr(a), a_off_p, a_off.size - 1, _ptr(b), b_off_p, b_off.size - 1,
+                          pair_a_p, pair_b_p, n, int(mode), float(penalty), int(min_length), _ptr(scores), _ptr(status), col_off_p,
+                          _ptr(cols[0]), _ptr(cols[1]), _ptr(col_need), aln_off_p, _ptr(aln_score), _ptr(aln_il[0]), _ptr(aln_il[1]),
+                          _ptr(aln_count))
+            return rc, (col_off, cols, aln_off, aln_score, aln_il)
+
+        _, (col_off, cols, aln_off, aln_score, aln_il) = _retry_slots(
+            self.handle, attempt, lambda: (_int64_host(col_need, n), _int64_host(aln_count, n)), (col_slots, aln_slots))
         cols, aln_il = cols.cpu().numpy(), aln_il.cpu().numpy()
         return (scores[:n].cpu().numpy(), status[:n].cpu().numpy(), cols[0], cols[1], col_off, aln_score.cpu().numpy(),
                 aln_il[0], aln_il[1], aln_off, aln_count[:n].cpu().numpy())
@@ -722,27 +708,24 @@ class Context(object):
         slot are counted, not stored (PS_ERR_CAPACITY); with retry the call then runs again with slots of the exact counts
         and rc is PS_OK; without, rc is returned as it is (PS_OK or PS_ERR_CAPACITY) with whatever fitted and the true
         counts.  Any other status raises."""
-        off, off_p = _offsets(off)
+        off, off_p = _host(off)
         n = off.size - 1
-        dev = _f64_device(mean, std)
+        dev = _device_input(mean, std, dtype=torch.float64, one_dim=False)
         if slots is None:
             slots = np.diff(off)
         slots = np.asarray(slots, np.int64).reshape(-1)
         assert slots.size == n
         count, status = (torch.zeros(max(n, 1), dtype=torch.int32, device=dev) for _ in range(2))
-        torch.cuda.current_stream(dev).synchronize()
-        for attempt in range(2):
-            slot_off, slot_off_p = _offsets(np.concatenate(([0], np.cumsum(slots))))
+
+        def attempt(slots):
+            slot_off, slot_off_p = _slot_offsets(slots)
             score = torch.zeros(max(int(slot_off[-1]), 1), dtype=torch.float64, device=dev)
             lij = torch.zeros((3, max(int(slot_off[-1]), 1)), dtype=torch.int32, device=dev)
-            rc = self.L.ps_trf_split_batch(self.handle, _ptr(mean), _ptr(std), off_p, n, float(penalty), float(min_score),
-                                           int(max_repeats), _ptr(score), _ptr(lij[0]), _ptr(lij[1]), _ptr(lij[2]), slot_off_p,
-                                           _ptr(count), _ptr(status))
-            if rc != _lib.PS_ERR_CAPACITY or attempt or not retry:
-                break
-            slots = count[:n].cpu().numpy().astype(np.int64)                  # the exact counts
-        if rc != _lib.PS_ERR_CAPACITY or retry:
-            _lib.check(rc, self.handle)
+            rc = _call_rc(dev, self.L.ps_trf_split_batch, self.handle, _ptr(mean), _ptr(std), off_p, n, float(penalty), float(min_score),
+                          int(max_repeats), _ptr(score), _ptr(lij[0]), _ptr(lij[1]), _ptr(lij[2]), slot_off_p, _ptr(count), _ptr(status))
+            return rc, (slot_off, score, lij)
+
+        rc, (slot_off, score, lij) = _retry_slots(self.handle, attempt, lambda: (_int64_host(count, n),), (slots,), retry)
         lij = lij.cpu().numpy()
         return rc, score.cpu().numpy(), lij[0], lij[1], lij[2], slot_off, count[:n].cpu().numpy(), status[:n].cpu().numpy()
 
@@ -753,32 +736,26 @@ class Context(object):
         [off[-1] + n_seq, n_states] or None, and for Viterbi: (path int32 tensor, path offsets, path lengths int32 tensor)
         -- else None).  A Viterbi path longer than its slot (path_slots[q] entries, default 2 (n + 1) + the silent states + 1)
         makes the call run again with slots of the exact lengths (PS_ERR_CAPACITY)."""
-        off, off_p = _offsets(off)
+        off, off_p = _host(off)
         n_seq = off.size - 1
-        dev = _f64_device(obs)
+        dev = _device_input(obs, dtype=torch.float64, one_dim=False)
         S = model.n_states
         logp = torch.empty(max(n_seq, 1), dtype=torch.float64, device=dev)
         mat = torch.empty((int(off[-1]) + n_seq, S), dtype=torch.float64, device=dev) if want_mat else None
-        torch.cuda.current_stream(dev).synchronize()
-
-        def call(path, path_off_p, path_len):
-            return self.L.ps_hmm_batch(self.handle, ctypes.byref(model), int(mode), _ptr(obs), off_p, n_seq, _ptr(logp),
-                                       _ptr(mat), _ptr(path), path_off_p, _ptr(path_len))
-
+        args = (self.L.ps_hmm_batch, self.handle, ctypes.byref(model), int(mode), _ptr(obs), off_p, n_seq, _ptr(logp), _ptr(mat))
         if mode != _lib.PS_HMM_VITERBI:
-            _lib.check(call(None, None, None), self.handle)
+            _call(dev, *args, None, None, None)
             return logp[:n_seq], mat, None
         if path_slots is None:
             path_slots = 2 * (np.diff(off) + 1) + (S - model.n_emit) + 1
         path_len = torch.empty(max(n_seq, 1), dtype=torch.int32, device=dev)
-        for attempt in range(2):
-            path_off, path_off_p = _offsets(np.concatenate(([0], np.cumsum(path_slots))))
+
+        def attempt(path_slots):
+            path_off, path_off_p = _slot_offsets(path_slots)
             path = torch.empty(max(int(path_off[-1]), 1), dtype=torch.int32, device=dev)
-            rc = call(path, path_off_p, path_len)
-            if rc != _lib.PS_ERR_CAPACITY or attempt:
-                break
-            path_slots = path_len[:n_seq].cpu().numpy().astype(np.int64)      # the exact lengths
-        _lib.check(rc, self.handle)
+            return _call_rc(dev, *args, _ptr(path), path_off_p, _ptr(path_len)), (path, path_off)
+
+        _, (path, path_off) = _retry_slots(self.handle, attempt, lambda: (_int64_host(path_len, n_seq),), (path_slots,))
         return logp[:n_seq], mat, (path, path_off, path_len[:n_seq])
 
     @_serialised
@@ -790,18 +767,17 @@ class Context(object):
         vector model (kind 4), whose obs holds n_dim doubles per observation; the caller, who built the model, says which
         (pypore_amd.hmm.Model._stat_width).  mix_rows: the mixture components of a model with kind-7 states (mix_ptr[n_emit]):
         the statistics are then [n_emit + mix_rows, 3], the states' rows followed by one row per component."""
-        off, off_p = _offsets(off)
+        off, off_p = _host(off)
         n_seq = off.size - 1
-        dev = _f64_device(obs)
+        dev = _device_input(obs, dtype=torch.float64, one_dim=False)
         n_edges = int(ctypes.cast(model.out_ptr, ctypes.POINTER(ctypes.c_int32))[model.n_states])
         logp = torch.empty(max(n_seq, 1), dtype=torch.float64, device=dev)
         counts = torch.empty(max(n_edges, 1), dtype=torch.float64, device=dev)
         rows = model.n_emit + int(mix_rows)
         stats = torch.empty((max(rows, 1), int(stat_width)), dtype=torch.float64, device=dev)
         skipped = ctypes.c_int32(0)
-        torch.cuda.current_stream(dev).synchronize()
-        _lib.check(self.L.ps_hmm_expect(self.handle, ctypes.byref(model), _ptr(obs), off_p, n_seq, _ptr(logp), _ptr(counts),
-                                        _ptr(stats), ctypes.byref(skipped)), self.handle)
+        _call(dev, self.L.ps_hmm_expect, self.handle, ctypes.byref(model), _ptr(obs), off_p, n_seq, _ptr(logp), _ptr(counts), _ptr(stats),
+              ctypes.byref(skipped))
         return logp[:n_seq], counts[:n_edges], stats[:rows], int(skipped.value)
 
     @_serialised
@@ -811,18 +787,17 @@ class Context(object):
         float64 [n_seq]; log posteriors float64 [off[-1], n_emit] when want_post; MAP states int32 [off[-1]] and MAP log
         probabilities float64 [n_seq] when want_map; per-sequence edge counts float64 [n_seq, n_edges] in out-edge order
         when want_counts), None for what was not asked for: only the outputs asked for are allocated."""
-        off, off_p = _offsets(off)
+        off, off_p = _host(off)
         n_seq, total = off.size - 1, int(off[-1])
-        dev = _f64_device(obs)
+        dev = _device_input(obs, dtype=torch.float64, one_dim=False)
         n_edges = int(ctypes.cast(model.out_ptr, ctypes.POINTER(ctypes.c_int32))[model.n_states])
         logp = torch.empty(max(n_seq, 1), dtype=torch.float64, device=dev)
         post = torch.empty((total, model.n_emit), dtype=torch.float64, device=dev) if want_post else None
         map_state = torch.empty(total, dtype=torch.int32, device=dev) if want_map else None
         map_logp = torch.empty(max(n_seq, 1), dtype=torch.float64, device=dev) if want_map else None
         counts = torch.empty((n_seq, n_edges), dtype=torch.float64, device=dev) if want_counts else None
-        torch.cuda.current_stream(dev).synchronize()
-        _lib.check(self.L.ps_hmm_posterior(self.handle, ctypes.byref(model), _ptr(obs), off_p, n_seq, _ptr(logp), _ptr(post),
-                                           _ptr(map_state), _ptr(map_logp), _ptr(counts)), self.handle)
+        _call(dev, self.L.ps_hmm_posterior, self.handle, ctypes.byref(model), _ptr(obs), off_p, n_seq, _ptr(logp), _ptr(post),
+              _ptr(map_state), _ptr(map_logp), _ptr(counts))
         return logp[:n_seq], post, map_state, map_logp[:n_seq] if want_map else None, counts
 
     @_serialised
@@ -847,25 +822,22 @@ class Context(object):
         lens = torch.empty(max(n_seq, 1), dtype=torch.int32, device=dev)
         flags = torch.empty(max(n_seq, 1), dtype=torch.int32, device=dev)
         path_len = torch.empty(max(n_seq, 1), dtype=torch.int32, device=dev) if want_path else None
-        torch.cuda.current_stream(dev).synchronize()
-        for attempt in range(2):
-            off, off_p = _offsets(np.concatenate(([0], np.cumsum(obs_slots))))
+
+        def attempt(obs_slots, path_slots):
+            off, off_p = _slot_offsets(obs_slots)
             obs = torch.empty((max(int(off[-1]), 1), D), dtype=torch.float64, device=dev)
             path = path_off = path_off_p = None
             if want_path:
-                path_off, path_off_p = _offsets(np.concatenate(([0], np.cumsum(np.asarray(path_slots, np.int64).reshape(-1)))))
+                path_off, path_off_p = _slot_offsets(np.asarray(path_slots, np.int64).reshape(-1))
                 path = torch.empty(max(int(path_off[-1]), 1), dtype=torch.int32, device=dev)
-            rc = self.L.ps_hmm_sample(self.handle, ctypes.byref(model), ctypes.byref(tables),
-                                      ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(first), n_seq, int(length),
-                                      int(max_length), ctypes.c_void_p(obs.data_ptr()), off_p, _ptr(lens), _ptr(flags),
-                                      ctypes.c_void_p(path.data_ptr()) if want_path else None, path_off_p, _ptr(path_len))
-            if rc != _lib.PS_ERR_CAPACITY or attempt or not retry:
-                break
-            obs_slots = lens[:n_seq].cpu().numpy().astype(np.int64)           # the exact lengths
-            if want_path:
-                path_slots = path_len[:n_seq].cpu().numpy().astype(np.int64)
-        if rc != _lib.PS_ERR_CAPACITY or retry:
-            _lib.check(rc, self.handle)
+            rc = _call_rc(dev, self.L.ps_hmm_sample, self.handle, ctypes.byref(model), ctypes.byref(tables),
+                          ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(first), n_seq, int(length), int(max_length), _addr(obs),
+                          off_p, _ptr(lens), _ptr(flags), _ptr(path), path_off_p, _ptr(path_len))
+            return rc, (obs, off, path, path_off)
+
+        rc, (obs, off, path, path_off) = _retry_slots(
+            self.handle, attempt, lambda: (_int64_host(lens, n_seq), _int64_host(path_len, n_seq) if want_path else None),
+            (obs_slots, path_slots), retry)
         return rc, obs, off, lens[:n_seq], flags[:n_seq], ((path, path_off, path_len[:n_seq]) if want_path else None)
 
     @_serialised
@@ -875,20 +847,15 @@ class Context(object):
         of sample i is splitmix64(seed + (i + 1) * GOLDEN), so the piece is the same generator with a shifted seed and a
         table cut at `start`."""
         out = torch.empty(n, dtype=dtype, device="cuda:%d" % self.device)
-        seg_end = np.ascontiguousarray(seg_end, dtype=np.int64)
-        level_counts = np.ascontiguousarray(level_counts, dtype=np.int32)
+        seg_end = np.asarray(seg_end, dtype=np.int64)
+        level_counts = np.asarray(level_counts, dtype=np.int32)
         if start:
             first = int(np.searchsorted(seg_end, start, side="right"))
-            seg_end = np.ascontiguousarray(seg_end[first:] - start)
-            level_counts = np.ascontiguousarray(level_counts[first:])
+            seg_end, level_counts = seg_end[first:] - start, level_counts[first:]
             seed = (int(seed) + int(start) * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
-        torch.cuda.current_stream(out.device).synchronize()
-        _lib.check(self.L.ps_synth_trace(self.handle, ctypes.c_void_p(out.data_ptr()),
-                                         _lib.PS_DTYPE_F32 if dtype == torch.float32 else _lib.PS_DTYPE_I16,
-                                         n, ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
-                                         seg_end.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                                         level_counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), seg_end.size),
-                   self.handle)
+        (seg_end, seg_end_p), (level_counts, level_counts_p) = _host(seg_end), _host(level_counts, np.int32)
+        _call(out.device, self.L.ps_synth_trace, self.handle, _addr(out), _lib.PS_DTYPE_F32 if dtype == torch.float32 else _lib.PS_DTYPE_I16,
+              n, ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), seg_end_p, level_counts_p, seg_end.size)
         return out
 
 

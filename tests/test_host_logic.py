@@ -24,6 +24,57 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert b"gfx950" in L.ps_version()
 
 
+def header_prototypes():
+    """name -> (return type, [parameter, ...]) of every function include/poreseg.h declares, as kinds: "ptr", "i32" (int and
+    int32_t), "i64", "u64", "f64", and "void" for a function that returns nothing."""
+    text = open(os.path.join(ROOT, "include", "poreseg.h")).read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    text = "\n".join(line for line in text.splitlines() if not line.lstrip().startswith("#"))
+    scalar = {"int": "i32", "int32_t": "i32", "int64_t": "i64", "uint64_t": "u64", "double": "f64", "void": "void"}
+
+    def kind(decl, named):
+        if "*" in decl:
+            return "ptr"
+        words = [w for w in decl.split() if w != "const"]
+        assert len(words) == (2 if named else 1), decl
+        return scalar[words[0]]
+
+    protos = {}
+    for statement in re.split(r"[;{}]", text):
+        m = re.match(r"\s*([\w\s\*]+?)\b(ps_[a-z_0-9]+)\s*\((.*)\)\s*$", statement, flags=re.S)
+        if not m or "typedef" in m.group(1):
+            continue
+        params = [p.strip() for p in m.group(3).split(",")]
+        protos[m.group(2)] = (kind(m.group(1), False), [] if params == ["void"] else [kind(p, True) for p in params])
+    return protos
+
+
+def ctypes_kind(t):
+    if t is None:
+        return "void"
+    if issubclass(t, (ctypes._Pointer, ctypes.c_void_p, ctypes.c_char_p)):
+        return "ptr"
+    return {ctypes.c_int32: "i32", ctypes.c_int64: "i64", ctypes.c_uint64: "u64", ctypes.c_double: "f64"}[t]
+
+
+def test_every_signature_matches_the_header():
+    """The ctypes declaration of all 48 functions against the header's prototype: arity, the kind of every parameter, the kind
+    of the result.  They are in force as soon as _lib.lib() returns -- one table, applied in one place: nothing in the binding
+    assigns argtypes later, so no call can go out with ctypes' guess of a 64-bit argument."""
+    protos = header_prototypes()
+    assert len(protos) == 48 and set(protos) == set(_lib.EXPORTS)
+    L = _lib.lib()
+    for name, (ret, params) in sorted(protos.items()):
+        fn = getattr(L, name)
+        assert fn.argtypes is not None, name
+        assert [ctypes_kind(t) for t in fn.argtypes] == params, name
+        assert ctypes_kind(fn.restype) == ret, name
+    from pypore_amd import engine
+    assert "argtypes" not in open(engine.__file__).read()
+    assert len(re.findall(r"\.argtypes\s*=", open(_lib.__file__).read())) == 1
+
+
 def test_comm_library_loads_and_exports_every_declared_symbol():
     """libporeseg_comm.so (include/poreseg_comm.h: SURVEY 8(b)'s ps_comm_init_all / ps_gather_bounds); no call that needs a GPU."""
     from pypore_amd import _comm
