@@ -2705,24 +2705,29 @@ namespace {
 // 8-byte tables before 4-byte ones).  The first `head` bytes are not copied from anywhere: fill(h_up) writes them in place.
 struct HostTable { const void *p; size_t bytes; };
 template <typename Fill>
-int upload_tables(ps_ctx *ctx, DevBuf &dev, size_t head, Fill &&fill, std::initializer_list<HostTable> tables)
+int upload_tables(ps_ctx *ctx, DevBuf &dev, size_t head, Fill &&fill, const HostTable *first, const HostTable *last)
 {
     size_t bytes = head;
-    for (const HostTable &t : tables) bytes += t.bytes;
+    for (const HostTable *t = first; t != last; ++t) bytes += t->bytes;
     HIP_TRY(ctx, ctx->h_up.reserve(bytes));
     HIP_TRY(ctx, dev.reserve(bytes));
     fill(ctx->h_up.p);
     char *h = static_cast<char *>(ctx->h_up.p) + head;
-    for (const HostTable &t : tables) {
-        if (t.bytes) std::memcpy(h, t.p, t.bytes);
-        h += t.bytes;
+    for (const HostTable *t = first; t != last; ++t) {
+        if (t->bytes) std::memcpy(h, t->p, t->bytes);
+        h += t->bytes;
     }
     HIP_TRY(ctx, hipMemcpyAsync(dev.p, ctx->h_up.p, bytes, hipMemcpyHostToDevice, ctx->stream));
     return PS_OK;
 }
+template <typename Fill>
+int upload_tables(ps_ctx *ctx, DevBuf &dev, size_t head, Fill &&fill, std::initializer_list<HostTable> tables)
+{
+    return upload_tables(ctx, dev, head, fill, tables.begin(), tables.end());
+}
 int upload_tables(ps_ctx *ctx, DevBuf &dev, std::initializer_list<HostTable> tables)
 {
-    return upload_tables(ctx, dev, 0, [](void *) {}, tables);
+    return upload_tables(ctx, dev, 0, [](void *) {}, tables.begin(), tables.end());
 }
 
 // The sample format of a filter call as the kernels' DevCfg: float32 on a grid / int16 counts as everywhere, or -- the filter
@@ -3488,178 +3493,37 @@ int ps_trf_split_batch(ps_ctx *ctx, const double *d_mean, const double *d_std, c
 
 namespace {
 
-// ps_hmm_batch: the model's arrays checked and packed into one blob (doubles first, then ints); the device copy is reused
-// while the blob is unchanged.  *has_kde: some state is a kernel density (kind 3); only then are the model's kde_* fields read,
-// checked and appended to the blob (points and log weights after the doubles, the CSR offsets after the ints).  *V, *has_vec:
-// the same for a vector model (every emitting state kind 4): only then are n_dim and the comp_* fields read, checked and
-// appended (parameters and weights after the doubles; the component kinds and n_dim after the ints), so a changed weight
-// or parameter is a changed blob.  *X, *has_mix: the same for a model with mixture states (kind 7): only then are mix_ptr,
-// mix_kind, mix_param and mix_lw read, checked and appended (parameters and log weights last among the doubles; the CSR
-// offsets and the component kinds last among the ints), so a changed weight, parameter, kind or split is a changed blob.
-// mix_cdf and mix_draw are ps_hmm_sample's and are not read here.
-constexpr int64_t HMM_KDE_POINTS_MAX = 1 << 24;
-constexpr int64_t HMM_MIX_COMPONENTS_MAX = 1 << 24;
-int hmm_upload(ps_ctx *ctx, const ps_hmm_model *m, HmmDevK *D, HmmDevV *V, HmmDevM *X, int *max_in, bool *has_kde, bool *has_vec,
-               bool *has_mix)
+// A sequence-model call's model: the sizes and decisions hmm_plan.hpp derives from it (I), and the kernels' structs aimed at its
+// device copy.  A vector model takes the HmmDevV instantiations, one with mixture states the HmmDevM ones, one with
+// kernel-density states (and no mixture) the HmmDevK ones, any other the HmmDev ones.
+struct HmmCall {
+    HmmModelInfo I;
+    HmmDevK DK;
+    HmmDevV DV;
+    HmmDevM DM;
+    const long long *d_off = nullptr;
+};
+template <typename F> int with_model(const HmmCall &C, F &&f)
 {
-    const int S = m->n_states, NE = m->n_emit, NL = m->n_levels;
-    if (S < 1 || S > HMM_S_MAX) return fail(ctx, PS_ERR_ARG, "model of %d states: the device HMM kernels take 1..%d", S, HMM_S_MAX);
-    if (NE < 0 || NE > S || NL < 0 || NL > S - NE || (NL == 0) != (NE == S)) return fail(ctx, PS_ERR_ARG, "bad state / level counts");
-    if (m->start < NE || m->start >= S || m->end < NE || m->end >= S) return fail(ctx, PS_ERR_ARG, "start and end must be silent states");
-    if (!m->kind || !m->level_ptr || !m->in_ptr || !m->out_ptr) return fail(ctx, PS_ERR_ARG, "null model array");
-    bool kde = false, vec = false, plain = false, mix = false;
-    for (int k = 0; k < S; ++k) {
-        const int kd = m->kind[k];
-        if ((k < NE) != (kd == HMM_NORMAL || kd == HMM_UNIFORM || kd == HMM_KDE || kd == HMM_VECTOR || kd == HMM_MIXTURE) || (k >= NE && kd != HMM_SILENT))
-            return fail(ctx, PS_ERR_ARG, "state %d: emitting states first, then silent ones", k);
-        kde = kde || kd == HMM_KDE;
-        vec = vec || kd == HMM_VECTOR;
-        mix = mix || kd == HMM_MIXTURE;
-        plain = plain || (k < NE && kd != HMM_VECTOR);
-    }
-    if (!vec && !m->param) return fail(ctx, PS_ERR_ARG, "null model array");      // (a vector model's param is not read)
-    size_t NC = 0;                                       // components of a vector model: n_emit * n_dim
-    if (vec) {
-        if (plain) return fail(ctx, PS_ERR_ARG, "a vector model's emitting states are all kind 4: kinds 1..3 cannot be mixed with it");
-        if (m->n_dim < 1 || m->n_dim > HMM_D_MAX) return fail(ctx, PS_ERR_ARG, "n_dim %d: a vector model takes 1..%d components", m->n_dim, HMM_D_MAX);
-        if (!m->comp_kind || !m->comp_param || !m->comp_w) return fail(ctx, PS_ERR_ARG, "a vector model needs comp_kind, comp_param and comp_w");
-        NC = static_cast<size_t>(NE) * m->n_dim;
-        for (size_t i = 0; i < NC; ++i) {
-            const int ck = m->comp_kind[i];
-            if (ck != HMM_NORMAL && ck != HMM_UNIFORM && ck != HMM_LOGNORMAL && ck != HMM_EXPONENTIAL)
-                return fail(ctx, PS_ERR_ARG, "component %lld: unknown component kind %d", static_cast<long long>(i), ck);
-            if (!std::isfinite(m->comp_w[i]) || !(m->comp_w[i] > 0.0))
-                return fail(ctx, PS_ERR_ARG, "component %lld: a weight must be finite and > 0", static_cast<long long>(i));
-        }
-    }
-    *has_vec = vec;
-    int64_t NP = 0;
-    if (kde) {
-        if (!m->kde_ptr || !m->kde_pt || !m->kde_lw) return fail(ctx, PS_ERR_ARG, "a kernel-density state needs kde_ptr, kde_pt and kde_lw");
-        if (m->kde_ptr[0] != 0) return fail(ctx, PS_ERR_ARG, "kde_ptr must start at 0");
-        for (int k = 0; k < NE; ++k) {
-            if (m->kde_ptr[k + 1] < m->kde_ptr[k]) return fail(ctx, PS_ERR_ARG, "descending kde_ptr at state %d", k);
-            if ((m->kde_ptr[k + 1] > m->kde_ptr[k]) != (m->kind[k] == HMM_KDE))
-                return fail(ctx, PS_ERR_ARG, "state %d: a kernel-density state has at least one point, any other state none", k);
-        }
-        NP = m->kde_ptr[NE];
-        if (NP > HMM_KDE_POINTS_MAX)
-            return fail(ctx, PS_ERR_ARG, "%lld kernel-density points: the device HMM kernels take at most %lld",
-                        static_cast<long long>(NP), static_cast<long long>(HMM_KDE_POINTS_MAX));
-        for (int64_t i = 0; i < NP; ++i)
-            if (!std::isfinite(m->kde_pt[i]) || !(m->kde_lw[i] <= 0.0))
-                return fail(ctx, PS_ERR_ARG, "kernel-density point %lld: points must be finite and log weights <= 0", static_cast<long long>(i));
-    }
-    *has_kde = kde;
-    int64_t NM = 0;                                      // mixture components in all
-    if (mix) {                                           // (never beside kind 4: refused above)
-        if (!m->mix_ptr || !m->mix_kind || !m->mix_param || !m->mix_lw)
-            return fail(ctx, PS_ERR_ARG, "a mixture state needs mix_ptr, mix_kind, mix_param and mix_lw");
-        if (m->mix_ptr[0] != 0) return fail(ctx, PS_ERR_ARG, "mix_ptr must start at 0");
-        for (int k = 0; k < NE; ++k) {
-            if (m->mix_ptr[k + 1] < m->mix_ptr[k]) return fail(ctx, PS_ERR_ARG, "descending mix_ptr at state %d", k);
-            if ((m->mix_ptr[k + 1] > m->mix_ptr[k]) != (m->kind[k] == HMM_MIXTURE))
-                return fail(ctx, PS_ERR_ARG, "state %d: a mixture state has at least one component, any other state none", k);
-        }
-        NM = m->mix_ptr[NE];
-        if (NM > HMM_MIX_COMPONENTS_MAX)
-            return fail(ctx, PS_ERR_ARG, "%lld mixture components: the device HMM kernels take at most %lld",
-                        static_cast<long long>(NM), static_cast<long long>(HMM_MIX_COMPONENTS_MAX));
-        for (int64_t i = 0; i < NM; ++i) {
-            const int ck = m->mix_kind[i];
-            if (ck != HMM_NORMAL && ck != HMM_UNIFORM && ck != HMM_LOGNORMAL && ck != HMM_EXPONENTIAL)
-                return fail(ctx, PS_ERR_ARG, "mixture component %lld: unknown component kind %d", static_cast<long long>(i), ck);
-            if (!(m->mix_lw[i] <= 0.0))
-                return fail(ctx, PS_ERR_ARG, "mixture component %lld: a log weight must be <= 0", static_cast<long long>(i));
-        }
-    }
-    *has_mix = mix;
-    if (m->level_ptr[0] != NE || m->level_ptr[NL] != S) return fail(ctx, PS_ERR_ARG, "levels must cover the silent states");
-    for (int L = 0; L < NL; ++L) if (m->level_ptr[L + 1] <= m->level_ptr[L]) return fail(ctx, PS_ERR_ARG, "empty or descending level %d", L);
-    std::vector<int> level(S, -1);
-    for (int L = 0; L < NL; ++L) for (int k = m->level_ptr[L]; k < m->level_ptr[L + 1]; ++k) level[k] = L;
-    const int32_t *ptrs[2] = {m->in_ptr, m->out_ptr}, *idx[2] = {m->in_src, m->out_dst};
-    int64_t n_edge[2];
-    *max_in = 0;
-    for (int d = 0; d < 2; ++d) {
-        if (ptrs[d][0] != 0) return fail(ctx, PS_ERR_ARG, "edge lists must start at 0");
-        for (int k = 0; k < S; ++k) {
-            if (ptrs[d][k + 1] < ptrs[d][k]) return fail(ctx, PS_ERR_ARG, "descending edge offsets");
-            if (d == 0) *max_in = std::max(*max_in, ptrs[d][k + 1] - ptrs[d][k]);
-        }
-        n_edge[d] = ptrs[d][S];
-        if (n_edge[d] > 0 && (!idx[d] || !(d ? m->out_lp : m->in_lp))) return fail(ctx, PS_ERR_ARG, "null edge array");
-        for (int k = 0; k < S; ++k)
-            for (int e = ptrs[d][k]; e < ptrs[d][k + 1]; ++e) {
-                const int o = idx[d][e];
-                if (o < 0 || o >= S) return fail(ctx, PS_ERR_ARG, "edge to a state out of range");
-                const int src = d ? k : o, dst = d ? o : k;
-                if (dst >= NE && src >= NE && level[src] >= level[dst]) return fail(ctx, PS_ERR_ARG, "silent edge %d -> %d does not go up a level", src, dst);
-            }
-    }
-    if (n_edge[0] != n_edge[1]) return fail(ctx, PS_ERR_ARG, "in- and out-edge lists differ in length");
-    if (*max_in > 65535) return fail(ctx, PS_ERR_ARG, "a state with %d in-edges: the device HMM kernels take at most 65535", *max_in);
-    const size_t nd0 = 3 * static_cast<size_t>(S) + 2 * n_edge[0], nd1 = nd0 + 2 * static_cast<size_t>(NP) + 4 * NC,
-                 nd = nd1 + 4 * static_cast<size_t>(NM);
-    const size_t ni0 = static_cast<size_t>(S) + (NL + 1) + 2 * (S + 1) + 2 * n_edge[0] + 3;
-    const size_t ni1 = ni0 + (kde ? static_cast<size_t>(NE) + 1 : 0) + (vec ? NC + 1 : 0);     // (kde and vec exclude each other)
-    const size_t ni = ni1 + (mix ? static_cast<size_t>(NE) + 1 + static_cast<size_t>(NM) : 0);
-    std::vector<char> blob(nd * sizeof(double) + ni * sizeof(int32_t), 0);
-    double *bd = reinterpret_cast<double *>(blob.data());
-    if (!vec) std::memcpy(bd, m->param, 3 * S * sizeof(double));      // (a vector model's slots stay 0)
-    if (n_edge[0]) {
-        std::memcpy(bd + 3 * S, m->in_lp, n_edge[0] * sizeof(double));
-        std::memcpy(bd + 3 * S + n_edge[0], m->out_lp, n_edge[0] * sizeof(double));
-    }
-    int32_t *bi = reinterpret_cast<int32_t *>(bd + nd);
-    int32_t *b_kind = bi, *b_lvl = b_kind + S, *b_inp = b_lvl + NL + 1, *b_outp = b_inp + S + 1, *b_src = b_outp + S + 1,
-            *b_dst = b_src + n_edge[0];
-    b_dst[n_edge[0]] = m->start; b_dst[n_edge[0] + 1] = m->end; b_dst[n_edge[0] + 2] = m->finite;   // (part of the comparison)
-    std::memcpy(b_kind, m->kind, S * sizeof(int32_t));
-    std::memcpy(b_lvl, m->level_ptr, (NL + 1) * sizeof(int32_t));
-    std::memcpy(b_inp, m->in_ptr, (S + 1) * sizeof(int32_t));
-    std::memcpy(b_outp, m->out_ptr, (S + 1) * sizeof(int32_t));
-    if (n_edge[0]) {
-        std::memcpy(b_src, m->in_src, n_edge[0] * sizeof(int32_t));
-        std::memcpy(b_dst, m->out_dst, n_edge[0] * sizeof(int32_t));
-    }
-    if (kde) {
-        std::memcpy(bd + nd0, m->kde_pt, NP * sizeof(double));
-        std::memcpy(bd + nd0 + NP, m->kde_lw, NP * sizeof(double));
-        std::memcpy(bi + ni0, m->kde_ptr, (static_cast<size_t>(NE) + 1) * sizeof(int32_t));
-    }
-    if (vec) {
-        std::memcpy(bd + nd0, m->comp_param, 3 * NC * sizeof(double));
-        std::memcpy(bd + nd0 + 3 * NC, m->comp_w, NC * sizeof(double));
-        std::memcpy(bi + ni0, m->comp_kind, NC * sizeof(int32_t));
-        bi[ni0 + NC] = m->n_dim;
-    }
-    if (mix) {
-        std::memcpy(bd + nd1, m->mix_param, 3 * static_cast<size_t>(NM) * sizeof(double));
-        std::memcpy(bd + nd1 + 3 * NM, m->mix_lw, static_cast<size_t>(NM) * sizeof(double));
-        std::memcpy(bi + ni1, m->mix_ptr, (static_cast<size_t>(NE) + 1) * sizeof(int32_t));
-        std::memcpy(bi + ni1 + NE + 1, m->mix_kind, static_cast<size_t>(NM) * sizeof(int32_t));
-    }
+    return C.I.vec ? f(C.DV) : C.I.mix ? f(C.DM) : C.I.kde ? f(C.DK) : f(static_cast<const HmmDev &>(C.DK));
+}
+
+// The model's arrays checked and packed into one blob (hmm_model_check, hmm_blob_layout, hmm_blob_pack: hmm_plan.hpp); the
+// device copy is reused while the blob is unchanged -- a changed parameter, weight, kind or split is a changed blob.
+int hmm_upload(ps_ctx *ctx, const ps_hmm_model *m, HmmCall *C)
+{
+    std::string why;
+    if (!hmm_model_check(m, &C->I, &why)) return fail(ctx, PS_ERR_ARG, "%s", why.c_str());
+    const HmmBlobLayout L = hmm_blob_layout(C->I);
+    std::vector<char> blob;
+    hmm_blob_pack(m, L, &blob);
     if (blob != ctx->hmm.blob || !ctx->hmm.model.p) {
         HIP_TRY(ctx, ctx->hmm.model.reserve(blob.size()));
         HIP_TRY(ctx, hipMemcpyAsync(ctx->hmm.model.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));       // (blob is a local: the copy completes before it goes)
         ctx->hmm.blob.swap(blob);
     }
-    const double *dd = ctx->hmm.model.as<double>();
-    const int32_t *di = reinterpret_cast<const int32_t *>(dd + nd);
-    D->param = dd; D->in_lp = dd + 3 * S; D->out_lp = dd + 3 * S + n_edge[0];
-    D->kind = di; D->level_ptr = di + S; D->in_ptr = D->level_ptr + NL + 1; D->out_ptr = D->in_ptr + S + 1;
-    D->in_src = D->out_ptr + S + 1; D->out_dst = D->in_src + n_edge[0];
-    D->S = S; D->n_emit = NE; D->n_levels = NL; D->start = m->start; D->end = m->end; D->finite = m->finite != 0;
-    D->kde_pt = kde ? dd + nd0 : nullptr; D->kde_lw = kde ? dd + nd0 + NP : nullptr; D->kde_ptr = kde ? di + ni0 : nullptr;
-    static_cast<HmmDev &>(*V) = *D;
-    V->comp_param = vec ? dd + nd0 : nullptr; V->comp_w = vec ? dd + nd0 + 3 * NC : nullptr; V->comp_kind = vec ? di + ni0 : nullptr;
-    V->D = vec ? m->n_dim : 1;
-    static_cast<HmmDevK &>(*X) = *D;
-    X->mix_param = mix ? dd + nd1 : nullptr; X->mix_lw = mix ? dd + nd1 + 3 * NM : nullptr;
-    X->mix_ptr = mix ? di + ni1 : nullptr; X->mix_kind = mix ? di + ni1 + NE + 1 : nullptr;
-    X->mix_cdf = X->mix_draw = nullptr;                  // (ps_hmm_sample's: it sets them after its own upload)
+    hmm_blob_resolve(ctx->hmm.model.p, L, C->I, &C->DK, &C->DV, &C->DM);
     return PS_OK;
 }
 
@@ -3670,7 +3534,7 @@ template <typename MD>
 int launch_forward(ps_ctx *ctx, const MD &D, const double *d_obs, const long long *d_off, int32_t q0, int32_t q1, double *d_logp,
                    double *fmat, long long row0)
 {
-    const size_t lds = 2 * static_cast<size_t>(D.S) * sizeof(double);
+    const size_t lds = hmm_lds_bytes(D.S);
     HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_fwd_kernel<HMM_FORWARD, uint8_t, MD>), static_cast<int>(lds)));
     hipLaunchKernelGGL((hmm_fwd_kernel<HMM_FORWARD, uint8_t, MD>), dim3(q1 - q0), dim3(HMM_NT), lds, ctx->stream, D, d_obs, d_off,
                        q0, d_logp, fmat, row0, static_cast<uint8_t *>(nullptr), 0ll, static_cast<int *>(nullptr));
@@ -3682,31 +3546,6 @@ int launch_forward(ps_ctx *ctx, const MD &D, const double *d_obs, const long lon
 // host pointers are there), the model uploaded -- a bad one is refused whatever the batch --, own(C): the entry point's
 // checks that need the model (and what it does for an empty batch), and last, for a batch that is not empty, the offsets,
 // followed by the path slots' where there are some, on the device.  An empty batch leaves d_off null.
-struct HmmCall {
-    HmmDevK DK;
-    HmmDevV DV;
-    HmmDevM DM;
-    bool kde = false, vec = false, mix = false;
-    int n_mix = 0;                          // mixture components of the model (mix_ptr[n_emit])
-    int max_in = 0, E = 0;                  // most in-edges of a state, out-edges of the model
-    const long long *d_off = nullptr;
-    int dim() const { return vec ? DV.D : 1; }                                        // doubles per observation
-    long long n_stats() const { return (1ll + 2 * dim()) * DK.n_emit + 3ll * n_mix; }  // doubles of ps_hmm_expect's d_stats
-    long long n_acc() const { return E + n_stats() + 1; }                              // hmm_expect_kernel's accumulators
-};
-// a vector model takes the HmmDevV instantiations, one with mixture states the HmmDevM ones, one with kernel-density states
-// (and no mixture) the HmmDevK ones, any other the HmmDev ones
-template <typename F> int with_model(const HmmCall &C, F &&f)
-{
-    return C.vec ? f(C.DV) : C.mix ? f(C.DM) : C.kde ? f(C.DK) : f(static_cast<const HmmDev &>(C.DK));
-}
-int hmm_upload(ps_ctx *ctx, const ps_hmm_model *model, HmmCall *C)
-{
-    if (int rc = hmm_upload(ctx, model, &C->DK, &C->DV, &C->DM, &C->max_in, &C->kde, &C->vec, &C->mix)) return rc;
-    C->E = model->out_ptr[C->DK.S];
-    C->n_mix = C->mix ? model->mix_ptr[C->DK.n_emit] : 0;
-    return PS_OK;
-}
 template <typename Own>
 int hmm_begin(ps_ctx *ctx, const ps_hmm_model *model, bool host_ok, const double *d_obs, const int64_t *h_off,
               const int64_t *h_path_off, int32_t n_seq, const double *d_logp, HmmCall *C, Own &&own)
@@ -3732,7 +3571,7 @@ template <typename BP, typename MD>
 int hmm_viterbi(ps_ctx *ctx, const MD &D, const double *d_obs, const int64_t *h_off, const long long *d_off, int32_t n_seq,
                 double *d_logp, double *d_mat, int32_t *d_path, int32_t *d_path_len)
 {
-    const size_t S = static_cast<size_t>(D.S), lds = 2 * S * sizeof(double);
+    const size_t S = static_cast<size_t>(D.S), lds = hmm_lds_bytes(D.S);
     const long long *d_path_off = d_off + n_seq + 1;
     const long long budget = std::max<long long>(1, ctx->hmm.bp_budget);
     HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_fwd_kernel<HMM_VITERBI, BP, MD>), static_cast<int>(lds)));
@@ -3742,7 +3581,7 @@ int hmm_viterbi(ps_ctx *ctx, const MD &D, const double *d_obs, const int64_t *h_
     for (int32_t q0 = 0, q1; q0 < n_seq; q0 = q1) {
         long long bytes;
         q1 = next_chunk(h_off, q0, n_seq, S * sizeof(BP), budget, &bytes);
-        if (bytes > (8ll << 30)) return fail(ctx, PS_ERR_ARG, "sequence %d needs %lld bytes of backpointers (8 GiB at most)", q0, bytes);
+        if (std::string why; !hmm_launch_check(q0, bytes, true, &why)) return fail(ctx, PS_ERR_ARG, "%s", why.c_str());
         HIP_TRY(ctx, ctx->hmm.bp.reserve(static_cast<size_t>(bytes)));
         const long long bp_row0 = h_off[q0] + q0;
         const int nq = q1 - q0;
@@ -3767,7 +3606,7 @@ template <bool ACC_LDS, typename MD>
 int hmm_expect_run(ps_ctx *ctx, const MD &D, const double *d_obs, const int64_t *h_off, const long long *d_off,
                    int32_t n_seq, int n_acc, int E, double *d_logp, double *d_counts, double *d_stats, int32_t *h_skipped)
 {
-    const size_t lds = (2 * static_cast<size_t>(D.S) + (ACC_LDS ? static_cast<size_t>(n_acc) : 0)) * sizeof(double);
+    const size_t lds = hmm_lds_bytes(D.S, ACC_LDS ? n_acc : 0);
     HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_expect_kernel<ACC_LDS, MD>), static_cast<int>(lds)));
     // a grid of resident workgroups (it depends on the device and the model only, never on timing), within the row budget
     const size_t row_bytes = static_cast<size_t>(n_acc) * sizeof(double);
@@ -3779,7 +3618,7 @@ int hmm_expect_run(ps_ctx *ctx, const MD &D, const double *d_obs, const int64_t 
     for (int32_t q0 = 0, q1; q0 < n_seq; q0 = q1) {
         long long bytes;
         q1 = next_chunk(h_off, q0, n_seq, static_cast<size_t>(D.S) * sizeof(double), budget, &bytes);
-        if (bytes > (16ll << 30)) return fail(ctx, PS_ERR_ARG, "sequence %d needs %lld bytes of forward matrix (16 GiB at most)", q0, bytes);
+        if (std::string why; !hmm_launch_check(q0, bytes, false, &why)) return fail(ctx, PS_ERR_ARG, "%s", why.c_str());
         HIP_TRY(ctx, ctx->hmm.fmat.reserve(static_cast<size_t>(bytes)));
         const long long row0 = h_off[q0] + q0;
         if (int rc = launch_forward(ctx, D, d_obs, d_off, q0, q1, d_logp, ctx->hmm.fmat.as<double>(), row0)) return rc;
@@ -3806,14 +3645,14 @@ int hmm_posterior_run(ps_ctx *ctx, const MD &D, const double *d_obs, const int64
                       int32_t n_seq, int E, double *d_logp, double *d_post, int32_t *d_map_state, double *d_map_logp,
                       double *d_counts_seq)
 {
-    const size_t lds = (2 * static_cast<size_t>(D.S) + (CNT == 2 ? static_cast<size_t>(E) : 0)) * sizeof(double);
+    const size_t lds = hmm_lds_bytes(D.S, CNT == 2 ? E : 0);
     HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_posterior_kernel<CNT, MD>), static_cast<int>(lds)));
     if (d_map_logp) HIP_TRY(ctx, ctx->hmm.pmax.reserve(std::max<size_t>(1, static_cast<size_t>(h_off[n_seq])) * sizeof(double)));
     const long long budget = std::max<long long>(1, ctx->hmm.fb_budget);
     for (int32_t q0 = 0, q1; q0 < n_seq; q0 = q1) {
         long long bytes;
         q1 = next_chunk(h_off, q0, n_seq, static_cast<size_t>(D.S) * sizeof(double), budget, &bytes);
-        if (bytes > (16ll << 30)) return fail(ctx, PS_ERR_ARG, "sequence %d needs %lld bytes of forward matrix (16 GiB at most)", q0, bytes);
+        if (std::string why; !hmm_launch_check(q0, bytes, false, &why)) return fail(ctx, PS_ERR_ARG, "%s", why.c_str());
         HIP_TRY(ctx, ctx->hmm.fmat.reserve(static_cast<size_t>(bytes)));
         const long long row0 = h_off[q0] + q0;
         if (ctx->debug) fprintf(stderr, "[poreseg] posterior launch: sequences %d..%d, %lld bytes of forward matrix, dynamic LDS %zu\n", q0, q1, bytes, lds);
@@ -3849,13 +3688,13 @@ int ps_hmm_batch(ps_ctx *ctx, const ps_hmm_model *model, int32_t mode, const dou
     if (!C.d_off) return PS_OK;
     if (vit)
         return with_model(C, [&](const auto &M) {
-            return C.max_in > 255 ? hmm_viterbi<uint16_t>(ctx, M, d_obs, h_off, C.d_off, n_seq, d_logp, d_mat, d_path, d_path_len)
-                                  : hmm_viterbi<uint8_t>(ctx, M, d_obs, h_off, C.d_off, n_seq, d_logp, d_mat, d_path, d_path_len);
+            return hmm_bp_wide(C.I) ? hmm_viterbi<uint16_t>(ctx, M, d_obs, h_off, C.d_off, n_seq, d_logp, d_mat, d_path, d_path_len)
+                                    : hmm_viterbi<uint8_t>(ctx, M, d_obs, h_off, C.d_off, n_seq, d_logp, d_mat, d_path, d_path_len);
         });
     const int rc = with_model(C, [&](const auto &M) -> int {
         using MD = std::decay_t<decltype(M)>;
         if (mode == PS_HMM_FORWARD) return launch_forward(ctx, M, d_obs, C.d_off, 0, n_seq, d_logp, d_mat, 0ll);
-        const size_t lds = 2 * static_cast<size_t>(M.S) * sizeof(double);
+        const size_t lds = hmm_lds_bytes(M.S);
         HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_bwd_kernel<MD>), static_cast<int>(lds)));
         hipLaunchKernelGGL(hmm_bwd_kernel<MD>, dim3(n_seq), dim3(HMM_NT), lds, ctx->stream, M, d_obs, C.d_off, 0, d_logp, d_mat);
         HIP_TRY(ctx, hipGetLastError());
@@ -3872,24 +3711,22 @@ int ps_hmm_expect(ps_ctx *ctx, const ps_hmm_model *model, const double *d_obs, c
     HmmCall C;
     int n_acc = 0;
     auto own = [&](const HmmCall &c) -> int {
-        const int E = c.E, NE = c.DK.n_emit;
-        const long long n_acc_ll = c.n_acc();
-        if (n_acc_ll > (1ll << 26)) return fail(ctx, PS_ERR_ARG, "model of %d edges: the E-step takes at most 2^26 accumulators", E);
-        n_acc = static_cast<int>(n_acc_ll);
+        const int E = c.I.E, NE = c.I.NE;
+        if (std::string why; !hmm_acc_check(c.I, true, &why)) return fail(ctx, PS_ERR_ARG, "%s", why.c_str());
+        n_acc = static_cast<int>(c.I.n_acc());
         if ((E > 0 && !d_counts) || (NE > 0 && !d_stats)) return fail(ctx, PS_ERR_ARG, "null device pointer");
         *h_skipped = 0;
         if (n_seq == 0) {
             if (E > 0) HIP_TRY(ctx, hipMemsetAsync(d_counts, 0, static_cast<size_t>(E) * sizeof(double), ctx->stream));
-            if (NE > 0) HIP_TRY(ctx, hipMemsetAsync(d_stats, 0, static_cast<size_t>(c.n_stats()) * sizeof(double), ctx->stream));
+            if (NE > 0) HIP_TRY(ctx, hipMemsetAsync(d_stats, 0, static_cast<size_t>(c.I.n_stats()) * sizeof(double), ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         }
         return PS_OK;
     };
     if (int rc = hmm_begin(ctx, model, h_skipped != nullptr, d_obs, h_off, nullptr, n_seq, d_logp, &C, own)) return rc;
     if (!C.d_off) return PS_OK;
-    const int E = C.E;
-    const bool in_lds = (2 * static_cast<size_t>(C.DK.S) + static_cast<size_t>(n_acc)) * sizeof(double) <= HMM_EXPECT_LDS
-                        && ctx->hmm.expect_lds;
+    const int E = C.I.E;
+    const bool in_lds = hmm_expect_in_lds(C.I, ctx->hmm.expect_lds);
     return with_model(C, [&](const auto &M) {
         return in_lds ? hmm_expect_run<true>(ctx, M, d_obs, h_off, C.d_off, n_seq, n_acc, E, d_logp, d_counts, d_stats, h_skipped)
                       : hmm_expect_run<false>(ctx, M, d_obs, h_off, C.d_off, n_seq, n_acc, E, d_logp, d_counts, d_stats, h_skipped);
@@ -3901,15 +3738,13 @@ int ps_hmm_posterior(ps_ctx *ctx, const ps_hmm_model *model, const double *d_obs
 {
     HmmCall C;
     auto own = [&](const HmmCall &c) -> int {
-        if (c.n_acc() > (1ll << 26)) return fail(ctx, PS_ERR_ARG, "model of %d edges: at most 2^26 accumulators", c.E);
+        if (std::string why; !hmm_acc_check(c.I, false, &why)) return fail(ctx, PS_ERR_ARG, "%s", why.c_str());
         return PS_OK;
     };
     if (int rc = hmm_begin(ctx, model, true, d_obs, h_off, nullptr, n_seq, d_logp, &C, own)) return rc;
     if (!C.d_off) return PS_OK;
-    const int E = C.E;
-    // the counts row of a sequence: none asked for (or no edges), in LDS when it fits beside the score rows, else in place
-    const int cnt = !d_counts_seq || E == 0 ? 0
-                    : (2 * static_cast<size_t>(C.DK.S) + static_cast<size_t>(E)) * sizeof(double) <= HMM_EXPECT_LDS && ctx->hmm.expect_lds ? 2 : 1;
+    const int E = C.I.E;
+    const int cnt = hmm_posterior_cnt(C.I, d_counts_seq != nullptr, ctx->hmm.expect_lds);
     return with_model(C, [&](const auto &M) {
         switch (cnt) {
         case 0: return hmm_posterior_run<0>(ctx, M, d_obs, h_off, C.d_off, n_seq, E, d_logp, d_post, d_map_state, d_map_logp, d_counts_seq);
@@ -3938,65 +3773,16 @@ int ps_hmm_sample(ps_ctx *ctx, const ps_hmm_model *model, const ps_hmm_sample_ta
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HmmCall C;
     if (int rc = hmm_upload(ctx, model, &C)) return rc;
-    const int S = C.DK.S, NE = C.DK.n_emit;
-    if (!model->finite && length == 0) return fail(ctx, PS_ERR_ARG, "a model without an edge into end never ends a walk: a length must be given");
-    if ((static_cast<long long>(max_length) + 1) * (C.DK.n_levels + 1) + 2 > INT32_MAX)
-        return fail(ctx, PS_ERR_ARG, "max_length %d with %d silent levels: a path could exceed int32", max_length, C.DK.n_levels);
-    // the tables against the model: sizes, every state's cdf ascending within [0, 1] and closed by exactly 1.0
-    const int64_t n_param = 2 * static_cast<int64_t>(NE) * C.dim(), n_kde = C.kde ? model->kde_ptr[NE] : 0, n_mix = C.n_mix;
-    if (C.mix && (!model->mix_cdf || !model->mix_draw)) return fail(ctx, PS_ERR_ARG, "sampling a mixture state needs mix_cdf and mix_draw");
-    if (tables->n_cdf != C.E || tables->n_param != n_param || tables->n_kde != n_kde)
-        return fail(ctx, PS_ERR_ARG, "sampling tables of %lld / %lld / %lld entries, the model takes %d / %lld / %lld",
-                    static_cast<long long>(tables->n_cdf), static_cast<long long>(tables->n_param), static_cast<long long>(tables->n_kde),
-                    C.E, static_cast<long long>(n_param), static_cast<long long>(n_kde));
-    if ((C.E > 0 && !tables->out_cdf) || (n_param > 0 && !tables->emit_param) || (n_kde > 0 && !tables->kde_cdf))
-        return fail(ctx, PS_ERR_ARG, "null sampling table");
-    // One row [lo, hi) of a cdf table beside the model's log probabilities lp of its entries.  A rounded running sum may pass
-    // 1.0 by an ulp, and the entries stored as 1.0 behind it then step back onto 1.0: both are above every u the kernel
-    // draws, so the bisection still finds the linear scan's entry.  An entry above its predecessor (the first: above 0)
-    // owns an interval of u; where the model says -inf the row gives mass to an impossible entry.
-    auto cdf_row = [&](const char *what, const double *cdf, const double *lp, const int32_t *ptr, int k) -> int {
-        const int lo = ptr[k], hi = ptr[k + 1];
-        double prev = 0.0;
-        for (int i = lo; i < hi; ++i) {
-            const double v = cdf[i];
-            const bool closes = i == hi - 1;
-            if (closes ? v != 1.0 : !std::isfinite(v) || !(v >= prev || (v == 1.0 && prev > 1.0)))
-                return fail(ctx, PS_ERR_ARG, "%s of state %d: ascending from >= 0 with the last entry 1.0", what, k);
-            if (v > prev && lp[i] == -INFINITY)
-                return fail(ctx, PS_ERR_ARG, "%s of state %d: entry %d rises above its predecessor, its log probability is -inf",
-                            what, k, i - lo);
-            prev = v;
-        }
-        return PS_OK;
-    };
-    for (int k = 0; k < S; ++k)
-        if (int rc = cdf_row("out_cdf", tables->out_cdf, model->out_lp, model->out_ptr, k)) return rc;
-    for (int k = 0; C.kde && k < NE; ++k)
-        if (int rc = cdf_row("kde_cdf", tables->kde_cdf, model->kde_lw, model->kde_ptr, k)) return rc;
-    for (int k = 0; C.mix && k < NE; ++k)
-        if (int rc = cdf_row("mix_cdf", model->mix_cdf, model->mix_lw, model->mix_ptr, k)) return rc;
-    for (int64_t i = 0; i < 2 * n_mix; ++i)
-        if (!std::isfinite(model->mix_draw[i])) return fail(ctx, PS_ERR_ARG, "mix_draw %lld is not finite", static_cast<long long>(i));
-    for (int64_t i = 0; i < n_param; ++i)
-        if (!std::isfinite(tables->emit_param[i])) return fail(ctx, PS_ERR_ARG, "emit_param %lld is not finite", static_cast<long long>(i));
+    if (std::string why; !hmm_sample_check(model, tables, C.I, length, max_length, &why)) return fail(ctx, PS_ERR_ARG, "%s", why.c_str());
     if (n_seq == 0) return PS_OK;
     if (!d_len || !d_flags || (h_off[n_seq] > 0 && !d_obs)) return fail(ctx, PS_ERR_ARG, "null device pointer");
-    const size_t nb = (static_cast<size_t>(n_seq) + 1) * sizeof(int64_t);
-    if (int rc = upload_tables(ctx, ctx->hmm.samp, {{tables->out_cdf, static_cast<size_t>(C.E) * sizeof(double)},
-                                                    {tables->emit_param, static_cast<size_t>(n_param) * sizeof(double)},
-                                                    {tables->kde_cdf, static_cast<size_t>(n_kde) * sizeof(double)},
-                                                    {C.mix ? model->mix_cdf : nullptr, static_cast<size_t>(n_mix) * sizeof(double)},
-                                                    {C.mix ? model->mix_draw : nullptr, 2 * static_cast<size_t>(n_mix) * sizeof(double)},
-                                                    {h_off, nb}, {h_path_off, want_path ? nb : 0}})) return rc;
+    const HmmSampleLayout U = hmm_sample_layout(model, tables, C.I, h_off, want_path ? h_path_off : nullptr, n_seq);
+    HostTable up[HMM_U_COUNT];
+    for (int t = 0; t < HMM_U_COUNT; ++t) up[t] = {U.src[t], U.bytes[t]};
+    if (int rc = upload_tables(ctx, ctx->hmm.samp, 0, [](void *) {}, up, up + HMM_U_COUNT)) return rc;
     HmmSampleDev T;
-    T.out_cdf = ctx->hmm.samp.as<double>();
-    T.emit_param = T.out_cdf + C.E;
-    T.kde_cdf = T.emit_param + n_param;
-    C.DM.mix_cdf = T.kde_cdf + n_kde;
-    C.DM.mix_draw = C.DM.mix_cdf + n_mix;
-    const long long *d_off = reinterpret_cast<const long long *>(C.DM.mix_draw + 2 * n_mix);
-    const long long *d_path_off = want_path ? d_off + n_seq + 1 : nullptr;
+    const long long *d_off, *d_path_off;
+    hmm_sample_resolve(ctx->hmm.samp.p, U, &T, &C.DM, &d_off, &d_path_off);
     const int rc = with_model(C, [&](const auto &M) -> int {
         using MD = std::decay_t<decltype(M)>;
         hipLaunchKernelGGL(hmm_sample_kernel<MD>, dim3((n_seq + HMM_NT - 1) / HMM_NT), dim3(HMM_NT), 0, ctx->stream, M, T,
@@ -4012,10 +3798,7 @@ int ps_hmm_sample(ps_ctx *ctx, const ps_hmm_model *model, const ps_hmm_sample_ta
     if (want_path) HIP_TRY(ctx, hipMemcpyAsync(plens.data(), d_path_len, plens.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     int64_t short_obs = 0, short_path = 0;
-    for (int32_t q = 0; q < n_seq; ++q) {
-        short_obs += lens[q] > h_off[q + 1] - h_off[q];
-        if (want_path) short_path += plens[q] > h_path_off[q + 1] - h_path_off[q];
-    }
+    hmm_short_slots(lens.data(), h_off, want_path ? plens.data() : nullptr, h_path_off, n_seq, &short_obs, &short_path);
     if (short_obs || short_path)
         return fail(ctx, PS_ERR_CAPACITY, "%lld observation slots and %lld path slots are too small (d_len and d_path_len hold the lengths)",
                     static_cast<long long>(short_obs), static_cast<long long>(short_path));

@@ -21,55 +21,9 @@
 #pragma once
 
 #include "batch_plan.hpp"                  // HMM_NT
+#include "hmm_plan.hpp"                    // the limits, the state kinds and modes; HmmDev, HmmDevK, HmmDevV, HmmDevM, HmmSampleDev
 
 namespace ps {
-
-constexpr int HMM_S_MAX = 4096;            // states: two fp64 rows of S in LDS = 64 KiB at most
-constexpr int HMM_VITERBI = 0, HMM_FORWARD = 1, HMM_BACKWARD = 2;   // include/poreseg.h PS_HMM_*
-constexpr int HMM_SILENT = 0, HMM_NORMAL = 1, HMM_UNIFORM = 2, HMM_KDE = 3;   // include/poreseg.h ps_hmm_model.kind
-constexpr int HMM_VECTOR = 4;              // ... kind: a state of D components (a vector model)
-constexpr int HMM_LOGNORMAL = 5, HMM_EXPONENTIAL = 6;   // ps_hmm_model.comp_kind, beside HMM_NORMAL and HMM_UNIFORM
-constexpr int HMM_D_MAX = 16;              // components of a vector model's observation
-constexpr int HMM_MIXTURE = 7;             // ... kind: a weighted choice between component distributions (HmmDevM)
-
-struct HmmDev {                 // device pointers into one upload of the baked model (include/poreseg.h ps_hmm_model)
-    const double *param;        // 3 per state: normal (mean, 1 / (2 std^2), -log(std sqrt(2 pi))), uniform (low, high, -log(high - low))
-    const double *in_lp, *out_lp;
-    const int *kind, *level_ptr, *in_ptr, *in_src, *out_ptr, *out_dst;
-    int S, n_emit, n_levels, start, end, finite;
-};
-
-// A model with kernel-density states (kind 3): state k's points are [kde_ptr[k], kde_ptr[k+1]) of kde_pt (the points) and
-// kde_lw (their log weights, the weights summing to 1), and its param is (weighted mean of the points, 1 / (2 h^2),
-// -log(h sqrt(2 pi))) for the bandwidth h.  The kernels are instantiated once per model type: a model without such states
-// runs the HmmDev instantiations, whose code knows nothing of these tables.
-struct HmmDevK : HmmDev {
-    const int *kde_ptr;
-    const double *kde_pt, *kde_lw;
-};
-
-// A vector model (every emitting state is kind 4): an observation is a row of D doubles, and state k scores it with the D
-// independent components [k D, (k + 1) D) of comp_kind / comp_param (3 per component: normal and uniform as param,
-// log-normal (mu, 1 / (2 sigma^2), -log(sigma sqrt(2 pi))), exponential (0, rate, log rate)) / comp_w (weights > 0).  Its
-// `param` is not read.  A third set of instantiations: the HmmDev and HmmDevK code knows nothing of these tables.
-struct HmmDevV : HmmDev {
-    const int *comp_kind;
-    const double *comp_param, *comp_w;
-    int D;
-};
-
-// A model with mixture states (kind 7), beside normal, uniform and kernel-density ones: state k's components are
-// [mix_ptr[k], mix_ptr[k+1]) of mix_kind (1, 2, 5, 6 as comp_kind), mix_param (3 per component, as comp_param) and mix_lw
-// (their log weights, the weights summing to 1; -inf: the component is skipped), and its param is (0, 0, 0).  A fourth set
-// of instantiations: the HmmDev, HmmDevK and HmmDevV code knows nothing of these tables.  The two sampling tables of
-// ps_hmm_model ride here as well (HmmSampleDev stays the struct the other instantiations were compiled with): they are set
-// by ps_hmm_sample alone, which uploads them per call, and are null in every other call.
-struct HmmDevM : HmmDevK {
-    const int *mix_ptr, *mix_kind;
-    const double *mix_param, *mix_lw;
-    const double *mix_cdf;      // per component: the running sum of the state's weights; 1.0 from the last positive weight on
-    const double *mix_draw;     // 2 per component, as HmmSampleDev.emit_param
-};
 
 // The observation as the kernels hand it to hmm_emit: doubles per observation, and observation t of the sequence that
 // starts at x -- the double itself, or for a vector model the row of D doubles (one address for the whole wave).
@@ -663,12 +617,6 @@ __global__ __launch_bounds__(HMM_NT) void hmm_trace_kernel(HmmDev M, const long 
 // j = 0, 1, 2, ... at counter (j low, j high, Q low, Q high); a block of four words gives two doubles in [0, 1) and the
 // walk consumes blocks strictly in walk order (one per transition, one per component of an emission, two for a
 // kernel-density or a mixture state), so a walk's path and length depend on (seed, Q, out_cdf) alone, never on the values drawn.
-
-struct HmmSampleDev {           // device copies of ps_hmm_sample_tables (include/poreseg.h)
-    const double *out_cdf;      // per out-edge: the running sum of the state's edge probabilities, its last entry 1.0
-    const double *emit_param;   // 2 per emitting state (per component k D + d of a vector model)
-    const double *kde_cdf;      // per kernel-density point: the running sum of the state's weights, its last entry 1.0
-};
 
 struct HmmPhilox {
     unsigned r[4];

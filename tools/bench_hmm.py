@@ -5,7 +5,11 @@ Prints one JSON line: device time per batch (HIP events around the library call,
 median of --reps) for Viterbi (paths included) and for forward (log probabilities), and the test oracle's host time
 (tests/hmm_oracle.py, numpy) measured on the first --oracle-events events and scaled to the batch by observation count.
 
-    python tools/bench_hmm.py [--events 10000] [--reps 5] [--oracle-events 40]
+With --small-calls N also the host's clock around a call where host time dominates: the forward pass of one sequence of two
+observations (argument checks, the model's check and packing, one upload, one launch, one synchronisation), median of N calls
+in microseconds.
+
+    python tools/bench_hmm.py [--events 10000] [--reps 5] [--oracle-events 40] [--small-calls 0]
 """
 import argparse
 import json
@@ -25,6 +29,7 @@ def main():
     ap.add_argument("--events", type=int, default=10000)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--oracle-events", type=int, default=40)
+    ap.add_argument("--small-calls", type=int, default=0)
     a = ap.parse_args()
     import torch
     import hmm_oracle as O
@@ -48,6 +53,14 @@ def main():
             t1.synchronize()
             ms.append(t0.elapsed_time(t1))
         res[name + "_ms"] = float(np.median(ms))
+    if a.small_calls:
+        off2 = np.array([0, 2], np.int64)
+        us = []
+        for i in range(20 + a.small_calls):                   # (the first 20: warm-up)
+            t = time.perf_counter()
+            ctx.hmm_batch(cm, _lib.PS_HMM_FORWARD, obs, off2)
+            us.append((time.perf_counter() - t) * 1e6)
+        res.update({"small_call_observations": 2, "small_call_host_us": float(np.median(us[20:]))})
     # a check that the timed batch is the right answer, on a few events
     c = O.Compiled(model)
     vit = model.viterbi_batch(seqs[:3])
