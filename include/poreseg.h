@@ -178,8 +178,9 @@ int ps_set_tiling(ps_ctx *ctx, int64_t tile_len, int64_t halo);
  * "scan_lds_pad", "rep_*") and the PORESEG_* variables exist in libporeseg_diag.so only (make -C pypore_amd/csrc diag;
  * ps_version() of that build says DIAGNOSTIC BUILD). */
 int ps_set_option(ps_ctx *ctx, const char *name, int64_t value);
-/* The current value of one of the options that "shared_device" plans -- "k0_waves", "k0_admit", "lat_help" -- or of
- * "shared_device" / "hw_queues" as last set; PS_ERR_ARG for any other name. */
+/* The current value of any option ps_set_option knows, as it was stored: the default, what was last set (a switch as 0 / 1,
+ * "timing" clamped), for "k0_waves", "k0_admit" and "lat_help" what "shared_device" planned since; "k0_unaligned" answers what the
+ * probe granted.  PS_ERR_ARG for an unknown name. */
 int ps_get_option(const ps_ctx *ctx, const char *name, int64_t *value);
 
 /* What option "shared_device" n sets on a process with hw_queues hardware queues: a pure function of min(n, hw_queues) -- no
@@ -740,7 +741,13 @@ int ps_hmm_sample(ps_ctx *ctx, const ps_hmm_model *model, const ps_hmm_sample_ta
  * screen kernel decided (they are part of [0] and [10], so [10] - [15] are the windows the subtree kernel scanned); both
  * cover every round of the call, like [0] and [10], and both are -1 when the call did not launch the screen kernel; [16] [17]
  * look-ahead / upload launches the call did without (option "short_chain": 0 or 1 each), [18] seams its bridges left deferred
- * that the look-ahead kernel finished behind the stitch (they are part of [4]).  Twenty counters in all. */
+ * that the look-ahead kernel finished behind the stitch (they are part of [4]).  Twenty counters in all ([19] is reserved).
+ * The indices by name, in the order above: ms[PS_MS_SPINE] .. ms[PS_MS_SEQ], counters[PS_CNT_WINDOWS] .. counters[PS_CNT_SEAMS_RESUMED]. */
+enum { PS_MS_SPINE = 0, PS_MS_TREE, PS_MS_GATHER, PS_MS_TOTAL, PS_MS_STITCH, PS_MS_BRIDGE, PS_MS_BLOCKSUM, PS_MS_SEQ, PS_MS_COUNT = 8 };
+enum { PS_CNT_WINDOWS = 0, PS_CNT_CANDIDATES, PS_CNT_TILES, PS_CNT_TREE_JOBS, PS_CNT_REPAIRS, PS_CNT_EXACT_RESCANS, PS_CNT_FULL_EXACT_SCANS,
+       PS_CNT_WIDE_REDO, PS_CNT_WINDOWS_SPINE, PS_CNT_WINDOWS_BRIDGE, PS_CNT_WINDOWS_TREE, PS_CNT_NEAR_TIES, PS_CNT_HELPER_CHUNKS_PUBLISHED,
+       PS_CNT_HELPER_CHUNKS_TAKEN, PS_CNT_TREE_DEFERRED, PS_CNT_WINDOWS_SCREEN, PS_CNT_LOOKAHEAD_SKIPPED, PS_CNT_UPLOAD_SKIPPED,
+       PS_CNT_SEAMS_RESUMED, PS_CNT_COUNT = 20 };
 int ps_get_timings(const ps_ctx *ctx, double *ms, int32_t n_ms, int64_t *counters, int32_t n_counters);
 /* The twenty work counters of ps_get_timings in place (valid for the life of the context; host memory, updated by every
  * call before it returns): a caller that checks one of them after each call -- counters[11], the near ties -- reads it

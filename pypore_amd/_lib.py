@@ -22,6 +22,11 @@ PS_PW_OK, PS_PW_INDEX_ERROR = 0, 1
 PS_TRF_DONE, PS_TRF_MAX_REPEATS = 0, 1
 TRF_N_MAX = 2048          # segments per sequence of ps_trf_split_batch
 PS_NT_NOT_COUNTED, PS_NT_INCOMPLETE = -1, -2     # ps_get_near_ties: *n_out when the sites are not counted / the log overflowed
+# What ps_get_timings returns, in index order (include/poreseg.h: PS_MS_<NAME>, PS_CNT_<NAME>; None: reserved)
+MS_NAMES = ("spine", "tree", "gather", "total", "stitch", "bridge", "blocksum", "seq")
+COUNTER_NAMES = ("windows", "candidates", "tiles", "tree_jobs", "repairs", "exact_rescans", "full_exact_scans", "wide_redo", "windows_spine",
+                 "windows_bridge", "windows_tree", "near_ties", "helper_chunks_published", "helper_chunks_taken", "tree_deferred", "windows_screen",
+                 "lookahead_skipped", "upload_skipped", "seams_resumed", None)
 
 
 class SplitParams(ctypes.Structure):

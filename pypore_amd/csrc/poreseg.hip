@@ -16,8 +16,11 @@
 // CPU (tests/native/seg_plan_check.cpp); device_stitch_batch and host_stitch_batch act on it: buffers, uploads, launches.
 // The context (ps_ctx) owns its GPU resources: DevBuf, HostBuf, Event and Stream free themselves, so ps_destroy is `delete ctx`
 // and a half-built context of ps_create releases what it had.  The segmentation chain's members are flat; every other feature
-// keeps its buffers, budgets and caches in one sub-struct of ps_ctx (filt, align, pw, ss, nt, hmm).  A new feature adds its
-// sub-struct there and needs no entry anywhere else.  ps_live_bytes counts what the owning buffers of the process hold.
+// keeps its buffers and caches in one sub-struct of ps_ctx (filt, align, pw, ss, nt, hmm).  A new feature adds its
+// sub-struct there and needs no entry anywhere else.  The context's options -- their defaults, names, ranges, PORESEG_* variables
+// (diagnostic library) and which of them act on the context when set -- are one struct and one table in ctx_options.hpp, checked on
+// the CPU (tests/native/ctx_options_check.cpp): ps_set_option, ps_get_option and diag_env go through it, and the code here reads
+// ctx->opt.  ps_live_bytes counts what the owning buffers of the process hold.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -52,6 +55,7 @@
 #include "seg_plan.hpp"
 #include "filt_plan.hpp"
 #include "batch_plan.hpp"
+#include "ctx_options.hpp"
 
 using namespace ps;
 
@@ -125,7 +129,7 @@ struct Stream : NoCopy {  // the context's stream: destroyed with it when the co
 
 }  // namespace
 
-enum : int { SC_NO_LA = 1, SC_NO_UPLOAD = 2, SC_ALL = 3 };
+static_assert(CtxOptions().mode == MODE_FAST && CtxOptions().bridge_patience == BR_PATIENCE_POOL, "ctx_options.hpp: defaults named in seg_device.hpp");
 constexpr int LA_KEEP = 16;        // calls that keep the look-ahead launch after one that needed it (ps_ctx::la_keep)
 struct ps_ctx {
     int device = 0;
@@ -137,61 +141,17 @@ struct ps_ctx {
     Event ev_front[2];        // hand-over events (no timing): [0] context stream -> front stream, [1] front stream -> context stream
     ~ps_ctx() { (void)hipSetDevice(device); if (stream.s) (void)hipStreamSynchronize(stream.s); }
     std::string err;
+    CtxOptions opt;           // every option of ps_set_option as last set (ctx_options.hpp: the values and the table of their rules)
+    int k0_unaligned = 1;     // what option k0_unaligned comes to: K0's fast route loads 16 bytes from sample-aligned addresses -- asked for (opt) and
+                              // granted by the probe, once per device at ps_create and again when the option is set (k0_unaligned_probe)
     int64_t tile_len = 0, halo = 0;
-    int mode = MODE_FAST, spine_nt = 512, tree_nt = 256;
     int lds_max_samples = 0;
-    int rep_eval = 1, rep_stage = 1, rep_sum = 1;
     uint8_t *d_is_spine = nullptr;   // optional output of the current call
-    int prune = 1;
     WideRedo wide;            // the last call K0 refused (counts too wide) and where the calls after it start (seg_plan.hpp)
-    int tree_mw = 0;          // 1: block-sum tree kernel with TREE_W waves per workgroup sharing their job list (round 3: single-wave workgroups are faster at four waves per SIMD and need no spills)
-    int upload_by_kernel = 1; // 1: the call's host tables are fetched by a kernel (no SDMA hand-over), 0: hipMemcpyAsync
-    int k0_waves = 0;         // > 0: K0 runs as a persistent kernel, this many waves per SIMD (twice that for int16 samples) striding over the call with
-                              // their next wave block's samples in flight (round 5) -- what a context that shares the chip wants (engine.StreamPool
-                              // sets 1: 0.193 -> 0.170 ms per step with sixteen calls in flight); 0: one wave per wave block, as many as the registers
-                              // allow -- faster for a call that has the chip to itself (1e9 samples: K0 0.91 against 0.98 ms)
-    float noise_k = 0.1f;     // near-tie accounting of the wide route (DevCfg::noise_k; PORESEG_NOISE_K)
-    int k0_admit = 0;         // > 0: at most this many calls of the device have their K0 in flight (K0Gate); 0: no limit
-    int k0_sets = 2;          // register sets of a persistent K0 wave (seg_bs.hpp: blocksum_kernel<DT, NS>); 3 / 4 in the diagnostic library only (rejected)
     bool chain_held = false;  // this call has a ticket of the device's K0 chain (K0Chain) and has not recorded its event yet
     unsigned long long chain_ticket = 0;
     bool defer_sync = false;  // (internal) ps_filter_requantise_batch: the filter entry only queues its kernels -- no status clear, copy, sync
-    int scan_lds_pad = 0;     // diagnostics (libporeseg_diag.so only: option scan_lds_pad): unused dynamic LDS per single-wave scan workgroup -- caps the scan waves per SIMD
-    int k0_unaligned = 1;     // K0's fast route loads 16 bytes from sample-aligned addresses: probed once per device at ps_create (k0_unaligned_probe);
-                              // option k0_unaligned 0 restores the 16-byte condition of rounds 1-4 (tests)
-    int single_pass = 1;      // 1 (round 6): ps_detect_segment_trace runs K0 once over the whole trace (detector + every event from one digest), 0: the two calls
-    int gather_fused = 1;     // 1 (round 6): the gather places its items from per-256-job count sums (gather_scan_kernel), no item_scan_kernel; 0: rounds 2-5
-    int download_by_kernel = 1;   // 1 (round 6): status block + per-event offsets go back by a kernel writing pinned memory, 0: hipMemcpyAsync
-    int debug = 0;            // option debug: the library says on stderr which seams gave up, which occupancy it found (prints only; results unchanged)
-#ifdef PS_DIAG
-    // Diagnostics that return WRONG or stale results exist in libporeseg_diag.so only (make -C pypore_amd/csrc diag): the product
-    // library neither holds this code nor reads the environment (round 6).
-    int dbg_phase = 0;        // 1 a call that repeats the previous one's layout skips K0 (the digest is still there: what the scan kernels cost
-                              // on their own), 2 K0 only
-    int dbg_k0_nogrp = 0;     // 1 a call that repeats the previous one's layout runs K0 WITHOUT its group-record part (the records of the previous
-                              // call are still there and the scans read those: what K0's ~37 instructions per block cost the step)
-#endif
-    int k0_shared = 0;        // 1: upload + K0 of this context run on the device's shared FRONT stream (round 5): the K0 launches of all contexts that
-                              // ask for it are serialised there, back to back, and the context's own stream takes over behind an event.  K0 is the
-                              // one kernel of a call that is bound by HBM; several of them at once only share the same bytes per second while the
-                              // scan kernels behind each of them wait -- in a row, call i's scans run under call i+1's K0.  engine.StreamPool sets it.
     bool stream_idle = true;  // the context's stream had nothing queued when the current call began (no hand-over to the front stream needed)
-    int tree_par = 1;         // 1: subtree jobs on the 64-bit digest (filtered events: deep recursions) are shared by the waves of a workgroup (tree_par_kernel), 0: one wave per job
-    int groups = 1;           // 1: K0 writes group records and the window scans start with the coarse pass over them (narrow digest), 0: every row is swept
-    int scan_bs = 1;          // 1: block-sum scan with single-wave workgroups (seg_bs.hpp), 0: LDS-window scan
-    int wide_bs = 1;          // 1: counts too wide for the 32-bit digest are retried on the 64-bit digest, 0: straight to the LDS-window scan
-    int bridge_single = 1 << 30;   // anchors a single-wave bridge adds before it hands the seam to the look-ahead kernel (measured: handing over early is slower)
-    int tree_tail_pct = 0;    // tree_mw_kernel: share of the job list drawn dynamically (counter in HBM) at the end
-    // Share of the resident wave slots the single-wave scan kernels are launched on (experiments; the subtree kernel
-    // decides on the device how many of its slots work: tree_jobs_per_wave, seg_device.hpp: tree_kernel).  Measured on
-    // the bench trace with 100 / 75 / 62 / 50 / 44 / 37 %: four calls in flight 0.274 / 0.253 / 0.250 / 0.2445 / 0.257 /
-    // 0.270 ms per step, one call 0.522 / 0.499 / 0.511 / 0.505 / 0.572 / 0.563 ms (below 50 % the spine kernel's 2 048
-    // tiles are no longer all resident); on the 1e9-sample trace 50 % costs 23 % (spine 0.76 -> 1.12 ms, subtrees 0.68 ->
-    // 0.90): with many jobs per slot four waves per SIMD deliver 1.4 x the throughput of two.
-    int slots_pct = 100;
-    int tree_jobs_per_wave = 4;   // subtree kernel: jobs / this many slots work, between half and all of them (0: all)
-    int tree_screen = 1;          // 1: on the narrow digest tree_screen_kernel runs in front of the subtree kernel and leaves it the jobs it cannot
-                                  // prove empty (seg_device.hpp), 0: the subtree kernel takes every job, launch for launch as before
     // host-side caches: workgroups per CU per kernel, dynamic-LDS attribute last set, the tile tables of the last call
     struct OccKey { const void *fn; int nt; size_t lds; int per_cu; };
     std::vector<OccKey> occ_cache;
@@ -202,28 +162,17 @@ struct ps_ctx {
         DeviceTilePlan plan;
     } tile_cache;
     DevBuf bsum, ev_info, chunk_mabs, ev_boff, blk_mm, grp, up_dev;
-    // The segmentation chain's own buffers and options are flat members.  The state of every self-contained feature stands
-    // together in a sub-struct (filt, align, pw, trf, ss, sp, nt, hmm): its buffers, its budgets, its host-side caches.  A new feature
-    // adds its group here and nowhere else: the buffers free themselves with the context.
+    // The segmentation chain's own buffers are flat members.  The state of every self-contained feature stands together in a
+    // sub-struct (filt, align, pw, trf, ss, sp, nt, hmm): its buffers and its host-side caches.  A new feature adds its group here
+    // -- the buffers free themselves with the context --, and an option of it is a member of CtxOptions and a row of its table.
     struct {                // Bessel filter (ps_filter_bessel, ps_filter_bessel_batch, ps_filter_requantise_batch)
         DevBuf fwd, agg, zin;
         DevBuf tab, rq_par;   // a batch's event and unit tables (filt_plan.hpp; the re-quantisation's behind them), (centre, 1 / step, step) per event
-        int fused = 1;        // option filter_fused 1: fast filters run both directions in one kernel over tiles with halos, 0: always the exact three-pass scan
-        long long batch_scratch = FILT_BATCH_SCRATCH_DEFAULT;   // option filt_batch_scratch: bytes of order-n scratch rows per launch of a batch
     } filt;
-    struct {                  // statistics of caller-given ranges (ps_range_stats): the range and unit tables (range_plan.hpp), a RangePart per unit
-        DevBuf tab, part;
-        long long tile = RANGE_TILE_DEFAULT;     // option range_tile: samples per unit at most
-    } rng;
+    struct { DevBuf tab, part; } rng;        // statistics of caller-given ranges (ps_range_stats): the range and unit tables (range_plan.hpp), a RangePart per unit
     struct { DevBuf in, scratch; } align;    // profile aligner (ps_align_batch)
-    struct {                  // pairwise aligner (ps_pairwise_scores / ps_pairwise_batch): offsets and pair tables, per-workgroup matrices
-        DevBuf in, scratch;
-        long long budget = 2ll << 30;        // option pairwise_budget: bytes of pairwise scratch per launch
-    } pw;
-    struct {                  // NaiveTRF's splitter (ps_trf_split_batch): offsets and the capacity flag, per-workgroup mask and pointer bits
-        DevBuf in, scratch;
-        long long budget = 2ll << 30;        // option trf_budget: bytes of splitter scratch per launch
-    } trf;
+    struct { DevBuf in, scratch; } pw;       // pairwise aligner (ps_pairwise_scores / ps_pairwise_batch): offsets and pair tables, per-workgroup matrices
+    struct { DevBuf in, scratch; } trf;      // NaiveTRF's splitter (ps_trf_split_batch): offsets and the capacity flag, per-workgroup mask and pointer bits
     DevBuf ev_info_tr;        // single-pass file route (ps_detect_segment_trace): (centre, phase, first block) of the events cut out of a trace-aligned digest
     DevBuf blk_cls, cls_mm;   // ... K0's verdict per block against the detector's threshold (2 bits), min / max per 128 blocks
     DevBuf pre_c;             // exact route (ps_segment_exact_f64): c and c2 of the call's samples, 16 B per sample
@@ -234,12 +183,12 @@ struct ps_ctx {
     // and their scan, hits before each event of the first / second compaction (off1, off2), hit list (hits: low / tics), pair
     // offsets, keep flags, kept pairs, the filtered current, event lengths, span offsets
     struct { DevBuf tab, tab2, mask, cnt, excl, off1, off2, hits, pair_off, keep, kept, y, len, span_off; } sp;
-    // Near-tie log of the segment calls (DevCfg::nt_log, ps_get_near_ties): nt.cap records (option near_tie_log, 0: off), allocated
+    // Near-tie log of the segment calls (DevCfg::nt_log, ps_get_near_ties): opt.near_tie_log records (0: off), allocated
     // with the first call that logs.  nt.seen: records the last segment call counted (-1: not counted), nt.call_cap the capacity
     // it ran with; nt.ev_start / nt.ev_len: its events, kept only when it logged any (the records are mapped to them on request).
     struct {
         DevBuf log;
-        int64_t cap = 65536, hdr_cap = -1;     // (hdr_cap: the capacity the header on the device names; -1: none written)
+        int64_t hdr_cap = -1;                  // the capacity the header on the device names; -1: none written
         int64_t seen = -1, call_cap = 0;
         std::vector<int64_t> ev_start, ev_len;
     } nt;
@@ -247,31 +196,17 @@ struct ps_ctx {
         // HMM decoding (ps_hmm_batch): the model's last upload (host copy compared on every call), offsets, backpointers, results
         DevBuf model, off, bp, last, flags;
         std::vector<char> blob;
-        long long bp_budget = 512ll << 20;   // option hmm_bp_budget: bytes of Viterbi backpointers per launch
         // Baum-Welch E-step (ps_hmm_expect): forward matrices of one launch, per-workgroup accumulator rows, the skipped count
         DevBuf fmat, acc, skip;
         DevBuf pmax;                         // ps_hmm_posterior: the per-observation maxima that d_map_logp sums
         DevBuf samp;                         // ps_hmm_sample: the sampling tables, then the observation and path offsets
-        long long fb_budget = 4ll << 30;     // option hmm_fb_budget: bytes of forward matrices per launch
-        bool expect_lds = true;              // option hmm_expect_lds 0: the accumulator rows stay in global memory
     } hmm;
-    int stitch_host = 0;      // 1: host stitch with halo tiles (the fallback path) always
     DevBuf ev_len, det_counts, det_tics, det_cand;
     DevBuf bridges, bmeta, tile_i32, sp_off, spine_items, asm_hdr, ev_first_tile;
     DevBuf bridge_ext, ext_slot, ext_list;          // second chance for seams that gave up (seg_device.hpp: EXT_MAX)
     DevBuf lat_state, lat_seam, lat_res;            // helpers of the look-ahead kernel (seg_device.hpp: LAT_D)
     unsigned lat_tag_next = 1;                      // tags handed to calls so far (24 bits; the results are cleared before they run out)
     unsigned lat_tag_base = 0;                      // this call's
-    int lat_help = 1;                               // option lat_help / PORESEG_LAT_HELP: 0 = every seam walks alone, as before round 5
-    int bridge_budget = BR_MAX;                     // option bridge_budget (1 .. BR_MAX): anchors before a seam gives up -- tests lower it to reach the second chance on small inputs
-    int bridge_ext_on = 1;                          // option bridge_ext / PORESEG_BRIDGE_EXT: 0 = straight to the host stitch, as before round 5
-    // option short_chain (include/poreseg.h): launches a call can do without.  Bits: SC_NO_LA a pooled call (shared_n > 1) issues no
-    // look-ahead launch -- its bridges walk pool_patience windows, a seam still deferred takes the second chance; SC_NO_UPLOAD the
-    // download kernel leaves the status block zero, so that a call that repeats the layout launches no upload (small_clean)
-    int short_chain = SC_ALL;
-    int shared_n = 0;                               // option shared_device as last set (<= 1: a lone context)
-    int hw_queues = 0;                              // option hw_queues: the hardware queues shared_device plans for (0: the process's, process_hw_queues)
-    int pool_patience = BR_PATIENCE_POOL;           // option bridge_patience (1 .. 4096): tests lower it to reach the hand-over on small inputs
     // la_keep: a pooled call whose bridges left seams deferred had the look-ahead kernel run behind its stitch, a round trip late;
     // the next LA_KEEP calls of the context launch it in the chain again, patience 3, as without the option (the data at hand has
     // long stretches without splits), then the option is tried anew.  la_now: the current call is one of those.
@@ -283,13 +218,9 @@ struct ps_ctx {
     DevBuf spine_jobs, spine_scratch, spine_dense, spine_meta, tree_jobs, tree_scratch, tree_spill, tree_defer, screen_acc,
         tree_counts, items, item_pos, first_item, ev_off, bounds_off, small;
     HostBuf h_meta, h_dense, h_small, h_up;
-    int timing = 1;           // 0: no events, 1: start/end of the sequence, 2: an event between the phases as well (each costs
-                              // ~6 us of idle GPU: the next kernel does not start back to back)
-    double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int64_t counters[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, -1, -1, 0, 0, 0, 0};   // [12] chunk results the look-ahead helpers published, [13] of which an owner took,
-                              // [14] subtree jobs tree_screen_kernel deferred, [15] windows it decided (-1: it was not launched),
-                              // [16] [17] look-ahead / upload launches the call did without (option short_chain), [18] seams its
-                              // bridges left deferred that the second chance resumed
+    double ms[PS_MS_COUNT] = {};              // what ps_get_timings returns (include/poreseg.h: PS_MS_*, PS_CNT_*)
+    int64_t counters[PS_CNT_COUNT] = {};
+    ps_ctx() { counters[PS_CNT_TREE_DEFERRED] = counters[PS_CNT_WINDOWS_SCREEN] = -1; }     // (the screen kernel was not launched)
     bool screen_ran = false;  // the current call launched tree_screen_kernel
 };
 
@@ -315,7 +246,7 @@ int fail(ps_ctx *ctx, int code, const char *fmt, ...)
             return fail(ctx, PS_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
-// The front stream of a device (ps_ctx::k0_shared): one stream per device and process on which the upload + K0 launches of
+// The front stream of a device (option k0_shared): one stream per device and process on which the upload + K0 launches of
 // all contexts are queued back to back (the mutex keeps one call's pair of launches and its event together).
 struct FrontStream { std::mutex mu; hipStream_t s = nullptr; };
 FrontStream g_front[16];
@@ -327,7 +258,7 @@ FrontStream *front_for(ps_ctx *ctx)
     if (!f->s) {
 #ifdef PS_DIAG
         int lo = 0, hi = 0;
-        const char *pr = std::getenv("PORESEG_FRONT_PRIORITY");         // 1: highest priority the device offers (experiments)
+        const char *pr = std::getenv(ENV_FRONT_PRIORITY);         // 1: highest priority the device offers (experiments)
         if (pr && std::atoi(pr) != 0 && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess) {
             if (hipStreamCreateWithPriority(&f->s, hipStreamNonBlocking, hi) != hipSuccess) { f->s = nullptr; (void)hipGetLastError(); }
         }
@@ -337,7 +268,7 @@ FrontStream *front_for(ps_ctx *ctx)
     return f;
 }
 
-// K0 admission (ps_ctx::k0_admit): at most M calls of a device have their K0 in flight at a time.  K0 is bound by HBM: T of them
+// K0 admission (option k0_admit): at most M calls of a device have their K0 in flight at a time.  K0 is bound by HBM: T of them
 // side by side only share the same bytes per second, and all of them -- with every call's scan kernels behind them -- finish late
 // together (sixteen contexts: 0.188 -> 0.175 ms per step with M = 3, round 5).  Round 6: ON THE DEVICE.  The calls of a device
 // take tickets; call t queues, in front of its K0, a wait for the event recorded behind the K0 of call t - M (hipStreamWaitEvent:
@@ -450,14 +381,14 @@ int make_cfg(ps_ctx *ctx, const void *d_samples, const ps_sample_format *fmt, in
     //  upstream, include/poreseg.h)
     c->off_counts = fmt->dtype == PS_DTYPE_F32 ? 0 : fmt->offset_counts;
     c->dc_counts = fmt->dtype == PS_DTYPE_F32 ? static_cast<double>(fmt->offset_counts) : 0.0;
-    c->noise_k = ctx->noise_k;
+    c->noise_k = opt_noise_k(ctx->opt.noise_k_ppm);
     c->inv_q = static_cast<float>(1.0 / fmt->quantum);
     c->q = fmt->quantum;
     c->q2 = fmt->quantum * fmt->quantum;
     c->mw = mw; c->maxw = maxw; c->W = W; c->half = W / 2;
     c->min_gain = min_gain;
-    c->mode = ctx->mode;
-    c->prune = ctx->prune;
+    c->mode = ctx->opt.mode;
+    c->prune = ctx->opt.prune;
     c->lds_cap = std::max(1, std::min(W, ctx->lds_max_samples));
     c->bsum = nullptr; c->ev_info = nullptr; c->chunk_tot = nullptr; c->blk_mm = nullptr; c->grp = nullptr; c->bs_wide = 0;
     c->blk_cls = nullptr; c->cls_mm = nullptr; c->cls_kthr = 0;
@@ -465,7 +396,7 @@ int make_cfg(ps_ctx *ctx, const void *d_samples, const ps_sample_format *fmt, in
     c->pre_c = nullptr; c->pre_c2 = nullptr;
     c->dbg = ctx->small.as<SmallLayout>()->stamp;
     c->nt_log = nullptr;
-    c->rep_eval = ctx->rep_eval; c->rep_stage = ctx->rep_stage; c->rep_sum = ctx->rep_sum;
+    c->rep_eval = ctx->opt.rep_eval; c->rep_stage = ctx->opt.rep_stage; c->rep_sum = ctx->opt.rep_sum;
     return PS_OK;
 }
 
@@ -520,13 +451,13 @@ template <typename K> unsigned resident_slots(ps_ctx *ctx, K kernel, int nt, siz
         cu_count(ctx);
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, nt, lds) != hipSuccess || per_cu <= 0)
             per_cu = 1;
-        if (ctx->debug) fprintf(stderr, "[poreseg] occupancy: %d workgroups of %d threads per CU (dynamic LDS %zu), %d CUs\n", per_cu, nt, lds, ctx->n_cu);
+        if (ctx->opt.debug) fprintf(stderr, "[poreseg] occupancy: %d workgroups of %d threads per CU (dynamic LDS %zu), %d CUs\n", per_cu, nt, lds, ctx->n_cu);
         ctx->occ_cache.push_back({fn, nt, lds, per_cu});
     }
     unsigned slots = static_cast<unsigned>(per_cu) * static_cast<unsigned>(ctx->n_cu);
-    const int pct = nt <= 256 ? ctx->slots_pct : 100;
+    const int pct = nt <= 256 ? ctx->opt.slots_pct : 100;
     slots = std::max(1u, static_cast<unsigned>(static_cast<unsigned long long>(slots) * static_cast<unsigned>(pct) / 100u));
-    if (ctx->debug) fprintf(stderr, "[poreseg] resident slots: %u (%d threads, dynamic LDS %zu, slots_pct %d)\n", slots, nt, lds, pct);
+    if (ctx->opt.debug) fprintf(stderr, "[poreseg] resident slots: %u (%d threads, dynamic LDS %zu, slots_pct %d)\n", slots, nt, lds, pct);
     return slots;
 }
 
@@ -560,7 +491,7 @@ template <typename K> int scan_shape(ps_ctx *ctx, K kernel, int nt, size_t lds, 
 // (block-sum scan) holds nothing (scan_lds_pad: diagnostics)
 template <int NT, typename K> int scan_shape(ps_ctx *ctx, K kernel, const DevCfg &cfg, unsigned want, ScanShape *s)
 {
-    return scan_shape(ctx, kernel, NT, NT == 64 ? static_cast<size_t>(ctx->scan_lds_pad) : lds_bytes_for(cfg.lds_cap, NT), want, s);
+    return scan_shape(ctx, kernel, NT, NT == 64 ? static_cast<size_t>(ctx->opt.scan_lds_pad) : lds_bytes_for(cfg.lds_cap, NT), want, s);
 }
 
 template <int NT, int DT> int launch_spine(ps_ctx *ctx, const DevCfg &cfg, unsigned nj, SmallLayout *sm, bool list_mode = false)
@@ -586,7 +517,7 @@ template <int NT, int DT> int launch_tree(ps_ctx *ctx, const DevCfg &cfg, unsign
                        static_cast<long long>(n_jobs), d_hdr,
                        // (not on the 64-bit digest: those are filtered events, whose jobs hold many windows each -- 32 of them:
                        //  subtree kernel 1.30 ms on all slots, 1.71 ms with the rule)
-                       NT == 64 && !(DT & DT_WIDE) ? ctx->tree_jobs_per_wave : 0, par_max_jobs,
+                       NT == 64 && !(DT & DT_WIDE) ? ctx->opt.tree_jobs_per_wave : 0, par_max_jobs,
                        screened ? ctx->tree_defer.as<int2>() : nullptr, screened ? sm->tree_defer : nullptr,
                        screened ? ctx->screen_acc.as<unsigned long long>() : nullptr);
     HIP_TRY(ctx, hipGetLastError());
@@ -615,7 +546,7 @@ template <int DT> int launch_tree_screened(ps_ctx *ctx, const DevCfg &cfg, unsig
 // LDS-window scan: the spine kernel at the option's width (spine_nt)
 int launch_spine_nt(ps_ctx *ctx, const DevCfg &cfg, unsigned nj, SmallLayout *sm, bool list_mode)
 {
-    return by_nt<256, 512, 1024>(ctx->spine_nt, [&](auto nt) {
+    return by_nt<256, 512, 1024>(ctx->opt.spine_nt, [&](auto nt) {
         return by_dtype(cfg.dtype, [&](auto dt) { return launch_spine<decltype(nt)::value, dt()>(ctx, cfg, nj, sm, list_mode); });
     });
 }
@@ -629,7 +560,7 @@ template <int DT> int launch_tree_mw(ps_ctx *ctx, const DevCfg &cfg, unsigned nj
     hipLaunchKernelGGL((tree_mw_kernel<DT>), dim3(s.grid), dim3(64 * TREE_W), s.lds, ctx->stream, cfg,
                        ctx->tree_jobs.as<TreeJob>(), ctx->tree_scratch.as<int32_t>(), ctx->tree_spill.as<int2>(),
                        ctx->tree_counts.as<int32_t>(), reinterpret_cast<unsigned *>(&sm->status), &sm->work0,
-                       static_cast<long long>(n_jobs), d_hdr, &sm->tree_tail, ctx->tree_tail_pct);
+                       static_cast<long long>(n_jobs), d_hdr, &sm->tree_tail, ctx->opt.tree_tail_pct);
     HIP_TRY(ctx, hipGetLastError());
     return PS_OK;
 }
@@ -657,12 +588,12 @@ template <int DT> int launch_tree_par(ps_ctx *ctx, const DevCfg &cfg, unsigned n
 int launch_subtrees(ps_ctx *ctx, const DevCfg &cfg, unsigned nj, SmallLayout *sm, size_t n_jobs, const AsmHeader *d_hdr)
 {
     if (cfg.bsum != nullptr && cfg.bs_wide) {
-        if (ctx->tree_par) return by_dtype<DT_WIDE>(cfg.dtype, [&](auto dt) { return launch_tree_par<dt()>(ctx, cfg, nj, sm, n_jobs, d_hdr); });
-        if (ctx->tree_mw) return by_dtype<DT_WIDE>(cfg.dtype, [&](auto dt) { return launch_tree_mw<dt()>(ctx, cfg, nj, sm, n_jobs, d_hdr); });
+        if (ctx->opt.tree_par) return by_dtype<DT_WIDE>(cfg.dtype, [&](auto dt) { return launch_tree_par<dt()>(ctx, cfg, nj, sm, n_jobs, d_hdr); });
+        if (ctx->opt.tree_mw) return by_dtype<DT_WIDE>(cfg.dtype, [&](auto dt) { return launch_tree_mw<dt()>(ctx, cfg, nj, sm, n_jobs, d_hdr); });
         return by_dtype<DT_WIDE>(cfg.dtype, [&](auto dt) { return launch_tree<64, dt()>(ctx, cfg, nj, sm, n_jobs, d_hdr); });
     }
     if (cfg.bsum != nullptr) {
-        if (ctx->tree_mw) return by_dtype(cfg.dtype, [&](auto dt) { return launch_tree_mw<dt()>(ctx, cfg, nj, sm, n_jobs, d_hdr); });
+        if (ctx->opt.tree_mw) return by_dtype(cfg.dtype, [&](auto dt) { return launch_tree_mw<dt()>(ctx, cfg, nj, sm, n_jobs, d_hdr); });
 #ifndef PS_STAMP
         // the screen proves windows empty from the group records, in the product's mode only: without them (option groups 0,
         // prune 0) it could decide nothing, and verify mode checks every window of the full scan
@@ -670,13 +601,13 @@ int launch_subtrees(ps_ctx *ctx, const DevCfg &cfg, unsigned nj, SmallLayout *sm
         //  subtree kernel alone, which computes the same)
         const bool reserved = ctx->tree_defer.cap >= n_jobs * sizeof(int2) &&
                               ctx->screen_acc.cap >= static_cast<size_t>(SCREEN_ACC) * SCREEN_ACC_STRIDE * sizeof(unsigned long long);
-        if (ctx->tree_screen && reserved && cfg.mode == MODE_FAST && cfg.grp != nullptr && cfg.prune) {
+        if (ctx->opt.tree_screen && reserved && cfg.mode == MODE_FAST && cfg.grp != nullptr && cfg.prune) {
             return by_dtype(cfg.dtype, [&](auto dt) { return launch_tree_screened<dt()>(ctx, cfg, nj, sm, n_jobs, d_hdr); });
         }
 #endif
         return by_dtype(cfg.dtype, [&](auto dt) { return launch_tree<64, dt()>(ctx, cfg, nj, sm, n_jobs, d_hdr); });
     }
-    return by_nt<512, 256>(ctx->tree_nt, [&](auto nt) {
+    return by_nt<512, 256>(ctx->opt.tree_nt, [&](auto nt) {
         return by_dtype(cfg.dtype, [&](auto dt) { return launch_tree<decltype(nt)::value, dt()>(ctx, cfg, nj, sm, n_jobs, d_hdr); });
     });
 }
@@ -712,9 +643,9 @@ int run_spines(ps_ctx *ctx, const DevCfg &cfg, const std::vector<SpineJob> &jobs
     SmallLayout *sm = ctx->small.as<SmallLayout>();
     HIP_TRY(ctx, hipMemcpyAsync(ctx->spine_jobs.p, ctx->h_up.p, nj * sizeof(SpineJob), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(&sm->dense, 0, sizeof(unsigned long long), ctx->stream));
-    if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
+    if (ctx->opt.timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[0], ctx->stream));
     if (int lrc = launch_spine_nt(ctx, cfg, static_cast<unsigned>(nj), sm, false)) return lrc;
-    if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    if (ctx->opt.timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
     HIP_TRY(ctx, ctx->h_meta.reserve(nj * sizeof(int4)));
     HIP_TRY(ctx, ctx->h_small.reserve(sizeof(SmallLayout)));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->h_meta.p, ctx->spine_meta.p, nj * sizeof(int4), hipMemcpyDeviceToHost, ctx->stream));
@@ -730,7 +661,7 @@ int run_spines(ps_ctx *ctx, const DevCfg &cfg, const std::vector<SpineJob> &jobs
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     float ms = 0;
-    if (ctx->timing >= 2 && hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess) ctx->ms[0] += ms;
+    if (ctx->opt.timing >= 2 && hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]) == hipSuccess) ctx->ms[PS_MS_SPINE] += ms;
     const int4 *meta = ctx->h_meta.as<int4>();
     const int2 *dense = ctx->h_dense.as<int2>();
     for (size_t j = 0; j < nj; ++j) {
@@ -766,24 +697,24 @@ struct SegBatch {
 // phase stamps on stderr)
 void read_call_counters(ps_ctx *ctx, const DevCfg &cfg, const SmallLayout &hs)
 {
-    ctx->counters[0] = static_cast<int64_t>(hs.work0);
-    ctx->counters[1] = static_cast<int64_t>(hs.work1);
-    ctx->counters[5] = static_cast<int64_t>(hs.work2 & 0xffffffffULL) + static_cast<int64_t>(hs.work2 >> 32);   // exact decisions
-    ctx->counters[6] = static_cast<int64_t>(hs.work2 >> 32);                                                   // of which full fp64 window scans (block-sum scan)
+    ctx->counters[PS_CNT_WINDOWS] = static_cast<int64_t>(hs.work0);
+    ctx->counters[PS_CNT_CANDIDATES] = static_cast<int64_t>(hs.work1);
+    ctx->counters[PS_CNT_EXACT_RESCANS] = static_cast<int64_t>(hs.work2 & 0xffffffffULL) + static_cast<int64_t>(hs.work2 >> 32);   // exact decisions
+    ctx->counters[PS_CNT_FULL_EXACT_SCANS] = static_cast<int64_t>(hs.work2 >> 32);                                                   // of which full fp64 window scans (block-sum scan)
 #ifndef PS_STAMP
-    for (int k = 0; k < 3; ++k) ctx->counters[8 + k] = static_cast<int64_t>(hs.life[3 * k + 1]);              // window scans of the spine / bridge / subtree kernels
+    for (int k = 0; k < 3; ++k) ctx->counters[PS_CNT_WINDOWS_SPINE + k] = static_cast<int64_t>(hs.life[3 * k + 1]);              // window scans of the spine / bridge / subtree kernels
     // near-tie decisions (seg_bs.hpp: bs_decide); -1: not counted -- the call ran on the LDS-window kernels, which decide every window
     // by one fp64 scan and keep no margins (a caller that redoes near ties on the exact route redoes such a call)
-    ctx->counters[11] = cfg.bsum ? static_cast<int64_t>(hs.stamp[0]) : -1;
+    ctx->counters[PS_CNT_NEAR_TIES] = cfg.bsum ? static_cast<int64_t>(hs.stamp[0]) : -1;
     // ... and their records (ps_get_near_ties): the cursor came back with the status block
     ctx->nt.seen = cfg.bsum && cfg.nt_log ? static_cast<int64_t>(hs.nt_cur) : -1;
 #else
-    ctx->nt.seen = -1;                                 // (the stamps take counters[11]'s words: not counted)
+    ctx->nt.seen = -1;                                 // (the stamps take the near-tie count's words: not counted)
 #endif
-    ctx->counters[14] = ctx->screen_ran ? static_cast<int64_t>(hs.tree_defer[2]) : -1;                         // subtree jobs the screen deferred
-    ctx->counters[15] = ctx->screen_ran ? static_cast<int64_t>(hs.tree_defer[1]) : -1;                         // windows the screen decided
-    ctx->counters[12] = static_cast<int64_t>(hs.lat_ctl[4]);                                                   // look-ahead helpers: chunk results published
-    ctx->counters[13] = static_cast<int64_t>(hs.lat_ctl[5]);                                                   // ... and taken by an owner instead of scanning
+    ctx->counters[PS_CNT_TREE_DEFERRED] = ctx->screen_ran ? static_cast<int64_t>(hs.tree_defer[2]) : -1;                         // subtree jobs the screen deferred
+    ctx->counters[PS_CNT_WINDOWS_SCREEN] = ctx->screen_ran ? static_cast<int64_t>(hs.tree_defer[1]) : -1;                         // windows the screen decided
+    ctx->counters[PS_CNT_HELPER_CHUNKS_PUBLISHED] = static_cast<int64_t>(hs.lat_ctl[4]);                                                   // look-ahead helpers: chunk results published
+    ctx->counters[PS_CNT_HELPER_CHUNKS_TAKEN] = static_cast<int64_t>(hs.lat_ctl[5]);                                                   // ... and taken by an owner instead of scanning
 #ifdef PS_STAMP
     {
         static const char *nm[12] = {"level", "sweep", "drain", "decide", "contend", "setup", "exact", "outside", "-", "-", "-", "-"};
@@ -805,7 +736,7 @@ void read_call_counters(ps_ctx *ctx, const DevCfg &cfg, const SmallLayout &hs)
 // Option debug: says on stderr which seams of a failed device stitch gave up (their records are fetched for this alone)
 void report_failed_seams(ps_ctx *ctx)
 {
-    const size_t nt = static_cast<size_t>(ctx->counters[2]);
+    const size_t nt = static_cast<size_t>(ctx->counters[PS_CNT_TILES]);
     std::vector<int4> bm(nt), mt(nt);
     std::vector<SpineJob> jb(nt);
     if (!nt || hipMemcpy(bm.data(), ctx->bmeta.p, nt * sizeof(int4), hipMemcpyDeviceToHost) != hipSuccess ||
@@ -871,12 +802,12 @@ int queue_download(ps_ctx *ctx, size_t evb, bool one_copy, bool may_clear, int *
     if (one_copy) {
         HIP_TRY(ctx, ctx->h_small.reserve(sizeof(SmallLayout) + evb));
         void *h_dev = nullptr;                         // the pinned block as the device sees it (else: plain copy)
-        if (ctx->download_by_kernel && hipHostGetDevicePointer(&h_dev, ctx->h_small.p, 0) != hipSuccess) { h_dev = nullptr; (void)hipGetLastError(); }
+        if (ctx->opt.download_by_kernel && hipHostGetDevicePointer(&h_dev, ctx->h_small.p, 0) != hipSuccess) { h_dev = nullptr; (void)hipGetLastError(); }
         if (h_dev) {
             static_assert(sizeof(SmallLayout) % 8 == 0, "the status block is copied in 8-byte words");
             const long long nw = static_cast<long long>((sizeof(SmallLayout) + evb) / 8);
             // (a call without statistics on the screened route, see short_route: the calls the option was measured on)
-            if (may_clear && ctx->screen_ran && (ctx->short_chain & SC_NO_UPLOAD)) *dl_clear = static_cast<int>(sizeof(SmallLayout) / 8);
+            if (may_clear && ctx->screen_ran && (opt_short_chain_bits(ctx->opt.short_chain) & SC_NO_UPLOAD)) *dl_clear = static_cast<int>(sizeof(SmallLayout) / 8);
             hipLaunchKernelGGL(download_kernel, dim3(static_cast<unsigned>(std::min<long long>((nw + 255) / 256, 64))), dim3(256), 0, ctx->stream,
                                ctx->small.as<unsigned long long>(), static_cast<unsigned long long *>(h_dev), nw, *dl_clear, &sm->hdr.fail);
             HIP_TRY(ctx, hipGetLastError());
@@ -906,13 +837,13 @@ int finish_batch(ps_ctx *ctx, const DevCfg &cfg, const SegBatch &B, size_t n_tj,
     int rc;
     const size_t evb = (static_cast<size_t>(n_ev) + 1) * sizeof(int64_t);
     SmallLayout *sm = ctx->small.as<SmallLayout>();
-    if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
+    if (ctx->opt.timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[2], ctx->stream));
     if (n_tj) {
         const unsigned g = static_cast<unsigned>(std::min<size_t>(n_tj, 0x7fffffff));
         if (int lrc = launch_subtrees(ctx, cfg, g, sm, n_tj, d_hdr)) return lrc;
     }
-    if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
-    const bool fused = d_hdr != nullptr && ctx->gather_fused;      // (device stitch: job index == item index)
+    if (ctx->opt.timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
+    const bool fused = d_hdr != nullptr && ctx->opt.gather_fused;      // (device stitch: job index == item index)
     const bool one_copy = ctx->bounds_off.p == ctx->small.as<char>() + sizeof(SmallLayout);
     int dl_clear = 0;                                  // (option short_chain: the download kernel leaves the status block zero behind its copy)
     if (int grc = queue_gather(ctx, B, n_items, d_hdr, fused)) return grc;
@@ -927,14 +858,14 @@ int finish_batch(ps_ctx *ctx, const DevCfg &cfg, const SegBatch &B, size_t n_tj,
                                reinterpret_cast<unsigned *>(&sm->status), d_hdr);
         });
         HIP_TRY(ctx, hipGetLastError());
-        if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
+        if (ctx->opt.timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
     }
     if (int drc = queue_download(ctx, evb, one_copy, fused && d_stats == nullptr, &dl_clear)) return drc;
-    if (ctx->timing >= 1) HIP_TRY(ctx, hipEventRecord(ctx->ev[9], ctx->stream));
+    if (ctx->opt.timing >= 1) HIP_TRY(ctx, hipEventRecord(ctx->ev[9], ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     {
         float seq = 0;                                 // the call's device work, upload to result copies, by HIP events
-        if (ctx->timing >= 1 && hipEventElapsedTime(&seq, ctx->ev[8], ctx->ev[9]) == hipSuccess) ctx->ms[7] = seq;
+        if (ctx->opt.timing >= 1 && hipEventElapsedTime(&seq, ctx->ev[8], ctx->ev[9]) == hipSuccess) ctx->ms[PS_MS_SEQ] = seq;
     }
     std::memcpy(h_bounds_off, one_copy ? ctx->h_small.as<char>() + sizeof(SmallLayout) : ctx->h_meta.as<char>(), evb);
     const SmallLayout hs = *ctx->h_small.as<SmallLayout>();
@@ -945,7 +876,7 @@ int finish_batch(ps_ctx *ctx, const DevCfg &cfg, const SegBatch &B, size_t n_tj,
         const AsmHeader hd = hs.hdr;
         if (hdr_out) *hdr_out = hd;
         if (hd.fail) {
-            if (ctx->debug) report_failed_seams(ctx);
+            if (ctx->opt.debug) report_failed_seams(ctx);
             return RC_FALLBACK;
         }
     }
@@ -966,13 +897,13 @@ int finish_batch(ps_ctx *ctx, const DevCfg &cfg, const SegBatch &B, size_t n_tj,
         }
     }
     if (!stats_from_digest) {
-        if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
+        if (ctx->opt.timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[4], ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     float ms = 0;
-    if (ctx->timing >= 2 && hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]) == hipSuccess) ctx->ms[1] = ms;
-    if (ctx->timing >= 2 && hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]) == hipSuccess) ctx->ms[2] = ms;
-    ctx->ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - B.t_begin).count();
+    if (ctx->opt.timing >= 2 && hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]) == hipSuccess) ctx->ms[PS_MS_TREE] = ms;
+    if (ctx->opt.timing >= 2 && hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]) == hipSuccess) ctx->ms[PS_MS_GATHER] = ms;
+    ctx->ms[PS_MS_TOTAL] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - B.t_begin).count();
     ctx->small_clean = dl_clear > 0;                   // (the copy of a call that came through left the status block zero)
     return PS_OK;
 }
@@ -981,7 +912,7 @@ int finish_batch(ps_ctx *ctx, const DevCfg &cfg, const SegBatch &B, size_t n_tj,
 // The helpers' shared state for this call (none when switched off, or not the block-sum pipeline)
 LatHelp lat_help_of(ps_ctx *ctx, const DevCfg &cfg, SmallLayout *sm)
 {
-    if (!ctx->lat_help || cfg.bsum == nullptr || !ctx->lat_res.p) return LAT_NONE;
+    if (!ctx->opt.lat_help || cfg.bsum == nullptr || !ctx->lat_res.p) return LAT_NONE;
     LatHelp h;
     h.ctl = sm->lat_ctl;
     h.state = ctx->lat_state.as<unsigned long long>();
@@ -989,7 +920,7 @@ LatHelp lat_help_of(ps_ctx *ctx, const DevCfg &cfg, SmallLayout *sm)
     h.prog = sm->lat_prog;
     h.res = ctx->lat_res.as<unsigned long long>();
     h.tag_base = ctx->lat_tag_base;
-    h.stay = ctx->lat_help == 2 ? 1 : 0;
+    h.stay = ctx->opt.lat_help == 2 ? 1 : 0;
     return h;
 }
 
@@ -999,7 +930,7 @@ template <int DT> int launch_bridge_la(ps_ctx *ctx, const DevCfg &cfg, unsigned 
     hipLaunchKernelGGL((bridge_la_kernel<DT>), dim3(grid), dim3(64 * BR_LA), 0, ctx->stream, cfg,
                        ctx->spine_jobs.as<SpineJob>(), ctx->spine_scratch.as<int2>(), ctx->spine_meta.as<int4>(),
                        ctx->bridges.as<int2>(), ctx->bmeta.as<int4>(), reinterpret_cast<unsigned *>(&sm->status),
-                       &sm->work0, static_cast<int>(nj), nullptr, nullptr, nullptr, 0, ctx->bridge_budget, static_cast<int>(EXT_MAX),
+                       &sm->work0, static_cast<int>(nj), nullptr, nullptr, nullptr, 0, ctx->opt.bridge_budget, static_cast<int>(EXT_MAX),
                        lat_help_of(ctx, cfg, sm));
     HIP_TRY(ctx, hipGetLastError());
     return PS_OK;
@@ -1009,12 +940,12 @@ template <int DT> int launch_bridge_la(ps_ctx *ctx, const DevCfg &cfg, unsigned 
 // tree_screen 1 (launch_subtrees) -- and leaves every other route its launches, one for one.
 bool short_route(const ps_ctx *ctx, const DevCfg &cfg)
 {
-    return cfg.bsum != nullptr && !cfg.bs_wide && !ctx->tree_mw && ctx->tree_screen && cfg.mode == MODE_FAST && cfg.grp != nullptr && cfg.prune;
+    return cfg.bsum != nullptr && !cfg.bs_wide && !ctx->opt.tree_mw && ctx->opt.tree_screen && cfg.mode == MODE_FAST && cfg.grp != nullptr && cfg.prune;
 }
 // (a pooled call on that route issues no look-ahead launch: its bridges keep walking in their own wave)
 bool no_look_ahead(const ps_ctx *ctx, const DevCfg &cfg)
 {
-    return (ctx->short_chain & SC_NO_LA) != 0 && ctx->shared_n > 1 && ctx->bridge_ext_on && !ctx->la_now && short_route(ctx, cfg);
+    return (opt_short_chain_bits(ctx->opt.short_chain) & SC_NO_LA) != 0 && ctx->opt.shared_device > 1 && ctx->opt.bridge_ext && !ctx->la_now && short_route(ctx, cfg);
 }
 
 template <int NT, int DT> int launch_bridge(ps_ctx *ctx, const DevCfg &cfg, unsigned nj, SmallLayout *sm)
@@ -1024,9 +955,9 @@ template <int NT, int DT> int launch_bridge(ps_ctx *ctx, const DevCfg &cfg, unsi
     hipLaunchKernelGGL((bridge_kernel<NT, DT>), dim3(s.grid), dim3(NT), s.lds, ctx->stream, cfg,
                        ctx->spine_jobs.as<SpineJob>(), ctx->spine_scratch.as<int2>(), ctx->spine_meta.as<int4>(),
                        ctx->bridges.as<int2>(), ctx->bmeta.as<int4>(), reinterpret_cast<unsigned *>(&sm->status),
-                       &sm->work0, static_cast<int>(nj), ctx->bridge_single, ctx->bridge_budget,
+                       &sm->work0, static_cast<int>(nj), ctx->opt.bridge_single, ctx->opt.bridge_budget,
                        NT == 64 ? lat_help_of(ctx, cfg, sm) : LAT_NONE,
-                       no_look_ahead(ctx, cfg) ? ctx->pool_patience : static_cast<int>(BR_PATIENCE));
+                       no_look_ahead(ctx, cfg) ? ctx->opt.bridge_patience : static_cast<int>(BR_PATIENCE));
     HIP_TRY(ctx, hipGetLastError());
     return PS_OK;
 }
@@ -1036,7 +967,7 @@ void reset_call_stats(ps_ctx *ctx)
 {
     for (double &m : ctx->ms) m = 0;
     for (int64_t &c : ctx->counters) c = 0;
-    ctx->counters[14] = ctx->counters[15] = -1;
+    ctx->counters[PS_CNT_TREE_DEFERRED] = ctx->counters[PS_CNT_WINDOWS_SCREEN] = -1;
     ctx->screen_ran = false;
 }
 
@@ -1053,7 +984,7 @@ int reserve_items(ps_ctx *ctx, int64_t items_cap, int64_t total_len, int mw)
     HIP_TRY(ctx, ctx->item_pos.reserve((static_cast<size_t>(items_cap) + 1) * sizeof(int64_t)));
     HIP_TRY(ctx, ctx->tree_scratch.reserve(tscratch_bound * sizeof(int32_t)));
     HIP_TRY(ctx, ctx->tree_spill.reserve(tscratch_bound * sizeof(int2)));
-    if (ctx->tree_screen) {
+    if (ctx->opt.tree_screen) {
         HIP_TRY(ctx, ctx->tree_defer.reserve(n * sizeof(int2)));                       // the screen's deferred list: at most every job
         // ... and where its waves leave their window counts.  Invariant: all zero between calls -- zeroed here when allocated,
         // and the subtree kernel launched behind the screen clears every line it collects (launch_tree_screened clears them
@@ -1115,13 +1046,13 @@ void enqueue_k0(ps_ctx *ctx, const DevCfg &cfg, hipStream_t st, const K0Call &k,
 template <int FLAGS> int launch_k0(ps_ctx *ctx, const DevCfg &cfg, hipStream_t st, const K0Call &k)
 {
     const bool f32 = cfg.dtype == PS_DTYPE_F32;
-    int ns = 2;                                        // register sets of a persistent wave (ps_ctx::k0_sets)
+    int ns = 2;                                        // register sets of a persistent wave (option k0_sets)
     bool skip_k0 = false;
     uint4 *k0_grp = const_cast<uint4 *>(static_cast<const uint4 *>(cfg.grp));
 #ifdef PS_DIAG
-    if (k.batch && !(FLAGS & DT_WIDE) && ctx->k0_sets > 2 && ctx->k0_waves > 0) ns = ctx->k0_sets;
-    skip_k0 = ctx->dbg_phase == 1 && k.repeat;         // diagnostics: the previous call's digest
-    if (ctx->dbg_k0_nogrp && k.repeat) k0_grp = nullptr;
+    if (k.batch && !(FLAGS & DT_WIDE) && ctx->opt.k0_sets > 2 && ctx->opt.k0_waves > 0) ns = ctx->opt.k0_sets;
+    skip_k0 = ctx->opt.dbg_phase == 1 && k.repeat;         // diagnostics: the previous call's digest
+    if (ctx->opt.dbg_k0_nogrp && k.repeat) k0_grp = nullptr;
 #endif
     // K0 is persistent (round 5): k0_waves workgroups per CU (K0_WAVES waves each, i.e. that many waves per SIMD), every
     // wave striding over the wave blocks of the call with its next block's samples in flight.  One or two waves per SIMD
@@ -1130,10 +1061,10 @@ template <int FLAGS> int launch_k0(ps_ctx *ctx, const DevCfg &cfg, hipStream_t s
     const unsigned n_cu = k.persistent ? static_cast<unsigned>(cu_count(ctx)) : 0u;
     const unsigned k0_full = static_cast<unsigned>((k.nb_pad / K0_WB + K0_WAVES - 1) / K0_WAVES);
     // (a wave block of int16 samples is half the bytes: twice the waves keep the same bytes in flight)
-    const unsigned k0_per_cu = static_cast<unsigned>(ctx->k0_waves) * ((f32 || ns > 2) ? 1u : 2u);   // (ns > 2: diagnostic library only)
-    const unsigned k0_grid = k.persistent && ctx->k0_waves > 0 ? std::min(k0_full, k0_per_cu * n_cu * (4u / K0_WAVES)) : k0_full;
-    if (k.admit && ctx->k0_admit > 0) {
-        const int grc = chain_enter(ctx, ctx->device, ctx->k0_admit, st, &ctx->chain_ticket);
+    const unsigned k0_per_cu = static_cast<unsigned>(ctx->opt.k0_waves) * ((f32 || ns > 2) ? 1u : 2u);   // (ns > 2: diagnostic library only)
+    const unsigned k0_grid = k.persistent && ctx->opt.k0_waves > 0 ? std::min(k0_full, k0_per_cu * n_cu * (4u / K0_WAVES)) : k0_full;
+    if (k.admit && ctx->opt.k0_admit > 0) {
+        const int grc = chain_enter(ctx, ctx->device, ctx->opt.k0_admit, st, &ctx->chain_ticket);
         if (grc) return grc;
         ctx->chain_held = true;
     }
@@ -1167,9 +1098,9 @@ int k0_done(ps_ctx *ctx, hipStream_t st)
 template <int FLAGS> int launch_scans_bs(ps_ctx *ctx, const DevCfg &cfg, unsigned nj, SmallLayout *sm)
 {
     if (int rc = by_dtype<FLAGS>(cfg.dtype, [&](auto dt) { return launch_spine<64, dt()>(ctx, cfg, nj, sm, true); })) return rc;
-    if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
+    if (ctx->opt.timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
     if (int rc = by_dtype<FLAGS>(cfg.dtype, [&](auto dt) { return launch_bridge<64, dt()>(ctx, cfg, nj, sm); })) return rc;
-    if (no_look_ahead(ctx, cfg)) { ctx->counters[16] += 1; return PS_OK; }
+    if (no_look_ahead(ctx, cfg)) { ctx->counters[PS_CNT_LOOKAHEAD_SKIPPED] += 1; return PS_OK; }
     return by_dtype<FLAGS>(cfg.dtype, [&](auto dt) { return launch_bridge_la<dt()>(ctx, cfg, nj, sm); });
 }
 
@@ -1211,7 +1142,7 @@ int plan_or_reuse(ps_ctx *ctx, const SegBatch &B, DeviceCall &C)
     }
     C.nj = tc.plan.jobs.size();
     C.max_items = tc.plan.list_entries + static_cast<int64_t>(C.nj) * BR_MAX;
-    ctx->counters[2] = static_cast<int64_t>(C.nj);
+    ctx->counters[PS_CNT_TILES] = static_cast<int64_t>(C.nj);
     return PS_OK;
 }
 
@@ -1223,7 +1154,7 @@ int reserve_call_buffers(ps_ctx *ctx, const SegBatch &B, const DeviceCall &C)
     HIP_TRY(ctx, ctx->spine_scratch.reserve(std::max<int64_t>(1, plan.list_entries) * sizeof(int2)));
     HIP_TRY(ctx, ctx->spine_meta.reserve(std::max<size_t>(4, nj) * sizeof(int4)));
     HIP_TRY(ctx, ctx->bridges.reserve(std::max<size_t>(1, nj) * BR_MAX * sizeof(int2)));
-    if (C.use_bs && ctx->lat_help) {
+    if (C.use_bs && ctx->opt.lat_help) {
         // (published chunk results carry the tag of their listing; a fresh buffer is zero, tags start at 1, and before the 24
         //  bits run out the buffer is cleared)
         const size_t res_bytes = static_cast<size_t>(LAT_D) * LAT_C * sizeof(unsigned long long);
@@ -1257,13 +1188,13 @@ int queue_upload(ps_ctx *ctx, const SegBatch &B, const DeviceCall &C, hipStream_
     const char *up = ctx->h_up.as<char>();
     const size_t up_bytes = ctx->tile_cache.plan.up_bytes(B.n_ev);
     void *up_devptr = nullptr;                     // the pinned blob as the device sees it (else: plain copy)
-    if (ctx->upload_by_kernel && hipHostGetDevicePointer(&up_devptr, const_cast<char *>(up), 0) != hipSuccess) { up_devptr = nullptr; (void)hipGetLastError(); }
+    if (ctx->opt.upload_by_kernel && hipHostGetDevicePointer(&up_devptr, const_cast<char *>(up), 0) != hipSuccess) { up_devptr = nullptr; (void)hipGetLastError(); }
     // (option short_chain: the tables are still on the device and the previous call's download kernel left the status block zero)
     // (... on the route the option applies to, short_route, as far as it is known before K0: every other route launches what it launched)
-    const bool short_rt = C.use_bs && !C.wide && !C.digest_ready && ctx->groups && !ctx->tree_mw && ctx->tree_screen && C.cfg.mode == MODE_FAST && C.cfg.prune;
-    const bool skip_upload = C.reuse && ctx->small_clean_in && !front && short_rt && ctx->upload_by_kernel && (ctx->short_chain & SC_NO_UPLOAD);
+    const bool short_rt = C.use_bs && !C.wide && !C.digest_ready && ctx->opt.groups && !ctx->opt.tree_mw && ctx->opt.tree_screen && C.cfg.mode == MODE_FAST && C.cfg.prune;
+    const bool skip_upload = C.reuse && ctx->small_clean_in && !front && short_rt && ctx->opt.upload_by_kernel && (opt_short_chain_bits(ctx->opt.short_chain) & SC_NO_UPLOAD);
     ctx->small_clean_in = false;                   // (a redo of this call on another digest starts from a block it cleared itself)
-    if (skip_upload) ctx->counters[17] += 1;
+    if (skip_upload) ctx->counters[PS_CNT_UPLOAD_SKIPPED] += 1;
     else if (up_devptr) {
         // (tables still on the device from the previous call: the kernel only clears the status block)
         const long long n16 = C.reuse ? 0 : static_cast<long long>((up_bytes + 15) / 16);
@@ -1302,14 +1233,14 @@ int queue_digest(ps_ctx *ctx, const SegBatch &B, DeviceCall &C, hipStream_t fs, 
         cfg.bsum = ctx->bsum.p;
         cfg.ev_info = ctx->ev_info_tr.as<int4>();
         cfg.chunk_tot = ctx->chunk_mabs.as<int4>();
-        cfg.grp = ctx->groups ? ctx->grp.p : nullptr;
+        cfg.grp = ctx->opt.groups ? ctx->grp.p : nullptr;
         cfg.blk_mm = B.d_stats ? ctx->blk_mm.as<int>() : nullptr;
     } else if (C.use_bs && C.nj) {
         const DeviceTilePlan &plan = ctx->tile_cache.plan;
         const int64_t nb_pad = k0_padded_blocks(plan.boff[n_ev]);
         DigestWant want;
         want.wide = C.wide;
-        want.grp = !C.wide && ctx->groups;
+        want.grp = !C.wide && ctx->opt.groups;
         want.blk_mm = B.d_stats && !C.wide;
         if (int drc = reserve_digest(ctx, nb_pad, n_ev, want)) return drc;
         if (want.grp) cfg.grp = ctx->grp.p;
@@ -1331,7 +1262,7 @@ int queue_digest(ps_ctx *ctx, const SegBatch &B, DeviceCall &C, hipStream_t fs, 
 // *k0_only (diagnostic library, dbg_phase 2): the call ends here.
 int queue_upload_k0(ps_ctx *ctx, const SegBatch &B, DeviceCall &C, bool *k0_only)
 {
-    FrontStream *front = (ctx->k0_shared && C.use_bs && C.nj) ? front_for(ctx) : nullptr;
+    FrontStream *front = (ctx->opt.k0_shared && C.use_bs && C.nj) ? front_for(ctx) : nullptr;
     hipStream_t fs = front ? front->s : ctx->stream;
     std::unique_lock<std::mutex> front_lock;
     if (front) {
@@ -1342,13 +1273,13 @@ int queue_upload_k0(ps_ctx *ctx, const SegBatch &B, DeviceCall &C, bool *k0_only
         }
     }
     if (int urc = queue_upload(ctx, B, C, fs, front != nullptr)) return urc;
-    if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[7], fs));
+    if (ctx->opt.timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[7], fs));
     if (int drc = queue_digest(ctx, B, C, fs, front != nullptr)) return drc;
-    if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[0], fs));
+    if (ctx->opt.timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[0], fs));
     if (int crc = k0_done(ctx, fs)) return crc;         // (K0 is behind this event)
     *k0_only = false;
 #ifdef PS_DIAG
-    if (ctx->dbg_phase == 2) {                           // diagnostics: K0 only
+    if (ctx->opt.dbg_phase == 2) {                           // diagnostics: K0 only
         if (front) front_lock.unlock();
         HIP_TRY(ctx, hipStreamSynchronize(fs));
         for (int e = 0; e <= B.n_ev; ++e) B.h_bounds_off[e] = 0;
@@ -1378,14 +1309,14 @@ int queue_scans(ps_ctx *ctx, const DeviceCall &C)
             // LDS-window scan at the option's width (spine_nt); the widest spine is bridged by the 512-thread kernel
             lrc = launch_spine_nt(ctx, cfg, g, sm, true);
             if (lrc) return lrc;
-            if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
-            lrc = by_nt<256, 512>(ctx->spine_nt, [&](auto nt) {
+            if (ctx->opt.timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
+            lrc = by_nt<256, 512>(ctx->opt.spine_nt, [&](auto nt) {
                 return by_dtype(cfg.dtype, [&](auto dt) { return launch_bridge<decltype(nt)::value, dt()>(ctx, cfg, g, sm); });
             });
         }
         if (lrc) return lrc;
     }
-    if (ctx->timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
+    if (ctx->opt.timing >= 2) HIP_TRY(ctx, hipEventRecord(ctx->ev[1], ctx->stream));
     return PS_OK;
 }
 
@@ -1425,13 +1356,13 @@ int queue_stitch(ps_ctx *ctx, const SegBatch &B, const DeviceCall &C, const Stit
 int resume_deferred_seams(ps_ctx *ctx, const DeviceCall &C, int64_t n_def)
 {
     SmallLayout *sm = ctx->small.as<SmallLayout>();
-    if (ctx->debug) fprintf(stderr, "[poreseg] look-ahead kernel behind the stitch: %lld deferred seams\n", static_cast<long long>(n_def));
+    if (ctx->opt.debug) fprintf(stderr, "[poreseg] look-ahead kernel behind the stitch: %lld deferred seams\n", static_cast<long long>(n_def));
     HIP_TRY(ctx, hipMemsetAsync(&sm->hdr, 0, sizeof(AsmHeader), ctx->stream));
-    if (ctx->tree_screen) HIP_TRY(ctx, hipMemsetAsync(&sm->tree_defer[0], 0, sizeof sm->tree_defer[0], ctx->stream));
+    if (ctx->opt.tree_screen) HIP_TRY(ctx, hipMemsetAsync(&sm->tree_defer[0], 0, sizeof sm->tree_defer[0], ctx->stream));
     if (int lrc = by_dtype(C.cfg.dtype, [&](auto dt) { return launch_bridge_la<dt()>(ctx, C.cfg, static_cast<unsigned>(C.nj), sm); })) return lrc;
     ctx->la_keep = LA_KEEP;
-    ctx->counters[4] += n_def;
-    ctx->counters[18] += n_def;
+    ctx->counters[PS_CNT_REPAIRS] += n_def;
+    ctx->counters[PS_CNT_SEAMS_RESUMED] += n_def;
     return PS_OK;
 }
 
@@ -1447,7 +1378,7 @@ int extend_seams(ps_ctx *ctx, const DeviceCall &C, const std::vector<int> &list,
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));                       // (the list is the caller's local)
     HIP_TRY(ctx, hipMemsetAsync(&sm->hdr, 0, sizeof(AsmHeader), ctx->stream));
     // (the next round's screen starts a new list; what the rounds so far decided and deferred stays, as in work[])
-    if (ctx->tree_screen) HIP_TRY(ctx, hipMemsetAsync(&sm->tree_defer[0], 0, sizeof sm->tree_defer[0], ctx->stream));
+    if (ctx->opt.tree_screen) HIP_TRY(ctx, hipMemsetAsync(&sm->tree_defer[0], 0, sizeof sm->tree_defer[0], ctx->stream));
     const unsigned g = static_cast<unsigned>(n_ext);
     auto extend = [&](auto dt) {
         hipLaunchKernelGGL((bridge_la_kernel<dt(), true>), dim3(g), dim3(64 * BR_LA), 0, ctx->stream, C.cfg,
@@ -1459,7 +1390,7 @@ int extend_seams(ps_ctx *ctx, const DeviceCall &C, const std::vector<int> &list,
     if (C.wide) by_dtype<DT_WIDE>(C.cfg.dtype, extend);
     else by_dtype(C.cfg.dtype, extend);
     HIP_TRY(ctx, hipGetLastError());
-    ctx->counters[4] += static_cast<int64_t>(n_ext);
+    ctx->counters[PS_CNT_REPAIRS] += static_cast<int64_t>(n_ext);
     return PS_OK;
 }
 
@@ -1481,15 +1412,15 @@ int stitch_rounds(ps_ctx *ctx, const SegBatch &B, const DeviceCall &C)
     bool la_done = false, stride_set = false;          // (the look-ahead kernel ran behind the stitch; the stride of the side buffer is fixed)
     for (int round = 0;; ++round) {
         if (int qrc = queue_stitch(ctx, B, C, shape, items_cap, ext_stride)) return qrc;
-        if (ctx->timing >= 2 && round == 0) HIP_TRY(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
+        if (ctx->opt.timing >= 2 && round == 0) HIP_TRY(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
         rc = finish_batch(ctx, C.cfg, B, static_cast<size_t>(items_cap), items_cap, ctx->asm_hdr.as<AsmHeader>(), &hd, C.use_bs);
-        if (rc != RC_FALLBACK || !C.use_bs || !nj || round == EXT_ROUNDS + (la_done ? 1 : 0) || !ctx->bridge_ext_on) break;
+        if (rc != RC_FALLBACK || !C.use_bs || !nj || round == EXT_ROUNDS + (la_done ? 1 : 0) || !ctx->opt.bridge_ext) break;
         HIP_TRY(ctx, ctx->h_meta.reserve(2 * nj * sizeof(int4)));
         int4 *h_bm = ctx->h_meta.as<int4>(), *h_mt = h_bm + nj;
         HIP_TRY(ctx, hipMemcpyAsync(h_bm, ctx->bmeta.p, nj * sizeof(int4), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(h_mt, ctx->spine_meta.p, nj * sizeof(int4), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        const SecondChance sc = pick_second_chance(h_bm, h_mt, nj, ctx->bridge_budget, slots_used, stride_set, ext_stride, no_la && !la_done);
+        const SecondChance sc = pick_second_chance(h_bm, h_mt, nj, ctx->opt.bridge_budget, slots_used, stride_set, ext_stride, no_la && !la_done);
         if (sc.n_deferred) {
             if (int lrc = resume_deferred_seams(ctx, C, sc.n_deferred)) return lrc;
             la_done = true;
@@ -1498,20 +1429,20 @@ int stitch_rounds(ps_ctx *ctx, const SegBatch &B, const DeviceCall &C)
         ext_stride = sc.ext_stride;
         stride_set = true;
         if (sc.list.empty() || sc.hopeless) break;
-        if (ctx->debug) fprintf(stderr, "[poreseg] second chance, round %d: %zu seams continued on the device\n", round + 1, sc.list.size());
+        if (ctx->opt.debug) fprintf(stderr, "[poreseg] second chance, round %d: %zu seams continued on the device\n", round + 1, sc.list.size());
         if (int erc = extend_seams(ctx, C, sc.list, slots_used, ext_stride)) return erc;
         slots_used += static_cast<int>(sc.list.size());
         // room for the anchors the continued seams may add
         items_cap += static_cast<int64_t>(sc.list.size()) * ext_stride;
         if (int irc = reserve_items(ctx, items_cap, ctx->tile_cache.plan.total_len, B.mw)) return irc;
     }
-    ctx->counters[3] = hd.n_items;
+    ctx->counters[PS_CNT_TREE_JOBS] = hd.n_items;
     if (slots_used > 0 || la_done) ctx->small_clean = false;   // (a second round: the next call uploads as ever)
     float ms = 0;
-    if (ctx->timing >= 2 && nj && hipEventElapsedTime(&ms, ctx->ev[7], ctx->ev[0]) == hipSuccess) ctx->ms[6] = ms;       // blocksum_kernel (K0)
-    if (ctx->timing >= 2 && nj && hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[6]) == hipSuccess) ctx->ms[0] = ms;       // spine_kernel
-    if (ctx->timing >= 2 && nj && hipEventElapsedTime(&ms, ctx->ev[6], ctx->ev[1]) == hipSuccess) ctx->ms[5] = ms;       // bridge_kernel
-    if (ctx->timing >= 2 && hipEventElapsedTime(&ms, ctx->ev[1], ctx->ev[5]) == hipSuccess) ctx->ms[4] = ms;     // device stitch incl. header sync
+    if (ctx->opt.timing >= 2 && nj && hipEventElapsedTime(&ms, ctx->ev[7], ctx->ev[0]) == hipSuccess) ctx->ms[PS_MS_BLOCKSUM] = ms;       // blocksum_kernel (K0)
+    if (ctx->opt.timing >= 2 && nj && hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[6]) == hipSuccess) ctx->ms[PS_MS_SPINE] = ms;       // spine_kernel
+    if (ctx->opt.timing >= 2 && nj && hipEventElapsedTime(&ms, ctx->ev[6], ctx->ev[1]) == hipSuccess) ctx->ms[PS_MS_BRIDGE] = ms;       // bridge_kernel
+    if (ctx->opt.timing >= 2 && hipEventElapsedTime(&ms, ctx->ev[1], ctx->ev[5]) == hipSuccess) ctx->ms[PS_MS_STITCH] = ms;     // device stitch incl. header sync
     return rc;
 }
 
@@ -1591,7 +1522,7 @@ int upload_host_stitch(ps_ctx *ctx, const SegBatch &B, const HostStitch &st)
 int host_stitch_batch(ps_ctx *ctx, const DevCfg &cfg, const SegBatch &B)
 {
     const HostTilePlan plan = plan_host_tiles(B.ev_start, B.ev_len, B.n_ev, B.mw, B.W, ctx->tile_len, ctx->halo);
-    ctx->counters[2] = static_cast<int64_t>(plan.jobs.size());
+    ctx->counters[PS_CNT_TILES] = static_cast<int64_t>(plan.jobs.size());
     std::vector<TileList> lists;
     int rc = run_spines(ctx, cfg, plan.jobs, plan.scratch, lists);
     if (rc) return rc;
@@ -1602,7 +1533,7 @@ int host_stitch_batch(ps_ctx *ctx, const DevCfg &cfg, const SegBatch &B)
         std::vector<TileList> got;
         rc = run_spines(ctx, cfg, rj, rj[0].out_cap, got);
         if (rc) return false;
-        ctx->counters[4] += 1;
+        ctx->counters[PS_CNT_REPAIRS] += 1;
         *ext = std::move(got[0]);
         return true;
     };
@@ -1612,8 +1543,8 @@ int host_stitch_batch(ps_ctx *ctx, const DevCfg &cfg, const SegBatch &B)
     case STITCH_REPAIR_FAILED: return rc;
     case STITCH_NO_PROGRESS: return fail(ctx, PS_ERR_INTERNAL, "seam repair made no progress");
     }
-    ctx->counters[3] = static_cast<int64_t>(st.tjobs.size());
-    ctx->ms[4] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_stitch0).count();
+    ctx->counters[PS_CNT_TREE_JOBS] = static_cast<int64_t>(st.tjobs.size());
+    ctx->ms[PS_MS_STITCH] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_stitch0).count();
 
     rc = upload_host_stitch(ctx, B, st);
     if (rc) return rc;
@@ -1654,44 +1585,19 @@ int k0_unaligned_probe(int device, hipStream_t st)
 
 #ifdef PS_DIAG
 // libporeseg_diag.so only (make -C pypore_amd/csrc diag): a new context takes its settings from PORESEG_* variables, as every
-// build did until round 5.  The product library has no getenv: what a call returns depends on its arguments and on
+// build did until round 5 -- every option that has a variable (ctx_options.hpp), by the setter's own rules: a value it refuses is
+// reported and the default stays.  The product library has no getenv: what a call returns depends on its arguments and on
 // ps_set_option / ps_set_tiling, never on the caller's environment.
 namespace {
 void diag_env(ps_ctx *ctx)
 {
-    if (const char *e = std::getenv("PORESEG_MODE")) ctx->mode = std::atoi(e);
-    if (const char *e = std::getenv("PORESEG_SPINE_NT")) ctx->spine_nt = std::atoi(e);
-    if (const char *e = std::getenv("PORESEG_TREE_NT")) ctx->tree_nt = std::atoi(e);
-    if (const char *e = std::getenv("PORESEG_REP_EVAL")) ctx->rep_eval = std::max(1, std::atoi(e));
-    if (const char *e = std::getenv("PORESEG_REP_STAGE")) ctx->rep_stage = std::max(1, std::atoi(e));
-    if (const char *e = std::getenv("PORESEG_REP_SUM")) ctx->rep_sum = std::max(1, std::atoi(e));
-    if (const char *e = std::getenv("PORESEG_PRUNE")) ctx->prune = std::atoi(e) != 0;
-    if (const char *e = std::getenv("PORESEG_SCAN_BS")) ctx->scan_bs = std::atoi(e) != 0;
-    if (const char *e = std::getenv("PORESEG_GROUPS")) ctx->groups = std::atoi(e) != 0;
-    if (const char *e = std::getenv("PORESEG_TREE_PAR")) ctx->tree_par = std::atoi(e) != 0;
-    if (const char *e = std::getenv("PORESEG_K0_WAVES")) ctx->k0_waves = std::max(0, std::atoi(e));
-    if (const char *e = std::getenv("PORESEG_K0_SHARED")) ctx->k0_shared = std::atoi(e) != 0;
-    if (const char *e = std::getenv("PORESEG_DBG_PHASE")) ctx->dbg_phase = std::atoi(e);
-    if (const char *e = std::getenv("PORESEG_SCAN_LDS_PAD")) ctx->scan_lds_pad = std::max(0, std::atoi(e));
-    if (const char *e = std::getenv("PORESEG_K0_MAX")) ctx->k0_admit = std::max(0, std::atoi(e));
-    if (const char *e = std::getenv("PORESEG_NOISE_K")) ctx->noise_k = static_cast<float>(std::atof(e));
-    if (const char *e = std::getenv("PORESEG_WIDE_BS")) ctx->wide_bs = std::atoi(e) != 0;
-    if (const char *e = std::getenv("PORESEG_BRIDGE_SINGLE")) ctx->bridge_single = std::max(1, std::atoi(e));
-    if (const char *e = std::getenv("PORESEG_TREE_TAIL")) ctx->tree_tail_pct = std::max(0, std::min(100, std::atoi(e)));
-    if (const char *e = std::getenv("PORESEG_FILTER_FUSED")) ctx->filt.fused = std::atoi(e) != 0;
-    if (const char *e = std::getenv("PORESEG_UPLOAD")) ctx->upload_by_kernel = std::atoi(e) != 0;
-    if (const char *e = std::getenv("PORESEG_TIMING")) ctx->timing = std::max(0, std::min(2, std::atoi(e)));
-    if (const char *e = std::getenv("PORESEG_TREE_MW")) ctx->tree_mw = std::atoi(e) != 0;
-    if (const char *e = std::getenv("PORESEG_TREE_JPW")) ctx->tree_jobs_per_wave = std::max(0, std::atoi(e));
-    if (const char *e = std::getenv("PORESEG_SLOTS_PCT")) ctx->slots_pct = std::max(1, std::min(100, std::atoi(e)));
-    if (const char *e = std::getenv("PORESEG_STITCH")) ctx->stitch_host = std::string(e) == "host";
-    if (const char *e = std::getenv("PORESEG_TILE")) ctx->tile_len = std::atoll(e);
-    if (const char *e = std::getenv("PORESEG_BRIDGE_EXT")) ctx->bridge_ext_on = std::atoi(e) != 0;
-    if (const char *e = std::getenv("PORESEG_LAT_HELP")) ctx->lat_help = std::max(0, std::min(2, std::atoi(e)));
-    if (const char *e = std::getenv("PORESEG_BRIDGE_BUDGET")) ctx->bridge_budget = std::min(std::max(std::atoi(e), 1), static_cast<int>(BR_MAX));
-    if (const char *e = std::getenv("PORESEG_HALO")) ctx->halo = std::atoll(e);
-    if (const char *e = std::getenv("PORESEG_DEBUG")) ctx->debug = std::atoi(e) != 0 || e[0] == 0;
-    if (const char *e = std::getenv("PORESEG_DBG_K0_NOGRP")) ctx->dbg_k0_nogrp = std::atoi(e) != 0;
+    for (const char *name : opt_apply_env(&ctx->opt, std::getenv)) fprintf(stderr, "[poreseg] the environment's value of option %s is refused\n", name);
+    if (!ctx->opt.k0_unaligned) ctx->k0_unaligned = 0;
+    // what is no whole number for an option: the tiling, the stitch route by name, and PORESEG_DEBUG set to nothing
+    if (const char *e = std::getenv(ENV_TILE)) ctx->tile_len = std::atoll(e);
+    if (const char *e = std::getenv(ENV_HALO)) ctx->halo = std::atoll(e);
+    if (const char *e = std::getenv(ENV_STITCH)) ctx->opt.stitch_host = std::string(e) == "host";
+    if (const char *e = std::getenv(ENV_DEBUG)) ctx->opt.debug = ctx->opt.debug || e[0] == 0;
 }
 }  // namespace
 #endif
@@ -1801,103 +1707,45 @@ static int diag_mask_stream(ps_ctx *ctx, hipStream_t *st, int first, int count, 
 int ps_set_option(ps_ctx *ctx, const char *name, int64_t value)
 {
     if (!ctx || !name) return PS_ERR_ARG;
-    const std::string n(name);
-    if (n == "mode" && value >= 0 && value <= 2) ctx->mode = static_cast<int>(value);
-    else if (n == "stitch_host") ctx->stitch_host = value != 0;
-    else if (n == "prune") ctx->prune = value != 0;
-    else if (n == "scan_bs") ctx->scan_bs = value != 0;
-    else if (n == "near_tie_log" && value >= 0 && value <= (int64_t(1) << 30)) ctx->nt.cap = value;
-    else if (n == "groups") ctx->groups = value != 0;
-    else if (n == "tree_par") ctx->tree_par = value != 0;
-    else if (n == "k0_waves" && value >= 0 && value <= 16) ctx->k0_waves = static_cast<int>(value);
-    else if (n == "k0_shared") ctx->k0_shared = value != 0;
-    else if (n == "k0_admit" && value >= 0) ctx->k0_admit = static_cast<int>(value);
-    else if (n == "bridge_ext" && (value == 0 || value == 1)) ctx->bridge_ext_on = static_cast<int>(value);
-    // lat_help: 0 every seam walks alone, 1 idle workgroups of the look-ahead kernel help (they leave when nothing has been listed
-    // for ~0.1 ms), 2 as 1 but the helpers stay until every workgroup of the launch is through with its own seams -- for a test
-    // that must SEE the helpers work; only for a call that has the chip to itself (a helper then waits for nobody)
-    else if (n == "lat_help" && value >= 0 && value <= 2) ctx->lat_help = static_cast<int>(value);
-    // shared_device: the number of contexts that share this device (a pool of host threads, include/poreseg.h) -- one call that sets
-    // what engine.StreamPool set by hand until round 5.  Of n contexts min(n, hardware queues) calls execute at a time: the call
-    // is planned for that many (ps_pool_plan, pool_plan.hpp), but it is a pooled call (shared_n: no_look_ahead) whenever n > 1
-    else if (n == "shared_device" && value >= 0 && value <= 4096) {
+    const CtxOptions before = ctx->opt;
+    const OptRow *row = nullptr;
+    if (opt_set(&ctx->opt, name, value, &row) != OPT_OK) return fail(ctx, PS_ERR_ARG, "unknown option or value: %s", name);
+    switch (row->effect) {                              // the options that act on the context
+    case FX_SHARED_DEVICE: {                            // one call that sets what ps_pool_plan says for that many contexts
         ps_pool_plan_t plan;
-        if (pool_plan(static_cast<int>(value), ctx->hw_queues > 0 ? ctx->hw_queues : process_hw_queues(), &plan) != PS_OK)
+        if (pool_plan(ctx->opt.shared_device, ctx->opt.hw_queues > 0 ? ctx->opt.hw_queues : process_hw_queues(), &plan) != PS_OK) {
+            ctx->opt = before;
             return fail(ctx, PS_ERR_ARG, "shared_device: no plan for %lld contexts", static_cast<long long>(value));
-        ctx->shared_n = static_cast<int>(value);
+        }
         ctx->la_keep = 0;
-        ctx->k0_waves = plan.k0_waves;
-        ctx->lat_help = plan.lat_help;
-        ctx->k0_admit = plan.k0_admit;
+        ctx->opt.k0_waves = plan.k0_waves;
+        ctx->opt.lat_help = plan.lat_help;
+        ctx->opt.k0_admit = plan.k0_admit;
+        break;
     }
-    // hw_queues: the hardware queues the next shared_device plans for (0: the process's own, GPU_MAX_HW_QUEUES) -- tests, tools
-    else if (n == "hw_queues" && value >= 0 && value <= HW_QUEUES_MAX) ctx->hw_queues = static_cast<int>(value);
-    else if (n == "hmm_bp_budget" && value >= 1) ctx->hmm.bp_budget = value;
-    else if (n == "hmm_fb_budget" && value >= 1) ctx->hmm.fb_budget = value;
-    else if (n == "pairwise_budget" && value >= 1) ctx->pw.budget = value;
-    else if (n == "trf_budget" && value >= 1) ctx->trf.budget = value;
-    else if (n == "hmm_expect_lds") ctx->hmm.expect_lds = value != 0;
-    else if (n == "single_pass") ctx->single_pass = value != 0;
-    else if (n == "gather_fused") ctx->gather_fused = value != 0;
-    else if (n == "download_by_kernel") ctx->download_by_kernel = value != 0;
-    else if (n == "debug") ctx->debug = value != 0;
-    // k0_unaligned 0: K0's fast route from 16-byte-aligned addresses only (what a device whose probe fails gets); 1: whatever the probe said
-    else if (n == "k0_unaligned") ctx->k0_unaligned = value != 0 ? k0_unaligned_probe(ctx->device, ctx->stream) : 0;
-    else if (n == "slots_pct" && value >= 1 && value <= 100) ctx->slots_pct = static_cast<int>(value);
-    else if (n == "tree_jobs_per_wave" && value >= 0 && value <= 1024) ctx->tree_jobs_per_wave = static_cast<int>(value);
-    else if (n == "tree_screen") ctx->tree_screen = value != 0;
-    // short_chain: 1 (default) the launches a call can do without are left out, 0 the launches of the library before the option,
-    // launch for launch; 2 / 3 one part at a time, for measurements: no look-ahead launch in a pooled call / no upload launch on a
-    // repeated layout (include/poreseg.h)
-    else if (n == "short_chain" && value >= 0 && value <= 3) {
-        static const int bits[4] = {0, SC_ALL, SC_NO_LA, SC_NO_UPLOAD};
-        if (ctx->short_chain != bits[value]) ctx->small_clean = false;
-        ctx->short_chain = bits[value];
-    }
-    // bridge_patience: windows without a hit that a bridge of a pooled call walks before it defers its seam (short_chain)
-    else if (n == "bridge_patience" && value >= 1 && value <= 4096) { ctx->pool_patience = static_cast<int>(value); ctx->la_keep = 0; }
-    else if (n == "noise_k_ppm" && value >= 0) ctx->noise_k = static_cast<float>(static_cast<double>(value) * 1.0e-6);
+    case FX_SHORT_CHAIN: if (ctx->opt.short_chain != before.short_chain) ctx->small_clean = false; break;
+    case FX_BRIDGE_PATIENCE: ctx->la_keep = 0; break;
+    case FX_WIDE_BS: ctx->wide.forget(); break;
+    case FX_K0_UNALIGNED: ctx->k0_unaligned = ctx->opt.k0_unaligned ? k0_unaligned_probe(ctx->device, ctx->stream) : 0; break;
+    case FX_CU_MASK:                                    // (diagnostic library) the context's OWN stream on those CUs only
 #ifdef PS_DIAG
-    else if (n == "dbg_phase" && value >= 0 && value <= 2) ctx->dbg_phase = static_cast<int>(value);
-    else if (n == "dbg_k0_nogrp") ctx->dbg_k0_nogrp = value != 0;
-    // cu_mask: value = first | count << 12 | stride << 24 | invert << 32: the context's OWN stream on those CUs only (count 0: all)
-    else if (n == "cu_mask" && ctx->stream.own)
-        return diag_mask_stream(ctx, &ctx->stream.s, static_cast<int>(value & 0xfff), static_cast<int>((value >> 12) & 0xfff),
-                                static_cast<int>((value >> 24) & 0xff), ((value >> 32) & 1) != 0);
-    else if (n == "k0_sets" && value >= 2 && value <= 4) ctx->k0_sets = static_cast<int>(value);
-    else if (n == "scan_lds_pad" && value >= 0 && value <= 65536) ctx->scan_lds_pad = static_cast<int>(value);
-    else if (n == "rep_eval" && value >= 1) ctx->rep_eval = static_cast<int>(value);
-    else if (n == "rep_stage" && value >= 1) ctx->rep_stage = static_cast<int>(value);
-    else if (n == "rep_sum" && value >= 1) ctx->rep_sum = static_cast<int>(value);
+        if (ctx->stream.own)
+            return diag_mask_stream(ctx, &ctx->stream.s, static_cast<int>(value & 0xfff), static_cast<int>((value >> 12) & 0xfff),
+                                    static_cast<int>((value >> 24) & 0xff), ((value >> 32) & 1) != 0);
 #endif
-    else if (n == "bridge_budget" && value >= 1 && value <= BR_MAX) ctx->bridge_budget = static_cast<int>(value);
-    else if (n == "wide_bs") { ctx->wide_bs = value != 0; ctx->wide.forget(); }
-    else if (n == "bridge_single" && value >= 1) ctx->bridge_single = static_cast<int>(value);
-    else if (n == "tree_tail_pct" && value >= 0 && value <= 100) ctx->tree_tail_pct = static_cast<int>(value);
-    else if (n == "filter_fused") ctx->filt.fused = value != 0;
-    else if (n == "filt_batch_scratch" && value >= 1) ctx->filt.batch_scratch = value;
-    else if (n == "range_tile" && range_tile_ok(value)) ctx->rng.tile = value;
-    else if (n == "upload_by_kernel") ctx->upload_by_kernel = value != 0;
-    else if (n == "timing") ctx->timing = static_cast<int>(std::max<int64_t>(0, std::min<int64_t>(2, value)));
-    else if (n == "tree_mw") ctx->tree_mw = value != 0;
-    else if (n == "spine_nt" && (value == 256 || value == 512 || value == 1024)) ctx->spine_nt = static_cast<int>(value);
-    else if (n == "tree_nt" && (value == 256 || value == 512)) ctx->tree_nt = static_cast<int>(value);
-    else return fail(ctx, PS_ERR_ARG, "unknown option or value: %s", name);
+        ctx->opt = before;
+        return fail(ctx, PS_ERR_ARG, "unknown option or value: %s", name);
+    case FX_NONE: break;
+    }
     return PS_OK;
 }
 
 int ps_get_option(const ps_ctx *ctx, const char *name, int64_t *value)
 {
     if (!ctx || !name || !value) return PS_ERR_ARG;
-    const std::string n(name);
-    if (n == "k0_waves") *value = ctx->k0_waves;
-    else if (n == "k0_admit") *value = ctx->k0_admit;
-    else if (n == "lat_help") *value = ctx->lat_help;
-    else if (n == "shared_device") *value = ctx->shared_n;
-    else if (n == "hw_queues") *value = ctx->hw_queues;
-    else if (n == "filt_batch_scratch") *value = ctx->filt.batch_scratch;
-    else if (n == "range_tile") *value = ctx->rng.tile;
-    else return PS_ERR_ARG;
+    const OptRow *row = nullptr;
+    if (opt_get(ctx->opt, name, value, &row) != OPT_OK) return PS_ERR_ARG;
+    if (row->effect == FX_K0_UNALIGNED) *value = ctx->k0_unaligned;     // what the probe granted
     return PS_OK;
 }
 
@@ -2153,7 +2001,7 @@ static int begin_segment_call(ps_ctx *ctx, const void *d_samples, const ps_sampl
 static void nt_reset(ps_ctx *ctx)
 {
     ctx->nt.seen = -1;
-    ctx->nt.call_cap = ctx->nt.cap;
+    ctx->nt.call_cap = ctx->opt.near_tie_log;
     ctx->nt.ev_start.clear();
     ctx->nt.ev_len.clear();
 }
@@ -2202,9 +2050,9 @@ static int segment_events_body(ps_ctx *ctx, const void *d_samples, const ps_samp
     if (!d_f64) { rc = nt_arm(ctx, cfg); if (rc) return rc; }
     reset_call_stats(ctx);
     ctx->stream_idle = true;
-    if (ctx->k0_shared && hipStreamQuery(ctx->stream) != hipSuccess) { ctx->stream_idle = false; (void)hipGetLastError(); }
-    if (ctx->timing >= 1) HIP_TRY(ctx, hipEventRecord(ctx->ev[8], ctx->stream));
-    if (ctx->stitch_host) HIP_TRY(ctx, hipMemsetAsync(ctx->small.p, 0, sizeof(SmallLayout), ctx->stream));   // (the device-stitch path clears it with its upload)
+    if (ctx->opt.k0_shared && hipStreamQuery(ctx->stream) != hipSuccess) { ctx->stream_idle = false; (void)hipGetLastError(); }
+    if (ctx->opt.timing >= 1) HIP_TRY(ctx, hipEventRecord(ctx->ev[8], ctx->stream));
+    if (ctx->opt.stitch_host) HIP_TRY(ctx, hipMemsetAsync(ctx->small.p, 0, sizeof(SmallLayout), ctx->stream));   // (the device-stitch path clears it with its upload)
     if (d_f64) {
         // exact route: c = cumsum(x), c2 = cumsum(x * x) per event, laid out like the samples (event e at ev_start[e])
         int64_t sample_end = 0;
@@ -2226,26 +2074,26 @@ static int segment_events_body(ps_ctx *ctx, const void *d_samples, const ps_samp
     }
 
     const SegBatch B = {ev_start, ev_len, n_ev, mw, W, d_bounds, cap, h_bounds_off, d_stats, t_begin};
-    if (!ctx->stitch_host) {
+    if (!ctx->opt.stitch_host) {
         // The route (seg_plan.hpp): the block-sum scan where the call fits it, else the LDS-window kernels.  Counts too wide for
         // the 32-bit digest (K0 says so: RC_WIDE): the call is redone on the 64-bit digest, and if that refuses too on the
-        // LDS-window kernels; the calls after it on the same grid start where it ended (counters[7]: 1 = 64-bit digest, 2 =
+        // LDS-window kernels; the calls after it on the same grid start where it ended (PS_CNT_WIDE_REDO: 1 = 64-bit digest, 2 =
         // LDS-window scan).
         WideRedo &wide = ctx->wide;
-        const bool use_bs = scan_route_bs(ctx->scan_bs != 0, mw, W, ctx->mode == MODE_EXACT, d_f64);
+        const bool use_bs = scan_route_bs(ctx->opt.scan_bs != 0, mw, W, ctx->opt.mode == MODE_EXACT, d_f64);
         rc = device_stitch_batch(ctx, cfg, wide.begin(use_bs, fmt->quantum), B);
         while (rc == RC_WIDE) {
-            const int bs_mode = wide.refused(ctx->wide_bs != 0, fmt->quantum);
+            const int bs_mode = wide.refused(ctx->opt.wide_bs != 0, fmt->quantum);
             reset_call_stats(ctx);
             HIP_TRY(ctx, hipMemsetAsync(ctx->small.p, 0, sizeof(SmallLayout), ctx->stream));
             ctx->stream_idle = false;                  // (the front stream, if used, waits for this memset)
             rc = device_stitch_batch(ctx, cfg, bs_mode, B);
         }
-        if (wide.redo) ctx->counters[7] = wide.redo;
+        if (wide.redo) ctx->counters[PS_CNT_WIDE_REDO] = wide.redo;
         if (rc != RC_FALLBACK) return rc;
         // a seam could not be bridged on the device: redo with the host stitch (halo tiles + repairs)
         reset_call_stats(ctx);
-        ctx->counters[4] = 1000000;
+        ctx->counters[PS_CNT_REPAIRS] = 1000000;
         HIP_TRY(ctx, hipMemsetAsync(ctx->small.p, 0, sizeof(SmallLayout), ctx->stream));
     }
     return host_stitch_batch(ctx, cfg, B);
@@ -2548,18 +2396,18 @@ int ps_detect_segment_trace(ps_ctx *ctx, const void *d_samples, const ps_sample_
         return ps_segment_events(ctx, d_samples, fmt, h_starts, h_lengths, static_cast<int32_t>(*n_events_out), params, d_bounds, cap,
                                  h_bounds_off, d_stats, nullptr);
     };
-    const bool use_bs = scan_route_bs(ctx->scan_bs != 0, mw, W, ctx->mode == MODE_EXACT, false) && !ctx->stitch_host && ctx->single_pass &&
+    const bool use_bs = scan_route_bs(ctx->opt.scan_bs != 0, mw, W, ctx->opt.mode == MODE_EXACT, false) && !ctx->opt.stitch_host && ctx->opt.single_pass &&
                         !ctx->wide.remembers(fmt->quantum);
     if (!use_bs) return two_calls();
     rc = nt_arm(ctx, cfg);
     if (rc) return rc;
     reset_call_stats(ctx);
     ctx->d_is_spine = nullptr;
-    if (ctx->timing >= 1) HIP_TRY(ctx, hipEventRecord(ctx->ev[8], ctx->stream));
+    if (ctx->opt.timing >= 1) HIP_TRY(ctx, hipEventRecord(ctx->ev[8], ctx->stream));
     // ---- K0 over the whole trace: one event [0, n), blocks aligned to the trace, per-block extremes on -------------------------
     const int64_t nb_total = (n + 7) / 8, nb_pad = k0_padded_blocks(nb_total);
     DigestWant want;
-    want.grp = ctx->groups != 0;
+    want.grp = ctx->opt.groups != 0;
     want.blk_mm = d_stats != nullptr;
     want.cls = true;
     rc = reserve_digest(ctx, nb_pad, 1, want);
@@ -2581,7 +2429,7 @@ int ps_detect_segment_trace(ps_ctx *ctx, const void *d_samples, const ps_sample_
                        static_cast<int>(sizeof(SmallLayout) / sizeof(unsigned long long)), ctx->det_cand.as<long long>(),
                        static_cast<long long>(n), static_cast<long long>(nb_total));
     HIP_TRY(ctx, hipGetLastError());
-    cfg.grp = ctx->groups ? ctx->grp.p : nullptr;
+    cfg.grp = ctx->opt.groups ? ctx->grp.p : nullptr;
     cfg.blk_mm = d_stats ? ctx->blk_mm.as<int>() : nullptr;
     cfg.blk_cls = ctx->blk_cls.as<unsigned char>();
     cfg.cls_mm = ctx->cls_mm.as<int2>();
@@ -2601,7 +2449,7 @@ int ps_detect_segment_trace(ps_ctx *ctx, const void *d_samples, const ps_sample_
     unsigned st = 0;
     rc = detect_edges(ctx, cfg, n, threshold, true, tics, &st);
     if (rc) return rc;
-    if (st & ST_WIDE_RANGE) { ctx->counters[7] = 3; const int r2 = two_calls(); ctx->counters[7] = 3; return r2; }    // counts too wide about the trace's first sample
+    if (st & ST_WIDE_RANGE) { ctx->counters[PS_CNT_WIDE_REDO] = 3; const int r2 = two_calls(); ctx->counters[PS_CNT_WIDE_REDO] = 3; return r2; }    // counts too wide about the trace's first sample
     rc = events_from_edges(ctx, cfg, n, tics, threshold, min_duration, min_current, h_starts, h_lengths, ev_cap, n_events_out);
     if (rc) return rc;
     const int32_t n_ev = static_cast<int32_t>(*n_events_out);
@@ -2667,13 +2515,13 @@ int ps_get_near_ties(const ps_ctx *ctx, ps_near_tie *out, int32_t cap, int64_t *
 int ps_get_timings(const ps_ctx *ctx, double *ms, int32_t n_ms, int64_t *counters, int32_t n_counters)
 {
     if (!ctx) return PS_ERR_ARG;
-    for (int i = 0; i < n_ms && ms; ++i) ms[i] = i < 8 ? ctx->ms[i] : 0.0;
-    for (int i = 0; i < n_counters && counters; ++i) counters[i] = i < 20 ? ctx->counters[i] : 0;
+    for (int i = 0; i < n_ms && ms; ++i) ms[i] = i < PS_MS_COUNT ? ctx->ms[i] : 0.0;
+    for (int i = 0; i < n_counters && counters; ++i) counters[i] = i < PS_CNT_COUNT ? ctx->counters[i] : 0;
     return PS_OK;
 }
 
 // The context's twenty work counters where ps_get_timings copies them from: a host that looks at one of them after every
-// call (the near-tie count, counters[11]) reads it in place instead of making a second call.
+// call (the near-tie count, PS_CNT_NEAR_TIES) reads it in place instead of making a second call.
 const int64_t *ps_counters(const ps_ctx *ctx) { return ctx ? ctx->counters : nullptr; }
 
 int ps_synth_trace(ps_ctx *ctx, void *d_out, int32_t dtype, int64_t n, uint64_t seed,
@@ -2885,7 +2733,7 @@ int ps_filter_bessel(ps_ctx *ctx, const void *d_samples, const ps_sample_format 
     // Fast filters (the state forgets within a halo of <= 1024 samples): both directions in one kernel over tiles
     // with halos.  alpha^H <= 2^-60.  The route is filt_plan.hpp's: the batch entry takes the same one.
     {
-        const int H = filt_route1(f.alpha, ctx->filt.fused);
+        const int H = filt_route1(f.alpha, ctx->opt.filter_fused);
         if (H) {
             g.lead = 0; g.padded = g.total;
             const int T = filt_tile(H);
@@ -3063,7 +2911,7 @@ int filter_batch_queue(ps_ctx *ctx, const void *d_samples, const ps_sample_forma
     int64_t unit = FILT_CHUNK, row_bytes = 0;            // (the scan route is planned for its refusals only)
     if (order == 1) {
         f1 = filter_coef1(wn);
-        H = filt_route1(f1.alpha, ctx->filt.fused);
+        H = filt_route1(f1.alpha, ctx->opt.filter_fused);
         if (H) unit = filt_tile(H);
     } else {
         if (int rc = filter_design_n(ctx, order, wn, &dn)) return rc;
@@ -3072,7 +2920,7 @@ int filter_batch_queue(ps_ctx *ctx, const void *d_samples, const ps_sample_forma
     }
     const bool per_event = order == 1 && !H;
     FiltPlan plan;
-    switch (plan_filter_batch(ev_start, ev_len, n_ev, pad, unit, row_bytes, ctx->filt.batch_scratch, &plan)) {
+    switch (plan_filter_batch(ev_start, ev_len, n_ev, pad, unit, row_bytes, ctx->opt.filt_batch_scratch, &plan)) {
     case FILT_PLAN_OK: break;
     case FILT_PLAN_RANGE: return fail(ctx, PS_ERR_ARG, "event %d: empty or negative range", plan.bad_event);
     case FILT_PLAN_SHORT:
@@ -3164,13 +3012,13 @@ int ps_range_stats(ps_ctx *ctx, const void *d_samples, const ps_sample_format *f
     // validated and planned (range_plan.hpp) before anything is reserved or queued
     RangePlan plan;
     int64_t bad = -1;
-    switch (plan_ranges(h_start, h_end, n_ranges, n, range_unit(fmt->dtype == PS_DTYPE_F32, ctx->rng.tile), &plan, &bad)) {
+    switch (plan_ranges(h_start, h_end, n_ranges, n, range_unit(fmt->dtype == PS_DTYPE_F32, ctx->opt.range_tile), &plan, &bad)) {
     case RANGE_PLAN_OK: break;
     case RANGE_PLAN_START: return fail(ctx, PS_ERR_ARG, "range %lld: negative start", static_cast<long long>(bad));
     case RANGE_PLAN_END: return fail(ctx, PS_ERR_ARG, "range %lld: ends behind the %lld samples", static_cast<long long>(bad), static_cast<long long>(n));
     case RANGE_PLAN_EMPTY: return fail(ctx, PS_ERR_ARG, "range %lld: empty (end <= start)", static_cast<long long>(bad));
     case RANGE_PLAN_LONG: return fail(ctx, PS_ERR_ARG, "range %lld: longer than 2^31 - 1 samples", static_cast<long long>(bad));
-    default: return fail(ctx, PS_ERR_ARG, "too many ranges or units for one call (option range_tile: %lld)", ctx->rng.tile);
+    default: return fail(ctx, PS_ERR_ARG, "too many ranges or units for one call (option range_tile: %lld)", ctx->opt.range_tile);
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     DevCfg cfg;
@@ -3411,7 +3259,7 @@ int ps_pairwise_batch(ps_ctx *ctx, const double *d_a, const int64_t *h_a_off, in
     // Launches: consecutive pairs while the scratch of their launch -- one matrix of the launch's largest pair per workgroup,
     // a workgroup per pair up to the resident slots -- stays within the budget; a launch whose first pair alone leaves room
     // for few matrices runs on that many workgroups (next_scratch_launch, batch_plan.hpp)
-    const unsigned long long budget = static_cast<unsigned long long>(std::max<long long>(1, ctx->pw.budget));
+    const unsigned long long budget = static_cast<unsigned long long>(std::max<long long>(1, ctx->opt.pairwise_budget));
     auto dims = [&](int32_t q) {
         const int64_t m = h_a_off[h_pair_a[q] + 1] - h_a_off[h_pair_a[q]], n = h_b_off[h_pair_b[q] + 1] - h_b_off[h_pair_b[q]];
         return PwDims{static_cast<unsigned long long>(m) * static_cast<unsigned long long>(n), static_cast<unsigned long long>(m), static_cast<int>(n)};
@@ -3423,7 +3271,7 @@ int ps_pairwise_batch(ps_ctx *ctx, const double *d_a, const int64_t *h_a_off, in
             if (next_scratch_launch(q0, n_pairs, budget, dims, slots, &L)) return fail(ctx, PS_ERR_ARG, "pair %d needs more than 32 GiB of scratch", q0);
             HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(kernel), static_cast<int>(L.lds)));
             HIP_TRY(ctx, ctx->pw.scratch.reserve(static_cast<size_t>(L.grid) * L.per_wg));
-            if (ctx->debug) fprintf(stderr, "[poreseg] pairwise launch: pairs %d..%d, grid %u, %llu bytes of scratch per workgroup, dynamic LDS %zu\n", L.q0, L.q1, L.grid, L.per_wg, L.lds);
+            if (ctx->opt.debug) fprintf(stderr, "[poreseg] pairwise launch: pairs %d..%d, grid %u, %llu bytes of scratch per workgroup, dynamic LDS %zu\n", L.q0, L.q1, L.grid, L.per_wg, L.lds);
             hipLaunchKernelGGL(kernel, dim3(L.grid), dim3(PW_NT), L.lds, ctx->stream, P, L.q0, L.q1 - L.q0, L.dims.n_cap, ctx->pw.scratch.as<unsigned char>(),
                                L.per_wg, L.dims.cells, L.dims.rows);
             HIP_TRY(ctx, hipGetLastError());
@@ -3470,7 +3318,7 @@ int ps_trf_split_batch(ps_ctx *ctx, const double *d_mean, const double *d_std, c
     // Launches: consecutive sequences while the scratch of their launch -- the mask and pointer bits of the launch's longest
     // sequence per workgroup, a workgroup per sequence up to the resident slots -- stays within the budget; a launch whose
     // first sequence alone leaves room for few workgroups runs on that many (next_scratch_launch, batch_plan.hpp)
-    const unsigned long long budget = static_cast<unsigned long long>(std::max<long long>(1, ctx->trf.budget));
+    const unsigned long long budget = static_cast<unsigned long long>(std::max<long long>(1, ctx->opt.trf_budget));
     static_assert(trf_lds_bytes(TRF_N_MAX) <= 64u << 10, "beyond 64 KiB the launch needs hipFuncAttributeMaxDynamicSharedMemorySize (set_dyn_lds)");
     auto dims = [&](int32_t q) { return TrfDims{static_cast<int>(h_off[q + 1] - h_off[q])}; };
     auto slots = [&](size_t lds) { return resident_slots(ctx, trf_kernel, TRF_NT, lds); };
@@ -3478,7 +3326,7 @@ int ps_trf_split_batch(ps_ctx *ctx, const double *d_mean, const double *d_std, c
     for (int32_t q0 = 0; q0 < n_seq; q0 = L.q1) {
         next_scratch_launch(q0, n_seq, budget, dims, slots, &L);        // (never refused: 1.6 MB of scratch at TRF_N_MAX)
         HIP_TRY(ctx, ctx->trf.scratch.reserve(static_cast<size_t>(L.grid) * L.per_wg));
-        if (ctx->debug) fprintf(stderr, "[poreseg] trf launch: sequences %d..%d, grid %u, %llu bytes of scratch per workgroup, dynamic LDS %zu\n", L.q0, L.q1, L.grid, L.per_wg, L.lds);
+        if (ctx->opt.debug) fprintf(stderr, "[poreseg] trf launch: sequences %d..%d, grid %u, %llu bytes of scratch per workgroup, dynamic LDS %zu\n", L.q0, L.q1, L.grid, L.per_wg, L.lds);
         hipLaunchKernelGGL(trf_kernel, dim3(L.grid), dim3(TRF_NT), L.lds, ctx->stream, P, L.q0, L.q1 - L.q0, L.dims.n_cap, ctx->trf.scratch.as<unsigned char>(), L.per_wg);
         HIP_TRY(ctx, hipGetLastError());
     }
@@ -3573,7 +3421,7 @@ int hmm_viterbi(ps_ctx *ctx, const MD &D, const double *d_obs, const int64_t *h_
 {
     const size_t S = static_cast<size_t>(D.S), lds = hmm_lds_bytes(D.S);
     const long long *d_path_off = d_off + n_seq + 1;
-    const long long budget = std::max<long long>(1, ctx->hmm.bp_budget);
+    const long long budget = std::max<long long>(1, ctx->opt.hmm_bp_budget);
     HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_fwd_kernel<HMM_VITERBI, BP, MD>), static_cast<int>(lds)));
     HIP_TRY(ctx, ctx->hmm.last.reserve(static_cast<size_t>(n_seq) * sizeof(int)));
     HIP_TRY(ctx, ctx->hmm.flags.reserve(sizeof(int)));
@@ -3614,7 +3462,7 @@ int hmm_expect_run(ps_ctx *ctx, const MD &D, const double *d_obs, const int64_t 
     HIP_TRY(ctx, ctx->hmm.acc.reserve(G * row_bytes));
     HIP_TRY(ctx, ctx->hmm.skip.reserve(sizeof(double)));
     HIP_TRY(ctx, hipMemsetAsync(ctx->hmm.acc.p, 0, G * row_bytes, ctx->stream));
-    const long long budget = std::max<long long>(1, ctx->hmm.fb_budget);
+    const long long budget = std::max<long long>(1, ctx->opt.hmm_fb_budget);
     for (int32_t q0 = 0, q1; q0 < n_seq; q0 = q1) {
         long long bytes;
         q1 = next_chunk(h_off, q0, n_seq, static_cast<size_t>(D.S) * sizeof(double), budget, &bytes);
@@ -3648,14 +3496,14 @@ int hmm_posterior_run(ps_ctx *ctx, const MD &D, const double *d_obs, const int64
     const size_t lds = hmm_lds_bytes(D.S, CNT == 2 ? E : 0);
     HIP_TRY(ctx, set_dyn_lds(ctx, reinterpret_cast<const void *>(hmm_posterior_kernel<CNT, MD>), static_cast<int>(lds)));
     if (d_map_logp) HIP_TRY(ctx, ctx->hmm.pmax.reserve(std::max<size_t>(1, static_cast<size_t>(h_off[n_seq])) * sizeof(double)));
-    const long long budget = std::max<long long>(1, ctx->hmm.fb_budget);
+    const long long budget = std::max<long long>(1, ctx->opt.hmm_fb_budget);
     for (int32_t q0 = 0, q1; q0 < n_seq; q0 = q1) {
         long long bytes;
         q1 = next_chunk(h_off, q0, n_seq, static_cast<size_t>(D.S) * sizeof(double), budget, &bytes);
         if (std::string why; !hmm_launch_check(q0, bytes, false, &why)) return fail(ctx, PS_ERR_ARG, "%s", why.c_str());
         HIP_TRY(ctx, ctx->hmm.fmat.reserve(static_cast<size_t>(bytes)));
         const long long row0 = h_off[q0] + q0;
-        if (ctx->debug) fprintf(stderr, "[poreseg] posterior launch: sequences %d..%d, %lld bytes of forward matrix, dynamic LDS %zu\n", q0, q1, bytes, lds);
+        if (ctx->opt.debug) fprintf(stderr, "[poreseg] posterior launch: sequences %d..%d, %lld bytes of forward matrix, dynamic LDS %zu\n", q0, q1, bytes, lds);
         if (int rc = launch_forward(ctx, D, d_obs, d_off, q0, q1, d_logp, ctx->hmm.fmat.as<double>(), row0)) return rc;
         hipLaunchKernelGGL((hmm_posterior_kernel<CNT, MD>), dim3(q1 - q0), dim3(HMM_NT), lds, ctx->stream, D, d_obs, d_off, q0,
                            static_cast<const double *>(d_logp), static_cast<const double *>(ctx->hmm.fmat.as<double>()), row0, d_post,
@@ -3726,7 +3574,7 @@ int ps_hmm_expect(ps_ctx *ctx, const ps_hmm_model *model, const double *d_obs, c
     if (int rc = hmm_begin(ctx, model, h_skipped != nullptr, d_obs, h_off, nullptr, n_seq, d_logp, &C, own)) return rc;
     if (!C.d_off) return PS_OK;
     const int E = C.I.E;
-    const bool in_lds = hmm_expect_in_lds(C.I, ctx->hmm.expect_lds);
+    const bool in_lds = hmm_expect_in_lds(C.I, ctx->opt.hmm_expect_lds);
     return with_model(C, [&](const auto &M) {
         return in_lds ? hmm_expect_run<true>(ctx, M, d_obs, h_off, C.d_off, n_seq, n_acc, E, d_logp, d_counts, d_stats, h_skipped)
                       : hmm_expect_run<false>(ctx, M, d_obs, h_off, C.d_off, n_seq, n_acc, E, d_logp, d_counts, d_stats, h_skipped);
@@ -3744,7 +3592,7 @@ int ps_hmm_posterior(ps_ctx *ctx, const ps_hmm_model *model, const double *d_obs
     if (int rc = hmm_begin(ctx, model, true, d_obs, h_off, nullptr, n_seq, d_logp, &C, own)) return rc;
     if (!C.d_off) return PS_OK;
     const int E = C.I.E;
-    const int cnt = hmm_posterior_cnt(C.I, d_counts_seq != nullptr, ctx->hmm.expect_lds);
+    const int cnt = hmm_posterior_cnt(C.I, d_counts_seq != nullptr, ctx->opt.hmm_expect_lds);
     return with_model(C, [&](const auto &M) {
         switch (cnt) {
         case 0: return hmm_posterior_run<0>(ctx, M, d_obs, h_off, C.d_off, n_seq, E, d_logp, d_post, d_map_state, d_map_logp, d_counts_seq);

@@ -27,6 +27,8 @@ POOL_OVERRIDES = {}
 
 EVENT_CAP = 1 << 16      # events the detector's host arrays hold at first (Context.detect_events / detect_segment_trace grow them when a trace has more)
 
+# variable -> option, the integer-valued ones: the same list as the table of pypore_amd/csrc/ctx_options.hpp has (kept here as well because
+# the package works without a compiler; tests/test_ctx_options_host.py compares the two).  PORESEG_NOISE_K, a fraction, is read below.
 _ENV_OPTIONS = {
     "PORESEG_MODE": "mode", "PORESEG_SPINE_NT": "spine_nt", "PORESEG_TREE_NT": "tree_nt", "PORESEG_PRUNE": "prune",
     "PORESEG_SCAN_BS": "scan_bs", "PORESEG_GROUPS": "groups", "PORESEG_TREE_PAR": "tree_par", "PORESEG_K0_WAVES": "k0_waves",
@@ -38,7 +40,8 @@ _ENV_OPTIONS = {
     "PORESEG_SHORT_CHAIN": "short_chain", "PORESEG_BRIDGE_PATIENCE": "bridge_patience",
     "PORESEG_GATHER_FUSED": "gather_fused", "PORESEG_SINGLE_PASS": "single_pass", "PORESEG_DOWNLOAD": "download_by_kernel", "PORESEG_K0_UNALIGNED": "k0_unaligned",
     # libporeseg_diag.so only (PORESEG_LIB=.../libporeseg_diag.so): stale or partial results, never the product
-    "PORESEG_DBG_PHASE": "dbg_phase", "PORESEG_DBG_K0_NOGRP": "dbg_k0_nogrp", "PORESEG_SCAN_LDS_PAD": "scan_lds_pad", "PORESEG_REP_STAGE": "rep_stage",
+    "PORESEG_DBG_PHASE": "dbg_phase", "PORESEG_DBG_K0_NOGRP": "dbg_k0_nogrp", "PORESEG_SCAN_LDS_PAD": "scan_lds_pad",
+    "PORESEG_REP_EVAL": "rep_eval", "PORESEG_REP_STAGE": "rep_stage", "PORESEG_REP_SUM": "rep_sum",
 }
 
 
@@ -223,7 +226,8 @@ class Context(object):
             _call(None, self.L.ps_set_option, self.handle, name.encode(), int(value))
 
     def get_option(self, name):
-        """ps_get_option: "k0_waves", "k0_admit", "lat_help" as they stand, "shared_device" / "hw_queues" / "range_tile" as last set."""
+        """ps_get_option: any option set_option knows, as it stands -- its default, what was last set (a switch as 0 / 1), what
+        "shared_device" planned for "k0_waves", "k0_admit" and "lat_help"; "k0_unaligned" is what the device's probe granted."""
         out = ctypes.c_int64()
         with self.lock:
             _call(None, self.L.ps_get_option, self.handle, name.encode(), ctypes.byref(out))
@@ -235,20 +239,16 @@ class Context(object):
         if not hasattr(self, "_tm"):
             self._tm = ((ctypes.c_double * 8)(), (ctypes.c_int64 * 8)())
         self.L.ps_get_timings(self.handle, self._tm[0], 8, self._tm[1], 8)
-        return self._tm[0][7]
+        return self._tm[0][_lib.MS_NAMES.index("seq")]
 
     def timings(self):
-        ms = (ctypes.c_double * 8)()
-        cnt = (ctypes.c_int64 * 20)()
-        _call(None, self.L.ps_get_timings, self.handle, ms, 8, cnt, 20)
-        return dict(spine_ms=ms[0], tree_ms=ms[1], gather_ms=ms[2], total_ms=ms[3], stitch_ms=ms[4], bridge_ms=ms[5], blocksum_ms=ms[6], seq_ms=ms[7],
-                    windows=cnt[0], candidates=cnt[1], tiles=cnt[2], tree_jobs=cnt[3], repairs=cnt[4],
-                    exact_rescans=cnt[5], full_exact_scans=cnt[6], wide_redo=cnt[7],
-                    windows_spine=cnt[8], windows_bridge=cnt[9], windows_tree=cnt[10], near_ties=cnt[11],
-                    helper_chunks_published=cnt[12], helper_chunks_taken=cnt[13],
-                    tree_deferred=cnt[14], windows_screen=cnt[15],
-                    # option "short_chain": launches the call did without, seams its bridges left to the second chance
-                    lookahead_skipped=cnt[16], upload_skipped=cnt[17], seams_resumed=cnt[18])
+        """ps_get_timings as a dict: "<name>_ms" for _lib.MS_NAMES, the counters by their _lib.COUNTER_NAMES."""
+        ms = (ctypes.c_double * len(_lib.MS_NAMES))()
+        cnt = (ctypes.c_int64 * len(_lib.COUNTER_NAMES))()
+        _call(None, self.L.ps_get_timings, self.handle, ms, len(ms), cnt, len(cnt))
+        out = {name + "_ms": ms[i] for i, name in enumerate(_lib.MS_NAMES)}
+        out.update({name: cnt[i] for i, name in enumerate(_lib.COUNTER_NAMES) if name})
+        return out
 
     def near_ties(self):
         """Windows of the most recent segment call that were decided among fp64 contenders with a margin inside the
@@ -257,7 +257,7 @@ class Context(object):
         kernels, which do not count them (callers that redo near ties on the exact route treat it as "some")."""
         if not hasattr(self, "_cnt"):
             self._cnt = self.L.ps_counters(self.handle)      # the context's counters in place: no call per look
-        return int(self._cnt[11])
+        return int(self._cnt[_lib.COUNTER_NAMES.index("near_ties")])
 
     def near_tie_sites(self):
         """Where the near ties of the most recent segment call lie (ps_get_near_ties): a numpy structured array of

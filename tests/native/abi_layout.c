@@ -1,6 +1,7 @@
 /* The layout of the nine public structs of include/poreseg.h as the C compiler sees it: one line "struct sizeof N" per struct
    and one line "struct.field N" per field, in declaration order.  tests/test_binding_host.py compares the lines with the
-   ctypes structures of pypore_amd/_lib.py.  Plain C, needs only -Iinclude. */
+   ctypes structures of pypore_amd/_lib.py.  Behind them the indices of what ps_get_timings returns, one line "NAME enum N" each,
+   in the header's order, which the test compares with the two tuples of names of _lib.py.  Plain C, needs only -Iinclude. */
 #include <stddef.h>
 #include <stdio.h>
 
@@ -8,6 +9,7 @@
 
 #define SIZE(T) printf(#T " sizeof %zu\n", sizeof(T))
 #define FIELD(T, f) printf(#T "." #f " %zu\n", offsetof(T, f))
+#define ENUM(e) printf(#e " enum %d\n", (int)(e))
 
 int main(void) {
     SIZE(ps_split_params);
@@ -49,5 +51,12 @@ int main(void) {
     FIELD(ps_filter_derivative_params, low_threshold); FIELD(ps_filter_derivative_params, high_threshold);
     FIELD(ps_filter_derivative_params, cutoff_freq); FIELD(ps_filter_derivative_params, sampling_freq);
     FIELD(ps_filter_derivative_params, prefiltered);
+
+    ENUM(PS_MS_SPINE); ENUM(PS_MS_TREE); ENUM(PS_MS_GATHER); ENUM(PS_MS_TOTAL); ENUM(PS_MS_STITCH); ENUM(PS_MS_BRIDGE); ENUM(PS_MS_BLOCKSUM);
+    ENUM(PS_MS_SEQ); ENUM(PS_MS_COUNT);
+    ENUM(PS_CNT_WINDOWS); ENUM(PS_CNT_CANDIDATES); ENUM(PS_CNT_TILES); ENUM(PS_CNT_TREE_JOBS); ENUM(PS_CNT_REPAIRS); ENUM(PS_CNT_EXACT_RESCANS);
+    ENUM(PS_CNT_FULL_EXACT_SCANS); ENUM(PS_CNT_WIDE_REDO); ENUM(PS_CNT_WINDOWS_SPINE); ENUM(PS_CNT_WINDOWS_BRIDGE); ENUM(PS_CNT_WINDOWS_TREE);
+    ENUM(PS_CNT_NEAR_TIES); ENUM(PS_CNT_HELPER_CHUNKS_PUBLISHED); ENUM(PS_CNT_HELPER_CHUNKS_TAKEN); ENUM(PS_CNT_TREE_DEFERRED);
+    ENUM(PS_CNT_WINDOWS_SCREEN); ENUM(PS_CNT_LOOKAHEAD_SKIPPED); ENUM(PS_CNT_UPLOAD_SKIPPED); ENUM(PS_CNT_SEAMS_RESUMED); ENUM(PS_CNT_COUNT);
     return 0;
 }

@@ -23,19 +23,39 @@ STRUCTS = {"ps_split_params": (_lib.SplitParams, 56), "ps_sample_format": (_lib.
            "ps_filter_derivative_params": (_lib.FilterDerivativeParams, 40)}
 
 
-def test_struct_layouts_match_the_compilers(tmp_path):
+@pytest.fixture(scope="module")
+def abi_lines(tmp_path_factory):
+    """What tests/native/abi_layout.c prints, split into words: the struct lines, then the enum lines."""
+    tmp_path = tmp_path_factory.mktemp("abi")
     cc = next((p for p in map(shutil.which, ("cc", "gcc", "clang", "/opt/rocm/lib/llvm/bin/clang", "/opt/rocm/llvm/bin/clang")) if p), None)
     assert cc, "no C compiler found for tests/native/abi_layout.c"
     exe = str(tmp_path / "abi_layout")
     subprocess.check_call([cc, "-std=c11", "-O1", "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "include"),
                            os.path.join(ROOT, "tests", "native", "abi_layout.c"), "-o", exe])
-    printed = [line.split() for line in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.splitlines()]
+    return [line.split() for line in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.splitlines()]
+
+
+def test_struct_layouts_match_the_compilers(abi_lines):
+    printed = [words for words in abi_lines if words[1] != "enum"]
     expected = []
     for name, (struct, size) in STRUCTS.items():
         assert ctypes.sizeof(struct) == size, name
         expected.append([name, "sizeof", str(size)])
         expected += [["%s.%s" % (name, f[0]), str(getattr(struct, f[0]).offset)] for f in struct._fields_]
     assert printed == expected
+
+
+def test_timing_indices_match_the_headers(abi_lines):
+    """PS_MS_* and PS_CNT_* of include/poreseg.h are _lib.MS_NAMES and _lib.COUNTER_NAMES: same names, same order, same counts."""
+    printed = [(words[0], int(words[2])) for words in abi_lines if words[1] == "enum"]
+    expected = [("PS_MS_" + name.upper(), i) for i, name in enumerate(_lib.MS_NAMES)] + [("PS_MS_COUNT", len(_lib.MS_NAMES))] + \
+               [("PS_CNT_" + name.upper(), i) for i, name in enumerate(_lib.COUNTER_NAMES) if name] + [("PS_CNT_COUNT", len(_lib.COUNTER_NAMES))]
+    assert printed == expected
+    assert (len(_lib.MS_NAMES), len(_lib.COUNTER_NAMES)) == (8, 20) and _lib.COUNTER_NAMES.index(None) == 19      # the last one is reserved
+    keys = ["spine_ms", "tree_ms", "gather_ms", "total_ms", "stitch_ms", "bridge_ms", "blocksum_ms", "seq_ms", "windows", "candidates", "tiles",
+            "tree_jobs", "repairs", "exact_rescans", "full_exact_scans", "wide_redo", "windows_spine", "windows_bridge", "windows_tree", "near_ties",
+            "helper_chunks_published", "helper_chunks_taken", "tree_deferred", "windows_screen", "lookahead_skipped", "upload_skipped", "seams_resumed"]
+    assert [n + "_ms" for n in _lib.MS_NAMES] + [n for n in _lib.COUNTER_NAMES if n] == keys           # the keys of Context.timings() as they were
 
 
 # ---- the scalar-capacity rule ----------------------------------------------------------------------------------------------
