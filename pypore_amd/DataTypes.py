@@ -585,7 +585,7 @@ class File(Segment):
         if parser is None:
             parser = lambda_event_parser(threshold=90)
         rate = self.second
-        device_route = isinstance(parser, lambda_event_parser) and parser._builtin
+        device_route = isinstance(parser, lambda_event_parser) and parser._device_route
         self.events = [Event(current=raw_current(seg), start=seg.start / rate, end=(seg.start + seg.duration) / rate,
                              duration=seg.duration / rate, second=rate, file=self)
                        for seg in parser.parse(raw_current(self) if device_route else self.current)]
@@ -765,7 +765,7 @@ class Experiment(object):
             segmenter = SpeedyStatSplit(prior_segments_per_second=10, cutoff_freq=2000.)
         entries = list(self.filenames)
         if workers is None:
-            ours = isinstance(event_detector, lambda_event_parser) and getattr(event_detector, "_builtin", False) and \
+            ours = isinstance(event_detector, lambda_event_parser) and getattr(event_detector, "_device_route", False) and \
                 (segmenter is None or isinstance(segmenter, SpeedyStatSplit))
             workers = 2 if ours else 1
         workers = max(1, min(int(workers), len(entries)))

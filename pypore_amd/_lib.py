@@ -143,12 +143,17 @@ _ABI = {
     "ps_filter_derivative_f64": (cint, [vp, vp, P(i64), P(i64), i32, P(FilterDerivativeParams), vp, i64, P(i64)]),
 }
 EXPORTS = list(_ABI)
+# include/poreseg_pieces.h, the extension header beside poreseg.h (same library; declared by the same loop in lib())
+_ABI_PIECES = {
+    "ps_detect_pieces": (cint, [vp, vp, P(SampleFormat), i64, dbl, vp, vp, i64, P(i64)]),
+}
+PIECES_EXPORTS = list(_ABI_PIECES)
 
 _lib = None
 
 
 def lib():
-    """Loads libporeseg.so and declares every function of _ABI; raises RuntimeError (never falls back) when it is absent."""
+    """Loads libporeseg.so and declares every function of _ABI and _ABI_PIECES; raises RuntimeError (never falls back) when it is absent."""
     global _lib
     if _lib is not None:
         return _lib
@@ -160,7 +165,7 @@ def lib():
     # process has exactly one HIP runtime, shared by torch's allocator and our kernels.
     import torch  # noqa: F401
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in _ABI.items():
+    for name, (restype, argtypes) in list(_ABI.items()) + list(_ABI_PIECES.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

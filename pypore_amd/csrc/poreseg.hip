@@ -42,6 +42,7 @@
 #include <vector>
 
 #include "poreseg.h"
+#include "poreseg_pieces.h"
 #include "seg_device.hpp"
 #include "seg_align.hpp"
 #include "seg_pairwise.hpp"
@@ -51,6 +52,7 @@
 #include "seg_statsplit.hpp"
 #include "seg_state.hpp"
 #include "seg_ranges.hpp"
+#include "seg_pieces.hpp"
 #include "pool_plan.hpp"
 #include "seg_plan.hpp"
 #include "filt_plan.hpp"
@@ -170,6 +172,7 @@ struct ps_ctx {
         DevBuf tab, rq_par;   // a batch's event and unit tables (filt_plan.hpp; the re-quantisation's behind them), (centre, 1 / step, step) per event
     } filt;
     struct { DevBuf tab, part; } rng;        // statistics of caller-given ranges (ps_range_stats): the range and unit tables (range_plan.hpp), a RangePart per unit
+    struct { DevBuf scratch; } pc;           // every piece of a trace (ps_detect_pieces): start bits, per-chunk tables and parts (piece_plan.hpp)
     struct { DevBuf in, scratch; } align;    // profile aligner (ps_align_batch)
     struct { DevBuf in, scratch; } pw;       // pairwise aligner (ps_pairwise_scores / ps_pairwise_batch): offsets and pair tables, per-workgroup matrices
     struct { DevBuf in, scratch; } trf;      // NaiveTRF's splitter (ps_trf_split_batch): offsets and the capacity flag, per-workgroup mask and pointer bits
@@ -2358,6 +2361,66 @@ int ps_detect_events(ps_ctx *ctx, const void *d_samples, const ps_sample_format 
     rc = detect_edges(ctx, cfg, n, threshold, false, tics, nullptr);
     if (rc) return rc;
     return events_from_edges(ctx, cfg, n, tics, threshold, min_duration, min_current, h_starts, h_lengths, cap, n_events_out);
+}
+
+// Every piece the threshold cuts the trace into (seg_pieces.hpp; planned by piece_plan.hpp): four launches, one status word, ONE
+// host synchronisation -- the kernels write only the rows the caller's tables have room for, the count comes back with the status.
+int ps_detect_pieces(ps_ctx *ctx, const void *d_samples, const ps_sample_format *fmt, int64_t n, double threshold,
+                     int64_t *d_edges, ps_segstat *d_stats, int64_t cap, int64_t *n_pieces_out)
+{
+    if (!ctx) return PS_ERR_ARG;
+    if (!n_pieces_out) return fail(ctx, PS_ERR_ARG, "bad argument");
+    *n_pieces_out = 0;
+    PiecePlan plan;
+    if (plan_pieces(n, cap, fmt && fmt->dtype == PS_DTYPE_F32, &plan) != PIECE_PLAN_OK || !d_edges || (cap > 0 && !d_stats))
+        return fail(ctx, PS_ERR_ARG, "bad argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (n == 0) {                                       // no piece: edges[0] = n
+        HIP_TRY(ctx, hipMemsetAsync(d_edges, 0, sizeof(int64_t), ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return PS_OK;
+    }
+    if (!d_samples) return fail(ctx, PS_ERR_ARG, "d_samples is NULL");
+    DevCfg cfg;
+    if (int rc = make_cfg(ctx, d_samples, fmt, 1, 1, 2, 0.0, &cfg)) return rc;
+    HIP_TRY(ctx, ctx->pc.scratch.reserve(plan.bytes()));
+    HIP_TRY(ctx, ctx->h_small.reserve(sizeof(SmallLayout)));
+    char *at = ctx->pc.scratch.as<char>();
+    uint16_t *d_bits = reinterpret_cast<uint16_t *>(at); at += plan.b_bits;
+    int *d_cnt = reinterpret_cast<int *>(at); at += plan.b_cnt;
+    int *d_last = reinterpret_cast<int *>(at); at += plan.b_last;
+    int *d_base = reinterpret_cast<int *>(at); at += plan.b_base;
+    int *d_open = reinterpret_cast<int *>(at); at += plan.b_open;
+    PiecePart *d_head = reinterpret_cast<PiecePart *>(at); at += plan.b_head;
+    PiecePart *d_tail = reinterpret_cast<PiecePart *>(at);
+    SmallLayout *sm = ctx->small.as<SmallLayout>();
+    unsigned *st = reinterpret_cast<unsigned *>(&sm->status);
+    HIP_TRY(ctx, hipMemsetAsync(ctx->small.p, 0, sizeof(SmallLayout), ctx->stream));
+    const dim3 grid(static_cast<unsigned>(plan.chunks));
+    by_dtype(cfg.dtype, [&](auto dt) {
+        hipLaunchKernelGGL((piece_mark_kernel<dt()>), grid, dim3(PIECE_NT), 0, ctx->stream, cfg, n, threshold, d_bits, d_cnt, d_last, st);
+        hipLaunchKernelGGL(piece_scan_kernel, dim3(1), dim3(PIECE_SCAN_NT), 0, ctx->stream, static_cast<const int *>(d_cnt),
+                           static_cast<const int *>(d_last), plan.chunks, plan.scan_per_thread, d_base, d_open, n, cap, d_edges, &sm->dense);
+        hipLaunchKernelGGL((piece_stats_kernel<dt()>), grid, dim3(PIECE_NT), 0, ctx->stream, cfg, n, plan.span_max,
+                           static_cast<const uint16_t *>(d_bits), static_cast<const int *>(d_cnt), static_cast<const int *>(d_last),
+                           static_cast<const int *>(d_base), static_cast<const int *>(d_open), d_head, d_tail, d_edges, d_stats, cap, st);
+        hipLaunchKernelGGL((piece_seam_kernel<dt()>), grid, dim3(PIECE_NT), 0, ctx->stream, cfg, static_cast<const int *>(d_cnt),
+                           static_cast<const int *>(d_last), static_cast<const int *>(d_base), static_cast<const PiecePart *>(d_head),
+                           static_cast<const PiecePart *>(d_tail), d_stats, cap);
+        return 0;
+    });
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_small.p, ctx->small.p, sizeof(SmallLayout), hipMemcpyDeviceToHost, ctx->stream));
+    // (the context's stream does not block on torch's: the caller may read the tables, or free d_samples, as soon as this returns)
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const SmallLayout hs = *ctx->h_small.as<SmallLayout>();
+    if (int rc = check_status(ctx, static_cast<unsigned>(hs.status))) return rc;
+    if (static_cast<unsigned>(hs.status) & ST_WIDE_RANGE)
+        return fail(ctx, PS_ERR_ARG, "counts too wide: a float32 sample lies more than %d counts from its piece's first (the sums of squares could overflow)", plan.span_max);
+    const int64_t pieces = static_cast<int64_t>(hs.dense);
+    *n_pieces_out = pieces;
+    if (!piece_capacity_ok(pieces, cap)) return fail(ctx, PS_ERR_CAPACITY, "piece capacity %lld < %lld", static_cast<long long>(cap), static_cast<long long>(pieces));
+    return PS_OK;
 }
 
 // File.parse + Event.parse for a whole file trace with ONE pass over its samples (round 6).  The two calls

@@ -97,6 +97,22 @@ __global__ __launch_bounds__(RANGE_NT) void range_part_kernel(DevCfg c, const Ra
     if (bad) atomicOr(status, bad);
 }
 
+// The final expressions of a range's -- or a piece's (seg_pieces.hpp) -- statistics, written once: t1 = sum of y = count - k0 and
+// t2 = sum of y^2 over the n samples (exact integers, converted to double by the caller), mn / mx the extremes of y.
+// mean = (k0 + t1 / n) q, std = sqrt(max(0, t2 / n - (t1 / n)^2)) q, min / max from the integers; no multiply-add is fused.
+__device__ __forceinline__ ps_segstat segstat_from_sums(int k0, double t1, double t2, int n, int mn, int mx, double q)
+{
+#pragma clang fp contract(off)
+    const double dn = static_cast<double>(n);
+    const double my = t1 / dn;
+    double var = t2 / dn - my * my;
+    if (var < 0) var = 0;
+    ps_segstat s;
+    s.mean = (static_cast<double>(k0) + my) * q; s.std = sqrt(var) * q;
+    s.min = static_cast<double>(k0 + mn) * q; s.max = static_cast<double>(k0 + mx) * q;
+    return s;
+}
+
 template <int DT>
 __global__ __launch_bounds__(RANGE_NT) void range_final_kernel(DevCfg c, const RangeRow *rows, int32_t n_ranges, const RangePart *part,
                                                                ps_segstat *stats)
@@ -124,14 +140,7 @@ __global__ __launch_bounds__(RANGE_NT) void range_final_kernel(DevCfg c, const R
             mn = p[k].mn < mn ? p[k].mn : mn; mx = p[k].mx > mx ? p[k].mx : mx;
         }
     }
-    const double dn = static_cast<double>(row.n);
-    const double my = t1 / dn;
-    double var = t2 / dn - my * my;
-    if (var < 0) var = 0;
-    ps_segstat s;
-    s.mean = (static_cast<double>(k0) + my) * c.q; s.std = sqrt(var) * c.q;
-    s.min = static_cast<double>(k0 + mn) * c.q; s.max = static_cast<double>(k0 + mx) * c.q;
-    stats[r] = s;
+    stats[r] = segstat_from_sums(k0, t1, t2, row.n, mn, mx, c.q);
 }
 
 }  // namespace ps

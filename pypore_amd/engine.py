@@ -25,6 +25,7 @@ DEFAULT_TILING = [0, 0]
 # options a StreamPool applies to its contexts on top of "shared_device" while it runs (experiments: tools/)
 POOL_OVERRIDES = {}
 
+PIECE_CAP = 1 << 16      # pieces Context.detect_pieces has room for at first (2 MB of rows; a trace with more takes a second call)
 EVENT_CAP = 1 << 16      # events the detector's host arrays hold at first (Context.detect_events / detect_segment_trace grow them when a trace has more)
 
 # variable -> option, the integer-valued ones: the same list as the table of pypore_amd/csrc/ctx_options.hpp has (kept here as well because
@@ -352,6 +353,27 @@ class Context(object):
         #  small min_duration; a file has a few hundred: start with EVENT_CAP and take the count the library reports if it is more)
         st, ln = _retry_capacity(self.handle, attempt, min(n // max(1, int(min_duration)) + 2, EVENT_CAP))
         return st[:cnt.value].copy(), ln[:cnt.value].copy()
+
+    @_serialised
+    def detect_pieces(self, samples, quantum, threshold, offset_counts=0):
+        """ps_detect_pieces on a device-resident trace: EVERY piece the threshold cuts it into -- (edges int64 [P + 1], stats
+        float64 [P, 4] in core.STAT_COLUMNS order), numpy arrays; piece p is [edges[p], edges[p + 1]).  The statistics are those
+        of count * quantum, from exact integer sums: range_stats on the same pieces gives the same bits.  Starts with room for
+        PIECE_CAP pieces and takes the count the library reports if a trace has more (one more call)."""
+        dev = _device_input(samples)
+        fmt = _fmt(samples, quantum, offset_counts)
+        n = samples.numel()
+        cnt = ctypes.c_int64()
+
+        def attempt(cap):
+            edges = torch.empty(cap + 1, dtype=torch.int64, device=dev)
+            stats = torch.empty((max(cap, 1), 4), dtype=torch.float64, device=dev)
+            rc = _call_rc(dev, self.L.ps_detect_pieces, self.handle, _addr(samples), ctypes.byref(fmt), n, float(threshold),
+                          _addr(edges), _addr(stats), cap, ctypes.byref(cnt))
+            return rc, cnt.value, (edges, stats)
+
+        edges, stats = _retry_capacity(self.handle, attempt, min(n, PIECE_CAP))
+        return edges[:cnt.value + 1].cpu().numpy(), stats[:cnt.value].cpu().numpy()
 
     @_serialised
     def detect_segment_trace(self, samples, quantum, params, threshold=90.0, min_duration=100000, min_current=-0.5,

@@ -17,7 +17,7 @@ import numpy as np
 from .core import Segment, dump_json, load_json, plain
 from .cparsers import FastStatSplit
 
-__all__ = ["parser", "MemoryParse", "lambda_event_parser", "SpeedyStatSplit", "StatSplit", "snakebase_parser",
+__all__ = ["parser", "MemoryParse", "lambda_event_parser", "PieceTable", "SpeedyStatSplit", "StatSplit", "snakebase_parser",
            "FilterDerivativeSegmenter", "FastStatSplit", "Segment"]
 
 _REGISTRY = {}
@@ -73,26 +73,115 @@ class MemoryParse(object):
         return [Segment(current=np.array(current[i:j], copy=True), start=s, duration=e - s) for i, j, s, e in spans]
 
 
+class PieceTable(object):
+    """Every piece a threshold cuts a trace into, as arrays (lambda_event_parser.pieces): `start`, `end`, `duration`, `n`
+    (int64, in samples) and `min`, `max`, `mean`, `std` (float64, in pA), in the order of the trace.  `edges` are the P + 1
+    cut positions and `stats` the (P, 4) rows in core.STAT_COLUMNS order; `offset` (the pA at count 0 of the upload) is added
+    to mean, min and max -- the device's statistics are those of count * quantum -- and not to std."""
+
+    def __init__(self, edges, stats, offset=0.0):
+        self.edges = np.ascontiguousarray(edges, dtype=np.int64)
+        stats = np.asarray(stats, dtype=np.float64).reshape(-1, 4)
+        if self.edges.ndim != 1 or self.edges.size != stats.shape[0] + 1:
+            raise ValueError("a table of P pieces has P + 1 edges")
+        if offset:
+            stats = stats + np.array([offset, 0.0, offset, offset])
+        self.stats = stats
+        self.start, self.end = self.edges[:-1], self.edges[1:]
+        self.duration = self.n = self.end - self.start
+        self.mean, self.std, self.min, self.max = (stats[:, j] for j in range(4))
+
+    def __len__(self):
+        return self.start.size
+
+    def segments(self, current, mask=None):
+        """The pieces (mask: those it selects) as Segments of `current`: slices of the caller's array, not copies, with the
+        table's rows as their statistics (core.segments_from_edges)."""
+        from .core import segments_from_edges
+        if mask is None:
+            return segments_from_edges(current, self.edges, self.stats)
+        out = []
+        for p in np.flatnonzero(np.asarray(mask, dtype=bool)).tolist():
+            out.extend(segments_from_edges(current, self.edges[p:p + 2], self.stats[p:p + 1]))
+        return out
+
+
+def _host_table(x, threshold):
+    """The PieceTable of a host array by numpy (where no count-space threshold reproduces x < threshold)."""
+    x = np.asarray(x, dtype=np.float64)
+    if not x.size:
+        return PieceTable([0], np.zeros((0, 4)))
+    below = x < threshold
+    edges = np.concatenate(([0], np.flatnonzero(below[1:] != below[:-1]) + 1, [x.size]))
+    n = np.diff(edges)
+    mean = np.add.reduceat(x, edges[:-1]) / n
+    dev = x - np.repeat(mean, n)
+    std = np.sqrt(np.add.reduceat(dev * dev, edges[:-1]) / n)
+    return PieceTable(edges, np.stack([mean, std, np.minimum.reduceat(x, edges[:-1]), np.maximum.reduceat(x, edges[:-1])], axis=1))
+
+
+def _apply_rules(pieces, rules):
+    """The pieces every rule accepts, in their order; each rule is called per piece, as the reference calls it."""
+    from .core import gc_paused
+    with gc_paused():
+        return [piece for piece in pieces if all(rule(piece) for rule in rules)]
+
+
 class lambda_event_parser(parser):
     """Threshold event detector.  The trace is cut wherever it crosses `threshold`; a piece is an event when every
     rule accepts it -- by default: longer than 100 000 samples, minimum above -0.5 pA, maximum below the threshold
-    (the blockade side of the cut).  Start and duration of the returned Segments are in samples."""
+    (the blockade side of the cut).  Start and duration of the returned Segments are in samples.
+
+    on_device=True (an extension; it stays out of the JSON) runs rules of the caller's own on the GPU's piece table: one device
+    call cuts the trace and computes every piece's statistics (ps_detect_pieces), the rules are then called per piece on
+    Segments that carry those rows and slices of the caller's current.  Same pieces, order, start, duration and current as
+    the host route and the same min and max; mean and std come from the device's exact integer sums (numpy's differ in the
+    last bits).  With rules=None the flag changes nothing."""
     MIN_DURATION = 100000
     MIN_CURRENT = -0.5
 
-    def __init__(self, threshold=90, rules=None):
+    def __init__(self, threshold=90, rules=None, on_device=False):
         self.threshold = threshold
         self._builtin = rules is None
+        self._on_device = bool(on_device)
         self.rules = rules or [lambda event: event.duration > self.MIN_DURATION,
                                lambda event: event.min > self.MIN_CURRENT,
                                lambda event: event.max < self.threshold]
 
+    @property
+    def _device_route(self):
+        """parse() takes the samples to the GPU itself: hand it a file's counts, not its float64 current."""
+        return self._builtin or self._on_device
+
     def parse(self, current, quantum=None, device=None, offset=None):
         """Built-in rules: one streaming pass on the GPU (ps_detect_events: crossings, then min / max of the long
-        pieces).  Custom rules are Python callables on Segment objects and run on the host over numpy pieces."""
+        pieces).  Custom rules are Python callables on Segment objects: over numpy pieces on the host, or -- on_device=True --
+        over the device's piece table."""
         if self._builtin:
             return self._parse_device(current, quantum, device, offset)
+        if self._on_device and len(current):
+            table, host = self._pieces(current, quantum, device, offset, fallback=False)
+            if table is not None:
+                return _apply_rules(table.segments(host), self.rules)
+            return self._parse_host(np.asarray(host))
         return self._parse_host(np.asarray(current))
+
+    def pieces(self, current, quantum=None, device=None, offset=None):
+        """Every piece `threshold` cuts `current` into, as a PieceTable computed on the GPU -- whatever the parser's rules
+        are; for callers who would rather filter with numpy than with lambdas."""
+        return self._pieces(current, quantum, device, offset, fallback=True)[0]
+
+    def _pieces(self, current, quantum, device, offset, fallback):
+        """(PieceTable, the host values the Segments are cut from).  Float samples whose counts are not monotone across the
+        threshold (detector_thresholds returns None) have no device table: numpy's with fallback, else None."""
+        from . import engine
+        if not len(current):
+            return PieceTable([0], np.zeros((0, 4))), current
+        s, thr, values, counts, on_device = self._stage(current, quantum, device, offset)
+        if thr is None:
+            return (_host_table(values, self.threshold) if fallback else None), values
+        edges, stats = engine.context(device).detect_pieces(s.tensor, s.quantum, thr[0])
+        return PieceTable(edges, stats, s.offset), self._host_values(current, s, values, counts, on_device)
 
     def _parse_host(self, x):
         below = x < self.threshold
@@ -101,7 +190,9 @@ class lambda_event_parser(parser):
         pieces = (Segment(current=np.array(x[a:b]), start=a, duration=b - a) for a, b in zip(edges[:-1], edges[1:]))
         return [piece for piece in pieces if all(rule(piece) for rule in self.rules)]
 
-    def _parse_device(self, current, quantum, device, offset):
+    def _stage(self, current, quantum, device, offset):
+        """The upload both device routes take: (Samples, the thresholds in count space or None, the caller's values, the
+        counts float samples went up as or None, whether the caller's samples were on the device)."""
         from . import engine
         s, counts = engine.to_device_with_counts(current, quantum, offset, device)
         # the kernel compares count * quantum with its arguments: the rules on the caller's pA values become thresholds in
@@ -114,22 +205,31 @@ class lambda_event_parser(parser):
             values = current.detach().cpu().numpy()
         if counts is None:
             thr = engine.detector_thresholds(s.quantum, self.threshold, self.MIN_CURRENT, offset=s.offset)
-        else:
+        else:                                        # (None: not monotone in the counts at a threshold -- the rules on the host)
             thr = engine.detector_thresholds(s.quantum, self.threshold, self.MIN_CURRENT, values=values, counts=counts)
-            if thr is None:                          # not monotone in the counts at a threshold: the rules on the host
-                return self._parse_host(np.asarray(values))
-        starts, lens = engine.context(device).detect_events(
-            s.tensor, s.quantum, threshold=thr[0], min_duration=self.MIN_DURATION, min_current=thr[1])
+        return s, thr, values, counts, on_device
+
+    @staticmethod
+    def _host_values(current, s, values, counts, on_device):
+        """What the returned Segments are cut from."""
         if on_device and counts is not None:        # (the events hold the caller's values, not count * quantum + offset again)
-            host = values
-        elif on_device:                             # device tensor in: the events' values come back as pA
+            return values
+        if on_device:                               # device tensor in: the events' values come back as pA
             host = s.tensor.cpu().numpy().astype(np.float64)
             if not s.tensor.dtype.is_floating_point:
                 host = host * s.quantum
-            host = host + s.offset
-        else:
-            from .grid import Deferred
-            host = current if isinstance(current, (np.ndarray, Deferred)) else np.asarray(current)
+            return host + s.offset
+        from .grid import Deferred
+        return current if isinstance(current, (np.ndarray, Deferred)) else np.asarray(current)
+
+    def _parse_device(self, current, quantum, device, offset):
+        from . import engine
+        s, thr, values, counts, on_device = self._stage(current, quantum, device, offset)
+        if thr is None:
+            return self._parse_host(np.asarray(values))
+        starts, lens = engine.context(device).detect_events(
+            s.tensor, s.quantum, threshold=thr[0], min_duration=self.MIN_DURATION, min_current=thr[1])
+        host = self._host_values(current, s, values, counts, on_device)
         # (slices, not copies: a GridArray -- or a current that has not been written out -- keeps its counts that way
         #  and Event.parse stays on the int16 route)
         return [Segment(current=host[a:a + n], start=a, duration=n) for a, n in zip(starts.tolist(), lens.tolist())]
